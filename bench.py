@@ -2,8 +2,13 @@
 """bench.py -- headline benchmark of the hot path (BASELINE.json metric:
 "Mpixels/sec end-to-end scale2.0x 7-layer conv, 1/2/4/8 GPU + host-CPU baseline").
 
-  python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: re-executes itself under torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: runs itself as a child under torch.distributed.run)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+  python bench.py ... --full                             (everything below "Extra objects", see there)
+  python bench.py ... --dump-outputs DIR                 (the timed path's output of its last step as DIR/output.npy)
+
+A plain run sets up, warms up, times the K steps and prints one JSON line with the headline alone: `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` and the run's shape.  Every other measurement and check is behind --full.
 
 A "step" is one convertWithModels pass (7 layers: pad-7 by clamped loads, 7 kernel launches, crop/stitch
 in the last kernel's store) over one batch of synthetic input:
@@ -26,7 +31,7 @@ HOST plane out (pad, H2D, layers, D2H, stitch; pageable numpy planes, median of 
 /root/reference/src/main.cpp:96,148 measures around its call -- and its ratio to `value`; PCIe-inclusive, so by the
 contract it is reported beside `value`, never as `value`.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line, with --full only (--no-cpu-baseline / --no-host / --no-extras drop parts of them):
   roofline     dominant kernel = layer 6 (128->128, 51% of the FLOPs): ALGORITHMIC FLOPs of one launch (18*Cin*Cout per
                pixel) / its average duration from hipEvents recorded on the launch stream (w2xc_opts.profile)
                in a second pass of the same K steps right after the timed region (so the events are not inside
@@ -51,6 +56,7 @@ import hashlib
 import json
 import os
 import statistics
+import subprocess
 import sys
 import time
 
@@ -63,6 +69,7 @@ PEAK_FP32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 2
 PEAK_16BIT_MFMA_TFLOPS = 2500.0
 PEAK_HBM_GBS = 8000.0
 PRECISIONS = ["fp32", "bf16", "bf16x2", "bf16x3", "fp16x2"]
+DUMP_BYTES = 64 * 1000 * 1000    # --dump-outputs writes at most this much in all (over every rank)
 
 
 def synth_luma(seed, h, w):
@@ -175,8 +182,10 @@ def cpu_baseline(layers, plane, budget_s=15.0):
 
 
 def self_launch(n, ndev):
-    """`python bench.py --gpus N` WITHOUT a launcher: re-exec this command line under torch.distributed.run, one rank per GPU
-    (--master-addr 127.0.0.1, a free port), so that a plain invocation cannot fail for a launcher reason.  RCCL cannot put two ranks
+    """`python bench.py --gpus N` WITHOUT a launcher: run this command line as a child under torch.distributed.run, one rank per GPU
+    (--master-addr 127.0.0.1, a free port), and exit with its status, so that a plain invocation cannot fail for a launcher reason.  A child
+    and not an exec: this process has already opened the device to count it, and a process that holds the GPU must not replace its
+    program.  RCCL cannot put two ranks
     on one device: on a box with fewer than N devices the ranks share them and the barrier / MAX run over gloo (the record says so in
     `backend` and `rank_devices`; the data path has no collective either way)."""
     import socket
@@ -190,7 +199,20 @@ def self_launch(n, ndev):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execve(sys.executable, cmd, env)
+    sys.exit(subprocess.run(cmd, env=env).returncode)
+
+
+def dump_outputs(directory, name, out, budget):
+    """--dump-outputs: `out` (a device tensor: the output of the timed path's last step) as directory/<name>.npy in float32 -- whole when it
+    fits `budget` bytes, else the rows of a fixed seeded sample (the same rows for the same arguments, so two builds compare row for row)"""
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    rows = out.shape[0]
+    keep = min(rows, max(1, budget // (out[0].numel() * 4)))
+    if keep < rows:
+        pick = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        out = out.index_select(0, torch.from_numpy(pick).to(out.device))
+    np.save(os.path.join(directory, name + ".npy"), out.cpu().numpy().astype(np.float32))
 
 
 def parity_patches(layers, plane_rows_of, d_out, ra, rb, H, W, n_layers):
@@ -216,8 +238,14 @@ def parity_patches(layers, plane_rows_of, d_out, ra, rb, H, W, n_layers):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (`ms_per_step` = their wall time / this)")
+    ap.add_argument("--warmup", type=int, default=2, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the profiled pass (roofline, per-layer and per-rank figures), host->host, parity "
+                         "against the CPU oracle, the CPU baseline, other precisions / kernels / sizes, the matrix-clock probe")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the output of the last one as DIR/output.npy (DIR/output_rank<r>.npy at N > 1), "
+                         "float32, whole if it fits %d MB over all ranks, else a fixed seeded sample of its rows" % (DUMP_BYTES // 10**6))
     ap.add_argument("--height", type=int, default=0, help="input frame height (CNN plane is 2x); default 1080 (plane workload: 8192)")
     ap.add_argument("--width", type=int, default=0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -235,8 +263,9 @@ def main():
     ap.add_argument("--workload", default="auto", choices=["auto", "scale2x_1080p", "plane", "image_u8"],
                     help="auto = scale2x_1080p at N=1, plane (8192x8192, BASELINE.json configs[2]) at N>1.  'plane': ONE --width x --height "
                          "frame whose CNN plane is sharded into row ranges over the ranks: strong scaling")
-    ap.add_argument("--dump-out", default="", help="(tests) directory: every rank saves its output rows of the last step as rank<r>.npz")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import __graft_entry__ as graft
@@ -366,6 +395,44 @@ def main():
         step, step_prof, d_in, d_out = resident_frame(y_src, lambda p: mk_opts(p))
 
     elapsed = time_steps(step, args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "output" if world == 1 else "output_rank%d" % rank, d_out, DUMP_BYTES // world - 4096)
+
+    wl_name = {"scale2x_1080p": "scale2x_1080p (BASELINE.json configs[1])", "plane": "plane, row-sharded over ranks (BASELINE.json configs[2] at 8192x8192)",
+               "image_u8": "image_u8 (N2: u8 RGB in -> u8 2x RGB out, colour + bicubic U/V on the GPU)"}[workload]
+    value = (1 if sharded else world) * in_h * in_w * args.steps / elapsed / 1e6
+    headline = {
+        "metric": "Mpixels/sec end-to-end scale2.0x 7-layer conv",
+        "value": round(value, 4),
+        "unit": "Mpix/s (input-image pixels; CNN-plane pixels = 4x)",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "strong" if sharded else "weak", "vs_baseline": None,
+        "dtype": {"fp32": "f32",
+                  "bf16": "bf16 activations/weights between layers, f32 accumulate (not the headline precision)",
+                  "bf16x2": "f32 values as 2 bf16 terms (3 bf16 MFMA products per multiply-add, f32 accumulate) in layers 2..n-1; not the headline precision",
+                  "fp16x2": "f32 values as 2 fp16 terms (3 fp16 MFMA products per multiply-add, f32 accumulate) in layers 2..n-1; not the headline precision",
+                  "bf16x3": "f32 values as 3 bf16 terms (6 bf16 MFMA products per multiply-add, f32 accumulate) in layers 2..n-1; not the headline precision"}[args.precision],
+        "data": "synthetic",
+        "value_resident": round(value, 4),
+        "config": {"workload": wl_name + ": scale2.0x topology (1-32-32-64-64-128-128-1, synthetic seeded weights) on a "
+                               "%dx%d RGB frame -> Y plane nearest-2x -> %dx%d CNN plane, %s" %
+                               (in_w, in_h, W, H, ("ONE frame per step, rank r computes rows [H*r/N, H*(r+1)/N) (+7-row halo), no exchange" if sharded
+                                                   else "one frame per GPU per step")),
+                   "cnn_plane": [H, W], "frames_per_step": 1 if sharded else world,
+                   "sharding": ("contiguous row ranges of one plane per rank, no collective on the data path, host-side gather" if sharded
+                                else "independent frames per rank, no collective on the data path")},
+        "ranks_seen": (dist.get_world_size() if dist is not None else 1), "backend": backend if dist is not None else None,
+    }
+    if not args.full:
+        # a plain run: the headline and nothing else
+        if rank == 0:
+            print(json.dumps(headline))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     # (a second, un-reduced look at the same K steps per rank would perturb the timed region: the per-rank figure is this rank's own
     #  wall time of the profiled pass below)
     # second pass, same K steps, with the per-layer hipEvents on the launch stream: per-kernel durations for `roofline`
@@ -386,9 +453,6 @@ def main():
         # the CPU oracle as the CHECKER of the plane just timed (never inside a timed region)
         rows_of = lambda a, b: nn2x(y_src[a // 2:(b + 1) // 2])[a - 2 * (a // 2):][:b - a]
         parity = parity_patches(layers, rows_of, d_out, ra, rb, H, W, n_layers)
-    if args.dump_out:
-        os.makedirs(args.dump_out, exist_ok=True)
-        np.savez(os.path.join(args.dump_out, "rank%d.npz" % rank), ra=ra, rb=rb, rows=d_out.cpu().numpy())
 
     # ---- host -> host: the convertWithModels call on HOST planes, PCIe and stitch included ----------------
     host = None
@@ -590,8 +654,6 @@ def main():
             extras["zero_operand_error"] = repr(e)
 
     if rank == 0:
-        in_px = in_h * in_w
-        value = (1 if sharded else world) * in_px * args.steps / elapsed / 1e6
         # algorithmic FLOPs of one step per layer: every band launch of layer k computes
         # (band rows + 2(n-k)) x (W + 2(n-k)) pixels (valid conv on the haloed band)
         band_h = rb - ra
@@ -646,38 +708,17 @@ def main():
                                          "figures do not); this launch only sums the partial tap planes")
         traffic, traffic_note = (pmc_traffic(ms.kernel_name(dom, opts), ms.planes(dom)[0], ms.planes(dom)[1], H, W, args.precision)
                                  if (dom == n_layers - 2 and bands == 1 and not sharded and args.precision in ("fp32", "bf16")) else (None, "no PMC profile for this configuration"))
-        wl_name = {"scale2x_1080p": "scale2x_1080p (BASELINE.json configs[1])", "plane": "plane, row-sharded over ranks (BASELINE.json configs[2] at 8192x8192)",
-                   "image_u8": "image_u8 (N2: u8 RGB in -> u8 2x RGB out, colour + bicubic U/V on the GPU)"}[workload]
-        out = {
-            "metric": "Mpixels/sec end-to-end scale2.0x 7-layer conv",
-            "value": round(value, 4),
-            "unit": "Mpix/s (input-image pixels; CNN-plane pixels = 4x)",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "strong" if sharded else "weak", "vs_baseline": None,
-            "dtype": {"fp32": "f32",
-                      "bf16": "bf16 activations/weights between layers, f32 accumulate (not the headline precision)",
-                      "bf16x2": "f32 values as 2 bf16 terms (3 bf16 MFMA products per multiply-add, f32 accumulate) in layers 2..n-1; not the headline precision",
-                      "fp16x2": "f32 values as 2 fp16 terms (3 fp16 MFMA products per multiply-add, f32 accumulate) in layers 2..n-1; not the headline precision",
-                      "bf16x3": "f32 values as 3 bf16 terms (6 bf16 MFMA products per multiply-add, f32 accumulate) in layers 2..n-1; not the headline precision"}[args.precision],
-            "data": "synthetic",
+        out = dict(headline)
+        out["config"]["bands_per_unit"] = max(bands, 1)
+        out.update({
             "value_is": ("`value` = planes resident in HBM when the timed region starts, as the bench contract defines it (a PCIe-inclusive rate is never `value`). "
                          "BASELINE.json's metric says END-TO-END, which SURVEY 8(d) defines as host plane in -> host plane out (what main.cpp:148 brackets): "
                          "that is `value_end_to_end` (= `value_host_to_host`, pageable planes), measured in the same run; quote it first wherever 'end-to-end' is meant"),
-            "value_resident": round(value, 4),
             "value_host_to_host": host["pageable"]["Mpix_s"] if host else None,
             "value_end_to_end": host["pageable"]["Mpix_s"] if host else None,
-            "config": {"workload": wl_name + ": scale2.0x topology (1-32-32-64-64-128-128-1, synthetic seeded weights) on a "
-                                   "%dx%d RGB frame -> Y plane nearest-2x -> %dx%d CNN plane, %s" %
-                                   (in_w, in_h, W, H, ("ONE frame per step, rank r computes rows [H*r/N, H*(r+1)/N) (+7-row halo), no exchange" if sharded
-                                                       else "one frame per GPU per step")),
-                       "cnn_plane": [H, W], "frames_per_step": 1 if sharded else world, "bands_per_unit": max(bands, 1),
-                       "sharding": ("contiguous row ranges of one plane per rank, no collective on the data path, host-side gather" if sharded
-                                    else "independent frames per rank, no collective on the data path")},
             "ms_per_step_profiled": round(elapsed_prof / args.steps * 1e3, 4),
-            # self-check of a multi-rank record: the world size the process group reports, the devices the ranks sit on, and each
+            # self-check of a multi-rank record (with `ranks_seen` / `backend` above): the devices the ranks sit on, and each
             # rank's own ms per step (profiled pass, barrier to barrier): N entries, all close to `ms_per_step`, or the run is not N-wide
-            "ranks_seen": (dist.get_world_size() if dist is not None else 1), "backend": backend if dist is not None else None,
             "visible_devices": torch.cuda.device_count(), "rank_devices": [int(v) for v in rank_dev],
             "rank_ms_per_step": [round(v, 4) for v in rank_ms],
             "roofline": {"bound": "mfma", "kernel": "%s (layer %d, %d->%d)" % ((ms.kernel_name(dom, opts), dom + 1) + ms.planes(dom)),
@@ -707,7 +748,7 @@ def main():
             "parity_patch_max_rel_err": (float("%.4g" % parity[0]) if parity else None),
             "parity_patch_within_gate": (parity[1] if parity else None),
             "parity_patch_spots": ([list(p) for p in parity[2]] if parity else None),
-        }
+        })
         if host:
             out["host_to_host"] = host
         out.update(extras)

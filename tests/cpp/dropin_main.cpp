@@ -1,8 +1,8 @@
 // tests/cpp/dropin_main.cpp -- ONE caller, written against the reference's public API only
 // (w2xc::modelUtility, w2xc::convertWithModels, w2xc::Model::filter; the call sequence of
-// /root/reference/src/main.cpp:79-98 and src/test.cpp:72-85), compiled TWICE by tests/cpp/Makefile:
-//   dropin_ref : -I/root/reference/src + the reference's modelHandler.cpp/convertRoutine.cpp (OpenCV shim)
-//   dropin_hip : -Iinclude/w2xc      + libw2xc_hip.so                                   (same shim for cv::Mat)
+// the reference's src/main.cpp:79-98 and src/test.cpp:72-85), compiled TWICE:
+//   oracle/_ref/dropin_ref     (oracle/Makefile)   : the reference's src/ + its modelHandler.cpp/convertRoutine.cpp (OpenCV shim)
+//   tests/cpp/_build/dropin_hip (tests/cpp/Makefile): -Iinclude/w2xc + libw2xc_hip.so                        (same shim for cv::Mat)
 // usage: dropin_xxx convert model.json in.f32 w h out.f32 [block_splitting]
 //        dropin_xxx filter  model.json layer in.f32 nplanes w h out.f32
 //        dropin_xxx chain   model.json in.f32 w h out.f32          (every layer through Model::filter, test.cpp:72-85)

@@ -1,7 +1,8 @@
 """The C++ drop-in boundary: tests/cpp/dropin_main.cpp is ONE caller written against the reference's
-public API (modelUtility::generateModelFromJSON, setNumberOfJobs, convertWithModels, Model::filter);
-tests/cpp/Makefile compiles it twice -- against the reference's own sources (dropin_ref) and against
-include/w2xc/*.hpp + libw2xc_hip.so (dropin_hip).  Same program, same arguments, compared outputs."""
+public API (modelUtility::generateModelFromJSON, setNumberOfJobs, convertWithModels, Model::filter),
+compiled twice -- against the reference's own sources (oracle/_ref/dropin_ref, made by build() through
+oracle/Makefile beside the other reference build) and against include/w2xc/*.hpp + libw2xc_hip.so
+(tests/cpp/_build/dropin_hip, tests/cpp/Makefile).  Same program, same arguments, compared outputs."""
 import os
 import subprocess
 
@@ -13,16 +14,18 @@ from tools import gen_model
 from oracle import oracle as orc
 
 CPP = os.path.join(ROOT, "tests", "cpp")
-REF_BIN = os.path.join(CPP, "_build", "dropin_ref")
+REF_BIN = os.path.join(ROOT, "oracle", "_ref", "dropin_ref")
 HIP_BIN = os.path.join(CPP, "_build", "dropin_hip")
 
 
 @pytest.fixture(scope="module")
 def bins(w2xc):
-    if not (os.path.exists(HIP_BIN) and os.path.exists(REF_BIN)):
+    if not os.path.exists(HIP_BIN):
         subprocess.run(["make", "-C", CPP], check=True)
+    if not os.path.exists(REF_BIN):
+        orc.build()
     assert os.path.exists(HIP_BIN), "dropin_hip did not build"
-    assert os.path.exists(REF_BIN), "dropin_ref is prebuilt where /root/reference exists and travels with the repo"
+    assert os.path.exists(REF_BIN), "oracle/_ref/dropin_ref is made by build() (oracle/Makefile) where the reference sources are present"
     return REF_BIN, HIP_BIN
 
 

@@ -346,7 +346,7 @@ def run_bench(args, env=None, nproc=1, timeout=600):
 
 def test_bench_line_single_gpu(gpu):
     """N = 1: `value` = resident planes (bench contract), host->host beside it with its ratio, roofline from the profiled pass"""
-    j = run_bench(["--height", "270", "--width", "480", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extras"])
+    j = run_bench(["--height", "270", "--width", "480", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras"])
     assert j["n_gpus"] == 1 and j["scaling"] == "weak" and j["dtype"] == "f32" and j["output_finite"]
     assert j["value"] == j["value_resident"] > 0 and j["value_host_to_host"] > 0
     h = j["host_to_host"]
@@ -368,13 +368,46 @@ def test_bench_line_single_gpu(gpu):
     assert j["parity_patch_max_rel_err"] is None   # (--no-cpu-baseline: the oracle is not touched)
 
 
+def test_bench_plain_line_and_dumped_output(gpu, tmp_path):
+    """a plain run (no --full) prints the headline alone, `ms_per_step` is the wall time of exactly --steps steps (`value` follows from it),
+    and --dump-outputs writes what the timed path computed in its last step: the whole 2x plane in float32, the oracle's plane within the
+    tolerance, the same file on a second run with the same arguments"""
+    from bench import synth_luma, nn2x
+    dumps = [str(tmp_path / "a"), str(tmp_path / "b")]
+    lines = [run_bench(["--height", "96", "--width", "128", "--steps", "4", "--warmup", "1", "--dump-outputs", d]) for d in dumps]
+    j = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in j, k
+    assert j["metric"] == "Mpixels/sec end-to-end scale2.0x 7-layer conv" and j["higher_is_better"] is True and j["dtype"] == "f32"
+    assert j["steps"] == 4 and j["warmup"] == 1 and j["n_gpus"] == 1 and j["ms_per_step"] > 0
+    assert abs(j["value"] - 96 * 128 / j["ms_per_step"] / 1e3) <= 1e-3 * j["value"] + 1e-4
+    for k in ("roofline", "layers", "host_to_host", "cpu_baseline", "parity_patch_max_rel_err", "other_precisions", "matrix_clock"):
+        assert k not in j, k   # (behind --full)
+    got = [np.load(os.path.join(d, "output.npy")) for d in dumps]
+    assert got[0].dtype == np.float32 and got[0].shape == (192, 256) and os.listdir(dumps[0]) == ["output.npy"]
+    assert np.array_equal(got[0], got[1])
+    layers = gen_model.synth_layers(seed=gen_model.SEEDS["scale2.0x"])
+    assert_close(got[0], orc.Oracle(layers).convert(nn2x(synth_luma(2, 96, 128)), njob=8), "bench --dump-outputs")
+
+
+def test_bench_plain_two_ranks(gpu, tmp_path):
+    """a plain N = 2 run (gloo, ranks sharing this GPU): one headline line from rank 0, every rank's rows in its own file, together the plane"""
+    from bench import synth_luma, nn2x
+    d = str(tmp_path / "dump")
+    j = run_bench(["--height", "96", "--width", "128", "--steps", "2", "--warmup", "1", "--dump-outputs", d], env={"W2XC_BENCH_BACKEND": "gloo"}, nproc=2)
+    assert j["n_gpus"] == 2 and j["ranks_seen"] == 2 and j["scaling"] == "strong" and j["ms_per_step"] > 0 and "host_to_host" not in j
+    got = np.concatenate([np.load(os.path.join(d, "output_rank%d.npy" % r)) for r in range(2)])
+    layers = gen_model.synth_layers(seed=gen_model.SEEDS["scale2.0x"])
+    assert_close(got, orc.Oracle(layers).convert(nn2x(synth_luma(2, 96, 128)), njob=8), "plain 2-rank --dump-outputs")
+
+
 def test_bench_rccl_process_group_one_rank(gpu):
     """the N > 1 code of bench.py on the REAL backend ("nccl" = RCCL): a one-rank process group under torch.distributed.run, so that the
     RCCL initialisation (dmabuf IPC: HSA_ENABLE_IPC_MODE_LEGACY=0), the barrier, the MAX all_reduce and the all_gather of the per-rank
     figures have run on this image before a multi-GPU node sees them (two ranks cannot share a device under RCCL: that is the gloo test)"""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29533",
            os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "plane", "--height", "96", "--width", "128", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-extras"]   # (the row-sharded workload of N > 1, here with one shard)
+           "--full", "--no-cpu-baseline", "--no-extras"]   # (the row-sharded workload of N > 1, here with one shard)
     r = subprocess.run(cmd, env=dict(os.environ, W2XC_BENCH_FORCE_PG="1", HSA_ENABLE_IPC_MODE_LEGACY="0"), capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -387,27 +420,27 @@ def test_bench_two_ranks_shard_one_plane_on_the_hip_path(gpu, tmp_path):
     the HIP path -- strong scaling, the weak figure beside it -- and the rows the ranks produced stitch to the oracle's plane"""
     from bench import synth_luma, nn2x
     d = str(tmp_path / "dump")
-    j = run_bench(["--height", "96", "--width", "128", "--steps", "2", "--warmup", "1", "--dump-out", d],
+    j = run_bench(["--height", "96", "--width", "128", "--steps", "2", "--warmup", "1", "--full", "--dump-outputs", d],
                   env={"W2XC_BENCH_BACKEND": "gloo"}, nproc=2)
     assert j["n_gpus"] == 2 and j["scaling"] == "strong" and j["config"]["frames_per_step"] == 1
     assert j["ranks_seen"] == 2 and len(j["rank_ms_per_step"]) == 2 and len(j["rank_devices"]) == 2 and all(v > 0 for v in j["rank_ms_per_step"])
     assert "row-sharded" in j["config"]["workload"] and j["value"] > 0 and j["value_host_to_host"] > 0
     assert j["host_to_host"]["max_abs_diff_vs_resident_output"] == 0.0
     assert j["weak"]["scaling"] == "weak" and j["weak"]["value"] > 0
-    parts = [np.load(os.path.join(d, "rank%d.npz" % r)) for r in range(2)]
-    assert int(parts[0]["ra"]) == 0 and int(parts[0]["rb"]) == int(parts[1]["ra"]) == 96 and int(parts[1]["rb"]) == 192
-    got = np.concatenate([p["rows"] for p in parts])
+    parts = [np.load(os.path.join(d, "output_rank%d.npy" % r)) for r in range(2)]
+    assert [p.shape for p in parts] == [(96, 256), (96, 256)]   # rows [0, 96) and [96, 192) of the 192x256 plane
+    got = np.concatenate(parts)
     layers = gen_model.synth_layers(seed=gen_model.SEEDS["scale2.0x"])
     want = orc.Oracle(layers).convert(nn2x(synth_luma(2, 96, 128)), njob=8)
     assert_close(got, want, "2-rank sharded plane")
 
 
 def test_bench_plain_invocation_gpus2(gpu):
-    """`python bench.py --gpus 2` WITHOUT torch.distributed.run (the shape of the driver's N = 1 command with another N): bench.py re-executes
-    itself under the launcher, one rank per GPU -- on this one-GPU box the two ranks share the device, so it picks gloo for the barrier by
+    """`python bench.py --gpus 2` WITHOUT torch.distributed.run (the shape of the driver's N = 1 command with another N): bench.py runs
+    itself as a child under the launcher, one rank per GPU -- on this one-GPU box the two ranks share the device, so it picks gloo for the barrier by
     itself -- and prints the one N = 2 line.  A first multi-GPU run cannot fail for a launcher reason."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "W2XC_BENCH_BACKEND")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--height", "96", "--width", "128", "--steps", "2", "--warmup", "1", "--no-extras"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--height", "96", "--width", "128", "--steps", "2", "--warmup", "1", "--full", "--no-extras"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -426,17 +459,17 @@ def test_bench_eight_ranks_shard_one_plane_bit_identical_to_one_rank(gpu, tmp_pa
     node -- every rank its rows plus the 28-row halo conv3x3_wino4's band geometry wants (4 rows per layer) -- and the eight shards, stitched, are
     BIT-identical to the plane one rank computes alone.  The record's self-checks (ranks_seen, per-rank times, devices) hold for N = 8."""
     d8, d1 = str(tmp_path / "d8"), str(tmp_path / "d1")
-    args = ["--workload", "plane", "--height", "1024", "--width", "768", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extras"]
-    j8 = run_bench(args + ["--dump-out", d8], env={"W2XC_BENCH_BACKEND": "gloo"}, nproc=8, timeout=1500)
+    args = ["--workload", "plane", "--height", "1024", "--width", "768", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras"]
+    j8 = run_bench(args + ["--dump-outputs", d8], env={"W2XC_BENCH_BACKEND": "gloo"}, nproc=8, timeout=1500)
     assert j8["n_gpus"] == 8 and j8["ranks_seen"] == 8 and j8["scaling"] == "strong" and j8["config"]["frames_per_step"] == 1
     assert len(j8["rank_ms_per_step"]) == 8 and all(v > 0 for v in j8["rank_ms_per_step"]) and len(j8["rank_devices"]) == 8
     assert j8["host_to_host"]["max_abs_diff_vs_resident_output"] == 0.0 and j8["output_finite"]
-    parts = [np.load(os.path.join(d8, "rank%d.npz" % r)) for r in range(8)]
-    assert int(parts[0]["ra"]) == 0 and int(parts[7]["rb"]) == 2048 and all(int(parts[r]["rb"]) == int(parts[r + 1]["ra"]) for r in range(7))
-    got = np.concatenate([p["rows"] for p in parts])
-    j1 = run_bench(args + ["--dump-out", d1])
-    one = np.load(os.path.join(d1, "rank0.npz"))
-    assert int(one["ra"]) == 0 and int(one["rb"]) == 2048 and j1["ranks_seen"] == 1
-    assert np.array_equal(got, one["rows"]), "8 row shards != the plane of one rank (max |diff| %g)" % float(np.abs(got - one["rows"]).max())
+    parts = [np.load(os.path.join(d8, "output_rank%d.npy" % r)) for r in range(8)]
+    assert [p.shape for p in parts] == [(b - a, 1536) for a, b in (gpu.shard_rows(2048, 8, r) for r in range(8))]
+    got = np.concatenate(parts)
+    j1 = run_bench(args + ["--dump-outputs", d1])
+    one = np.load(os.path.join(d1, "output.npy"))
+    assert one.shape == (2048, 1536) and j1["ranks_seen"] == 1
+    assert np.array_equal(got, one), "8 row shards != the plane of one rank (max |diff| %g)" % float(np.abs(got - one).max())
     h = j8["host_to_host"]
     print("8 ranks on one device, 2048x1536 plane: resident %.2f ms per step, host gather %s" % (j8["ms_per_step"], {k: v for k, v in h.items() if isinstance(v, dict)}))

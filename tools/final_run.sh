@@ -19,8 +19,9 @@ python tools/make_profile_summary.py gpurun_out/prof_$TAG gpurun_out/$TAG fp32 2
 python tools/make_profile_summary.py gpurun_out/prof_${TAG}_bf16 gpurun_out/${TAG}_bf16 bf16 2>&1 | tail -3
 cp gpurun_out/${TAG}_roofline.json profiles/${TAG}_roofline.json
 cp gpurun_out/${TAG}_bf16_roofline.json profiles/${TAG}_bf16_roofline.json
-python bench.py > gpurun_out/${TAG}_bench_fp32.json 2> gpurun_out/bench_fp32.err; tail -c 1200 gpurun_out/${TAG}_bench_fp32.json
-python bench.py --precision bf16 --no-cpu-baseline > gpurun_out/${TAG}_bench_bf16.json 2> gpurun_out/bench_bf16.err; tail -c 400 gpurun_out/${TAG}_bench_bf16.json
+# the bench lines every figure of README / DESIGN is quoted from: full lines (--full), straight into profiles/
+python bench.py --full > profiles/${TAG}_bench_fp32.json; tail -c 1200 profiles/${TAG}_bench_fp32.json
+python bench.py --full --precision bf16 --no-cpu-baseline > profiles/${TAG}_bench_bf16.json; tail -c 400 profiles/${TAG}_bench_bf16.json
 python tools/host_ab.py > gpurun_out/${TAG}_host_ab.log 2>&1; python tools/host_ab.py --pinned >> gpurun_out/${TAG}_host_ab.log 2>&1; grep -v amdgpu.ids gpurun_out/${TAG}_host_ab.log
 python tools/fusion_ab.py --rounds 3 > gpurun_out/${TAG}_fusion_ab.log 2>&1; grep round gpurun_out/${TAG}_fusion_ab.log
 python tools/run_configs.py > gpurun_out/configs.log 2> gpurun_out/configs.err; cp gpurun_out/configs.json gpurun_out/${TAG}_configs.json; tail -c 600 gpurun_out/configs.log

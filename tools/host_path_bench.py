@@ -8,7 +8,7 @@ ap.add_argument("--precision", default="fp32")
 ap.add_argument("--jobs", default="4,8,16,32")
 a = ap.parse_args()
 for j in a.jobs.split(","):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-extras", "--precision", a.precision,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-extras", "--precision", a.precision,
                           "--jobs", j, "--steps", "10", "--host-steps", "15"], capture_output=True, text=True).stdout.strip().splitlines()[-1]
     r = json.loads(out)
     h = r["host_to_host"]
