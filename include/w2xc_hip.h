@@ -228,6 +228,26 @@ int w2xc_convert_plane_nn2x_device(w2xc_model *m, const float *d_in, size_t in_s
                                    float *d_out, size_t out_stride_bytes, void *hip_stream,
                                    const w2xc_opts *opts);
 
+/* Batches: n planes of ONE size in one call (sprite sheets, icon sets, thumbnails, dataset crops, short clips).  (w, h) is the SOURCE size, the
+ * output planes are (w << nn2x) x (h << nn2x) (nn2x = 1: the nearest-neighbour 2x of w2xc_convert_plane_nn2x folded into layer 1).  out[i] is
+ * BIT-identical to w2xc_convert_plane[_nn2x][_device] on in[i] with the same opts, for every option set.  With the default fp32 chain (fp32,
+ * W2XC_KERNEL_AUTO, a one-plane model whose layers 1 + 2, mid layers and fused last layer run conv3x3_first2_wino4 / conv3x3_wino4 / the gather, an
+ * image that fits one band) a sub-batch of images -- as many as w2xc_opts.workspace_mb holds -- is ONE launch per layer, the kernels walking the
+ * items of all its images; every other case (16-bit precisions, named kernels, other fusion settings, planes larger than one band) runs the
+ * single-plane launch sequence per image, with no host synchronisation in between.  n < 1, null pointers, non-positive sizes, short strides and
+ * output planes that overlap each other or an input plane return W2XC_ERR_ARG, a model that does not take one plane to one plane
+ * W2XC_ERR_PLANES, before any device is touched.
+ * Device form: plane i starts i * *_plane_stride_bytes after d_in / d_out, on device opts->device, enqueued on `hip_stream` and NOT synchronised
+ * (as w2xc_convert_plane_device: asynchronous calls on one (model, device) share one stream).
+ * Host form: in[i] / out[i] are host planes; sub-batches are striped over opts->device_mask and run through the model's per-device host pipeline --
+ * the upload of sub-batch k + 1, the layers of sub-batch k and the download of sub-batch k - 1 overlap; pageable planes are staged by modelUtility's
+ * nJob threads through pinned slots, page-locked ones are DMA'd in place.  Returns when every out[i] is complete. */
+int w2xc_convert_batch_device(w2xc_model *m, int n, int nn2x, const float *d_in, size_t in_plane_stride_bytes,
+                              size_t in_stride_bytes, int w, int h, float *d_out, size_t out_plane_stride_bytes,
+                              size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts);
+int w2xc_convert_batch(w2xc_model *m, int n, int nn2x, const float *const *in, size_t in_stride_bytes, int w, int h,
+                       float *const *out, size_t out_stride_bytes, const w2xc_opts *opts);
+
 /* One UNIT of the tile farm from host memory (the reference's block walk, convertRoutine.cpp:114-165, made parallel across
  * processes): output rows [row_begin, row_end) of the conversion of a w x h source plane (nn2x = 1: of its nearest-
  * neighbour 2x, main.cpp:132-140, so the output plane is 2w x 2h and row numbers are in OUTPUT coordinates).

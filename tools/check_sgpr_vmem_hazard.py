@@ -40,6 +40,12 @@ for part in re.split(r'\n(?=[0-9a-f]{16} <)', txt):
                 bad += 1
                 print("%s: %s  <- %d wait states after: %s" % (m.group(1)[:50], l, states, p))
                 break
+            # a SALU instruction in between that writes the register (an asm helper's in-statement s_mov_b64 copy) is what the VMEM reads: SALU -> VMEM has no
+            # hazard, and VALU -> SALU is interlocked
+            ms = re.match(r's_(?!nop|waitcnt|cbranch|branch|barrier|setprio|sleep)\S+\s+(s\[\d+:\d+\]|s\d+)\s*,', p)
+            if ms:
+                used -= sregs(ms.group(1))
+                if not used: break
             mn = re.match(r's_nop (\d+)', p)
             states += (int(mn.group(1)) + 1) if mn else 1
 print("hazards found: %d" % bad)

@@ -104,6 +104,8 @@ def _load():
         "w2xc_layer_filter_device": (ci, [vp, ci, ci, fp, C.c_longlong, C.c_longlong, C.c_longlong, ci, ci, fp, C.c_longlong,
                                           C.c_longlong, C.c_longlong, vp, C.POINTER(Opts)]),
         "w2xc_convert_rows_device": (ci, [vp, fp, cs, ci, ci, ci, ci, ci, ci, fp, cs, vp, C.POINTER(Opts)]),
+        "w2xc_convert_batch_device": (ci, [vp, ci, ci, fp, cs, cs, ci, ci, fp, cs, cs, vp, C.POINTER(Opts)]),
+        "w2xc_convert_batch": (ci, [vp, ci, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, C.POINTER(Opts)]),
         "w2xc_layer_filter": (ci, [vp, ci, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, C.POINTER(Opts)]),
         "w2xc_profile_read": (ci, [vp, ci, C.POINTER(C.c_float), C.POINTER(ci), ci]),
         "w2xc_profile_reset": (None, [vp, ci]),
@@ -307,6 +309,45 @@ class _ModelSet:
         """Device-pointer form (ints: hipDeviceptr / hipStream_t).  Asynchronous on `stream`."""
         rc = _lib.w2xc_convert_plane_device(self.handle, C.c_void_p(d_in), in_stride_bytes, w, h,
                                             C.c_void_p(d_out), out_stride_bytes, C.c_void_p(stream),
+                                            C.byref(opts) if opts is not None else None)
+        if rc != OK:
+            raise W2xcError(rc, last_error())
+
+    def convert_batch(self, planes, nn2x=False, opts=None, out=None):
+        """n host planes of one size in one call (w2xc_convert_batch): `planes` is a list of h x w float32 planes or an (n, h, w) array; returns
+        an (n, h << nn2x, w << nn2x) float32 array (or fills `out`, such an array).  Plane i is bit-identical to convert[_nn2x](planes[i])."""
+        up = 1 if nn2x else 0
+        if isinstance(planes, np.ndarray):
+            if planes.ndim != 3:
+                raise ValueError("convert_batch wants an (n, h, w) array or a list of h x w planes")
+            planes = [planes[i] for i in range(planes.shape[0])]
+        srcs = [Mat(p).array for p in planes]
+        if not srcs:
+            raise ValueError("convert_batch wants at least one plane")
+        h, w = srcs[0].shape
+        if any(a.shape != (h, w) for a in srcs):
+            raise ValueError("convert_batch: every plane must have the same size (group planes by size)")
+        if len({a.strides[0] for a in srcs}) != 1:
+            srcs = [np.ascontiguousarray(a) for a in srcs]
+        n = len(srcs)
+        if out is None:
+            out = np.empty((n, h << up, w << up), np.float32)
+        elif out.shape != (n, h << up, w << up) or out.dtype != np.float32 or out.strides[2] != 4:
+            raise ValueError("convert_batch: `out` must be a float32 (n, h', w') array with contiguous rows")
+        ip = (C.c_void_p * n)(*[a.ctypes.data for a in srcs])
+        op = (C.c_void_p * n)(*[out[i].ctypes.data for i in range(n)])
+        rc = _lib.w2xc_convert_batch(self.handle, n, up, ip, srcs[0].strides[0], w, h, op, out.strides[1],
+                                     C.byref(opts) if opts is not None else None)
+        if rc != OK:
+            raise W2xcError(rc, last_error())
+        return out
+
+    def convert_batch_device(self, n, d_in, in_plane_stride_bytes, in_stride_bytes, w, h, d_out, out_plane_stride_bytes,
+                             out_stride_bytes, nn2x=False, stream=0, opts=None):
+        """Device-pointer batch (w2xc_convert_batch_device): n planes of w x h at d_in + i * in_plane_stride_bytes, outputs
+        (w << nn2x) x (h << nn2x) at d_out + i * out_plane_stride_bytes.  Asynchronous on `stream`."""
+        rc = _lib.w2xc_convert_batch_device(self.handle, n, 1 if nn2x else 0, C.c_void_p(d_in), in_plane_stride_bytes, in_stride_bytes, w, h,
+                                            C.c_void_p(d_out), out_plane_stride_bytes, out_stride_bytes, C.c_void_p(stream),
                                             C.byref(opts) if opts is not None else None)
         if rc != OK:
             raise W2xcError(rc, last_error())

@@ -90,6 +90,7 @@ struct HostPipe {
     size_t in_slot_bytes = 0, out_slot_bytes = 0;
     hipEvent_t ev_in_slot[IN_SLOTS] = {}, ev_out_slot[OUT_SLOTS] = {};   // last DMA that used the slot
     hipEvent_t ev_input = nullptr, ev_chunk = nullptr;                   // band input landed / last-layer chunk computed
+    hipEvent_t ev_batch[4] = {};   // w2xc_convert_batch: [slot] = the layers of the sub-batch in device slot `slot` done, [2 + slot] = its download done
     // conv3x3_wino4 PROG: two page-locked band buffers the gather jobs write the output rows into over PCIe (bands alternate), and their job flags
     char *pin_band[2] = {nullptr, nullptr};
     size_t band_bytes[2] = {0, 0};
@@ -107,6 +108,7 @@ struct HostPipe {
         for (auto &e : ev_out_slot) if (e) { hipEventDestroy(e); e = nullptr; }
         if (ev_input) { hipEventDestroy(ev_input); ev_input = nullptr; }
         if (ev_chunk) { hipEventDestroy(ev_chunk); ev_chunk = nullptr; }
+        for (auto &e : ev_batch) if (e) { hipEventDestroy(e); e = nullptr; }
         if (d_in) { hipFree(d_in); d_in = nullptr; d_in_bytes = 0; }
         if (d_out) { hipFree(d_out); d_out = nullptr; d_out_bytes = 0; }
         if (pin_in) { hipHostFree(pin_in); pin_in = nullptr; in_slot_bytes = 0; }
@@ -263,7 +265,9 @@ struct RowPlan {
 int plan_rows(const w2xc_model *m, const w2xc_opts &o_in, int w, int vh, int vy0, int ra, int rb, int plane_h, int n_in, bool all_out, RowPlan *p);
 
 // ---- w2xc_rows.cpp ----
-int launch_layer(DevCtx *c, const w2xc_model *m, int l, W2xcKernelKind kind, W2xcConvDesc d, hipStream_t st, const w2xc_opts &o);
+// bd != nullptr: the batch form of the launch (w2xc_convert_batch*; conv3x3_first2_wino4 / conv3x3_wino4 planar or fused-last / the gather) on bd->batch images
+int launch_layer(DevCtx *c, const w2xc_model *m, int l, W2xcKernelKind kind, W2xcConvDesc d, hipStream_t st, const w2xc_opts &o,
+                 const W2xcBatchDesc *bd = nullptr);
 
 // Hooks of the host->host tile farm into the band loop (all optional; enqueue-only, never synchronise the device):
 struct BandHooks {
@@ -292,5 +296,22 @@ int run_rows(w2xc_model *m, DevCtx *c, const float *d_in, size_t in_stride_f, in
              float *d_out, size_t out_stride_f, hipStream_t st, const w2xc_opts &o_in, int up = 0, int n_in = 1,
              long long in_cs = 0, long long out_cs = 0, const BandHooks *hk = nullptr, int plane_h = 0);
 int check_plane_args(const w2xc_model *m, const void *in, size_t in_stride, int w, int h, const void *out, size_t out_stride);
+
+// ---- batches of same-size planes (w2xc_convert_batch*) ----
+// the batched launch chain runs a call planned as P (one image of the batch): fp32, W2XC_KERNEL_AUTO, conv3x3_first2_wino4 -> conv3x3_wino4 (planar) ... ->
+// conv3x3_wino4 FUSE7 -> gather, one plane in and out, the whole image in one band.  Everything else takes the single-image launch sequence per image.
+bool batch_eligible(const w2xc_model *m, const RowPlan &P);
+// images per sub-batch for a per-image workspace of img_floats[2] floats under the call's workspace_mb budget (>= 1)
+int batch_sub_size(const w2xc_opts &o, const size_t img_floats[2]);
+// nimg planes of the (w << up) x (h << up) conversion of w x h source planes (image i at d_in + i in_ps / d_out + i out_ps, rows in_rs / out_rs apart; all
+// in floats) on `st`; enqueue-only.  max_sub > 0 caps the sub-batch size.  The caller holds c->mu.
+int run_batch(w2xc_model *m, DevCtx *c, int nimg, int up, const float *d_in, long long in_ps, size_t in_rs, int w, int h, float *d_out, long long out_ps,
+              size_t out_rs, hipStream_t st, const w2xc_opts &o_in, int max_sub = 0);
+// per-image workspace floats of the batched chain (0, 0 when P is not eligible) -- what a sub-batch of k images needs is k times this
+void batch_ws_floats(const RowPlan &P, size_t img_floats[2]);
+int check_batch_model(const w2xc_model *m);
+int check_batch_args(const w2xc_model *m, int nimg, int nn2x, int w, int h, size_t in_stride, size_t out_stride);
+// byte ranges [lo, hi) tagged 1 = output, 0 = input (sorted in place): W2XC_ERR_ARG when an output overlaps another output or an input
+int check_batch_overlap(std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> &iv);
 
 }  // namespace w2xc_eng

@@ -59,6 +59,17 @@ struct W2xcConvDesc {
     unsigned prog_epoch;
 };
 
+// Batch launches (w2xc_convert_batch*): `batch` images of identical geometry, each described by the W2xcConvDesc of the single-image launch; image i's
+// input / output start in_bs / out_bs floats after image 0's (for a fused-last producer out_bs is one image's block of tap planes).  `items` = the
+// single-image launch's item (first2: tile) count: the batch kernels walk batch x items items, image-major, and add i * stride to their 64-bit scalar
+// bases only -- every 32-bit lane offset and every range check of the single-image launcher stays per image.  (A struct of its own rather than fields
+// appended to W2xcConvDesc: that struct is the by-value argument of every existing kernel, and growing it would move their kernel-argument offsets.)
+struct W2xcBatchDesc {
+    int batch;
+    int items;
+    long long in_bs, out_bs;
+};
+
 enum W2xcKernelKind {
     W2XC_K_DIRECT = 0,   // any shape, any strides, reference summation order (VALU)
     W2XC_K_MFMA = 1,     // cin, cout in {32,64,128}; NHWC in/out; fp32 MFMA implicit GEMM
@@ -108,6 +119,12 @@ bool w2xc_wino4_prog_supported(int cin, int cout);
 size_t w2xc_wino4_prog_counters(int out_w, int out_h, int wino_py);
 // the job grid of such a launch: tile rows (16 rows each, the first one starting wino_py rows above the region) x groups of 8 tile columns (256 pixels)
 void w2xc_wino4_prog_jobs(int out_w, int out_h, int wino_py, int *tile_rows, int *groups);
+// batch forms (bit-identical per image to the launches above; b.items is set by the launcher): conv3x3_wino4_batch (planar in, planar out or FUSE7, no
+// PROG), conv3x3_first2_wino4_batch, conv3x3_last_gather_x4_batch.  w2xc_wino4_batch_supported: a batch instantiation exists for this layer.
+bool w2xc_wino4_batch_supported(int cin, int cout, bool fused_last);
+hipError_t w2xc_launch_wino4_batch(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream);
+hipError_t w2xc_launch_first2_wino4_batch(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream);
+hipError_t w2xc_launch_last_gather_batch(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream);
 size_t w2xc_wino4_pack_last_floats(int cin);
 void w2xc_wino4_pack_last(int cin, const float *w, float *dst);
 

@@ -187,7 +187,7 @@ int w2xc_set_default_opts(const w2xc_opts *defaults)
 const char *w2xc_last_error(void) { return g_last_error.c_str(); }
 // 0.2: w2xc_opts grew (host_numa; 56 bytes), W2XC_FUSION_FIRST / _LAST, w2xc_opts_init_sized, w2xc_set_default_opts, w2xc_plan_rows; since 0.1 (rounds 3-5)
 // also: W2XC_KERNEL_WINOGRAD = _WINOGRAD32, W2XC_KERNEL_AUTO refused on a minimum-halo row view, `verbose` a bit mask (INTEGRATION.md "ABI history")
-const char *w2xc_version(void) { return "w2xc_hip 0.2 (gfx950)"; }
+const char *w2xc_version(void) { return "w2xc_hip 0.3 (gfx950)"; }
 
 int w2xc_plan_rows(const w2xc_model *m, int w, int view_y0, int view_h, int plane_h, int row_begin, int row_end, const w2xc_opts *opts, w2xc_row_plan *plan)
 try {

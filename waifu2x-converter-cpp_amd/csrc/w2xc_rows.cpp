@@ -12,7 +12,7 @@
 
 namespace w2xc_eng {
 
-int launch_layer(DevCtx *c, const w2xc_model *m, int l, W2xcKernelKind kind, W2xcConvDesc d, hipStream_t st, const w2xc_opts &o)
+int launch_layer(DevCtx *c, const w2xc_model *m, int l, W2xcKernelKind kind, W2xcConvDesc d, hipStream_t st, const w2xc_opts &o, const W2xcBatchDesc *bd)
 {
     DevLayer &dl = c->layers[l];
     d.cin = m->layers[l].nin;
@@ -88,7 +88,11 @@ int launch_layer(DevCtx *c, const w2xc_model *m, int l, W2xcKernelKind kind, W2x
     ProfEvent ev;
     const bool profile = o.profile != 0;
     if (profile) { int rc = prof_begin(c, l, st, &ev); if (rc) return rc; }
-    hipError_t e = kind == W2XC_K_MID_SPLIT     ? w2xc_launch_split_mid(d, st)
+    hipError_t e = bd ? (kind == W2XC_K_LAST_GATHER    ? w2xc_launch_last_gather_batch(d, *bd, st)
+                         : kind == W2XC_K_FIRST2_WINO4 ? w2xc_launch_first2_wino4_batch(d, *bd, st)
+                         : midv == MID_WINO4           ? w2xc_launch_wino4_batch(d, *bd, st)
+                                                       : hipErrorInvalidValue)
+                   : kind == W2XC_K_MID_SPLIT     ? w2xc_launch_split_mid(d, st)
                    : kind == W2XC_K_FIRST_SPLIT ? w2xc_launch_split_first(d, st)
                    : kind == W2XC_K_LAST_GATHER ? w2xc_launch_last_gather(d, st)
                    : kind == W2XC_K_FIRST2_SPLIT ? w2xc_launch_first2_split(d, st)
@@ -458,6 +462,133 @@ int check_plane_args(const w2xc_model *m, const void *in, size_t in_stride, int 
     return W2XC_OK;
 }
 
+// nimg planes of one size (w2xc_convert_batch*).  The plan is that of ONE image, exactly as the single-plane device call makes it.  Where the batched chain
+// applies (batch_eligible), a sub-batch of k images is one launch per layer: the descriptor of every launch is the single-image one (same regions, offsets,
+// wino_py, clamps, strides), and the batch kernels add image x stride to their scalar bases -- input planes, the k per-image blocks of the two workspaces,
+// output planes.  Everything else runs the single-image launch sequence per image on the same stream (no host synchronisation in between).
+int run_batch(w2xc_model *m, DevCtx *c, int nimg, int up, const float *d_in, long long in_ps, size_t in_rs, int w, int h, float *d_out, long long out_ps,
+              size_t out_rs, hipStream_t st, const w2xc_opts &o_in, int max_sub)
+{
+    const int W = w << up, H = h << up;
+    RowPlan P;
+    {
+        int rc = plan_rows(m, o_in, W, H, 0, 0, H, H, 1, false, &P);
+        if (rc) return rc;
+    }
+    if (!batch_eligible(m, P)) {
+        for (int i = 0; i < nimg; i++) {
+            int rc = run_rows(m, c, d_in + (size_t)i * in_ps, in_rs, H, 0, W, 0, H, d_out + (size_t)i * out_ps, out_rs, st, o_in, up, 1, 0, 0, nullptr, H);
+            if (rc) return rc;
+        }
+        return W2XC_OK;
+    }
+    const w2xc_opts &o = P.o;
+    const int n = P.n;
+    size_t img_f[2];
+    batch_ws_floats(P, img_f);
+    int sub = batch_sub_size(o, img_f);
+    if (max_sub > 0 && sub > max_sub) sub = max_sub;
+    if (sub > nimg) sub = nimg;
+    for (int i = 0; i < 2; i++)
+        if (img_f[i]) { int rc = ensure_ws(c, i, img_f[i] * (size_t)sub); if (rc) return rc; }
+
+    for (int b0 = 0; b0 < nimg; b0 += sub) {
+        W2xcBatchDesc bd;
+        memset(&bd, 0, sizeof bd);
+        bd.batch = std::min(sub, nimg - b0);
+        // run_rows' band loop for the one band [0, H), no hooks, on the fp32 chain batch_eligible accepted
+        const float *src = d_in + (size_t)b0 * in_ps;
+        long long src_rs = (long long)in_rs, src_ps = 1, src_cs = 0, src_ts = 0, src_gs = 0, src_bs = in_ps;
+        int src_halves = 0, src_h = H, src_w = W, Tprev = 0;
+        W2xcConvDesc first_d;
+        memset(&first_d, 0, sizeof first_d);
+        long long first_bs = 0;
+        for (int k = 1; k <= n; k++) {
+            const HostLayer &hl = m->layers[k - 1];
+            W2xcConvDesc d;
+            memset(&d, 0, sizeof d);
+            d.in = src; d.in_rs = src_rs; d.in_ps = src_ps; d.in_cs = src_cs;
+            d.in_h = src_h; d.in_w = src_w;
+            int Tk, Bk;
+            P.region(k, 0, H, Tk, Bk);
+            d.out_h = Bk - Tk;
+            d.out_w = W + 2 * (n - k);
+            d.off_y = Tk - 1 - Tprev;
+            Tprev = Tk;
+            d.off_x = k == 1 ? -n : 0;
+            const W2xcKernelKind kind = layer_kind(m, k - 1, o);
+            d.wino_py = Tk & (((w2xc_pick_kernel(hl.nin, hl.nout) == W2XC_K_MFMA && layer_mid_variant(m, k - 1, o) == MID_WINO4) || kind == W2XC_K_FIRST2_WINO4) ? 3 : 1);
+            d.in_shift = k == 1 ? up : 0;
+            if (kind == W2XC_K_FUSED_AWAY) {
+                first_d = d;
+                first_bs = src_bs;
+                continue;
+            }
+            bd.in_bs = src_bs;
+            if (kind == W2XC_K_FIRST2_WINO4) {
+                d.in = first_d.in; d.in_rs = first_d.in_rs; d.in_ps = first_d.in_ps; d.in_cs = first_d.in_cs;
+                d.in_h = first_d.in_h; d.in_w = first_d.in_w;
+                d.off_y += first_d.off_y; d.off_x += first_d.off_x; d.in_shift = first_d.in_shift;
+                bd.in_bs = first_bs;
+            }
+            d.out_terms = out_terms_of(m, k - 1, o);
+            if (kind == W2XC_K_LAST_GATHER) {
+                d.halves = src_halves; d.in_ts = src_ts; d.in_gs = src_gs;
+                d.in += (long long)d.off_y * d.in_rs;
+                d.in_h -= d.off_y;
+                d.off_y = 0;
+            }
+            if (k == n) {   // (batch_eligible: the gather writes the output planes)
+                d.out = d_out + (size_t)b0 * out_ps;
+                d.out_rs = (long long)out_rs; d.out_ps = 1; d.out_cs = 0;
+                bd.out_bs = out_ps;
+            } else {
+                d.out = c->ws[(k - 1) & 1];
+                d.out_rs = (d.out_w + 31) & ~31; d.out_ps = 1; d.out_cs = d.out_rs * (long long)d.out_h;   // (planar_between: batch_eligible)
+                if (d.out_terms == 9) {   // G[64-plane block][tap][y][x], as run_rows lays them out
+                    d.out_rs = gather_in_producer(m, o) ? ((d.out_w + 31) & ~31) : d.out_w; d.out_ps = 1;
+                    d.out_gs = (long long)d.out_h * d.out_rs;
+                    d.out_ts = 9 * d.out_gs;
+                    d.halves = fused_halves(0, hl.nout);
+                }
+                bd.out_bs = (long long)img_f[(k - 1) & 1];
+            }
+            int rc = launch_layer(c, m, k - 1, kind, d, st, o, &bd);
+            if (rc) return rc;
+            src = d.out; src_rs = d.out_rs; src_ps = d.out_ps; src_cs = d.out_cs; src_ts = d.out_ts; src_gs = d.out_gs; src_halves = d.halves;
+            src_h = d.out_h; src_w = d.out_w; src_bs = bd.out_bs;
+        }
+    }
+    return W2XC_OK;
+}
+
+// the argument checks of the batch entry points (no device is touched): n >= 1, sizes, strides, planes that do not overlap
+int check_batch_args(const w2xc_model *m, int nimg, int nn2x, int w, int h, size_t in_stride, size_t out_stride)
+{
+    if (!m) return fail(W2XC_ERR_ARG, "null model");
+    if (nimg < 1) return fail(W2XC_ERR_ARG, "batch of %d planes", nimg);
+    if (nn2x != 0 && nn2x != 1) return fail(W2XC_ERR_ARG, "nn2x must be 0 or 1");
+    if (w <= 0 || h <= 0) return fail(W2XC_ERR_ARG, "plane size must be positive (got %dx%d)", w, h);
+    if (w > (1 << 28) || h > (1 << 28)) return fail(W2XC_ERR_ARG, "plane too large");
+    if (in_stride < (size_t)w * 4 || out_stride < ((size_t)w << nn2x) * 4 || (in_stride & 3) || (out_stride & 3))
+        return fail(W2XC_ERR_ARG, "row strides must be multiples of 4 bytes and >= 4*width");
+    return W2XC_OK;
+}
+
+// [lo, hi) byte ranges: does any output overlap another output or any input?  (inputs may share memory with each other)
+int check_batch_overlap(std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> &iv)
+{
+    std::sort(iv.begin(), iv.end());
+    uintptr_t end_out = 0, end_in = 0;
+    for (const auto &e : iv) {
+        const uintptr_t lo = e.first.first, hi = e.first.second;
+        if (lo < end_out || (e.second && lo < end_in)) return fail(W2XC_ERR_ARG, "output planes overlap each other or an input plane");
+        if (e.second) end_out = std::max(end_out, hi);
+        else end_in = std::max(end_in, hi);
+    }
+    return W2XC_OK;
+}
+
 }  // namespace w2xc_eng
 
 using namespace w2xc_eng;
@@ -554,6 +685,37 @@ try {
     std::lock_guard<std::mutex> lk(c->mu);
     return run_rows(m, c, d_in, in_stride_bytes / 4, 2 * h, 0, 2 * w, 0, 2 * h, d_out, out_stride_bytes / 4,
                     (hipStream_t)hip_stream, o, 1, 1, 0, 0, nullptr, 2 * h);
+} W2XC_CATCH_ALL
+
+// ---- batches of same-size planes -----------------------------------------------------------------
+int w2xc_convert_batch_device(w2xc_model *m, int n, int nn2x, const float *d_in, size_t in_plane_stride_bytes, size_t in_stride_bytes, int w, int h,
+                              float *d_out, size_t out_plane_stride_bytes, size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts)
+try {
+    int rc = check_batch_args(m, n, nn2x, w, h, in_stride_bytes, out_stride_bytes);
+    if (rc) return rc;
+    if (!d_in || !d_out) return fail(W2XC_ERR_ARG, "null argument");
+    if ((in_plane_stride_bytes & 3) || (out_plane_stride_bytes & 3)) return fail(W2XC_ERR_ARG, "plane strides must be multiples of 4 bytes");
+    const int H = h << nn2x, W = w << nn2x;
+    const size_t in_ext = (size_t)(h - 1) * in_stride_bytes + (size_t)w * 4, out_ext = (size_t)(H - 1) * out_stride_bytes + (size_t)W * 4;
+    if (n > 1 && out_plane_stride_bytes < out_ext) return fail(W2XC_ERR_ARG, "output planes overlap each other (plane stride %zu < %zu bytes)", out_plane_stride_bytes, out_ext);
+    {
+        const uintptr_t i0 = (uintptr_t)d_in, i1 = i0 + (size_t)(n - 1) * in_plane_stride_bytes + in_ext;
+        const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (size_t)(n - 1) * out_plane_stride_bytes + out_ext;
+        if (i0 < o1 && o0 < i1) return fail(W2XC_ERR_ARG, "output planes overlap the input planes");
+    }
+    rc = check_batch_model(m);
+    if (rc) return rc;
+    const w2xc_opts o = resolve_opts(opts);
+    int dev = o.device;
+    if (dev < 0) HIP_TRY(hipGetDevice(&dev));
+    DeviceGuard guard(dev);
+    if (!guard.ok) return fail(W2XC_ERR_HIP, "cannot select HIP device %d", dev);
+    DevCtx *c = nullptr;
+    rc = get_ctx(m, dev, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return run_batch(m, c, n, nn2x, d_in, (long long)(in_plane_stride_bytes / 4), in_stride_bytes / 4, w, h, d_out, (long long)(out_plane_stride_bytes / 4),
+                     out_stride_bytes / 4, (hipStream_t)hip_stream, o);
 } W2XC_CATCH_ALL
 
 }  // extern "C"

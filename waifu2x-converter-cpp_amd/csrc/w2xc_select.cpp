@@ -301,4 +301,51 @@ int plan_rows(const w2xc_model *m, const w2xc_opts &o_in, int w, int vh, int vy0
     return W2XC_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Batches of same-size planes (w2xc_convert_batch*, run_batch in w2xc_rows.cpp): the launch chain that has batch kernels is exactly the default fp32 one --
+// conv3x3_first2_wino4 (layers 1 + 2), conv3x3_wino4 with planar planes in and out (layers 3 .. n - 2), conv3x3_wino4 FUSE7 (layer n - 1 + the last layer's
+// taps), the gather -- with one plane in, one plane out and the whole image in one band.  The decision is on the plan of ONE image, so it is the chain the
+// single-image call runs with the same options: an image of a batch is bit-identical to it either way.
+bool batch_eligible(const w2xc_model *m, const RowPlan &P)
+{
+    const w2xc_opts &o = P.o;
+    const int n = P.n;
+    if (P.T != 0 || o.precision != W2XC_PRECISION_FP32 || o.kernel != W2XC_KERNEL_AUTO || o.fusion == W2XC_FUSION_PROG) return false;
+    if (n < 5 || P.HL != 4 || P.all_out || !P.last_direct || P.band < P.plane_h || P.plane_h <= 0) return false;
+    if (m->layers[0].nin != 1 || m->layers[n - 1].nout != 1) return false;
+    if (layer_kind(m, 0, o) != W2XC_K_FUSED_AWAY || layer_kind(m, 1, o) != W2XC_K_FIRST2_WINO4) return false;
+    if (layer_kind(m, n - 1, o) != W2XC_K_LAST_GATHER || out_terms_of(m, n - 2, o) != 9) return false;
+    for (int l = 2; l <= n - 2; l++) {
+        const HostLayer &hl = m->layers[l];
+        if (layer_kind(m, l, o) != W2XC_K_MFMA || !is_wino4_layer(m, l, o) || !planar_between(m, l - 1, o)) return false;
+        if (l < n - 2 && (!planar_between(m, l, o) || out_terms_of(m, l, o) != 0)) return false;
+        if (!w2xc_wino4_batch_supported(hl.nin, hl.nout, l == n - 2)) return false;
+    }
+    return true;
+}
+
+void batch_ws_floats(const RowPlan &P, size_t img_floats[2])
+{
+    for (int i = 0; i < 2; i++) img_floats[i] = P.need[i] ? (((P.need[i] + 3) / 4 + 63) & ~(size_t)63) : 0;   // (every image's planes on 256-byte boundaries)
+}
+
+int batch_sub_size(const w2xc_opts &o, const size_t img_floats[2])
+{
+    const size_t budget = (size_t)(o.workspace_mb > 0 ? o.workspace_mb : 16384) << 20;   // the budget that sizes bands (plan_rows)
+    const size_t per = 4 * (img_floats[0] + img_floats[1]);
+    if (per == 0) return 1;
+    const size_t k = budget / per;
+    return k < 1 ? 1 : k > 65535 ? 65535 : (int)k;   // (the gather's grid has one row of workgroups per image)
+}
+
+// a batch converts one plane into one plane: what the multi-plane entry points (w2xc_convert_planes_device) are for is refused
+int check_batch_model(const w2xc_model *m)
+{
+    if (m->layers.empty()) return fail(W2XC_ERR_ARG, "model has no layers");
+    if (m->layers[0].nin != 1 || m->layers.back().nout != 1)
+        return fail(W2XC_ERR_PLANES, "w2xc_convert_batch*: one plane in and one plane out (the model takes %d and gives %d; see w2xc_convert_planes_device)",
+                    m->layers[0].nin, m->layers.back().nout);
+    return W2XC_OK;
+}
+
 }  // namespace w2xc_eng
