@@ -2,10 +2,13 @@
 //
 //   w2xc_model.cpp          error state, model container + JSON loader (the reference's Model / modelUtility,
 //                           src/modelHandler.{hpp,cpp}), per-(model, device) contexts, the measurement entry points
-//   w2xc_select.cpp         which kernel runs which layer, which layers fuse, the layouts between layers, and the band
-//                           geometry of run_rows (pure host arithmetic: unit-tested on the CPU through w2xc_plan_rows)
-//   w2xc_rows.cpp           launch_layer + run_rows: the band loop that replaces convertWithModels / ...Basic / ...BlockSplit
-//                           (src/convertRoutine.cpp:21-169), and the device-pointer entry points
+//   w2xc_select.cpp         which kernel runs which layer, which layers fuse, the layouts between layers, the band geometry
+//                           (plan_rows) and the launch descriptor of one layer of a band (layer_desc) -- pure host arithmetic:
+//                           unit-tested on the CPU through w2xc_plan_rows
+//   w2xc_cuts.hpp           where the chunked launch strategies cut a band's rows (integers only; tests/cpp/cuts_test.cpp)
+//   w2xc_rows.cpp           launch_layer, run_rows (the band loop that replaces convertWithModels / ...Basic / ...BlockSplit,
+//                           src/convertRoutine.cpp:21-169: run_band picks one launch strategy per layer -- prog, tail16, tail32,
+//                           first_chunks, last_chunks, plain), run_batch, and the device-pointer entry points
 //   w2xc_host_pipeline.cpp  host plane in -> host plane out: staging rings, three streams, feeder + drainer, the unit fan-out
 //   w2xc_filter.cpp         Model::filter at the host / device boundary (src/modelHandler.cpp:26-72)
 //   w2xc_image.cpp          N2: the CLI's image pipeline around the plane conversion (main.cpp:74-172)
@@ -263,6 +266,24 @@ struct RowPlan {
     void ws_need(const w2xc_model *m, int rows, size_t need_[2]) const;
 };
 int plan_rows(const w2xc_model *m, const w2xc_opts &o_in, int w, int vh, int vy0, int ra, int rb, int plane_h, int n_in, bool all_out, RowPlan *p);
+
+// the buffer a layer of a band reads: the caller's view (layer 1) or what the layer before it wrote
+struct LayerSrc {
+    const float *p = nullptr;
+    long long rs = 0, ps = 1, cs = 0, ts = 0, gs = 0;
+    int halves = 0, h = 0, w = 0;
+    int top = 0;   // first plane row it holds
+};
+// where a band's layers write: `out` = the caller's rows of this band (the last layer when P.last_direct), ws = the two ping-pong workspaces
+struct LayerDst {
+    float *out;
+    long long out_rs, out_cs;
+    float *ws[2];
+};
+// The launch descriptor *d of layer k (1 .. n) of the band [y0, y1) (no HIP call), the kind that runs it, and *next = what layer k + 1 reads.  first_d keeps
+// layer 1's input description from the W2XC_K_FUSED_AWAY call (no launch: *d is not to be used) to layer 2's.  run_rows and run_batch both build with this.
+W2xcKernelKind layer_desc(const w2xc_model *m, const RowPlan &P, int k, int y0, int y1, int up, const LayerSrc &src, const LayerDst &dst,
+                          W2xcConvDesc &first_d, W2xcConvDesc *d, LayerSrc *next);
 
 // ---- w2xc_rows.cpp ----
 // bd != nullptr: the batch form of the launch (w2xc_convert_batch*; conv3x3_first2_wino4 / conv3x3_wino4 planar or fused-last / the gather) on bd->batch images

@@ -301,6 +301,86 @@ int plan_rows(const w2xc_model *m, const w2xc_opts &o_in, int w, int vh, int vy0
     return W2XC_OK;
 }
 
+// The launch descriptor of layer k of the band [y0, y1): region, offsets into what it reads, Winograd block phase, the fused-first merge, the gather's
+// rebased view, and the layout of what it writes (the layouts between layers above).  The one place this is derived: run_rows and run_batch (w2xc_rows.cpp).
+W2xcKernelKind layer_desc(const w2xc_model *m, const RowPlan &P, int k, int y0, int y1, int up, const LayerSrc &src, const LayerDst &dst,
+                          W2xcConvDesc &first_d, W2xcConvDesc *dp, LayerSrc *next)
+{
+    const w2xc_opts &o = P.o;
+    const int n = P.n, T = P.T;
+    const HostLayer &hl = m->layers[k - 1];
+    W2xcConvDesc &d = *dp;
+    memset(&d, 0, sizeof d);
+    d.in = src.p; d.in_rs = src.rs; d.in_ps = src.ps; d.in_cs = src.cs;
+    d.in_h = src.h; d.in_w = src.w;
+    int Tk, Bk;
+    P.region(k, y0, y1, Tk, Bk);
+    d.out_h = Bk - Tk;
+    d.out_w = P.w + 2 * (n - k);
+    d.off_y = Tk - 1 - src.top;   // (k = 1: y0 - n - vy0; k > 1: 0 on the one-row-per-layer geometry)
+    d.off_x = k == 1 ? -n : 0;
+    // this launch's first output row in the coordinates of the whole plane, modulo the Winograd block height (2; conv3x3_wino4: 4)
+    const W2xcKernelKind kind = layer_kind(m, k - 1, o);
+    d.wino_py = Tk & (((w2xc_pick_kernel(hl.nin, hl.nout) == W2XC_K_MFMA && layer_mid_variant(m, k - 1, o) == MID_WINO4) || kind == W2XC_K_FIRST2_WINO4) ? 3 : 1);
+    d.in_shift = k == 1 ? up : 0;
+    *next = src;
+    next->top = Tk;
+    if (kind == W2XC_K_FUSED_AWAY) {   // layer 1 inside layer 2's kernel: keep its input description for that launch
+        first_d = d;
+        return kind;
+    }
+    if (kind == W2XC_K_FIRST2_SPLIT || kind == W2XC_K_FIRST2_WINO4) {
+        d.in = first_d.in; d.in_rs = first_d.in_rs; d.in_ps = first_d.in_ps; d.in_cs = first_d.in_cs;
+        d.in_h = first_d.in_h; d.in_w = first_d.in_w;
+        d.in_shift = first_d.in_shift;
+        // conv3x3_first2_wino4 takes layer 1's input view; a source row of layer 2's output row y, taps r' and r: y + r' + r + (both offsets)
+        if (kind == W2XC_K_FIRST2_WINO4) { d.off_y += first_d.off_y; d.off_x += first_d.off_x; }
+        else { d.off_y = first_d.off_y; d.off_x = first_d.off_x; }
+    }
+    d.out_terms = out_terms_of(m, k - 1, o);
+    d.in_ts = src.ts; d.in_gs = src.gs;   // (0 unless src holds term planes or the partial planes of a fused last layer; fp32: only that one uses the term fields)
+    if (kind == W2XC_K_LAST_GATHER) d.halves = src.halves;
+    if (T == 0 && kind == W2XC_K_LAST_GATHER) {
+        d.in += (long long)d.off_y * d.in_rs;   // (no offsets in that kernel; off_y > 0 on the four-rows-per-layer geometry only)
+        d.in_h -= d.off_y;
+        d.off_y = 0;
+    }
+    const int split_grp = T > 0 ? 16 : 0;   // channel-group size of the blocked term planes
+    if (T > 0) {
+        d.terms = (kind == W2XC_K_MID_SPLIT || kind == W2XC_K_FIRST2_SPLIT) ? T : 0;
+        d.fmt = split_fmt(o);
+        d.out_ts = (long long)d.out_h * d.out_w * hl.nout;
+        d.out_gs = (long long)d.out_h * d.out_w * split_grp;
+    }
+    if (k == n && P.last_direct) {
+        d.out = dst.out;
+        d.out_rs = dst.out_rs; d.out_ps = 1; d.out_cs = dst.out_cs;
+    } else {
+        d.out = dst.ws[(k - 1) & 1];
+        d.out_rs = (long long)d.out_w * hl.nout; d.out_ps = hl.nout; d.out_cs = 1;
+        if (planar_between(m, k - 1, o)) {
+            // planes of out_h rows of roundup32(out_w) floats: conv3x3_wino4 reads 16-byte pixel quads, and a tile's 32-pixel row segment
+            // (tiles start at multiples of 32 pixels) is then ONE 128-byte line -- with rows of roundup4(w) floats every segment straddled two
+            // lines, each written in two pieces by different workgroups (the 32 -> 32 layer in front: 2.0 ms instead of 0.8, measured)
+            d.out_rs = (d.out_w + 31) & ~31; d.out_ps = 1; d.out_cs = d.out_rs * (long long)d.out_h;
+        }
+        if (T > 0 && d.out_terms >= 1 && d.out_terms <= 3) { d.out_rs = (long long)d.out_w * split_grp; d.out_ps = split_grp; }
+        if (d.out_terms == 9) {   // G[half][tap][y][x]
+            // (where the producing launch finishes the last layer itself -- conv3x3_wino4 PROG --, rows start on 128-byte lines: a tile's 32-pixel row
+            //  segment of a tap plane is then exactly ONE line, written whole, and a gather job never pulls a line into its XCD's L2 that holds
+            //  columns of a tile it does not depend on -- with rows of out_w floats such a line, cached before its last columns were written, was
+            //  served stale to the neighbouring job later: intermittent mismatches on small planes)
+            d.out_rs = (T == 0 && gather_in_producer(m, o)) ? ((d.out_w + 31) & ~31) : d.out_w; d.out_ps = 1;
+            d.out_gs = (long long)d.out_h * d.out_rs;
+            d.out_ts = 9 * d.out_gs;
+            d.halves = fused_halves(T, hl.nout);   // (fp32: conv3x3_wino4 writes planar partial planes G[64-plane block][tap][y][x]: its epilogue sums the four plane tiles of a block on chip)
+        }
+    }
+    next->p = d.out; next->rs = d.out_rs; next->ps = d.out_ps; next->cs = d.out_cs; next->ts = d.out_ts; next->gs = d.out_gs;
+    next->halves = d.halves; next->h = d.out_h; next->w = d.out_w;
+    return kind;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Batches of same-size planes (w2xc_convert_batch*, run_batch in w2xc_rows.cpp): the launch chain that has batch kernels is exactly the default fp32 one --
 // conv3x3_first2_wino4 (layers 1 + 2), conv3x3_wino4 with planar planes in and out (layers 3 .. n - 2), conv3x3_wino4 FUSE7 (layer n - 1 + the last layer's
