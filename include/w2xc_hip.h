@@ -343,6 +343,16 @@ int w2xc_plan_rows(const w2xc_model *m, int w, int view_y0, int view_h, int plan
  * (negative rows / rows >= plane_h + ...: the replicate padding of convertRoutine.cpp:35 seen from that layer) */
 int w2xc_plan_region(const w2xc_row_plan *plan, int plane_h, int layer, int y0, int y1, int *top, int *bottom);
 
+/* Test aid.  Fills every grow-only scratch buffer the (model, device) context owns with the
+ * 32-bit word `word` and returns the number of bytes filled in *bytes (0 when the context does
+ * not exist yet: it is not created).  Synchronises the device before and after.
+ * Filled, each allocation whole: the two activation workspaces, Model::filter's device planes and bounce ring, the host pipeline's device rows,
+ * staging rings and page-locked band buffers, the image pipeline's planes -- data only.  Weights, biases and every synchronisation word (job counters
+ * and flags, events) are left alone.  What w2xc_opts.filter_resident promises is gone afterwards.  A conversion that follows must give the result it
+ * gives on fresh memory for every `word`: tests/test_gpu_scratch_poison.py.  device = -1: the current device.  Not to be called concurrently with
+ * asynchronous work of the caller on this (model, device) that has not been synchronised. */
+int w2xc_debug_fill_scratch(w2xc_model *m, int device, unsigned word, unsigned long long *bytes);
+
 int w2xc_device_count(void);          /* hipGetDeviceCount, 0 when no device / no driver           */
 const char *w2xc_last_error(void);    /* thread-local message of the last failing call             */
 const char *w2xc_version(void);

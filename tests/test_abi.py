@@ -283,6 +283,34 @@ def test_no_cpu_fallback_without_gpu(w2xc, noise1_layers):
     assert e.value.code == w2xc.ERR_HIP
 
 
+def test_fill_scratch_argument_errors(w2xc, noise1_layers):
+    """w2xc_debug_fill_scratch (the test aid behind tests/test_gpu_scratch_poison.py): null model / null byte count are ERR_ARG before a
+    device is looked for, and *bytes is written (0) on every later path"""
+    ms = w2xc._ModelSet.from_layers(noise1_layers)
+    lib = w2xc.lib()
+    n = C.c_ulonglong(77)
+    assert lib.w2xc_debug_fill_scratch(None, 0, 0x7FC00000, C.byref(n)) == w2xc.ERR_ARG and n.value == 77
+    assert lib.w2xc_debug_fill_scratch(ms.handle, 0, 0x7FC00000, None) == w2xc.ERR_ARG
+    assert lib.w2xc_debug_fill_scratch(None, -1, 0, None) == w2xc.ERR_ARG
+    if w2xc.device_count() > 0:
+        # no conversion has run on this model: there is no context, none is created, nothing is filled
+        assert ms.fill_scratch(0x7149F2CA, 0) == 0 and ms.fill_scratch(0) == 0
+
+
+def test_fill_scratch_fails_without_gpu(w2xc, noise1_layers):
+    """like every compute entry point: without a HIP device the hook fails with ERR_HIP (for the current device and for a named one)"""
+    if w2xc.device_count() > 0:
+        pytest.skip("a GPU is present; covered by the -m gpu tests")
+    ms = w2xc._ModelSet.from_layers(noise1_layers)
+    lib = w2xc.lib()
+    for dev in (-1, 0):
+        n = C.c_ulonglong(77)
+        assert lib.w2xc_debug_fill_scratch(ms.handle, dev, 0, C.byref(n)) == w2xc.ERR_HIP and n.value == 0
+        with pytest.raises(w2xc.W2xcError) as e:
+            ms.fill_scratch(0x7FC00000, dev)
+        assert e.value.code == w2xc.ERR_HIP
+
+
 def test_arbitrary_model_lists_get_their_own_container(w2xc):
     a = w2xc._ModelSet.from_layers(small_layers([1, 4, 4, 1], 3))
     models = [w2xc.Model(a, i) for i in range(3)]

@@ -29,7 +29,7 @@ def test_batch_symbols_declared_and_exported(w2xc):
         assert hasattr(lib, name), name
         assert name in w2xc.ABI_SYMBOLS
     lib.w2xc_version.restype = C.c_char_p
-    assert lib.w2xc_version().startswith(b"w2xc_hip 0.3")
+    assert lib.w2xc_version().startswith(b"w2xc_hip 0.4")
 
 
 @pytest.fixture(scope="module")

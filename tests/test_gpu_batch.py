@@ -197,3 +197,79 @@ def test_batch_of_64x64_matches_oracle(gpu, ms, layers):
     ref = orc.Oracle(layers)
     for i in range(len(x)):
         assert_close(got[i], ref.convert(x[i]), "plane %d" % i)
+
+
+# ---- image offsets at and past 2^32 bytes: the batch forms move only 64-bit scalar bases (image x stride) ---------------------------------------
+GIB = 1 << 30
+
+
+def need_free_memory(need_bytes, what):
+    """the one route to a skip in the two tests below: a device with less free memory than the test needs plus 4 GiB (not an MI355X: 288 GB)"""
+    free = torch.cuda.mem_get_info()[0]
+    if free < need_bytes + 4 * GIB:
+        pytest.skip("%s needs %.1f GiB of device memory plus 4 GiB of headroom; %.1f GiB are free" % (what, need_bytes / GIB, free / GIB))
+
+
+def test_batch_workspace_blocks_beyond_4gib(gpu, ms, layers):
+    """ONE sub-batch whose per-image workspace blocks reach past 4 GiB in BOTH workspaces: 256 x 256 planes, as many as put the last image's block of
+    the smaller workspace 2^32 + 2^28 bytes in.  Every image has its own seed, so an image offset that wraps at 32 bits lands on ANOTHER image's
+    activations.  Bit-identical to the single-plane calls for every image; image 0, the images whose blocks straddle 2^32 in either workspace and
+    the last image also against the oracle."""
+    h = w = 256
+    plan = ms.plan_rows(w, h, opts=gpu.make_opts(device=0))
+    assert plan.n_bands == 1 and min(plan.workspace_bytes) > 0
+    n = -(-((1 << 32) + (1 << 28)) // int(min(plan.workspace_bytes)))
+    blk = [((int(b) + 3) // 4 + 63) // 64 * 64 * 4 for b in plan.workspace_bytes]   # batch_ws_floats: every image's block on a 256-byte boundary
+    per = sum(blk)
+    mb = 0 if (16384 << 20) // per >= n else (n * per + (1 << 20) - 1) >> 20        # batch_sub_size: all n images in one sub-batch
+    assert all((n - 1) * b >= 1 << 32 for b in blk), (n, blk)
+    need_free_memory(n * per + 2 * n * h * w * 4, "test_batch_workspace_blocks_beyond_4gib")
+    print("n = %d images, workspace blocks %s bytes per image, %.2f GiB of workspace, workspace_mb = %d" % (n, blk, n * per / GIB, mb))
+    x = planes(n, h, w, 5000)
+    try:
+        o = gpu.make_opts(device=0, profile=1, workspace_mb=mb)
+        got = []
+        cnt = launches(gpu, ms, lambda: got.append(batch(gpu, ms, x, opts=o)))
+        got = got[0]
+        assert cnt == [0] + [1] * 6, cnt     # one launch per layer: one sub-batch holds all n images
+        assert np.isfinite(got).all()
+        want = single(gpu, ms, x, opts=gpu.make_opts(device=0, workspace_mb=mb))
+        bad = [i for i in range(n) if not np.array_equal(got[i], want[i])]
+        assert not bad, "images %s differ from the single-plane call (blocks %s bytes)" % (bad, blk)
+        ref = orc.Oracle(layers)
+        for i in sorted({0, n - 1} | {(1 << 32) // b for b in blk}):
+            assert_close(got[i], ref.convert(x[i], njob=8), "image %d" % i)
+    finally:
+        ms.trim()      # (the module's model: do not leave 13 GiB of workspace to the tests that follow)
+
+
+@pytest.mark.parametrize("nn2x", [False, True])
+def test_batch_plane_strides_beyond_4gib(gpu, ms, nn2x):
+    """n = 3 planes of 64 x 80 whose input and output plane strides are 2.2 GiB: plane 1 starts past 2^31 bytes, plane 2 past 2^32.  NaN everywhere
+    outside the planes, in the input buffer too.  Bit-identical to the single calls; the guard is still NaN in a window around every output plane."""
+    n, h, w = 3, 64, 80
+    up = 1 if nn2x else 0
+    H, W = h << up, w << up
+    stride_f = 590558004            # floats: 2.2 GiB, a multiple of 4 floats
+    lead = 4096                     # guard floats in front of plane 0
+    need_free_memory(2 * n * stride_f * 4, "test_batch_plane_strides_beyond_4gib")
+    x = planes(n, h, w, 6000)
+    d_in = d_out = None
+    try:
+        d_in = torch.full((n * stride_f,), float("nan"), dtype=torch.float32, device="cuda")
+        d_out = torch.full((n * stride_f,), float("nan"), dtype=torch.float32, device="cuda")
+        for i in range(n):
+            d_in[lead + i * stride_f: lead + i * stride_f + h * w] = torch.from_numpy(x[i].ravel()).cuda()
+        st = torch.cuda.current_stream()
+        ms.convert_batch_device(n, d_in.data_ptr() + lead * 4, stride_f * 4, w * 4, w, h, d_out.data_ptr() + lead * 4, stride_f * 4, W * 4,
+                                nn2x=nn2x, stream=st.cuda_stream, opts=gpu.make_opts(device=0))
+        st.synchronize()
+        want = single(gpu, ms, x, nn2x)
+        for i in range(n):
+            a = lead + i * stride_f
+            win = d_out[a - lead: a + H * W + lead].cpu().numpy()      # the plane and 4096 floats on either side
+            assert np.array_equal(win[lead: lead + H * W].reshape(H, W), want[i]), "plane %d" % i
+            assert np.isnan(win[:lead]).all() and np.isnan(win[lead + H * W:]).all(), "plane %d: the guard around it was written" % i
+    finally:
+        del d_in, d_out
+        torch.cuda.empty_cache()

@@ -109,6 +109,7 @@ def _load():
         "w2xc_layer_filter": (ci, [vp, ci, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, C.POINTER(Opts)]),
         "w2xc_profile_read": (ci, [vp, ci, C.POINTER(C.c_float), C.POINTER(ci), ci]),
         "w2xc_profile_reset": (None, [vp, ci]),
+        "w2xc_debug_fill_scratch": (ci, [vp, ci, C.c_uint, C.POINTER(C.c_ulonglong)]),
         "w2xc_layer_kernel_name": (C.c_char_p, [vp, ci, C.POINTER(Opts)]),
         "w2xc_device_count": (ci, []),
         "w2xc_last_error": (C.c_char_p, []),
@@ -436,6 +437,15 @@ class _ModelSet:
 
     def profile_reset(self, device=-1):
         _lib.w2xc_profile_reset(self.handle, device)
+
+    def fill_scratch(self, word, device=-1):
+        """Test aid (w2xc_debug_fill_scratch): fill every grow-only scratch buffer of this model's context on `device` with the
+        32-bit `word`; returns the number of bytes filled (0: no context yet)."""
+        n = C.c_ulonglong(0)
+        rc = _lib.w2xc_debug_fill_scratch(self.handle, device, word & 0xFFFFFFFF, C.byref(n))
+        if rc != OK:
+            raise W2xcError(rc, last_error())
+        return n.value
 
 
 class Model:

@@ -187,7 +187,8 @@ int w2xc_set_default_opts(const w2xc_opts *defaults)
 const char *w2xc_last_error(void) { return g_last_error.c_str(); }
 // 0.2: w2xc_opts grew (host_numa; 56 bytes), W2XC_FUSION_FIRST / _LAST, w2xc_opts_init_sized, w2xc_set_default_opts, w2xc_plan_rows; since 0.1 (rounds 3-5)
 // also: W2XC_KERNEL_WINOGRAD = _WINOGRAD32, W2XC_KERNEL_AUTO refused on a minimum-halo row view, `verbose` a bit mask (INTEGRATION.md "ABI history")
-const char *w2xc_version(void) { return "w2xc_hip 0.3 (gfx950)"; }
+// 0.3: w2xc_convert_batch / w2xc_convert_batch_device; 0.4: w2xc_debug_fill_scratch (both additive, no struct change)
+const char *w2xc_version(void) { return "w2xc_hip 0.4 (gfx950)"; }
 
 int w2xc_plan_rows(const w2xc_model *m, int w, int view_y0, int view_h, int plane_h, int row_begin, int row_end, const w2xc_opts *opts, w2xc_row_plan *plan)
 try {
@@ -461,6 +462,65 @@ void w2xc_profile_reset(w2xc_model *m, int device)
     c->pending.clear();
     std::fill(c->layer_ms.begin(), c->layer_ms.end(), 0.0);
     std::fill(c->layer_launches.begin(), c->layer_launches.end(), 0);
+}
+
+// Test aid (tests/test_gpu_scratch_poison.py): every grow-only DATA buffer of the context, whole, so that a kernel which reads what its producer did not
+// write meets `word` and not the previous call's answer.  Synchronisation words stay as they are -- prog_cnt, pipe.pin_flags / flags_epoch, events: they are
+// not data, a wrong value there could only make a launch wait for ever.  Weights and biases are not scratch.
+int w2xc_debug_fill_scratch(w2xc_model *m, int device, unsigned word, unsigned long long *bytes)
+{
+    if (!m || !bytes) return fail(W2XC_ERR_ARG, "null argument");
+    *bytes = 0;
+    if (device < 0) HIP_TRY(hipGetDevice(&device));
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(W2XC_ERR_HIP, "cannot select HIP device %d", device);
+    DevCtx *c = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(m->mu);
+        auto it = m->ctx.find(device);
+        if (it == m->ctx.end()) return W2XC_OK;   // nothing to fill; the context is not created for this
+        c = it->second.get();
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipDeviceSynchronize());
+    unsigned long long total = 0;
+    auto dev_fill = [&](void *p, size_t nbytes) -> int {
+        if (!p || !nbytes) return W2XC_OK;
+        HIP_TRY(hipMemsetD32((hipDeviceptr_t)p, (int)word, nbytes / 4));
+        if (nbytes & 3) HIP_TRY(hipMemsetD8((hipDeviceptr_t)((char *)p + (nbytes & ~(size_t)3)), (unsigned char)word, nbytes & 3));
+        total += nbytes;
+        return W2XC_OK;
+    };
+    auto host_fill = [&](void *p, size_t nbytes) {
+        if (!p || !nbytes) return;
+        unsigned *q = (unsigned *)p;   // (hipHostMalloc: page aligned)
+        for (size_t i = 0; i < nbytes / 4; i++) q[i] = word;
+        for (size_t i = nbytes & ~(size_t)3; i < nbytes; i++) ((unsigned char *)p)[i] = (unsigned char)word;
+        total += nbytes;
+    };
+    int rc = W2XC_OK;
+    FilterCache &fc = c->fc;
+    HostPipe &p = c->pipe;
+    for (int i = 0; i < 2 && !rc; i++) {
+        rc = dev_fill(c->ws[i], c->ws_floats[i] * sizeof(float));
+        if (!rc) rc = dev_fill(fc.planar[i], fc.planar_floats[i] * sizeof(float));
+        if (!rc) rc = dev_fill(fc.nhwc[i], fc.nhwc_floats[i] * sizeof(float));
+    }
+    if (!rc) rc = dev_fill(fc.pad, fc.pad_floats * sizeof(float));
+    if (!rc) rc = dev_fill(fc.pout, fc.pout_floats * sizeof(float));
+    if (!rc) rc = dev_fill(p.d_in, p.d_in_bytes);
+    if (!rc) rc = dev_fill(p.d_out, p.d_out_bytes);
+    if (!rc) rc = dev_fill(c->aux, c->aux_floats * sizeof(float));
+    if (!rc) rc = dev_fill(c->img_io, c->img_io_bytes);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    host_fill(fc.pin, fc.slot_bytes * FilterCache::SLOTS);
+    host_fill(p.pin_in, p.in_slot_bytes * HostPipe::IN_SLOTS);
+    host_fill(p.pin_out, p.out_slot_bytes * HostPipe::OUT_SLOTS);
+    for (int i = 0; i < 2; i++) host_fill(p.pin_band[i], p.band_bytes[i]);
+    fc.res_valid = false;   // the resident copy w2xc_opts.filter_resident promises is gone
+    *bytes = total;
+    return W2XC_OK;
 }
 
 const char *w2xc_layer_kernel_name(const w2xc_model *m, int layer, const w2xc_opts *opts)
