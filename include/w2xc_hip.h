@@ -290,6 +290,34 @@ int w2xc_process_image_u8_ex_device(w2xc_model *noise_model, w2xc_model *scale_m
 int w2xc_process_image_u8_ex(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes,
                              int w, int h, unsigned char *out, size_t out_stride_bytes, int iterations, double shrink_ratio,
                              const w2xc_opts *opts);
+/* Batches: n uint8 images of ONE source size w x h in one call -- the batch forms of w2xc_process_image_u8_ex[_device], for the callers
+ * w2xc_convert_batch names, who hold images and not luma planes.  Every image is 3-channel interleaved uint8 as in the single-image call; the
+ * output images have its final size, (w << iterations) x (h << iterations), then the optional shrink.
+ * out[i] is BYTE-identical to w2xc_process_image_u8_ex[_device] on in[i] with the same models, iterations, shrink_ratio and opts, for every
+ * option set (precisions, named kernels, fusion settings, band_rows, workspace_mb).
+ * A sub-batch of S images is ONE launch per colour / resize stage (uint8 -> YUV; the bicubic 2x of all U and V planes; the shrink of all Y, U
+ * and V planes; YUV -> uint8) and one w2xc_convert_batch_device-style pass per model pass on its S luma planes: one launch per layer on the
+ * default fp32 chain, the single-plane launch sequence per image otherwise.  S = as many images as w2xc_opts.workspace_mb (0 = 16384 MiB)
+ * holds of the pipeline's own memory per image -- the float Y / U / V planes of every level plus the uint8 image in and out -- but no more than
+ * the sub-batch the batched layer chain takes at the call's largest level (its workspace rule, see w2xc_convert_batch), and never less than 1.
+ * The pipeline's memory grows with S, not with n.
+ * n < 1, null pointers (a null in[i] / out[i] too), non-positive sizes, iterations outside 0..4, a shrink_ratio outside [0, 1), a shrink that
+ * leaves an empty image, row strides below 3 x width, output images that overlap each other or an input image, and a model / iteration
+ * combination the single-image call refuses return W2XC_ERR_ARG; a model that does not take one plane to one plane W2XC_ERR_PLANES -- all
+ * before any device is touched.
+ * Device form: image i starts i * *_image_stride_bytes after d_in / d_out (64-bit offsets, no alignment asked), on device opts->device;
+ * enqueued on `hip_stream` and NOT synchronised (asynchronous calls that share a (model, device) share one stream).
+ * Host form: in[i] / out[i] are host images; sub-batches are striped over opts->device_mask and run through the per-device host pipeline of
+ * w2xc_convert_batch -- the upload of sub-batch k + 1, the launches of sub-batch k and the download of sub-batch k - 1 overlap; pageable
+ * images are staged by modelUtility's nJob threads through pinned slots, page-locked ones are DMA'd in place.  Returns when every out[i] is
+ * complete; without a device W2XC_ERR_HIP.  Both models' contexts are locked together for the call, as in the single-image call. */
+int w2xc_process_image_u8_batch_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in,
+                                       size_t in_image_stride_bytes, size_t in_stride_bytes, int w, int h, unsigned char *d_out,
+                                       size_t out_image_stride_bytes, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                       void *hip_stream, const w2xc_opts *opts);
+int w2xc_process_image_u8_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in,
+                                size_t in_stride_bytes, int w, int h, unsigned char *const *out, size_t out_stride_bytes, int iterations,
+                                double shrink_ratio, const w2xc_opts *opts);
 /* the building blocks on contiguous float planes (device pointers): main.cpp:144 on one plane, :75-76, :171-172 */
 int w2xc_resize2x_cubic_device(const float *d_src, int w, int h, float *d_dst, void *hip_stream);
 int w2xc_u8_to_yuv_device(const unsigned char *d_in, size_t in_stride_bytes, int w, int h, float *d_y, float *d_u,

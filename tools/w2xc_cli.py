@@ -4,7 +4,9 @@ libw2xc_hip, for machines without OpenCV.  Same flags (main.cpp:26-60), same mod
 (:83-121, iter = ceil(log2 ratio), shrink iff int(ratio) != 2^iter, :107-114,158-167), same automatic output
 name (:173-189).  Image I/O is PIL instead of cv::imread/imwrite; everything between -- convertTo,
 RGB2YUV on BGR data (Q3), noise pass, nearest/bicubic 2x + CNN, linear shrink, YUV2RGB, saturate to uint8 --
-runs on the GPU in one call (w2xc_process_image_u8_ex)."""
+runs on the GPU in one call (w2xc_process_image_u8_ex).
+Extension: several input files (-i a.png b.png ...).  They are grouped by image size and every group is ONE w2xc_process_image_u8_batch call; each
+output gets its automatic name (-o is for a single input only).  A single input behaves exactly as before."""
 import argparse
 import math
 import os
@@ -41,9 +43,26 @@ def auto_output_name(input_file, mode, noise_level, scale_ratio):
     return name + ".png"
 
 
+def group_inputs(files_with_sizes, mode, noise_level, scale_ratio):
+    """[(file, (width, height)), ...] -> [((width, height), [files], [output names]), ...]: one entry per image size in order of first appearance, the files
+    of a size in the order given; every output under its automatic name.  Pure: no file is opened."""
+    groups = {}
+    for name, size in files_with_sizes:
+        groups.setdefault(tuple(size), []).append(name)
+    return [(size, names, [auto_output_name(f, mode, noise_level, scale_ratio) for f in names]) for size, names in groups.items()]
+
+
+def check_inputs(ap, args):
+    """-o names ONE output file: with several inputs it is refused (argparse's error exit, status 2)"""
+    if len(args.input_file) > 1 and args.output_file != "(auto)":
+        ap.error("-o/--output_file needs a single input file (%d given): several inputs are written under their automatic names" % len(args.input_file))
+    return args
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description="waifu2x reimplementation using libw2xc_hip (MI355X)")
-    ap.add_argument("-i", "--input_file", required=True, help="path to input image file (you should input full path)")
+    ap.add_argument("-i", "--input_file", required=True, nargs="+", action="extend",
+                    help="path to input image file (you should input full path); several files = batches of same-size images")
     ap.add_argument("-o", "--output_file", default="(auto)", help="path to output image file (you should input full path)")
     ap.add_argument("-m", "--mode", default="noise_scale", choices=["noise", "scale", "noise_scale"], help="image processing mode")
     ap.add_argument("--noise_level", type=int, default=1, choices=[1, 2], help="noise reduction level")
@@ -57,13 +76,15 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = check_inputs(ap, ap.parse_args(argv))
     from PIL import Image
     import __graft_entry__ as graft
     w2xc = graft.load_package()
 
-    img = np.asarray(Image.open(args.input_file).convert("RGB"))
-    bgr = np.ascontiguousarray(img[:, :, ::-1])                       # cv::imread(IMREAD_COLOR) order (Q3)
+    def load_bgr(path):
+        return np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB"))[:, :, ::-1])   # cv::imread(IMREAD_COLOR) order (Q3)
+    images = [load_bgr(f) for f in args.input_file]
     w2xc.modelUtility.getInstance().setNumberOfJobs(args.jobs)        # :79
 
     noise = scale = None
@@ -74,18 +95,27 @@ def main(argv=None):
         iterations, shrink = plan_scale(args.scale_ratio)
         scale = w2xc._ModelSet.from_json(os.path.join(args.model_dir, "scale2.0x_model.json"))
         print("start scaling")
+    outs = {}
     if noise is None and iterations == 0 and not shrink:
-        out = bgr                                                      # ratio 1.0 in scale mode: nothing to do
+        outs = dict(zip(args.input_file, images))                      # ratio 1.0 in scale mode: nothing to do
     elif iterations == 0 and noise is None:
         raise SystemExit("scale_ratio %g needs no 2x step; the reference would only shrink, which is not supported without a model pass" % args.scale_ratio)
     else:
         prec = {"fp32": w2xc.PRECISION_FP32, "bf16": w2xc.PRECISION_BF16, "bf16x2": w2xc.PRECISION_BF16X2, "bf16x3": w2xc.PRECISION_BF16X3, "fp16x2": w2xc.PRECISION_FP16X2}[args.precision]
         opts = w2xc.make_opts(precision=prec)      # always explicit: an explicit --precision beats the W2XC_PRECISION env default
-        out = w2xc.process_image_u8(bgr, noise, scale if iterations else None, iterations, opts, shrink)
-    name = args.output_file
-    if name == "(auto)":
-        name = auto_output_name(args.input_file, args.mode, args.noise_level, args.scale_ratio)
-    Image.fromarray(np.ascontiguousarray(out[:, :, ::-1])).save(name)
+        if len(images) == 1:
+            outs[args.input_file[0]] = w2xc.process_image_u8(images[0], noise, scale if iterations else None, iterations, opts, shrink)
+        else:
+            by_file = dict(zip(args.input_file, images))
+            sized = [(f, (im.shape[1], im.shape[0])) for f, im in zip(args.input_file, images)]
+            for _, files, _ in group_inputs(sized, args.mode, args.noise_level, args.scale_ratio):   # one batch call per image size
+                res = w2xc.process_image_u8_batch([by_file[f] for f in files], noise, scale if iterations else None, iterations, opts, shrink)
+                outs.update(zip(files, res))
+    for f in args.input_file:
+        name = args.output_file
+        if name == "(auto)":
+            name = auto_output_name(f, args.mode, args.noise_level, args.scale_ratio)
+        Image.fromarray(np.ascontiguousarray(outs[f][:, :, ::-1])).save(name)
     print("process successfully done!")
     return 0
 

@@ -91,6 +91,8 @@ def _load():
         "w2xc_convert_planes_device": (ci, [vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, vp, C.POINTER(Opts)]),
         "w2xc_process_image_u8_ex_device": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.c_double, vp, C.POINTER(Opts)]),
         "w2xc_process_image_u8_ex": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.c_double, C.POINTER(Opts)]),
+        "w2xc_process_image_u8_batch_device": (ci, [vp, vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, ci, C.c_double, vp, C.POINTER(Opts)]),
+        "w2xc_process_image_u8_batch": (ci, [vp, vp, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, ci, C.c_double, C.POINTER(Opts)]),
         "w2xc_process_image_u8_device": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, vp, C.POINTER(Opts)]),
         "w2xc_process_image_u8": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.POINTER(Opts)]),
         "w2xc_scale2x_image_u8_device": (ci, [vp, fp, cs, ci, ci, fp, cs, ci, vp, C.POINTER(Opts)]),
@@ -578,3 +580,58 @@ def process_image_u8(img, noise=None, scale=None, iterations=0, opts=None, shrin
     if rc != OK:
         raise W2xcError(rc, last_error())
     return out
+
+
+def _final_size(w, h, iterations, shrink_ratio):
+    fw, fh = w << iterations, h << iterations
+    if shrink_ratio:
+        fw, fh = int(float(fw * shrink_ratio)), int(float(fh * shrink_ratio))
+    return fw, fh
+
+
+def process_image_u8_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, out=None):
+    """n uint8 images of one size in one call (w2xc_process_image_u8_batch): `imgs` is an (n, h, w, 3) uint8 array or a sequence of equal-shape
+    (h, w, 3) uint8 arrays (ROI views with padded rows are passed as they are, page-locked arrays are DMA'd in place); returns an (n, H, W, 3)
+    uint8 array (or fills `out`, such an array).  Image i is byte-identical to process_image_u8(imgs[i], ...) with the same arguments."""
+    if isinstance(imgs, np.ndarray):
+        if imgs.ndim != 4:
+            raise ValueError("process_image_u8_batch wants an (n, h, w, 3) array or a sequence of h x w x 3 images")
+        imgs = [imgs[i] for i in range(imgs.shape[0])]
+    srcs = [np.asarray(a) for a in imgs]
+    if not srcs:
+        raise ValueError("process_image_u8_batch wants at least one image")
+    for a in srcs:
+        if a.dtype != np.uint8:
+            raise ValueError("process_image_u8_batch wants uint8 images (got %s)" % a.dtype)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError("process_image_u8_batch wants h x w x 3 images (got shape %r)" % (a.shape,))
+    h, w, _ = srcs[0].shape
+    if any(a.shape != (h, w, 3) for a in srcs):
+        raise ValueError("process_image_u8_batch: every image must have the same size (group images by size)")
+    if any(a.strides[1:] != (3, 1) for a in srcs) or len({a.strides[0] for a in srcs}) != 1:
+        srcs = [np.ascontiguousarray(a) for a in srcs]
+    n = len(srcs)
+    fw, fh = _final_size(w, h, iterations, shrink_ratio)
+    if out is None:
+        out = np.empty((n, max(fh, 0), max(fw, 0), 3), np.uint8)
+    elif not isinstance(out, np.ndarray) or out.shape != (n, fh, fw, 3) or out.dtype != np.uint8 or out.strides[2:] != (3, 1):
+        raise ValueError("process_image_u8_batch: `out` must be a uint8 (n, H, W, 3) array with contiguous rows")
+    ip = (C.c_void_p * n)(*[a.ctypes.data for a in srcs])
+    op = (C.c_void_p * n)(*[out[i].ctypes.data for i in range(n)])
+    rc = _lib.w2xc_process_image_u8_batch(noise.handle if noise else None, scale.handle if scale else None, n, ip, srcs[0].strides[0], w, h,
+                                          op, out.strides[1], iterations, float(shrink_ratio), C.byref(opts) if opts is not None else None)
+    if rc != OK:
+        raise W2xcError(rc, last_error())
+    return out
+
+
+def process_image_u8_batch_device(n, d_in, in_image_stride_bytes, in_stride_bytes, w, h, d_out, out_image_stride_bytes, out_stride_bytes,
+                                  noise=None, scale=None, iterations=0, shrink_ratio=0.0, stream=0, opts=None):
+    """Device-pointer image batch (w2xc_process_image_u8_batch_device): n images of w x h x 3 uint8 at d_in + i * in_image_stride_bytes, the
+    outputs at d_out + i * out_image_stride_bytes.  Asynchronous on `stream`."""
+    rc = _lib.w2xc_process_image_u8_batch_device(noise.handle if noise else None, scale.handle if scale else None, n, C.c_void_p(d_in),
+                                                 in_image_stride_bytes, in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes,
+                                                 out_stride_bytes, iterations, float(shrink_ratio), C.c_void_p(stream),
+                                                 C.byref(opts) if opts is not None else None)
+    if rc != OK:
+        raise W2xcError(rc, last_error())

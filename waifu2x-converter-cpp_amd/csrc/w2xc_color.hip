@@ -1,44 +1,77 @@
 // w2xc_color.hip -- row N2 of SURVEY.md 8f: the colour front/back end and the U/V resize of the reference
 // CLI's scale loop (/root/reference/src/main.cpp:74-76,136,144,171-172), so that the whole scale phase of
-// one image runs device-resident.  All three kernels are HBM-streaming (a few bytes per pixel) and keep
+// one image runs device-resident.  All kernels are HBM-streaming (a few bytes per pixel) and keep
 // OpenCV's float evaluation order with unfused mul/add (the file is built with -ffp-contract=off).
+// Every stage is ONE __device__ body per output element (*_px), shared by the one-image kernel and its batch form
+// (w2xc_process_image_u8_batch*): a batch kernel takes its image / plane from blockIdx.y -- uniform per workgroup -- and moves only the
+// 64-bit base pointers by image x stride; the index arithmetic inside an image is the one-image kernel's.
 #include "w2xc_kernels.h"
 
 static __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // main.cpp:75-76 (+ cv::split): convertTo(CV_32F, 1/255) and COLOR_RGB2YUV on the channels AS GIVEN
 // (the reference feeds imread's BGR order, Q3): Y = .299 c0 + .587 c1 + .114 c2, U = (c2-Y)*.492+.5, V = (c0-Y)*.877+.5
+static __device__ __forceinline__ void u8_to_yuv_px(const unsigned char *src, long long stride, int w, long long q, float *y, float *u, float *v)
+{
+    const float s = (float)(1.0 / 255.0);
+    const int r = (int)(q / w), c = (int)(q - (long long)r * w);
+    const unsigned char *p = src + r * stride + (long long)c * 3;
+    const float c0 = (float)p[0] * s, c1 = (float)p[1] * s, c2 = (float)p[2] * s;
+    float Y = c0 * 0.299f;
+    Y = Y + c1 * 0.587f;
+    Y = Y + c2 * 0.114f;
+    y[q] = Y;
+    u[q] = (c2 - Y) * 0.492f + 0.5f;
+    v[q] = (c0 - Y) * 0.877f + 0.5f;
+}
+
 __global__ void __launch_bounds__(256) k_u8_to_yuv(const unsigned char *src, long long stride, int w, int h, float *y, float *u, float *v)
 {
     const long long total = (long long)w * h;
-    const float s = (float)(1.0 / 255.0);
-    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) {
-        const int r = (int)(q / w), c = (int)(q - (long long)r * w);
-        const unsigned char *p = src + r * stride + (long long)c * 3;
-        const float c0 = (float)p[0] * s, c1 = (float)p[1] * s, c2 = (float)p[2] * s;
-        float Y = c0 * 0.299f;
-        Y = Y + c1 * 0.587f;
-        Y = Y + c2 * 0.114f;
-        y[q] = Y;
-        u[q] = (c2 - Y) * 0.492f + 0.5f;
-        v[q] = (c0 - Y) * 0.877f + 0.5f;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) u8_to_yuv_px(src, stride, w, q, y, u, v);
+}
+
+// n images, image i at src + i * img_stride bytes; its planes at y / u / v + i * ps floats
+__global__ void __launch_bounds__(256) k_u8_to_yuv_batch(const unsigned char *src, long long img_stride, long long stride, int w, int h, float *y, float *u,
+                                                         float *v, long long ps, int n)
+{
+    const long long total = (long long)w * h;
+    for (int img = blockIdx.y; img < n; img += gridDim.y) {
+        const unsigned char *s = src + img * img_stride;
+        float *yi = y + img * ps, *ui = u + img * ps, *vi = v + img * ps;
+        for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) u8_to_yuv_px(s, stride, w, q, yi, ui, vi);
     }
 }
 
 // main.cpp:171-172 (+ cv::merge): COLOR_YUV2RGB and convertTo(CV_8U, 255) = saturate(cvRound(v*255))
+static __device__ __forceinline__ void yuv_to_u8_px(const float *y, const float *u, const float *v, int w, long long q, unsigned char *dst, long long stride)
+{
+    const int r = (int)(q / w), c = (int)(q - (long long)r * w);
+    const float Y = y[q], U = u[q] - 0.5f, V = v[q] - 0.5f;
+    float ch[3];
+    ch[2] = Y + U * 2.032f;
+    ch[1] = (Y + U * -0.395f) + V * -0.581f;
+    ch[0] = Y + V * 1.140f;
+    unsigned char *p = dst + r * stride + (long long)c * 3;
+#pragma unroll
+    for (int k = 0; k < 3; k++) p[k] = (unsigned char)clampi(__float2int_rn(ch[k] * 255.0f), 0, 255);   // round half to even
+}
+
 __global__ void __launch_bounds__(256) k_yuv_to_u8(const float *y, const float *u, const float *v, int w, int h, unsigned char *dst, long long stride)
 {
     const long long total = (long long)w * h;
-    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) {
-        const int r = (int)(q / w), c = (int)(q - (long long)r * w);
-        const float Y = y[q], U = u[q] - 0.5f, V = v[q] - 0.5f;
-        float ch[3];
-        ch[2] = Y + U * 2.032f;
-        ch[1] = (Y + U * -0.395f) + V * -0.581f;
-        ch[0] = Y + V * 1.140f;
-        unsigned char *p = dst + r * stride + (long long)c * 3;
-#pragma unroll
-        for (int k = 0; k < 3; k++) p[k] = (unsigned char)clampi(__float2int_rn(ch[k] * 255.0f), 0, 255);   // round half to even
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) yuv_to_u8_px(y, u, v, w, q, dst, stride);
+}
+
+// n images: planes of image i at y / u / v + i * ps floats, its pixels at dst + i * img_stride bytes
+__global__ void __launch_bounds__(256) k_yuv_to_u8_batch(const float *y, const float *u, const float *v, long long ps, int w, int h, unsigned char *dst,
+                                                         long long img_stride, long long stride, int n)
+{
+    const long long total = (long long)w * h;
+    for (int img = blockIdx.y; img < n; img += gridDim.y) {
+        const float *yi = y + img * ps, *ui = u + img * ps, *vi = v + img * ps;
+        unsigned char *d = dst + img * img_stride;
+        for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) yuv_to_u8_px(yi, ui, vi, w, q, d, stride);
     }
 }
 
@@ -53,63 +86,93 @@ static __device__ __forceinline__ void cubic_coeffs(float t, float *c)   // Keys
 
 // main.cpp:144 on one plane: cv::resize(2x, INTER_CUBIC): horizontal pass to float, then vertical pass,
 // taps sx-1..sx+2 clipped to the image.  One thread per output pixel (4 x 4 source taps from L2/L1).
+static __device__ __forceinline__ void resize2x_cubic_px(const float *src, int w, int h, long long q, float *dst)
+{
+    const int W = 2 * w;
+    const int dy = (int)(q / W), dx = (int)(q - (long long)dy * W);
+    const float fx = (float)((dx + 0.5) * 0.5 - 0.5), fy = (float)((dy + 0.5) * 0.5 - 0.5);
+    const int sx = (int)floorf(fx), sy = (int)floorf(fy);
+    float cx[4], cy[4];
+    cubic_coeffs(fx - sx, cx);
+    cubic_coeffs(fy - sy, cy);
+    int xs[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) xs[k] = clampi(sx - 1 + k, 0, w - 1);
+    float rowv[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const float *S = src + (long long)clampi(sy - 1 + j, 0, h - 1) * w;
+        float a = S[xs[0]] * cx[0];
+        a = a + S[xs[1]] * cx[1];
+        a = a + S[xs[2]] * cx[2];
+        a = a + S[xs[3]] * cx[3];
+        rowv[j] = a;
+    }
+    float a = rowv[0] * cy[0];
+    a = a + rowv[1] * cy[1];
+    a = a + rowv[2] * cy[2];
+    a = a + rowv[3] * cy[3];
+    dst[q] = a;
+}
+
 __global__ void __launch_bounds__(256) k_resize2x_cubic(const float *src, int w, int h, float *dst)
 {
-    const int W = 2 * w, H = 2 * h;
-    const long long total = (long long)W * H;
-    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) {
-        const int dy = (int)(q / W), dx = (int)(q - (long long)dy * W);
-        const float fx = (float)((dx + 0.5) * 0.5 - 0.5), fy = (float)((dy + 0.5) * 0.5 - 0.5);
-        const int sx = (int)floorf(fx), sy = (int)floorf(fy);
-        float cx[4], cy[4];
-        cubic_coeffs(fx - sx, cx);
-        cubic_coeffs(fy - sy, cy);
-        int xs[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) xs[k] = clampi(sx - 1 + k, 0, w - 1);
-        float rowv[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const float *S = src + (long long)clampi(sy - 1 + j, 0, h - 1) * w;
-            float a = S[xs[0]] * cx[0];
-            a = a + S[xs[1]] * cx[1];
-            a = a + S[xs[2]] * cx[2];
-            a = a + S[xs[3]] * cx[3];
-            rowv[j] = a;
-        }
-        float a = rowv[0] * cy[0];
-        a = a + rowv[1] * cy[1];
-        a = a + rowv[2] * cy[2];
-        a = a + rowv[3] * cy[3];
-        dst[q] = a;
+    const long long total = 4LL * w * h;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) resize2x_cubic_px(src, w, h, q, dst);
+}
+
+// n planes (the U and the V planes of a sub-batch, adjacent): plane p at src + p * sps, its 2x plane at dst + p * dps (floats)
+__global__ void __launch_bounds__(256) k_resize2x_cubic_batch(const float *src, long long sps, int w, int h, float *dst, long long dps, int n)
+{
+    const long long total = 4LL * w * h;
+    for (int p = blockIdx.y; p < n; p += gridDim.y) {
+        const float *s = src + p * sps;
+        float *d = dst + p * dps;
+        for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) resize2x_cubic_px(s, w, h, q, d);
     }
 }
 
 // main.cpp:158-167 on one plane: cv::resize(Size(dw, dh), INTER_LINEAR): half-pixel centres, the two taps
 // clipped to the image, horizontal pass to float then vertical pass (no antialiasing, like OpenCV).
+static __device__ __forceinline__ void resize_linear_px(const float *src, int sw, int sh, long long q, float *dst, int dw, double scale_x, double scale_y)
+{
+    const int dy = (int)(q / dw), dx = (int)(q - (long long)dy * dw);
+    float fx = (float)((dx + 0.5) * scale_x - 0.5), fy = (float)((dy + 0.5) * scale_y - 0.5);
+    int sx = (int)floorf(fx), sy = (int)floorf(fy);
+    fx -= sx;
+    fy -= sy;
+    if (sx < 0) { fx = 0; sx = 0; }
+    if (sx >= sw - 1) { fx = 0; sx = sw - 1; }
+    if (sy < 0) { fy = 0; sy = 0; }
+    if (sy >= sh - 1) { fy = 0; sy = sh - 1; }
+    const int sx1 = sx + 1 < sw ? sx + 1 : sw - 1, sy1 = sy + 1 < sh ? sy + 1 : sh - 1;
+    const float a0 = 1.f - fx, a1 = fx, b0 = 1.f - fy, b1 = fy;
+    const float *R0 = src + (long long)sy * sw, *R1 = src + (long long)sy1 * sw;
+    float h0 = R0[sx] * a0;
+    h0 = h0 + R0[sx1] * a1;
+    float h1 = R1[sx] * a0;
+    h1 = h1 + R1[sx1] * a1;
+    float a = h0 * b0;
+    a = a + h1 * b1;
+    dst[q] = a;
+}
+
 __global__ void __launch_bounds__(256) k_resize_linear(const float *src, int sw, int sh, float *dst, int dw, int dh, double scale_x, double scale_y)
 {
     const long long total = (long long)dw * dh;
-    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) {
-        const int dy = (int)(q / dw), dx = (int)(q - (long long)dy * dw);
-        float fx = (float)((dx + 0.5) * scale_x - 0.5), fy = (float)((dy + 0.5) * scale_y - 0.5);
-        int sx = (int)floorf(fx), sy = (int)floorf(fy);
-        fx -= sx;
-        fy -= sy;
-        if (sx < 0) { fx = 0; sx = 0; }
-        if (sx >= sw - 1) { fx = 0; sx = sw - 1; }
-        if (sy < 0) { fy = 0; sy = 0; }
-        if (sy >= sh - 1) { fy = 0; sy = sh - 1; }
-        const int sx1 = sx + 1 < sw ? sx + 1 : sw - 1, sy1 = sy + 1 < sh ? sy + 1 : sh - 1;
-        const float a0 = 1.f - fx, a1 = fx, b0 = 1.f - fy, b1 = fy;
-        const float *R0 = src + (long long)sy * sw, *R1 = src + (long long)sy1 * sw;
-        float h0 = R0[sx] * a0;
-        h0 = h0 + R0[sx1] * a1;
-        float h1 = R1[sx] * a0;
-        h1 = h1 + R1[sx1] * a1;
-        float a = h0 * b0;
-        a = a + h1 * b1;
-        dst[q] = a;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) resize_linear_px(src, sw, sh, q, dst, dw, scale_x, scale_y);
+}
+
+// n planes (Y, U and V of a sub-batch): the first ny planes at src_y + p * sps (the Y planes: after a noise pass they do not adjoin U), plane p >= ny at
+// src_uv + (p - ny) * sps; destination plane p at dst + p * dps (floats)
+__global__ void __launch_bounds__(256) k_resize_linear_batch(const float *src_y, const float *src_uv, int ny, long long sps, int sw, int sh, float *dst,
+                                                             long long dps, int dw, int dh, double scale_x, double scale_y, int n)
+{
+    const long long total = (long long)dw * dh;
+    for (int p = blockIdx.y; p < n; p += gridDim.y) {
+        const float *s = p < ny ? src_y + p * sps : src_uv + (p - ny) * sps;
+        float *d = dst + p * dps;
+        for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) resize_linear_px(s, sw, sh, q, d, dw, scale_x, scale_y);
     }
 }
 
@@ -138,5 +201,33 @@ hipError_t w2xc_launch_resize_linear(const float *src, int sw, int sh, float *ds
 {
     hipLaunchKernelGGL(k_resize_linear, dim3(grid_for((long long)dw * dh)), dim3(256), 0, st, src, sw, sh, dst, dw, dh,
                        (double)sw / dw, (double)sh / dh);
+    return hipGetLastError();
+}
+
+// ---- batch forms: grid.y = images / planes (a grid-stride loop inside the kernel covers more than 65535) ----
+static dim3 grid_batch(long long total, int n) { return dim3(grid_for(total), (unsigned)(n > 65535 ? 65535 : n)); }
+
+hipError_t w2xc_launch_u8_to_yuv_batch(const unsigned char *src, size_t img_stride, size_t stride, int w, int h, float *y, float *u, float *v,
+                                       long long ps, int n, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_u8_to_yuv_batch, grid_batch((long long)w * h, n), dim3(256), 0, st, src, (long long)img_stride, (long long)stride, w, h, y, u, v, ps, n);
+    return hipGetLastError();
+}
+hipError_t w2xc_launch_yuv_to_u8_batch(const float *y, const float *u, const float *v, long long ps, int w, int h, unsigned char *dst, size_t img_stride,
+                                       size_t stride, int n, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_yuv_to_u8_batch, grid_batch((long long)w * h, n), dim3(256), 0, st, y, u, v, ps, w, h, dst, (long long)img_stride, (long long)stride, n);
+    return hipGetLastError();
+}
+hipError_t w2xc_launch_resize2x_cubic_batch(const float *src, long long sps, int w, int h, float *dst, long long dps, int n, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_resize2x_cubic_batch, grid_batch(4LL * w * h, n), dim3(256), 0, st, src, sps, w, h, dst, dps, n);
+    return hipGetLastError();
+}
+hipError_t w2xc_launch_resize_linear_batch(const float *src_y, const float *src_uv, int ny, long long sps, int sw, int sh, float *dst, long long dps, int dw,
+                                           int dh, int n, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_resize_linear_batch, grid_batch((long long)dw * dh, n), dim3(256), 0, st, src_y, src_uv, ny, sps, sw, sh, dst, dps, dw, dh,
+                       (double)sw / dw, (double)sh / dh, n);
     return hipGetLastError();
 }

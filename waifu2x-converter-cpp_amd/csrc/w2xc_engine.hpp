@@ -335,4 +335,25 @@ int check_batch_args(const w2xc_model *m, int nimg, int nn2x, int w, int h, size
 // byte ranges [lo, hi) tagged 1 = output, 0 = input (sorted in place): W2XC_ERR_ARG when an output overlaps another output or an input
 int check_batch_overlap(std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> &iv);
 
+// ---- w2xc_host_pipeline.cpp: what the host batch forms share (w2xc_convert_batch: float planes, w2xc_process_image_u8_batch: uint8 images) ----
+int host_devices(const w2xc_opts &o, std::vector<int> *devs);   // the devices of w2xc_opts.device_mask that exist (W2XC_ERR_HIP: none at all)
+// n host images of one size in and out, in BYTES, and the two things the pipeline cannot know
+struct HostBatch {
+    int n = 0;
+    const void *const *in = nullptr;
+    void *const *out = nullptr;
+    size_t in_stride = 0, out_stride = 0;   // the caller's row strides
+    size_t in_row = 0, out_row = 0;         // bytes of one row
+    int in_rows = 0, out_rows = 0;
+    size_t in_img = 0, out_img = 0;         // bytes per image in the device slots (a multiple of 256)
+    // the context(s) of device `dev` and their lock(s); *pipe = the host pipeline (three streams, device slots, pinned rings) the call runs through
+    std::function<int(int dev, std::unique_lock<std::mutex> &l1, std::unique_lock<std::mutex> &l2, HostPipe **pipe)> acquire;
+    // enqueue cnt images din -> dout (device slots, images in_img / out_img bytes apart) on st, no synchronisation; max_sub = the call's largest sub-batch
+    std::function<int(int dev, int cnt, const void *din, void *dout, hipStream_t st, int max_sub)> run;
+};
+// sub-batches of at most `sub` images striped over the devices, one worker thread each: upload of k + 1 || launches of k || download of k - 1
+int batch_host_run(const HostBatch &b, const w2xc_opts &o, int sub);
+// no null image pointer, no output range [out[i], out[i] + out_ext) that overlaps another output or an input (check_batch_overlap)
+int check_batch_host_ptrs(int n, const void *const *in, size_t in_ext, void *const *out, size_t out_ext);
+
 }  // namespace w2xc_eng

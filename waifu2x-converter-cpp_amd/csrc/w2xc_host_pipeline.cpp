@@ -571,12 +571,11 @@ int convert_plane_host(w2xc_model *m, const float *in, size_t in_stride_bytes, i
                                       "banding-invariant results; pass them or choose w2xc_opts.kernel explicitly (W2XC_KERNEL_WINOGRAD32: F(2x2))",
                         in_row0, in_row0 + in_rows, need0, need1);
     }
-    const int ndev_all = w2xc_device_count();
-    if (ndev_all <= 0) return fail(W2XC_ERR_HIP, "no HIP device available (libw2xc_hip has no CPU fallback)");
     std::vector<int> devs;
-    for (int d = 0; d < ndev_all && d < 32; d++)
-        if (o.device_mask == 0 || (o.device_mask >> d) & 1u) devs.push_back(d);
-    if (devs.empty()) return fail(W2XC_ERR_ARG, "device_mask 0x%x selects no available device (%d present)", o.device_mask, ndev_all);
+    {
+        int rc = host_devices(o, &devs);
+        if (rc) return rc;
+    }
     int nd = (int)devs.size();
     // w2xc_opts.host_units = k (test aid): cut the rows into k units, round-robin over the selected devices,
     // so the multi-device arithmetic below can be exercised on a single-GPU box
@@ -648,53 +647,51 @@ int convert_plane_host(w2xc_model *m, const float *in, size_t in_stride_bytes, i
     return W2XC_OK;
 }
 
-// ---- batches of same-size planes from host memory (w2xc_convert_batch) ----
+// ---- batches of same-size images from host memory (w2xc_convert_batch: float planes; w2xc_process_image_u8_batch: uint8 images) ----
 // One device's share: the sub-batches `subs` ([first image, count), in order) of the call.  Device slots 0 / 1 of sub images each for the inputs and the outputs
-// alternate between sub-batches, so that sub-batch j + 1's upload (s_h2d), sub-batch j's layers (s_compute, one launch per layer: run_batch) and sub-batch
-// j - 1's download (s_d2h) overlap; this thread stages the next sub-batch's pageable planes into a pinned slot and stitches the previous one's out of its pinned
-// slot meanwhile.  Page-locked planes are DMA'd in place.  Kernels only ever see device memory: every output leaves by a D2H copy.
-int batch_host_on_device(w2xc_model *m, int dev, int nn2x, const float *const *in, size_t in_stride, int w, int h, float *const *out, size_t out_stride,
-                         const w2xc_opts &o, int copy_threads, const std::vector<std::pair<int, int>> &subs, const std::vector<char> &in_pin,
-                         const std::vector<char> &out_pin)
+// alternate between sub-batches, so that sub-batch j + 1's upload (s_h2d), sub-batch j's launches (s_compute: b.run) and sub-batch j - 1's download (s_d2h)
+// overlap; this thread stages the next sub-batch's pageable images into a pinned slot and stitches the previous one's out of its pinned slot meanwhile.
+// Page-locked images are DMA'd in place.  Kernels only ever see device memory: every output leaves by a D2H copy.
+int batch_host_on_device(const HostBatch &b, int dev, const w2xc_opts &o, int copy_threads, const std::vector<std::pair<int, int>> &subs,
+                         const std::vector<char> &in_pin, const std::vector<char> &out_pin)
 {
     if (subs.empty()) return W2XC_OK;
     HIP_TRY(hipSetDevice(dev));
     NodeAffinity node_guard(dev, o.host_numa == 0);
-    DevCtx *c = nullptr;
-    int rc = get_ctx(m, dev, &c);
+    std::unique_lock<std::mutex> l1, l2;   // (as every entry point: calls that share a (model, device) serialise)
+    HostPipe *pp = nullptr;
+    int rc = b.acquire(dev, l1, l2, &pp);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);   // (as every entry point: calls that share a (model, device) serialise)
-    HostPipe &p = c->pipe;
+    HostPipe &p = *pp;
     if ((rc = pipe_init(p))) return rc;
     for (auto &e : p.ev_batch)
         if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    const int W = w << nn2x, H = h << nn2x;
-    const size_t in_img = ((size_t)w * h + 63) & ~(size_t)63, out_img = ((size_t)W * H + 63) & ~(size_t)63;   // floats per image in the device slots
+    const size_t in_img = b.in_img, out_img = b.out_img;   // bytes per image in the device slots
     int sub = 0;
     bool any_in_pageable = false, any_out_pageable = false;
     for (const auto &sb : subs) {
         sub = std::max(sub, sb.second);
         for (int i = sb.first; i < sb.first + sb.second; i++) { any_in_pageable |= !in_pin[i]; any_out_pageable |= !out_pin[i]; }
     }
-    rc = pipe_reserve(p, 2 * (size_t)sub * in_img * 4, 2 * (size_t)sub * out_img * 4, any_in_pageable ? (size_t)sub * in_img * 4 : 0,
-                      any_out_pageable ? (size_t)sub * out_img * 4 : 0);
+    rc = pipe_reserve(p, 2 * (size_t)sub * in_img, 2 * (size_t)sub * out_img, any_in_pageable ? (size_t)sub * in_img : 0,
+                      any_out_pageable ? (size_t)sub * out_img : 0);
     if (rc) return rc;
-    const size_t in_row = (size_t)w * 4, out_row = (size_t)W * 4;
-    auto stitch = [&](int j) -> int {   // sub-batch j's pageable planes out of its pinned slot, behind its download
+    const size_t in_row = b.in_row, out_row = b.out_row;
+    auto stitch = [&](int j) -> int {   // sub-batch j's pageable images out of its pinned slot, behind its download
         const int os = j % HostPipe::OUT_SLOTS;
         HIP_TRY(hipEventSynchronize(p.ev_out_slot[os]));
         const char *stage = p.pin_out + (size_t)os * p.out_slot_bytes;
         for (int k = 0; k < subs[j].second; k++) {
             const int i = subs[j].first + k;
             if (!out_pin[i])
-                w2xc_host::CopyPool::get().copy_rows((char *)out[i], out_stride, stage + (size_t)k * out_img * 4, out_row, out_row, H, copy_threads);
+                w2xc_host::CopyPool::get().copy_rows((char *)b.out[i], b.out_stride, stage + (size_t)k * out_img, out_row, out_row, b.out_rows, copy_threads);
         }
         return W2XC_OK;
     };
     for (int j = 0; j < (int)subs.size(); j++) {
         const int first = subs[j].first, cnt = subs[j].second, slot = j & 1;
-        float *din = p.d_in + (size_t)slot * sub * in_img, *dout = p.d_out + (size_t)slot * sub * out_img;
-        // ---- upload into device slot `slot` once the layers of sub-batch j - 2 have read it ----
+        char *din = (char *)p.d_in + (size_t)slot * sub * in_img, *dout = (char *)p.d_out + (size_t)slot * sub * out_img;
+        // ---- upload into device slot `slot` once the launches of sub-batch j - 2 have read it ----
         if (j >= 2) HIP_TRY(hipStreamWaitEvent(p.s_h2d, p.ev_batch[slot], 0));
         const int is = j % HostPipe::IN_SLOTS;
         char *stage = any_in_pageable ? p.pin_in + (size_t)is * p.in_slot_bytes : nullptr;
@@ -702,28 +699,28 @@ int batch_host_on_device(w2xc_model *m, int dev, int nn2x, const float *const *i
         for (int k = 0; k < cnt; k++) {
             const int i = first + k;
             if (in_pin[i]) {
-                HIP_TRY(hipMemcpy2DAsync(din + (size_t)k * in_img, in_row, in[i], in_stride, in_row, h, hipMemcpyHostToDevice, p.s_h2d));
+                HIP_TRY(hipMemcpy2DAsync(din + (size_t)k * in_img, in_row, b.in[i], b.in_stride, in_row, b.in_rows, hipMemcpyHostToDevice, p.s_h2d));
             } else {
-                char *st = stage + (size_t)k * in_img * 4;
-                w2xc_host::CopyPool::get().copy_rows(st, in_row, (const char *)in[i], in_stride, in_row, h, copy_threads);
-                HIP_TRY(hipMemcpyAsync(din + (size_t)k * in_img, st, in_row * h, hipMemcpyHostToDevice, p.s_h2d));
+                char *st = stage + (size_t)k * in_img;
+                w2xc_host::CopyPool::get().copy_rows(st, in_row, (const char *)b.in[i], b.in_stride, in_row, b.in_rows, copy_threads);
+                HIP_TRY(hipMemcpyAsync(din + (size_t)k * in_img, st, in_row * b.in_rows, hipMemcpyHostToDevice, p.s_h2d));
             }
         }
         HIP_TRY(hipEventRecord(p.ev_in_slot[is], p.s_h2d));
         HIP_TRY(hipEventRecord(p.ev_input, p.s_h2d));
-        // ---- the layers, behind the upload and behind the download of sub-batch j - 2 out of the same output slot ----
+        // ---- the launches, behind the upload and behind the download of sub-batch j - 2 out of the same output slot ----
         HIP_TRY(hipStreamWaitEvent(p.s_compute, p.ev_input, 0));
         if (j >= 2) HIP_TRY(hipStreamWaitEvent(p.s_compute, p.ev_batch[2 + slot], 0));
-        rc = run_batch(m, c, cnt, nn2x, din, (long long)in_img, (size_t)w, w, h, dout, (long long)out_img, (size_t)W, p.s_compute, o, sub);
+        rc = b.run(dev, cnt, din, dout, p.s_compute, sub);
         if (rc) return rc;
         HIP_TRY(hipEventRecord(p.ev_batch[slot], p.s_compute));
-        // ---- download: page-locked planes in place, the others into pinned slot j % OUT_SLOTS (stitched below, one sub-batch later) ----
+        // ---- download: page-locked images in place, the others into pinned slot j % OUT_SLOTS (stitched below, one sub-batch later) ----
         HIP_TRY(hipStreamWaitEvent(p.s_d2h, p.ev_batch[slot], 0));
         const int os = j % HostPipe::OUT_SLOTS;
         for (int k = 0; k < cnt; k++) {
             const int i = first + k;
-            if (out_pin[i]) HIP_TRY(hipMemcpy2DAsync(out[i], out_stride, dout + (size_t)k * out_img, out_row, out_row, H, hipMemcpyDeviceToHost, p.s_d2h));
-            else HIP_TRY(hipMemcpyAsync(p.pin_out + (size_t)os * p.out_slot_bytes + (size_t)k * out_img * 4, dout + (size_t)k * out_img, out_row * H,
+            if (out_pin[i]) HIP_TRY(hipMemcpy2DAsync(b.out[i], b.out_stride, dout + (size_t)k * out_img, out_row, out_row, b.out_rows, hipMemcpyDeviceToHost, p.s_d2h));
+            else HIP_TRY(hipMemcpyAsync(p.pin_out + (size_t)os * p.out_slot_bytes + (size_t)k * out_img, dout + (size_t)k * out_img, out_row * b.out_rows,
                                         hipMemcpyDeviceToHost, p.s_d2h));
         }
         HIP_TRY(hipEventRecord(p.ev_out_slot[os], p.s_d2h));
@@ -736,55 +733,36 @@ int batch_host_on_device(w2xc_model *m, int dev, int nn2x, const float *const *i
     return W2XC_OK;
 }
 
-int convert_batch_host(w2xc_model *m, int n, int nn2x, const float *const *in, size_t in_stride, int w, int h, float *const *out, size_t out_stride,
-                       const w2xc_opts *opts)
+// the devices a host-pointer call runs on: those of w2xc_opts.device_mask that exist
+int host_devices(const w2xc_opts &o, std::vector<int> *devs)
 {
-    int rc = check_batch_args(m, n, nn2x, w, h, in_stride, out_stride);
-    if (rc) return rc;
-    if (!in || !out) return fail(W2XC_ERR_ARG, "null argument");
-    const int W = w << nn2x, H = h << nn2x;
-    const size_t in_ext = (size_t)(h - 1) * in_stride + (size_t)w * 4, out_ext = (size_t)(H - 1) * out_stride + (size_t)W * 4;
-    {
-        std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> iv;
-        iv.reserve(2 * (size_t)n);
-        for (int i = 0; i < n; i++) {
-            if (!in[i] || !out[i]) return fail(W2XC_ERR_ARG, "null plane pointer (plane %d)", i);
-            iv.push_back({{(uintptr_t)in[i], (uintptr_t)in[i] + in_ext}, 0});
-            iv.push_back({{(uintptr_t)out[i], (uintptr_t)out[i] + out_ext}, 1});
-        }
-        rc = check_batch_overlap(iv);
-        if (rc) return rc;
-    }
-    rc = check_batch_model(m);
-    if (rc) return rc;
-    const w2xc_opts o = resolve_opts(opts);
-    RowPlan P;   // (host arithmetic: the options' errors before any device is touched)
-    rc = plan_rows(m, o, W, H, 0, 0, H, H, 1, false, &P);
-    if (rc) return rc;
     const int ndev_all = w2xc_device_count();
     if (ndev_all <= 0) return fail(W2XC_ERR_HIP, "no HIP device available (libw2xc_hip has no CPU fallback)");
-    std::vector<int> devs;
     for (int d = 0; d < ndev_all && d < 32; d++)
-        if (o.device_mask == 0 || (o.device_mask >> d) & 1u) devs.push_back(d);
-    if (devs.empty()) return fail(W2XC_ERR_ARG, "device_mask 0x%x selects no available device (%d present)", o.device_mask, ndev_all);
-    // sub-batch size: the workspace budget's (as run_batch), at most ~32 MiB of output planes (a pinned slot each), and at least two sub-batches per device
-    // where there are images enough, so that uploads, layers and downloads have something to overlap with
-    int sub = 1 << 20;
-    if (batch_eligible(m, P)) {
-        size_t img_f[2];
-        batch_ws_floats(P, img_f);
-        sub = batch_sub_size(P.o, img_f);
-    }
-    sub = std::min<long long>(sub, std::max<long long>(1, ((long long)32 << 20) / ((long long)W * H * 4)));
+        if (o.device_mask == 0 || (o.device_mask >> d) & 1u) devs->push_back(d);
+    if (devs->empty()) return fail(W2XC_ERR_ARG, "device_mask 0x%x selects no available device (%d present)", o.device_mask, ndev_all);
+    return W2XC_OK;
+}
+
+// What the two host batch forms share behind their argument checks: the device list, sub-batches of at most `sub` images striped over the devices (at least
+// two per device where there are images enough, so that uploads, launches and downloads have something to overlap with), which images are page-locked,
+// one worker thread per device.
+int batch_host_run(const HostBatch &b, const w2xc_opts &o, int sub)
+{
+    std::vector<int> devs;
+    int rc = host_devices(o, &devs);
+    if (rc) return rc;
+    const int n = b.n;
     sub = std::min(sub, std::max(1, (n + 2 * (int)devs.size() - 1) / (2 * (int)devs.size())));
     const int nsub = (n + sub - 1) / sub;
     const int nd = std::min((int)devs.size(), nsub);
     std::vector<std::vector<std::pair<int, int>>> share(nd);   // sub-batches striped over the devices
     for (int j = 0; j < nsub; j++) share[j % nd].push_back({j * sub, std::min(sub, n - j * sub)});
+    const size_t in_ext = (size_t)(b.in_rows - 1) * b.in_stride + b.in_row, out_ext = (size_t)(b.out_rows - 1) * b.out_stride + b.out_row;
     std::vector<char> in_pin(n), out_pin(n);
     for (int i = 0; i < n; i++) {
-        in_pin[i] = host_range_pinned(in[i], in_ext);
-        out_pin[i] = host_range_pinned(out[i], out_ext);
+        in_pin[i] = host_range_pinned(b.in[i], in_ext);
+        out_pin[i] = host_range_pinned(b.out[i], out_ext);
     }
     const int copy_threads = std::max(1, std::min(w2xc_get_jobs(), 32) / nd);
     w2xc_host::CopyPool::get().reserve(std::min(w2xc_get_jobs(), 32) - 1);
@@ -794,7 +772,7 @@ int convert_batch_host(w2xc_model *m, int n, int nn2x, const float *const *in, s
     std::vector<std::string> errs(nd);
     auto worker = [&](int t) {
         try {
-            rcs[t] = batch_host_on_device(m, devs[t], nn2x, in, in_stride, w, h, out, out_stride, o, copy_threads, share[t], in_pin, out_pin);
+            rcs[t] = batch_host_on_device(b, devs[t], o, copy_threads, share[t], in_pin, out_pin);
             if (rcs[t]) errs[t] = g_last_error;
         } catch (const std::bad_alloc &) {
             rcs[t] = W2XC_ERR_NOMEM;
@@ -817,6 +795,68 @@ int convert_batch_host(w2xc_model *m, int n, int nn2x, const float *const *in, s
     for (int t = 0; t < nd; t++)
         if (rcs[t]) { g_last_error = errs[t]; return rcs[t]; }
     return W2XC_OK;
+}
+
+// byte ranges of n host images in / out ([ptr, ptr + ext)): no null pointer, no output that overlaps another output or an input
+int check_batch_host_ptrs(int n, const void *const *in, size_t in_ext, void *const *out, size_t out_ext)
+{
+    std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> iv;
+    iv.reserve(2 * (size_t)n);
+    for (int i = 0; i < n; i++) {
+        if (!in[i] || !out[i]) return fail(W2XC_ERR_ARG, "null plane pointer (plane %d)", i);
+        iv.push_back({{(uintptr_t)in[i], (uintptr_t)in[i] + in_ext}, 0});
+        iv.push_back({{(uintptr_t)out[i], (uintptr_t)out[i] + out_ext}, 1});
+    }
+    return check_batch_overlap(iv);
+}
+
+int convert_batch_host(w2xc_model *m, int n, int nn2x, const float *const *in, size_t in_stride, int w, int h, float *const *out, size_t out_stride,
+                       const w2xc_opts *opts)
+{
+    int rc = check_batch_args(m, n, nn2x, w, h, in_stride, out_stride);
+    if (rc) return rc;
+    if (!in || !out) return fail(W2XC_ERR_ARG, "null argument");
+    const int W = w << nn2x, H = h << nn2x;
+    rc = check_batch_host_ptrs(n, (const void *const *)in, (size_t)(h - 1) * in_stride + (size_t)w * 4, (void *const *)out,
+                               (size_t)(H - 1) * out_stride + (size_t)W * 4);
+    if (rc) return rc;
+    rc = check_batch_model(m);
+    if (rc) return rc;
+    const w2xc_opts o = resolve_opts(opts);
+    RowPlan P;   // (host arithmetic: the options' errors before any device is touched)
+    rc = plan_rows(m, o, W, H, 0, 0, H, H, 1, false, &P);
+    if (rc) return rc;
+    // sub-batch size: the workspace budget's (as run_batch) and at most ~32 MiB of output planes (a pinned slot each)
+    int sub = 1 << 20;
+    if (batch_eligible(m, P)) {
+        size_t img_f[2];
+        batch_ws_floats(P, img_f);
+        sub = batch_sub_size(P.o, img_f);
+    }
+    sub = std::min<long long>(sub, std::max<long long>(1, ((long long)32 << 20) / ((long long)W * H * 4)));
+    HostBatch b;
+    b.n = n;
+    b.in = (const void *const *)in; b.out = (void *const *)out;
+    b.in_stride = in_stride; b.out_stride = out_stride;
+    b.in_row = (size_t)w * 4; b.out_row = (size_t)W * 4;
+    b.in_rows = h; b.out_rows = H;
+    b.in_img = (((size_t)w * h + 63) & ~(size_t)63) * 4; b.out_img = (((size_t)W * H + 63) & ~(size_t)63) * 4;
+    b.acquire = [&](int dev, std::unique_lock<std::mutex> &l1, std::unique_lock<std::mutex> &, HostPipe **pipe) -> int {
+        DevCtx *c = nullptr;
+        int r = get_ctx(m, dev, &c);
+        if (r) return r;
+        l1 = std::unique_lock<std::mutex>(c->mu);
+        *pipe = &c->pipe;
+        return W2XC_OK;
+    };
+    b.run = [&](int dev, int cnt, const void *din, void *dout, hipStream_t st, int max_sub) -> int {
+        DevCtx *c = nullptr;
+        int r = get_ctx(m, dev, &c);
+        if (r) return r;
+        return run_batch(m, c, cnt, nn2x, (const float *)din, (long long)(b.in_img / 4), (size_t)w, w, h, (float *)dout, (long long)(b.out_img / 4), (size_t)W,
+                         st, o, max_sub);
+    };
+    return batch_host_run(b, o, sub);
 }
 
 }  // namespace w2xc_eng

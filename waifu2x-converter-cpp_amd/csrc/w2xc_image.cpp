@@ -68,6 +68,94 @@ int process_image_device(w2xc_model *mn, DevCtx *cn, w2xc_model *msc, DevCtx *cs
     return W2XC_OK;
 }
 
+// ---- batches of same-size images (w2xc_process_image_u8_batch*) ----
+// float planes of ONE image over all levels of the pipeline: what process_image_device allocates, every plane on a 256-byte boundary
+size_t plane_floats(int w, int h) { return ((size_t)w * h + 63) & ~(size_t)63; }
+size_t image_aux_floats(int w, int h, int iterations, double shrink)
+{
+    size_t need = 4 * plane_floats(w, h);
+    for (int i = 1; i <= iterations; i++) need += 3 * plane_floats(w << i, h << i);
+    int fw, fh;
+    final_size(w, h, iterations, shrink, &fw, &fh);
+    if (shrink > 0.0) need += 3 * plane_floats(fw, fh);
+    return need;
+}
+
+// Images per sub-batch: as many as w2xc_opts.workspace_mb holds of the pipeline's own memory per image (the float planes of every level + the uint8 image
+// in and out), at most the sub-batch run_batch takes at the LARGEST level where its batched chain applies (more images would only be cut again there, and
+// the planes of a larger sub-batch would be memory without a launch saved), at least 1.  Also where the options' errors surface (host arithmetic only).
+int image_sub_size(const w2xc_model *mn, const w2xc_model *msc, int w, int h, int iterations, double shrink, const w2xc_opts &o, int *sub)
+{
+    int fw, fh;
+    final_size(w, h, iterations, shrink, &fw, &fh);
+    const size_t budget = (size_t)(o.workspace_mb > 0 ? o.workspace_mb : 16384) << 20;
+    const size_t per = image_aux_floats(w, h, iterations, shrink) * 4 + (size_t)w * 3 * h + (size_t)fw * 3 * fh;
+    size_t k = std::min<size_t>(std::max<size_t>(budget / per, 1), 65535);
+    const w2xc_model *pass[2] = {mn, iterations > 0 ? msc : nullptr};
+    for (int i = 0; i < 2; i++) {
+        if (!pass[i]) continue;
+        const int W = i ? w << iterations : w, H = i ? h << iterations : h;   // (the last scale iteration: the largest planes of the call)
+        RowPlan P;
+        int rc = plan_rows(pass[i], o, W, H, 0, 0, H, H, 1, false, &P);
+        if (rc) return rc;
+        if (batch_eligible(pass[i], P)) {
+            size_t img_f[2];
+            batch_ws_floats(P, img_f);
+            k = std::min<size_t>(k, (size_t)batch_sub_size(P.o, img_f));
+        }
+    }
+    *sub = (int)k;
+    return W2XC_OK;
+}
+
+// process_image_device for a sub-batch of S images (S <= cap, the call's sub-batch size: the planes are sized by cap, not by the call's n).  Per level the
+// planes are S Y planes, S U planes, S V planes, all ps floats apart: the Y planes go to run_batch as they lie, U and V are 2 S adjacent planes for the
+// bicubic launch, Y / U / V 3 S planes for the shrink.  One launch per colour / resize stage; the CNN passes are run_batch's.
+int process_image_batch_device(w2xc_model *mn, DevCtx *cn, w2xc_model *msc, DevCtx *cs, int S, int cap, const unsigned char *d_in, size_t in_img,
+                               size_t in_stride, int w, int h, unsigned char *d_out, size_t out_img, size_t out_stride, int iterations, double shrink,
+                               hipStream_t st, const w2xc_opts &o)
+{
+    DevCtx *c = cs ? cs : cn;
+    const size_t need = image_aux_floats(w, h, iterations, shrink) * (size_t)cap;
+    int fw, fh;
+    final_size(w, h, iterations, shrink, &fw, &fh);
+    if (c->aux_floats < need) {
+        if (c->aux) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->aux)); c->aux = nullptr; c->aux_floats = 0; }
+        hipError_t e = hipMalloc((void **)&c->aux, need * sizeof(float));
+        if (e != hipSuccess) return fail(W2XC_ERR_NOMEM, "hipMalloc(%zu MiB) for the image planes failed: %s", (need * 4) >> 20, hipGetErrorString(e));
+        c->aux_floats = need;
+    }
+    float *base = c->aux;
+    int cw = w, ch = h;
+    long long ps = (long long)plane_floats(cw, ch);
+    float *y = base, *u = y + (size_t)S * ps, *v = u + (size_t)S * ps, *yn = v + (size_t)S * ps;
+    base += 4 * (size_t)cap * ps;
+    HIP_TRY(w2xc_launch_u8_to_yuv_batch(d_in, in_img, in_stride, w, h, y, u, v, ps, S, st));               // :75-76
+    if (mn) {                                                                                             // :91-98
+        int rc = run_batch(mn, cn, S, 0, y, ps, (size_t)cw, cw, ch, yn, ps, (size_t)cw, st, o);
+        if (rc) return rc;
+        y = yn;
+    }
+    for (int it = 0; it < iterations; it++) {
+        const int nw = cw * 2, nh = ch * 2;
+        const long long ps2 = (long long)plane_floats(nw, nh);
+        float *y2 = base, *u2 = y2 + (size_t)S * ps2, *v2 = u2 + (size_t)S * ps2;
+        base += 3 * (size_t)cap * ps2;
+        int rc = run_batch(msc, cs, S, 1, y, ps, (size_t)cw, cw, ch, y2, ps2, (size_t)nw, st, o);         // :136-148
+        if (rc) return rc;
+        HIP_TRY(w2xc_launch_resize2x_cubic_batch(u, ps, cw, ch, u2, ps2, 2 * S, st));                      // :144-146 (v = u + S ps, v2 = u2 + S ps2)
+        y = y2; u = u2; v = v2; cw = nw; ch = nh; ps = ps2;
+    }
+    if (shrink > 0.0) {                                                                                   // :158-167
+        const long long pss = (long long)plane_floats(fw, fh);
+        float *ys = base, *us = ys + (size_t)S * pss, *vs = us + (size_t)S * pss;
+        HIP_TRY(w2xc_launch_resize_linear_batch(y, u, S, ps, cw, ch, ys, pss, fw, fh, 3 * S, st));
+        y = ys; u = us; v = vs; cw = fw; ch = fh; ps = pss;
+    }
+    HIP_TRY(w2xc_launch_yuv_to_u8_batch(y, u, v, ps, cw, ch, d_out, out_img, out_stride, S, st));          // :171-172
+    return W2XC_OK;
+}
+
 // Both contexts of a noise + scale call, taken TOGETHER (std::lock's deadlock avoidance): two threads that pass the same two models in opposite
 // roles -- (A as noise, B as scale) and (B as noise, A as scale) -- would otherwise each hold one mutex and wait for the other.
 void lock_contexts(DevCtx *cn, DevCtx *cs, std::unique_lock<std::mutex> &l1, std::unique_lock<std::mutex> &l2)
@@ -111,6 +199,55 @@ int check_image_args(const w2xc_model *m, const void *in, size_t in_stride, int 
     final_size(w, h, iterations, shrink, &fw, &fh);
     if (fw < 1 || fh < 1) return fail(W2XC_ERR_ARG, "shrink_ratio leaves an empty image");
     if (in_stride < (size_t)w * 3 || out_stride < (size_t)fw * 3) return fail(W2XC_ERR_ARG, "row strides must be >= 3*width bytes");
+    return W2XC_OK;
+}
+
+// One host image on device `dev`, synchronously (w2xc_process_image_u8_ex; a batch of one image, which has nothing to overlap with): blocking copies
+// around the pipeline on the null stream.
+int process_image_host(w2xc_model *mn, w2xc_model *msc, const unsigned char *in, size_t in_stride, int w, int h, unsigned char *out, size_t out_stride,
+                       int iterations, double shrink, const w2xc_opts &o, int dev)
+{
+    DeviceGuard guard(dev);
+    if (!guard.ok) return fail(W2XC_ERR_HIP, "cannot select HIP device %d", dev);
+    int W, H;
+    final_size(w, h, iterations, shrink, &W, &H);
+    // contexts of the (up to two) models, locked for the whole call: the device copies of the image live in the owning context
+    // (the scale model's when present) and are kept between calls -- no hipMalloc / hipFree per image
+    DevCtx *cn = nullptr, *cs = nullptr;
+    int rc;
+    if (mn && (rc = get_ctx(mn, dev, &cn))) return rc;
+    if (msc && (rc = get_ctx(msc, dev, &cs))) return rc;
+    std::unique_lock<std::mutex> l1, l2;
+    lock_contexts(cn, cs, l1, l2);
+    DevCtx *c = cs ? cs : cn;
+    const size_t in_bytes = ((size_t)w * 3 * h + 255) & ~(size_t)255, out_bytes = (size_t)W * 3 * H;
+    if (c->img_io_bytes < in_bytes + out_bytes) {
+        if (c->img_io) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->img_io)); c->img_io = nullptr; c->img_io_bytes = 0; }
+        if (hipMalloc((void **)&c->img_io, in_bytes + out_bytes) != hipSuccess)
+            return fail(W2XC_ERR_NOMEM, "hipMalloc(%zu MiB) for the image failed", (in_bytes + out_bytes) >> 20);
+        c->img_io_bytes = in_bytes + out_bytes;
+    }
+    unsigned char *d_in = c->img_io, *d_out = c->img_io + in_bytes;
+    HIP_TRY(hipMemcpy2D(d_in, (size_t)w * 3, in, in_stride, (size_t)w * 3, h, hipMemcpyHostToDevice));
+    rc = process_image_device(mn, cn, msc, cs, d_in, (size_t)w * 3, w, h, d_out, (size_t)W * 3, iterations, shrink, nullptr, o);
+    if (rc) { hipDeviceSynchronize(); return rc; }
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy2D(out, out_stride, d_out, (size_t)W * 3, (size_t)W * 3, H, hipMemcpyDeviceToHost));
+    return W2XC_OK;
+}
+
+// what both batch forms refuse before any device is touched (the image pointers are the caller's: checked there)
+int check_image_batch_args(const w2xc_model *mn, const w2xc_model *msc, int n, size_t in_stride, int w, int h, size_t out_stride, int iterations,
+                           double shrink)
+{
+    if (n < 1) return fail(W2XC_ERR_ARG, "batch of %d images", n);
+    int rc = check_process_args(mn, msc, iterations);
+    if (rc) return rc;
+    rc = check_image_args(mn ? mn : msc, &n, in_stride, w, h, &n, out_stride, iterations, shrink);   // (pointers: see above)
+    if (rc) return rc;
+    if (w > (1 << 28) >> iterations || h > (1 << 28) >> iterations) return fail(W2XC_ERR_ARG, "image too large");
+    if (mn && (rc = check_batch_model(mn))) return rc;
+    if (msc && (rc = check_batch_model(msc))) return rc;
     return W2XC_OK;
 }
 
@@ -158,32 +295,7 @@ try {
     const w2xc_opts o = resolve_opts(opts);
     int dev = o.device;
     if (dev < 0) HIP_TRY(hipGetDevice(&dev));
-    DeviceGuard guard(dev);
-    if (!guard.ok) return fail(W2XC_ERR_HIP, "cannot select HIP device %d", dev);
-    int W, H;
-    final_size(w, h, iterations, shrink_ratio, &W, &H);
-    // contexts of the (up to two) models, locked for the whole call: the device copies of the image live in the owning context
-    // (the scale model's when present) and are kept between calls -- no hipMalloc / hipFree per image
-    DevCtx *cn = nullptr, *cs = nullptr;
-    if (noise_model && (rc = get_ctx(noise_model, dev, &cn))) return rc;
-    if (scale_model && (rc = get_ctx(scale_model, dev, &cs))) return rc;
-    std::unique_lock<std::mutex> l1, l2;
-    lock_contexts(cn, cs, l1, l2);
-    DevCtx *c = cs ? cs : cn;
-    const size_t in_bytes = ((size_t)w * 3 * h + 255) & ~(size_t)255, out_bytes = (size_t)W * 3 * H;
-    if (c->img_io_bytes < in_bytes + out_bytes) {
-        if (c->img_io) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->img_io)); c->img_io = nullptr; c->img_io_bytes = 0; }
-        if (hipMalloc((void **)&c->img_io, in_bytes + out_bytes) != hipSuccess)
-            return fail(W2XC_ERR_NOMEM, "hipMalloc(%zu MiB) for the image failed", (in_bytes + out_bytes) >> 20);
-        c->img_io_bytes = in_bytes + out_bytes;
-    }
-    unsigned char *d_in = c->img_io, *d_out = c->img_io + in_bytes;
-    HIP_TRY(hipMemcpy2D(d_in, (size_t)w * 3, in, in_stride_bytes, (size_t)w * 3, h, hipMemcpyHostToDevice));
-    rc = process_image_device(noise_model, cn, scale_model, cs, d_in, (size_t)w * 3, w, h, d_out, (size_t)W * 3, iterations, shrink_ratio, nullptr, o);
-    if (rc) { hipDeviceSynchronize(); return rc; }
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy2D(out, out_stride_bytes, d_out, (size_t)W * 3, (size_t)W * 3, H, hipMemcpyDeviceToHost));
-    return W2XC_OK;
+    return process_image_host(noise_model, scale_model, in, in_stride_bytes, w, h, out, out_stride_bytes, iterations, shrink_ratio, o, dev);
 } W2XC_CATCH_ALL
 
 int w2xc_process_image_u8(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes, int w, int h,
@@ -191,6 +303,97 @@ int w2xc_process_image_u8(w2xc_model *noise_model, w2xc_model *scale_model, cons
 {
     return w2xc_process_image_u8_ex(noise_model, scale_model, in, in_stride_bytes, w, h, out, out_stride_bytes, iterations, 0.0, opts);
 }
+
+// ---- batches of same-size images ----------------------------------------------------------------
+int w2xc_process_image_u8_batch_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in, size_t in_image_stride_bytes,
+                                       size_t in_stride_bytes, int w, int h, unsigned char *d_out, size_t out_image_stride_bytes,
+                                       size_t out_stride_bytes, int iterations, double shrink_ratio, void *hip_stream, const w2xc_opts *opts)
+try {
+    int rc = check_image_batch_args(noise_model, scale_model, n, in_stride_bytes, w, h, out_stride_bytes, iterations, shrink_ratio);
+    if (rc) return rc;
+    if (!d_in || !d_out) return fail(W2XC_ERR_ARG, "null argument");
+    int W, H;
+    final_size(w, h, iterations, shrink_ratio, &W, &H);
+    const size_t in_ext = (size_t)(h - 1) * in_stride_bytes + (size_t)w * 3, out_ext = (size_t)(H - 1) * out_stride_bytes + (size_t)W * 3;
+    if (n > 1 && out_image_stride_bytes < out_ext)
+        return fail(W2XC_ERR_ARG, "output images overlap each other (image stride %zu < %zu bytes)", out_image_stride_bytes, out_ext);
+    {
+        const uintptr_t i0 = (uintptr_t)d_in, i1 = i0 + (size_t)(n - 1) * in_image_stride_bytes + in_ext;
+        const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (size_t)(n - 1) * out_image_stride_bytes + out_ext;
+        if (i0 < o1 && o0 < i1) return fail(W2XC_ERR_ARG, "output images overlap the input images");
+    }
+    const w2xc_opts o = resolve_opts(opts);
+    int sub = 1;
+    if ((rc = image_sub_size(noise_model, scale_model, w, h, iterations, shrink_ratio, o, &sub))) return rc;
+    sub = std::min(sub, n);
+    int dev = o.device;
+    if (dev < 0) HIP_TRY(hipGetDevice(&dev));
+    DeviceGuard guard(dev);
+    if (!guard.ok) return fail(W2XC_ERR_HIP, "cannot select HIP device %d", dev);
+    DevCtx *cn = nullptr, *cs = nullptr;
+    if (noise_model && (rc = get_ctx(noise_model, dev, &cn))) return rc;
+    if (scale_model && (rc = get_ctx(scale_model, dev, &cs))) return rc;
+    std::unique_lock<std::mutex> l1, l2;
+    lock_contexts(cn, cs, l1, l2);
+    for (int b0 = 0; b0 < n; b0 += sub) {
+        rc = process_image_batch_device(noise_model, cn, scale_model, cs, std::min(sub, n - b0), sub, d_in + (size_t)b0 * in_image_stride_bytes,
+                                        in_image_stride_bytes, in_stride_bytes, w, h, d_out + (size_t)b0 * out_image_stride_bytes, out_image_stride_bytes,
+                                        out_stride_bytes, iterations, shrink_ratio, (hipStream_t)hip_stream, o);
+        if (rc) return rc;
+    }
+    return W2XC_OK;
+} W2XC_CATCH_ALL
+
+int w2xc_process_image_u8_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes, int w,
+                                int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio, const w2xc_opts *opts)
+try {
+    int rc = check_image_batch_args(noise_model, scale_model, n, in_stride_bytes, w, h, out_stride_bytes, iterations, shrink_ratio);
+    if (rc) return rc;
+    if (!in || !out) return fail(W2XC_ERR_ARG, "null argument");
+    int W, H;
+    final_size(w, h, iterations, shrink_ratio, &W, &H);
+    rc = check_batch_host_ptrs(n, (const void *const *)in, (size_t)(h - 1) * in_stride_bytes + (size_t)w * 3, (void *const *)out,
+                               (size_t)(H - 1) * out_stride_bytes + (size_t)W * 3);
+    if (rc) return rc;
+    const w2xc_opts o = resolve_opts(opts);
+    if (n == 1) {   // nothing to overlap: the synchronous single-image sequence, on the first device of the mask
+        std::vector<int> devs;
+        if ((rc = host_devices(o, &devs))) return rc;
+        return process_image_host(noise_model, scale_model, in[0], in_stride_bytes, w, h, out[0], out_stride_bytes, iterations, shrink_ratio, o, devs[0]);
+    }
+    int sub = 1;
+    if ((rc = image_sub_size(noise_model, scale_model, w, h, iterations, shrink_ratio, o, &sub))) return rc;
+    HostBatch b;
+    b.n = n;
+    b.in = (const void *const *)in; b.out = (void *const *)out;
+    b.in_stride = in_stride_bytes; b.out_stride = out_stride_bytes;
+    b.in_row = (size_t)w * 3; b.out_row = (size_t)W * 3;
+    b.in_rows = h; b.out_rows = H;
+    b.in_img = (b.in_row * h + 255) & ~(size_t)255; b.out_img = (b.out_row * H + 255) & ~(size_t)255;
+    // both models' contexts, locked together for this device's share of the call; the pipeline is the owning context's (the scale model's when present)
+    auto contexts = [&](int dev, DevCtx **cn, DevCtx **cs) -> int {
+        int r;
+        if (noise_model && (r = get_ctx(noise_model, dev, cn))) return r;
+        if (scale_model && (r = get_ctx(scale_model, dev, cs))) return r;
+        return W2XC_OK;
+    };
+    b.acquire = [&](int dev, std::unique_lock<std::mutex> &l1, std::unique_lock<std::mutex> &l2, HostPipe **pipe) -> int {
+        DevCtx *cn = nullptr, *cs = nullptr;
+        int r = contexts(dev, &cn, &cs);
+        if (r) return r;
+        lock_contexts(cn, cs, l1, l2);
+        *pipe = &(cs ? cs : cn)->pipe;
+        return W2XC_OK;
+    };
+    b.run = [&](int dev, int cnt, const void *din, void *dout, hipStream_t st, int max_sub) -> int {
+        DevCtx *cn = nullptr, *cs = nullptr;
+        int r = contexts(dev, &cn, &cs);
+        if (r) return r;
+        return process_image_batch_device(noise_model, cn, scale_model, cs, cnt, max_sub, (const unsigned char *)din, b.in_img, b.in_row, w, h,
+                                          (unsigned char *)dout, b.out_img, b.out_row, iterations, shrink_ratio, st, o);
+    };
+    return batch_host_run(b, o, sub);
+} W2XC_CATCH_ALL
 
 int w2xc_scale2x_image_u8_device(w2xc_model *m, const unsigned char *d_in, size_t in_stride_bytes, int w, int h, unsigned char *d_out,
                                  size_t out_stride_bytes, int iterations, void *hip_stream, const w2xc_opts *opts)

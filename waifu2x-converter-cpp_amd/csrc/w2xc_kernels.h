@@ -156,3 +156,14 @@ hipError_t w2xc_launch_u8_to_yuv(const unsigned char *src, size_t stride, int w,
 hipError_t w2xc_launch_yuv_to_u8(const float *y, const float *u, const float *v, int w, int h, unsigned char *dst, size_t stride, hipStream_t st);
 hipError_t w2xc_launch_resize2x_cubic(const float *src, int w, int h, float *dst, hipStream_t st);
 hipError_t w2xc_launch_resize_linear(const float *src, int sw, int sh, float *dst, int dw, int dh, hipStream_t st);
+// their batch forms (w2xc_process_image_u8_batch*), one launch for a sub-batch of n images: image i at src / dst + i * img_stride BYTES, the float planes
+// of image (plane) i at base + i * ps FLOATS.  Per output element the arithmetic of the one-image kernels (shared bodies).
+hipError_t w2xc_launch_u8_to_yuv_batch(const unsigned char *src, size_t img_stride, size_t stride, int w, int h, float *y, float *u, float *v,
+                                       long long ps, int n, hipStream_t st);
+hipError_t w2xc_launch_yuv_to_u8_batch(const float *y, const float *u, const float *v, long long ps, int w, int h, unsigned char *dst, size_t img_stride,
+                                       size_t stride, int n, hipStream_t st);
+// n planes src + p * sps -> dst + p * dps (the U and V planes of a sub-batch adjoin: n = 2 x images)
+hipError_t w2xc_launch_resize2x_cubic_batch(const float *src, long long sps, int w, int h, float *dst, long long dps, int n, hipStream_t st);
+// n planes (Y, U, V of a sub-batch: n = 3 x images): plane p < ny at src_y + p * sps, the others at src_uv + (p - ny) * sps; -> dst + p * dps
+hipError_t w2xc_launch_resize_linear_batch(const float *src_y, const float *src_uv, int ny, long long sps, int sw, int sh, float *dst, long long dps, int dw,
+                                           int dh, int n, hipStream_t st);
