@@ -1,9 +1,10 @@
 // conv3x3_wino4 alone: correctness against a double-precision direct sum on sampled outputs (every tile edge included), time per launch, and --
 // with -DW4_TIMING -- where the cycles go (s_memtime stamps of waves 0 and 4 of workgroup 0 after every stage close and every epilogue).
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize [-DW4_TIMING] [-DW4_ABL=n] -I../../waifu2x-converter-cpp_amd/csrc wino4_timing.hip -o wino4_timing
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize [-DW4_TIMING] [-DW4_ABL=n] -I../../waifu2x-converter-cpp_amd/csrc wino4_timing.hip ../../waifu2x-converter-cpp_amd/csrc/w2xc_pack.cpp -o wino4_timing
 //   ./wino4_timing <cin> <cout> [h w [nhwc_out]]
 #include "w2xc_wino4.hip"
 #include <cmath>
+#include <cstring>
 #include <cstdio>
 #include <vector>
 

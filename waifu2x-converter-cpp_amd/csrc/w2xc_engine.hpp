@@ -5,6 +5,10 @@
 //   w2xc_select.cpp         which kernel runs which layer, which layers fuse, the layouts between layers, the band geometry
 //                           (plan_rows) and the launch descriptor of one layer of a band (layer_desc) -- pure host arithmetic:
 //                           unit-tested on the CPU through w2xc_plan_rows
+//   w2xc_pack.cpp           which kernel kind a (cin, cout) layer has, the shape predicates of every kernel family and ALL weight packers
+//                           (w2xc_pack.hpp; no HIP header: tests/cpp/pack_test.cpp builds it with g++ and checks the images).  The kernel
+//                           files (*.hip) hold kernels and their launchers only; w2xc_layout.h = the constants both sides share,
+//                           w2xc_launch.hpp = the large-LDS opt-in and the persistent grid rule of the launchers
 //   w2xc_cuts.hpp           where the chunked launch strategies cut a band's rows (integers only; tests/cpp/cuts_test.cpp)
 //   w2xc_rows.cpp           launch_layer, run_rows (the band loop that replaces convertWithModels / ...Basic / ...BlockSplit,
 //                           src/convertRoutine.cpp:21-169: run_band picks one launch strategy per layer -- prog, tail16, tail32,

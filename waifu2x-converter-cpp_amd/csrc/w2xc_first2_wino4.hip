@@ -28,14 +28,11 @@
 //   Edges       source rows / columns clamped (replicate) in the tile fill; patch columns >= layer 2's input width are zeroed (they only reach
 //               outputs >= out_w), rows beyond it are layer-1 values of clamped source rows (they only reach outputs >= out_h).  Blocks sit on
 //               rows = 0 mod 4 of layer 2's whole output (W2xcConvDesc::wino_py): banding-invariant on run_rows' four-rows-per-layer geometry.
+// Kernels and launchers only: w2xc_first2_wino4_supported and the weight image (w2xc_first2_wino4_pack) are in w2xc_pack.cpp.
 #include "w2xc_kernels.h"
 #include "w2xc_device.h"
+#include "w2xc_launch.hpp"
 #include "w2xc_wino4_math.h"
-
-#include <stdlib.h>
-#include <string.h>
-
-#include <atomic>
 
 #ifndef W4S_ABL
 #define W4S_ABL 0   // timing-only ablations (wrong results): 1 no input transform arithmetic | 2 no layer-1 arithmetic | 4 no MFMAs | 8 no output transform | 16 no stores
@@ -75,32 +72,9 @@ __global__ void __launch_bounds__(256, 2) conv3x3_first2_wino4_batch(W2xcConvDes
 #endif
 
 // ------------------------------------------------------------------------------------------------
-// host side
+// host side (w2xc_first2_wino4_supported and the packer w2xc_first2_wino4_pack: w2xc_pack.cpp)
 // ------------------------------------------------------------------------------------------------
 #if !W2XC_FIRST2_BATCH
-bool w2xc_first2_wino4_supported(int cin1, int cout1, int cout2) { return cin1 == 1 && cout1 == 32 && cout2 == 32; }
-
-// layer 2's weights: wpk[wave g][xi - 9 g][plane tile pt][k-step ks][lane = 16 k + o] = U_xi[plane 16 pt + o][channel 4 ks + k], xi = 6 i + j,
-// U = G g G^T formed in double and rounded once.  w is [32][32][3][3] (modelHandler.cpp:102).  36 * 32 * 32 floats.
-void w2xc_first2_wino4_pack(const float *w, float *dst)
-{
-    const int cin = 32, cout = 32;
-    for (int plane = 0; plane < cout; plane++)
-        for (int c = 0; c < cin; c++) {
-            const float *g = w + ((size_t)plane * cin + c) * 9;
-            double tmp[6][3];
-            for (int i = 0; i < 6; i++)
-                for (int j = 0; j < 3; j++) tmp[i][j] = W2XC_WINO4_G[i][0] * g[0 * 3 + j] + W2XC_WINO4_G[i][1] * g[1 * 3 + j] + W2XC_WINO4_G[i][2] * g[2 * 3 + j];
-            const int pt = plane / 16, o = plane % 16, ks = c / 4, k = c % 4;
-            for (int i = 0; i < 6; i++)
-                for (int j = 0; j < 6; j++) {
-                    const double u = tmp[i][0] * W2XC_WINO4_G[j][0] + tmp[i][1] * W2XC_WINO4_G[j][1] + tmp[i][2] * W2XC_WINO4_G[j][2];
-                    const int xi = 6 * i + j, gw = xi / 9, xl = xi % 9;
-                    dst[((((size_t)gw * 9 + xl) * 2 + pt) * 8 + ks) * 64 + k * 16 + o] = (float)u;
-                }
-        }
-}
-
 // d.in .. in_shift: layer 1's one-plane input (any row stride; in_h / in_w in UPSCALED coordinates when in_shift = 1), off_y / off_x = layer 1's offsets
 // plus layer 2's; d.w1pk / d.bias1 = layer 1's W2XC_K_FIRST image / bias; d.wpk = w2xc_first2_wino4_pack image, d.bias, planar fp32 out (out_ps = 1,
 // 16-byte aligned rows of >= roundup4(out_w) floats), d.out_h / out_w / wino_py = layer 2's region
@@ -115,18 +89,10 @@ hipError_t w2xc_launch_first2_wino4(const W2xcConvDesc &d, hipStream_t stream)
     const int ntiles = tiles_x * tiles_y;
     constexpr size_t lds_bytes = 36 * 2 * 64 * 16 + 12 * 40 * 4 + 32 * 12 * 4;   // V (then M over it): 72 KiB; the source tile; layer 1's weights
     auto kern = conv3x3_first2_wino4;
-    static std::atomic<unsigned long long> attr_done{0};   // function attributes are per device
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    static W2xcLdsOptIn opt_in;   // per (kernel, device)
+    const hipError_t e = opt_in(kern, lds_bytes);
     if (e != hipSuccess) return e;
-    if (dev >= 64 || !((attr_done.load() >> dev) & 1ull)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        if (dev < 64) attr_done.fetch_or(1ull << dev);
-    }
-    int grid = 512;   // two persistent workgroups per CU; a multiple of 8 (one share per XCD)
-    if (grid > ((ntiles + 7) & ~7)) grid = (ntiles + 7) & ~7;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, stream, d, tiles_x, ntiles);
+    hipLaunchKernelGGL(kern, dim3(w2xc_persistent_grid(ntiles, 2)), dim3(256), lds_bytes, stream, d, tiles_x, ntiles);
     return hipGetLastError();
 }
 #endif
@@ -148,18 +114,10 @@ hipError_t w2xc_launch_first2_wino4_batch(const W2xcConvDesc &d, W2xcBatchDesc b
     const int ntiles = (int)(items * b.batch);
     constexpr size_t lds_bytes = 36 * 2 * 64 * 16 + 12 * 40 * 4 + 32 * 12 * 4;   // V (then M over it): 72 KiB; the source tile; layer 1's weights
     auto kern = conv3x3_first2_wino4_batch;
-    static std::atomic<unsigned long long> attr_done{0};   // function attributes are per device
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    static W2xcLdsOptIn opt_in;   // per (kernel, device)
+    const hipError_t e = opt_in(kern, lds_bytes);
     if (e != hipSuccess) return e;
-    if (dev >= 64 || !((attr_done.load() >> dev) & 1ull)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        if (dev < 64) attr_done.fetch_or(1ull << dev);
-    }
-    int grid = 512;   // two persistent workgroups per CU; a multiple of 8 (one share per XCD)
-    if (grid > ((ntiles + 7) & ~7)) grid = (ntiles + 7) & ~7;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, stream, d, tiles_x, ntiles, b);
+    hipLaunchKernelGGL(kern, dim3(w2xc_persistent_grid(ntiles, 2)), dim3(256), lds_bytes, stream, d, tiles_x, ntiles, b);
     return hipGetLastError();
 }
 #endif

@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "w2xc_pack.hpp"   // W2xcKernelKind, the shape predicates and the weight packers (host code without HIP)
+
 struct W2xcConvDesc {
     const float *in;
     float *out;
@@ -70,76 +72,32 @@ struct W2xcBatchDesc {
     long long in_bs, out_bs;
 };
 
-enum W2xcKernelKind {
-    W2XC_K_DIRECT = 0,   // any shape, any strides, reference summation order (VALU)
-    W2XC_K_MFMA = 1,     // cin, cout in {32,64,128}; NHWC in/out; fp32 MFMA implicit GEMM
-    W2XC_K_FIRST = 2,    // cin <= 3 -> cout multiple of 32: planar in, NHWC out, fp32 MFMA (K = 9*cin)
-    W2XC_K_LAST = 3,     // cin multiple of 32 -> cout <= 3: NHWC in, planar out, taps-as-N fp32 MFMA
-    // W2XC_PRECISION_BF16X2 / BF16X3 (and BF16 through the same pipeline): fp32 values carried as d.terms bf16 terms
-    W2XC_K_MID_SPLIT = 7,      // cin, cout in {32,64,128}: term planes in, term planes (or fp32 when out_terms = 0) out
-    W2XC_K_FIRST_SPLIT = 8,    // W2XC_K_FIRST storing d.out_terms term planes
-    W2XC_K_LAST_GATHER = 9,    // sums the partial G planes of a fused W2XC_K_MID_SPLIT (out_terms = 9) into the output plane
-    W2XC_K_FIRST2_SPLIT = 10,  // layers 1 (1 -> 32) and 2 (32 -> {32,64,128}) in one kernel; launched in layer 2's slot
-    W2XC_K_FUSED_AWAY = 11,    // layer 1 when W2XC_K_FIRST2_SPLIT / W2XC_K_FIRST2_WINO4 computes it: no launch
-    W2XC_K_FIRST2_WINO4 = 12,  // fp32: layers 1 (1 -> 32) and 2 (32 -> 32, Winograd F(4x4,3x3)) in one kernel (w2xc_first2_wino4.hip); launched in layer 2's slot
-};
-
-// Which kernel kind the fast path has for a (cin, cout) layer; W2XC_K_DIRECT when none.
-W2xcKernelKind w2xc_pick_kernel(int cin, int cout);
-const char *w2xc_kernel_name(W2xcKernelKind kind, int cin, int cout);
-
-// Size in floats of the packed weight image for `kind`, and the packer (host side).
-// w is [cout][cin][3][3] (index o*cin+i, modelHandler.cpp:102).
-size_t w2xc_packed_weight_floats(W2xcKernelKind kind, int cin, int cout);
-void w2xc_pack_weights(W2xcKernelKind kind, int cin, int cout, const float *w, float *dst);
-
 // Enqueue one layer on `stream`.  Returns hipSuccess or the launch error.
 hipError_t w2xc_launch_conv(W2xcKernelKind kind, const W2xcConvDesc &d, hipStream_t stream);
 
 // Winograd F(2x2, 3x3) on the fp32 MFMA (w2xc_wino.hip): the same layer as W2XC_K_MFMA (NHWC fp32 in / out) with 2.25x fewer MFMAs,
 // for the shapes w2xc_wino_supported() names; d.wpk = the w2xc_wino_pack image (16 * cin * cout floats).
-bool w2xc_wino_supported(int cin, int cout);
-size_t w2xc_wino_packed_floats(int cin, int cout);
-void w2xc_wino_pack(int cin, int cout, const float *w, float *dst);
 hipError_t w2xc_launch_wino(const W2xcConvDesc &d, hipStream_t stream);
 // Winograd F(4x4,3x3) on PLANAR activations (w2xc_wino4.hip): in_ps = 1 / in_cs = plane stride; out planar (out_ps = 1) or NHWC (out_cs = 1, out_ps = cout);
 // d.wpk = the w2xc_wino4_pack image (36 * cin * cout floats), d.wino_py = first output row mod 4, off_x a non-negative multiple of 4
-bool w2xc_wino4_supported(int cin, int cout);
-void w2xc_wino4_pack(int cin, int cout, const float *w, float *dst);
+// d.out_terms = 9: the one-plane LAST layer in conv3x3_wino4's epilogue; d.w7pk = w2xc_wino4_pack_last image, `out` = partial tap planes
+// G[64-plane block][tap][y][x] (out_ts / out_gs / out_rs), finished by W2XC_K_LAST_GATHER with halves = cout / 64
 hipError_t w2xc_launch_wino4(const W2xcConvDesc &d, hipStream_t stream);
 // layers 1 + 2 of the fp32 path in one launch (w2xc_first2_wino4.hip): `in` / in_* / in_h / in_w / in_shift describe LAYER 1's one-plane input, off_y / off_x =
 // layer 1's offsets + layer 2's, w1pk / bias1 = layer 1's W2XC_K_FIRST image and bias; wpk = the w2xc_first2_wino4_pack image (36 * 32 * 32 floats), bias,
 // planar out, out_h / out_w / wino_py (first output row mod 4) = layer 2's region
-bool w2xc_first2_wino4_supported(int cin1, int cout1, int cout2);
-void w2xc_first2_wino4_pack(const float *w, float *dst);
 hipError_t w2xc_launch_first2_wino4(const W2xcConvDesc &d, hipStream_t stream);
-// d.out_terms = 9: the one-plane LAST layer in conv3x3_wino4's epilogue; d.w7pk = w2xc_wino4_pack_last image, `out` = partial tap planes
-// G[64-plane block][tap][y][x] (out_ts / out_gs / out_rs), finished by W2XC_K_LAST_GATHER with halves = cout / 64
-bool w2xc_wino4_prog_supported(int cin, int cout);
-size_t w2xc_wino4_prog_counters(int out_w, int out_h, int wino_py);
-// the job grid of such a launch: tile rows (16 rows each, the first one starting wino_py rows above the region) x groups of 8 tile columns (256 pixels)
-void w2xc_wino4_prog_jobs(int out_w, int out_h, int wino_py, int *tile_rows, int *groups);
 // batch forms (bit-identical per image to the launches above; b.items is set by the launcher): conv3x3_wino4_batch (planar in, planar out or FUSE7, no
-// PROG), conv3x3_first2_wino4_batch, conv3x3_last_gather_x4_batch.  w2xc_wino4_batch_supported: a batch instantiation exists for this layer.
-bool w2xc_wino4_batch_supported(int cin, int cout, bool fused_last);
+// PROG; the layers w2xc_wino4_batch_supported names), conv3x3_first2_wino4_batch, conv3x3_last_gather_x4_batch.
 hipError_t w2xc_launch_wino4_batch(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream);
 hipError_t w2xc_launch_first2_wino4_batch(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream);
 hipError_t w2xc_launch_last_gather_batch(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream);
-size_t w2xc_wino4_pack_last_floats(int cin);
-void w2xc_wino4_pack_last(int cin, const float *w, float *dst);
 
-// split kernels (w2xc_split.hip).  Packed weights of a mid layer: `terms` 16-bit terms of every weight in
-// fragment order; W2XC_K_FIRST_SPLIT uses the W2XC_K_FIRST image.
-int w2xc_split_kg(int terms, int cin);
-size_t w2xc_split_packed_bytes(int cin, int cout, int terms);
-float w2xc_split_pack(int cin, int cout, int terms, int fmt, const float *w, void *dst);   // returns the weight scale (1 for bf16)
+// split kernels (w2xc_split.hip); d.wpk = the w2xc_split_pack image (W2XC_K_FIRST_SPLIT: the W2XC_K_FIRST image)
 hipError_t w2xc_launch_split_mid(const W2xcConvDesc &d, hipStream_t stream);
 hipError_t w2xc_launch_split_first(const W2xcConvDesc &d, hipStream_t stream);
 hipError_t w2xc_launch_first2_split(const W2xcConvDesc &d, hipStream_t stream);
-// last layer fused into a two-term mid layer
-int w2xc_split_halves(int terms, int cout);
-size_t w2xc_split_pack_last_bytes(int cin, int terms);   // terms = 2 (one- and two-term modes) or 3
-float w2xc_split_pack_last(int cin, int terms, int fmt, const float *w, void *dst);
+// last layer fused into a two-term mid layer (d.w7pk = the w2xc_split_pack_last image)
 hipError_t w2xc_launch_last_gather(const W2xcConvDesc &d, hipStream_t stream);
 
 // strided element copy (planar <-> NHWC repack at the Model::filter boundary)

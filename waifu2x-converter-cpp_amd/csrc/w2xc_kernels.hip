@@ -23,21 +23,17 @@
 //                       convertRoutine.cpp:40-46,143-161).  HBM-read bound.
 //
 // fp32 MFMA on gfx950 is an exact k-ordered fmaf chain at the f32 vector rate (157.3 TF peak).
+// Kernels and launchers only: w2xc_pick_kernel and the weight images (w2xc_pack_weights) are in w2xc_pack.cpp.
 #include "w2xc_kernels.h"
 #include "w2xc_device.h"
-
-#include <stdlib.h>
-#include <string.h>
-
-#include <atomic>
-
+#include "w2xc_launch.hpp"
+#include "w2xc_layout.h"
 
 // ------------------------------------------------------------------------------------------------
 // conv3x3_direct: reference-ordered VALU kernel (bit-exact vs the oracle).
 //   weights packed [cin][9][cout8-padded]: for one (i, tap) the 8 output planes of a group are
 //   contiguous and wave-uniform -> scalar loads.
 // ------------------------------------------------------------------------------------------------
-#define DIRECT_CG 8
 __global__ void __launch_bounds__(256) conv3x3_direct(W2xcConvDesc d, int cout_pad)
 {
     const int x = blockIdx.x * 64 + threadIdx.x;
@@ -709,88 +705,8 @@ __global__ void __launch_bounds__(256) repack_kernel(const float *src, long long
 }
 
 // ================================================================================================
-// host side: kernel selection, weight packing, launch
+// host side: launch (kernel selection and the weight packers: w2xc_pack.cpp)
 // ================================================================================================
-static bool is_mid(int c) { return c == 32 || c == 64 || c == 128; }
-
-W2xcKernelKind w2xc_pick_kernel(int cin, int cout)
-{
-    if (is_mid(cin) && is_mid(cout)) return W2XC_K_MFMA;
-    if ((cin == 1 || cin == 3) && is_mid(cout)) return W2XC_K_FIRST;
-    if (is_mid(cin) && (cout == 1 || cout == 3)) return W2XC_K_LAST;
-    return W2XC_K_DIRECT;
-}
-
-const char *w2xc_kernel_name(W2xcKernelKind kind, int cin, int cout)
-{
-    (void)cin; (void)cout;
-    switch (kind) {
-    case W2XC_K_MFMA: return "conv3x3_mfma";
-    case W2XC_K_FIRST: return "conv3x3_first";
-    case W2XC_K_LAST: return "conv3x3_last";
-    case W2XC_K_MID_SPLIT: return "conv3x3_split";
-    case W2XC_K_FIRST_SPLIT: return "conv3x3_first_split";
-    case W2XC_K_LAST_GATHER: return "conv3x3_last_gather";
-    case W2XC_K_FIRST2_SPLIT: return "conv3x3_first2_split";
-    case W2XC_K_FUSED_AWAY: return "(in_next_layer)";
-    case W2XC_K_FIRST2_WINO4: return "conv3x3_first2_wino4";
-    default: return "conv3x3_direct";
-    }
-}
-
-static int direct_cout_pad(int cout) { return (cout + DIRECT_CG - 1) / DIRECT_CG * DIRECT_CG; }
-
-size_t w2xc_packed_weight_floats(W2xcKernelKind kind, int cin, int cout)
-{
-    switch (kind) {
-    case W2XC_K_MFMA: return (size_t)9 * cin * cout;
-    case W2XC_K_FIRST: case W2XC_K_FIRST_SPLIT: return (size_t)(cout / 32) * ((9 * cin + 1) / 2) * 64;
-    case W2XC_K_LAST: return (size_t)(cin / 16) * 4 * ((9 * cout + 15) / 16) * 64;
-    default: return (size_t)cin * 9 * direct_cout_pad(cout);
-    }
-}
-
-void w2xc_pack_weights(W2xcKernelKind kind, int cin, int cout, const float *w, float *dst)
-{
-    auto W = [&](int o, int i, int tap) { return w[((size_t)o * cin + i) * 9 + tap]; };
-    memset(dst, 0, w2xc_packed_weight_floats(kind, cin, cout) * sizeof(float));
-    if (kind == W2XC_K_FIRST_SPLIT) kind = W2XC_K_FIRST;
-    if (kind == W2XC_K_MFMA) {
-        const int nbt = cout / 32, c8n = cin / 8;
-        for (int tap = 0; tap < 9; tap++)
-            for (int c8 = 0; c8 < c8n; c8++)
-                for (int nb = 0; nb < nbt; nb++)
-                    for (int lane = 0; lane < 64; lane++)
-                        for (int j = 0; j < 4; j++) {
-                            const int kk = lane >> 5, n = lane & 31;
-                            dst[((((size_t)tap * c8n + c8) * nbt + nb) * 64 + lane) * 4 + j] =
-                                W(nb * 32 + n, c8 * 8 + kk * 4 + j, tap);
-                        }
-    } else if (kind == W2XC_K_FIRST) {
-        const int nbt = cout / 32, K = 9 * cin, S = (K + 1) / 2;
-        for (int nb = 0; nb < nbt; nb++)
-            for (int s = 0; s < S; s++)
-                for (int lane = 0; lane < 64; lane++) {
-                    const int k = 2 * s + (lane >> 5);
-                    dst[((size_t)nb * S + s) * 64 + lane] = k < K ? W(nb * 32 + (lane & 31), k / 9, k % 9) : 0.0f;
-                }
-    } else if (kind == W2XC_K_LAST) {
-        const int N = 9 * cout, nb16 = (N + 15) / 16, s4n = cin / 16;
-        for (int s4 = 0; s4 < s4n; s4++)
-            for (int j = 0; j < 4; j++)
-                for (int nb = 0; nb < nb16; nb++)
-                    for (int lane = 0; lane < 64; lane++) {
-                        const int n = nb * 16 + (lane & 15), c = 16 * s4 + 4 * (lane >> 4) + j;
-                        dst[(((size_t)s4 * 4 + j) * nb16 + nb) * 64 + lane] = n < N ? W(n % cout, c, n / cout) : 0.0f;
-                    }
-    } else {
-        const int cp = direct_cout_pad(cout);
-        for (int i = 0; i < cin; i++)
-            for (int tap = 0; tap < 9; tap++)
-                for (int o = 0; o < cout; o++) dst[((size_t)i * 9 + tap) * cp + o] = W(o, i, tap);
-    }
-}
-
 template <int CIN, int COUT, int MB, int NB, int WM, int WN>
 static hipError_t launch_mfma2(const W2xcConvDesc &d, hipStream_t stream)
 {
@@ -799,20 +715,10 @@ static hipError_t launch_mfma2(const W2xcConvDesc &d, hipStream_t stream)
     constexpr int NW = WM * WN;
     const size_t lds_bytes = 2 * (size_t)(NW * ((43 + NW) / NW) * 1024) + 4 * (size_t)(4 * (COUT / 32) * 1024);
     auto kern = conv3x3_mfma2<CIN, COUT, MB, NB, WM, WN>;
-    // > 64 KiB of dynamic LDS needs the opt-in attribute, and function attributes are per DEVICE
-    // (the in-process multi-GPU path launches this kernel on several devices from several threads)
-    static std::atomic<unsigned long long> attr_done{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    static W2xcLdsOptIn opt_in;   // per (kernel, device)
+    const hipError_t e = opt_in(kern, lds_bytes);
     if (e != hipSuccess) return e;
-    if (dev >= 64 || !((attr_done.load() >> dev) & 1ull)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        if (dev < 64) attr_done.fetch_or(1ull << dev);
-    }
-    int grid = 256;   // one persistent workgroup per CU; a multiple of 8 (one share per XCD)
-    if (grid > ((ntiles + 7) & ~7)) grid = (ntiles + 7) & ~7;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds_bytes, stream, d, tiles_x, ntiles);
+    hipLaunchKernelGGL(kern, dim3(w2xc_persistent_grid(ntiles)), dim3(NW * 64), lds_bytes, stream, d, tiles_x, ntiles);
     return hipGetLastError();
 }
 

@@ -1,0 +1,60 @@
+// w2xc_pack.hpp -- which kernel a layer gets, and the weight image each kernel reads (w2xc_pack.cpp).  Plain C++: no HIP, nothing here touches the GPU.
+// Every packer takes w as [cout][cin][3][3] (index o*cin+i, modelHandler.cpp:102); the image layouts are stated at the packers and must match the
+// fragment addressing of the kernel named there (shared constants: w2xc_layout.h).  tests/cpp/pack_test.cpp checks them on the CPU.
+#pragma once
+#include <stddef.h>
+
+enum W2xcKernelKind {
+    W2XC_K_DIRECT = 0,   // any shape, any strides, reference summation order (VALU)
+    W2XC_K_MFMA = 1,     // cin, cout in {32,64,128}; NHWC in/out; fp32 MFMA implicit GEMM
+    W2XC_K_FIRST = 2,    // cin <= 3 -> cout multiple of 32: planar in, NHWC out, fp32 MFMA (K = 9*cin)
+    W2XC_K_LAST = 3,     // cin multiple of 32 -> cout <= 3: NHWC in, planar out, taps-as-N fp32 MFMA
+    // W2XC_PRECISION_BF16X2 / BF16X3 (and BF16 through the same pipeline): fp32 values carried as d.terms bf16 terms
+    W2XC_K_MID_SPLIT = 7,      // cin, cout in {32,64,128}: term planes in, term planes (or fp32 when out_terms = 0) out
+    W2XC_K_FIRST_SPLIT = 8,    // W2XC_K_FIRST storing d.out_terms term planes
+    W2XC_K_LAST_GATHER = 9,    // sums the partial G planes of a fused W2XC_K_MID_SPLIT (out_terms = 9) into the output plane
+    W2XC_K_FIRST2_SPLIT = 10,  // layers 1 (1 -> 32) and 2 (32 -> {32,64,128}) in one kernel; launched in layer 2's slot
+    W2XC_K_FUSED_AWAY = 11,    // layer 1 when W2XC_K_FIRST2_SPLIT / W2XC_K_FIRST2_WINO4 computes it: no launch
+    W2XC_K_FIRST2_WINO4 = 12,  // fp32: layers 1 (1 -> 32) and 2 (32 -> 32, Winograd F(4x4,3x3)) in one kernel (w2xc_first2_wino4.hip); launched in layer 2's slot
+};
+
+// Which kernel kind the fast path has for a (cin, cout) layer; W2XC_K_DIRECT when none.
+W2xcKernelKind w2xc_pick_kernel(int cin, int cout);
+const char *w2xc_kernel_name(W2xcKernelKind kind, int cin, int cout);
+
+// Size in floats of the packed weight image for `kind`, and the packer.
+size_t w2xc_packed_weight_floats(W2xcKernelKind kind, int cin, int cout);
+void w2xc_pack_weights(W2xcKernelKind kind, int cin, int cout, const float *w, float *dst);
+
+// conv3x3_wino (Winograd F(2x2,3x3), w2xc_wino.hip): the shapes it exists for, and its image (16 * cin * cout floats)
+bool w2xc_wino_supported(int cin, int cout);
+size_t w2xc_wino_packed_floats(int cin, int cout);
+void w2xc_wino_pack(int cin, int cout, const float *w, float *dst);
+
+// conv3x3_wino4 (Winograd F(4x4,3x3), w2xc_wino4.hip): its image is 36 * cin * cout floats
+bool w2xc_wino4_supported(int cin, int cout);
+void w2xc_wino4_pack(int cin, int cout, const float *w, float *dst);
+// d.out_terms = 9: the one-plane LAST layer in conv3x3_wino4's epilogue reads the w2xc_wino4_pack_last image
+size_t w2xc_wino4_pack_last_floats(int cin);
+void w2xc_wino4_pack_last(int cin, const float *w, float *dst);
+// PROG (the fused launch finishes the last layer itself): the shapes, its counter words, and its job grid: tile rows (16 rows each, the first one
+// starting wino_py rows above the region) x groups of 8 tile columns (256 pixels)
+bool w2xc_wino4_prog_supported(int cin, int cout);
+size_t w2xc_wino4_prog_counters(int out_w, int out_h, int wino_py);
+void w2xc_wino4_prog_jobs(int out_w, int out_h, int wino_py, int *tile_rows, int *groups);
+// a batch instantiation (conv3x3_wino4_batch) exists for this layer
+bool w2xc_wino4_batch_supported(int cin, int cout, bool fused_last);
+
+// conv3x3_first2_wino4 (w2xc_first2_wino4.hip): layer 2's image is 36 * 32 * 32 floats
+bool w2xc_first2_wino4_supported(int cin1, int cout1, int cout2);
+void w2xc_first2_wino4_pack(const float *w, float *dst);
+
+// split kernels (w2xc_split.hip).  Packed weights of a mid layer: `terms` 16-bit terms of every weight in
+// fragment order; W2XC_K_FIRST_SPLIT uses the W2XC_K_FIRST image.
+int w2xc_split_kg(int terms, int cin);
+size_t w2xc_split_packed_bytes(int cin, int cout, int terms);
+float w2xc_split_pack(int cin, int cout, int terms, int fmt, const float *w, void *dst);   // returns the weight scale (1 for bf16)
+// last layer fused into a two-term mid layer
+int w2xc_split_halves(int terms, int cout);
+size_t w2xc_split_pack_last_bytes(int cin, int terms);   // terms = 2 (one- and two-term modes) or 3
+float w2xc_split_pack_last(int cin, int terms, int fmt, const float *w, void *dst);

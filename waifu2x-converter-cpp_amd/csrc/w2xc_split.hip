@@ -9,7 +9,7 @@
 //     T = 3 bf16  (W2XC_PRECISION_BF16X3)  6 products  + a1b1 + a2b0 + a0b2          ~24-bit operands, |err| ~ 2^-24 |ab|,
 //                                                                                    the error level of an fp32 FMA chain
 //     T = 2 fp16  (W2XC_PRECISION_FP16X2, FMT = 1)  3 products                       ~22-bit operands; weights pre-scaled per
-//                 layer by a power of two (w2xc_split_pack), activations clamped to +-65504
+//                 layer by a power of two (w2xc_split_pack, w2xc_pack.cpp), activations clamped to +-65504
 //     (T = 1 compiles but is not instantiated: W2XC_PRECISION_BF16 keeps its own kernels in w2xc_kernels.hip.)
 //
 // Activations between the layers are T "term planes" (`ts` elements apart), each channel-group blocked:
@@ -27,19 +27,28 @@
 //                        one-plane LAST layer is computed in the epilogue from the accumulator registers and its partial
 //                        tap planes go to conv3x3_last_gather.
 //   conv3x3_first_split  cin <= 3 (layer 1) on the fp32 MFMA exactly like conv3x3_first, storing term planes.
+// Kernels and launchers only: the weight images (w2xc_split_pack, w2xc_split_pack_last: the same term split on the host) and w2xc_split_kg / _halves are in w2xc_pack.cpp.
 #include "w2xc_kernels.h"
 #include "w2xc_device.h"
+#include "w2xc_launch.hpp"
 
-#include <stdlib.h>
-#include <math.h>
-#include <string.h>
-
-#include <atomic>
 #include <type_traits>
 
 #ifndef W2XC_SPLIT_T
 #error "compile with -DW2XC_SPLIT_T=1, 2, 3, 4 (= fp16 x 2) or 5 (= 3 terms, fp32 / fused-last out): one object per variant, see the Makefile"
 #endif
+// the per-variant entry points (each defined in its own object) behind the dispatchers of the t3 object
+hipError_t w2xc_launch_split_mid_2(const W2xcConvDesc &d, hipStream_t stream);
+hipError_t w2xc_launch_split_first_2(const W2xcConvDesc &d, hipStream_t stream);
+hipError_t w2xc_launch_split_mid_h(const W2xcConvDesc &d, hipStream_t stream);
+hipError_t w2xc_launch_split_first_h(const W2xcConvDesc &d, hipStream_t stream);
+hipError_t w2xc_launch_split_mid_1(const W2xcConvDesc &d, hipStream_t stream);
+hipError_t w2xc_launch_split_first_1(const W2xcConvDesc &d, hipStream_t stream);
+hipError_t w2xc_launch_split_mid_3x(const W2xcConvDesc &d, hipStream_t stream);
+hipError_t w2xc_launch_first2_1(const W2xcConvDesc &d, hipStream_t stream);
+hipError_t w2xc_launch_first2_2(const W2xcConvDesc &d, hipStream_t stream);
+hipError_t w2xc_launch_first2_h(const W2xcConvDesc &d, hipStream_t stream);
+
 #ifndef W2XC_SPLIT_LATE
 #define W2XC_SPLIT_LATE 4   // MFMAs kept after the last fragment read of a step
 #endif
@@ -79,6 +88,20 @@ template <int HI> static __device__ __forceinline__ float sub_f16(float v, unsig
     return r;
 }
 
+// The term split of a pair (a, b), FMT = 0 bf16 / 1 fp16: pack16 rounds both to nearest even into one packed pair (a -> bits 0..15, b -> bits 16..31),
+// resid16 subtracts the rounded values p back: exact in fp32 (|v - round(v)| fits), the operands of the next term.
+template <int FMT> static __device__ __forceinline__ unsigned pack16(float a, float b) { return FMT ? pk_f16(a, b) : pk_bf16(a, b); }
+template <int FMT> static __device__ __forceinline__ void resid16(float &a, float &b, unsigned p)
+{
+    if (FMT) {
+        a = sub_f16<0>(a, p);
+        b = sub_f16<1>(b, p);
+    } else {
+        a -= __uint_as_float(p << 16);
+        b -= __uint_as_float(p & 0xFFFF0000u);
+    }
+}
+
 // Store 4 consecutive channels of one pixel as OT term planes (OT >= 1) or as fp32 (OT == 0).
 // FMT = 0: bf16 terms (same exponent range as fp32).  FMT = 1: fp16 terms -- values are clamped to the fp16
 // range (+-65504) first; residuals below 2^-14 are held to 2^-25 absolute by fp16's subnormals.
@@ -98,17 +121,11 @@ static __device__ __forceinline__ void store_terms_at(gbyte_t *base, long long t
         }
 #pragma unroll
         for (int t = 0; t < OT; t++) {
-            const unsigned p01 = FMT ? pk_f16(v0, v1) : pk_bf16(v0, v1), p23 = FMT ? pk_f16(v2, v3) : pk_bf16(v2, v3);
+            const unsigned p01 = pack16<FMT>(v0, v1), p23 = pack16<FMT>(v2, v3);
             *(__attribute__((address_space(1))) u32x2 *)(base + (long long)t * ts_bytes) = (u32x2){p01, p23};
-            if (t + 1 < OT) {   // exact residuals: |v - round(v)| fits fp32
-                if (FMT) {
-                    v0 = sub_f16<0>(v0, p01); v1 = sub_f16<1>(v1, p01); v2 = sub_f16<0>(v2, p23); v3 = sub_f16<1>(v3, p23);
-                } else {
-                    v0 -= __uint_as_float(p01 << 16);
-                    v1 -= __uint_as_float(p01 & 0xFFFF0000u);
-                    v2 -= __uint_as_float(p23 << 16);
-                    v3 -= __uint_as_float(p23 & 0xFFFF0000u);
-                }
+            if (t + 1 < OT) {
+                resid16<FMT>(v0, v1, p01);
+                resid16<FMT>(v2, v3, p23);
             }
         }
     }
@@ -128,20 +145,22 @@ static __device__ __forceinline__ void store_terms(float *out, long long elem_of
         }
 #pragma unroll
         for (int t = 0; t < OT; t++) {
-            const unsigned p01 = FMT ? pk_f16(v0, v1) : pk_bf16(v0, v1), p23 = FMT ? pk_f16(v2, v3) : pk_bf16(v2, v3);
+            const unsigned p01 = pack16<FMT>(v0, v1), p23 = pack16<FMT>(v2, v3);
             *reinterpret_cast<u32x2 *>(o16 + (long long)t * out_ts) = (u32x2){p01, p23};
-            if (t + 1 < OT) {   // exact residuals: |v - round(v)| fits fp32
-                if (FMT) {
-                    v0 = sub_f16<0>(v0, p01); v1 = sub_f16<1>(v1, p01); v2 = sub_f16<0>(v2, p23); v3 = sub_f16<1>(v3, p23);
-                } else {
-                    v0 -= __uint_as_float(p01 << 16);
-                    v1 -= __uint_as_float(p01 & 0xFFFF0000u);
-                    v2 -= __uint_as_float(p23 << 16);
-                    v3 -= __uint_as_float(p23 & 0xFFFF0000u);
-                }
+            if (t + 1 < OT) {
+                resid16<FMT>(v0, v1, p01);
+                resid16<FMT>(v2, v3, p23);
             }
         }
     }
+}
+
+// acc + w x: v_mfma_f32_32x32x16_bf16 / _f16 on 16-byte fragments (operands swapped: the weights are the A operand)
+template <int FMT>
+static __device__ __forceinline__ f32x16 mfma16(u32x4 w, u32x4 x, f32x16 acc)
+{
+    if constexpr (FMT == 1) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, w), __builtin_bit_cast(h16x8, x), acc, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), acc, 0, 0, 0);
 }
 
 // term products in issue order: activation term a(i) x weight term b(i)
@@ -453,14 +472,7 @@ __global__ void __launch_bounds__(WM *WN * 64, WM *WN / 4) conv3x3_split(W2xcCon
                 static_for<0, M>([&](auto MI) {
                     constexpr int m = decltype(MI)::value;
                     constexpr int pi = m / Q, j = m % Q, mb = j / NB, nb = j % NB;
-                    if constexpr (FMT == 1)
-                        acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(
-                            __builtin_bit_cast(h16x8, w_cur[Prod<2>::b(pi)][nb]),
-                            __builtin_bit_cast(h16x8, x_cur[Prod<2>::a(pi)][mb]), acc[mb][nb], 0, 0, 0);
-                    else
-                        acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                            __builtin_bit_cast(bf16x8, w_cur[Prod<2>::b(pi)][nb]),
-                            __builtin_bit_cast(bf16x8, x_cur[Prod<2>::a(pi)][mb]), acc[mb][nb], 0, 0, 0);
+                    acc[mb][nb] = mfma16<FMT>(w_cur[Prod<2>::b(pi)][nb], x_cur[Prod<2>::a(pi)][mb], acc[mb][nb]);
                     // fillers of this window that sit behind MFMA j: windows 0 and 2 front-loaded, window 1 spread
                     constexpr int nwin = pi == 0 ? MB + NB : pi == 1 ? n_a + n_b + MB : NB;
                     static_for<0, nwin>([&](auto FI) {
@@ -504,14 +516,7 @@ __global__ void __launch_bounds__(WM *WN * 64, WM *WN / 4) conv3x3_split(W2xcCon
                 static_for<0, M>([&](auto MI) {
                     constexpr int m = decltype(MI)::value;            // MFMA index in the step
                     constexpr int pi = m / (MB * NB), mb = (m / NB) % MB, nb = m % NB;
-                    if constexpr (FMT == 1)
-                        acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(
-                            __builtin_bit_cast(h16x8, w_cur[Prod<T>::b(pi)][nb]),
-                            __builtin_bit_cast(h16x8, x_cur[Prod<T>::a(pi)][mb]), acc[mb][nb], 0, 0, 0);
-                    else
-                        acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                            __builtin_bit_cast(bf16x8, w_cur[Prod<T>::b(pi)][nb]),
-                            __builtin_bit_cast(bf16x8, x_cur[Prod<T>::a(pi)][mb]), acc[mb][nb], 0, 0, 0);
+                    acc[mb][nb] = mfma16<FMT>(w_cur[Prod<T>::b(pi)][nb], x_cur[Prod<T>::a(pi)][mb], acc[mb][nb]);
                     constexpr int f0 = m < D ? (m * F + D - 1) / D : F;
                     constexpr int f1 = m < D ? (((m + 1) * F + D - 1) / D < F ? ((m + 1) * F + D - 1) / D : F) : F;
                     static_for<f0, f1>([&](auto FI) {
@@ -617,26 +622,13 @@ __global__ void __launch_bounds__(WM *WN * 64, WM *WN / 4) conv3x3_split(W2xcCon
                             for (int t = 0; t < LT; t++)
 #pragma unroll
                                 for (int u = 0; u < 4; u++) {
-                                    const unsigned ph = FMT ? pk_f16(a[2 * u], a[2 * u + 1]) : pk_bf16(a[2 * u], a[2 * u + 1]);
+                                    const unsigned ph = pack16<FMT>(a[2 * u], a[2 * u + 1]);
                                     xt[t][u] = ph;
-                                    if (t + 1 < LT) {
-                                        if (FMT) {
-                                            a[2 * u] = sub_f16<0>(a[2 * u], ph);
-                                            a[2 * u + 1] = sub_f16<1>(a[2 * u + 1], ph);
-                                        } else {
-                                            a[2 * u] -= __uint_as_float(ph << 16);
-                                            a[2 * u + 1] -= __uint_as_float(ph & 0xFFFF0000u);
-                                        }
-                                    }
+                                    if (t + 1 < LT) resid16<FMT>(a[2 * u], a[2 * u + 1], ph);
                                 }
                             static_for<0, Prod<LT>::N>([&](auto PI) {
                                 constexpr int pi = decltype(PI)::value;
-                                if constexpr (FMT == 1)
-                                    g = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, w7[Prod<LT>::b(pi)][nb][h]),
-                                                                               __builtin_bit_cast(h16x8, xt[Prod<LT>::a(pi)]), g, 0, 0, 0);
-                                else
-                                    g = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w7[Prod<LT>::b(pi)][nb][h]),
-                                                                                __builtin_bit_cast(bf16x8, xt[Prod<LT>::a(pi)]), g, 0, 0, 0);
+                                g = mfma16<FMT>(w7[Prod<LT>::b(pi)][nb][h], xt[Prod<LT>::a(pi)], g);
                             });
                         }
                     // rows of g held by lane (pixel, kk): registers 0..3 = taps 4kk .. 4kk+3, register 4 = tap 8 (kk = 0)
@@ -859,17 +851,11 @@ __global__ void __launch_bounds__(256) conv3x3_first2_split(W2xcConvDesc d, int 
 #pragma unroll
             for (int c4 = 0; c4 < 4; c4++) {
                 float *q = &v[4 * c4];
-                const unsigned p01 = FMT ? pk_f16(q[0], q[1]) : pk_bf16(q[0], q[1]), p23 = FMT ? pk_f16(q[2], q[3]) : pk_bf16(q[2], q[3]);
+                const unsigned p01 = pack16<FMT>(q[0], q[1]), p23 = pack16<FMT>(q[2], q[3]);
                 *reinterpret_cast<u32x2 *>(ldsb + pbase + t * ACT_TERM + (((unsigned)c4 ^ sw) << 4)) = (u32x2){p01, p23};
                 if (t + 1 < T) {
-                    if (FMT) {
-                        q[0] = sub_f16<0>(q[0], p01); q[1] = sub_f16<1>(q[1], p01); q[2] = sub_f16<0>(q[2], p23); q[3] = sub_f16<1>(q[3], p23);
-                    } else {
-                        q[0] -= __uint_as_float(p01 << 16);
-                        q[1] -= __uint_as_float(p01 & 0xFFFF0000u);
-                        q[2] -= __uint_as_float(p23 << 16);
-                        q[3] -= __uint_as_float(p23 & 0xFFFF0000u);
-                    }
+                    resid16<FMT>(q[0], q[1], p01);
+                    resid16<FMT>(q[2], q[3], p23);
                 }
             }
     }
@@ -942,12 +928,7 @@ __global__ void __launch_bounds__(256) conv3x3_first2_split(W2xcConvDesc d, int 
             for (int mb = 0; mb < MB; mb++)
 #pragma unroll
                 for (int nb = 0; nb < NBT; nb++) {
-                    if constexpr (FMT == 1)
-                        acc2[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, wq[it % PF][Prod<T>::b(pi)][nb]),
-                                                                              __builtin_bit_cast(h16x8, x[Prod<T>::a(pi)][mb]), acc2[mb][nb], 0, 0, 0);
-                    else
-                        acc2[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wq[it % PF][Prod<T>::b(pi)][nb]),
-                                                                               __builtin_bit_cast(bf16x8, x[Prod<T>::a(pi)][mb]), acc2[mb][nb], 0, 0, 0);
+                    acc2[mb][nb] = mfma16<FMT>(wq[it % PF][Prod<T>::b(pi)][nb], x[Prod<T>::a(pi)][mb], acc2[mb][nb]);
                 }
     }
 
@@ -987,9 +968,9 @@ __global__ void __launch_bounds__(256) conv3x3_first2_split(W2xcConvDesc d, int 
 }
 
 // ================================================================================================
-// host side
+// host side: launch (the packers w2xc_split_pack / w2xc_split_pack_last and their size functions: w2xc_pack.cpp)
 // ================================================================================================
-#if W2XC_SPLIT_T == 3   // shared host code lives in one object
+#if W2XC_SPLIT_T == 3   // (the gather kernels live in one object)
 // ---- last layer fused into the epilogue of the two-term kernels (out_terms = 9) ----
 // conv3x3_last_gather: out(y,x) = leaky(bias + sum over taps (ty,tx) and wave-column halves of G[half][tap][y+ty][x+tx]),
 // G = [halves][9][gh][gw] fp32 tap planes as written by conv3x3_split<.., OT = 9>; (gh, gw) = (out_h + 2, out_w + 2).
@@ -1060,127 +1041,6 @@ hipError_t w2xc_launch_last_gather(const W2xcConvDesc &d, hipStream_t stream)
                        d.out_rs, d.out_ps, d.out_h, d.out_w);
     return hipGetLastError();
 }
-
-// wave columns (WN) of the two-term tile shape for `cout` planes = partial-G planes the fused epilogue writes
-int w2xc_split_halves(int terms, int cout) { return terms == 2 ? (cout >= 64 ? 2 : 1) : (cout >= 128 ? 2 : 1); }
-
-size_t w2xc_split_pack_last_bytes(int cin, int terms) { return (size_t)terms * (cin / 32) * 2 * 64 * 8 * 2; }
-
-// w7pk[term < terms][plane block][k-group h][lane][8] = term of S * W[0][c][tap = lane & 31] (0 for taps >= 9), with
-// c = 32*block + 16*h + 4*(lane>>5) + (e < 4 ? e : 4 + e)   -- the channel order of the accumulator registers 8h .. 8h+7.
-// Same scale rule as w2xc_split_pack.  w is [1][cin][3][3].
-float w2xc_split_pack_last(int cin, int terms, int fmt, const float *w, void *dst)
-{
-    auto bf = [](float f) -> unsigned short {
-        unsigned u;
-        memcpy(&u, &f, 4);
-        u += 0x7FFFu + ((u >> 16) & 1u);
-        return (unsigned short)(u >> 16);
-    };
-    auto bf2f = [](unsigned short h) -> float {
-        const unsigned u = (unsigned)h << 16;
-        float f;
-        memcpy(&f, &u, 4);
-        return f;
-    };
-    float scale = 1.0f;
-    if (fmt == 1) {
-        float mx = 0.0f;
-        for (int i = 0; i < 9 * cin; i++) mx = fabsf(w[i]) > mx ? fabsf(w[i]) : mx;
-        if (mx > 0.0f && mx < INFINITY) {
-            int e = 0;
-            frexpf(mx, &e);
-            scale = ldexpf(1.0f, 15 - e);
-        }
-    }
-    const int nbt = cin / 32;
-    unsigned short *d16 = static_cast<unsigned short *>(dst);
-    for (int nb = 0; nb < nbt; nb++)
-        for (int h = 0; h < 2; h++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int e = 0; e < 8; e++) {
-                    const int tap = lane & 31, kk = lane >> 5;
-                    const int c = 32 * nb + 16 * h + 4 * kk + (e < 4 ? e : 4 + e);
-                    float r = tap < 9 ? w[(size_t)c * 9 + tap] * scale : 0.0f;
-                    for (int t = 0; t < terms; t++) {
-                        unsigned short hv;
-                        float back;
-                        if (fmt == 1) {
-                            const _Float16 hf = (_Float16)r;
-                            memcpy(&hv, &hf, 2);
-                            back = (float)hf;
-                        } else {
-                            hv = bf(r);
-                            back = bf2f(hv);
-                        }
-                        d16[((((size_t)t * nbt + nb) * 2 + h) * 64 + lane) * 8 + e] = hv;
-                        r -= back;
-                    }
-                }
-    return scale;
-}
-
-// k-groups (16-channel layout groups) per stage: one for the two/three-term modes; the one-term mode has a third of
-// the MFMAs per byte and takes 64-channel stages to amortise the stage barrier
-int w2xc_split_kg(int terms, int cin) { return terms == 1 ? (cin >= 64 ? 4 : 2) : 1; }
-
-size_t w2xc_split_packed_bytes(int cin, int cout, int terms) { return (size_t)9 * cin * cout * 2 * terms; }
-
-// wpk[tap][slice][term][g][nb][lane][8] (16-bit) = term `term` of S * W[32*nb + (lane&31)][slice*16*KG + 16*g + 8*(lane>>5) + e][tap]
-// fmt 0: bf16 terms, S = 1.  fmt 1: fp16 terms, S = the power of two that puts max|W| into [2^14, 2^15): the low
-// term of every weight down to 2^-17 max|W| is then a NORMAL fp16 number (22 significant bits in two terms).
-// Returns S; the consumer multiplies its accumulators by 1/S (exact).
-float w2xc_split_pack(int cin, int cout, int terms, int fmt, const float *w, void *dst)
-{
-    auto bf = [](float f) -> unsigned short {
-        unsigned u;
-        memcpy(&u, &f, 4);
-        u += 0x7FFFu + ((u >> 16) & 1u);
-        return (unsigned short)(u >> 16);
-    };
-    auto bf2f = [](unsigned short h) -> float {
-        const unsigned u = (unsigned)h << 16;
-        float f;
-        memcpy(&f, &u, 4);
-        return f;
-    };
-    float scale = 1.0f;
-    if (fmt == 1) {
-        float mx = 0.0f;
-        for (size_t i = 0; i < (size_t)9 * cin * cout; i++) mx = fabsf(w[i]) > mx ? fabsf(w[i]) : mx;
-        if (mx > 0.0f && mx < INFINITY) {
-            int e = 0;
-            frexpf(mx, &e);                 // mx = f * 2^e, f in [0.5, 1)
-            scale = ldexpf(1.0f, 15 - e);   // mx * scale in [2^14, 2^15)
-        }
-    }
-    const int kg = w2xc_split_kg(terms, cin), nsl = cin / (16 * kg), nbt = cout / 32;
-    unsigned short *d16 = static_cast<unsigned short *>(dst);
-    for (int tap = 0; tap < 9; tap++)
-        for (int sl = 0; sl < nsl; sl++)
-            for (int nb = 0; nb < nbt; nb++)
-                for (int g = 0; g < kg; g++)
-                    for (int lane = 0; lane < 64; lane++)
-                        for (int e = 0; e < 8; e++) {
-                            const int o = nb * 32 + (lane & 31), c = sl * 16 * kg + 16 * g + 8 * (lane >> 5) + e;
-                            float r = w[((size_t)o * cin + c) * 9 + tap] * scale;   // exact (power of two)
-                            for (int t = 0; t < terms; t++) {
-                                unsigned short h;
-                                float back;
-                                if (fmt == 1) {
-                                    const _Float16 hf = (_Float16)r;                 // round to nearest even
-                                    memcpy(&h, &hf, 2);
-                                    back = (float)hf;
-                                } else {
-                                    h = bf(r);
-                                    back = bf2f(h);
-                                }
-                                d16[((((((size_t)tap * nsl + sl) * terms + t) * kg + g) * nbt + nb) * 64 + lane) * 8 + e] = h;
-                                r -= back;
-                            }
-                        }
-    return scale;
-}
 #endif
 
 template <int CIN, int COUT, int MB, int NB, int WM, int WN, int T, int OT, int KG, int RING, int FMT, int E = 1>
@@ -1195,18 +1055,10 @@ static hipError_t launch_split(const W2xcConvDesc &d, hipStream_t stream)
                                  ((OT == 9 && T == 2 && E == 1) ? 4 * (COUT / 32) * 1024 : (OT == 9 && T == 1) ? 2 * (COUT / 32) * 1024 : 0);
     static_assert(lds_bytes <= 160 * 1024, "LDS budget");
     auto kern = conv3x3_split<CIN, COUT, MB, NB, WM, WN, T, OT, KG, RING, FMT, E>;
-    static std::atomic<unsigned long long> attr_done{0};   // function attributes are per device
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    static W2xcLdsOptIn opt_in;   // per (kernel, device)
+    const hipError_t e = opt_in(kern, lds_bytes);
     if (e != hipSuccess) return e;
-    if (dev >= 64 || !((attr_done.load() >> dev) & 1ull)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        if (dev < 64) attr_done.fetch_or(1ull << dev);
-    }
-    int grid = 256;   // one persistent workgroup per CU; a multiple of 8 (one share per XCD)
-    if (grid > ((ntiles + 7) & ~7)) grid = (ntiles + 7) & ~7;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds_bytes, stream, d, tiles_x, ntiles);
+    hipLaunchKernelGGL(kern, dim3(w2xc_persistent_grid(ntiles)), dim3(NW * 64), lds_bytes, stream, d, tiles_x, ntiles);
     return hipGetLastError();
 }
 
@@ -1256,9 +1108,9 @@ static hipError_t launch_split_t(const W2xcConvDesc &d, hipStream_t stream)
     switch (d.cin * 1000 + d.cout) {
 #ifndef W2XC_SPLIT_DEV   // (development aid: -DW2XC_SPLIT_DEV instantiates 128->128 only)
     //                                     CIN  COUT  MB NB WM WN
-    case 32032: { if constexpr (BIG) return launch_split<32, 32, 4, 1, 4, 1, T, OT, KG, RG, FMT>(d, stream); else return launch_split<32, 32, 4, 1, 4, 1, T, OT, KG, RG, FMT>(d, stream); }
-    case 64032: { if constexpr (BIG) return launch_split<64, 32, 4, 1, 4, 1, T, OT, KG, RG, FMT>(d, stream); else return launch_split<64, 32, 4, 1, 4, 1, T, OT, KG, RG, FMT>(d, stream); }
-    case 128032: { if constexpr (BIG) return launch_split<128, 32, 4, 1, 4, 1, T, OT, KG, RG, FMT>(d, stream); else return launch_split<128, 32, 4, 1, 4, 1, T, OT, KG, RG, FMT>(d, stream); }
+    case 32032: return launch_split<32, 32, 4, 1, 4, 1, T, OT, KG, RG, FMT>(d, stream);
+    case 64032: return launch_split<64, 32, 4, 1, 4, 1, T, OT, KG, RG, FMT>(d, stream);
+    case 128032: return launch_split<128, 32, 4, 1, 4, 1, T, OT, KG, RG, FMT>(d, stream);
     case 32064: { if constexpr (BIG) return launch_split<32, 64, 4, 1, 4, 2, T, OT, KG, RG, FMT>(d, stream); else return launch_split<32, 64, 4, 2, 4, 1, T, OT, KG, RG, FMT>(d, stream); }
     case 64064: { if constexpr (BIG) return launch_split<64, 64, 4, 1, 4, 2, T, OT, KG, RG, FMT>(d, stream); else return launch_split<64, 64, 4, 2, 4, 1, T, OT, KG, RG, FMT>(d, stream); }
     case 128064: { if constexpr (BIG) return launch_split<128, 64, 4, 1, 4, 2, T, OT, KG, RG, FMT>(d, stream); else return launch_split<128, 64, 4, 2, 4, 1, T, OT, KG, RG, FMT>(d, stream); }
@@ -1277,16 +1129,10 @@ static hipError_t launch_first2(const W2xcConvDesc &d, hipStream_t stream)
     const int ntiles = tiles_x * tiles_y;
     constexpr size_t lds_bytes = 2048 + (size_t)T * 11 * 32 * 64;
     auto kern = conv3x3_first2_split<COUT, T, OT, FMT>;
-    if (lds_bytes > 64 * 1024) {   // function attributes are per device
-        static std::atomic<unsigned long long> attr_done{0};
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
+    if (lds_bytes > 64 * 1024) {   // (only the three-term form needs the opt-in)
+        static W2xcLdsOptIn opt_in;   // per (kernel, device)
+        const hipError_t e = opt_in(kern, lds_bytes);
         if (e != hipSuccess) return e;
-        if (dev >= 64 || !((attr_done.load() >> dev) & 1ull)) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-            if (e != hipSuccess) return e;
-            if (dev < 64) attr_done.fetch_or(1ull << dev);
-        }
     }
     hipLaunchKernelGGL(kern, dim3(ntiles), dim3(256), lds_bytes, stream, d, tiles_x, ntiles);
     return hipGetLastError();
@@ -1354,17 +1200,6 @@ hipError_t w2xc_launch_split_mid_h(const W2xcConvDesc &d, hipStream_t stream)
 hipError_t w2xc_launch_split_first_h(const W2xcConvDesc &d, hipStream_t stream) { return launch_first_split_t<2, 1>(d, stream); }
 hipError_t w2xc_launch_first2_h(const W2xcConvDesc &d, hipStream_t stream) { return launch_first2_t<2, 1>(d, stream); }
 #else
-hipError_t w2xc_launch_split_mid_2(const W2xcConvDesc &d, hipStream_t stream);
-hipError_t w2xc_launch_split_first_2(const W2xcConvDesc &d, hipStream_t stream);
-hipError_t w2xc_launch_split_mid_h(const W2xcConvDesc &d, hipStream_t stream);
-hipError_t w2xc_launch_split_first_h(const W2xcConvDesc &d, hipStream_t stream);
-hipError_t w2xc_launch_split_mid_1(const W2xcConvDesc &d, hipStream_t stream);
-hipError_t w2xc_launch_split_first_1(const W2xcConvDesc &d, hipStream_t stream);
-hipError_t w2xc_launch_split_mid_3x(const W2xcConvDesc &d, hipStream_t stream);
-hipError_t w2xc_launch_first2_1(const W2xcConvDesc &d, hipStream_t stream);
-hipError_t w2xc_launch_first2_2(const W2xcConvDesc &d, hipStream_t stream);
-hipError_t w2xc_launch_first2_h(const W2xcConvDesc &d, hipStream_t stream);
-
 // layers 1 + 2 in one kernel (d.terms / d.fmt = format of the layer-1 activations, d.cin = 32)
 hipError_t w2xc_launch_first2_split(const W2xcConvDesc &d, hipStream_t stream)
 {

@@ -31,13 +31,11 @@
 //   Banding    the 2x2 blocks sit on EVEN rows of the layer's whole output (W2xcConvDesc::wino_py): results do not depend on the band origin.
 // Measured (round 2, 2160x3840, profiles/): 128->128 10.4 ms vs 16.9 ms for conv3x3_mfma2 -- 235 TFLOP/s of algorithmic FLOPs, 1.5x the
 // MFMA roofline of a direct convolution, 2/3 of the MFMA peak on the multiplies it really issues; what the rest is, DESIGN.md 3.
+// Kernel and launcher only: w2xc_wino_supported and the weight image (w2xc_wino_pack) are in w2xc_pack.cpp.
 #include "w2xc_kernels.h"
 #include "w2xc_device.h"
+#include "w2xc_launch.hpp"
 
-#include <stdlib.h>
-#include <string.h>
-
-#include <atomic>
 #include <type_traits>
 
 typedef float f32x2v __attribute__((ext_vector_type(2)));
@@ -343,39 +341,8 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino(W2xcConvDesc d, int tiles
 }
 
 // ------------------------------------------------------------------------------------------------
-// host side
+// host side (w2xc_wino_supported and the packer w2xc_wino_pack: w2xc_pack.cpp)
 // ------------------------------------------------------------------------------------------------
-bool w2xc_wino_supported(int cin, int cout)
-{
-    return (cin == 32 || cin == 64 || cin == 128) && (cout == 32 || cout == 64 || cout == 128);
-}
-
-size_t w2xc_wino_packed_floats(int cin, int cout) { return (size_t)16 * cin * cout; }
-
-// wpk[plane block][slice][k-group G][step s][xi / 4][lane][xi % 4] = U_xi[o][c],  U = G g G^T  (G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1]),
-// o = 32*block + (lane & 31), c = 16*slice + 8*(lane >> 5) + 2*G + s.  w is [cout][cin][3][3] (modelHandler.cpp:102); the products with
-// 1/2 and 1/4 are formed in double and rounded once.
-void w2xc_wino_pack(int cin, int cout, const float *w, float *dst)
-{
-    static const double GM[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-    const int nsl = cin / 16, nob = cout / 32;
-    for (int ob = 0; ob < nob; ob++)
-        for (int sl = 0; sl < nsl; sl++)
-            for (int G = 0; G < 4; G++)
-                for (int s = 0; s < 2; s++)
-                    for (int lane = 0; lane < 64; lane++) {
-                        const int o = 32 * ob + (lane & 31), c = 16 * sl + 8 * (lane >> 5) + 2 * G + s;
-                        const float *g = w + ((size_t)o * cin + c) * 9;
-                        double tmp[4][3], U[4][4];
-                        for (int i = 0; i < 4; i++)
-                            for (int j = 0; j < 3; j++) tmp[i][j] = GM[i][0] * g[0 * 3 + j] + GM[i][1] * g[1 * 3 + j] + GM[i][2] * g[2 * 3 + j];
-                        for (int i = 0; i < 4; i++)
-                            for (int j = 0; j < 4; j++) U[i][j] = tmp[i][0] * GM[j][0] + tmp[i][1] * GM[j][1] + tmp[i][2] * GM[j][2];
-                        for (int xi = 0; xi < 16; xi++)
-                            dst[((((((size_t)ob * nsl + sl) * 4 + G) * 2 + s) * 4 + (xi >> 2)) * 64 + lane) * 4 + (xi & 3)] = (float)U[xi >> 2][xi & 3];
-                    }
-}
-
 template <int CIN, int COUT>
 static hipError_t launch_wino(const W2xcConvDesc &d, hipStream_t stream)
 {
@@ -384,18 +351,10 @@ static hipError_t launch_wino(const W2xcConvDesc &d, hipStream_t stream)
     constexpr size_t lds_bytes = 2 * (size_t)(4 * 10 * 1024) + 2 * (size_t)(32 * 1024) + 10 * 1024 + COUT * 4;   // tile + U ring + the DMA offset table + bias
     static_assert(lds_bytes <= 160 * 1024, "LDS budget");
     auto kern = conv3x3_wino<CIN, COUT>;
-    static std::atomic<unsigned long long> attr_done{0};   // function attributes are per device
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    static W2xcLdsOptIn opt_in;   // per (kernel, device)
+    const hipError_t e = opt_in(kern, lds_bytes);
     if (e != hipSuccess) return e;
-    if (dev >= 64 || !((attr_done.load() >> dev) & 1ull)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        if (dev < 64) attr_done.fetch_or(1ull << dev);
-    }
-    int grid = 256;   // one persistent workgroup per CU; a multiple of 8 (one share per XCD)
-    if (grid > ((nitems + 7) & ~7)) grid = (nitems + 7) & ~7;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, stream, d, tiles_x, nitems);
+    hipLaunchKernelGGL(kern, dim3(w2xc_persistent_grid(nitems)), dim3(256), lds_bytes, stream, d, tiles_x, nitems);
     return hipGetLastError();
 }
 

@@ -43,13 +43,14 @@
 // Measured (round 4, 2160x3840, one MI355X): 128 -> 128 6.4-6.8 ms (round 3's NHWC kernel: 7.5 on the same box), frame 14.4-14.9 ms (16.4).  s_memtime: a
 // stage takes ~3350 cycles (2304 = the matrix pipe's time for the 72 MFMAs of a SIMD; a synthetic loop of the same shape without transfers: 2670), an
 // item's boundary another ~8k of its 116k (profiles/r4_sweeps.log).
+// Kernels and launchers only: the shape predicates, PROG's job arithmetic and the weight images (w2xc_wino4_pack, w2xc_wino4_pack_last) are in w2xc_pack.cpp,
+// xi_of in w2xc_layout.h, bt6 / at6 in w2xc_wino4_math.h.
 #include "w2xc_kernels.h"
 #include "w2xc_device.h"
+#include "w2xc_launch.hpp"
+#include "w2xc_layout.h"
+#include "w2xc_wino4_math.h"
 
-#include <stdlib.h>
-#include <string.h>
-
-#include <atomic>
 #include <type_traits>
 
 #ifdef W4_TIMING
@@ -75,37 +76,9 @@ __device__ unsigned long long w4_stamps[2][8192];
 
 namespace {
 
-// y = B^T x for a 6-vector, in place (14 fma / mul / add)
-static __device__ __forceinline__ void bt6(float &x0, float &x1, float &x2, float &x3, float &x4, float &x5)
-{
-    const float y0 = __builtin_fmaf(-2.8125f, x2, __builtin_fmaf(1.265625f, x0, x4));
-    const float p = __builtin_fmaf(-2.25f, x2, x4), q = __builtin_fmaf(-1.6875f, x1, 0.75f * x3);
-    const float u = __builtin_fmaf(-0.5625f, x2, x4), v = __builtin_fmaf(-0.84375f, x1, 1.5f * x3);
-    const float y5 = __builtin_fmaf(-2.8125f, x3, __builtin_fmaf(1.265625f, x1, x5));
-    x0 = y0;
-    x1 = p + q;
-    x2 = p - q;
-    x3 = u + v;
-    x4 = u - v;
-    x5 = y5;
-}
-
-// y = A^T m for a 6-vector (12 fma / mul / add)
-static __device__ __forceinline__ void at6(float m0, float m1, float m2, float m3, float m4, float m5, float &y0, float &y1, float &y2, float &y3)
-{
-    const float s1 = m1 + m2, d1 = m1 - m2, s2 = m3 + m4, d2 = m3 - m4;
-    y0 = m0 + s1 + s2;
-    y1 = __builtin_fmaf(1.5f, d2, 0.75f * d1);
-    y2 = __builtin_fmaf(2.25f, s2, 0.5625f * s1);
-    y3 = __builtin_fmaf(3.375f, d2, __builtin_fmaf(0.421875f, d1, m5));
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // a 16-byte global access on a dword-aligned address
 
-// position (i, j) of the transformed domain in the fragment order: the column halves j < 3 / j >= 3 as the xi ranges [0, 18) / [18, 36)
-static constexpr __host__ __device__ int xi_of(int i, int j) { return j < 3 ? 3 * i + j : 18 + 3 * i + (j - 3); }
-// register (dd[6 i + j]) of the value at position xi of the fragment order
+// register (dd[6 i + j]) of the value at position xi of the fragment order (xi_of(i, j): w2xc_layout.h)
 static constexpr __host__ __device__ int w4p_dd_of(int xi) { return 6 * ((xi % 18) / 3) + 3 * (xi / 18) + (xi % 18) % 3; }
 
 }   // namespace
@@ -278,7 +251,8 @@ __global__ void __launch_bounds__(512, 2) conv3x3_wino4_batch(W2xcConvDesc d, in
 }
 
 // ------------------------------------------------------------------------------------------------
-// host side.  Five objects (make -j): W2XC_WINO4_PART = 0 the planar-out instantiations + packers + dispatcher, 1 the NHWC-out ones, 2 the fused-last ones,
+// host side: launch (shape predicates, PROG's job arithmetic and the packers: w2xc_pack.cpp).
+// Five objects (make -j): W2XC_WINO4_PART = 0 the planar-out instantiations + dispatcher, 1 the NHWC-out ones, 2 the fused-last ones,
 // 3 the batch forms with planar out + the batch dispatcher, 4 the fused-last batch forms.
 // ------------------------------------------------------------------------------------------------
 #ifndef W2XC_WINO4_PART
@@ -298,18 +272,10 @@ static hipError_t launch_wino4(const W2xcConvDesc &d, hipStream_t stream)
         if (em != hipSuccess) return em;
     }
     auto kern = conv3x3_wino4<CIN, COUT, OUT_PLANAR, IN_NHWC, FUSE7, PROG>;
-    static std::atomic<unsigned long long> attr_done{0};   // function attributes are per device
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    static W2xcLdsOptIn opt_in;   // per (kernel, device)
+    const hipError_t e = opt_in(kern, lds_bytes);
     if (e != hipSuccess) return e;
-    if (dev >= 64 || !((attr_done.load() >> dev) & 1ull)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        if (dev < 64) attr_done.fetch_or(1ull << dev);
-    }
-    int grid = 256;   // one persistent workgroup per CU; a multiple of 8 (one share per XCD)
-    if (grid > ((nitems + 7) & ~7)) grid = (nitems + 7) & ~7;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds_bytes, stream, d, tiles_x, nitems);
+    hipLaunchKernelGGL(kern, dim3(w2xc_persistent_grid(nitems)), dim3(512), lds_bytes, stream, d, tiles_x, nitems);
     return hipGetLastError();
 }
 
@@ -370,68 +336,6 @@ hipError_t w2xc_launch_wino4_fused(const W2xcConvDesc &d, hipStream_t stream)
 #endif
 
 #if W2XC_WINO4_PART == 0 || W2XC_WINO4_PART == -1
-// the last layer's weights as MFMA A fragments for conv3x3_wino4's fused epilogue: [16-plane group g][e][lane = 16 kk + m] = w7[plane 16 g + 4 kk + e][tap m]
-// (m < 9, else 0).  w is [1][cin][3][3] (modelHandler.cpp:102).  16 * cin floats.
-size_t w2xc_wino4_pack_last_floats(int cin) { return (size_t)16 * cin; }
-void w2xc_wino4_pack_last(int cin, const float *w, float *dst)
-{
-    for (int g = 0; g < cin / 16; g++)
-        for (int e = 0; e < 4; e++)
-            for (int kk = 0; kk < 4; kk++)
-                for (int m = 0; m < 16; m++) dst[((size_t)g * 4 + e) * 64 + kk * 16 + m] = m < 9 ? w[(size_t)(16 * g + 4 * kk + e) * 9 + m] : 0.0f;
-}
-#endif
-
-#if W2XC_WINO4_PART == 0 || W2XC_WINO4_PART == -1
-bool w2xc_wino4_supported(int cin, int cout)
-{
-    return (cin == 32 || cin == 64 || cin == 128) && (cout == 64 || cout == 128);
-}
-// PROG: the fused launch that finishes the last layer itself exists for planar 64 / 128-plane inputs
-bool w2xc_wino4_prog_supported(int cin, int cout) { return (cin == 64 || cin == 128) && (cout == 64 || cout == 128); }
-// ... and its control words: per job (tile row, group of 8 tile columns of the launch's region) an arrival counter and a queue slot, + head and tail
-void w2xc_wino4_prog_jobs(int out_w, int out_h, int wino_py, int *tile_rows, int *groups)
-{
-    *tile_rows = (out_h + (wino_py & 3) + 15) / 16;
-    *groups = ((out_w + 31) / 32 + 7) / 8;
-}
-size_t w2xc_wino4_prog_counters(int out_w, int out_h, int wino_py)
-{
-    const int tiles_x = (out_w + 31) / 32, tiles_y = (out_h + (wino_py & 3) + 15) / 16;
-    return 2 * (size_t)tiles_y * ((tiles_x + 7) / 8) + 2;   // arrivals per job | the ready queue | head, tail
-}
-
-// wpk[64-plane block ob][stage s (4 channels)][xi / 4][plane tile pt][lane = 16 k + o][xi % 4] = U_xi[plane 64 ob + 16 pt + o][channel 4 s + k], xi = xi_of(i, j),
-// U = G g G^T formed in double and rounded once.  w is [cout][cin][3][3] (modelHandler.cpp:102).  36 * cin * cout floats.
-void w2xc_wino4_pack(int cin, int cout, const float *w, float *dst)
-{
-    static const double GM[6][3] = {{64.0 / 81, 0, 0},
-                                    {-128.0 / 243, -32.0 / 81, -8.0 / 27},
-                                    {-128.0 / 243, 32.0 / 81, -8.0 / 27},
-                                    {32.0 / 243, 16.0 / 81, 8.0 / 27},
-                                    {32.0 / 243, -16.0 / 81, 8.0 / 27},
-                                    {0, 0, 1}};
-    const int nst = cin / 4, nob = cout / 64;
-    for (int ob = 0; ob < nob; ob++)
-        for (int s = 0; s < nst; s++)
-            for (int pt = 0; pt < 4; pt++)
-                for (int k = 0; k < 4; k++)
-                    for (int o = 0; o < 16; o++) {
-                        const int plane = 64 * ob + 16 * pt + o, c = 4 * s + k;
-                        const float *g = w + ((size_t)plane * cin + c) * 9;
-                        double tmp[6][3];
-                        for (int i = 0; i < 6; i++)
-                            for (int j = 0; j < 3; j++) tmp[i][j] = GM[i][0] * g[0 * 3 + j] + GM[i][1] * g[1 * 3 + j] + GM[i][2] * g[2 * 3 + j];
-                        for (int i = 0; i < 6; i++)
-                            for (int j = 0; j < 6; j++) {
-                                const double u = tmp[i][0] * GM[j][0] + tmp[i][1] * GM[j][1] + tmp[i][2] * GM[j][2];
-                                const int xi = xi_of(i, j);
-                                dst[(((((size_t)ob * nst + s) * 9 + (xi >> 2)) * 4 + pt) * 64 + k * 16 + o) * 4 + (xi & 3)] = (float)u;
-                            }
-                    }
-}
-
-
 // d.wpk = w2xc_wino4_pack image; planar fp32 in (in_ps = 1, in_cs = plane stride), planar (out_ps = 1) or NHWC (out_cs = 1, out_ps = cout) out;
 // d.wino_py = first output row mod 4; off_x a multiple of 4 (the engine's layers: 0)
 hipError_t w2xc_launch_wino4(const W2xcConvDesc &d, hipStream_t stream)
@@ -486,18 +390,10 @@ static hipError_t launch_wino4_batch(const W2xcConvDesc &d, W2xcBatchDesc b, hip
     constexpr size_t lds_bytes = 3 * (size_t)(11 * 1024) + 2 * (size_t)(36 * 1024) + 3 * (size_t)(18 * 1024) + COUT * 4;   // raw + U + V + bias
     static_assert(lds_bytes <= 160 * 1024, "LDS budget");
     auto kern = conv3x3_wino4_batch<CIN, COUT, FUSE7>;
-    static std::atomic<unsigned long long> attr_done{0};   // function attributes are per device
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    static W2xcLdsOptIn opt_in;   // per (kernel, device)
+    const hipError_t e = opt_in(kern, lds_bytes);
     if (e != hipSuccess) return e;
-    if (dev >= 64 || !((attr_done.load() >> dev) & 1ull)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        if (dev < 64) attr_done.fetch_or(1ull << dev);
-    }
-    int grid = 256;   // one persistent workgroup per CU; a multiple of 8 (one share per XCD)
-    if (grid > ((nitems + 7) & ~7)) grid = (nitems + 7) & ~7;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds_bytes, stream, d, tiles_x, nitems, b);
+    hipLaunchKernelGGL(kern, dim3(w2xc_persistent_grid(nitems)), dim3(512), lds_bytes, stream, d, tiles_x, nitems, b);
     return hipGetLastError();
 }
 
@@ -516,12 +412,6 @@ hipError_t w2xc_launch_wino4_batch_fused(const W2xcConvDesc &d, W2xcBatchDesc b,
 #endif
 
 #if W2XC_WINO4_PART == 3 || W2XC_WINO4_PART == -1
-// planar in (in_ps = 1) only: the 32-plane NHWC-in forms and PROG have no batch instantiation (the engine's batch chain never needs them)
-bool w2xc_wino4_batch_supported(int cin, int cout, bool fused_last)
-{
-    return fused_last ? (cin == 64 || cin == 128) && (cout == 64 || cout == 128) : w2xc_wino4_supported(cin, cout);
-}
-
 // d = the single-image descriptor (the checks of w2xc_launch_wino4 apply to it unchanged), b.in_bs / b.out_bs = image strides in floats (multiples of 4:
 // every image's planes keep the 16-byte alignment of image 0's)
 hipError_t w2xc_launch_wino4_batch(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream)

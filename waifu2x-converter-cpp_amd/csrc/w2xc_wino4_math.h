@@ -1,4 +1,5 @@
-// w2xc_wino4_math.h -- the Winograd F(4x4, 3x3) transforms shared by conv3x3_wino4 (w2xc_wino4.hip) and conv3x3_wino4s (w2xc_wino4s.hip).
+// w2xc_wino4_math.h -- the Winograd F(4x4, 3x3) transforms shared by conv3x3_wino4 (w2xc_wino4.hip) and conv3x3_first2_wino4 (w2xc_first2_wino4.hip):
+// B^T and A^T, the kernels' side; G, the packers' side, is in w2xc_pack.cpp.
 // Cook-Toom on the points 0, +-3/4, +-3/2, inf (tools/winograd_points.py: every entry a dyadic rational <= 27/8):
 //   B^T = [81/64 0 -45/16 0 1 0; 0 -27/16 -9/4 3/4 1 0; 0 27/16 -9/4 -3/4 1 0; 0 -27/32 -9/16 3/2 1 0; 0 27/32 -9/16 -3/2 1 0; 0 81/64 0 -45/16 0 1]
 //   G   = [64/81 0 0; -128/243 -32/81 -8/27; -128/243 32/81 -8/27; 32/243 16/81 8/27; 32/243 -16/81 8/27; 0 0 1]
@@ -34,11 +35,3 @@ static __device__ __forceinline__ void at6(float m0, float m1, float m2, float m
     y2 = __builtin_fmaf(2.25f, s2, 0.5625f * s1);
     y3 = __builtin_fmaf(3.375f, d2, __builtin_fmaf(0.421875f, d1, m5));
 }
-
-// G as doubles (host side: the weight images U = G g G^T are formed in double and rounded once)
-static const double W2XC_WINO4_G[6][3] = {{64.0 / 81, 0, 0},
-                                          {-128.0 / 243, -32.0 / 81, -8.0 / 27},
-                                          {-128.0 / 243, 32.0 / 81, -8.0 / 27},
-                                          {32.0 / 243, 16.0 / 81, 8.0 / 27},
-                                          {32.0 / 243, -16.0 / 81, 8.0 / 27},
-                                          {0, 0, 1}};
