@@ -1,0 +1,244 @@
+// host_geom_test.cpp -- the integers of the engine's host side (waifu2x-converter-cpp_amd/csrc/w2xc_host_geom.hpp) checked as properties on the CPU.
+// Nothing here is taken from the code under test but the functions themselves: the conditions are what their consumers need --
+//   * the units of a call tile its output rows, and a unit's source view holds every row its output rows read through the halo;
+//   * the tapering first chunks make progress and end at whole slices;
+//   * the runs of finished tile rows the drainer stitches tile a band's rows once;
+//   * a job flag of an earlier band never reads as finished, up to and across the restart of the epochs;
+//   * the sub-batches of a host batch cover its images once;
+//   * the image pipeline's plane buffer holds every plane the batched pipeline lays out in it.
+// Prints the first failing input of each property; exit status = number of failed properties.
+#include "../../waifu2x-converter-cpp_amd/csrc/w2xc_host_geom.hpp"
+
+#include <cstdio>
+
+using namespace w2xc_eng;
+
+static int g_failed = 0;
+#define CHECK(cond, ...)                                               \
+    do {                                                               \
+        if (!(cond)) {                                                 \
+            std::printf("FAIL %s:%d: %s -- ", __func__, __LINE__, #cond); \
+            std::printf(__VA_ARGS__);                                  \
+            std::printf("\n");                                         \
+            g_failed++;                                                \
+            return;                                                    \
+        }                                                              \
+    } while (0)
+
+// row counts around every threshold (8-row tiles, 16-row job rows, the slice sizes), the minimum sizes, the 1080 / 2160-row frames, 16384 rows
+static std::vector<int> heights()
+{
+    std::vector<int> h;
+    for (int r = 1; r <= 300; r++) h.push_back(r);
+    const int more[] = {511, 512, 513, 1023, 1024, 1025, 1079, 1080, 1081, 2047, 2048, 2049, 2159, 2160, 2161, 4320, 16383, 16384};
+    for (size_t i = 0; i < sizeof more / sizeof *more; i++) h.push_back(more[i]);
+    return h;
+}
+
+// units tile [row_begin, row_end) in order; none is empty when nd <= R (convert_plane_host clamps nd to R)
+static void test_unit_rows()
+{
+    const std::vector<int> hs = heights();
+    for (size_t i = 0; i < hs.size(); i++)
+        for (int row_begin = 0; row_begin <= 37; row_begin += 37)
+            for (int nd = 1; nd <= 64 && nd <= hs[i]; nd++) {
+                const int R = hs[i];
+                int at = row_begin;
+                for (int t = 0; t < nd; t++) {
+                    const int ra = unit_rows(row_begin, row_begin + R, t, nd).first, rb = unit_rows(row_begin, row_begin + R, t, nd).second;
+                    CHECK(ra == at && rb > ra, "R=%d row_begin=%d nd=%d: unit %d is [%d, %d), expected to start at %d", R, row_begin, nd, t, ra, rb, at);
+                    at = rb;
+                }
+                CHECK(at == row_begin + R, "R=%d row_begin=%d nd=%d: units end at %d", R, row_begin, nd, at);
+            }
+}
+
+// Output row y of the (h << up)-row plane reads rows y - hs .. y + hs of it, clipped to the plane (replicate border); row r of it is source row r >> up.
+// A unit's source range [sy0, sy1) holds them all and lies inside the source plane, and so does what a band that ends at y1 has uploaded.
+static void test_src_rows()
+{
+    const std::vector<int> hv = heights();
+    const int halos[] = {1, 3, 7, 28};
+    for (int up = 0; up <= 1; up++)
+        for (size_t i = 0; i < hv.size(); i++)
+            for (size_t k = 0; k < sizeof halos / sizeof *halos; k++) {
+                const int h = hv[i], H = h << up, hs = halos[k];
+                const int cuts[] = {0, 1, hs, hs + 1, H / 3, H / 2, H / 2 + 1, H - hs - 1, H - hs, H - 1, H};
+                for (size_t a = 0; a < sizeof cuts / sizeof *cuts; a++)
+                    for (size_t b = 0; b < sizeof cuts / sizeof *cuts; b++) {
+                        const int ra = cuts[a], rb = cuts[b];
+                        if (ra < 0 || rb > H || ra >= rb) continue;
+                        const int sy0 = src_rows(ra, rb, hs, up, H).first, sy1 = src_rows(ra, rb, hs, up, H).second;
+                        CHECK(0 <= sy0 && sy0 < sy1 && sy1 <= h, "up=%d h=%d hs=%d [%d, %d): source rows [%d, %d) outside the plane", up, h, hs, ra, rb, sy0, sy1);
+                        const int first = std::max(0, ra - hs) >> up, last = std::min(H - 1, rb - 1 + hs) >> up;
+                        CHECK(sy0 <= first && last < sy1, "up=%d h=%d hs=%d [%d, %d): reads source rows %d..%d, has [%d, %d)", up, h, hs, ra, rb, first, last, sy0, sy1);
+                        for (int y1 = ra + 1; y1 <= rb; y1 += (y1 < ra + 40 || y1 > rb - 40) ? 1 : 97) {
+                            const int end = band_src_end(y1, hs, up, H, sy0, false, sy1 - sy0), need = (std::min(H - 1, y1 - 1 + hs) >> up) - sy0;
+                            CHECK(need < end && end <= sy1 - sy0, "up=%d h=%d hs=%d [%d, %d): a band that ends at %d reads view row %d, %d uploaded of %d", up, h, hs, ra, rb,
+                                  y1, need, end, sy1 - sy0);
+                        }
+                        CHECK(band_src_end(ra + 1, hs, up, H, sy0, true, sy1 - sy0) == sy1 - sy0, "up=%d h=%d hs=%d: overlapping planes stage the whole view first", up, h, hs);
+                    }
+            }
+}
+
+// the staging sizes are whole rows, at least one (eight for the output: the last-layer kernels' tiles), the taper's minimum is not above its maximum;
+// tapering chunks are positive and, from any start, reach a whole slice and stay there
+static void test_chunks()
+{
+    const int kbs[] = {0, 1, 4, 16, 64, 1024, 8192, 65536}, widths[] = {1, 4, 31, 256, 1920, 3840, 7680, 1 << 20};
+    for (size_t a = 0; a < sizeof kbs / sizeof *kbs; a++)
+        for (size_t b = 0; b < sizeof widths / sizeof *widths; b++)
+            for (int up = 0; up <= 1; up++) {
+                const int kb = kbs[a], w = widths[b];
+                const HostChunks c = host_chunks(kb, (size_t)w * 4, (size_t)(w << up) * 4);
+                CHECK(c.in_rows >= 1 && c.out_rows >= 8 && c.out_min >= 8, "kb=%d w=%d up=%d: chunks of %d / %d / %d rows", kb, w, up, c.in_rows, c.out_rows, c.out_min);
+                CHECK(c.out_rows % 8 == 0 && c.out_min % 8 == 0 && c.out_min <= c.out_rows, "kb=%d w=%d up=%d: output chunks of %d tapering to %d rows", kb, w, up, c.out_rows, c.out_min);
+                const int full = layer1_chunk(c.in_rows, up);
+                CHECK(full >= 8 && full % 8 == 0 && full >= (c.in_rows << up), "kb=%d w=%d up=%d: layer-1 chunks of %d rows for slices of %d", kb, w, up, full, c.in_rows);
+                for (int start = 0; start <= 2 * full; start += std::max(1, full / 37)) {
+                    int c0 = start, steps = 0;
+                    bool at_full = false;
+                    for (; steps < 64; steps++) {
+                        const int rows = taper_chunk(c0, full);
+                        CHECK(rows > 0 && rows <= full, "full=%d c0=%d: chunk of %d rows", full, c0, rows);
+                        CHECK(!at_full || rows == full, "full=%d c0=%d: %d rows after a whole slice", full, c0, rows);
+                        at_full = rows == full;
+                        c0 += rows;
+                    }
+                    CHECK(at_full, "full=%d start=%d: no whole slice after %d chunks", full, start, steps);
+                }
+            }
+}
+
+// job row jr of a band of R rows holds rows [16 jr - first, 16 jr - first + 16) clipped: trows = ceil((R + first) / 16) job rows.  However the finished
+// job rows come in -- one by one, in runs, all at once -- the spans stitched tile [0, R) in order, nothing twice
+static void test_tile_rows_span()
+{
+    const std::vector<int> hv = heights();
+    const int strides[] = {1, 2, 3, 7, 1 << 20};
+    for (size_t i = 0; i < hv.size(); i++)
+        for (int first = 0; first <= 15; first++)
+            for (size_t s = 0; s < sizeof strides / sizeof *strides; s++) {
+                const int R = hv[i], trows = (R + first + 15) / 16;
+                int at = 0;
+                for (int jr = 0; jr < trows;) {
+                    const int ready = std::min(trows, jr + strides[s]);
+                    const int a = tile_rows_span(jr, ready, first, R).first, b = tile_rows_span(jr, ready, first, R).second;
+                    if (b > a) {
+                        CHECK(a == at && b <= R, "R=%d first=%d: job rows [%d, %d) cover [%d, %d), stitched so far %d", R, first, jr, ready, a, b, at);
+                        at = b;
+                    }
+                    jr = ready;
+                }
+                CHECK(at == R, "R=%d first=%d stride=%d: rows stitched end at %d", R, first, strides[s], at);
+            }
+}
+
+// A band's jobs store its epoch; the words hold 0 (fresh) or the epoch of any earlier band since.  Only the current band's value may read as finished,
+// for the first bands of a buffer and for the last ones before PROG_EPOCH_LAST, where the flags are zeroed and the epochs start over.
+static void test_flag_epochs()
+{
+    const unsigned starts[] = {0u, 1u, 1000u, 0x3FFFFFFFu, 0x7FFFFFF0u};
+    for (size_t s = 0; s < sizeof starts / sizeof *starts; s++) {
+        unsigned epoch = starts[s];
+        std::vector<unsigned> words;   // every value a flag can still hold
+        words.push_back(0);
+        if (epoch > 0) { words.push_back(1); words.push_back(epoch / 2 + 1); words.push_back(epoch); }
+        for (int band = 0; band < 40; band++) {
+            if (epoch == PROG_EPOCH_LAST) { words.assign(1, 0u); epoch = 0; }   // (what prog_begin does)
+            const unsigned e = ++epoch;
+            CHECK(e >= 1 && e <= PROG_EPOCH_LAST, "epoch %u handed out", e);
+            for (size_t k = 0; k < words.size(); k++) CHECK(!flag_reached(words[k], e), "a flag that holds %u reads as finished in epoch %u", words[k], e);
+            CHECK(flag_reached(e, e), "a flag that holds %u does not read as finished in its own epoch", e);
+            words.push_back(e);
+        }
+    }
+    // The test is the SIGNED distance flag - epoch, not flag >= epoch: it holds for flags up to 2^31 - 1 behind their epoch and no further.  That is why the
+    // epochs may not run past PROG_EPOCH_LAST: at PROG_EPOCH_LAST + 1 a fresh (zero) flag still reads as unfinished, one epoch later it would read as finished.
+    CHECK(!flag_reached(0u, PROG_EPOCH_LAST + 1u), "a fresh flag reads as finished in epoch 2^31");
+    CHECK(flag_reached(0u, PROG_EPOCH_LAST + 2u), "the flag test is not the signed distance: a flag 2^31 - 1 ahead (mod 2^32) does not read as finished");
+    CHECK(flag_reached(5u, 0xFFFFFFFEu) && !flag_reached(0xFFFFFFFEu, 5u), "the flag test is not the signed distance across the 2^32 wrap");
+}
+
+// the sub-batches of n images cover 0 .. n once, in order on every device, each of 1 .. sub images, on no more devices than there are
+static void test_batch_stripes()
+{
+    const int ns[] = {1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 33, 64, 100, 255, 1000, 4097}, subs[] = {1, 2, 3, 8, 33, 64, 1 << 20};
+    for (size_t a = 0; a < sizeof ns / sizeof *ns; a++)
+        for (size_t b = 0; b < sizeof subs / sizeof *subs; b++)
+            for (int ndev = 1; ndev <= 8; ndev++) {
+                const int n = ns[a], sub = batch_stripe_sub(subs[b], n, ndev);
+                CHECK(sub >= 1 && sub <= subs[b], "n=%d sub=%d ndev=%d: sub-batches of %d", n, subs[b], ndev, sub);
+                const std::vector<std::vector<std::pair<int, int> > > share = batch_stripes(n, sub, ndev);
+                CHECK(!share.empty() && (int)share.size() <= ndev, "n=%d sub=%d ndev=%d: %d shares", n, sub, ndev, (int)share.size());
+                std::vector<int> seen(n, 0);
+                for (size_t d = 0; d < share.size(); d++) {
+                    CHECK(!share[d].empty(), "n=%d sub=%d ndev=%d: device %d has nothing to do", n, sub, ndev, (int)d);
+                    int prev_end = -1;
+                    for (size_t j = 0; j < share[d].size(); j++) {
+                        const int first = share[d][j].first, cnt = share[d][j].second;
+                        CHECK(cnt >= 1 && cnt <= sub && first >= 0 && first + cnt <= n, "n=%d sub=%d ndev=%d: sub-batch [%d, +%d)", n, sub, ndev, first, cnt);
+                        CHECK(first >= prev_end, "n=%d sub=%d ndev=%d: device %d's sub-batches out of order at image %d", n, sub, ndev, (int)d, first);
+                        prev_end = first + cnt;
+                        for (int i = first; i < first + cnt; i++) seen[i]++;
+                    }
+                }
+                for (int i = 0; i < n; i++) CHECK(seen[i] == 1, "n=%d sub=%d ndev=%d: image %d is in %d sub-batches", n, sub, ndev, i, seen[i]);
+            }
+}
+
+// The batched image pipeline lays its planes out per level, `cap` images wide (S <= cap of them in use), every plane on a 256-byte boundary: level 0 holds
+// Y, U, V and the noise pass's second Y; every scale iteration Y, U, V of twice the size; the shrink Y, U, V of the final size.  All of it lies inside
+// cap x image_aux_floats, and no level runs into the next.
+static void test_image_aux()
+{
+    const int sizes[][2] = {{1, 1}, {3, 5}, {7, 9}, {8, 8}, {63, 1}, {64, 64}, {65, 63}, {256, 256}, {640, 480}, {1920, 1080}};
+    const double shrinks[] = {0.0, 0.3, 0.5, 0.99};
+    for (size_t i = 0; i < sizeof sizes / sizeof *sizes; i++)
+        for (int it = 0; it <= 4; it++)
+            for (size_t k = 0; k < sizeof shrinks / sizeof *shrinks; k++)
+                for (int cap = 1; cap <= 33; cap += 16)
+                    for (int S = 1; S <= cap; S += cap - 1 > 0 ? cap - 1 : 1) {
+                        const int w = sizes[i][0], h = sizes[i][1];
+                        const double shrink = shrinks[k];
+                        int fw, fh;
+                        final_size(w, h, it, shrink, &fw, &fh);
+                        if (fw < 1 || fh < 1) continue;   // (refused by the argument checks)
+                        CHECK(fw <= (w << it) && fh <= (h << it), "%dx%d it=%d shrink=%g: final size %dx%d", w, h, it, shrink, fw, fh);
+                        const size_t have = image_aux_floats(w, h, it, shrink) * (size_t)cap;
+                        size_t base = 0, end = 0;
+                        // planes [first, first + count) of a level whose planes are ps floats apart hold cw x ch floats each
+                        struct { size_t *end; bool ok; void use(size_t base, size_t ps, size_t first, size_t count, size_t px) {
+                            ok = ok && px <= ps && ps % 64 == 0;
+                            *end = std::max(*end, base + (first + count - 1) * ps + px); } } lay = {&end, true};
+                        int cw = w, ch = h;
+                        size_t ps = plane_floats(cw, ch);
+                        lay.use(base, ps, 0, 4 * (size_t)S, (size_t)cw * ch);   // y, u, v, yn: S planes each
+                        base += 4 * (size_t)cap * ps;
+                        CHECK(end <= base, "%dx%d it=%d cap=%d S=%d: level 0 runs into the next level", w, h, it, cap, S);
+                        for (int l = 0; l < it; l++) {
+                            cw *= 2; ch *= 2;
+                            ps = plane_floats(cw, ch);
+                            lay.use(base, ps, 0, 3 * (size_t)S, (size_t)cw * ch);
+                            base += 3 * (size_t)cap * ps;
+                            CHECK(end <= base, "%dx%d it=%d cap=%d S=%d: level %d runs into the next level", w, h, it, cap, S, l + 1);
+                        }
+                        if (shrink > 0.0) lay.use(base, plane_floats(fw, fh), 0, 3 * (size_t)S, (size_t)fw * fh);
+                        CHECK(lay.ok, "%dx%d it=%d: a plane is larger than its slot or not on a 256-byte boundary", w, h, it);
+                        CHECK(end <= have, "%dx%d it=%d shrink=%g cap=%d S=%d: planes end at float %zu, the buffer holds %zu", w, h, it, shrink, cap, S, end, have);
+                    }
+}
+
+int main()
+{
+    test_unit_rows();
+    test_src_rows();
+    test_chunks();
+    test_tile_rows_span();
+    test_flag_epochs();
+    test_batch_stripes();
+    test_image_aux();
+    std::printf(g_failed ? "%d properties FAILED\n" : "all host geometry properties hold\n", g_failed);
+    return g_failed;
+}

@@ -221,6 +221,20 @@ def test_memory_follows_sub_batch_not_n(gpu):
     assert ms.fill_scratch(0, 0) == 0           # w2xc_model_trim releases all of it
 
 
+def test_trim_releases_the_filter_ring(gpu):
+    """Model::filter from host planes allocates a page-locked bounce ring that w2xc_debug_fill_scratch counts: w2xc_model_trim, which the header says
+    releases Model::filter's buffers, releases it too, so nothing is left to fill.  The next call grows everything again and gives the same planes."""
+    ms = gpu._ModelSet.from_layers(gen_model.synth_layers([1, 16, 16, 1], 31))
+    planes = [np.random.default_rng(77).random((40, 56), dtype=np.float32)]
+    want = ms.filter(0, planes)
+    assert ms.fill_scratch(0, 0) >= 2 * (8 << 20)   # (the ring alone: two 8 MiB slots)
+    ms.trim()
+    assert ms.fill_scratch(0, 0) == 0
+    assert np.array_equal(ms.filter(0, planes), want)
+    ms.trim()
+    assert ms.fill_scratch(0, 0) == 0
+
+
 def test_batch_against_the_oracle(gpu, mn, msc, noise1_layers, scale_layers):
     """W2XC_KERNEL_DIRECT: the batch output equals the CPU restatement of main.cpp byte for byte, for every image of a batch of distinct images"""
     x = images(3, 20, 28, 9)

@@ -13,7 +13,12 @@
 //   w2xc_rows.cpp           launch_layer, run_rows (the band loop that replaces convertWithModels / ...Basic / ...BlockSplit,
 //                           src/convertRoutine.cpp:21-169: run_band picks one launch strategy per layer -- prog, tail16, tail32,
 //                           first_chunks, last_chunks, plain), run_batch, and the device-pointer entry points
-//   w2xc_host_pipeline.cpp  host plane in -> host plane out: staging rings, three streams, feeder + drainer, the unit fan-out
+//   w2xc_scratch.hpp        Scratch: the one owner of every grow-only device / page-locked buffer (reserve, release, the drain rule); a context lists its
+//                           buffers once, DevCtx::for_each_scratch below -- destruction, w2xc_model_trim and w2xc_debug_fill_scratch go by that list
+//   w2xc_host_geom.hpp      the integers of the host side: a unit's rows and source view, staging chunks and their taper, the rows finished job rows
+//                           cover, the job flags' epoch test, sub-batch striping, the image pipeline's planes (no HIP header; tests/cpp/host_geom_test.cpp)
+//   w2xc_host_pipeline.cpp  host plane in -> host plane out: staging rings, three streams, the feeder with its Uploader, the drainer (Stitcher), the unit
+//                           fan-out (run_units), the host batch pipeline
 //   w2xc_filter.cpp         Model::filter at the host / device boundary (src/modelHandler.cpp:26-72)
 //   w2xc_image.cpp          N2: the CLI's image pipeline around the plane conversion (main.cpp:74-172)
 #pragma once
@@ -36,6 +41,7 @@
 #include <vector>
 
 #include "w2xc_kernels.h"
+#include "w2xc_scratch.hpp"
 
 namespace w2xc_eng {
 
@@ -91,42 +97,28 @@ struct ProfEvent {
 struct HostPipe {
     static constexpr int IN_SLOTS = 3, OUT_SLOTS = 4;
     hipStream_t s_compute = nullptr, s_h2d = nullptr, s_d2h = nullptr;
-    float *d_in = nullptr, *d_out = nullptr;
-    size_t d_in_bytes = 0, d_out_bytes = 0;
-    char *pin_in = nullptr, *pin_out = nullptr;
-    size_t in_slot_bytes = 0, out_slot_bytes = 0;
+    Scratch d_in, d_out;
+    Scratch pin_in{Scratch::PINNED}, pin_out{Scratch::PINNED};   // IN_SLOTS / OUT_SLOTS slots each (default policy: ROCm places pinned host memory near the allocating device)
+    size_t in_slot_bytes() const { return pin_in.bytes() / IN_SLOTS; }
+    size_t out_slot_bytes() const { return pin_out.bytes() / OUT_SLOTS; }
     hipEvent_t ev_in_slot[IN_SLOTS] = {}, ev_out_slot[OUT_SLOTS] = {};   // last DMA that used the slot
     hipEvent_t ev_input = nullptr, ev_chunk = nullptr;                   // band input landed / last-layer chunk computed
     hipEvent_t ev_batch[4] = {};   // w2xc_convert_batch: [slot] = the layers of the sub-batch in device slot `slot` done, [2 + slot] = its download done
     // conv3x3_wino4 PROG: two page-locked band buffers the gather jobs write the output rows into over PCIe (bands alternate), and their job flags
-    char *pin_band[2] = {nullptr, nullptr};
-    size_t band_bytes[2] = {0, 0};
-    unsigned *pin_flags[2] = {nullptr, nullptr};
-    size_t flags_n[2] = {0, 0};
-    unsigned flags_epoch[2] = {0, 0};
+    Scratch pin_band[2] = {Scratch(Scratch::PINNED_COHERENT), Scratch(Scratch::PINNED_COHERENT)};
+    ProgFlags flags[2];
     bool ready = false;
 
-    void destroy()
+    void destroy()   // streams and events; the buffers are the context's (DevCtx::for_each_scratch)
     {
-        if (s_compute) hipStreamSynchronize(s_compute);
-        if (s_h2d) hipStreamSynchronize(s_h2d);
-        if (s_d2h) hipStreamSynchronize(s_d2h);
+        hipStream_t *const streams[3] = {&s_compute, &s_h2d, &s_d2h};
+        for (hipStream_t *s : streams) if (*s) hipStreamSynchronize(*s);
         for (auto &e : ev_in_slot) if (e) { hipEventDestroy(e); e = nullptr; }
         for (auto &e : ev_out_slot) if (e) { hipEventDestroy(e); e = nullptr; }
         if (ev_input) { hipEventDestroy(ev_input); ev_input = nullptr; }
         if (ev_chunk) { hipEventDestroy(ev_chunk); ev_chunk = nullptr; }
         for (auto &e : ev_batch) if (e) { hipEventDestroy(e); e = nullptr; }
-        if (d_in) { hipFree(d_in); d_in = nullptr; d_in_bytes = 0; }
-        if (d_out) { hipFree(d_out); d_out = nullptr; d_out_bytes = 0; }
-        if (pin_in) { hipHostFree(pin_in); pin_in = nullptr; in_slot_bytes = 0; }
-        if (pin_out) { hipHostFree(pin_out); pin_out = nullptr; out_slot_bytes = 0; }
-        for (int i = 0; i < 2; i++) {
-            if (pin_band[i]) { hipHostFree(pin_band[i]); pin_band[i] = nullptr; band_bytes[i] = 0; }
-            if (pin_flags[i]) { hipHostFree(pin_flags[i]); pin_flags[i] = nullptr; flags_n[i] = 0; flags_epoch[i] = 0; }
-        }
-        if (s_compute) { hipStreamDestroy(s_compute); s_compute = nullptr; }
-        if (s_h2d) { hipStreamDestroy(s_h2d); s_h2d = nullptr; }
-        if (s_d2h) { hipStreamDestroy(s_d2h); s_d2h = nullptr; }
+        for (hipStream_t *s : streams) if (*s) { hipStreamDestroy(*s); *s = nullptr; }
         ready = false;
     }
 };
@@ -136,12 +128,10 @@ struct HostPipe {
 // (the reference's test.cpp:72-85 pattern) -- see w2xc_opts.filter_resident.
 struct FilterCache {
     static constexpr int SLOTS = 2;
-    float *planar[2] = {nullptr, nullptr}, *nhwc[2] = {nullptr, nullptr};   // ping-pong: a call reads [ob ^ 1], writes [ob]
-    size_t planar_floats[2] = {0, 0}, nhwc_floats[2] = {0, 0};
-    float *pad = nullptr, *pout = nullptr;   // conv3x3_wino4: the replicate-padded planar copy of the input planes / an aligned planar result
-    size_t pad_floats = 0, pout_floats = 0;
-    char *pin = nullptr;            // SLOTS pinned bounce slots between the caller's pageable planes and the DMA engine
-    size_t slot_bytes = 0;
+    Scratch planar[2], nhwc[2];   // ping-pong: a call reads [ob ^ 1], writes [ob]
+    Scratch pad, pout;            // conv3x3_wino4: the replicate-padded planar copy of the input planes / an aligned planar result
+    Scratch pin{Scratch::PINNED};   // SLOTS pinned bounce slots between the caller's pageable planes and the DMA engine
+    size_t slot_bytes() const { return pin.bytes() / SLOTS; }
     hipStream_t st = nullptr;
     hipEvent_t ev[SLOTS] = {};
     int ob = 0;                     // buffer index the LAST call wrote
@@ -154,53 +144,44 @@ struct FilterCache {
 struct DevCtx {
     int device = 0;
     std::vector<DevLayer> layers;
-    float *ws[2] = {nullptr, nullptr};
-    size_t ws_floats[2] = {0, 0};
+    Scratch ws[2];              // the two ping-pong activation workspaces
     HostPipe pipe;
     FilterCache fc;
-    unsigned *prog_cnt = nullptr;   // conv3x3_wino4 PROG: gather-job counters of the launch in flight (grow-only)
-    size_t prog_cnt_n = 0;
-    float *aux = nullptr;       // N2: Y/U/V planes of the image pipeline
-    size_t aux_floats = 0;
-    unsigned char *img_io = nullptr;   // N2, host entry points: device copies of the uint8 image in / out (grow-only)
-    size_t img_io_bytes = 0;
+    Scratch prog_cnt;           // conv3x3_wino4 PROG: gather-job counters of the launch in flight (zeroed by the launcher)
+    Scratch aux;                // N2: Y/U/V planes of the image pipeline
+    Scratch img_io;             // N2, host entry points: device copies of the uint8 image in / out
     std::vector<ProfEvent> pending, pool;
     std::vector<double> layer_ms;
     std::vector<int> layer_launches;
     std::mutex mu;
+
+    // THE list of the context's grow-only buffers: destruction, w2xc_model_trim and w2xc_debug_fill_scratch go by it and by nothing else
+    template <class F> void for_each_scratch(F f)
+    {
+        for (auto &s : ws) f(s, ScratchTag::DATA);
+        f(aux, ScratchTag::DATA);
+        f(img_io, ScratchTag::DATA);
+        f(prog_cnt, ScratchTag::SYNC);
+        for (Scratch *s : {&pipe.d_in, &pipe.d_out, &pipe.pin_in, &pipe.pin_out, &pipe.pin_band[0], &pipe.pin_band[1]}) f(*s, ScratchTag::DATA);
+        for (auto &fl : pipe.flags) f(fl.words, ScratchTag::SYNC);
+        for (Scratch *s : {&fc.planar[0], &fc.planar[1], &fc.nhwc[0], &fc.nhwc[1], &fc.pad, &fc.pout, &fc.pin}) f(*s, ScratchTag::DATA);
+    }
 
     ~DevCtx()
     {
         int prev = 0;
         hipGetDevice(&prev);
         hipSetDevice(device);
-        for (auto &l : layers) {
-            if (l.w_fast) hipFree(l.w_fast);
-            if (l.w_direct) hipFree(l.w_direct);
-            if (l.w_wino) hipFree(l.w_wino);
-            if (l.w_wino4) hipFree(l.w_wino4);
-            if (l.w_first2) hipFree(l.w_first2);
-            if (l.w_last_wino4) hipFree(l.w_last_wino4);
-            for (float *p : l.w_split)
-                if (p) hipFree(p);
-            for (float *p : l.w_last_fused)
-                if (p) hipFree(p);
-            if (l.bias) hipFree(l.bias);
+        for (auto &l : layers) {   // the weights: uploaded once (upload, w2xc_model.cpp), not scratch
+            for (float *p : {l.w_fast, l.w_direct, l.w_wino, l.w_wino4, l.w_first2, l.w_last_wino4, l.bias}) if (p) hipFree(p);
+            for (float *p : l.w_split) if (p) hipFree(p);
+            for (float *p : l.w_last_fused) if (p) hipFree(p);
         }
         pipe.destroy();
         if (fc.st) hipStreamSynchronize(fc.st);
-        for (float *p : fc.planar) if (p) hipFree(p);
-        for (float *p : fc.nhwc) if (p) hipFree(p);
-        if (fc.pad) hipFree(fc.pad);
-        if (fc.pout) hipFree(fc.pout);
-        if (fc.pin) hipHostFree(fc.pin);
         for (auto &e : fc.ev) if (e) hipEventDestroy(e);
         if (fc.st) hipStreamDestroy(fc.st);
-        for (int i = 0; i < 2; i++)
-            if (ws[i]) hipFree(ws[i]);
-        if (aux) hipFree(aux);
-        if (prog_cnt) hipFree(prog_cnt);
-        if (img_io) hipFree(img_io);
+        for_each_scratch([](Scratch &s, ScratchTag) { s.release(); });
         for (auto &e : pending) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
         for (auto &e : pool) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
         hipSetDevice(prev);
@@ -236,7 +217,6 @@ w2xc_opts resolve_opts(const w2xc_opts *o);
 int njob();                                  // modelUtility's nJob (w2xc_get_jobs)
 int upload(const std::vector<float> &h, float **d);
 int get_ctx(w2xc_model *m, int device, DevCtx **out);
-int ensure_ws(DevCtx *c, int which, size_t floats);
 int prof_begin(DevCtx *c, int layer, hipStream_t st, ProfEvent *ev);
 
 // ---- w2xc_select.cpp ----

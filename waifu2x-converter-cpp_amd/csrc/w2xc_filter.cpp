@@ -9,14 +9,7 @@ namespace w2xc_eng {
 
 namespace {
 
-int grow(float **buf, size_t *have, size_t want)
-{
-    if (*have >= want) return W2XC_OK;
-    if (*buf) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(*buf)); *buf = nullptr; *have = 0; }
-    if (hipMalloc((void **)buf, want * sizeof(float)) != hipSuccess) return fail(W2XC_ERR_NOMEM, "hipMalloc(%zu MiB) for Model::filter planes failed", (want * 4) >> 20);
-    *have = want;
-    return W2XC_OK;
-}
+int grow(Scratch &buf, size_t floats) { return buf.reserve(floats * sizeof(float), "Model::filter planes"); }
 
 bool nhwc_ok(const float *p, long long cs, long long rs, long long ps, int planes)
 {
@@ -49,10 +42,10 @@ int filter_on_device(w2xc_model *m, DevCtx *c, int layer, const float *in, long 
         // conv3x3_wino4 runs a valid conv on planar planes with 16-byte aligned pixel quads: the replicate border (:141-142) is made explicit in a
         // padded planar copy of the input (one pass over Cin planes; the kernel then reads it with offset 0)
         const long long prs = ((long long)w + 2 + 31) & ~31ll, pcs = prs * (h + 2);
-        int rc = grow(&fc.pad, &fc.pad_floats, (size_t)pcs * hl.nin);
+        int rc = grow(fc.pad, (size_t)pcs * hl.nin);
         if (rc) return rc;
-        HIP_TRY(w2xc_launch_pad_planar(in, in_rs, in_ps, in_cs, fc.pad, prs, pcs, h, w, hl.nin, 1, st));
-        d.in = fc.pad; d.in_rs = prs; d.in_ps = 1; d.in_cs = pcs;
+        HIP_TRY(w2xc_launch_pad_planar(in, in_rs, in_ps, in_cs, fc.pad.as<float>(), prs, pcs, h, w, hl.nin, 1, st));
+        d.in = fc.pad.as<float>(); d.in_rs = prs; d.in_ps = 1; d.in_cs = pcs;
         d.in_h = h + 2; d.in_w = w + 2;
         d.off_y = d.off_x = 0;
         const long long ors = ((long long)w + 31) & ~31ll;
@@ -63,9 +56,9 @@ int filter_on_device(w2xc_model *m, DevCtx *c, int layer, const float *in, long 
         if (planar_direct || nhwc_direct) {
             d.out = out; d.out_rs = out_rs; d.out_ps = out_ps; d.out_cs = out_cs;
         } else {
-            rc = grow(&fc.pout, &fc.pout_floats, (size_t)ors * h * hl.nout);
+            rc = grow(fc.pout, (size_t)ors * h * hl.nout);
             if (rc) return rc;
-            d.out = fc.pout; d.out_rs = ors; d.out_ps = 1; d.out_cs = ors * h;
+            d.out = fc.pout.as<float>(); d.out_rs = ors; d.out_ps = 1; d.out_cs = ors * h;
         }
         int r = launch_layer(c, m, layer, kind, d, st, of);
         if (r) return r;
@@ -74,10 +67,10 @@ int filter_on_device(w2xc_model *m, DevCtx *c, int layer, const float *in, long 
         return W2XC_OK;
     }
     if (want_nhwc_in && !nhwc_ok(in, in_cs, in_rs, in_ps, hl.nin)) {
-        int rc = grow(&fc.nhwc[ob ^ 1], &fc.nhwc_floats[ob ^ 1], px * hl.nin);
+        int rc = grow(fc.nhwc[ob ^ 1], px * hl.nin);
         if (rc) return rc;
-        HIP_TRY(w2xc_launch_repack(in, in_rs, in_ps, in_cs, fc.nhwc[ob ^ 1], (long long)w * hl.nin, hl.nin, 1, h, w, hl.nin, st));
-        d.in = fc.nhwc[ob ^ 1]; d.in_rs = (long long)w * hl.nin; d.in_ps = hl.nin; d.in_cs = 1;
+        HIP_TRY(w2xc_launch_repack(in, in_rs, in_ps, in_cs, fc.nhwc[ob ^ 1].as<float>(), (long long)w * hl.nin, hl.nin, 1, h, w, hl.nin, st));
+        d.in = fc.nhwc[ob ^ 1].as<float>(); d.in_rs = (long long)w * hl.nin; d.in_ps = hl.nin; d.in_cs = 1;
     } else {
         d.in = in; d.in_rs = in_rs; d.in_ps = in_ps; d.in_cs = in_cs;
     }
@@ -85,9 +78,9 @@ int filter_on_device(w2xc_model *m, DevCtx *c, int layer, const float *in, long 
     if (direct_out) {
         d.out = out; d.out_rs = out_rs; d.out_ps = out_ps; d.out_cs = out_cs;
     } else {
-        int rc = grow(&fc.nhwc[ob], &fc.nhwc_floats[ob], px * hl.nout);
+        int rc = grow(fc.nhwc[ob], px * hl.nout);
         if (rc) return rc;
-        d.out = fc.nhwc[ob]; d.out_rs = (long long)w * hl.nout; d.out_ps = hl.nout; d.out_cs = 1;
+        d.out = fc.nhwc[ob].as<float>(); d.out_rs = (long long)w * hl.nout; d.out_ps = hl.nout; d.out_cs = 1;
     }
     int r = launch_layer(c, m, layer, kind, d, st, of);
     if (r) return r;
@@ -163,15 +156,9 @@ try {
     }
     const size_t px = (size_t)w * h, row = (size_t)w * 4;
     const size_t want_slot = std::max<size_t>((size_t)8 << 20, row);
-    if (fc.slot_bytes < want_slot) {
-        HIP_TRY(hipStreamSynchronize(fc.st));
-        if (fc.pin) { HIP_TRY(hipHostFree(fc.pin)); fc.pin = nullptr; fc.slot_bytes = 0; }
-        if (hipHostMalloc((void **)&fc.pin, want_slot * FilterCache::SLOTS, hipHostMallocDefault) != hipSuccess)
-            return fail(W2XC_ERR_NOMEM, "hipHostMalloc of the Model::filter bounce ring failed");
-        fc.slot_bytes = want_slot;
-    }
+    if ((rc = fc.pin.reserve(want_slot * FilterCache::SLOTS, "the Model::filter bounce ring"))) return rc;
     const int copy_threads = std::max(1, std::min(w2xc_get_jobs(), 32));
-    const int rows_per_slot = (int)(fc.slot_bytes / row);
+    const int rows_per_slot = (int)(fc.slot_bytes() / row);
 
     // filter_resident: the planes handed in are exactly the planes the previous filter() call on this model wrote (same
     // pointers, count, size) and the caller has not touched them since -- its result is still on the device
@@ -188,7 +175,7 @@ try {
         for (long g0 = 0; g0 < total; g0 += rows_per_slot, seq++) {
             const long g1 = std::min(total, g0 + rows_per_slot);
             const int si = (int)(seq % FilterCache::SLOTS);
-            int r = fn(g0, g1, fc.pin + (size_t)si * fc.slot_bytes, si);
+            int r = fn(g0, g1, fc.pin.as<char>() + (size_t)si * fc.slot_bytes(), si);
             if (r) return r;
         }
         return W2XC_OK;
@@ -204,17 +191,17 @@ try {
         }
     };
 
-    rc = grow(&fc.planar[ob], &fc.planar_floats[ob], px * hl.nout);
+    rc = grow(fc.planar[ob], px * hl.nout);
     if (rc) return rc;
     const float *d_in;
     long long in_cs, in_rs, in_ps;
     if (resident && fc.res_nhwc) {
-        d_in = fc.nhwc[ob ^ 1]; in_cs = 1; in_rs = (long long)w * hl.nin; in_ps = hl.nin;
+        d_in = fc.nhwc[ob ^ 1].as<float>(); in_cs = 1; in_rs = (long long)w * hl.nin; in_ps = hl.nin;
     } else {
         if (!resident) {
-            rc = grow(&fc.planar[ob ^ 1], &fc.planar_floats[ob ^ 1], px * hl.nin);
+            rc = grow(fc.planar[ob ^ 1], px * hl.nin);
             if (rc) return rc;
-            float *dst = fc.planar[ob ^ 1];
+            float *dst = fc.planar[ob ^ 1].as<float>();
             rc = for_runs(hl.nin, [&](long g0, long g1, char *slot, int si) -> int {
                 if (seq >= FilterCache::SLOTS) HIP_TRY(hipEventSynchronize(fc.ev[si]));   // the slot's previous DMA is done
                 host_rows(true, slot, g0, g1, in_planes, nullptr, in_stride_bytes);
@@ -224,10 +211,10 @@ try {
             });
             if (rc) { hipStreamSynchronize(fc.st); return rc; }
         }
-        d_in = fc.planar[ob ^ 1]; in_cs = (long long)px; in_rs = w; in_ps = 1;
+        d_in = fc.planar[ob ^ 1].as<float>(); in_cs = (long long)px; in_rs = w; in_ps = 1;
     }
     bool res_nhwc = false;
-    rc = filter_on_device(m, c, layer, d_in, in_cs, in_rs, in_ps, w, h, fc.planar[ob], (long long)px, w, 1, fc.st, o, ob, &res_nhwc);
+    rc = filter_on_device(m, c, layer, d_in, in_cs, in_rs, in_ps, w, h, fc.planar[ob].as<float>(), (long long)px, w, 1, fc.st, o, ob, &res_nhwc);
     if (rc) { hipStreamSynchronize(fc.st); return rc; }
 
     // download: D2H of run k+1 overlaps the host copy of run k
@@ -235,7 +222,7 @@ try {
     std::vector<Run> inflight;
     auto finish_run = [&](const Run &r) -> int {
         HIP_TRY(hipEventSynchronize(fc.ev[r.si]));
-        host_rows(false, fc.pin + (size_t)r.si * fc.slot_bytes, r.g0, r.g1, nullptr, out_planes, out_stride_bytes);
+        host_rows(false, fc.pin.as<char>() + (size_t)r.si * fc.slot_bytes(), r.g0, r.g1, nullptr, out_planes, out_stride_bytes);
         return W2XC_OK;
     };
     HIP_TRY(hipStreamSynchronize(fc.st));   // uploads done: the ring is free again, the layer has run
@@ -246,7 +233,7 @@ try {
             if (r) return r;
             inflight.erase(inflight.begin());
         }
-        HIP_TRY(hipMemcpyAsync(slot, fc.planar[ob] + (size_t)g0 * w, (size_t)(g1 - g0) * row, hipMemcpyDeviceToHost, fc.st));
+        HIP_TRY(hipMemcpyAsync(slot, fc.planar[ob].as<float>() + (size_t)g0 * w, (size_t)(g1 - g0) * row, hipMemcpyDeviceToHost, fc.st));
         HIP_TRY(hipEventRecord(fc.ev[si], fc.st));
         inflight.push_back({g0, g1, si});
         return W2XC_OK;

@@ -1,0 +1,97 @@
+// w2xc_host_geom.hpp -- the integers of the host side of the engine (w2xc_host_pipeline.cpp, w2xc_image.cpp): which rows a unit converts and reads, the
+// staging chunk sizes, which output rows finished tile rows cover, the job flags' epoch test, how a batch is cut into sub-batches, the float planes of the
+// image pipeline.  No HIP header: tests/cpp/host_geom_test.cpp builds it with g++ and checks what the consumers of these numbers need.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <utility>
+#include <vector>
+
+namespace w2xc_eng {
+
+typedef std::pair<int, int> RowSpan;   // rows [first, second)
+
+// contiguous share of the output rows [row_begin, row_end) for unit t of nd: independent, no exchange
+inline RowSpan unit_rows(int row_begin, int row_end, int t, int nd)
+{
+    const int R = row_end - row_begin;
+    return {row_begin + (int)((long long)R * t / nd), row_begin + (int)((long long)R * (t + 1) / nd)};
+}
+
+// source rows that cover output rows [ra - hs, rb + hs) (clipped to the H output rows) of a conversion that doubles `up` times, in source coordinates
+inline RowSpan src_rows(int ra, int rb, int hs, int up, int H) { return {std::max(0, ra - hs) >> up, (std::min(H, rb + hs) + up) >> up}; }
+
+// view rows (source coordinates, relative to sy0) a band of output rows that ends at y1 reads; overlapping planes: every row of the view (svh)
+inline int band_src_end(int y1, int hs, int up, int H, int sy0, bool overlap, int svh)
+{
+    return overlap ? svh : ((std::min(H, y1 + hs) + up) >> up) - sy0;
+}
+
+// staging granularity, whole rows: input slices of ~2 MiB; output chunks of at most ~8 MiB tapering to 1/16 of that (multiples of the 8-row tiles of the
+// last-layer kernels).  w2xc_opts.host_chunk_kb overrides the maximum (test aid).
+struct HostChunks { int in_rows, out_rows, out_min; };
+inline HostChunks host_chunks(int host_chunk_kb, size_t in_row, size_t out_row)
+{
+    const size_t chunk_max = host_chunk_kb > 0 ? (size_t)host_chunk_kb << 10 : (size_t)8 << 20;
+    HostChunks c;
+    c.in_rows = (int)std::max<size_t>(1, std::min<size_t>(chunk_max, (size_t)2 << 20) / in_row);
+    c.out_rows = (int)std::max<size_t>(8, (chunk_max / out_row) & ~(size_t)7);
+    c.out_min = (int)std::max<size_t>(8, (chunk_max / 16 / out_row) & ~(size_t)7);
+    return c;
+}
+
+// output rows of layer 1 per chunk while the band's input is still arriving in slices of in_chunk_rows source rows
+inline int layer1_chunk(int in_chunk_rows, int up) { return std::max(8, ((in_chunk_rows << up) + 7) & ~7); }
+
+// the call's first chunks are an eighth, a quarter, a half of a slice (the chunk that starts at output row c0): the first launch starts ~30 us into the call
+// instead of behind the first 2 MiB; later chunks are whole slices, every launch of the persistent kernel has a ramp
+inline int taper_chunk(int c0, int full)
+{
+    return c0 < full / 8 ? full / 8 : c0 < full / 8 + full / 4 ? full / 4 : c0 < full / 8 + full / 4 + full / 2 ? full / 2 : full;
+}
+
+// conv3x3_wino4 PROG: job row jr holds the band's rows [16 jr - first, 16 jr - first + 16) clipped to its R rows; what tile rows [jr, ready) cover (empty: second <= first)
+inline RowSpan tile_rows_span(int jr, int ready, int first, int R) { return {std::max(0, 16 * jr - first), std::min(R, 16 * ready - first)}; }
+
+// a job flag holds the epoch of the band whose job stored it last; epochs count up from 1 per band buffer and the comparison is signed, so the flags start
+// over (zeroed, epoch 0) once the epoch has reached PROG_EPOCH_LAST
+constexpr unsigned PROG_EPOCH_LAST = 0x7FFFFFFFu;
+inline bool flag_reached(unsigned flag, unsigned epoch) { return (int)(flag - epoch) >= 0; }
+
+// images per sub-batch of a host batch of n images on ndev devices: at most `sub`, and at least two sub-batches per device where there are images enough
+// (uploads, launches and downloads then have something to overlap with)
+inline int batch_stripe_sub(int sub, int n, int ndev) { return std::min(sub, std::max(1, (n + 2 * ndev - 1) / (2 * ndev))); }
+// the sub-batches ([first image, count), in order) striped over the devices; share.size() = the devices that get any
+inline std::vector<std::vector<std::pair<int, int>>> batch_stripes(int n, int sub, int ndev)
+{
+    const int nsub = (n + sub - 1) / sub;
+    const int nd = std::min(ndev, nsub);
+    std::vector<std::vector<std::pair<int, int>>> share(nd);
+    for (int j = 0; j < nsub; j++) share[j % nd].push_back({j * sub, std::min(sub, n - j * sub)});
+    return share;
+}
+
+// final size of the image pipeline: (w << iterations) x (h << iterations), then the optional shrink of main.cpp:158-167
+inline void final_size(int w, int h, int iterations, double shrink, int *fw, int *fh)
+{
+    *fw = w << iterations;
+    *fh = h << iterations;
+    if (shrink > 0.0) {
+        *fw = static_cast<int>(static_cast<double>(*fw * shrink));   // :160-165
+        *fh = static_cast<int>(static_cast<double>(*fh * shrink));
+    }
+}
+
+// float planes of ONE image over all levels of the batched image pipeline, every plane on a 256-byte boundary
+inline size_t plane_floats(int w, int h) { return ((size_t)w * h + 63) & ~(size_t)63; }
+inline size_t image_aux_floats(int w, int h, int iterations, double shrink)
+{
+    size_t need = 4 * plane_floats(w, h);
+    for (int i = 1; i <= iterations; i++) need += 3 * plane_floats(w << i, h << i);
+    int fw, fh;
+    final_size(w, h, iterations, shrink, &fw, &fh);
+    if (shrink > 0.0) need += 3 * plane_floats(fw, fh);
+    return need;
+}
+
+}  // namespace w2xc_eng

@@ -12,6 +12,7 @@
 #include <thread>
 
 #include "w2xc_copy_pool.hpp"
+#include "w2xc_host_geom.hpp"
 
 namespace w2xc_eng {
 
@@ -142,52 +143,230 @@ struct NodeAffinity {
     ~NodeAffinity() { if (bound) pthread_setaffinity_np(pthread_self(), sizeof prev, &prev); }
 };
 
-// grow-only device / pinned buffers; growing drains the pipe first (earlier calls may still use the old ones)
+// grow-only device rows and pinned staging rings of the pipe (a slot size of 0: no ring needed, the planes are page-locked)
 int pipe_reserve(HostPipe &p, size_t in_bytes, size_t out_bytes, size_t in_slot, size_t out_slot)
 {
-    auto drain = [&]() -> int {
-        HIP_TRY(hipStreamSynchronize(p.s_compute));
-        HIP_TRY(hipStreamSynchronize(p.s_h2d));
-        HIP_TRY(hipStreamSynchronize(p.s_d2h));
-        return W2XC_OK;
-    };
-    if (p.d_in_bytes < in_bytes) {
-        int rc = drain(); if (rc) return rc;
-        if (p.d_in) { HIP_TRY(hipFree(p.d_in)); p.d_in = nullptr; p.d_in_bytes = 0; }
-        if (hipMalloc((void **)&p.d_in, in_bytes) != hipSuccess) return fail(W2XC_ERR_NOMEM, "hipMalloc(%zu MiB) for the input rows failed", in_bytes >> 20);
-        p.d_in_bytes = in_bytes;
-    }
-    if (p.d_out_bytes < out_bytes) {
-        int rc = drain(); if (rc) return rc;
-        if (p.d_out) { HIP_TRY(hipFree(p.d_out)); p.d_out = nullptr; p.d_out_bytes = 0; }
-        if (hipMalloc((void **)&p.d_out, out_bytes) != hipSuccess) return fail(W2XC_ERR_NOMEM, "hipMalloc(%zu MiB) for the output rows failed", out_bytes >> 20);
-        p.d_out_bytes = out_bytes;
-    }
-    if (in_slot && p.in_slot_bytes < in_slot) {
-        int rc = drain(); if (rc) return rc;
-        if (p.pin_in) { HIP_TRY(hipHostFree(p.pin_in)); p.pin_in = nullptr; p.in_slot_bytes = 0; }
-        if (hipHostMalloc((void **)&p.pin_in, in_slot * HostPipe::IN_SLOTS, hipHostMallocDefault) != hipSuccess)
-            return fail(W2XC_ERR_NOMEM, "hipHostMalloc of the input staging ring failed");
-        p.in_slot_bytes = in_slot;   // (default policy: ROCm places pinned host memory near the allocating device)
-    }
-    if (out_slot && p.out_slot_bytes < out_slot) {
-        int rc = drain(); if (rc) return rc;
-        if (p.pin_out) { HIP_TRY(hipHostFree(p.pin_out)); p.pin_out = nullptr; p.out_slot_bytes = 0; }
-        if (hipHostMalloc((void **)&p.pin_out, out_slot * HostPipe::OUT_SLOTS, hipHostMallocDefault) != hipSuccess)
-            return fail(W2XC_ERR_NOMEM, "hipHostMalloc of the output staging ring failed");
-        p.out_slot_bytes = out_slot;
-    }
-    return W2XC_OK;
+    int rc = p.d_in.reserve(in_bytes, "the input rows");
+    if (!rc) rc = p.d_out.reserve(out_bytes, "the output rows");
+    if (!rc) rc = p.pin_in.reserve(in_slot * HostPipe::IN_SLOTS, "the input staging ring");
+    if (!rc) rc = p.pin_out.reserve(out_slot * HostPipe::OUT_SLOTS, "the output staging ring");
+    return rc;
 }
+
+// (debug aid) the clock of one unit's phase timestamps on stderr: w2xc_opts.verbose & 2
+struct Trace {
+    bool on;
+    std::chrono::steady_clock::time_point t0;
+    double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+// The input side of one unit: source rows [0, svh) of its view (`src` = view row 0), uploaded in order up to a high-water mark -- DMA'd straight from a
+// page-locked plane, staged through the pinned ring otherwise.
+struct Uploader {
+    HostPipe &p;
+    const char *src;
+    size_t in_stride, in_row;
+    int w, svh, chunk_rows, copy_threads;
+    bool pinned;
+    const Trace &tr;
+    int uploaded = 0;    // view rows already queued on s_h2d
+    long seq = 0;        // staging slots used so far
+    double t_done = -1;
+
+    // view rows < s_end are queued on s_h2d; compute_waits: and the launch stream waits for them
+    int upto(int s_end, bool compute_waits = false)
+    {
+        s_end = std::min(s_end, svh);
+        float *const d_in = p.d_in.as<float>();
+        while (uploaded < s_end) {
+            if (pinned) {   // DMA straight from the caller's plane
+                const int rows = s_end - uploaded;
+                const char *from = src + (size_t)uploaded * in_stride;
+                if (in_stride == in_row) HIP_TRY(hipMemcpyAsync(d_in + (size_t)uploaded * w, from, (size_t)rows * in_row, hipMemcpyHostToDevice, p.s_h2d));
+                else HIP_TRY(hipMemcpy2DAsync(d_in + (size_t)uploaded * w, in_row, from, in_stride, in_row, rows, hipMemcpyHostToDevice, p.s_h2d));
+                uploaded = s_end;
+                break;
+            }
+            const int rows = std::min(chunk_rows, s_end - uploaded);
+            const int slot = (int)(seq % HostPipe::IN_SLOTS);
+            if (seq >= HostPipe::IN_SLOTS) HIP_TRY(hipEventSynchronize(p.ev_in_slot[slot]));   // its last DMA has read it
+            char *stage = p.pin_in.as<char>() + (size_t)slot * p.in_slot_bytes();
+            w2xc_host::CopyPool::get().copy_rows(stage, in_row, src + (size_t)uploaded * in_stride, in_stride, in_row, rows, copy_threads);
+            HIP_TRY(hipMemcpyAsync(d_in + (size_t)uploaded * w, stage, (size_t)rows * in_row, hipMemcpyHostToDevice, p.s_h2d));
+            HIP_TRY(hipEventRecord(p.ev_in_slot[slot], p.s_h2d));
+            seq++;
+            uploaded += rows;
+        }
+        if (tr.on && t_done < 0 && uploaded >= svh) t_done = tr.ms();
+        if (compute_waits) {
+            HIP_TRY(hipEventRecord(p.ev_input, p.s_h2d));
+            HIP_TRY(hipStreamWaitEvent(p.s_compute, p.ev_input, 0));
+        }
+        return W2XC_OK;
+    }
+};
+
+// The output side of one unit whose plane is pageable: the drainer thread and everything it shares with the feeder.  The feeder takes a free staging slot,
+// queues the D2H of a chunk into it and submits it; or, for a band whose last layer the launch of layer n - 1 finishes itself (conv3x3_wino4 PROG), waits
+// until the band buffer is free and submits the band.  The drainer copies what arrives into the caller's plane (`out` = its row 0), in order.
+class Stitcher {
+public:
+    Stitcher(HostPipe &p, int dev, char *out, size_t out_stride, size_t out_row, int copy_threads, const Trace &tr)
+        : p_(p), dev_(dev), out_(out), out_stride_(out_stride), out_row_(out_row), copy_threads_(copy_threads), tr_(tr) {}
+    ~Stitcher() { finish(); }   // (an exception in the feeder must not unwind past a joinable thread)
+
+    int take_slot(int *slot)
+    {
+        std::unique_lock<std::mutex> ql(mu_);
+        cv_.wait(ql, [&] { return queued_ - drained_ < HostPipe::OUT_SLOTS; });
+        *slot = (int)(queued_ % HostPipe::OUT_SLOTS);
+        return rc_.load();
+    }
+    // rows [r0, r1) arrive in staging slot `slot` behind its D2H event
+    void submit_chunk(int r0, int r1, int slot) { push(Item{r0, r1, slot}, queued_); }
+    // the band buffers alternate: band s waits until band s - 2 has been stitched (the drainer reads the buffer and its flags until then)
+    int wait_band_free()
+    {
+        std::unique_lock<std::mutex> ql(mu_);
+        cv_.wait(ql, [&] { return bands_drained_ >= bands_ - 1 || rc_.load() != W2XC_OK; });
+        return rc_.load();
+    }
+    // rows [r0, r1) are written by a launch into the page-locked band buffer `src` and flagged per job: job (jr, jg) = rows [16 jr - first, 16 jr - first + 16)
+    // x columns [256 jg, 256 jg + 256) of the band; the drainer follows the flags and stitches rows while the launch runs
+    void submit_band(int r0, int r1, int trows, int groups, int first, const unsigned *flags, unsigned epoch, const char *src)
+    {
+        push(Item{r0, r1, -1, trows, groups, first, flags, epoch, src}, bands_);
+    }
+    long bands() const { return bands_; }   // (the feeder's own count)
+    void finish()
+    {
+        if (!th_.joinable()) return;
+        { std::lock_guard<std::mutex> ql(mu_); done_ = true; }
+        cv_.notify_all();
+        th_.join();
+    }
+    int rc() const { return rc_.load(); }
+    const std::string &error() const { return err_; }   // after finish()
+
+private:
+    struct Item { int r0, r1, slot; int trows = 0, groups = 0, first = 0; const volatile unsigned *flags = nullptr; unsigned epoch = 0; const char *src = nullptr; };
+
+    // (the thread starts with the first item it is handed, not at the call's start: creating a thread costs tens of microseconds the first upload would wait behind)
+    void push(const Item &it, long &counter)
+    {
+        if (!th_.joinable()) th_ = std::thread([this] { run(); });
+        {
+            std::lock_guard<std::mutex> ql(mu_);
+            pending_.push_back(it);
+            counter++;
+        }
+        cv_.notify_all();
+    }
+    void run()
+    {
+        hipSetDevice(dev_);
+        for (;;) {
+            Item it;
+            {
+                std::unique_lock<std::mutex> ql(mu_);
+                cv_.wait(ql, [&] { return !pending_.empty() || done_; });
+                if (pending_.empty()) return;
+                it = pending_.front();
+                pending_.pop_front();
+            }
+            if (it.slot < 0) stitch_band(it);
+            else if (rc_.load() == W2XC_OK) stitch_chunk(it);
+            {
+                std::lock_guard<std::mutex> ql(mu_);
+                (it.slot < 0 ? bands_drained_ : drained_)++;
+            }
+            cv_.notify_all();
+        }
+    }
+    void set_error(int code, const std::string &text) { err_ = text; rc_.store(code); }
+    // `rows` rows from `src` (packed) to the caller's rows from row0 on (a std::bad_alloc / std::system_error on this thread would be std::terminate, not an error code)
+    void copy_out(int row0, const char *src, int rows, const char *what)
+    {
+        try {
+            w2xc_host::CopyPool::get().copy_rows(out_ + (size_t)row0 * out_stride_, out_stride_, src, out_row_, out_row_, rows, copy_threads_);
+        }
+        catch (const std::exception &ex) { set_error(W2XC_ERR_NOMEM, std::string("host copy of ") + what + " failed: " + ex.what()); }
+        catch (...) { set_error(W2XC_ERR_NOMEM, std::string("host copy of ") + what + " failed"); }
+    }
+    void stitch_chunk(const Item &it)
+    {
+        const hipError_t e = hipEventSynchronize(p_.ev_out_slot[it.slot]);
+        if (e != hipSuccess) return set_error(W2XC_ERR_HIP, std::string("hipEventSynchronize(D2H chunk) failed: ") + hipGetErrorString(e));
+        copy_out(it.r0, p_.pin_out.as<char>() + (size_t)it.slot * p_.out_slot_bytes(), it.r1 - it.r0, "a downloaded chunk");
+    }
+    // follow the job flags: tile rows complete top to bottom (roughly); every run of finished tile rows is stitched at once
+    void stitch_band(const Item &it)
+    {
+        const int R = it.r1 - it.r0;
+        int jr = 0, runs = 0;
+        long spins = 0;
+        bool launch_over = false;
+        double t_first_seen = 0, t_last_seen = 0;
+        while (jr < it.trows && rc_.load() == W2XC_OK) {
+            int ready = jr;
+            while (ready < it.trows) {
+                bool all = true;
+                for (int g = 0; g < it.groups && all; g++) all = flag_reached(it.flags[(size_t)ready * it.groups + g], it.epoch);
+                if (!all && !launch_over) break;
+                ready++;
+            }
+            if (ready == jr) {
+                // nothing new: the launch may be over (every row written, the flags' last stores included -- or it failed)
+                if ((++spins & 1023) == 0) {
+                    const hipError_t q = hipStreamQuery(p_.s_compute);
+                    if (q == hipSuccess) launch_over = true;
+                    else if (q != hipErrorNotReady) set_error(W2XC_ERR_HIP, std::string("the launch that finishes the last layer failed: ") + hipGetErrorString(q));
+                }
+#if defined(__x86_64__)
+                __builtin_ia32_pause();
+#endif
+                continue;
+            }
+            std::atomic_thread_fence(std::memory_order_acquire);
+            const auto [a, b] = tile_rows_span(jr, ready, it.first, R);
+            const double t_seen = tr_.on ? tr_.ms() : 0.0;
+            if (b > a) copy_out(it.r0 + a, it.src + (size_t)a * out_row_, b - a, "finished rows");
+            if (tr_.on) {
+                if (runs == 0) t_first_seen = t_seen;
+                runs++;
+                t_last_seen = t_seen;
+            }
+            jr = ready;
+        }
+        if (tr_.on) fprintf(stderr, "[w2xc host] rows %d..%d finished by the launch of layer n-1 itself: %d tile rows stitched in %d runs, first seen %.3f ms, last seen %.3f ms, "
+                                    "stitched %.3f ms%s\n", it.r0, it.r1, it.trows, runs, t_first_seen, t_last_seen, tr_.ms(), launch_over ? " (the launch was over before its last flags were seen)" : "");
+    }
+
+    HostPipe &p_;
+    const int dev_;
+    char *const out_;
+    const size_t out_stride_, out_row_;
+    const int copy_threads_;
+    const Trace &tr_;
+    std::mutex mu_;
+    std::condition_variable cv_;
+    std::deque<Item> pending_;      // submitted, not yet stitched (consumed in order)
+    long queued_ = 0, drained_ = 0;             // slot chunks (slots are used round-robin)
+    long bands_ = 0, bands_drained_ = 0;        // PROG bands handed over / stitched
+    bool done_ = false;
+    std::atomic<int> rc_{W2XC_OK};
+    std::string err_;               // written before rc_, read by the feeder after finish()
+    std::thread th_;
+};
 
 // Output rows [ra, rb) of the (w << up) x (h << up) conversion of the HOST plane `in` (h rows of w floats) on device
 // `dev`, written to rows [ra, rb) of the HOST plane `out`.  One unit of the tile farm: the caller runs one of these
 // per device (threads) or per rank (processes); units never exchange data.
 //
-//   feeder (this thread)   stages the band's source rows (pageable -> pinned slot -> s_h2d), enqueues the band's
+//   feeder (this thread)   stages the band's source rows (Uploader: pageable -> pinned slot -> s_h2d), enqueues the band's
 //                          layers on s_compute, stages the NEXT band's rows while it computes, then launches the
 //                          last layer in row chunks and queues each chunk's D2H on s_d2h into a pinned slot
-//   drainer (one thread)   waits for each chunk's D2H and copies it into the caller's plane (the "stitch" of
+//   drainer (Stitcher)     waits for each chunk's D2H and copies it into the caller's plane (the "stitch" of
 //                          convertRoutine.cpp:143-161), freeing the slot
 // so H2D(band k+1) || layers(band k) || D2H + stitch(band k-1 / earlier chunks).  Planes that are already pinned
 // are DMA'd in place without staging.
@@ -196,8 +375,8 @@ int host_rows_on_device(w2xc_model *m, int dev, const float *in_, size_t in_stri
                         float *out_, size_t out_stride, const w2xc_opts &o, int copy_threads, int in_row0, int out_row0, int hs)
 {
     // `in_` points at source row in_row0, `out_` at output row out_row0: rebase both to row 0 (only rows that exist are touched)
-    const float *in = (const float *)((const char *)in_ - (ptrdiff_t)in_row0 * (ptrdiff_t)in_stride);
-    float *out = (float *)((char *)out_ - (ptrdiff_t)out_row0 * (ptrdiff_t)out_stride);
+    const char *in = (const char *)in_ - (ptrdiff_t)in_row0 * (ptrdiff_t)in_stride;
+    char *out = (char *)out_ - (ptrdiff_t)out_row0 * (ptrdiff_t)out_stride;
     HIP_TRY(hipSetDevice(dev));
     // this thread is the unit's feeder: it (and the drainer it starts, which inherits the affinity) runs on the device's CPU node, and
     // the pinned rings it allocates land there; the caller's affinity is restored on return
@@ -210,328 +389,141 @@ int host_rows_on_device(w2xc_model *m, int dev, const float *in_, size_t in_stri
     HostPipe &p = c->pipe;
     if ((rc = pipe_init(p))) return rc;
 
+    // ---- planning ----
     const int W = w << up, H = h << up;
-    // source rows that cover output rows [ra - hs, rb + hs) (clipped), in source coordinates
-    const int sy0 = std::max(0, ra - hs) >> up, sy1 = (std::min(H, rb + hs) + up) >> up;
-    const int svh = sy1 - sy0;
+    const RowSpan sv = src_rows(ra, rb, hs, up, H);
+    const int sy0 = sv.first, sy1 = sv.second, svh = sy1 - sy0;
     const size_t in_row = (size_t)w * 4, out_row = (size_t)W * 4;
-    const bool in_pinned = host_range_pinned((const char *)in + (size_t)sy0 * in_stride, (size_t)(svh - 1) * in_stride + in_row);
-    const bool out_pinned = host_range_pinned((const char *)out + (size_t)ra * out_stride, (size_t)(rb - ra - 1) * out_stride + out_row);
-    // staging granularity, whole rows: input slices of ~2 MiB; output chunks of at most ~8 MiB tapering to 1/16 of that
-    // (multiples of the 8-row tiles of the last-layer kernels).  w2xc_opts.host_chunk_kb overrides the maximum (test aid).
-    const size_t chunk_max = o.host_chunk_kb > 0 ? (size_t)o.host_chunk_kb << 10 : (size_t)8 << 20;
-    const int in_chunk_rows = (int)std::max<size_t>(1, std::min<size_t>(chunk_max, (size_t)2 << 20) / in_row);
-    const int out_chunk_rows = (int)std::max<size_t>(8, (chunk_max / out_row) & ~(size_t)7);
-    const int out_chunk_min = (int)std::max<size_t>(8, (chunk_max / 16 / out_row) & ~(size_t)7);
-    rc = pipe_reserve(p, (size_t)svh * in_row, (size_t)(rb - ra) * out_row, in_pinned ? 0 : (size_t)in_chunk_rows * in_row,
-                      out_pinned ? 0 : (size_t)out_chunk_rows * out_row);
-    if (rc) return rc;
-
-    const bool trace = (o.verbose & 2) != 0;   // (debug aid) phase timestamps of one unit on stderr
-    const auto t0 = std::chrono::steady_clock::now();
-    auto ms_since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
-    double t_in_done = -1, t_first_out = -1;
-
-    // ---- input side: source rows [0, svh) of this unit's view, uploaded in order up to a high-water mark ----
-    int uploaded = 0;        // view rows already queued on s_h2d
-    long in_seq = 0;         // staging slots used so far
-    auto upload_to = [&](int s_end) -> int {
-        s_end = std::min(s_end, svh);
-        struct Stamp { double &t; bool on; int &up; int all; std::function<double()> now; ~Stamp() { if (on && t < 0 && up >= all) t = now(); } }
-            stamp{t_in_done, trace, uploaded, svh, [&] { return ms_since(t0); }};
-        while (uploaded < s_end) {
-            if (in_pinned) {   // DMA straight from the caller's plane
-                const int rows = s_end - uploaded;
-                const char *src = (const char *)in + (size_t)(sy0 + uploaded) * in_stride;
-                if (in_stride == in_row) HIP_TRY(hipMemcpyAsync(p.d_in + (size_t)uploaded * w, src, (size_t)rows * in_row, hipMemcpyHostToDevice, p.s_h2d));
-                else HIP_TRY(hipMemcpy2DAsync(p.d_in + (size_t)uploaded * w, in_row, src, in_stride, in_row, rows, hipMemcpyHostToDevice, p.s_h2d));
-                uploaded = s_end;
-                break;
-            }
-            const int rows = std::min(in_chunk_rows, s_end - uploaded);
-            const int slot = (int)(in_seq % HostPipe::IN_SLOTS);
-            if (in_seq >= HostPipe::IN_SLOTS) HIP_TRY(hipEventSynchronize(p.ev_in_slot[slot]));   // its last DMA has read it
-            char *stage = p.pin_in + (size_t)slot * p.in_slot_bytes;
-            w2xc_host::CopyPool::get().copy_rows(stage, in_row, (const char *)in + (size_t)(sy0 + uploaded) * in_stride, in_stride, in_row, rows, copy_threads);
-            HIP_TRY(hipMemcpyAsync(p.d_in + (size_t)uploaded * w, stage, (size_t)rows * in_row, hipMemcpyHostToDevice, p.s_h2d));
-            HIP_TRY(hipEventRecord(p.ev_in_slot[slot], p.s_h2d));
-            in_seq++;
-            uploaded += rows;
-        }
-        return W2XC_OK;
-    };
+    const char *in_lo = in + (size_t)sy0 * in_stride, *in_hi = in + (size_t)(sy1 - 1) * in_stride + in_row;
+    const char *out_lo = out + (size_t)ra * out_stride, *out_hi = out + (size_t)(rb - 1) * out_stride + out_row;
+    const bool in_pinned = host_range_pinned(in_lo, (size_t)(in_hi - in_lo)), out_pinned = host_range_pinned(out_lo, (size_t)(out_hi - out_lo));
     // in-place / overlapping planes (the reference never does this, main.cpp:94-96 copies first; a library must survive it):
     // the drainer writes band b's rows while later bands still read theirs, so every source row is staged before any output exists
-    const char *in_lo = (const char *)in + (size_t)sy0 * in_stride, *in_hi = (const char *)in + (size_t)(sy1 - 1) * in_stride + in_row;
-    const char *out_lo = (const char *)out + (size_t)ra * out_stride, *out_hi = (const char *)out + (size_t)(rb - 1) * out_stride + out_row;
     const bool overlap = in_lo < out_hi && out_lo < in_hi;
-    // view rows (source coordinates, relative to sy0) a band of output rows [y0, y1) reads
-    auto band_src_end = [&](int y1) { return overlap ? svh : ((std::min(H, y1 + hs) + up) >> up) - sy0; };
+    const HostChunks ck = host_chunks(o.host_chunk_kb, in_row, out_row);
+    const int l1_chunk = layer1_chunk(ck.in_rows, up);
+    rc = pipe_reserve(p, (size_t)svh * in_row, (size_t)(rb - ra) * out_row, in_pinned ? 0 : (size_t)ck.in_rows * in_row, out_pinned ? 0 : (size_t)ck.out_rows * out_row);
+    if (rc) return rc;
+    const Trace tr{(o.verbose & 2) != 0, std::chrono::steady_clock::now()};
+    double t_first_out = -1;
+    Uploader input{p, in_lo, in_stride, in_row, w, svh, ck.in_rows, copy_threads, in_pinned, tr};
+    Stitcher stitch(p, dev, out, out_stride, out_row, copy_threads, tr);
+    auto src_end = [&](int y1) { return band_src_end(y1, hs, up, H, sy0, overlap, svh); };
 
-    // ---- output side ----
-    // slot >= 0: rows [r0, r1) arrive in staging slot `slot` behind its D2H event.  slot < 0: a band whose last layer the launch of layer n - 1 finishes itself
-    // (conv3x3_wino4 PROG): its gather jobs write the rows into the page-locked band buffer `src` over PCIe and flag them (job (jr, jg) = rows
-    // [16 jr - first, 16 jr - first + 16) x columns [256 jg, 256 jg + 256) of the band); the drainer follows the flags and stitches rows while the launch runs
-    struct Chunk { int r0, r1, slot; int trows = 0, groups = 0, first = 0; const volatile unsigned *flags = nullptr; unsigned epoch = 0; const char *src = nullptr; };
-    std::mutex qmu;
-    std::condition_variable qcv;
-    std::deque<Chunk> pending;     // D2H queued, not yet stitched (drainer consumes in order)
-    long queued = 0, drained = 0;  // chunk counters (slots are used round-robin)
-    long prog_bands = 0, prog_bands_drained = 0;   // PROG bands handed to the drainer / stitched (the band buffers alternate)
-    bool feeder_done = false;
-    std::atomic<int> drain_rc{W2XC_OK};
-    std::string drain_err;
-    // (started with the first chunk it is handed, not at the call's start: creating a thread costs tens of microseconds the first upload would wait behind)
-    std::thread drainer;
-    auto start_drainer = [&] {
-        if (out_pinned || drainer.joinable()) return;
-        drainer = std::thread([&] {
-            hipSetDevice(dev);
-            for (;;) {
-                Chunk ch;
-                {
-                    std::unique_lock<std::mutex> ql(qmu);
-                    qcv.wait(ql, [&] { return !pending.empty() || feeder_done; });
-                    if (pending.empty()) return;
-                    ch = pending.front();
-                    pending.pop_front();
-                }
-                if (ch.slot < 0) {
-                    // follow the job flags: tile rows complete top to bottom (roughly); every run of finished tile rows is stitched at once
-                    const int R = ch.r1 - ch.r0;
-                    int jr = 0, runs = 0;
-                    long spins = 0;
-                    bool launch_over = false;
-                    double t_first_seen = 0, t_last_seen = 0;
-                    while (jr < ch.trows && drain_rc.load() == W2XC_OK) {
-                        int ready = jr;
-                        while (ready < ch.trows) {
-                            bool all = true;
-                            for (int g = 0; g < ch.groups && all; g++) all = (int)(ch.flags[(size_t)ready * ch.groups + g] - ch.epoch) >= 0;
-                            if (!all && !launch_over) break;
-                            ready++;
-                        }
-                        if (ready == jr) {
-                            // nothing new: the launch may be over (every row written, the flags' last stores included -- or it failed)
-                            if ((++spins & 1023) == 0) {
-                                const hipError_t q = hipStreamQuery(p.s_compute);
-                                if (q == hipSuccess) launch_over = true;
-                                else if (q != hipErrorNotReady) {
-                                    drain_err = std::string("the launch that finishes the last layer failed: ") + hipGetErrorString(q);
-                                    drain_rc.store(W2XC_ERR_HIP);
-                                }
-                            }
-#if defined(__x86_64__)
-                            __builtin_ia32_pause();
-#endif
-                            continue;
-                        }
-                        std::atomic_thread_fence(std::memory_order_acquire);
-                        const int a = std::max(0, 16 * jr - ch.first), b = std::min(R, 16 * ready - ch.first);
-                        const double t_seen = trace ? ms_since(t0) : 0.0;
-                        if (b > a) {
-                            try {
-                                w2xc_host::CopyPool::get().copy_rows((char *)out + (size_t)(ch.r0 + a) * out_stride, out_stride, ch.src + (size_t)a * out_row, out_row, out_row,
-                                                                     b - a, copy_threads);
-                            } catch (const std::exception &ex) {
-                                drain_err = std::string("host copy of finished rows failed: ") + ex.what();
-                                drain_rc.store(W2XC_ERR_NOMEM);
-                            } catch (...) {
-                                drain_err = "host copy of finished rows failed";
-                                drain_rc.store(W2XC_ERR_NOMEM);
-                            }
-                        }
-                        if (trace) {
-                            if (runs == 0) t_first_seen = t_seen;
-                            runs++;
-                            t_last_seen = t_seen;
-                        }
-                        jr = ready;
-                    }
-                    if (trace) fprintf(stderr, "[w2xc host] rows %d..%d finished by the launch of layer n-1 itself: %d tile rows stitched in %d runs, first seen %.3f ms, last seen %.3f ms, "
-                                               "stitched %.3f ms%s\n", ch.r0, ch.r1, ch.trows, runs, t_first_seen, t_last_seen, ms_since(t0), launch_over ? " (the launch was over before its last flags were seen)" : "");
-                    {
-                        std::lock_guard<std::mutex> ql(qmu);
-                        prog_bands_drained++;
-                    }
-                    qcv.notify_all();
-                    continue;
-                }
-                if (drain_rc.load() == W2XC_OK) {
-                    hipError_t e = hipEventSynchronize(p.ev_out_slot[ch.slot]);
-                    if (e != hipSuccess) {
-                        drain_err = std::string("hipEventSynchronize(D2H chunk) failed: ") + hipGetErrorString(e);
-                        drain_rc.store(W2XC_ERR_HIP);
-                    } else {
-                        try {   // (a std::bad_alloc / std::system_error on this thread would be std::terminate, not an error code)
-                            w2xc_host::CopyPool::get().copy_rows((char *)out + (size_t)ch.r0 * out_stride, out_stride,
-                                                                 p.pin_out + (size_t)ch.slot * p.out_slot_bytes, out_row, out_row, ch.r1 - ch.r0, copy_threads);
-                        } catch (const std::exception &ex) {
-                            drain_err = std::string("host copy of a downloaded chunk failed: ") + ex.what();
-                            drain_rc.store(W2XC_ERR_NOMEM);
-                        } catch (...) {
-                            drain_err = "host copy of a downloaded chunk failed";
-                            drain_rc.store(W2XC_ERR_NOMEM);
-                        }
-                    }
-                }
-                {
-                    std::lock_guard<std::mutex> ql(qmu);
-                    drained++;
-                }
-                qcv.notify_all();
-            }
-        });
-    };
-    auto finish_drainer = [&] {
-        if (drainer.joinable()) {
-            { std::lock_guard<std::mutex> ql(qmu); feeder_done = true; }
-            qcv.notify_all();
-            drainer.join();
-        }
-    };
-    struct AtExit {   // an exception below (std::bad_alloc in a queue) must not unwind past a joinable thread
-        std::function<void()> f;
-        ~AtExit() { f(); }
-    } join_guard{finish_drainer};
-
+    // ---- the hooks of the band loop: enqueue-only ----
     BandHooks hk;
-    hk.out_chunk_rows = out_chunk_rows;
-    hk.out_chunk_min = out_chunk_min;
-    hk.input_needed = [&](int, int y1) -> int {
-        int r = upload_to(band_src_end(y1));
-        if (r) return r;
-        HIP_TRY(hipEventRecord(p.ev_input, p.s_h2d));
-        HIP_TRY(hipStreamWaitEvent(p.s_compute, p.ev_input, 0));
-        return W2XC_OK;
-    };
-    hk.prefetch = [&](int, int y1n) -> int { return upload_to(band_src_end(y1n)); };
+    hk.out_chunk_rows = ck.out_rows;
+    hk.out_chunk_min = ck.out_min;
+    hk.input_needed = [&](int, int y1) -> int { return input.upto(src_end(y1), true); };
+    hk.prefetch = [&](int, int y1n) -> int { return input.upto(src_end(y1n)); };
     // a band whose rows were prefetched under the previous band is launched whole; otherwise layer 1 follows the upload slice by slice
-    hk.in_chunk = [&](int, int y1) -> int {
-        if (overlap || uploaded >= std::min(band_src_end(y1), svh)) return 0;
-        return std::max(8, ((in_chunk_rows << up) + 7) & ~7);
-    };
-    // the call's first chunks are an eighth, a quarter, a half of a slice: the first launch starts ~30 us into the call instead of behind the first 2 MiB
-    // (pageable: staged by the copy threads first); later chunks are whole slices, every launch of the persistent kernel has a ramp
+    hk.in_chunk = [&](int, int y1) -> int { return overlap || input.uploaded >= std::min(src_end(y1), svh) ? 0 : l1_chunk; };
     hk.in_chunk_at = [&](int c0) -> int {
-        const int full = std::max(8, ((in_chunk_rows << up) + 7) & ~7);
-        if (uploaded > 0 && c0 == 0) return 0;   // (a later band whose first rows were prefetched)
-        return c0 < full / 8 ? full / 8 : c0 < full / 8 + full / 4 ? full / 4 : c0 < full / 8 + full / 4 + full / 2 ? full / 2 : full;
+        if (input.uploaded > 0 && c0 == 0) return 0;   // (a later band whose first rows were prefetched)
+        return taper_chunk(c0, l1_chunk);              // (pageable: staged by the copy threads first)
     };
-    hk.input_upto = [&](int vlast) -> int {
-        int r = upload_to((vlast >> up) + 1);
-        if (r) return r;
-        HIP_TRY(hipEventRecord(p.ev_input, p.s_h2d));
-        HIP_TRY(hipStreamWaitEvent(p.s_compute, p.ev_input, 0));
-        return W2XC_OK;
-    };
+    hk.input_upto = [&](int vlast) -> int { return input.upto((vlast >> up) + 1, true); };
     hk.output_ready = [&](int r0, int r1) -> int {
-        if (trace && t_first_out < 0) t_first_out = ms_since(t0);
+        if (tr.on && t_first_out < 0) t_first_out = tr.ms();
         HIP_TRY(hipEventRecord(p.ev_chunk, p.s_compute));
         HIP_TRY(hipStreamWaitEvent(p.s_d2h, p.ev_chunk, 0));
+        const float *d_out = p.d_out.as<float>();
         if (out_pinned) {
-            char *dst = (char *)out + (size_t)r0 * out_stride;
-            const float *src = p.d_out + (size_t)(r0 - ra) * W;
+            char *dst = out + (size_t)r0 * out_stride;
+            const float *src = d_out + (size_t)(r0 - ra) * W;
             if (out_stride == out_row) HIP_TRY(hipMemcpyAsync(dst, src, (size_t)(r1 - r0) * out_row, hipMemcpyDeviceToHost, p.s_d2h));
             else HIP_TRY(hipMemcpy2DAsync(dst, out_stride, src, out_row, out_row, r1 - r0, hipMemcpyDeviceToHost, p.s_d2h));
             return W2XC_OK;
         }
-        for (int a = r0; a < r1; a += out_chunk_rows) {   // (an unchunked last layer reports the whole band at once)
-            const int b2 = std::min(r1, a + out_chunk_rows);
+        for (int a = r0; a < r1; a += ck.out_rows) {   // (an unchunked last layer reports the whole band at once)
+            const int b2 = std::min(r1, a + ck.out_rows);
             int slot;
-            {
-                std::unique_lock<std::mutex> ql(qmu);
-                qcv.wait(ql, [&] { return queued - drained < HostPipe::OUT_SLOTS; });   // a free staging slot
-                slot = (int)(queued % HostPipe::OUT_SLOTS);
-            }
-            if (drain_rc.load()) return drain_rc.load();
-            HIP_TRY(hipMemcpyAsync(p.pin_out + (size_t)slot * p.out_slot_bytes, p.d_out + (size_t)(a - ra) * W, (size_t)(b2 - a) * out_row,
+            int r = stitch.take_slot(&slot);
+            if (r) return r;
+            HIP_TRY(hipMemcpyAsync(p.pin_out.as<char>() + (size_t)slot * p.out_slot_bytes(), d_out + (size_t)(a - ra) * W, (size_t)(b2 - a) * out_row,
                                    hipMemcpyDeviceToHost, p.s_d2h));
             HIP_TRY(hipEventRecord(p.ev_out_slot[slot], p.s_d2h));
-            start_drainer();
-            {
-                std::lock_guard<std::mutex> ql(qmu);
-                pending.push_back({a, b2, slot});
-                queued++;
-            }
-            qcv.notify_all();
+            stitch.submit_chunk(a, b2, slot);
         }
         return W2XC_OK;
     };
-
     // conv3x3_wino4 PROG: the band's rows are written by the launch of layer n - 1 itself, into the caller's plane when it is page-locked, else into one of
-    // two page-locked band buffers (bands alternate; band s waits for band s - 2 to have been stitched), and flagged per job for the drainer
+    // two page-locked band buffers (bands alternate) and flagged per job for the drainer
     hk.prog_begin = [&](int y0, int y1, int trows, int groups, BandHooks::ProgTail *pt) -> int {
         if (o.fusion == W2XC_FUSION_GATHER_LAUNCH) return W2XC_OK;   // (pt->out stays null: the chunked launches + gather of rounds 4 / 5)
         if (out_pinned) {   // nothing to stitch: the rows are complete when the launch is (the closing synchronisation)
-            pt->out = (float *)((char *)out + (size_t)y0 * out_stride);
+            pt->out = (float *)(out + (size_t)y0 * out_stride);
             pt->out_stride_f = (long long)(out_stride / 4);
             pt->flags = nullptr;
             return W2XC_OK;
         }
-        const int par = (int)(prog_bands & 1);
-        const size_t need = (size_t)(y1 - y0) * out_row, nflags = (size_t)trows * groups;
-        if (p.band_bytes[par] < need) {
-            HIP_TRY(hipStreamSynchronize(p.s_compute));   // (an earlier launch may still write the old buffer)
-            if (p.pin_band[par]) { HIP_TRY(hipHostFree(p.pin_band[par])); p.pin_band[par] = nullptr; p.band_bytes[par] = 0; }
-            // (COHERENT: uncached on the GPU side, every store goes out over PCIe at once -- default host allocations may be cached in the GPU's L2 until the launch
-            //  ends: the system-scope flag then arrived long before the rows it announces, measured)
-            if (hipHostMalloc((void **)&p.pin_band[par], need, hipHostMallocCoherent) != hipSuccess) return fail(W2XC_ERR_NOMEM, "hipHostMalloc(%zu MiB) of the band buffer failed", need >> 20);
-            p.band_bytes[par] = need;
-        }
-        if (p.flags_n[par] < nflags) {
-            HIP_TRY(hipStreamSynchronize(p.s_compute));
-            if (p.pin_flags[par]) { HIP_TRY(hipHostFree(p.pin_flags[par])); p.pin_flags[par] = nullptr; p.flags_n[par] = 0; }
-            if (hipHostMalloc((void **)&p.pin_flags[par], nflags * sizeof(unsigned), hipHostMallocCoherent) != hipSuccess) return fail(W2XC_ERR_NOMEM, "hipHostMalloc of the job flags failed");
-            memset(p.pin_flags[par], 0, nflags * sizeof(unsigned));
-            p.flags_n[par] = nflags;
-            p.flags_epoch[par] = 0;
-        }
-        {   // the buffer's previous band has been stitched
-            std::unique_lock<std::mutex> ql(qmu);
-            qcv.wait(ql, [&] { return prog_bands_drained >= prog_bands - 1 || drain_rc.load() != W2XC_OK; });
-        }
-        if (drain_rc.load()) return drain_rc.load();
-        if (p.flags_epoch[par] == 0x7FFFFFFFu) { memset(p.pin_flags[par], 0, p.flags_n[par] * sizeof(unsigned)); p.flags_epoch[par] = 0; }   // (the epoch comparison is signed: start over, nothing is in flight on this buffer)
-        pt->out = (float *)p.pin_band[par];
+        const int par = (int)(stitch.bands() & 1);
+        ProgFlags &fl = p.flags[par];
+        // (first: the drainer may still read this buffer and its flags for band s - 2, and either may be about to grow)
+        int r = stitch.wait_band_free();
+        if (!r) r = p.pin_band[par].reserve((size_t)(y1 - y0) * out_row, "the band buffer");
+        if (!r) r = fl.reserve((size_t)trows * groups);
+        if (r) return r;
+        pt->out = p.pin_band[par].as<float>();
         pt->out_stride_f = (long long)W;
-        pt->flags = p.pin_flags[par];
-        pt->epoch = ++p.flags_epoch[par];
+        pt->flags = fl.words.as<unsigned>();
+        pt->epoch = fl.next_epoch();   // (nothing is in flight on this buffer)
         return W2XC_OK;
     };
     hk.prog_launched = [&](int y0, int y1, int trows, int groups, int first) -> int {
-        if (trace && t_first_out < 0) t_first_out = ms_since(t0);
+        if (tr.on && t_first_out < 0) t_first_out = tr.ms();
         if (out_pinned) return W2XC_OK;
-        const int par = (int)(prog_bands & 1);
-        Chunk ch{y0, y1, -1};
-        ch.trows = trows; ch.groups = groups; ch.first = first;
-        ch.flags = p.pin_flags[par]; ch.epoch = p.flags_epoch[par]; ch.src = p.pin_band[par];
-        start_drainer();
-        {
-            std::lock_guard<std::mutex> ql(qmu);
-            pending.push_back(ch);
-            prog_bands++;
-        }
-        qcv.notify_all();
+        const int par = (int)(stitch.bands() & 1);
+        stitch.submit_band(y0, y1, trows, groups, first, p.flags[par].words.as<unsigned>(), p.flags[par].epoch(), p.pin_band[par].as<char>());
         return W2XC_OK;
     };
 
-    rc = run_rows(m, c, p.d_in, w, svh << up, sy0 << up, W, ra, rb, p.d_out, W, p.s_compute, o, up, 1, 0, 0, &hk, H);
-    const double t_enq = ms_since(t0);
+    rc = run_rows(m, c, p.d_in.as<float>(), w, svh << up, sy0 << up, W, ra, rb, p.d_out.as<float>(), W, p.s_compute, o, up, 1, 0, 0, &hk, H);
+    const double t_enq = tr.ms();
     double t_comp = 0;
     // (not while a PROG band is being followed: the drainer polls hipStreamQuery on the same stream, and a synchronise in flight here holds it up until the launch ends)
-    if (trace && prog_bands == 0) { hipStreamSynchronize(p.s_compute); t_comp = ms_since(t0); }
+    if (tr.on && stitch.bands() == 0) { hipStreamSynchronize(p.s_compute); t_comp = tr.ms(); }
     std::string err = g_last_error;
-    finish_drainer();
-    if (trace) fprintf(stderr, "[w2xc host] device %d (cpu node %d%s) rows %d..%d: input queued %.3f ms, first output chunk enqueued %.3f ms, enqueued %.3f ms, layers done %.3f ms, stitched %.3f ms (in %s, out %s, %d copy threads)\n",
-                       dev, node_guard.node, node_guard.bound ? ", threads bound" : "", ra, rb, t_in_done, t_first_out, t_enq, t_comp,
-                       ms_since(t0), in_pinned ? "pinned" : "pageable", out_pinned ? "pinned" : "pageable", copy_threads);
+    stitch.finish();
+    if (tr.on) fprintf(stderr, "[w2xc host] device %d (cpu node %d%s) rows %d..%d: input queued %.3f ms, first output chunk enqueued %.3f ms, enqueued %.3f ms, layers done %.3f ms, stitched %.3f ms (in %s, out %s, %d copy threads)\n",
+                       dev, node_guard.node, node_guard.bound ? ", threads bound" : "", ra, rb, input.t_done, t_first_out, t_enq, t_comp,
+                       tr.ms(), in_pinned ? "pinned" : "pageable", out_pinned ? "pinned" : "pageable", copy_threads);
     // leave nothing in flight, whatever happened: the pipe and the caller's planes are reused by the next call
     hipError_t e1 = hipStreamSynchronize(p.s_h2d), e2 = hipStreamSynchronize(p.s_compute), e3 = hipStreamSynchronize(p.s_d2h);
     if (rc) { g_last_error = err; return rc; }
-    if (drain_rc.load()) return fail(drain_rc.load(), "%s", drain_err.c_str());
+    if (stitch.rc()) return fail(stitch.rc(), "%s", stitch.error().c_str());
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess)
         return fail(W2XC_ERR_HIP, "stream synchronisation failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2 != hipSuccess ? e2 : e3));
+    return W2XC_OK;
+}
+
+// fn(t) for every unit t < nd: on this thread when nd == 1, else one thread each.  No exception leaves a unit's thread (std::terminate) or crosses the C ABI;
+// the caller's device is restored; the first failing unit's code is returned and its message is w2xc_last_error() (the C++ adapter prints it, a C-ABI
+// consumer decides itself).  `what` names a unit in the messages.
+int run_units(int nd, const char *what, const std::function<int(int)> &fn)
+{
+    int prev = 0;
+    hipGetDevice(&prev);
+    std::vector<int> rcs(nd, W2XC_OK);
+    std::vector<std::string> errs(nd);
+    auto worker = [&](int t) {
+        try {
+            rcs[t] = fn(t);
+            if (rcs[t]) errs[t] = g_last_error;
+        }
+        catch (const std::bad_alloc &) { rcs[t] = W2XC_ERR_NOMEM; errs[t] = std::string("out of host memory in ") + what; }
+        catch (const std::exception &ex) { rcs[t] = W2XC_ERR_HIP; errs[t] = std::string("exception in ") + what + ": " + ex.what(); }
+        catch (...) { rcs[t] = W2XC_ERR_HIP; errs[t] = std::string("unknown exception in ") + what; }
+    };
+    if (nd == 1) worker(0);
+    else {
+        std::vector<std::thread> th;
+        for (int t = 0; t < nd; t++) th.emplace_back(worker, t);
+        for (auto &x : th) x.join();
+    }
+    hipSetDevice(prev);
+    for (int t = 0; t < nd; t++)
+        if (rcs[t]) { g_last_error = errs[t]; return rcs[t]; }
     return W2XC_OK;
 }
 
@@ -553,7 +545,7 @@ int convert_plane_host(w2xc_model *m, const float *in, size_t in_stride_bytes, i
     if (m->layers.empty()) return fail(W2XC_ERR_ARG, "model has no layers");
     {   // the source rows handed over must cover the rows [row_begin - n, row_end + n) reads (clipped to the plane)
         const int n = (int)m->layers.size();
-        const int need0 = std::max(0, row_begin - n) >> up, need1 = (std::min(H, row_end + n) + up) >> up;
+        const auto [need0, need1] = src_rows(row_begin, row_end, n, up, H);
         if (in_rows < 0) in_rows = h - in_row0;
         if (in_row0 < 0 || in_row0 > need0 || in_row0 + in_rows < need1 || in_row0 + in_rows > h)
             return fail(W2XC_ERR_ARG, "source rows [%d,%d) do not cover the rows [%d,%d) this row range reads", in_row0, in_row0 + in_rows, need0, need1);
@@ -564,7 +556,7 @@ int convert_plane_host(w2xc_model *m, const float *in, size_t in_stride_bytes, i
     int hs = (int)m->layers.size();
     if (uses_wino4(m, o)) {
         const int h4 = 4 * hs;
-        const int need0 = std::max(0, row_begin - h4) >> up, need1 = (std::min(H, row_end + h4) + up) >> up;
+        const auto [need0, need1] = src_rows(row_begin, row_end, h4, up, H);
         if (in_row0 <= need0 && in_row0 + in_rows >= need1) hs = h4;
         else if (o.kernel == W2XC_KERNEL_AUTO)   // (as run_rows: no silent change of kernel and rounding with the view's halo)
             return fail(W2XC_ERR_ARG, "source rows [%d,%d) hold the minimum halo only: the default F(4x4) kernel needs rows [%d,%d) (4 halo rows per layer) for "
@@ -595,7 +587,7 @@ int convert_plane_host(w2xc_model *m, const float *in, size_t in_stride_bytes, i
     // (convertRoutine.cpp:35,96); here the source rows are snapshotted once before the units fan out.
     std::vector<float> snapshot;
     if (nd > 1) {
-        const int s0 = std::max(0, row_begin - hs) >> up, s1 = (std::min(H, row_end + hs) + up) >> up;
+        const auto [s0, s1] = src_rows(row_begin, row_end, hs, up, H);
         const char *in_lo = (const char *)in + (ptrdiff_t)(s0 - in_row0) * (ptrdiff_t)in_stride_bytes;
         const char *in_hi = (const char *)in + (ptrdiff_t)(s1 - 1 - in_row0) * (ptrdiff_t)in_stride_bytes + (size_t)w * 4;
         const char *out_lo = (const char *)out, *out_hi = (const char *)out + (size_t)(R - 1) * out_stride_bytes + (size_t)W * 4;
@@ -614,37 +606,10 @@ int convert_plane_host(w2xc_model *m, const float *in, size_t in_stride_bytes, i
     // lazily from there would keep that node's mask while serving every device
     w2xc_host::CopyPool::get().reserve(std::min(w2xc_get_jobs(), 32) - 1);
 
-    int prev = 0;
-    hipGetDevice(&prev);
-    std::vector<int> rcs(nd, W2XC_OK);
-    std::vector<std::string> errs(nd);
-    auto worker = [&](int t) {
-        // contiguous share [ra, rb) of the OUTPUT rows for unit t: independent, no exchange
-        const int ra = row_begin + (int)((long long)R * t / nd), rb = row_begin + (int)((long long)R * (t + 1) / nd);
-        try {   // no exception may leave a unit's thread (std::terminate) or cross the C ABI
-            rcs[t] = host_rows_on_device(m, devs[t], in, in_stride_bytes, w, h, up, ra, rb, out, out_stride_bytes, o, copy_threads, in_row0, row_begin, hs);
-            if (rcs[t]) errs[t] = g_last_error;
-        } catch (const std::bad_alloc &) {
-            rcs[t] = W2XC_ERR_NOMEM;
-            errs[t] = "out of host memory in a conversion unit";
-        } catch (const std::exception &ex) {
-            rcs[t] = W2XC_ERR_HIP;
-            errs[t] = std::string("exception in a conversion unit: ") + ex.what();
-        } catch (...) {
-            rcs[t] = W2XC_ERR_HIP;
-            errs[t] = "unknown exception in a conversion unit";
-        }
-    };
-    if (nd == 1) worker(0);
-    else {
-        std::vector<std::thread> th;
-        for (int t = 0; t < nd; t++) th.emplace_back(worker, t);
-        for (auto &x : th) x.join();
-    }
-    hipSetDevice(prev);
-    for (int t = 0; t < nd; t++)
-        if (rcs[t]) { g_last_error = errs[t]; return rcs[t]; }   // (the message is w2xc_last_error(); the C++ adapter prints it, a C-ABI consumer decides itself)
-    return W2XC_OK;
+    return run_units(nd, "a conversion unit", [&](int t) {
+        const auto [ra, rb] = unit_rows(row_begin, row_end, t, nd);
+        return host_rows_on_device(m, devs[t], in, in_stride_bytes, w, h, up, ra, rb, out, out_stride_bytes, o, copy_threads, in_row0, row_begin, hs);
+    });
 }
 
 // ---- batches of same-size images from host memory (w2xc_convert_batch: float planes; w2xc_process_image_u8_batch: uint8 images) ----
@@ -680,7 +645,7 @@ int batch_host_on_device(const HostBatch &b, int dev, const w2xc_opts &o, int co
     auto stitch = [&](int j) -> int {   // sub-batch j's pageable images out of its pinned slot, behind its download
         const int os = j % HostPipe::OUT_SLOTS;
         HIP_TRY(hipEventSynchronize(p.ev_out_slot[os]));
-        const char *stage = p.pin_out + (size_t)os * p.out_slot_bytes;
+        const char *stage = p.pin_out.as<char>() + (size_t)os * p.out_slot_bytes();
         for (int k = 0; k < subs[j].second; k++) {
             const int i = subs[j].first + k;
             if (!out_pin[i])
@@ -690,11 +655,11 @@ int batch_host_on_device(const HostBatch &b, int dev, const w2xc_opts &o, int co
     };
     for (int j = 0; j < (int)subs.size(); j++) {
         const int first = subs[j].first, cnt = subs[j].second, slot = j & 1;
-        char *din = (char *)p.d_in + (size_t)slot * sub * in_img, *dout = (char *)p.d_out + (size_t)slot * sub * out_img;
+        char *din = p.d_in.as<char>() + (size_t)slot * sub * in_img, *dout = p.d_out.as<char>() + (size_t)slot * sub * out_img;
         // ---- upload into device slot `slot` once the launches of sub-batch j - 2 have read it ----
         if (j >= 2) HIP_TRY(hipStreamWaitEvent(p.s_h2d, p.ev_batch[slot], 0));
         const int is = j % HostPipe::IN_SLOTS;
-        char *stage = any_in_pageable ? p.pin_in + (size_t)is * p.in_slot_bytes : nullptr;
+        char *stage = any_in_pageable ? p.pin_in.as<char>() + (size_t)is * p.in_slot_bytes() : nullptr;
         if (any_in_pageable && j >= HostPipe::IN_SLOTS) HIP_TRY(hipEventSynchronize(p.ev_in_slot[is]));   // its last DMA has read it
         for (int k = 0; k < cnt; k++) {
             const int i = first + k;
@@ -720,7 +685,7 @@ int batch_host_on_device(const HostBatch &b, int dev, const w2xc_opts &o, int co
         for (int k = 0; k < cnt; k++) {
             const int i = first + k;
             if (out_pin[i]) HIP_TRY(hipMemcpy2DAsync(b.out[i], b.out_stride, dout + (size_t)k * out_img, out_row, out_row, b.out_rows, hipMemcpyDeviceToHost, p.s_d2h));
-            else HIP_TRY(hipMemcpyAsync(p.pin_out + (size_t)os * p.out_slot_bytes + (size_t)k * out_img, dout + (size_t)k * out_img, out_row * b.out_rows,
+            else HIP_TRY(hipMemcpyAsync(p.pin_out.as<char>() + (size_t)os * p.out_slot_bytes() + (size_t)k * out_img, dout + (size_t)k * out_img, out_row * b.out_rows,
                                         hipMemcpyDeviceToHost, p.s_d2h));
         }
         HIP_TRY(hipEventRecord(p.ev_out_slot[os], p.s_d2h));
@@ -753,11 +718,8 @@ int batch_host_run(const HostBatch &b, const w2xc_opts &o, int sub)
     int rc = host_devices(o, &devs);
     if (rc) return rc;
     const int n = b.n;
-    sub = std::min(sub, std::max(1, (n + 2 * (int)devs.size() - 1) / (2 * (int)devs.size())));
-    const int nsub = (n + sub - 1) / sub;
-    const int nd = std::min((int)devs.size(), nsub);
-    std::vector<std::vector<std::pair<int, int>>> share(nd);   // sub-batches striped over the devices
-    for (int j = 0; j < nsub; j++) share[j % nd].push_back({j * sub, std::min(sub, n - j * sub)});
+    const auto share = batch_stripes(n, batch_stripe_sub(sub, n, (int)devs.size()), (int)devs.size());
+    const int nd = (int)share.size();
     const size_t in_ext = (size_t)(b.in_rows - 1) * b.in_stride + b.in_row, out_ext = (size_t)(b.out_rows - 1) * b.out_stride + b.out_row;
     std::vector<char> in_pin(n), out_pin(n);
     for (int i = 0; i < n; i++) {
@@ -766,35 +728,7 @@ int batch_host_run(const HostBatch &b, const w2xc_opts &o, int sub)
     }
     const int copy_threads = std::max(1, std::min(w2xc_get_jobs(), 32) / nd);
     w2xc_host::CopyPool::get().reserve(std::min(w2xc_get_jobs(), 32) - 1);
-    int prev = 0;
-    hipGetDevice(&prev);
-    std::vector<int> rcs(nd, W2XC_OK);
-    std::vector<std::string> errs(nd);
-    auto worker = [&](int t) {
-        try {
-            rcs[t] = batch_host_on_device(b, devs[t], o, copy_threads, share[t], in_pin, out_pin);
-            if (rcs[t]) errs[t] = g_last_error;
-        } catch (const std::bad_alloc &) {
-            rcs[t] = W2XC_ERR_NOMEM;
-            errs[t] = "out of host memory in a batch unit";
-        } catch (const std::exception &ex) {
-            rcs[t] = W2XC_ERR_HIP;
-            errs[t] = std::string("exception in a batch unit: ") + ex.what();
-        } catch (...) {
-            rcs[t] = W2XC_ERR_HIP;
-            errs[t] = "unknown exception in a batch unit";
-        }
-    };
-    if (nd == 1) worker(0);
-    else {
-        std::vector<std::thread> th;
-        for (int t = 0; t < nd; t++) th.emplace_back(worker, t);
-        for (auto &x : th) x.join();
-    }
-    hipSetDevice(prev);
-    for (int t = 0; t < nd; t++)
-        if (rcs[t]) { g_last_error = errs[t]; return rcs[t]; }
-    return W2XC_OK;
+    return run_units(nd, "a batch unit", [&](int t) { return batch_host_on_device(b, devs[t], o, copy_threads, share[t], in_pin, out_pin); });
 }
 
 // byte ranges of n host images in / out ([ptr, ptr + ext)): no null pointer, no output that overlaps another output or an input

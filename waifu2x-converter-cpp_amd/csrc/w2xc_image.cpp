@@ -1,25 +1,18 @@
 // w2xc_image.cpp -- N2: the CLI's image pipeline around the plane conversion -- uint8 BGR -> float YUV, the noise /
 // scale passes on Y through run_rows, bicubic U/V, the final shrink, YUV -> uint8 (main.cpp:74-76,83-98,126-172).
 #include "w2xc_engine.hpp"
+#include "w2xc_host_geom.hpp"
 
 namespace w2xc_eng {
 
 namespace {
 
+// the Y / U / V planes of both image pipelines live in the owning context's aux buffer
+int reserve_aux(DevCtx *c, size_t floats) { return c->aux.reserve(floats * sizeof(float), "the image planes"); }
+
 // noise (optional, main.cpp:83-98) then `iterations` 2x scale steps (optional model, main.cpp:126-156).
 // `c` is the context that owns the plane buffer (the scale model's when present, else the noise model's);
 // cn / cs are the contexts of the two models (locked by the caller).
-// final size of the pipeline: (w << iterations) x (h << iterations), then the optional shrink of main.cpp:158-167
-void final_size(int w, int h, int iterations, double shrink, int *fw, int *fh)
-{
-    *fw = w << iterations;
-    *fh = h << iterations;
-    if (shrink > 0.0) {
-        *fw = static_cast<int>(static_cast<double>(*fw * shrink));   // :160-165
-        *fh = static_cast<int>(static_cast<double>(*fh * shrink));
-    }
-}
-
 int process_image_device(w2xc_model *mn, DevCtx *cn, w2xc_model *msc, DevCtx *cs, const unsigned char *d_in, size_t in_stride, int w,
                          int h, unsigned char *d_out, size_t out_stride, int iterations, double shrink, hipStream_t st, const w2xc_opts &o)
 {
@@ -30,13 +23,8 @@ int process_image_device(w2xc_model *mn, DevCtx *cn, w2xc_model *msc, DevCtx *cs
     int fw, fh;
     final_size(w, h, iterations, shrink, &fw, &fh);
     if (shrink > 0.0) need += 3 * (size_t)fw * fh;
-    if (c->aux_floats < need) {
-        if (c->aux) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->aux)); c->aux = nullptr; c->aux_floats = 0; }
-        hipError_t e = hipMalloc((void **)&c->aux, need * sizeof(float));
-        if (e != hipSuccess) return fail(W2XC_ERR_NOMEM, "hipMalloc(%zu MiB) for the image planes failed: %s", (need * 4) >> 20, hipGetErrorString(e));
-        c->aux_floats = need;
-    }
-    float *base = c->aux;
+    if (int rc = reserve_aux(c, need)) return rc;
+    float *base = c->aux.as<float>();
     int cw = w, ch = h;
     float *y = base, *u = y + (size_t)cw * ch, *v = u + (size_t)cw * ch, *yn = v + (size_t)cw * ch;
     base = yn + (size_t)cw * ch;
@@ -69,18 +57,6 @@ int process_image_device(w2xc_model *mn, DevCtx *cn, w2xc_model *msc, DevCtx *cs
 }
 
 // ---- batches of same-size images (w2xc_process_image_u8_batch*) ----
-// float planes of ONE image over all levels of the pipeline: what process_image_device allocates, every plane on a 256-byte boundary
-size_t plane_floats(int w, int h) { return ((size_t)w * h + 63) & ~(size_t)63; }
-size_t image_aux_floats(int w, int h, int iterations, double shrink)
-{
-    size_t need = 4 * plane_floats(w, h);
-    for (int i = 1; i <= iterations; i++) need += 3 * plane_floats(w << i, h << i);
-    int fw, fh;
-    final_size(w, h, iterations, shrink, &fw, &fh);
-    if (shrink > 0.0) need += 3 * plane_floats(fw, fh);
-    return need;
-}
-
 // Images per sub-batch: as many as w2xc_opts.workspace_mb holds of the pipeline's own memory per image (the float planes of every level + the uint8 image
 // in and out), at most the sub-batch run_batch takes at the LARGEST level where its batched chain applies (more images would only be cut again there, and
 // the planes of a larger sub-batch would be memory without a launch saved), at least 1.  Also where the options' errors surface (host arithmetic only).
@@ -119,13 +95,8 @@ int process_image_batch_device(w2xc_model *mn, DevCtx *cn, w2xc_model *msc, DevC
     const size_t need = image_aux_floats(w, h, iterations, shrink) * (size_t)cap;
     int fw, fh;
     final_size(w, h, iterations, shrink, &fw, &fh);
-    if (c->aux_floats < need) {
-        if (c->aux) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->aux)); c->aux = nullptr; c->aux_floats = 0; }
-        hipError_t e = hipMalloc((void **)&c->aux, need * sizeof(float));
-        if (e != hipSuccess) return fail(W2XC_ERR_NOMEM, "hipMalloc(%zu MiB) for the image planes failed: %s", (need * 4) >> 20, hipGetErrorString(e));
-        c->aux_floats = need;
-    }
-    float *base = c->aux;
+    if (int rc = reserve_aux(c, need)) return rc;
+    float *base = c->aux.as<float>();
     int cw = w, ch = h;
     long long ps = (long long)plane_floats(cw, ch);
     float *y = base, *u = y + (size_t)S * ps, *v = u + (size_t)S * ps, *yn = v + (size_t)S * ps;
@@ -156,29 +127,36 @@ int process_image_batch_device(w2xc_model *mn, DevCtx *cn, w2xc_model *msc, DevC
     return W2XC_OK;
 }
 
-// Both contexts of a noise + scale call, taken TOGETHER (std::lock's deadlock avoidance): two threads that pass the same two models in opposite
-// roles -- (A as noise, B as scale) and (B as noise, A as scale) -- would otherwise each hold one mutex and wait for the other.
-void lock_contexts(DevCtx *cn, DevCtx *cs, std::unique_lock<std::mutex> &l1, std::unique_lock<std::mutex> &l2)
+// The contexts of the (up to two) models of an image call on `dev`; with l1 / l2 they are locked, TOGETHER (std::lock's deadlock avoidance): two threads
+// that pass the same two models in opposite roles -- (A as noise, B as scale) and (B as noise, A as scale) -- would otherwise each hold one mutex and
+// wait for the other.  The plane buffers and the host pipeline are the owning context's: the scale model's when present.
+struct ImageCtx {
+    DevCtx *cn = nullptr, *cs = nullptr;
+    DevCtx *owner() const { return cs ? cs : cn; }
+};
+int image_contexts(w2xc_model *mn, w2xc_model *msc, int dev, ImageCtx *ic, std::unique_lock<std::mutex> *l1 = nullptr, std::unique_lock<std::mutex> *l2 = nullptr)
 {
-    if (cn && cs && cn != cs) {
-        l1 = std::unique_lock<std::mutex>(cn->mu, std::defer_lock);
-        l2 = std::unique_lock<std::mutex>(cs->mu, std::defer_lock);
-        std::lock(l1, l2);
-    } else if (cn) l1 = std::unique_lock<std::mutex>(cn->mu);
-    else if (cs) l1 = std::unique_lock<std::mutex>(cs->mu);
+    int rc;
+    if (mn && (rc = get_ctx(mn, dev, &ic->cn))) return rc;
+    if (msc && (rc = get_ctx(msc, dev, &ic->cs))) return rc;
+    if (!l1) return W2XC_OK;
+    // (at least one model: check_process_args has refused a call without any before a context is asked for)
+    if (ic->cn && ic->cs && ic->cn != ic->cs) {
+        *l1 = std::unique_lock<std::mutex>(ic->cn->mu, std::defer_lock);
+        *l2 = std::unique_lock<std::mutex>(ic->cs->mu, std::defer_lock);
+        std::lock(*l1, *l2);
+    } else *l1 = std::unique_lock<std::mutex>(ic->owner()->mu);
+    return W2XC_OK;
 }
 
 // resolve device + contexts of the (up to two) models and run the pipeline under their locks
 int process_image_locked(w2xc_model *mn, w2xc_model *msc, const unsigned char *d_in, size_t in_stride, int w, int h, unsigned char *d_out,
                          size_t out_stride, int iterations, double shrink, hipStream_t st, const w2xc_opts &o, int dev)
 {
-    DevCtx *cn = nullptr, *cs = nullptr;
-    int rc;
-    if (mn && (rc = get_ctx(mn, dev, &cn))) return rc;
-    if (msc && (rc = get_ctx(msc, dev, &cs))) return rc;
+    ImageCtx ic;
     std::unique_lock<std::mutex> l1, l2;
-    lock_contexts(cn, cs, l1, l2);
-    return process_image_device(mn, cn, msc, cs, d_in, in_stride, w, h, d_out, out_stride, iterations, shrink, st, o);
+    if (int rc = image_contexts(mn, msc, dev, &ic, &l1, &l2)) return rc;
+    return process_image_device(mn, ic.cn, msc, ic.cs, d_in, in_stride, w, h, d_out, out_stride, iterations, shrink, st, o);
 }
 
 int check_process_args(const w2xc_model *mn, const w2xc_model *msc, int iterations)
@@ -213,23 +191,16 @@ int process_image_host(w2xc_model *mn, w2xc_model *msc, const unsigned char *in,
     final_size(w, h, iterations, shrink, &W, &H);
     // contexts of the (up to two) models, locked for the whole call: the device copies of the image live in the owning context
     // (the scale model's when present) and are kept between calls -- no hipMalloc / hipFree per image
-    DevCtx *cn = nullptr, *cs = nullptr;
-    int rc;
-    if (mn && (rc = get_ctx(mn, dev, &cn))) return rc;
-    if (msc && (rc = get_ctx(msc, dev, &cs))) return rc;
+    ImageCtx ic;
     std::unique_lock<std::mutex> l1, l2;
-    lock_contexts(cn, cs, l1, l2);
-    DevCtx *c = cs ? cs : cn;
+    int rc = image_contexts(mn, msc, dev, &ic, &l1, &l2);
+    if (rc) return rc;
+    DevCtx *c = ic.owner();
     const size_t in_bytes = ((size_t)w * 3 * h + 255) & ~(size_t)255, out_bytes = (size_t)W * 3 * H;
-    if (c->img_io_bytes < in_bytes + out_bytes) {
-        if (c->img_io) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->img_io)); c->img_io = nullptr; c->img_io_bytes = 0; }
-        if (hipMalloc((void **)&c->img_io, in_bytes + out_bytes) != hipSuccess)
-            return fail(W2XC_ERR_NOMEM, "hipMalloc(%zu MiB) for the image failed", (in_bytes + out_bytes) >> 20);
-        c->img_io_bytes = in_bytes + out_bytes;
-    }
-    unsigned char *d_in = c->img_io, *d_out = c->img_io + in_bytes;
+    if ((rc = c->img_io.reserve(in_bytes + out_bytes, "the image"))) return rc;
+    unsigned char *d_in = c->img_io.as<unsigned char>(), *d_out = d_in + in_bytes;
     HIP_TRY(hipMemcpy2D(d_in, (size_t)w * 3, in, in_stride, (size_t)w * 3, h, hipMemcpyHostToDevice));
-    rc = process_image_device(mn, cn, msc, cs, d_in, (size_t)w * 3, w, h, d_out, (size_t)W * 3, iterations, shrink, nullptr, o);
+    rc = process_image_device(mn, ic.cn, msc, ic.cs, d_in, (size_t)w * 3, w, h, d_out, (size_t)W * 3, iterations, shrink, nullptr, o);
     if (rc) { hipDeviceSynchronize(); return rc; }
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy2D(out, out_stride, d_out, (size_t)W * 3, (size_t)W * 3, H, hipMemcpyDeviceToHost));
@@ -330,13 +301,11 @@ try {
     if (dev < 0) HIP_TRY(hipGetDevice(&dev));
     DeviceGuard guard(dev);
     if (!guard.ok) return fail(W2XC_ERR_HIP, "cannot select HIP device %d", dev);
-    DevCtx *cn = nullptr, *cs = nullptr;
-    if (noise_model && (rc = get_ctx(noise_model, dev, &cn))) return rc;
-    if (scale_model && (rc = get_ctx(scale_model, dev, &cs))) return rc;
+    ImageCtx ic;
     std::unique_lock<std::mutex> l1, l2;
-    lock_contexts(cn, cs, l1, l2);
+    if ((rc = image_contexts(noise_model, scale_model, dev, &ic, &l1, &l2))) return rc;
     for (int b0 = 0; b0 < n; b0 += sub) {
-        rc = process_image_batch_device(noise_model, cn, scale_model, cs, std::min(sub, n - b0), sub, d_in + (size_t)b0 * in_image_stride_bytes,
+        rc = process_image_batch_device(noise_model, ic.cn, scale_model, ic.cs, std::min(sub, n - b0), sub, d_in + (size_t)b0 * in_image_stride_bytes,
                                         in_image_stride_bytes, in_stride_bytes, w, h, d_out + (size_t)b0 * out_image_stride_bytes, out_image_stride_bytes,
                                         out_stride_bytes, iterations, shrink_ratio, (hipStream_t)hip_stream, o);
         if (rc) return rc;
@@ -370,26 +339,19 @@ try {
     b.in_row = (size_t)w * 3; b.out_row = (size_t)W * 3;
     b.in_rows = h; b.out_rows = H;
     b.in_img = (b.in_row * h + 255) & ~(size_t)255; b.out_img = (b.out_row * H + 255) & ~(size_t)255;
-    // both models' contexts, locked together for this device's share of the call; the pipeline is the owning context's (the scale model's when present)
-    auto contexts = [&](int dev, DevCtx **cn, DevCtx **cs) -> int {
-        int r;
-        if (noise_model && (r = get_ctx(noise_model, dev, cn))) return r;
-        if (scale_model && (r = get_ctx(scale_model, dev, cs))) return r;
-        return W2XC_OK;
-    };
+    // both models' contexts, locked together for this device's share of the call; the pipeline is the owning context's
     b.acquire = [&](int dev, std::unique_lock<std::mutex> &l1, std::unique_lock<std::mutex> &l2, HostPipe **pipe) -> int {
-        DevCtx *cn = nullptr, *cs = nullptr;
-        int r = contexts(dev, &cn, &cs);
+        ImageCtx ic;
+        int r = image_contexts(noise_model, scale_model, dev, &ic, &l1, &l2);
         if (r) return r;
-        lock_contexts(cn, cs, l1, l2);
-        *pipe = &(cs ? cs : cn)->pipe;
+        *pipe = &ic.owner()->pipe;
         return W2XC_OK;
     };
     b.run = [&](int dev, int cnt, const void *din, void *dout, hipStream_t st, int max_sub) -> int {
-        DevCtx *cn = nullptr, *cs = nullptr;
-        int r = contexts(dev, &cn, &cs);
+        ImageCtx ic;
+        int r = image_contexts(noise_model, scale_model, dev, &ic);
         if (r) return r;
-        return process_image_batch_device(noise_model, cn, scale_model, cs, cnt, max_sub, (const unsigned char *)din, b.in_img, b.in_row, w, h,
+        return process_image_batch_device(noise_model, ic.cn, scale_model, ic.cs, cnt, max_sub, (const unsigned char *)din, b.in_img, b.in_row, w, h,
                                           (unsigned char *)dout, b.out_img, b.out_row, iterations, shrink_ratio, st, o);
     };
     return batch_host_run(b, o, sub);

@@ -110,21 +110,6 @@ int get_ctx(w2xc_model *m, int device, DevCtx **out)
     return W2XC_OK;
 }
 
-int ensure_ws(DevCtx *c, int which, size_t floats)
-{
-    if (c->ws_floats[which] >= floats) return W2XC_OK;
-    if (c->ws[which]) {
-        HIP_TRY(hipDeviceSynchronize());   // earlier launches may still use the old buffer
-        HIP_TRY(hipFree(c->ws[which]));
-        c->ws[which] = nullptr;
-        c->ws_floats[which] = 0;
-    }
-    hipError_t e = hipMalloc((void **)&c->ws[which], floats * sizeof(float));
-    if (e != hipSuccess) return fail(W2XC_ERR_NOMEM, "hipMalloc(%zu MiB) for the activation workspace failed: %s", (floats * 4) >> 20, hipGetErrorString(e));
-    c->ws_floats[which] = floats;
-    return W2XC_OK;
-}
-
 int prof_begin(DevCtx *c, int layer, hipStream_t st, ProfEvent *ev)
 {
     if (!c->pool.empty()) { *ev = c->pool.back(); c->pool.pop_back(); }
@@ -355,23 +340,8 @@ int w2xc_model_trim(w2xc_model *m)
         std::lock_guard<std::mutex> lk2(c->mu);
         hipSetDevice(c->device);
         hipDeviceSynchronize();
-        for (int i = 0; i < 2; i++) {
-            if (c->ws[i]) { hipFree(c->ws[i]); c->ws[i] = nullptr; c->ws_floats[i] = 0; }
-            if (c->fc.planar[i]) { hipFree(c->fc.planar[i]); c->fc.planar[i] = nullptr; c->fc.planar_floats[i] = 0; }
-            if (c->fc.nhwc[i]) { hipFree(c->fc.nhwc[i]); c->fc.nhwc[i] = nullptr; c->fc.nhwc_floats[i] = 0; }
-            if (i == 0 && c->fc.pad) { hipFree(c->fc.pad); c->fc.pad = nullptr; c->fc.pad_floats = 0; }
-            if (i == 0 && c->fc.pout) { hipFree(c->fc.pout); c->fc.pout = nullptr; c->fc.pout_floats = 0; }
-        }
+        c->for_each_scratch([](Scratch &s, ScratchTag) { s.release(); });
         c->fc.res_valid = false;
-        if (c->aux) { hipFree(c->aux); c->aux = nullptr; c->aux_floats = 0; }
-        if (c->img_io) { hipFree(c->img_io); c->img_io = nullptr; c->img_io_bytes = 0; }
-        HostPipe &p = c->pipe;
-        if (p.d_in) { hipFree(p.d_in); p.d_in = nullptr; p.d_in_bytes = 0; }
-        if (p.d_out) { hipFree(p.d_out); p.d_out = nullptr; p.d_out_bytes = 0; }
-        if (p.pin_in) { hipHostFree(p.pin_in); p.pin_in = nullptr; p.in_slot_bytes = 0; }
-        if (p.pin_out) { hipHostFree(p.pin_out); p.pin_out = nullptr; p.out_slot_bytes = 0; }
-        for (int i = 0; i < 2; i++)
-            if (p.pin_band[i]) { hipHostFree(p.pin_band[i]); p.pin_band[i] = nullptr; p.band_bytes[i] = 0; }
     }
     hipSetDevice(prev);
     return W2XC_OK;
@@ -465,8 +435,8 @@ void w2xc_profile_reset(w2xc_model *m, int device)
 }
 
 // Test aid (tests/test_gpu_scratch_poison.py): every grow-only DATA buffer of the context, whole, so that a kernel which reads what its producer did not
-// write meets `word` and not the previous call's answer.  Synchronisation words stay as they are -- prog_cnt, pipe.pin_flags / flags_epoch, events: they are
-// not data, a wrong value there could only make a launch wait for ever.  Weights and biases are not scratch.
+// write meets `word` and not the previous call's answer.  Synchronisation words stay as they are -- prog_cnt, pipe.flags and their epochs, events: they are
+// not data (ScratchTag::SYNC in DevCtx::for_each_scratch), a wrong value there could only make a launch wait for ever.  Weights and biases are not scratch.
 int w2xc_debug_fill_scratch(w2xc_model *m, int device, unsigned word, unsigned long long *bytes)
 {
     if (!m || !bytes) return fail(W2XC_ERR_ARG, "null argument");
@@ -484,41 +454,22 @@ int w2xc_debug_fill_scratch(w2xc_model *m, int device, unsigned word, unsigned l
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipDeviceSynchronize());
     unsigned long long total = 0;
-    auto dev_fill = [&](void *p, size_t nbytes) -> int {
-        if (!p || !nbytes) return W2XC_OK;
-        HIP_TRY(hipMemsetD32((hipDeviceptr_t)p, (int)word, nbytes / 4));
-        if (nbytes & 3) HIP_TRY(hipMemsetD8((hipDeviceptr_t)((char *)p + (nbytes & ~(size_t)3)), (unsigned char)word, nbytes & 3));
+    hipError_t e = hipSuccess;
+    c->for_each_scratch([&](Scratch &s, ScratchTag tag) {
+        const size_t nbytes = s.bytes();
+        if (tag != ScratchTag::DATA || !nbytes || e != hipSuccess) return;
         total += nbytes;
-        return W2XC_OK;
-    };
-    auto host_fill = [&](void *p, size_t nbytes) {
-        if (!p || !nbytes) return;
-        unsigned *q = (unsigned *)p;   // (hipHostMalloc: page aligned)
-        for (size_t i = 0; i < nbytes / 4; i++) q[i] = word;
-        for (size_t i = nbytes & ~(size_t)3; i < nbytes; i++) ((unsigned char *)p)[i] = (unsigned char)word;
-        total += nbytes;
-    };
-    int rc = W2XC_OK;
-    FilterCache &fc = c->fc;
-    HostPipe &p = c->pipe;
-    for (int i = 0; i < 2 && !rc; i++) {
-        rc = dev_fill(c->ws[i], c->ws_floats[i] * sizeof(float));
-        if (!rc) rc = dev_fill(fc.planar[i], fc.planar_floats[i] * sizeof(float));
-        if (!rc) rc = dev_fill(fc.nhwc[i], fc.nhwc_floats[i] * sizeof(float));
-    }
-    if (!rc) rc = dev_fill(fc.pad, fc.pad_floats * sizeof(float));
-    if (!rc) rc = dev_fill(fc.pout, fc.pout_floats * sizeof(float));
-    if (!rc) rc = dev_fill(p.d_in, p.d_in_bytes);
-    if (!rc) rc = dev_fill(p.d_out, p.d_out_bytes);
-    if (!rc) rc = dev_fill(c->aux, c->aux_floats * sizeof(float));
-    if (!rc) rc = dev_fill(c->img_io, c->img_io_bytes);
-    if (rc) return rc;
+        if (s.on_device()) {
+            e = hipMemsetD32((hipDeviceptr_t)s.as<char>(), (int)word, nbytes / 4);
+            if (e == hipSuccess && (nbytes & 3)) e = hipMemsetD8((hipDeviceptr_t)(s.as<char>() + (nbytes & ~(size_t)3)), (unsigned char)word, nbytes & 3);
+            return;
+        }
+        for (size_t i = 0; i < nbytes / 4; i++) s.as<unsigned>()[i] = word;   // (page-locked host memory: page aligned; the device was drained above)
+        for (size_t i = nbytes & ~(size_t)3; i < nbytes; i++) s.as<unsigned char>()[i] = (unsigned char)word;
+    });
+    HIP_TRY(e);
     HIP_TRY(hipDeviceSynchronize());
-    host_fill(fc.pin, fc.slot_bytes * FilterCache::SLOTS);
-    host_fill(p.pin_in, p.in_slot_bytes * HostPipe::IN_SLOTS);
-    host_fill(p.pin_out, p.out_slot_bytes * HostPipe::OUT_SLOTS);
-    for (int i = 0; i < 2; i++) host_fill(p.pin_band[i], p.band_bytes[i]);
-    fc.res_valid = false;   // the resident copy w2xc_opts.filter_resident promises is gone
+    c->fc.res_valid = false;   // the resident copy w2xc_opts.filter_resident promises is gone
     *bytes = total;
     return W2XC_OK;
 }

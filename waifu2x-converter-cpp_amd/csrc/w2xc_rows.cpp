@@ -191,12 +191,9 @@ int run_prog(const Band &B, int k, W2xcKernelKind kind, W2xcConvDesc &d, int Tk,
     *launched = pt.out != nullptr;
     if (!pt.out) return W2XC_OK;
     const size_t nc = w2xc_wino4_prog_counters(d.out_w, d.out_h, d.wino_py);
-    if (c->prog_cnt_n < nc) {
-        if (c->prog_cnt) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->prog_cnt)); c->prog_cnt = nullptr; c->prog_cnt_n = 0; }
-        HIP_TRY(hipMalloc((void **)&c->prog_cnt, nc * sizeof(unsigned)));
-        c->prog_cnt_n = nc;
-    }
-    d.prog_cnt = c->prog_cnt;
+    int rc = c->prog_cnt.reserve(nc * sizeof(unsigned), "the gather-job counters");
+    if (rc) return rc;
+    d.prog_cnt = c->prog_cnt.as<unsigned>();
     d.g_out = pt.out;
     d.g_out_rs = pt.out_stride_f;
     d.g_h = B.y1 - B.y0;
@@ -205,7 +202,7 @@ int run_prog(const Band &B, int k, W2xcKernelKind kind, W2xcConvDesc &d, int Tk,
     d.g_bias = c->layers[B.P.n - 1].bias;
     d.prog_flags = pt.flags;
     d.prog_epoch = pt.epoch;
-    int rc = B.prefetch();
+    rc = B.prefetch();
     if (rc) return rc;
     rc = B.launch(k, kind, d);
     if (rc) return rc;
@@ -324,7 +321,7 @@ int run_band(Band &B, const LayerSrc &view, int up)
     const bool first2_fp32 = kind1 == W2XC_K_FUSED_AWAY && n > 1 && layer_kind(m, 1, o) == W2XC_K_FIRST2_WINO4;   // (layers 1 + 2 in one launch: chunked like layer 1)
     B.in_chunk = (hk && hk->in_chunk && hk->input_upto && n > 1 && (kind1 == W2XC_K_FIRST || kind1 == W2XC_K_DIRECT || first2_fp32)) ? hk->in_chunk(B.y0, B.y1) : 0;
     if (hk && hk->input_needed && B.in_chunk <= 0) { int rc = hk->input_needed(B.y0, B.y1); if (rc) return rc; }
-    const LayerDst dst = {B.out, B.out_rs, B.out_cs, {B.c->ws[0], B.c->ws[1]}};
+    const LayerDst dst = {B.out, B.out_rs, B.out_cs, {B.c->ws[0].as<float>(), B.c->ws[1].as<float>()}};
     LayerSrc src = view, next;
     W2xcConvDesc first_d, d;
     memset(&first_d, 0, sizeof first_d);
@@ -372,7 +369,7 @@ int run_rows(w2xc_model *m, DevCtx *c, const float *d_in, size_t in_stride_f, in
         if (rc) return rc;
     }
     for (int i = 0; i < 2; i++)
-        if (P.need[i]) { int rc = ensure_ws(c, i, (P.need[i] + 3) / 4); if (rc) return rc; }
+        if (P.need[i]) { int rc = c->ws[i].reserve((P.need[i] + 3) / 4 * sizeof(float), "the activation workspace"); if (rc) return rc; }
     LayerSrc view;   // the source view; its first row is plane row vy0
     view.p = d_in; view.rs = (long long)in_stride_f; view.cs = in_cs;
     view.h = vh; view.w = w; view.top = vy0;
@@ -420,7 +417,7 @@ int run_batch(w2xc_model *m, DevCtx *c, int nimg, int up, const float *d_in, lon
     if (max_sub > 0 && sub > max_sub) sub = max_sub;
     if (sub > nimg) sub = nimg;
     for (int i = 0; i < 2; i++)
-        if (img_f[i]) { int rc = ensure_ws(c, i, img_f[i] * (size_t)sub); if (rc) return rc; }
+        if (img_f[i]) { int rc = c->ws[i].reserve(img_f[i] * (size_t)sub * sizeof(float), "the activation workspace"); if (rc) return rc; }
 
     for (int b0 = 0; b0 < nimg; b0 += sub) {
         W2xcBatchDesc bd;
@@ -431,7 +428,7 @@ int run_batch(w2xc_model *m, DevCtx *c, int nimg, int up, const float *d_in, lon
         LayerSrc src, next;
         src.p = d_in + (size_t)b0 * in_ps; src.rs = (long long)in_rs;
         src.h = H; src.w = W;
-        const LayerDst dst = {d_out + (size_t)b0 * out_ps, (long long)out_rs, 0, {c->ws[0], c->ws[1]}};
+        const LayerDst dst = {d_out + (size_t)b0 * out_ps, (long long)out_rs, 0, {c->ws[0].as<float>(), c->ws[1].as<float>()}};
         long long src_bs = in_ps;   // (layer 1 is fused away: the first launch reads the input planes)
         W2xcConvDesc first_d, d;
         memset(&first_d, 0, sizeof first_d);
