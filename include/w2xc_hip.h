@@ -217,6 +217,12 @@ int w2xc_convert_planes_device(w2xc_model *m, int n_in_planes, const float *d_in
                                size_t in_stride_bytes, int w, int h, float *d_out, size_t out_plane_stride_bytes,
                                size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts);
 
+/* ... with the nearest-neighbour 2x of w2xc_convert_plane_nn2x_device folded into layer 1: (w, h) is the SOURCE size, the n_in_planes input planes are
+ * h rows of w floats, the output planes 2h x 2w.  Result == w2xc_convert_planes_device on the explicitly upscaled planes, bit for bit. */
+int w2xc_convert_planes_nn2x_device(w2xc_model *m, int n_in_planes, const float *d_in, size_t in_plane_stride_bytes,
+                                    size_t in_stride_bytes, int w, int h, float *d_out, size_t out_plane_stride_bytes,
+                                    size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts);
+
 /* N1: the scale loop of the CLI -- cv::resize(INTER_NEAREST, 2x) of the luma plane
  * (main.cpp:132-140) followed by convertWithModels (:148) -- as ONE call.  `in` is the h x w plane
  * BEFORE the resize, `out` is 2h x 2w.  The nearest-neighbour upscale is folded into layer 1's load
@@ -318,12 +324,45 @@ int w2xc_process_image_u8_batch_device(w2xc_model *noise_model, w2xc_model *scal
 int w2xc_process_image_u8_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in,
                                 size_t in_stride_bytes, int w, int h, unsigned char *const *out, size_t out_stride_bytes, int iterations,
                                 double shrink_ratio, const w2xc_opts *opts);
+/* RGB models: the same four calls for models that take the three colour planes and return three (3 -> 32 -> ... -> 3, the form most published
+ * waifu2x weights have).  v1 of the reference has no such path (its CLI converts Y only); the arithmetic is that of later upstream versions:
+ *   x = u8 / 255 on the three channels AS GIVEN (no colour matrix, no channel swap);
+ *   with a noise model x <- CNN(x), all three output planes; `iterations` times x <- CNN(nearest2x(x));
+ *   shrink_ratio in (0,1): INTER_LINEAR on each of the three planes;   out = saturate(rint(255 x))  (the only clip).
+ * Between passes the image is three float planes.  With W2XC_PRECISION_FP32 and w2xc_opts.fusion other than W2XC_FUSION_OFF the first layer of the
+ * call's first pass reads the uint8 image itself and the last layer of its last pass (no shrink behind it) writes the uint8 result itself, where those
+ * layers have the kernels for it (3 -> 32 / 64 / 128, 32 / 64 / 128 -> 3; not W2XC_KERNEL_DIRECT): the float copy of the source and of the result --
+ * 4^iterations as many pixels -- then never exists in device memory.  Every other case runs colour kernels around float planes: the same float
+ * operations in the same order, so the same bytes.
+ * Arguments, argument errors (W2XC_ERR_ARG), sub-batch sizing by w2xc_opts.workspace_mb, the host forms' pipeline and the byte-identity of a batch's
+ * images with the single-image call are those of w2xc_process_image_u8_ex* / _batch* above; in addition the single-image device form refuses an output
+ * that overlaps the input.  noise_model / scale_model: NULL or a model whose first layer takes 3 planes and whose last layer gives 3 -- anything else,
+ * a Y model beside an RGB one included, is W2XC_ERR_PLANES.  All of that before a device is touched; without a device W2XC_ERR_HIP.
+ * RGB chains have no batch kernels: a sub-batch runs the single-image launch sequence per image, with no host synchronisation in between (the colour
+ * kernels and the shrink, where they run, are one launch per sub-batch). */
+int w2xc_process_image_rgb_u8_ex_device(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *d_in, size_t in_stride_bytes, int w,
+                                        int h, unsigned char *d_out, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                        void *hip_stream, const w2xc_opts *opts);
+int w2xc_process_image_rgb_u8_ex(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes, int w, int h,
+                                 unsigned char *out, size_t out_stride_bytes, int iterations, double shrink_ratio, const w2xc_opts *opts);
+int w2xc_process_image_rgb_u8_batch_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in,
+                                           size_t in_image_stride_bytes, size_t in_stride_bytes, int w, int h, unsigned char *d_out,
+                                           size_t out_image_stride_bytes, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                           void *hip_stream, const w2xc_opts *opts);
+int w2xc_process_image_rgb_u8_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes,
+                                    int w, int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                    const w2xc_opts *opts);
 /* the building blocks on contiguous float planes (device pointers): main.cpp:144 on one plane, :75-76, :171-172 */
 int w2xc_resize2x_cubic_device(const float *d_src, int w, int h, float *d_dst, void *hip_stream);
 int w2xc_u8_to_yuv_device(const unsigned char *d_in, size_t in_stride_bytes, int w, int h, float *d_y, float *d_u,
                           float *d_v, void *hip_stream);
 int w2xc_yuv_to_u8_device(const float *d_y, const float *d_u, const float *d_v, int w, int h, unsigned char *d_out,
                           size_t out_stride_bytes, void *hip_stream);
+
+/* ... and the RGB pipeline's: u8 / 255 into three contiguous w x h float planes, saturate(rint(255 x)) back */
+int w2xc_u8_to_rgb_device(const unsigned char *d_in, size_t in_stride_bytes, int w, int h, float *d_c0, float *d_c1, float *d_c2, void *hip_stream);
+int w2xc_rgb_to_u8_device(const float *d_c0, const float *d_c1, const float *d_c2, int w, int h, unsigned char *d_out, size_t out_stride_bytes,
+                          void *hip_stream);
 
 /* == Model::filter(inputPlanes, outputPlanes) for layer `layer` (modelHandler.cpp:26-72):
  * n_in_planes host planes of h x w floats in, nout planes out, SAME size, per-layer

@@ -6,7 +6,9 @@ name (:173-189).  Image I/O is PIL instead of cv::imread/imwrite; everything bet
 RGB2YUV on BGR data (Q3), noise pass, nearest/bicubic 2x + CNN, linear shrink, YUV2RGB, saturate to uint8 --
 runs on the GPU in one call (w2xc_process_image_u8_ex).
 Extension: several input files (-i a.png b.png ...).  They are grouped by image size and every group is ONE w2xc_process_image_u8_batch call; each
-output gets its automatic name (-o is for a single input only).  A single input behaves exactly as before."""
+output gets its automatic name (-o is for a single input only).  A single input behaves exactly as before.
+Extension: RGB models.  When the loaded model's first layer takes 3 planes the image goes through w2xc_process_image_rgb_u8_ex / _batch instead: the three
+channels in PIL's RGB order as they are (no BGR swap: that mimics what the reference feeds its Y path), all three planes through the CNN."""
 import argparse
 import math
 import os
@@ -52,6 +54,21 @@ def group_inputs(files_with_sizes, mode, noise_level, scale_ratio):
     return [(size, names, [auto_output_name(f, mode, noise_level, scale_ratio) for f in names]) for size, names in groups.items()]
 
 
+def model_route(noise, scale):
+    """'rgb' when the loaded models take three planes (w2xc_process_image_rgb_u8*), 'y' when they take one; models of different kinds, or of neither
+    kind, are a SystemExit with a message.  `noise` / `scale`: (name, input planes of the first layer) or None."""
+    loaded = [m for m in (noise, scale) if m is not None]
+    kinds = {3: "rgb", 1: "y"}
+    for name, nin in loaded:
+        if nin not in kinds:
+            raise SystemExit("%s: the first layer takes %d planes; only Y models (1 plane) and RGB models (3 planes) are supported" % (name, nin))
+    routes = {kinds[nin] for _, nin in loaded}
+    if len(routes) > 1:
+        raise SystemExit("mixed model kinds: " + ", ".join("%s takes %d plane%s" % (name, nin, "" if nin == 1 else "s") for name, nin in loaded) +
+                         "; use a noise model and a scale model of the same kind")
+    return routes.pop() if routes else "y"
+
+
 def check_inputs(ap, args):
     """-o names ONE output file: with several inputs it is refused (argparse's error exit, status 2)"""
     if len(args.input_file) > 1 and args.output_file != "(auto)":
@@ -82,19 +99,24 @@ def main(argv=None):
     import __graft_entry__ as graft
     w2xc = graft.load_package()
 
-    def load_bgr(path):
-        return np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB"))[:, :, ::-1])   # cv::imread(IMREAD_COLOR) order (Q3)
-    images = [load_bgr(f) for f in args.input_file]
     w2xc.modelUtility.getInstance().setNumberOfJobs(args.jobs)        # :79
 
     noise = scale = None
+    noise_name, scale_name = "noise%d_model.json" % args.noise_level, "scale2.0x_model.json"
     if args.mode in ("noise", "noise_scale"):                         # :83-89
-        noise = w2xc._ModelSet.from_json(os.path.join(args.model_dir, "noise%d_model.json" % args.noise_level))
+        noise = w2xc._ModelSet.from_json(os.path.join(args.model_dir, noise_name))
     iterations, shrink = 0, 0.0
     if args.mode in ("scale", "noise_scale"):                         # :103-121
         iterations, shrink = plan_scale(args.scale_ratio)
-        scale = w2xc._ModelSet.from_json(os.path.join(args.model_dir, "scale2.0x_model.json"))
+        scale = w2xc._ModelSet.from_json(os.path.join(args.model_dir, scale_name))
         print("start scaling")
+    rgb = model_route((noise_name, noise.planes(0)[0]) if noise else None, (scale_name, scale.planes(0)[0]) if scale else None) == "rgb"
+    process, process_batch = (w2xc.process_image_rgb_u8, w2xc.process_image_rgb_u8_batch) if rgb else (w2xc.process_image_u8, w2xc.process_image_u8_batch)
+
+    def load(path):
+        im = np.asarray(Image.open(path).convert("RGB"))
+        return np.ascontiguousarray(im if rgb else im[:, :, ::-1])   # Y route: cv::imread(IMREAD_COLOR)'s BGR order (Q3); RGB models take RGB as it is
+    images = [load(f) for f in args.input_file]
     outs = {}
     if noise is None and iterations == 0 and not shrink:
         outs = dict(zip(args.input_file, images))                      # ratio 1.0 in scale mode: nothing to do
@@ -104,18 +126,18 @@ def main(argv=None):
         prec = {"fp32": w2xc.PRECISION_FP32, "bf16": w2xc.PRECISION_BF16, "bf16x2": w2xc.PRECISION_BF16X2, "bf16x3": w2xc.PRECISION_BF16X3, "fp16x2": w2xc.PRECISION_FP16X2}[args.precision]
         opts = w2xc.make_opts(precision=prec)      # always explicit: an explicit --precision beats the W2XC_PRECISION env default
         if len(images) == 1:
-            outs[args.input_file[0]] = w2xc.process_image_u8(images[0], noise, scale if iterations else None, iterations, opts, shrink)
+            outs[args.input_file[0]] = process(images[0], noise, scale if iterations else None, iterations, opts, shrink)
         else:
             by_file = dict(zip(args.input_file, images))
             sized = [(f, (im.shape[1], im.shape[0])) for f, im in zip(args.input_file, images)]
             for _, files, _ in group_inputs(sized, args.mode, args.noise_level, args.scale_ratio):   # one batch call per image size
-                res = w2xc.process_image_u8_batch([by_file[f] for f in files], noise, scale if iterations else None, iterations, opts, shrink)
+                res = process_batch([by_file[f] for f in files], noise, scale if iterations else None, iterations, opts, shrink)
                 outs.update(zip(files, res))
     for f in args.input_file:
         name = args.output_file
         if name == "(auto)":
             name = auto_output_name(f, args.mode, args.noise_level, args.scale_ratio)
-        Image.fromarray(np.ascontiguousarray(outs[f][:, :, ::-1])).save(name)
+        Image.fromarray(np.ascontiguousarray(outs[f] if rgb else outs[f][:, :, ::-1])).save(name)
     print("process successfully done!")
     return 0
 

@@ -93,6 +93,13 @@ def _load():
         "w2xc_process_image_u8_ex": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.c_double, C.POINTER(Opts)]),
         "w2xc_process_image_u8_batch_device": (ci, [vp, vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, ci, C.c_double, vp, C.POINTER(Opts)]),
         "w2xc_process_image_u8_batch": (ci, [vp, vp, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, ci, C.c_double, C.POINTER(Opts)]),
+        "w2xc_process_image_rgb_u8_ex_device": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.c_double, vp, C.POINTER(Opts)]),
+        "w2xc_process_image_rgb_u8_ex": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.c_double, C.POINTER(Opts)]),
+        "w2xc_process_image_rgb_u8_batch_device": (ci, [vp, vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, ci, C.c_double, vp, C.POINTER(Opts)]),
+        "w2xc_process_image_rgb_u8_batch": (ci, [vp, vp, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, ci, C.c_double, C.POINTER(Opts)]),
+        "w2xc_convert_planes_nn2x_device": (ci, [vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, vp, C.POINTER(Opts)]),
+        "w2xc_u8_to_rgb_device": (ci, [fp, cs, ci, ci, fp, fp, fp, vp]),
+        "w2xc_rgb_to_u8_device": (ci, [fp, fp, fp, ci, ci, fp, cs, vp]),
         "w2xc_process_image_u8_device": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, vp, C.POINTER(Opts)]),
         "w2xc_process_image_u8": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.POINTER(Opts)]),
         "w2xc_scale2x_image_u8_device": (ci, [vp, fp, cs, ci, ci, fp, cs, ci, vp, C.POINTER(Opts)]),
@@ -269,6 +276,16 @@ class _ModelSet:
         rc = _lib.w2xc_convert_planes_device(self.handle, n_in, C.c_void_p(d_in), in_plane_stride_bytes, in_stride_bytes, w, h,
                                              C.c_void_p(d_out), out_plane_stride_bytes, out_stride_bytes, C.c_void_p(stream),
                                              C.byref(opts) if opts is not None else None)
+        if rc != OK:
+            raise W2xcError(rc, last_error())
+
+    def convert_planes_nn2x_device(self, n_in, d_in, in_plane_stride_bytes, in_stride_bytes, w, h, d_out,
+                                   out_plane_stride_bytes, out_stride_bytes, stream=0, opts=None):
+        """convert_planes_device with the nearest-neighbour 2x folded into layer 1 (w2xc_convert_planes_nn2x_device): (w, h) is the
+        source size, the output planes are 2w x 2h."""
+        rc = _lib.w2xc_convert_planes_nn2x_device(self.handle, n_in, C.c_void_p(d_in), in_plane_stride_bytes, in_stride_bytes, w, h,
+                                                  C.c_void_p(d_out), out_plane_stride_bytes, out_stride_bytes, C.c_void_p(stream),
+                                                  C.byref(opts) if opts is not None else None)
         if rc != OK:
             raise W2xcError(rc, last_error())
 
@@ -593,21 +610,26 @@ def process_image_u8_batch(imgs, noise=None, scale=None, iterations=0, opts=None
     """n uint8 images of one size in one call (w2xc_process_image_u8_batch): `imgs` is an (n, h, w, 3) uint8 array or a sequence of equal-shape
     (h, w, 3) uint8 arrays (ROI views with padded rows are passed as they are, page-locked arrays are DMA'd in place); returns an (n, H, W, 3)
     uint8 array (or fills `out`, such an array).  Image i is byte-identical to process_image_u8(imgs[i], ...) with the same arguments."""
+    return _image_batch(_lib.w2xc_process_image_u8_batch, "process_image_u8_batch", imgs, noise, scale, iterations, opts, shrink_ratio, out)
+
+
+def _image_batch(entry, who, imgs, noise, scale, iterations, opts, shrink_ratio, out):
+    """the host image batch of Y models (process_image_u8_batch) and of RGB models (process_image_rgb_u8_batch): same arguments, same checks"""
     if isinstance(imgs, np.ndarray):
         if imgs.ndim != 4:
-            raise ValueError("process_image_u8_batch wants an (n, h, w, 3) array or a sequence of h x w x 3 images")
+            raise ValueError("%s wants an (n, h, w, 3) array or a sequence of h x w x 3 images" % who)
         imgs = [imgs[i] for i in range(imgs.shape[0])]
     srcs = [np.asarray(a) for a in imgs]
     if not srcs:
-        raise ValueError("process_image_u8_batch wants at least one image")
+        raise ValueError("%s wants at least one image" % who)
     for a in srcs:
         if a.dtype != np.uint8:
-            raise ValueError("process_image_u8_batch wants uint8 images (got %s)" % a.dtype)
+            raise ValueError("%s wants uint8 images (got %s)" % (who, a.dtype))
         if a.ndim != 3 or a.shape[2] != 3:
-            raise ValueError("process_image_u8_batch wants h x w x 3 images (got shape %r)" % (a.shape,))
+            raise ValueError("%s wants h x w x 3 images (got shape %r)" % (who, a.shape))
     h, w, _ = srcs[0].shape
     if any(a.shape != (h, w, 3) for a in srcs):
-        raise ValueError("process_image_u8_batch: every image must have the same size (group images by size)")
+        raise ValueError("%s: every image must have the same size (group images by size)" % who)
     if any(a.strides[1:] != (3, 1) for a in srcs) or len({a.strides[0] for a in srcs}) != 1:
         srcs = [np.ascontiguousarray(a) for a in srcs]
     n = len(srcs)
@@ -615,11 +637,11 @@ def process_image_u8_batch(imgs, noise=None, scale=None, iterations=0, opts=None
     if out is None:
         out = np.empty((n, max(fh, 0), max(fw, 0), 3), np.uint8)
     elif not isinstance(out, np.ndarray) or out.shape != (n, fh, fw, 3) or out.dtype != np.uint8 or out.strides[2:] != (3, 1):
-        raise ValueError("process_image_u8_batch: `out` must be a uint8 (n, H, W, 3) array with contiguous rows")
+        raise ValueError("%s: `out` must be a uint8 (n, H, W, 3) array with contiguous rows" % who)
     ip = (C.c_void_p * n)(*[a.ctypes.data for a in srcs])
     op = (C.c_void_p * n)(*[out[i].ctypes.data for i in range(n)])
-    rc = _lib.w2xc_process_image_u8_batch(noise.handle if noise else None, scale.handle if scale else None, n, ip, srcs[0].strides[0], w, h,
-                                          op, out.strides[1], iterations, float(shrink_ratio), C.byref(opts) if opts is not None else None)
+    rc = entry(noise.handle if noise else None, scale.handle if scale else None, n, ip, srcs[0].strides[0], w, h,
+               op, out.strides[1], iterations, float(shrink_ratio), C.byref(opts) if opts is not None else None)
     if rc != OK:
         raise W2xcError(rc, last_error())
     return out
@@ -633,5 +655,73 @@ def process_image_u8_batch_device(n, d_in, in_image_stride_bytes, in_stride_byte
                                                  in_image_stride_bytes, in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes,
                                                  out_stride_bytes, iterations, float(shrink_ratio), C.c_void_p(stream),
                                                  C.byref(opts) if opts is not None else None)
+    if rc != OK:
+        raise W2xcError(rc, last_error())
+
+
+# ---- RGB models (3 planes in, 3 out): the image calls above for the form most published waifu2x weights have ----
+def process_image_rgb_u8(img, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0):
+    """An h x w x 3 uint8 image through RGB models (w2xc_process_image_rgb_u8_ex): x = u8 / 255 on the channels as given, an optional noise
+    pass, `iterations` 2x passes (nearest 2x + CNN on all three planes), the optional INTER_LINEAR shrink, saturate(rint(255 x)).
+    `noise` / `scale` are _ModelSet objects whose first layer takes 3 planes and whose last gives 3 (either may be None)."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8:
+        raise ValueError("process_image_rgb_u8 wants a uint8 image (got %s)" % img.dtype)
+    if img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("process_image_rgb_u8 wants an h x w x 3 image (got shape %r)" % (img.shape,))
+    if img.strides[1:] != (3, 1):
+        img = np.ascontiguousarray(img)
+    h, w, _ = img.shape
+    fw, fh = _final_size(w, h, iterations, shrink_ratio)
+    out = np.empty((max(fh, 0), max(fw, 0), 3), np.uint8)
+    rc = _lib.w2xc_process_image_rgb_u8_ex(noise.handle if noise else None, scale.handle if scale else None, img.ctypes.data,
+                                           img.strides[0], w, h, out.ctypes.data, out.strides[0], iterations, float(shrink_ratio),
+                                           C.byref(opts) if opts is not None else None)
+    if rc != OK:
+        raise W2xcError(rc, last_error())
+    return out
+
+
+def process_image_rgb_u8_device(d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, noise=None, scale=None, iterations=0, shrink_ratio=0.0,
+                                stream=0, opts=None):
+    """Device-pointer form (w2xc_process_image_rgb_u8_ex_device): w x h x 3 uint8 at d_in, the result at d_out.  Asynchronous on `stream`."""
+    rc = _lib.w2xc_process_image_rgb_u8_ex_device(noise.handle if noise else None, scale.handle if scale else None, C.c_void_p(d_in),
+                                                  in_stride_bytes, w, h, C.c_void_p(d_out), out_stride_bytes, iterations, float(shrink_ratio),
+                                                  C.c_void_p(stream), C.byref(opts) if opts is not None else None)
+    if rc != OK:
+        raise W2xcError(rc, last_error())
+
+
+def process_image_rgb_u8_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, out=None):
+    """n uint8 images of one size through RGB models in one call (w2xc_process_image_rgb_u8_batch); arguments and checks as
+    process_image_u8_batch.  Image i is byte-identical to process_image_rgb_u8(imgs[i], ...) with the same arguments."""
+    return _image_batch(_lib.w2xc_process_image_rgb_u8_batch, "process_image_rgb_u8_batch", imgs, noise, scale, iterations, opts, shrink_ratio, out)
+
+
+def process_image_rgb_u8_batch_device(n, d_in, in_image_stride_bytes, in_stride_bytes, w, h, d_out, out_image_stride_bytes, out_stride_bytes,
+                                      noise=None, scale=None, iterations=0, shrink_ratio=0.0, stream=0, opts=None):
+    """Device-pointer image batch for RGB models (w2xc_process_image_rgb_u8_batch_device); arguments as process_image_u8_batch_device."""
+    rc = _lib.w2xc_process_image_rgb_u8_batch_device(noise.handle if noise else None, scale.handle if scale else None, n, C.c_void_p(d_in),
+                                                     in_image_stride_bytes, in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes,
+                                                     out_stride_bytes, iterations, float(shrink_ratio), C.c_void_p(stream),
+                                                     C.byref(opts) if opts is not None else None)
+    if rc != OK:
+        raise W2xcError(rc, last_error())
+
+
+def u8_to_rgb_device(d_in, in_stride_bytes, w, h, d_planes, stream=0):
+    """uint8 / 255 of a w x h x 3 image into three contiguous w x h float planes at d_planes (w2xc_u8_to_rgb_device)."""
+    ps = w * h * 4
+    rc = _lib.w2xc_u8_to_rgb_device(C.c_void_p(d_in), in_stride_bytes, w, h, C.c_void_p(d_planes), C.c_void_p(d_planes + ps),
+                                    C.c_void_p(d_planes + 2 * ps), C.c_void_p(stream))
+    if rc != OK:
+        raise W2xcError(rc, last_error())
+
+
+def rgb_to_u8_device(d_planes, w, h, d_out, out_stride_bytes, stream=0):
+    """saturate(rint(255 x)) of three contiguous w x h float planes at d_planes into a w x h x 3 uint8 image (w2xc_rgb_to_u8_device)."""
+    ps = w * h * 4
+    rc = _lib.w2xc_rgb_to_u8_device(C.c_void_p(d_planes), C.c_void_p(d_planes + ps), C.c_void_p(d_planes + 2 * ps), w, h, C.c_void_p(d_out),
+                                    out_stride_bytes, C.c_void_p(stream))
     if rc != OK:
         raise W2xcError(rc, last_error())

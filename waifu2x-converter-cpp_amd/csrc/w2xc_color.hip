@@ -75,6 +75,63 @@ __global__ void __launch_bounds__(256) k_yuv_to_u8_batch(const float *y, const f
     }
 }
 
+// The RGB image pipeline (w2xc_process_image_rgb_u8*; no counterpart in v1 of the reference): x = u8 / 255 on the three channels as given, and
+// back out = saturate(rint(255 x)) -- the two expressions of u8_to_yuv_px / yuv_to_u8_px without the colour matrix, and the ones the uint8 forms of
+// conv3x3_first / conv3x3_last (w2xc_kernels.hip) evaluate in their load / store.  Three planar float planes p0 / p1 / p2.
+static __device__ __forceinline__ void u8_to_rgb_px(const unsigned char *src, long long stride, int w, long long q, float *p0, float *p1, float *p2)
+{
+    const float s = (float)(1.0 / 255.0);
+    const int r = (int)(q / w), c = (int)(q - (long long)r * w);
+    const unsigned char *p = src + r * stride + (long long)c * 3;
+    p0[q] = (float)p[0] * s;
+    p1[q] = (float)p[1] * s;
+    p2[q] = (float)p[2] * s;
+}
+
+__global__ void __launch_bounds__(256) k_u8_to_rgb(const unsigned char *src, long long stride, int w, int h, float *p0, float *p1, float *p2)
+{
+    const long long total = (long long)w * h;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) u8_to_rgb_px(src, stride, w, q, p0, p1, p2);
+}
+
+// n images, image i at src + i * img_stride bytes; its three planes at planes + i * is + {0, 1, 2} * ps floats
+__global__ void __launch_bounds__(256) k_u8_to_rgb_batch(const unsigned char *src, long long img_stride, long long stride, int w, int h, float *planes,
+                                                         long long ps, long long is, int n)
+{
+    const long long total = (long long)w * h;
+    for (int img = blockIdx.y; img < n; img += gridDim.y) {
+        const unsigned char *s = src + img * img_stride;
+        float *p0 = planes + img * is;
+        for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) u8_to_rgb_px(s, stride, w, q, p0, p0 + ps, p0 + 2 * ps);
+    }
+}
+
+static __device__ __forceinline__ void rgb_to_u8_px(const float *p0, const float *p1, const float *p2, int w, long long q, unsigned char *dst, long long stride)
+{
+    const int r = (int)(q / w), c = (int)(q - (long long)r * w);
+    unsigned char *p = dst + r * stride + (long long)c * 3;
+    p[0] = (unsigned char)clampi(__float2int_rn(p0[q] * 255.0f), 0, 255);   // round half to even
+    p[1] = (unsigned char)clampi(__float2int_rn(p1[q] * 255.0f), 0, 255);
+    p[2] = (unsigned char)clampi(__float2int_rn(p2[q] * 255.0f), 0, 255);
+}
+
+__global__ void __launch_bounds__(256) k_rgb_to_u8(const float *p0, const float *p1, const float *p2, int w, int h, unsigned char *dst, long long stride)
+{
+    const long long total = (long long)w * h;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) rgb_to_u8_px(p0, p1, p2, w, q, dst, stride);
+}
+
+__global__ void __launch_bounds__(256) k_rgb_to_u8_batch(const float *planes, long long ps, long long is, int w, int h, unsigned char *dst, long long img_stride,
+                                                         long long stride, int n)
+{
+    const long long total = (long long)w * h;
+    for (int img = blockIdx.y; img < n; img += gridDim.y) {
+        const float *p0 = planes + img * is;
+        unsigned char *d = dst + img * img_stride;
+        for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) rgb_to_u8_px(p0, p0 + ps, p0 + 2 * ps, w, q, d, stride);
+    }
+}
+
 static __device__ __forceinline__ void cubic_coeffs(float t, float *c)   // Keys cubic, A = -0.75 (OpenCV interpolateCubic)
 {
     const float A = -0.75f;
@@ -229,5 +286,29 @@ hipError_t w2xc_launch_resize_linear_batch(const float *src_y, const float *src_
 {
     hipLaunchKernelGGL(k_resize_linear_batch, grid_batch((long long)dw * dh, n), dim3(256), 0, st, src_y, src_uv, ny, sps, sw, sh, dst, dps, dw, dh,
                        (double)sw / dw, (double)sh / dh, n);
+    return hipGetLastError();
+}
+
+// ---- the RGB pipeline's colour stages ----
+hipError_t w2xc_launch_u8_to_rgb(const unsigned char *src, size_t stride, int w, int h, float *p0, float *p1, float *p2, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_u8_to_rgb, dim3(grid_for((long long)w * h)), dim3(256), 0, st, src, (long long)stride, w, h, p0, p1, p2);
+    return hipGetLastError();
+}
+hipError_t w2xc_launch_rgb_to_u8(const float *p0, const float *p1, const float *p2, int w, int h, unsigned char *dst, size_t stride, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_rgb_to_u8, dim3(grid_for((long long)w * h)), dim3(256), 0, st, p0, p1, p2, w, h, dst, (long long)stride);
+    return hipGetLastError();
+}
+hipError_t w2xc_launch_u8_to_rgb_batch(const unsigned char *src, size_t img_stride, size_t stride, int w, int h, float *planes, long long ps, long long is,
+                                       int n, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_u8_to_rgb_batch, grid_batch((long long)w * h, n), dim3(256), 0, st, src, (long long)img_stride, (long long)stride, w, h, planes, ps, is, n);
+    return hipGetLastError();
+}
+hipError_t w2xc_launch_rgb_to_u8_batch(const float *planes, long long ps, long long is, int w, int h, unsigned char *dst, size_t img_stride, size_t stride,
+                                       int n, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_rgb_to_u8_batch, grid_batch((long long)w * h, n), dim3(256), 0, st, planes, ps, is, w, h, dst, (long long)img_stride, (long long)stride, n);
     return hipGetLastError();
 }

@@ -20,7 +20,7 @@
 //   w2xc_host_pipeline.cpp  host plane in -> host plane out: staging rings, three streams, the feeder with its Uploader, the drainer (Stitcher), the unit
 //                           fan-out (run_units), the host batch pipeline
 //   w2xc_filter.cpp         Model::filter at the host / device boundary (src/modelHandler.cpp:26-72)
-//   w2xc_image.cpp          N2: the CLI's image pipeline around the plane conversion (main.cpp:74-172)
+//   w2xc_image.cpp          N2: the CLI's image pipeline around the plane conversion (main.cpp:74-172), for Y models and for RGB models
 #pragma once
 #include "../../include/w2xc_hip.h"
 
@@ -234,6 +234,10 @@ bool planar_between(const w2xc_model *m, int l, const w2xc_opts &o);
 int out_terms_of(const w2xc_model *m, int l, const w2xc_opts &o);
 bool gather_in_producer(const w2xc_model *m, const w2xc_opts &o);
 int fused_halves(int T, int cout);
+// the RGB image pipeline: may layer 1 read / the last layer write the caller's interleaved uint8 image itself (conv3x3_first / conv3x3_last, U8)?  fp32 with
+// the fast kernels and w2xc_opts.fusion other than W2XC_FUSION_OFF, a three-plane W2XC_K_FIRST / W2XC_K_LAST layer.
+bool u8_source_layer(const w2xc_model *m, const w2xc_opts &o);
+bool u8_sink_layer(const w2xc_model *m, const w2xc_opts &o);
 enum MidVariant { MID_MFMA = 0, MID_WINO32 = 1, MID_WINO4 = 3 };
 
 // the band geometry of one run_rows call (plan_rows, w2xc_select.cpp): pure host arithmetic
@@ -297,9 +301,13 @@ struct BandHooks {
     std::function<int(int, int, int, int, int)> prog_launched;
 };
 
+// u8 (the RGB image pipeline; no hooks): ROWS_U8_SRC = d_in is an interleaved uint8 image of three channels, in_stride_f its row stride in BYTES, in_cs = 1
+// (layer 1 runs as W2XC_K_FIRST_U8); ROWS_U8_DST = the same for d_out / out_stride_f / out_cs and the last layer (W2XC_K_LAST_U8).  The caller asks only
+// where u8_source_layer / u8_sink_layer say yes.
+enum { ROWS_U8_SRC = 1, ROWS_U8_DST = 2 };
 int run_rows(w2xc_model *m, DevCtx *c, const float *d_in, size_t in_stride_f, int vh, int vy0, int w, int ra, int rb,
              float *d_out, size_t out_stride_f, hipStream_t st, const w2xc_opts &o_in, int up = 0, int n_in = 1,
-             long long in_cs = 0, long long out_cs = 0, const BandHooks *hk = nullptr, int plane_h = 0);
+             long long in_cs = 0, long long out_cs = 0, const BandHooks *hk = nullptr, int plane_h = 0, int u8 = 0);
 int check_plane_args(const w2xc_model *m, const void *in, size_t in_stride, int w, int h, const void *out, size_t out_stride);
 
 // ---- batches of same-size planes (w2xc_convert_batch*) ----

@@ -1,5 +1,7 @@
 // w2xc_image.cpp -- N2: the CLI's image pipeline around the plane conversion -- uint8 BGR -> float YUV, the noise /
 // scale passes on Y through run_rows, bicubic U/V, the final shrink, YUV -> uint8 (main.cpp:74-76,83-98,126-172).
+// And the same surface for RGB models (3 planes in, 3 out; w2xc_process_image_rgb_u8*): no chroma side path, every pass a CNN pass on all three planes,
+// the first and the last layer of the call reading / writing the uint8 image themselves where their kernels can (no counterpart in v1).
 #include "w2xc_engine.hpp"
 #include "w2xc_host_geom.hpp"
 
@@ -127,6 +129,113 @@ int process_image_batch_device(w2xc_model *mn, DevCtx *cn, w2xc_model *msc, DevC
     return W2XC_OK;
 }
 
+// ---- RGB models (w2xc_process_image_rgb_u8*) ----
+// x = u8 / 255 on the three channels as given; with a noise model x <- CNN(x); per iteration x <- CNN(nearest2x(x)), the 2x folded into layer 1; an optional
+// INTER_LINEAR shrink per plane; out = saturate(rint(255 x)).  Between passes the image is three float planes, unclipped, like Y in the pipeline above.
+// What one image needs of float planes, and whether the call's first / last layer takes the uint8 image itself (u8_source_layer / u8_sink_layer: then the
+// float copy of the source / of the result -- 4^iterations as many pixels -- does not exist):
+struct RgbPlan {
+    bool src_u8 = false, dst_u8 = false;
+    size_t floats = 0;
+};
+RgbPlan rgb_plan(const w2xc_model *mn, const w2xc_model *msc, int w, int h, int iterations, double shrink, const w2xc_opts &o)
+{
+    RgbPlan R;
+    const int passes = (mn ? 1 : 0) + iterations;
+    R.src_u8 = u8_source_layer(mn ? mn : msc, o);
+    R.dst_u8 = shrink == 0.0 && u8_sink_layer(iterations > 0 ? msc : mn, o);
+    if (!R.src_u8) R.floats += 3 * plane_floats(w, h);
+    for (int p = 1; p <= passes; p++) {
+        const int lvl = p - (mn ? 1 : 0);   // the pass's output level: the noise pass stays on level 0
+        if (p < passes || !R.dst_u8) R.floats += 3 * plane_floats(w << lvl, h << lvl);
+    }
+    int fw, fh;
+    final_size(w, h, iterations, shrink, &fw, &fh);
+    if (shrink > 0.0) R.floats += 3 * plane_floats(fw, fh);
+    return R;
+}
+
+// A sub-batch of S images (S <= cap; the planes are sized by cap): per level the three planes of image i lie at level + i * 3 ps, ps floats apart.  The
+// colour stages and the shrink are one launch for the sub-batch; RGB chains have no batch kernels, so every pass is the single-image launch sequence per
+// image, enqueued back to back.  A single image is a sub-batch of one.
+int process_rgb_batch_device(w2xc_model *mn, DevCtx *cn, w2xc_model *msc, DevCtx *cs, int S, int cap, const unsigned char *d_in, size_t in_img,
+                             size_t in_stride, int w, int h, unsigned char *d_out, size_t out_img, size_t out_stride, int iterations, double shrink,
+                             hipStream_t st, const w2xc_opts &o)
+{
+    DevCtx *c = cs ? cs : cn;
+    const RgbPlan R = rgb_plan(mn, msc, w, h, iterations, shrink, o);
+    float *base = nullptr;
+    if (R.floats) {
+        if (int rc = reserve_aux(c, R.floats * (size_t)cap)) return rc;
+        base = c->aux.as<float>();
+    }
+    int cw = w, ch = h;
+    long long ps = (long long)plane_floats(cw, ch);
+    float *cur = nullptr;   // the current level's planes; nullptr = the image is still the caller's uint8 source
+    if (!R.src_u8) {
+        cur = base;
+        base += 3 * (size_t)cap * ps;
+        HIP_TRY(w2xc_launch_u8_to_rgb_batch(d_in, in_img, in_stride, w, h, cur, ps, 3 * ps, S, st));
+    }
+    const int passes = (mn ? 1 : 0) + iterations;
+    for (int p = 1; p <= passes; p++) {
+        const bool noise = mn && p == 1;
+        w2xc_model *m = noise ? mn : msc;
+        DevCtx *cm = noise ? cn : cs;
+        const int up = noise ? 0 : 1, nw = cw << up, nh = ch << up;
+        const long long ps2 = (long long)plane_floats(nw, nh);
+        const bool from_u8 = cur == nullptr, to_u8 = p == passes && R.dst_u8;
+        float *nxt = nullptr;
+        if (!to_u8) { nxt = base; base += 3 * (size_t)cap * ps2; }
+        for (int i = 0; i < S; i++) {
+            const float *in = from_u8 ? reinterpret_cast<const float *>(d_in + (size_t)i * in_img) : cur + (size_t)i * 3 * ps;
+            float *out = to_u8 ? reinterpret_cast<float *>(d_out + (size_t)i * out_img) : nxt + (size_t)i * 3 * ps2;
+            int rc = run_rows(m, cm, in, from_u8 ? in_stride : (size_t)cw, nh, 0, nw, 0, nh, out, to_u8 ? out_stride : (size_t)nw, st, o, up, 3,
+                              from_u8 ? 1 : ps, to_u8 ? 1 : ps2, nullptr, nh, (from_u8 ? ROWS_U8_SRC : 0) | (to_u8 ? ROWS_U8_DST : 0));
+            if (rc) return rc;
+        }
+        if (to_u8) return W2XC_OK;
+        cur = nxt; cw = nw; ch = nh; ps = ps2;
+    }
+    if (shrink > 0.0) {
+        int fw, fh;
+        final_size(w, h, iterations, shrink, &fw, &fh);
+        const long long pss = (long long)plane_floats(fw, fh);
+        float *dst = base;
+        HIP_TRY(w2xc_launch_resize_linear_batch(cur, cur, 3 * S, ps, cw, ch, dst, pss, fw, fh, 3 * S, st));   // (the 3 S planes of a level are ps apart)
+        cur = dst; cw = fw; ch = fh; ps = pss;
+    }
+    HIP_TRY(w2xc_launch_rgb_to_u8_batch(cur, ps, 3 * ps, cw, ch, d_out, out_img, out_stride, S, st));
+    return W2XC_OK;
+}
+
+// RGB forms: each model takes three planes and gives three (a Y model beside an RGB one fails here too), and the options' errors (plan_rows: host
+// arithmetic) -- before any device is touched.  *sub = images per sub-batch of a batch: what w2xc_opts.workspace_mb holds of float planes + uint8 images.
+int check_rgb_call(const w2xc_model *mn, const w2xc_model *msc, int w, int h, int iterations, double shrink, const w2xc_opts &o, int *sub)
+{
+    const w2xc_model *pass[2] = {mn, msc};
+    for (const w2xc_model *m : pass) {
+        if (!m) continue;
+        if (m->layers.empty()) return fail(W2XC_ERR_ARG, "model has no layers");
+        if (m->layers[0].nin != 3 || m->layers.back().nout != 3)
+            return fail(W2XC_ERR_PLANES, "w2xc_process_image_rgb_u8*: three planes in and three planes out (the model takes %d and gives %d)",
+                        m->layers[0].nin, m->layers.back().nout);
+    }
+    pass[1] = iterations > 0 ? msc : nullptr;
+    for (int i = 0; i < 2; i++) {
+        if (!pass[i]) continue;
+        const int W = i ? w << iterations : w, H = i ? h << iterations : h;
+        RowPlan P;
+        if (int rc = plan_rows(pass[i], o, W, H, 0, 0, H, H, 3, true, &P)) return rc;
+    }
+    int fw, fh;
+    final_size(w, h, iterations, shrink, &fw, &fh);
+    const size_t budget = (size_t)(o.workspace_mb > 0 ? o.workspace_mb : 16384) << 20;
+    const size_t per = rgb_plan(mn, msc, w, h, iterations, shrink, o).floats * 4 + (size_t)w * 3 * h + (size_t)fw * 3 * fh;
+    *sub = (int)std::min<size_t>(std::max<size_t>(budget / per, 1), 65535);
+    return W2XC_OK;
+}
+
 // The contexts of the (up to two) models of an image call on `dev`; with l1 / l2 they are locked, TOGETHER (std::lock's deadlock avoidance): two threads
 // that pass the same two models in opposite roles -- (A as noise, B as scale) and (B as noise, A as scale) -- would otherwise each hold one mutex and
 // wait for the other.  The plane buffers and the host pipeline are the owning context's: the scale model's when present.
@@ -150,12 +259,13 @@ int image_contexts(w2xc_model *mn, w2xc_model *msc, int dev, ImageCtx *ic, std::
 }
 
 // resolve device + contexts of the (up to two) models and run the pipeline under their locks
-int process_image_locked(w2xc_model *mn, w2xc_model *msc, const unsigned char *d_in, size_t in_stride, int w, int h, unsigned char *d_out,
+int process_image_locked(bool rgb, w2xc_model *mn, w2xc_model *msc, const unsigned char *d_in, size_t in_stride, int w, int h, unsigned char *d_out,
                          size_t out_stride, int iterations, double shrink, hipStream_t st, const w2xc_opts &o, int dev)
 {
     ImageCtx ic;
     std::unique_lock<std::mutex> l1, l2;
     if (int rc = image_contexts(mn, msc, dev, &ic, &l1, &l2)) return rc;
+    if (rgb) return process_rgb_batch_device(mn, ic.cn, msc, ic.cs, 1, 1, d_in, 0, in_stride, w, h, d_out, 0, out_stride, iterations, shrink, st, o);
     return process_image_device(mn, ic.cn, msc, ic.cs, d_in, in_stride, w, h, d_out, out_stride, iterations, shrink, st, o);
 }
 
@@ -182,7 +292,7 @@ int check_image_args(const w2xc_model *m, const void *in, size_t in_stride, int 
 
 // One host image on device `dev`, synchronously (w2xc_process_image_u8_ex; a batch of one image, which has nothing to overlap with): blocking copies
 // around the pipeline on the null stream.
-int process_image_host(w2xc_model *mn, w2xc_model *msc, const unsigned char *in, size_t in_stride, int w, int h, unsigned char *out, size_t out_stride,
+int process_image_host(bool rgb, w2xc_model *mn, w2xc_model *msc, const unsigned char *in, size_t in_stride, int w, int h, unsigned char *out, size_t out_stride,
                        int iterations, double shrink, const w2xc_opts &o, int dev)
 {
     DeviceGuard guard(dev);
@@ -200,7 +310,8 @@ int process_image_host(w2xc_model *mn, w2xc_model *msc, const unsigned char *in,
     if ((rc = c->img_io.reserve(in_bytes + out_bytes, "the image"))) return rc;
     unsigned char *d_in = c->img_io.as<unsigned char>(), *d_out = d_in + in_bytes;
     HIP_TRY(hipMemcpy2D(d_in, (size_t)w * 3, in, in_stride, (size_t)w * 3, h, hipMemcpyHostToDevice));
-    rc = process_image_device(mn, ic.cn, msc, ic.cs, d_in, (size_t)w * 3, w, h, d_out, (size_t)W * 3, iterations, shrink, nullptr, o);
+    rc = rgb ? process_rgb_batch_device(mn, ic.cn, msc, ic.cs, 1, 1, d_in, 0, (size_t)w * 3, w, h, d_out, 0, (size_t)W * 3, iterations, shrink, nullptr, o)
+             : process_image_device(mn, ic.cn, msc, ic.cs, d_in, (size_t)w * 3, w, h, d_out, (size_t)W * 3, iterations, shrink, nullptr, o);
     if (rc) { hipDeviceSynchronize(); return rc; }
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy2D(out, out_stride, d_out, (size_t)W * 3, (size_t)W * 3, H, hipMemcpyDeviceToHost));
@@ -208,7 +319,7 @@ int process_image_host(w2xc_model *mn, w2xc_model *msc, const unsigned char *in,
 }
 
 // what both batch forms refuse before any device is touched (the image pointers are the caller's: checked there)
-int check_image_batch_args(const w2xc_model *mn, const w2xc_model *msc, int n, size_t in_stride, int w, int h, size_t out_stride, int iterations,
+int check_image_batch_args(bool rgb, const w2xc_model *mn, const w2xc_model *msc, int n, size_t in_stride, int w, int h, size_t out_stride, int iterations,
                            double shrink)
 {
     if (n < 1) return fail(W2XC_ERR_ARG, "batch of %d images", n);
@@ -217,70 +328,59 @@ int check_image_batch_args(const w2xc_model *mn, const w2xc_model *msc, int n, s
     rc = check_image_args(mn ? mn : msc, &n, in_stride, w, h, &n, out_stride, iterations, shrink);   // (pointers: see above)
     if (rc) return rc;
     if (w > (1 << 28) >> iterations || h > (1 << 28) >> iterations) return fail(W2XC_ERR_ARG, "image too large");
+    if (rgb) return W2XC_OK;   // (the models' plane form: check_rgb_call, behind the caller's pointer checks)
     if (mn && (rc = check_batch_model(mn))) return rc;
     if (msc && (rc = check_batch_model(msc))) return rc;
     return W2XC_OK;
 }
 
-}  // namespace
-
-}  // namespace w2xc_eng
-
-using namespace w2xc_eng;
-
-extern "C" {
-
-int w2xc_process_image_u8_ex_device(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *d_in, size_t in_stride_bytes,
-                                    int w, int h, unsigned char *d_out, size_t out_stride_bytes, int iterations, double shrink_ratio,
-                                    void *hip_stream, const w2xc_opts *opts)
-try {
+// ---- the four forms of the image call, for Y models (rgb = false: w2xc_process_image_u8*) and RGB models (w2xc_process_image_rgb_u8*) ----
+int image_ex_device(bool rgb, w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *d_in, size_t in_stride_bytes, int w, int h,
+                    unsigned char *d_out, size_t out_stride_bytes, int iterations, double shrink_ratio, void *hip_stream, const w2xc_opts *opts)
+{
     int rc = check_process_args(noise_model, scale_model, iterations);
     if (rc) return rc;
     rc = check_image_args(noise_model ? noise_model : scale_model, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, iterations, shrink_ratio);
     if (rc) return rc;
     const w2xc_opts o = resolve_opts(opts);
+    if (rgb) {
+        // (the first layer may read the source while bands of the result are already written: the two must not share memory)
+        int W, H, sub;
+        final_size(w, h, iterations, shrink_ratio, &W, &H);
+        const uintptr_t i0 = (uintptr_t)d_in, i1 = i0 + (size_t)(h - 1) * in_stride_bytes + (size_t)w * 3;
+        const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (size_t)(H - 1) * out_stride_bytes + (size_t)W * 3;
+        if (i0 < o1 && o0 < i1) return fail(W2XC_ERR_ARG, "the output image overlaps the input image");
+        if ((rc = check_rgb_call(noise_model, scale_model, w, h, iterations, shrink_ratio, o, &sub))) return rc;
+    }
     int dev = o.device;
     if (dev < 0) HIP_TRY(hipGetDevice(&dev));
     DeviceGuard guard(dev);
     if (!guard.ok) return fail(W2XC_ERR_HIP, "cannot select HIP device %d", dev);
-    return process_image_locked(noise_model, scale_model, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, iterations, shrink_ratio,
+    return process_image_locked(rgb, noise_model, scale_model, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, iterations, shrink_ratio,
                                 (hipStream_t)hip_stream, o, dev);
-} W2XC_CATCH_ALL
-
-int w2xc_process_image_u8_device(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *d_in, size_t in_stride_bytes,
-                                 int w, int h, unsigned char *d_out, size_t out_stride_bytes, int iterations, void *hip_stream,
-                                 const w2xc_opts *opts)
-{
-    return w2xc_process_image_u8_ex_device(noise_model, scale_model, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, iterations, 0.0,
-                                           hip_stream, opts);
 }
 
-int w2xc_process_image_u8_ex(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes, int w, int h,
-                             unsigned char *out, size_t out_stride_bytes, int iterations, double shrink_ratio, const w2xc_opts *opts)
-try {
+int image_ex_host(bool rgb, w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes, int w, int h,
+                  unsigned char *out, size_t out_stride_bytes, int iterations, double shrink_ratio, const w2xc_opts *opts)
+{
     int rc = check_process_args(noise_model, scale_model, iterations);
     if (rc) return rc;
     rc = check_image_args(noise_model ? noise_model : scale_model, in, in_stride_bytes, w, h, out, out_stride_bytes, iterations, shrink_ratio);
     if (rc) return rc;
-    if (w2xc_device_count() <= 0) return fail(W2XC_ERR_HIP, "no HIP device available (libw2xc_hip has no CPU fallback)");
     const w2xc_opts o = resolve_opts(opts);
+    int sub;
+    if (rgb && (rc = check_rgb_call(noise_model, scale_model, w, h, iterations, shrink_ratio, o, &sub))) return rc;
+    if (w2xc_device_count() <= 0) return fail(W2XC_ERR_HIP, "no HIP device available (libw2xc_hip has no CPU fallback)");
     int dev = o.device;
     if (dev < 0) HIP_TRY(hipGetDevice(&dev));
-    return process_image_host(noise_model, scale_model, in, in_stride_bytes, w, h, out, out_stride_bytes, iterations, shrink_ratio, o, dev);
-} W2XC_CATCH_ALL
-
-int w2xc_process_image_u8(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes, int w, int h,
-                          unsigned char *out, size_t out_stride_bytes, int iterations, const w2xc_opts *opts)
-{
-    return w2xc_process_image_u8_ex(noise_model, scale_model, in, in_stride_bytes, w, h, out, out_stride_bytes, iterations, 0.0, opts);
+    return process_image_host(rgb, noise_model, scale_model, in, in_stride_bytes, w, h, out, out_stride_bytes, iterations, shrink_ratio, o, dev);
 }
 
-// ---- batches of same-size images ----------------------------------------------------------------
-int w2xc_process_image_u8_batch_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in, size_t in_image_stride_bytes,
-                                       size_t in_stride_bytes, int w, int h, unsigned char *d_out, size_t out_image_stride_bytes,
-                                       size_t out_stride_bytes, int iterations, double shrink_ratio, void *hip_stream, const w2xc_opts *opts)
-try {
-    int rc = check_image_batch_args(noise_model, scale_model, n, in_stride_bytes, w, h, out_stride_bytes, iterations, shrink_ratio);
+int image_batch_device(bool rgb, w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in, size_t in_image_stride_bytes,
+                       size_t in_stride_bytes, int w, int h, unsigned char *d_out, size_t out_image_stride_bytes, size_t out_stride_bytes,
+                       int iterations, double shrink_ratio, void *hip_stream, const w2xc_opts *opts)
+{
+    int rc = check_image_batch_args(rgb, noise_model, scale_model, n, in_stride_bytes, w, h, out_stride_bytes, iterations, shrink_ratio);
     if (rc) return rc;
     if (!d_in || !d_out) return fail(W2XC_ERR_ARG, "null argument");
     int W, H;
@@ -295,7 +395,9 @@ try {
     }
     const w2xc_opts o = resolve_opts(opts);
     int sub = 1;
-    if ((rc = image_sub_size(noise_model, scale_model, w, h, iterations, shrink_ratio, o, &sub))) return rc;
+    rc = rgb ? check_rgb_call(noise_model, scale_model, w, h, iterations, shrink_ratio, o, &sub)
+             : image_sub_size(noise_model, scale_model, w, h, iterations, shrink_ratio, o, &sub);
+    if (rc) return rc;
     sub = std::min(sub, n);
     int dev = o.device;
     if (dev < 0) HIP_TRY(hipGetDevice(&dev));
@@ -304,19 +406,20 @@ try {
     ImageCtx ic;
     std::unique_lock<std::mutex> l1, l2;
     if ((rc = image_contexts(noise_model, scale_model, dev, &ic, &l1, &l2))) return rc;
+    const auto run = rgb ? process_rgb_batch_device : process_image_batch_device;
     for (int b0 = 0; b0 < n; b0 += sub) {
-        rc = process_image_batch_device(noise_model, ic.cn, scale_model, ic.cs, std::min(sub, n - b0), sub, d_in + (size_t)b0 * in_image_stride_bytes,
-                                        in_image_stride_bytes, in_stride_bytes, w, h, d_out + (size_t)b0 * out_image_stride_bytes, out_image_stride_bytes,
-                                        out_stride_bytes, iterations, shrink_ratio, (hipStream_t)hip_stream, o);
+        rc = run(noise_model, ic.cn, scale_model, ic.cs, std::min(sub, n - b0), sub, d_in + (size_t)b0 * in_image_stride_bytes, in_image_stride_bytes,
+                 in_stride_bytes, w, h, d_out + (size_t)b0 * out_image_stride_bytes, out_image_stride_bytes, out_stride_bytes, iterations, shrink_ratio,
+                 (hipStream_t)hip_stream, o);
         if (rc) return rc;
     }
     return W2XC_OK;
-} W2XC_CATCH_ALL
+}
 
-int w2xc_process_image_u8_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes, int w,
-                                int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio, const w2xc_opts *opts)
-try {
-    int rc = check_image_batch_args(noise_model, scale_model, n, in_stride_bytes, w, h, out_stride_bytes, iterations, shrink_ratio);
+int image_batch_host(bool rgb, w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes, int w, int h,
+                     unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio, const w2xc_opts *opts)
+{
+    int rc = check_image_batch_args(rgb, noise_model, scale_model, n, in_stride_bytes, w, h, out_stride_bytes, iterations, shrink_ratio);
     if (rc) return rc;
     if (!in || !out) return fail(W2XC_ERR_ARG, "null argument");
     int W, H;
@@ -325,13 +428,14 @@ try {
                                (size_t)(H - 1) * out_stride_bytes + (size_t)W * 3);
     if (rc) return rc;
     const w2xc_opts o = resolve_opts(opts);
+    int sub = 1;
+    if (rgb && (rc = check_rgb_call(noise_model, scale_model, w, h, iterations, shrink_ratio, o, &sub))) return rc;
     if (n == 1) {   // nothing to overlap: the synchronous single-image sequence, on the first device of the mask
         std::vector<int> devs;
         if ((rc = host_devices(o, &devs))) return rc;
-        return process_image_host(noise_model, scale_model, in[0], in_stride_bytes, w, h, out[0], out_stride_bytes, iterations, shrink_ratio, o, devs[0]);
+        return process_image_host(rgb, noise_model, scale_model, in[0], in_stride_bytes, w, h, out[0], out_stride_bytes, iterations, shrink_ratio, o, devs[0]);
     }
-    int sub = 1;
-    if ((rc = image_sub_size(noise_model, scale_model, w, h, iterations, shrink_ratio, o, &sub))) return rc;
+    if (!rgb && (rc = image_sub_size(noise_model, scale_model, w, h, iterations, shrink_ratio, o, &sub))) return rc;
     HostBatch b;
     b.n = n;
     b.in = (const void *const *)in; b.out = (void *const *)out;
@@ -351,10 +455,91 @@ try {
         ImageCtx ic;
         int r = image_contexts(noise_model, scale_model, dev, &ic);
         if (r) return r;
-        return process_image_batch_device(noise_model, ic.cn, scale_model, ic.cs, cnt, max_sub, (const unsigned char *)din, b.in_img, b.in_row, w, h,
-                                          (unsigned char *)dout, b.out_img, b.out_row, iterations, shrink_ratio, st, o);
+        const auto run = rgb ? process_rgb_batch_device : process_image_batch_device;
+        return run(noise_model, ic.cn, scale_model, ic.cs, cnt, max_sub, (const unsigned char *)din, b.in_img, b.in_row, w, h, (unsigned char *)dout, b.out_img,
+                   b.out_row, iterations, shrink_ratio, st, o);
     };
     return batch_host_run(b, o, sub);
+}
+
+}  // namespace
+
+}  // namespace w2xc_eng
+
+using namespace w2xc_eng;
+
+extern "C" {
+
+int w2xc_process_image_u8_ex_device(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *d_in, size_t in_stride_bytes,
+                                    int w, int h, unsigned char *d_out, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                    void *hip_stream, const w2xc_opts *opts)
+try {
+    return image_ex_device(false, noise_model, scale_model, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, iterations, shrink_ratio, hip_stream, opts);
+} W2XC_CATCH_ALL
+
+int w2xc_process_image_u8_device(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *d_in, size_t in_stride_bytes,
+                                 int w, int h, unsigned char *d_out, size_t out_stride_bytes, int iterations, void *hip_stream,
+                                 const w2xc_opts *opts)
+{
+    return w2xc_process_image_u8_ex_device(noise_model, scale_model, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, iterations, 0.0,
+                                           hip_stream, opts);
+}
+
+int w2xc_process_image_u8_ex(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes, int w, int h,
+                             unsigned char *out, size_t out_stride_bytes, int iterations, double shrink_ratio, const w2xc_opts *opts)
+try {
+    return image_ex_host(false, noise_model, scale_model, in, in_stride_bytes, w, h, out, out_stride_bytes, iterations, shrink_ratio, opts);
+} W2XC_CATCH_ALL
+
+int w2xc_process_image_u8(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes, int w, int h,
+                          unsigned char *out, size_t out_stride_bytes, int iterations, const w2xc_opts *opts)
+{
+    return w2xc_process_image_u8_ex(noise_model, scale_model, in, in_stride_bytes, w, h, out, out_stride_bytes, iterations, 0.0, opts);
+}
+
+// ---- batches of same-size images ----------------------------------------------------------------
+int w2xc_process_image_u8_batch_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in, size_t in_image_stride_bytes,
+                                       size_t in_stride_bytes, int w, int h, unsigned char *d_out, size_t out_image_stride_bytes,
+                                       size_t out_stride_bytes, int iterations, double shrink_ratio, void *hip_stream, const w2xc_opts *opts)
+try {
+    return image_batch_device(false, noise_model, scale_model, n, d_in, in_image_stride_bytes, in_stride_bytes, w, h, d_out, out_image_stride_bytes,
+                              out_stride_bytes, iterations, shrink_ratio, hip_stream, opts);
+} W2XC_CATCH_ALL
+
+int w2xc_process_image_u8_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes, int w,
+                                int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio, const w2xc_opts *opts)
+try {
+    return image_batch_host(false, noise_model, scale_model, n, in, in_stride_bytes, w, h, out, out_stride_bytes, iterations, shrink_ratio, opts);
+} W2XC_CATCH_ALL
+
+// ---- RGB models: the same four forms ---------------------------------------------------------------
+int w2xc_process_image_rgb_u8_ex_device(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *d_in, size_t in_stride_bytes,
+                                        int w, int h, unsigned char *d_out, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                        void *hip_stream, const w2xc_opts *opts)
+try {
+    return image_ex_device(true, noise_model, scale_model, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, iterations, shrink_ratio, hip_stream, opts);
+} W2XC_CATCH_ALL
+
+int w2xc_process_image_rgb_u8_ex(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes, int w, int h,
+                                 unsigned char *out, size_t out_stride_bytes, int iterations, double shrink_ratio, const w2xc_opts *opts)
+try {
+    return image_ex_host(true, noise_model, scale_model, in, in_stride_bytes, w, h, out, out_stride_bytes, iterations, shrink_ratio, opts);
+} W2XC_CATCH_ALL
+
+int w2xc_process_image_rgb_u8_batch_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in,
+                                           size_t in_image_stride_bytes, size_t in_stride_bytes, int w, int h, unsigned char *d_out,
+                                           size_t out_image_stride_bytes, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                           void *hip_stream, const w2xc_opts *opts)
+try {
+    return image_batch_device(true, noise_model, scale_model, n, d_in, in_image_stride_bytes, in_stride_bytes, w, h, d_out, out_image_stride_bytes,
+                              out_stride_bytes, iterations, shrink_ratio, hip_stream, opts);
+} W2XC_CATCH_ALL
+
+int w2xc_process_image_rgb_u8_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes,
+                                    int w, int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                    const w2xc_opts *opts)
+try {
+    return image_batch_host(true, noise_model, scale_model, n, in, in_stride_bytes, w, h, out, out_stride_bytes, iterations, shrink_ratio, opts);
 } W2XC_CATCH_ALL
 
 int w2xc_scale2x_image_u8_device(w2xc_model *m, const unsigned char *d_in, size_t in_stride_bytes, int w, int h, unsigned char *d_out,
@@ -388,6 +573,21 @@ int w2xc_yuv_to_u8_device(const float *d_y, const float *d_u, const float *d_v, 
 {
     if (!d_out || !d_y || !d_u || !d_v || w <= 0 || h <= 0 || out_stride_bytes < (size_t)w * 3) return fail(W2XC_ERR_ARG, "bad argument");
     HIP_TRY(w2xc_launch_yuv_to_u8(d_y, d_u, d_v, w, h, d_out, out_stride_bytes, (hipStream_t)hip_stream));
+    return W2XC_OK;
+}
+
+int w2xc_u8_to_rgb_device(const unsigned char *d_in, size_t in_stride_bytes, int w, int h, float *d_c0, float *d_c1, float *d_c2, void *hip_stream)
+{
+    if (!d_in || !d_c0 || !d_c1 || !d_c2 || w <= 0 || h <= 0 || in_stride_bytes < (size_t)w * 3) return fail(W2XC_ERR_ARG, "bad argument");
+    HIP_TRY(w2xc_launch_u8_to_rgb(d_in, in_stride_bytes, w, h, d_c0, d_c1, d_c2, (hipStream_t)hip_stream));
+    return W2XC_OK;
+}
+
+int w2xc_rgb_to_u8_device(const float *d_c0, const float *d_c1, const float *d_c2, int w, int h, unsigned char *d_out, size_t out_stride_bytes,
+                          void *hip_stream)
+{
+    if (!d_out || !d_c0 || !d_c1 || !d_c2 || w <= 0 || h <= 0 || out_stride_bytes < (size_t)w * 3) return fail(W2XC_ERR_ARG, "bad argument");
+    HIP_TRY(w2xc_launch_rgb_to_u8(d_c0, d_c1, d_c2, w, h, d_out, out_stride_bytes, (hipStream_t)hip_stream));
     return W2XC_OK;
 }
 

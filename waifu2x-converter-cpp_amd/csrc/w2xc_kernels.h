@@ -23,6 +23,8 @@ struct W2xcConvDesc {
     int in_h, in_w;      // extent of the input view (clamp bounds)
     int out_h, out_w;    // region to compute
     int off_y, off_x;
+    // W2XC_K_FIRST_U8 / W2XC_K_LAST_U8 (the RGB image pipeline): `in` / `out` points at the BYTES of an interleaved uint8 image and in_* / out_* are byte
+    // strides (row stride, 3, 1); the kernels convert in their load / store (conv3x3_first / conv3x3_last, U8).
     // N1 (nearest-neighbour 2x of main.cpp:132-140 folded into the load): in_h/in_w and all offsets are
     // in UPSCALED coordinates, memory is addressed at (y >> in_shift, x >> in_shift).  0 or 1; only the
     // first-layer kernels (conv3x3_first, conv3x3_direct) honour it.
@@ -120,6 +122,14 @@ hipError_t w2xc_launch_u8_to_yuv_batch(const unsigned char *src, size_t img_stri
                                        long long ps, int n, hipStream_t st);
 hipError_t w2xc_launch_yuv_to_u8_batch(const float *y, const float *u, const float *v, long long ps, int w, int h, unsigned char *dst, size_t img_stride,
                                        size_t stride, int n, hipStream_t st);
+// the RGB pipeline (w2xc_process_image_rgb_u8*): uint8 / 255 on the three channels as given <-> three planar float planes, saturate(rint(255 x)) back.
+// Batch forms: the three planes of image i at planes + i * is + {0, 1, 2} * ps FLOATS.
+hipError_t w2xc_launch_u8_to_rgb(const unsigned char *src, size_t stride, int w, int h, float *p0, float *p1, float *p2, hipStream_t st);
+hipError_t w2xc_launch_rgb_to_u8(const float *p0, const float *p1, const float *p2, int w, int h, unsigned char *dst, size_t stride, hipStream_t st);
+hipError_t w2xc_launch_u8_to_rgb_batch(const unsigned char *src, size_t img_stride, size_t stride, int w, int h, float *planes, long long ps, long long is,
+                                       int n, hipStream_t st);
+hipError_t w2xc_launch_rgb_to_u8_batch(const float *planes, long long ps, long long is, int w, int h, unsigned char *dst, size_t img_stride, size_t stride,
+                                       int n, hipStream_t st);
 // n planes src + p * sps -> dst + p * dps (the U and V planes of a sub-batch adjoin: n = 2 x images)
 hipError_t w2xc_launch_resize2x_cubic_batch(const float *src, long long sps, int w, int h, float *dst, long long dps, int n, hipStream_t st);
 // n planes (Y, U, V of a sub-batch: n = 3 x images): plane p < ny at src_y + p * sps, the others at src_uv + (p - ny) * sps; -> dst + p * dps

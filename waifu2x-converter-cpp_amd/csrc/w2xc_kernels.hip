@@ -375,7 +375,10 @@ __global__ void __launch_bounds__(WM *WN * 64, WM *WN / 4) conv3x3_mfma2(W2xcCon
 #ifndef FIRST_TPW
 #define FIRST_TPW 4
 #endif
-template <int CIN, int NBT, bool PLANAR = false>
+// U8 (W2XC_K_FIRST_U8): the source is an interleaved uint8 image -- d.in points at BYTES, in_rs / in_ps / in_cs are byte strides (row stride, 3, 1) -- and the
+// patch load converts, (float)byte * (float)(1.0 / 255.0): the expression of the colour kernels (w2xc_color.hip), so the float planes they would write for
+// this layer to read never exist.  Everything behind the patch load is the float form's.
+template <int CIN, int NBT, bool PLANAR = false, bool U8 = false>
 __global__ void __launch_bounds__(256) conv3x3_first(W2xcConvDesc d, int tiles_x, int ntiles)
 {
     constexpr int ROWS = 8, MB = 2, HW = 34, HH = ROWS + 2;
@@ -415,7 +418,9 @@ __global__ void __launch_bounds__(256) conv3x3_first(W2xcConvDesc d, int tiles_x
             const int py = p / HW, px = p - py * HW;
             const int gy = clampi(oy0 + py + d.off_y, 0, d.in_h - 1) >> d.in_shift;
             const int gx = clampi(ox0 + px + d.off_x, 0, d.in_w - 1) >> d.in_shift;
-            v[t] = d.in[(long long)c * d.in_cs + (long long)gy * d.in_rs + (long long)gx * d.in_ps];
+            const long long at = (long long)c * d.in_cs + (long long)gy * d.in_rs + (long long)gx * d.in_ps;
+            if constexpr (U8) v[t] = (float)reinterpret_cast<const unsigned char *>(d.in)[at] * (float)(1.0 / 255.0);
+            else v[t] = d.in[at];
         }
     };
     float pv[PL];
@@ -568,7 +573,10 @@ __global__ void __launch_bounds__(256) conv3x3_first(W2xcConvDesc d, int tiles_x
 #ifndef LAST_TPW
 #define LAST_TPW 4
 #endif
-template <int CIN, int COUT>
+// U8 (W2XC_K_LAST_U8): the sink is an interleaved uint8 image -- d.out points at BYTES, out_rs / out_ps / out_cs are byte strides (row stride, COUT, 1) -- and
+// the epilogue stores saturate(rint(255 v)) with the rounding of the colour kernels (w2xc_color.hip): one byte store per value, so a thread writes its own
+// bytes only (the neighbours are other threads' or, with an ROI as output, the caller's).
+template <int CIN, int COUT, bool U8 = false>
 __global__ void __launch_bounds__(256) conv3x3_last(W2xcConvDesc d, int tiles_x, int ntiles)
 {
     constexpr int ROWS = 8, HW = 34, HH = ROWS + 2, NPIX = HH * HW;
@@ -667,7 +675,9 @@ __global__ void __launch_bounds__(256) conv3x3_last(W2xcConvDesc d, int tiles_x,
 #pragma unroll
                 for (int tap = 0; tap < 9; tap++)
                     v += G[((py + tap / 3) * HW + px + tap % 3) * GS + tap * COUT + o];
-                d.out[(long long)o * d.out_cs + (long long)y * d.out_rs + (long long)x * d.out_ps] = leaky(v + bo[o]);
+                const long long at = (long long)o * d.out_cs + (long long)y * d.out_rs + (long long)x * d.out_ps;
+                if constexpr (U8) reinterpret_cast<unsigned char *>(d.out)[at] = (unsigned char)clampi(__float2int_rn(leaky(v + bo[o]) * 255.0f), 0, 255);
+                else d.out[at] = leaky(v + bo[o]);
             }
         }
         __syncthreads();                                 // (G is rewritten by the next tile)
@@ -752,7 +762,7 @@ static hipError_t launch_first(KernelT kernel, const W2xcConvDesc &d, hipStream_
 hipError_t w2xc_launch_conv(W2xcKernelKind kind, const W2xcConvDesc &d, hipStream_t stream)
 {
     if (d.out_w <= 0 || d.out_h <= 0) return hipSuccess;
-    if (d.in_shift != 0 && kind != W2XC_K_FIRST && kind != W2XC_K_DIRECT) return hipErrorInvalidValue;
+    if (d.in_shift != 0 && kind != W2XC_K_FIRST && kind != W2XC_K_FIRST_U8 && kind != W2XC_K_DIRECT) return hipErrorInvalidValue;
     if (kind == W2XC_K_MFMA) {
         if (d.in_ps != d.cin || d.in_cs != 1 || d.out_ps != d.cout || d.out_cs != 1) return hipErrorInvalidValue;
         const int key = d.cin * 1000 + d.cout;
@@ -771,6 +781,34 @@ hipError_t w2xc_launch_conv(W2xcKernelKind kind, const W2xcConvDesc &d, hipStrea
         case 128032: return launch_mfma2<128, 32, 2, 1, 4, 1>(d, stream);
         case 128064: return w8 ? launch_mfma2<128, 64, 2, 1, 4, 2>(d, stream) : launch_mfma2<128, 64, 2, 2, 4, 1>(d, stream);
         case 128128: return w8 ? launch_mfma2<128, 128, 2, 2, 4, 2>(d, stream) : launch_mfma2<128, 128, 4, 2, 2, 2>(d, stream);
+        default: return hipErrorInvalidValue;
+        }
+    }
+    if (kind == W2XC_K_FIRST_U8) {   // three interleaved uint8 channels in; either output layout, with the float form's conditions
+        if (d.cin != 3 || d.in_ps != 3 || d.in_cs != 1) return hipErrorInvalidValue;
+        if (d.out_ps == 1) {
+            if (((d.out_rs | d.out_cs) & 3) != 0 || d.out_rs < ((d.out_w + 3) & ~3) || (((size_t)d.out) & 15) != 0) return hipErrorInvalidValue;
+            switch (d.cout) {
+            case 32: return launch_first(conv3x3_first<3, 1, true, true>, d, stream);
+            case 64: return launch_first(conv3x3_first<3, 2, true, true>, d, stream);
+            case 128: return launch_first(conv3x3_first<3, 4, true, true>, d, stream);
+            default: return hipErrorInvalidValue;
+            }
+        }
+        if (d.out_ps != d.cout || d.out_cs != 1) return hipErrorInvalidValue;
+        switch (d.cout) {
+        case 32: return launch_first(conv3x3_first<3, 1, false, true>, d, stream);
+        case 64: return launch_first(conv3x3_first<3, 2, false, true>, d, stream);
+        case 128: return launch_first(conv3x3_first<3, 4, false, true>, d, stream);
+        default: return hipErrorInvalidValue;
+        }
+    }
+    if (kind == W2XC_K_LAST_U8) {   // three interleaved uint8 channels out
+        if (d.in_ps != d.cin || d.in_cs != 1 || d.cout != 3 || d.out_ps != 3 || d.out_cs != 1) return hipErrorInvalidValue;
+        switch (d.cin) {
+        case 32: return launch_last(conv3x3_last<32, 3, true>, d, stream);
+        case 64: return launch_last(conv3x3_last<64, 3, true>, d, stream);
+        case 128: return launch_last(conv3x3_last<128, 3, true>, d, stream);
         default: return hipErrorInvalidValue;
         }
     }

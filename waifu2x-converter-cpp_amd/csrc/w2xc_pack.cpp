@@ -30,6 +30,8 @@ const char *w2xc_kernel_name(W2xcKernelKind kind, int cin, int cout)
     case W2XC_K_FIRST2_SPLIT: return "conv3x3_first2_split";
     case W2XC_K_FUSED_AWAY: return "(in_next_layer)";
     case W2XC_K_FIRST2_WINO4: return "conv3x3_first2_wino4";
+    case W2XC_K_FIRST_U8: return "conv3x3_first_u8";
+    case W2XC_K_LAST_U8: return "conv3x3_last_u8";
     default: return "conv3x3_direct";
     }
 }

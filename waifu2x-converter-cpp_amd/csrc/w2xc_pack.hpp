@@ -16,6 +16,10 @@ enum W2xcKernelKind {
     W2XC_K_FIRST2_SPLIT = 10,  // layers 1 (1 -> 32) and 2 (32 -> {32,64,128}) in one kernel; launched in layer 2's slot
     W2XC_K_FUSED_AWAY = 11,    // layer 1 when W2XC_K_FIRST2_SPLIT / W2XC_K_FIRST2_WINO4 computes it: no launch
     W2XC_K_FIRST2_WINO4 = 12,  // fp32: layers 1 (1 -> 32) and 2 (32 -> 32, Winograd F(4x4,3x3)) in one kernel (w2xc_first2_wino4.hip); launched in layer 2's slot
+    // the RGB image pipeline (w2xc_process_image_rgb_u8*): never what w2xc_pick_kernel / layer_kind answer -- run_rows puts them in place of W2XC_K_FIRST /
+    // W2XC_K_LAST for the layer that touches the caller's uint8 image; both read the weight image of the kind they stand in for
+    W2XC_K_FIRST_U8 = 13,      // W2XC_K_FIRST (3 -> {32,64,128}) reading an interleaved uint8 image: d.in = bytes, in_rs / in_ps / in_cs = row stride in bytes / 3 / 1
+    W2XC_K_LAST_U8 = 14,       // W2XC_K_LAST ({32,64,128} -> 3) writing one: d.out = bytes, out_rs / out_ps / out_cs likewise
 };
 
 // Which kernel kind the fast path has for a (cin, cout) layer; W2XC_K_DIRECT when none.

@@ -123,6 +123,7 @@ struct Band {
     long long out_rs, out_cs;
     int y0, y1, rb;
     int in_chunk;   // > 0: layer 1 (or the fused layers 1 + 2) runs in chunks of this many rows behind the upload (first_chunks)
+    int u8;         // ROWS_U8_SRC / ROWS_U8_DST: the view / `out` is an interleaved uint8 image, its strides are in bytes (no hooks: every launch is the plain one)
 
     int launch(int k, W2xcKernelKind kind, const W2xcConvDesc &d) const { return launch_layer(c, m, k - 1, kind, d, st, P.o); }
     // stage the next band's input while this one computes
@@ -327,8 +328,11 @@ int run_band(Band &B, const LayerSrc &view, int up)
     memset(&first_d, 0, sizeof first_d);
     for (int k = 1; k <= n; k++, src = next) {
         if (o.verbose & 1) std::cout << "Iteration #" << k << "..." << std::endl;   // convertRoutine.cpp:67
-        const W2xcKernelKind kind = layer_desc(m, P, k, B.y0, B.y1, up, src, dst, first_d, &d, &next);
+        W2xcKernelKind kind = layer_desc(m, P, k, B.y0, B.y1, up, src, dst, first_d, &d, &next);
         if (kind == W2XC_K_FUSED_AWAY) continue;
+        // the uint8 forms (run_rows has checked the kinds they stand in for): the descriptor's strides are the image's, in bytes
+        if (k == 1 && (B.u8 & ROWS_U8_SRC)) kind = W2XC_K_FIRST_U8;
+        if (k == n && (B.u8 & ROWS_U8_DST)) { kind = W2XC_K_LAST_U8; d.out_ps = 3; }
         const int Tk = next.top;   // first plane row of the layer's region
         // the strategies that run layer n - 1 and the last layer together end the band
         if (prog_eligible(B, k, kind, d)) {
@@ -361,20 +365,27 @@ int run_band(Band &B, const LayerSrc &view, int up)
 // layers run on the banding-invariant geometry conv3x3_wino4 needs (plan_rows); without, W2XC_KERNEL_AUTO is refused (W2XC_ERR_ARG).
 int run_rows(w2xc_model *m, DevCtx *c, const float *d_in, size_t in_stride_f, int vh, int vy0, int w, int ra, int rb,
              float *d_out, size_t out_stride_f, hipStream_t st, const w2xc_opts &o_in, int up, int n_in,
-             long long in_cs, long long out_cs, const BandHooks *hk, int plane_h)
+             long long in_cs, long long out_cs, const BandHooks *hk, int plane_h, int u8)
 {
     RowPlan P;
     {
         int rc = plan_rows(m, o_in, w, vh, vy0, ra, rb, plane_h, n_in, out_cs != 0, &P);
         if (rc) return rc;
     }
+    if (u8 && (hk || ((u8 & ROWS_U8_SRC) && (in_cs != 1 || !u8_source_layer(m, P.o))) ||
+               ((u8 & ROWS_U8_DST) && (out_cs != 1 || !P.last_direct || !u8_sink_layer(m, P.o)))))
+        return fail(W2XC_ERR_ARG, "internal error: a uint8 view for a layer without the uint8 kernel");
     for (int i = 0; i < 2; i++)
         if (P.need[i]) { int rc = c->ws[i].reserve((P.need[i] + 3) / 4 * sizeof(float), "the activation workspace"); if (rc) return rc; }
     LayerSrc view;   // the source view; its first row is plane row vy0
     view.p = d_in; view.rs = (long long)in_stride_f; view.cs = in_cs;
     view.h = vh; view.w = w; view.top = vy0;
+    if (u8 & ROWS_U8_SRC) view.ps = 3;   // (bytes: row stride in_stride_f, pixels 3 apart, channels in_cs = 1 apart)
     for (int y0 = ra; y0 < rb; y0 += P.band) {
-        Band B = {m, c, P, hk, st, d_out + (size_t)(y0 - ra) * out_stride_f, (long long)out_stride_f, out_cs, y0, std::min(rb, y0 + P.band), rb, 0};
+        // the band's first output row: out_stride_f floats per row, or -- a uint8 image -- as many BYTES
+        float *band_out = (u8 & ROWS_U8_DST) ? reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(d_out) + (size_t)(y0 - ra) * out_stride_f)
+                                              : d_out + (size_t)(y0 - ra) * out_stride_f;
+        Band B = {m, c, P, hk, st, band_out, (long long)out_stride_f, out_cs, y0, std::min(rb, y0 + P.band), rb, 0, u8};
         int rc = run_band(B, view, up);
         if (rc) return rc;
     }
@@ -524,22 +535,40 @@ try {
                     out_stride_bytes / 4, (hipStream_t)hip_stream, o, 0, 1, 0, 0, nullptr, plane_h); });
 } W2XC_CATCH_ALL
 
-int w2xc_convert_planes_device(w2xc_model *m, int n_in_planes, const float *d_in, size_t in_plane_stride_bytes,
-                               size_t in_stride_bytes, int w, int h, float *d_out, size_t out_plane_stride_bytes,
-                               size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts)
-try {
-    int rc = check_plane_args(m, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes);
-    if (rc) return rc;
+// w2xc_convert_planes_device (up = 0) and its nearest-2x form (up = 1: (w, h) is the SOURCE size, the output planes are 2w x 2h)
+static int convert_planes(w2xc_model *m, int up, int n_in_planes, const float *d_in, size_t in_plane_stride_bytes, size_t in_stride_bytes, int w, int h,
+                          float *d_out, size_t out_plane_stride_bytes, size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts)
+{
+    const int W = w << up, H = h << up;
+    if (!m || !d_in || !d_out) return fail(W2XC_ERR_ARG, "null argument");
+    if (w <= 0 || h <= 0) return fail(W2XC_ERR_ARG, "plane size must be positive (got %dx%d)", w, h);
+    if (up && (w > (1 << 28) || h > (1 << 28))) return fail(W2XC_ERR_ARG, "plane too large");
+    if (in_stride_bytes < (size_t)w * 4 || out_stride_bytes < (size_t)W * 4 || (in_stride_bytes & 3) || (out_stride_bytes & 3))
+        return fail(W2XC_ERR_ARG, "row strides must be multiples of 4 bytes and >= 4*width");
     if (n_in_planes < 1 || (in_plane_stride_bytes & 3) || (out_plane_stride_bytes & 3) ||
-        (n_in_planes > 1 && in_plane_stride_bytes < in_stride_bytes * (size_t)h) || out_plane_stride_bytes < out_stride_bytes * (size_t)h)
+        (n_in_planes > 1 && in_plane_stride_bytes < in_stride_bytes * (size_t)h) || out_plane_stride_bytes < out_stride_bytes * (size_t)H)
         return fail(W2XC_ERR_ARG, "bad plane count / plane strides");
     const w2xc_opts o = resolve_opts(opts);
     if (o.precision != W2XC_PRECISION_FP32 && split_terms(o) == 0)
         return fail(W2XC_ERR_UNSUPPORTED, "w2xc_convert_planes_* supports W2XC_PRECISION_FP32 / BF16X2 / BF16X3 / FP16X2");
     const long long in_cs = (long long)(in_plane_stride_bytes / 4), out_cs = (long long)(out_plane_stride_bytes / 4);
     return with_ctx(m, o, [&](DevCtx *c) {
-        return run_rows(m, c, d_in, in_stride_bytes / 4, h, 0, w, 0, h, d_out, out_stride_bytes / 4, (hipStream_t)hip_stream, o, 0, n_in_planes, in_cs, out_cs, nullptr, h);
+        return run_rows(m, c, d_in, in_stride_bytes / 4, H, 0, W, 0, H, d_out, out_stride_bytes / 4, (hipStream_t)hip_stream, o, up, n_in_planes, in_cs, out_cs, nullptr, H);
     });
+}
+
+int w2xc_convert_planes_device(w2xc_model *m, int n_in_planes, const float *d_in, size_t in_plane_stride_bytes,
+                               size_t in_stride_bytes, int w, int h, float *d_out, size_t out_plane_stride_bytes,
+                               size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts)
+try {
+    return convert_planes(m, 0, n_in_planes, d_in, in_plane_stride_bytes, in_stride_bytes, w, h, d_out, out_plane_stride_bytes, out_stride_bytes, hip_stream, opts);
+} W2XC_CATCH_ALL
+
+int w2xc_convert_planes_nn2x_device(w2xc_model *m, int n_in_planes, const float *d_in, size_t in_plane_stride_bytes,
+                                    size_t in_stride_bytes, int w, int h, float *d_out, size_t out_plane_stride_bytes,
+                                    size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts)
+try {
+    return convert_planes(m, 1, n_in_planes, d_in, in_plane_stride_bytes, in_stride_bytes, w, h, d_out, out_plane_stride_bytes, out_stride_bytes, hip_stream, opts);
 } W2XC_CATCH_ALL
 
 int w2xc_convert_plane_nn2x_device(w2xc_model *m, const float *d_in, size_t in_stride_bytes, int w, int h, float *d_out,

@@ -178,6 +178,23 @@ bool fuse_first_fp32(const w2xc_model *m, const w2xc_opts &o)
     return is_wino4_layer(m, 2, o);   // (layer 3 = conv3x3_wino4: it reads layer 2's planar planes)
 }
 
+// The RGB image pipeline (w2xc_image.cpp): the layer that touches the caller's interleaved uint8 image converts in its own load / store where a kernel for
+// that exists -- the W2XC_K_FIRST layer of the call's first pass (3 -> 32 / 64 / 128), the W2XC_K_LAST layer of its last pass (32 / 64 / 128 -> 3) -- and
+// the float copy of that image never reaches HBM.  fp32 and the fast kernels only; w2xc_opts.fusion = W2XC_FUSION_OFF keeps the colour kernels around
+// float planes (the same float operations in the same order: the same bytes).
+static bool u8_forms_on(const w2xc_opts &o)
+{
+    return split_terms(o) == 0 && o.precision == W2XC_PRECISION_FP32 && o.kernel != W2XC_KERNEL_DIRECT && o.fusion != W2XC_FUSION_OFF;
+}
+bool u8_source_layer(const w2xc_model *m, const w2xc_opts &o)
+{
+    return u8_forms_on(o) && !m->layers.empty() && m->layers[0].nin == 3 && layer_kind(m, 0, o) == W2XC_K_FIRST;
+}
+bool u8_sink_layer(const w2xc_model *m, const w2xc_opts &o)
+{
+    const int n = (int)m->layers.size();
+    return u8_forms_on(o) && n > 0 && m->layers[n - 1].nout == 3 && layer_kind(m, n - 1, o) == W2XC_K_LAST;
+}
 
 // ------------------------------------------------------------------------------------------------
 // The band geometry of run_rows (w2xc_rows.cpp) as pure host arithmetic: no device, no allocation.  w2xc_plan_rows exposes it
