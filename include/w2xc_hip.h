@@ -352,6 +352,37 @@ int w2xc_process_image_rgb_u8_batch_device(w2xc_model *noise_model, w2xc_model *
 int w2xc_process_image_rgb_u8_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes,
                                     int w, int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio,
                                     const w2xc_opts *opts);
+/* RGBA images: the image calls above for an image with an alpha channel.  v1 of the reference has no such path (main.cpp reads IMREAD_COLOR); like later
+ * upstream versions, alpha goes through the SCALE model and the colour is first extended ("bled") under the transparent pixels, so that the CNN does not
+ * pull the colour that happens to lie under alpha == 0 -- usually black -- into the visible edge.  The arithmetic is defined here:
+ *   in:    h rows of w pixels of 4 interleaved bytes, rows in_stride_bytes >= 4 w apart: three colour channels in the order the 3-channel call of the route
+ *          expects, alpha last.   out: (w << iterations) x (h << iterations), then the optional shrink -- the size of the 3-channel calls -- 4 bytes per
+ *          pixel, rows out_stride_bytes >= 4 W apart; bytes of an output row behind 4 W are not written.
+ *   route: the models choose it.  First layer takes 1 plane (and the last gives 1): the Y pipeline, w2xc_process_image_u8_ex*; 3 planes in and 3 out: the
+ *          RGB pipeline, w2xc_process_image_rgb_u8_ex*; a Y model beside an RGB one, or any other plane count: W2XC_ERR_PLANES.
+ *   bleed: on bytes, in integers.  mask = alpha > 0.  P times, each pass reading only the image and the mask the pass before left: a pixel with mask 0 that
+ *          has n > 0 pixels with mask 1 among the in-bounds pixels of its 3x3 window becomes, per channel, (2 sum + n) / (2 n) in integer division (sum =
+ *          those neighbours' bytes: their mean, half rounded up), and its mask becomes 1.  Every other pixel keeps its bytes, pixels never reached too.
+ *          P = bleed_passes: < 0 = automatic -- the layer count of the noise model, if given, plus that of the scale model, if given: the CNN's reach at
+ *          source resolution; 0 = off; > 0 = that many (passes beyond max(w, h) - 1 change nothing and are not run; more than 65534 that would be run:
+ *          W2XC_ERR_ARG).  With no transparent pixel the bleed is the identity.
+ *   colour: byte for byte what the 3-channel call of the route gives on the bled 3-channel image with the same models, iterations, shrink_ratio and opts.
+ *          It is not clipped or zeroed by alpha afterwards.
+ *   alpha: never sees the noise model.  iterations == 0: the alpha bytes are copied -- or, with a shrink_ratio (the output is then smaller than the
+ *          input), on both routes a = (float)byte * (float)(1.0 / 255.0), the shrink's INTER_LINEAR, out = saturate(rint(255 a)).  Y route: a = (float)byte * (float)(1.0 / 255.0); per iteration
+ *          a <- CNN_scale(nearest2x(a)), what w2xc_convert_plane_nn2x_device does; the shrink's INTER_LINEAR; out = saturate(rint(255 a)), half to even.
+ *          Y and alpha run as ONE batch of two planes per iteration (w2xc_convert_batch_device's launches where they apply: the launch count of the
+ *          3-channel call; the per-plane sequence with the same bits where not).  RGB route: channel 1 of w2xc_process_image_rgb_u8_ex_device(NULL,
+ *          scale_model, ...) with the same iterations, shrink_ratio and opts on the image (A, A, A).
+ * No step depends on the data: an all-255 alpha is processed like any other (callers that know their image is opaque use the 3-channel calls), and the
+ * device form is asynchronous on hip_stream like the other device forms.  The host form runs on w2xc_opts.device: blocking 2-D copies around the device
+ * sequence.  W2XC_ERR_ARG -- before any device is touched -- for everything the 3-channel call of the route refuses, for row strides below 4 * width
+ * and for an output that overlaps the input; without a device W2XC_ERR_HIP.  The merge into 4-byte pixels is one pass of its own over the result. */
+int w2xc_process_image_rgba_u8_ex_device(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *d_in, size_t in_stride_bytes, int w, int h,
+                                         unsigned char *d_out, size_t out_stride_bytes, int iterations, double shrink_ratio, int bleed_passes,
+                                         void *hip_stream, const w2xc_opts *opts);
+int w2xc_process_image_rgba_u8_ex(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes, int w, int h,
+                                  unsigned char *out, size_t out_stride_bytes, int iterations, double shrink_ratio, int bleed_passes, const w2xc_opts *opts);
 /* the building blocks on contiguous float planes (device pointers): main.cpp:144 on one plane, :75-76, :171-172 */
 int w2xc_resize2x_cubic_device(const float *d_src, int w, int h, float *d_dst, void *hip_stream);
 int w2xc_u8_to_yuv_device(const unsigned char *d_in, size_t in_stride_bytes, int w, int h, float *d_y, float *d_u,
@@ -363,6 +394,15 @@ int w2xc_yuv_to_u8_device(const float *d_y, const float *d_u, const float *d_v, 
 int w2xc_u8_to_rgb_device(const unsigned char *d_in, size_t in_stride_bytes, int w, int h, float *d_c0, float *d_c1, float *d_c2, void *hip_stream);
 int w2xc_rgb_to_u8_device(const float *d_c0, const float *d_c1, const float *d_c2, int w, int h, unsigned char *d_out, size_t out_stride_bytes,
                           void *hip_stream);
+
+/* ... and the RGBA call's: the colour bleed alone.  `passes` (>= 0) passes of the bleed above on the w x h RGBA image d_in; d_out_rgb receives the packed
+ * 3-channel image (rows out_stride_bytes >= 3 w apart, bytes behind 3 w untouched; it must not overlap d_in).  Asynchronous on hip_stream, on the current
+ * device.  The call has no model: its scratch (2 bytes per pixel of the largest image so far) is one buffer per device, shared by all callers and kept until
+ * w2xc_bleed_rgba_u8_trim -- calls on different streams that may run at the same time are the caller's to order, as with the calls of one model.
+ * w2xc_bleed_rgba_u8_trim waits for every device that holds such a buffer and releases it (what w2xc_model_trim is to a model's buffers). */
+int w2xc_bleed_rgba_u8_device(const unsigned char *d_in, size_t in_stride_bytes, int w, int h, int passes, unsigned char *d_out_rgb,
+                              size_t out_stride_bytes, void *hip_stream);
+int w2xc_bleed_rgba_u8_trim(void);
 
 /* == Model::filter(inputPlanes, outputPlanes) for layer `layer` (modelHandler.cpp:26-72):
  * n_in_planes host planes of h x w floats in, nout planes out, SAME size, per-layer

@@ -8,7 +8,10 @@ runs on the GPU in one call (w2xc_process_image_u8_ex).
 Extension: several input files (-i a.png b.png ...).  They are grouped by image size and every group is ONE w2xc_process_image_u8_batch call; each
 output gets its automatic name (-o is for a single input only).  A single input behaves exactly as before.
 Extension: RGB models.  When the loaded model's first layer takes 3 planes the image goes through w2xc_process_image_rgb_u8_ex / _batch instead: the three
-channels in PIL's RGB order as they are (no BGR swap: that mimics what the reference feeds its Y path), all three planes through the CNN."""
+channels in PIL's RGB order as they are (no BGR swap: that mimics what the reference feeds its Y path), all three planes through the CNN.
+Extension: transparency.  An input whose decoded image has an alpha channel with any byte below 255 (PIL modes RGBA, LA, P with transparency, ...) goes through
+w2xc_process_image_rgba_u8_ex on the route of the models -- the colour bled under the transparent pixels, alpha through the scale model -- and is written as
+RGBA.  Every other input goes exactly as before, the batch grouping included."""
 import argparse
 import math
 import os
@@ -69,6 +72,12 @@ def model_route(noise, scale):
     return routes.pop() if routes else "y"
 
 
+def wants_alpha(arr):
+    """The alpha decision, on the decoded array: True for an h x w x 4 uint8 array with at least one alpha byte below 255 (the RGBA call), False for
+    everything else -- three channels, or an alpha that is 255 everywhere (the 3-channel route, as before)."""
+    return arr.ndim == 3 and arr.shape[2] == 4 and bool((arr[:, :, 3] < 255).any())
+
+
 def check_inputs(ap, args):
     """-o names ONE output file: with several inputs it is refused (argparse's error exit, status 2)"""
     if len(args.input_file) > 1 and args.output_file != "(auto)":
@@ -114,9 +123,15 @@ def main(argv=None):
     process, process_batch = (w2xc.process_image_rgb_u8, w2xc.process_image_rgb_u8_batch) if rgb else (w2xc.process_image_u8, w2xc.process_image_u8_batch)
 
     def load(path):
-        im = np.asarray(Image.open(path).convert("RGB"))
+        pil = Image.open(path)
+        if pil.mode in ("RGBA", "LA", "PA", "RGBa", "La") or "transparency" in pil.info:
+            im = np.asarray(pil.convert("RGBA"))
+            if wants_alpha(im):
+                return np.ascontiguousarray(im if rgb else im[:, :, [2, 1, 0, 3]])   # (the colour order of the route, alpha last)
+        im = np.asarray(pil.convert("RGB"))
         return np.ascontiguousarray(im if rgb else im[:, :, ::-1])   # Y route: cv::imread(IMREAD_COLOR)'s BGR order (Q3); RGB models take RGB as it is
     images = [load(f) for f in args.input_file]
+    opaque = [(f, im) for f, im in zip(args.input_file, images) if im.shape[2] == 3]
     outs = {}
     if noise is None and iterations == 0 and not shrink:
         outs = dict(zip(args.input_file, images))                      # ratio 1.0 in scale mode: nothing to do
@@ -125,11 +140,14 @@ def main(argv=None):
     else:
         prec = {"fp32": w2xc.PRECISION_FP32, "bf16": w2xc.PRECISION_BF16, "bf16x2": w2xc.PRECISION_BF16X2, "bf16x3": w2xc.PRECISION_BF16X3, "fp16x2": w2xc.PRECISION_FP16X2}[args.precision]
         opts = w2xc.make_opts(precision=prec)      # always explicit: an explicit --precision beats the W2XC_PRECISION env default
-        if len(images) == 1:
-            outs[args.input_file[0]] = process(images[0], noise, scale if iterations else None, iterations, opts, shrink)
-        else:
-            by_file = dict(zip(args.input_file, images))
-            sized = [(f, (im.shape[1], im.shape[0])) for f, im in zip(args.input_file, images)]
+        for f, im in zip(args.input_file, images):
+            if im.shape[2] == 4:                   # (the RGBA call has no batch form)
+                outs[f] = w2xc.process_image_rgba_u8(im, noise, scale if iterations else None, iterations, opts, shrink)
+        if len(opaque) == 1:
+            outs[opaque[0][0]] = process(opaque[0][1], noise, scale if iterations else None, iterations, opts, shrink)
+        elif opaque:
+            by_file = dict(opaque)
+            sized = [(f, (im.shape[1], im.shape[0])) for f, im in opaque]
             for _, files, _ in group_inputs(sized, args.mode, args.noise_level, args.scale_ratio):   # one batch call per image size
                 res = process_batch([by_file[f] for f in files], noise, scale if iterations else None, iterations, opts, shrink)
                 outs.update(zip(files, res))
@@ -137,7 +155,10 @@ def main(argv=None):
         name = args.output_file
         if name == "(auto)":
             name = auto_output_name(f, args.mode, args.noise_level, args.scale_ratio)
-        Image.fromarray(np.ascontiguousarray(outs[f] if rgb else outs[f][:, :, ::-1])).save(name)
+        res = outs[f]
+        if not rgb:
+            res = res[:, :, ::-1] if res.shape[2] == 3 else res[:, :, [2, 1, 0, 3]]
+        Image.fromarray(np.ascontiguousarray(res)).save(name)
     print("process successfully done!")
     return 0
 

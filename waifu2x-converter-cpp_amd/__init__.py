@@ -97,6 +97,10 @@ def _load():
         "w2xc_process_image_rgb_u8_ex": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.c_double, C.POINTER(Opts)]),
         "w2xc_process_image_rgb_u8_batch_device": (ci, [vp, vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, ci, C.c_double, vp, C.POINTER(Opts)]),
         "w2xc_process_image_rgb_u8_batch": (ci, [vp, vp, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, ci, C.c_double, C.POINTER(Opts)]),
+        "w2xc_process_image_rgba_u8_ex_device": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.c_double, ci, vp, C.POINTER(Opts)]),
+        "w2xc_process_image_rgba_u8_ex": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.c_double, ci, C.POINTER(Opts)]),
+        "w2xc_bleed_rgba_u8_device": (ci, [fp, cs, ci, ci, ci, fp, cs, vp]),
+        "w2xc_bleed_rgba_u8_trim": (ci, []),
         "w2xc_convert_planes_nn2x_device": (ci, [vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, vp, C.POINTER(Opts)]),
         "w2xc_u8_to_rgb_device": (ci, [fp, cs, ci, ci, fp, fp, fp, vp]),
         "w2xc_rgb_to_u8_device": (ci, [fp, fp, fp, ci, ci, fp, cs, vp]),
@@ -723,5 +727,52 @@ def rgb_to_u8_device(d_planes, w, h, d_out, out_stride_bytes, stream=0):
     ps = w * h * 4
     rc = _lib.w2xc_rgb_to_u8_device(C.c_void_p(d_planes), C.c_void_p(d_planes + ps), C.c_void_p(d_planes + 2 * ps), w, h, C.c_void_p(d_out),
                                     out_stride_bytes, C.c_void_p(stream))
+    if rc != OK:
+        raise W2xcError(rc, last_error())
+
+
+# ---- RGBA images: alpha through the scale model, the colour bled under the transparent pixels ----
+def process_image_rgba_u8(img, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, bleed_passes=-1):
+    """An h x w x 4 uint8 image (three colour channels in the order the 3-channel call of the route expects, alpha last) through Y models or RGB models
+    -- the models choose the route (w2xc_process_image_rgba_u8_ex): the colour bytes are those of process_image_u8 / process_image_rgb_u8 on the image
+    after `bleed_passes` passes of the colour bleed (< 0: the layer counts of the models given; 0: none), alpha goes through the scale model."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8:
+        raise ValueError("process_image_rgba_u8 wants a uint8 image (got %s)" % img.dtype)
+    if img.ndim != 3 or img.shape[2] != 4:
+        raise ValueError("process_image_rgba_u8 wants an h x w x 4 image (got shape %r)" % (img.shape,))
+    if img.strides[1:] != (4, 1):
+        img = np.ascontiguousarray(img)
+    h, w, _ = img.shape
+    fw, fh = _final_size(w, h, iterations, shrink_ratio)
+    out = np.empty((max(fh, 0), max(fw, 0), 4), np.uint8)
+    rc = _lib.w2xc_process_image_rgba_u8_ex(noise.handle if noise else None, scale.handle if scale else None, img.ctypes.data, img.strides[0], w, h,
+                                            out.ctypes.data, out.strides[0], iterations, float(shrink_ratio), int(bleed_passes),
+                                            C.byref(opts) if opts is not None else None)
+    if rc != OK:
+        raise W2xcError(rc, last_error())
+    return out
+
+
+def process_image_rgba_u8_device(d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, noise=None, scale=None, iterations=0, shrink_ratio=0.0,
+                                 bleed_passes=-1, stream=0, opts=None):
+    """Device-pointer form (w2xc_process_image_rgba_u8_ex_device): w x h x 4 uint8 at d_in, the result at d_out.  Asynchronous on `stream`."""
+    rc = _lib.w2xc_process_image_rgba_u8_ex_device(noise.handle if noise else None, scale.handle if scale else None, C.c_void_p(d_in), in_stride_bytes, w, h,
+                                                   C.c_void_p(d_out), out_stride_bytes, iterations, float(shrink_ratio), int(bleed_passes),
+                                                   C.c_void_p(stream), C.byref(opts) if opts is not None else None)
+    if rc != OK:
+        raise W2xcError(rc, last_error())
+
+
+def bleed_rgba_u8_device(d_in, in_stride_bytes, w, h, passes, d_out_rgb, out_stride_bytes, stream=0):
+    """`passes` passes of the colour bleed on the w x h x 4 uint8 image at d_in -> the packed w x h x 3 image at d_out_rgb (w2xc_bleed_rgba_u8_device)."""
+    rc = _lib.w2xc_bleed_rgba_u8_device(C.c_void_p(d_in), in_stride_bytes, w, h, int(passes), C.c_void_p(d_out_rgb), out_stride_bytes, C.c_void_p(stream))
+    if rc != OK:
+        raise W2xcError(rc, last_error())
+
+
+def bleed_rgba_u8_trim():
+    """release the scratch bleed_rgba_u8_device keeps per device (w2xc_bleed_rgba_u8_trim); waits for those devices first"""
+    rc = _lib.w2xc_bleed_rgba_u8_trim()
     if rc != OK:
         raise W2xcError(rc, last_error())

@@ -233,6 +233,137 @@ __global__ void __launch_bounds__(256) k_resize_linear_batch(const float *src_y,
     }
 }
 
+// ---- RGBA images (w2xc_process_image_rgba_u8*; no counterpart in v1 of the reference) ----
+// Colour bleed: a transparent pixel (alpha == 0) beside opaque ones takes the rounded mean of its opaque 3x3 neighbours, (2 sum + n) / (2 n) per channel,
+// and counts as opaque in the next pass; P passes carry the colour P pixels into the transparent region.  The passes are defined as a ping-pong (a pass
+// reads only what the pass before left); they run IN PLACE on the packed 3-channel image, exactly, because a pixel filled in pass k (its stamp: 0 = opaque in
+// the source, k = filled in pass k, BLEED_FAR = not reached) reads only neighbours whose stamp is below k, and those are written by no thread of pass k; a
+// neighbour's stamp that is being set to k reads as BLEED_FAR or as k, neither of them below k.
+#define BLEED_FAR 0xFFFFu
+
+// writes pixel q of the packed image, its stamp, and -- with first_pass -- pass 1, read from the RGBA source's own alpha
+static __device__ __forceinline__ void rgba_bleed_first_px(const unsigned char *src, long long stride, int w, int h, long long q, int first_pass,
+                                                           unsigned char *dst, long long dst_stride, unsigned short *stamp)
+{
+    const int r = (int)(q / w), c = (int)(q - (long long)r * w);
+    const unsigned char *p = src + r * stride + (long long)c * 4;
+    int o0 = p[0], o1 = p[1], o2 = p[2];
+    unsigned s = p[3] ? 0u : BLEED_FAR;
+    if (s && first_pass) {
+        int n = 0, s0 = 0, s1 = 0, s2 = 0;
+        for (int dy = -1; dy <= 1; dy++) {
+            const int rr = r + dy;
+            if (rr < 0 || rr >= h) continue;
+            for (int dx = -1; dx <= 1; dx++) {
+                const int cc = c + dx;
+                if (cc < 0 || cc >= w) continue;
+                const unsigned char *nb = src + rr * stride + (long long)cc * 4;
+                if (nb[3]) { n++; s0 += nb[0]; s1 += nb[1]; s2 += nb[2]; }
+            }
+        }
+        if (n) { o0 = (2 * s0 + n) / (2 * n); o1 = (2 * s1 + n) / (2 * n); o2 = (2 * s2 + n) / (2 * n); s = 1u; }
+    }
+    unsigned char *d = dst + r * dst_stride + (long long)c * 3;
+    d[0] = (unsigned char)o0; d[1] = (unsigned char)o1; d[2] = (unsigned char)o2;
+    stamp[q] = (unsigned short)s;
+}
+
+__global__ void __launch_bounds__(256) k_rgba_bleed_first(const unsigned char *src, long long stride, int w, int h, int first_pass, unsigned char *dst,
+                                                          long long dst_stride, unsigned short *stamp)
+{
+    const long long total = (long long)w * h;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256)
+        rgba_bleed_first_px(src, stride, w, h, q, first_pass, dst, dst_stride, stamp);
+}
+
+// pass k >= 2, in place (see above)
+static __device__ __forceinline__ void rgba_bleed_pass_px(unsigned char *img, long long stride, int w, int h, long long q, unsigned k, unsigned short *stamp)
+{
+    if (stamp[q] != BLEED_FAR) return;
+    const int r = (int)(q / w), c = (int)(q - (long long)r * w);
+    int n = 0, s0 = 0, s1 = 0, s2 = 0;
+    for (int dy = -1; dy <= 1; dy++) {
+        const int rr = r + dy;
+        if (rr < 0 || rr >= h) continue;
+        for (int dx = -1; dx <= 1; dx++) {
+            const int cc = c + dx;
+            if (cc < 0 || cc >= w) continue;
+            if (stamp[(long long)rr * w + cc] < k) {
+                const unsigned char *nb = img + rr * stride + (long long)cc * 3;
+                n++; s0 += nb[0]; s1 += nb[1]; s2 += nb[2];
+            }
+        }
+    }
+    if (!n) return;
+    unsigned char *d = img + r * stride + (long long)c * 3;
+    d[0] = (unsigned char)((2 * s0 + n) / (2 * n));
+    d[1] = (unsigned char)((2 * s1 + n) / (2 * n));
+    d[2] = (unsigned char)((2 * s2 + n) / (2 * n));
+    stamp[q] = (unsigned short)k;
+}
+
+__global__ void __launch_bounds__(256) k_rgba_bleed_pass(unsigned char *img, long long stride, int w, int h, unsigned k, unsigned short *stamp)
+{
+    const long long total = (long long)w * h;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) rgba_bleed_pass_px(img, stride, w, h, q, k, stamp);
+}
+
+// alpha byte -> a = u8 / 255 (the Y route: the plane that rides with Y through the scale model)
+static __device__ __forceinline__ void alpha_to_plane_px(const unsigned char *src, long long stride, int w, long long q, float *a)
+{
+    const int r = (int)(q / w), c = (int)(q - (long long)r * w);
+    a[q] = (float)src[r * stride + (long long)c * 4 + 3] * (float)(1.0 / 255.0);
+}
+
+__global__ void __launch_bounds__(256) k_alpha_to_plane(const unsigned char *src, long long stride, int w, int h, float *a)
+{
+    const long long total = (long long)w * h;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) alpha_to_plane_px(src, stride, w, q, a);
+}
+
+// alpha byte -> the packed 3-channel image (A, A, A) (the RGB route: alpha goes through the RGB pipeline as a grey image)
+static __device__ __forceinline__ void alpha_to_grey_px(const unsigned char *src, long long stride, int w, long long q, unsigned char *dst, long long dst_stride)
+{
+    const int r = (int)(q / w), c = (int)(q - (long long)r * w);
+    const unsigned char a = src[r * stride + (long long)c * 4 + 3];
+    unsigned char *d = dst + r * dst_stride + (long long)c * 3;
+    d[0] = a; d[1] = a; d[2] = a;
+}
+
+__global__ void __launch_bounds__(256) k_alpha_to_grey(const unsigned char *src, long long stride, int w, int h, unsigned char *dst, long long dst_stride)
+{
+    const long long total = (long long)w * h;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) alpha_to_grey_px(src, stride, w, q, dst, dst_stride);
+}
+
+// the merge: a packed 3-channel result + alpha -> the caller's 4-byte pixels.  Alpha is a float plane (saturate(rint(255 a)), the expression of yuv_to_u8_px)
+// or a byte of an image with a_px bytes per pixel (the RGBA source: 4; the grey result of the RGB route: 3).
+static __device__ __forceinline__ void merge_rgba_px(const unsigned char *rgb, long long rgb_stride, unsigned char a, int w, long long q, unsigned char *dst,
+                                                     long long stride)
+{
+    const int r = (int)(q / w), c = (int)(q - (long long)r * w);
+    const unsigned char *s = rgb + r * rgb_stride + (long long)c * 3;
+    unsigned char *d = dst + r * stride + (long long)c * 4;
+    d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = a;
+}
+
+__global__ void __launch_bounds__(256) k_merge_rgba_f32(const unsigned char *rgb, long long rgb_stride, const float *a, int w, int h, unsigned char *dst, long long stride)
+{
+    const long long total = (long long)w * h;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256)
+        merge_rgba_px(rgb, rgb_stride, (unsigned char)clampi(__float2int_rn(a[q] * 255.0f), 0, 255), w, q, dst, stride);   // round half to even
+}
+
+__global__ void __launch_bounds__(256) k_merge_rgba_u8(const unsigned char *rgb, long long rgb_stride, const unsigned char *a, long long a_stride, int a_px,
+                                                       int w, int h, unsigned char *dst, long long stride)
+{
+    const long long total = (long long)w * h;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) {
+        const int r = (int)(q / w), c = (int)(q - (long long)r * w);
+        merge_rgba_px(rgb, rgb_stride, a[r * a_stride + (long long)c * a_px], w, q, dst, stride);
+    }
+}
+
 static unsigned grid_for(long long total)
 {
     long long b = (total + 255) / 256;
@@ -310,5 +441,38 @@ hipError_t w2xc_launch_rgb_to_u8_batch(const float *planes, long long ps, long l
                                        int n, hipStream_t st)
 {
     hipLaunchKernelGGL(k_rgb_to_u8_batch, grid_batch((long long)w * h, n), dim3(256), 0, st, planes, ps, is, w, h, dst, (long long)img_stride, (long long)stride, n);
+    return hipGetLastError();
+}
+
+// ---- RGBA images ----
+// d_in -> the packed 3-channel image dst after `passes` bleed passes (<= 65534); stamp = w * h 16-bit words of scratch
+hipError_t w2xc_launch_rgba_bleed(const unsigned char *src, size_t stride, int w, int h, int passes, unsigned char *dst, size_t dst_stride, unsigned short *stamp,
+                                  hipStream_t st)
+{
+    const dim3 grid(grid_for((long long)w * h));
+    hipLaunchKernelGGL(k_rgba_bleed_first, grid, dim3(256), 0, st, src, (long long)stride, w, h, passes > 0 ? 1 : 0, dst, (long long)dst_stride, stamp);
+    for (int k = 2; k <= passes; k++) hipLaunchKernelGGL(k_rgba_bleed_pass, grid, dim3(256), 0, st, dst, (long long)dst_stride, w, h, (unsigned)k, stamp);
+    return hipGetLastError();
+}
+hipError_t w2xc_launch_alpha_to_plane(const unsigned char *src, size_t stride, int w, int h, float *a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_alpha_to_plane, dim3(grid_for((long long)w * h)), dim3(256), 0, st, src, (long long)stride, w, h, a);
+    return hipGetLastError();
+}
+hipError_t w2xc_launch_alpha_to_grey(const unsigned char *src, size_t stride, int w, int h, unsigned char *dst, size_t dst_stride, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_alpha_to_grey, dim3(grid_for((long long)w * h)), dim3(256), 0, st, src, (long long)stride, w, h, dst, (long long)dst_stride);
+    return hipGetLastError();
+}
+hipError_t w2xc_launch_merge_rgba(const unsigned char *rgb, size_t rgb_stride, const float *a, int w, int h, unsigned char *dst, size_t stride, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_merge_rgba_f32, dim3(grid_for((long long)w * h)), dim3(256), 0, st, rgb, (long long)rgb_stride, a, w, h, dst, (long long)stride);
+    return hipGetLastError();
+}
+hipError_t w2xc_launch_merge_rgba_u8(const unsigned char *rgb, size_t rgb_stride, const unsigned char *a, size_t a_stride, int a_px, int w, int h,
+                                     unsigned char *dst, size_t stride, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_merge_rgba_u8, dim3(grid_for((long long)w * h)), dim3(256), 0, st, rgb, (long long)rgb_stride, a, (long long)a_stride, a_px, w, h, dst,
+                       (long long)stride);
     return hipGetLastError();
 }

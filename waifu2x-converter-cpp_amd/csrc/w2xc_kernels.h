@@ -135,3 +135,13 @@ hipError_t w2xc_launch_resize2x_cubic_batch(const float *src, long long sps, int
 // n planes (Y, U, V of a sub-batch: n = 3 x images): plane p < ny at src_y + p * sps, the others at src_uv + (p - ny) * sps; -> dst + p * dps
 hipError_t w2xc_launch_resize_linear_batch(const float *src_y, const float *src_uv, int ny, long long sps, int sw, int sh, float *dst, long long dps, int dw,
                                            int dh, int n, hipStream_t st);
+// RGBA images (w2xc_process_image_rgba_u8*): the colour bleed under transparent pixels (`passes` <= 65534 passes, in place on the packed 3-channel image dst;
+// stamp = w * h 16-bit words of scratch, written before they are read), alpha -> a float plane (u8 / 255) or a packed grey image (A, A, A), and the merge of a
+// packed 3-channel result with alpha -- a float plane (saturate(rint(255 a))) or a byte a_px apart in rows a_stride apart -- into 4-byte pixels.
+hipError_t w2xc_launch_rgba_bleed(const unsigned char *src, size_t stride, int w, int h, int passes, unsigned char *dst, size_t dst_stride, unsigned short *stamp,
+                                  hipStream_t st);
+hipError_t w2xc_launch_alpha_to_plane(const unsigned char *src, size_t stride, int w, int h, float *a, hipStream_t st);
+hipError_t w2xc_launch_alpha_to_grey(const unsigned char *src, size_t stride, int w, int h, unsigned char *dst, size_t dst_stride, hipStream_t st);
+hipError_t w2xc_launch_merge_rgba(const unsigned char *rgb, size_t rgb_stride, const float *a, int w, int h, unsigned char *dst, size_t stride, hipStream_t st);
+hipError_t w2xc_launch_merge_rgba_u8(const unsigned char *rgb, size_t rgb_stride, const unsigned char *a, size_t a_stride, int a_px, int w, int h,
+                                     unsigned char *dst, size_t stride, hipStream_t st);

@@ -174,7 +174,9 @@ const char *w2xc_last_error(void) { return g_last_error.c_str(); }
 // also: W2XC_KERNEL_WINOGRAD = _WINOGRAD32, W2XC_KERNEL_AUTO refused on a minimum-halo row view, `verbose` a bit mask (INTEGRATION.md "ABI history")
 // 0.3: w2xc_convert_batch / w2xc_convert_batch_device; 0.4: w2xc_debug_fill_scratch (both additive, no struct change)
 // 0.4.1: the RGB image calls (w2xc_process_image_rgb_u8*), w2xc_convert_planes_nn2x_device, w2xc_u8_to_rgb_device / w2xc_rgb_to_u8_device (additive)
-const char *w2xc_version(void) { return "w2xc_hip 0.4.1 (gfx950)"; }
+// 0.4.1.1: the RGBA image calls (w2xc_process_image_rgba_u8_ex[_device]), w2xc_bleed_rgba_u8_device / _trim (additive; the prefix "w2xc_hip 0.4.1" stays -- callers
+// find the symbols by lookup)
+const char *w2xc_version(void) { return "w2xc_hip 0.4.1.1 (gfx950)"; }
 
 int w2xc_plan_rows(const w2xc_model *m, int w, int view_y0, int view_h, int plane_h, int row_begin, int row_end, const w2xc_opts *opts, w2xc_row_plan *plan)
 try {
