@@ -188,9 +188,10 @@ static void test_batch_stripes()
             }
 }
 
-// The batched image pipeline lays its planes out per level, `cap` images wide (S <= cap of them in use), every plane on a 256-byte boundary: level 0 holds
+// The Y image pipeline lays its planes out per level, `cap` images wide (S <= cap of them in use), every plane on a 256-byte boundary: level 0 holds
 // Y, U, V and the noise pass's second Y; every scale iteration Y, U, V of twice the size; the shrink Y, U, V of the final size.  All of it lies inside
-// cap x image_aux_floats, and no level runs into the next.
+// cap x image_aux_floats, and no level runs into the next.  With alpha (the RGBA call: one image) every Y is a group of two planes, Y and its alpha --
+// on level 0 twice, in every level and in the shrink -- and U follows the group.
 static void test_image_aux()
 {
     const int sizes[][2] = {{1, 1}, {3, 5}, {7, 9}, {8, 8}, {63, 1}, {64, 64}, {65, 63}, {256, 256}, {640, 480}, {1920, 1080}};
@@ -199,14 +200,16 @@ static void test_image_aux()
         for (int it = 0; it <= 4; it++)
             for (size_t k = 0; k < sizeof shrinks / sizeof *shrinks; k++)
                 for (int cap = 1; cap <= 33; cap += 16)
-                    for (int S = 1; S <= cap; S += cap - 1 > 0 ? cap - 1 : 1) {
+                    for (int S = 1; S <= cap; S += cap - 1 > 0 ? cap - 1 : 1)
+                      for (int alpha = 0; alpha <= (cap == 1 ? 1 : 0); alpha++) {
+                        const size_t ya = alpha ? 2 : 1, ny = ya * (size_t)S;   // planes of a Y, of the Y group
                         const int w = sizes[i][0], h = sizes[i][1];
                         const double shrink = shrinks[k];
                         int fw, fh;
                         final_size(w, h, it, shrink, &fw, &fh);
                         if (fw < 1 || fh < 1) continue;   // (refused by the argument checks)
                         CHECK(fw <= (w << it) && fh <= (h << it), "%dx%d it=%d shrink=%g: final size %dx%d", w, h, it, shrink, fw, fh);
-                        const size_t have = image_aux_floats(w, h, it, shrink) * (size_t)cap;
+                        const size_t have = image_aux_floats(w, h, it, shrink, alpha != 0) * (size_t)cap;
                         size_t base = 0, end = 0;
                         // planes [first, first + count) of a level whose planes are ps floats apart hold cw x ch floats each
                         struct { size_t *end; bool ok; void use(size_t base, size_t ps, size_t first, size_t count, size_t px) {
@@ -214,20 +217,22 @@ static void test_image_aux()
                             *end = std::max(*end, base + (first + count - 1) * ps + px); } } lay = {&end, true};
                         int cw = w, ch = h;
                         size_t ps = plane_floats(cw, ch);
-                        lay.use(base, ps, 0, 4 * (size_t)S, (size_t)cw * ch);   // y, u, v, yn: S planes each
-                        base += 4 * (size_t)cap * ps;
+                        lay.use(base, ps, 0, ny, (size_t)cw * ch);                        // the Y group
+                        lay.use(base, ps, ny, 2 * (size_t)S, (size_t)cw * ch);           // u, v: S planes each
+                        lay.use(base, ps, ny + 2 * (size_t)S, ny, (size_t)cw * ch);      // the noise pass's Y group
+                        base += (2 * ya + 2) * (size_t)cap * ps;
                         CHECK(end <= base, "%dx%d it=%d cap=%d S=%d: level 0 runs into the next level", w, h, it, cap, S);
                         for (int l = 0; l < it; l++) {
                             cw *= 2; ch *= 2;
                             ps = plane_floats(cw, ch);
-                            lay.use(base, ps, 0, 3 * (size_t)S, (size_t)cw * ch);
-                            base += 3 * (size_t)cap * ps;
+                            lay.use(base, ps, 0, ny + 2 * (size_t)S, (size_t)cw * ch);   // the Y group, then u, v
+                            base += (ya + 2) * (size_t)cap * ps;
                             CHECK(end <= base, "%dx%d it=%d cap=%d S=%d: level %d runs into the next level", w, h, it, cap, S, l + 1);
                         }
-                        if (shrink > 0.0) lay.use(base, plane_floats(fw, fh), 0, 3 * (size_t)S, (size_t)fw * fh);
+                        if (shrink > 0.0) lay.use(base, plane_floats(fw, fh), 0, ny + 2 * (size_t)S, (size_t)fw * fh);
                         CHECK(lay.ok, "%dx%d it=%d: a plane is larger than its slot or not on a 256-byte boundary", w, h, it);
-                        CHECK(end <= have, "%dx%d it=%d shrink=%g cap=%d S=%d: planes end at float %zu, the buffer holds %zu", w, h, it, shrink, cap, S, end, have);
-                    }
+                        CHECK(end <= have, "%dx%d it=%d shrink=%g cap=%d S=%d alpha=%d: planes end at float %zu, the buffer holds %zu", w, h, it, shrink, cap, S, alpha, end, have);
+                      }
 }
 
 int main()

@@ -232,6 +232,38 @@ def test_jobs_are_the_staging_threads(gpu, scale_layers):
         util.setNumberOfJobs(prev)
 
 
+# ---- the image call: one pipeline behind every form ------------------------------------------------------------------------
+def test_image_single_batch_of_one_and_host_form_agree(gpu):
+    """One 37 x 53 image (w * h is no multiple of 64) through a noise model, one scale iteration and a 0.75 shrink: the single device call (its CNN passes are
+    run_rows'), the batch device call with n = 1 (run_batch's) and the host call return the same bytes.  After the noise pass the Y plane does not adjoin U
+    and V, and one linear launch shrinks all three."""
+    import torch
+    noise = gpu._ModelSet.from_layers(small_layers([1, 16, 16, 1], 41))
+    scale = gpu._ModelSet.from_layers(small_layers([1, 16, 16, 1], 42))
+    w, h, it, shrink = 37, 53, 1, 0.75
+    W, H = int(float((w << it) * shrink)), int(float((h << it) * shrink))
+    img = np.random.default_rng(43).integers(0, 256, (h, w, 3)).astype(np.uint8)
+    d_in = torch.from_numpy(img).cuda()
+    st = torch.cuda.current_stream()
+    o = gpu.make_opts(device=0)
+    got = {"host": gpu.process_image_u8(img, noise, scale, it, o, shrink)}
+    assert got["host"].shape == (H, W, 3)
+    for name in ("single", "batch"):
+        d_out = torch.full((H, W, 3), 0xA5, dtype=torch.uint8, device="cuda")
+        if name == "single":
+            rc = gpu.lib().w2xc_process_image_u8_ex_device(noise.handle, scale.handle, d_in.data_ptr(), w * 3, w, h, d_out.data_ptr(), W * 3, it, shrink,
+                                                           st.cuda_stream, C.byref(o))
+            assert rc == gpu.OK, gpu.last_error()
+        else:
+            gpu.process_image_u8_batch_device(1, d_in.data_ptr(), w * 3 * h, w * 3, w, h, d_out.data_ptr(), W * 3 * H, W * 3, noise, scale, it, shrink,
+                                              stream=st.cuda_stream, opts=o)
+        st.synchronize()
+        got[name] = d_out.cpu().numpy()
+    assert len(np.unique(got["host"])) > 16, "a flat result would compare equal whatever ran"
+    assert np.array_equal(got["single"], got["host"]), "single device call != host call"
+    assert np.array_equal(got["batch"], got["host"]), "batch device call with n = 1 != host call"
+
+
 # ---- Model::filter: persistent buffers, device-resident chain ----------------------------------------------------------
 def test_filter_chain_resident_and_not(gpu):
     """the reference's test.cpp:72-85 pattern (filter() chained by hand).  filter_resident = 1 reuses the previous call's

@@ -585,22 +585,13 @@ def shard_view(plane_h, row_begin, row_end, n_layers):
     return max(0, row_begin - n_layers), min(plane_h, row_end + n_layers)
 
 
-def process_image_u8(img, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0):
-    """The CLI's processing modes on an h x w x 3 uint8 image (main.cpp -m noise | scale | noise_scale):
-    `noise` / `scale` are _ModelSet objects (either may be None); shrink_ratio = the final INTER_LINEAR shrink
-    of main.cpp:158-167 (0 = none)."""
-    img = np.ascontiguousarray(img, dtype=np.uint8)
-    h, w, _ = img.shape
-    fh, fw = h << iterations, w << iterations
-    if shrink_ratio:
-        fw, fh = int(float(fw * shrink_ratio)), int(float(fh * shrink_ratio))
-    out = np.empty((fh, fw, 3), np.uint8)
-    rc = _lib.w2xc_process_image_u8_ex(noise.handle if noise else None, scale.handle if scale else None, img.ctypes.data,
-                                       img.strides[0], w, h, out.ctypes.data, out.strides[0], iterations, float(shrink_ratio),
-                                       C.byref(opts) if opts is not None else None)
+def _check(rc):
     if rc != OK:
         raise W2xcError(rc, last_error())
-    return out
+
+
+def _handles(noise, scale):
+    return noise.handle if noise else None, scale.handle if scale else None
 
 
 def _final_size(w, h, iterations, shrink_ratio):
@@ -608,6 +599,34 @@ def _final_size(w, h, iterations, shrink_ratio):
     if shrink_ratio:
         fw, fh = int(float(fw * shrink_ratio)), int(float(fh * shrink_ratio))
     return fw, fh
+
+
+def _image_host(entry, who, img, channels, noise, scale, iterations, opts, shrink_ratio, extra=(), lenient=False):
+    """the single-image host calls: an h x w x channels uint8 image in, the H x W x channels result out; `extra` = the entry's arguments between
+    shrink_ratio and opts.  lenient (process_image_u8): whatever numpy casts to a contiguous uint8 array, unchecked"""
+    if lenient:
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+    else:
+        img = np.asarray(img)
+        if img.dtype != np.uint8:
+            raise ValueError("%s wants a uint8 image (got %s)" % (who, img.dtype))
+        if img.ndim != 3 or img.shape[2] != channels:
+            raise ValueError("%s wants an h x w x %d image (got shape %r)" % (who, channels, img.shape))
+        if img.strides[1:] != (channels, 1):
+            img = np.ascontiguousarray(img)
+    h, w, _ = img.shape
+    fw, fh = _final_size(w, h, iterations, shrink_ratio)
+    out = np.empty((max(fh, 0), max(fw, 0), channels), np.uint8)
+    _check(entry(*_handles(noise, scale), img.ctypes.data, img.strides[0], w, h, out.ctypes.data, out.strides[0], iterations, float(shrink_ratio),
+                 *extra, C.byref(opts) if opts is not None else None))
+    return out
+
+
+def process_image_u8(img, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0):
+    """The CLI's processing modes on an h x w x 3 uint8 image (main.cpp -m noise | scale | noise_scale):
+    `noise` / `scale` are _ModelSet objects (either may be None); shrink_ratio = the final INTER_LINEAR shrink
+    of main.cpp:158-167 (0 = none)."""
+    return _image_host(_lib.w2xc_process_image_u8_ex, "process_image_u8", img, 3, noise, scale, iterations, opts, shrink_ratio, lenient=True)
 
 
 def process_image_u8_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, out=None):
@@ -644,10 +663,8 @@ def _image_batch(entry, who, imgs, noise, scale, iterations, opts, shrink_ratio,
         raise ValueError("%s: `out` must be a uint8 (n, H, W, 3) array with contiguous rows" % who)
     ip = (C.c_void_p * n)(*[a.ctypes.data for a in srcs])
     op = (C.c_void_p * n)(*[out[i].ctypes.data for i in range(n)])
-    rc = entry(noise.handle if noise else None, scale.handle if scale else None, n, ip, srcs[0].strides[0], w, h,
-               op, out.strides[1], iterations, float(shrink_ratio), C.byref(opts) if opts is not None else None)
-    if rc != OK:
-        raise W2xcError(rc, last_error())
+    _check(entry(*_handles(noise, scale), n, ip, srcs[0].strides[0], w, h,
+                 op, out.strides[1], iterations, float(shrink_ratio), C.byref(opts) if opts is not None else None))
     return out
 
 
@@ -655,12 +672,10 @@ def process_image_u8_batch_device(n, d_in, in_image_stride_bytes, in_stride_byte
                                   noise=None, scale=None, iterations=0, shrink_ratio=0.0, stream=0, opts=None):
     """Device-pointer image batch (w2xc_process_image_u8_batch_device): n images of w x h x 3 uint8 at d_in + i * in_image_stride_bytes, the
     outputs at d_out + i * out_image_stride_bytes.  Asynchronous on `stream`."""
-    rc = _lib.w2xc_process_image_u8_batch_device(noise.handle if noise else None, scale.handle if scale else None, n, C.c_void_p(d_in),
-                                                 in_image_stride_bytes, in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes,
-                                                 out_stride_bytes, iterations, float(shrink_ratio), C.c_void_p(stream),
-                                                 C.byref(opts) if opts is not None else None)
-    if rc != OK:
-        raise W2xcError(rc, last_error())
+    _check(_lib.w2xc_process_image_u8_batch_device(*_handles(noise, scale), n, C.c_void_p(d_in),
+                                                   in_image_stride_bytes, in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes,
+                                                   out_stride_bytes, iterations, float(shrink_ratio), C.c_void_p(stream),
+                                                   C.byref(opts) if opts is not None else None))
 
 
 # ---- RGB models (3 planes in, 3 out): the image calls above for the form most published waifu2x weights have ----
@@ -668,32 +683,15 @@ def process_image_rgb_u8(img, noise=None, scale=None, iterations=0, opts=None, s
     """An h x w x 3 uint8 image through RGB models (w2xc_process_image_rgb_u8_ex): x = u8 / 255 on the channels as given, an optional noise
     pass, `iterations` 2x passes (nearest 2x + CNN on all three planes), the optional INTER_LINEAR shrink, saturate(rint(255 x)).
     `noise` / `scale` are _ModelSet objects whose first layer takes 3 planes and whose last gives 3 (either may be None)."""
-    img = np.asarray(img)
-    if img.dtype != np.uint8:
-        raise ValueError("process_image_rgb_u8 wants a uint8 image (got %s)" % img.dtype)
-    if img.ndim != 3 or img.shape[2] != 3:
-        raise ValueError("process_image_rgb_u8 wants an h x w x 3 image (got shape %r)" % (img.shape,))
-    if img.strides[1:] != (3, 1):
-        img = np.ascontiguousarray(img)
-    h, w, _ = img.shape
-    fw, fh = _final_size(w, h, iterations, shrink_ratio)
-    out = np.empty((max(fh, 0), max(fw, 0), 3), np.uint8)
-    rc = _lib.w2xc_process_image_rgb_u8_ex(noise.handle if noise else None, scale.handle if scale else None, img.ctypes.data,
-                                           img.strides[0], w, h, out.ctypes.data, out.strides[0], iterations, float(shrink_ratio),
-                                           C.byref(opts) if opts is not None else None)
-    if rc != OK:
-        raise W2xcError(rc, last_error())
-    return out
+    return _image_host(_lib.w2xc_process_image_rgb_u8_ex, "process_image_rgb_u8", img, 3, noise, scale, iterations, opts, shrink_ratio)
 
 
 def process_image_rgb_u8_device(d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, noise=None, scale=None, iterations=0, shrink_ratio=0.0,
                                 stream=0, opts=None):
     """Device-pointer form (w2xc_process_image_rgb_u8_ex_device): w x h x 3 uint8 at d_in, the result at d_out.  Asynchronous on `stream`."""
-    rc = _lib.w2xc_process_image_rgb_u8_ex_device(noise.handle if noise else None, scale.handle if scale else None, C.c_void_p(d_in),
-                                                  in_stride_bytes, w, h, C.c_void_p(d_out), out_stride_bytes, iterations, float(shrink_ratio),
-                                                  C.c_void_p(stream), C.byref(opts) if opts is not None else None)
-    if rc != OK:
-        raise W2xcError(rc, last_error())
+    _check(_lib.w2xc_process_image_rgb_u8_ex_device(*_handles(noise, scale), C.c_void_p(d_in),
+                                                    in_stride_bytes, w, h, C.c_void_p(d_out), out_stride_bytes, iterations, float(shrink_ratio),
+                                                    C.c_void_p(stream), C.byref(opts) if opts is not None else None))
 
 
 def process_image_rgb_u8_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, out=None):
@@ -705,30 +703,24 @@ def process_image_rgb_u8_batch(imgs, noise=None, scale=None, iterations=0, opts=
 def process_image_rgb_u8_batch_device(n, d_in, in_image_stride_bytes, in_stride_bytes, w, h, d_out, out_image_stride_bytes, out_stride_bytes,
                                       noise=None, scale=None, iterations=0, shrink_ratio=0.0, stream=0, opts=None):
     """Device-pointer image batch for RGB models (w2xc_process_image_rgb_u8_batch_device); arguments as process_image_u8_batch_device."""
-    rc = _lib.w2xc_process_image_rgb_u8_batch_device(noise.handle if noise else None, scale.handle if scale else None, n, C.c_void_p(d_in),
-                                                     in_image_stride_bytes, in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes,
-                                                     out_stride_bytes, iterations, float(shrink_ratio), C.c_void_p(stream),
-                                                     C.byref(opts) if opts is not None else None)
-    if rc != OK:
-        raise W2xcError(rc, last_error())
+    _check(_lib.w2xc_process_image_rgb_u8_batch_device(*_handles(noise, scale), n, C.c_void_p(d_in),
+                                                       in_image_stride_bytes, in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes,
+                                                       out_stride_bytes, iterations, float(shrink_ratio), C.c_void_p(stream),
+                                                       C.byref(opts) if opts is not None else None))
 
 
 def u8_to_rgb_device(d_in, in_stride_bytes, w, h, d_planes, stream=0):
     """uint8 / 255 of a w x h x 3 image into three contiguous w x h float planes at d_planes (w2xc_u8_to_rgb_device)."""
     ps = w * h * 4
-    rc = _lib.w2xc_u8_to_rgb_device(C.c_void_p(d_in), in_stride_bytes, w, h, C.c_void_p(d_planes), C.c_void_p(d_planes + ps),
-                                    C.c_void_p(d_planes + 2 * ps), C.c_void_p(stream))
-    if rc != OK:
-        raise W2xcError(rc, last_error())
+    _check(_lib.w2xc_u8_to_rgb_device(C.c_void_p(d_in), in_stride_bytes, w, h, C.c_void_p(d_planes), C.c_void_p(d_planes + ps),
+                                      C.c_void_p(d_planes + 2 * ps), C.c_void_p(stream)))
 
 
 def rgb_to_u8_device(d_planes, w, h, d_out, out_stride_bytes, stream=0):
     """saturate(rint(255 x)) of three contiguous w x h float planes at d_planes into a w x h x 3 uint8 image (w2xc_rgb_to_u8_device)."""
     ps = w * h * 4
-    rc = _lib.w2xc_rgb_to_u8_device(C.c_void_p(d_planes), C.c_void_p(d_planes + ps), C.c_void_p(d_planes + 2 * ps), w, h, C.c_void_p(d_out),
-                                    out_stride_bytes, C.c_void_p(stream))
-    if rc != OK:
-        raise W2xcError(rc, last_error())
+    _check(_lib.w2xc_rgb_to_u8_device(C.c_void_p(d_planes), C.c_void_p(d_planes + ps), C.c_void_p(d_planes + 2 * ps), w, h, C.c_void_p(d_out),
+                                      out_stride_bytes, C.c_void_p(stream)))
 
 
 # ---- RGBA images: alpha through the scale model, the colour bled under the transparent pixels ----
@@ -736,43 +728,23 @@ def process_image_rgba_u8(img, noise=None, scale=None, iterations=0, opts=None, 
     """An h x w x 4 uint8 image (three colour channels in the order the 3-channel call of the route expects, alpha last) through Y models or RGB models
     -- the models choose the route (w2xc_process_image_rgba_u8_ex): the colour bytes are those of process_image_u8 / process_image_rgb_u8 on the image
     after `bleed_passes` passes of the colour bleed (< 0: the layer counts of the models given; 0: none), alpha goes through the scale model."""
-    img = np.asarray(img)
-    if img.dtype != np.uint8:
-        raise ValueError("process_image_rgba_u8 wants a uint8 image (got %s)" % img.dtype)
-    if img.ndim != 3 or img.shape[2] != 4:
-        raise ValueError("process_image_rgba_u8 wants an h x w x 4 image (got shape %r)" % (img.shape,))
-    if img.strides[1:] != (4, 1):
-        img = np.ascontiguousarray(img)
-    h, w, _ = img.shape
-    fw, fh = _final_size(w, h, iterations, shrink_ratio)
-    out = np.empty((max(fh, 0), max(fw, 0), 4), np.uint8)
-    rc = _lib.w2xc_process_image_rgba_u8_ex(noise.handle if noise else None, scale.handle if scale else None, img.ctypes.data, img.strides[0], w, h,
-                                            out.ctypes.data, out.strides[0], iterations, float(shrink_ratio), int(bleed_passes),
-                                            C.byref(opts) if opts is not None else None)
-    if rc != OK:
-        raise W2xcError(rc, last_error())
-    return out
+    return _image_host(_lib.w2xc_process_image_rgba_u8_ex, "process_image_rgba_u8", img, 4, noise, scale, iterations, opts, shrink_ratio,
+                       extra=(int(bleed_passes),))
 
 
 def process_image_rgba_u8_device(d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, noise=None, scale=None, iterations=0, shrink_ratio=0.0,
                                  bleed_passes=-1, stream=0, opts=None):
     """Device-pointer form (w2xc_process_image_rgba_u8_ex_device): w x h x 4 uint8 at d_in, the result at d_out.  Asynchronous on `stream`."""
-    rc = _lib.w2xc_process_image_rgba_u8_ex_device(noise.handle if noise else None, scale.handle if scale else None, C.c_void_p(d_in), in_stride_bytes, w, h,
-                                                   C.c_void_p(d_out), out_stride_bytes, iterations, float(shrink_ratio), int(bleed_passes),
-                                                   C.c_void_p(stream), C.byref(opts) if opts is not None else None)
-    if rc != OK:
-        raise W2xcError(rc, last_error())
+    _check(_lib.w2xc_process_image_rgba_u8_ex_device(*_handles(noise, scale), C.c_void_p(d_in), in_stride_bytes, w, h,
+                                                     C.c_void_p(d_out), out_stride_bytes, iterations, float(shrink_ratio), int(bleed_passes),
+                                                     C.c_void_p(stream), C.byref(opts) if opts is not None else None))
 
 
 def bleed_rgba_u8_device(d_in, in_stride_bytes, w, h, passes, d_out_rgb, out_stride_bytes, stream=0):
     """`passes` passes of the colour bleed on the w x h x 4 uint8 image at d_in -> the packed w x h x 3 image at d_out_rgb (w2xc_bleed_rgba_u8_device)."""
-    rc = _lib.w2xc_bleed_rgba_u8_device(C.c_void_p(d_in), in_stride_bytes, w, h, int(passes), C.c_void_p(d_out_rgb), out_stride_bytes, C.c_void_p(stream))
-    if rc != OK:
-        raise W2xcError(rc, last_error())
+    _check(_lib.w2xc_bleed_rgba_u8_device(C.c_void_p(d_in), in_stride_bytes, w, h, int(passes), C.c_void_p(d_out_rgb), out_stride_bytes, C.c_void_p(stream)))
 
 
 def bleed_rgba_u8_trim():
     """release the scratch bleed_rgba_u8_device keeps per device (w2xc_bleed_rgba_u8_trim); waits for those devices first"""
-    rc = _lib.w2xc_bleed_rgba_u8_trim()
-    if rc != OK:
-        raise W2xcError(rc, last_error())
+    _check(_lib.w2xc_bleed_rgba_u8_trim())

@@ -2,9 +2,8 @@
 // CLI's scale loop (/root/reference/src/main.cpp:74-76,136,144,171-172), so that the whole scale phase of
 // one image runs device-resident.  All kernels are HBM-streaming (a few bytes per pixel) and keep
 // OpenCV's float evaluation order with unfused mul/add (the file is built with -ffp-contract=off).
-// Every stage is ONE __device__ body per output element (*_px), shared by the one-image kernel and its batch form
-// (w2xc_process_image_u8_batch*): a batch kernel takes its image / plane from blockIdx.y -- uniform per workgroup -- and moves only the
-// 64-bit base pointers by image x stride; the index arithmetic inside an image is the one-image kernel's.
+// Every stage is ONE __device__ body per output element (*_px).  The YUV and resize stages have a batch kernel only (one image: n = 1): it takes its
+// image / plane from blockIdx.y -- uniform per workgroup -- and moves only the 64-bit base pointers by image x stride.
 #include "w2xc_kernels.h"
 
 static __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -23,12 +22,6 @@ static __device__ __forceinline__ void u8_to_yuv_px(const unsigned char *src, lo
     y[q] = Y;
     u[q] = (c2 - Y) * 0.492f + 0.5f;
     v[q] = (c0 - Y) * 0.877f + 0.5f;
-}
-
-__global__ void __launch_bounds__(256) k_u8_to_yuv(const unsigned char *src, long long stride, int w, int h, float *y, float *u, float *v)
-{
-    const long long total = (long long)w * h;
-    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) u8_to_yuv_px(src, stride, w, q, y, u, v);
 }
 
 // n images, image i at src + i * img_stride bytes; its planes at y / u / v + i * ps floats
@@ -55,12 +48,6 @@ static __device__ __forceinline__ void yuv_to_u8_px(const float *y, const float 
     unsigned char *p = dst + r * stride + (long long)c * 3;
 #pragma unroll
     for (int k = 0; k < 3; k++) p[k] = (unsigned char)clampi(__float2int_rn(ch[k] * 255.0f), 0, 255);   // round half to even
-}
-
-__global__ void __launch_bounds__(256) k_yuv_to_u8(const float *y, const float *u, const float *v, int w, int h, unsigned char *dst, long long stride)
-{
-    const long long total = (long long)w * h;
-    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) yuv_to_u8_px(y, u, v, w, q, dst, stride);
 }
 
 // n images: planes of image i at y / u / v + i * ps floats, its pixels at dst + i * img_stride bytes
@@ -172,12 +159,6 @@ static __device__ __forceinline__ void resize2x_cubic_px(const float *src, int w
     dst[q] = a;
 }
 
-__global__ void __launch_bounds__(256) k_resize2x_cubic(const float *src, int w, int h, float *dst)
-{
-    const long long total = 4LL * w * h;
-    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) resize2x_cubic_px(src, w, h, q, dst);
-}
-
 // n planes (the U and the V planes of a sub-batch, adjacent): plane p at src + p * sps, its 2x plane at dst + p * dps (floats)
 __global__ void __launch_bounds__(256) k_resize2x_cubic_batch(const float *src, long long sps, int w, int h, float *dst, long long dps, int n)
 {
@@ -212,12 +193,6 @@ static __device__ __forceinline__ void resize_linear_px(const float *src, int sw
     float a = h0 * b0;
     a = a + h1 * b1;
     dst[q] = a;
-}
-
-__global__ void __launch_bounds__(256) k_resize_linear(const float *src, int sw, int sh, float *dst, int dw, int dh, double scale_x, double scale_y)
-{
-    const long long total = (long long)dw * dh;
-    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) resize_linear_px(src, sw, sh, q, dst, dw, scale_x, scale_y);
 }
 
 // n planes (Y, U and V of a sub-batch): the first ny planes at src_y + p * sps (the Y planes: after a noise pass they do not adjoin U), plane p >= ny at
@@ -370,28 +345,6 @@ static unsigned grid_for(long long total)
     return (unsigned)(b > 65536 ? 65536 : (b < 1 ? 1 : b));
 }
 
-hipError_t w2xc_launch_u8_to_yuv(const unsigned char *src, size_t stride, int w, int h, float *y, float *u, float *v, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_u8_to_yuv, dim3(grid_for((long long)w * h)), dim3(256), 0, st, src, (long long)stride, w, h, y, u, v);
-    return hipGetLastError();
-}
-hipError_t w2xc_launch_yuv_to_u8(const float *y, const float *u, const float *v, int w, int h, unsigned char *dst, size_t stride, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_yuv_to_u8, dim3(grid_for((long long)w * h)), dim3(256), 0, st, y, u, v, w, h, dst, (long long)stride);
-    return hipGetLastError();
-}
-hipError_t w2xc_launch_resize2x_cubic(const float *src, int w, int h, float *dst, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_resize2x_cubic, dim3(grid_for(4LL * w * h)), dim3(256), 0, st, src, w, h, dst);
-    return hipGetLastError();
-}
-hipError_t w2xc_launch_resize_linear(const float *src, int sw, int sh, float *dst, int dw, int dh, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_resize_linear, dim3(grid_for((long long)dw * dh)), dim3(256), 0, st, src, sw, sh, dst, dw, dh,
-                       (double)sw / dw, (double)sh / dh);
-    return hipGetLastError();
-}
-
 // ---- batch forms: grid.y = images / planes (a grid-stride loop inside the kernel covers more than 65535) ----
 static dim3 grid_batch(long long total, int n) { return dim3(grid_for(total), (unsigned)(n > 65535 ? 65535 : n)); }
 
@@ -418,6 +371,21 @@ hipError_t w2xc_launch_resize_linear_batch(const float *src_y, const float *src_
     hipLaunchKernelGGL(k_resize_linear_batch, grid_batch((long long)dw * dh, n), dim3(256), 0, st, src_y, src_uv, ny, sps, sw, sh, dst, dps, dw, dh,
                        (double)sw / dw, (double)sh / dh, n);
     return hipGetLastError();
+}
+
+// one image / one plane: the batch launch with n = 1
+hipError_t w2xc_launch_u8_to_yuv(const unsigned char *src, size_t stride, int w, int h, float *y, float *u, float *v, hipStream_t st)
+{
+    return w2xc_launch_u8_to_yuv_batch(src, 0, stride, w, h, y, u, v, 0, 1, st);
+}
+hipError_t w2xc_launch_yuv_to_u8(const float *y, const float *u, const float *v, int w, int h, unsigned char *dst, size_t stride, hipStream_t st)
+{
+    return w2xc_launch_yuv_to_u8_batch(y, u, v, 0, w, h, dst, 0, stride, 1, st);
+}
+hipError_t w2xc_launch_resize2x_cubic(const float *src, int w, int h, float *dst, hipStream_t st) { return w2xc_launch_resize2x_cubic_batch(src, 0, w, h, dst, 0, 1, st); }
+hipError_t w2xc_launch_resize_linear(const float *src, int sw, int sh, float *dst, int dw, int dh, hipStream_t st)
+{
+    return w2xc_launch_resize_linear_batch(src, src, 1, 0, sw, sh, dst, 0, dw, dh, 1, st);
 }
 
 // ---- the RGB pipeline's colour stages ----

@@ -20,7 +20,8 @@
 //   w2xc_host_pipeline.cpp  host plane in -> host plane out: staging rings, three streams, the feeder with its Uploader, the drainer (Stitcher), the unit
 //                           fan-out (run_units), the host batch pipeline
 //   w2xc_filter.cpp         Model::filter at the host / device boundary (src/modelHandler.cpp:26-72)
-//   w2xc_image.cpp          N2: the CLI's image pipeline around the plane conversion (main.cpp:74-172), for Y models and for RGB models
+//   w2xc_image.cpp          N2: the CLI's image pipeline around the plane conversion (main.cpp:74-172): one pipeline for Y models and one for RGB models, each
+//                           for S images of one size; the single-image, batch and RGBA entry points around them
 #pragma once
 #include "../../include/w2xc_hip.h"
 

@@ -82,15 +82,17 @@ inline void final_size(int w, int h, int iterations, double shrink, int *fw, int
     }
 }
 
-// float planes of ONE image over all levels of the batched image pipeline, every plane on a 256-byte boundary
+// float planes of ONE image over all levels of the Y image pipeline, every plane on a 256-byte boundary: per level Y, U and V, on level 0 a second Y for
+// the noise pass; with alpha (one image: the RGBA call) every Y has an alpha plane behind it
 inline size_t plane_floats(int w, int h) { return ((size_t)w * h + 63) & ~(size_t)63; }
-inline size_t image_aux_floats(int w, int h, int iterations, double shrink)
+inline size_t image_aux_floats(int w, int h, int iterations, double shrink, bool alpha = false)
 {
-    size_t need = 4 * plane_floats(w, h);
-    for (int i = 1; i <= iterations; i++) need += 3 * plane_floats(w << i, h << i);
+    const size_t ya = alpha ? 2 : 1;
+    size_t need = (2 * ya + 2) * plane_floats(w, h);
+    for (int i = 1; i <= iterations; i++) need += (ya + 2) * plane_floats(w << i, h << i);
     int fw, fh;
     final_size(w, h, iterations, shrink, &fw, &fh);
-    if (shrink > 0.0) need += 3 * plane_floats(fw, fh);
+    if (shrink > 0.0) need += (ya + 2) * plane_floats(fw, fh);
     return need;
 }
 
