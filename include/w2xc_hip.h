@@ -383,6 +383,71 @@ int w2xc_process_image_rgba_u8_ex_device(w2xc_model *noise_model, w2xc_model *sc
                                          void *hip_stream, const w2xc_opts *opts);
 int w2xc_process_image_rgba_u8_ex(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes, int w, int h,
                                   unsigned char *out, size_t out_stride_bytes, int iterations, double shrink_ratio, int bleed_passes, const w2xc_opts *opts);
+/* Test-time augmentation (TTA): every CNN pass runs on the 8 flips and transposes of its input, each result is transformed back and the 8 are averaged --
+ * the quality option later upstream versions of the converter have as --tta (v1 of the reference has none); 8x the CNN work.  The arithmetic is defined here:
+ *   T_k, k = 0..7, on a plane x of h rows x w columns applies, in this order: the horizontal flip (x[:, ::-1]) if k & 1, the vertical flip (x[::-1, :]) if
+ *          k & 2, the transpose if k & 4.  T_k^-1 undoes them in the reverse order.  Variants 0..3 are h x w ("upright"), variants 4..7 are w x h ("transposed").
+ *   One TTA pass of a model, plane-wise for a model of several planes:
+ *          v_k = T_k^-1( CNN( T_k(x) ) ),  k = 0..7
+ *          out = (((((((v_0 + v_1) + v_2) + v_3) + v_4) + v_5) + v_6) + v_7) * 0.125f
+ *          in fp32, in exactly this order, nothing contracted.  CNN = what the call without TTA runs with the same options: w2xc_convert_plane[_nn2x]_device for
+ *          a one-plane model (the variants of one size go through w2xc_convert_batch_device's launches -- one batch of 8 n planes where w == h, two of 4 n
+ *          otherwise -- whose planes are bit-identical to the single call), w2xc_convert_planes[_nn2x]_device for a model of several planes (the single-image
+ *          launch sequence per variant).  Nearest-2x commutes with every T_k: a scale pass transforms the SOURCE, runs with the 2x folded into layer 1 as
+ *          always and transforms back at 2x; the 2x float source never exists.
+ *   Image calls: TTA replaces every CNN pass of the route by its TTA pass -- the noise pass and every scale iteration; Y on the Y route, all three planes on the
+ *          RGB route.  Everything else is the call without TTA: the colour conversion, the bicubic U / V, the shrink, the final rounding; the image stays float
+ *          between passes.  On the RGB route the first / last layer does NOT read / write the uint8 image itself under TTA (the mean is taken before the
+ *          rounding): the colour kernels run around float planes.
+ * Memory: the variant planes of the largest pass -- 8 planes at its input level, 8 at its output level per plane that goes through the CNN -- live with the
+ * image planes in the model's context (released by w2xc_model_trim, filled by w2xc_debug_fill_scratch), count into the per-image bytes that size a sub-batch
+ * under w2xc_opts.workspace_mb, and are reused by every pass.
+ *
+ * Plane calls.  w2xc_convert_batch_tta_device: one TTA pass on each of n planes, the arguments and errors of w2xc_convert_batch_device (one plane in, one plane
+ * out).  w2xc_convert_planes_tta_device: one TTA pass of a model of n_in_planes planes, the arguments and errors of w2xc_convert_planes_device (nn2x = 0) /
+ * w2xc_convert_planes_nn2x_device (nn2x = 1); nn2x outside {0, 1} and a plane count the model does not take are refused before a device is touched.  Both are
+ * asynchronous on hip_stream, on device opts->device. */
+int w2xc_convert_batch_tta_device(w2xc_model *m, int n, int nn2x, const float *d_in, size_t in_plane_stride_bytes, size_t in_stride_bytes, int w, int h,
+                                  float *d_out, size_t out_plane_stride_bytes, size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts);
+int w2xc_convert_planes_tta_device(w2xc_model *m, int n_in_planes, int nn2x, const float *d_in, size_t in_plane_stride_bytes, size_t in_stride_bytes, int w,
+                                   int h, float *d_out, size_t out_plane_stride_bytes, size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts);
+/* Image calls: each takes the arguments of the call it is named after -- w2xc_process_image_u8_ex[_device], w2xc_process_image_u8_batch[_device] and their
+ * rgb forms -- and `int tta` behind them: 0 = exactly that call, 1 = TTA, anything else W2XC_ERR_ARG.  Argument and model errors are those of that call (on the
+ * Y route a model that does not take one plane to one plane is W2XC_ERR_PLANES already here), before a device is touched; without a device W2XC_ERR_HIP.  The
+ * device forms are asynchronous.  A batch's images are byte-identical to the single-image TTA call.  There is no TTA form of the RGBA call. */
+int w2xc_process_image_u8_tta_device(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *d_in, size_t in_stride_bytes, int w, int h,
+                                     unsigned char *d_out, size_t out_stride_bytes, int iterations, double shrink_ratio, void *hip_stream,
+                                     const w2xc_opts *opts, int tta);
+int w2xc_process_image_u8_tta(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes, int w, int h,
+                              unsigned char *out, size_t out_stride_bytes, int iterations, double shrink_ratio, const w2xc_opts *opts, int tta);
+int w2xc_process_image_u8_batch_tta_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in, size_t in_image_stride_bytes,
+                                           size_t in_stride_bytes, int w, int h, unsigned char *d_out, size_t out_image_stride_bytes,
+                                           size_t out_stride_bytes, int iterations, double shrink_ratio, void *hip_stream, const w2xc_opts *opts, int tta);
+int w2xc_process_image_u8_batch_tta(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes, int w,
+                                    int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio, const w2xc_opts *opts,
+                                    int tta);
+int w2xc_process_image_rgb_u8_tta_device(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *d_in, size_t in_stride_bytes, int w, int h,
+                                         unsigned char *d_out, size_t out_stride_bytes, int iterations, double shrink_ratio, void *hip_stream,
+                                         const w2xc_opts *opts, int tta);
+int w2xc_process_image_rgb_u8_tta(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes, int w, int h,
+                                  unsigned char *out, size_t out_stride_bytes, int iterations, double shrink_ratio, const w2xc_opts *opts, int tta);
+int w2xc_process_image_rgb_u8_batch_tta_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in,
+                                               size_t in_image_stride_bytes, size_t in_stride_bytes, int w, int h, unsigned char *d_out,
+                                               size_t out_image_stride_bytes, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                               void *hip_stream, const w2xc_opts *opts, int tta);
+int w2xc_process_image_rgb_u8_batch_tta(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes,
+                                        int w, int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                        const w2xc_opts *opts, int tta);
+/* TTA's building blocks, without a model, on the current device, asynchronous on hip_stream.  Variant planes have contiguous rows (w floats upright, h floats
+ * transposed) and lie variant_plane_stride_bytes >= 4 w h apart: T_k of plane i at d_up + (k n + i) strides for k = 0..3, at d_tr + ((k - 4) n + i) strides for
+ * k = 4..7 -- two groups of 4 n planes that must not overlap each other or the n planes on the other side.
+ * spread: n source planes of w x h (rows src_stride_bytes apart, planes src_plane_stride_bytes apart) -> their 8 n variants.
+ * gather: 8 n result planes in that layout, the upright ones w x h -> n planes of w x h: the sum above.  Bytes of a row behind 4 w are not written. */
+int w2xc_tta_spread_device(const float *d_src, int n, size_t src_plane_stride_bytes, size_t src_stride_bytes, int w, int h, float *d_up, float *d_tr,
+                           size_t variant_plane_stride_bytes, void *hip_stream);
+int w2xc_tta_gather_device(const float *d_up, const float *d_tr, size_t variant_plane_stride_bytes, int n, int w, int h, float *d_dst,
+                           size_t dst_plane_stride_bytes, size_t dst_stride_bytes, void *hip_stream);
+
 /* the building blocks on contiguous float planes (device pointers): main.cpp:144 on one plane, :75-76, :171-172 */
 int w2xc_resize2x_cubic_device(const float *d_src, int w, int h, float *d_dst, void *hip_stream);
 int w2xc_u8_to_yuv_device(const unsigned char *d_in, size_t in_stride_bytes, int w, int h, float *d_y, float *d_u,

@@ -11,7 +11,10 @@ Extension: RGB models.  When the loaded model's first layer takes 3 planes the i
 channels in PIL's RGB order as they are (no BGR swap: that mimics what the reference feeds its Y path), all three planes through the CNN.
 Extension: transparency.  An input whose decoded image has an alpha channel with any byte below 255 (PIL modes RGBA, LA, P with transparency, ...) goes through
 w2xc_process_image_rgba_u8_ex on the route of the models -- the colour bled under the transparent pixels, alpha through the scale model -- and is written as
-RGBA.  Every other input goes exactly as before, the batch grouping included."""
+RGBA.  Every other input goes exactly as before, the batch grouping included.
+Extension: -t/--tta 1 = test-time augmentation, the --tta of later upstream versions: every model pass on the 8 flips / transposes of the image, averaged
+(w2xc_process_image_[rgb_]u8[_batch]_tta; 8x the CNN work), on both routes and for grouped inputs.  The RGBA call has no TTA form: with an input that would
+take it, --tta 1 exits with a message before anything is converted."""
 import argparse
 import math
 import os
@@ -78,6 +81,13 @@ def wants_alpha(arr):
     return arr.ndim == 3 and arr.shape[2] == 4 and bool((arr[:, :, 3] < 255).any())
 
 
+def check_tta(tta, alpha_files):
+    """--tta 1 with inputs that take the RGBA call (`alpha_files`: their names): a SystemExit with a message; everything else passes"""
+    if tta and alpha_files:
+        raise SystemExit("--tta 1 is not available for images with transparency (%s): the RGBA call has no TTA form; convert them with --tta 0 or "
+                         "flatten the alpha channel first" % ", ".join(alpha_files))
+
+
 def check_inputs(ap, args):
     """-o names ONE output file: with several inputs it is refused (argparse's error exit, status 2)"""
     if len(args.input_file) > 1 and args.output_file != "(auto)":
@@ -98,6 +108,8 @@ def build_parser():
     # not a reference flag: w2xc_opts.precision of the engine (fp32 = the reference's arithmetic on the fp32 MFMA)
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16x3", "fp16x2", "bf16x2", "bf16"],
                     help="engine arithmetic for the CNN layers (extension; default fp32)")
+    # not a reference flag in v1: later upstream versions have it as --tta
+    ap.add_argument("-t", "--tta", type=int, default=0, choices=[0, 1], help="test-time augmentation: 8 flips / transposes per model pass, averaged (extension; 8x the time)")
     return ap
 
 
@@ -132,6 +144,8 @@ def main(argv=None):
         return np.ascontiguousarray(im if rgb else im[:, :, ::-1])   # Y route: cv::imread(IMREAD_COLOR)'s BGR order (Q3); RGB models take RGB as it is
     images = [load(f) for f in args.input_file]
     opaque = [(f, im) for f, im in zip(args.input_file, images) if im.shape[2] == 3]
+    check_tta(args.tta, [f for f, im in zip(args.input_file, images) if im.shape[2] == 4])
+    tta = dict(tta=True) if args.tta else {}
     outs = {}
     if noise is None and iterations == 0 and not shrink:
         outs = dict(zip(args.input_file, images))                      # ratio 1.0 in scale mode: nothing to do
@@ -144,12 +158,12 @@ def main(argv=None):
             if im.shape[2] == 4:                   # (the RGBA call has no batch form)
                 outs[f] = w2xc.process_image_rgba_u8(im, noise, scale if iterations else None, iterations, opts, shrink)
         if len(opaque) == 1:
-            outs[opaque[0][0]] = process(opaque[0][1], noise, scale if iterations else None, iterations, opts, shrink)
+            outs[opaque[0][0]] = process(opaque[0][1], noise, scale if iterations else None, iterations, opts, shrink, **tta)
         elif opaque:
             by_file = dict(opaque)
             sized = [(f, (im.shape[1], im.shape[0])) for f, im in opaque]
             for _, files, _ in group_inputs(sized, args.mode, args.noise_level, args.scale_ratio):   # one batch call per image size
-                res = process_batch([by_file[f] for f in files], noise, scale if iterations else None, iterations, opts, shrink)
+                res = process_batch([by_file[f] for f in files], noise, scale if iterations else None, iterations, opts, shrink, **tta)
                 outs.update(zip(files, res))
     for f in args.input_file:
         name = args.output_file

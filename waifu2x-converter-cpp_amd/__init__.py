@@ -99,6 +99,18 @@ def _load():
         "w2xc_process_image_rgb_u8_batch": (ci, [vp, vp, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, ci, C.c_double, C.POINTER(Opts)]),
         "w2xc_process_image_rgba_u8_ex_device": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.c_double, ci, vp, C.POINTER(Opts)]),
         "w2xc_process_image_rgba_u8_ex": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.c_double, ci, C.POINTER(Opts)]),
+        "w2xc_process_image_u8_tta_device": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.c_double, vp, C.POINTER(Opts), ci]),
+        "w2xc_process_image_u8_tta": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.c_double, C.POINTER(Opts), ci]),
+        "w2xc_process_image_u8_batch_tta_device": (ci, [vp, vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, ci, C.c_double, vp, C.POINTER(Opts), ci]),
+        "w2xc_process_image_u8_batch_tta": (ci, [vp, vp, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, ci, C.c_double, C.POINTER(Opts), ci]),
+        "w2xc_process_image_rgb_u8_tta_device": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.c_double, vp, C.POINTER(Opts), ci]),
+        "w2xc_process_image_rgb_u8_tta": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.c_double, C.POINTER(Opts), ci]),
+        "w2xc_process_image_rgb_u8_batch_tta_device": (ci, [vp, vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, ci, C.c_double, vp, C.POINTER(Opts), ci]),
+        "w2xc_process_image_rgb_u8_batch_tta": (ci, [vp, vp, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, ci, C.c_double, C.POINTER(Opts), ci]),
+        "w2xc_convert_batch_tta_device": (ci, [vp, ci, ci, fp, cs, cs, ci, ci, fp, cs, cs, vp, C.POINTER(Opts)]),
+        "w2xc_convert_planes_tta_device": (ci, [vp, ci, ci, fp, cs, cs, ci, ci, fp, cs, cs, vp, C.POINTER(Opts)]),
+        "w2xc_tta_spread_device": (ci, [fp, ci, cs, cs, ci, ci, fp, fp, cs, vp]),
+        "w2xc_tta_gather_device": (ci, [fp, fp, cs, ci, ci, ci, fp, cs, cs, vp]),
         "w2xc_bleed_rgba_u8_device": (ci, [fp, cs, ci, ci, ci, fp, cs, vp]),
         "w2xc_bleed_rgba_u8_trim": (ci, []),
         "w2xc_convert_planes_nn2x_device": (ci, [vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, vp, C.POINTER(Opts)]),
@@ -376,6 +388,26 @@ class _ModelSet:
         if rc != OK:
             raise W2xcError(rc, last_error())
 
+    def convert_batch_tta_device(self, n, d_in, in_plane_stride_bytes, in_stride_bytes, w, h, d_out, out_plane_stride_bytes,
+                                 out_stride_bytes, nn2x=False, stream=0, opts=None):
+        """One test-time-augmentation pass on each of n planes (w2xc_convert_batch_tta_device; arguments as convert_batch_device): the model on
+        the 8 flips / transposes of a plane, each result transformed back, their fp32 mean (the order of the sum: include/w2xc_hip.h)."""
+        rc = _lib.w2xc_convert_batch_tta_device(self.handle, n, 1 if nn2x else 0, C.c_void_p(d_in), in_plane_stride_bytes, in_stride_bytes, w, h,
+                                                C.c_void_p(d_out), out_plane_stride_bytes, out_stride_bytes, C.c_void_p(stream),
+                                                C.byref(opts) if opts is not None else None)
+        if rc != OK:
+            raise W2xcError(rc, last_error())
+
+    def convert_planes_tta_device(self, n_in, d_in, in_plane_stride_bytes, in_stride_bytes, w, h, d_out, out_plane_stride_bytes,
+                                  out_stride_bytes, nn2x=False, stream=0, opts=None):
+        """One test-time-augmentation pass of a multi-plane model (w2xc_convert_planes_tta_device; arguments as convert_planes_device, or -- nn2x
+        -- as convert_planes_nn2x_device)."""
+        rc = _lib.w2xc_convert_planes_tta_device(self.handle, n_in, 1 if nn2x else 0, C.c_void_p(d_in), in_plane_stride_bytes, in_stride_bytes, w, h,
+                                                 C.c_void_p(d_out), out_plane_stride_bytes, out_stride_bytes, C.c_void_p(stream),
+                                                 C.byref(opts) if opts is not None else None)
+        if rc != OK:
+            raise W2xcError(rc, last_error())
+
     def convert_rows_device(self, d_view, view_stride_bytes, view_h, view_y0, w, plane_h, row_begin, row_end,
                             d_out, out_stride_bytes, stream=0, opts=None):
         """Row-band form (one shard of a plane): see w2xc_convert_rows_device in include/w2xc_hip.h."""
@@ -601,9 +633,16 @@ def _final_size(w, h, iterations, shrink_ratio):
     return fw, fh
 
 
-def _image_host(entry, who, img, channels, noise, scale, iterations, opts, shrink_ratio, extra=(), lenient=False):
+def _tta_entry(name, tta):
+    """the entry point of an image call and its arguments behind opts: `name` itself without test-time augmentation, its *_tta form (int tta last) with"""
+    if not tta:
+        return getattr(_lib, name), ()
+    return getattr(_lib, name.replace("_ex", "").replace("_device", "") + "_tta" + ("_device" if name.endswith("_device") else "")), (int(tta),)
+
+
+def _image_host(entry, who, img, channels, noise, scale, iterations, opts, shrink_ratio, extra=(), lenient=False, tail=()):
     """the single-image host calls: an h x w x channels uint8 image in, the H x W x channels result out; `extra` = the entry's arguments between
-    shrink_ratio and opts.  lenient (process_image_u8): whatever numpy casts to a contiguous uint8 array, unchecked"""
+    shrink_ratio and opts, `tail` those behind opts.  lenient (process_image_u8): whatever numpy casts to a contiguous uint8 array, unchecked"""
     if lenient:
         img = np.ascontiguousarray(img, dtype=np.uint8)
     else:
@@ -618,25 +657,36 @@ def _image_host(entry, who, img, channels, noise, scale, iterations, opts, shrin
     fw, fh = _final_size(w, h, iterations, shrink_ratio)
     out = np.empty((max(fh, 0), max(fw, 0), channels), np.uint8)
     _check(entry(*_handles(noise, scale), img.ctypes.data, img.strides[0], w, h, out.ctypes.data, out.strides[0], iterations, float(shrink_ratio),
-                 *extra, C.byref(opts) if opts is not None else None))
+                 *extra, C.byref(opts) if opts is not None else None, *tail))
     return out
 
 
-def process_image_u8(img, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0):
+def process_image_u8(img, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, tta=False):
     """The CLI's processing modes on an h x w x 3 uint8 image (main.cpp -m noise | scale | noise_scale):
     `noise` / `scale` are _ModelSet objects (either may be None); shrink_ratio = the final INTER_LINEAR shrink
-    of main.cpp:158-167 (0 = none)."""
-    return _image_host(_lib.w2xc_process_image_u8_ex, "process_image_u8", img, 3, noise, scale, iterations, opts, shrink_ratio, lenient=True)
+    of main.cpp:158-167 (0 = none).  tta: test-time augmentation -- every model pass on the 8 flips / transposes of Y, averaged
+    (w2xc_process_image_u8_tta; 8x the CNN work)."""
+    entry, tail = _tta_entry("w2xc_process_image_u8_ex", tta)
+    return _image_host(entry, "process_image_u8", img, 3, noise, scale, iterations, opts, shrink_ratio, lenient=True, tail=tail)
 
 
-def process_image_u8_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, out=None):
+def process_image_u8_device(d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, noise=None, scale=None, iterations=0, shrink_ratio=0.0,
+                            stream=0, opts=None, tta=False):
+    """Device-pointer form (w2xc_process_image_u8_ex_device / _tta_device): w x h x 3 uint8 at d_in, the result at d_out.  Asynchronous on `stream`."""
+    entry, tail = _tta_entry("w2xc_process_image_u8_ex_device", tta)
+    _check(entry(*_handles(noise, scale), C.c_void_p(d_in), in_stride_bytes, w, h, C.c_void_p(d_out), out_stride_bytes, iterations, float(shrink_ratio),
+                 C.c_void_p(stream), C.byref(opts) if opts is not None else None, *tail))
+
+
+def process_image_u8_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, out=None, tta=False):
     """n uint8 images of one size in one call (w2xc_process_image_u8_batch): `imgs` is an (n, h, w, 3) uint8 array or a sequence of equal-shape
     (h, w, 3) uint8 arrays (ROI views with padded rows are passed as they are, page-locked arrays are DMA'd in place); returns an (n, H, W, 3)
     uint8 array (or fills `out`, such an array).  Image i is byte-identical to process_image_u8(imgs[i], ...) with the same arguments."""
-    return _image_batch(_lib.w2xc_process_image_u8_batch, "process_image_u8_batch", imgs, noise, scale, iterations, opts, shrink_ratio, out)
+    entry, tail = _tta_entry("w2xc_process_image_u8_batch", tta)
+    return _image_batch(entry, "process_image_u8_batch", imgs, noise, scale, iterations, opts, shrink_ratio, out, tail)
 
 
-def _image_batch(entry, who, imgs, noise, scale, iterations, opts, shrink_ratio, out):
+def _image_batch(entry, who, imgs, noise, scale, iterations, opts, shrink_ratio, out, tail=()):
     """the host image batch of Y models (process_image_u8_batch) and of RGB models (process_image_rgb_u8_batch): same arguments, same checks"""
     if isinstance(imgs, np.ndarray):
         if imgs.ndim != 4:
@@ -664,49 +714,50 @@ def _image_batch(entry, who, imgs, noise, scale, iterations, opts, shrink_ratio,
     ip = (C.c_void_p * n)(*[a.ctypes.data for a in srcs])
     op = (C.c_void_p * n)(*[out[i].ctypes.data for i in range(n)])
     _check(entry(*_handles(noise, scale), n, ip, srcs[0].strides[0], w, h,
-                 op, out.strides[1], iterations, float(shrink_ratio), C.byref(opts) if opts is not None else None))
+                 op, out.strides[1], iterations, float(shrink_ratio), C.byref(opts) if opts is not None else None, *tail))
     return out
 
 
 def process_image_u8_batch_device(n, d_in, in_image_stride_bytes, in_stride_bytes, w, h, d_out, out_image_stride_bytes, out_stride_bytes,
-                                  noise=None, scale=None, iterations=0, shrink_ratio=0.0, stream=0, opts=None):
+                                  noise=None, scale=None, iterations=0, shrink_ratio=0.0, stream=0, opts=None, tta=False):
     """Device-pointer image batch (w2xc_process_image_u8_batch_device): n images of w x h x 3 uint8 at d_in + i * in_image_stride_bytes, the
     outputs at d_out + i * out_image_stride_bytes.  Asynchronous on `stream`."""
-    _check(_lib.w2xc_process_image_u8_batch_device(*_handles(noise, scale), n, C.c_void_p(d_in),
-                                                   in_image_stride_bytes, in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes,
-                                                   out_stride_bytes, iterations, float(shrink_ratio), C.c_void_p(stream),
-                                                   C.byref(opts) if opts is not None else None))
+    entry, tail = _tta_entry("w2xc_process_image_u8_batch_device", tta)
+    _check(entry(*_handles(noise, scale), n, C.c_void_p(d_in), in_image_stride_bytes, in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes,
+                 out_stride_bytes, iterations, float(shrink_ratio), C.c_void_p(stream), C.byref(opts) if opts is not None else None, *tail))
 
 
 # ---- RGB models (3 planes in, 3 out): the image calls above for the form most published waifu2x weights have ----
-def process_image_rgb_u8(img, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0):
+def process_image_rgb_u8(img, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, tta=False):
     """An h x w x 3 uint8 image through RGB models (w2xc_process_image_rgb_u8_ex): x = u8 / 255 on the channels as given, an optional noise
     pass, `iterations` 2x passes (nearest 2x + CNN on all three planes), the optional INTER_LINEAR shrink, saturate(rint(255 x)).
-    `noise` / `scale` are _ModelSet objects whose first layer takes 3 planes and whose last gives 3 (either may be None)."""
-    return _image_host(_lib.w2xc_process_image_rgb_u8_ex, "process_image_rgb_u8", img, 3, noise, scale, iterations, opts, shrink_ratio)
+    `noise` / `scale` are _ModelSet objects whose first layer takes 3 planes and whose last gives 3 (either may be None).  tta: test-time
+    augmentation -- every pass on the 8 flips / transposes of the three planes, averaged before the rounding (w2xc_process_image_rgb_u8_tta)."""
+    entry, tail = _tta_entry("w2xc_process_image_rgb_u8_ex", tta)
+    return _image_host(entry, "process_image_rgb_u8", img, 3, noise, scale, iterations, opts, shrink_ratio, tail=tail)
 
 
 def process_image_rgb_u8_device(d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, noise=None, scale=None, iterations=0, shrink_ratio=0.0,
-                                stream=0, opts=None):
+                                stream=0, opts=None, tta=False):
     """Device-pointer form (w2xc_process_image_rgb_u8_ex_device): w x h x 3 uint8 at d_in, the result at d_out.  Asynchronous on `stream`."""
-    _check(_lib.w2xc_process_image_rgb_u8_ex_device(*_handles(noise, scale), C.c_void_p(d_in),
-                                                    in_stride_bytes, w, h, C.c_void_p(d_out), out_stride_bytes, iterations, float(shrink_ratio),
-                                                    C.c_void_p(stream), C.byref(opts) if opts is not None else None))
+    entry, tail = _tta_entry("w2xc_process_image_rgb_u8_ex_device", tta)
+    _check(entry(*_handles(noise, scale), C.c_void_p(d_in), in_stride_bytes, w, h, C.c_void_p(d_out), out_stride_bytes, iterations, float(shrink_ratio),
+                 C.c_void_p(stream), C.byref(opts) if opts is not None else None, *tail))
 
 
-def process_image_rgb_u8_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, out=None):
+def process_image_rgb_u8_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, out=None, tta=False):
     """n uint8 images of one size through RGB models in one call (w2xc_process_image_rgb_u8_batch); arguments and checks as
     process_image_u8_batch.  Image i is byte-identical to process_image_rgb_u8(imgs[i], ...) with the same arguments."""
-    return _image_batch(_lib.w2xc_process_image_rgb_u8_batch, "process_image_rgb_u8_batch", imgs, noise, scale, iterations, opts, shrink_ratio, out)
+    entry, tail = _tta_entry("w2xc_process_image_rgb_u8_batch", tta)
+    return _image_batch(entry, "process_image_rgb_u8_batch", imgs, noise, scale, iterations, opts, shrink_ratio, out, tail)
 
 
 def process_image_rgb_u8_batch_device(n, d_in, in_image_stride_bytes, in_stride_bytes, w, h, d_out, out_image_stride_bytes, out_stride_bytes,
-                                      noise=None, scale=None, iterations=0, shrink_ratio=0.0, stream=0, opts=None):
+                                      noise=None, scale=None, iterations=0, shrink_ratio=0.0, stream=0, opts=None, tta=False):
     """Device-pointer image batch for RGB models (w2xc_process_image_rgb_u8_batch_device); arguments as process_image_u8_batch_device."""
-    _check(_lib.w2xc_process_image_rgb_u8_batch_device(*_handles(noise, scale), n, C.c_void_p(d_in),
-                                                       in_image_stride_bytes, in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes,
-                                                       out_stride_bytes, iterations, float(shrink_ratio), C.c_void_p(stream),
-                                                       C.byref(opts) if opts is not None else None))
+    entry, tail = _tta_entry("w2xc_process_image_rgb_u8_batch_device", tta)
+    _check(entry(*_handles(noise, scale), n, C.c_void_p(d_in), in_image_stride_bytes, in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes,
+                 out_stride_bytes, iterations, float(shrink_ratio), C.c_void_p(stream), C.byref(opts) if opts is not None else None, *tail))
 
 
 def u8_to_rgb_device(d_in, in_stride_bytes, w, h, d_planes, stream=0):
@@ -721,6 +772,21 @@ def rgb_to_u8_device(d_planes, w, h, d_out, out_stride_bytes, stream=0):
     ps = w * h * 4
     _check(_lib.w2xc_rgb_to_u8_device(C.c_void_p(d_planes), C.c_void_p(d_planes + ps), C.c_void_p(d_planes + 2 * ps), w, h, C.c_void_p(d_out),
                                       out_stride_bytes, C.c_void_p(stream)))
+
+
+# ---- test-time augmentation's building blocks (the image and plane calls take tta=True / are _ModelSet.convert_*_tta_device) ----
+def tta_spread_device(d_src, n, src_plane_stride_bytes, src_stride_bytes, w, h, d_up, d_tr, variant_plane_stride_bytes, stream=0):
+    """n float planes of w x h at d_src -> their 8 n flips / transposes (w2xc_tta_spread_device): T_k of plane i at d_up + (k n + i) variant strides
+    for k = 0..3 (h x w), at d_tr + ((k - 4) n + i) strides for k = 4..7 (w x h); T_k = hflip if k & 1, then vflip if k & 2, then transpose if k & 4."""
+    _check(_lib.w2xc_tta_spread_device(C.c_void_p(d_src), n, src_plane_stride_bytes, src_stride_bytes, w, h, C.c_void_p(d_up), C.c_void_p(d_tr),
+                                       variant_plane_stride_bytes, C.c_void_p(stream)))
+
+
+def tta_gather_device(d_up, d_tr, variant_plane_stride_bytes, n, w, h, d_dst, dst_plane_stride_bytes, dst_stride_bytes, stream=0):
+    """8 n result planes in tta_spread_device's layout (the upright ones w x h) -> n planes of w x h at d_dst: each variant transformed back, their
+    fp32 sum in the order k = 0..7, times 0.125 (w2xc_tta_gather_device)."""
+    _check(_lib.w2xc_tta_gather_device(C.c_void_p(d_up), C.c_void_p(d_tr), variant_plane_stride_bytes, n, w, h, C.c_void_p(d_dst),
+                                       dst_plane_stride_bytes, dst_stride_bytes, C.c_void_p(stream)))
 
 
 # ---- RGBA images: alpha through the scale model, the colour bled under the transparent pixels ----

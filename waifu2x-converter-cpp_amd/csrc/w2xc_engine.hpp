@@ -22,6 +22,8 @@
 //   w2xc_filter.cpp         Model::filter at the host / device boundary (src/modelHandler.cpp:26-72)
 //   w2xc_image.cpp          N2: the CLI's image pipeline around the plane conversion (main.cpp:74-172): one pipeline for Y models and one for RGB models, each
 //                           for S images of one size; the single-image, batch and RGBA entry points around them
+//                           and test-time augmentation: tta_pass (spread -> the CNN on the 8 variants -> gather; kernels in w2xc_tta.hip), which both pipelines
+//                           and the TTA plane calls share
 #pragma once
 #include "../../include/w2xc_hip.h"
 
@@ -310,6 +312,9 @@ int run_rows(w2xc_model *m, DevCtx *c, const float *d_in, size_t in_stride_f, in
              float *d_out, size_t out_stride_f, hipStream_t st, const w2xc_opts &o_in, int up = 0, int n_in = 1,
              long long in_cs = 0, long long out_cs = 0, const BandHooks *hk = nullptr, int plane_h = 0, int u8 = 0);
 int check_plane_args(const w2xc_model *m, const void *in, size_t in_stride, int w, int h, const void *out, size_t out_stride);
+// what w2xc_convert_planes[_nn2x]_device refuses (no device is touched); o = the resolved options
+int check_planes_args(const w2xc_model *m, int up, int n_in_planes, const void *d_in, size_t in_plane_stride, size_t in_stride, int w, int h, const void *d_out,
+                      size_t out_plane_stride, size_t out_stride, const w2xc_opts &o);
 
 // ---- batches of same-size planes (w2xc_convert_batch*) ----
 // the batched launch chain runs a call planned as P (one image of the batch): fp32, W2XC_KERNEL_AUTO, conv3x3_first2_wino4 -> conv3x3_wino4 (planar) ... ->
@@ -325,6 +330,8 @@ int run_batch(w2xc_model *m, DevCtx *c, int nimg, int up, const float *d_in, lon
 void batch_ws_floats(const RowPlan &P, size_t img_floats[2]);
 int check_batch_model(const w2xc_model *m);
 int check_batch_args(const w2xc_model *m, int nimg, int nn2x, int w, int h, size_t in_stride, size_t out_stride);
+int check_batch_device_args(const w2xc_model *m, int n, int nn2x, const void *d_in, size_t in_plane_stride, size_t in_stride, int w, int h, const void *d_out,
+                            size_t out_plane_stride, size_t out_stride);
 // byte ranges [lo, hi) tagged 1 = output, 0 = input (sorted in place): W2XC_ERR_ARG when an output overlaps another output or an input
 int check_batch_overlap(std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> &iv);
 

@@ -85,10 +85,19 @@ inline void final_size(int w, int h, int iterations, double shrink, int *fw, int
 // float planes of ONE image over all levels of the Y image pipeline, every plane on a 256-byte boundary: per level Y, U and V, on level 0 a second Y for
 // the noise pass; with alpha (one image: the RGBA call) every Y has an alpha plane behind it
 inline size_t plane_floats(int w, int h) { return ((size_t)w * h + 63) & ~(size_t)63; }
-inline size_t image_aux_floats(int w, int h, int iterations, double shrink, bool alpha = false)
+// test-time augmentation: the variant planes of one pass on one plane -- 8 at the pass's input level, 8 at its output level -- and the most a pass of an image
+// call needs of them per plane that goes through the CNN (every pass reuses them: the last scale iteration is the largest; without one, the noise pass)
+inline size_t tta_pass_floats(int w, int h, int up) { return 8 * (plane_floats(w, h) + plane_floats(w << up, h << up)); }
+inline size_t tta_variant_floats(int w, int h, int iterations)
+{
+    return iterations > 0 ? tta_pass_floats(w << (iterations - 1), h << (iterations - 1), 1) : tta_pass_floats(w, h, 0);
+}
+// (tta: the Y planes go through the CNN -- one per image; never with alpha)
+inline size_t image_aux_floats(int w, int h, int iterations, double shrink, bool alpha = false, bool tta = false)
 {
     const size_t ya = alpha ? 2 : 1;
     size_t need = (2 * ya + 2) * plane_floats(w, h);
+    if (tta) need += tta_variant_floats(w, h, iterations);
     for (int i = 1; i <= iterations; i++) need += (ya + 2) * plane_floats(w << i, h << i);
     int fw, fh;
     final_size(w, h, iterations, shrink, &fw, &fh);

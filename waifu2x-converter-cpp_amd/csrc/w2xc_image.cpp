@@ -72,9 +72,55 @@ struct ImageCall {
     w2xc_opts o;
     // who runs a CNN pass of the Y pipeline: run_rows (the single-image calls: bands for large images) or run_batch (everything else)
     bool rows = false;
-    ImageCall(w2xc_model *noise, w2xc_model *scale, int w_, int h_, int iterations_, double shrink_, void *hip_stream, const w2xc_opts *opts)
-        : mn(noise), msc(scale), w(w_), h(h_), iterations(iterations_), shrink(shrink_), st((hipStream_t)hip_stream), o(resolve_opts(opts)) {}
+    // test-time augmentation (the *_tta entry points): every CNN pass of the route is its TTA pass (tta_pass).  tta_arg = the caller's int as given:
+    // check_process_args refuses anything but 0 and 1
+    int tta_arg;
+    bool tta;
+    ImageCall(w2xc_model *noise, w2xc_model *scale, int w_, int h_, int iterations_, double shrink_, void *hip_stream, const w2xc_opts *opts, int tta_ = 0)
+        : mn(noise), msc(scale), w(w_), h(h_), iterations(iterations_), shrink(shrink_), st((hipStream_t)hip_stream), o(resolve_opts(opts)), tta_arg(tta_),
+          tta(tta_ == 1) {}
 };
+
+// ---- test-time augmentation: one TTA pass of a model (the arithmetic: include/w2xc_hip.h) ----
+// spread -> the CNN on the 8 variants -> gather, for `runs` CNN runs per variant of nin planes in and nout planes out each.  The runs * nin source planes lie
+// sps floats apart (rows srs), the runs * nout result planes dps apart (rows drs); `var` holds tta_pass_floats(w, h, up) floats per source plane and per
+// result plane's share (8 (ni ps + no PS) in all): the input variants -- the upright group, the transposed group directly behind it -- then the output
+// variants likewise.  rows = false (nin = nout = 1): the one-plane chain, run_batch on all variants of one size -- ONE batch of 8 where w == h, where the
+// transposed group continues the upright one.  rows = true: the multi-plane form, the single-image run_rows sequence per variant and run.
+// Nearest-2x commutes with every T_k: a scale pass (up = 1) spreads at source resolution and gathers at 2x.
+struct TtaPass {
+    w2xc_model *m;
+    DevCtx *cm;
+    int up, nin, nout;
+    bool rows;
+};
+int tta_pass(const TtaPass &t, int runs, const float *src, long long sps, size_t srs, int w, int h, float *dst, long long dps, size_t drs, float *var,
+             hipStream_t st, const w2xc_opts &o)
+{
+    const int W = w << t.up, H = h << t.up, ni = runs * t.nin, no = runs * t.nout;
+    const long long ps = (long long)plane_floats(w, h), PS = (long long)plane_floats(W, H);
+    float *in_up = var, *in_tr = in_up + 4 * (size_t)ni * ps, *out_up = in_tr + 4 * (size_t)ni * ps, *out_tr = out_up + 4 * (size_t)no * PS;
+    HIP_TRY(w2xc_launch_tta_spread(src, sps, (long long)srs, w, h, in_up, in_tr, ps, ni, st));
+    if (!t.rows) {
+        if (w == h) {
+            if (int rc = run_batch(t.m, t.cm, 8 * ni, t.up, in_up, ps, (size_t)w, w, h, out_up, PS, (size_t)W, st, o)) return rc;
+        } else {
+            if (int rc = run_batch(t.m, t.cm, 4 * ni, t.up, in_up, ps, (size_t)w, w, h, out_up, PS, (size_t)W, st, o)) return rc;
+            if (int rc = run_batch(t.m, t.cm, 4 * ni, t.up, in_tr, ps, (size_t)h, h, w, out_tr, PS, (size_t)H, st, o)) return rc;
+        }
+    } else {
+        for (int k = 0; k < 8; k++) {
+            const int vw = k < 4 ? w : h, vh = k < 4 ? h : w, VW = vw << t.up, VH = vh << t.up;
+            for (int r = 0; r < runs; r++) {
+                const float *in = (k < 4 ? in_up : in_tr) + ((size_t)(k & 3) * ni + (size_t)r * t.nin) * ps;
+                float *out = (k < 4 ? out_up : out_tr) + ((size_t)(k & 3) * no + (size_t)r * t.nout) * PS;
+                if (int rc = run_rows(t.m, t.cm, in, (size_t)vw, VH, 0, VW, 0, VH, out, (size_t)VW, st, o, t.up, t.nin, ps, PS, nullptr, VH)) return rc;
+            }
+        }
+    }
+    HIP_TRY(w2xc_launch_tta_gather(out_up, out_tr, PS, W, H, dst, dps, (long long)drs, no, st));
+    return W2XC_OK;
+}
 
 // uint8 images of one size: image i at p + i * img bytes, its rows `row` bytes apart
 template <class T> struct U8Images {
@@ -102,7 +148,9 @@ int process_y_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, siz
 {
     DevCtx *own = c.ctx.owner();
     const size_t ya = al ? 2 : 1, ny = ya * S;   // planes a Y takes (itself and its alpha), planes of the Y group
-    if (int rc = reserve_aux(own, skip, image_aux_floats(c.w, c.h, c.iterations, c.shrink, al != nullptr) * (size_t)cap)) return rc;
+    if (int rc = reserve_aux(own, skip, image_aux_floats(c.w, c.h, c.iterations, c.shrink, al != nullptr, c.tta) * (size_t)cap)) return rc;
+    // (TTA: the variant planes of a pass lie behind the planes of every level, cap images' worth; every pass reuses them)
+    float *var = aux_planes(own, skip) + image_aux_floats(c.w, c.h, c.iterations, c.shrink, al != nullptr) * (size_t)cap;
     // One CNN pass on Y: the noise pass (up = 0) on the S Y planes alone -- alpha never goes through the noise model; beside an alpha plane the one Y
     // plane is the single call's run_rows -- a scale pass (up = 1) on the whole Y group.  Per plane the bits of the single call either way (run_batch).
     const auto pass = [&](int up, const float *src, long long sps, int w, int h, float *dst, long long dps) {
@@ -110,6 +158,7 @@ int process_y_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, siz
         w2xc_model *m = noise ? c.mn : c.msc;
         DevCtx *cm = noise ? c.ctx.cn : c.ctx.cs;
         const int nw = w << up, nh = h << up;   // (up = 1: INTER_NEAREST 2x folded into layer 1, :136-140, + convertWithModels, :148)
+        if (c.tta) return tta_pass(TtaPass{m, cm, up, 1, 1, false}, noise ? S : (int)ny, src, sps, (size_t)w, w, h, dst, dps, (size_t)nw, var, c.st, c.o);
         return c.rows || (noise && al) ? run_rows(m, cm, src, w, nh, 0, nw, 0, nh, dst, nw, c.st, c.o, up, 1, 0, 0, nullptr, nh)
                                        : run_batch(m, cm, noise ? S : (int)ny, up, src, sps, (size_t)w, w, h, dst, dps, (size_t)nw, c.st, c.o);
     };
@@ -152,19 +201,23 @@ int process_y_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, siz
 struct RgbPlan {
     bool src_u8 = false, dst_u8 = false;
     size_t floats = 0;
+    size_t var = 0;   // TTA: floats of the levels' planes, behind which the variant planes of a pass lie (three planes' worth per image)
 };
 RgbPlan rgb_plan(const ImageCall &c)
 {
     RgbPlan R;
     const int passes = (c.mn ? 1 : 0) + c.iterations;
-    R.src_u8 = u8_source_layer(c.mn ? c.mn : c.msc, c.o);
-    R.dst_u8 = c.shrink == 0.0 && u8_sink_layer(c.iterations > 0 ? c.msc : c.mn, c.o);
+    // (TTA: the mean is taken before the rounding, so the colour kernels run around float planes)
+    R.src_u8 = !c.tta && u8_source_layer(c.mn ? c.mn : c.msc, c.o);
+    R.dst_u8 = !c.tta && c.shrink == 0.0 && u8_sink_layer(c.iterations > 0 ? c.msc : c.mn, c.o);
     if (!R.src_u8) R.floats += 3 * plane_floats(c.w, c.h);
     for (int p = 1; p <= passes; p++) {
         const int lvl = p - (c.mn ? 1 : 0);   // the pass's output level: the noise pass stays on level 0
         if (p < passes || !R.dst_u8) R.floats += 3 * plane_floats(c.w << lvl, c.h << lvl);
     }
     if (c.shrink > 0.0) R.floats += 3 * plane_floats(c.fw, c.fh);
+    R.var = R.floats;
+    if (c.tta) R.floats += 3 * tta_variant_floats(c.w, c.h, c.iterations);
     return R;
 }
 
@@ -181,6 +234,7 @@ int process_rgb_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, s
         if (int rc = reserve_aux(own, skip, R.floats * (size_t)cap)) return rc;
         base = aux_planes(own, skip);
     }
+    float *var = base + R.var * (size_t)cap;
     int cw = c.w, ch = c.h;
     long long ps = (long long)plane_floats(cw, ch);
     float *cur = nullptr;   // the current level's planes; nullptr = the image is still the caller's uint8 source
@@ -199,7 +253,9 @@ int process_rgb_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, s
         const bool from_u8 = cur == nullptr, to_u8 = p == passes && R.dst_u8;
         float *nxt = nullptr;
         if (!to_u8) { nxt = base; base += 3 * (size_t)cap * ps2; }
-        for (int i = 0; i < S; i++) {
+        if (c.tta) {   // (neither from_u8 nor to_u8: rgb_plan)
+            if (int rc = tta_pass(TtaPass{m, cm, up, 3, 3, true}, S, cur, ps, (size_t)cw, cw, ch, nxt, ps2, (size_t)nw, var, c.st, c.o)) return rc;
+        } else for (int i = 0; i < S; i++) {
             const float *src = from_u8 ? reinterpret_cast<const float *>(in.p + (size_t)i * in.img) : cur + (size_t)i * 3 * ps;
             float *dst = to_u8 ? reinterpret_cast<float *>(out.p + (size_t)i * out.img) : nxt + (size_t)i * 3 * ps2;
             int rc = run_rows(m, cm, src, from_u8 ? in.row : (size_t)cw, nh, 0, nw, 0, nh, dst, to_u8 ? out.row : (size_t)nw, c.st, c.o, up, 3,
@@ -255,7 +311,7 @@ int plan_image_call(PlanKind kind, const ImageCall &c, int *sub)
         }
     }
     const size_t budget = (size_t)(c.o.workspace_mb > 0 ? c.o.workspace_mb : 16384) << 20;
-    const size_t floats = rgb ? rgb_plan(c).floats : image_aux_floats(c.w, c.h, c.iterations, c.shrink, false);
+    const size_t floats = rgb ? rgb_plan(c).floats : image_aux_floats(c.w, c.h, c.iterations, c.shrink, false, c.tta);
     const size_t per = floats * 4 + (size_t)c.w * 3 * c.h + (size_t)c.fw * 3 * c.fh;
     *sub = (int)std::min(k, std::max<size_t>(budget / per, 1));
     return W2XC_OK;
@@ -263,6 +319,7 @@ int plan_image_call(PlanKind kind, const ImageCall &c, int *sub)
 
 int check_process_args(const ImageCall &c)
 {
+    if (c.tta_arg != 0 && c.tta_arg != 1) return fail(W2XC_ERR_ARG, "tta must be 0 or 1 (got %d)", c.tta_arg);
     if (!c.mn && !c.msc) return fail(W2XC_ERR_ARG, "need a noise model, a scale model or both");
     if (c.iterations > 0 && !c.msc) return fail(W2XC_ERR_ARG, "scale iterations need a scale model");
     if (!c.mn && c.iterations == 0) return fail(W2XC_ERR_ARG, "nothing to do (no noise model, 0 iterations)");
@@ -474,6 +531,14 @@ BleedScratch &bleed_scratch()
     return *b;
 }
 
+// the variants of a Y plane go through run_batch: one plane in, one out (what the batch forms ask of their models)
+int check_tta_y_models(const ImageCall &c)
+{
+    if (c.mn) if (int rc = check_batch_model(c.mn)) return rc;
+    if (c.msc) if (int rc = check_batch_model(c.msc)) return rc;
+    return W2XC_OK;
+}
+
 // ---- the four forms of the image call, for Y models (rgb = false: w2xc_process_image_u8*) and RGB models (w2xc_process_image_rgb_u8*) ----
 int image_ex_device(bool rgb, ImageCall c, U8In in, U8Out out)
 {
@@ -487,6 +552,7 @@ int image_ex_device(bool rgb, ImageCall c, U8In in, U8Out out)
             return fail(W2XC_ERR_ARG, "the output image overlaps the input image");
         if ((rc = plan_image_call(PLAN_RGB, c, &sub))) return rc;
     }
+    if (!rgb && c.tta && (rc = check_tta_y_models(c))) return rc;
     LockedImageCtx lc;
     if ((rc = lc.open(c.mn, c.msc, c.o.device))) return rc;
     c.ctx = lc;
@@ -501,6 +567,7 @@ int image_ex_host(bool rgb, ImageCall c, U8In in, U8Out out)
     if ((rc = check_image_args(c, in.p, in.row, out.p, out.row))) return rc;
     int sub;
     if (rgb && (rc = plan_image_call(PLAN_RGB, c, &sub))) return rc;
+    if (!rgb && c.tta && (rc = check_tta_y_models(c))) return rc;
     if (w2xc_device_count() <= 0) return fail(W2XC_ERR_HIP, "no HIP device available (libw2xc_hip has no CPU fallback)");
     return image_host_single(rgb, c, in, out, c.o.device);
 }
@@ -576,13 +643,20 @@ using namespace w2xc_eng;
 
 extern "C" {
 
+int w2xc_process_image_u8_tta_device(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *d_in, size_t in_stride_bytes,
+                                    int w, int h, unsigned char *d_out, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                    void *hip_stream, const w2xc_opts *opts, int tta)
+try {
+    return image_ex_device(false, ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, hip_stream, opts, tta), U8In{d_in, 0, in_stride_bytes},
+                           U8Out{d_out, 0, out_stride_bytes});
+} W2XC_CATCH_ALL
+
 int w2xc_process_image_u8_ex_device(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *d_in, size_t in_stride_bytes,
                                     int w, int h, unsigned char *d_out, size_t out_stride_bytes, int iterations, double shrink_ratio,
                                     void *hip_stream, const w2xc_opts *opts)
-try {
-    return image_ex_device(false, ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, hip_stream, opts), U8In{d_in, 0, in_stride_bytes},
-                           U8Out{d_out, 0, out_stride_bytes});
-} W2XC_CATCH_ALL
+{
+    return w2xc_process_image_u8_tta_device(noise_model, scale_model, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, iterations, shrink_ratio, hip_stream, opts, 0);
+}
 
 int w2xc_process_image_u8_device(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *d_in, size_t in_stride_bytes,
                                  int w, int h, unsigned char *d_out, size_t out_stride_bytes, int iterations, void *hip_stream,
@@ -592,12 +666,18 @@ int w2xc_process_image_u8_device(w2xc_model *noise_model, w2xc_model *scale_mode
                                            hip_stream, opts);
 }
 
-int w2xc_process_image_u8_ex(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes, int w, int h,
-                             unsigned char *out, size_t out_stride_bytes, int iterations, double shrink_ratio, const w2xc_opts *opts)
+int w2xc_process_image_u8_tta(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes, int w, int h,
+                             unsigned char *out, size_t out_stride_bytes, int iterations, double shrink_ratio, const w2xc_opts *opts, int tta)
 try {
-    return image_ex_host(false, ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, nullptr, opts), U8In{in, 0, in_stride_bytes},
+    return image_ex_host(false, ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, nullptr, opts, tta), U8In{in, 0, in_stride_bytes},
                          U8Out{out, 0, out_stride_bytes});
 } W2XC_CATCH_ALL
+
+int w2xc_process_image_u8_ex(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes, int w, int h,
+                             unsigned char *out, size_t out_stride_bytes, int iterations, double shrink_ratio, const w2xc_opts *opts)
+{
+    return w2xc_process_image_u8_tta(noise_model, scale_model, in, in_stride_bytes, w, h, out, out_stride_bytes, iterations, shrink_ratio, opts, 0);
+}
 
 int w2xc_process_image_u8(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes, int w, int h,
                           unsigned char *out, size_t out_stride_bytes, int iterations, const w2xc_opts *opts)
@@ -606,53 +686,94 @@ int w2xc_process_image_u8(w2xc_model *noise_model, w2xc_model *scale_model, cons
 }
 
 // ---- batches of same-size images ----------------------------------------------------------------
+int w2xc_process_image_u8_batch_tta_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in, size_t in_image_stride_bytes,
+                                       size_t in_stride_bytes, int w, int h, unsigned char *d_out, size_t out_image_stride_bytes,
+                                       size_t out_stride_bytes, int iterations, double shrink_ratio, void *hip_stream, const w2xc_opts *opts, int tta)
+try {
+    return image_batch_device(false, ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, hip_stream, opts, tta), n,
+                              U8In{d_in, in_image_stride_bytes, in_stride_bytes}, U8Out{d_out, out_image_stride_bytes, out_stride_bytes});
+} W2XC_CATCH_ALL
+
 int w2xc_process_image_u8_batch_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in, size_t in_image_stride_bytes,
                                        size_t in_stride_bytes, int w, int h, unsigned char *d_out, size_t out_image_stride_bytes,
                                        size_t out_stride_bytes, int iterations, double shrink_ratio, void *hip_stream, const w2xc_opts *opts)
+{
+    return w2xc_process_image_u8_batch_tta_device(noise_model, scale_model, n, d_in, in_image_stride_bytes, in_stride_bytes, w, h, d_out, out_image_stride_bytes, out_stride_bytes, iterations, shrink_ratio, hip_stream, opts, 0);
+}
+
+int w2xc_process_image_u8_batch_tta(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes, int w,
+                                int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio, const w2xc_opts *opts, int tta)
 try {
-    return image_batch_device(false, ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, hip_stream, opts), n,
-                              U8In{d_in, in_image_stride_bytes, in_stride_bytes}, U8Out{d_out, out_image_stride_bytes, out_stride_bytes});
+    return image_batch_host(false, ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, nullptr, opts, tta), n, in, in_stride_bytes, out,
+                            out_stride_bytes);
 } W2XC_CATCH_ALL
 
 int w2xc_process_image_u8_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes, int w,
                                 int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio, const w2xc_opts *opts)
-try {
-    return image_batch_host(false, ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, nullptr, opts), n, in, in_stride_bytes, out,
-                            out_stride_bytes);
-} W2XC_CATCH_ALL
+{
+    return w2xc_process_image_u8_batch_tta(noise_model, scale_model, n, in, in_stride_bytes, w, h, out, out_stride_bytes, iterations, shrink_ratio, opts, 0);
+}
 
 // ---- RGB models: the same four forms ---------------------------------------------------------------
+int w2xc_process_image_rgb_u8_tta_device(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *d_in, size_t in_stride_bytes,
+                                        int w, int h, unsigned char *d_out, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                        void *hip_stream, const w2xc_opts *opts, int tta)
+try {
+    return image_ex_device(true, ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, hip_stream, opts, tta), U8In{d_in, 0, in_stride_bytes},
+                           U8Out{d_out, 0, out_stride_bytes});
+} W2XC_CATCH_ALL
+
 int w2xc_process_image_rgb_u8_ex_device(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *d_in, size_t in_stride_bytes,
                                         int w, int h, unsigned char *d_out, size_t out_stride_bytes, int iterations, double shrink_ratio,
                                         void *hip_stream, const w2xc_opts *opts)
+{
+    return w2xc_process_image_rgb_u8_tta_device(noise_model, scale_model, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, iterations, shrink_ratio, hip_stream, opts, 0);
+}
+
+int w2xc_process_image_rgb_u8_tta(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes, int w, int h,
+                                 unsigned char *out, size_t out_stride_bytes, int iterations, double shrink_ratio, const w2xc_opts *opts, int tta)
 try {
-    return image_ex_device(true, ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, hip_stream, opts), U8In{d_in, 0, in_stride_bytes},
-                           U8Out{d_out, 0, out_stride_bytes});
+    return image_ex_host(true, ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, nullptr, opts, tta), U8In{in, 0, in_stride_bytes},
+                         U8Out{out, 0, out_stride_bytes});
 } W2XC_CATCH_ALL
 
 int w2xc_process_image_rgb_u8_ex(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes, int w, int h,
                                  unsigned char *out, size_t out_stride_bytes, int iterations, double shrink_ratio, const w2xc_opts *opts)
+{
+    return w2xc_process_image_rgb_u8_tta(noise_model, scale_model, in, in_stride_bytes, w, h, out, out_stride_bytes, iterations, shrink_ratio, opts, 0);
+}
+
+int w2xc_process_image_rgb_u8_batch_tta_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in,
+                                           size_t in_image_stride_bytes, size_t in_stride_bytes, int w, int h, unsigned char *d_out,
+                                           size_t out_image_stride_bytes, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                           void *hip_stream, const w2xc_opts *opts, int tta)
 try {
-    return image_ex_host(true, ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, nullptr, opts), U8In{in, 0, in_stride_bytes},
-                         U8Out{out, 0, out_stride_bytes});
+    return image_batch_device(true, ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, hip_stream, opts, tta), n,
+                              U8In{d_in, in_image_stride_bytes, in_stride_bytes}, U8Out{d_out, out_image_stride_bytes, out_stride_bytes});
 } W2XC_CATCH_ALL
 
 int w2xc_process_image_rgb_u8_batch_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in,
                                            size_t in_image_stride_bytes, size_t in_stride_bytes, int w, int h, unsigned char *d_out,
                                            size_t out_image_stride_bytes, size_t out_stride_bytes, int iterations, double shrink_ratio,
                                            void *hip_stream, const w2xc_opts *opts)
+{
+    return w2xc_process_image_rgb_u8_batch_tta_device(noise_model, scale_model, n, d_in, in_image_stride_bytes, in_stride_bytes, w, h, d_out, out_image_stride_bytes, out_stride_bytes, iterations, shrink_ratio, hip_stream, opts, 0);
+}
+
+int w2xc_process_image_rgb_u8_batch_tta(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes,
+                                    int w, int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                    const w2xc_opts *opts, int tta)
 try {
-    return image_batch_device(true, ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, hip_stream, opts), n,
-                              U8In{d_in, in_image_stride_bytes, in_stride_bytes}, U8Out{d_out, out_image_stride_bytes, out_stride_bytes});
+    return image_batch_host(true, ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, nullptr, opts, tta), n, in, in_stride_bytes, out,
+                            out_stride_bytes);
 } W2XC_CATCH_ALL
 
 int w2xc_process_image_rgb_u8_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes,
                                     int w, int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio,
                                     const w2xc_opts *opts)
-try {
-    return image_batch_host(true, ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, nullptr, opts), n, in, in_stride_bytes, out,
-                            out_stride_bytes);
-} W2XC_CATCH_ALL
+{
+    return w2xc_process_image_rgb_u8_batch_tta(noise_model, scale_model, n, in, in_stride_bytes, w, h, out, out_stride_bytes, iterations, shrink_ratio, opts, 0);
+}
 
 // ---- RGBA images: alpha through the scale model, colour bled under the transparent pixels ----------
 int w2xc_process_image_rgba_u8_ex_device(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *d_in, size_t in_stride_bytes, int w, int h,
@@ -749,6 +870,76 @@ int w2xc_rgb_to_u8_device(const float *d_c0, const float *d_c1, const float *d_c
 {
     if (!d_out || !d_c0 || !d_c1 || !d_c2 || w <= 0 || h <= 0 || out_stride_bytes < (size_t)w * 3) return fail(W2XC_ERR_ARG, "bad argument");
     HIP_TRY(w2xc_launch_rgb_to_u8(d_c0, d_c1, d_c2, w, h, d_out, out_stride_bytes, (hipStream_t)hip_stream));
+    return W2XC_OK;
+}
+
+// ---- test-time augmentation: the plane calls and the two building blocks ------------------------------
+int w2xc_convert_batch_tta_device(w2xc_model *m, int n, int nn2x, const float *d_in, size_t in_plane_stride_bytes, size_t in_stride_bytes, int w, int h,
+                                  float *d_out, size_t out_plane_stride_bytes, size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts)
+try {
+    int rc = check_batch_device_args(m, n, nn2x, d_in, in_plane_stride_bytes, in_stride_bytes, w, h, d_out, out_plane_stride_bytes, out_stride_bytes);
+    if (rc) return rc;
+    if (n > (1 << 24)) return fail(W2XC_ERR_ARG, "batch of %d planes under TTA", n);   // (8 n variant planes)
+    const w2xc_opts o = resolve_opts(opts);
+    LockedImageCtx lc;
+    if ((rc = lc.open(nullptr, m, o.device))) return rc;
+    if ((rc = reserve_aux(lc.cs, 0, tta_pass_floats(w, h, nn2x) * (size_t)n))) return rc;
+    return tta_pass(TtaPass{m, lc.cs, nn2x, 1, 1, false}, n, d_in, (long long)(in_plane_stride_bytes / 4), in_stride_bytes / 4, w, h, d_out,
+                    (long long)(out_plane_stride_bytes / 4), out_stride_bytes / 4, aux_planes(lc.cs, 0), (hipStream_t)hip_stream, o);
+} W2XC_CATCH_ALL
+
+int w2xc_convert_planes_tta_device(w2xc_model *m, int n_in_planes, int nn2x, const float *d_in, size_t in_plane_stride_bytes, size_t in_stride_bytes, int w,
+                                   int h, float *d_out, size_t out_plane_stride_bytes, size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts)
+try {
+    if (nn2x != 0 && nn2x != 1) return fail(W2XC_ERR_ARG, "nn2x must be 0 or 1");
+    const w2xc_opts o = resolve_opts(opts);
+    int rc = check_planes_args(m, nn2x, n_in_planes, d_in, in_plane_stride_bytes, in_stride_bytes, w, h, d_out, out_plane_stride_bytes, out_stride_bytes, o);
+    if (rc) return rc;
+    if (m->layers.empty()) return fail(W2XC_ERR_ARG, "model has no layers");
+    if (w > (1 << 28) || h > (1 << 28) || n_in_planes > (1 << 20)) return fail(W2XC_ERR_ARG, "plane too large / too many planes");
+    // the plan of both orientations, for its errors (the plane count the model takes among them) before a device is touched
+    for (int t = 0; t < 2; t++) {
+        const int W = (t ? h : w) << nn2x, H = (t ? w : h) << nn2x;
+        RowPlan P;
+        if ((rc = plan_rows(m, o, W, H, 0, 0, H, H, n_in_planes, true, &P))) return rc;
+    }
+    const int nout = m->layers.back().nout;
+    LockedImageCtx lc;
+    if ((rc = lc.open(nullptr, m, o.device))) return rc;
+    const size_t need = 8 * ((size_t)n_in_planes * plane_floats(w, h) + (size_t)nout * plane_floats(w << nn2x, h << nn2x));
+    if ((rc = reserve_aux(lc.cs, 0, need))) return rc;
+    return tta_pass(TtaPass{m, lc.cs, nn2x, n_in_planes, nout, true}, 1, d_in, (long long)(in_plane_stride_bytes / 4), in_stride_bytes / 4, w, h, d_out,
+                    (long long)(out_plane_stride_bytes / 4), out_stride_bytes / 4, aux_planes(lc.cs, 0), (hipStream_t)hip_stream, o);
+} W2XC_CATCH_ALL
+
+// what both building blocks refuse: n planes of w x h at p (rows `row` bytes apart, planes `plane` bytes apart) and their 8 n variants at up / tr
+static int check_tta_block_args(const void *p, size_t plane, size_t row, int n, int w, int h, const void *up, const void *tr, size_t variant)
+{
+    if (!p || !up || !tr) return fail(W2XC_ERR_ARG, "null argument");
+    if (n < 1 || n > (1 << 24) || w <= 0 || h <= 0 || w > (1 << 29) || h > (1 << 29)) return fail(W2XC_ERR_ARG, "bad plane count / plane size");
+    if (row < (size_t)w * 4 || (row & 3) || (plane & 3) || (variant & 3)) return fail(W2XC_ERR_ARG, "row strides must be multiples of 4 bytes and >= 4*width");
+    if ((n > 1 && plane < (size_t)(h - 1) * row + (size_t)w * 4) || variant < (size_t)w * 4 * h) return fail(W2XC_ERR_ARG, "plane strides below one plane");
+    const size_t group = 4 * (size_t)n * variant, ext = (size_t)(n - 1) * plane + (size_t)(h - 1) * row + (size_t)w * 4;
+    if (ranges_overlap(up, group, tr, group) || ranges_overlap(p, ext, up, group) || ranges_overlap(p, ext, tr, group))
+        return fail(W2XC_ERR_ARG, "the planes and the two groups of variant planes overlap");
+    return W2XC_OK;
+}
+
+int w2xc_tta_spread_device(const float *d_src, int n, size_t src_plane_stride_bytes, size_t src_stride_bytes, int w, int h, float *d_up, float *d_tr,
+                           size_t variant_plane_stride_bytes, void *hip_stream)
+{
+    if (int rc = check_tta_block_args(d_src, src_plane_stride_bytes, src_stride_bytes, n, w, h, d_up, d_tr, variant_plane_stride_bytes)) return rc;
+    HIP_TRY(w2xc_launch_tta_spread(d_src, (long long)(src_plane_stride_bytes / 4), (long long)(src_stride_bytes / 4), w, h, d_up, d_tr,
+                                   (long long)(variant_plane_stride_bytes / 4), n, (hipStream_t)hip_stream));
+    return W2XC_OK;
+}
+
+int w2xc_tta_gather_device(const float *d_up, const float *d_tr, size_t variant_plane_stride_bytes, int n, int w, int h, float *d_dst,
+                           size_t dst_plane_stride_bytes, size_t dst_stride_bytes, void *hip_stream)
+{
+    if (int rc = check_tta_block_args(d_dst, dst_plane_stride_bytes, dst_stride_bytes, n, w, h, d_up, d_tr, variant_plane_stride_bytes)) return rc;
+    HIP_TRY(w2xc_launch_tta_gather(d_up, d_tr, (long long)(variant_plane_stride_bytes / 4), w, h, d_dst, (long long)(dst_plane_stride_bytes / 4),
+                                   (long long)(dst_stride_bytes / 4), n, (hipStream_t)hip_stream));
     return W2XC_OK;
 }
 

@@ -145,3 +145,10 @@ hipError_t w2xc_launch_alpha_to_grey(const unsigned char *src, size_t stride, in
 hipError_t w2xc_launch_merge_rgba(const unsigned char *rgb, size_t rgb_stride, const float *a, int w, int h, unsigned char *dst, size_t stride, hipStream_t st);
 hipError_t w2xc_launch_merge_rgba_u8(const unsigned char *rgb, size_t rgb_stride, const unsigned char *a, size_t a_stride, int a_px, int w, int h,
                                      unsigned char *dst, size_t stride, hipStream_t st);
+
+// test-time augmentation (w2xc_tta.hip): T_k, k = 0..7 = horizontal flip if k & 1, then vertical flip if k & 2, then transpose if k & 4.  Variant planes have
+// contiguous rows and lie ps floats apart: upright (k, i) at up + (k n + i) ps, transposed (k, i) at tr + ((k - 4) n + i) ps.
+// spread: n source planes of w x h (plane i at src + i * sps, rows srs floats apart) -> their 8 n variants.
+// gather: 8 n result planes (upright ones w x h) -> n planes (plane i at dst + i * dps, rows drs apart): the fp32 sum of T_k^-1 in the order k = 0..7, * 0.125f.
+hipError_t w2xc_launch_tta_spread(const float *src, long long sps, long long srs, int w, int h, float *up, float *tr, long long ps, int n, hipStream_t st);
+hipError_t w2xc_launch_tta_gather(const float *up, const float *tr, long long ps, int w, int h, float *dst, long long dps, long long drs, int n, hipStream_t st);

@@ -401,6 +401,23 @@ int check_plane_args(const w2xc_model *m, const void *in, size_t in_stride, int 
     return W2XC_OK;
 }
 
+int check_planes_args(const w2xc_model *m, int up, int n_in_planes, const void *d_in, size_t in_plane_stride_bytes, size_t in_stride_bytes, int w, int h,
+                      const void *d_out, size_t out_plane_stride_bytes, size_t out_stride_bytes, const w2xc_opts &o)
+{
+    const int W = w << up, H = h << up;
+    if (!m || !d_in || !d_out) return fail(W2XC_ERR_ARG, "null argument");
+    if (w <= 0 || h <= 0) return fail(W2XC_ERR_ARG, "plane size must be positive (got %dx%d)", w, h);
+    if (up && (w > (1 << 28) || h > (1 << 28))) return fail(W2XC_ERR_ARG, "plane too large");
+    if (in_stride_bytes < (size_t)w * 4 || out_stride_bytes < (size_t)W * 4 || (in_stride_bytes & 3) || (out_stride_bytes & 3))
+        return fail(W2XC_ERR_ARG, "row strides must be multiples of 4 bytes and >= 4*width");
+    if (n_in_planes < 1 || (in_plane_stride_bytes & 3) || (out_plane_stride_bytes & 3) ||
+        (n_in_planes > 1 && in_plane_stride_bytes < in_stride_bytes * (size_t)h) || out_plane_stride_bytes < out_stride_bytes * (size_t)H)
+        return fail(W2XC_ERR_ARG, "bad plane count / plane strides");
+    if (o.precision != W2XC_PRECISION_FP32 && split_terms(o) == 0)
+        return fail(W2XC_ERR_UNSUPPORTED, "w2xc_convert_planes_* supports W2XC_PRECISION_FP32 / BF16X2 / BF16X3 / FP16X2");
+    return W2XC_OK;
+}
+
 // nimg planes of one size (w2xc_convert_batch*).  The plan is that of ONE image, exactly as the single-plane device call makes it.  Where the batched chain
 // applies (batch_eligible), a sub-batch of k images is one launch per layer: the descriptor of every launch is the single-image one (same regions, offsets,
 // wino_py, clamps, strides), and the batch kernels add image x stride to their scalar bases -- input planes, the k per-image blocks of the two workspaces,
@@ -467,6 +484,25 @@ int check_batch_args(const w2xc_model *m, int nimg, int nn2x, int w, int h, size
     if (in_stride < (size_t)w * 4 || out_stride < ((size_t)w << nn2x) * 4 || (in_stride & 3) || (out_stride & 3))
         return fail(W2XC_ERR_ARG, "row strides must be multiples of 4 bytes and >= 4*width");
     return W2XC_OK;
+}
+
+// everything w2xc_convert_batch_device refuses
+int check_batch_device_args(const w2xc_model *m, int n, int nn2x, const void *d_in, size_t in_plane_stride_bytes, size_t in_stride_bytes, int w, int h,
+                            const void *d_out, size_t out_plane_stride_bytes, size_t out_stride_bytes)
+{
+    int rc = check_batch_args(m, n, nn2x, w, h, in_stride_bytes, out_stride_bytes);
+    if (rc) return rc;
+    if (!d_in || !d_out) return fail(W2XC_ERR_ARG, "null argument");
+    if ((in_plane_stride_bytes & 3) || (out_plane_stride_bytes & 3)) return fail(W2XC_ERR_ARG, "plane strides must be multiples of 4 bytes");
+    const int H = h << nn2x, W = w << nn2x;
+    const size_t in_ext = (size_t)(h - 1) * in_stride_bytes + (size_t)w * 4, out_ext = (size_t)(H - 1) * out_stride_bytes + (size_t)W * 4;
+    if (n > 1 && out_plane_stride_bytes < out_ext) return fail(W2XC_ERR_ARG, "output planes overlap each other (plane stride %zu < %zu bytes)", out_plane_stride_bytes, out_ext);
+    {
+        const uintptr_t i0 = (uintptr_t)d_in, i1 = i0 + (size_t)(n - 1) * in_plane_stride_bytes + in_ext;
+        const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (size_t)(n - 1) * out_plane_stride_bytes + out_ext;
+        if (i0 < o1 && o0 < i1) return fail(W2XC_ERR_ARG, "output planes overlap the input planes");
+    }
+    return check_batch_model(m);
 }
 
 // [lo, hi) byte ranges: does any output overlap another output or any input?  (inputs may share memory with each other)
@@ -540,17 +576,9 @@ static int convert_planes(w2xc_model *m, int up, int n_in_planes, const float *d
                           float *d_out, size_t out_plane_stride_bytes, size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts)
 {
     const int W = w << up, H = h << up;
-    if (!m || !d_in || !d_out) return fail(W2XC_ERR_ARG, "null argument");
-    if (w <= 0 || h <= 0) return fail(W2XC_ERR_ARG, "plane size must be positive (got %dx%d)", w, h);
-    if (up && (w > (1 << 28) || h > (1 << 28))) return fail(W2XC_ERR_ARG, "plane too large");
-    if (in_stride_bytes < (size_t)w * 4 || out_stride_bytes < (size_t)W * 4 || (in_stride_bytes & 3) || (out_stride_bytes & 3))
-        return fail(W2XC_ERR_ARG, "row strides must be multiples of 4 bytes and >= 4*width");
-    if (n_in_planes < 1 || (in_plane_stride_bytes & 3) || (out_plane_stride_bytes & 3) ||
-        (n_in_planes > 1 && in_plane_stride_bytes < in_stride_bytes * (size_t)h) || out_plane_stride_bytes < out_stride_bytes * (size_t)H)
-        return fail(W2XC_ERR_ARG, "bad plane count / plane strides");
     const w2xc_opts o = resolve_opts(opts);
-    if (o.precision != W2XC_PRECISION_FP32 && split_terms(o) == 0)
-        return fail(W2XC_ERR_UNSUPPORTED, "w2xc_convert_planes_* supports W2XC_PRECISION_FP32 / BF16X2 / BF16X3 / FP16X2");
+    if (int rc = check_planes_args(m, up, n_in_planes, d_in, in_plane_stride_bytes, in_stride_bytes, w, h, d_out, out_plane_stride_bytes, out_stride_bytes, o))
+        return rc;
     const long long in_cs = (long long)(in_plane_stride_bytes / 4), out_cs = (long long)(out_plane_stride_bytes / 4);
     return with_ctx(m, o, [&](DevCtx *c) {
         return run_rows(m, c, d_in, in_stride_bytes / 4, H, 0, W, 0, H, d_out, out_stride_bytes / 4, (hipStream_t)hip_stream, o, up, n_in_planes, in_cs, out_cs, nullptr, H);
@@ -588,19 +616,7 @@ try {
 int w2xc_convert_batch_device(w2xc_model *m, int n, int nn2x, const float *d_in, size_t in_plane_stride_bytes, size_t in_stride_bytes, int w, int h,
                               float *d_out, size_t out_plane_stride_bytes, size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts)
 try {
-    int rc = check_batch_args(m, n, nn2x, w, h, in_stride_bytes, out_stride_bytes);
-    if (rc) return rc;
-    if (!d_in || !d_out) return fail(W2XC_ERR_ARG, "null argument");
-    if ((in_plane_stride_bytes & 3) || (out_plane_stride_bytes & 3)) return fail(W2XC_ERR_ARG, "plane strides must be multiples of 4 bytes");
-    const int H = h << nn2x, W = w << nn2x;
-    const size_t in_ext = (size_t)(h - 1) * in_stride_bytes + (size_t)w * 4, out_ext = (size_t)(H - 1) * out_stride_bytes + (size_t)W * 4;
-    if (n > 1 && out_plane_stride_bytes < out_ext) return fail(W2XC_ERR_ARG, "output planes overlap each other (plane stride %zu < %zu bytes)", out_plane_stride_bytes, out_ext);
-    {
-        const uintptr_t i0 = (uintptr_t)d_in, i1 = i0 + (size_t)(n - 1) * in_plane_stride_bytes + in_ext;
-        const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (size_t)(n - 1) * out_plane_stride_bytes + out_ext;
-        if (i0 < o1 && o0 < i1) return fail(W2XC_ERR_ARG, "output planes overlap the input planes");
-    }
-    rc = check_batch_model(m);
+    int rc = check_batch_device_args(m, n, nn2x, d_in, in_plane_stride_bytes, in_stride_bytes, w, h, d_out, out_plane_stride_bytes, out_stride_bytes);
     if (rc) return rc;
     const w2xc_opts o = resolve_opts(opts);
     const long long in_ps = (long long)(in_plane_stride_bytes / 4), out_ps = (long long)(out_plane_stride_bytes / 4);
