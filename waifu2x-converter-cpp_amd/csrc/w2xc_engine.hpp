@@ -12,7 +12,9 @@
 //   w2xc_cuts.hpp           where the chunked launch strategies cut a band's rows (integers only; tests/cpp/cuts_test.cpp)
 //   w2xc_rows.cpp           launch_layer, run_rows (the band loop that replaces convertWithModels / ...Basic / ...BlockSplit,
 //                           src/convertRoutine.cpp:21-169: run_band picks one launch strategy per layer -- prog, tail16, tail32,
-//                           first_chunks, last_chunks, plain), run_batch, and the device-pointer entry points
+//                           first_chunks, last_chunks, plain), run_batch (the same run_band on a batched Band), and the device-pointer entry points
+//   (this file)             what those calls are made of: Planes (PlanesIn / PlanesOut: float planes of one size in device memory), RowsCall (one run_rows call;
+//                           RowsCall::whole = the whole plane, no hooks), LockedCtx (the call's context(s), locked), check_plane_size / check_row_strides, ranges_overlap
 //   w2xc_scratch.hpp        Scratch: the one owner of every grow-only device / page-locked buffer (reserve, release, the drain rule); a context lists its
 //                           buffers once, DevCtx::for_each_scratch below -- destruction, w2xc_model_trim and w2xc_debug_fill_scratch go by that list
 //   w2xc_host_geom.hpp      the integers of the host side: a unit's rows and source view, staging chunks and their taper, the rows finished job rows
@@ -40,6 +42,7 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -222,6 +225,61 @@ int upload(const std::vector<float> &h, float **d);
 int get_ctx(w2xc_model *m, int device, DevCtx **out);
 int prof_begin(DevCtx *c, int layer, hipStream_t st, ProfEvent *ev);
 
+// The contexts of the (up to two) models of a call on `dev` (the image calls: noise and scale; the plane calls: their one model as msc); with l1 / l2 they are
+// locked, TOGETHER (std::lock's deadlock avoidance; one model is one plain lock): two threads that pass the same two models in opposite roles -- (A as noise, B as
+// scale) and (B as noise, A as scale) -- would otherwise each hold one mutex and wait for the other.  The plane buffers and the host pipeline are the owning context's.
+struct CallCtx {
+    DevCtx *cn = nullptr, *cs = nullptr;
+    DevCtx *owner() const { return cs ? cs : cn; }
+};
+inline int call_contexts(w2xc_model *mn, w2xc_model *msc, int dev, CallCtx *ic, std::unique_lock<std::mutex> *l1 = nullptr, std::unique_lock<std::mutex> *l2 = nullptr)
+{
+    int rc;
+    if (mn && (rc = get_ctx(mn, dev, &ic->cn))) return rc;
+    if (msc && (rc = get_ctx(msc, dev, &ic->cs))) return rc;
+    if (!l1) return W2XC_OK;
+    // (at least one model: the entry points refuse a call without any before a context is asked for)
+    if (ic->cn && ic->cs && ic->cn != ic->cs) {
+        *l1 = std::unique_lock<std::mutex>(ic->cn->mu, std::defer_lock);
+        *l2 = std::unique_lock<std::mutex>(ic->cs->mu, std::defer_lock);
+        std::lock(*l1, *l2);
+    } else *l1 = std::unique_lock<std::mutex>(ic->owner()->mu);
+    return W2XC_OK;
+}
+// ... on the device of a call (dev < 0: the current one), selected and locked until this goes out of scope -- what every device entry point opens behind its
+// argument checks.  The lock covers the enqueue; the device guard outlives the lock (members are destroyed in reverse order).
+struct LockedCtx : CallCtx {
+    std::optional<DeviceGuard> guard;
+    std::unique_lock<std::mutex> l1, l2;
+    int open(w2xc_model *mn, w2xc_model *msc, int dev)
+    {
+        if (dev < 0) HIP_TRY(hipGetDevice(&dev));
+        guard.emplace(dev);
+        if (!guard->ok) return fail(W2XC_ERR_HIP, "cannot select HIP device %d", dev);
+        return call_contexts(mn, msc, dev, this, &l1, &l2);
+    }
+};
+
+// what the argument checks of the entry points share -- a w x h plane: positive and, where `cap` (the calls that compute with twice the size, or with a batch of them), at most 2^28 a side
+inline int check_plane_size(int w, int h, bool cap)
+{
+    if (w <= 0 || h <= 0) return fail(W2XC_ERR_ARG, "plane size must be positive (got %dx%d)", w, h);
+    return cap && (w > (1 << 28) || h > (1 << 28)) ? fail(W2XC_ERR_ARG, "plane too large") : W2XC_OK;
+}
+// the row strides (bytes) of float planes in_w wide in and out_w wide out
+inline int check_row_strides(size_t in_stride, size_t in_w, size_t out_stride, size_t out_w)
+{
+    const bool ok = in_stride >= in_w * 4 && out_stride >= out_w * 4 && !((in_stride | out_stride) & 3);
+    return ok ? W2XC_OK : fail(W2XC_ERR_ARG, "row strides must be multiples of 4 bytes and >= 4*width");
+}
+// bytes from the first pixel of an image (a plane) of `rows` rows of w pixels of px bytes to behind its last one
+inline size_t image_extent(int rows, size_t stride, int w, int px) { return (size_t)(rows - 1) * stride + (size_t)w * px; }
+inline bool ranges_overlap(const void *in, size_t in_extent, const void *out, size_t out_extent)
+{
+    const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out;
+    return i0 < o0 + out_extent && o0 < i0 + in_extent;
+}
+
 // ---- w2xc_select.cpp ----
 int split_terms(const w2xc_opts &o);
 int split_fmt(const w2xc_opts &o);
@@ -272,7 +330,7 @@ struct LayerDst {
     float *ws[2];
 };
 // The launch descriptor *d of layer k (1 .. n) of the band [y0, y1) (no HIP call), the kind that runs it, and *next = what layer k + 1 reads.  first_d keeps
-// layer 1's input description from the W2XC_K_FUSED_AWAY call (no launch: *d is not to be used) to layer 2's.  run_rows and run_batch both build with this.
+// layer 1's input description from the W2XC_K_FUSED_AWAY call (no launch: *d is not to be used) to layer 2's.  run_band (w2xc_rows.cpp) is the one loop that builds with this.
 W2xcKernelKind layer_desc(const w2xc_model *m, const RowPlan &P, int k, int y0, int y1, int up, const LayerSrc &src, const LayerDst &dst,
                           W2xcConvDesc &first_d, W2xcConvDesc *d, LayerSrc *next);
 
@@ -304,14 +362,40 @@ struct BandHooks {
     std::function<int(int, int, int, int, int)> prog_launched;
 };
 
-// u8 (the RGB image pipeline; no hooks): ROWS_U8_SRC = d_in is an interleaved uint8 image of three channels, in_stride_f its row stride in BYTES, in_cs = 1
-// (layer 1 runs as W2XC_K_FIRST_U8); ROWS_U8_DST = the same for d_out / out_stride_f / out_cs and the last layer (W2XC_K_LAST_U8).  The caller asks only
-// where u8_source_layer / u8_sink_layer say yes.
+// planes of one size in device memory, in FLOATS: plane i at p + i * ps, its rows rs apart.  The uint8 forms of run_rows (ROWS_U8_SRC / ROWS_U8_DST below) keep
+// the type: p is the reinterpret-cast pointer to the interleaved image, rs its row stride in BYTES, ps = 1 (the channels lie one byte apart).
+template <class T> struct Planes {
+    T *p; size_t rs; long long ps;
+    Planes from(size_t i) const { return {p + i * ps, rs, ps}; }    // the planes from plane i on
+    Planes plane(size_t i) const { return {p + i * ps, rs, 0}; }    // plane i alone
+    operator Planes<const T>() const { return {p, rs, ps}; }
+};
+typedef Planes<const float> PlanesIn;   // (a PlanesOut converts to it)
+typedef Planes<float> PlanesOut;
+
+// u8 (the RGB image pipeline; no hooks): ROWS_U8_SRC = `in` is an interleaved uint8 image of three channels (layer 1 runs as W2XC_K_FIRST_U8); ROWS_U8_DST =
+// the same for `out` and the last layer (W2XC_K_LAST_U8).  The caller asks only where u8_source_layer / u8_sink_layer say yes.
 enum { ROWS_U8_SRC = 1, ROWS_U8_DST = 2 };
-int run_rows(w2xc_model *m, DevCtx *c, const float *d_in, size_t in_stride_f, int vh, int vy0, int w, int ra, int rb,
-             float *d_out, size_t out_stride_f, hipStream_t st, const w2xc_opts &o_in, int up = 0, int n_in = 1,
-             long long in_cs = 0, long long out_cs = 0, const BandHooks *hk = nullptr, int plane_h = 0, int u8 = 0);
-int check_plane_args(const w2xc_model *m, const void *in, size_t in_stride, int w, int h, const void *out, size_t out_stride);
+// One run_rows call: output rows [ra, rb) of convertWithModels on a plane of plane_h rows, w wide.
+struct RowsCall {
+    // the source view: n_in planar input planes in.ps floats apart, of which `in` holds rows [view_y0, view_y0 + view_h) -- every row in [ra - n, rb + n)
+    // clipped to the plane must be inside the view
+    PlanesIn in;
+    int n_in, view_h, view_y0;
+    // plane_h = rows of the whole plane (the units of view_h / view_y0 / ra / rb), 0 = unknown.  With it, and a view that holds 4 n halo rows, the layers run
+    // on the banding-invariant geometry conv3x3_wino4 needs (plan_rows); without, W2XC_KERNEL_AUTO is refused (W2XC_ERR_ARG).
+    int w, plane_h, ra, rb;
+    // where rows [ra, rb) go (out.p = row ra).  out.ps != 0: ALL planes of the last layer, planar, that many floats apart (w2xc_convert_planes_*); 0 = plane 0
+    // only -- with n_in == 1 convertWithModels proper, which returns only outputPlanes[0] (convertRoutine.cpp:78).
+    PlanesOut out;
+    // up = 1 folds a nearest-neighbour 2x (main.cpp:132-140) into layer 1: view_h, view_y0, w, plane_h, ra, rb are then in UPSCALED coordinates while `in`
+    // holds the (view_h / 2) x (w / 2) source rows starting at source row view_y0 / 2.
+    int up, u8;              // (u8: ROWS_U8_SRC | ROWS_U8_DST)
+    const BandHooks *hk;     // the host pipeline's hooks into the band loop
+    // the common case: the whole plane of a W x H result (view = plane, every row), no hooks
+    static RowsCall whole(PlanesIn in, int n_in, int W, int H, PlanesOut out, int up, int u8 = 0) { return {in, n_in, H, 0, W, H, 0, H, out, up, u8, nullptr}; }
+};
+int run_rows(w2xc_model *m, DevCtx *c, const RowsCall &r, hipStream_t st, const w2xc_opts &o_in);
 // what w2xc_convert_planes[_nn2x]_device refuses (no device is touched); o = the resolved options
 int check_planes_args(const w2xc_model *m, int up, int n_in_planes, const void *d_in, size_t in_plane_stride, size_t in_stride, int w, int h, const void *d_out,
                       size_t out_plane_stride, size_t out_stride, const w2xc_opts &o);
@@ -322,10 +406,9 @@ int check_planes_args(const w2xc_model *m, int up, int n_in_planes, const void *
 bool batch_eligible(const w2xc_model *m, const RowPlan &P);
 // images per sub-batch for a per-image workspace of img_floats[2] floats under the call's workspace_mb budget (>= 1)
 int batch_sub_size(const w2xc_opts &o, const size_t img_floats[2]);
-// nimg planes of the (w << up) x (h << up) conversion of w x h source planes (image i at d_in + i in_ps / d_out + i out_ps, rows in_rs / out_rs apart; all
-// in floats) on `st`; enqueue-only.  max_sub > 0 caps the sub-batch size.  The caller holds c->mu.
-int run_batch(w2xc_model *m, DevCtx *c, int nimg, int up, const float *d_in, long long in_ps, size_t in_rs, int w, int h, float *d_out, long long out_ps,
-              size_t out_rs, hipStream_t st, const w2xc_opts &o_in, int max_sub = 0);
+// the nimg planes `out` of the (w << up) x (h << up) conversion of the w x h source planes `in` on `st`; enqueue-only.  max_sub > 0 caps the sub-batch
+// size.  The caller holds c->mu.
+int run_batch(w2xc_model *m, DevCtx *c, int nimg, int up, PlanesIn in, int w, int h, PlanesOut out, hipStream_t st, const w2xc_opts &o_in, int max_sub = 0);
 // per-image workspace floats of the batched chain (0, 0 when P is not eligible) -- what a sub-batch of k images needs is k times this
 void batch_ws_floats(const RowPlan &P, size_t img_floats[2]);
 int check_batch_model(const w2xc_model *m);

@@ -399,7 +399,7 @@ int host_rows_on_device(w2xc_model *m, int dev, const float *in_, size_t in_stri
     const bool in_pinned = host_range_pinned(in_lo, (size_t)(in_hi - in_lo)), out_pinned = host_range_pinned(out_lo, (size_t)(out_hi - out_lo));
     // in-place / overlapping planes (the reference never does this, main.cpp:94-96 copies first; a library must survive it):
     // the drainer writes band b's rows while later bands still read theirs, so every source row is staged before any output exists
-    const bool overlap = in_lo < out_hi && out_lo < in_hi;
+    const bool overlap = ranges_overlap(in_lo, (size_t)(in_hi - in_lo), out_lo, (size_t)(out_hi - out_lo));
     const HostChunks ck = host_chunks(o.host_chunk_kb, in_row, out_row);
     const int l1_chunk = layer1_chunk(ck.in_rows, up);
     rc = pipe_reserve(p, (size_t)svh * in_row, (size_t)(rb - ra) * out_row, in_pinned ? 0 : (size_t)ck.in_rows * in_row, out_pinned ? 0 : (size_t)ck.out_rows * out_row);
@@ -478,7 +478,9 @@ int host_rows_on_device(w2xc_model *m, int dev, const float *in_, size_t in_stri
         return W2XC_OK;
     };
 
-    rc = run_rows(m, c, p.d_in.as<float>(), w, svh << up, sy0 << up, W, ra, rb, p.d_out.as<float>(), W, p.s_compute, o, up, 1, 0, 0, &hk, H);
+    RowsCall r = RowsCall::whole({p.d_in.as<float>(), (size_t)w, 0}, 1, W, H, {p.d_out.as<float>(), (size_t)W, 0}, up);   // (of that plane: this unit's rows, from the source rows staged for them)
+    r.view_h = svh << up; r.view_y0 = sy0 << up; r.ra = ra; r.rb = rb; r.hk = &hk;
+    rc = run_rows(m, c, r, p.s_compute, o);
     const double t_enq = tr.ms();
     double t_comp = 0;
     // (not while a PROG band is being followed: the drainer polls hipStreamQuery on the same stream, and a synchronise in flight here holds it up until the launch ends)
@@ -536,12 +538,11 @@ int convert_plane_host(w2xc_model *m, const float *in, size_t in_stride_bytes, i
                        int in_row0 = 0, int in_rows = -1)
 {
     if (!m || !in || !out) return fail(W2XC_ERR_ARG, "null argument");
-    if (w <= 0 || h <= 0) return fail(W2XC_ERR_ARG, "plane size must be positive (got %dx%d)", w, h);
+    if (int rc = check_plane_size(w, h, false)) return rc;
     const int W = w << up, H = h << up;
     if (row_end < 0) row_end = H;
     if (row_begin < 0 || row_end > H || row_begin >= row_end) return fail(W2XC_ERR_ARG, "bad row range [%d,%d) for a %d-row plane", row_begin, row_end, H);
-    if (in_stride_bytes < (size_t)w * 4 || out_stride_bytes < (size_t)W * 4 || (in_stride_bytes & 3) || (out_stride_bytes & 3))
-        return fail(W2XC_ERR_ARG, "row strides must be multiples of 4 bytes and >= 4*width");
+    if (int rc = check_row_strides(in_stride_bytes, w, out_stride_bytes, W)) return rc;
     if (m->layers.empty()) return fail(W2XC_ERR_ARG, "model has no layers");
     {   // the source rows handed over must cover the rows [row_begin - n, row_end + n) reads (clipped to the plane)
         const int n = (int)m->layers.size();
@@ -591,7 +592,7 @@ int convert_plane_host(w2xc_model *m, const float *in, size_t in_stride_bytes, i
         const char *in_lo = (const char *)in + (ptrdiff_t)(s0 - in_row0) * (ptrdiff_t)in_stride_bytes;
         const char *in_hi = (const char *)in + (ptrdiff_t)(s1 - 1 - in_row0) * (ptrdiff_t)in_stride_bytes + (size_t)w * 4;
         const char *out_lo = (const char *)out, *out_hi = (const char *)out + (size_t)(R - 1) * out_stride_bytes + (size_t)W * 4;
-        if (in_lo < out_hi && out_lo < in_hi) {
+        if (ranges_overlap(in_lo, (size_t)(in_hi - in_lo), out_lo, (size_t)(out_hi - out_lo))) {
             snapshot.resize((size_t)(s1 - s0) * w);
             w2xc_host::CopyPool::get().copy_rows((char *)snapshot.data(), (size_t)w * 4, in_lo, in_stride_bytes, (size_t)w * 4, s1 - s0,
                                                  std::max(1, std::min(w2xc_get_jobs(), 32)));
@@ -751,8 +752,7 @@ int convert_batch_host(w2xc_model *m, int n, int nn2x, const float *const *in, s
     if (rc) return rc;
     if (!in || !out) return fail(W2XC_ERR_ARG, "null argument");
     const int W = w << nn2x, H = h << nn2x;
-    rc = check_batch_host_ptrs(n, (const void *const *)in, (size_t)(h - 1) * in_stride + (size_t)w * 4, (void *const *)out,
-                               (size_t)(H - 1) * out_stride + (size_t)W * 4);
+    rc = check_batch_host_ptrs(n, (const void *const *)in, image_extent(h, in_stride, w, 4), (void *const *)out, image_extent(H, out_stride, W, 4));
     if (rc) return rc;
     rc = check_batch_model(m);
     if (rc) return rc;
@@ -787,7 +787,7 @@ int convert_batch_host(w2xc_model *m, int n, int nn2x, const float *const *in, s
         DevCtx *c = nullptr;
         int r = get_ctx(m, dev, &c);
         if (r) return r;
-        return run_batch(m, c, cnt, nn2x, (const float *)din, (long long)(b.in_img / 4), (size_t)w, w, h, (float *)dout, (long long)(b.out_img / 4), (size_t)W,
+        return run_batch(m, c, cnt, nn2x, {(const float *)din, (size_t)w, (long long)(b.in_img / 4)}, w, h, {(float *)dout, (size_t)W, (long long)(b.out_img / 4)},
                          st, o, max_sub);
     };
     return batch_host_run(b, o, sub);

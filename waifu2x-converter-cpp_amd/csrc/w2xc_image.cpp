@@ -7,8 +7,6 @@
 #include "w2xc_engine.hpp"
 #include "w2xc_host_geom.hpp"
 
-#include <optional>
-
 namespace w2xc_eng {
 
 namespace {
@@ -19,52 +17,10 @@ int reserve_aux(DevCtx *c, size_t skip, size_t floats) { return c->aux.reserve(s
 float *aux_planes(DevCtx *c, size_t skip) { return reinterpret_cast<float *>(c->aux.as<unsigned char>() + skip); }
 size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
-// bytes from the first pixel of an image of `rows` rows of w pixels of px bytes to behind its last one
-size_t image_extent(int rows, size_t stride, int w, int px) { return (size_t)(rows - 1) * stride + (size_t)w * px; }
-bool ranges_overlap(const void *in, size_t in_extent, const void *out, size_t out_extent)
-{
-    const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out;
-    return i0 < o0 + out_extent && o0 < i0 + in_extent;
-}
-
-// The contexts of the (up to two) models of an image call on `dev`; with l1 / l2 they are locked, TOGETHER (std::lock's deadlock avoidance): two threads
-// that pass the same two models in opposite roles -- (A as noise, B as scale) and (B as noise, A as scale) -- would otherwise each hold one mutex and
-// wait for the other.  The plane buffers and the host pipeline are the owning context's: the scale model's when present.
-struct ImageCtx {
-    DevCtx *cn = nullptr, *cs = nullptr;
-    DevCtx *owner() const { return cs ? cs : cn; }
-};
-int image_contexts(w2xc_model *mn, w2xc_model *msc, int dev, ImageCtx *ic, std::unique_lock<std::mutex> *l1 = nullptr, std::unique_lock<std::mutex> *l2 = nullptr)
-{
-    int rc;
-    if (mn && (rc = get_ctx(mn, dev, &ic->cn))) return rc;
-    if (msc && (rc = get_ctx(msc, dev, &ic->cs))) return rc;
-    if (!l1) return W2XC_OK;
-    // (at least one model: check_process_args has refused a call without any before a context is asked for)
-    if (ic->cn && ic->cs && ic->cn != ic->cs) {
-        *l1 = std::unique_lock<std::mutex>(ic->cn->mu, std::defer_lock);
-        *l2 = std::unique_lock<std::mutex>(ic->cs->mu, std::defer_lock);
-        std::lock(*l1, *l2);
-    } else *l1 = std::unique_lock<std::mutex>(ic->owner()->mu);
-    return W2XC_OK;
-}
-// ... on the device of a call (dev < 0: the current one), selected and locked until this goes out of scope: what every call on one device opens first
-struct LockedImageCtx : ImageCtx {
-    std::optional<DeviceGuard> guard;
-    std::unique_lock<std::mutex> l1, l2;
-    int open(w2xc_model *mn, w2xc_model *msc, int dev)
-    {
-        if (dev < 0) HIP_TRY(hipGetDevice(&dev));
-        guard.emplace(dev);
-        if (!guard->ok) return fail(W2XC_ERR_HIP, "cannot select HIP device %d", dev);
-        return image_contexts(mn, msc, dev, this, &l1, &l2);
-    }
-};
-
 // What is fixed for one image call: the models and (once a device is open) their contexts, the source size and the passes, the final size, stream, options.
 struct ImageCall {
     w2xc_model *mn, *msc;
-    ImageCtx ctx;
+    CallCtx ctx;
     int w, h, iterations;
     double shrink;
     int fw = 0, fh = 0;   // final_size: set by check_image_args, which refuses the arguments it cannot be computed from
@@ -82,11 +38,11 @@ struct ImageCall {
 };
 
 // ---- test-time augmentation: one TTA pass of a model (the arithmetic: include/w2xc_hip.h) ----
-// spread -> the CNN on the 8 variants -> gather, for `runs` CNN runs per variant of nin planes in and nout planes out each.  The runs * nin source planes lie
-// sps floats apart (rows srs), the runs * nout result planes dps apart (rows drs); `var` holds tta_pass_floats(w, h, up) floats per source plane and per
-// result plane's share (8 (ni ps + no PS) in all): the input variants -- the upright group, the transposed group directly behind it -- then the output
-// variants likewise.  rows = false (nin = nout = 1): the one-plane chain, run_batch on all variants of one size -- ONE batch of 8 where w == h, where the
-// transposed group continues the upright one.  rows = true: the multi-plane form, the single-image run_rows sequence per variant and run.
+// spread -> the CNN on the 8 variants -> gather, for `runs` CNN runs per variant of nin planes in and nout planes out each: `src` = the runs * nin source
+// planes, `dst` = the runs * nout result planes.  `var` holds tta_pass_floats(w, h, up) floats per source plane and per result plane's share
+// (8 (ni ps + no PS) in all): the input variants -- the upright group, the transposed group directly behind it -- then the output variants likewise.
+// rows = false (nin = nout = 1): the one-plane chain, run_batch on all variants of one size -- ONE batch of 8 where w == h, where the transposed group
+// continues the upright one.  rows = true: the multi-plane form, the single-image run_rows sequence per variant and run.
 // Nearest-2x commutes with every T_k: a scale pass (up = 1) spreads at source resolution and gathers at 2x.
 struct TtaPass {
     w2xc_model *m;
@@ -94,31 +50,33 @@ struct TtaPass {
     int up, nin, nout;
     bool rows;
 };
-int tta_pass(const TtaPass &t, int runs, const float *src, long long sps, size_t srs, int w, int h, float *dst, long long dps, size_t drs, float *var,
-             hipStream_t st, const w2xc_opts &o)
+int tta_pass(const TtaPass &t, int runs, PlanesIn src, int w, int h, PlanesOut dst, float *var, hipStream_t st, const w2xc_opts &o)
 {
     const int W = w << t.up, H = h << t.up, ni = runs * t.nin, no = runs * t.nout;
     const long long ps = (long long)plane_floats(w, h), PS = (long long)plane_floats(W, H);
-    float *in_up = var, *in_tr = in_up + 4 * (size_t)ni * ps, *out_up = in_tr + 4 * (size_t)ni * ps, *out_tr = out_up + 4 * (size_t)no * PS;
-    HIP_TRY(w2xc_launch_tta_spread(src, sps, (long long)srs, w, h, in_up, in_tr, ps, ni, st));
+    // the four groups of variant planes: 4 ni upright and 4 ni transposed (h x w) in, 4 no and 4 no out
+    const PlanesOut in_up{var, (size_t)w, ps}, in_tr{in_up.p + 4 * (size_t)ni * ps, (size_t)h, ps};
+    const PlanesOut out_up{in_tr.p + 4 * (size_t)ni * ps, (size_t)W, PS}, out_tr{out_up.p + 4 * (size_t)no * PS, (size_t)H, PS};
+    HIP_TRY(w2xc_launch_tta_spread(src.p, src.ps, (long long)src.rs, w, h, in_up.p, in_tr.p, ps, ni, st));
     if (!t.rows) {
         if (w == h) {
-            if (int rc = run_batch(t.m, t.cm, 8 * ni, t.up, in_up, ps, (size_t)w, w, h, out_up, PS, (size_t)W, st, o)) return rc;
+            if (int rc = run_batch(t.m, t.cm, 8 * ni, t.up, in_up, w, h, out_up, st, o)) return rc;
         } else {
-            if (int rc = run_batch(t.m, t.cm, 4 * ni, t.up, in_up, ps, (size_t)w, w, h, out_up, PS, (size_t)W, st, o)) return rc;
-            if (int rc = run_batch(t.m, t.cm, 4 * ni, t.up, in_tr, ps, (size_t)h, h, w, out_tr, PS, (size_t)H, st, o)) return rc;
+            if (int rc = run_batch(t.m, t.cm, 4 * ni, t.up, in_up, w, h, out_up, st, o)) return rc;
+            if (int rc = run_batch(t.m, t.cm, 4 * ni, t.up, in_tr, h, w, out_tr, st, o)) return rc;
         }
     } else {
         for (int k = 0; k < 8; k++) {
-            const int vw = k < 4 ? w : h, vh = k < 4 ? h : w, VW = vw << t.up, VH = vh << t.up;
+            const PlanesOut &in = k < 4 ? in_up : in_tr, &out = k < 4 ? out_up : out_tr;
+            const int VW = (k < 4 ? w : h) << t.up, VH = (k < 4 ? h : w) << t.up;
             for (int r = 0; r < runs; r++) {
-                const float *in = (k < 4 ? in_up : in_tr) + ((size_t)(k & 3) * ni + (size_t)r * t.nin) * ps;
-                float *out = (k < 4 ? out_up : out_tr) + ((size_t)(k & 3) * no + (size_t)r * t.nout) * PS;
-                if (int rc = run_rows(t.m, t.cm, in, (size_t)vw, VH, 0, VW, 0, VH, out, (size_t)VW, st, o, t.up, t.nin, ps, PS, nullptr, VH)) return rc;
+                const RowsCall call = RowsCall::whole(in.from((size_t)(k & 3) * ni + (size_t)r * t.nin), t.nin, VW, VH,
+                                                      out.from((size_t)(k & 3) * no + (size_t)r * t.nout), t.up);
+                if (int rc = run_rows(t.m, t.cm, call, st, o)) return rc;
             }
         }
     }
-    HIP_TRY(w2xc_launch_tta_gather(out_up, out_tr, PS, W, H, dst, dps, (long long)drs, no, st));
+    HIP_TRY(w2xc_launch_tta_gather(out_up.p, out_tr.p, PS, W, H, dst.p, dst.ps, (long long)dst.rs, no, st));
     return W2XC_OK;
 }
 
@@ -158,9 +116,12 @@ int process_y_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, siz
         w2xc_model *m = noise ? c.mn : c.msc;
         DevCtx *cm = noise ? c.ctx.cn : c.ctx.cs;
         const int nw = w << up, nh = h << up;   // (up = 1: INTER_NEAREST 2x folded into layer 1, :136-140, + convertWithModels, :148)
-        if (c.tta) return tta_pass(TtaPass{m, cm, up, 1, 1, false}, noise ? S : (int)ny, src, sps, (size_t)w, w, h, dst, dps, (size_t)nw, var, c.st, c.o);
-        return c.rows || (noise && al) ? run_rows(m, cm, src, w, nh, 0, nw, 0, nh, dst, nw, c.st, c.o, up, 1, 0, 0, nullptr, nh)
-                                       : run_batch(m, cm, noise ? S : (int)ny, up, src, sps, (size_t)w, w, h, dst, dps, (size_t)nw, c.st, c.o);
+        const int np = noise ? S : (int)ny;
+        const PlanesIn in{src, (size_t)w, sps};
+        const PlanesOut out{dst, (size_t)nw, dps};
+        if (c.tta) return tta_pass(TtaPass{m, cm, up, 1, 1, false}, np, in, w, h, out, var, c.st, c.o);
+        return c.rows || (noise && al) ? run_rows(m, cm, RowsCall::whole(in.plane(0), 1, nw, nh, out.plane(0), up), c.st, c.o)
+                                       : run_batch(m, cm, np, up, in, w, h, out, c.st, c.o);
     };
     float *base = aux_planes(own, skip);
     int cw = c.w, ch = c.h;
@@ -254,12 +215,12 @@ int process_rgb_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, s
         float *nxt = nullptr;
         if (!to_u8) { nxt = base; base += 3 * (size_t)cap * ps2; }
         if (c.tta) {   // (neither from_u8 nor to_u8: rgb_plan)
-            if (int rc = tta_pass(TtaPass{m, cm, up, 3, 3, true}, S, cur, ps, (size_t)cw, cw, ch, nxt, ps2, (size_t)nw, var, c.st, c.o)) return rc;
+            if (int rc = tta_pass(TtaPass{m, cm, up, 3, 3, true}, S, {cur, (size_t)cw, ps}, cw, ch, {nxt, (size_t)nw, ps2}, var, c.st, c.o)) return rc;
         } else for (int i = 0; i < S; i++) {
-            const float *src = from_u8 ? reinterpret_cast<const float *>(in.p + (size_t)i * in.img) : cur + (size_t)i * 3 * ps;
-            float *dst = to_u8 ? reinterpret_cast<float *>(out.p + (size_t)i * out.img) : nxt + (size_t)i * 3 * ps2;
-            int rc = run_rows(m, cm, src, from_u8 ? in.row : (size_t)cw, nh, 0, nw, 0, nh, dst, to_u8 ? out.row : (size_t)nw, c.st, c.o, up, 3,
-                              from_u8 ? 1 : ps, to_u8 ? 1 : ps2, nullptr, nh, (from_u8 ? ROWS_U8_SRC : 0) | (to_u8 ? ROWS_U8_DST : 0));
+            // image i's three planes, or -- the uint8 forms -- the caller's image itself: strides in bytes (Planes, w2xc_engine.hpp)
+            const PlanesIn src = from_u8 ? PlanesIn{reinterpret_cast<const float *>(in.p + (size_t)i * in.img), in.row, 1} : PlanesIn{cur + (size_t)i * 3 * ps, (size_t)cw, ps};
+            const PlanesOut dst = to_u8 ? PlanesOut{reinterpret_cast<float *>(out.p + (size_t)i * out.img), out.row, 1} : PlanesOut{nxt + (size_t)i * 3 * ps2, (size_t)nw, ps2};
+            int rc = run_rows(m, cm, RowsCall::whole(src, 3, nw, nh, dst, up, (from_u8 ? ROWS_U8_SRC : 0) | (to_u8 ? ROWS_U8_DST : 0)), c.st, c.o);
             if (rc) return rc;
         }
         if (to_u8) return W2XC_OK;
@@ -317,6 +278,14 @@ int plan_image_call(PlanKind kind, const ImageCall &c, int *sub)
     return W2XC_OK;
 }
 
+// the Y route through run_batch -- the batch forms, the alpha ride, the variants of a TTA pass -- asks one plane in and one out of each model
+int check_y_models(const ImageCall &c)
+{
+    if (c.mn) if (int rc = check_batch_model(c.mn)) return rc;
+    if (c.msc) if (int rc = check_batch_model(c.msc)) return rc;
+    return W2XC_OK;
+}
+
 int check_process_args(const ImageCall &c)
 {
     if (c.tta_arg != 0 && c.tta_arg != 1) return fail(W2XC_ERR_ARG, "tta must be 0 or 1 (got %d)", c.tta_arg);
@@ -364,7 +333,7 @@ template <class F> int host_round_trip(const ImageCall &c, int px, U8In in, U8Ou
 // w2xc_process_image_[rgb_]u8_ex on device `dev`, and a host batch of one image
 int image_host_single(bool rgb, ImageCall &c, U8In in, U8Out out, int dev)
 {
-    LockedImageCtx lc;
+    LockedCtx lc;
     if (int rc = lc.open(c.mn, c.msc, dev)) return rc;
     c.ctx = lc;
     c.rows = true;
@@ -379,10 +348,7 @@ int check_image_batch_args(bool rgb, ImageCall &c, int n, size_t in_stride, size
     if (rc) return rc;
     if ((rc = check_image_args(c, &n, in_stride, &n, out_stride))) return rc;   // (pointers: see above)
     if ((rc = check_image_extent(c))) return rc;
-    if (rgb) return W2XC_OK;   // (the models' plane form: plan_image_call, behind the caller's pointer checks)
-    if (c.mn && (rc = check_batch_model(c.mn))) return rc;
-    if (c.msc && (rc = check_batch_model(c.msc))) return rc;
-    return W2XC_OK;
+    return rgb ? W2XC_OK : check_y_models(c);   // (RGB: the models' plane form is plan_image_call's, behind the caller's pointer checks)
 }
 
 // ---- RGBA images (w2xc_process_image_rgba_u8*) ----
@@ -413,10 +379,7 @@ int plan_rgba(const ImageCall &c, int bleed_passes, RgbaPlan *R)
     if (first->layers.empty()) return fail(W2XC_ERR_ARG, "model has no layers");
     if (int rc = check_image_extent(c)) return rc;
     R->rgb = first->layers[0].nin == 3;
-    if (!R->rgb) {
-        if (c.mn) if (int rc = check_batch_model(c.mn)) return rc;
-        if (c.msc) if (int rc = check_batch_model(c.msc)) return rc;
-    }
+    if (!R->rgb) if (int rc = check_y_models(c)) return rc;
     int sub;
     if (int rc = plan_image_call(R->rgb ? PLAN_RGB : PLAN_Y, c, &sub)) return rc;
     long long P = bleed_passes;
@@ -499,7 +462,7 @@ int check_rgba_call(ImageCall &c, U8In in, U8Out out, int bleed_passes, RgbaPlan
 int rgba_ex_device(ImageCall c, U8In in, U8Out out, int bleed_passes)
 {
     RgbaPlan R;
-    LockedImageCtx lc;
+    LockedCtx lc;
     int rc = check_rgba_call(c, in, out, bleed_passes, &R);
     if (rc || (rc = lc.open(c.mn, c.msc, c.o.device))) return rc;
     c.ctx = lc;
@@ -510,7 +473,7 @@ int rgba_ex_device(ImageCall c, U8In in, U8Out out, int bleed_passes)
 int rgba_ex_host(ImageCall c, U8In in, U8Out out, int bleed_passes)
 {
     RgbaPlan R;
-    LockedImageCtx lc;
+    LockedCtx lc;
     int rc = check_rgba_call(c, in, out, bleed_passes, &R);
     if (rc) return rc;
     if (w2xc_device_count() <= 0) return fail(W2XC_ERR_HIP, "no HIP device available (libw2xc_hip has no CPU fallback)");
@@ -531,14 +494,6 @@ BleedScratch &bleed_scratch()
     return *b;
 }
 
-// the variants of a Y plane go through run_batch: one plane in, one out (what the batch forms ask of their models)
-int check_tta_y_models(const ImageCall &c)
-{
-    if (c.mn) if (int rc = check_batch_model(c.mn)) return rc;
-    if (c.msc) if (int rc = check_batch_model(c.msc)) return rc;
-    return W2XC_OK;
-}
-
 // ---- the four forms of the image call, for Y models (rgb = false: w2xc_process_image_u8*) and RGB models (w2xc_process_image_rgb_u8*) ----
 int image_ex_device(bool rgb, ImageCall c, U8In in, U8Out out)
 {
@@ -552,8 +507,8 @@ int image_ex_device(bool rgb, ImageCall c, U8In in, U8Out out)
             return fail(W2XC_ERR_ARG, "the output image overlaps the input image");
         if ((rc = plan_image_call(PLAN_RGB, c, &sub))) return rc;
     }
-    if (!rgb && c.tta && (rc = check_tta_y_models(c))) return rc;
-    LockedImageCtx lc;
+    if (!rgb && c.tta && (rc = check_y_models(c))) return rc;
+    LockedCtx lc;
     if ((rc = lc.open(c.mn, c.msc, c.o.device))) return rc;
     c.ctx = lc;
     c.rows = true;
@@ -567,7 +522,7 @@ int image_ex_host(bool rgb, ImageCall c, U8In in, U8Out out)
     if ((rc = check_image_args(c, in.p, in.row, out.p, out.row))) return rc;
     int sub;
     if (rgb && (rc = plan_image_call(PLAN_RGB, c, &sub))) return rc;
-    if (!rgb && c.tta && (rc = check_tta_y_models(c))) return rc;
+    if (!rgb && c.tta && (rc = check_y_models(c))) return rc;
     if (w2xc_device_count() <= 0) return fail(W2XC_ERR_HIP, "no HIP device available (libw2xc_hip has no CPU fallback)");
     return image_host_single(rgb, c, in, out, c.o.device);
 }
@@ -585,7 +540,7 @@ int image_batch_device(bool rgb, ImageCall c, int n, U8In in, U8Out out)
     int sub = 1;
     if ((rc = plan_image_call(rgb ? PLAN_RGB : PLAN_Y, c, &sub))) return rc;
     sub = std::min(sub, n);
-    LockedImageCtx lc;
+    LockedCtx lc;
     if ((rc = lc.open(c.mn, c.msc, c.o.device))) return rc;
     c.ctx = lc;
     for (int b0 = 0; b0 < n; b0 += sub) {
@@ -619,8 +574,8 @@ int image_batch_host(bool rgb, ImageCall c, int n, const unsigned char *const *i
     b.in_img = align256(b.in_row * c.h); b.out_img = align256(b.out_row * c.fh);
     // both models' contexts, locked together for this device's share of the call; the pipeline is the owning context's
     b.acquire = [&](int dev, std::unique_lock<std::mutex> &l1, std::unique_lock<std::mutex> &l2, HostPipe **pipe) -> int {
-        ImageCtx ic;
-        int r = image_contexts(c.mn, c.msc, dev, &ic, &l1, &l2);
+        CallCtx ic;
+        int r = call_contexts(c.mn, c.msc, dev, &ic, &l1, &l2);
         if (r) return r;
         *pipe = &ic.owner()->pipe;
         return W2XC_OK;
@@ -628,7 +583,7 @@ int image_batch_host(bool rgb, ImageCall c, int n, const unsigned char *const *i
     b.run = [&](int dev, int cnt, const void *din, void *dout, hipStream_t st, int max_sub) -> int {
         ImageCall d = c;   // (this device's share of the call: its contexts, locked by acquire, and the pipeline's stream)
         d.st = st;
-        int r = image_contexts(c.mn, c.msc, dev, &d.ctx);
+        int r = call_contexts(c.mn, c.msc, dev, &d.ctx);
         if (r) return r;
         return process_sub_batch(rgb, d, cnt, max_sub, U8In{(const unsigned char *)din, b.in_img, b.in_row}, U8Out{(unsigned char *)dout, b.out_img, b.out_row});
     };
@@ -881,11 +836,11 @@ try {
     if (rc) return rc;
     if (n > (1 << 24)) return fail(W2XC_ERR_ARG, "batch of %d planes under TTA", n);   // (8 n variant planes)
     const w2xc_opts o = resolve_opts(opts);
-    LockedImageCtx lc;
+    LockedCtx lc;
     if ((rc = lc.open(nullptr, m, o.device))) return rc;
     if ((rc = reserve_aux(lc.cs, 0, tta_pass_floats(w, h, nn2x) * (size_t)n))) return rc;
-    return tta_pass(TtaPass{m, lc.cs, nn2x, 1, 1, false}, n, d_in, (long long)(in_plane_stride_bytes / 4), in_stride_bytes / 4, w, h, d_out,
-                    (long long)(out_plane_stride_bytes / 4), out_stride_bytes / 4, aux_planes(lc.cs, 0), (hipStream_t)hip_stream, o);
+    return tta_pass(TtaPass{m, lc.cs, nn2x, 1, 1, false}, n, {d_in, in_stride_bytes / 4, (long long)(in_plane_stride_bytes / 4)}, w, h,
+                    {d_out, out_stride_bytes / 4, (long long)(out_plane_stride_bytes / 4)}, aux_planes(lc.cs, 0), (hipStream_t)hip_stream, o);
 } W2XC_CATCH_ALL
 
 int w2xc_convert_planes_tta_device(w2xc_model *m, int n_in_planes, int nn2x, const float *d_in, size_t in_plane_stride_bytes, size_t in_stride_bytes, int w,
@@ -904,12 +859,12 @@ try {
         if ((rc = plan_rows(m, o, W, H, 0, 0, H, H, n_in_planes, true, &P))) return rc;
     }
     const int nout = m->layers.back().nout;
-    LockedImageCtx lc;
+    LockedCtx lc;
     if ((rc = lc.open(nullptr, m, o.device))) return rc;
     const size_t need = 8 * ((size_t)n_in_planes * plane_floats(w, h) + (size_t)nout * plane_floats(w << nn2x, h << nn2x));
     if ((rc = reserve_aux(lc.cs, 0, need))) return rc;
-    return tta_pass(TtaPass{m, lc.cs, nn2x, n_in_planes, nout, true}, 1, d_in, (long long)(in_plane_stride_bytes / 4), in_stride_bytes / 4, w, h, d_out,
-                    (long long)(out_plane_stride_bytes / 4), out_stride_bytes / 4, aux_planes(lc.cs, 0), (hipStream_t)hip_stream, o);
+    return tta_pass(TtaPass{m, lc.cs, nn2x, n_in_planes, nout, true}, 1, {d_in, in_stride_bytes / 4, (long long)(in_plane_stride_bytes / 4)}, w, h,
+                    {d_out, out_stride_bytes / 4, (long long)(out_plane_stride_bytes / 4)}, aux_planes(lc.cs, 0), (hipStream_t)hip_stream, o);
 } W2XC_CATCH_ALL
 
 // what both building blocks refuse: n planes of w x h at p (rows `row` bytes apart, planes `plane` bytes apart) and their 8 n variants at up / tr

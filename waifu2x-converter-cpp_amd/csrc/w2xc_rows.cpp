@@ -124,8 +124,24 @@ struct Band {
     int y0, y1, rb;
     int in_chunk;   // > 0: layer 1 (or the fused layers 1 + 2) runs in chunks of this many rows behind the upload (first_chunks)
     int u8;         // ROWS_U8_SRC / ROWS_U8_DST: the view / `out` is an interleaved uint8 image, its strides are in bytes (no hooks: every launch is the plain one)
+    // run_batch: > 0 = every launch is the batch form on this many images of the band's geometry (no hooks: every launch is the plain one), image i in_bs / out_bs
+    // floats behind image 0 in the caller's planes and img_f[j] floats behind it in workspace j
+    int batch = 0;
+    long long in_bs = 0, out_bs = 0;
+    size_t img_f[2] = {0, 0};
 
-    int launch(int k, W2xcKernelKind kind, const W2xcConvDesc &d) const { return launch_layer(c, m, k - 1, kind, d, st, P.o); }
+    int launch(int k, W2xcKernelKind kind, const W2xcConvDesc &d) const
+    {
+        if (!batch) return launch_layer(c, m, k - 1, kind, d, st, P.o);
+        // the image strides of layer k: the first launched layer reads the caller's planes, layer n writes them; layer j < n writes workspace (j - 1) & 1
+        W2xcBatchDesc bd;
+        memset(&bd, 0, sizeof bd);
+        bd.batch = batch;
+        const bool first = k == 1 || (k == 2 && layer_kind(m, 0, P.o) == W2XC_K_FUSED_AWAY);
+        bd.in_bs = first ? in_bs : (long long)img_f[(k - 2) & 1];
+        bd.out_bs = k == P.n ? out_bs : (long long)img_f[(k - 1) & 1];
+        return launch_layer(c, m, k - 1, kind, d, st, P.o, &bd);
+    }
     // stage the next band's input while this one computes
     int prefetch() const { return (hk && hk->prefetch && y1 < rb) ? hk->prefetch(y1, std::min(rb, y1 + P.band)) : W2XC_OK; }
 };
@@ -317,6 +333,10 @@ int run_band(Band &B, const LayerSrc &view, int up)
     const RowPlan &P = B.P;
     const w2xc_opts &o = P.o;
     const int n = P.n;
+    // a batched band is one plain launch per layer: every other strategy needs hooks or W2XC_FUSION_PROG, the repack a last layer that cannot store planar
+    // (batch_eligible lets none of them through; nothing is launched otherwise)
+    if (B.batch && (hk || B.u8 || o.fusion == W2XC_FUSION_PROG || !P.last_direct))
+        return fail(W2XC_ERR_ARG, "internal error: a batched band that is not one plain launch per layer");
     // layer 1 of this band in row chunks (each waits only for the rows it reads) or in one launch behind the whole upload
     const W2xcKernelKind kind1 = layer_kind(m, 0, o);
     const bool first2_fp32 = kind1 == W2XC_K_FUSED_AWAY && n > 1 && layer_kind(m, 1, o) == W2XC_K_FIRST2_WINO4;   // (layers 1 + 2 in one launch: chunked like layer 1)
@@ -327,7 +347,7 @@ int run_band(Band &B, const LayerSrc &view, int up)
     W2xcConvDesc first_d, d;
     memset(&first_d, 0, sizeof first_d);
     for (int k = 1; k <= n; k++, src = next) {
-        if (o.verbose & 1) std::cout << "Iteration #" << k << "..." << std::endl;   // convertRoutine.cpp:67
+        if ((o.verbose & 1) && !B.batch) std::cout << "Iteration #" << k << "..." << std::endl;   // convertRoutine.cpp:67
         W2xcKernelKind kind = layer_desc(m, P, k, B.y0, B.y1, up, src, dst, first_d, &d, &next);
         if (kind == W2XC_K_FUSED_AWAY) continue;
         // the uint8 forms (run_rows has checked the kinds they stand in for): the descriptor's strides are the image's, in bytes
@@ -354,62 +374,45 @@ int run_band(Band &B, const LayerSrc &view, int up)
 
 }  // namespace
 
-// Output rows [ra, rb) of convertWithModels on an h-row plane of which `d_in` holds rows
-// [vy0, vy0+vh) -- every row in [ra-n, rb+n) clipped to the plane must be inside the view.
-// `up` = 1 folds a nearest-neighbour 2x (main.cpp:132-140) into layer 1: vh, vy0, w, ra, rb are then in
-// UPSCALED coordinates while d_in holds the (vh/2) x (w/2) source rows starting at source row vy0/2.
-// Multi-plane form (w2xc_convert_planes_*): n_in planar input planes `in_cs` floats apart, ALL planes of the
-// last layer written planar `out_cs` floats apart.  n_in == 1 && out_cs == 0 is convertWithModels proper,
-// which returns only outputPlanes[0] (convertRoutine.cpp:78).
-// plane_h = rows of the whole plane (the units of vh / vy0 / ra / rb), 0 = unknown.  With it, and a view that holds 4 n halo rows, the
-// layers run on the banding-invariant geometry conv3x3_wino4 needs (plan_rows); without, W2XC_KERNEL_AUTO is refused (W2XC_ERR_ARG).
-int run_rows(w2xc_model *m, DevCtx *c, const float *d_in, size_t in_stride_f, int vh, int vy0, int w, int ra, int rb,
-             float *d_out, size_t out_stride_f, hipStream_t st, const w2xc_opts &o_in, int up, int n_in,
-             long long in_cs, long long out_cs, const BandHooks *hk, int plane_h, int u8)
+// one call of the band loop (RowsCall, w2xc_engine.hpp): plan, reserve the workspaces, run_band per band
+int run_rows(w2xc_model *m, DevCtx *c, const RowsCall &r, hipStream_t st, const w2xc_opts &o_in)
 {
     RowPlan P;
-    {
-        int rc = plan_rows(m, o_in, w, vh, vy0, ra, rb, plane_h, n_in, out_cs != 0, &P);
-        if (rc) return rc;
-    }
-    if (u8 && (hk || ((u8 & ROWS_U8_SRC) && (in_cs != 1 || !u8_source_layer(m, P.o))) ||
-               ((u8 & ROWS_U8_DST) && (out_cs != 1 || !P.last_direct || !u8_sink_layer(m, P.o)))))
+    if (int rc = plan_rows(m, o_in, r.w, r.view_h, r.view_y0, r.ra, r.rb, r.plane_h, r.n_in, r.out.ps != 0, &P)) return rc;
+    if (r.u8 && (r.hk || ((r.u8 & ROWS_U8_SRC) && (r.in.ps != 1 || !u8_source_layer(m, P.o))) ||
+               ((r.u8 & ROWS_U8_DST) && (r.out.ps != 1 || !P.last_direct || !u8_sink_layer(m, P.o)))))
         return fail(W2XC_ERR_ARG, "internal error: a uint8 view for a layer without the uint8 kernel");
     for (int i = 0; i < 2; i++)
         if (P.need[i]) { int rc = c->ws[i].reserve((P.need[i] + 3) / 4 * sizeof(float), "the activation workspace"); if (rc) return rc; }
-    LayerSrc view;   // the source view; its first row is plane row vy0
-    view.p = d_in; view.rs = (long long)in_stride_f; view.cs = in_cs;
-    view.h = vh; view.w = w; view.top = vy0;
-    if (u8 & ROWS_U8_SRC) view.ps = 3;   // (bytes: row stride in_stride_f, pixels 3 apart, channels in_cs = 1 apart)
-    for (int y0 = ra; y0 < rb; y0 += P.band) {
-        // the band's first output row: out_stride_f floats per row, or -- a uint8 image -- as many BYTES
-        float *band_out = (u8 & ROWS_U8_DST) ? reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(d_out) + (size_t)(y0 - ra) * out_stride_f)
-                                              : d_out + (size_t)(y0 - ra) * out_stride_f;
-        Band B = {m, c, P, hk, st, band_out, (long long)out_stride_f, out_cs, y0, std::min(rb, y0 + P.band), rb, 0, u8};
-        int rc = run_band(B, view, up);
-        if (rc) return rc;
+    LayerSrc view;   // the source view; its first row is plane row view_y0
+    view.p = r.in.p; view.rs = (long long)r.in.rs; view.cs = r.in.ps;
+    view.h = r.view_h; view.w = r.w; view.top = r.view_y0;
+    if (r.u8 & ROWS_U8_SRC) view.ps = 3;   // (bytes: row stride in.rs, pixels 3 apart, channels in.ps = 1 apart)
+    for (int y0 = r.ra; y0 < r.rb; y0 += P.band) {
+        // the band's first output row: out.rs floats per row, or -- a uint8 image -- as many BYTES
+        float *band_out = (r.u8 & ROWS_U8_DST) ? reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(r.out.p) + (size_t)(y0 - r.ra) * r.out.rs)
+                                              : r.out.p + (size_t)(y0 - r.ra) * r.out.rs;
+        Band B = {m, c, P, r.hk, st, band_out, (long long)r.out.rs, r.out.ps, y0, std::min(r.rb, y0 + P.band), r.rb, 0, r.u8};
+        if (int rc = run_band(B, view, r.up)) return rc;
     }
     return W2XC_OK;
 }
 
-int check_plane_args(const w2xc_model *m, const void *in, size_t in_stride, int w, int h, const void *out, size_t out_stride)
+// what the one-plane device calls refuse: a w x h plane (view) in, rows (w << up) wide out
+static int check_plane_args(const w2xc_model *m, const void *in, size_t in_stride, int w, int h, const void *out, size_t out_stride, int up = 0)
 {
     if (!m || !in || !out) return fail(W2XC_ERR_ARG, "null argument");
-    if (w <= 0 || h <= 0) return fail(W2XC_ERR_ARG, "plane size must be positive (got %dx%d)", w, h);
-    if (in_stride < (size_t)w * 4 || out_stride < (size_t)w * 4 || (in_stride & 3) || (out_stride & 3))
-        return fail(W2XC_ERR_ARG, "row strides must be multiples of 4 bytes and >= 4*w");
-    return W2XC_OK;
+    if (int rc = check_plane_size(w, h, false)) return rc;
+    return check_row_strides(in_stride, w, out_stride, (size_t)w << up);
 }
 
 int check_planes_args(const w2xc_model *m, int up, int n_in_planes, const void *d_in, size_t in_plane_stride_bytes, size_t in_stride_bytes, int w, int h,
                       const void *d_out, size_t out_plane_stride_bytes, size_t out_stride_bytes, const w2xc_opts &o)
 {
-    const int W = w << up, H = h << up;
     if (!m || !d_in || !d_out) return fail(W2XC_ERR_ARG, "null argument");
-    if (w <= 0 || h <= 0) return fail(W2XC_ERR_ARG, "plane size must be positive (got %dx%d)", w, h);
-    if (up && (w > (1 << 28) || h > (1 << 28))) return fail(W2XC_ERR_ARG, "plane too large");
-    if (in_stride_bytes < (size_t)w * 4 || out_stride_bytes < (size_t)W * 4 || (in_stride_bytes & 3) || (out_stride_bytes & 3))
-        return fail(W2XC_ERR_ARG, "row strides must be multiples of 4 bytes and >= 4*width");
+    if (int rc = check_plane_size(w, h, up != 0)) return rc;
+    const int W = w << up, H = h << up;
+    if (int rc = check_row_strides(in_stride_bytes, w, out_stride_bytes, W)) return rc;
     if (n_in_planes < 1 || (in_plane_stride_bytes & 3) || (out_plane_stride_bytes & 3) ||
         (n_in_planes > 1 && in_plane_stride_bytes < in_stride_bytes * (size_t)h) || out_plane_stride_bytes < out_stride_bytes * (size_t)H)
         return fail(W2XC_ERR_ARG, "bad plane count / plane strides");
@@ -419,26 +422,20 @@ int check_planes_args(const w2xc_model *m, int up, int n_in_planes, const void *
 }
 
 // nimg planes of one size (w2xc_convert_batch*).  The plan is that of ONE image, exactly as the single-plane device call makes it.  Where the batched chain
-// applies (batch_eligible), a sub-batch of k images is one launch per layer: the descriptor of every launch is the single-image one (same regions, offsets,
-// wino_py, clamps, strides), and the batch kernels add image x stride to their scalar bases -- input planes, the k per-image blocks of the two workspaces,
-// output planes.  Everything else runs the single-image launch sequence per image on the same stream (no host synchronisation in between).
-int run_batch(w2xc_model *m, DevCtx *c, int nimg, int up, const float *d_in, long long in_ps, size_t in_rs, int w, int h, float *d_out, long long out_ps,
-              size_t out_rs, hipStream_t st, const w2xc_opts &o_in, int max_sub)
+// applies (batch_eligible), a sub-batch of k images is run_band on ONE batched band [0, H): one launch per layer, the descriptor of every launch the
+// single-image one (same regions, offsets, wino_py, clamps, strides), and the batch kernels add image x stride (Band::launch) to their scalar bases -- input
+// planes, the k per-image blocks of the two workspaces, output planes.  Everything else runs the single-image launch sequence per image on the same stream
+// (no host synchronisation in between).
+int run_batch(w2xc_model *m, DevCtx *c, int nimg, int up, PlanesIn in, int w, int h, PlanesOut out, hipStream_t st, const w2xc_opts &o_in, int max_sub)
 {
     const int W = w << up, H = h << up;
     RowPlan P;
-    {
-        int rc = plan_rows(m, o_in, W, H, 0, 0, H, H, 1, false, &P);
-        if (rc) return rc;
-    }
+    if (int rc = plan_rows(m, o_in, W, H, 0, 0, H, H, 1, false, &P)) return rc;
     if (!batch_eligible(m, P)) {
-        for (int i = 0; i < nimg; i++) {
-            int rc = run_rows(m, c, d_in + (size_t)i * in_ps, in_rs, H, 0, W, 0, H, d_out + (size_t)i * out_ps, out_rs, st, o_in, up, 1, 0, 0, nullptr, H);
-            if (rc) return rc;
-        }
+        for (int i = 0; i < nimg; i++)
+            if (int rc = run_rows(m, c, RowsCall::whole(in.plane(i), 1, W, H, out.plane(i), up), st, o_in)) return rc;
         return W2XC_OK;
     }
-    const int n = P.n;
     size_t img_f[2];
     batch_ws_floats(P, img_f);
     int sub = batch_sub_size(P.o, img_f);
@@ -448,27 +445,12 @@ int run_batch(w2xc_model *m, DevCtx *c, int nimg, int up, const float *d_in, lon
         if (img_f[i]) { int rc = c->ws[i].reserve(img_f[i] * (size_t)sub * sizeof(float), "the activation workspace"); if (rc) return rc; }
 
     for (int b0 = 0; b0 < nimg; b0 += sub) {
-        W2xcBatchDesc bd;
-        memset(&bd, 0, sizeof bd);
-        bd.batch = std::min(sub, nimg - b0);
-        // run_band's layer loop for the one band [0, H), no hooks, on the fp32 chain batch_eligible accepted: every launch is the plain one.  What is the
-        // batch's own: the image strides -- input planes, the per-image blocks of the two workspaces, output planes
-        LayerSrc src, next;
-        src.p = d_in + (size_t)b0 * in_ps; src.rs = (long long)in_rs;
-        src.h = H; src.w = W;
-        const LayerDst dst = {d_out + (size_t)b0 * out_ps, (long long)out_rs, 0, {c->ws[0].as<float>(), c->ws[1].as<float>()}};
-        long long src_bs = in_ps;   // (layer 1 is fused away: the first launch reads the input planes)
-        W2xcConvDesc first_d, d;
-        memset(&first_d, 0, sizeof first_d);
-        for (int k = 1; k <= n; k++, src = next) {
-            const W2xcKernelKind kind = layer_desc(m, P, k, 0, H, up, src, dst, first_d, &d, &next);
-            if (kind == W2XC_K_FUSED_AWAY) continue;
-            bd.in_bs = src_bs;
-            bd.out_bs = k == n ? out_ps : (long long)img_f[(k - 1) & 1];   // (batch_eligible: the gather writes the output planes)
-            int rc = launch_layer(c, m, k - 1, kind, d, st, P.o, &bd);
-            if (rc) return rc;
-            src_bs = bd.out_bs;
-        }
+        Band B = {m, c, P, nullptr, st, out.p + (size_t)b0 * out.ps, (long long)out.rs, 0, 0, H, H, 0, 0};
+        B.batch = std::min(sub, nimg - b0); B.in_bs = in.ps; B.out_bs = out.ps;
+        B.img_f[0] = img_f[0]; B.img_f[1] = img_f[1];
+        LayerSrc view;   // (as run_rows makes it: the W x H plane, also where up = 1)
+        view.p = in.p + (size_t)b0 * in.ps; view.rs = (long long)in.rs; view.h = H; view.w = W;
+        if (int rc = run_band(B, view, up)) return rc;
     }
     return W2XC_OK;
 }
@@ -479,29 +461,22 @@ int check_batch_args(const w2xc_model *m, int nimg, int nn2x, int w, int h, size
     if (!m) return fail(W2XC_ERR_ARG, "null model");
     if (nimg < 1) return fail(W2XC_ERR_ARG, "batch of %d planes", nimg);
     if (nn2x != 0 && nn2x != 1) return fail(W2XC_ERR_ARG, "nn2x must be 0 or 1");
-    if (w <= 0 || h <= 0) return fail(W2XC_ERR_ARG, "plane size must be positive (got %dx%d)", w, h);
-    if (w > (1 << 28) || h > (1 << 28)) return fail(W2XC_ERR_ARG, "plane too large");
-    if (in_stride < (size_t)w * 4 || out_stride < ((size_t)w << nn2x) * 4 || (in_stride & 3) || (out_stride & 3))
-        return fail(W2XC_ERR_ARG, "row strides must be multiples of 4 bytes and >= 4*width");
-    return W2XC_OK;
+    if (int rc = check_plane_size(w, h, true)) return rc;
+    return check_row_strides(in_stride, w, out_stride, (size_t)w << nn2x);
 }
 
 // everything w2xc_convert_batch_device refuses
 int check_batch_device_args(const w2xc_model *m, int n, int nn2x, const void *d_in, size_t in_plane_stride_bytes, size_t in_stride_bytes, int w, int h,
                             const void *d_out, size_t out_plane_stride_bytes, size_t out_stride_bytes)
 {
-    int rc = check_batch_args(m, n, nn2x, w, h, in_stride_bytes, out_stride_bytes);
-    if (rc) return rc;
+    if (int rc = check_batch_args(m, n, nn2x, w, h, in_stride_bytes, out_stride_bytes)) return rc;
     if (!d_in || !d_out) return fail(W2XC_ERR_ARG, "null argument");
     if ((in_plane_stride_bytes & 3) || (out_plane_stride_bytes & 3)) return fail(W2XC_ERR_ARG, "plane strides must be multiples of 4 bytes");
     const int H = h << nn2x, W = w << nn2x;
-    const size_t in_ext = (size_t)(h - 1) * in_stride_bytes + (size_t)w * 4, out_ext = (size_t)(H - 1) * out_stride_bytes + (size_t)W * 4;
+    const size_t in_ext = image_extent(h, in_stride_bytes, w, 4), out_ext = image_extent(H, out_stride_bytes, W, 4);
     if (n > 1 && out_plane_stride_bytes < out_ext) return fail(W2XC_ERR_ARG, "output planes overlap each other (plane stride %zu < %zu bytes)", out_plane_stride_bytes, out_ext);
-    {
-        const uintptr_t i0 = (uintptr_t)d_in, i1 = i0 + (size_t)(n - 1) * in_plane_stride_bytes + in_ext;
-        const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (size_t)(n - 1) * out_plane_stride_bytes + out_ext;
-        if (i0 < o1 && o0 < i1) return fail(W2XC_ERR_ARG, "output planes overlap the input planes");
-    }
+    if (ranges_overlap(d_in, (size_t)(n - 1) * in_plane_stride_bytes + in_ext, d_out, (size_t)(n - 1) * out_plane_stride_bytes + out_ext))
+        return fail(W2XC_ERR_ARG, "output planes overlap the input planes");
     return check_batch_model(m);
 }
 
@@ -523,18 +498,12 @@ int check_batch_overlap(std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, i
 
 using namespace w2xc_eng;
 
-// what every device entry point does behind its argument checks: pick the device, make it current, take the (model, device) context and its lock, call
-template <class F> static int with_ctx(w2xc_model *m, const w2xc_opts &o, F &&call)
+// what every device entry point does behind its argument checks: open the model's locked context on the call's device (LockedCtx), then enqueue
+static int rows_on_device(w2xc_model *m, const RowsCall &r, void *hip_stream, const w2xc_opts &o)
 {
-    int dev = o.device;
-    if (dev < 0) HIP_TRY(hipGetDevice(&dev));
-    DeviceGuard guard(dev);
-    if (!guard.ok) return fail(W2XC_ERR_HIP, "cannot select HIP device %d", dev);
-    DevCtx *c = nullptr;
-    int rc = get_ctx(m, dev, &c);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    return call(c);
+    LockedCtx lc;
+    if (int rc = lc.open(nullptr, m, o.device)) return rc;
+    return run_rows(m, lc.cs, r, (hipStream_t)hip_stream, o);
 }
 
 extern "C" {
@@ -543,18 +512,16 @@ extern "C" {
 int w2xc_convert_plane_device(w2xc_model *m, const float *d_in, size_t in_stride_bytes, int w, int h, float *d_out,
                               size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts)
 try {
-    int rc = check_plane_args(m, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes);
-    if (rc) return rc;
+    if (int rc = check_plane_args(m, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes)) return rc;
     const w2xc_opts o = resolve_opts(opts);
-    return with_ctx(m, o, [&](DevCtx *c) { return run_rows(m, c, d_in, in_stride_bytes / 4, h, 0, w, 0, h, d_out, out_stride_bytes / 4, (hipStream_t)hip_stream, o, 0, 1, 0, 0, nullptr, h); });
+    return rows_on_device(m, RowsCall::whole({d_in, in_stride_bytes / 4, 0}, 1, w, h, {d_out, out_stride_bytes / 4, 0}, 0), hip_stream, o);
 } W2XC_CATCH_ALL
 
 int w2xc_convert_rows_device(w2xc_model *m, const float *d_view, size_t view_stride_bytes, int view_h, int view_y0, int w,
                              int plane_h, int row_begin, int row_end, float *d_out, size_t out_stride_bytes,
                              void *hip_stream, const w2xc_opts *opts)
 try {
-    int rc = check_plane_args(m, d_view, view_stride_bytes, w, view_h, d_out, out_stride_bytes);
-    if (rc) return rc;
+    if (int rc = check_plane_args(m, d_view, view_stride_bytes, w, view_h, d_out, out_stride_bytes)) return rc;
     const int n = (int)m->layers.size();
     if (plane_h <= 0 || row_begin < 0 || row_end > plane_h || row_begin >= row_end)
         return fail(W2XC_ERR_ARG, "bad row range [%d,%d) for a %d-row plane", row_begin, row_end, plane_h);
@@ -567,8 +534,9 @@ try {
     // them lies outside [row_begin, row_end), so clamping there never reaches a kept output row
     // (conv3x3_wino4, the F(4x4) kernel: a view with 4 n halo rows gets its banding-invariant geometry; on a narrower one
     //  W2XC_KERNEL_AUTO runs the F(2x2) kernels: run_rows)
-    return with_ctx(m, o, [&](DevCtx *c) { return run_rows(m, c, d_view, view_stride_bytes / 4, view_h, view_y0, w, row_begin, row_end, d_out,
-                    out_stride_bytes / 4, (hipStream_t)hip_stream, o, 0, 1, 0, 0, nullptr, plane_h); });
+    RowsCall r = RowsCall::whole({d_view, view_stride_bytes / 4, 0}, 1, w, plane_h, {d_out, out_stride_bytes / 4, 0}, 0);
+    r.view_h = view_h; r.view_y0 = view_y0; r.ra = row_begin; r.rb = row_end;
+    return rows_on_device(m, r, hip_stream, o);
 } W2XC_CATCH_ALL
 
 // w2xc_convert_planes_device (up = 0) and its nearest-2x form (up = 1: (w, h) is the SOURCE size, the output planes are 2w x 2h)
@@ -579,10 +547,8 @@ static int convert_planes(w2xc_model *m, int up, int n_in_planes, const float *d
     const w2xc_opts o = resolve_opts(opts);
     if (int rc = check_planes_args(m, up, n_in_planes, d_in, in_plane_stride_bytes, in_stride_bytes, w, h, d_out, out_plane_stride_bytes, out_stride_bytes, o))
         return rc;
-    const long long in_cs = (long long)(in_plane_stride_bytes / 4), out_cs = (long long)(out_plane_stride_bytes / 4);
-    return with_ctx(m, o, [&](DevCtx *c) {
-        return run_rows(m, c, d_in, in_stride_bytes / 4, H, 0, W, 0, H, d_out, out_stride_bytes / 4, (hipStream_t)hip_stream, o, up, n_in_planes, in_cs, out_cs, nullptr, H);
-    });
+    const PlanesIn in{d_in, in_stride_bytes / 4, (long long)(in_plane_stride_bytes / 4)};
+    return rows_on_device(m, RowsCall::whole(in, n_in_planes, W, H, {d_out, out_stride_bytes / 4, (long long)(out_plane_stride_bytes / 4)}, up), hip_stream, o);
 }
 
 int w2xc_convert_planes_device(w2xc_model *m, int n_in_planes, const float *d_in, size_t in_plane_stride_bytes,
@@ -602,14 +568,9 @@ try {
 int w2xc_convert_plane_nn2x_device(w2xc_model *m, const float *d_in, size_t in_stride_bytes, int w, int h, float *d_out,
                                    size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts)
 try {
-    if (!m || !d_in || !d_out) return fail(W2XC_ERR_ARG, "null argument");
-    if (w <= 0 || h <= 0) return fail(W2XC_ERR_ARG, "plane size must be positive (got %dx%d)", w, h);
-    if (in_stride_bytes < (size_t)w * 4 || out_stride_bytes < (size_t)w * 8 || (in_stride_bytes & 3) || (out_stride_bytes & 3))
-        return fail(W2XC_ERR_ARG, "row strides must be multiples of 4 bytes and >= 4*width");
+    if (int rc = check_plane_args(m, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, 1)) return rc;
     const w2xc_opts o = resolve_opts(opts);
-    return with_ctx(m, o, [&](DevCtx *c) {
-        return run_rows(m, c, d_in, in_stride_bytes / 4, 2 * h, 0, 2 * w, 0, 2 * h, d_out, out_stride_bytes / 4, (hipStream_t)hip_stream, o, 1, 1, 0, 0, nullptr, 2 * h);
-    });
+    return rows_on_device(m, RowsCall::whole({d_in, in_stride_bytes / 4, 0}, 1, 2 * w, 2 * h, {d_out, out_stride_bytes / 4, 0}, 1), hip_stream, o);
 } W2XC_CATCH_ALL
 
 // ---- batches of same-size planes -----------------------------------------------------------------
@@ -620,9 +581,9 @@ try {
     if (rc) return rc;
     const w2xc_opts o = resolve_opts(opts);
     const long long in_ps = (long long)(in_plane_stride_bytes / 4), out_ps = (long long)(out_plane_stride_bytes / 4);
-    return with_ctx(m, o, [&](DevCtx *c) {
-        return run_batch(m, c, n, nn2x, d_in, in_ps, in_stride_bytes / 4, w, h, d_out, out_ps, out_stride_bytes / 4, (hipStream_t)hip_stream, o);
-    });
+    LockedCtx lc;
+    if ((rc = lc.open(nullptr, m, o.device))) return rc;
+    return run_batch(m, lc.cs, n, nn2x, {d_in, in_stride_bytes / 4, in_ps}, w, h, {d_out, out_stride_bytes / 4, out_ps}, (hipStream_t)hip_stream, o);
 } W2XC_CATCH_ALL
 
 }  // extern "C"
