@@ -283,6 +283,58 @@ def test_image_strides_beyond_4gib(gpu, mn, msc):
         torch.cuda.empty_cache()
 
 
+def test_plane_loop_past_65535(gpu):
+    """n = 33000 images of 1 x 1 in ONE sub-batch: the cubic stage gets 2 n = 66000 planes and the shrink's linear stage 3 n = 99000, both more than the
+    65535 rows of workgroups a grid has, so the V planes of the images from 32535 on are the second trip of the kernel's plane loop.  330 distinct images
+    tiled 100 times; expected, byte for byte: the same calls on the 330 images (the regime every other test here covers), tiled.
+    One sub-batch with the default workspace_mb, nothing set: S = 16384 MiB / (the planes of every level + the uint8 image in and out, per image) is far
+    above n, and this model has no batched chain whose own rule could cap it; afterwards the context's scratch holds the planes of all n images."""
+    ms = gpu._ModelSet.from_layers(gen_model.synth_layers([1, 16, 16, 1], 31))
+    n, pf = 33000, 64                                   # pf = floats of a 1 x 1 or 2 x 2 plane, rounded up to 256 bytes
+    x330 = images(330, 1, 1, 65535)
+    x = np.tile(x330, (100, 1, 1, 1))
+    assert len(x) == n and 2 * n > 65535 and n + 65535 > 2 * n      # (U and V: a second trip of the plane loop, no third)
+    for shrink, planes in ((0.5, 4 + 3 + 3), (0.0, 4 + 3)):         # planes per image: level 0 (Y, U, V, the noise pass's Y), level 1, the shrunk level
+        per = 4 * pf * planes + 3 + 3 * (1 if shrink else 4)
+        assert (16384 << 20) // per >= n
+        want = np.tile(device_batch(gpu, x330, None, ms, 1, shrink), (100, 1, 1, 1))
+        ms.trim()
+        got = device_batch(gpu, x, None, ms, 1, shrink)
+        assert got.shape == want.shape == (n,) + final_size(1, 1, 1, shrink) + (3,)
+        bad = np.nonzero((got != want).reshape(n, -1).any(axis=1))[0]
+        assert bad.size == 0, "shrink %g: %d images differ from the 330-image call, first %s" % (shrink, bad.size, bad[:8])
+        # one sub-batch: the planes of all n images exist at once.  (The layer launch count cannot show it for this model: it has no batched chain, so its
+        # layers are launched per image whatever S is -- and for the same reason its conv scratch is one image's, a few KiB, which is what makes the
+        # scratch total a statement about the image planes: with S = n / 2 the total would be half of this bound.)
+        assert ms.fill_scratch(0, 0) >= n * 4 * pf * planes
+    # an index mix-up cannot pass: every channel of the result (channel 0 follows V, channel 2 follows U) takes many values over the 330 images, so planes
+    # taken from other images change bytes (this small model's Y is near 0, so many results share a clipped 0: not all 330 are distinct)
+    assert all(len(set(want[:330, ..., ch].ravel().tolist())) >= 16 for ch in range(3))
+
+
+def test_element_loop_past_65536_workgroups(gpu):
+    """w2xc_u8_to_yuv_device then w2xc_yuv_to_u8_device on 4100 x 4100 pixels: 16 810 000 elements, more than the 65536 x 256 a grid covers in one trip, so
+    the last 32 784 are every workgroup's second trip of the element loop.  All three planes and all bytes against the oracle -- the whole image, not
+    windows (the oracle takes well under a second) -- and exactly, as the small-image test of these two entry points compares (test_gpu_parity.py)."""
+    h = w = 4100
+    assert 65536 * 256 < h * w < 2 * 65536 * 256
+    img = images(1, h, w, 4100)[0]
+    lib = gpu.lib()
+    d_img = torch.from_numpy(img).cuda()
+    d_p = torch.full((3, h, w), float("nan"), dtype=torch.float32, device="cuda")
+    d_out = torch.full((h, w, 3), 0xAB, dtype=torch.uint8, device="cuda")
+    assert lib.w2xc_u8_to_yuv_device(d_img.data_ptr(), w * 3, w, h, d_p[0].data_ptr(), d_p[1].data_ptr(), d_p[2].data_ptr(), None) == 0
+    assert lib.w2xc_yuv_to_u8_device(d_p[0].data_ptr(), d_p[1].data_ptr(), d_p[2].data_ptr(), w, h, d_out.data_ptr(), w * 3, None) == 0
+    torch.cuda.synchronize()
+    want = orc.u8_to_yuv(img)
+    got = d_p.cpu().numpy()
+    for name, g, t in zip("YUV", got, want):
+        diff = g != t
+        assert not diff.any(), "%s: %d elements differ, first at %s" % (name, int(diff.sum()), tuple(int(i[0]) for i in np.nonzero(diff)))
+    diff = d_out.cpu().numpy() != orc.yuv_to_u8(*want)
+    assert not diff.any(), "bytes: %d differ, first at %s" % (int(diff.sum()), tuple(int(i[0]) for i in np.nonzero(diff)))
+
+
 def poisoned_runs(call, sets):
     """call() after each of the three fills of every scratch buffer of the models in `sets` on device 0: byte-identical results"""
     for _ in range(2):         # warm: every buffer this call needs exists at its final size (buffers only grow)

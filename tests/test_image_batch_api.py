@@ -159,7 +159,7 @@ def test_batch_colour_kernels_no_spill_no_scratch(w2xc):
         m = re.match(r"(\S+)\s+vgpr\s+(\d+) sgpr\s+(\d+) vspill\s+(\d+) sspill\s+(\d+) scratch\s+(\d+)", line)
         if m:
             rows[m.group(1)] = dict(vspill=int(m.group(4)), scratch=int(m.group(6)))
-    for k in ("k_u8_to_yuv_batch", "k_resize2x_cubic_batch", "k_resize_linear_batch", "k_yuv_to_u8_batch"):
+    for k in ("U8ToYuv", "Resize2xCubic", "ResizeLinear", "YuvToU8"):   # the stage names, as they stand in the mangled k_px<Stage>
         hit = [name for name in rows if k in name]
         assert len(hit) == 1, (k, sorted(rows))
         assert rows[hit[0]] == dict(vspill=0, scratch=0), (hit[0], rows[hit[0]])

@@ -258,7 +258,7 @@ def test_rgba_colour_kernels_no_spill_no_scratch(w2xc):
         m = re.match(r"(\S+)\s+vgpr\s+(\d+) sgpr\s+(\d+) vspill\s+(\d+) sspill\s+(\d+) scratch\s+(\d+)", line)
         if m:
             rows[m.group(1)] = dict(vspill=int(m.group(4)), scratch=int(m.group(6)))
-    for k in ("k_rgba_bleed_first", "k_rgba_bleed_pass", "k_alpha_to_plane", "k_alpha_to_grey", "k_merge_rgba_f32", "k_merge_rgba_u8"):
+    for k in ("RgbaBleedFirst", "RgbaBleedPass", "AlphaToPlane", "AlphaToGrey", "MergeRgbaF32", "MergeRgbaU8"):   # stage names, in the mangled k_px<Stage>
         hit = [name for name in rows if k in name]
         assert len(hit) == 1, (k, sorted(rows))
         assert rows[hit[0]] == dict(vspill=0, scratch=0), (hit[0], rows[hit[0]])

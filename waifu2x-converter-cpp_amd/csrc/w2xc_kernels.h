@@ -111,13 +111,14 @@ hipError_t w2xc_launch_repack(const float *src, long long s_rs, long long s_ps, 
 hipError_t w2xc_launch_pad_planar(const float *src, long long s_rs, long long s_ps, long long s_cs, float *dst, long long d_rs, long long d_cs,
                                   int h, int w, int c, int pad, hipStream_t stream);
 
-// N2 (w2xc_color.hip): colour front/back end and U/V bicubic of the CLI scale loop (main.cpp:74-76,144,171-172)
+// N2 (w2xc_color.hip): colour front/back end and U/V bicubic of the CLI scale loop (main.cpp:74-76,144,171-172).  One kernel per stage (k_px<Stage>): every
+// one-image launcher here is its batch launch with n = 1.
 hipError_t w2xc_launch_u8_to_yuv(const unsigned char *src, size_t stride, int w, int h, float *y, float *u, float *v, hipStream_t st);
 hipError_t w2xc_launch_yuv_to_u8(const float *y, const float *u, const float *v, int w, int h, unsigned char *dst, size_t stride, hipStream_t st);
 hipError_t w2xc_launch_resize2x_cubic(const float *src, int w, int h, float *dst, hipStream_t st);
 hipError_t w2xc_launch_resize_linear(const float *src, int sw, int sh, float *dst, int dw, int dh, hipStream_t st);
 // their batch forms (w2xc_process_image_u8_batch*), one launch for a sub-batch of n images: image i at src / dst + i * img_stride BYTES, the float planes
-// of image (plane) i at base + i * ps FLOATS.  Per output element the arithmetic of the one-image kernels (shared bodies).
+// of image (plane) i at base + i * ps FLOATS.  The image index moves only the 64-bit bases: per output element the arithmetic does not depend on n.
 hipError_t w2xc_launch_u8_to_yuv_batch(const unsigned char *src, size_t img_stride, size_t stride, int w, int h, float *y, float *u, float *v,
                                        long long ps, int n, hipStream_t st);
 hipError_t w2xc_launch_yuv_to_u8_batch(const float *y, const float *u, const float *v, long long ps, int w, int h, unsigned char *dst, size_t img_stride,
