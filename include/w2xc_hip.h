@@ -383,6 +383,29 @@ int w2xc_process_image_rgba_u8_ex_device(w2xc_model *noise_model, w2xc_model *sc
                                          void *hip_stream, const w2xc_opts *opts);
 int w2xc_process_image_rgba_u8_ex(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *in, size_t in_stride_bytes, int w, int h,
                                   unsigned char *out, size_t out_stride_bytes, int iterations, double shrink_ratio, int bleed_passes, const w2xc_opts *opts);
+/* n RGBA images of one size in ONE call (revision 0.4.1.3): what w2xc_process_image_u8_batch* is to w2xc_process_image_u8_ex*.  Nothing new is defined: the
+ * route, the bleed, the colour and the alpha are the single call's, and
+ * out[i] is BYTE-identical to w2xc_process_image_rgba_u8_ex[_device] on in[i] with the same models, iterations, shrink_ratio, bleed_passes and opts, for
+ * every option set (precisions, named kernels, fusion settings, band_rows, workspace_mb).
+ * A sub-batch of S images is ONE launch per colour stage (the bleed, alpha -> plane / grey image, the merge) and the 3-channel batch of the route around
+ * them.  Y route: the Y group of a scale pass is 2 S planes, the S Y planes and their S alpha planes, one w2xc_convert_batch_device-style pass; the noise
+ * pass runs on the S Y planes alone.  RGB route: the colour pass and the alpha pass are the RGB batch's, the single-image launch sequence per image.
+ * iterations == 0: the alpha bytes of all S images are copied, or resized by the shrink, in one launch each.  S = as many images as
+ * w2xc_opts.workspace_mb (0 = 16384 MiB) holds of the call's memory per image -- the float planes, alpha's among them, the uint8 images between the
+ * stages, the 4-byte image in and out -- on the Y route at most half the sub-batch the batched layer chain takes at the call's largest level (a Y brings
+ * its alpha), and never less than 1.  Memory grows with S, not with n.
+ * n < 1, null pointers (a null in[i] / out[i] too), row strides below 4 x width, output images that overlap each other or an input image, and everything
+ * the single RGBA call refuses return W2XC_ERR_ARG; a Y model beside an RGB one, or any other plane count, W2XC_ERR_PLANES -- all before any device is
+ * touched; without a device W2XC_ERR_HIP.
+ * Device form: image i starts i * *_image_stride_bytes after d_in / d_out (64-bit offsets, no alignment asked), on device opts->device; asynchronous on
+ * hip_stream.  Host form: sub-batches are striped over opts->device_mask through the per-device host pipeline of w2xc_process_image_u8_batch; n = 1 is
+ * the single call on the first device of the mask.  Returns when every out[i] is complete. */
+int w2xc_process_image_rgba_u8_batch_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in, size_t in_image_stride_bytes,
+                                            size_t in_stride_bytes, int w, int h, unsigned char *d_out, size_t out_image_stride_bytes, size_t out_stride_bytes,
+                                            int iterations, double shrink_ratio, int bleed_passes, void *hip_stream, const w2xc_opts *opts);
+int w2xc_process_image_rgba_u8_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes, int w, int h,
+                                     unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio, int bleed_passes,
+                                     const w2xc_opts *opts);
 /* Test-time augmentation (TTA): every CNN pass runs on the 8 flips and transposes of its input, each result is transformed back and the 8 are averaged --
  * the quality option later upstream versions of the converter have as --tta (v1 of the reference has none); 8x the CNN work.  The arithmetic is defined here:
  *   T_k, k = 0..7, on a plane x of h rows x w columns applies, in this order: the horizontal flip (x[:, ::-1]) if k & 1, the vertical flip (x[::-1, :]) if
@@ -462,7 +485,8 @@ int w2xc_rgb_to_u8_device(const float *d_c0, const float *d_c1, const float *d_c
 
 /* ... and the RGBA call's: the colour bleed alone.  `passes` (>= 0) passes of the bleed above on the w x h RGBA image d_in; d_out_rgb receives the packed
  * 3-channel image (rows out_stride_bytes >= 3 w apart, bytes behind 3 w untouched; it must not overlap d_in).  Asynchronous on hip_stream, on the current
- * device.  The call has no model: its scratch (2 bytes per pixel of the largest image so far) is one buffer per device, shared by all callers and kept until
+ * device.  Up to 16 effective passes run in one launch and need no scratch.  More run as one launch per pass, and as the call has no model, their scratch
+ * (2 bytes per pixel of the largest such image so far) is one buffer per device, shared by all callers and kept until
  * w2xc_bleed_rgba_u8_trim -- calls on different streams that may run at the same time are the caller's to order, as with the calls of one model.
  * w2xc_bleed_rgba_u8_trim waits for every device that holds such a buffer and releases it (what w2xc_model_trim is to a model's buffers). */
 int w2xc_bleed_rgba_u8_device(const unsigned char *d_in, size_t in_stride_bytes, int w, int h, int passes, unsigned char *d_out_rgb,

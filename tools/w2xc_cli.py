@@ -11,7 +11,8 @@ Extension: RGB models.  When the loaded model's first layer takes 3 planes the i
 channels in PIL's RGB order as they are (no BGR swap: that mimics what the reference feeds its Y path), all three planes through the CNN.
 Extension: transparency.  An input whose decoded image has an alpha channel with any byte below 255 (PIL modes RGBA, LA, P with transparency, ...) goes through
 w2xc_process_image_rgba_u8_ex on the route of the models -- the colour bled under the transparent pixels, alpha through the scale model -- and is written as
-RGBA.  Every other input goes exactly as before, the batch grouping included.
+RGBA; several such inputs are grouped by image size like the opaque ones, and a group of two or more is ONE w2xc_process_image_rgba_u8_batch call.  Every
+other input goes exactly as before, the batch grouping included.
 Extension: -t/--tta 1 = test-time augmentation, the --tta of later upstream versions: every model pass on the 8 flips / transposes of the image, averaged
 (w2xc_process_image_[rgb_]u8[_batch]_tta; 8x the CNN work), on both routes and for grouped inputs.  The RGBA call has no TTA form: with an input that would
 take it, --tta 1 exits with a message before anything is converted."""
@@ -73,6 +74,13 @@ def model_route(noise, scale):
         raise SystemExit("mixed model kinds: " + ", ".join("%s takes %d plane%s" % (name, nin, "" if nin == 1 else "s") for name, nin in loaded) +
                          "; use a noise model and a scale model of the same kind")
     return routes.pop() if routes else "y"
+
+
+def group_alpha(files_with_sizes, mode, noise_level, scale_ratio):
+    """The inputs that take the RGBA call, [(file, (width, height)), ...] -> ([files of the single calls], [[files of a batch call], ...]): group_inputs'
+    groups; a group of two or more is one batch call, a file alone with its size stays the single call.  Pure: no file is opened."""
+    groups = [files for _, files, _ in group_inputs(files_with_sizes, mode, noise_level, scale_ratio)]
+    return [g[0] for g in groups if len(g) == 1], [g for g in groups if len(g) > 1]
 
 
 def wants_alpha(arr):
@@ -154,9 +162,12 @@ def main(argv=None):
     else:
         prec = {"fp32": w2xc.PRECISION_FP32, "bf16": w2xc.PRECISION_BF16, "bf16x2": w2xc.PRECISION_BF16X2, "bf16x3": w2xc.PRECISION_BF16X3, "fp16x2": w2xc.PRECISION_FP16X2}[args.precision]
         opts = w2xc.make_opts(precision=prec)      # always explicit: an explicit --precision beats the W2XC_PRECISION env default
-        for f, im in zip(args.input_file, images):
-            if im.shape[2] == 4:                   # (the RGBA call has no batch form)
-                outs[f] = w2xc.process_image_rgba_u8(im, noise, scale if iterations else None, iterations, opts, shrink)
+        alpha = {f: im for f, im in zip(args.input_file, images) if im.shape[2] == 4}
+        singles, batches = group_alpha([(f, (im.shape[1], im.shape[0])) for f, im in alpha.items()], args.mode, args.noise_level, args.scale_ratio)
+        for f in singles:
+            outs[f] = w2xc.process_image_rgba_u8(alpha[f], noise, scale if iterations else None, iterations, opts, shrink)
+        for files in batches:                      # one batch call per image size
+            outs.update(zip(files, w2xc.process_image_rgba_u8_batch([alpha[f] for f in files], noise, scale if iterations else None, iterations, opts, shrink)))
         if len(opaque) == 1:
             outs[opaque[0][0]] = process(opaque[0][1], noise, scale if iterations else None, iterations, opts, shrink, **tta)
         elif opaque:

@@ -99,6 +99,8 @@ def _load():
         "w2xc_process_image_rgb_u8_batch": (ci, [vp, vp, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, ci, C.c_double, C.POINTER(Opts)]),
         "w2xc_process_image_rgba_u8_ex_device": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.c_double, ci, vp, C.POINTER(Opts)]),
         "w2xc_process_image_rgba_u8_ex": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.c_double, ci, C.POINTER(Opts)]),
+        "w2xc_process_image_rgba_u8_batch_device": (ci, [vp, vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, ci, C.c_double, ci, vp, C.POINTER(Opts)]),
+        "w2xc_process_image_rgba_u8_batch": (ci, [vp, vp, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, ci, C.c_double, ci, C.POINTER(Opts)]),
         "w2xc_process_image_u8_tta_device": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.c_double, vp, C.POINTER(Opts), ci]),
         "w2xc_process_image_u8_tta": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, C.c_double, C.POINTER(Opts), ci]),
         "w2xc_process_image_u8_batch_tta_device": (ci, [vp, vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, ci, C.c_double, vp, C.POINTER(Opts), ci]),
@@ -686,11 +688,13 @@ def process_image_u8_batch(imgs, noise=None, scale=None, iterations=0, opts=None
     return _image_batch(entry, "process_image_u8_batch", imgs, noise, scale, iterations, opts, shrink_ratio, out, tail)
 
 
-def _image_batch(entry, who, imgs, noise, scale, iterations, opts, shrink_ratio, out, tail=()):
-    """the host image batch of Y models (process_image_u8_batch) and of RGB models (process_image_rgb_u8_batch): same arguments, same checks"""
+def _image_batch(entry, who, imgs, noise, scale, iterations, opts, shrink_ratio, out, tail=(), channels=3, extra=()):
+    """the host image batch of Y models (process_image_u8_batch), of RGB models (process_image_rgb_u8_batch) and of RGBA images (process_image_rgba_u8_batch,
+    channels = 4): same arguments, same checks; `extra` = the entry's arguments between shrink_ratio and opts, `tail` those behind opts"""
+    ch = channels
     if isinstance(imgs, np.ndarray):
         if imgs.ndim != 4:
-            raise ValueError("%s wants an (n, h, w, 3) array or a sequence of h x w x 3 images" % who)
+            raise ValueError("%s wants an (n, h, w, %d) array or a sequence of h x w x %d images" % (who, ch, ch))
         imgs = [imgs[i] for i in range(imgs.shape[0])]
     srcs = [np.asarray(a) for a in imgs]
     if not srcs:
@@ -698,23 +702,23 @@ def _image_batch(entry, who, imgs, noise, scale, iterations, opts, shrink_ratio,
     for a in srcs:
         if a.dtype != np.uint8:
             raise ValueError("%s wants uint8 images (got %s)" % (who, a.dtype))
-        if a.ndim != 3 or a.shape[2] != 3:
-            raise ValueError("%s wants h x w x 3 images (got shape %r)" % (who, a.shape))
+        if a.ndim != 3 or a.shape[2] != ch:
+            raise ValueError("%s wants h x w x %d images (got shape %r)" % (who, ch, a.shape))
     h, w, _ = srcs[0].shape
-    if any(a.shape != (h, w, 3) for a in srcs):
+    if any(a.shape != (h, w, ch) for a in srcs):
         raise ValueError("%s: every image must have the same size (group images by size)" % who)
-    if any(a.strides[1:] != (3, 1) for a in srcs) or len({a.strides[0] for a in srcs}) != 1:
+    if any(a.strides[1:] != (ch, 1) for a in srcs) or len({a.strides[0] for a in srcs}) != 1:
         srcs = [np.ascontiguousarray(a) for a in srcs]
     n = len(srcs)
     fw, fh = _final_size(w, h, iterations, shrink_ratio)
     if out is None:
-        out = np.empty((n, max(fh, 0), max(fw, 0), 3), np.uint8)
-    elif not isinstance(out, np.ndarray) or out.shape != (n, fh, fw, 3) or out.dtype != np.uint8 or out.strides[2:] != (3, 1):
-        raise ValueError("%s: `out` must be a uint8 (n, H, W, 3) array with contiguous rows" % who)
+        out = np.empty((n, max(fh, 0), max(fw, 0), ch), np.uint8)
+    elif not isinstance(out, np.ndarray) or out.shape != (n, fh, fw, ch) or out.dtype != np.uint8 or out.strides[2:] != (ch, 1):
+        raise ValueError("%s: `out` must be a uint8 (n, H, W, %d) array with contiguous rows" % (who, ch))
     ip = (C.c_void_p * n)(*[a.ctypes.data for a in srcs])
     op = (C.c_void_p * n)(*[out[i].ctypes.data for i in range(n)])
     _check(entry(*_handles(noise, scale), n, ip, srcs[0].strides[0], w, h,
-                 op, out.strides[1], iterations, float(shrink_ratio), C.byref(opts) if opts is not None else None, *tail))
+                 op, out.strides[1], iterations, float(shrink_ratio), *extra, C.byref(opts) if opts is not None else None, *tail))
     return out
 
 
@@ -804,6 +808,23 @@ def process_image_rgba_u8_device(d_in, in_stride_bytes, w, h, d_out, out_stride_
     _check(_lib.w2xc_process_image_rgba_u8_ex_device(*_handles(noise, scale), C.c_void_p(d_in), in_stride_bytes, w, h,
                                                      C.c_void_p(d_out), out_stride_bytes, iterations, float(shrink_ratio), int(bleed_passes),
                                                      C.c_void_p(stream), C.byref(opts) if opts is not None else None))
+
+
+def process_image_rgba_u8_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, bleed_passes=-1, out=None):
+    """n RGBA images of one size in one call (w2xc_process_image_rgba_u8_batch): `imgs` is an (n, h, w, 4) uint8 array or a sequence of equal-shape
+    (h, w, 4) uint8 arrays; returns an (n, H, W, 4) uint8 array (or fills `out`, such an array).  Image i is byte-identical to
+    process_image_rgba_u8(imgs[i], ...) with the same arguments."""
+    return _image_batch(_lib.w2xc_process_image_rgba_u8_batch, "process_image_rgba_u8_batch", imgs, noise, scale, iterations, opts, shrink_ratio, out,
+                        channels=4, extra=(int(bleed_passes),))
+
+
+def process_image_rgba_u8_batch_device(n, d_in, in_image_stride_bytes, in_stride_bytes, w, h, d_out, out_image_stride_bytes, out_stride_bytes,
+                                       noise=None, scale=None, iterations=0, shrink_ratio=0.0, bleed_passes=-1, stream=0, opts=None):
+    """Device-pointer batch of RGBA images (w2xc_process_image_rgba_u8_batch_device): n images of w x h x 4 uint8 at d_in + i * in_image_stride_bytes, the
+    outputs at d_out + i * out_image_stride_bytes.  Asynchronous on `stream`."""
+    _check(_lib.w2xc_process_image_rgba_u8_batch_device(*_handles(noise, scale), n, C.c_void_p(d_in), in_image_stride_bytes, in_stride_bytes, w, h,
+                                                        C.c_void_p(d_out), out_image_stride_bytes, out_stride_bytes, iterations, float(shrink_ratio),
+                                                        int(bleed_passes), C.c_void_p(stream), C.byref(opts) if opts is not None else None))
 
 
 def bleed_rgba_u8_device(d_in, in_stride_bytes, w, h, passes, d_out_rgb, out_stride_bytes, stream=0):

@@ -8,25 +8,20 @@
 #include "w2xc_kernels.h"
 
 // blockIdx.y strides over the n images / planes (more than 65535 take further trips), blockIdx.x x 256 threads over the `total` elements of each.
-// ONE_IMAGE: the stage has no batch form and is launched with n = 1 on one row of workgroups, so the image loop ends after its first trip -- said at compile
-// time, because a loop nest the compiler has to carry costs these small kernels 5-6 VGPRs and measurable time (profiles/color_stage_resources.txt).
-template <class Stage, bool ONE_IMAGE> __global__ void __launch_bounds__(256) k_px(Stage s, long long total, int n)
+// (Every stage has a batch form: the register cost of the loop nest for the stages that once ran one image only is in profiles/color_stage_resources.txt.)
+template <class Stage> __global__ void __launch_bounds__(256) k_px(Stage s, long long total, int n)
 {
-    for (int img = blockIdx.y; img < n; img += gridDim.y) {
+    for (int img = blockIdx.y; img < n; img += gridDim.y)
         for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) s(img, q);
-        if (ONE_IMAGE) break;
-    }
 }
 
-template <bool ONE_IMAGE = false, class Stage> static hipError_t launch_px(const Stage &s, long long total, int n, hipStream_t st)
+template <class Stage> static hipError_t launch_px(const Stage &s, long long total, int n, hipStream_t st)
 {
     const long long b = (total + 255) / 256;
     const dim3 grid((unsigned)(b > 65536 ? 65536 : (b < 1 ? 1 : b)), (unsigned)(n > 65535 ? 65535 : n));
-    hipLaunchKernelGGL((k_px<Stage, ONE_IMAGE>), grid, dim3(256), 0, st, s, total, n);
+    hipLaunchKernelGGL((k_px<Stage>), grid, dim3(256), 0, st, s, total, n);
     return hipGetLastError();
 }
-// a stage that has no batch form
-template <class Stage> static hipError_t launch_px(const Stage &s, long long total, hipStream_t st) { return launch_px<true>(s, total, 1, st); }
 
 static __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
@@ -266,12 +261,14 @@ hipError_t w2xc_launch_resize_linear(const float *src, int sw, int sh, float *ds
     return w2xc_launch_resize_linear_batch(src, src, 1, 0, sw, sh, dst, 0, dw, dh, 1, st);
 }
 
-// ---- RGBA images (w2xc_process_image_rgba_u8*; no counterpart in v1 of the reference): one-image stages, launched with n = 1 ----
+// ---- RGBA images (w2xc_process_image_rgba_u8*; no counterpart in v1 of the reference): n images per launch, one image is n = 1 ----
 // Colour bleed: a transparent pixel (alpha == 0) beside opaque ones takes the rounded mean of its opaque 3x3 neighbours, (2 sum + n) / (2 n) per channel,
 // and counts as opaque in the next pass; P passes carry the colour P pixels into the transparent region.  The passes are defined as a ping-pong (a pass
 // reads only what the pass before left); they run IN PLACE on the packed 3-channel image, exactly, because a pixel filled in pass k (its stamp: 0 = opaque in
 // the source, k = filled in pass k, BLEED_FAR = not reached) reads only neighbours whose stamp is below k, and those are written by no thread of pass k; a
 // neighbour's stamp that is being set to k reads as BLEED_FAR or as k, neither of them below k.
+// Two forms: 2 to W2XC_BLEED_TILED_MAX passes run in ONE launch, a workgroup per tile with the passes between LDS words (k_bleed_tiled); more passes are the
+// chain RgbaBleedFirst, RgbaBleedPass x (P - 1) on a 16-bit stamp plane in memory, and one pass is RgbaBleedFirst alone, without stamps.  The bytes are the same.
 #define BLEED_FAR 0xFFFFu
 
 // which neighbours count: the opaque pixels of the RGBA source (pass 1), the pixels stamped below k (pass k)
@@ -308,99 +305,221 @@ template <class Counts> static __device__ __forceinline__ BleedSum bleed_sum(con
     return b;
 }
 
-// writes pixel q of the packed image, its stamp, and -- with first_pass -- pass 1, read from the RGBA source's own alpha
+// writes pixel q of the packed image, its stamp (where there is a stamp plane: the plain repack, first_pass = 0, needs none), and -- with first_pass --
+// pass 1, read from the RGBA source's own alpha.  Image i: src + i * img_stride, dst + i * dst_img_stride bytes, stamp + i * stamp_stride words
 struct RgbaBleedFirst {
     const unsigned char *src;
-    long long stride;
+    long long img_stride, stride;
     int w, h, first_pass;
     unsigned char *dst;
-    long long dst_stride;
+    long long dst_img_stride, dst_stride;
     unsigned short *stamp;
-    __device__ __forceinline__ void operator()(int, long long q) const
+    long long stamp_stride;
+    __device__ __forceinline__ void operator()(int img, long long q) const
     {
         const RowCol at = row_col(q, w);
-        const unsigned char *p = src + at.r * stride + (long long)at.c * 4;
+        const unsigned char *s = src + img * img_stride;
+        const unsigned char *p = s + at.r * stride + (long long)at.c * 4;
         int o0 = p[0], o1 = p[1], o2 = p[2];
-        unsigned s = p[3] ? 0u : BLEED_FAR;
-        if (s && first_pass) {
-            const BleedSum b = bleed_sum(src, stride, 4, w, h, at.r, at.c, AlphaSet{src, stride});
-            if (b.n) { o0 = b.mean(b.s0); o1 = b.mean(b.s1); o2 = b.mean(b.s2); s = 1u; }
+        unsigned st = p[3] ? 0u : BLEED_FAR;
+        if (st && first_pass) {
+            const BleedSum b = bleed_sum(s, stride, 4, w, h, at.r, at.c, AlphaSet{s, stride});
+            if (b.n) { o0 = b.mean(b.s0); o1 = b.mean(b.s1); o2 = b.mean(b.s2); st = 1u; }
         }
-        unsigned char *d = dst + at.r * dst_stride + (long long)at.c * 3;
+        unsigned char *d = dst + img * dst_img_stride + at.r * dst_stride + (long long)at.c * 3;
         d[0] = (unsigned char)o0; d[1] = (unsigned char)o1; d[2] = (unsigned char)o2;
-        stamp[q] = (unsigned short)s;
+        if (stamp) stamp[img * stamp_stride + q] = (unsigned short)st;
     }
 };
 
 // pass k >= 2, in place (see above)
 struct RgbaBleedPass {
     unsigned char *img;
-    long long stride;
+    long long img_stride, stride;
     int w, h;
     unsigned k;
     unsigned short *stamp;
-    __device__ __forceinline__ void operator()(int, long long q) const
+    long long stamp_stride;
+    __device__ __forceinline__ void operator()(int i, long long q) const
     {
-        if (stamp[q] != BLEED_FAR) return;
+        unsigned short *sp = stamp + i * stamp_stride;
+        if (sp[q] != BLEED_FAR) return;
+        unsigned char *im = img + i * img_stride;
         const RowCol at = row_col(q, w);
-        const BleedSum b = bleed_sum(img, stride, 3, w, h, at.r, at.c, StampBelow{stamp, w, k});
+        const BleedSum b = bleed_sum(im, stride, 3, w, h, at.r, at.c, StampBelow{sp, w, k});
         if (!b.n) return;
-        unsigned char *d = img + at.r * stride + (long long)at.c * 3;
+        unsigned char *d = im + at.r * stride + (long long)at.c * 3;
         d[0] = (unsigned char)b.mean(b.s0);
         d[1] = (unsigned char)b.mean(b.s1);
         d[2] = (unsigned char)b.mean(b.s2);
-        stamp[q] = (unsigned short)k;
+        sp[q] = (unsigned short)k;
     }
 };
-// d_in -> the packed 3-channel image dst after `passes` bleed passes (<= 65534); stamp = w * h 16-bit words of scratch
-hipError_t w2xc_launch_rgba_bleed(const unsigned char *src, size_t stride, int w, int h, int passes, unsigned char *dst, size_t dst_stride, unsigned short *stamp,
-                                  hipStream_t st)
+
+// The tiled form: all P <= BLEED_L passes of one BLEED_T x BLEED_T tile of one image in one workgroup.  The tile and a halo of P pixels live in LDS as one
+// 32-bit word per pixel -- the three colour bytes and, on top, an 8-bit stamp: 0 = opaque in the source, k = filled in pass k, TILE_FAR = not reached,
+// TILE_OUT = outside the image (never a neighbour, never filled) -- in rows of BLEED_R words, so the lanes of a wave read consecutive banks.
+// The halo suffices: a pixel filled in pass k depends only on pixels within Chebyshev distance k, so a region pixel at distance d from the tile has to be
+// right through pass P - d only, and its (P - d)-neighbourhood lies inside the region: pass k covers the rows and columns [k, R - k) of the region's R =
+// T + 2 P, and reads [k - 1, R - k + 1).  In place for the reason above, between LDS words: a pass reads only neighbours stamped below k, which no thread of
+// pass k writes, and a word that is being written reads as the old one (TILE_FAR) or the new one (k), neither below k.
+// A pass that fills nothing in its part of the region ends the tile's passes -- then no later pass can fill anything there (a pixel still TILE_FAR has no
+// neighbour stamped below k, and none was stamped k) -- and so does a tile without a transparent pixel; both are decisions of the whole workgroup.
+#define BLEED_T 32
+#define BLEED_L W2XC_BLEED_TILED_MAX
+#define BLEED_R (BLEED_T + 2 * BLEED_L)
+#define TILE_FAR 0xFEu
+#define TILE_OUT 0xFFu
+static_assert(BLEED_L >= 14 && BLEED_L <= 253 && BLEED_R == 64 && BLEED_R * BLEED_R * 4 <= 64 * 1024, "the tile region: 64 x 64 words, 256 threads = 4 rows");
+
+// BleedSum::mean, (2 s + n) / (2 n), for n = 1..8 neighbours and s <= 255 n without a division: x / d = (x * ceil(2^16 / d)) >> 16 exactly while x * (d ceil(2^16 / d)
+// - 2^16) < 2^16, and x <= 4088, d <= 16 gives at most 4088 * 15.  The eight multipliers, 16 bits each.
+static __device__ __forceinline__ unsigned tile_mean(unsigned s, unsigned n)
 {
+    const unsigned long long m = n <= 4 ? 0x20002aab40008000ull : 0x1000124a1556199aull;
+    return ((2 * s + n) * ((unsigned)(m >> (16 * ((n - 1) & 3))) & 0xFFFFu)) >> 16;
+}
+
+// blockIdx.x strides over the tiles of an image, blockIdx.y over the n images (k_px's loops); thread t = column t & 63 of the region, in rows that depend on t >> 6
+__global__ void __launch_bounds__(256) k_bleed_tiled(const unsigned char *src, long long img_stride, long long stride, int w, int h, int passes,
+                                                     unsigned char *dst, long long dst_img_stride, long long dst_stride, int tiles_x, long long tiles, int n)
+{
+    __shared__ unsigned px[BLEED_R * BLEED_R];
+    __shared__ int live[BLEED_L + 1];   // [0]: the tile holds a transparent pixel; [k]: pass k filled a pixel
+    const int P = passes, R = BLEED_T + 2 * P;
+    const int tx = threadIdx.x & (BLEED_R - 1), ty = threadIdx.x >> 6;
+    for (int img = blockIdx.y; img < n; img += gridDim.y) {
+        const unsigned char *s = src + img * img_stride;
+        unsigned char *d = dst + img * dst_img_stride;
+        const bool words = ((reinterpret_cast<unsigned long long>(s) | (unsigned long long)stride) & 3) == 0;   // (uniform: 4-byte pixels as one load)
+        for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+            const int y0 = (int)(tile / tiles_x) * BLEED_T, x0 = (int)(tile % tiles_x) * BLEED_T;
+            if (threadIdx.x <= BLEED_L) live[threadIdx.x] = 0;
+            __syncthreads();   // (also: the tile before has left the LDS words)
+            const int gx = x0 - P + tx;
+            if (tx < R) for (int ry = ty; ry < R; ry += 4) {
+                const int gy = y0 - P + ry;
+                unsigned v = TILE_OUT << 24;
+                if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
+                    const unsigned char *p = s + gy * stride + (long long)gx * 4;
+                    if (words) v = *reinterpret_cast<const unsigned *>(p);
+                    else v = (unsigned)p[0] | (unsigned)p[1] << 8 | (unsigned)p[2] << 16 | (unsigned)p[3] << 24;
+                    v = (v & 0xFFFFFFu) | (v >> 24 ? 0u : TILE_FAR << 24);
+                    if (v >> 24 && tx >= P && tx < P + BLEED_T && ry >= P && ry < P + BLEED_T) live[0] = 1;
+                }
+                px[ry * BLEED_R + tx] = v;
+            }
+            __syncthreads();
+            if (live[0]) for (int k = 1; k <= P; k++) {
+                // a thread walks its column down a quarter of the pass's rows with the 3 x 3 window in registers: three words a row, and the row below is
+                // on its way while this one is summed.  A word read before another thread restamped it reads as TILE_FAR: not below k either way.
+                const int rows = (R - 2 * k + 3) >> 2, r0 = k + ty * rows, r1 = r0 + rows < R - k ? r0 + rows : R - k;
+                if (tx >= k && tx < R - k && r0 < r1) {
+                    const unsigned *col = px + tx;
+                    unsigned a0 = col[(r0 - 1) * BLEED_R - 1], a1 = col[(r0 - 1) * BLEED_R], a2 = col[(r0 - 1) * BLEED_R + 1];
+                    unsigned b0 = col[r0 * BLEED_R - 1], b1 = col[r0 * BLEED_R], b2 = col[r0 * BLEED_R + 1];
+                    for (int ry = r0; ry < r1; ry++) {
+                        const unsigned c0 = col[(ry + 1) * BLEED_R - 1], c1 = col[(ry + 1) * BLEED_R], c2 = col[(ry + 1) * BLEED_R + 1];
+                        if (b1 >> 24 == TILE_FAR) {
+                            const unsigned nb[8] = {a0, a1, a2, b0, b2, c0, c1, c2};
+                            unsigned cnt = 0;
+#pragma unroll
+                            for (int j = 0; j < 8; j++) cnt += nb[j] >> 24 < (unsigned)k ? 1u : 0u;
+                            if (cnt) {   // (on this pass's front)
+                                unsigned s0 = 0, s1 = 0, s2 = 0;
+#pragma unroll
+                                for (int j = 0; j < 8; j++) {
+                                    const unsigned v = nb[j] >> 24 < (unsigned)k ? nb[j] : 0u;
+                                    s0 += v & 255; s1 += v >> 8 & 255; s2 += v >> 16 & 255;
+                                }
+                                px[ry * BLEED_R + tx] = tile_mean(s0, cnt) | tile_mean(s1, cnt) << 8 | tile_mean(s2, cnt) << 16 | (unsigned)k << 24;
+                                live[k] = 1;
+                            }
+                        }
+                        a0 = b0; a1 = b1; a2 = b2; b0 = c0; b1 = c1; b2 = c2;
+                    }
+                }
+                __syncthreads();
+                if (!live[k]) break;
+            }
+            // the tile's pixels: 8 rows of 32 per trip
+            const int cx = threadIdx.x & (BLEED_T - 1);
+            if (x0 + cx < w) for (int cy = threadIdx.x >> 5; cy < BLEED_T && y0 + cy < h; cy += 8) {
+                const unsigned v = px[(P + cy) * BLEED_R + P + cx];
+                unsigned char *o = d + (y0 + cy) * dst_stride + (long long)(x0 + cx) * 3;
+                o[0] = (unsigned char)v; o[1] = (unsigned char)(v >> 8); o[2] = (unsigned char)(v >> 16);
+            }
+        }
+    }
+}
+
+// n RGBA images (image i at src + i * img_stride bytes) -> the packed 3-channel images dst + i * dst_img_stride after `passes` bleed passes (<= 65534).
+// w2xc_bleed_stamps(passes): stamp = n planes of w * h 16-bit words of scratch, stamp_stride words apart; otherwise no stamp is read or written.
+hipError_t w2xc_launch_rgba_bleed(const unsigned char *src, size_t img_stride, size_t stride, int w, int h, int passes, unsigned char *dst, size_t dst_img_stride,
+                                  size_t dst_stride, unsigned short *stamp, size_t stamp_stride, int n, hipStream_t st)
+{
+    const long long total = (long long)w * h;
+    if (passes <= 1)   // the plain repack; one pass, which reads the source alone: already one launch, and without LDS and barriers the faster one
+        return launch_px(RgbaBleedFirst{src, (long long)img_stride, (long long)stride, w, h, passes, dst, (long long)dst_img_stride, (long long)dst_stride, nullptr, 0}, total, n, st);
+    if (passes <= W2XC_BLEED_TILED_MAX) {
+        const int tiles_x = (w + BLEED_T - 1) / BLEED_T;
+        const long long tiles = (long long)tiles_x * ((h + BLEED_T - 1) / BLEED_T);
+        const dim3 grid((unsigned)(tiles > (1 << 20) ? (1 << 20) : tiles), (unsigned)(n > 65535 ? 65535 : n));
+        hipLaunchKernelGGL(k_bleed_tiled, grid, dim3(256), 0, st, src, (long long)img_stride, (long long)stride, w, h, passes, dst, (long long)dst_img_stride,
+                           (long long)dst_stride, tiles_x, tiles, n);
+        return hipGetLastError();
+    }
     // every pass is launched, whatever an earlier launch reported; the first error is the call's
-    hipError_t e = launch_px(RgbaBleedFirst{src, (long long)stride, w, h, passes > 0 ? 1 : 0, dst, (long long)dst_stride, stamp}, (long long)w * h, st);
-    for (int k = 2; k <= passes; k++) { const hipError_t ek = launch_px(RgbaBleedPass{dst, (long long)dst_stride, w, h, (unsigned)k, stamp}, (long long)w * h, st); if (e == hipSuccess) e = ek; }
+    hipError_t e = launch_px(RgbaBleedFirst{src, (long long)img_stride, (long long)stride, w, h, 1, dst, (long long)dst_img_stride, (long long)dst_stride, stamp,
+                                            (long long)stamp_stride}, total, n, st);
+    for (int k = 2; k <= passes; k++) {
+        const hipError_t ek = launch_px(RgbaBleedPass{dst, (long long)dst_img_stride, (long long)dst_stride, w, h, (unsigned)k, stamp, (long long)stamp_stride}, total, n, st);
+        if (e == hipSuccess) e = ek;
+    }
     return e;
 }
 
-// alpha byte -> a = u8 / 255 (the Y route: the plane that rides with Y through the scale model)
+// alpha byte -> a = u8 / 255 (the Y route: the planes that ride with Y through the scale model); image i's plane at a + i * ps floats
 struct AlphaToPlane {
     const unsigned char *src;
-    long long stride;
+    long long img_stride, stride;
     int w;
     float *a;
-    __device__ __forceinline__ void operator()(int, long long q) const
+    long long ps;
+    __device__ __forceinline__ void operator()(int img, long long q) const
     {
         const RowCol at = row_col(q, w);
-        a[q] = (float)src[at.r * stride + (long long)at.c * 4 + 3] * (float)(1.0 / 255.0);
+        a[img * ps + q] = (float)src[img * img_stride + at.r * stride + (long long)at.c * 4 + 3] * (float)(1.0 / 255.0);
     }
 };
-hipError_t w2xc_launch_alpha_to_plane(const unsigned char *src, size_t stride, int w, int h, float *a, hipStream_t st)
+hipError_t w2xc_launch_alpha_to_plane(const unsigned char *src, size_t img_stride, size_t stride, int w, int h, float *a, long long ps, int n, hipStream_t st)
 {
-    return launch_px(AlphaToPlane{src, (long long)stride, w, a}, (long long)w * h, st);
+    return launch_px(AlphaToPlane{src, (long long)img_stride, (long long)stride, w, a, ps}, (long long)w * h, n, st);
 }
 
 // alpha byte -> the packed 3-channel image (A, A, A) (the RGB route: alpha goes through the RGB pipeline as a grey image)
 struct AlphaToGrey {
     const unsigned char *src;
-    long long stride;
+    long long img_stride, stride;
     int w;
     unsigned char *dst;
-    long long dst_stride;
-    __device__ __forceinline__ void operator()(int, long long q) const
+    long long dst_img_stride, dst_stride;
+    __device__ __forceinline__ void operator()(int img, long long q) const
     {
         const RowCol at = row_col(q, w);
-        const unsigned char a = src[at.r * stride + (long long)at.c * 4 + 3];
-        unsigned char *d = dst + at.r * dst_stride + (long long)at.c * 3;
+        const unsigned char a = src[img * img_stride + at.r * stride + (long long)at.c * 4 + 3];
+        unsigned char *d = dst + img * dst_img_stride + at.r * dst_stride + (long long)at.c * 3;
         d[0] = a; d[1] = a; d[2] = a;
     }
 };
-hipError_t w2xc_launch_alpha_to_grey(const unsigned char *src, size_t stride, int w, int h, unsigned char *dst, size_t dst_stride, hipStream_t st)
+hipError_t w2xc_launch_alpha_to_grey(const unsigned char *src, size_t img_stride, size_t stride, int w, int h, unsigned char *dst, size_t dst_img_stride,
+                                     size_t dst_stride, int n, hipStream_t st)
 {
-    return launch_px(AlphaToGrey{src, (long long)stride, w, dst, (long long)dst_stride}, (long long)w * h, st);
+    return launch_px(AlphaToGrey{src, (long long)img_stride, (long long)stride, w, dst, (long long)dst_img_stride, (long long)dst_stride}, (long long)w * h, n, st);
 }
 
-// the merge: a packed 3-channel result + alpha -> the caller's 4-byte pixels.  Alpha is a float plane (saturate(rint(255 a)), the expression of YuvToU8)
-// or a byte of an image with a_px bytes per pixel (the RGBA source: 4; the grey result of the RGB route: 3).
+// the merge: a packed 3-channel result + alpha -> the caller's 4-byte pixels.  Alpha is a float plane (saturate(rint(255 a)), the expression of YuvToU8;
+// image i's at a + i * ps floats) or a byte of an image with a_px bytes per pixel (the RGBA source: 4; the grey result of the RGB route: 3).
 static __device__ __forceinline__ void merge_rgba_px(const unsigned char *rgb, long long rgb_stride, unsigned char a, RowCol at, unsigned char *dst, long long stride)
 {
     const unsigned char *s = rgb + at.r * rgb_stride + (long long)at.c * 3;
@@ -409,33 +528,39 @@ static __device__ __forceinline__ void merge_rgba_px(const unsigned char *rgb, l
 }
 struct MergeRgbaF32 {
     const unsigned char *rgb;
-    long long rgb_stride;
+    long long rgb_img_stride, rgb_stride;
     const float *a;
+    long long ps;
     int w;
     unsigned char *dst;
-    long long stride;
-    __device__ __forceinline__ void operator()(int, long long q) const { merge_rgba_px(rgb, rgb_stride, to_u8(a[q]), row_col(q, w), dst, stride); }
+    long long img_stride, stride;
+    __device__ __forceinline__ void operator()(int img, long long q) const
+    {
+        merge_rgba_px(rgb + img * rgb_img_stride, rgb_stride, to_u8(a[img * ps + q]), row_col(q, w), dst + img * img_stride, stride);
+    }
 };
 struct MergeRgbaU8 {
     const unsigned char *rgb;
-    long long rgb_stride;
+    long long rgb_img_stride, rgb_stride;
     const unsigned char *a;
-    long long a_stride;
+    long long a_img_stride, a_stride;
     int a_px, w;
     unsigned char *dst;
-    long long stride;
-    __device__ __forceinline__ void operator()(int, long long q) const
+    long long img_stride, stride;
+    __device__ __forceinline__ void operator()(int img, long long q) const
     {
         const RowCol at = row_col(q, w);
-        merge_rgba_px(rgb, rgb_stride, a[at.r * a_stride + (long long)at.c * a_px], at, dst, stride);
+        merge_rgba_px(rgb + img * rgb_img_stride, rgb_stride, a[img * a_img_stride + at.r * a_stride + (long long)at.c * a_px], at, dst + img * img_stride, stride);
     }
 };
-hipError_t w2xc_launch_merge_rgba(const unsigned char *rgb, size_t rgb_stride, const float *a, int w, int h, unsigned char *dst, size_t stride, hipStream_t st)
+hipError_t w2xc_launch_merge_rgba(const unsigned char *rgb, size_t rgb_img_stride, size_t rgb_stride, const float *a, long long ps, int w, int h,
+                                  unsigned char *dst, size_t img_stride, size_t stride, int n, hipStream_t st)
 {
-    return launch_px(MergeRgbaF32{rgb, (long long)rgb_stride, a, w, dst, (long long)stride}, (long long)w * h, st);
+    return launch_px(MergeRgbaF32{rgb, (long long)rgb_img_stride, (long long)rgb_stride, a, ps, w, dst, (long long)img_stride, (long long)stride}, (long long)w * h, n, st);
 }
-hipError_t w2xc_launch_merge_rgba_u8(const unsigned char *rgb, size_t rgb_stride, const unsigned char *a, size_t a_stride, int a_px, int w, int h,
-                                     unsigned char *dst, size_t stride, hipStream_t st)
+hipError_t w2xc_launch_merge_rgba_u8(const unsigned char *rgb, size_t rgb_img_stride, size_t rgb_stride, const unsigned char *a, size_t a_img_stride, size_t a_stride,
+                                     int a_px, int w, int h, unsigned char *dst, size_t img_stride, size_t stride, int n, hipStream_t st)
 {
-    return launch_px(MergeRgbaU8{rgb, (long long)rgb_stride, a, (long long)a_stride, a_px, w, dst, (long long)stride}, (long long)w * h, st);
+    return launch_px(MergeRgbaU8{rgb, (long long)rgb_img_stride, (long long)rgb_stride, a, (long long)a_img_stride, (long long)a_stride, a_px, w, dst,
+                                 (long long)img_stride, (long long)stride}, (long long)w * h, n, st);
 }

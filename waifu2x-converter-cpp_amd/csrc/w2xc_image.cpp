@@ -88,19 +88,19 @@ template <class T> struct U8Images {
 typedef U8Images<const unsigned char> U8In;
 typedef U8Images<unsigned char> U8Out;
 
-// An alpha plane that rides with Y (the Y route of w2xc_process_image_rgba_u8*): a = u8 / 255 of the RGBA image `src`, through every scale iteration as the
-// second plane of a run_batch of two -- one plane stride behind the Y plane that feeds the iteration -- and through the shrink; never through the noise model.
-// *plane = where the call left it (the final size, floats).  Only with iterations >= 1, and only for one image.
+// The alpha planes that ride with Y (the Y route of w2xc_process_image_rgba_u8*): a = u8 / 255 of the S RGBA images `src`, through every scale iteration as
+// the second half of a run_batch of 2 S planes -- the S alpha planes directly behind the S Y planes that feed the iteration -- and through the shrink; never
+// through the noise model.  plane = where the call left image 0's (the final size), image i's ps floats on.  Only with iterations >= 1.
 struct AlphaRide {
-    const unsigned char *src;
-    size_t stride;
+    U8In src;
     float *plane;
+    long long ps;
 };
 
 // The Y pipeline for a sub-batch of S images (S <= cap, the call's sub-batch size: the planes are sized by cap, not by the call's n): noise (optional,
 // main.cpp:83-98) then `iterations` 2x scale steps (main.cpp:126-156), the shrink, the colour stages around them.  Every plane lies on a plane_floats
-// boundary, ps floats from the next; a level holds the Y group (S planes, or Y and its alpha), S U planes, S V planes, level 0 also the Y group of the
-// noise pass (image_aux_floats).  So the Y planes go to run_batch as they lie, U and V are 2 S adjacent planes for the bicubic launch, all of them the
+// boundary, ps floats from the next; a level holds the Y group (S Y planes, with alpha S alpha planes behind them), S U planes, S V planes, level 0 also
+// the Y group of the noise pass (image_aux_floats).  So the Y planes go to run_batch as they lie, U and V are 2 S adjacent planes for the bicubic launch, all of them the
 // planes of the one shrink launch.  One launch per colour / resize stage.
 int process_y_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, size_t skip = 0, AlphaRide *al = nullptr)
 {
@@ -109,7 +109,7 @@ int process_y_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, siz
     if (int rc = reserve_aux(own, skip, image_aux_floats(c.w, c.h, c.iterations, c.shrink, al != nullptr, c.tta) * (size_t)cap)) return rc;
     // (TTA: the variant planes of a pass lie behind the planes of every level, cap images' worth; every pass reuses them)
     float *var = aux_planes(own, skip) + image_aux_floats(c.w, c.h, c.iterations, c.shrink, al != nullptr) * (size_t)cap;
-    // One CNN pass on Y: the noise pass (up = 0) on the S Y planes alone -- alpha never goes through the noise model; beside an alpha plane the one Y
+    // One CNN pass on Y: the noise pass (up = 0) on the S Y planes alone -- alpha never goes through the noise model; beside an alpha plane ONE Y
     // plane is the single call's run_rows -- a scale pass (up = 1) on the whole Y group.  Per plane the bits of the single call either way (run_batch).
     const auto pass = [&](int up, const float *src, long long sps, int w, int h, float *dst, long long dps) {
         const bool noise = up == 0;
@@ -120,7 +120,7 @@ int process_y_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, siz
         const PlanesIn in{src, (size_t)w, sps};
         const PlanesOut out{dst, (size_t)nw, dps};
         if (c.tta) return tta_pass(TtaPass{m, cm, up, 1, 1, false}, np, in, w, h, out, var, c.st, c.o);
-        return c.rows || (noise && al) ? run_rows(m, cm, RowsCall::whole(in.plane(0), 1, nw, nh, out.plane(0), up), c.st, c.o)
+        return c.rows || (noise && al && S == 1) ? run_rows(m, cm, RowsCall::whole(in.plane(0), 1, nw, nh, out.plane(0), up), c.st, c.o)
                                        : run_batch(m, cm, np, up, in, w, h, out, c.st, c.o);
     };
     float *base = aux_planes(own, skip);
@@ -129,7 +129,7 @@ int process_y_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, siz
     float *y = base, *u = y + ny * ps, *v = u + (size_t)S * ps, *yn = v + (size_t)S * ps;
     base += (2 * ya + 2) * (size_t)cap * ps;
     HIP_TRY(w2xc_launch_u8_to_yuv_batch(in.p, in.img, in.row, cw, ch, y, u, v, ps, S, c.st));                // :75-76
-    if (al) HIP_TRY(w2xc_launch_alpha_to_plane(al->src, al->stride, cw, ch, (c.mn ? yn : y) + ps, c.st));
+    if (al) HIP_TRY(w2xc_launch_alpha_to_plane(al->src.p, al->src.img, al->src.row, cw, ch, (c.mn ? yn : y) + (size_t)S * ps, ps, S, c.st));
     if (c.mn) {                                                                                             // :91-98
         if (int rc = pass(0, y, ps, cw, ch, yn, ps)) return rc;
         y = yn;
@@ -150,7 +150,7 @@ int process_y_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, siz
         y = base; u = y + ny * pss; cw = c.fw; ch = c.fh; ps = pss;
     }
     HIP_TRY(w2xc_launch_yuv_to_u8_batch(y, u, u + (size_t)S * ps, ps, cw, ch, out.p, out.img, out.row, S, c.st));   // :171-172
-    if (al) al->plane = y + ps;
+    if (al) { al->plane = y + (size_t)S * ps; al->ps = ps; }
     return W2XC_OK;
 }
 
@@ -246,8 +246,10 @@ int process_sub_batch(bool rgb, const ImageCall &c, int S, int cap, U8In in, U8O
 //   PLAN_RGB  first: each model takes three planes and gives three (a Y model beside an RGB one fails here too)
 //   PLAN_Y    at most the sub-batch run_batch takes at the LARGEST level where its batched chain applies (more images would only be cut again there, and
 //             the planes of a larger sub-batch would be memory without a launch saved)
+// The RGBA call gives its own bytes per image (per_image; 0 = the 3-channel call's, above) and ya = 2 on the Y route: a Y brings its alpha plane, so a
+// sub-batch run_batch takes whole holds half as many images.
 enum PlanKind { PLAN_Y, PLAN_RGB };
-int plan_image_call(PlanKind kind, const ImageCall &c, int *sub)
+int plan_image_call(PlanKind kind, const ImageCall &c, int *sub, size_t per_image = 0, int ya = 1)
 {
     const bool rgb = kind == PLAN_RGB;
     const w2xc_model *pass[2] = {c.mn, c.msc};
@@ -273,8 +275,8 @@ int plan_image_call(PlanKind kind, const ImageCall &c, int *sub)
     }
     const size_t budget = (size_t)(c.o.workspace_mb > 0 ? c.o.workspace_mb : 16384) << 20;
     const size_t floats = rgb ? rgb_plan(c).floats : image_aux_floats(c.w, c.h, c.iterations, c.shrink, false, c.tta);
-    const size_t per = floats * 4 + (size_t)c.w * 3 * c.h + (size_t)c.fw * 3 * c.fh;
-    *sub = (int)std::min(k, std::max<size_t>(budget / per, 1));
+    const size_t per = per_image ? per_image : floats * 4 + (size_t)c.w * 3 * c.h + (size_t)c.fw * 3 * c.fh;
+    *sub = (int)std::max<size_t>(std::min(k / ya, budget / per), 1);
     return W2XC_OK;
 }
 
@@ -295,16 +297,21 @@ int check_process_args(const ImageCall &c)
     return W2XC_OK;
 }
 
-// the image arguments (px bytes per pixel); sets the call's final size (behind check_process_args: one model is there)
-int check_image_args(ImageCall &c, const void *in, size_t in_stride, const void *out, size_t out_stride, int px = 3)
+// the sizes and row strides of an image call (px bytes per pixel); sets the call's final size (behind check_process_args: one model is there)
+int check_image_size(ImageCall &c, size_t in_stride, size_t out_stride, int px = 3)
 {
-    if (!in || !out) return fail(W2XC_ERR_ARG, "null argument");
     if (c.w <= 0 || c.h <= 0 || c.iterations < 0 || c.iterations > 4) return fail(W2XC_ERR_ARG, "bad image size / iteration count");
     if (c.shrink < 0.0 || c.shrink >= 1.0) return fail(W2XC_ERR_ARG, "shrink_ratio must be 0 (none) or in (0,1)");
     final_size(c.w, c.h, c.iterations, c.shrink, &c.fw, &c.fh);
     if (c.fw < 1 || c.fh < 1) return fail(W2XC_ERR_ARG, "shrink_ratio leaves an empty image");
     if (in_stride < (size_t)c.w * px || out_stride < (size_t)c.fw * px) return fail(W2XC_ERR_ARG, "row strides must be >= %d*width bytes", px);
     return W2XC_OK;
+}
+// ... and the two pointers of a single image (a batch checks its own)
+int check_image_args(ImageCall &c, const void *in, size_t in_stride, const void *out, size_t out_stride, int px = 3)
+{
+    if (!in || !out) return fail(W2XC_ERR_ARG, "null argument");
+    return check_image_size(c, in_stride, out_stride, px);
 }
 
 // the largest level of the call, (w << iterations) x (h << iterations), is at most 2^28 a side (what the plans and the layouts above compute with)
@@ -346,21 +353,35 @@ int check_image_batch_args(bool rgb, ImageCall &c, int n, size_t in_stride, size
     if (n < 1) return fail(W2XC_ERR_ARG, "batch of %d images", n);
     int rc = check_process_args(c);
     if (rc) return rc;
-    if ((rc = check_image_args(c, &n, in_stride, &n, out_stride))) return rc;   // (pointers: see above)
+    if ((rc = check_image_size(c, in_stride, out_stride))) return rc;
     if ((rc = check_image_extent(c))) return rc;
     return rgb ? W2XC_OK : check_y_models(c);   // (RGB: the models' plane form is plan_image_call's, behind the caller's pointer checks)
 }
 
 // ---- RGBA images (w2xc_process_image_rgba_u8*) ----
-// bleed -> the 3-channel pipeline of the route on the bled image -> alpha through the scale model -> merge.  The call's uint8 images
-// live at the head of the owning context's aux buffer, the pipelines' float planes behind them:
-//   bled   the packed 3-channel image after the bleed      stamp  the bleed's pass stamps (16 bits per pixel)
-//   res    the packed 3-channel result of the colour call  grey / ares (RGB route, iterations >= 1)  alpha as the image (A, A, A), and its result
+// bleed -> the 3-channel pipeline of the route on the bled images -> alpha through the scale model -> merge, for a sub-batch of S
+// images; the single call is a sub-batch of one.  The call's uint8 images live at the head of the owning context's aux buffer, cap images each at
+// 256-byte-aligned image strides, the pipelines' float planes behind them:
+//   bled   the packed 3-channel images after the bleed      stamp  the bleed's pass stamps (16 bits per pixel; only the pass chain has them)
+//   res    the packed 3-channel results of the colour call  grey / ares (RGB route, iterations >= 1)  alpha as the images (A, A, A), and their results
 struct RgbaPlan {
     bool rgb = false;
     int passes = 0;          // bleed passes that can change a pixel: no pixel is farther than max(w, h) - 1 from an opaque one
-    size_t bled = 0, stamp = 0, res = 0, grey = 0, ares = 0, head = 0;   // byte offsets; head = where the float planes start
-    size_t bytes = 0;        // the whole call
+    int sub = 1;             // images per sub-batch (plan_image_call)
+    size_t bled = 0, stamp = 0, res = 0, grey = 0, ares = 0;   // bytes per image of each (a multiple of 256; 0 = the call has none)
+    size_t floats = 0;       // float planes per image
+};
+// where those lie for sub-batches of at most cap images: byte offsets; head = where the float planes start
+struct RgbaLayout {
+    size_t bled, stamp, res, grey, ares, head, bytes;
+    RgbaLayout(const RgbaPlan &R, size_t cap)
+    {
+        size_t at = 0;
+        const auto take = [&](size_t img) { const size_t a = at; at += cap * img; return a; };
+        bled = take(R.bled); stamp = take(R.stamp); res = take(R.res); grey = take(R.grey); ares = take(R.ares);
+        head = at;
+        bytes = at + cap * R.floats * sizeof(float);
+    }
 };
 
 // the scale-only call on the same image: what alpha goes through on the RGB route
@@ -380,80 +401,87 @@ int plan_rgba(const ImageCall &c, int bleed_passes, RgbaPlan *R)
     if (int rc = check_image_extent(c)) return rc;
     R->rgb = first->layers[0].nin == 3;
     if (!R->rgb) if (int rc = check_y_models(c)) return rc;
-    int sub;
-    if (int rc = plan_image_call(R->rgb ? PLAN_RGB : PLAN_Y, c, &sub)) return rc;
+    if (int rc = plan_image_call(R->rgb ? PLAN_RGB : PLAN_Y, c, &R->sub)) return rc;   // (the models' and the options' errors, before the models are asked anything)
     long long P = bleed_passes;
     if (P < 0) P = (long long)(c.mn ? c.mn->layers.size() : 0) + (long long)(c.msc ? c.msc->layers.size() : 0);   // the CNN's reach at source resolution
     P = std::min<long long>(P, std::max(c.w, c.h) - 1);
     if (P > 65534) return fail(W2XC_ERR_ARG, "more than 65534 effective bleed passes");
     R->passes = (int)P;
-    size_t at = 0;
-    const auto take = [&](size_t bytes) { const size_t a = at; at += align256(bytes); return a; };
-    R->bled = take((size_t)c.w * 3 * c.h);
-    R->stamp = take((size_t)c.w * 2 * c.h);
-    R->res = take((size_t)c.fw * 3 * c.fh);
-    size_t floats;
+    R->bled = align256((size_t)c.w * 3 * c.h);
+    if (w2xc_bleed_stamps((int)P)) R->stamp = align256((size_t)c.w * 2 * c.h);
+    R->res = align256((size_t)c.fw * 3 * c.fh);
+    const bool ride = c.iterations > 0;   // alpha goes through the scale model
     if (R->rgb) {
-        floats = rgb_plan(c).floats;
-        if (c.iterations > 0) {
-            R->grey = take((size_t)c.w * 3 * c.h);
-            R->ares = take((size_t)c.fw * 3 * c.fh);
-            floats = std::max(floats, rgb_plan(alpha_call(c)).floats);
+        R->floats = rgb_plan(c).floats;
+        if (ride) {
+            R->grey = align256((size_t)c.w * 3 * c.h);
+            R->ares = align256((size_t)c.fw * 3 * c.fh);
+            R->floats = std::max(R->floats, rgb_plan(alpha_call(c)).floats);
         }
-    } else floats = image_aux_floats(c.w, c.h, c.iterations, c.shrink, c.iterations > 0);
-    if (c.iterations == 0 && c.shrink > 0.0) floats = std::max(floats, plane_floats(c.w, c.h) + plane_floats(c.fw, c.fh));   // alpha as a plane and its shrunk plane
-    R->head = at;
-    R->bytes = at + floats * sizeof(float);
-    return W2XC_OK;
+    } else R->floats = image_aux_floats(c.w, c.h, c.iterations, c.shrink, ride);
+    if (!ride && c.shrink > 0.0) R->floats = std::max(R->floats, plane_floats(c.w, c.h) + plane_floats(c.fw, c.fh));   // alpha as a plane and its shrunk plane
+    // what one image takes: the float planes, alpha's among them, the uint8 images above, the 4-byte image in and out
+    const size_t per = R->floats * sizeof(float) + R->bled + R->stamp + R->res + R->grey + R->ares + (size_t)c.w * 4 * c.h + (size_t)c.fw * 4 * c.fh;
+    return plan_image_call(R->rgb ? PLAN_RGB : PLAN_Y, c, &R->sub, per, !R->rgb && ride ? 2 : 1);
 }
 
-int process_rgba_device(const RgbaPlan &R, const ImageCall &c, U8In in, U8Out out)
+// a sub-batch of S images (S <= cap, the call's sub-batch size).  c.rows: the single call -- where Y runs alone (no scale pass) its pass is run_rows
+int process_rgba_device(const RgbaPlan &R, const ImageCall &c, int S, int cap, U8In in, U8Out out)
 {
     DevCtx *own = c.ctx.owner();
-    if (int rc = own->aux.reserve(R.bytes, "the RGBA image and its planes")) return rc;   // (all of it first: a buffer that grows loses its content)
+    const RgbaLayout L(R, (size_t)cap);
+    if (int rc = own->aux.reserve(L.bytes, "the RGBA images and their planes")) return rc;   // (all of it first: a buffer that grows loses its content)
     unsigned char *a8 = own->aux.as<unsigned char>();
     const int w = c.w, h = c.h, W = c.fw, H = c.fh;
     const size_t rs = (size_t)w * 3, RS = (size_t)W * 3;
-    const U8In bled{a8 + R.bled, 0, rs};
-    const U8Out res{a8 + R.res, 0, RS};
-    HIP_TRY(w2xc_launch_rgba_bleed(in.p, in.row, w, h, R.passes, a8 + R.bled, rs, reinterpret_cast<unsigned short *>(a8 + R.stamp), c.st));
+    const U8In bled{a8 + L.bled, R.bled, rs};
+    const U8Out res{a8 + L.res, R.res, RS};
+    HIP_TRY(w2xc_launch_rgba_bleed(in.p, in.img, in.row, w, h, R.passes, a8 + L.bled, R.bled, rs, reinterpret_cast<unsigned short *>(a8 + L.stamp), R.stamp / 2, S, c.st));
     if (R.rgb) {
-        if (int rc = process_rgb_device(c, 1, 1, bled, res, R.head)) return rc;
+        if (int rc = process_rgb_device(c, S, cap, bled, res, L.head)) return rc;
         if (c.iterations > 0) {   // alpha = channel 1 of the scale-only call on (A, A, A)
-            HIP_TRY(w2xc_launch_alpha_to_grey(in.p, in.row, w, h, a8 + R.grey, rs, c.st));
-            if (int rc = process_rgb_device(alpha_call(c), 1, 1, U8In{a8 + R.grey, 0, rs}, U8Out{a8 + R.ares, 0, RS}, R.head)) return rc;
-            HIP_TRY(w2xc_launch_merge_rgba_u8(a8 + R.res, RS, a8 + R.ares + 1, RS, 3, W, H, out.p, out.row, c.st));
+            HIP_TRY(w2xc_launch_alpha_to_grey(in.p, in.img, in.row, w, h, a8 + L.grey, R.grey, rs, S, c.st));
+            if (int rc = process_rgb_device(alpha_call(c), S, cap, U8In{a8 + L.grey, R.grey, rs}, U8Out{a8 + L.ares, R.ares, RS}, L.head)) return rc;
+            HIP_TRY(w2xc_launch_merge_rgba_u8(res.p, res.img, RS, a8 + L.ares + 1, R.ares, RS, 3, W, H, out.p, out.img, out.row, S, c.st));
             return W2XC_OK;
         }
-    } else {   // with a scale pass alpha rides with Y (run_batch's passes); without one the single-image call as it is
-        AlphaRide al = {in.p, in.row, nullptr};
+    } else {   // with a scale pass alpha rides with Y (run_batch's passes); without one the 3-channel call as it is: the single image through run_rows
+        AlphaRide al = {in, nullptr, 0};
         ImageCall y = c;
-        y.rows = c.iterations == 0;
-        if (int rc = process_y_device(y, 1, 1, bled, res, R.head, c.iterations > 0 ? &al : nullptr)) return rc;
+        y.rows = c.rows && c.iterations == 0;
+        if (int rc = process_y_device(y, S, cap, bled, res, L.head, c.iterations > 0 ? &al : nullptr)) return rc;
         if (c.iterations > 0) {
-            HIP_TRY(w2xc_launch_merge_rgba(a8 + R.res, RS, al.plane, W, H, out.p, out.row, c.st));
+            HIP_TRY(w2xc_launch_merge_rgba(res.p, res.img, RS, al.plane, al.ps, W, H, out.p, out.img, out.row, S, c.st));
             return W2XC_OK;
         }
     }
     if (c.shrink > 0.0) {
         // no scale pass but a shrink (both routes): a = u8 / 255, INTER_LINEAR like every other plane, rounded in the merge.  The pipeline's float planes
-        // are free again: its result is the uint8 image `res`, and everything here follows it on the stream.
-        float *a0 = aux_planes(own, R.head), *a1 = a0 + plane_floats(w, h);
-        HIP_TRY(w2xc_launch_alpha_to_plane(in.p, in.row, w, h, a0, c.st));
-        HIP_TRY(w2xc_launch_resize_linear(a0, w, h, a1, W, H, c.st));
-        HIP_TRY(w2xc_launch_merge_rgba(a8 + R.res, RS, a1, W, H, out.p, out.row, c.st));
+        // are free again: its result is the uint8 images `res`, and everything here follows it on the stream.
+        const long long ps = (long long)plane_floats(w, h), pss = (long long)plane_floats(W, H);
+        float *a0 = aux_planes(own, L.head), *a1 = a0 + (size_t)cap * ps;
+        HIP_TRY(w2xc_launch_alpha_to_plane(in.p, in.img, in.row, w, h, a0, ps, S, c.st));
+        HIP_TRY(w2xc_launch_resize_linear_batch(a0, a0, S, ps, w, h, a1, pss, W, H, S, c.st));
+        HIP_TRY(w2xc_launch_merge_rgba(res.p, res.img, RS, a1, pss, W, H, out.p, out.img, out.row, S, c.st));
         return W2XC_OK;
     }
-    HIP_TRY(w2xc_launch_merge_rgba_u8(a8 + R.res, RS, in.p + 3, in.row, 4, W, H, out.p, out.row, c.st));   // same size: the alpha bytes as they are
+    // same size: the alpha bytes as they are
+    HIP_TRY(w2xc_launch_merge_rgba_u8(res.p, res.img, RS, in.p + 3, in.img, in.row, 4, W, H, out.p, out.img, out.row, S, c.st));
     return W2XC_OK;
 }
 
-// what both forms of the RGBA call refuse before any device is touched
-int check_rgba_call(ImageCall &c, U8In in, U8Out out, int bleed_passes, RgbaPlan *R)
+// what every form of the RGBA call refuses before any device is touched (the image pointers are the caller's: checked there)
+int check_rgba_call(ImageCall &c, size_t in_stride, size_t out_stride, int bleed_passes, RgbaPlan *R)
 {
     int rc = check_process_args(c);
     if (rc) return rc;
-    if ((rc = check_image_args(c, in.p, in.row, out.p, out.row, 4))) return rc;
+    if ((rc = check_image_size(c, in_stride, out_stride, 4))) return rc;
+    return plan_rgba(c, bleed_passes, R);
+}
+int check_rgba_single(ImageCall &c, U8In in, U8Out out, int bleed_passes, RgbaPlan *R)
+{
+    int rc = check_process_args(c);
+    if (rc || (rc = check_image_args(c, in.p, in.row, out.p, out.row, 4))) return rc;
     if (ranges_overlap(in.p, image_extent(c.h, in.row, c.w, 4), out.p, image_extent(c.fh, out.row, c.fw, 4)))
         return fail(W2XC_ERR_ARG, "the output image overlaps the input image");
     return plan_rgba(c, bleed_passes, R);
@@ -463,23 +491,93 @@ int rgba_ex_device(ImageCall c, U8In in, U8Out out, int bleed_passes)
 {
     RgbaPlan R;
     LockedCtx lc;
-    int rc = check_rgba_call(c, in, out, bleed_passes, &R);
+    int rc = check_rgba_single(c, in, out, bleed_passes, &R);
     if (rc || (rc = lc.open(c.mn, c.msc, c.o.device))) return rc;
     c.ctx = lc;
-    return process_rgba_device(R, c, in, out);
+    c.rows = true;
+    return process_rgba_device(R, c, 1, 1, in, out);
 }
 
-// one host image on w2xc_opts.device, synchronously
+// one host image on device `dev`, synchronously: w2xc_process_image_rgba_u8_ex (w2xc_opts.device), and a host batch of one image
+int rgba_host_single(const RgbaPlan &R, ImageCall &c, U8In in, U8Out out, int dev)
+{
+    LockedCtx lc;
+    if (int rc = lc.open(c.mn, c.msc, dev)) return rc;
+    c.ctx = lc;
+    c.rows = true;
+    return host_round_trip(c, 4, in, out, [&](U8In d_in, U8Out d_out) { return process_rgba_device(R, c, 1, 1, d_in, d_out); });
+}
+
 int rgba_ex_host(ImageCall c, U8In in, U8Out out, int bleed_passes)
 {
     RgbaPlan R;
-    LockedCtx lc;
-    int rc = check_rgba_call(c, in, out, bleed_passes, &R);
-    if (rc) return rc;
+    if (int rc = check_rgba_single(c, in, out, bleed_passes, &R)) return rc;
     if (w2xc_device_count() <= 0) return fail(W2XC_ERR_HIP, "no HIP device available (libw2xc_hip has no CPU fallback)");
+    return rgba_host_single(R, c, in, out, c.o.device);
+}
+
+// ---- batches of RGBA images: image i byte for byte the single call's ----
+int rgba_batch_device(ImageCall c, int n, U8In in, U8Out out, int bleed_passes)
+{
+    if (n < 1) return fail(W2XC_ERR_ARG, "batch of %d images", n);
+    if (!in.p || !out.p) return fail(W2XC_ERR_ARG, "null argument");
+    RgbaPlan R;
+    int rc = check_rgba_call(c, in.row, out.row, bleed_passes, &R);
+    if (rc) return rc;
+    const size_t in_ext = image_extent(c.h, in.row, c.w, 4), out_ext = image_extent(c.fh, out.row, c.fw, 4);
+    if (n > 1 && out.img < out_ext)
+        return fail(W2XC_ERR_ARG, "output images overlap each other (image stride %zu < %zu bytes)", out.img, out_ext);
+    if (ranges_overlap(in.p, (size_t)(n - 1) * in.img + in_ext, out.p, (size_t)(n - 1) * out.img + out_ext))
+        return fail(W2XC_ERR_ARG, "output images overlap the input images");
+    const int sub = std::min(R.sub, n);
+    LockedCtx lc;
     if ((rc = lc.open(c.mn, c.msc, c.o.device))) return rc;
     c.ctx = lc;
-    return host_round_trip(c, 4, in, out, [&](U8In d_in, U8Out d_out) { return process_rgba_device(R, c, d_in, d_out); });
+    c.rows = n == 1;   // (a batch of one is the single call, bands included)
+    for (int b0 = 0; b0 < n; b0 += sub) {
+        rc = process_rgba_device(R, c, std::min(sub, n - b0), sub, U8In{in.p + (size_t)b0 * in.img, in.img, in.row},
+                                 U8Out{out.p + (size_t)b0 * out.img, out.img, out.row});
+        if (rc) return rc;
+    }
+    return W2XC_OK;
+}
+
+int rgba_batch_host(ImageCall c, int n, const unsigned char *const *in, size_t in_stride, unsigned char *const *out, size_t out_stride, int bleed_passes)
+{
+    if (n < 1) return fail(W2XC_ERR_ARG, "batch of %d images", n);
+    if (!in || !out) return fail(W2XC_ERR_ARG, "null argument");
+    RgbaPlan R;
+    int rc = check_rgba_call(c, in_stride, out_stride, bleed_passes, &R);
+    if (rc) return rc;
+    rc = check_batch_host_ptrs(n, (const void *const *)in, image_extent(c.h, in_stride, c.w, 4), (void *const *)out, image_extent(c.fh, out_stride, c.fw, 4));
+    if (rc) return rc;
+    if (n == 1) {   // nothing to overlap: the synchronous single-image sequence, on the first device of the mask
+        std::vector<int> devs;
+        if ((rc = host_devices(c.o, &devs))) return rc;
+        return rgba_host_single(R, c, U8In{in[0], 0, in_stride}, U8Out{out[0], 0, out_stride}, devs[0]);
+    }
+    HostBatch b;
+    b.n = n;
+    b.in = (const void *const *)in; b.out = (void *const *)out;
+    b.in_stride = in_stride; b.out_stride = out_stride;
+    b.in_row = (size_t)c.w * 4; b.out_row = (size_t)c.fw * 4;
+    b.in_rows = c.h; b.out_rows = c.fh;
+    b.in_img = align256(b.in_row * c.h); b.out_img = align256(b.out_row * c.fh);
+    b.acquire = [&](int dev, std::unique_lock<std::mutex> &l1, std::unique_lock<std::mutex> &l2, HostPipe **pipe) -> int {
+        CallCtx ic;
+        int r = call_contexts(c.mn, c.msc, dev, &ic, &l1, &l2);
+        if (r) return r;
+        *pipe = &ic.owner()->pipe;
+        return W2XC_OK;
+    };
+    b.run = [&](int dev, int cnt, const void *din, void *dout, hipStream_t st, int max_sub) -> int {
+        ImageCall d = c;   // (this device's share of the call: its contexts, locked by acquire, and the pipeline's stream)
+        d.st = st;
+        int r = call_contexts(c.mn, c.msc, dev, &d.ctx);
+        if (r) return r;
+        return process_rgba_device(R, d, cnt, max_sub, U8In{(const unsigned char *)din, b.in_img, b.in_row}, U8Out{(unsigned char *)dout, b.out_img, b.out_row});
+    };
+    return batch_host_run(b, c.o, R.sub);
 }
 
 // w2xc_bleed_rgba_u8_device has no model and so no context: its pass stamps (2 bytes per pixel, written before they are read) live in one buffer per device,
@@ -746,6 +844,22 @@ try {
                         U8Out{out, 0, out_stride_bytes}, bleed_passes);
 } W2XC_CATCH_ALL
 
+int w2xc_process_image_rgba_u8_batch_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in, size_t in_image_stride_bytes,
+                                            size_t in_stride_bytes, int w, int h, unsigned char *d_out, size_t out_image_stride_bytes, size_t out_stride_bytes,
+                                            int iterations, double shrink_ratio, int bleed_passes, void *hip_stream, const w2xc_opts *opts)
+try {
+    return rgba_batch_device(ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, hip_stream, opts), n,
+                             U8In{d_in, in_image_stride_bytes, in_stride_bytes}, U8Out{d_out, out_image_stride_bytes, out_stride_bytes}, bleed_passes);
+} W2XC_CATCH_ALL
+
+int w2xc_process_image_rgba_u8_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes, int w, int h,
+                                     unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio, int bleed_passes,
+                                     const w2xc_opts *opts)
+try {
+    return rgba_batch_host(ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, nullptr, opts), n, in, in_stride_bytes, out, out_stride_bytes,
+                           bleed_passes);
+} W2XC_CATCH_ALL
+
 int w2xc_bleed_rgba_u8_device(const unsigned char *d_in, size_t in_stride_bytes, int w, int h, int passes, unsigned char *d_out_rgb, size_t out_stride_bytes,
                               void *hip_stream)
 try {
@@ -759,9 +873,13 @@ try {
     HIP_TRY(hipGetDevice(&dev));
     BleedScratch &b = bleed_scratch();
     std::lock_guard<std::mutex> lk(b.mu);
-    Scratch &s = b.stamp[dev];
-    if (int rc = s.reserve((size_t)w * 2 * h, "the bleed's pass stamps")) return rc;
-    HIP_TRY(w2xc_launch_rgba_bleed(d_in, in_stride_bytes, w, h, passes, d_out_rgb, out_stride_bytes, s.as<unsigned short>(), (hipStream_t)hip_stream));
+    unsigned short *stamp = nullptr;   // (only the pass chain has stamps)
+    if (w2xc_bleed_stamps(passes)) {
+        Scratch &s = b.stamp[dev];
+        if (int rc = s.reserve((size_t)w * 2 * h, "the bleed's pass stamps")) return rc;
+        stamp = s.as<unsigned short>();
+    }
+    HIP_TRY(w2xc_launch_rgba_bleed(d_in, 0, in_stride_bytes, w, h, passes, d_out_rgb, 0, out_stride_bytes, stamp, 0, 1, (hipStream_t)hip_stream));
     return W2XC_OK;
 } W2XC_CATCH_ALL
 

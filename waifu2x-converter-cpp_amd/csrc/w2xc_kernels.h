@@ -136,16 +136,22 @@ hipError_t w2xc_launch_resize2x_cubic_batch(const float *src, long long sps, int
 // n planes (Y, U, V of a sub-batch: n = 3 x images): plane p < ny at src_y + p * sps, the others at src_uv + (p - ny) * sps; -> dst + p * dps
 hipError_t w2xc_launch_resize_linear_batch(const float *src_y, const float *src_uv, int ny, long long sps, int sw, int sh, float *dst, long long dps, int dw,
                                            int dh, int n, hipStream_t st);
-// RGBA images (w2xc_process_image_rgba_u8*): the colour bleed under transparent pixels (`passes` <= 65534 passes, in place on the packed 3-channel image dst;
-// stamp = w * h 16-bit words of scratch, written before they are read), alpha -> a float plane (u8 / 255) or a packed grey image (A, A, A), and the merge of a
-// packed 3-channel result with alpha -- a float plane (saturate(rint(255 a))) or a byte a_px apart in rows a_stride apart -- into 4-byte pixels.
-hipError_t w2xc_launch_rgba_bleed(const unsigned char *src, size_t stride, int w, int h, int passes, unsigned char *dst, size_t dst_stride, unsigned short *stamp,
-                                  hipStream_t st);
-hipError_t w2xc_launch_alpha_to_plane(const unsigned char *src, size_t stride, int w, int h, float *a, hipStream_t st);
-hipError_t w2xc_launch_alpha_to_grey(const unsigned char *src, size_t stride, int w, int h, unsigned char *dst, size_t dst_stride, hipStream_t st);
-hipError_t w2xc_launch_merge_rgba(const unsigned char *rgb, size_t rgb_stride, const float *a, int w, int h, unsigned char *dst, size_t stride, hipStream_t st);
-hipError_t w2xc_launch_merge_rgba_u8(const unsigned char *rgb, size_t rgb_stride, const unsigned char *a, size_t a_stride, int a_px, int w, int h,
-                                     unsigned char *dst, size_t stride, hipStream_t st);
+// RGBA images (w2xc_process_image_rgba_u8*), n images of one size per launch (image i at a byte pointer + i * its image stride, its float plane at a +
+// i * ps floats): the colour bleed under transparent pixels -- `passes` <= 65534 passes from the RGBA images src into the packed 3-channel images dst; up to
+// W2XC_BLEED_TILED_MAX passes are one launch (one pass: RgbaBleedFirst alone; more: the tiled kernel) and touch no stamp (nullptr will do), more run in place on dst with stamp = n planes of w * h 16-bit words of
+// scratch, stamp_stride words apart, written before they are read -- alpha -> a float plane (u8 / 255) or a packed grey image (A, A, A), and the merge of
+// a packed 3-channel result with alpha -- a float plane (saturate(rint(255 a))) or a byte a_px apart in rows a_stride apart -- into 4-byte pixels.
+#define W2XC_BLEED_TILED_MAX 16
+inline bool w2xc_bleed_stamps(int passes) { return passes > W2XC_BLEED_TILED_MAX; }   // (the pass chain alone has stamps)
+hipError_t w2xc_launch_rgba_bleed(const unsigned char *src, size_t img_stride, size_t stride, int w, int h, int passes, unsigned char *dst, size_t dst_img_stride,
+                                  size_t dst_stride, unsigned short *stamp, size_t stamp_stride, int n, hipStream_t st);
+hipError_t w2xc_launch_alpha_to_plane(const unsigned char *src, size_t img_stride, size_t stride, int w, int h, float *a, long long ps, int n, hipStream_t st);
+hipError_t w2xc_launch_alpha_to_grey(const unsigned char *src, size_t img_stride, size_t stride, int w, int h, unsigned char *dst, size_t dst_img_stride,
+                                     size_t dst_stride, int n, hipStream_t st);
+hipError_t w2xc_launch_merge_rgba(const unsigned char *rgb, size_t rgb_img_stride, size_t rgb_stride, const float *a, long long ps, int w, int h,
+                                  unsigned char *dst, size_t img_stride, size_t stride, int n, hipStream_t st);
+hipError_t w2xc_launch_merge_rgba_u8(const unsigned char *rgb, size_t rgb_img_stride, size_t rgb_stride, const unsigned char *a, size_t a_img_stride, size_t a_stride,
+                                     int a_px, int w, int h, unsigned char *dst, size_t img_stride, size_t stride, int n, hipStream_t st);
 
 // test-time augmentation (w2xc_tta.hip): T_k, k = 0..7 = horizontal flip if k & 1, then vertical flip if k & 2, then transpose if k & 4.  Variant planes have
 // contiguous rows and lie ps floats apart: upright (k, i) at up + (k n + i) ps, transposed (k, i) at tr + ((k - 4) n + i) ps.
