@@ -473,6 +473,12 @@ int w2xc_tta_gather_device(const float *d_up, const float *d_tr, size_t variant_
 
 /* the building blocks on contiguous float planes (device pointers): main.cpp:144 on one plane, :75-76, :171-172 */
 int w2xc_resize2x_cubic_device(const float *d_src, int w, int h, float *d_dst, void *hip_stream);
+/* main.cpp:158-167 on one plane (revision 0.4.1.4): cv::resize(Size(dw, dh), INTER_LINEAR) of the contiguous sw x sh plane d_src into the contiguous
+ * dw x dh plane d_dst, any sizes >= 1 (the image calls only shrink).  Output (dx, dy) reads fx = float((dx + 0.5) * (double)sw / dw - 0.5), sx =
+ * floor(fx), fx -= sx; sx < 0 or sx >= sw - 1 clamps sx into the row with fx = 0, the second tap is min(sx + 1, sw - 1); the same in y.  Rows first,
+ * h = S[sx] * (1 - fx) + S[sx + 1] * fx for the two rows, then h0 * (1 - fy) + h1 * fy, all in unfused fp32; no antialiasing, like OpenCV.
+ * W2XC_ERR_ARG for a null pointer or a size below 1.  Asynchronous on hip_stream, on the current device. */
+int w2xc_resize_linear_device(const float *d_src, int sw, int sh, float *d_dst, int dw, int dh, void *hip_stream);
 int w2xc_u8_to_yuv_device(const unsigned char *d_in, size_t in_stride_bytes, int w, int h, float *d_y, float *d_u,
                           float *d_v, void *hip_stream);
 int w2xc_yuv_to_u8_device(const float *d_y, const float *d_u, const float *d_v, int w, int h, unsigned char *d_out,

@@ -605,18 +605,32 @@ def test_process_image_modes(gpu, noise1_layers, scale_layers, mode):
     assert e.value.code == gpu.ERR_ARG
 
 
-@pytest.mark.parametrize("ratio", [1.5, 3.0])
+@pytest.mark.parametrize("ratio", [1.1, 1.25, 1.5, 1.8, 1.998, 2.2, 3.0])
 def test_process_image_shrink(gpu, scale_layers, ratio):
     """--scale_ratio that is not a power of two: iter = ceil(log2 r) 2x steps, then INTER_LINEAR shrink by
-    r / 2^iter (main.cpp:107-114,158-167)"""
+    r / 2^iter (main.cpp:107-114,158-167): shrinks 0.55, 0.625, 0.75, 0.9, 0.999, and 0.55, 0.75 after two steps"""
     import math
     msc = gpu._ModelSet.from_layers(scale_layers)
-    img = np.random.default_rng(3).integers(0, 256, (18, 26, 3), dtype=np.uint8)
     it = int(math.ceil(math.log2(ratio)))
     shrink = ratio / 2.0 ** it
-    want = orc.process_image_u8(img, None, orc.Oracle(scale_layers), it, shrink)
-    got = gpu.process_image_u8(img, None, msc, it, direct(gpu), shrink)
-    assert got.shape == want.shape == (int(float((18 << it) * shrink)), int(float((26 << it) * shrink)), 3)
+    for (h, w) in [(18, 26), (37, 53)]:
+        img = np.random.default_rng(3).integers(0, 256, (h, w, 3), dtype=np.uint8)
+        want = orc.process_image_u8(img, None, orc.Oracle(scale_layers), it, shrink)
+        got = gpu.process_image_u8(img, None, msc, it, direct(gpu), shrink)
+        assert got.shape == want.shape == (int(float((h << it) * shrink)), int(float((w << it) * shrink)), 3), (h, w)
+        assert np.array_equal(got, want), (h, w)
+
+
+@pytest.mark.parametrize("hw", [(18, 26), (37, 53)], ids=["18x26", "37x53"])
+@pytest.mark.parametrize("shrink", [0.3, 0.5, 0.6])
+def test_process_image_noise_then_shrink(gpu, noise1_layers, shrink, hw):
+    """a noise pass and no 2x step in front of the shrink: the resize scales of 2 and above (1 / 0.3, 1 / 0.5, 1 / 0.6 -- the two taps skip source pixels)"""
+    h, w = hw
+    mn = gpu._ModelSet.from_layers(noise1_layers)
+    img = np.random.default_rng(3).integers(0, 256, (h, w, 3), dtype=np.uint8)
+    want = orc.process_image_u8(img, orc.Oracle(noise1_layers), None, 0, shrink)
+    got = gpu.process_image_u8(img, mn, None, 0, direct(gpu), shrink)
+    assert got.shape == want.shape == (int(float(h * shrink)), int(float(w * shrink)), 3)
     assert np.array_equal(got, want)
 
 

@@ -160,6 +160,18 @@ def test_pipeline_against_oracle(gpu, models, case):
     gate(run(gpu, models, case), want, case[0])
 
 
+# a noise pass and no 2x step in front of the shrink: resize scales of 2 and above (the cases of CASES stay as they are: other tests index them)
+NOISE_SHRINK = [("noise_shrink%g_%s" % (s, img), "m7", None, img, 0, s) for img in ("a", "b") for s in (0.3, 0.5, 0.6)]
+
+
+@pytest.mark.parametrize("case", NOISE_SHRINK, ids=[c[0] for c in NOISE_SHRINK])
+def test_noise_then_shrink_against_oracle(gpu, models, case):
+    want = expected(case)
+    assert want.shape[:2] == final_size(image(case[3]).shape[0], image(case[3]).shape[1], 0, case[5])
+    assert np.array_equal(run(gpu, models, case, kernel=gpu.KERNEL_DIRECT), want), "the reference-ordered kernels give the oracle's bytes"
+    gate(run(gpu, models, case), want, case[0])
+
+
 # ---- 3. the uint8 first / last layers give the bytes of the route through float planes ----
 def composed(gpu, models, case):
     """w2xc_u8_to_rgb_device -> convert_planes[_nn2x]_device per pass -> (the shrink: the oracle's resize_linear on the downloaded planes, the ABI

@@ -100,15 +100,19 @@ def variant_planes(buf, ps, n, k, shape):
     return rows[:, :q].reshape((n,) + shape), rows[:, q:]
 
 
-@pytest.mark.parametrize("n", [1, 3])
-@pytest.mark.parametrize("hw", SHAPES, ids=["%dx%d" % s for s in SHAPES])
-def test_spread_bit_for_bit(gpu, hw, n):
+# the second trips of the kernels' two grid-stride loops (tta_grid: at most 65536 tiles, 65535 planes): 65537 tiles along x, along y; 65537 planes of one tile.
+# The tile loop's second trip reuses the LDS tile behind its leading barrier.
+SECOND_TRIPS = [((1, TILE * 65536 + 1), 1), ((TILE * 65536 + 1, 1), 1), ((1, 1), 65537)]
+SECOND_TRIP_IDS = ["%dx%d-n%d" % (s + (n,)) for s, n in SECOND_TRIPS]
+
+
+def check_spread(gpu, hw, n):
     h, w = hw
     rs, ps = w + 3, w * h + 5
     sps = h * rs + 7
     rng = np.random.default_rng(h * 1000 + w + n)
     src = rng.standard_normal((n, sps)).astype(np.float32)
-    x = np.stack([src[i, :h * rs].reshape(h, rs)[:, :w] for i in range(n)])
+    x = np.ascontiguousarray(src[:, :h * rs].reshape(n, h, rs)[:, :, :w])
     d_src = torch.from_numpy(src).cuda()
     d_up = torch.full((4 * n * ps,), float("nan"), dtype=torch.float32, device="cuda")
     d_tr = torch.full((4 * n * ps,), float("nan"), dtype=torch.float32, device="cuda")
@@ -123,7 +127,16 @@ def test_spread_bit_for_bit(gpu, hw, n):
 
 @pytest.mark.parametrize("n", [1, 3])
 @pytest.mark.parametrize("hw", SHAPES, ids=["%dx%d" % s for s in SHAPES])
-def test_gather_bit_for_bit(gpu, hw, n):
+def test_spread_bit_for_bit(gpu, hw, n):
+    check_spread(gpu, hw, n)
+
+
+@pytest.mark.parametrize("hw,n", SECOND_TRIPS, ids=SECOND_TRIP_IDS)
+def test_spread_second_trips(gpu, hw, n):
+    check_spread(gpu, hw, n)
+
+
+def check_gather(gpu, hw, n):
     h, w = hw
     rs, ps = w + 3, w * h + 5
     dps = h * rs + 7
@@ -146,10 +159,20 @@ def test_gather_bit_for_bit(gpu, hw, n):
     gpu.tta_gather_device(groups[0].data_ptr(), groups[1].data_ptr(), ps * 4, n, w, h, d_dst.data_ptr(), dps * 4, rs * 4, stream=stream().cuda_stream)
     stream().synchronize()
     dst = d_dst.cpu().numpy()
-    for i in range(n):
-        rows = dst[i, :h * rs].reshape(h, rs)
-        assert np.array_equal(rows[:, :w].view(np.uint32), want[i].view(np.uint32)), i
-        assert np.isnan(rows[:, w:]).all() and np.isnan(dst[i, h * rs:]).all(), "floats outside the plane's rows were written"
+    rows = dst[:, :h * rs].reshape(n, h, rs)
+    assert np.array_equal(np.ascontiguousarray(rows[:, :, :w]).view(np.uint32), want.view(np.uint32))
+    assert np.isnan(rows[:, :, w:]).all() and np.isnan(dst[:, h * rs:]).all(), "floats outside the plane's rows were written"
+
+
+@pytest.mark.parametrize("n", [1, 3])
+@pytest.mark.parametrize("hw", SHAPES, ids=["%dx%d" % s for s in SHAPES])
+def test_gather_bit_for_bit(gpu, hw, n):
+    check_gather(gpu, hw, n)
+
+
+@pytest.mark.parametrize("hw,n", SECOND_TRIPS, ids=SECOND_TRIP_IDS)
+def test_gather_second_trips(gpu, hw, n):
+    check_gather(gpu, hw, n)
 
 
 # ---- 2. plane calls == the composition a caller had before ----

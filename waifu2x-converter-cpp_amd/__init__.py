@@ -123,6 +123,7 @@ def _load():
         "w2xc_scale2x_image_u8_device": (ci, [vp, fp, cs, ci, ci, fp, cs, ci, vp, C.POINTER(Opts)]),
         "w2xc_scale2x_image_u8": (ci, [vp, fp, cs, ci, ci, fp, cs, ci, C.POINTER(Opts)]),
         "w2xc_resize2x_cubic_device": (ci, [fp, ci, ci, fp, vp]),
+        "w2xc_resize_linear_device": (ci, [fp, ci, ci, fp, ci, ci, vp]),
         "w2xc_u8_to_yuv_device": (ci, [fp, cs, ci, ci, fp, fp, fp, vp]),
         "w2xc_yuv_to_u8_device": (ci, [fp, fp, fp, ci, ci, fp, cs, vp]),
         "w2xc_convert_plane_nn2x": (ci, [vp, fp, cs, ci, ci, fp, cs, C.POINTER(Opts)]),
@@ -776,6 +777,12 @@ def rgb_to_u8_device(d_planes, w, h, d_out, out_stride_bytes, stream=0):
     ps = w * h * 4
     _check(_lib.w2xc_rgb_to_u8_device(C.c_void_p(d_planes), C.c_void_p(d_planes + ps), C.c_void_p(d_planes + 2 * ps), w, h, C.c_void_p(d_out),
                                       out_stride_bytes, C.c_void_p(stream)))
+
+
+def resize_linear_device(d_src, sw, sh, d_dst, dw, dh, stream=0):
+    """cv::resize(Size(dw, dh), INTER_LINEAR) of the contiguous sw x sh float plane at d_src into the contiguous dw x dh plane at d_dst
+    (w2xc_resize_linear_device): the resize of the image calls' shrink, at any pair of sizes."""
+    _check(_lib.w2xc_resize_linear_device(C.c_void_p(d_src), sw, sh, C.c_void_p(d_dst), dw, dh, C.c_void_p(stream)))
 
 
 # ---- test-time augmentation's building blocks (the image and plane calls take tta=True / are _ModelSet.convert_*_tta_device) ----

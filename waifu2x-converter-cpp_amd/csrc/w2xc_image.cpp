@@ -916,6 +916,13 @@ int w2xc_resize2x_cubic_device(const float *d_src, int w, int h, float *d_dst, v
     return W2XC_OK;
 }
 
+int w2xc_resize_linear_device(const float *d_src, int sw, int sh, float *d_dst, int dw, int dh, void *hip_stream)
+{
+    if (!d_src || !d_dst || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0) return fail(W2XC_ERR_ARG, "bad argument");
+    HIP_TRY(w2xc_launch_resize_linear(d_src, sw, sh, d_dst, dw, dh, (hipStream_t)hip_stream));
+    return W2XC_OK;
+}
+
 int w2xc_u8_to_yuv_device(const unsigned char *d_in, size_t in_stride_bytes, int w, int h, float *d_y, float *d_u, float *d_v, void *hip_stream)
 {
     if (!d_in || !d_y || !d_u || !d_v || w <= 0 || h <= 0 || in_stride_bytes < (size_t)w * 3) return fail(W2XC_ERR_ARG, "bad argument");
