@@ -109,8 +109,10 @@ def test_direct_path_is_bit_exact_end_to_end(gpu, noise1_layers):
     assert np.array_equal(got, want)
 
 
-@pytest.mark.parametrize("h,w", [(1, 1), (7, 9), (33, 65), (100, 31), (64, 200)])
+@pytest.mark.parametrize("h,w", [(1, 1), (7, 9), (33, 65), (100, 31), (64, 200), (4120, 3), (3, 8230)])
 def test_odd_sizes(gpu, scale_layers, h, w):
+    """(4120 x 3 and 3 x 8230: one tile column / one tile row of more tiles than a persistent grid has workgroups -- the second trip of
+    a workgroup through its tile loop, in either coordinate of the tile decode, against the oracle)"""
     ms = gpu._ModelSet.from_layers(scale_layers)
     x = rand_plane(h, w, h * 1000 + w)
     assert_close(ms.convert(x), orc.Oracle(scale_layers).convert(x), "%dx%d" % (h, w))
@@ -409,7 +411,7 @@ def _emulated(layers, x, mode, n_in=1):
 @pytest.mark.parametrize("mode", SPLIT_MODES)
 @pytest.mark.parametrize("planes", [[1, 32, 32, 1], [1, 64, 128, 1], [1, 128, 64, 32, 1], [1, 32, 128, 128, 64, 1],
                                     [1, 128, 32, 64, 1], [1, 32, 32, 64, 64, 128, 128, 1]])
-@pytest.mark.parametrize("h,w", [(45, 77), (8, 32), (70, 130)])
+@pytest.mark.parametrize("h,w", [(45, 77), (8, 32), (70, 130), (1, 1), (4120, 3)])
 def test_split_path_matches_its_emulation(gpu, mode, planes, h, w):
     """Layers 2..n-1 carry every fp32 activation / weight as 2 or 3 16-bit terms and sum 3 (two terms) or 6
     (three) term products in the fp32 accumulator of the bf16 / fp16 MFMA.  Checked against a float64-accumulate

@@ -269,7 +269,7 @@ def test_last_layer_finished_inside_the_producing_launch(gpu, planes):
     prog, sep = gpu.make_opts(fusion=gpu.FUSION_PROG), gpu.make_opts(fusion=gpu.FUSION_GATHER_LAUNCH)
     assert ms.kernel_name(n - 1, prog) == "(in_previous_layer)" and ms.kernel_name(n - 1, sep) == "conv3x3_last_gather"
     assert ms.kernel_name(n - 1) == "conv3x3_last_gather"   # (what the device entry points launch by default; ms.convert below is the HOST entry: PROG by default)
-    for (h, wd) in ((1, 1), (5, 3), (16, 32), (17, 33), (40, 257), (150, 290), (333, 1000), (131, 2051), (700, 70)):
+    for (h, wd) in ((1, 1), (5, 3), (16, 32), (17, 33), (40, 257), (150, 290), (333, 1000), (131, 2051), (700, 70), (4120, 3), (3, 8230)):
         x = rand_plane(h, wd, h * 7 + wd)
         want = ms.convert(x, opts=sep)
         for rep in range(2):

@@ -294,7 +294,7 @@ bool uses_wino4(const w2xc_model *m, const w2xc_opts &o);
 bool planar_between(const w2xc_model *m, int l, const w2xc_opts &o);
 int out_terms_of(const w2xc_model *m, int l, const w2xc_opts &o);
 bool gather_in_producer(const w2xc_model *m, const w2xc_opts &o);
-int fused_halves(int T, int cout);
+int fused_halves(int T, int cin, int cout);
 // the RGB image pipeline: may layer 1 read / the last layer write the caller's interleaved uint8 image itself (conv3x3_first / conv3x3_last, U8)?  fp32 with
 // the fast kernels and w2xc_opts.fusion other than W2XC_FUSION_OFF, a three-plane W2XC_K_FIRST / W2XC_K_LAST layer.
 bool u8_source_layer(const w2xc_model *m, const w2xc_opts &o);

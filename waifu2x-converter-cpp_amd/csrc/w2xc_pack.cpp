@@ -309,8 +309,16 @@ float w2xc_split_pack(int cin, int cout, int terms, int fmt, const float *w, voi
     return scale;
 }
 
-// wave columns (WN) of the two-term tile shape for `cout` planes = partial-G planes the fused epilogue writes
-int w2xc_split_halves(int terms, int cout) { return terms == 2 ? (cout >= 64 ? 2 : 1) : (cout >= 128 ? 2 : 1); }
+// wave columns (WN) of the tile shape that launch_split_t (w2xc_split.hip) runs a (cin, cout) layer with at `terms` terms = partial-G planes
+// the fused epilogue writes (each wave column writes its own nine tap planes).  Two terms: 2 for 64 / 128 planes; one and three terms: 2 for
+// 128 planes -- and for the one-term 64 -> 64 shape, which runs 8 waves of 4 rows x 32 planes (answered 1 here, the gather dropped planes
+// 32..63 and the second wave column stored past the nine tap planes the workspace was sized for).
+int w2xc_split_halves(int terms, int cin, int cout)
+{
+    if (terms == 2) return cout >= 64 ? 2 : 1;
+    if (terms == 1 && cin == 64 && cout == 64) return 2;
+    return cout >= 128 ? 2 : 1;
+}
 
 size_t w2xc_split_pack_last_bytes(int cin, int terms) { return (size_t)terms * (cin / 32) * 2 * W2XC_WAVE * 8 * 2; }
 

@@ -59,6 +59,6 @@ int w2xc_split_kg(int terms, int cin);
 size_t w2xc_split_packed_bytes(int cin, int cout, int terms);
 float w2xc_split_pack(int cin, int cout, int terms, int fmt, const float *w, void *dst);   // returns the weight scale (1 for bf16)
 // last layer fused into a two-term mid layer
-int w2xc_split_halves(int terms, int cout);
+int w2xc_split_halves(int terms, int cin, int cout);
 size_t w2xc_split_pack_last_bytes(int cin, int terms);   // terms = 2 (one- and two-term modes) or 3
 float w2xc_split_pack_last(int cin, int terms, int fmt, const float *w, void *dst);

@@ -83,7 +83,7 @@ int out_terms_of(const w2xc_model *m, int l, const w2xc_opts &o)
 }
 
 // partial-G planes a fused-last producer writes per tap: wave columns of the split tile shapes, 64-plane blocks of conv3x3_wino4
-int fused_halves(int T, int cout) { return T > 0 ? w2xc_split_halves(T, cout) : cout / 64; }
+int fused_halves(int T, int cin, int cout) { return T > 0 ? w2xc_split_halves(T, cin, cout) : cout / 64; }
 
 // fp32 path, layers with 32 / 64 / 128 planes in and out (W2XC_K_MFMA): which kernel runs them.
 //   MID_MFMA    conv3x3_mfma2: direct implicit GEMM, a k-ordered fp32 fma chain (the closest MFMA analogue of modelHandler.cpp:134-145)
@@ -223,7 +223,7 @@ void RowPlan::ws_need(const w2xc_model *m, int rows, size_t need[2]) const
         const int ot = out_terms_of(m, k - 1, o);
         const bool fused = ot == 9;   // partial G planes of the fused last layer
         const size_t bpe = (ot >= 1 && ot <= 3) ? 2 * (size_t)ot : 4;   // bytes per activation element of layer k's output
-        const size_t px_bytes = fused ? (size_t)fused_halves(T, m->layers[k - 1].nout) * 9 * 4 : m->layers[k - 1].nout * bpe;
+        const size_t px_bytes = fused ? (size_t)fused_halves(T, m->layers[k - 1].nin, m->layers[k - 1].nout) * 9 * 4 : m->layers[k - 1].nout * bpe;
         const size_t wk_mem = (planar_between(m, k - 1, o) || (fused && T == 0 && gather_in_producer(m, o))) ? ((wk + 31) & ~(size_t)31) : wk;   // planar rows (and the tap planes a PROG launch gathers itself) start on 128-byte lines
         need[(k - 1) & 1] = std::max(need[(k - 1) & 1], hk * wk_mem * px_bytes);
     }
@@ -390,7 +390,7 @@ W2xcKernelKind layer_desc(const w2xc_model *m, const RowPlan &P, int k, int y0, 
             d.out_rs = (T == 0 && gather_in_producer(m, o)) ? ((d.out_w + 31) & ~31) : d.out_w; d.out_ps = 1;
             d.out_gs = (long long)d.out_h * d.out_rs;
             d.out_ts = 9 * d.out_gs;
-            d.halves = fused_halves(T, hl.nout);   // (fp32: conv3x3_wino4 writes planar partial planes G[64-plane block][tap][y][x]: its epilogue sums the four plane tiles of a block on chip)
+            d.halves = fused_halves(T, hl.nin, hl.nout);   // (fp32: conv3x3_wino4 writes planar partial planes G[64-plane block][tap][y][x]: its epilogue sums the four plane tiles of a block on chip)
         }
     }
     next->p = d.out; next->rs = d.out_rs; next->ps = d.out_ps; next->cs = d.out_cs; next->ts = d.out_ts; next->gs = d.out_gs;

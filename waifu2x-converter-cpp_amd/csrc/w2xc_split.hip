@@ -1054,6 +1054,10 @@ static hipError_t launch_split(const W2xcConvDesc &d, hipStream_t stream)
     constexpr size_t lds_bytes = 2 * (size_t)(NW * APW * 1024) + (size_t)RING * (T * KG * (COUT / 32) * 1024) + COUT * 4 +
                                  ((OT == 9 && T == 2 && E == 1) ? 4 * (COUT / 32) * 1024 : (OT == 9 && T == 1) ? 2 * (COUT / 32) * 1024 : 0);
     static_assert(lds_bytes <= 160 * 1024, "LDS budget");
+    // fused last layer: every wave column stores its own nine tap planes.  The workspace and the gather count them by w2xc_split_halves (w2xc_pack.cpp):
+    // a tile shape that disagrees would store past the planes that were sized, or leave planes the gather sums unwritten.
+    if constexpr (OT == 9)
+        if (d.halves != WN) return hipErrorInvalidValue;
     auto kern = conv3x3_split<CIN, COUT, MB, NB, WM, WN, T, OT, KG, RING, FMT, E>;
     static W2xcLdsOptIn opt_in;   // per (kernel, device)
     const hipError_t e = opt_in(kern, lds_bytes);
