@@ -254,6 +254,28 @@ int w2xc_convert_batch_device(w2xc_model *m, int n, int nn2x, const float *d_in,
 int w2xc_convert_batch(w2xc_model *m, int n, int nn2x, const float *const *in, size_t in_stride_bytes, int w, int h,
                        float *const *out, size_t out_stride_bytes, const w2xc_opts *opts);
 
+/* (revision 0.4.1.5) The multi-plane sibling of w2xc_convert_batch_device: n IMAGES of one size, each n_in_planes planar planes in and ALL planes of the
+ * model's last layer out (w2xc_convert_planes[_nn2x]_device for n images; RGB models: 3 in, 3 out).  Image i starts i * *_image_stride_bytes after d_in /
+ * d_out, its planes *_plane_stride_bytes apart, their rows *_stride_bytes apart; (w, h) is the SOURCE size, the output planes are (w << nn2x) x
+ * (h << nn2x).  Image i is BIT-identical to w2xc_convert_planes[_nn2x]_device on it with the same opts, for every option set.  Where the batched chain
+ * applies -- fp32, W2XC_KERNEL_AUTO, w2xc_opts.fusion other than W2XC_FUSION_PROG, an image that fits one band, and a three-plane model whose layers run
+ * conv3x3_first / conv3x3_wino ({32, 64, 128} -> 32) / conv3x3_wino4 / conv3x3_last (3 -> {32, 64, 128} -> ... -> 3), or the one-plane chain of
+ * w2xc_convert_batch_device -- a sub-batch of images, as many as w2xc_opts.workspace_mb holds, is ONE launch per layer; every other case runs the
+ * single-image launch sequence per image, with no host synchronisation in between.  w2xc_batch_plan tells which.  Enqueued on `hip_stream`, not synchronised.
+ * Errors, before any device is touched: those of w2xc_convert_batch_device and w2xc_convert_planes_device (n < 1, nn2x other than 0 / 1, null pointers,
+ * sizes, row strides short or no multiple of 4, plane strides short or no multiple of 4: W2XC_ERR_ARG); image strides that are no multiple of 4, output
+ * images that overlap each other or the input images: W2XC_ERR_ARG; a model whose first layer does not take n_in_planes planes: W2XC_ERR_PLANES. */
+int w2xc_convert_planes_batch_device(w2xc_model *m, int n, int nn2x, int n_in_planes, const float *d_in, size_t in_image_stride_bytes,
+                                     size_t in_plane_stride_bytes, size_t in_stride_bytes, int w, int h, float *d_out,
+                                     size_t out_image_stride_bytes, size_t out_plane_stride_bytes, size_t out_stride_bytes, void *hip_stream,
+                                     const w2xc_opts *opts);
+/* (revision 0.4.1.5) Pure host arithmetic, no device: how a batch of w x h images of n_in_planes planes (nn2x: converted at twice the size) runs with these
+ * options -- *batched = 1 where a sub-batch is one launch per layer (the conditions above; a one-plane model is planned as w2xc_convert_batch_device
+ * runs it), 0 where every image takes the single-image launch sequence; *sub_batch = images per sub-batch under w2xc_opts.workspace_mb (>= 1; 1 when
+ * not batched).  The image calls on RGB models (w2xc_process_image_rgb_u8_batch*, the RGB route of the RGBA calls, TTA passes) batch their passes under
+ * the same conditions.  W2XC_ERR_ARG for null pointers, nn2x other than 0 / 1 and bad sizes; the errors of the options and W2XC_ERR_PLANES as the call. */
+int w2xc_batch_plan(const w2xc_model *m, int n_in_planes, int w, int h, int nn2x, const w2xc_opts *opts, int *batched, int *sub_batch);
+
 /* One UNIT of the tile farm from host memory (the reference's block walk, convertRoutine.cpp:114-165, made parallel across
  * processes): output rows [row_begin, row_end) of the conversion of a w x h source plane (nn2x = 1: of its nearest-
  * neighbour 2x, main.cpp:132-140, so the output plane is 2w x 2h and row numbers are in OUTPUT coordinates).

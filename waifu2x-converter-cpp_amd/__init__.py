@@ -133,6 +133,8 @@ def _load():
                                           C.c_longlong, C.c_longlong, vp, C.POINTER(Opts)]),
         "w2xc_convert_rows_device": (ci, [vp, fp, cs, ci, ci, ci, ci, ci, ci, fp, cs, vp, C.POINTER(Opts)]),
         "w2xc_convert_batch_device": (ci, [vp, ci, ci, fp, cs, cs, ci, ci, fp, cs, cs, vp, C.POINTER(Opts)]),
+        "w2xc_convert_planes_batch_device": (ci, [vp, ci, ci, ci, fp, cs, cs, cs, ci, ci, fp, cs, cs, cs, vp, C.POINTER(Opts)]),
+        "w2xc_batch_plan": (ci, [vp, ci, ci, ci, ci, C.POINTER(Opts), C.POINTER(ci), C.POINTER(ci)]),
         "w2xc_convert_batch": (ci, [vp, ci, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, C.POINTER(Opts)]),
         "w2xc_layer_filter": (ci, [vp, ci, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, C.POINTER(Opts)]),
         "w2xc_profile_read": (ci, [vp, ci, C.POINTER(C.c_float), C.POINTER(ci), ci]),
@@ -390,6 +392,26 @@ class _ModelSet:
                                             C.byref(opts) if opts is not None else None)
         if rc != OK:
             raise W2xcError(rc, last_error())
+
+    def convert_planes_batch_device(self, n, n_in, d_in, in_image_stride_bytes, in_plane_stride_bytes, in_stride_bytes, w, h, d_out,
+                                    out_image_stride_bytes, out_plane_stride_bytes, out_stride_bytes, nn2x=False, stream=0, opts=None):
+        """Device-pointer batch of multi-plane images (w2xc_convert_planes_batch_device): n images of n_in planes of w x h, image i at d_in +
+        i * in_image_stride_bytes, all planes of the last layer out, (w << nn2x) x (h << nn2x).  Each image has the bits of
+        convert_planes[_nn2x]_device.  Asynchronous on `stream`."""
+        rc = _lib.w2xc_convert_planes_batch_device(self.handle, n, 1 if nn2x else 0, n_in, C.c_void_p(d_in), in_image_stride_bytes, in_plane_stride_bytes,
+                                                   in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes, out_plane_stride_bytes,
+                                                   out_stride_bytes, C.c_void_p(stream), C.byref(opts) if opts is not None else None)
+        if rc != OK:
+            raise W2xcError(rc, last_error())
+
+    def batch_plan(self, n_in, w, h, nn2x=False, opts=None):
+        """(batched, sub_batch) of w2xc_batch_plan: does a batch of w x h images of n_in planes run one launch per layer with these options, and how
+        many images one sub-batch takes.  Host arithmetic only."""
+        batched, sub = C.c_int(0), C.c_int(0)
+        rc = _lib.w2xc_batch_plan(self.handle, n_in, w, h, 1 if nn2x else 0, C.byref(opts) if opts is not None else None, C.byref(batched), C.byref(sub))
+        if rc != OK:
+            raise W2xcError(rc, last_error())
+        return batched.value, sub.value
 
     def convert_batch_tta_device(self, n, d_in, in_plane_stride_bytes, in_stride_bytes, w, h, d_out, out_plane_stride_bytes,
                                  out_stride_bytes, nn2x=False, stream=0, opts=None):

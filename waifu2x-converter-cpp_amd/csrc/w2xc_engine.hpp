@@ -335,7 +335,7 @@ W2xcKernelKind layer_desc(const w2xc_model *m, const RowPlan &P, int k, int y0, 
                           W2xcConvDesc &first_d, W2xcConvDesc *d, LayerSrc *next);
 
 // ---- w2xc_rows.cpp ----
-// bd != nullptr: the batch form of the launch (w2xc_convert_batch*; conv3x3_first2_wino4 / conv3x3_wino4 planar or fused-last / the gather) on bd->batch images
+// bd != nullptr: the batch form of the launch (conv3x3_first2_wino4 / conv3x3_wino4 / the gather; conv3x3_first / conv3x3_wino / conv3x3_last) on bd->batch images
 int launch_layer(DevCtx *c, const w2xc_model *m, int l, W2xcKernelKind kind, W2xcConvDesc d, hipStream_t st, const w2xc_opts &o,
                  const W2xcBatchDesc *bd = nullptr);
 
@@ -401,20 +401,32 @@ int check_planes_args(const w2xc_model *m, int up, int n_in_planes, const void *
                       size_t out_plane_stride, size_t out_stride, const w2xc_opts &o);
 
 // ---- batches of same-size planes (w2xc_convert_batch*) ----
-// the batched launch chain runs a call planned as P (one image of the batch): fp32, W2XC_KERNEL_AUTO, conv3x3_first2_wino4 -> conv3x3_wino4 (planar) ... ->
-// conv3x3_wino4 FUSE7 -> gather, one plane in and out, the whole image in one band.  Everything else takes the single-image launch sequence per image.
+// a batched launch chain runs a call planned as P (one image of the batch): fp32, W2XC_KERNEL_AUTO, the whole image in one band, and either conv3x3_first2_wino4 ->
+// conv3x3_wino4 (planar) ... -> conv3x3_wino4 FUSE7 -> gather with one plane in and out, or -- three planes in, three out -- conv3x3_first -> conv3x3_wino /
+// conv3x3_wino4 ... -> conv3x3_last.  Everything else takes the single-image launch sequence per image.
 bool batch_eligible(const w2xc_model *m, const RowPlan &P);
 // images per sub-batch for a per-image workspace of img_floats[2] floats under the call's workspace_mb budget (>= 1)
 int batch_sub_size(const w2xc_opts &o, const size_t img_floats[2]);
 // the nimg planes `out` of the (w << up) x (h << up) conversion of the w x h source planes `in` on `st`; enqueue-only.  max_sub > 0 caps the sub-batch
 // size.  The caller holds c->mu.
 int run_batch(w2xc_model *m, DevCtx *c, int nimg, int up, PlanesIn in, int w, int h, PlanesOut out, hipStream_t st, const w2xc_opts &o_in, int max_sub = 0);
+// nimg IMAGES of planes: image i's planes start in_is / out_is floats behind image 0's, in.ps / out.ps apart (out.ps != 0: all planes of the last layer;
+// 0: plane 0 alone, as RowsCall).  u8 (ROWS_U8_SRC / ROWS_U8_DST): that side is interleaved uint8 images as in RowsCall, its image stride in BYTES.
+struct BatchIO {
+    PlanesIn in; long long in_is; int n_in;
+    PlanesOut out; long long out_is;
+    int u8;
+};
+int run_batch_planes(w2xc_model *m, DevCtx *c, int nimg, int up, const BatchIO &io, int w, int h, hipStream_t st, const w2xc_opts &o_in, int max_sub = 0);
 // per-image workspace floats of the batched chain (0, 0 when P is not eligible) -- what a sub-batch of k images needs is k times this
 void batch_ws_floats(const RowPlan &P, size_t img_floats[2]);
 int check_batch_model(const w2xc_model *m);
 int check_batch_args(const w2xc_model *m, int nimg, int nn2x, int w, int h, size_t in_stride, size_t out_stride);
 int check_batch_device_args(const w2xc_model *m, int n, int nn2x, const void *d_in, size_t in_plane_stride, size_t in_stride, int w, int h, const void *d_out,
                             size_t out_plane_stride, size_t out_stride);
+int check_planes_batch_device_args(const w2xc_model *m, int n, int nn2x, int n_in_planes, const void *d_in, size_t in_image_stride, size_t in_plane_stride,
+                                   size_t in_stride, int w, int h, const void *d_out, size_t out_image_stride, size_t out_plane_stride, size_t out_stride,
+                                   const w2xc_opts &o);
 // byte ranges [lo, hi) tagged 1 = output, 0 = input (sorted in place): W2XC_ERR_ARG when an output overlaps another output or an input
 int check_batch_overlap(std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> &iv);
 

@@ -42,7 +42,8 @@ struct ImageCall {
 // planes, `dst` = the runs * nout result planes.  `var` holds tta_pass_floats(w, h, up) floats per source plane and per result plane's share
 // (8 (ni ps + no PS) in all): the input variants -- the upright group, the transposed group directly behind it -- then the output variants likewise.
 // rows = false (nin = nout = 1): the one-plane chain, run_batch on all variants of one size -- ONE batch of 8 where w == h, where the transposed group
-// continues the upright one.  rows = true: the multi-plane form, the single-image run_rows sequence per variant and run.
+// continues the upright one.  rows = true: the multi-plane form, run_batch_planes on the variants of one size as images of nin planes (8 runs of them where
+// w == h, else 4 runs + 4 runs) -- one launch per layer where the model's chain has batch kernels, the single-image run_rows sequence per variant and run elsewhere.
 // Nearest-2x commutes with every T_k: a scale pass (up = 1) spreads at source resolution and gathers at 2x.
 struct TtaPass {
     w2xc_model *m;
@@ -66,14 +67,17 @@ int tta_pass(const TtaPass &t, int runs, PlanesIn src, int w, int h, PlanesOut d
             if (int rc = run_batch(t.m, t.cm, 4 * ni, t.up, in_tr, h, w, out_tr, st, o)) return rc;
         }
     } else {
-        for (int k = 0; k < 8; k++) {
-            const PlanesOut &in = k < 4 ? in_up : in_tr, &out = k < 4 ? out_up : out_tr;
-            const int VW = (k < 4 ? w : h) << t.up, VH = (k < 4 ? h : w) << t.up;
-            for (int r = 0; r < runs; r++) {
-                const RowsCall call = RowsCall::whole(in.from((size_t)(k & 3) * ni + (size_t)r * t.nin), t.nin, VW, VH,
-                                                      out.from((size_t)(k & 3) * no + (size_t)r * t.nout), t.up);
-                if (int rc = run_rows(t.m, t.cm, call, st, o)) return rc;
-            }
+        // variant (k, run r) is "image" (k & 3) runs + r of its group: nin planes ps apart in, nout planes PS apart out.  Where the model's chain has batch
+        // kernels (batch_eligible) a group is ONE run_batch_planes launch sequence, otherwise that call is the single-image run_rows sequence per variant and run
+        const auto group = [&](int nv, const PlanesOut &in, int vw, int vh, const PlanesOut &out) {
+            const BatchIO io = {in, t.nin * ps, t.nin, out, t.nout * PS, 0};
+            return run_batch_planes(t.m, t.cm, nv * runs, t.up, io, vw, vh, st, o);
+        };
+        if (w == h) {
+            if (int rc = group(8, in_up, w, h, out_up)) return rc;
+        } else {
+            if (int rc = group(4, in_up, w, h, out_up)) return rc;
+            if (int rc = group(4, in_tr, h, w, out_tr)) return rc;
         }
     }
     HIP_TRY(w2xc_launch_tta_gather(out_up.p, out_tr.p, PS, W, H, dst.p, dst.ps, (long long)dst.rs, no, st));
@@ -183,8 +187,8 @@ RgbPlan rgb_plan(const ImageCall &c)
 }
 
 // A sub-batch of S images (S <= cap; the planes are sized by cap): per level the three planes of image i lie at level + i * 3 ps, ps floats apart.  The
-// colour stages and the shrink are one launch for the sub-batch; RGB chains have no batch kernels, so every pass is the single-image launch sequence per
-// image, enqueued back to back.  A single image is a sub-batch of one.
+// colour stages and the shrink are one launch for the sub-batch, and so is every layer of a pass of S >= 2 images where the model's chain has batch kernels
+// (run_batch_planes; elsewhere it is the single-image launch sequence per image, enqueued back to back).  A single image is a sub-batch of one: run_rows.
 // (skip: the float planes start that many bytes into the aux buffer -- reserve_aux)
 int process_rgb_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, size_t skip = 0)
 {
@@ -216,7 +220,14 @@ int process_rgb_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, s
         if (!to_u8) { nxt = base; base += 3 * (size_t)cap * ps2; }
         if (c.tta) {   // (neither from_u8 nor to_u8: rgb_plan)
             if (int rc = tta_pass(TtaPass{m, cm, up, 3, 3, true}, S, {cur, (size_t)cw, ps}, cw, ch, {nxt, (size_t)nw, ps2}, var, c.st, c.o)) return rc;
-        } else for (int i = 0; i < S; i++) {
+        } else if (S >= 2) {
+            // ONE run_batch_planes for the sub-batch (one launch per layer where the chain has batch kernels): image i's three planes 3 ps on, or -- the uint8
+            // forms -- the caller's images themselves: strides in bytes
+            const BatchIO io = {from_u8 ? PlanesIn{reinterpret_cast<const float *>(in.p), in.row, 1} : PlanesIn{cur, (size_t)cw, ps}, from_u8 ? (long long)in.img : 3 * ps, 3,
+                                to_u8 ? PlanesOut{reinterpret_cast<float *>(out.p), out.row, 1} : PlanesOut{nxt, (size_t)nw, ps2}, to_u8 ? (long long)out.img : 3 * ps2,
+                                (from_u8 ? ROWS_U8_SRC : 0) | (to_u8 ? ROWS_U8_DST : 0)};
+            if (int rc = run_batch_planes(m, cm, S, up, io, cw, ch, c.st, c.o)) return rc;
+        } else for (int i = 0; i < S; i++) {   // (a sub-batch of one: the single-image call, bands included)
             // image i's three planes, or -- the uint8 forms -- the caller's image itself: strides in bytes (Planes, w2xc_engine.hpp)
             const PlanesIn src = from_u8 ? PlanesIn{reinterpret_cast<const float *>(in.p + (size_t)i * in.img), in.row, 1} : PlanesIn{cur + (size_t)i * 3 * ps, (size_t)cw, ps};
             const PlanesOut dst = to_u8 ? PlanesOut{reinterpret_cast<float *>(out.p + (size_t)i * out.img), out.row, 1} : PlanesOut{nxt + (size_t)i * 3 * ps2, (size_t)nw, ps2};
@@ -244,8 +255,8 @@ int process_sub_batch(bool rgb, const ImageCall &c, int S, int cap, U8In in, U8O
 // The options' errors (plan_rows) of the noise pass and of the largest scale pass, and *sub = images per sub-batch of a batch: as many as
 // w2xc_opts.workspace_mb holds of the pipeline's own memory per image (the float planes of every level + the uint8 image in and out), at least 1.
 //   PLAN_RGB  first: each model takes three planes and gives three (a Y model beside an RGB one fails here too)
-//   PLAN_Y    at most the sub-batch run_batch takes at the LARGEST level where its batched chain applies (more images would only be cut again there, and
-//             the planes of a larger sub-batch would be memory without a launch saved)
+//   both      at most the sub-batch run_batch / run_batch_planes takes at the LARGEST level where a batched chain applies (more images would only be cut again
+//             there, and the planes of a larger sub-batch would be memory without a launch saved)
 // The RGBA call gives its own bytes per image (per_image; 0 = the 3-channel call's, above) and ya = 2 on the Y route: a Y brings its alpha plane, so a
 // sub-batch run_batch takes whole holds half as many images.
 enum PlanKind { PLAN_Y, PLAN_RGB };
@@ -267,7 +278,7 @@ int plan_image_call(PlanKind kind, const ImageCall &c, int *sub, size_t per_imag
         const int W = i ? c.w << c.iterations : c.w, H = i ? c.h << c.iterations : c.h;   // (the last scale iteration: the largest planes of the call)
         RowPlan P;
         if (int rc = plan_rows(pass[i], c.o, W, H, 0, 0, H, H, rgb ? 3 : 1, rgb, &P)) return rc;
-        if (!rgb && batch_eligible(pass[i], P)) {
+        if (batch_eligible(pass[i], P)) {
             size_t img_f[2];
             batch_ws_floats(P, img_f);
             k = std::min<size_t>(k, (size_t)batch_sub_size(P.o, img_f));

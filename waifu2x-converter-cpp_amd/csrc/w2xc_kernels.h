@@ -68,6 +68,8 @@ struct W2xcConvDesc {
 // single-image launch's item (first2: tile) count: the batch kernels walk batch x items items, image-major, and add i * stride to their 64-bit scalar
 // bases only -- every 32-bit lane offset and every range check of the single-image launcher stays per image.  (A struct of its own rather than fields
 // appended to W2xcConvDesc: that struct is the by-value argument of every existing kernel, and growing it would move their kernel-argument offsets.)
+// The uint8 forms (W2XC_K_FIRST_U8 / W2XC_K_LAST_U8): the descriptor's strides on the uint8 side are BYTES, and so is that side's image stride -- in_bs of
+// conv3x3_first_batch<U8>, out_bs of conv3x3_last_batch<U8>; the other side (a workspace of floats) stays in floats.
 struct W2xcBatchDesc {
     int batch;
     int items;
@@ -94,6 +96,11 @@ hipError_t w2xc_launch_first2_wino4(const W2xcConvDesc &d, hipStream_t stream);
 hipError_t w2xc_launch_wino4_batch(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream);
 hipError_t w2xc_launch_first2_wino4_batch(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream);
 hipError_t w2xc_launch_last_gather_batch(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream);
+// ... and of the multi-plane (RGB) chains: conv3x3_first_batch / conv3x3_last_batch (kind = W2XC_K_FIRST / _FIRST_U8 with three planes in, W2XC_K_LAST / _LAST_U8
+// with three planes out; w2xc_conv_batch.hip), conv3x3_wino_batch (w2xc_wino_batch_supported), and through w2xc_launch_wino4_batch the layouts
+// w2xc_wino4_batch_layout_supported names (conv3x3_wino4_batch_l: 32 NHWC planes in and / or NHWC out)
+hipError_t w2xc_launch_conv_batch(W2xcKernelKind kind, const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream);
+hipError_t w2xc_launch_wino_batch(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream);
 
 // split kernels (w2xc_split.hip); d.wpk = the w2xc_split_pack image (W2XC_K_FIRST_SPLIT: the W2XC_K_FIRST image)
 hipError_t w2xc_launch_split_mid(const W2xcConvDesc &d, hipStream_t stream);

@@ -381,182 +381,15 @@ __global__ void __launch_bounds__(WM *WN * 64, WM *WN / 4) conv3x3_mfma2(W2xcCon
 template <int CIN, int NBT, bool PLANAR = false, bool U8 = false>
 __global__ void __launch_bounds__(256) conv3x3_first(W2xcConvDesc d, int tiles_x, int ntiles)
 {
-    constexpr int ROWS = 8, MB = 2, HW = 34, HH = ROWS + 2;
-    constexpr int K = 9 * CIN, S = (K + 1) / 2;
-    constexpr int COUT = 32 * NBT;
-    constexpr int TPS = 36;   // floats per pixel in the store-transpose tile: 32 planes + 4 pad (144-byte stride: conflict-free 16-byte writes)
-    constexpr int PATCH = CIN * HH * HW, PL = (PATCH + 255) / 256;   // the tile's haloed source pixels; loads per thread
-    __shared__ float lds2[2][PATCH];   // the tile's patch, double-buffered: the next tile's is written while this one's stores are still in flight
-    __shared__ __attribute__((aligned(16))) float lbias[COUT];
-    constexpr int PLS = 68;   // planar out: floats per plane in the store-transpose tile, MB rows x 32 pixels + 4 pad (272-byte stride: conflict-free 16-byte writes)
-    __shared__ __attribute__((aligned(16))) float tps[PLANAR ? 4 * 32 * PLS : 4 * MB * 32 * TPS];   // per wave: its MB rows x 32 pixels x 32 planes
-
-    // a workgroup walks FIRST_TPW consecutive tiles (a write-bound kernel of 32 791 four-wave workgroups was bound by their turnover)
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int kk = lane >> 5, i = lane & 31;
-    const int tile_base = xcd_remap(blockIdx.x, (ntiles + FIRST_TPW - 1) / FIRST_TPW) * FIRST_TPW;
-    // The layer's weights live in REGISTERS for the workgroup's lifetime (NBT x S <= 56 values per lane), the biases in LDS.  Round 6: loaded inside the
-    // plane-block loop, the compiler gave all S of them ONE register -- fourteen L2 round trips per plane block, each behind s_waitcnt vmcnt(0) (which also
-    // waited for the block's stores), and the patch fill was a loop of one load + vmcnt(0) per pass: 3 -> 128 on 2048 x 2048 ran 0.93 ms = 2.3 TB/s of
-    // writes where the same store stream alone reaches 5.5 (tools/ubench/planar_store.hip -- the stores' shape was never the limit).
-    float bw[NBT][S];
-#pragma unroll
-    for (int nb = 0; nb < NBT; nb++)
-#pragma unroll
-        for (int s = 0; s < S; s++) bw[nb][s] = d.wpk[(nb * S + s) * 64 + lane];
-    for (int idx = threadIdx.x; idx < COUT; idx += 256) lbias[idx] = d.bias[idx];
-
-    // the patch of one tile: PL loads per thread, all in flight at once (copyMakeBorder REPLICATE and INTER_NEAREST 2x folded into the addresses)
-    auto patch_load = [&](int tile, float (&v)[PL]) {
-        const int tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x;
-        const int oy0 = tile_y * ROWS, ox0 = tile_x * 32;
-#pragma unroll
-        for (int t = 0; t < PL; t++) {
-            const int idx = min(threadIdx.x + 256 * t, PATCH - 1);
-            const int c = idx / (HH * HW), p = idx - c * (HH * HW);
-            const int py = p / HW, px = p - py * HW;
-            const int gy = clampi(oy0 + py + d.off_y, 0, d.in_h - 1) >> d.in_shift;
-            const int gx = clampi(ox0 + px + d.off_x, 0, d.in_w - 1) >> d.in_shift;
-            const long long at = (long long)c * d.in_cs + (long long)gy * d.in_rs + (long long)gx * d.in_ps;
-            if constexpr (U8) v[t] = (float)reinterpret_cast<const unsigned char *>(d.in)[at] * (float)(1.0 / 255.0);
-            else v[t] = d.in[at];
-        }
-    };
-    float pv[PL];
-    if (tile_base < ntiles) patch_load(tile_base, pv);
-    // (register VALUES from here on: an empty asm statement "uses" every weight, so the waits for their loads stand here and not -- conservatively,
-    //  in every pass -- inside the tile loop)
-#pragma unroll
-    for (int nb = 0; nb < NBT; nb++)
-#pragma unroll
-        for (int s = 0; s < S; s++) asm volatile("" : "+v"(bw[nb][s]));
-    auto patch_to_lds = [&](int buf) {
-#pragma unroll
-        for (int t = 0; t < PL; t++)
-            if (threadIdx.x + 256 * t < PATCH) lds2[buf][threadIdx.x + 256 * t] = pv[t];
-    };
-    if (tile_base < ntiles) patch_to_lds(0);
-
-  for (int it = 0; it < FIRST_TPW; it++) {
-    const int tile = tile_base + it;
-    if (tile >= ntiles) break;                       // (workgroup-uniform)
-    const int tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x;
-    const int oy0 = tile_y * ROWS, ox0 = tile_x * 32;
-    // ONE barrier per tile: this tile's patch (written behind the previous tile's first plane block, below) is complete, and every wave has read
-    // the patch of the tile before that, whose buffer the next write reuses
-    __syncthreads();
-    const float *lds = lds2[it & 1];
-    const bool have_next = it + 1 < FIRST_TPW && tile + 1 < ntiles;
-
-    float a[MB][S];
-#pragma unroll
-    for (int s = 0; s < S; s++) {
-        const int k0 = 2 * s, k1 = 2 * s + 1;
-        const int off0 = (k0 / 9) * (HH * HW) + ((k0 % 9) / 3) * HW + (k0 % 9) % 3;
-        const int off1 = k1 < K ? (k1 / 9) * (HH * HW) + ((k1 % 9) / 3) * HW + (k1 % 9) % 3 : 0;
-        const int off = kk ? off1 : off0;
-#pragma unroll
-        for (int mb = 0; mb < MB; mb++) a[mb][s] = lds[(wave * MB + mb) * HW + i + off];
-    }
-    // The next tile's patch is fetched under plane block 0's MFMAs and goes to LDS IN FRONT of that block's stores: vmcnt counts in order, so a wait
-    // for these loads also waits for every store issued before them -- here the previous tile's, a whole tile old; at the tile's end it would be
-    // this tile's own 32 stores, just issued (the compiler cannot count stores behind the edge tests and waits for all of them: measured, the
-    // workgroup then runs store-acknowledge to store-acknowledge).
-    if (have_next) patch_load(tile + 1, pv);
-
-    if constexpr (PLANAR) {
-        // planar out (the layout conv3x3_wino4 reads).  Pixels = MFMA A, weights = B: the accumulator tile is [pixel][plane], a lane owns plane 32 nb + i and per
-        // register quad q the 4 CONSECUTIVE PIXELS 8q + 4kk .. +3 of a row.  The wave's MB rows x 32 pixels x 32 planes change owner through LDS (own region,
-        // no workgroup barrier) and leave as 16-byte stores, 8 lanes = the 128-byte line of one (plane, row): 8 store instructions per plane block where the
-        // dword form of rounds 3-5 (a half-wave = one line) issued 32 -- at ~28 cycles of the CU's address path per wave instruction those were the kernel's
-        // time once the weight loads were out of the way (0.52 ms; stores alone in that shape: tools/ubench/planar_store.hip).
-        float *tw = tps + wave * (32 * PLS);
-#pragma unroll
-        for (int nb = 0; nb < NBT; nb++) {
-            const float bv = lbias[nb * 32 + i];
-            f32x16 acc[MB];
-#pragma unroll
-            for (int mb = 0; mb < MB; mb++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) acc[mb][r] = bv;
-#pragma unroll
-            for (int s = 0; s < S; s++)
-#pragma unroll
-                for (int mb = 0; mb < MB; mb++)
-                    acc[mb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mb][s], bw[nb][s], acc[mb], 0, 0, 0);
-            if (nb == 0 && have_next) patch_to_lds((it + 1) & 1);
-#pragma unroll
-            for (int mb = 0; mb < MB; mb++)
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; e++) v[e] = leaky(acc[mb][4 * q + e]);
-                    *reinterpret_cast<f32x4 *>(tw + i * PLS + mb * 32 + 8 * q + 4 * kk) = v;
-                }
-            // (16-byte stores want rows and planes on 16-byte boundaries and room for a row's last quad: the engine's workspaces have both -- rows of
-            //  roundup32(w) floats -- and the launcher refuses anything else; the quad's columns beyond out_w hold finite values nobody reads)
-            // lane = (pixel quad j, row mb, plane pl0 of a group of four); instruction n of a plane block covers planes 32 nb + 4 n + pl0
-            const int j = lane & 7, mb = (lane >> 3) % MB, pl0 = (lane >> 3) / MB;
-            static_assert(MB == 2, "lane map of the planar stores");
-            const float *tr = tw + pl0 * PLS + mb * 32 + 4 * j;
-            const int y = oy0 + wave * MB + mb, x = ox0 + 4 * j;
-            float *ob = d.out + ((long long)pl0 * d.out_cs + (long long)y * d.out_rs + x);   // + a wave-uniform plane offset per instruction
-#pragma unroll
-            for (int n = 0; n < 8; n++) {
-                const f32x4 v = *reinterpret_cast<const f32x4 *>(tr + n * 4 * PLS);
-                if (y < d.out_h && x < d.out_w) *reinterpret_cast<f32x4 *>(ob + (long long)(nb * 32 + n * 4) * d.out_cs) = v;
-            }
-        }
-        continue;   // (next tile)
-    }
-
-    // NHWC out.  Operands swapped (weights = MFMA A, pixels = B): the accumulator tile is [plane][pixel], a lane owns pixel ox0 + i and
-    // per register quad q the 4 consecutive planes 32*nb + 8q + 4kk .. +3 -> one 16-byte store per quad instead of 4 scattered dwords;
-    // the accumulators start at the bias.
-#pragma unroll
-    for (int nb = 0; nb < NBT; nb++) {
-        f32x4 bq[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) bq[q] = *reinterpret_cast<const f32x4 *>(lbias + nb * 32 + 8 * q + 4 * kk);
-        f32x16 acc[MB];
-#pragma unroll
-        for (int mb = 0; mb < MB; mb++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[mb][r] = bq[r >> 2][r & 3];
-#pragma unroll
-        for (int s = 0; s < S; s++)
-#pragma unroll
-            for (int mb = 0; mb < MB; mb++)
-                acc[mb] = __builtin_amdgcn_mfma_f32_32x32x2f32(bw[nb][s], a[mb][s], acc[mb], 0, 0, 0);
-        if (nb == 0 && have_next) patch_to_lds((it + 1) & 1);
-        // Stores: a lane holds 4 x 4 consecutive planes of ONE pixel, so direct stores write 32-byte pieces of 32 different cache lines per
-        // instruction -- 3.4-3.6 TB/s where a pure write stream reaches 6.9 (tools/ubench/hbm_streams.py).  The wave's MB x 32 pixels x 32
-        // planes go through LDS instead (own region, no workgroup barrier) and leave as whole lines: 8 consecutive lanes = one pixel's
-        // 128 bytes, 64 lanes = 8 pixels (1 KiB contiguous when COUT = 32).
-        float *tw = tps + wave * (MB * 32 * TPS);
-#pragma unroll
-        for (int mb = 0; mb < MB; mb++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; e++) v[e] = leaky(acc[mb][4 * q + e]);
-                *reinterpret_cast<f32x4 *>(tw + (mb * 32 + i) * TPS + 8 * q + 4 * kk) = v;
-            }
-#pragma unroll
-        for (int n = 0; n < MB * 4; n++) {
-            const int c = n * 64 + lane;             // 16-byte chunk c of the wave's MB x 32 x 8 chunks
-            const int p = c >> 3, ch = c & 7;         // pixel p = mb * 32 + x, chunk ch of its 32 planes
-            const int mb = p >> 5, px = p & 31;
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(tw + p * TPS + 4 * ch);
-            const int y = oy0 + wave * MB + mb, x = ox0 + px;
-            if (y < d.out_h && x < d.out_w)
-                *reinterpret_cast<f32x4 *>(d.out + (long long)y * d.out_rs + (long long)x * COUT + nb * 32 + 4 * ch) = v;
-        }
-    }
-  }
+#define FLB_ONLY(...)
+#define FLB_SEL(b_, s_) s_
+#define FLB_IN d.in
+#define FLB_OUT d.out
+#include "w2xc_first_body.inc"
+#undef FLB_OUT
+#undef FLB_IN
+#undef FLB_SEL
+#undef FLB_ONLY
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -579,109 +412,15 @@ __global__ void __launch_bounds__(256) conv3x3_first(W2xcConvDesc d, int tiles_x
 template <int CIN, int COUT, bool U8 = false>
 __global__ void __launch_bounds__(256) conv3x3_last(W2xcConvDesc d, int tiles_x, int ntiles)
 {
-    constexpr int ROWS = 8, HW = 34, HH = ROWS + 2, NPIX = HH * HW;
-    constexpr int NBLK = (NPIX + 15) / 16;
-    constexpr int N = 9 * COUT, NB16 = (N + 15) / 16;
-    constexpr int GS = N | 1;                  // odd LDS row stride
-    constexpr int S4 = CIN / 16;
-    __shared__ float G[NBLK * 16 * GS];
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int kk = lane >> 4, i = lane & 15;
-
-    // the layer's weights once per workgroup, which walks LAST_TPW consecutive tiles (round 6: one tile per workgroup re-read the 16 KiB image per tile,
-    // and a wave's pixel blocks ran load -> wait -> 64 MFMAs one after the other: 3.9 TB/s of reads on 128 -> 3)
-    float b[S4][4][NB16];
-#pragma unroll
-    for (int s4 = 0; s4 < S4; s4++)
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-#pragma unroll
-            for (int nb = 0; nb < NB16; nb++) b[s4][j][nb] = d.wpk[((s4 * 4 + j) * NB16 + nb) * 64 + lane];
-
-    // the 16 channels-of-four of pixel block `blk` of tile `tile` (clamped: the haloed tile's pixels outside the plane repeat the edge)
-    auto blk_load = [&](int tile, int blk, f32x4 (&v)[S4]) {
-        const int tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x;
-        int q = blk * 16 + i;
-        q = q < NPIX ? q : NPIX - 1;
-        const int py = q / HW, px = q - py * HW;
-        const int gy = clampi(tile_y * ROWS + py + d.off_y, 0, d.in_h - 1);
-        const int gx = clampi(tile_x * 32 + px + d.off_x, 0, d.in_w - 1);
-        const f32x4 *src = reinterpret_cast<const f32x4 *>(d.in + (long long)gy * d.in_rs + (long long)gx * CIN) + kk;
-#pragma unroll
-        for (int s4 = 0; s4 < S4; s4++) v[s4] = src[s4 * 4];
-    };
-
-    float bo[COUT];
-#pragma unroll
-    for (int o = 0; o < COUT; o++) bo[o] = d.bias[o];
-    const int tile_base = xcd_remap(blockIdx.x, (ntiles + LAST_TPW - 1) / LAST_TPW) * LAST_TPW;
-    f32x4 av[S4];
-    if (tile_base < ntiles) blk_load(tile_base, wave, av);
-    // (register VALUES from here on: left pending, the weights' waits sit INSIDE the loop -- s_waitcnt vmcnt(7) behind the eight loads of the next
-    //  block, i.e. a wait for the first of those -- in every pass)
-#pragma unroll
-    for (int s4 = 0; s4 < S4; s4++)
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-#pragma unroll
-            for (int nb = 0; nb < NB16; nb++) asm volatile("" : "+v"(b[s4][j][nb]));
-    for (int it = 0; it < LAST_TPW; it++) {
-        const int tile = tile_base + it;
-        if (tile >= ntiles) break;                       // (workgroup-uniform)
-        const int tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x;
-        const int oy0 = tile_y * ROWS, ox0 = tile_x * 32;
-        for (int blk = wave; blk < NBLK; blk += 4) {
-            // the next block's loads (this tile's, or the first of the next tile) fly under this block's MFMAs
-            f32x4 nv[S4];
-            const bool more = blk + 4 < NBLK;
-            const bool next_tile = !more && it + 1 < LAST_TPW && tile + 1 < ntiles;
-            if (more) blk_load(tile, blk + 4, nv);
-            else if (next_tile) blk_load(tile + 1, wave, nv);
-            f32x4 acc[NB16];
-#pragma unroll
-            for (int nb = 0; nb < NB16; nb++) acc[nb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s4 = 0; s4 < S4; s4++)
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-#pragma unroll
-                    for (int nb = 0; nb < NB16; nb++)
-                        acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s4][j], b[s4][j][nb], acc[nb], 0, 0, 0);
-            // C/D map of 16x16 MFMA: column = lane&15 (n), row = 4*(lane>>4) + r (pixel in block)
-#pragma unroll
-            for (int nb = 0; nb < NB16; nb++) {
-                const int n = nb * 16 + i;
-                if (n < N) {
-#pragma unroll
-                    for (int r = 0; r < 4; r++) G[(blk * 16 + kk * 4 + r) * GS + n] = acc[nb][r];
-                }
-            }
-            if (more || next_tile) {
-#pragma unroll
-                for (int s4 = 0; s4 < S4; s4++) av[s4] = nv[s4];
-            }
-        }
-        __syncthreads();
-
-        for (int p = threadIdx.x; p < ROWS * 32; p += 256) {
-            const int py = p >> 5, px = p & 31;
-            const int y = oy0 + py, x = ox0 + px;
-            if (y >= d.out_h || x >= d.out_w) continue;
-#pragma unroll
-            for (int o = 0; o < COUT; o++) {
-                float v = 0.0f;
-#pragma unroll
-                for (int tap = 0; tap < 9; tap++)
-                    v += G[((py + tap / 3) * HW + px + tap % 3) * GS + tap * COUT + o];
-                const long long at = (long long)o * d.out_cs + (long long)y * d.out_rs + (long long)x * d.out_ps;
-                if constexpr (U8) reinterpret_cast<unsigned char *>(d.out)[at] = (unsigned char)clampi(__float2int_rn(leaky(v + bo[o]) * 255.0f), 0, 255);
-                else d.out[at] = leaky(v + bo[o]);
-            }
-        }
-        __syncthreads();                                 // (G is rewritten by the next tile)
-    }
+#define FLB_ONLY(...)
+#define FLB_SEL(b_, s_) s_
+#define FLB_IN d.in
+#define FLB_OUT d.out
+#include "w2xc_last_body.inc"
+#undef FLB_OUT
+#undef FLB_IN
+#undef FLB_SEL
+#undef FLB_ONLY
 }
 
 // replicate-padded planar copy: dst plane c (ph x pw pixels, row stride d_rs, plane stride d_cs) = src(clamp(y - pad), clamp(x - pad)) -- the

@@ -180,7 +180,8 @@ const char *w2xc_last_error(void) { return g_last_error.c_str(); }
 //          w2xc_tta_spread_device / w2xc_tta_gather_device (additive; w2xc_opts stays 56 bytes)
 // 0.4.1.3: the batch forms of the RGBA call, w2xc_process_image_rgba_u8_batch[_device] (additive; w2xc_opts stays 56 bytes)
 // 0.4.1.4: w2xc_resize_linear_device, the INTER_LINEAR resize of the image calls' shrink as a building block (additive; w2xc_opts stays 56 bytes)
-const char *w2xc_version(void) { return "w2xc_hip 0.4.1.4 (gfx950)"; }
+// 0.4.1.5: w2xc_convert_planes_batch_device (n images of several planes: the batched chain of RGB models) and w2xc_batch_plan (additive; w2xc_opts stays 56 bytes)
+const char *w2xc_version(void) { return "w2xc_hip 0.4.1.5 (gfx950)"; }
 
 int w2xc_plan_rows(const w2xc_model *m, int w, int view_y0, int view_h, int plane_h, int row_begin, int row_end, const w2xc_opts *opts, w2xc_row_plan *plan)
 try {

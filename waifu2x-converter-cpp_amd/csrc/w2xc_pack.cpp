@@ -150,6 +150,13 @@ bool w2xc_wino4_batch_supported(int cin, int cout, bool fused_last)
 {
     return fused_last ? (cin == 64 || cin == 128) && (cout == 64 || cout == 128) : w2xc_wino4_supported(cin, cout);
 }
+bool w2xc_wino4_batch_layout_supported(int cin, int cout, bool in_nhwc, bool out_planar)
+{
+    if (cout != 64 && cout != 128) return false;
+    if (in_nhwc) return cin == 32;
+    return out_planar ? w2xc_wino4_batch_supported(cin, cout, false) : (cin == 64 || cin == 128);
+}
+bool w2xc_wino_batch_supported(int cin, int cout) { return is_mid(cin) && cout == 32; }
 
 // ... and PROG's control words: per job (tile row, group of 8 tile columns of the launch's region) an arrival counter and a queue slot, + head and tail
 void w2xc_wino4_prog_jobs(int out_w, int out_h, int wino_py, int *tile_rows, int *groups)

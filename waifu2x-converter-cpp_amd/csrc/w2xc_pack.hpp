@@ -48,6 +48,11 @@ size_t w2xc_wino4_prog_counters(int out_w, int out_h, int wino_py);
 void w2xc_wino4_prog_jobs(int out_w, int out_h, int wino_py, int *tile_rows, int *groups);
 // a batch instantiation (conv3x3_wino4_batch) exists for this layer
 bool w2xc_wino4_batch_supported(int cin, int cout, bool fused_last);
+// ... and the layouts of the multi-plane (RGB) chains, no fused last layer: 32 NHWC planes in (the layer behind conv3x3_first / conv3x3_wino) -> 64 / 128
+// planes, planar or NHWC out; 64 / 128 planar planes in -> NHWC out (the layer in front of conv3x3_last).  Planar in and out: the predicate above.
+bool w2xc_wino4_batch_layout_supported(int cin, int cout, bool in_nhwc, bool out_planar);
+// conv3x3_wino_batch: the layers W2XC_KERNEL_AUTO sends to conv3x3_wino ({32, 64, 128} -> 32 planes)
+bool w2xc_wino_batch_supported(int cin, int cout);
 
 // conv3x3_first2_wino4 (w2xc_first2_wino4.hip): layer 2's image is 36 * 32 * 32 floats
 bool w2xc_first2_wino4_supported(int cin1, int cout1, int cout2);

@@ -60,11 +60,15 @@ hipError_t launch_kind(W2xcKernelKind kind, int midv, const W2xcConvDesc &d, con
     case W2XC_K_MID_SPLIT: return bd ? hipErrorInvalidValue : w2xc_launch_split_mid(d, st);
     case W2XC_K_FIRST_SPLIT: return bd ? hipErrorInvalidValue : w2xc_launch_split_first(d, st);
     case W2XC_K_FIRST2_SPLIT: return bd ? hipErrorInvalidValue : w2xc_launch_first2_split(d, st);
+    case W2XC_K_FIRST:
+    case W2XC_K_FIRST_U8:
+    case W2XC_K_LAST:
+    case W2XC_K_LAST_U8: return bd ? w2xc_launch_conv_batch(kind, d, *bd, st) : w2xc_launch_conv(kind, d, st);
     default: break;
     }
     if (midv == MID_WINO4) return bd ? w2xc_launch_wino4_batch(d, *bd, st) : w2xc_launch_wino4(d, st);
-    if (bd) return hipErrorInvalidValue;
-    return midv == MID_WINO32 ? w2xc_launch_wino(d, st) : w2xc_launch_conv(kind, d, st);
+    if (midv == MID_WINO32) return bd ? w2xc_launch_wino_batch(d, *bd, st) : w2xc_launch_wino(d, st);
+    return bd ? hipErrorInvalidValue : w2xc_launch_conv(kind, d, st);
 }
 
 }  // namespace
@@ -124,8 +128,8 @@ struct Band {
     int y0, y1, rb;
     int in_chunk;   // > 0: layer 1 (or the fused layers 1 + 2) runs in chunks of this many rows behind the upload (first_chunks)
     int u8;         // ROWS_U8_SRC / ROWS_U8_DST: the view / `out` is an interleaved uint8 image, its strides are in bytes (no hooks: every launch is the plain one)
-    // run_batch: > 0 = every launch is the batch form on this many images of the band's geometry (no hooks: every launch is the plain one), image i in_bs / out_bs
-    // floats behind image 0 in the caller's planes and img_f[j] floats behind it in workspace j
+    // run_batch_planes: > 0 = every launch is the batch form on this many images of the band's geometry (no hooks: every launch is the plain one), image i in_bs /
+    // out_bs floats (a uint8 view / `out`: bytes) behind image 0 in the caller's planes and img_f[j] floats behind it in workspace j
     int batch = 0;
     long long in_bs = 0, out_bs = 0;
     size_t img_f[2] = {0, 0};
@@ -335,7 +339,7 @@ int run_band(Band &B, const LayerSrc &view, int up)
     const int n = P.n;
     // a batched band is one plain launch per layer: every other strategy needs hooks or W2XC_FUSION_PROG, the repack a last layer that cannot store planar
     // (batch_eligible lets none of them through; nothing is launched otherwise)
-    if (B.batch && (hk || B.u8 || o.fusion == W2XC_FUSION_PROG || !P.last_direct))
+    if (B.batch && (hk || o.fusion == W2XC_FUSION_PROG || !P.last_direct))
         return fail(W2XC_ERR_ARG, "internal error: a batched band that is not one plain launch per layer");
     // layer 1 of this band in row chunks (each waits only for the rows it reads) or in one launch behind the whole upload
     const W2xcKernelKind kind1 = layer_kind(m, 0, o);
@@ -374,14 +378,21 @@ int run_band(Band &B, const LayerSrc &view, int up)
 
 }  // namespace
 
+// the uint8 views of a call planned as P: no hooks, channels one byte apart, and the layers they touch have the uint8 kernels
+static int check_u8_views(const w2xc_model *m, const RowPlan &P, int u8, bool hooks, long long in_ps, long long out_ps)
+{
+    if (u8 && (hooks || ((u8 & ROWS_U8_SRC) && (in_ps != 1 || !u8_source_layer(m, P.o))) ||
+               ((u8 & ROWS_U8_DST) && (out_ps != 1 || !P.last_direct || !u8_sink_layer(m, P.o)))))
+        return fail(W2XC_ERR_ARG, "internal error: a uint8 view for a layer without the uint8 kernel");
+    return W2XC_OK;
+}
+
 // one call of the band loop (RowsCall, w2xc_engine.hpp): plan, reserve the workspaces, run_band per band
 int run_rows(w2xc_model *m, DevCtx *c, const RowsCall &r, hipStream_t st, const w2xc_opts &o_in)
 {
     RowPlan P;
     if (int rc = plan_rows(m, o_in, r.w, r.view_h, r.view_y0, r.ra, r.rb, r.plane_h, r.n_in, r.out.ps != 0, &P)) return rc;
-    if (r.u8 && (r.hk || ((r.u8 & ROWS_U8_SRC) && (r.in.ps != 1 || !u8_source_layer(m, P.o))) ||
-               ((r.u8 & ROWS_U8_DST) && (r.out.ps != 1 || !P.last_direct || !u8_sink_layer(m, P.o)))))
-        return fail(W2XC_ERR_ARG, "internal error: a uint8 view for a layer without the uint8 kernel");
+    if (int rc = check_u8_views(m, P, r.u8, r.hk != nullptr, r.in.ps, r.out.ps)) return rc;
     for (int i = 0; i < 2; i++)
         if (P.need[i]) { int rc = c->ws[i].reserve((P.need[i] + 3) / 4 * sizeof(float), "the activation workspace"); if (rc) return rc; }
     LayerSrc view;   // the source view; its first row is plane row view_y0
@@ -421,21 +432,32 @@ int check_planes_args(const w2xc_model *m, int up, int n_in_planes, const void *
     return W2XC_OK;
 }
 
-// nimg planes of one size (w2xc_convert_batch*).  The plan is that of ONE image, exactly as the single-plane device call makes it.  Where the batched chain
+// nimg images of one size (w2xc_convert_batch*: one plane each; w2xc_convert_planes_batch_device and the RGB image calls: io.n_in planes in, all planes of
+// the last layer out).  The plan is that of ONE image, exactly as the single-image device call makes it.  Where a batched chain
 // applies (batch_eligible), a sub-batch of k images is run_band on ONE batched band [0, H): one launch per layer, the descriptor of every launch the
 // single-image one (same regions, offsets, wino_py, clamps, strides), and the batch kernels add image x stride (Band::launch) to their scalar bases -- input
 // planes, the k per-image blocks of the two workspaces, output planes.  Everything else runs the single-image launch sequence per image on the same stream
 // (no host synchronisation in between).
-int run_batch(w2xc_model *m, DevCtx *c, int nimg, int up, PlanesIn in, int w, int h, PlanesOut out, hipStream_t st, const w2xc_opts &o_in, int max_sub)
+int run_batch_planes(w2xc_model *m, DevCtx *c, int nimg, int up, const BatchIO &io, int w, int h, hipStream_t st, const w2xc_opts &o_in, int max_sub)
 {
     const int W = w << up, H = h << up;
     RowPlan P;
-    if (int rc = plan_rows(m, o_in, W, H, 0, 0, H, H, 1, false, &P)) return rc;
+    if (int rc = plan_rows(m, o_in, W, H, 0, 0, H, H, io.n_in, io.out.ps != 0, &P)) return rc;
+    // image i's view: its stride is floats, or -- a uint8 image -- bytes
+    const auto image_in = [&](size_t i) -> PlanesIn {
+        if (io.u8 & ROWS_U8_SRC) return {reinterpret_cast<const float *>(reinterpret_cast<const unsigned char *>(io.in.p) + i * (size_t)io.in_is), io.in.rs, io.in.ps};
+        return {io.in.p + i * (size_t)io.in_is, io.in.rs, io.in.ps};
+    };
+    const auto image_out = [&](size_t i) -> PlanesOut {
+        if (io.u8 & ROWS_U8_DST) return {reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(io.out.p) + i * (size_t)io.out_is), io.out.rs, io.out.ps};
+        return {io.out.p + i * (size_t)io.out_is, io.out.rs, io.out.ps};
+    };
     if (!batch_eligible(m, P)) {
         for (int i = 0; i < nimg; i++)
-            if (int rc = run_rows(m, c, RowsCall::whole(in.plane(i), 1, W, H, out.plane(i), up), st, o_in)) return rc;
+            if (int rc = run_rows(m, c, RowsCall::whole(image_in(i), io.n_in, W, H, image_out(i), up, io.u8), st, o_in)) return rc;
         return W2XC_OK;
     }
+    if (int rc = check_u8_views(m, P, io.u8, false, io.in.ps, io.out.ps)) return rc;
     size_t img_f[2];
     batch_ws_floats(P, img_f);
     int sub = batch_sub_size(P.o, img_f);
@@ -445,14 +467,23 @@ int run_batch(w2xc_model *m, DevCtx *c, int nimg, int up, PlanesIn in, int w, in
         if (img_f[i]) { int rc = c->ws[i].reserve(img_f[i] * (size_t)sub * sizeof(float), "the activation workspace"); if (rc) return rc; }
 
     for (int b0 = 0; b0 < nimg; b0 += sub) {
-        Band B = {m, c, P, nullptr, st, out.p + (size_t)b0 * out.ps, (long long)out.rs, 0, 0, H, H, 0, 0};
-        B.batch = std::min(sub, nimg - b0); B.in_bs = in.ps; B.out_bs = out.ps;
+        const PlanesIn in0 = image_in(b0);
+        Band B = {m, c, P, nullptr, st, image_out(b0).p, (long long)io.out.rs, io.out.ps, 0, H, H, 0, io.u8};
+        B.batch = std::min(sub, nimg - b0); B.in_bs = io.in_is; B.out_bs = io.out_is;
         B.img_f[0] = img_f[0]; B.img_f[1] = img_f[1];
         LayerSrc view;   // (as run_rows makes it: the W x H plane, also where up = 1)
-        view.p = in.p + (size_t)b0 * in.ps; view.rs = (long long)in.rs; view.h = H; view.w = W;
+        view.p = in0.p; view.rs = (long long)in0.rs; view.cs = in0.ps; view.h = H; view.w = W;
+        if (io.u8 & ROWS_U8_SRC) view.ps = 3;
         if (int rc = run_band(B, view, up)) return rc;
     }
     return W2XC_OK;
+}
+
+// one plane in, one plane out per image: plane i at in.p + i * in.ps
+int run_batch(w2xc_model *m, DevCtx *c, int nimg, int up, PlanesIn in, int w, int h, PlanesOut out, hipStream_t st, const w2xc_opts &o_in, int max_sub)
+{
+    const BatchIO io = {{in.p, in.rs, 0}, in.ps, 1, {out.p, out.rs, 0}, out.ps, 0};
+    return run_batch_planes(m, c, nimg, up, io, w, h, st, o_in, max_sub);
 }
 
 // the argument checks of the batch entry points (no device is touched): n >= 1, sizes, strides, planes that do not overlap
@@ -478,6 +509,27 @@ int check_batch_device_args(const w2xc_model *m, int n, int nn2x, const void *d_
     if (ranges_overlap(d_in, (size_t)(n - 1) * in_plane_stride_bytes + in_ext, d_out, (size_t)(n - 1) * out_plane_stride_bytes + out_ext))
         return fail(W2XC_ERR_ARG, "output planes overlap the input planes");
     return check_batch_model(m);
+}
+
+// everything w2xc_convert_planes_batch_device refuses: check_batch_args + check_planes_args, the plane counts, and images that overlap
+int check_planes_batch_device_args(const w2xc_model *m, int n, int nn2x, int n_in_planes, const void *d_in, size_t in_image_stride_bytes, size_t in_plane_stride_bytes,
+                                   size_t in_stride_bytes, int w, int h, const void *d_out, size_t out_image_stride_bytes, size_t out_plane_stride_bytes,
+                                   size_t out_stride_bytes, const w2xc_opts &o)
+{
+    if (int rc = check_batch_args(m, n, nn2x, w, h, in_stride_bytes, out_stride_bytes)) return rc;
+    if (int rc = check_planes_args(m, nn2x, n_in_planes, d_in, in_plane_stride_bytes, in_stride_bytes, w, h, d_out, out_plane_stride_bytes, out_stride_bytes, o)) return rc;
+    if (m->layers.empty()) return fail(W2XC_ERR_ARG, "model has no layers");
+    if (m->layers[0].nin != n_in_planes)
+        return fail(W2XC_ERR_PLANES, "Error : Model-filter : \nnumber of input planes mismatch.\n%d,%d", n_in_planes, m->layers[0].nin);
+    if ((in_image_stride_bytes & 3) || (out_image_stride_bytes & 3)) return fail(W2XC_ERR_ARG, "image strides must be multiples of 4 bytes");
+    const int H = h << nn2x, W = w << nn2x, nout = m->layers.back().nout;
+    const size_t in_ext = (size_t)(n_in_planes - 1) * in_plane_stride_bytes + image_extent(h, in_stride_bytes, w, 4);
+    const size_t out_ext = (size_t)(nout - 1) * out_plane_stride_bytes + image_extent(H, out_stride_bytes, W, 4);
+    if (n > 1 && out_image_stride_bytes < out_ext)
+        return fail(W2XC_ERR_ARG, "output images overlap each other (image stride %zu < %zu bytes)", out_image_stride_bytes, out_ext);
+    if (ranges_overlap(d_in, (size_t)(n - 1) * in_image_stride_bytes + in_ext, d_out, (size_t)(n - 1) * out_image_stride_bytes + out_ext))
+        return fail(W2XC_ERR_ARG, "output images overlap the input images");
+    return W2XC_OK;
 }
 
 // [lo, hi) byte ranges: does any output overlap another output or any input?  (inputs may share memory with each other)
@@ -584,6 +636,46 @@ try {
     LockedCtx lc;
     if ((rc = lc.open(nullptr, m, o.device))) return rc;
     return run_batch(m, lc.cs, n, nn2x, {d_in, in_stride_bytes / 4, in_ps}, w, h, {d_out, out_stride_bytes / 4, out_ps}, (hipStream_t)hip_stream, o);
+} W2XC_CATCH_ALL
+
+// a one-plane model gives one plane: the call is then w2xc_convert_batch_device's (the same launches as w2xc_convert_planes_device on each image)
+static bool one_plane_model(const w2xc_model *m, int n_in_planes) { return n_in_planes == 1 && m->layers.back().nout == 1; }
+
+int w2xc_convert_planes_batch_device(w2xc_model *m, int n, int nn2x, int n_in_planes, const float *d_in, size_t in_image_stride_bytes, size_t in_plane_stride_bytes,
+                                     size_t in_stride_bytes, int w, int h, float *d_out, size_t out_image_stride_bytes, size_t out_plane_stride_bytes,
+                                     size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts)
+try {
+    const w2xc_opts o = resolve_opts(opts);
+    int rc = check_planes_batch_device_args(m, n, nn2x, n_in_planes, d_in, in_image_stride_bytes, in_plane_stride_bytes, in_stride_bytes, w, h, d_out,
+                                            out_image_stride_bytes, out_plane_stride_bytes, out_stride_bytes, o);
+    if (rc) return rc;
+    const bool one = one_plane_model(m, n_in_planes);
+    const BatchIO io = {{d_in, in_stride_bytes / 4, (long long)(in_plane_stride_bytes / 4)}, (long long)(in_image_stride_bytes / 4), n_in_planes,
+                        {d_out, out_stride_bytes / 4, one ? 0 : (long long)(out_plane_stride_bytes / 4)}, (long long)(out_image_stride_bytes / 4), 0};
+    LockedCtx lc;
+    if ((rc = lc.open(nullptr, m, o.device))) return rc;
+    return run_batch_planes(m, lc.cs, n, nn2x, io, w, h, (hipStream_t)hip_stream, o);
+} W2XC_CATCH_ALL
+
+// host arithmetic only: the plan of one image of the batch, as run_batch_planes makes it
+int w2xc_batch_plan(const w2xc_model *m, int n_in_planes, int w, int h, int nn2x, const w2xc_opts *opts, int *batched, int *sub_batch)
+try {
+    if (!m || !batched || !sub_batch) return fail(W2XC_ERR_ARG, "null argument");
+    if (nn2x != 0 && nn2x != 1) return fail(W2XC_ERR_ARG, "nn2x must be 0 or 1");
+    if (int rc = check_plane_size(w, h, true)) return rc;
+    if (m->layers.empty()) return fail(W2XC_ERR_ARG, "model has no layers");
+    const w2xc_opts o = resolve_opts(opts);
+    const int W = w << nn2x, H = h << nn2x;
+    RowPlan P;
+    if (int rc = plan_rows(m, o, W, H, 0, 0, H, H, n_in_planes, !one_plane_model(m, n_in_planes), &P)) return rc;
+    *batched = batch_eligible(m, P) ? 1 : 0;
+    *sub_batch = 1;
+    if (*batched) {
+        size_t img_f[2];
+        batch_ws_floats(P, img_f);
+        *sub_batch = batch_sub_size(P.o, img_f);
+    }
+    return W2XC_OK;
 } W2XC_CATCH_ALL
 
 }  // extern "C"

@@ -403,12 +403,46 @@ W2xcKernelKind layer_desc(const w2xc_model *m, const RowPlan &P, int k, int y0, 
 // conv3x3_first2_wino4 (layers 1 + 2), conv3x3_wino4 with planar planes in and out (layers 3 .. n - 2), conv3x3_wino4 FUSE7 (layer n - 1 + the last layer's
 // taps), the gather -- with one plane in, one plane out and the whole image in one band.  The decision is on the plan of ONE image, so it is the chain the
 // single-image call runs with the same options: an image of a batch is bit-identical to it either way.
+//
+// The second chain is that of a multi-plane (RGB) model (w2xc_convert_planes_batch_device, the RGB image calls, their TTA passes), under the same conditions:
+// conv3x3_first (three planes in; NHWC or planar out), then W2XC_K_MFMA layers run by conv3x3_wino4 or conv3x3_wino in a layout combination that has a batch
+// form (w2xc_wino4_batch_supported / w2xc_wino4_batch_layout_supported / w2xc_wino_batch_supported), then conv3x3_last storing all three planes in place.
+namespace {
+bool batch_chain_planes(const w2xc_model *m, const RowPlan &P)
+{
+    const w2xc_opts &o = P.o;
+    const int n = P.n;
+    if (n < 2 || !P.all_out || !P.last_direct) return false;
+    if (m->layers[0].nin != 3 || m->layers[n - 1].nout != 3) return false;
+    if (layer_kind(m, 0, o) != W2XC_K_FIRST || layer_kind(m, n - 1, o) != W2XC_K_LAST || out_terms_of(m, 0, o) != 0) return false;
+    if (planar_between(m, n - 2, o)) return false;   // (conv3x3_last reads NHWC pixels)
+    for (int l = 1; l <= n - 2; l++) {
+        const HostLayer &hl = m->layers[l];
+        if (layer_kind(m, l, o) != W2XC_K_MFMA || out_terms_of(m, l, o) != 0) return false;
+        const bool in_planar = planar_between(m, l - 1, o), out_planar = planar_between(m, l, o);
+        switch (layer_mid_variant(m, l, o)) {
+        case MID_WINO4:
+            if (in_planar && out_planar ? !w2xc_wino4_batch_supported(hl.nin, hl.nout, false) : !w2xc_wino4_batch_layout_supported(hl.nin, hl.nout, !in_planar, out_planar))
+                return false;
+            break;
+        case MID_WINO32:
+            if (in_planar || out_planar || !w2xc_wino_batch_supported(hl.nin, hl.nout)) return false;
+            break;
+        default: return false;
+        }
+    }
+    return true;
+}
+}  // namespace
+
 bool batch_eligible(const w2xc_model *m, const RowPlan &P)
 {
     const w2xc_opts &o = P.o;
     const int n = P.n;
     if (P.T != 0 || o.precision != W2XC_PRECISION_FP32 || o.kernel != W2XC_KERNEL_AUTO || o.fusion == W2XC_FUSION_PROG) return false;
-    if (n < 5 || P.HL != 4 || P.all_out || !P.last_direct || P.band < P.plane_h || P.plane_h <= 0) return false;
+    if (P.band < P.plane_h || P.plane_h <= 0) return false;
+    if (batch_chain_planes(m, P)) return true;
+    if (n < 5 || P.HL != 4 || P.all_out || !P.last_direct) return false;
     if (m->layers[0].nin != 1 || m->layers[n - 1].nout != 1) return false;
     if (layer_kind(m, 0, o) != W2XC_K_FUSED_AWAY || layer_kind(m, 1, o) != W2XC_K_FIRST2_WINO4) return false;
     if (layer_kind(m, n - 1, o) != W2XC_K_LAST_GATHER || out_terms_of(m, n - 2, o) != 9) return false;

@@ -250,10 +250,26 @@ __global__ void __launch_bounds__(512, 2) conv3x3_wino4_batch(W2xcConvDesc d, in
 #undef W4B_ONLY
 }
 
+// batch form of the multi-plane (RGB) chains: the layouts conv3x3_wino4_batch above does not have -- 32 NHWC planes in (IN_NHWC: the layer behind conv3x3_first /
+// conv3x3_wino) and / or NHWC out (the layer in front of conv3x3_last); no fused last layer
+template <int CIN, int COUT, bool OUT_PLANAR, bool IN_NHWC>
+__global__ void __launch_bounds__(512, 2) conv3x3_wino4_batch_l(W2xcConvDesc d, int tiles_x, int nitems, W2xcBatchDesc bd)
+{
+    constexpr bool FUSE7 = false, PROG = false;
+#define W4B_ONLY(...) __VA_ARGS__
+#define W4B_SEL(b_, s_) b_
+#define W4B_OUT (d.out + (long long)(item / bd.items) * bd.out_bs)
+#include "w2xc_wino4_body.inc"
+#undef W4B_OUT
+#undef W4B_SEL
+#undef W4B_ONLY
+}
+
 // ------------------------------------------------------------------------------------------------
 // host side: launch (shape predicates, PROG's job arithmetic and the packers: w2xc_pack.cpp).
 // Five objects (make -j): W2XC_WINO4_PART = 0 the planar-out instantiations + dispatcher, 1 the NHWC-out ones, 2 the fused-last ones,
-// 3 the batch forms with planar out + the batch dispatcher, 4 the fused-last batch forms.
+// 3 the batch forms with planar out + the batch dispatcher, 4 the fused-last batch forms, 5 the batch forms with 32 NHWC planes in, 6 those with planar
+// planes in and NHWC out.
 // ------------------------------------------------------------------------------------------------
 #ifndef W2XC_WINO4_PART
 #define W2XC_WINO4_PART -1   // one translation unit with everything (tools/ubench)
@@ -397,6 +413,49 @@ static hipError_t launch_wino4_batch(const W2xcConvDesc &d, W2xcBatchDesc b, hip
     return hipGetLastError();
 }
 
+template <int CIN, int COUT, bool OUT_PLANAR, bool IN_NHWC>
+static hipError_t launch_wino4_batch_l(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream)
+{
+    const int tiles_x = (d.out_w + 31) / 32, tiles_y = (d.out_h + (d.wino_py & 3) + 15) / 16;
+    const long long items = (long long)tiles_x * tiles_y * (COUT / 64);
+    if (items * b.batch >= (1ll << 31)) return hipErrorInvalidValue;
+    b.items = (int)items;
+    const int nitems = (int)(items * b.batch);
+    constexpr size_t lds_bytes = 3 * (size_t)(11 * 1024) + 2 * (size_t)(36 * 1024) + 3 * (size_t)(18 * 1024) + COUT * 4;   // raw + U + V + bias
+    static_assert(lds_bytes <= 160 * 1024, "LDS budget");
+    auto kern = conv3x3_wino4_batch_l<CIN, COUT, OUT_PLANAR, IN_NHWC>;
+    static W2xcLdsOptIn opt_in;   // per (kernel, device)
+    const hipError_t e = opt_in(kern, lds_bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(w2xc_persistent_grid(nitems)), dim3(512), lds_bytes, stream, d, tiles_x, nitems, b);
+    return hipGetLastError();
+}
+
+// 32 NHWC planes in, planar or NHWC out (d.out_ps tells); the dispatcher below has checked everything but the output layout's alignment
+hipError_t w2xc_launch_wino4_batch_nhwc_in(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream);
+#if W2XC_WINO4_PART == 5 || W2XC_WINO4_PART == -1
+hipError_t w2xc_launch_wino4_batch_nhwc_in(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream)
+{
+    if (d.out_ps == 1) return d.cout == 64 ? launch_wino4_batch_l<32, 64, true, true>(d, b, stream) : d.cout == 128 ? launch_wino4_batch_l<32, 128, true, true>(d, b, stream) : hipErrorInvalidValue;
+    return d.cout == 64 ? launch_wino4_batch_l<32, 64, false, true>(d, b, stream) : d.cout == 128 ? launch_wino4_batch_l<32, 128, false, true>(d, b, stream) : hipErrorInvalidValue;
+}
+#endif
+
+// planar planes in (64 / 128 of them), NHWC out
+hipError_t w2xc_launch_wino4_batch_nhwc_out(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream);
+#if W2XC_WINO4_PART == 6 || W2XC_WINO4_PART == -1
+hipError_t w2xc_launch_wino4_batch_nhwc_out(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream)
+{
+    switch (d.cin * 1000 + d.cout) {
+    case 64064:  return launch_wino4_batch_l<64, 64, false, false>(d, b, stream);
+    case 64128:  return launch_wino4_batch_l<64, 128, false, false>(d, b, stream);
+    case 128064: return launch_wino4_batch_l<128, 64, false, false>(d, b, stream);
+    case 128128: return launch_wino4_batch_l<128, 128, false, false>(d, b, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+#endif
+
 hipError_t w2xc_launch_wino4_batch_fused(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream);
 #if W2XC_WINO4_PART == 4 || W2XC_WINO4_PART == -1
 hipError_t w2xc_launch_wino4_batch_fused(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream)
@@ -419,6 +478,20 @@ hipError_t w2xc_launch_wino4_batch(const W2xcConvDesc &d, W2xcBatchDesc b, hipSt
     if (d.out_w <= 0 || d.out_h <= 0 || b.batch == 0) return hipSuccess;
     if (b.batch < 0 || b.in_bs < 0 || b.out_bs < 0 || (b.in_bs & 3) != 0 || (b.out_bs & 3) != 0) return hipErrorInvalidValue;
     if (d.in_shift != 0 || (d.in_rs & 3) != 0 || (((size_t)d.in) & 15) != 0 || d.prog_cnt) return hipErrorInvalidValue;
+    const bool in_nhwc = d.cin == 32 && d.in_ps == 32 && d.in_cs == 1, out_nhwc = d.out_terms != 9 && d.out_ps != 1;
+    if (in_nhwc || out_nhwc) {   // the layouts of the multi-plane chains (w2xc_wino4_batch_layout_supported); the checks of w2xc_launch_wino4
+        if (!w2xc_wino4_batch_layout_supported(d.cin, d.cout, in_nhwc, !out_nhwc) || d.out_terms == 9) return hipErrorInvalidValue;
+        if (in_nhwc) {
+            if (24 * d.in_rs * 4 >= (1ll << 32)) return hipErrorInvalidValue;
+        } else {
+            if (d.in_ps != 1 || (d.in_cs & 3) != 0 || d.off_x < 0 || (d.off_x & 3) != 0 || d.in_rs < ((d.in_w + 3) & ~3)) return hipErrorInvalidValue;
+            if (3 * d.in_cs * 4 + 24 * d.in_rs * 4 >= (1ll << 32)) return hipErrorInvalidValue;
+        }
+        if (out_nhwc) {
+            if (d.out_ps != d.cout || d.out_cs != 1 || (d.out_rs & 3) != 0 || (((size_t)d.out) & 15) != 0) return hipErrorInvalidValue;
+        } else if ((d.out_rs & 3) != 0 || (d.out_cs & 3) != 0 || (((size_t)d.out) & 15) != 0 || d.out_rs < ((d.out_w + 3) & ~3)) return hipErrorInvalidValue;
+        return in_nhwc ? w2xc_launch_wino4_batch_nhwc_in(d, b, stream) : w2xc_launch_wino4_batch_nhwc_out(d, b, stream);
+    }
     if (d.in_ps != 1 || (d.in_cs & 3) != 0 || d.off_x < 0 || (d.off_x & 3) != 0 || d.in_rs < ((d.in_w + 3) & ~3)) return hipErrorInvalidValue;
     if (3 * d.in_cs * 4 + 24 * d.in_rs * 4 >= (1ll << 32)) return hipErrorInvalidValue;   // 32-bit lane offsets inside a 4-channel slice of a tile
     if (!w2xc_wino4_batch_supported(d.cin, d.cout, d.out_terms == 9)) return hipErrorInvalidValue;
