@@ -144,6 +144,41 @@ int w2xc_model_load_json(const char *path, w2xc_model **out);
 int w2xc_model_from_arrays(int n_layers, const int *nin, const int *nout,
                            const float *const *weight, const double *const *bias, w2xc_model **out);
 
+/* ---- upconv head models (revision 0.4.1.6) ----
+ * The upconv_7 family of later upstream versions: the model does the 2x enlargement itself, in its last layer, so nothing is enlarged in front of it.  v1
+ * of the reference has no such path; the arithmetic is defined here.
+ *   model:  a HEAD MODEL is n - 1 >= 1 ordinary 3x3 layers followed by one head layer: C planes in, nout in {1, 3} planes out, a 4x4 kernel, stride 2,
+ *           padding 3 (a transposed convolution).  The published topology is 3 -> 16 -> 32 -> 64 -> 128 -> 128 -> 256, head 256 -> 3.
+ *   head:   with z the C input planes of (H + 2) x (W + 2) pixels, output row Y in [0, 2H) and column X in [0, 2W):
+ *               out[o][Y][X] = bias[o] + sum_c sum_{r, s in 0..3, (Y + 3 - r) and (X + 3 - s) even} Wt[c][o][r][s] * z[c][(Y + 3 - r) / 2][(X + 3 - s) / 2]
+ *           all in fp32, the bias narrowed double -> float as elsewhere in the engine.  Exactly 2 x 2 taps per plane contribute to a pixel and all their
+ *           indices lie inside z.  This is torch.nn.functional.conv_transpose2d(z, Wt, bias, stride=2, padding=3).
+ *           NO activation follows the head: it is the network's linear output upstream (a deliberate departure from quirk Q1; the uint8 result is the
+ *           same either way, since 0.1 x keeps the sign and saturates to 0).
+ *   order:  per output pixel and plane o the sum is taken taps outer, planes inner, bias last:  v = 0;  for r ascending, for s ascending (the two r and the
+ *           two s of the pixel's parity):  v += T(r, s);  v += (float)bias[o],  where T(r, s) = sum_c Wt[c][o][r][s] * z[c][..] is one fp32 MFMA accumulation
+ *           chain from 0 over the planes in k-order: step (g, j), g = 0 .. C / 16 - 1, j = 0 .. 3, contracts the planes {16 g + 4 k + j, k = 0 .. 3}
+ *           (v_mfma_f32_16x16x4_f32).  Every pixel of every band and of both output forms (float planes, uint8) is this one sequence: same bits.
+ *   whole:  z = the valid CNN (LeakyReLU(0.1) behind every 3x3 layer) over layers 1 .. n - 1 of the source replicate-padded by n pixels -- pad = layer
+ *           count, as convertRoutine.cpp:33-35 -- so n - 1 valid layers leave a one-pixel rim: z has (H + 2) x (W + 2) pixels, the result exactly 2H x 2W.
+ *   JSON:   the LAST array element is the head when kW == kH == 4, dW == dH == 2, padW == padH == 3 and class_name, if present, is
+ *           "nn.SpatialFullConvolution"; its weight is [nInputPlane][nOutputPlane][4][4] (torch's layout for that module), its bias may be absent and then
+ *           counts as zeros (upstream builds the head with :noBias()).  Unknown keys on the 3x3 layers are ignored as before; every other non-3x3 layer, or
+ *           a head anywhere but last, is refused as before (W2XC_ERR_UNSUPPORTED; a head that gives neither 1 nor 3 planes likewise).
+ *   planes: on the fast path plane counts below 32 BETWEEN the layers of a head model are zero-padded to 32 when the model is built (zero weights and zero
+ *           bias for the added output planes, zero weights for the added input planes of the next layer: exact zeros that add exact zeros), so that
+ *           3 -> 16 -> 32 runs as conv3x3_first 3 -> 32 and a 32 -> 32 layer; w2xc_model_nin / _nout / _get_layer answer what the model declares.  The head
+ *           has a kernel for C in {32, 64, 128, 256} (after padding); other counts, and the 16-bit precisions, are W2XC_ERR_UNSUPPORTED.  Models
+ *           without a head are untouched.
+ *   calls:  w2xc_convert_planes_up2x_device and w2xc_process_image_rgb_u8_ex[_device] (a head model as scale_model) run a head model.  EVERY other entry
+ *           point given one returns W2XC_ERR_UNSUPPORTED from its argument checks, before a device is touched: the Y route, w2xc_convert_plane*,
+ *           w2xc_convert_planes[_nn2x]_device, the batch, TTA and RGBA calls, w2xc_layer_filter*; w2xc_batch_plan answers "not batched".
+ * w2xc_model_add_upconv_head appends the head to a model from w2xc_model_from_arrays: weight is [nin][nout][4][4] with nin = the last 3x3 layer's output
+ * planes, bias nout doubles or NULL (zeros).  It must come before the model's first use on a device and only once: otherwise W2XC_ERR_ARG.
+ * w2xc_model_layers / _nin / _nout count the head as the last layer; w2xc_model_get_layer gives its weight as [nin][nout][4][4]. */
+int w2xc_model_add_upconv_head(w2xc_model *m, int nout, const float *weight, const double *bias);
+int w2xc_model_has_head(const w2xc_model *m);   /* 1 / 0 */
+
 void w2xc_model_free(w2xc_model *m);
 /* Release what grew with the largest plane converted so far -- activation workspaces, the host pipeline's device rows and
  * pinned rings, Model::filter's buffers -- on every device the model has run on.  Weights, streams and events stay; the
@@ -233,6 +268,14 @@ int w2xc_convert_plane_nn2x(w2xc_model *m, const float *in, size_t in_stride_byt
 int w2xc_convert_plane_nn2x_device(w2xc_model *m, const float *d_in, size_t in_stride_bytes, int w, int h,
                                    float *d_out, size_t out_stride_bytes, void *hip_stream,
                                    const w2xc_opts *opts);
+
+/* An upconv head model ("upconv head models" above) on float planes: n_in_planes planar planes of w x h in, ALL planes of the head out at 2w x 2h -- the raw
+ * head output, no clip (quirk Q2), no enlargement in front.  Arguments as w2xc_convert_planes_device, the output planes 2w x 2h (W2XC_ERR_ARG as
+ * there; sizes at most 2^28 a side); a model without a head is W2XC_ERR_ARG.  w2xc_opts.band_rows counts SOURCE rows (a band of b source rows gives 2b output rows), memory follows
+ * w2xc_opts.workspace_mb as for every call, and a banded run gives the bits of the unbanded one.  Asynchronous on hip_stream. */
+int w2xc_convert_planes_up2x_device(w2xc_model *m, int n_in_planes, const float *d_in, size_t in_plane_stride_bytes,
+                                    size_t in_stride_bytes, int w, int h, float *d_out, size_t out_plane_stride_bytes,
+                                    size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts);
 
 /* Batches: n planes of ONE size in one call (sprite sheets, icon sets, thumbnails, dataset crops, short clips).  (w, h) is the SOURCE size, the
  * output planes are (w << nn2x) x (h << nn2x) (nn2x = 1: the nearest-neighbour 2x of w2xc_convert_plane_nn2x folded into layer 1).  out[i] is
@@ -360,6 +403,9 @@ int w2xc_process_image_u8_batch(w2xc_model *noise_model, w2xc_model *scale_model
  * images with the single-image call are those of w2xc_process_image_u8_ex* / _batch* above; in addition the single-image device form refuses an output
  * that overlaps the input.  noise_model / scale_model: NULL or a model whose first layer takes 3 planes and whose last layer gives 3 -- anything else,
  * a Y model beside an RGB one included, is W2XC_ERR_PLANES.  All of that before a device is touched; without a device W2XC_ERR_HIP.
+ * An upconv head model as scale_model (w2xc_process_image_rgb_u8_ex[_device] only; the noise model stays a same-size RGB model): an iteration is then ONE
+ * pass of the head model on the image as it is, x <- upconv(x), instead of CNN(nearest2x(x)); the shrink and the final uint8 step stay.  With fp32 and
+ * fusion other than OFF layer 1 reads the uint8 image and the head writes the uint8 result; with fusion OFF the same bytes through float planes.
  * RGB chains have no batch kernels: a sub-batch runs the single-image launch sequence per image, with no host synchronisation in between (the colour
  * kernels and the shrink, where they run, are one launch per sub-batch). */
 int w2xc_process_image_rgb_u8_ex_device(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *d_in, size_t in_stride_bytes, int w,
@@ -564,7 +610,10 @@ typedef struct w2xc_row_plan {
 int w2xc_plan_rows(const w2xc_model *m, int w, int view_y0, int view_h, int plane_h, int row_begin, int row_end, const w2xc_opts *opts,
                    w2xc_row_plan *plan);
 /* plane rows [*top, *bottom) that layer `layer` (1 .. n_layers) computes for the band of output rows [y0, y1) under `plan`
- * (negative rows / rows >= plane_h + ...: the replicate padding of convertRoutine.cpp:35 seen from that layer) */
+ * (negative rows / rows >= plane_h + ...: the replicate padding of convertRoutine.cpp:35 seen from that layer).
+ * An upconv head model: every row here is a SOURCE row (w, plane_h, row_begin / row_end of w2xc_plan_rows are the source's), the head is layer n_layers and
+ * its region [y0, y1) stands for the output rows [2 y0, 2 y1); it reads z rows [y0, y1 + 2) -- z row i is plane row i - 1 of layer n - 1, whose region
+ * [y0 - 1, y1 + 1) on the one-row-per-layer geometry (a superset on the four-row one) is exactly those. */
 int w2xc_plan_region(const w2xc_row_plan *plan, int plane_h, int layer, int y0, int y1, int *top, int *bottom);
 
 /* Test aid.  Fills every grow-only scratch buffer the (model, device) context owns with the

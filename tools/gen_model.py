@@ -22,8 +22,9 @@ import numpy as np
 
 TOPOLOGY_WAIFU2X = [1, 32, 32, 64, 64, 128, 128, 1]          # srcnn.lua:13-26
 TOPOLOGY_WIDE = [3, 128, 128, 128, 128, 128, 128, 3]         # BASELINE.json configs[4]
+TOPOLOGY_UPCONV7 = [3, 16, 32, 64, 128, 128, 256]            # upstream's upconv_7: six 3x3 layers, then a 4x4 stride-2 transposed-convolution head 256 -> 3
 
-SEEDS = {"noise1": 101, "scale2.0x": 102, "noise2": 104, "wide": 105}
+SEEDS = {"noise1": 101, "scale2.0x": 102, "noise2": 104, "wide": 105, "upconv7": 106}
 
 
 def synth_layers(planes=TOPOLOGY_WAIFU2X, seed=102, init="he_leaky"):
@@ -59,12 +60,22 @@ def synth_layers(planes=TOPOLOGY_WAIFU2X, seed=102, init="he_leaky"):
     return layers
 
 
+def synth_head(cin, nout=3, seed=106, bias=True):
+    """(W[c,o,4,4] float32, bias[o] float64 or None): the head of an upconv model, W ~ N(0, 1 / (4 cin)) -- four taps per plane reach an
+    output pixel, so the output stays O(1) --, bias ~ U(-0.05, 0.05) or none (upstream builds the head with :noBias())"""
+    rng = np.random.default_rng(seed + 7919)
+    w = (rng.standard_normal((cin, nout, 4, 4)) * np.sqrt(1.0 / (4.0 * cin))).astype(np.float32)
+    b = rng.uniform(-0.05, 0.05, size=nout).astype(np.float64) if bias else None
+    return np.ascontiguousarray(w), b
+
+
 def _f32_repr(x):
     # shortest decimal string that round-trips the float32 value (and hence, via strtod->(float), too)
     return float(np.format_float_scientific(np.float32(x), unique=True))
 
 
-def write_json(layers, path):
+def write_json(layers, path, head=None):
+    """head = (W[c,o,4,4], bias or None): appended in upstream's upconv_7 schema (nn.SpatialFullConvolution, weight [nIn][nOut][4][4])"""
     objs = []
     for nin, nout, w, b in layers:
         objs.append({
@@ -73,6 +84,15 @@ def write_json(layers, path):
             "weight": [[[[_f32_repr(w[o, i, r, c]) for c in range(3)] for r in range(3)]
                         for i in range(nin)] for o in range(nout)],
         })
+    if head is not None:
+        hw, hb = head
+        cin, nout = hw.shape[:2]
+        obj = {"class_name": "nn.SpatialFullConvolution", "kW": 4, "kH": 4, "dW": 2, "dH": 2, "padW": 3, "padH": 3,
+               "nInputPlane": cin, "nOutputPlane": nout,
+               "weight": [[[[_f32_repr(hw[c, o, r, s]) for s in range(4)] for r in range(4)] for o in range(nout)] for c in range(cin)]}
+        if hb is not None:
+            obj["bias"] = [float(v) for v in hb]
+        objs.append(obj)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
         json.dump(objs, f)

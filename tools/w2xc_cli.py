@@ -96,6 +96,23 @@ def check_tta(tta, alpha_files):
                          "flatten the alpha channel first" % ", ".join(alpha_files))
 
 
+def check_head(head, tta, alpha_files, groups):
+    """A scale model with an upconv head (upconv_7: the model enlarges by itself) runs through the single-image RGB call alone: --tta 1, inputs that
+    take the RGBA call (`alpha_files`: their names) and inputs of one size that would go as a batch (`groups`: lists of names, one per image size) are a
+    SystemExit with a message, before anything is converted; everything else passes"""
+    if not head:
+        return
+    if tta:
+        raise SystemExit("--tta 1 is not available for an upconv scale model: its TTA form is not built; use --tta 0")
+    if alpha_files:
+        raise SystemExit("images with transparency (%s) are not available for an upconv scale model: its RGBA form is not built; flatten the alpha "
+                         "channel first" % ", ".join(alpha_files))
+    batched = [g for g in groups if len(g) > 1]
+    if batched:
+        raise SystemExit("several inputs of one size (%s) would run as a batch, which is not built for an upconv scale model: convert them one per call"
+                         % "; ".join(", ".join(g) for g in batched))
+
+
 def check_inputs(ap, args):
     """-o names ONE output file: with several inputs it is refused (argparse's error exit, status 2)"""
     if len(args.input_file) > 1 and args.output_file != "(auto)":
@@ -153,6 +170,9 @@ def main(argv=None):
     images = [load(f) for f in args.input_file]
     opaque = [(f, im) for f, im in zip(args.input_file, images) if im.shape[2] == 3]
     check_tta(args.tta, [f for f, im in zip(args.input_file, images) if im.shape[2] == 4])
+    head = bool(scale is not None and iterations and scale.has_head)   # (an upconv model: the RGB route's single-image call, passed through as it is)
+    check_head(head, args.tta, [f for f, im in zip(args.input_file, images) if im.shape[2] == 4],
+               [files for _, files, _ in group_inputs([(f, (im.shape[1], im.shape[0])) for f, im in opaque], args.mode, args.noise_level, args.scale_ratio)])
     tta = dict(tta=True) if args.tta else {}
     outs = {}
     if noise is None and iterations == 0 and not shrink:
@@ -168,8 +188,9 @@ def main(argv=None):
             outs[f] = w2xc.process_image_rgba_u8(alpha[f], noise, scale if iterations else None, iterations, opts, shrink)
         for files in batches:                      # one batch call per image size
             outs.update(zip(files, w2xc.process_image_rgba_u8_batch([alpha[f] for f in files], noise, scale if iterations else None, iterations, opts, shrink)))
-        if len(opaque) == 1:
-            outs[opaque[0][0]] = process(opaque[0][1], noise, scale if iterations else None, iterations, opts, shrink, **tta)
+        if len(opaque) == 1 or head:   # (an upconv scale model: every input its own call -- check_head)
+            for f, im in opaque:
+                outs[f] = process(im, noise, scale if iterations else None, iterations, opts, shrink, **tta)
         elif opaque:
             by_file = dict(opaque)
             sized = [(f, (im.shape[1], im.shape[0])) for f, im in opaque]

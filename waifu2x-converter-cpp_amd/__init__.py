@@ -75,6 +75,8 @@ def _load():
         "w2xc_plan_region": (ci, [C.POINTER(RowPlan), ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci)]),
         "w2xc_model_load_json": (ci, [C.c_char_p, C.POINTER(vp)]),
         "w2xc_model_from_arrays": (ci, [ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+        "w2xc_model_add_upconv_head": (ci, [vp, ci, fp, fp]),
+        "w2xc_model_has_head": (ci, [vp]),
         "w2xc_model_free": (None, [vp]),
         "w2xc_model_trim": (ci, [vp]),
         "w2xc_model_layers": (ci, [vp]),
@@ -116,6 +118,7 @@ def _load():
         "w2xc_bleed_rgba_u8_device": (ci, [fp, cs, ci, ci, ci, fp, cs, vp]),
         "w2xc_bleed_rgba_u8_trim": (ci, []),
         "w2xc_convert_planes_nn2x_device": (ci, [vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, vp, C.POINTER(Opts)]),
+        "w2xc_convert_planes_up2x_device": (ci, [vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, vp, C.POINTER(Opts)]),
         "w2xc_u8_to_rgb_device": (ci, [fp, cs, ci, ci, fp, fp, fp, vp]),
         "w2xc_rgb_to_u8_device": (ci, [fp, fp, fp, ci, ci, fp, cs, vp]),
         "w2xc_process_image_u8_device": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, vp, C.POINTER(Opts)]),
@@ -238,8 +241,9 @@ class _ModelSet:
         return cls(h.value)
 
     @classmethod
-    def from_layers(cls, layers):
-        """layers: [(nin, nout, W[o,i,3,3] float32, bias[o] float64)]"""
+    def from_layers(cls, layers, head=None):
+        """layers: [(nin, nout, W[o,i,3,3] float32, bias[o] float64)]; head = (W[c,o,4,4] float32, bias[o] float64 or None): the 4x4 stride-2
+        transposed-convolution head of an upconv model behind them (w2xc_model_add_upconv_head)"""
         n = len(layers)
         nin = (C.c_int * n)(*[l[0] for l in layers])
         nout = (C.c_int * n)(*[l[1] for l in layers])
@@ -254,7 +258,27 @@ class _ModelSet:
         rc = _lib.w2xc_model_from_arrays(n, nin, nout, wp, bp, C.byref(h))
         if rc != OK:
             raise W2xcError(rc, last_error())
-        return cls(h.value)
+        ms = cls(h.value)
+        if head is not None:
+            ms.add_upconv_head(*head)
+        return ms
+
+    def add_upconv_head(self, weight, bias=None):
+        """append the head: weight [nin, nout, 4, 4] (nin = the last layer's output planes), bias [nout] or None = zeros"""
+        w = np.ascontiguousarray(weight, dtype=np.float32)
+        # (a model that has its head already: the library refuses before it reads the weights)
+        if not self.has_head and (w.ndim != 4 or w.shape[0] != self.planes(self.n_layers - 1)[1] or w.shape[2:] != (4, 4)):
+            raise ValueError("head weight must be [nin, nout, 4, 4]")
+        b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float64)
+        if b is not None and b.shape != (w.shape[1],):
+            raise ValueError("head bias must be [nout]")
+        rc = _lib.w2xc_model_add_upconv_head(self.handle, int(w.shape[1]), w.ctypes.data, None if b is None else b.ctypes.data)
+        if rc != OK:
+            raise W2xcError(rc, last_error())
+
+    @property
+    def has_head(self):
+        return bool(_lib.w2xc_model_has_head(self.handle))
 
     def trim(self):
         """release the buffers that grew with the largest plane so far (w2xc_model_trim); weights stay resident"""
@@ -271,7 +295,8 @@ class _ModelSet:
 
     def layer_arrays(self, l):
         nin, nout = self.planes(l)
-        w = np.empty((nout, nin, 3, 3), np.float32)
+        head = self.has_head and l == self.n_layers - 1   # (the head's weight is [nin, nout, 4, 4])
+        w = np.empty((nin, nout, 4, 4) if head else (nout, nin, 3, 3), np.float32)
         b = np.empty((nout,), np.float64)
         rc = _lib.w2xc_model_get_layer(self.handle, l, w.ctypes.data, b.ctypes.data)
         if rc != OK:
@@ -305,6 +330,16 @@ class _ModelSet:
         """convert_planes_device with the nearest-neighbour 2x folded into layer 1 (w2xc_convert_planes_nn2x_device): (w, h) is the
         source size, the output planes are 2w x 2h."""
         rc = _lib.w2xc_convert_planes_nn2x_device(self.handle, n_in, C.c_void_p(d_in), in_plane_stride_bytes, in_stride_bytes, w, h,
+                                                  C.c_void_p(d_out), out_plane_stride_bytes, out_stride_bytes, C.c_void_p(stream),
+                                                  C.byref(opts) if opts is not None else None)
+        if rc != OK:
+            raise W2xcError(rc, last_error())
+
+    def convert_planes_up2x_device(self, n_in, d_in, in_plane_stride_bytes, in_stride_bytes, w, h, d_out,
+                                   out_plane_stride_bytes, out_stride_bytes, stream=0, opts=None):
+        """an upconv head model on planar device planes (w2xc_convert_planes_up2x_device): (w, h) is the source size, every plane of the
+        head comes out at 2w x 2h, unclipped"""
+        rc = _lib.w2xc_convert_planes_up2x_device(self.handle, n_in, C.c_void_p(d_in), in_plane_stride_bytes, in_stride_bytes, w, h,
                                                   C.c_void_p(d_out), out_plane_stride_bytes, out_stride_bytes, C.c_void_p(stream),
                                                   C.byref(opts) if opts is not None else None)
         if rc != OK:

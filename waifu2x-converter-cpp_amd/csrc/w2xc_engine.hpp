@@ -71,6 +71,14 @@ struct HostLayer {
     int nin = 0, nout = 0;
     std::vector<float> w;       // [nout][nin][3][3], index o*nin+i (modelHandler.cpp:102)
     std::vector<double> bias;   // modelHandler.cpp:109-112 keeps doubles
+    // upconv head models (include/w2xc_hip.h): the last layer is the head -- w is [nin][nout][4][4] -- and plane counts below 32 between the layers are
+    // zero-padded to 32 (pad_head_model, w2xc_model.cpp): nin / nout / w / bias above are what the engine runs, nin0 / nout0 / w0 what the model declares
+    // (w0 empty: w as it is).  Models without a head are never padded.
+    bool head = false;
+    int nin0 = 0, nout0 = 0;
+    std::vector<float> w0;
+    int decl_nin() const { return nin0 ? nin0 : nin; }
+    int decl_nout() const { return nout0 ? nout0 : nout; }
 };
 
 struct DevLayer {
@@ -212,6 +220,7 @@ struct DeviceGuard {
 
 struct w2xc_model {
     std::vector<w2xc_eng::HostLayer> layers;
+    bool has_head() const { return !layers.empty() && layers.back().head; }
     std::mutex mu;
     std::map<int, std::unique_ptr<w2xc_eng::DevCtx>> ctx;
 };
@@ -280,7 +289,19 @@ inline bool ranges_overlap(const void *in, size_t in_extent, const void *out, si
     return i0 < o0 + out_extent && o0 < i0 + in_extent;
 }
 
+// what every entry point but w2xc_convert_planes_up2x_device and w2xc_process_image_rgb_u8_ex[_device] answers for an upconv head model, in its argument
+// checks (no device is touched)
+inline int refuse_head(const w2xc_model *m, const char *call)
+{
+    if (!m || !m->has_head()) return W2XC_OK;
+    return fail(W2XC_ERR_UNSUPPORTED, "%s: the model ends in an upconv head (a 2x transposed convolution); such models run through "
+                "w2xc_convert_planes_up2x_device and w2xc_process_image_rgb_u8_ex[_device] only", call);
+}
+
 // ---- w2xc_select.cpp ----
+// the fast path's kernel kind for layer l by its shape: w2xc_pick_kernel, but the head of an upconv model is W2XC_K_UPCONV and the 128 -> 256 layer in
+// front of one is a W2XC_K_MFMA layer (conv3x3_wino4 alone has a kernel for it: layer_kind)
+W2xcKernelKind pick_kind(const w2xc_model *m, int l);
 int split_terms(const w2xc_opts &o);
 int split_fmt(const w2xc_opts &o);
 W2xcKernelKind layer_kind(const w2xc_model *m, int l, const w2xc_opts &o);

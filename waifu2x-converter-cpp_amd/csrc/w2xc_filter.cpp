@@ -92,6 +92,8 @@ int filter_on_device(w2xc_model *m, DevCtx *c, int layer, const float *in, long 
 int filter_check(const w2xc_model *m, int layer, int n_in_planes)
 {
     if (!m || layer < 0 || layer >= (int)m->layers.size()) return fail(W2XC_ERR_ARG, "bad model/layer");
+    // (an upconv head model: the head is no Model::filter, and the 3x3 layers in front of it are kept zero-padded to 32 planes -- none of its layers)
+    if (int rc = refuse_head(m, "w2xc_layer_filter*")) return rc;
     const HostLayer &hl = m->layers[layer];
     if (n_in_planes != hl.nin) {   // modelHandler.cpp:29-35
         std::cerr << "Error : Model-filter : \nnumber of input planes mismatch." << std::endl;

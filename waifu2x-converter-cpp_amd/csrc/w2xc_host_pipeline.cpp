@@ -538,6 +538,7 @@ int convert_plane_host(w2xc_model *m, const float *in, size_t in_stride_bytes, i
                        int in_row0 = 0, int in_rows = -1)
 {
     if (!m || !in || !out) return fail(W2XC_ERR_ARG, "null argument");
+    if (int rc = refuse_head(m, "w2xc_convert_plane[_nn2x / _rows]")) return rc;
     if (int rc = check_plane_size(w, h, false)) return rc;
     const int W = w << up, H = h << up;
     if (row_end < 0) row_end = H;

@@ -213,7 +213,8 @@ int process_rgb_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, s
         const bool noise = c.mn && p == 1;
         w2xc_model *m = noise ? c.mn : c.msc;
         DevCtx *cm = noise ? c.ctx.cn : c.ctx.cs;
-        const int up = noise ? 0 : 1, nw = cw << up, nh = ch << up;
+        const bool head = m->has_head();   // (the scale model of the single-image call: the pass enlarges by itself, nothing is folded into layer 1)
+        const int up = noise || head ? 0 : 1, nw = cw << (noise ? 0 : 1), nh = ch << (noise ? 0 : 1);
         const long long ps2 = (long long)plane_floats(nw, nh);
         const bool from_u8 = cur == nullptr, to_u8 = p == passes && R.dst_u8;
         float *nxt = nullptr;
@@ -231,7 +232,7 @@ int process_rgb_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, s
             // image i's three planes, or -- the uint8 forms -- the caller's image itself: strides in bytes (Planes, w2xc_engine.hpp)
             const PlanesIn src = from_u8 ? PlanesIn{reinterpret_cast<const float *>(in.p + (size_t)i * in.img), in.row, 1} : PlanesIn{cur + (size_t)i * 3 * ps, (size_t)cw, ps};
             const PlanesOut dst = to_u8 ? PlanesOut{reinterpret_cast<float *>(out.p + (size_t)i * out.img), out.row, 1} : PlanesOut{nxt + (size_t)i * 3 * ps2, (size_t)nw, ps2};
-            int rc = run_rows(m, cm, RowsCall::whole(src, 3, nw, nh, dst, up, (from_u8 ? ROWS_U8_SRC : 0) | (to_u8 ? ROWS_U8_DST : 0)), c.st, c.o);
+            int rc = run_rows(m, cm, RowsCall::whole(src, 3, head ? cw : nw, head ? ch : nh, dst, up, (from_u8 ? ROWS_U8_SRC : 0) | (to_u8 ? ROWS_U8_DST : 0)), c.st, c.o);
             if (rc) return rc;
         }
         if (to_u8) return W2XC_OK;
@@ -275,7 +276,8 @@ int plan_image_call(PlanKind kind, const ImageCall &c, int *sub, size_t per_imag
     pass[1] = c.iterations > 0 ? c.msc : nullptr;
     for (int i = 0; i < 2; i++) {
         if (!pass[i]) continue;
-        const int W = i ? c.w << c.iterations : c.w, H = i ? c.h << c.iterations : c.h;   // (the last scale iteration: the largest planes of the call)
+        int W = i ? c.w << c.iterations : c.w, H = i ? c.h << c.iterations : c.h;   // (the last scale iteration: the largest planes of the call)
+        if (i && pass[i]->has_head()) { W >>= 1; H >>= 1; }   // (an upconv head model is planned on its source)
         RowPlan P;
         if (int rc = plan_rows(pass[i], c.o, W, H, 0, 0, H, H, rgb ? 3 : 1, rgb, &P)) return rc;
         if (batch_eligible(pass[i], P)) {
@@ -299,9 +301,12 @@ int check_y_models(const ImageCall &c)
     return W2XC_OK;
 }
 
-int check_process_args(const ImageCall &c)
+// head_ok: the call is w2xc_process_image_rgb_u8_ex[_device], which takes an upconv head model as its scale model; every other image call refuses one
+int check_process_args(const ImageCall &c, bool head_ok = false)
 {
     if (c.tta_arg != 0 && c.tta_arg != 1) return fail(W2XC_ERR_ARG, "tta must be 0 or 1 (got %d)", c.tta_arg);
+    if (int rc = refuse_head(c.mn, "the noise model of an image call")) return rc;
+    if (!(head_ok && !c.tta)) if (int rc = refuse_head(c.msc, "this image call")) return rc;
     if (!c.mn && !c.msc) return fail(W2XC_ERR_ARG, "need a noise model, a scale model or both");
     if (c.iterations > 0 && !c.msc) return fail(W2XC_ERR_ARG, "scale iterations need a scale model");
     if (!c.mn && c.iterations == 0) return fail(W2XC_ERR_ARG, "nothing to do (no noise model, 0 iterations)");
@@ -606,7 +611,7 @@ BleedScratch &bleed_scratch()
 // ---- the four forms of the image call, for Y models (rgb = false: w2xc_process_image_u8*) and RGB models (w2xc_process_image_rgb_u8*) ----
 int image_ex_device(bool rgb, ImageCall c, U8In in, U8Out out)
 {
-    int rc = check_process_args(c);
+    int rc = check_process_args(c, rgb);
     if (rc) return rc;
     if ((rc = check_image_args(c, in.p, in.row, out.p, out.row))) return rc;
     if (rgb) {
@@ -626,7 +631,7 @@ int image_ex_device(bool rgb, ImageCall c, U8In in, U8Out out)
 
 int image_ex_host(bool rgb, ImageCall c, U8In in, U8Out out)
 {
-    int rc = check_process_args(c);
+    int rc = check_process_args(c, rgb);
     if (rc) return rc;
     if ((rc = check_image_args(c, in.p, in.row, out.p, out.row))) return rc;
     int sub;

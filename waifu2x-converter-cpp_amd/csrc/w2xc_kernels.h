@@ -109,6 +109,13 @@ hipError_t w2xc_launch_first2_split(const W2xcConvDesc &d, hipStream_t stream);
 // last layer fused into a two-term mid layer (d.w7pk = the w2xc_split_pack_last image)
 hipError_t w2xc_launch_last_gather(const W2xcConvDesc &d, hipStream_t stream);
 
+// the head of an upconv model (w2xc_upconv.hip; kind = W2XC_K_UPCONV / W2XC_K_UPCONV_U8): `in` = the NHWC view of z (in_ps = cin in {32, 64, 128, 256}), off_y / off_x
+// = the view's row / column of z row y0 / column 0, out_h x out_w = the SOURCE pixels; writes 2 out_h x 2 out_w pixels of cout in {1, 3} planes (planar
+// floats, or -- U8 -- an interleaved uint8 image with byte strides), out_rs = the row stride of the doubled image; d.wpk = the w2xc_upconv_pack image
+hipError_t w2xc_launch_upconv(W2xcKernelKind kind, const W2xcConvDesc &d, hipStream_t stream);
+// conv3x3_wino4 128 -> 256 planes, planar in, NHWC out (the layer in front of the head of the published upconv_7 topology; an object of its own)
+hipError_t w2xc_launch_wino4_wide(const W2xcConvDesc &d, hipStream_t stream);
+
 // strided element copy (planar <-> NHWC repack at the Model::filter boundary)
 hipError_t w2xc_launch_repack(const float *src, long long s_rs, long long s_ps, long long s_cs,
                               float *dst, long long d_rs, long long d_ps, long long d_cs,

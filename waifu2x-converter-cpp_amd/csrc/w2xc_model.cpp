@@ -89,16 +89,25 @@ int get_ctx(w2xc_model *m, int device, DevCtx **out)
     for (size_t l = 0; l < m->layers.size(); l++) {
         const HostLayer &hl = m->layers[l];
         DevLayer &dl = c->layers[l];
-        dl.fast = w2xc_pick_kernel(hl.nin, hl.nout);
-        std::vector<float> pk(w2xc_packed_weight_floats(W2XC_K_DIRECT, hl.nin, hl.nout));
-        w2xc_pack_weights(W2XC_K_DIRECT, hl.nin, hl.nout, hl.w.data(), pk.data());
-        int rc = upload(pk, &dl.w_direct);
-        if (rc) return rc;
-        if (dl.fast != W2XC_K_DIRECT) {
-            pk.assign(w2xc_packed_weight_floats(dl.fast, hl.nin, hl.nout), 0.f);
-            w2xc_pack_weights(dl.fast, hl.nin, hl.nout, hl.w.data(), pk.data());
-            rc = upload(pk, &dl.w_fast);
-            if (rc) return rc;
+        int rc;
+        std::vector<float> pk;
+        if (hl.head) {   // the head has one kernel and one image (a shape without it: plan_rows refuses the call)
+            dl.fast = W2XC_K_UPCONV;
+            if (w2xc_upconv_supported(hl.nin, hl.nout)) {
+                pk.resize(w2xc_upconv_packed_floats(hl.nin, hl.nout));
+                w2xc_upconv_pack(hl.nin, hl.nout, hl.w.data(), pk.data());
+                if ((rc = upload(pk, &dl.w_fast))) return rc;
+            }
+        } else {
+            dl.fast = w2xc_pick_kernel(hl.nin, hl.nout);
+            pk.resize(w2xc_packed_weight_floats(W2XC_K_DIRECT, hl.nin, hl.nout));
+            w2xc_pack_weights(W2XC_K_DIRECT, hl.nin, hl.nout, hl.w.data(), pk.data());
+            if ((rc = upload(pk, &dl.w_direct))) return rc;
+            if (dl.fast != W2XC_K_DIRECT) {
+                pk.assign(w2xc_packed_weight_floats(dl.fast, hl.nin, hl.nout), 0.f);
+                w2xc_pack_weights(dl.fast, hl.nin, hl.nout, hl.w.data(), pk.data());
+                if ((rc = upload(pk, &dl.w_fast))) return rc;
+            }
         }
         std::vector<float> bf(hl.nout);
         for (int o = 0; o < hl.nout; o++) bf[o] = (float)hl.bias[o];   // cv::add(UMat, double) narrows to the array depth
@@ -108,6 +117,27 @@ int get_ctx(w2xc_model *m, int device, DevCtx **out)
     *out = c.get();
     m->ctx[device] = std::move(c);
     return W2XC_OK;
+}
+
+// An upconv head model as the engine runs it: plane counts below 32 between its layers zero-padded to 32 -- zero weights and zero bias for the added output
+// planes of a 3x3 layer (leaky(0) = 0: those planes are exact zeros), zero weights for the added input planes of the layer behind it (exact zeros added to
+// its sums) -- so that 3 -> 16 -> 32 of the published topology runs as conv3x3_first 3 -> 32 and a 32 -> 32 layer instead of conv3x3_direct.  The model's own
+// planes (layer 1's input, the head's output) stay.  What the model declares is kept beside (HostLayer::nin0 / nout0 / w0) for the getters.
+static void pad_head_model(w2xc_model *m)
+{
+    const int n = (int)m->layers.size();
+    for (int l = 0; l < n; l++) {
+        HostLayer &hl = m->layers[l];
+        hl.nin0 = hl.nin; hl.nout0 = hl.nout;
+        const int nin_p = (l > 0 && hl.nin < 32) ? 32 : hl.nin, nout_p = (!hl.head && hl.nout < 32) ? 32 : hl.nout;
+        if (nin_p == hl.nin && nout_p == hl.nout) continue;
+        hl.w0 = hl.w;
+        hl.w.assign((size_t)nin_p * nout_p * (hl.head ? 16 : 9), 0.f);
+        if (hl.head) w2xc_pad_head(hl.nin, hl.nout, nin_p, hl.w0.data(), hl.w.data());
+        else w2xc_pad_layer(hl.nin, hl.nout, nin_p, nout_p, hl.w0.data(), hl.w.data());
+        hl.bias.resize(nout_p, 0.0);
+        hl.nin = nin_p; hl.nout = nout_p;
+    }
 }
 
 int prof_begin(DevCtx *c, int layer, hipStream_t st, ProfEvent *ev)
@@ -181,7 +211,9 @@ const char *w2xc_last_error(void) { return g_last_error.c_str(); }
 // 0.4.1.3: the batch forms of the RGBA call, w2xc_process_image_rgba_u8_batch[_device] (additive; w2xc_opts stays 56 bytes)
 // 0.4.1.4: w2xc_resize_linear_device, the INTER_LINEAR resize of the image calls' shrink as a building block (additive; w2xc_opts stays 56 bytes)
 // 0.4.1.5: w2xc_convert_planes_batch_device (n images of several planes: the batched chain of RGB models) and w2xc_batch_plan (additive; w2xc_opts stays 56 bytes)
-const char *w2xc_version(void) { return "w2xc_hip 0.4.1.5 (gfx950)"; }
+// 0.4.1.6: upconv head models -- w2xc_model_add_upconv_head, w2xc_model_has_head, w2xc_convert_planes_up2x_device; the JSON loader takes a last layer that is
+//          an nn.SpatialFullConvolution 4x4 / stride 2 / padding 3; every other entry point refuses such a model (additive; w2xc_opts stays 56 bytes)
+const char *w2xc_version(void) { return "w2xc_hip 0.4.1.6 (gfx950)"; }
 
 int w2xc_plan_rows(const w2xc_model *m, int w, int view_y0, int view_h, int plane_h, int row_begin, int row_end, const w2xc_opts *opts, w2xc_row_plan *plan)
 try {
@@ -250,6 +282,47 @@ try {
     return fail(W2XC_ERR_NOMEM, "out of memory while copying the model");
 }
 
+int w2xc_model_add_upconv_head(w2xc_model *m, int nout, const float *weight, const double *bias)
+try {
+    if (!m || !weight) return fail(W2XC_ERR_ARG, "null argument");
+    if (nout != 1 && nout != 3) return fail(W2XC_ERR_ARG, "an upconv head gives 1 or 3 planes (got %d)", nout);
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (m->layers.empty()) return fail(W2XC_ERR_ARG, "model has no layers");
+    if (m->has_head()) return fail(W2XC_ERR_ARG, "the model has a head already");
+    if (!m->ctx.empty()) return fail(W2XC_ERR_ARG, "w2xc_model_add_upconv_head must come before the model's first use on a device");
+    HostLayer hl;
+    hl.head = true;
+    hl.nin = m->layers.back().nout;
+    hl.nout = nout;
+    hl.w.assign(weight, weight + (size_t)hl.nin * nout * 16);
+    hl.bias.assign(nout, 0.0);
+    if (bias) hl.bias.assign(bias, bias + nout);
+    m->layers.push_back(std::move(hl));
+    pad_head_model(m);
+    return W2XC_OK;
+} catch (const std::bad_alloc &) {
+    return fail(W2XC_ERR_NOMEM, "out of memory while copying the head");
+}
+
+int w2xc_model_has_head(const w2xc_model *m) { return m && m->has_head() ? 1 : 0; }
+
+// the number behind an optional numeric key of a layer object (absent or not a number: `missing`)
+static double json_num(const jsonmin::Value &o, const char *key, double missing)
+{
+    const jsonmin::Value *v = o.find(key);
+    return v && v->is_number() ? v->num : missing;
+}
+
+// Is element o of the model array -- the last one -- the head of an upconv model?  kW = kH = 4, dW = dH = 2, padW = padH = 3, and class_name, if present,
+// "nn.SpatialFullConvolution" (include/w2xc_hip.h).  Anything else with a 4x4 kernel is a non-3x3 layer like any other.
+static bool json_is_head(const jsonmin::Value &o)
+{
+    if (json_num(o, "kW", 0) != 4 || json_num(o, "kH", 0) != 4) return false;
+    if (json_num(o, "dW", 0) != 2 || json_num(o, "dH", 0) != 2 || json_num(o, "padW", -1) != 3 || json_num(o, "padH", -1) != 3) return false;
+    const jsonmin::Value *cn = o.find("class_name");
+    return !cn || (cn->type == jsonmin::Value::String && cn->str == "nn.SpatialFullConvolution");
+}
+
 static int model_load_json_impl(const char *path, w2xc_model **out)
 {
     if (!path || !out) return fail(W2XC_ERR_ARG, "null argument");
@@ -275,8 +348,9 @@ static int model_load_json_impl(const char *path, w2xc_model **out)
         if (!o.is_object()) return fail(W2XC_ERR_JSON, "layer %zu is not an object", l);
         const jsonmin::Value *nip = o.find("nInputPlane"), *nop = o.find("nOutputPlane"), *kw = o.find("kW"),
                              *kh = o.find("kH"), *wv = o.find("weight"), *bv = o.find("bias");
-        if (!nip || !nop || !kw || !kh || !wv || !bv || !nip->is_number() || !nop->is_number() || !kw->is_number() ||
-            !kh->is_number() || !wv->is_array() || !bv->is_array())
+        const bool head = l + 1 == root.arr.size() && l > 0 && json_is_head(o);   // (its bias may be absent: upstream builds the head with :noBias())
+        if (!nip || !nop || !kw || !kh || !wv || (!bv && !head) || !nip->is_number() || !nop->is_number() || !kw->is_number() ||
+            !kh->is_number() || !wv->is_array() || (bv && !bv->is_array()))
             return fail(W2XC_ERR_JSON, "layer %zu lacks one of nInputPlane/nOutputPlane/kW/kH/weight/bias", l);
         HostLayer hl;
         // the reference casts these doubles straight to int (modelHandler.hpp:50-51); a library first makes sure the cast
@@ -291,8 +365,38 @@ static int model_load_json_impl(const char *path, w2xc_model **out)
             std::cerr << "Error : Model-Constructor : \nkernel in model is not square.\nstop." << std::endl;
             return fail(W2XC_ERR_UNSUPPORTED, "kernel in model is not square");
         }
-        if (ks != 3) return fail(W2XC_ERR_UNSUPPORTED, "layer %zu: kernel size %d; only 3x3 is supported (convertWithModels pads by the layer count, which assumes 3x3)", l, ks);
+        if (ks != 3 && !head) return fail(W2XC_ERR_UNSUPPORTED, "layer %zu: kernel size %d; only 3x3 is supported (convertWithModels pads by the layer count, which assumes 3x3)", l, ks);
         if (hl.nin <= 0 || hl.nout <= 0 || hl.nin > 4096 || hl.nout > 4096) return fail(W2XC_ERR_JSON, "layer %zu: bad plane counts (%d, %d)", l, hl.nin, hl.nout);
+        if (head) {   // weight[nInputPlane][nOutputPlane][4][4], torch's layout of nn.SpatialFullConvolution
+            if (hl.nout != 1 && hl.nout != 3) return fail(W2XC_ERR_UNSUPPORTED, "layer %zu: an upconv head gives 1 or 3 planes (got %d)", l, hl.nout);
+            if ((int)wv->arr.size() != hl.nin || (bv && (int)bv->arr.size() < hl.nout))
+                return fail(W2XC_ERR_JSON, "layer %zu: weight/bias outer size does not match nInputPlane / nOutputPlane of the head", l);
+            hl.head = true;
+            hl.w.resize((size_t)hl.nin * hl.nout * 16);
+            hl.bias.assign(hl.nout, 0.0);
+            for (int i = 0; i < hl.nin; i++) {
+                const jsonmin::Value &wi = wv->arr[i];
+                if (!wi.is_array() || (int)wi.arr.size() != hl.nout) return fail(W2XC_ERR_JSON, "layer %zu: weight[%d] size != nOutputPlane", l, i);
+                for (int oo = 0; oo < hl.nout; oo++) {
+                    const jsonmin::Value &km = wi.arr[oo];
+                    if (!km.is_array() || (int)km.arr.size() < 4) return fail(W2XC_ERR_JSON, "layer %zu: weight[%d][%d] is not a 4x4 matrix", l, i, oo);
+                    for (int r = 0; r < 4; r++) {
+                        const jsonmin::Value &row = km.arr[r];
+                        if (!row.is_array() || (int)row.arr.size() < 4) return fail(W2XC_ERR_JSON, "layer %zu: weight[%d][%d][%d] too short", l, i, oo, r);
+                        for (int cidx = 0; cidx < 4; cidx++) {
+                            if (!row.arr[cidx].is_number()) return fail(W2XC_ERR_JSON, "layer %zu: non-numeric weight", l);
+                            hl.w[((size_t)i * hl.nout + oo) * 16 + r * 4 + cidx] = (float)row.arr[cidx].num;
+                        }
+                    }
+                }
+            }
+            for (int oo = 0; bv && oo < hl.nout; oo++) {
+                if (!bv->arr[oo].is_number()) return fail(W2XC_ERR_JSON, "layer %zu: non-numeric bias", l);
+                hl.bias[oo] = bv->arr[oo].num;
+            }
+            m->layers.push_back(std::move(hl));
+            break;
+        }
         if ((int)wv->arr.size() != hl.nout || (int)bv->arr.size() < hl.nout)
             return fail(W2XC_ERR_JSON, "layer %zu: weight/bias outer size does not match nOutputPlane", l);
         hl.w.resize((size_t)hl.nout * hl.nin * 9);
@@ -317,6 +421,7 @@ static int model_load_json_impl(const char *path, w2xc_model **out)
         }
         m->layers.push_back(std::move(hl));
     }
+    if (m->has_head()) pad_head_model(m.get());
     *out = m.release();
     return W2XC_OK;
 }
@@ -355,15 +460,17 @@ int w2xc_model_trim(w2xc_model *m)
     return W2XC_OK;
 }
 int w2xc_model_layers(const w2xc_model *m) { return m ? (int)m->layers.size() : 0; }
-int w2xc_model_nin(const w2xc_model *m, int l) { return (m && l >= 0 && l < (int)m->layers.size()) ? m->layers[l].nin : -1; }
-int w2xc_model_nout(const w2xc_model *m, int l) { return (m && l >= 0 && l < (int)m->layers.size()) ? m->layers[l].nout : -1; }
+// (an upconv head model: the plane counts and weights the model declares, not the zero-padded ones the engine runs -- pad_head_model)
+int w2xc_model_nin(const w2xc_model *m, int l) { return (m && l >= 0 && l < (int)m->layers.size()) ? m->layers[l].decl_nin() : -1; }
+int w2xc_model_nout(const w2xc_model *m, int l) { return (m && l >= 0 && l < (int)m->layers.size()) ? m->layers[l].decl_nout() : -1; }
 
 int w2xc_model_get_layer(const w2xc_model *m, int l, float *weight, double *bias)
 {
     if (!m || l < 0 || l >= (int)m->layers.size()) return fail(W2XC_ERR_ARG, "bad layer index");
     const HostLayer &hl = m->layers[l];
-    if (weight) memcpy(weight, hl.w.data(), hl.w.size() * sizeof(float));
-    if (bias) memcpy(bias, hl.bias.data(), hl.bias.size() * sizeof(double));
+    const std::vector<float> &w = hl.w0.empty() ? hl.w : hl.w0;
+    if (weight) memcpy(weight, w.data(), w.size() * sizeof(float));
+    if (bias) memcpy(bias, hl.bias.data(), (size_t)hl.decl_nout() * sizeof(double));
     return W2XC_OK;
 }
 

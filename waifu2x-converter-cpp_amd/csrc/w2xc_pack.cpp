@@ -32,6 +32,8 @@ const char *w2xc_kernel_name(W2xcKernelKind kind, int cin, int cout)
     case W2XC_K_FIRST2_WINO4: return "conv3x3_first2_wino4";
     case W2XC_K_FIRST_U8: return "conv3x3_first_u8";
     case W2XC_K_LAST_U8: return "conv3x3_last_u8";
+    case W2XC_K_UPCONV: return "upconv4x4_head";
+    case W2XC_K_UPCONV_U8: return "upconv4x4_head_u8";
     default: return "conv3x3_direct";
     }
 }
@@ -92,6 +94,42 @@ void w2xc_pack_weights(W2xcKernelKind kind, int cin, int cout, const float *w, f
             for (int tap = 0; tap < 9; tap++)
                 for (int o = 0; o < cout; o++) dst[((size_t)i * 9 + tap) * cp + o] = W(o, i, tap);
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// upconv4x4_head (w2xc_upconv.hip): the 4x4 stride-2 transposed convolution that ends an upconv model
+// ------------------------------------------------------------------------------------------------
+bool w2xc_upconv_supported(int cin, int nout) { return (is_mid(cin) || cin == 256) && (nout == 1 || nout == 3); }
+size_t w2xc_upconv_packed_floats(int cin, int nout) { return (size_t)16 * nout * cin; }
+
+// wpk[c / 16][j][nb][lane] = Wt[c][n % nout][n / nout], c = 16 (c / 16) + 4 (lane >> 4) + j, n = 16 nb + (lane & 15) = tap * nout + o, tap = 4 r + s:
+// conv3x3_last's "taps as N" image with 16 taps; N = 16 nout is whole 16-column blocks, so every lane of the image is a weight and every weight has one lane
+void w2xc_upconv_pack(int cin, int nout, const float *w, float *dst)
+{
+    const int nb16 = nout, s4n = cin / 16;
+    for (int s4 = 0; s4 < s4n; s4++)
+        for (int j = 0; j < 4; j++)
+            for (int nb = 0; nb < nb16; nb++)
+                for (int lane = 0; lane < W2XC_WAVE; lane++) {
+                    const int n = nb * 16 + (lane & 15), c = 16 * s4 + 4 * (lane >> 4) + j;
+                    dst[(((size_t)s4 * 4 + j) * nb16 + nb) * W2XC_WAVE + lane] = w[((size_t)c * nout + n % nout) * 16 + n / nout];
+                }
+}
+
+// one workgroup per tile up to two per CU (512); beyond that every workgroup walks a run of consecutive tiles
+int w2xc_upconv_grid(int ntiles) { return ntiles < 512 ? ntiles : 512; }
+
+void w2xc_pad_layer(int cin, int cout, int cin_p, int cout_p, const float *w, float *dst)
+{
+    memset(dst, 0, (size_t)cin_p * cout_p * 9 * sizeof(float));
+    for (int o = 0; o < cout; o++)
+        for (int i = 0; i < cin; i++) memcpy(dst + ((size_t)o * cin_p + i) * 9, w + ((size_t)o * cin + i) * 9, 9 * sizeof(float));
+}
+
+void w2xc_pad_head(int cin, int nout, int cin_p, const float *w, float *dst)
+{
+    memset(dst, 0, (size_t)cin_p * nout * 16 * sizeof(float));
+    memcpy(dst, w, (size_t)cin * nout * 16 * sizeof(float));
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -20,6 +20,10 @@ enum W2xcKernelKind {
     // W2XC_K_LAST for the layer that touches the caller's uint8 image; both read the weight image of the kind they stand in for
     W2XC_K_FIRST_U8 = 13,      // W2XC_K_FIRST (3 -> {32,64,128}) reading an interleaved uint8 image: d.in = bytes, in_rs / in_ps / in_cs = row stride in bytes / 3 / 1
     W2XC_K_LAST_U8 = 14,       // W2XC_K_LAST ({32,64,128} -> 3) writing one: d.out = bytes, out_rs / out_ps / out_cs likewise
+    // the head of an upconv model (w2xc_upconv.hip): {32,64,128,256} NHWC planes in -> {1,3} planes out at twice the size, 4x4 stride-2 transposed convolution;
+    // never what w2xc_pick_kernel answers (a head is a property of the model, not of a plane count) -- layer_kind puts it in place for the head layer
+    W2XC_K_UPCONV = 15,        // planar float planes out
+    W2XC_K_UPCONV_U8 = 16,     // three interleaved uint8 channels out (as W2XC_K_LAST_U8)
 };
 
 // Which kernel kind the fast path has for a (cin, cout) layer; W2XC_K_DIRECT when none.
@@ -67,3 +71,14 @@ float w2xc_split_pack(int cin, int cout, int terms, int fmt, const float *w, voi
 int w2xc_split_halves(int terms, int cin, int cout);
 size_t w2xc_split_pack_last_bytes(int cin, int terms);   // terms = 2 (one- and two-term modes) or 3
 float w2xc_split_pack_last(int cin, int terms, int fmt, const float *w, void *dst);
+
+// upconv4x4_head (w2xc_upconv.hip), the head of an upconv model: w is [cin][nout][4][4] (torch's layout of nn.SpatialFullConvolution); the image is
+// 16 * nout * cin floats.  Tiles of 8 x 32 source pixels; the launch has w2xc_upconv_grid(tiles) workgroups, each walking tiles grid-stride.
+bool w2xc_upconv_supported(int cin, int nout);
+size_t w2xc_upconv_packed_floats(int cin, int nout);
+void w2xc_upconv_pack(int cin, int nout, const float *w, float *dst);
+int w2xc_upconv_grid(int ntiles);
+// a 3x3 layer of a head model with fewer than 32 planes on a side, zero-padded to cin_p x cout_p planes: dst[o][i][3][3] = w[o][i] for o < cout, i < cin, else 0
+void w2xc_pad_layer(int cin, int cout, int cin_p, int cout_p, const float *w, float *dst);
+// ... and the head's weights with zero input planes behind the model's: dst[c][nout][4][4], c < cin_p
+void w2xc_pad_head(int cin, int nout, int cin_p, const float *w, float *dst);

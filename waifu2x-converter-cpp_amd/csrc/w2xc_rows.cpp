@@ -64,6 +64,8 @@ hipError_t launch_kind(W2xcKernelKind kind, int midv, const W2xcConvDesc &d, con
     case W2XC_K_FIRST_U8:
     case W2XC_K_LAST:
     case W2XC_K_LAST_U8: return bd ? w2xc_launch_conv_batch(kind, d, *bd, st) : w2xc_launch_conv(kind, d, st);
+    case W2XC_K_UPCONV:
+    case W2XC_K_UPCONV_U8: return bd ? hipErrorInvalidValue : w2xc_launch_upconv(kind, d, st);
     default: break;
     }
     if (midv == MID_WINO4) return bd ? w2xc_launch_wino4_batch(d, *bd, st) : w2xc_launch_wino4(d, st);
@@ -356,7 +358,7 @@ int run_band(Band &B, const LayerSrc &view, int up)
         if (kind == W2XC_K_FUSED_AWAY) continue;
         // the uint8 forms (run_rows has checked the kinds they stand in for): the descriptor's strides are the image's, in bytes
         if (k == 1 && (B.u8 & ROWS_U8_SRC)) kind = W2XC_K_FIRST_U8;
-        if (k == n && (B.u8 & ROWS_U8_DST)) { kind = W2XC_K_LAST_U8; d.out_ps = 3; }
+        if (k == n && (B.u8 & ROWS_U8_DST)) { kind = kind == W2XC_K_UPCONV ? W2XC_K_UPCONV_U8 : W2XC_K_LAST_U8; d.out_ps = 3; }
         const int Tk = next.top;   // first plane row of the layer's region
         // the strategies that run layer n - 1 and the last layer together end the band
         if (prog_eligible(B, k, kind, d)) {
@@ -393,16 +395,18 @@ int run_rows(w2xc_model *m, DevCtx *c, const RowsCall &r, hipStream_t st, const 
     RowPlan P;
     if (int rc = plan_rows(m, o_in, r.w, r.view_h, r.view_y0, r.ra, r.rb, r.plane_h, r.n_in, r.out.ps != 0, &P)) return rc;
     if (int rc = check_u8_views(m, P, r.u8, r.hk != nullptr, r.in.ps, r.out.ps)) return rc;
+    if (m->has_head() && (r.hk || r.up)) return fail(W2XC_ERR_ARG, "internal error: an upconv head model behind hooks or a nearest-2x");
     for (int i = 0; i < 2; i++)
         if (P.need[i]) { int rc = c->ws[i].reserve((P.need[i] + 3) / 4 * sizeof(float), "the activation workspace"); if (rc) return rc; }
     LayerSrc view;   // the source view; its first row is plane row view_y0
     view.p = r.in.p; view.rs = (long long)r.in.rs; view.cs = r.in.ps;
     view.h = r.view_h; view.w = r.w; view.top = r.view_y0;
     if (r.u8 & ROWS_U8_SRC) view.ps = 3;   // (bytes: row stride in.rs, pixels 3 apart, channels in.ps = 1 apart)
+    const size_t out_rows_per_row = m->has_head() ? 2 : 1;   // (an upconv head model: ra, rb and the bands count SOURCE rows, each gives two output rows)
     for (int y0 = r.ra; y0 < r.rb; y0 += P.band) {
         // the band's first output row: out.rs floats per row, or -- a uint8 image -- as many BYTES
-        float *band_out = (r.u8 & ROWS_U8_DST) ? reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(r.out.p) + (size_t)(y0 - r.ra) * r.out.rs)
-                                              : r.out.p + (size_t)(y0 - r.ra) * r.out.rs;
+        const size_t row0 = (size_t)(y0 - r.ra) * out_rows_per_row;
+        float *band_out = (r.u8 & ROWS_U8_DST) ? reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(r.out.p) + row0 * r.out.rs) : r.out.p + row0 * r.out.rs;
         Band B = {m, c, P, r.hk, st, band_out, (long long)r.out.rs, r.out.ps, y0, std::min(r.rb, y0 + P.band), r.rb, 0, r.u8};
         if (int rc = run_band(B, view, r.up)) return rc;
     }
@@ -413,6 +417,7 @@ int run_rows(w2xc_model *m, DevCtx *c, const RowsCall &r, hipStream_t st, const 
 static int check_plane_args(const w2xc_model *m, const void *in, size_t in_stride, int w, int h, const void *out, size_t out_stride, int up = 0)
 {
     if (!m || !in || !out) return fail(W2XC_ERR_ARG, "null argument");
+    if (int rc = refuse_head(m, "w2xc_convert_plane* / w2xc_convert_rows_device")) return rc;
     if (int rc = check_plane_size(w, h, false)) return rc;
     return check_row_strides(in_stride, w, out_stride, (size_t)w << up);
 }
@@ -421,6 +426,10 @@ int check_planes_args(const w2xc_model *m, int up, int n_in_planes, const void *
                       const void *d_out, size_t out_plane_stride_bytes, size_t out_stride_bytes, const w2xc_opts &o)
 {
     if (!m || !d_in || !d_out) return fail(W2XC_ERR_ARG, "null argument");
+    // up = 2: w2xc_convert_planes_up2x_device -- a head model, and only there; the output planes are 2w x 2h as with up = 1
+    if (up == 2 ? !m->has_head() : m->has_head())
+        return up == 2 ? fail(W2XC_ERR_ARG, "w2xc_convert_planes_up2x_device: the model has no upconv head") : refuse_head(m, "w2xc_convert_planes[_nn2x][_batch]_device");
+    up = up ? 1 : 0;
     if (int rc = check_plane_size(w, h, up != 0)) return rc;
     const int W = w << up, H = h << up;
     if (int rc = check_row_strides(in_stride_bytes, w, out_stride_bytes, W)) return rc;
@@ -490,6 +499,7 @@ int run_batch(w2xc_model *m, DevCtx *c, int nimg, int up, PlanesIn in, int w, in
 int check_batch_args(const w2xc_model *m, int nimg, int nn2x, int w, int h, size_t in_stride, size_t out_stride)
 {
     if (!m) return fail(W2XC_ERR_ARG, "null model");
+    if (int rc = refuse_head(m, "the batch calls")) return rc;
     if (nimg < 1) return fail(W2XC_ERR_ARG, "batch of %d planes", nimg);
     if (nn2x != 0 && nn2x != 1) return fail(W2XC_ERR_ARG, "nn2x must be 0 or 1");
     if (int rc = check_plane_size(w, h, true)) return rc;
@@ -617,6 +627,19 @@ try {
     return convert_planes(m, 1, n_in_planes, d_in, in_plane_stride_bytes, in_stride_bytes, w, h, d_out, out_plane_stride_bytes, out_stride_bytes, hip_stream, opts);
 } W2XC_CATCH_ALL
 
+// an upconv head model on float planes: (w, h) is the source size, the output planes are 2w x 2h; the band loop runs on SOURCE rows (run_rows)
+int w2xc_convert_planes_up2x_device(w2xc_model *m, int n_in_planes, const float *d_in, size_t in_plane_stride_bytes,
+                                    size_t in_stride_bytes, int w, int h, float *d_out, size_t out_plane_stride_bytes,
+                                    size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts)
+try {
+    const w2xc_opts o = resolve_opts(opts);
+    if (int rc = check_planes_args(m, 2, n_in_planes, d_in, in_plane_stride_bytes, in_stride_bytes, w, h, d_out, out_plane_stride_bytes, out_stride_bytes, o))
+        return rc;
+    if (o.precision != W2XC_PRECISION_FP32) return fail(W2XC_ERR_UNSUPPORTED, "16-bit precision modes: not available for a model with an upconv head (W2XC_PRECISION_FP32 only)");
+    const PlanesIn in{d_in, in_stride_bytes / 4, (long long)(in_plane_stride_bytes / 4)};
+    return rows_on_device(m, RowsCall::whole(in, n_in_planes, w, h, {d_out, out_stride_bytes / 4, (long long)(out_plane_stride_bytes / 4)}, 0), hip_stream, o);
+} W2XC_CATCH_ALL
+
 int w2xc_convert_plane_nn2x_device(w2xc_model *m, const float *d_in, size_t in_stride_bytes, int w, int h, float *d_out,
                                    size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts)
 try {
@@ -664,6 +687,7 @@ try {
     if (nn2x != 0 && nn2x != 1) return fail(W2XC_ERR_ARG, "nn2x must be 0 or 1");
     if (int rc = check_plane_size(w, h, true)) return rc;
     if (m->layers.empty()) return fail(W2XC_ERR_ARG, "model has no layers");
+    if (m->has_head()) { *batched = 0; *sub_batch = 1; return W2XC_OK; }   // (no batch call runs an upconv head model)
     const w2xc_opts o = resolve_opts(opts);
     const int W = w << nn2x, H = h << nn2x;
     RowPlan P;

@@ -13,10 +13,28 @@ int split_terms(const w2xc_opts &o)
 }
 int split_fmt(const w2xc_opts &o) { return o.precision == W2XC_PRECISION_FP16X2 ? 1 : 0; }
 
+// the 128 -> 256 layer in front of the head of an upconv model (the published upconv_7 topology; half of its work): conv3x3_wino4 has an instantiation
+// for it, planar in and NHWC out, and no other fast kernel has -- with any other choice of w2xc_opts.kernel it runs conv3x3_direct like every shape
+// without a kernel.  Models without a head are not asked: their selection stays w2xc_pick_kernel's.
+static bool wide_layer(const w2xc_model *m, int l)
+{
+    const int n = (int)m->layers.size();
+    return m->has_head() && l == n - 2 && l > 0 && m->layers[l].nin == 128 && m->layers[l].nout == 256;
+}
+
+W2xcKernelKind pick_kind(const w2xc_model *m, int l)
+{
+    if (m->layers[l].head) return W2XC_K_UPCONV;
+    if (wide_layer(m, l)) return W2XC_K_MFMA;
+    return w2xc_pick_kernel(m->layers[l].nin, m->layers[l].nout);
+}
+
 W2xcKernelKind layer_kind(const w2xc_model *m, int l, const w2xc_opts &o)
 {
+    if (m->layers[l].head) return W2XC_K_UPCONV;   // (the head has one kernel, whatever runs the 3x3 layers)
     if (o.kernel == W2XC_KERNEL_DIRECT) return W2XC_K_DIRECT;
-    const W2xcKernelKind k = w2xc_pick_kernel(m->layers[l].nin, m->layers[l].nout);
+    const W2xcKernelKind k = pick_kind(m, l);
+    if (wide_layer(m, l) && layer_mid_variant(m, l, o) != MID_WINO4) return W2XC_K_DIRECT;
     const int n = (int)m->layers.size();
     if (split_terms(o) > 0) {
         // term planes live only BETWEEN a first/mid layer and a mid layer; everything that touches the
@@ -24,7 +42,7 @@ W2xcKernelKind layer_kind(const w2xc_model *m, int l, const w2xc_opts &o)
         if (l <= 1 && fuse_first(m, o)) return l == 0 ? W2XC_K_FUSED_AWAY : W2XC_K_FIRST2_SPLIT;
         if (k == W2XC_K_MFMA) return l > 0 ? W2XC_K_MID_SPLIT : W2XC_K_DIRECT;
         if (k == W2XC_K_FIRST && l == 0)
-            return (n > 1 && w2xc_pick_kernel(m->layers[1].nin, m->layers[1].nout) == W2XC_K_MFMA) ? W2XC_K_FIRST_SPLIT : W2XC_K_FIRST;
+            return (n > 1 && pick_kind(m, 1) == W2XC_K_MFMA) ? W2XC_K_FIRST_SPLIT : W2XC_K_FIRST;
         if (k == W2XC_K_LAST && l == n - 1 && l > 0) return fuse_last(m, o) ? W2XC_K_LAST_GATHER : W2XC_K_LAST;
         return W2XC_K_DIRECT;   // run_rows rejects this
     }
@@ -53,9 +71,9 @@ bool gather_in_producer(const w2xc_model *m, const w2xc_opts &o)
 bool fuse_first(const w2xc_model *m, const w2xc_opts &o)
 {
     const int n = (int)m->layers.size();
-    if (!fusion_first_on(o) || o.kernel == W2XC_KERNEL_DIRECT || n < 3 || split_terms(o) == 0) return false;
+    if (!fusion_first_on(o) || o.kernel == W2XC_KERNEL_DIRECT || n < 3 || split_terms(o) == 0 || m->has_head()) return false;
     if (m->layers[0].nin != 1 || m->layers[0].nout != 32) return false;
-    if (w2xc_pick_kernel(m->layers[1].nin, m->layers[1].nout) != W2XC_K_MFMA) return false;
+    if (pick_kind(m, 1) != W2XC_K_MFMA) return false;
     return !(n == 3 && fuse_last(m, o));   // (layer 2 would be the fused-last producer: keep that fusion instead)
 }
 
@@ -67,8 +85,8 @@ bool fuse_last(const w2xc_model *m, const w2xc_opts &o)
     if (!fusion_last_on(o) || o.kernel == W2XC_KERNEL_DIRECT || n < 3) return false;
     const int T = split_terms(o);
     if (T < 1 || T > 3) return false;
-    return m->layers[n - 1].nout == 1 && w2xc_pick_kernel(m->layers[n - 1].nin, 1) == W2XC_K_LAST &&
-           w2xc_pick_kernel(m->layers[n - 2].nin, m->layers[n - 2].nout) == W2XC_K_MFMA && n - 2 > 0;
+    return m->layers[n - 1].nout == 1 && pick_kind(m, n - 1) == W2XC_K_LAST &&
+           pick_kind(m, n - 2) == W2XC_K_MFMA && n - 2 > 0;
 }
 
 // terms of layer l's OUTPUT in the split pipeline: T when layer l+1 is a split mid layer, else 0 (fp32); 9 = this layer writes
@@ -118,6 +136,7 @@ int layer_mid_variant(const w2xc_model *m, int l, const w2xc_opts &o)
 {
     const HostLayer &p = m->layers[l];
     int midv = mid_variant(o);
+    if (wide_layer(m, l)) return midv == MID_WINO4 ? MID_WINO4 : MID_MFMA;   // (conv3x3_wino4 or nothing: layer_kind)
     return mid_variant_for(midv, p.nin, p.nout);
 }
 // does any layer of the fp32 path run conv3x3_wino4 (F(4x4,3x3))?  Its 4x4 blocks make results depend on where a band's per-layer regions end,
@@ -126,7 +145,7 @@ bool uses_wino4(const w2xc_model *m, const w2xc_opts &o)
 {
     if (split_terms(o) != 0 || o.precision != W2XC_PRECISION_FP32 || o.kernel == W2XC_KERNEL_DIRECT) return false;
     for (int l = 0; l < (int)m->layers.size(); l++)
-        if (w2xc_pick_kernel(m->layers[l].nin, m->layers[l].nout) == W2XC_K_MFMA && layer_mid_variant(m, l, o) == MID_WINO4) return true;
+        if (pick_kind(m, l) == W2XC_K_MFMA && layer_mid_variant(m, l, o) == MID_WINO4) return true;
     return false;
 }
 // conv3x3_wino4 reads PLANAR activations (one plane per channel, rows of roundup32(w) floats: 16-byte aligned pixel quads, tiles on 128-byte lines)
@@ -138,7 +157,7 @@ bool uses_wino4(const w2xc_model *m, const w2xc_opts &o)
 bool is_wino4_layer(const w2xc_model *m, int l, const w2xc_opts &o)
 {
     if (split_terms(o) != 0 || o.precision != W2XC_PRECISION_FP32 || o.kernel == W2XC_KERNEL_DIRECT) return false;
-    return l >= 0 && l < (int)m->layers.size() && w2xc_pick_kernel(m->layers[l].nin, m->layers[l].nout) == W2XC_K_MFMA && layer_mid_variant(m, l, o) == MID_WINO4;
+    return l >= 0 && l < (int)m->layers.size() && pick_kind(m, l) == W2XC_K_MFMA && layer_mid_variant(m, l, o) == MID_WINO4;
 }
 bool planar_between(const w2xc_model *m, int l, const w2xc_opts &o)   // layout of layer l's output = layer l + 1's input
 {
@@ -159,7 +178,7 @@ bool fuse_last_fp32(const w2xc_model *m, const w2xc_opts &o)
     if (split_terms(o) != 0 || o.precision != W2XC_PRECISION_FP32 || o.kernel == W2XC_KERNEL_DIRECT || n < 3) return false;
     if (!fusion_last_on(o)) return false;   // (W2XC_FUSION_AUTO = on)
     const HostLayer &p = m->layers[n - 2], &q = m->layers[n - 1];
-    if (q.nout != 1 || q.nin != p.nout || w2xc_pick_kernel(q.nin, 1) != W2XC_K_LAST || w2xc_pick_kernel(p.nin, p.nout) != W2XC_K_MFMA) return false;
+    if (q.nout != 1 || q.nin != p.nout || pick_kind(m, n - 1) != W2XC_K_LAST || pick_kind(m, n - 2) != W2XC_K_MFMA) return false;
     const int v = layer_mid_variant(m, n - 2, o);
     return v == MID_WINO4;
 }
@@ -170,7 +189,7 @@ bool fuse_last_fp32(const w2xc_model *m, const w2xc_opts &o)
 bool fuse_first_fp32(const w2xc_model *m, const w2xc_opts &o)
 {
     const int n = (int)m->layers.size();
-    if (split_terms(o) != 0 || o.precision != W2XC_PRECISION_FP32 || n < 3 || !fusion_first_on(o)) return false;
+    if (split_terms(o) != 0 || o.precision != W2XC_PRECISION_FP32 || n < 3 || !fusion_first_on(o) || m->has_head()) return false;   // (head models: no cross-layer fusion)
     if (o.kernel != W2XC_KERNEL_AUTO && o.kernel != W2XC_KERNEL_WINOGRAD4) return false;
     const HostLayer &a = m->layers[0], &b = m->layers[1];
     if (!w2xc_first2_wino4_supported(a.nin, a.nout, b.nout) || b.nin != a.nout) return false;
@@ -193,7 +212,9 @@ bool u8_source_layer(const w2xc_model *m, const w2xc_opts &o)
 bool u8_sink_layer(const w2xc_model *m, const w2xc_opts &o)
 {
     const int n = (int)m->layers.size();
-    return u8_forms_on(o) && n > 0 && m->layers[n - 1].nout == 3 && layer_kind(m, n - 1, o) == W2XC_K_LAST;
+    if (!u8_forms_on(o) || n == 0 || m->layers[n - 1].nout != 3) return false;
+    const W2xcKernelKind k = layer_kind(m, n - 1, o);
+    return k == W2XC_K_LAST || k == W2XC_K_UPCONV;   // (the head of an upconv model: upconv4x4_head, U8)
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -248,11 +269,19 @@ int plan_rows(const w2xc_model *m, const w2xc_opts &o_in, int w, int vh, int vy0
                         vy0, vy0 + vh, ra, rb, hs);
         // (an explicit W2XC_KERNEL_WINOGRAD4 on a narrow view runs as asked: results then depend on the banding at rounding level)
     }
+    const bool head = m->has_head();
+    if (head) {   // (the entry points that run a head model: every other one has refused it -- refuse_head)
+        const HostLayer &hd = m->layers[n - 1];
+        if (split_terms(P.o) != 0) return fail(W2XC_ERR_UNSUPPORTED, "16-bit precision modes: not available for a model with an upconv head (W2XC_PRECISION_FP32 only)");
+        if (n < 2) return fail(W2XC_ERR_UNSUPPORTED, "an upconv head needs at least one 3x3 layer in front of it");
+        if (!w2xc_upconv_supported(hd.nin, hd.nout))
+            return fail(W2XC_ERR_UNSUPPORTED, "upconv head %d->%d: the head kernel takes 32, 64, 128 or 256 planes (fewer than 32 are zero-padded) and gives 1 or 3", hd.decl_nin(), hd.decl_nout());
+    }
     if (m->layers[0].nin != n_in)   // convertWithModelsBasic pushes exactly one plane (convertRoutine.cpp:63-64)
         return fail(W2XC_ERR_PLANES, "Error : Model-filter : \nnumber of input planes mismatch.\n%d,%d", n_in, m->layers[0].nin);
     for (int l = 1; l < n; l++)
-        if (m->layers[l].nin != m->layers[l - 1].nout)
-            return fail(W2XC_ERR_PLANES, "Error : Model-filter : \nnumber of input planes mismatch.\n%d,%d", m->layers[l - 1].nout, m->layers[l].nin);
+        if (m->layers[l].decl_nin() != m->layers[l - 1].decl_nout())   // (what the model declares: a head model's zero padding would hide 16 against 20)
+            return fail(W2XC_ERR_PLANES, "Error : Model-filter : \nnumber of input planes mismatch.\n%d,%d", m->layers[l - 1].decl_nout(), m->layers[l].decl_nin());
     P.T = split_terms(P.o);
     if (P.o.precision != W2XC_PRECISION_FP32 && P.T == 0) return fail(W2XC_ERR_ARG, "unknown precision %d", P.o.precision);
     if (P.o.fusion < W2XC_FUSION_AUTO || P.o.fusion > W2XC_FUSION_PROG) return fail(W2XC_ERR_ARG, "unknown w2xc_opts.fusion %d", P.o.fusion);
@@ -278,9 +307,9 @@ int plan_rows(const w2xc_model *m, const w2xc_opts &o_in, int w, int vh, int vy0
     // the last layer stores straight into the caller's planar plane(s) when its kernel can address planar
     // output (conv3x3_last / conv3x3_direct); otherwise it goes through the NHWC workspace + a repack
     P.last_kind = layer_kind(m, n - 1, P.o);
-    P.last_direct = (m->layers[n - 1].nout == 1 || all_out) &&
+    P.last_direct = head || ((m->layers[n - 1].nout == 1 || all_out) &&
                     (P.last_kind == W2XC_K_LAST || P.last_kind == W2XC_K_LAST_GATHER || P.last_kind == W2XC_K_DIRECT ||
-                     (m->layers[n - 1].nout == 1 && P.last_kind != W2XC_K_MFMA && P.last_kind != W2XC_K_FIRST));
+                     (m->layers[n - 1].nout == 1 && P.last_kind != W2XC_K_MFMA && P.last_kind != W2XC_K_FIRST)));
     int band = P.o.band_rows;
     const int total = rb - ra;
     if (band <= 0) {
@@ -338,7 +367,7 @@ W2xcKernelKind layer_desc(const w2xc_model *m, const RowPlan &P, int k, int y0, 
     d.off_x = k == 1 ? -n : 0;
     // this launch's first output row in the coordinates of the whole plane, modulo the Winograd block height (2; conv3x3_wino4: 4)
     const W2xcKernelKind kind = layer_kind(m, k - 1, o);
-    d.wino_py = Tk & (((w2xc_pick_kernel(hl.nin, hl.nout) == W2XC_K_MFMA && layer_mid_variant(m, k - 1, o) == MID_WINO4) || kind == W2XC_K_FIRST2_WINO4) ? 3 : 1);
+    d.wino_py = Tk & (((pick_kind(m, k - 1) == W2XC_K_MFMA && layer_mid_variant(m, k - 1, o) == MID_WINO4) || kind == W2XC_K_FIRST2_WINO4) ? 3 : 1);
     d.in_shift = k == 1 ? up : 0;
     *next = src;
     next->top = Tk;

@@ -267,9 +267,9 @@ __global__ void __launch_bounds__(512, 2) conv3x3_wino4_batch_l(W2xcConvDesc d, 
 
 // ------------------------------------------------------------------------------------------------
 // host side: launch (shape predicates, PROG's job arithmetic and the packers: w2xc_pack.cpp).
-// Five objects (make -j): W2XC_WINO4_PART = 0 the planar-out instantiations + dispatcher, 1 the NHWC-out ones, 2 the fused-last ones,
+// Eight objects (make -j): W2XC_WINO4_PART = 0 the planar-out instantiations + dispatcher, 1 the NHWC-out ones, 2 the fused-last ones,
 // 3 the batch forms with planar out + the batch dispatcher, 4 the fused-last batch forms, 5 the batch forms with 32 NHWC planes in, 6 those with planar
-// planes in and NHWC out.
+// planes in and NHWC out, 7 the 128 -> 256 layer of upconv models (NHWC out).
 // ------------------------------------------------------------------------------------------------
 #ifndef W2XC_WINO4_PART
 #define W2XC_WINO4_PART -1   // one translation unit with everything (tools/ubench)
@@ -312,9 +312,20 @@ hipError_t w2xc_launch_wino4_nhwc_out(const W2xcConvDesc &d, hipStream_t stream)
     case 64128:  return launch_wino4<64, 128, false>(d, stream);
     case 128064: return launch_wino4<128, 64, false>(d, stream);
     case 128128: return launch_wino4<128, 128, false>(d, stream);
+    case 128256: return w2xc_launch_wino4_wide(d, stream);   // (part 7)
     default: return hipErrorInvalidValue;
     }
 #endif
+}
+#endif
+
+// 128 -> 256 planes, planar in, NHWC out: the layer in front of an upconv head.  The plain instantiation -- the item walk is tiles x (COUT / 64) for any COUT,
+// and its LDS comes to exactly 160 KiB (the bias is the only term that grows); reached through w2xc_launch_wino4's checks and the NHWC-out dispatcher above
+#if W2XC_WINO4_PART == 7 || W2XC_WINO4_PART == -1
+hipError_t w2xc_launch_wino4_wide(const W2xcConvDesc &d, hipStream_t stream)
+{
+    if (d.cin != 128 || d.cout != 256 || d.in_ps != 1 || d.out_ps != 256 || d.out_cs != 1 || d.out_terms == 9) return hipErrorInvalidValue;
+    return launch_wino4<128, 256, false>(d, stream);
 }
 #endif
 
