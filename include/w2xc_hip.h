@@ -144,7 +144,7 @@ int w2xc_model_load_json(const char *path, w2xc_model **out);
 int w2xc_model_from_arrays(int n_layers, const int *nin, const int *nout,
                            const float *const *weight, const double *const *bias, w2xc_model **out);
 
-/* ---- upconv head models (revision 0.4.1.6) ----
+/* ---- upconv head models (revision 0.4.1.6; their batch and TTA forms: 0.4.1.6.1) ----
  * The upconv_7 family of later upstream versions: the model does the 2x enlargement itself, in its last layer, so nothing is enlarged in front of it.  v1
  * of the reference has no such path; the arithmetic is defined here.
  *   model:  a HEAD MODEL is n - 1 >= 1 ordinary 3x3 layers followed by one head layer: C planes in, nout in {1, 3} planes out, a 4x4 kernel, stride 2,
@@ -173,6 +173,8 @@ int w2xc_model_from_arrays(int n_layers, const int *nin, const int *nout,
  *   calls:  w2xc_convert_planes_up2x_device and w2xc_process_image_rgb_u8_ex[_device] (a head model as scale_model) run a head model.  EVERY other entry
  *           point given one returns W2XC_ERR_UNSUPPORTED from its argument checks, before a device is touched: the Y route, w2xc_convert_plane*,
  *           w2xc_convert_planes[_nn2x]_device, the batch, TTA and RGBA calls, w2xc_layer_filter*; w2xc_batch_plan answers "not batched".
+ *   batch:  (0.4.1.6.1) the batch and TTA forms of a head model are entry points of their own, below: w2xc_convert_planes_up2x_batch_device and
+ *           w2xc_process_image_rgb_u8_up2x_batch[_device]; w2xc_batch_plan plans them with nn2x = 2.  The calls above go on refusing a head model.
  * w2xc_model_add_upconv_head appends the head to a model from w2xc_model_from_arrays: weight is [nin][nout][4][4] with nin = the last 3x3 layer's output
  * planes, bias nout doubles or NULL (zeros).  It must come before the model's first use on a device and only once: otherwise W2XC_ERR_ARG.
  * w2xc_model_layers / _nin / _nout count the head as the last layer; w2xc_model_get_layer gives its weight as [nin][nout][4][4]. */
@@ -277,6 +279,37 @@ int w2xc_convert_planes_up2x_device(w2xc_model *m, int n_in_planes, const float 
                                     size_t in_stride_bytes, int w, int h, float *d_out, size_t out_plane_stride_bytes,
                                     size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts);
 
+/* (0.4.1.6.1) The batch form of w2xc_convert_planes_up2x_device: n images of n_in_planes planes of w x h, image i's planes in_image_stride_bytes behind
+ * image 0's, ALL planes of the head out at 2w x 2h, image i's out_image_stride_bytes behind image 0's.  Arguments as w2xc_convert_planes_batch_device
+ * without nn2x; its checks too (n < 1, null pointers, bad sizes and strides, images that overlap: W2XC_ERR_ARG; a plane count the model does not take:
+ * W2XC_ERR_PLANES), a model without a head is W2XC_ERR_ARG, a 16-bit precision W2XC_ERR_UNSUPPORTED; no device is touched by a refused call.  Image i is
+ * BIT-identical to w2xc_convert_planes_up2x_device on image i for every option set.  A three-plane head model under the default options (fp32,
+ * W2XC_KERNEL_AUTO, one band) runs ONE launch per layer for a sub-batch of as many images as w2xc_opts.workspace_mb holds -- conv3x3_first_batch,
+ * conv3x3_wino_batch / conv3x3_wino4_batch[_l] (the 128 -> 256 layer among them), upconv4x4_head_batch --; everything else (a one-plane head model,
+ * named kernels, images of more than one band) runs the single-image launch sequence per image.  w2xc_batch_plan(m, n_in_planes, w, h, 2, ...) answers
+ * which, and the sub-batch size (a model without a head: W2XC_ERR_ARG).  Asynchronous on hip_stream. */
+int w2xc_convert_planes_up2x_batch_device(w2xc_model *m, int n, int n_in_planes, const float *d_in, size_t in_image_stride_bytes,
+                                          size_t in_plane_stride_bytes, size_t in_stride_bytes, int w, int h, float *d_out,
+                                          size_t out_image_stride_bytes, size_t out_plane_stride_bytes, size_t out_stride_bytes, void *hip_stream,
+                                          const w2xc_opts *opts);
+
+/* (0.4.1.6.1) n RGB images of one size with an upconv head model as scale_model (it must be one: otherwise W2XC_ERR_ARG; noise_model is an ordinary RGB
+ * model or NULL, a head model there is W2XC_ERR_UNSUPPORTED).  Arguments, checks and the host form's overlap of sub-batches as
+ * w2xc_process_image_rgb_u8_batch_tta[_device]; tta must be 0 or 1 (W2XC_ERR_ARG).
+ *   tta = 0: image i has the bytes of w2xc_process_image_rgb_u8_ex[_device] on image i; a scale pass of S >= 2 images is one launch per layer where the
+ *            chain has batch kernels (above), the uint8-fused first and last layers included.
+ *   tta = 1: (n >= 1; n = 1 is the single-image TTA form) every pass is its TTA pass in the arithmetic of "test-time augmentation": spread at source
+ *            resolution, the head model on the 8 variants -- the images of ONE head batch where w == h, else 4 + 4 --, gather at 2x.  Image i has the bytes
+ *            of w2xc_u8_to_rgb_device, w2xc_tta_spread_device, w2xc_convert_planes_up2x_device on each variant, w2xc_tta_gather_device, w2xc_rgb_to_u8_device.
+ * Not built: RGBA forms, the Y route and 16-bit precisions for head models (W2XC_ERR_UNSUPPORTED / W2XC_ERR_PLANES as for the single-image call). */
+int w2xc_process_image_rgb_u8_up2x_batch_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in,
+                                                size_t in_image_stride_bytes, size_t in_stride_bytes, int w, int h, unsigned char *d_out,
+                                                size_t out_image_stride_bytes, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                                void *hip_stream, const w2xc_opts *opts, int tta);
+int w2xc_process_image_rgb_u8_up2x_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes,
+                                         int w, int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                         const w2xc_opts *opts, int tta);
+
 /* Batches: n planes of ONE size in one call (sprite sheets, icon sets, thumbnails, dataset crops, short clips).  (w, h) is the SOURCE size, the
  * output planes are (w << nn2x) x (h << nn2x) (nn2x = 1: the nearest-neighbour 2x of w2xc_convert_plane_nn2x folded into layer 1).  out[i] is
  * BIT-identical to w2xc_convert_plane[_nn2x][_device] on in[i] with the same opts, for every option set.  With the default fp32 chain (fp32,
@@ -316,7 +349,9 @@ int w2xc_convert_planes_batch_device(w2xc_model *m, int n, int nn2x, int n_in_pl
  * options -- *batched = 1 where a sub-batch is one launch per layer (the conditions above; a one-plane model is planned as w2xc_convert_batch_device
  * runs it), 0 where every image takes the single-image launch sequence; *sub_batch = images per sub-batch under w2xc_opts.workspace_mb (>= 1; 1 when
  * not batched).  The image calls on RGB models (w2xc_process_image_rgb_u8_batch*, the RGB route of the RGBA calls, TTA passes) batch their passes under
- * the same conditions.  W2XC_ERR_ARG for null pointers, nn2x other than 0 / 1 and bad sizes; the errors of the options and W2XC_ERR_PLANES as the call. */
+ * the same conditions.  W2XC_ERR_ARG for null pointers, nn2x other than 0 / 1 / 2 and bad sizes; the errors of the options and W2XC_ERR_PLANES as the call.
+ * (0.4.1.6.1) nn2x = 2 plans w2xc_convert_planes_up2x_batch_device: an upconv head model on its w x h source (a model without a head: W2XC_ERR_ARG).  With
+ * nn2x = 0 / 1 a head model is answered "not batched", (0, 1), as before: the calls those values plan refuse it. */
 int w2xc_batch_plan(const w2xc_model *m, int n_in_planes, int w, int h, int nn2x, const w2xc_opts *opts, int *batched, int *sub_batch);
 
 /* One UNIT of the tile farm from host memory (the reference's block walk, convertRoutine.cpp:114-165, made parallel across

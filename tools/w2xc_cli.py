@@ -15,7 +15,10 @@ RGBA; several such inputs are grouped by image size like the opaque ones, and a 
 other input goes exactly as before, the batch grouping included.
 Extension: -t/--tta 1 = test-time augmentation, the --tta of later upstream versions: every model pass on the 8 flips / transposes of the image, averaged
 (w2xc_process_image_[rgb_]u8[_batch]_tta; 8x the CNN work), on both routes and for grouped inputs.  The RGBA call has no TTA form: with an input that would
-take it, --tta 1 exits with a message before anything is converted."""
+take it, --tta 1 exits with a message before anything is converted.
+Extension: upconv scale models (upconv_7: the model enlarges by itself).  The RGB route; a size group of two or more opaque inputs, and every input under
+--tta 1, is ONE w2xc_process_image_rgb_u8_up2x_batch call (head_routes), an input alone its single-image call.  Inputs with transparency are refused: the
+RGBA form of such a model is not built."""
 import argparse
 import math
 import os
@@ -97,9 +100,10 @@ def check_tta(tta, alpha_files):
 
 
 def check_head(head, tta, alpha_files, groups):
-    """A scale model with an upconv head (upconv_7: the model enlarges by itself) runs through the single-image RGB call alone: --tta 1, inputs that
+    """What a scale model with an upconv head (upconv_7: the model enlarges by itself) cannot run THROUGH THE SINGLE-IMAGE RGB CALL: --tta 1, inputs that
     take the RGBA call (`alpha_files`: their names) and inputs of one size that would go as a batch (`groups`: lists of names, one per image size) are a
-    SystemExit with a message, before anything is converted; everything else passes"""
+    SystemExit with a message, before anything is converted; everything else passes.  main hands it the transparency case alone: same-size groups and
+    --tta 1 go to the head batch call (head_routes)."""
     if not head:
         return
     if tta:
@@ -111,6 +115,14 @@ def check_head(head, tta, alpha_files, groups):
     if batched:
         raise SystemExit("several inputs of one size (%s) would run as a batch, which is not built for an upconv scale model: convert them one per call"
                          % "; ".join(", ".join(g) for g in batched))
+
+
+def head_routes(tta, alpha_files, groups):
+    """How the opaque inputs of an upconv scale model run: [(call, [files]), ...], one entry per size group in the order given -- call = "up2x_batch" (ONE
+    w2xc_process_image_rgb_u8_up2x_batch call, with tta as given) for a group of two or more files and, under --tta 1, for every group; "single" (the
+    single-image RGB call) for a file alone without TTA.  Inputs with transparency (`alpha_files`) are check_head's SystemExit.  Pure: no file is opened."""
+    check_head(True, 0, alpha_files, [])
+    return [("up2x_batch" if tta or len(g) > 1 else "single", list(g)) for g in groups if g]
 
 
 def check_inputs(ap, args):
@@ -171,8 +183,9 @@ def main(argv=None):
     opaque = [(f, im) for f, im in zip(args.input_file, images) if im.shape[2] == 3]
     check_tta(args.tta, [f for f, im in zip(args.input_file, images) if im.shape[2] == 4])
     head = bool(scale is not None and iterations and scale.has_head)   # (an upconv model: the RGB route's single-image call, passed through as it is)
-    check_head(head, args.tta, [f for f, im in zip(args.input_file, images) if im.shape[2] == 4],
-               [files for _, files, _ in group_inputs([(f, (im.shape[1], im.shape[0])) for f, im in opaque], args.mode, args.noise_level, args.scale_ratio)])
+    routes = head_routes(args.tta, [f for f, im in zip(args.input_file, images) if im.shape[2] == 4],
+                         [files for _, files, _ in group_inputs([(f, (im.shape[1], im.shape[0])) for f, im in opaque], args.mode, args.noise_level,
+                                                                args.scale_ratio)]) if head else []
     tta = dict(tta=True) if args.tta else {}
     outs = {}
     if noise is None and iterations == 0 and not shrink:
@@ -188,7 +201,14 @@ def main(argv=None):
             outs[f] = w2xc.process_image_rgba_u8(alpha[f], noise, scale if iterations else None, iterations, opts, shrink)
         for files in batches:                      # one batch call per image size
             outs.update(zip(files, w2xc.process_image_rgba_u8_batch([alpha[f] for f in files], noise, scale if iterations else None, iterations, opts, shrink)))
-        if len(opaque) == 1 or head:   # (an upconv scale model: every input its own call -- check_head)
+        if head:   # (an upconv scale model: the head batch call per size group, an input alone its single-image call -- head_routes)
+            by_file = dict(opaque)
+            for call, files in routes:
+                if call == "single":
+                    outs[files[0]] = process(by_file[files[0]], noise, scale, iterations, opts, shrink)
+                else:
+                    outs.update(zip(files, w2xc.process_image_rgb_u8_up2x_batch([by_file[f] for f in files], noise, scale, iterations, opts, shrink, **tta)))
+        elif len(opaque) == 1:
             for f, im in opaque:
                 outs[f] = process(im, noise, scale if iterations else None, iterations, opts, shrink, **tta)
         elif opaque:

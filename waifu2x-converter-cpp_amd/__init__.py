@@ -119,6 +119,9 @@ def _load():
         "w2xc_bleed_rgba_u8_trim": (ci, []),
         "w2xc_convert_planes_nn2x_device": (ci, [vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, vp, C.POINTER(Opts)]),
         "w2xc_convert_planes_up2x_device": (ci, [vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, vp, C.POINTER(Opts)]),
+        "w2xc_convert_planes_up2x_batch_device": (ci, [vp, ci, ci, fp, cs, cs, cs, ci, ci, fp, cs, cs, cs, vp, C.POINTER(Opts)]),
+        "w2xc_process_image_rgb_u8_up2x_batch_device": (ci, [vp, vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, ci, C.c_double, vp, C.POINTER(Opts), ci]),
+        "w2xc_process_image_rgb_u8_up2x_batch": (ci, [vp, vp, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, ci, C.c_double, C.POINTER(Opts), ci]),
         "w2xc_u8_to_rgb_device": (ci, [fp, cs, ci, ci, fp, fp, fp, vp]),
         "w2xc_rgb_to_u8_device": (ci, [fp, fp, fp, ci, ci, fp, cs, vp]),
         "w2xc_process_image_u8_device": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, vp, C.POINTER(Opts)]),
@@ -439,11 +442,23 @@ class _ModelSet:
         if rc != OK:
             raise W2xcError(rc, last_error())
 
-    def batch_plan(self, n_in, w, h, nn2x=False, opts=None):
+    def convert_planes_up2x_batch_device(self, n, n_in, d_in, in_image_stride_bytes, in_plane_stride_bytes, in_stride_bytes, w, h, d_out,
+                                         out_image_stride_bytes, out_plane_stride_bytes, out_stride_bytes, stream=0, opts=None):
+        """Device-pointer batch for an upconv head model (w2xc_convert_planes_up2x_batch_device): n images of n_in planes of w x h, image i at d_in +
+        i * in_image_stride_bytes, every plane of the head out at 2w x 2h.  Each image has the bits of convert_planes_up2x_device.  Asynchronous
+        on `stream`."""
+        rc = _lib.w2xc_convert_planes_up2x_batch_device(self.handle, n, n_in, C.c_void_p(d_in), in_image_stride_bytes, in_plane_stride_bytes,
+                                                        in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes, out_plane_stride_bytes,
+                                                        out_stride_bytes, C.c_void_p(stream), C.byref(opts) if opts is not None else None)
+        if rc != OK:
+            raise W2xcError(rc, last_error())
+
+    def batch_plan(self, n_in, w, h, nn2x=False, opts=None, up2x=False):
         """(batched, sub_batch) of w2xc_batch_plan: does a batch of w x h images of n_in planes run one launch per layer with these options, and how
-        many images one sub-batch takes.  Host arithmetic only."""
+        many images one sub-batch takes.  up2x: the plan of convert_planes_up2x_batch_device (an upconv head model; nn2x does not apply).  Host
+        arithmetic only."""
         batched, sub = C.c_int(0), C.c_int(0)
-        rc = _lib.w2xc_batch_plan(self.handle, n_in, w, h, 1 if nn2x else 0, C.byref(opts) if opts is not None else None, C.byref(batched), C.byref(sub))
+        rc = _lib.w2xc_batch_plan(self.handle, n_in, w, h, 2 if up2x else 1 if nn2x else 0, C.byref(opts) if opts is not None else None, C.byref(batched), C.byref(sub))
         if rc != OK:
             raise W2xcError(rc, last_error())
         return batched.value, sub.value
@@ -820,6 +835,22 @@ def process_image_rgb_u8_batch_device(n, d_in, in_image_stride_bytes, in_stride_
     entry, tail = _tta_entry("w2xc_process_image_rgb_u8_batch_device", tta)
     _check(entry(*_handles(noise, scale), n, C.c_void_p(d_in), in_image_stride_bytes, in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes,
                  out_stride_bytes, iterations, float(shrink_ratio), C.c_void_p(stream), C.byref(opts) if opts is not None else None, *tail))
+
+
+def process_image_rgb_u8_up2x_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, out=None, tta=False):
+    """n uint8 images of one size with an upconv head model as `scale` (w2xc_process_image_rgb_u8_up2x_batch); arguments and checks as
+    process_image_rgb_u8_batch.  Image i is byte-identical to process_image_rgb_u8(imgs[i], ...); tta: every pass on the 8 flips / transposes, the
+    variants as the images of a head batch (n = 1 is the single-image TTA form)."""
+    return _image_batch(_lib.w2xc_process_image_rgb_u8_up2x_batch, "process_image_rgb_u8_up2x_batch", imgs, noise, scale, iterations, opts, shrink_ratio, out,
+                        (1 if tta else 0,))
+
+
+def process_image_rgb_u8_up2x_batch_device(n, d_in, in_image_stride_bytes, in_stride_bytes, w, h, d_out, out_image_stride_bytes, out_stride_bytes,
+                                           noise=None, scale=None, iterations=0, shrink_ratio=0.0, stream=0, opts=None, tta=False):
+    """Device-pointer form (w2xc_process_image_rgb_u8_up2x_batch_device); arguments as process_image_rgb_u8_batch_device."""
+    _check(_lib.w2xc_process_image_rgb_u8_up2x_batch_device(*_handles(noise, scale), n, C.c_void_p(d_in), in_image_stride_bytes, in_stride_bytes, w, h,
+                                                            C.c_void_p(d_out), out_image_stride_bytes, out_stride_bytes, iterations, float(shrink_ratio),
+                                                            C.c_void_p(stream), C.byref(opts) if opts is not None else None, 1 if tta else 0))
 
 
 def u8_to_rgb_device(d_in, in_stride_bytes, w, h, d_planes, stream=0):

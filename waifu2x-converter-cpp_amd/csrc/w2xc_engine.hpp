@@ -289,8 +289,9 @@ inline bool ranges_overlap(const void *in, size_t in_extent, const void *out, si
     return i0 < o0 + out_extent && o0 < i0 + in_extent;
 }
 
-// what every entry point but w2xc_convert_planes_up2x_device and w2xc_process_image_rgb_u8_ex[_device] answers for an upconv head model, in its argument
-// checks (no device is touched)
+// what every entry point but w2xc_convert_planes_up2x_device and w2xc_process_image_rgb_u8_ex[_device] -- and, since 0.4.1.6.1, their batch / TTA forms
+// w2xc_convert_planes_up2x_batch_device and w2xc_process_image_rgb_u8_up2x_batch[_device] -- answers for an upconv head model, in its argument checks (no
+// device is touched; the message is pinned by tests/test_upconv_api.py)
 inline int refuse_head(const w2xc_model *m, const char *call)
 {
     if (!m || !m->has_head()) return W2XC_OK;
@@ -424,7 +425,7 @@ int check_planes_args(const w2xc_model *m, int up, int n_in_planes, const void *
 // ---- batches of same-size planes (w2xc_convert_batch*) ----
 // a batched launch chain runs a call planned as P (one image of the batch): fp32, W2XC_KERNEL_AUTO, the whole image in one band, and either conv3x3_first2_wino4 ->
 // conv3x3_wino4 (planar) ... -> conv3x3_wino4 FUSE7 -> gather with one plane in and out, or -- three planes in, three out -- conv3x3_first -> conv3x3_wino /
-// conv3x3_wino4 ... -> conv3x3_last.  Everything else takes the single-image launch sequence per image.
+// conv3x3_wino4 ... -> conv3x3_last, or -- a three-plane upconv head model -- -> upconv4x4_head.  Everything else takes the single-image launch sequence per image.
 bool batch_eligible(const w2xc_model *m, const RowPlan &P);
 // images per sub-batch for a per-image workspace of img_floats[2] floats under the call's workspace_mb budget (>= 1)
 int batch_sub_size(const w2xc_opts &o, const size_t img_floats[2]);
@@ -442,12 +443,12 @@ int run_batch_planes(w2xc_model *m, DevCtx *c, int nimg, int up, const BatchIO &
 // per-image workspace floats of the batched chain (0, 0 when P is not eligible) -- what a sub-batch of k images needs is k times this
 void batch_ws_floats(const RowPlan &P, size_t img_floats[2]);
 int check_batch_model(const w2xc_model *m);
-int check_batch_args(const w2xc_model *m, int nimg, int nn2x, int w, int h, size_t in_stride, size_t out_stride);
+int check_batch_args(const w2xc_model *m, int nimg, int nn2x, int w, int h, size_t in_stride, size_t out_stride, bool head_call = false);
 int check_batch_device_args(const w2xc_model *m, int n, int nn2x, const void *d_in, size_t in_plane_stride, size_t in_stride, int w, int h, const void *d_out,
                             size_t out_plane_stride, size_t out_stride);
 int check_planes_batch_device_args(const w2xc_model *m, int n, int nn2x, int n_in_planes, const void *d_in, size_t in_image_stride, size_t in_plane_stride,
                                    size_t in_stride, int w, int h, const void *d_out, size_t out_image_stride, size_t out_plane_stride, size_t out_stride,
-                                   const w2xc_opts &o);
+                                   const w2xc_opts &o, bool head_call = false);
 // byte ranges [lo, hi) tagged 1 = output, 0 = input (sorted in place): W2XC_ERR_ARG when an output overlaps another output or an input
 int check_batch_overlap(std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> &iv);
 

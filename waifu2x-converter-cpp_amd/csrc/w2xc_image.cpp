@@ -32,6 +32,8 @@ struct ImageCall {
     // check_process_args refuses anything but 0 and 1
     int tta_arg;
     bool tta;
+    // w2xc_process_image_rgb_u8_up2x_batch[_device]: the scale model is an upconv head model (and must be one), also under TTA
+    bool up2x = false;
     ImageCall(w2xc_model *noise, w2xc_model *scale, int w_, int h_, int iterations_, double shrink_, void *hip_stream, const w2xc_opts *opts, int tta_ = 0)
         : mn(noise), msc(scale), w(w_), h(h_), iterations(iterations_), shrink(shrink_), st((hipStream_t)hip_stream), o(resolve_opts(opts)), tta_arg(tta_),
           tta(tta_ == 1) {}
@@ -44,16 +46,19 @@ struct ImageCall {
 // rows = false (nin = nout = 1): the one-plane chain, run_batch on all variants of one size -- ONE batch of 8 where w == h, where the transposed group
 // continues the upright one.  rows = true: the multi-plane form, run_batch_planes on the variants of one size as images of nin planes (8 runs of them where
 // w == h, else 4 runs + 4 runs) -- one launch per layer where the model's chain has batch kernels, the single-image run_rows sequence per variant and run elsewhere.
-// Nearest-2x commutes with every T_k: a scale pass (up = 1) spreads at source resolution and gathers at 2x.
+// Nearest-2x commutes with every T_k: a scale pass (up = 1) spreads at source resolution and gathers at 2x.  So does an upconv head model's pass (head: up = 0,
+// nothing is folded into layer 1, and the model itself gives the 2x planes): its variants are the images of a head batch.
 struct TtaPass {
     w2xc_model *m;
     DevCtx *cm;
     int up, nin, nout;
     bool rows;
+    bool head = false;
 };
 int tta_pass(const TtaPass &t, int runs, PlanesIn src, int w, int h, PlanesOut dst, float *var, hipStream_t st, const w2xc_opts &o)
 {
-    const int W = w << t.up, H = h << t.up, ni = runs * t.nin, no = runs * t.nout;
+    const int sc = t.head ? 1 : t.up;   // the pass's enlargement
+    const int W = w << sc, H = h << sc, ni = runs * t.nin, no = runs * t.nout;
     const long long ps = (long long)plane_floats(w, h), PS = (long long)plane_floats(W, H);
     // the four groups of variant planes: 4 ni upright and 4 ni transposed (h x w) in, 4 no and 4 no out
     const PlanesOut in_up{var, (size_t)w, ps}, in_tr{in_up.p + 4 * (size_t)ni * ps, (size_t)h, ps};
@@ -213,14 +218,14 @@ int process_rgb_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, s
         const bool noise = c.mn && p == 1;
         w2xc_model *m = noise ? c.mn : c.msc;
         DevCtx *cm = noise ? c.ctx.cn : c.ctx.cs;
-        const bool head = m->has_head();   // (the scale model of the single-image call: the pass enlarges by itself, nothing is folded into layer 1)
+        const bool head = m->has_head();   // (the scale model of the single-image call and of the up2x batch: the pass enlarges by itself, nothing is folded into layer 1)
         const int up = noise || head ? 0 : 1, nw = cw << (noise ? 0 : 1), nh = ch << (noise ? 0 : 1);
         const long long ps2 = (long long)plane_floats(nw, nh);
         const bool from_u8 = cur == nullptr, to_u8 = p == passes && R.dst_u8;
         float *nxt = nullptr;
         if (!to_u8) { nxt = base; base += 3 * (size_t)cap * ps2; }
         if (c.tta) {   // (neither from_u8 nor to_u8: rgb_plan)
-            if (int rc = tta_pass(TtaPass{m, cm, up, 3, 3, true}, S, {cur, (size_t)cw, ps}, cw, ch, {nxt, (size_t)nw, ps2}, var, c.st, c.o)) return rc;
+            if (int rc = tta_pass(TtaPass{m, cm, up, 3, 3, true, head}, S, {cur, (size_t)cw, ps}, cw, ch, {nxt, (size_t)nw, ps2}, var, c.st, c.o)) return rc;
         } else if (S >= 2) {
             // ONE run_batch_planes for the sub-batch (one launch per layer where the chain has batch kernels): image i's three planes 3 ps on, or -- the uint8
             // forms -- the caller's images themselves: strides in bytes
@@ -306,7 +311,9 @@ int check_process_args(const ImageCall &c, bool head_ok = false)
 {
     if (c.tta_arg != 0 && c.tta_arg != 1) return fail(W2XC_ERR_ARG, "tta must be 0 or 1 (got %d)", c.tta_arg);
     if (int rc = refuse_head(c.mn, "the noise model of an image call")) return rc;
-    if (!(head_ok && !c.tta)) if (int rc = refuse_head(c.msc, "this image call")) return rc;
+    if (c.up2x) {
+        if (!c.msc || !c.msc->has_head()) return fail(W2XC_ERR_ARG, "w2xc_process_image_rgb_u8_up2x_batch*: the scale model must be an upconv head model");
+    } else if (!(head_ok && !c.tta)) if (int rc = refuse_head(c.msc, "this image call")) return rc;
     if (!c.mn && !c.msc) return fail(W2XC_ERR_ARG, "need a noise model, a scale model or both");
     if (c.iterations > 0 && !c.msc) return fail(W2XC_ERR_ARG, "scale iterations need a scale model");
     if (!c.mn && c.iterations == 0) return fail(W2XC_ERR_ARG, "nothing to do (no noise model, 0 iterations)");
@@ -843,6 +850,26 @@ int w2xc_process_image_rgb_u8_batch(w2xc_model *noise_model, w2xc_model *scale_m
 {
     return w2xc_process_image_rgb_u8_batch_tta(noise_model, scale_model, n, in, in_stride_bytes, w, h, out, out_stride_bytes, iterations, shrink_ratio, opts, 0);
 }
+
+// ---- upconv head models as scale model: the batch forms, with and without TTA (n = 1 with tta = 1: the single-image TTA form) ----
+int w2xc_process_image_rgb_u8_up2x_batch_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in,
+                                                size_t in_image_stride_bytes, size_t in_stride_bytes, int w, int h, unsigned char *d_out,
+                                                size_t out_image_stride_bytes, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                                void *hip_stream, const w2xc_opts *opts, int tta)
+try {
+    ImageCall c(noise_model, scale_model, w, h, iterations, shrink_ratio, hip_stream, opts, tta);
+    c.up2x = true;
+    return image_batch_device(true, c, n, U8In{d_in, in_image_stride_bytes, in_stride_bytes}, U8Out{d_out, out_image_stride_bytes, out_stride_bytes});
+} W2XC_CATCH_ALL
+
+int w2xc_process_image_rgb_u8_up2x_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes,
+                                         int w, int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                         const w2xc_opts *opts, int tta)
+try {
+    ImageCall c(noise_model, scale_model, w, h, iterations, shrink_ratio, nullptr, opts, tta);
+    c.up2x = true;
+    return image_batch_host(true, c, n, in, in_stride_bytes, out, out_stride_bytes);
+} W2XC_CATCH_ALL
 
 // ---- RGBA images: alpha through the scale model, colour bled under the transparent pixels ----------
 int w2xc_process_image_rgba_u8_ex_device(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *d_in, size_t in_stride_bytes, int w, int h,

@@ -115,6 +115,9 @@ hipError_t w2xc_launch_last_gather(const W2xcConvDesc &d, hipStream_t stream);
 hipError_t w2xc_launch_upconv(W2xcKernelKind kind, const W2xcConvDesc &d, hipStream_t stream);
 // conv3x3_wino4 128 -> 256 planes, planar in, NHWC out (the layer in front of the head of the published upconv_7 topology; an object of its own)
 hipError_t w2xc_launch_wino4_wide(const W2xcConvDesc &d, hipStream_t stream);
+// their batch forms (bit-identical per image): upconv4x4_head_batch -- b.in_bs floats between the images' NHWC planes, b.out_bs floats (U8: bytes) between
+// their outputs --, and conv3x3_wino4_batch_l<128, 256> through w2xc_launch_wino4_batch (w2xc_wino4_batch_layout_supported)
+hipError_t w2xc_launch_upconv_batch(W2xcKernelKind kind, const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream);
 
 // strided element copy (planar <-> NHWC repack at the Model::filter boundary)
 hipError_t w2xc_launch_repack(const float *src, long long s_rs, long long s_ps, long long s_cs,

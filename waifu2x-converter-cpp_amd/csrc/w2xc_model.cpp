@@ -213,7 +213,9 @@ const char *w2xc_last_error(void) { return g_last_error.c_str(); }
 // 0.4.1.5: w2xc_convert_planes_batch_device (n images of several planes: the batched chain of RGB models) and w2xc_batch_plan (additive; w2xc_opts stays 56 bytes)
 // 0.4.1.6: upconv head models -- w2xc_model_add_upconv_head, w2xc_model_has_head, w2xc_convert_planes_up2x_device; the JSON loader takes a last layer that is
 //          an nn.SpatialFullConvolution 4x4 / stride 2 / padding 3; every other entry point refuses such a model (additive; w2xc_opts stays 56 bytes)
-const char *w2xc_version(void) { return "w2xc_hip 0.4.1.6 (gfx950)"; }
+// 0.4.1.6.1: the batch and TTA forms for upconv head models -- w2xc_convert_planes_up2x_batch_device, w2xc_process_image_rgb_u8_up2x_batch[_device] (with tta),
+// w2xc_batch_plan with nn2x = 2; no struct change, and every existing call refuses a head model as before.
+const char *w2xc_version(void) { return "w2xc_hip 0.4.1.6.1 (gfx950)"; }
 
 int w2xc_plan_rows(const w2xc_model *m, int w, int view_y0, int view_h, int plane_h, int row_begin, int row_end, const w2xc_opts *opts, w2xc_row_plan *plan)
 try {

@@ -190,6 +190,7 @@ bool w2xc_wino4_batch_supported(int cin, int cout, bool fused_last)
 }
 bool w2xc_wino4_batch_layout_supported(int cin, int cout, bool in_nhwc, bool out_planar)
 {
+    if (cin == 128 && cout == 256) return !in_nhwc && !out_planar;   // (the layer in front of an upconv head: planar in, NHWC out)
     if (cout != 64 && cout != 128) return false;
     if (in_nhwc) return cin == 32;
     return out_planar ? w2xc_wino4_batch_supported(cin, cout, false) : (cin == 64 || cin == 128);

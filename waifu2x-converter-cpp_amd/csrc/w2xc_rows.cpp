@@ -65,7 +65,7 @@ hipError_t launch_kind(W2xcKernelKind kind, int midv, const W2xcConvDesc &d, con
     case W2XC_K_LAST:
     case W2XC_K_LAST_U8: return bd ? w2xc_launch_conv_batch(kind, d, *bd, st) : w2xc_launch_conv(kind, d, st);
     case W2XC_K_UPCONV:
-    case W2XC_K_UPCONV_U8: return bd ? hipErrorInvalidValue : w2xc_launch_upconv(kind, d, st);
+    case W2XC_K_UPCONV_U8: return bd ? w2xc_launch_upconv_batch(kind, d, *bd, st) : w2xc_launch_upconv(kind, d, st);
     default: break;
     }
     if (midv == MID_WINO4) return bd ? w2xc_launch_wino4_batch(d, *bd, st) : w2xc_launch_wino4(d, st);
@@ -428,7 +428,7 @@ int check_planes_args(const w2xc_model *m, int up, int n_in_planes, const void *
     if (!m || !d_in || !d_out) return fail(W2XC_ERR_ARG, "null argument");
     // up = 2: w2xc_convert_planes_up2x_device -- a head model, and only there; the output planes are 2w x 2h as with up = 1
     if (up == 2 ? !m->has_head() : m->has_head())
-        return up == 2 ? fail(W2XC_ERR_ARG, "w2xc_convert_planes_up2x_device: the model has no upconv head") : refuse_head(m, "w2xc_convert_planes[_nn2x][_batch]_device");
+        return up == 2 ? fail(W2XC_ERR_ARG, "w2xc_convert_planes_up2x[_batch]_device: the model has no upconv head") : refuse_head(m, "w2xc_convert_planes[_nn2x][_batch]_device");
     up = up ? 1 : 0;
     if (int rc = check_plane_size(w, h, up != 0)) return rc;
     const int W = w << up, H = h << up;
@@ -495,11 +495,12 @@ int run_batch(w2xc_model *m, DevCtx *c, int nimg, int up, PlanesIn in, int w, in
     return run_batch_planes(m, c, nimg, up, io, w, h, st, o_in, max_sub);
 }
 
-// the argument checks of the batch entry points (no device is touched): n >= 1, sizes, strides, planes that do not overlap
-int check_batch_args(const w2xc_model *m, int nimg, int nn2x, int w, int h, size_t in_stride, size_t out_stride)
+// the argument checks of the batch entry points (no device is touched): n >= 1, sizes, strides, planes that do not overlap.  head_call: the call is
+// w2xc_convert_planes_up2x_batch_device, which runs a head model (and nothing else: check_planes_args); its nn2x is 1, the size of what it writes
+int check_batch_args(const w2xc_model *m, int nimg, int nn2x, int w, int h, size_t in_stride, size_t out_stride, bool head_call)
 {
     if (!m) return fail(W2XC_ERR_ARG, "null model");
-    if (int rc = refuse_head(m, "the batch calls")) return rc;
+    if (!head_call) if (int rc = refuse_head(m, "the batch calls")) return rc;
     if (nimg < 1) return fail(W2XC_ERR_ARG, "batch of %d planes", nimg);
     if (nn2x != 0 && nn2x != 1) return fail(W2XC_ERR_ARG, "nn2x must be 0 or 1");
     if (int rc = check_plane_size(w, h, true)) return rc;
@@ -524,10 +525,12 @@ int check_batch_device_args(const w2xc_model *m, int n, int nn2x, const void *d_
 // everything w2xc_convert_planes_batch_device refuses: check_batch_args + check_planes_args, the plane counts, and images that overlap
 int check_planes_batch_device_args(const w2xc_model *m, int n, int nn2x, int n_in_planes, const void *d_in, size_t in_image_stride_bytes, size_t in_plane_stride_bytes,
                                    size_t in_stride_bytes, int w, int h, const void *d_out, size_t out_image_stride_bytes, size_t out_plane_stride_bytes,
-                                   size_t out_stride_bytes, const w2xc_opts &o)
+                                   size_t out_stride_bytes, const w2xc_opts &o, bool head_call)
 {
-    if (int rc = check_batch_args(m, n, nn2x, w, h, in_stride_bytes, out_stride_bytes)) return rc;
-    if (int rc = check_planes_args(m, nn2x, n_in_planes, d_in, in_plane_stride_bytes, in_stride_bytes, w, h, d_out, out_plane_stride_bytes, out_stride_bytes, o)) return rc;
+    if (head_call) nn2x = 1;   // (the head's own 2x: the output planes are 2w x 2h as with a nearest-2x)
+    if (int rc = check_batch_args(m, n, nn2x, w, h, in_stride_bytes, out_stride_bytes, head_call)) return rc;
+    if (int rc = check_planes_args(m, head_call ? 2 : nn2x, n_in_planes, d_in, in_plane_stride_bytes, in_stride_bytes, w, h, d_out, out_plane_stride_bytes, out_stride_bytes, o)) return rc;
+    if (head_call && o.precision != W2XC_PRECISION_FP32) return fail(W2XC_ERR_UNSUPPORTED, "16-bit precision modes: not available for a model with an upconv head (W2XC_PRECISION_FP32 only)");
     if (m->layers.empty()) return fail(W2XC_ERR_ARG, "model has no layers");
     if (m->layers[0].nin != n_in_planes)
         return fail(W2XC_ERR_PLANES, "Error : Model-filter : \nnumber of input planes mismatch.\n%d,%d", n_in_planes, m->layers[0].nin);
@@ -680,18 +683,42 @@ try {
     return run_batch_planes(m, lc.cs, n, nn2x, io, w, h, (hipStream_t)hip_stream, o);
 } W2XC_CATCH_ALL
 
-// host arithmetic only: the plan of one image of the batch, as run_batch_planes makes it
+// a batch of head-model conversions: image i is w2xc_convert_planes_up2x_device on image i, bit for bit; one launch per layer where the chain has batch kernels
+int w2xc_convert_planes_up2x_batch_device(w2xc_model *m, int n, int n_in_planes, const float *d_in, size_t in_image_stride_bytes, size_t in_plane_stride_bytes,
+                                          size_t in_stride_bytes, int w, int h, float *d_out, size_t out_image_stride_bytes, size_t out_plane_stride_bytes,
+                                          size_t out_stride_bytes, void *hip_stream, const w2xc_opts *opts)
+try {
+    const w2xc_opts o = resolve_opts(opts);
+    int rc = check_planes_batch_device_args(m, n, 1, n_in_planes, d_in, in_image_stride_bytes, in_plane_stride_bytes, in_stride_bytes, w, h, d_out,
+                                            out_image_stride_bytes, out_plane_stride_bytes, out_stride_bytes, o, true);
+    if (rc) return rc;
+    RowPlan P;   // (the plan's own refusals -- a head shape without a kernel among them -- before a device is touched)
+    if ((rc = plan_rows(m, o, w, h, 0, 0, h, h, n_in_planes, true, &P))) return rc;
+    // (all planes of the head, also where it gives one: out.ps != 0, as w2xc_convert_planes_up2x_device)
+    const BatchIO io = {{d_in, in_stride_bytes / 4, (long long)(in_plane_stride_bytes / 4)}, (long long)(in_image_stride_bytes / 4), n_in_planes,
+                        {d_out, out_stride_bytes / 4, (long long)(out_plane_stride_bytes / 4)}, (long long)(out_image_stride_bytes / 4), 0};
+    LockedCtx lc;
+    if ((rc = lc.open(nullptr, m, o.device))) return rc;
+    return run_batch_planes(m, lc.cs, n, 0, io, w, h, (hipStream_t)hip_stream, o);
+} W2XC_CATCH_ALL
+
+// host arithmetic only: the plan of one image of the batch, as run_batch_planes makes it.  nn2x = 2: the plan of w2xc_convert_planes_up2x_batch_device (a head
+// model on its source size)
 int w2xc_batch_plan(const w2xc_model *m, int n_in_planes, int w, int h, int nn2x, const w2xc_opts *opts, int *batched, int *sub_batch)
 try {
     if (!m || !batched || !sub_batch) return fail(W2XC_ERR_ARG, "null argument");
-    if (nn2x != 0 && nn2x != 1) return fail(W2XC_ERR_ARG, "nn2x must be 0 or 1");
+    if (nn2x < 0 || nn2x > 2) return fail(W2XC_ERR_ARG, "nn2x must be 0, 1 or 2 (the plan of w2xc_convert_planes_up2x_batch_device)");
     if (int rc = check_plane_size(w, h, true)) return rc;
     if (m->layers.empty()) return fail(W2XC_ERR_ARG, "model has no layers");
-    if (m->has_head()) { *batched = 0; *sub_batch = 1; return W2XC_OK; }   // (no batch call runs an upconv head model)
+    const bool head_plan = nn2x == 2;
+    if (head_plan) {
+        if (!m->has_head()) return fail(W2XC_ERR_ARG, "w2xc_batch_plan with nn2x = 2: the model has no upconv head");
+        nn2x = 0;   // (the head enlarges: the layers run on the source size)
+    } else if (m->has_head()) { *batched = 0; *sub_batch = 1; return W2XC_OK; }   // (the batch calls these values of nn2x plan refuse an upconv head model)
     const w2xc_opts o = resolve_opts(opts);
     const int W = w << nn2x, H = h << nn2x;
     RowPlan P;
-    if (int rc = plan_rows(m, o, W, H, 0, 0, H, H, n_in_planes, !one_plane_model(m, n_in_planes), &P)) return rc;
+    if (int rc = plan_rows(m, o, W, H, 0, 0, H, H, n_in_planes, head_plan || !one_plane_model(m, n_in_planes), &P)) return rc;   // (the head call writes all planes of the head)
     *batched = batch_eligible(m, P) ? 1 : 0;
     *sub_batch = 1;
     if (*batched) {

@@ -436,6 +436,10 @@ W2xcKernelKind layer_desc(const w2xc_model *m, const RowPlan &P, int k, int y0, 
 // The second chain is that of a multi-plane (RGB) model (w2xc_convert_planes_batch_device, the RGB image calls, their TTA passes), under the same conditions:
 // conv3x3_first (three planes in; NHWC or planar out), then W2XC_K_MFMA layers run by conv3x3_wino4 or conv3x3_wino in a layout combination that has a batch
 // form (w2xc_wino4_batch_supported / w2xc_wino4_batch_layout_supported / w2xc_wino_batch_supported), then conv3x3_last storing all three planes in place.
+//
+// A three-plane upconv head model (w2xc_convert_planes_up2x_batch_device, the head-model image batch and its TTA pass) has the same chain with the head in
+// conv3x3_last's place: layer n - 1 is W2XC_K_UPCONV (upconv4x4_head_batch) on the NHWC planes of layer n - 2, which may be the 128 -> 256 layer
+// (conv3x3_wino4_batch_l<128, 256>: the predicate says so).  A one-plane head model has no batched chain: the single-image launch sequence per image.
 namespace {
 bool batch_chain_planes(const w2xc_model *m, const RowPlan &P)
 {
@@ -443,8 +447,10 @@ bool batch_chain_planes(const w2xc_model *m, const RowPlan &P)
     const int n = P.n;
     if (n < 2 || !P.all_out || !P.last_direct) return false;
     if (m->layers[0].nin != 3 || m->layers[n - 1].nout != 3) return false;
-    if (layer_kind(m, 0, o) != W2XC_K_FIRST || layer_kind(m, n - 1, o) != W2XC_K_LAST || out_terms_of(m, 0, o) != 0) return false;
-    if (planar_between(m, n - 2, o)) return false;   // (conv3x3_last reads NHWC pixels)
+    const bool head = m->has_head();
+    if (layer_kind(m, 0, o) != W2XC_K_FIRST || layer_kind(m, n - 1, o) != (head ? W2XC_K_UPCONV : W2XC_K_LAST) || out_terms_of(m, 0, o) != 0) return false;
+    if (head && !w2xc_upconv_supported(m->layers[n - 1].nin, m->layers[n - 1].nout)) return false;
+    if (planar_between(m, n - 2, o)) return false;   // (conv3x3_last and upconv4x4_head read NHWC pixels)
     for (int l = 1; l <= n - 2; l++) {
         const HostLayer &hl = m->layers[l];
         if (layer_kind(m, l, o) != W2XC_K_MFMA || out_terms_of(m, l, o) != 0) return false;

@@ -269,7 +269,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_wino4_batch_l(W2xcConvDesc d, 
 // host side: launch (shape predicates, PROG's job arithmetic and the packers: w2xc_pack.cpp).
 // Eight objects (make -j): W2XC_WINO4_PART = 0 the planar-out instantiations + dispatcher, 1 the NHWC-out ones, 2 the fused-last ones,
 // 3 the batch forms with planar out + the batch dispatcher, 4 the fused-last batch forms, 5 the batch forms with 32 NHWC planes in, 6 those with planar
-// planes in and NHWC out, 7 the 128 -> 256 layer of upconv models (NHWC out).
+// planes in and NHWC out, 7 the 128 -> 256 layer of upconv models (NHWC out), 8 its batch form.
 // ------------------------------------------------------------------------------------------------
 #ifndef W2XC_WINO4_PART
 #define W2XC_WINO4_PART -1   // one translation unit with everything (tools/ubench)
@@ -467,6 +467,17 @@ hipError_t w2xc_launch_wino4_batch_nhwc_out(const W2xcConvDesc &d, W2xcBatchDesc
 }
 #endif
 
+// 128 -> 256 planes, planar in, NHWC out: the batch form of the layer in front of an upconv head (w2xc_launch_wino4_wide): one more instantiation of the
+// batch body, 160 KiB of LDS like the one-image launch
+hipError_t w2xc_launch_wino4_batch_wide(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream);
+#if W2XC_WINO4_PART == 8 || W2XC_WINO4_PART == -1
+hipError_t w2xc_launch_wino4_batch_wide(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream)
+{
+    if (d.cin != 128 || d.cout != 256 || d.in_ps != 1 || d.out_ps != 256 || d.out_cs != 1 || d.out_terms == 9) return hipErrorInvalidValue;
+    return launch_wino4_batch_l<128, 256, false, false>(d, b, stream);
+}
+#endif
+
 hipError_t w2xc_launch_wino4_batch_fused(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream);
 #if W2XC_WINO4_PART == 4 || W2XC_WINO4_PART == -1
 hipError_t w2xc_launch_wino4_batch_fused(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream)
@@ -501,6 +512,7 @@ hipError_t w2xc_launch_wino4_batch(const W2xcConvDesc &d, W2xcBatchDesc b, hipSt
         if (out_nhwc) {
             if (d.out_ps != d.cout || d.out_cs != 1 || (d.out_rs & 3) != 0 || (((size_t)d.out) & 15) != 0) return hipErrorInvalidValue;
         } else if ((d.out_rs & 3) != 0 || (d.out_cs & 3) != 0 || (((size_t)d.out) & 15) != 0 || d.out_rs < ((d.out_w + 3) & ~3)) return hipErrorInvalidValue;
+        if (!in_nhwc && d.cout == 256) return w2xc_launch_wino4_batch_wide(d, b, stream);   // (part 8)
         return in_nhwc ? w2xc_launch_wino4_batch_nhwc_in(d, b, stream) : w2xc_launch_wino4_batch_nhwc_out(d, b, stream);
     }
     if (d.in_ps != 1 || (d.in_cs & 3) != 0 || d.off_x < 0 || (d.off_x & 3) != 0 || d.in_rs < ((d.in_w + 3) & ~3)) return hipErrorInvalidValue;
