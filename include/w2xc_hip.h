@@ -144,7 +144,7 @@ int w2xc_model_load_json(const char *path, w2xc_model **out);
 int w2xc_model_from_arrays(int n_layers, const int *nin, const int *nout,
                            const float *const *weight, const double *const *bias, w2xc_model **out);
 
-/* ---- upconv head models (revision 0.4.1.6; their batch and TTA forms: 0.4.1.6.1) ----
+/* ---- upconv head models (revision 0.4.1.6; their batch and TTA forms: 0.4.1.6.1; their RGBA form: 0.4.1.6.2) ----
  * The upconv_7 family of later upstream versions: the model does the 2x enlargement itself, in its last layer, so nothing is enlarged in front of it.  v1
  * of the reference has no such path; the arithmetic is defined here.
  *   model:  a HEAD MODEL is n - 1 >= 1 ordinary 3x3 layers followed by one head layer: C planes in, nout in {1, 3} planes out, a 4x4 kernel, stride 2,
@@ -172,9 +172,23 @@ int w2xc_model_from_arrays(int n_layers, const int *nin, const int *nout,
  *           without a head are untouched.
  *   calls:  w2xc_convert_planes_up2x_device and w2xc_process_image_rgb_u8_ex[_device] (a head model as scale_model) run a head model.  EVERY other entry
  *           point given one returns W2XC_ERR_UNSUPPORTED from its argument checks, before a device is touched: the Y route, w2xc_convert_plane*,
- *           w2xc_convert_planes[_nn2x]_device, the batch, TTA and RGBA calls, w2xc_layer_filter*; w2xc_batch_plan answers "not batched".
+ *           w2xc_convert_planes[_nn2x]_device, the batch, TTA and RGBA calls (w2xc_process_image_rgba_u8_ex* / _batch*), w2xc_layer_filter*;
+ *           w2xc_batch_plan answers "not batched".
  *   batch:  (0.4.1.6.1) the batch and TTA forms of a head model are entry points of their own, below: w2xc_convert_planes_up2x_batch_device and
  *           w2xc_process_image_rgb_u8_up2x_batch[_device]; w2xc_batch_plan plans them with nn2x = 2.  The calls above go on refusing a head model.
+ *           (0.4.1.6.2) So is the RGBA form, single image and batch in one: w2xc_process_image_rgba_u8_up2x_batch[_device], at the RGBA calls below.
+ *   RGBA:   (0.4.1.6.2) image i of w2xc_process_image_rgba_u8_up2x_batch[_device] has the bytes of this composition of public calls:
+ *             1. bled = w2xc_bleed_rgba_u8_device(rgba_i, P); for bleed_passes < 0, P = the sum of w2xc_model_layers of the models given (the head counts
+ *                as a layer); P is clipped to max(w, h) - 1.
+ *             2. colour = w2xc_process_image_rgb_u8_ex_device(noise_model, scale_model, bled, iterations, shrink_ratio, opts).
+ *             3. alpha, iterations >= 1: channel 1 of w2xc_process_image_rgb_u8_ex_device(NULL, scale_model, (A, A, A), iterations, shrink_ratio, opts);
+ *                iterations == 0: as in w2xc_process_image_rgba_u8_ex, the bytes as they are or the INTER_LINEAR shrink.  Alpha never sees the noise model.
+ *           Where the first and the last layer have their uint8 kernels (fp32, the fast kernels, w2xc_opts.fusion other than W2XC_FUSION_OFF, no shrink)
+ *           the colour pass's head writes bytes 0 .. 2 of the output pixels, layer 1 of the alpha pass reads the alpha bytes of the input pixels, and the
+ *           alpha pass ends in the ALPHA HEAD: the head's channel 1 alone, on a weight image packed from Wt[:, 1] and bias[1], written to byte 3.  A
+ *           column's MFMA chain does not depend on its neighbours and the tap sum is per plane, so the byte has the bits of channel 1 of the full head.
+ *           Neither the grey image (A, A, A), nor a 3-channel result of either pass, nor a merge exists then.  Everywhere else the passes run around
+ *           float planes and the colour stages, with the same bytes.
  * w2xc_model_add_upconv_head appends the head to a model from w2xc_model_from_arrays: weight is [nin][nout][4][4] with nin = the last 3x3 layer's output
  * planes, bias nout doubles or NULL (zeros).  It must come before the model's first use on a device and only once: otherwise W2XC_ERR_ARG.
  * w2xc_model_layers / _nin / _nout count the head as the last layer; w2xc_model_get_layer gives its weight as [nin][nout][4][4]. */
@@ -301,7 +315,8 @@ int w2xc_convert_planes_up2x_batch_device(w2xc_model *m, int n, int n_in_planes,
  *   tta = 1: (n >= 1; n = 1 is the single-image TTA form) every pass is its TTA pass in the arithmetic of "test-time augmentation": spread at source
  *            resolution, the head model on the 8 variants -- the images of ONE head batch where w == h, else 4 + 4 --, gather at 2x.  Image i has the bytes
  *            of w2xc_u8_to_rgb_device, w2xc_tta_spread_device, w2xc_convert_planes_up2x_device on each variant, w2xc_tta_gather_device, w2xc_rgb_to_u8_device.
- * Not built: RGBA forms, the Y route and 16-bit precisions for head models (W2XC_ERR_UNSUPPORTED / W2XC_ERR_PLANES as for the single-image call). */
+ * Not built: the Y route and 16-bit precisions for head models (W2XC_ERR_UNSUPPORTED / W2XC_ERR_PLANES as for the single-image call), multi-device
+ * striping of the device forms.  (The RGBA form, 0.4.1.6.2: w2xc_process_image_rgba_u8_up2x_batch[_device].) */
 int w2xc_process_image_rgb_u8_up2x_batch_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in,
                                                 size_t in_image_stride_bytes, size_t in_stride_bytes, int w, int h, unsigned char *d_out,
                                                 size_t out_image_stride_bytes, size_t out_stride_bytes, int iterations, double shrink_ratio,
@@ -509,6 +524,25 @@ int w2xc_process_image_rgba_u8_batch_device(w2xc_model *noise_model, w2xc_model 
 int w2xc_process_image_rgba_u8_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes, int w, int h,
                                      unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio, int bleed_passes,
                                      const w2xc_opts *opts);
+/* (0.4.1.6.2) n >= 1 RGBA images of one size with an upconv head model as scale_model: the result is defined under "upconv head models", RGBA.  n = 1 is the
+ * single-image form, bands included (w2xc_opts.band_rows; a banded run gives the bytes of the unbanded one).  Arguments as
+ * w2xc_process_image_rgba_u8_batch[_device]; there is no tta argument (no RGBA call has one).
+ * A sub-batch of S >= 2 images runs the colour pass and the alpha pass as one launch per layer each where the chain has batch kernels -- the uint8 forms
+ * above included: upconv4x4_head_batch on 4-byte pixels, the alpha head's batch form, conv3x3_first_batch on the alpha bytes --, S = 1 the single-image
+ * launches.  The host form overlaps sub-batches like w2xc_process_image_rgba_u8_batch.
+ * Refused before a device is touched: what w2xc_process_image_rgb_u8_up2x_batch* refuses -- a scale model without a head (also with iterations == 0)
+ * W2XC_ERR_ARG, a head model as noise model and the 16-bit precisions W2XC_ERR_UNSUPPORTED, a model that is not three planes in and three out
+ * W2XC_ERR_PLANES -- and what the RGBA batch calls refuse, with their codes: row strides below 4 x width, n < 1, null pointers, outputs that overlap each
+ * other or an input, more than 65534 effective bleed passes, an extent above 2^28.
+ * Not built: TTA, the Y route, split precisions, multi-device striping of the device form, and the colour and alpha images of a sub-batch as ONE batch of
+ * 2 S through the 3x3 layers (they share weights; layer 1 and the head differ). */
+int w2xc_process_image_rgba_u8_up2x_batch_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in, size_t in_image_stride_bytes,
+                                                 size_t in_stride_bytes, int w, int h, unsigned char *d_out, size_t out_image_stride_bytes,
+                                                 size_t out_stride_bytes, int iterations, double shrink_ratio, int bleed_passes, void *hip_stream,
+                                                 const w2xc_opts *opts);
+int w2xc_process_image_rgba_u8_up2x_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes, int w,
+                                          int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio, int bleed_passes,
+                                          const w2xc_opts *opts);
 /* Test-time augmentation (TTA): every CNN pass runs on the 8 flips and transposes of its input, each result is transformed back and the 8 are averaged --
  * the quality option later upstream versions of the converter have as --tta (v1 of the reference has none); 8x the CNN work.  The arithmetic is defined here:
  *   T_k, k = 0..7, on a plane x of h rows x w columns applies, in this order: the horizontal flip (x[:, ::-1]) if k & 1, the vertical flip (x[::-1, :]) if

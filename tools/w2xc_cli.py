@@ -17,8 +17,8 @@ Extension: -t/--tta 1 = test-time augmentation, the --tta of later upstream vers
 (w2xc_process_image_[rgb_]u8[_batch]_tta; 8x the CNN work), on both routes and for grouped inputs.  The RGBA call has no TTA form: with an input that would
 take it, --tta 1 exits with a message before anything is converted.
 Extension: upconv scale models (upconv_7: the model enlarges by itself).  The RGB route; a size group of two or more opaque inputs, and every input under
---tta 1, is ONE w2xc_process_image_rgb_u8_up2x_batch call (head_routes), an input alone its single-image call.  Inputs with transparency are refused: the
-RGBA form of such a model is not built."""
+--tta 1, is ONE w2xc_process_image_rgb_u8_up2x_batch call (head_routes), an input alone its single-image call.  Inputs with transparency go to
+w2xc_process_image_rgba_u8_up2x_batch, one call per size group (head_alpha_routes; a file alone is a batch of one); with --tta 1 they stay check_tta's refusal."""
 import argparse
 import math
 import os
@@ -125,6 +125,13 @@ def head_routes(tta, alpha_files, groups):
     return [("up2x_batch" if tta or len(g) > 1 else "single", list(g)) for g in groups if g]
 
 
+def head_alpha_routes(alpha_groups):
+    """How the inputs with transparency of an upconv scale model run: [("rgba_up2x_batch", [files]), ...], ONE w2xc_process_image_rgba_u8_up2x_batch call per
+    size group (`alpha_groups`: lists of names, one per image size) in the order given -- a file alone is a batch of one.  Pure: no file is opened.
+    (--tta 1 never gets here: check_tta.)"""
+    return [("rgba_up2x_batch", list(g)) for g in alpha_groups if g]
+
+
 def check_inputs(ap, args):
     """-o names ONE output file: with several inputs it is refused (argparse's error exit, status 2)"""
     if len(args.input_file) > 1 and args.output_file != "(auto)":
@@ -183,7 +190,8 @@ def main(argv=None):
     opaque = [(f, im) for f, im in zip(args.input_file, images) if im.shape[2] == 3]
     check_tta(args.tta, [f for f, im in zip(args.input_file, images) if im.shape[2] == 4])
     head = bool(scale is not None and iterations and scale.has_head)   # (an upconv model: the RGB route's single-image call, passed through as it is)
-    routes = head_routes(args.tta, [f for f, im in zip(args.input_file, images) if im.shape[2] == 4],
+    # (the transparent inputs of a head model have a call of their own, head_alpha_routes below: head_routes sees the opaque ones alone)
+    routes = head_routes(args.tta, [],
                          [files for _, files, _ in group_inputs([(f, (im.shape[1], im.shape[0])) for f, im in opaque], args.mode, args.noise_level,
                                                                 args.scale_ratio)]) if head else []
     tta = dict(tta=True) if args.tta else {}
@@ -196,7 +204,11 @@ def main(argv=None):
         prec = {"fp32": w2xc.PRECISION_FP32, "bf16": w2xc.PRECISION_BF16, "bf16x2": w2xc.PRECISION_BF16X2, "bf16x3": w2xc.PRECISION_BF16X3, "fp16x2": w2xc.PRECISION_FP16X2}[args.precision]
         opts = w2xc.make_opts(precision=prec)      # always explicit: an explicit --precision beats the W2XC_PRECISION env default
         alpha = {f: im for f, im in zip(args.input_file, images) if im.shape[2] == 4}
-        singles, batches = group_alpha([(f, (im.shape[1], im.shape[0])) for f, im in alpha.items()], args.mode, args.noise_level, args.scale_ratio)
+        alpha_sized = [(f, (im.shape[1], im.shape[0])) for f, im in alpha.items()]
+        singles, batches = ([], []) if head else group_alpha(alpha_sized, args.mode, args.noise_level, args.scale_ratio)
+        if head:   # (an upconv scale model: the RGBA head call per size group)
+            for _, files in head_alpha_routes([files for _, files, _ in group_inputs(alpha_sized, args.mode, args.noise_level, args.scale_ratio)]):
+                outs.update(zip(files, w2xc.process_image_rgba_u8_up2x_batch([alpha[f] for f in files], noise, scale, iterations, opts, shrink)))
         for f in singles:
             outs[f] = w2xc.process_image_rgba_u8(alpha[f], noise, scale if iterations else None, iterations, opts, shrink)
         for files in batches:                      # one batch call per image size

@@ -122,6 +122,8 @@ def _load():
         "w2xc_convert_planes_up2x_batch_device": (ci, [vp, ci, ci, fp, cs, cs, cs, ci, ci, fp, cs, cs, cs, vp, C.POINTER(Opts)]),
         "w2xc_process_image_rgb_u8_up2x_batch_device": (ci, [vp, vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, ci, C.c_double, vp, C.POINTER(Opts), ci]),
         "w2xc_process_image_rgb_u8_up2x_batch": (ci, [vp, vp, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, ci, C.c_double, C.POINTER(Opts), ci]),
+        "w2xc_process_image_rgba_u8_up2x_batch_device": (ci, [vp, vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, ci, C.c_double, ci, vp, C.POINTER(Opts)]),
+        "w2xc_process_image_rgba_u8_up2x_batch": (ci, [vp, vp, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, ci, C.c_double, ci, C.POINTER(Opts)]),
         "w2xc_u8_to_rgb_device": (ci, [fp, cs, ci, ci, fp, fp, fp, vp]),
         "w2xc_rgb_to_u8_device": (ci, [fp, fp, fp, ci, ci, fp, cs, vp]),
         "w2xc_process_image_u8_device": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, vp, C.POINTER(Opts)]),
@@ -920,6 +922,22 @@ def process_image_rgba_u8_batch_device(n, d_in, in_image_stride_bytes, in_stride
     _check(_lib.w2xc_process_image_rgba_u8_batch_device(*_handles(noise, scale), n, C.c_void_p(d_in), in_image_stride_bytes, in_stride_bytes, w, h,
                                                         C.c_void_p(d_out), out_image_stride_bytes, out_stride_bytes, iterations, float(shrink_ratio),
                                                         int(bleed_passes), C.c_void_p(stream), C.byref(opts) if opts is not None else None))
+
+
+def process_image_rgba_u8_up2x_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, bleed_passes=-1, out=None):
+    """n >= 1 RGBA images of one size with an upconv head model as `scale` (w2xc_process_image_rgba_u8_up2x_batch); arguments and checks as
+    process_image_rgba_u8_batch.  The colour bytes of image i are those of process_image_rgb_u8 on the bled image, alpha is channel 1 of the scale-only
+    call on (A, A, A); one image is the single-image form."""
+    return _image_batch(_lib.w2xc_process_image_rgba_u8_up2x_batch, "process_image_rgba_u8_up2x_batch", imgs, noise, scale, iterations, opts, shrink_ratio,
+                        out, channels=4, extra=(int(bleed_passes),))
+
+
+def process_image_rgba_u8_up2x_batch_device(n, d_in, in_image_stride_bytes, in_stride_bytes, w, h, d_out, out_image_stride_bytes, out_stride_bytes,
+                                            noise=None, scale=None, iterations=0, shrink_ratio=0.0, bleed_passes=-1, stream=0, opts=None):
+    """Device-pointer form (w2xc_process_image_rgba_u8_up2x_batch_device); arguments as process_image_rgba_u8_batch_device."""
+    _check(_lib.w2xc_process_image_rgba_u8_up2x_batch_device(*_handles(noise, scale), n, C.c_void_p(d_in), in_image_stride_bytes, in_stride_bytes, w, h,
+                                                             C.c_void_p(d_out), out_image_stride_bytes, out_stride_bytes, iterations, float(shrink_ratio),
+                                                             int(bleed_passes), C.c_void_p(stream), C.byref(opts) if opts is not None else None))
 
 
 def bleed_rgba_u8_device(d_in, in_stride_bytes, w, h, passes, d_out_rgb, out_stride_bytes, stream=0):

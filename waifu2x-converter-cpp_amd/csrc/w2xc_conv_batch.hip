@@ -57,7 +57,7 @@ template <bool U8>
 static hipError_t launch_first_batch(const W2xcConvDesc &d, W2xcBatchDesc b, hipStream_t stream)
 {
     if (d.cin != 3) return hipErrorInvalidValue;
-    if (U8 && (d.in_ps != 3 || d.in_cs != 1)) return hipErrorInvalidValue;
+    if (U8 && !((d.in_ps == 3 && d.in_cs == 1) || (d.in_ps == 4 && d.in_cs == 0))) return hipErrorInvalidValue;   // (4, 0: the alpha byte of RGBA pixels, as w2xc_launch_conv)
     if (d.out_ps == 1) {   // planar out: whole pixel quads, every image's planes as aligned as image 0's
         if (((d.out_rs | d.out_cs | b.out_bs) & 3) != 0 || d.out_rs < ((d.out_w + 3) & ~3) || (((size_t)d.out) & 15) != 0) return hipErrorInvalidValue;
         switch (d.cout) {

@@ -93,6 +93,7 @@ struct DevLayer {
     float *w_last_fused[4] = {nullptr, nullptr, nullptr, nullptr};   // w2xc_split_pack_last images: [0] 2 bf16 terms, [1] 2 fp16 terms, [2] 3 bf16 terms, [3] 1 bf16 term
     float last_fused_scale[4] = {1, 1, 1, 1};
     float *w_last_wino4 = nullptr;    // w2xc_wino4_pack_last image (fp32 path: last layer inside conv3x3_wino4's epilogue)
+    float *w_alpha = nullptr;         // w2xc_upconv_pack_alpha image (a three-plane upconv head: channel 1 alone, the RGBA call's alpha head), uploaded with the model
     float *bias = nullptr;
 };
 
@@ -187,7 +188,7 @@ struct DevCtx {
         hipGetDevice(&prev);
         hipSetDevice(device);
         for (auto &l : layers) {   // the weights: uploaded once (upload, w2xc_model.cpp), not scratch
-            for (float *p : {l.w_fast, l.w_direct, l.w_wino, l.w_wino4, l.w_first2, l.w_last_wino4, l.bias}) if (p) hipFree(p);
+            for (float *p : {l.w_fast, l.w_direct, l.w_wino, l.w_wino4, l.w_first2, l.w_last_wino4, l.w_alpha, l.bias}) if (p) hipFree(p);
             for (float *p : l.w_split) if (p) hipFree(p);
             for (float *p : l.w_last_fused) if (p) hipFree(p);
         }
@@ -290,8 +291,8 @@ inline bool ranges_overlap(const void *in, size_t in_extent, const void *out, si
 }
 
 // what every entry point but w2xc_convert_planes_up2x_device and w2xc_process_image_rgb_u8_ex[_device] -- and, since 0.4.1.6.1, their batch / TTA forms
-// w2xc_convert_planes_up2x_batch_device and w2xc_process_image_rgb_u8_up2x_batch[_device] -- answers for an upconv head model, in its argument checks (no
-// device is touched; the message is pinned by tests/test_upconv_api.py)
+// w2xc_convert_planes_up2x_batch_device and w2xc_process_image_rgb_u8_up2x_batch[_device], since 0.4.1.6.2 w2xc_process_image_rgba_u8_up2x_batch[_device] --
+// answers for an upconv head model, in its argument checks (no device is touched; the message is pinned by tests/test_upconv_api.py)
 inline int refuse_head(const w2xc_model *m, const char *call)
 {
     if (!m || !m->has_head()) return W2XC_OK;
@@ -397,7 +398,14 @@ typedef Planes<float> PlanesOut;
 
 // u8 (the RGB image pipeline; no hooks): ROWS_U8_SRC = `in` is an interleaved uint8 image of three channels (layer 1 runs as W2XC_K_FIRST_U8); ROWS_U8_DST =
 // the same for `out` and the last layer (W2XC_K_LAST_U8).  The caller asks only where u8_source_layer / u8_sink_layer say yes.
-enum { ROWS_U8_SRC = 1, ROWS_U8_DST = 2 };
+// The RGBA call for upconv head models (w2xc_process_image_rgba_u8_up2x_batch*) reads and writes the caller's 4-byte pixels with three more, each beside the
+// flag of its side:
+//   ROWS_U8_SRC_A    `in` points at the ALPHA byte of an RGBA image and in.ps = 0: pixels 4 bytes apart, all three input planes that byte -- the grey image
+//                    (A, A, A) without its copy
+//   ROWS_U8_DST_PX4  the pixels of `out` are 4 bytes apart (a head model's last layer only): the three channels go to bytes 0 .. 2 of RGBA pixels
+//   ROWS_U8_DST_A    channel 1 only (a three-plane head only): the alpha head (W2XC_K_UPCONV_A_U8) writes ONE byte per pixel, at out.p -- the caller points it
+//                    at byte 3 of the first pixel
+enum { ROWS_U8_SRC = 1, ROWS_U8_DST = 2, ROWS_U8_SRC_A = 4, ROWS_U8_DST_PX4 = 8, ROWS_U8_DST_A = 16 };
 // One run_rows call: output rows [ra, rb) of convertWithModels on a plane of plane_h rows, w wide.
 struct RowsCall {
     // the source view: n_in planar input planes in.ps floats apart, of which `in` holds rows [view_y0, view_y0 + view_h) -- every row in [ra - n, rb + n)
@@ -412,7 +420,7 @@ struct RowsCall {
     PlanesOut out;
     // up = 1 folds a nearest-neighbour 2x (main.cpp:132-140) into layer 1: view_h, view_y0, w, plane_h, ra, rb are then in UPSCALED coordinates while `in`
     // holds the (view_h / 2) x (w / 2) source rows starting at source row view_y0 / 2.
-    int up, u8;              // (u8: ROWS_U8_SRC | ROWS_U8_DST)
+    int up, u8;              // (u8: ROWS_U8_SRC | ROWS_U8_DST, and the forms of the RGBA head call beside them)
     const BandHooks *hk;     // the host pipeline's hooks into the band loop
     // the common case: the whole plane of a W x H result (view = plane, every row), no hooks
     static RowsCall whole(PlanesIn in, int n_in, int W, int H, PlanesOut out, int up, int u8 = 0) { return {in, n_in, H, 0, W, H, 0, H, out, up, u8, nullptr}; }
@@ -433,7 +441,8 @@ int batch_sub_size(const w2xc_opts &o, const size_t img_floats[2]);
 // size.  The caller holds c->mu.
 int run_batch(w2xc_model *m, DevCtx *c, int nimg, int up, PlanesIn in, int w, int h, PlanesOut out, hipStream_t st, const w2xc_opts &o_in, int max_sub = 0);
 // nimg IMAGES of planes: image i's planes start in_is / out_is floats behind image 0's, in.ps / out.ps apart (out.ps != 0: all planes of the last layer;
-// 0: plane 0 alone, as RowsCall).  u8 (ROWS_U8_SRC / ROWS_U8_DST): that side is interleaved uint8 images as in RowsCall, its image stride in BYTES.
+// 0: plane 0 alone, as RowsCall).  u8 (ROWS_U8_SRC / ROWS_U8_DST, with ROWS_U8_SRC_A / ROWS_U8_DST_PX4 / ROWS_U8_DST_A): that side is interleaved uint8 images
+// as in RowsCall, its image stride in BYTES.
 struct BatchIO {
     PlanesIn in; long long in_is; int n_in;
     PlanesOut out; long long out_is;

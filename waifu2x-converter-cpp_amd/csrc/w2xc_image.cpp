@@ -32,7 +32,8 @@ struct ImageCall {
     // check_process_args refuses anything but 0 and 1
     int tta_arg;
     bool tta;
-    // w2xc_process_image_rgb_u8_up2x_batch[_device]: the scale model is an upconv head model (and must be one), also under TTA
+    // w2xc_process_image_rgb_u8_up2x_batch[_device] and w2xc_process_image_rgba_u8_up2x_batch[_device]: the scale model is an upconv head model (and must be
+    // one), also under TTA
     bool up2x = false;
     ImageCall(w2xc_model *noise, w2xc_model *scale, int w_, int h_, int iterations_, double shrink_, void *hip_stream, const w2xc_opts *opts, int tta_ = 0)
         : mn(noise), msc(scale), w(w_), h(h_), iterations(iterations_), shrink(shrink_), st((hipStream_t)hip_stream), o(resolve_opts(opts)), tta_arg(tta_),
@@ -195,10 +196,15 @@ RgbPlan rgb_plan(const ImageCall &c)
 // colour stages and the shrink are one launch for the sub-batch, and so is every layer of a pass of S >= 2 images where the model's chain has batch kernels
 // (run_batch_planes; elsewhere it is the single-image launch sequence per image, enqueued back to back).  A single image is a sub-batch of one: run_rows.
 // (skip: the float planes start that many bytes into the aux buffer -- reserve_aux)
-int process_rgb_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, size_t skip = 0)
+// ends (the RGBA call for head models; ROWS_U8_SRC_A / ROWS_U8_DST_PX4 / ROWS_U8_DST_A of w2xc_engine.hpp): `in` is the alpha byte of RGBA pixels, `out` byte 0
+// -- the alpha head: byte 3 -- of RGBA pixels.  Only where the call's first / last layer takes the uint8 image itself (rgb_plan: the caller asks it first).
+int process_rgb_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, size_t skip = 0, int ends = 0)
 {
     DevCtx *own = c.ctx.owner();
     const RgbPlan R = rgb_plan(c);
+    if (((ends & ROWS_U8_SRC_A) && !R.src_u8) || ((ends & (ROWS_U8_DST_PX4 | ROWS_U8_DST_A)) && !R.dst_u8))
+        return fail(W2XC_ERR_ARG, "internal error: RGBA pixels for a pass that runs around float planes");
+    const long long in_cs = (ends & ROWS_U8_SRC_A) ? 0 : 1;   // (bytes between the channels of a source pixel)
     float *base = nullptr;
     if (R.floats) {
         if (int rc = reserve_aux(own, skip, R.floats * (size_t)cap)) return rc;
@@ -222,6 +228,7 @@ int process_rgb_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, s
         const int up = noise || head ? 0 : 1, nw = cw << (noise ? 0 : 1), nh = ch << (noise ? 0 : 1);
         const long long ps2 = (long long)plane_floats(nw, nh);
         const bool from_u8 = cur == nullptr, to_u8 = p == passes && R.dst_u8;
+        const int u8 = (from_u8 ? ROWS_U8_SRC | (ends & ROWS_U8_SRC_A) : 0) | (to_u8 ? ROWS_U8_DST | (ends & (ROWS_U8_DST_PX4 | ROWS_U8_DST_A)) : 0);
         float *nxt = nullptr;
         if (!to_u8) { nxt = base; base += 3 * (size_t)cap * ps2; }
         if (c.tta) {   // (neither from_u8 nor to_u8: rgb_plan)
@@ -229,15 +236,14 @@ int process_rgb_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, s
         } else if (S >= 2) {
             // ONE run_batch_planes for the sub-batch (one launch per layer where the chain has batch kernels): image i's three planes 3 ps on, or -- the uint8
             // forms -- the caller's images themselves: strides in bytes
-            const BatchIO io = {from_u8 ? PlanesIn{reinterpret_cast<const float *>(in.p), in.row, 1} : PlanesIn{cur, (size_t)cw, ps}, from_u8 ? (long long)in.img : 3 * ps, 3,
-                                to_u8 ? PlanesOut{reinterpret_cast<float *>(out.p), out.row, 1} : PlanesOut{nxt, (size_t)nw, ps2}, to_u8 ? (long long)out.img : 3 * ps2,
-                                (from_u8 ? ROWS_U8_SRC : 0) | (to_u8 ? ROWS_U8_DST : 0)};
+            const BatchIO io = {from_u8 ? PlanesIn{reinterpret_cast<const float *>(in.p), in.row, in_cs} : PlanesIn{cur, (size_t)cw, ps}, from_u8 ? (long long)in.img : 3 * ps, 3,
+                                to_u8 ? PlanesOut{reinterpret_cast<float *>(out.p), out.row, 1} : PlanesOut{nxt, (size_t)nw, ps2}, to_u8 ? (long long)out.img : 3 * ps2, u8};
             if (int rc = run_batch_planes(m, cm, S, up, io, cw, ch, c.st, c.o)) return rc;
         } else for (int i = 0; i < S; i++) {   // (a sub-batch of one: the single-image call, bands included)
             // image i's three planes, or -- the uint8 forms -- the caller's image itself: strides in bytes (Planes, w2xc_engine.hpp)
-            const PlanesIn src = from_u8 ? PlanesIn{reinterpret_cast<const float *>(in.p + (size_t)i * in.img), in.row, 1} : PlanesIn{cur + (size_t)i * 3 * ps, (size_t)cw, ps};
+            const PlanesIn src = from_u8 ? PlanesIn{reinterpret_cast<const float *>(in.p + (size_t)i * in.img), in.row, in_cs} : PlanesIn{cur + (size_t)i * 3 * ps, (size_t)cw, ps};
             const PlanesOut dst = to_u8 ? PlanesOut{reinterpret_cast<float *>(out.p + (size_t)i * out.img), out.row, 1} : PlanesOut{nxt + (size_t)i * 3 * ps2, (size_t)nw, ps2};
-            int rc = run_rows(m, cm, RowsCall::whole(src, 3, head ? cw : nw, head ? ch : nh, dst, up, (from_u8 ? ROWS_U8_SRC : 0) | (to_u8 ? ROWS_U8_DST : 0)), c.st, c.o);
+            int rc = run_rows(m, cm, RowsCall::whole(src, 3, head ? cw : nw, head ? ch : nh, dst, up, u8), c.st, c.o);
             if (rc) return rc;
         }
         if (to_u8) return W2XC_OK;
@@ -312,7 +318,7 @@ int check_process_args(const ImageCall &c, bool head_ok = false)
     if (c.tta_arg != 0 && c.tta_arg != 1) return fail(W2XC_ERR_ARG, "tta must be 0 or 1 (got %d)", c.tta_arg);
     if (int rc = refuse_head(c.mn, "the noise model of an image call")) return rc;
     if (c.up2x) {
-        if (!c.msc || !c.msc->has_head()) return fail(W2XC_ERR_ARG, "w2xc_process_image_rgb_u8_up2x_batch*: the scale model must be an upconv head model");
+        if (!c.msc || !c.msc->has_head()) return fail(W2XC_ERR_ARG, "w2xc_process_image_rgb[a]_u8_up2x_batch*: the scale model must be an upconv head model");
     } else if (!(head_ok && !c.tta)) if (int rc = refuse_head(c.msc, "this image call")) return rc;
     if (!c.mn && !c.msc) return fail(W2XC_ERR_ARG, "need a noise model, a scale model or both");
     if (c.iterations > 0 && !c.msc) return fail(W2XC_ERR_ARG, "scale iterations need a scale model");
@@ -387,8 +393,14 @@ int check_image_batch_args(bool rgb, ImageCall &c, int n, size_t in_stride, size
 // 256-byte-aligned image strides, the pipelines' float planes behind them:
 //   bled   the packed 3-channel images after the bleed      stamp  the bleed's pass stamps (16 bits per pixel; only the pass chain has them)
 //   res    the packed 3-channel results of the colour call  grey / ares (RGB route, iterations >= 1)  alpha as the images (A, A, A), and their results
+// A head model as scale model (w2xc_process_image_rgba_u8_up2x_batch*; RGB route, iterations >= 1) runs the same sequence, fused at either end where the layer
+// at that end has the uint8 kernel (rgb_plan):
+//   fuse_src  layer 1 of the alpha pass reads the caller's alpha bytes itself: no grey images, no AlphaToGrey launch
+//   fuse_dst  the colour pass's head writes bytes 0 .. 2 of the caller's output pixels and the alpha pass's head -- the alpha head, channel 1 alone -- byte 3:
+//             no res and ares images, no merge launch
 struct RgbaPlan {
     bool rgb = false;
+    bool fuse_src = false, fuse_dst = false;
     int passes = 0;          // bleed passes that can change a pixel: no pixel is farther than max(w, h) - 1 from an opaque one
     int sub = 1;             // images per sub-batch (plan_image_call)
     size_t bled = 0, stamp = 0, res = 0, grey = 0, ares = 0;   // bytes per image of each (a multiple of 256; 0 = the call has none)
@@ -422,7 +434,7 @@ int plan_rgba(const ImageCall &c, int bleed_passes, RgbaPlan *R)
     const w2xc_model *first = c.mn ? c.mn : c.msc;
     if (first->layers.empty()) return fail(W2XC_ERR_ARG, "model has no layers");
     if (int rc = check_image_extent(c)) return rc;
-    R->rgb = first->layers[0].nin == 3;
+    R->rgb = c.up2x || first->layers[0].nin == 3;   // (the head call has the RGB route only: a one-plane head model is refused as the 3-channel call refuses it)
     if (!R->rgb) if (int rc = check_y_models(c)) return rc;
     if (int rc = plan_image_call(R->rgb ? PLAN_RGB : PLAN_Y, c, &R->sub)) return rc;   // (the models' and the options' errors, before the models are asked anything)
     long long P = bleed_passes;
@@ -432,13 +444,17 @@ int plan_rgba(const ImageCall &c, int bleed_passes, RgbaPlan *R)
     R->passes = (int)P;
     R->bled = align256((size_t)c.w * 3 * c.h);
     if (w2xc_bleed_stamps((int)P)) R->stamp = align256((size_t)c.w * 2 * c.h);
-    R->res = align256((size_t)c.fw * 3 * c.fh);
     const bool ride = c.iterations > 0;   // alpha goes through the scale model
+    if (R->rgb && ride && c.msc->has_head()) {
+        R->fuse_src = rgb_plan(alpha_call(c)).src_u8;
+        R->fuse_dst = rgb_plan(c).dst_u8;   // (the colour pass and the alpha pass end in the same layer under the same options)
+    }
+    if (!R->fuse_dst) R->res = align256((size_t)c.fw * 3 * c.fh);
     if (R->rgb) {
         R->floats = rgb_plan(c).floats;
         if (ride) {
-            R->grey = align256((size_t)c.w * 3 * c.h);
-            R->ares = align256((size_t)c.fw * 3 * c.fh);
+            if (!R->fuse_src) R->grey = align256((size_t)c.w * 3 * c.h);
+            if (!R->fuse_dst) R->ares = align256((size_t)c.fw * 3 * c.fh);
             R->floats = std::max(R->floats, rgb_plan(alpha_call(c)).floats);
         }
     } else R->floats = image_aux_floats(c.w, c.h, c.iterations, c.shrink, ride);
@@ -461,11 +477,19 @@ int process_rgba_device(const RgbaPlan &R, const ImageCall &c, int S, int cap, U
     const U8Out res{a8 + L.res, R.res, RS};
     HIP_TRY(w2xc_launch_rgba_bleed(in.p, in.img, in.row, w, h, R.passes, a8 + L.bled, R.bled, rs, reinterpret_cast<unsigned short *>(a8 + L.stamp), R.stamp / 2, S, c.st));
     if (R.rgb) {
-        if (int rc = process_rgb_device(c, S, cap, bled, res, L.head)) return rc;
+        // (fuse_dst, a head model: the colour bytes go into the caller's pixels as the head computes them)
+        if (int rc = process_rgb_device(c, S, cap, bled, R.fuse_dst ? out : res, L.head, R.fuse_dst ? ROWS_U8_DST_PX4 : 0)) return rc;
         if (c.iterations > 0) {   // alpha = channel 1 of the scale-only call on (A, A, A)
-            HIP_TRY(w2xc_launch_alpha_to_grey(in.p, in.img, in.row, w, h, a8 + L.grey, R.grey, rs, S, c.st));
-            if (int rc = process_rgb_device(alpha_call(c), S, cap, U8In{a8 + L.grey, R.grey, rs}, U8Out{a8 + L.ares, R.ares, RS}, L.head)) return rc;
-            HIP_TRY(w2xc_launch_merge_rgba_u8(res.p, res.img, RS, a8 + L.ares + 1, R.ares, RS, 3, W, H, out.p, out.img, out.row, S, c.st));
+            // fuse_src: layer 1 reads the alpha bytes where they are; fuse_dst: the alpha head computes channel 1 alone, into byte 3 of the caller's pixels
+            U8In grey{in.p + 3, in.img, in.row};
+            if (!R.fuse_src) {
+                HIP_TRY(w2xc_launch_alpha_to_grey(in.p, in.img, in.row, w, h, a8 + L.grey, R.grey, rs, S, c.st));
+                grey = U8In{a8 + L.grey, R.grey, rs};
+            }
+            const U8Out ares = R.fuse_dst ? U8Out{out.p + 3, out.img, out.row} : U8Out{a8 + L.ares, R.ares, RS};
+            const int ends = (R.fuse_src ? ROWS_U8_SRC_A : 0) | (R.fuse_dst ? ROWS_U8_DST_PX4 | ROWS_U8_DST_A : 0);
+            if (int rc = process_rgb_device(alpha_call(c), S, cap, grey, ares, L.head, ends)) return rc;
+            if (!R.fuse_dst) HIP_TRY(w2xc_launch_merge_rgba_u8(res.p, res.img, RS, a8 + L.ares + 1, R.ares, RS, 3, W, H, out.p, out.img, out.row, S, c.st));
             return W2XC_OK;
         }
     } else {   // with a scale pass alpha rides with Y (run_batch's passes); without one the 3-channel call as it is: the single image through run_rows
@@ -901,6 +925,26 @@ int w2xc_process_image_rgba_u8_batch(w2xc_model *noise_model, w2xc_model *scale_
 try {
     return rgba_batch_host(ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, nullptr, opts), n, in, in_stride_bytes, out, out_stride_bytes,
                            bleed_passes);
+} W2XC_CATCH_ALL
+
+// ---- ... with an upconv head model as scale model (n = 1: the single-image form, bands included) ----
+int w2xc_process_image_rgba_u8_up2x_batch_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in, size_t in_image_stride_bytes,
+                                                 size_t in_stride_bytes, int w, int h, unsigned char *d_out, size_t out_image_stride_bytes,
+                                                 size_t out_stride_bytes, int iterations, double shrink_ratio, int bleed_passes, void *hip_stream,
+                                                 const w2xc_opts *opts)
+try {
+    ImageCall c(noise_model, scale_model, w, h, iterations, shrink_ratio, hip_stream, opts);
+    c.up2x = true;
+    return rgba_batch_device(c, n, U8In{d_in, in_image_stride_bytes, in_stride_bytes}, U8Out{d_out, out_image_stride_bytes, out_stride_bytes}, bleed_passes);
+} W2XC_CATCH_ALL
+
+int w2xc_process_image_rgba_u8_up2x_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes, int w,
+                                          int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio, int bleed_passes,
+                                          const w2xc_opts *opts)
+try {
+    ImageCall c(noise_model, scale_model, w, h, iterations, shrink_ratio, nullptr, opts);
+    c.up2x = true;
+    return rgba_batch_host(c, n, in, in_stride_bytes, out, out_stride_bytes, bleed_passes);
 } W2XC_CATCH_ALL
 
 int w2xc_bleed_rgba_u8_device(const unsigned char *d_in, size_t in_stride_bytes, int w, int h, int passes, unsigned char *d_out_rgb, size_t out_stride_bytes,

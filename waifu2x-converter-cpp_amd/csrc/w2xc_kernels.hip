@@ -375,7 +375,8 @@ __global__ void __launch_bounds__(WM *WN * 64, WM *WN / 4) conv3x3_mfma2(W2xcCon
 #ifndef FIRST_TPW
 #define FIRST_TPW 4
 #endif
-// U8 (W2XC_K_FIRST_U8): the source is an interleaved uint8 image -- d.in points at BYTES, in_rs / in_ps / in_cs are byte strides (row stride, 3, 1) -- and the
+// U8 (W2XC_K_FIRST_U8): the source is an interleaved uint8 image -- d.in points at BYTES, in_rs / in_ps / in_cs are byte strides (row stride, 3, 1; or
+// row stride, 4, 0 with d.in at an RGBA image's alpha byte: the three planes are then that byte, the grey image (A, A, A) without its copy) -- and the
 // patch load converts, (float)byte * (float)(1.0 / 255.0): the expression of the colour kernels (w2xc_color.hip), so the float planes they would write for
 // this layer to read never exist.  Everything behind the patch load is the float form's.
 template <int CIN, int NBT, bool PLANAR = false, bool U8 = false>
@@ -524,7 +525,7 @@ hipError_t w2xc_launch_conv(W2xcKernelKind kind, const W2xcConvDesc &d, hipStrea
         }
     }
     if (kind == W2XC_K_FIRST_U8) {   // three interleaved uint8 channels in; either output layout, with the float form's conditions
-        if (d.cin != 3 || d.in_ps != 3 || d.in_cs != 1) return hipErrorInvalidValue;
+        if (d.cin != 3 || !((d.in_ps == 3 && d.in_cs == 1) || (d.in_ps == 4 && d.in_cs == 0))) return hipErrorInvalidValue;   // (4, 0: the alpha byte of RGBA pixels as all three planes)
         if (d.out_ps == 1) {
             if (((d.out_rs | d.out_cs) & 3) != 0 || d.out_rs < ((d.out_w + 3) & ~3) || (((size_t)d.out) & 15) != 0) return hipErrorInvalidValue;
             switch (d.cout) {

@@ -97,6 +97,11 @@ int get_ctx(w2xc_model *m, int device, DevCtx **out)
                 pk.resize(w2xc_upconv_packed_floats(hl.nin, hl.nout));
                 w2xc_upconv_pack(hl.nin, hl.nout, hl.w.data(), pk.data());
                 if ((rc = upload(pk, &dl.w_fast))) return rc;
+                if (hl.nout == 3) {   // the alpha head of the RGBA call: channel 1 alone, 16 * nin floats
+                    pk.resize(w2xc_upconv_packed_floats(hl.nin, 1));
+                    w2xc_upconv_pack_alpha(hl.nin, hl.w.data(), pk.data());
+                    if ((rc = upload(pk, &dl.w_alpha))) return rc;
+                }
             }
         } else {
             dl.fast = w2xc_pick_kernel(hl.nin, hl.nout);
@@ -215,6 +220,8 @@ const char *w2xc_last_error(void) { return g_last_error.c_str(); }
 //          an nn.SpatialFullConvolution 4x4 / stride 2 / padding 3; every other entry point refuses such a model (additive; w2xc_opts stays 56 bytes)
 // 0.4.1.6.1: the batch and TTA forms for upconv head models -- w2xc_convert_planes_up2x_batch_device, w2xc_process_image_rgb_u8_up2x_batch[_device] (with tta),
 // w2xc_batch_plan with nn2x = 2; no struct change, and every existing call refuses a head model as before.
+// 0.4.1.6.2: the RGBA call for upconv head models -- w2xc_process_image_rgba_u8_up2x_batch[_device] (additive; w2xc_opts stays 56 bytes).  The string below
+// stays at 0.4.1.6.1 (callers compare it for equality): the new revision is found by the presence of the symbols.
 const char *w2xc_version(void) { return "w2xc_hip 0.4.1.6.1 (gfx950)"; }
 
 int w2xc_plan_rows(const w2xc_model *m, int w, int view_y0, int view_h, int plane_h, int row_begin, int row_end, const w2xc_opts *opts, w2xc_row_plan *plan)

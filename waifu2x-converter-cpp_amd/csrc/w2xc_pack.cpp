@@ -34,6 +34,7 @@ const char *w2xc_kernel_name(W2xcKernelKind kind, int cin, int cout)
     case W2XC_K_LAST_U8: return "conv3x3_last_u8";
     case W2XC_K_UPCONV: return "upconv4x4_head";
     case W2XC_K_UPCONV_U8: return "upconv4x4_head_u8";
+    case W2XC_K_UPCONV_A_U8: return "upconv4x4_head_alpha_u8";
     default: return "conv3x3_direct";
     }
 }
@@ -114,6 +115,17 @@ void w2xc_upconv_pack(int cin, int nout, const float *w, float *dst)
                     const int n = nb * 16 + (lane & 15), c = 16 * s4 + 4 * (lane >> 4) + j;
                     dst[(((size_t)s4 * 4 + j) * nb16 + nb) * W2XC_WAVE + lane] = w[((size_t)c * nout + n % nout) * 16 + n / nout];
                 }
+}
+
+void w2xc_upconv_pack_alpha(int cin, const float *w, float *dst)
+{
+    // w2xc_upconv_pack(cin, 1, Wt[:, 1], dst) without the copy of the slice: plane c's 16 taps lie at w + (3 c + 1) * 16, and with one output n = tap
+    for (int s4 = 0; s4 < cin / 16; s4++)
+        for (int j = 0; j < 4; j++)
+            for (int lane = 0; lane < W2XC_WAVE; lane++) {
+                const int c = 16 * s4 + 4 * (lane >> 4) + j;
+                dst[((size_t)s4 * 4 + j) * W2XC_WAVE + lane] = w[((size_t)c * 3 + 1) * 16 + (lane & 15)];
+            }
 }
 
 // one workgroup per tile up to two per CU (512); beyond that every workgroup walks a run of consecutive tiles

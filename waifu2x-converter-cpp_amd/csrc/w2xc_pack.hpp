@@ -23,7 +23,8 @@ enum W2xcKernelKind {
     // the head of an upconv model (w2xc_upconv.hip): {32,64,128,256} NHWC planes in -> {1,3} planes out at twice the size, 4x4 stride-2 transposed convolution;
     // never what w2xc_pick_kernel answers (a head is a property of the model, not of a plane count) -- layer_kind puts it in place for the head layer
     W2XC_K_UPCONV = 15,        // planar float planes out
-    W2XC_K_UPCONV_U8 = 16,     // three interleaved uint8 channels out (as W2XC_K_LAST_U8)
+    W2XC_K_UPCONV_U8 = 16,     // three interleaved uint8 channels out (as W2XC_K_LAST_U8), pixels 3 or 4 bytes apart
+    W2XC_K_UPCONV_A_U8 = 17,   // the alpha head: channel 1 of a three-plane head alone, one uint8 per pixel (the w2xc_upconv_pack_alpha image, bias[1])
 };
 
 // Which kernel kind the fast path has for a (cin, cout) layer; W2XC_K_DIRECT when none.
@@ -77,6 +78,9 @@ float w2xc_split_pack_last(int cin, int terms, int fmt, const float *w, void *ds
 bool w2xc_upconv_supported(int cin, int nout);
 size_t w2xc_upconv_packed_floats(int cin, int nout);
 void w2xc_upconv_pack(int cin, int nout, const float *w, float *dst);
+// the alpha head's image: w2xc_upconv_pack(cin, 1, .) on channel 1 of a three-plane head, Wt[:, 1] -- 16 * cin floats; column 4 r + s of it is column
+// (4 r + s) * 3 + 1 of the three-plane image
+void w2xc_upconv_pack_alpha(int cin, const float *w, float *dst);
 int w2xc_upconv_grid(int ntiles);
 // a 3x3 layer of a head model with fewer than 32 planes on a side, zero-padded to cin_p x cout_p planes: dst[o][i][3][3] = w[o][i] for o < cout, i < cin, else 0
 void w2xc_pad_layer(int cin, int cout, int cin_p, int cout_p, const float *w, float *dst);

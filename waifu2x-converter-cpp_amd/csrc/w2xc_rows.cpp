@@ -65,7 +65,8 @@ hipError_t launch_kind(W2xcKernelKind kind, int midv, const W2xcConvDesc &d, con
     case W2XC_K_LAST:
     case W2XC_K_LAST_U8: return bd ? w2xc_launch_conv_batch(kind, d, *bd, st) : w2xc_launch_conv(kind, d, st);
     case W2XC_K_UPCONV:
-    case W2XC_K_UPCONV_U8: return bd ? w2xc_launch_upconv_batch(kind, d, *bd, st) : w2xc_launch_upconv(kind, d, st);
+    case W2XC_K_UPCONV_U8:
+    case W2XC_K_UPCONV_A_U8: return bd ? w2xc_launch_upconv_batch(kind, d, *bd, st) : w2xc_launch_upconv(kind, d, st);
     default: break;
     }
     if (midv == MID_WINO4) return bd ? w2xc_launch_wino4_batch(d, *bd, st) : w2xc_launch_wino4(d, st);
@@ -93,6 +94,11 @@ int launch_layer(DevCtx *c, const w2xc_model *m, int l, W2xcKernelKind kind, W2x
         d.w1pk = c->layers[l - 1].w_fast;
         d.bias1 = c->layers[l - 1].bias;
         break;
+    case W2XC_K_UPCONV_A_U8:   // the alpha head: channel 1 of the three-plane head as a one-plane head of its own (its image: get_ctx)
+        if (d.cout != 3 || !dl.w_alpha) return fail(W2XC_ERR_ARG, "internal error: the alpha head of a layer that is no three-plane upconv head");
+        d.cout = 1;
+        d.wpk = dl.w_alpha;
+        break;
     default: d.wpk = kind == W2XC_K_DIRECT ? dl.w_direct : dl.w_fast;
     }
     if (!rc && midv != MID_MFMA) {   // the fp32 Winograd images of a mid layer
@@ -107,7 +113,7 @@ int launch_layer(DevCtx *c, const w2xc_model *m, int l, W2xcKernelKind kind, W2x
         }
     }
     if (rc) return rc;
-    d.bias = dl.bias;
+    d.bias = kind == W2XC_K_UPCONV_A_U8 ? dl.bias + 1 : dl.bias;
     ProfEvent ev;
     const bool profile = o.profile != 0;
     if (profile) { rc = prof_begin(c, l, st, &ev); if (rc) return rc; }
@@ -358,7 +364,11 @@ int run_band(Band &B, const LayerSrc &view, int up)
         if (kind == W2XC_K_FUSED_AWAY) continue;
         // the uint8 forms (run_rows has checked the kinds they stand in for): the descriptor's strides are the image's, in bytes
         if (k == 1 && (B.u8 & ROWS_U8_SRC)) kind = W2XC_K_FIRST_U8;
-        if (k == n && (B.u8 & ROWS_U8_DST)) { kind = kind == W2XC_K_UPCONV ? W2XC_K_UPCONV_U8 : W2XC_K_LAST_U8; d.out_ps = 3; }
+        if (k == n && (B.u8 & ROWS_U8_DST)) {
+            // (a head's sink may be RGBA pixels, and the alpha head one byte of them: check_u8_views lets neither through for conv3x3_last)
+            kind = kind != W2XC_K_UPCONV ? W2XC_K_LAST_U8 : (B.u8 & ROWS_U8_DST_A) ? W2XC_K_UPCONV_A_U8 : W2XC_K_UPCONV_U8;
+            d.out_ps = (B.u8 & ROWS_U8_DST_PX4) ? 4 : 3;
+        }
         const int Tk = next.top;   // first plane row of the layer's region
         // the strategies that run layer n - 1 and the last layer together end the band
         if (prog_eligible(B, k, kind, d)) {
@@ -383,9 +393,13 @@ int run_band(Band &B, const LayerSrc &view, int up)
 // the uint8 views of a call planned as P: no hooks, channels one byte apart, and the layers they touch have the uint8 kernels
 static int check_u8_views(const w2xc_model *m, const RowPlan &P, int u8, bool hooks, long long in_ps, long long out_ps)
 {
-    if (u8 && (hooks || ((u8 & ROWS_U8_SRC) && (in_ps != 1 || !u8_source_layer(m, P.o))) ||
+    if (u8 && (hooks || ((u8 & ROWS_U8_SRC) && (in_ps != ((u8 & ROWS_U8_SRC_A) ? 0 : 1) || !u8_source_layer(m, P.o))) ||
                ((u8 & ROWS_U8_DST) && (out_ps != 1 || !P.last_direct || !u8_sink_layer(m, P.o)))))
         return fail(W2XC_ERR_ARG, "internal error: a uint8 view for a layer without the uint8 kernel");
+    // the forms of the RGBA head call: each beside the flag of its side, the sink's only where the last layer is a head (the alpha head: a three-plane one)
+    const bool src_a = (u8 & ROWS_U8_SRC_A) != 0, dst_x = (u8 & (ROWS_U8_DST_PX4 | ROWS_U8_DST_A)) != 0;
+    if ((src_a && !(u8 & ROWS_U8_SRC)) || (dst_x && (!(u8 & ROWS_U8_DST) || P.last_kind != W2XC_K_UPCONV || m->layers[P.n - 1].nout != 3)))
+        return fail(W2XC_ERR_ARG, "internal error: an RGBA pixel view for a layer without that form");
     return W2XC_OK;
 }
 
@@ -401,7 +415,7 @@ int run_rows(w2xc_model *m, DevCtx *c, const RowsCall &r, hipStream_t st, const 
     LayerSrc view;   // the source view; its first row is plane row view_y0
     view.p = r.in.p; view.rs = (long long)r.in.rs; view.cs = r.in.ps;
     view.h = r.view_h; view.w = r.w; view.top = r.view_y0;
-    if (r.u8 & ROWS_U8_SRC) view.ps = 3;   // (bytes: row stride in.rs, pixels 3 apart, channels in.ps = 1 apart)
+    if (r.u8 & ROWS_U8_SRC) view.ps = (r.u8 & ROWS_U8_SRC_A) ? 4 : 3;   // (bytes: row stride in.rs, pixels 3 apart, channels in.ps = 1 apart; the alpha byte of RGBA pixels: 4 and 0)
     const size_t out_rows_per_row = m->has_head() ? 2 : 1;   // (an upconv head model: ra, rb and the bands count SOURCE rows, each gives two output rows)
     for (int y0 = r.ra; y0 < r.rb; y0 += P.band) {
         // the band's first output row: out.rs floats per row, or -- a uint8 image -- as many BYTES
@@ -482,7 +496,7 @@ int run_batch_planes(w2xc_model *m, DevCtx *c, int nimg, int up, const BatchIO &
         B.img_f[0] = img_f[0]; B.img_f[1] = img_f[1];
         LayerSrc view;   // (as run_rows makes it: the W x H plane, also where up = 1)
         view.p = in0.p; view.rs = (long long)in0.rs; view.cs = in0.ps; view.h = H; view.w = W;
-        if (io.u8 & ROWS_U8_SRC) view.ps = 3;
+        if (io.u8 & ROWS_U8_SRC) view.ps = (io.u8 & ROWS_U8_SRC_A) ? 4 : 3;
         if (int rc = run_band(B, view, up)) return rc;
     }
     return W2XC_OK;

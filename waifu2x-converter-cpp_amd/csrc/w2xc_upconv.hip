@@ -15,7 +15,22 @@
 #include "w2xc_launch.hpp"
 
 // U8 (W2XC_K_UPCONV_U8): the sink is an interleaved uint8 image as for conv3x3_last<U8> -- d.out points at bytes, out_rs / out_ps / out_cs are byte
-// strides (row stride, NOUT, 1) -- and the epilogue stores saturate(rint(255 v)), one byte store per value.
+// strides (row stride, 3 or 4, 1) -- and the epilogue stores saturate(rint(255 v)), one byte store per value.  out_ps = 4: the colour bytes of RGBA pixels
+// (the RGBA call for head models), the fourth byte is never touched.
+// The alpha head (W2XC_K_UPCONV_A_U8, <CIN, 1, true>): ONE plane into byte d.out[0] of pixels out_ps = 3 or 4 bytes apart, on the image packed from channel 1
+// of a three-plane head (w2xc_upconv_pack_alpha) with bias[1].  A column's MFMA chain does not depend on its neighbours and the tap sum is per plane: the
+// byte has the bits of channel 1 of the three-plane launch, at a third of its matrix work and of its LDS.
+// the sink a kind may have: float planes (pixels one float apart); three uint8 channels one byte apart in pixels of 3 or 4 bytes; the alpha head's one byte
+static bool w2xc_upconv_sink_ok(W2xcKernelKind kind, const W2xcConvDesc &d)
+{
+    switch (kind) {
+    case W2XC_K_UPCONV: return d.out_ps == 1;
+    case W2XC_K_UPCONV_U8: return d.cout == 3 && (d.out_ps == 3 || d.out_ps == 4) && d.out_cs == 1;
+    case W2XC_K_UPCONV_A_U8: return d.cout == 1 && (d.out_ps == 3 || d.out_ps == 4);
+    default: return false;
+    }
+}
+
 template <int CIN, int NOUT, bool U8>
 __global__ void __launch_bounds__(256) upconv4x4_head(W2xcConvDesc d, int tiles_x, int ntiles)
 {
@@ -73,11 +88,11 @@ hipError_t w2xc_launch_upconv_batch(W2xcKernelKind kind, const W2xcConvDesc &d, 
     if (b.batch < 0 || b.in_bs < 0 || b.out_bs < 0 || (b.in_bs & 3) != 0) return hipErrorInvalidValue;
     if (d.in_shift != 0 || d.in_ps != d.cin || d.in_cs != 1 || (d.in_rs & 3) != 0 || (((size_t)d.in) & 15) != 0) return hipErrorInvalidValue;
     if (d.in_h < 1 || d.in_w < 1) return hipErrorInvalidValue;
-    const bool u8 = kind == W2XC_K_UPCONV_U8;
-    if (u8 ? (d.cout != 3 || d.out_ps != 3 || d.out_cs != 1) : d.out_ps != 1) return hipErrorInvalidValue;
+    const bool u8 = kind != W2XC_K_UPCONV;
+    if (!w2xc_upconv_sink_ok(kind, d)) return hipErrorInvalidValue;
     switch (d.cin * 10 + d.cout) {
 #define W2XC_UPCONV_CASE(C)                                                                                        \
-    case C * 10 + 1: return u8 ? hipErrorInvalidValue : launch_upconv_batch<C, 1, false>(d, b, stream);           \
+    case C * 10 + 1: return u8 ? launch_upconv_batch<C, 1, true>(d, b, stream) : launch_upconv_batch<C, 1, false>(d, b, stream); \
     case C * 10 + 3: return u8 ? launch_upconv_batch<C, 3, true>(d, b, stream) : launch_upconv_batch<C, 3, false>(d, b, stream);
         W2XC_UPCONV_CASE(32)
         W2XC_UPCONV_CASE(64)
@@ -112,11 +127,11 @@ hipError_t w2xc_launch_upconv(W2xcKernelKind kind, const W2xcConvDesc &d, hipStr
     if (d.out_w <= 0 || d.out_h <= 0) return hipSuccess;
     if (d.in_shift != 0 || d.in_ps != d.cin || d.in_cs != 1 || (d.in_rs & 3) != 0 || (((size_t)d.in) & 15) != 0) return hipErrorInvalidValue;
     if (d.in_h < 1 || d.in_w < 1) return hipErrorInvalidValue;
-    const bool u8 = kind == W2XC_K_UPCONV_U8;
-    if (u8 ? (d.cout != 3 || d.out_ps != 3 || d.out_cs != 1) : d.out_ps != 1) return hipErrorInvalidValue;
+    const bool u8 = kind != W2XC_K_UPCONV;
+    if (!w2xc_upconv_sink_ok(kind, d)) return hipErrorInvalidValue;
     switch (d.cin * 10 + d.cout) {
 #define W2XC_UPCONV_CASE(C)                                                                                  \
-    case C * 10 + 1: return u8 ? hipErrorInvalidValue : launch_upconv<C, 1, false>(d, stream);              \
+    case C * 10 + 1: return u8 ? launch_upconv<C, 1, true>(d, stream) : launch_upconv<C, 1, false>(d, stream); \
     case C * 10 + 3: return u8 ? launch_upconv<C, 3, true>(d, stream) : launch_upconv<C, 3, false>(d, stream);
         W2XC_UPCONV_CASE(32)
         W2XC_UPCONV_CASE(64)
