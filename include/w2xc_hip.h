@@ -526,7 +526,7 @@ int w2xc_process_image_rgba_u8_batch(w2xc_model *noise_model, w2xc_model *scale_
                                      const w2xc_opts *opts);
 /* (0.4.1.6.2) n >= 1 RGBA images of one size with an upconv head model as scale_model: the result is defined under "upconv head models", RGBA.  n = 1 is the
  * single-image form, bands included (w2xc_opts.band_rows; a banded run gives the bytes of the unbanded one).  Arguments as
- * w2xc_process_image_rgba_u8_batch[_device]; there is no tta argument (no RGBA call has one).
+ * w2xc_process_image_rgba_u8_batch[_device]; there is no tta argument here: the TTA form is w2xc_process_image_rgba_u8_up2x_batch_tta[_device] below (0.4.1.6.3).
  * A sub-batch of S >= 2 images runs the colour pass and the alpha pass as one launch per layer each where the chain has batch kernels -- the uint8 forms
  * above included: upconv4x4_head_batch on 4-byte pixels, the alpha head's batch form, conv3x3_first_batch on the alpha bytes --, S = 1 the single-image
  * launches.  The host form overlaps sub-batches like w2xc_process_image_rgba_u8_batch.
@@ -534,7 +534,7 @@ int w2xc_process_image_rgba_u8_batch(w2xc_model *noise_model, w2xc_model *scale_
  * W2XC_ERR_ARG, a head model as noise model and the 16-bit precisions W2XC_ERR_UNSUPPORTED, a model that is not three planes in and three out
  * W2XC_ERR_PLANES -- and what the RGBA batch calls refuse, with their codes: row strides below 4 x width, n < 1, null pointers, outputs that overlap each
  * other or an input, more than 65534 effective bleed passes, an extent above 2^28.
- * Not built: TTA, the Y route, split precisions, multi-device striping of the device form, and the colour and alpha images of a sub-batch as ONE batch of
+ * Not built: the Y route, split precisions, multi-device striping of the device form, and the colour and alpha images of a sub-batch as ONE batch of
  * 2 S through the 3x3 layers (they share weights; layer 1 and the head differ). */
 int w2xc_process_image_rgba_u8_up2x_batch_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in, size_t in_image_stride_bytes,
                                                  size_t in_stride_bytes, int w, int h, unsigned char *d_out, size_t out_image_stride_bytes,
@@ -543,6 +543,46 @@ int w2xc_process_image_rgba_u8_up2x_batch_device(w2xc_model *noise_model, w2xc_m
 int w2xc_process_image_rgba_u8_up2x_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes, int w,
                                           int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio, int bleed_passes,
                                           const w2xc_opts *opts);
+/* (0.4.1.6.3) The RGBA calls under test-time augmentation (the arithmetic: "Test-time augmentation" below): the arguments of
+ * w2xc_process_image_rgba_u8_batch[_device] (Y and RGB models; a head model is refused as there) and of w2xc_process_image_rgba_u8_up2x_batch[_device] (a head
+ * model as scale model) and `int tta` behind them.  n >= 1; n = 1 is the single-image form, bands included.  tta = 0 is exactly the call without the argument,
+ * anything but 0 and 1 W2XC_ERR_ARG.  Each refuses, with the same codes and before any device is touched, everything its sibling without tta refuses; without
+ * a device W2XC_ERR_HIP.  The device forms are asynchronous on hip_stream, the host forms overlap sub-batches as their siblings do.  Image i of a batch is
+ * byte-identical to the n = 1 call on image i, for every option set.
+ * With tta = 1 the result is, byte for byte, this composition of calls that exist without it:
+ *   bleed   unchanged: w2xc_bleed_rgba_u8_device with the same automatic pass count (TTA changes no layer count).
+ *   colour  the 3-channel TTA call of the route on the bled image, same models, iterations, shrink_ratio and opts: w2xc_process_image_u8_tta_device(..., 1)
+ *           for Y models, w2xc_process_image_rgb_u8_tta_device(..., 1) for RGB models, w2xc_process_image_rgb_u8_up2x_batch_device(n = 1, ..., tta = 1) for a
+ *           head model as scale model.
+ *   alpha   never sees the noise model, and goes through TTA only where it goes through the CNN.  iterations == 0: the bytes are copied, or linearly shrunk,
+ *           as without TTA.  Y route: a = (float)byte * (float)(1.0 / 255.0); per iteration one TTA pass of the scale model with the nearest-2x fold
+ *           (w2xc_convert_batch_tta_device(scale, 1, nn2x = 1, ...)); the shrink's INTER_LINEAR; saturate(rint(255 a)).  RGB route: channel 1 of the
+ *           scale-only 3-channel TTA call on the image (A, A, A); head route: the same through the up2x TTA call.
+ * How it runs.  Y route: alpha rides with Y -- the scale pass's variants are 16 S planes in one batch where w == h, two of 8 S otherwise; the noise pass runs
+ * on the S Y planes alone.  RGB and head routes, w2xc_opts.fusion other than W2XC_FUSION_OFF: the first spread of the colour sequence reads the bled uint8
+ * image and that of the alpha sequence the caller's alpha bytes (w2xc_tta_spread_u8_device's kernel: no float copy of the source, no grey image), and where the
+ * last pass is a scale pass with no shrink behind it the colour gather writes bytes 0 .. 2 and the alpha gather byte 3 of the caller's pixels
+ * (w2xc_tta_gather_u8_device's kernel: no final float planes, no intermediate uint8 results, no merge launch).  These ends do not depend on precision or kernel
+ * choice.  On the head route the last alpha pass runs the one-plane alpha head with its float sink (the bits of channel 1 of the full head), so its gather
+ * reads 8 planes per image instead of 24; for RGB models without a head it runs the full chain and the gather selects channel 1.  Every other case --
+ * W2XC_FUSION_OFF, a shrink, iterations == 0, the levels between two passes -- runs the stages of the calls above around float planes.  The variant planes of
+ * the larger of the two sequences count into the per-image bytes that size a sub-batch under w2xc_opts.workspace_mb.
+ * Not built: fused uint8 ends for the opaque TTA calls and for the Y route, a one-plane last layer for RGB models without a head, colour and alpha as one
+ * batch of 2 S through the 3x3 layers, 16-bit precisions for head models, multi-device striping of the device forms. */
+int w2xc_process_image_rgba_u8_batch_tta_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in, size_t in_image_stride_bytes,
+                                                size_t in_stride_bytes, int w, int h, unsigned char *d_out, size_t out_image_stride_bytes,
+                                                size_t out_stride_bytes, int iterations, double shrink_ratio, int bleed_passes, void *hip_stream,
+                                                const w2xc_opts *opts, int tta);
+int w2xc_process_image_rgba_u8_batch_tta(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes, int w,
+                                         int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio, int bleed_passes,
+                                         const w2xc_opts *opts, int tta);
+int w2xc_process_image_rgba_u8_up2x_batch_tta_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in,
+                                                     size_t in_image_stride_bytes, size_t in_stride_bytes, int w, int h, unsigned char *d_out,
+                                                     size_t out_image_stride_bytes, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                                     int bleed_passes, void *hip_stream, const w2xc_opts *opts, int tta);
+int w2xc_process_image_rgba_u8_up2x_batch_tta(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes,
+                                              int w, int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                              int bleed_passes, const w2xc_opts *opts, int tta);
 /* Test-time augmentation (TTA): every CNN pass runs on the 8 flips and transposes of its input, each result is transformed back and the 8 are averaged --
  * the quality option later upstream versions of the converter have as --tta (v1 of the reference has none); 8x the CNN work.  The arithmetic is defined here:
  *   T_k, k = 0..7, on a plane x of h rows x w columns applies, in this order: the horizontal flip (x[:, ::-1]) if k & 1, the vertical flip (x[::-1, :]) if
@@ -574,7 +614,8 @@ int w2xc_convert_planes_tta_device(w2xc_model *m, int n_in_planes, int nn2x, con
 /* Image calls: each takes the arguments of the call it is named after -- w2xc_process_image_u8_ex[_device], w2xc_process_image_u8_batch[_device] and their
  * rgb forms -- and `int tta` behind them: 0 = exactly that call, 1 = TTA, anything else W2XC_ERR_ARG.  Argument and model errors are those of that call (on the
  * Y route a model that does not take one plane to one plane is W2XC_ERR_PLANES already here), before a device is touched; without a device W2XC_ERR_HIP.  The
- * device forms are asynchronous.  A batch's images are byte-identical to the single-image TTA call.  There is no TTA form of the RGBA call. */
+ * device forms are asynchronous.  A batch's images are byte-identical to the single-image TTA call.  The TTA forms of the RGBA calls (0.4.1.6.3) are
+ * w2xc_process_image_rgba_u8_batch_tta[_device] and w2xc_process_image_rgba_u8_up2x_batch_tta[_device], above. */
 int w2xc_process_image_u8_tta_device(w2xc_model *noise_model, w2xc_model *scale_model, const unsigned char *d_in, size_t in_stride_bytes, int w, int h,
                                      unsigned char *d_out, size_t out_stride_bytes, int iterations, double shrink_ratio, void *hip_stream,
                                      const w2xc_opts *opts, int tta);
@@ -607,6 +648,23 @@ int w2xc_tta_spread_device(const float *d_src, int n, size_t src_plane_stride_by
                            size_t variant_plane_stride_bytes, void *hip_stream);
 int w2xc_tta_gather_device(const float *d_up, const float *d_tr, size_t variant_plane_stride_bytes, int n, int w, int h, float *d_dst,
                            size_t dst_plane_stride_bytes, size_t dst_stride_bytes, void *hip_stream);
+/* (0.4.1.6.3) The two blocks with an interleaved uint8 image at their outer side -- what the RGBA TTA calls run on their RGB and head routes.
+ * spread_u8: n images of w x h (pixels px_bytes = 3 or 4 bytes, rows stride_bytes >= px_bytes w apart, images image_stride_bytes apart) -> the 8 variants of
+ *   their 3 n planes, in exactly the layout and with exactly the floats of w2xc_u8_to_rgb_device followed by w2xc_tta_spread_device with 3 n planes: source
+ *   plane 3 i + c, c = 0 .. 2, is (float)byte * (float)(1.0 / 255.0) of byte ch0 + c * ch_step of each pixel of image i.  (ch0, ch_step) = (0, 1): the colour
+ *   of RGB or RGBA pixels; (3, 0) with 4-byte pixels: the grey image (A, A, A) without building it.
+ * gather_u8: 8 m result planes in the gather's layout, m = planes_per_image * n, the upright ones w x h -> for image i and c in [0, n_ch), byte byte0 + c of
+ *   each px_bytes-wide pixel = saturate(rint(255 x)) (half to even, as w2xc_rgb_to_u8_device) of w2xc_tta_gather_device's sum x for plane
+ *   planes_per_image * i + first_plane + c.  Bytes not named are not written -- byte stores, no pixel is read --, nor are bytes of a row behind px_bytes * w: two
+ *   gathers into different bytes of the same pixels may be in flight in either order.  (3, 0, 3) into bytes 0 .. 2: colour; (3, 1, 1) or (1, 0, 1) into byte 3: alpha.
+ * W2XC_ERR_ARG before a device is touched: null pointers, n < 1, sizes < 1, strides below a row (an image stride below an image where n > 1), a variant plane
+ * stride below 4 w h or no multiple of 4, px_bytes outside {3, 4}, a selected byte outside the pixel (ch0, ch_step < 0 or ch0 + 2 ch_step >= px_bytes; byte0 < 0,
+ * n_ch < 1 or byte0 + n_ch > px_bytes), selected planes outside the image (first_plane < 0 or first_plane + n_ch > planes_per_image), variant groups that overlap
+ * each other, the source or the destination. */
+int w2xc_tta_spread_u8_device(const unsigned char *d_src, int n, size_t image_stride_bytes, size_t stride_bytes, int px_bytes, int ch0, int ch_step, int w, int h,
+                              float *d_up, float *d_tr, size_t variant_plane_stride_bytes, void *hip_stream);
+int w2xc_tta_gather_u8_device(const float *d_up, const float *d_tr, size_t variant_plane_stride_bytes, int n, int planes_per_image, int first_plane, int n_ch,
+                              int w, int h, unsigned char *d_dst, size_t image_stride_bytes, size_t stride_bytes, int px_bytes, int byte0, void *hip_stream);
 
 /* the building blocks on contiguous float planes (device pointers): main.cpp:144 on one plane, :75-76, :171-172 */
 int w2xc_resize2x_cubic_device(const float *d_src, int w, int h, float *d_dst, void *hip_stream);

@@ -14,11 +14,13 @@ w2xc_process_image_rgba_u8_ex on the route of the models -- the colour bled unde
 RGBA; several such inputs are grouped by image size like the opaque ones, and a group of two or more is ONE w2xc_process_image_rgba_u8_batch call.  Every
 other input goes exactly as before, the batch grouping included.
 Extension: -t/--tta 1 = test-time augmentation, the --tta of later upstream versions: every model pass on the 8 flips / transposes of the image, averaged
-(w2xc_process_image_[rgb_]u8[_batch]_tta; 8x the CNN work), on both routes and for grouped inputs.  The RGBA call has no TTA form: with an input that would
-take it, --tta 1 exits with a message before anything is converted.
+(w2xc_process_image_[rgb_]u8[_batch]_tta; 8x the CNN work), on both routes and for grouped inputs.  With an input that would take the RGBA call, --tta 1
+alone exits with a message before anything is converted; --tta 1 --tta_alpha 1 opts in: such inputs go to the TTA forms of the RGBA calls
+(w2xc_process_image_rgba_u8[_up2x]_batch_tta: colour AND alpha through 8 variants per pass), one call per size group (alpha_tta_routes).
 Extension: upconv scale models (upconv_7: the model enlarges by itself).  The RGB route; a size group of two or more opaque inputs, and every input under
 --tta 1, is ONE w2xc_process_image_rgb_u8_up2x_batch call (head_routes), an input alone its single-image call.  Inputs with transparency go to
-w2xc_process_image_rgba_u8_up2x_batch, one call per size group (head_alpha_routes; a file alone is a batch of one); with --tta 1 they stay check_tta's refusal."""
+w2xc_process_image_rgba_u8_up2x_batch, one call per size group (head_alpha_routes; a file alone is a batch of one); with --tta 1 they stay check_tta's refusal
+unless --tta_alpha 1 is given."""
 import argparse
 import math
 import os
@@ -92,11 +94,21 @@ def wants_alpha(arr):
     return arr.ndim == 3 and arr.shape[2] == 4 and bool((arr[:, :, 3] < 255).any())
 
 
-def check_tta(tta, alpha_files):
-    """--tta 1 with inputs that take the RGBA call (`alpha_files`: their names): a SystemExit with a message; everything else passes"""
-    if tta and alpha_files:
-        raise SystemExit("--tta 1 is not available for images with transparency (%s): the RGBA call has no TTA form; convert them with --tta 0 or "
-                         "flatten the alpha channel first" % ", ".join(alpha_files))
+def check_tta(tta, alpha_files, tta_alpha=0):
+    """--tta 1 with inputs that take the RGBA call (`alpha_files`: their names) and without --tta_alpha 1: a SystemExit with a message; everything else passes"""
+    if tta and alpha_files and not tta_alpha:
+        raise SystemExit("--tta 1 is not applied to images with transparency (%s) by default: alpha would go through 8 variants per pass too; add "
+                         "--tta_alpha 1 to run them through the TTA form of the RGBA call, convert them with --tta 0 or flatten the alpha channel first"
+                         % ", ".join(alpha_files))
+
+
+def alpha_tta_routes(head, alpha_groups):
+    """How the inputs with transparency run under --tta 1 --tta_alpha 1: [(call, [files]), ...], ONE call per size group (`alpha_groups`: lists of names, one
+    per image size) in the order given, a file alone a batch of one -- call = "rgba_up2x_batch_tta" for an upconv scale model (head_alpha_routes' grouping),
+    "rgba_batch_tta" for Y and RGB models.  Pure: no file is opened."""
+    if head:
+        return [(call + "_tta", files) for call, files in head_alpha_routes(alpha_groups)]
+    return [("rgba_batch_tta", list(g)) for g in alpha_groups if g]
 
 
 def check_head(head, tta, alpha_files, groups):
@@ -128,7 +140,7 @@ def head_routes(tta, alpha_files, groups):
 def head_alpha_routes(alpha_groups):
     """How the inputs with transparency of an upconv scale model run: [("rgba_up2x_batch", [files]), ...], ONE w2xc_process_image_rgba_u8_up2x_batch call per
     size group (`alpha_groups`: lists of names, one per image size) in the order given -- a file alone is a batch of one.  Pure: no file is opened.
-    (--tta 1 never gets here: check_tta.)"""
+    (--tta 1 never gets here: check_tta, or with --tta_alpha 1 alpha_tta_routes.)"""
     return [("rgba_up2x_batch", list(g)) for g in alpha_groups if g]
 
 
@@ -154,6 +166,8 @@ def build_parser():
                     help="engine arithmetic for the CNN layers (extension; default fp32)")
     # not a reference flag in v1: later upstream versions have it as --tta
     ap.add_argument("-t", "--tta", type=int, default=0, choices=[0, 1], help="test-time augmentation: 8 flips / transposes per model pass, averaged (extension; 8x the time)")
+    ap.add_argument("--tta_alpha", type=int, default=0, choices=[0, 1],
+                    help="with --tta 1: also run images with transparency, colour and alpha, through test-time augmentation (extension; default 0 = refuse them)")
     return ap
 
 
@@ -188,7 +202,7 @@ def main(argv=None):
         return np.ascontiguousarray(im if rgb else im[:, :, ::-1])   # Y route: cv::imread(IMREAD_COLOR)'s BGR order (Q3); RGB models take RGB as it is
     images = [load(f) for f in args.input_file]
     opaque = [(f, im) for f, im in zip(args.input_file, images) if im.shape[2] == 3]
-    check_tta(args.tta, [f for f, im in zip(args.input_file, images) if im.shape[2] == 4])
+    check_tta(args.tta, [f for f, im in zip(args.input_file, images) if im.shape[2] == 4], args.tta_alpha)
     head = bool(scale is not None and iterations and scale.has_head)   # (an upconv model: the RGB route's single-image call, passed through as it is)
     # (the transparent inputs of a head model have a call of their own, head_alpha_routes below: head_routes sees the opaque ones alone)
     routes = head_routes(args.tta, [],
@@ -205,8 +219,13 @@ def main(argv=None):
         opts = w2xc.make_opts(precision=prec)      # always explicit: an explicit --precision beats the W2XC_PRECISION env default
         alpha = {f: im for f, im in zip(args.input_file, images) if im.shape[2] == 4}
         alpha_sized = [(f, (im.shape[1], im.shape[0])) for f, im in alpha.items()]
-        singles, batches = ([], []) if head else group_alpha(alpha_sized, args.mode, args.noise_level, args.scale_ratio)
-        if head:   # (an upconv scale model: the RGBA head call per size group)
+        alpha_groups = [files for _, files, _ in group_inputs(alpha_sized, args.mode, args.noise_level, args.scale_ratio)]
+        singles, batches = ([], []) if head or args.tta else group_alpha(alpha_sized, args.mode, args.noise_level, args.scale_ratio)
+        if args.tta:   # (--tta_alpha 1, or there are no such inputs -- check_tta: the TTA form of the RGBA call of the models, one call per size group)
+            for call, files in alpha_tta_routes(head, alpha_groups):
+                fn = w2xc.process_image_rgba_u8_up2x_batch if call == "rgba_up2x_batch_tta" else w2xc.process_image_rgba_u8_batch
+                outs.update(zip(files, fn([alpha[f] for f in files], noise, scale if iterations else None, iterations, opts, shrink, tta=True)))
+        elif head:   # (an upconv scale model: the RGBA head call per size group)
             for _, files in head_alpha_routes([files for _, files, _ in group_inputs(alpha_sized, args.mode, args.noise_level, args.scale_ratio)]):
                 outs.update(zip(files, w2xc.process_image_rgba_u8_up2x_batch([alpha[f] for f in files], noise, scale, iterations, opts, shrink)))
         for f in singles:

@@ -124,6 +124,12 @@ def _load():
         "w2xc_process_image_rgb_u8_up2x_batch": (ci, [vp, vp, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, ci, C.c_double, C.POINTER(Opts), ci]),
         "w2xc_process_image_rgba_u8_up2x_batch_device": (ci, [vp, vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, ci, C.c_double, ci, vp, C.POINTER(Opts)]),
         "w2xc_process_image_rgba_u8_up2x_batch": (ci, [vp, vp, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, ci, C.c_double, ci, C.POINTER(Opts)]),
+        "w2xc_process_image_rgba_u8_batch_tta_device": (ci, [vp, vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, ci, C.c_double, ci, vp, C.POINTER(Opts), ci]),
+        "w2xc_process_image_rgba_u8_batch_tta": (ci, [vp, vp, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, ci, C.c_double, ci, C.POINTER(Opts), ci]),
+        "w2xc_process_image_rgba_u8_up2x_batch_tta_device": (ci, [vp, vp, ci, fp, cs, cs, ci, ci, fp, cs, cs, ci, C.c_double, ci, vp, C.POINTER(Opts), ci]),
+        "w2xc_process_image_rgba_u8_up2x_batch_tta": (ci, [vp, vp, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, ci, C.c_double, ci, C.POINTER(Opts), ci]),
+        "w2xc_tta_spread_u8_device": (ci, [fp, ci, cs, cs, ci, ci, ci, ci, ci, fp, fp, cs, vp]),
+        "w2xc_tta_gather_u8_device": (ci, [fp, fp, cs, ci, ci, ci, ci, ci, ci, fp, cs, cs, ci, ci, vp]),
         "w2xc_u8_to_rgb_device": (ci, [fp, cs, ci, ci, fp, fp, fp, vp]),
         "w2xc_rgb_to_u8_device": (ci, [fp, fp, fp, ci, ci, fp, cs, vp]),
         "w2xc_process_image_u8_device": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, vp, C.POINTER(Opts)]),
@@ -890,54 +896,79 @@ def tta_gather_device(d_up, d_tr, variant_plane_stride_bytes, n, w, h, d_dst, ds
                                        dst_plane_stride_bytes, dst_stride_bytes, C.c_void_p(stream)))
 
 
+def tta_spread_u8_device(d_src, n, image_stride_bytes, stride_bytes, px_bytes, ch0, ch_step, w, h, d_up, d_tr, variant_plane_stride_bytes, stream=0):
+    """n interleaved uint8 images of w x h (pixels px_bytes apart) -> the 8 variants of their 3 n planes, plane 3 i + c = byte ch0 + c * ch_step of each
+    pixel / 255: the floats and the layout of u8_to_rgb_device + tta_spread_device on 3 n planes (w2xc_tta_spread_u8_device)."""
+    _check(_lib.w2xc_tta_spread_u8_device(C.c_void_p(d_src), n, image_stride_bytes, stride_bytes, px_bytes, ch0, ch_step, w, h, C.c_void_p(d_up),
+                                          C.c_void_p(d_tr), variant_plane_stride_bytes, C.c_void_p(stream)))
+
+
+def tta_gather_u8_device(d_up, d_tr, variant_plane_stride_bytes, n, planes_per_image, first_plane, n_ch, w, h, d_dst, image_stride_bytes, stride_bytes,
+                         px_bytes, byte0, stream=0):
+    """8 planes_per_image n result planes in tta_spread_device's layout -> bytes byte0 .. byte0 + n_ch - 1 of the px_bytes-wide pixels of n images at d_dst:
+    saturate(rint(255 x)) of tta_gather_device's sum for planes first_plane .. of each image; no other byte is written (w2xc_tta_gather_u8_device)."""
+    _check(_lib.w2xc_tta_gather_u8_device(C.c_void_p(d_up), C.c_void_p(d_tr), variant_plane_stride_bytes, n, planes_per_image, first_plane, n_ch, w, h,
+                                          C.c_void_p(d_dst), image_stride_bytes, stride_bytes, px_bytes, byte0, C.c_void_p(stream)))
+
+
 # ---- RGBA images: alpha through the scale model, the colour bled under the transparent pixels ----
-def process_image_rgba_u8(img, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, bleed_passes=-1):
+def process_image_rgba_u8(img, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, bleed_passes=-1, tta=False):
     """An h x w x 4 uint8 image (three colour channels in the order the 3-channel call of the route expects, alpha last) through Y models or RGB models
     -- the models choose the route (w2xc_process_image_rgba_u8_ex): the colour bytes are those of process_image_u8 / process_image_rgb_u8 on the image
-    after `bleed_passes` passes of the colour bleed (< 0: the layer counts of the models given; 0: none), alpha goes through the scale model."""
+    after `bleed_passes` passes of the colour bleed (< 0: the layer counts of the models given; 0: none), alpha goes through the scale model.
+    tta: test-time augmentation -- the n = 1 form of w2xc_process_image_rgba_u8_batch_tta."""
+    if tta:
+        return process_image_rgba_u8_batch([img], noise, scale, iterations, opts, shrink_ratio, bleed_passes, tta=tta)[0]
     return _image_host(_lib.w2xc_process_image_rgba_u8_ex, "process_image_rgba_u8", img, 4, noise, scale, iterations, opts, shrink_ratio,
                        extra=(int(bleed_passes),))
 
 
 def process_image_rgba_u8_device(d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, noise=None, scale=None, iterations=0, shrink_ratio=0.0,
-                                 bleed_passes=-1, stream=0, opts=None):
-    """Device-pointer form (w2xc_process_image_rgba_u8_ex_device): w x h x 4 uint8 at d_in, the result at d_out.  Asynchronous on `stream`."""
+                                 bleed_passes=-1, stream=0, opts=None, tta=False):
+    """Device-pointer form (w2xc_process_image_rgba_u8_ex_device): w x h x 4 uint8 at d_in, the result at d_out.  Asynchronous on `stream`.
+    tta: the n = 1 form of w2xc_process_image_rgba_u8_batch_tta_device."""
+    if tta:
+        return process_image_rgba_u8_batch_device(1, d_in, 0, in_stride_bytes, w, h, d_out, 0, out_stride_bytes, noise, scale, iterations, shrink_ratio,
+                                                  bleed_passes, stream, opts, tta=tta)
     _check(_lib.w2xc_process_image_rgba_u8_ex_device(*_handles(noise, scale), C.c_void_p(d_in), in_stride_bytes, w, h,
                                                      C.c_void_p(d_out), out_stride_bytes, iterations, float(shrink_ratio), int(bleed_passes),
                                                      C.c_void_p(stream), C.byref(opts) if opts is not None else None))
 
 
-def process_image_rgba_u8_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, bleed_passes=-1, out=None):
+def process_image_rgba_u8_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, bleed_passes=-1, out=None, tta=False):
     """n RGBA images of one size in one call (w2xc_process_image_rgba_u8_batch): `imgs` is an (n, h, w, 4) uint8 array or a sequence of equal-shape
     (h, w, 4) uint8 arrays; returns an (n, H, W, 4) uint8 array (or fills `out`, such an array).  Image i is byte-identical to
-    process_image_rgba_u8(imgs[i], ...) with the same arguments."""
-    return _image_batch(_lib.w2xc_process_image_rgba_u8_batch, "process_image_rgba_u8_batch", imgs, noise, scale, iterations, opts, shrink_ratio, out,
-                        channels=4, extra=(int(bleed_passes),))
+    process_image_rgba_u8(imgs[i], ...) with the same arguments.  tta: every CNN pass of colour and alpha is its TTA pass
+    (w2xc_process_image_rgba_u8_batch_tta)."""
+    entry, tail = _tta_entry("w2xc_process_image_rgba_u8_batch", tta)
+    return _image_batch(entry, "process_image_rgba_u8_batch", imgs, noise, scale, iterations, opts, shrink_ratio, out, tail, channels=4,
+                        extra=(int(bleed_passes),))
 
 
 def process_image_rgba_u8_batch_device(n, d_in, in_image_stride_bytes, in_stride_bytes, w, h, d_out, out_image_stride_bytes, out_stride_bytes,
-                                       noise=None, scale=None, iterations=0, shrink_ratio=0.0, bleed_passes=-1, stream=0, opts=None):
-    """Device-pointer batch of RGBA images (w2xc_process_image_rgba_u8_batch_device): n images of w x h x 4 uint8 at d_in + i * in_image_stride_bytes, the
-    outputs at d_out + i * out_image_stride_bytes.  Asynchronous on `stream`."""
-    _check(_lib.w2xc_process_image_rgba_u8_batch_device(*_handles(noise, scale), n, C.c_void_p(d_in), in_image_stride_bytes, in_stride_bytes, w, h,
-                                                        C.c_void_p(d_out), out_image_stride_bytes, out_stride_bytes, iterations, float(shrink_ratio),
-                                                        int(bleed_passes), C.c_void_p(stream), C.byref(opts) if opts is not None else None))
+                                       noise=None, scale=None, iterations=0, shrink_ratio=0.0, bleed_passes=-1, stream=0, opts=None, tta=False):
+    """Device-pointer batch of RGBA images (w2xc_process_image_rgba_u8_batch_device / _batch_tta_device): n images of w x h x 4 uint8 at
+    d_in + i * in_image_stride_bytes, the outputs at d_out + i * out_image_stride_bytes.  Asynchronous on `stream`."""
+    entry, tail = _tta_entry("w2xc_process_image_rgba_u8_batch_device", tta)
+    _check(entry(*_handles(noise, scale), n, C.c_void_p(d_in), in_image_stride_bytes, in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes,
+                 out_stride_bytes, iterations, float(shrink_ratio), int(bleed_passes), C.c_void_p(stream), C.byref(opts) if opts is not None else None, *tail))
 
 
-def process_image_rgba_u8_up2x_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, bleed_passes=-1, out=None):
+def process_image_rgba_u8_up2x_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, bleed_passes=-1, out=None, tta=False):
     """n >= 1 RGBA images of one size with an upconv head model as `scale` (w2xc_process_image_rgba_u8_up2x_batch); arguments and checks as
     process_image_rgba_u8_batch.  The colour bytes of image i are those of process_image_rgb_u8 on the bled image, alpha is channel 1 of the scale-only
-    call on (A, A, A); one image is the single-image form."""
-    return _image_batch(_lib.w2xc_process_image_rgba_u8_up2x_batch, "process_image_rgba_u8_up2x_batch", imgs, noise, scale, iterations, opts, shrink_ratio,
-                        out, channels=4, extra=(int(bleed_passes),))
+    call on (A, A, A); one image is the single-image form.  tta: w2xc_process_image_rgba_u8_up2x_batch_tta."""
+    entry, tail = _tta_entry("w2xc_process_image_rgba_u8_up2x_batch", tta)
+    return _image_batch(entry, "process_image_rgba_u8_up2x_batch", imgs, noise, scale, iterations, opts, shrink_ratio, out, tail, channels=4,
+                        extra=(int(bleed_passes),))
 
 
 def process_image_rgba_u8_up2x_batch_device(n, d_in, in_image_stride_bytes, in_stride_bytes, w, h, d_out, out_image_stride_bytes, out_stride_bytes,
-                                            noise=None, scale=None, iterations=0, shrink_ratio=0.0, bleed_passes=-1, stream=0, opts=None):
-    """Device-pointer form (w2xc_process_image_rgba_u8_up2x_batch_device); arguments as process_image_rgba_u8_batch_device."""
-    _check(_lib.w2xc_process_image_rgba_u8_up2x_batch_device(*_handles(noise, scale), n, C.c_void_p(d_in), in_image_stride_bytes, in_stride_bytes, w, h,
-                                                             C.c_void_p(d_out), out_image_stride_bytes, out_stride_bytes, iterations, float(shrink_ratio),
-                                                             int(bleed_passes), C.c_void_p(stream), C.byref(opts) if opts is not None else None))
+                                            noise=None, scale=None, iterations=0, shrink_ratio=0.0, bleed_passes=-1, stream=0, opts=None, tta=False):
+    """Device-pointer form (w2xc_process_image_rgba_u8_up2x_batch_device / _batch_tta_device); arguments as process_image_rgba_u8_batch_device."""
+    entry, tail = _tta_entry("w2xc_process_image_rgba_u8_up2x_batch_device", tta)
+    _check(entry(*_handles(noise, scale), n, C.c_void_p(d_in), in_image_stride_bytes, in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes,
+                 out_stride_bytes, iterations, float(shrink_ratio), int(bleed_passes), C.c_void_p(stream), C.byref(opts) if opts is not None else None, *tail))
 
 
 def bleed_rgba_u8_device(d_in, in_stride_bytes, w, h, passes, d_out_rgb, out_stride_bytes, stream=0):

@@ -6,6 +6,7 @@
 // template k_px holds the loops over both, and launch_px the grid and the launch.  A stage is its kernel's by-value argument: img comes from blockIdx.y --
 // uniform per workgroup -- and moves only the stage's 64-bit base pointers by img x stride.  One image is n = 1.
 #include "w2xc_kernels.h"
+#include "w2xc_tta_px.h"   // clampi, to_u8: shared with w2xc_tta_u8.hip
 
 // blockIdx.y strides over the n images / planes (more than 65535 take further trips), blockIdx.x x 256 threads over the `total` elements of each.
 // (Every stage has a batch form: the register cost of the loop nest for the stages that once ran one image only is in profiles/color_stage_resources.txt.)
@@ -22,11 +23,6 @@ template <class Stage> static hipError_t launch_px(const Stage &s, long long tot
     hipLaunchKernelGGL((k_px<Stage>), grid, dim3(256), 0, st, s, total, n);
     return hipGetLastError();
 }
-
-static __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// convertTo(CV_8U, 255) = saturate(cvRound(x * 255)): round half to even
-static __device__ __forceinline__ unsigned char to_u8(float x) { return (unsigned char)clampi(__float2int_rn(x * 255.0f), 0, 255); }
 
 // element q of rows of w: its row and column
 struct RowCol { int r, c; };

@@ -24,8 +24,9 @@
 //   w2xc_filter.cpp         Model::filter at the host / device boundary (src/modelHandler.cpp:26-72)
 //   w2xc_image.cpp          N2: the CLI's image pipeline around the plane conversion (main.cpp:74-172): one pipeline for Y models and one for RGB models, each
 //                           for S images of one size; the single-image, batch and RGBA entry points around them
-//                           and test-time augmentation: tta_pass (spread -> the CNN on the 8 variants -> gather; kernels in w2xc_tta.hip), which both pipelines
-//                           and the TTA plane calls share
+//                           and test-time augmentation: tta_pass (spread -> the CNN on the 8 variants -> gather; kernels in w2xc_tta.hip, and -- the uint8
+//                           image at the outer side: the RGB and head routes of the RGBA TTA calls -- w2xc_tta_u8.hip), which both pipelines and the TTA
+//                           plane calls share
 #pragma once
 #include "../../include/w2xc_hip.h"
 
@@ -405,7 +406,9 @@ typedef Planes<float> PlanesOut;
 //   ROWS_U8_DST_PX4  the pixels of `out` are 4 bytes apart (a head model's last layer only): the three channels go to bytes 0 .. 2 of RGBA pixels
 //   ROWS_U8_DST_A    channel 1 only (a three-plane head only): the alpha head (W2XC_K_UPCONV_A_U8) writes ONE byte per pixel, at out.p -- the caller points it
 //                    at byte 3 of the first pixel
-enum { ROWS_U8_SRC = 1, ROWS_U8_DST = 2, ROWS_U8_SRC_A = 4, ROWS_U8_DST_PX4 = 8, ROWS_U8_DST_A = 16 };
+// And one form with FLOAT planes (the alpha pass of the RGBA TTA call for head models):
+//   ROWS_F32_DST_A   channel 1 only of a three-plane head, as ONE float plane at out.p (W2XC_K_UPCONV_A: the alpha head's image and bias[1] with the float sink)
+enum { ROWS_U8_SRC = 1, ROWS_U8_DST = 2, ROWS_U8_SRC_A = 4, ROWS_U8_DST_PX4 = 8, ROWS_U8_DST_A = 16, ROWS_F32_DST_A = 32 };
 // One run_rows call: output rows [ra, rb) of convertWithModels on a plane of plane_h rows, w wide.
 struct RowsCall {
     // the source view: n_in planar input planes in.ps floats apart, of which `in` holds rows [view_y0, view_y0 + view_h) -- every row in [ra - n, rb + n)

@@ -92,12 +92,12 @@ inline size_t tta_variant_floats(int w, int h, int iterations)
 {
     return iterations > 0 ? tta_pass_floats(w << (iterations - 1), h << (iterations - 1), 1) : tta_pass_floats(w, h, 0);
 }
-// (tta: the Y planes go through the CNN -- one per image; never with alpha)
+// (tta: the Y planes go through the CNN -- one per image, with alpha its alpha plane beside it in the scale passes)
 inline size_t image_aux_floats(int w, int h, int iterations, double shrink, bool alpha = false, bool tta = false)
 {
     const size_t ya = alpha ? 2 : 1;
     size_t need = (2 * ya + 2) * plane_floats(w, h);
-    if (tta) need += tta_variant_floats(w, h, iterations);
+    if (tta) need += ya * tta_variant_floats(w, h, iterations);
     for (int i = 1; i <= iterations; i++) need += (ya + 2) * plane_floats(w << i, h << i);
     int fw, fh;
     final_size(w, h, iterations, shrink, &fw, &fh);

@@ -35,6 +35,9 @@ struct ImageCall {
     // w2xc_process_image_rgb_u8_up2x_batch[_device] and w2xc_process_image_rgba_u8_up2x_batch[_device]: the scale model is an upconv head model (and must be
     // one), also under TTA
     bool up2x = false;
+    // the RGBA TTA calls, RGB and head routes, w2xc_opts.fusion other than W2XC_FUSION_OFF (check_rgba_call sets it): the first spread of a sequence reads the
+    // uint8 image itself, the gather behind a last scale pass without a shrink writes the caller's pixels (w2xc_tta_u8.hip; rgb_plan)
+    bool tta_u8 = false;
     ImageCall(w2xc_model *noise, w2xc_model *scale, int w_, int h_, int iterations_, double shrink_, void *hip_stream, const w2xc_opts *opts, int tta_ = 0)
         : mn(noise), msc(scale), w(w_), h(h_), iterations(iterations_), shrink(shrink_), st((hipStream_t)hip_stream), o(resolve_opts(opts)), tta_arg(tta_),
           tta(tta_ == 1) {}
@@ -55,8 +58,19 @@ struct TtaPass {
     int up, nin, nout;
     bool rows;
     bool head = false;
+    bool head_a = false;   // head, nout = 1: the head launches compute channel 1 alone, as one float plane (ROWS_F32_DST_A)
 };
-int tta_pass(const TtaPass &t, int runs, PlanesIn src, int w, int h, PlanesOut dst, float *var, hipStream_t st, const w2xc_opts &o)
+// The uint8 ends of a pass (nin = 3; `runs` = images): src -- the spread reads n interleaved images itself, `src` of tta_pass is not used; dst -- the gather
+// writes n_ch bytes of each pixel, from the result planes first .. first + n_ch - 1 of each image, `dst` of tta_pass is not used.
+struct TtaU8 {
+    const unsigned char *src = nullptr;
+    size_t src_img = 0, src_row = 0;
+    int px = 3, ch0 = 0, ch_step = 1;
+    unsigned char *dst = nullptr;   // (the first byte the gather writes: byte0 is in the pointer)
+    size_t dst_img = 0, dst_row = 0;
+    int dpx = 4, n_ch = 3, first = 0;
+};
+int tta_pass(const TtaPass &t, int runs, PlanesIn src, int w, int h, PlanesOut dst, float *var, hipStream_t st, const w2xc_opts &o, const TtaU8 *u8 = nullptr)
 {
     const int sc = t.head ? 1 : t.up;   // the pass's enlargement
     const int W = w << sc, H = h << sc, ni = runs * t.nin, no = runs * t.nout;
@@ -64,7 +78,8 @@ int tta_pass(const TtaPass &t, int runs, PlanesIn src, int w, int h, PlanesOut d
     // the four groups of variant planes: 4 ni upright and 4 ni transposed (h x w) in, 4 no and 4 no out
     const PlanesOut in_up{var, (size_t)w, ps}, in_tr{in_up.p + 4 * (size_t)ni * ps, (size_t)h, ps};
     const PlanesOut out_up{in_tr.p + 4 * (size_t)ni * ps, (size_t)W, PS}, out_tr{out_up.p + 4 * (size_t)no * PS, (size_t)H, PS};
-    HIP_TRY(w2xc_launch_tta_spread(src.p, src.ps, (long long)src.rs, w, h, in_up.p, in_tr.p, ps, ni, st));
+    if (u8 && u8->src) HIP_TRY(w2xc_launch_tta_spread_u8(u8->src, u8->src_img, u8->src_row, u8->px, u8->ch0, u8->ch_step, w, h, in_up.p, in_tr.p, ps, runs, st));
+    else HIP_TRY(w2xc_launch_tta_spread(src.p, src.ps, (long long)src.rs, w, h, in_up.p, in_tr.p, ps, ni, st));
     if (!t.rows) {
         if (w == h) {
             if (int rc = run_batch(t.m, t.cm, 8 * ni, t.up, in_up, w, h, out_up, st, o)) return rc;
@@ -76,7 +91,7 @@ int tta_pass(const TtaPass &t, int runs, PlanesIn src, int w, int h, PlanesOut d
         // variant (k, run r) is "image" (k & 3) runs + r of its group: nin planes ps apart in, nout planes PS apart out.  Where the model's chain has batch
         // kernels (batch_eligible) a group is ONE run_batch_planes launch sequence, otherwise that call is the single-image run_rows sequence per variant and run
         const auto group = [&](int nv, const PlanesOut &in, int vw, int vh, const PlanesOut &out) {
-            const BatchIO io = {in, t.nin * ps, t.nin, out, t.nout * PS, 0};
+            const BatchIO io = {in, t.nin * ps, t.nin, out, t.nout * PS, t.head_a ? ROWS_F32_DST_A : 0};
             return run_batch_planes(t.m, t.cm, nv * runs, t.up, io, vw, vh, st, o);
         };
         if (w == h) {
@@ -86,7 +101,8 @@ int tta_pass(const TtaPass &t, int runs, PlanesIn src, int w, int h, PlanesOut d
             if (int rc = group(4, in_tr, h, w, out_tr)) return rc;
         }
     }
-    HIP_TRY(w2xc_launch_tta_gather(out_up.p, out_tr.p, PS, W, H, dst.p, dst.ps, (long long)dst.rs, no, st));
+    if (u8 && u8->dst) HIP_TRY(w2xc_launch_tta_gather_u8(out_up.p, out_tr.p, PS, W, H, u8->dst, u8->dst_img, u8->dst_row, u8->dpx, 0, u8->n_ch, t.nout, u8->first, runs, st));
+    else HIP_TRY(w2xc_launch_tta_gather(out_up.p, out_tr.p, PS, W, H, dst.p, dst.ps, (long long)dst.rs, no, st));
     return W2XC_OK;
 }
 
@@ -178,9 +194,10 @@ RgbPlan rgb_plan(const ImageCall &c)
 {
     RgbPlan R;
     const int passes = (c.mn ? 1 : 0) + c.iterations;
-    // (TTA: the mean is taken before the rounding, so the colour kernels run around float planes)
-    R.src_u8 = !c.tta && u8_source_layer(c.mn ? c.mn : c.msc, c.o);
-    R.dst_u8 = !c.tta && c.shrink == 0.0 && u8_sink_layer(c.iterations > 0 ? c.msc : c.mn, c.o);
+    // (TTA: the mean is taken before the rounding, so no LAYER takes the uint8 image; the RGBA TTA calls have the spread and the gather take it -- whatever
+    // the precision and the kernels -- the gather where the last pass is a scale pass with nothing behind it)
+    R.src_u8 = c.tta ? c.tta_u8 : u8_source_layer(c.mn ? c.mn : c.msc, c.o);
+    R.dst_u8 = c.tta ? c.tta_u8 && c.shrink == 0.0 && c.iterations > 0 : c.shrink == 0.0 && u8_sink_layer(c.iterations > 0 ? c.msc : c.mn, c.o);
     if (!R.src_u8) R.floats += 3 * plane_floats(c.w, c.h);
     for (int p = 1; p <= passes; p++) {
         const int lvl = p - (c.mn ? 1 : 0);   // the pass's output level: the noise pass stays on level 0
@@ -231,8 +248,16 @@ int process_rgb_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, s
         const int u8 = (from_u8 ? ROWS_U8_SRC | (ends & ROWS_U8_SRC_A) : 0) | (to_u8 ? ROWS_U8_DST | (ends & (ROWS_U8_DST_PX4 | ROWS_U8_DST_A)) : 0);
         float *nxt = nullptr;
         if (!to_u8) { nxt = base; base += 3 * (size_t)cap * ps2; }
-        if (c.tta) {   // (neither from_u8 nor to_u8: rgb_plan)
-            if (int rc = tta_pass(TtaPass{m, cm, up, 3, 3, true, head}, S, {cur, (size_t)cw, ps}, cw, ch, {nxt, (size_t)nw, ps2}, var, c.st, c.o)) return rc;
+        if (c.tta) {
+            // (from_u8 / to_u8: the RGBA TTA calls.  ends as without TTA, but ROWS_U8_SRC_A: `in` is the RGBA image itself, alpha is byte 3 of its pixels;
+            // ROWS_U8_DST_A: `out` points at byte 3, which gets channel 1 -- from a head the one plane its alpha launches compute)
+            TtaU8 u;
+            if (from_u8) { u.src = in.p; u.src_img = in.img; u.src_row = in.row; }
+            if (from_u8 && (ends & ROWS_U8_SRC_A)) { u.px = 4; u.ch0 = 3; u.ch_step = 0; }
+            const bool one = to_u8 && (ends & ROWS_U8_DST_A), head_a = one && head;
+            if (to_u8) { u.dst = out.p; u.dst_img = out.img; u.dst_row = out.row; u.n_ch = one ? 1 : 3; u.first = one && !head_a ? 1 : 0; }
+            const TtaPass t{m, cm, up, 3, head_a ? 1 : 3, true, head, head_a};
+            if (int rc = tta_pass(t, S, {cur, (size_t)cw, ps}, cw, ch, {nxt, (size_t)nw, ps2}, var, c.st, c.o, &u)) return rc;
         } else if (S >= 2) {
             // ONE run_batch_planes for the sub-batch (one launch per layer where the chain has batch kernels): image i's three planes 3 ps on, or -- the uint8
             // forms -- the caller's images themselves: strides in bytes
@@ -398,6 +423,10 @@ int check_image_batch_args(bool rgb, ImageCall &c, int n, size_t in_stride, size
 //   fuse_src  layer 1 of the alpha pass reads the caller's alpha bytes itself: no grey images, no AlphaToGrey launch
 //   fuse_dst  the colour pass's head writes bytes 0 .. 2 of the caller's output pixels and the alpha pass's head -- the alpha head, channel 1 alone -- byte 3:
 //             no res and ares images, no merge launch
+// Under TTA (w2xc_process_image_rgba_u8[_up2x]_batch_tta*; c.tta) every CNN pass of the sequence is its TTA pass.  Y route: the alpha planes ride in the scale
+// pass's tta_pass.  RGB and head routes, c.tta_u8: the same two flags, for every model, now the spread's and the gather's (w2xc_tta_u8.hip) -- fuse_src: the
+// alpha sequence's first spread reads the caller's alpha bytes (and the colour sequence's the bled image: rgb_plan); fuse_dst: the gathers behind the last scale
+// pass write the caller's pixels, the alpha one from channel 1 (a head: from the one plane its alpha launches compute, ROWS_F32_DST_A).
 struct RgbaPlan {
     bool rgb = false;
     bool fuse_src = false, fuse_dst = false;
@@ -445,7 +474,7 @@ int plan_rgba(const ImageCall &c, int bleed_passes, RgbaPlan *R)
     R->bled = align256((size_t)c.w * 3 * c.h);
     if (w2xc_bleed_stamps((int)P)) R->stamp = align256((size_t)c.w * 2 * c.h);
     const bool ride = c.iterations > 0;   // alpha goes through the scale model
-    if (R->rgb && ride && c.msc->has_head()) {
+    if (R->rgb && ride && (c.msc->has_head() || c.tta)) {   // (under TTA the ends are the spread's and the gather's: every model)
         R->fuse_src = rgb_plan(alpha_call(c)).src_u8;
         R->fuse_dst = rgb_plan(c).dst_u8;   // (the colour pass and the alpha pass end in the same layer under the same options)
     }
@@ -457,7 +486,7 @@ int plan_rgba(const ImageCall &c, int bleed_passes, RgbaPlan *R)
             if (!R->fuse_dst) R->ares = align256((size_t)c.fw * 3 * c.fh);
             R->floats = std::max(R->floats, rgb_plan(alpha_call(c)).floats);
         }
-    } else R->floats = image_aux_floats(c.w, c.h, c.iterations, c.shrink, ride);
+    } else R->floats = image_aux_floats(c.w, c.h, c.iterations, c.shrink, ride, c.tta);
     if (!ride && c.shrink > 0.0) R->floats = std::max(R->floats, plane_floats(c.w, c.h) + plane_floats(c.fw, c.fh));   // alpha as a plane and its shrunk plane
     // what one image takes: the float planes, alpha's among them, the uint8 images above, the 4-byte image in and out
     const size_t per = R->floats * sizeof(float) + R->bled + R->stamp + R->res + R->grey + R->ares + (size_t)c.w * 4 * c.h + (size_t)c.fw * 4 * c.fh;
@@ -481,7 +510,7 @@ int process_rgba_device(const RgbaPlan &R, const ImageCall &c, int S, int cap, U
         if (int rc = process_rgb_device(c, S, cap, bled, R.fuse_dst ? out : res, L.head, R.fuse_dst ? ROWS_U8_DST_PX4 : 0)) return rc;
         if (c.iterations > 0) {   // alpha = channel 1 of the scale-only call on (A, A, A)
             // fuse_src: layer 1 reads the alpha bytes where they are; fuse_dst: the alpha head computes channel 1 alone, into byte 3 of the caller's pixels
-            U8In grey{in.p + 3, in.img, in.row};
+            U8In grey{c.tta ? in.p : in.p + 3, in.img, in.row};   // (TTA: the spread selects the byte)
             if (!R.fuse_src) {
                 HIP_TRY(w2xc_launch_alpha_to_grey(in.p, in.img, in.row, w, h, a8 + L.grey, R.grey, rs, S, c.st));
                 grey = U8In{a8 + L.grey, R.grey, rs};
@@ -523,6 +552,7 @@ int check_rgba_call(ImageCall &c, size_t in_stride, size_t out_stride, int bleed
     int rc = check_process_args(c);
     if (rc) return rc;
     if ((rc = check_image_size(c, in_stride, out_stride, 4))) return rc;
+    c.tta_u8 = c.tta && c.o.fusion != W2XC_FUSION_OFF;
     return plan_rgba(c, bleed_passes, R);
 }
 int check_rgba_single(ImageCall &c, U8In in, U8Out out, int bleed_passes, RgbaPlan *R)
@@ -531,6 +561,7 @@ int check_rgba_single(ImageCall &c, U8In in, U8Out out, int bleed_passes, RgbaPl
     if (rc || (rc = check_image_args(c, in.p, in.row, out.p, out.row, 4))) return rc;
     if (ranges_overlap(in.p, image_extent(c.h, in.row, c.w, 4), out.p, image_extent(c.fh, out.row, c.fw, 4)))
         return fail(W2XC_ERR_ARG, "the output image overlaps the input image");
+    c.tta_u8 = c.tta && c.o.fusion != W2XC_FUSION_OFF;
     return plan_rgba(c, bleed_passes, R);
 }
 
@@ -911,41 +942,74 @@ try {
                         U8Out{out, 0, out_stride_bytes}, bleed_passes);
 } W2XC_CATCH_ALL
 
+int w2xc_process_image_rgba_u8_batch_tta_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in, size_t in_image_stride_bytes,
+                                                size_t in_stride_bytes, int w, int h, unsigned char *d_out, size_t out_image_stride_bytes, size_t out_stride_bytes,
+                                                int iterations, double shrink_ratio, int bleed_passes, void *hip_stream, const w2xc_opts *opts, int tta)
+try {
+    return rgba_batch_device(ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, hip_stream, opts, tta), n,
+                             U8In{d_in, in_image_stride_bytes, in_stride_bytes}, U8Out{d_out, out_image_stride_bytes, out_stride_bytes}, bleed_passes);
+} W2XC_CATCH_ALL
+
 int w2xc_process_image_rgba_u8_batch_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in, size_t in_image_stride_bytes,
                                             size_t in_stride_bytes, int w, int h, unsigned char *d_out, size_t out_image_stride_bytes, size_t out_stride_bytes,
                                             int iterations, double shrink_ratio, int bleed_passes, void *hip_stream, const w2xc_opts *opts)
+{
+    return w2xc_process_image_rgba_u8_batch_tta_device(noise_model, scale_model, n, d_in, in_image_stride_bytes, in_stride_bytes, w, h, d_out, out_image_stride_bytes,
+                                                       out_stride_bytes, iterations, shrink_ratio, bleed_passes, hip_stream, opts, 0);
+}
+
+int w2xc_process_image_rgba_u8_batch_tta(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes, int w,
+                                         int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio, int bleed_passes,
+                                         const w2xc_opts *opts, int tta)
 try {
-    return rgba_batch_device(ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, hip_stream, opts), n,
-                             U8In{d_in, in_image_stride_bytes, in_stride_bytes}, U8Out{d_out, out_image_stride_bytes, out_stride_bytes}, bleed_passes);
+    return rgba_batch_host(ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, nullptr, opts, tta), n, in, in_stride_bytes, out, out_stride_bytes,
+                           bleed_passes);
 } W2XC_CATCH_ALL
 
 int w2xc_process_image_rgba_u8_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes, int w, int h,
                                      unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio, int bleed_passes,
                                      const w2xc_opts *opts)
-try {
-    return rgba_batch_host(ImageCall(noise_model, scale_model, w, h, iterations, shrink_ratio, nullptr, opts), n, in, in_stride_bytes, out, out_stride_bytes,
-                           bleed_passes);
-} W2XC_CATCH_ALL
+{
+    return w2xc_process_image_rgba_u8_batch_tta(noise_model, scale_model, n, in, in_stride_bytes, w, h, out, out_stride_bytes, iterations, shrink_ratio, bleed_passes,
+                                                opts, 0);
+}
 
 // ---- ... with an upconv head model as scale model (n = 1: the single-image form, bands included) ----
+int w2xc_process_image_rgba_u8_up2x_batch_tta_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in,
+                                                     size_t in_image_stride_bytes, size_t in_stride_bytes, int w, int h, unsigned char *d_out,
+                                                     size_t out_image_stride_bytes, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                                     int bleed_passes, void *hip_stream, const w2xc_opts *opts, int tta)
+try {
+    ImageCall c(noise_model, scale_model, w, h, iterations, shrink_ratio, hip_stream, opts, tta);
+    c.up2x = true;
+    return rgba_batch_device(c, n, U8In{d_in, in_image_stride_bytes, in_stride_bytes}, U8Out{d_out, out_image_stride_bytes, out_stride_bytes}, bleed_passes);
+} W2XC_CATCH_ALL
+
 int w2xc_process_image_rgba_u8_up2x_batch_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *d_in, size_t in_image_stride_bytes,
                                                  size_t in_stride_bytes, int w, int h, unsigned char *d_out, size_t out_image_stride_bytes,
                                                  size_t out_stride_bytes, int iterations, double shrink_ratio, int bleed_passes, void *hip_stream,
                                                  const w2xc_opts *opts)
+{
+    return w2xc_process_image_rgba_u8_up2x_batch_tta_device(noise_model, scale_model, n, d_in, in_image_stride_bytes, in_stride_bytes, w, h, d_out,
+                                                            out_image_stride_bytes, out_stride_bytes, iterations, shrink_ratio, bleed_passes, hip_stream, opts, 0);
+}
+
+int w2xc_process_image_rgba_u8_up2x_batch_tta(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes,
+                                              int w, int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio,
+                                              int bleed_passes, const w2xc_opts *opts, int tta)
 try {
-    ImageCall c(noise_model, scale_model, w, h, iterations, shrink_ratio, hip_stream, opts);
+    ImageCall c(noise_model, scale_model, w, h, iterations, shrink_ratio, nullptr, opts, tta);
     c.up2x = true;
-    return rgba_batch_device(c, n, U8In{d_in, in_image_stride_bytes, in_stride_bytes}, U8Out{d_out, out_image_stride_bytes, out_stride_bytes}, bleed_passes);
+    return rgba_batch_host(c, n, in, in_stride_bytes, out, out_stride_bytes, bleed_passes);
 } W2XC_CATCH_ALL
 
 int w2xc_process_image_rgba_u8_up2x_batch(w2xc_model *noise_model, w2xc_model *scale_model, int n, const unsigned char *const *in, size_t in_stride_bytes, int w,
                                           int h, unsigned char *const *out, size_t out_stride_bytes, int iterations, double shrink_ratio, int bleed_passes,
                                           const w2xc_opts *opts)
-try {
-    ImageCall c(noise_model, scale_model, w, h, iterations, shrink_ratio, nullptr, opts);
-    c.up2x = true;
-    return rgba_batch_host(c, n, in, in_stride_bytes, out, out_stride_bytes, bleed_passes);
-} W2XC_CATCH_ALL
+{
+    return w2xc_process_image_rgba_u8_up2x_batch_tta(noise_model, scale_model, n, in, in_stride_bytes, w, h, out, out_stride_bytes, iterations, shrink_ratio,
+                                                     bleed_passes, opts, 0);
+}
 
 int w2xc_bleed_rgba_u8_device(const unsigned char *d_in, size_t in_stride_bytes, int w, int h, int passes, unsigned char *d_out_rgb, size_t out_stride_bytes,
                               void *hip_stream)
@@ -1107,6 +1171,46 @@ int w2xc_tta_gather_device(const float *d_up, const float *d_tr, size_t variant_
     if (int rc = check_tta_block_args(d_dst, dst_plane_stride_bytes, dst_stride_bytes, n, w, h, d_up, d_tr, variant_plane_stride_bytes)) return rc;
     HIP_TRY(w2xc_launch_tta_gather(d_up, d_tr, (long long)(variant_plane_stride_bytes / 4), w, h, d_dst, (long long)(dst_plane_stride_bytes / 4),
                                    (long long)(dst_stride_bytes / 4), n, (hipStream_t)hip_stream));
+    return W2XC_OK;
+}
+
+// ---- ... with the uint8 image at the outer side (w2xc_tta_u8.hip) ----
+// what both refuse: n images of w x h pixels of px bytes at p (rows `row` bytes apart, images `img` bytes apart) and the 8 m variant planes at up / tr
+static int check_tta_u8_block_args(const void *p, size_t img, size_t row, int px, int n, long long m, int w, int h, const void *up, const void *tr, size_t variant)
+{
+    if (!p || !up || !tr) return fail(W2XC_ERR_ARG, "null argument");
+    if (px != 3 && px != 4) return fail(W2XC_ERR_ARG, "pixels of 3 or 4 bytes (got %d)", px);
+    if (n < 1 || m < 1 || m > (1 << 24) || w <= 0 || h <= 0 || w > (1 << 29) || h > (1 << 29)) return fail(W2XC_ERR_ARG, "bad image count / image size");
+    if (row < (size_t)w * px) return fail(W2XC_ERR_ARG, "row strides must be >= %d*width bytes", px);
+    if (variant & 3) return fail(W2XC_ERR_ARG, "the variant plane stride must be a multiple of 4 bytes");
+    const size_t ext = image_extent(h, row, w, px);
+    if ((n > 1 && img < ext) || variant < (size_t)w * 4 * h) return fail(W2XC_ERR_ARG, "image / plane strides below one image / plane");
+    const size_t group = 4 * (size_t)m * variant, all = (size_t)(n - 1) * img + ext;
+    if (ranges_overlap(up, group, tr, group) || ranges_overlap(p, all, up, group) || ranges_overlap(p, all, tr, group))
+        return fail(W2XC_ERR_ARG, "the images and the two groups of variant planes overlap");
+    return W2XC_OK;
+}
+
+int w2xc_tta_spread_u8_device(const unsigned char *d_src, int n, size_t image_stride_bytes, size_t stride_bytes, int px_bytes, int ch0, int ch_step, int w, int h,
+                              float *d_up, float *d_tr, size_t variant_plane_stride_bytes, void *hip_stream)
+{
+    if (int rc = check_tta_u8_block_args(d_src, image_stride_bytes, stride_bytes, px_bytes, n, 3ll * n, w, h, d_up, d_tr, variant_plane_stride_bytes)) return rc;
+    if (ch0 < 0 || ch_step < 0 || ch0 + 2 * (long long)ch_step >= px_bytes) return fail(W2XC_ERR_ARG, "a selected byte lies outside the pixel");
+    HIP_TRY(w2xc_launch_tta_spread_u8(d_src, image_stride_bytes, stride_bytes, px_bytes, ch0, ch_step, w, h, d_up, d_tr, (long long)(variant_plane_stride_bytes / 4),
+                                      n, (hipStream_t)hip_stream));
+    return W2XC_OK;
+}
+
+int w2xc_tta_gather_u8_device(const float *d_up, const float *d_tr, size_t variant_plane_stride_bytes, int n, int planes_per_image, int first_plane, int n_ch,
+                              int w, int h, unsigned char *d_dst, size_t image_stride_bytes, size_t stride_bytes, int px_bytes, int byte0, void *hip_stream)
+{
+    if (planes_per_image < 1) return fail(W2XC_ERR_ARG, "bad plane count");
+    if (int rc = check_tta_u8_block_args(d_dst, image_stride_bytes, stride_bytes, px_bytes, n, (long long)planes_per_image * n, w, h, d_up, d_tr,
+                                         variant_plane_stride_bytes)) return rc;
+    if (byte0 < 0 || n_ch < 1 || (long long)byte0 + n_ch > px_bytes) return fail(W2XC_ERR_ARG, "a selected byte lies outside the pixel");
+    if (first_plane < 0 || (long long)first_plane + n_ch > planes_per_image) return fail(W2XC_ERR_ARG, "a selected plane lies outside the image's planes");
+    HIP_TRY(w2xc_launch_tta_gather_u8(d_up, d_tr, (long long)(variant_plane_stride_bytes / 4), w, h, d_dst, image_stride_bytes, stride_bytes, px_bytes, byte0, n_ch,
+                                      planes_per_image, first_plane, n, (hipStream_t)hip_stream));
     return W2XC_OK;
 }
 

@@ -176,3 +176,11 @@ hipError_t w2xc_launch_merge_rgba_u8(const unsigned char *rgb, size_t rgb_img_st
 // gather: 8 n result planes (upright ones w x h) -> n planes (plane i at dst + i * dps, rows drs apart): the fp32 sum of T_k^-1 in the order k = 0..7, * 0.125f.
 hipError_t w2xc_launch_tta_spread(const float *src, long long sps, long long srs, int w, int h, float *up, float *tr, long long ps, int n, hipStream_t st);
 hipError_t w2xc_launch_tta_gather(const float *up, const float *tr, long long ps, int w, int h, float *dst, long long dps, long long drs, int n, hipStream_t st);
+// ... with the uint8 image at the outer side (w2xc_tta_u8.hip).  spread_u8: n interleaved images (image i at src + i * img_stride BYTES, rows `stride` bytes
+// apart, pixels px = 3 or 4 bytes) -> the 8 variants of their 3 n planes, plane 3 i + c = byte ch0 + c * ch_step of each pixel / 255 (ch_step = 0: three times
+// the same byte).  gather_u8: 8 m result planes, m = planes_per_image * n -> byte byte0 + c, c < n_ch, of each pixel of image i = to_u8 of the gather's sum
+// for plane planes_per_image * i + first_plane + c; byte stores, nothing else is written.
+hipError_t w2xc_launch_tta_spread_u8(const unsigned char *src, size_t img_stride, size_t stride, int px, int ch0, int ch_step, int w, int h, float *up,
+                                     float *tr, long long ps, int n, hipStream_t st);
+hipError_t w2xc_launch_tta_gather_u8(const float *up, const float *tr, long long ps, int w, int h, unsigned char *dst, size_t img_stride, size_t stride, int px,
+                                     int byte0, int n_ch, int planes_per_image, int first_plane, int n, hipStream_t st);

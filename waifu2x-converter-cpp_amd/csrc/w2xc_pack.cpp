@@ -35,6 +35,7 @@ const char *w2xc_kernel_name(W2xcKernelKind kind, int cin, int cout)
     case W2XC_K_UPCONV: return "upconv4x4_head";
     case W2XC_K_UPCONV_U8: return "upconv4x4_head_u8";
     case W2XC_K_UPCONV_A_U8: return "upconv4x4_head_alpha_u8";
+    case W2XC_K_UPCONV_A: return "upconv4x4_head_alpha";
     default: return "conv3x3_direct";
     }
 }

@@ -25,6 +25,7 @@ enum W2xcKernelKind {
     W2XC_K_UPCONV = 15,        // planar float planes out
     W2XC_K_UPCONV_U8 = 16,     // three interleaved uint8 channels out (as W2XC_K_LAST_U8), pixels 3 or 4 bytes apart
     W2XC_K_UPCONV_A_U8 = 17,   // the alpha head: channel 1 of a three-plane head alone, one uint8 per pixel (the w2xc_upconv_pack_alpha image, bias[1])
+    W2XC_K_UPCONV_A = 18,      // the alpha head with the float sink: channel 1 of a three-plane head as one float plane (the alpha pass of the RGBA TTA call)
 };
 
 // Which kernel kind the fast path has for a (cin, cout) layer; W2XC_K_DIRECT when none.

@@ -66,7 +66,8 @@ hipError_t launch_kind(W2xcKernelKind kind, int midv, const W2xcConvDesc &d, con
     case W2XC_K_LAST_U8: return bd ? w2xc_launch_conv_batch(kind, d, *bd, st) : w2xc_launch_conv(kind, d, st);
     case W2XC_K_UPCONV:
     case W2XC_K_UPCONV_U8:
-    case W2XC_K_UPCONV_A_U8: return bd ? w2xc_launch_upconv_batch(kind, d, *bd, st) : w2xc_launch_upconv(kind, d, st);
+    case W2XC_K_UPCONV_A_U8:
+    case W2XC_K_UPCONV_A: return bd ? w2xc_launch_upconv_batch(kind, d, *bd, st) : w2xc_launch_upconv(kind, d, st);
     default: break;
     }
     if (midv == MID_WINO4) return bd ? w2xc_launch_wino4_batch(d, *bd, st) : w2xc_launch_wino4(d, st);
@@ -94,6 +95,7 @@ int launch_layer(DevCtx *c, const w2xc_model *m, int l, W2xcKernelKind kind, W2x
         d.w1pk = c->layers[l - 1].w_fast;
         d.bias1 = c->layers[l - 1].bias;
         break;
+    case W2XC_K_UPCONV_A:
     case W2XC_K_UPCONV_A_U8:   // the alpha head: channel 1 of the three-plane head as a one-plane head of its own (its image: get_ctx)
         if (d.cout != 3 || !dl.w_alpha) return fail(W2XC_ERR_ARG, "internal error: the alpha head of a layer that is no three-plane upconv head");
         d.cout = 1;
@@ -113,7 +115,7 @@ int launch_layer(DevCtx *c, const w2xc_model *m, int l, W2xcKernelKind kind, W2x
         }
     }
     if (rc) return rc;
-    d.bias = kind == W2XC_K_UPCONV_A_U8 ? dl.bias + 1 : dl.bias;
+    d.bias = kind == W2XC_K_UPCONV_A_U8 || kind == W2XC_K_UPCONV_A ? dl.bias + 1 : dl.bias;
     ProfEvent ev;
     const bool profile = o.profile != 0;
     if (profile) { rc = prof_begin(c, l, st, &ev); if (rc) return rc; }
@@ -369,6 +371,7 @@ int run_band(Band &B, const LayerSrc &view, int up)
             kind = kind != W2XC_K_UPCONV ? W2XC_K_LAST_U8 : (B.u8 & ROWS_U8_DST_A) ? W2XC_K_UPCONV_A_U8 : W2XC_K_UPCONV_U8;
             d.out_ps = (B.u8 & ROWS_U8_DST_PX4) ? 4 : 3;
         }
+        if (k == n && (B.u8 & ROWS_F32_DST_A)) kind = W2XC_K_UPCONV_A;   // (check_u8_views: the last layer is a three-plane head)
         const int Tk = next.top;   // first plane row of the layer's region
         // the strategies that run layer n - 1 and the last layer together end the band
         if (prog_eligible(B, k, kind, d)) {
@@ -397,8 +400,9 @@ static int check_u8_views(const w2xc_model *m, const RowPlan &P, int u8, bool ho
                ((u8 & ROWS_U8_DST) && (out_ps != 1 || !P.last_direct || !u8_sink_layer(m, P.o)))))
         return fail(W2XC_ERR_ARG, "internal error: a uint8 view for a layer without the uint8 kernel");
     // the forms of the RGBA head call: each beside the flag of its side, the sink's only where the last layer is a head (the alpha head: a three-plane one)
-    const bool src_a = (u8 & ROWS_U8_SRC_A) != 0, dst_x = (u8 & (ROWS_U8_DST_PX4 | ROWS_U8_DST_A)) != 0;
-    if ((src_a && !(u8 & ROWS_U8_SRC)) || (dst_x && (!(u8 & ROWS_U8_DST) || P.last_kind != W2XC_K_UPCONV || m->layers[P.n - 1].nout != 3)))
+    const bool src_a = (u8 & ROWS_U8_SRC_A) != 0, dst_x = (u8 & (ROWS_U8_DST_PX4 | ROWS_U8_DST_A)) != 0, dst_fa = (u8 & ROWS_F32_DST_A) != 0;
+    const bool head3 = P.last_kind == W2XC_K_UPCONV && m->layers[P.n - 1].nout == 3;
+    if ((src_a && !(u8 & ROWS_U8_SRC)) || (dst_x && (!(u8 & ROWS_U8_DST) || !head3)) || (dst_fa && ((u8 & ROWS_U8_DST) || hooks || !P.last_direct || !head3)))
         return fail(W2XC_ERR_ARG, "internal error: an RGBA pixel view for a layer without that form");
     return W2XC_OK;
 }

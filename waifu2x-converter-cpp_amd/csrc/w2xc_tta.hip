@@ -10,15 +10,7 @@
 // One __device__ body per output element (*_px); the plane comes from blockIdx.y -- uniform per workgroup -- with a grid-stride loop past 65535.
 #include "w2xc_kernels.h"
 
-#define TTA_T 32
-#define TTA_LD (TTA_T + 1)
-
-// where element (y, x) of the upright h x w plane lies in variant k: upright variants have rows of w, transposed ones rows of h
-static __device__ __forceinline__ long long tta_at(int k, int y, int x, int w, int h)
-{
-    const int xx = (k & 1) ? w - 1 - x : x, yy = (k & 2) ? h - 1 - y : y;
-    return (k & 4) ? (long long)xx * h + yy : (long long)yy * w + xx;
-}
+#include "w2xc_tta_px.h"   // TTA_T, TTA_LD, tta_at, tta_gather_px: shared with w2xc_tta_u8.hip
 
 // the four upright variants of source element (y, x)
 static __device__ __forceinline__ void tta_spread_up_px(float v, int y, int x, int w, int h, float *up, long long ks)
@@ -65,19 +57,6 @@ __global__ void __launch_bounds__(256) k_tta_spread(const float *src, long long 
             }
         }
     }
-}
-
-// element (y, x) of the result from its eight variants' values
-static __device__ __forceinline__ float tta_gather_px(const float v[8])
-{
-    float a = v[0] + v[1];
-    a = a + v[2];
-    a = a + v[3];
-    a = a + v[4];
-    a = a + v[5];
-    a = a + v[6];
-    a = a + v[7];
-    return a * 0.125f;
 }
 
 // 8 n result planes of the upright size w x h (transposed ones: h x w) -> n planes (plane i at dst + i * dps, rows drs floats apart)

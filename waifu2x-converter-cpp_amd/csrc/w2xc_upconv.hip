@@ -20,11 +20,14 @@
 // The alpha head (W2XC_K_UPCONV_A_U8, <CIN, 1, true>): ONE plane into byte d.out[0] of pixels out_ps = 3 or 4 bytes apart, on the image packed from channel 1
 // of a three-plane head (w2xc_upconv_pack_alpha) with bias[1].  A column's MFMA chain does not depend on its neighbours and the tap sum is per plane: the
 // byte has the bits of channel 1 of the three-plane launch, at a third of its matrix work and of its LDS.
+// W2XC_K_UPCONV_A is that head with the float sink (<CIN, 1, false>, the instantiation of one-plane head models): the same image and bias[1], ONE float plane
+// at d.out with the bits of plane 1 of the three-plane launch -- the last alpha pass of the RGBA TTA call, whose mean is taken before the rounding.
 // the sink a kind may have: float planes (pixels one float apart); three uint8 channels one byte apart in pixels of 3 or 4 bytes; the alpha head's one byte
 static bool w2xc_upconv_sink_ok(W2xcKernelKind kind, const W2xcConvDesc &d)
 {
     switch (kind) {
     case W2XC_K_UPCONV: return d.out_ps == 1;
+    case W2XC_K_UPCONV_A: return d.cout == 1 && d.out_ps == 1;   // (the alpha head with the float sink: <CIN, 1, false>)
     case W2XC_K_UPCONV_U8: return d.cout == 3 && (d.out_ps == 3 || d.out_ps == 4) && d.out_cs == 1;
     case W2XC_K_UPCONV_A_U8: return d.cout == 1 && (d.out_ps == 3 || d.out_ps == 4);
     default: return false;
@@ -88,7 +91,7 @@ hipError_t w2xc_launch_upconv_batch(W2xcKernelKind kind, const W2xcConvDesc &d, 
     if (b.batch < 0 || b.in_bs < 0 || b.out_bs < 0 || (b.in_bs & 3) != 0) return hipErrorInvalidValue;
     if (d.in_shift != 0 || d.in_ps != d.cin || d.in_cs != 1 || (d.in_rs & 3) != 0 || (((size_t)d.in) & 15) != 0) return hipErrorInvalidValue;
     if (d.in_h < 1 || d.in_w < 1) return hipErrorInvalidValue;
-    const bool u8 = kind != W2XC_K_UPCONV;
+    const bool u8 = kind != W2XC_K_UPCONV && kind != W2XC_K_UPCONV_A;
     if (!w2xc_upconv_sink_ok(kind, d)) return hipErrorInvalidValue;
     switch (d.cin * 10 + d.cout) {
 #define W2XC_UPCONV_CASE(C)                                                                                        \
@@ -127,7 +130,7 @@ hipError_t w2xc_launch_upconv(W2xcKernelKind kind, const W2xcConvDesc &d, hipStr
     if (d.out_w <= 0 || d.out_h <= 0) return hipSuccess;
     if (d.in_shift != 0 || d.in_ps != d.cin || d.in_cs != 1 || (d.in_rs & 3) != 0 || (((size_t)d.in) & 15) != 0) return hipErrorInvalidValue;
     if (d.in_h < 1 || d.in_w < 1) return hipErrorInvalidValue;
-    const bool u8 = kind != W2XC_K_UPCONV;
+    const bool u8 = kind != W2XC_K_UPCONV && kind != W2XC_K_UPCONV_A;
     if (!w2xc_upconv_sink_ok(kind, d)) return hipErrorInvalidValue;
     switch (d.cin * 10 + d.cout) {
 #define W2XC_UPCONV_CASE(C)                                                                                  \
