@@ -13,6 +13,7 @@ import pytest
 from conftest import ROOT
 from tools import gen_model
 import upconv_ref as ur
+from fp32_matrix import kernel_names   # (the device kernels a call launches, by torch's profiler)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -334,15 +335,6 @@ def test_launches_per_layer(gpu, models, route, h, w):
     if route != "y":
         groups = 1 if h == w else 2
         assert want_s == [groups] * models[s].n_layers and want_n == [groups] * models[nz].n_layers, (want_s, want_n)
-
-
-def kernel_names(run):
-    """the names of the device kernels `run` launches, in order (torch's profiler listens to the HIP runtime, whoever launches)"""
-    from torch.profiler import profile, ProfilerActivity
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        run()
-        torch.cuda.synchronize()
-    return [e.name for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and "Memcpy" not in e.name and "Memset" not in e.name]
 
 
 STAGES_AWAY = ("U8ToRgb", "RgbToU8", "AlphaToGrey", "MergeRgba")

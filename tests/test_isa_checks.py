@@ -12,10 +12,11 @@ import sys
 
 import pytest
 
+from fp32_matrix import kernel_objects   # (tests/test_fp32_matrix.py checks the list itself)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "waifu2x-converter-cpp_amd", "lib")
-KERNEL_OBJS = ["w2xc_kernels.o", "w2xc_split_t1.o", "w2xc_split_t2.o", "w2xc_split_t3.o", "w2xc_split_t4.o", "w2xc_split_t5.o", "w2xc_wino.o",
-               "w2xc_wino4_p.o", "w2xc_wino4_n.o", "w2xc_wino4_f.o", "w2xc_first2_wino4.o", "w2xc_color.o"]   # (csrc/Makefile: the objects built from .hip sources)
+KERNEL_OBJS = kernel_objects()   # csrc/Makefile's OBJ line: every object built from a .hip source, the batch forms, the head, TTA and the colour stages included
 OBJS = [os.path.join(LIB, o) for o in KERNEL_OBJS if os.path.exists(os.path.join(LIB, o))]
 
 
@@ -52,6 +53,19 @@ def _resources(obj):
     # (the PROG instantiations -- ...ELb1ELb1EE -- call w4_prog_job, a real function: its frame is the only scratch in that object)
     ("w2xc_wino4_f.o", r"conv3x3_wino4I.*ELb1ELb0EEv", False),
     ("w2xc_kernels.o", r"conv3x3_(first|last|mfma2)", False),
+    # the batch forms, the 128 -> 256 layer and the head of upconv models
+    ("w2xc_wino4_b.o", r"conv3x3_wino4_batch", False),
+    ("w2xc_wino4_bf.o", r"conv3x3_wino4_batch", False),
+    ("w2xc_wino4_bi.o", r"conv3x3_wino4_batch_l", False),
+    ("w2xc_wino4_bo.o", r"conv3x3_wino4_batch_l", False),
+    ("w2xc_wino4_bw.o", r"conv3x3_wino4_batch_l", False),
+    ("w2xc_wino4_w.o", r"conv3x3_wino4", False),
+    ("w2xc_first2_wino4_b.o", r"conv3x3_first2_wino4_batch", False),
+    ("w2xc_conv_batch.o", r"conv3x3_(first|last)_batch", False),
+    ("w2xc_wino_b.o", r"conv3x3_wino_batch", False),
+    ("w2xc_gather_batch.o", r"conv3x3_last_gather_x4_batch", False),
+    ("w2xc_upconv.o", r"upconv4x4_head", False),
+    ("w2xc_upconv_b.o", r"upconv4x4_head_batch", False),
 ])
 def test_hot_kernels_do_not_spill_vector_registers(obj, pattern, allow_scratch):
     if not os.path.exists(os.path.join(LIB, obj)):
