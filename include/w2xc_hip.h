@@ -666,6 +666,72 @@ int w2xc_tta_spread_u8_device(const unsigned char *d_src, int n, size_t image_st
 int w2xc_tta_gather_u8_device(const float *d_up, const float *d_tr, size_t variant_plane_stride_bytes, int n, int planes_per_image, int first_plane, int n_ch,
                               int w, int h, unsigned char *d_dst, size_t image_stride_bytes, size_t stride_bytes, int px_bytes, int byte0, void *hip_stream);
 
+/* ---- YUV frames (revision 0.4.1.7) ----------------------------------------------------------------
+ * Frames that are Y, U and V already -- what a video decoder, a y4m / raw-yuv pipeline or a grey scan holds -- through Y models: luma through the CNN, chroma
+ * enlarged on bytes (the reference's pipeline, SURVEY Q9, without the RGB image it starts from).  NO colour matrix is involved anywhere: Y is the frame's
+ * own luma, not OpenCV's full-range BT.601 Y of an RGB image.  v1 of the reference has no such entry point; the arithmetic is defined here.
+ *   frame:   a luma plane of w x h bytes and, by `chroma`, two chroma planes of cw x ch bytes:
+ *              W2XC_YUV_420: cw = (w + 1) / 2, ch = (h + 1) / 2      W2XC_YUV_422: cw = (w + 1) / 2, ch = h
+ *              W2XC_YUV_444: cw = w, ch = h                          W2XC_YUV_400: no chroma, the chroma pointers are ignored
+ *            n frames are one w2xc_yuv_planes per side: frame i's luma at y + i * y_frame_stride, rows y_stride bytes apart; its chroma at u / v +
+ *            i * c_frame_stride, rows c_stride apart, samples c_px bytes apart -- 1: planar; 2: two interleaved planes, NV12 is v = u + 1 (NV21: u = v + 1).
+ *            A row of luma is w bytes, a row of chroma c_px * (cw - 1) + 1 bytes from its plane's pointer.
+ *   luma in: (float)Y the byte as a float.  W2XC_RANGE_FULL: y = (float)Y * (float)(1.0 / 255.0); W2XC_RANGE_LIMITED: y = ((float)Y - 16.0f) * (float)(1.0 / 219.0).
+ *   models:  with a noise model y <- CNN_noise(y); then, `iterations` (0 or 1) times, y <- CNN_scale(nearest2x(y)) -- exactly the passes
+ *            w2xc_convert_batch_device runs with nn2x = 0 / 1 on the luma planes of a sub-batch: one launch per layer on the default chain, and bands,
+ *            precisions, named kernels and fusion settings as there.
+ *   luma out: full range saturate(rint(255 y)), half to even, as w2xc_rgb_to_u8_device; limited range saturate(rint(y * 219.0f + 16.0f)), the product and the sum
+ *            two fp32 operations.
+ *   chroma:  iterations = 1: c = (float)C * (float)(1.0 / 255.0), the 2x enlargement of w2xc_resize2x_cubic_device -- its taps, clamping, coefficient
+ *            expressions and summation order --, saturate(rint(255 c)).  The output plane is the leading (2 w + 1) / 2 x (2 h + 1) / 2 samples of the 2 cw x 2 ch
+ *            enlargement (4:2:2: (2 w + 1) / 2 x 2 h; 4:4:4: all of it): the chroma size of a frame of 2 w x 2 h.  `range` does not touch chroma.
+ *            iterations = 0: the chroma bytes are copied.
+ *            The enlargement treats a chroma sample as CENTRED on its block of luma samples (JPEG / MPEG-1 siting); left-sited chroma (MPEG-2, H.264 and
+ *            later: the sample sits on the block's left column) is not corrected, and comes out a quarter of an output chroma sample to the right.
+ *   refused, before a device is touched: a model that is not one plane to one plane W2XC_ERR_PLANES; an upconv head model W2XC_ERR_UNSUPPORTED; neither model
+ *            given, iterations outside 0 .. 1, iterations = 1 without a scale model, iterations = 0 without a noise model, n < 1, null pointers (the chroma
+ *            pointers too, unless W2XC_YUV_400), non-positive sizes or more than 2^22 a side, row strides below the row's bytes, frame strides below a plane
+ *            where n > 1, c_px not 1 or 2, an unknown chroma / range, output planes that overlap each other or an input plane: W2XC_ERR_ARG.
+ * Device form: device pointers on device opts->device, enqueued on hip_stream and NOT synchronised (asynchronous calls that share a (model, device) share one
+ * stream).  Frames run in sub-batches of S: as many as w2xc_opts.workspace_mb (0 = 16384 MiB) holds of the pipeline's own memory per frame -- two float luma
+ * planes per level, and the frame's bytes in and out -- but no more than the sub-batch the batched layer chain takes at the call's largest level, and never
+ * less than 1.  A sub-batch is one launch of each luma stage, the passes on its S luma planes, and ONE launch of the chroma kernel for its 2 S chroma
+ * planes (bytes in, bytes out: no float plane of chroma exists).  The float planes live in the model's context.
+ * Host form: the same with host planes; per sub-batch the planes are uploaded, the device sequence runs and the result is downloaded, on the first device of
+ * opts->device_mask, with blocking copies around it; returns when every output plane is complete.  Host planes with c_px = 2 must be the two interleaved
+ * planes of one buffer, v = u + 1 (NV12) or u = v + 1 (NV21): anything else is W2XC_ERR_ARG here.  Without a device W2XC_ERR_HIP.
+ * Left out: RGB and head models on YUV frames (they need a colour matrix chosen by the caller), 10 / 16-bit samples, TTA, more than one 2x step, the shrink,
+ * chroma siting correction, a submit / wait pair that overlaps frames across calls, overlapped host sub-batches, multi-device striping. */
+#define W2XC_YUV_420 0
+#define W2XC_YUV_422 1
+#define W2XC_YUV_444 2
+#define W2XC_YUV_400 3
+#define W2XC_RANGE_FULL    0
+#define W2XC_RANGE_LIMITED 1
+typedef struct w2xc_yuv_planes {   /* one side of a call: n frames */
+    unsigned char *y;  size_t y_stride,  y_frame_stride;     /* bytes */
+    unsigned char *u, *v; size_t c_stride, c_frame_stride;    /* bytes; NV12: v = u + 1, c_px = 2 */
+    int c_px;
+} w2xc_yuv_planes;
+int w2xc_process_frames_yuv_u8_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range,
+                                      const w2xc_yuv_planes *d_in, const w2xc_yuv_planes *d_out, int iterations, void *hip_stream, const w2xc_opts *opts);
+int w2xc_process_frames_yuv_u8(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, const w2xc_yuv_planes *in,
+                               const w2xc_yuv_planes *out, int iterations, const w2xc_opts *opts);
+/* Its building blocks, without a model, on the current device, asynchronous on hip_stream; n planes each, plane i frame_stride_bytes / plane_stride_bytes on.
+ * y8_to_plane: "luma in" on n byte planes of w x h (rows stride_bytes apart) -> n float planes with contiguous rows, plane_stride_bytes (a multiple of 4,
+ *   at least 4 w h) apart.   plane_to_y8: "luma out", the other way.  Bytes of a row behind w are not written.
+ * chroma2x_u8: "chroma" with iterations = 1 on n byte planes of cw x ch samples, src_px bytes apart -> the leading ow x oh samples (1 <= ow <= 2 cw, 1 <= oh <=
+ *   2 ch) of their enlargements, dst_px bytes apart.  Only the bytes of those samples are written, each with a byte store: with dst_px = 2 the bytes between them
+ *   are another plane's, and two calls may fill the two planes in either order.
+ * W2XC_ERR_ARG: null pointers, n < 1, sizes below 1 or above 2^22, strides below a row (a frame / plane stride below a plane where n > 1), an unknown range,
+ * src_px / dst_px not 1 or 2, an output size outside the enlargement, source and destination that overlap. */
+int w2xc_y8_to_plane_device(const unsigned char *d_src, int n, size_t frame_stride_bytes, size_t stride_bytes, int w, int h, int range, float *d_dst,
+                            size_t plane_stride_bytes, void *hip_stream);
+int w2xc_plane_to_y8_device(const float *d_src, int n, size_t plane_stride_bytes, int w, int h, int range, unsigned char *d_dst, size_t frame_stride_bytes,
+                            size_t stride_bytes, void *hip_stream);
+int w2xc_chroma2x_u8_device(const unsigned char *d_src, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int cw, int ch,
+                            unsigned char *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int ow, int oh, void *hip_stream);
+
 /* the building blocks on contiguous float planes (device pointers): main.cpp:144 on one plane, :75-76, :171-172 */
 int w2xc_resize2x_cubic_device(const float *d_src, int w, int h, float *d_dst, void *hip_stream);
 /* main.cpp:158-167 on one plane (revision 0.4.1.4): cv::resize(Size(dw, dh), INTER_LINEAR) of the contiguous sw x sh plane d_src into the contiguous

@@ -1,0 +1,220 @@
+#!/usr/bin/env python3
+"""tools/w2xc_y4m.py in.y4m out.y4m -m noise|scale|noise_scale --model_dir DIR [--noise_level N] [--range full|limited] [--frames_per_call N]
+
+An 8-bit YUV4MPEG2 stream through the YUV frame call (w2xc_process_frames_yuv_u8): luma through the Y models, chroma enlarged on bytes -- no RGB image, no
+colour matrix.  The reader and the writer are pure Python (numpy for the planes): colour spaces C420* (C420, C420jpeg, C420mpeg2, C420paldv: all of them
+(w + 1) / 2 x (h + 1) / 2 chroma; the siting is not corrected, include/w2xc_hip.h), C422, C444 and Cmono; no C tag means C420jpeg, as the format says.
+The range is the stream's XCOLORRANGE=FULL|LIMITED where present, otherwise --range (default limited).  Frames go through the host call in groups of
+--frames_per_call.  With a scale step the W and H fields are doubled; F (the frame rate) and A (the pixel aspect) are those of the input -- twice the samples
+in both directions change neither --, every other header field is passed on as it is.  Interlaced streams (I other than p / ?) are refused: fields would have
+to be enlarged separately.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+MAGIC = b"YUV4MPEG2"
+# colour-space tag -> the chroma layout's name (the values of w2xc_amd.YUV_*: 420 = 0, 422 = 1, 444 = 2, 400 = 3)
+LAYOUTS = {"420": 0, "422": 1, "444": 2, "mono": 3}
+
+
+INTERLACED = "interlaced stream (I%s): not supported -- its fields would have to be enlarged separately; deinterlace first"
+
+
+class Y4mError(ValueError):
+    pass
+
+
+def layout_of(tag):
+    """the chroma layout of a C tag's value: 420jpeg / 420mpeg2 / 420paldv / 420 -> 0, 422 -> 1, 444 -> 2, mono -> 3; everything else (10-bit forms such as
+    420p10, 444alpha) is refused"""
+    if tag in ("420", "420jpeg", "420mpeg2", "420paldv"):
+        return LAYOUTS["420"]
+    if tag in ("422", "444", "mono"):
+        return LAYOUTS[tag]
+    raise Y4mError("unsupported colour space C%s (8-bit C420*, C422, C444 and Cmono only)" % tag)
+
+
+def chroma_size(w, h, layout):
+    if layout == LAYOUTS["mono"]:
+        return 0, 0
+    return ((w + 1) // 2 if layout != LAYOUTS["444"] else w), ((h + 1) // 2 if layout == LAYOUTS["420"] else h)
+
+
+class Header:
+    """the stream header: width, height, and every other field as (letter, value) in the order given"""
+
+    def __init__(self, w, h, fields):
+        self.w, self.h, self.fields = w, h, list(fields)
+
+    def get(self, letter, default=None):
+        for k, v in self.fields:
+            if k == letter:
+                return v
+        return default
+
+    @property
+    def layout(self):
+        return layout_of(self.get("C", "420jpeg"))
+
+    @property
+    def interlaced(self):
+        return self.get("I", "p") not in ("p", "?")
+
+    def colour_range(self):
+        """'full' / 'limited' from an XCOLORRANGE field, None without one"""
+        for k, v in self.fields:
+            if k == "X" and v.upper().startswith("COLORRANGE="):
+                r = v.split("=", 1)[1].lower()
+                if r not in ("full", "limited"):
+                    raise Y4mError("unknown XCOLORRANGE=%s" % v.split("=", 1)[1])
+                return r
+        return None
+
+    def scaled(self, iterations):
+        """the header of the output: W and H doubled `iterations` times, every other field -- F and A among them -- kept"""
+        return Header(self.w << iterations, self.h << iterations, self.fields)
+
+    def line(self):
+        return b" ".join([MAGIC, b"W%d" % self.w, b"H%d" % self.h] + [("%s%s" % kv).encode("ascii") for kv in self.fields]) + b"\n"
+
+
+def read_line(f, limit=4096):
+    line = bytearray()
+    while True:
+        b = f.read(1)
+        if not b:
+            return None if not line else bytes(line)
+        if b == b"\n":
+            return bytes(line)
+        line += b
+        if len(line) > limit:
+            raise Y4mError("header line longer than %d bytes" % limit)
+
+
+def read_header(f):
+    line = read_line(f)
+    if line is None or not line.startswith(MAGIC):
+        raise Y4mError("not a YUV4MPEG2 stream")
+    w = h = None
+    fields = []
+    for tok in line[len(MAGIC):].decode("ascii", "replace").split():
+        k, v = tok[0], tok[1:]
+        if k == "W":
+            w = int(v)
+        elif k == "H":
+            h = int(v)
+        else:
+            fields.append((k, v))
+    if not w or not h or w < 1 or h < 1:
+        raise Y4mError("the header gives no frame size")
+    return Header(w, h, fields)
+
+
+def read_frames(f, hdr, count):
+    """up to `count` frames: (y, u, v) as (n, h, w) and (n, ch, cw) uint8 arrays (u = v = None for Cmono), n = 0 at the end of the stream"""
+    cw, ch = chroma_size(hdr.w, hdr.h, hdr.layout)
+    ysz, csz = hdr.w * hdr.h, cw * ch
+    ys, us, vs = [], [], []
+    while len(ys) < count:
+        line = read_line(f)
+        if line is None:
+            break
+        if not line.startswith(b"FRAME"):
+            raise Y4mError("expected a FRAME header, got %r" % line[:16])
+        data = f.read(ysz + 2 * csz)
+        if len(data) != ysz + 2 * csz:
+            raise Y4mError("the stream ends inside a frame")
+        a = np.frombuffer(data, np.uint8)
+        ys.append(a[:ysz].reshape(hdr.h, hdr.w))
+        if csz:
+            us.append(a[ysz:ysz + csz].reshape(ch, cw))
+            vs.append(a[ysz + csz:].reshape(ch, cw))
+    if not ys:
+        return np.empty((0, hdr.h, hdr.w), np.uint8), None, None
+    return np.stack(ys), (np.stack(us) if csz else None), (np.stack(vs) if csz else None)
+
+
+def write_header(f, hdr):
+    f.write(hdr.line())
+
+
+def write_frames(f, y, u, v):
+    for i in range(y.shape[0]):
+        f.write(b"FRAME\n")
+        f.write(np.ascontiguousarray(y[i]).tobytes())
+        if u is not None:
+            f.write(np.ascontiguousarray(u[i]).tobytes())
+            f.write(np.ascontiguousarray(v[i]).tobytes())
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description="8-bit YUV4MPEG2 streams through waifu2x Y models on an MI355X: luma through the CNN, chroma 2x on bytes")
+    ap.add_argument("input")
+    ap.add_argument("output")
+    ap.add_argument("-m", "--mode", default="noise_scale", choices=["noise", "scale", "noise_scale"])
+    ap.add_argument("--noise_level", type=int, default=1, choices=[1, 2])
+    ap.add_argument("--model_dir", default="models")
+    ap.add_argument("--range", default="limited", choices=["full", "limited"], help="luma range where the stream has no XCOLORRANGE field")
+    ap.add_argument("--frames_per_call", type=int, default=8)
+    return ap
+
+
+def convert_stream(fin, fout, process, iterations, default_range="limited", frames_per_call=8):
+    """read fin, write fout; process(y, u, v, layout, full_range) -> (Y, U, V) is the frame call.  Returns the number of frames."""
+    hdr = read_header(fin)
+    if hdr.interlaced:
+        raise Y4mError(INTERLACED % hdr.get("I"))
+    layout = hdr.layout
+    full = (hdr.colour_range() or default_range) == "full"
+    write_header(fout, hdr.scaled(iterations))
+    total = 0
+    while True:
+        y, u, v = read_frames(fin, hdr, max(1, frames_per_call))
+        if y.shape[0] == 0:
+            return total
+        write_frames(fout, *process(y, u, v, layout, full))
+        total += y.shape[0]
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    try:
+        with open(args.input, "rb") as fin:
+            # what the stream itself rules out, before a model is loaded or the output file is created
+            hdr = read_header(fin)
+            if hdr.interlaced:
+                raise Y4mError(INTERLACED % hdr.get("I"))
+            hdr.layout, hdr.colour_range()
+            fin.seek(0)
+            import __graft_entry__ as graft
+            w2xc = graft.load_package()
+            noise = scale = None
+            if args.mode in ("noise", "noise_scale"):
+                noise = w2xc._ModelSet.from_json(os.path.join(args.model_dir, "noise%d_model.json" % args.noise_level))
+            if args.mode in ("scale", "noise_scale"):
+                scale = w2xc._ModelSet.from_json(os.path.join(args.model_dir, "scale2.0x_model.json"))
+            iterations = 1 if scale is not None else 0
+
+            def process(y, u, v, layout, full):
+                out = w2xc.process_frames_yuv_u8(y, u, v, chroma=layout, noise=noise, scale=scale, iterations=iterations,
+                                                 range=w2xc.RANGE_FULL if full else w2xc.RANGE_LIMITED)
+                return out if len(out) == 3 else (out[0], None, None)
+
+            with open(args.output, "wb") as fout:
+                n = convert_stream(fin, fout, process, iterations, args.range, args.frames_per_call)
+    except Y4mError as e:
+        sys.stderr.write("w2xc_y4m: %s\n" % e)
+        return 2
+    sys.stderr.write("w2xc_y4m: %d frames\n" % n)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -31,6 +31,8 @@ OK, ERR_IO, ERR_JSON, ERR_ARG, ERR_PLANES, ERR_HIP, ERR_UNSUPPORTED, ERR_NOMEM =
 PRECISION_FP32, PRECISION_BF16, PRECISION_BF16X2, PRECISION_BF16X3, PRECISION_FP16X2 = 0, 1, 2, 3, 4
 KERNEL_AUTO, KERNEL_DIRECT, KERNEL_MFMA, KERNEL_WINOGRAD, KERNEL_WINOGRAD32, KERNEL_WINOGRAD4 = 0, 1, 2, 3, 4, 5
 FUSION_AUTO, FUSION_OFF, FUSION_ON, FUSION_FIRST, FUSION_LAST, FUSION_GATHER_LAUNCH, FUSION_PROG = 0, 1, 2, 3, 4, 5, 6
+YUV_420, YUV_422, YUV_444, YUV_400 = 0, 1, 2, 3
+RANGE_FULL, RANGE_LIMITED = 0, 1
 
 
 class W2xcError(RuntimeError):
@@ -51,6 +53,13 @@ class RowPlan(C.Structure):
     """struct w2xc_row_plan (include/w2xc_hip.h): the band geometry of one row-range conversion."""
     _fields_ = [("struct_size", C.c_int), ("n_layers", C.c_int), ("halo_rows_per_layer", C.c_int), ("band_rows", C.c_int),
                 ("n_bands", C.c_int), ("fused_first", C.c_int), ("fused_last", C.c_int), ("workspace_bytes", C.c_ulonglong * 2)]
+
+
+class YuvPlanes(C.Structure):
+    """struct w2xc_yuv_planes (include/w2xc_hip.h): one side of a YUV frame call -- n frames, pointers as integers, strides in bytes; c_px = 1: planar
+    chroma, 2: two interleaved planes (NV12: v = u + 1)."""
+    _fields_ = [("y", C.c_void_p), ("y_stride", C.c_size_t), ("y_frame_stride", C.c_size_t), ("u", C.c_void_p), ("v", C.c_void_p),
+                ("c_stride", C.c_size_t), ("c_frame_stride", C.c_size_t), ("c_px", C.c_int)]
 
 
 def _load():
@@ -130,6 +139,11 @@ def _load():
         "w2xc_process_image_rgba_u8_up2x_batch_tta": (ci, [vp, vp, ci, C.POINTER(fp), cs, ci, ci, C.POINTER(fp), cs, ci, C.c_double, ci, C.POINTER(Opts), ci]),
         "w2xc_tta_spread_u8_device": (ci, [fp, ci, cs, cs, ci, ci, ci, ci, ci, fp, fp, cs, vp]),
         "w2xc_tta_gather_u8_device": (ci, [fp, fp, cs, ci, ci, ci, ci, ci, ci, fp, cs, cs, ci, ci, vp]),
+        "w2xc_process_frames_yuv_u8_device": (ci, [vp, vp, ci, ci, ci, ci, ci, C.POINTER(YuvPlanes), C.POINTER(YuvPlanes), ci, vp, C.POINTER(Opts)]),
+        "w2xc_process_frames_yuv_u8": (ci, [vp, vp, ci, ci, ci, ci, ci, C.POINTER(YuvPlanes), C.POINTER(YuvPlanes), ci, C.POINTER(Opts)]),
+        "w2xc_y8_to_plane_device": (ci, [fp, ci, cs, cs, ci, ci, ci, fp, cs, vp]),
+        "w2xc_plane_to_y8_device": (ci, [fp, ci, cs, ci, ci, ci, fp, cs, cs, vp]),
+        "w2xc_chroma2x_u8_device": (ci, [fp, ci, cs, cs, ci, ci, ci, fp, cs, cs, ci, ci, ci, vp]),
         "w2xc_u8_to_rgb_device": (ci, [fp, cs, ci, ci, fp, fp, fp, vp]),
         "w2xc_rgb_to_u8_device": (ci, [fp, fp, fp, ci, ci, fp, cs, vp]),
         "w2xc_process_image_u8_device": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, vp, C.POINTER(Opts)]),
@@ -979,3 +993,90 @@ def bleed_rgba_u8_device(d_in, in_stride_bytes, w, h, passes, d_out_rgb, out_str
 def bleed_rgba_u8_trim():
     """release the scratch bleed_rgba_u8_device keeps per device (w2xc_bleed_rgba_u8_trim); waits for those devices first"""
     _check(_lib.w2xc_bleed_rgba_u8_trim())
+
+
+# ---- YUV frames: luma through Y models, chroma 2x on bytes (include/w2xc_hip.h, "YUV frames") ----
+def yuv_chroma_size(w, h, chroma):
+    """(cw, ch) of the chroma planes of a w x h frame; (0, 0) for YUV_400"""
+    if chroma == YUV_400:
+        return 0, 0
+    if chroma not in (YUV_420, YUV_422, YUV_444):
+        raise ValueError("unknown chroma layout %r" % (chroma,))
+    return ((w + 1) // 2 if chroma != YUV_444 else w), ((h + 1) // 2 if chroma == YUV_420 else h)
+
+
+def process_frames_yuv_u8_device(n, w, h, chroma, d_in, d_out, noise=None, scale=None, iterations=0, range=RANGE_LIMITED, stream=0, opts=None):
+    """Device-pointer form (w2xc_process_frames_yuv_u8_device): n frames of w x h described by the YuvPlanes d_in, the (w << iterations) x (h << iterations)
+    frames by d_out.  Asynchronous on `stream`."""
+    _check(_lib.w2xc_process_frames_yuv_u8_device(*_handles(noise, scale), n, w, h, chroma, range, C.byref(d_in), C.byref(d_out), iterations,
+                                                  C.c_void_p(stream), C.byref(opts) if opts is not None else None))
+
+
+def _yuv_side(y, u, v, uv):
+    """the YuvPlanes of host arrays: y (n, h, w); u and v (n, ch, cw) planar, or uv (n, ch, cw, 2) interleaved (NV12); neither: no chroma"""
+    s = YuvPlanes()
+    s.y, s.y_stride, s.y_frame_stride = y.ctypes.data, y.strides[1], y.strides[0]
+    s.c_px = 1
+    if uv is not None:
+        s.u, s.v, s.c_stride, s.c_frame_stride, s.c_px = uv.ctypes.data, uv.ctypes.data + 1, uv.strides[1], uv.strides[0], 2
+    elif u is not None:
+        s.u, s.v, s.c_stride, s.c_frame_stride = u.ctypes.data, v.ctypes.data, u.strides[1], u.strides[0]
+    return s
+
+
+def process_frames_yuv_u8(y, u=None, v=None, uv=None, chroma=YUV_420, noise=None, scale=None, iterations=0, range=RANGE_LIMITED, opts=None, out_nv12=None):
+    """n YUV frames in one call (w2xc_process_frames_yuv_u8): y is an (n, h, w) uint8 array; chroma either planar -- u and v, (n, ch, cw) uint8 -- or
+    interleaved -- uv, (n, ch, cw, 2) uint8, NV12 --, none with YUV_400.  Luma goes through `noise` and, `iterations` (0 or 1) times, through `scale`;
+    chroma is enlarged on bytes.  Returns (Y, U, V), or (Y, UV) where the output is interleaved (out_nv12; default: as the input), or (Y,) for YUV_400."""
+    def u8(a, nd, what):
+        a = np.asarray(a)
+        if a.dtype != np.uint8 or a.ndim != nd:
+            raise ValueError("process_frames_yuv_u8 wants %s as a %d-D uint8 array (got %s, shape %r)" % (what, nd, a.dtype, a.shape))
+        return np.ascontiguousarray(a)
+    y = u8(y, 3, "y")
+    n, h, w = y.shape
+    cw, ch = yuv_chroma_size(w, h, chroma)
+    if chroma == YUV_400:
+        u = v = uv = None
+    elif uv is not None:
+        uv = u8(uv, 4, "uv")
+        if uv.shape != (n, ch, cw, 2):
+            raise ValueError("process_frames_yuv_u8: uv must be (n, %d, %d, 2), got %r" % (ch, cw, uv.shape))
+    else:
+        if u is None or v is None:
+            raise ValueError("process_frames_yuv_u8 wants u and v, or uv, unless chroma is YUV_400")
+        u, v = u8(u, 3, "u"), u8(v, 3, "v")
+        if u.shape != (n, ch, cw) or v.shape != (n, ch, cw):
+            raise ValueError("process_frames_yuv_u8: u and v must be (n, %d, %d), got %r and %r" % (ch, cw, u.shape, v.shape))
+    W, H = w << iterations, h << iterations
+    ocw, och = yuv_chroma_size(W, H, chroma)
+    nv12 = (uv is not None) if out_nv12 is None else bool(out_nv12)
+    oy = np.empty((n, max(H, 0), max(W, 0)), np.uint8)
+    ou = ov = ouv = None
+    if chroma != YUV_400:
+        if nv12:
+            ouv = np.empty((n, och, ocw, 2), np.uint8)
+        else:
+            ou, ov = np.empty((n, och, ocw), np.uint8), np.empty((n, och, ocw), np.uint8)
+    si, so = _yuv_side(y, u, v, uv), _yuv_side(oy, ou, ov, ouv)
+    _check(_lib.w2xc_process_frames_yuv_u8(*_handles(noise, scale), n, w, h, chroma, range, C.byref(si), C.byref(so), iterations,
+                                           C.byref(opts) if opts is not None else None))
+    return (oy,) if chroma == YUV_400 else (oy, ouv) if nv12 else (oy, ou, ov)
+
+
+def y8_to_plane_device(d_src, n, frame_stride_bytes, stride_bytes, w, h, range, d_dst, plane_stride_bytes, stream=0):
+    """n luma byte planes of w x h -> n float planes with contiguous rows: y = byte / 255 (RANGE_FULL) or (byte - 16) / 219 (RANGE_LIMITED)
+    (w2xc_y8_to_plane_device)."""
+    _check(_lib.w2xc_y8_to_plane_device(C.c_void_p(d_src), n, frame_stride_bytes, stride_bytes, w, h, range, C.c_void_p(d_dst), plane_stride_bytes, C.c_void_p(stream)))
+
+
+def plane_to_y8_device(d_src, n, plane_stride_bytes, w, h, range, d_dst, frame_stride_bytes, stride_bytes, stream=0):
+    """n float planes with contiguous rows -> n luma byte planes: saturate(rint(255 y)) or saturate(rint(219 y + 16)) (w2xc_plane_to_y8_device)."""
+    _check(_lib.w2xc_plane_to_y8_device(C.c_void_p(d_src), n, plane_stride_bytes, w, h, range, C.c_void_p(d_dst), frame_stride_bytes, stride_bytes, C.c_void_p(stream)))
+
+
+def chroma2x_u8_device(d_src, n, src_frame_stride_bytes, src_stride_bytes, src_px, cw, ch, d_dst, dst_frame_stride_bytes, dst_stride_bytes, dst_px, ow, oh, stream=0):
+    """the bicubic 2x of n chroma byte planes of cw x ch samples (src_px bytes apart), bytes to bytes: the leading ow x oh samples of each enlargement, dst_px
+    bytes apart (w2xc_chroma2x_u8_device)."""
+    _check(_lib.w2xc_chroma2x_u8_device(C.c_void_p(d_src), n, src_frame_stride_bytes, src_stride_bytes, src_px, cw, ch, C.c_void_p(d_dst), dst_frame_stride_bytes,
+                                        dst_stride_bytes, dst_px, ow, oh, C.c_void_p(stream)))

@@ -2,35 +2,10 @@
 // CLI's scale loop (/root/reference/src/main.cpp:74-76,136,144,171-172), so that the whole scale phase of
 // one image runs device-resident.  All kernels are HBM-streaming (a few bytes per pixel) and keep
 // OpenCV's float evaluation order with unfused mul/add (the file is built with -ffp-contract=off).
-// Every stage is ONE struct of pointers, strides and sizes whose operator()(img, q) computes output element q of image / plane img; the one kernel
-// template k_px holds the loops over both, and launch_px the grid and the launch.  A stage is its kernel's by-value argument: img comes from blockIdx.y --
-// uniform per workgroup -- and moves only the stage's 64-bit base pointers by img x stride.  One image is n = 1.
+// Every stage is ONE struct on the per-pixel skeleton of w2xc_px.h: k_px holds the loops over images and elements, launch_px the grid and the launch.
 #include "w2xc_kernels.h"
 #include "w2xc_tta_px.h"   // clampi, to_u8: shared with w2xc_tta_u8.hip
-
-// blockIdx.y strides over the n images / planes (more than 65535 take further trips), blockIdx.x x 256 threads over the `total` elements of each.
-// (Every stage has a batch form: the register cost of the loop nest for the stages that once ran one image only is in profiles/color_stage_resources.txt.)
-template <class Stage> __global__ void __launch_bounds__(256) k_px(Stage s, long long total, int n)
-{
-    for (int img = blockIdx.y; img < n; img += gridDim.y)
-        for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) s(img, q);
-}
-
-template <class Stage> static hipError_t launch_px(const Stage &s, long long total, int n, hipStream_t st)
-{
-    const long long b = (total + 255) / 256;
-    const dim3 grid((unsigned)(b > 65536 ? 65536 : (b < 1 ? 1 : b)), (unsigned)(n > 65535 ? 65535 : n));
-    hipLaunchKernelGGL((k_px<Stage>), grid, dim3(256), 0, st, s, total, n);
-    return hipGetLastError();
-}
-
-// element q of rows of w: its row and column
-struct RowCol { int r, c; };
-static __device__ __forceinline__ RowCol row_col(long long q, int w)
-{
-    const int r = (int)(q / w);
-    return {r, (int)(q - (long long)r * w)};
-}
+#include "w2xc_px.h"       // k_px, launch_px, row_col, cubic_coeffs: shared with w2xc_yuv.hip
 
 // main.cpp:75-76 (+ cv::split): convertTo(CV_32F, 1/255) and COLOR_RGB2YUV on the channels AS GIVEN
 // (the reference feeds imread's BGR order, Q3): Y = .299 c0 + .587 c1 + .114 c2, U = (c2-Y)*.492+.5, V = (c0-Y)*.877+.5
@@ -153,15 +128,6 @@ hipError_t w2xc_launch_rgb_to_u8_batch(const float *planes, long long ps, long l
 hipError_t w2xc_launch_rgb_to_u8(const float *p0, const float *p1, const float *p2, int w, int h, unsigned char *dst, size_t stride, hipStream_t st)
 {
     return launch_px(RgbToU8{p0, p1, p2, 0, w, dst, 0, (long long)stride}, (long long)w * h, 1, st);
-}
-
-static __device__ __forceinline__ void cubic_coeffs(float t, float *c)   // Keys cubic, A = -0.75 (OpenCV interpolateCubic)
-{
-    const float A = -0.75f;
-    c[0] = ((A * (t + 1) - 5 * A) * (t + 1) + 8 * A) * (t + 1) - 4 * A;
-    c[1] = ((A + 2) * t - (A + 3)) * t * t + 1;
-    c[2] = ((A + 2) * (1 - t) - (A + 3)) * (1 - t) * (1 - t) + 1;
-    c[3] = 1.f - c[0] - c[1] - c[2];
 }
 
 // main.cpp:144 on one plane: cv::resize(2x, INTER_CUBIC): horizontal pass to float, then vertical pass,

@@ -27,6 +27,8 @@
 //                           and test-time augmentation: tta_pass (spread -> the CNN on the 8 variants -> gather; kernels in w2xc_tta.hip, and -- the uint8
 //                           image at the outer side: the RGB and head routes of the RGBA TTA calls -- w2xc_tta_u8.hip), which both pipelines and the TTA
 //                           plane calls share
+//                           and YUV frames (w2xc_process_frames_yuv_u8*): process_yuv_device -- luma bytes through run_batch, chroma bytes to bytes
+//                           (kernels in w2xc_yuv.hip, on the per-pixel skeleton of w2xc_px.h)
 #pragma once
 #include "../../include/w2xc_hip.h"
 

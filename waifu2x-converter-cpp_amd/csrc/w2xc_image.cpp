@@ -4,6 +4,7 @@
 // the first and the last layer of the call reading / writing the uint8 image themselves where their kernels can (no counterpart in v1).
 // One pipeline per route -- process_y_device, process_rgb_device -- for S images of one size: the single-image calls, the batches and the RGBA call
 // (process_rgba_device, around either) all run these two.  What is fixed for a call travels as an ImageCall, the uint8 images as U8Images views.
+// And frames that are Y, U and V already (w2xc_process_frames_yuv_u8*): process_yuv_device, the Y pipeline without its colour stages.
 #include "w2xc_engine.hpp"
 #include "w2xc_host_geom.hpp"
 
@@ -766,6 +767,204 @@ int image_batch_host(bool rgb, ImageCall c, int n, const unsigned char *const *i
     return batch_host_run(b, c.o, sub);
 }
 
+// ---- YUV frames (w2xc_process_frames_yuv_u8*; the arithmetic: include/w2xc_hip.h) ----
+// Luma through the models as the planes of run_batch, chroma from bytes to bytes in one launch: no colour matrix, no float plane of chroma.
+struct YuvGeom {
+    int chroma, range;
+    int cw = 0, ch = 0;     // the chroma planes of a w x h frame (0 x 0: W2XC_YUV_400)
+    int ocw = 0, och = 0;   // ... of the call's output frame
+    int W = 0, H = 0;       // the output frame
+};
+size_t chroma_row_bytes(int cw, int px) { return (size_t)px * (cw - 1) + 1; }
+// the float planes of one frame: two luma planes per level
+size_t yuv_aux_floats(int w, int h, int iterations) { return 2 * plane_floats(w, h) + (iterations ? 2 * plane_floats(2 * w, 2 * h) : 0); }
+// the bytes of one frame's planes: w x h luma, two planes of cw x ch chroma
+size_t yuv_frame_bytes(int w, int h, int cw, int ch) { return (size_t)w * h + 2 * (size_t)cw * ch; }
+
+// one side's planes from frame b0 on
+w2xc_yuv_planes yuv_from(const w2xc_yuv_planes &s, size_t b0, bool chroma)
+{
+    w2xc_yuv_planes t = s;
+    t.y += b0 * s.y_frame_stride;
+    if (chroma) { t.u += b0 * s.c_frame_stride; t.v += b0 * s.c_frame_stride; }
+    return t;
+}
+
+// n frames of w x h luma and cw x ch chroma on one side: pointers, strides, c_px; its byte ranges go to iv tagged `tag` (check_batch_overlap)
+int check_yuv_side(const w2xc_yuv_planes *s, int n, int w, int h, int cw, int ch, int tag, std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> &iv)
+{
+    if (!s || !s->y) return fail(W2XC_ERR_ARG, "null argument");
+    const size_t y_ext = image_extent(h, s->y_stride, w, 1);
+    if (s->y_stride < (size_t)w || (n > 1 && s->y_frame_stride < y_ext)) return fail(W2XC_ERR_ARG, "luma: row stride below the row's bytes / frame stride below a plane");
+    for (int i = 0; i < n; i++) iv.push_back({{(uintptr_t)s->y + i * s->y_frame_stride, (uintptr_t)s->y + i * s->y_frame_stride + y_ext}, tag});
+    if (!cw) return W2XC_OK;
+    if (!s->u || !s->v) return fail(W2XC_ERR_ARG, "null argument");
+    if (s->c_px != 1 && s->c_px != 2) return fail(W2XC_ERR_ARG, "c_px must be 1 (planar) or 2 (interleaved), got %d", s->c_px);
+    const size_t row = chroma_row_bytes(cw, s->c_px), c_ext = (size_t)(ch - 1) * s->c_stride + row;
+    if (s->c_stride < row || (n > 1 && s->c_frame_stride < c_ext)) return fail(W2XC_ERR_ARG, "chroma: row stride below the row's bytes / frame stride below a plane");
+    // two interleaved planes (NV12: v = u + 1) are one range of bytes, two planes otherwise
+    const uintptr_t u = (uintptr_t)s->u, v = (uintptr_t)s->v;
+    const bool pair = s->c_px == 2 && (v == u + 1 || u == v + 1);
+    for (int i = 0; i < n; i++) {
+        const uintptr_t off = i * s->c_frame_stride;
+        if (pair) iv.push_back({{std::min(u, v) + off, std::min(u, v) + off + c_ext + 1}, tag});
+        else { iv.push_back({{u + off, u + off + c_ext}, tag}); iv.push_back({{v + off, v + off + c_ext}, tag}); }
+    }
+    return W2XC_OK;
+}
+
+// everything both forms refuse, before a device is touched; *g = the geometry, *sub = frames per sub-batch
+int check_yuv_call(ImageCall &c, int n, int chroma, int range, const w2xc_yuv_planes *in, const w2xc_yuv_planes *out, YuvGeom *g, int *sub)
+{
+    int rc = check_process_args(c);
+    if (rc || (rc = check_y_models(c))) return rc;
+    if (c.iterations < 0 || c.iterations > 1) return fail(W2XC_ERR_ARG, "iterations must be 0 or 1 (got %d)", c.iterations);
+    if (n < 1 || n > (1 << 20)) return fail(W2XC_ERR_ARG, "batch of %d frames", n);
+    if (c.w <= 0 || c.h <= 0 || c.w > (1 << 22) || c.h > (1 << 22)) return fail(W2XC_ERR_ARG, "bad frame size");
+    if (chroma < W2XC_YUV_420 || chroma > W2XC_YUV_400) return fail(W2XC_ERR_ARG, "unknown chroma layout %d", chroma);
+    if (range != W2XC_RANGE_FULL && range != W2XC_RANGE_LIMITED) return fail(W2XC_ERR_ARG, "unknown range %d", range);
+    g->chroma = chroma; g->range = range;
+    g->W = c.w << c.iterations; g->H = c.h << c.iterations;
+    if (chroma != W2XC_YUV_400) {
+        const bool half_x = chroma != W2XC_YUV_444, half_y = chroma == W2XC_YUV_420;
+        g->cw = half_x ? (c.w + 1) / 2 : c.w;     g->ch = half_y ? (c.h + 1) / 2 : c.h;
+        g->ocw = half_x ? (g->W + 1) / 2 : g->W;  g->och = half_y ? (g->H + 1) / 2 : g->H;
+    }
+    std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> iv;
+    if ((rc = check_yuv_side(in, n, c.w, c.h, g->cw, g->ch, 0, iv)) || (rc = check_yuv_side(out, n, g->W, g->H, g->ocw, g->och, 1, iv))) return rc;
+    if ((rc = check_batch_overlap(iv))) return rc;
+    c.fw = g->W; c.fh = g->H;
+    const size_t per = yuv_aux_floats(c.w, c.h, c.iterations) * sizeof(float) + yuv_frame_bytes(c.w, c.h, g->cw, g->ch) + yuv_frame_bytes(g->W, g->H, g->ocw, g->och);
+    return plan_image_call(PLAN_Y, c, sub, per);
+}
+
+W2xcU8Planes chroma_planes(const w2xc_yuv_planes &s) { return {s.u, (long long)s.c_frame_stride, (long long)s.c_stride, s.c_px}; }
+
+// A sub-batch of S frames (S <= cap, the call's sub-batch size: the planes are sized by cap): luma bytes -> planes, the noise pass, the scale pass with the
+// nearest-2x folded into layer 1 -- run_batch, so bands, precisions, named kernels and fusion settings are those of w2xc_convert_batch_device --, planes ->
+// luma bytes; chroma in ONE launch, bytes to bytes.
+int process_yuv_device(const ImageCall &c, const YuvGeom &g, int S, int cap, const w2xc_yuv_planes &in, const w2xc_yuv_planes &out)
+{
+    DevCtx *own = c.ctx.owner();
+    if (int rc = reserve_aux(own, 0, yuv_aux_floats(c.w, c.h, c.iterations) * (size_t)cap)) return rc;
+    float *base = aux_planes(own, 0);
+    long long ps = (long long)plane_floats(c.w, c.h);
+    float *y = base, *yn = y + (size_t)cap * ps;
+    base += 2 * (size_t)cap * ps;
+    HIP_TRY(w2xc_launch_y8_to_plane({in.y, (long long)in.y_frame_stride, (long long)in.y_stride, 1}, c.w, c.h, g.range, y, ps, S, c.st));
+    if (c.mn) {
+        if (int rc = run_batch(c.mn, c.ctx.cn, S, 0, {y, (size_t)c.w, ps}, c.w, c.h, {yn, (size_t)c.w, ps}, c.st, c.o)) return rc;
+        y = yn;
+    }
+    if (c.iterations) {
+        const long long ps2 = (long long)plane_floats(g.W, g.H);
+        if (int rc = run_batch(c.msc, c.ctx.cs, S, 1, {y, (size_t)c.w, ps}, c.w, c.h, {base, (size_t)g.W, ps2}, c.st, c.o)) return rc;
+        y = base; ps = ps2;
+    }
+    HIP_TRY(w2xc_launch_plane_to_y8(y, ps, g.W, g.H, g.range, {out.y, (long long)out.y_frame_stride, (long long)out.y_stride, 1}, S, c.st));
+    if (!g.cw) return W2XC_OK;
+    if (c.iterations) HIP_TRY(w2xc_launch_chroma2x_u8(chroma_planes(in), in.v, g.cw, g.ch, chroma_planes(out), out.v, g.ocw, g.och, S, c.st));
+    else HIP_TRY(w2xc_launch_chroma_copy_u8(chroma_planes(in), in.v, g.cw, g.ch, chroma_planes(out), out.v, S, c.st));
+    return W2XC_OK;
+}
+
+int frames_yuv_device(ImageCall c, int n, int chroma, int range, const w2xc_yuv_planes *in, const w2xc_yuv_planes *out)
+{
+    YuvGeom g;
+    int sub = 1;
+    int rc = check_yuv_call(c, n, chroma, range, in, out, &g, &sub);
+    if (rc) return rc;
+    sub = std::min(sub, n);
+    LockedCtx lc;
+    if ((rc = lc.open(c.mn, c.msc, c.o.device))) return rc;
+    c.ctx = lc;
+    for (int b0 = 0; b0 < n; b0 += sub)
+        if ((rc = process_yuv_device(c, g, std::min(sub, n - b0), sub, yuv_from(*in, b0, g.cw != 0), yuv_from(*out, b0, g.cw != 0)))) return rc;
+    return W2XC_OK;
+}
+
+// The device copy of one side of a host call for sub-batches of at most cap frames, at `at` in the image buffer: luma rows w bytes apart; chroma as the caller
+// has it -- planar planes, or the two interleaved planes as one plane of 2 cw-byte rows --, every frame on a 256-byte boundary.  *bytes = what it takes.
+struct YuvMirror {
+    w2xc_yuv_planes d;
+    size_t c_copy_row = 0;   // bytes of a chroma row the copies move (both interleaved planes at once)
+    bool pair = false;
+};
+YuvMirror yuv_mirror(const w2xc_yuv_planes &host, unsigned char *at, int cap, int w, int h, int cw, int ch, size_t *bytes)
+{
+    YuvMirror m;
+    m.d = host;
+    m.d.y = at;
+    m.d.y_stride = (size_t)w;
+    m.d.y_frame_stride = align256((size_t)w * h);
+    size_t used = m.d.y_frame_stride * cap;
+    if (cw) {
+        m.pair = host.c_px == 2;
+        m.c_copy_row = m.pair ? 2 * (size_t)cw : (size_t)cw;
+        m.d.c_stride = m.c_copy_row;
+        const size_t plane = align256(m.c_copy_row * ch);
+        m.d.c_frame_stride = m.pair ? plane : 2 * plane;
+        unsigned char *c0 = at + used;
+        if (m.pair) { m.d.u = c0 + (host.u < host.v ? 0 : 1); m.d.v = c0 + (host.u < host.v ? 1 : 0); }
+        else { m.d.u = c0; m.d.v = c0 + plane; }
+        used += m.d.c_frame_stride * cap;
+    }
+    *bytes = used;
+    return m;
+}
+// frames [b0, b0 + S) of the host side <-> the mirror's first S frames, blocking
+int yuv_copy(const YuvMirror &m, const w2xc_yuv_planes &host, size_t b0, int S, int w, int h, int ch, bool upload)
+{
+    const hipMemcpyKind kind = upload ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    const auto copy = [&](unsigned char *dev, size_t dev_row, unsigned char *hst, size_t hst_row, size_t row, int rows) {
+        return upload ? hipMemcpy2D(dev, dev_row, hst, hst_row, row, rows, kind) : hipMemcpy2D(hst, hst_row, dev, dev_row, row, rows, kind);
+    };
+    for (int i = 0; i < S; i++) {
+        HIP_TRY(copy(m.d.y + i * m.d.y_frame_stride, m.d.y_stride, host.y + (b0 + i) * host.y_frame_stride, host.y_stride, (size_t)w, h));
+        if (!m.c_copy_row) continue;
+        const size_t hoff = (b0 + i) * host.c_frame_stride, doff = i * m.d.c_frame_stride;
+        if (m.pair) HIP_TRY(copy(std::min(m.d.u, m.d.v) + doff, m.d.c_stride, std::min(host.u, host.v) + hoff, host.c_stride, m.c_copy_row, ch));
+        else {
+            HIP_TRY(copy(m.d.u + doff, m.d.c_stride, host.u + hoff, host.c_stride, m.c_copy_row, ch));
+            HIP_TRY(copy(m.d.v + doff, m.d.c_stride, host.v + hoff, host.c_stride, m.c_copy_row, ch));
+        }
+    }
+    return W2XC_OK;
+}
+
+int frames_yuv_host(ImageCall c, int n, int chroma, int range, const w2xc_yuv_planes *in, const w2xc_yuv_planes *out)
+{
+    YuvGeom g;
+    int sub = 1;
+    int rc = check_yuv_call(c, n, chroma, range, in, out, &g, &sub);
+    if (rc) return rc;
+    if (g.cw) for (const w2xc_yuv_planes *s : {in, out})
+        if (s->c_px == 2 && s->v != s->u + 1 && s->u != s->v + 1)
+            return fail(W2XC_ERR_ARG, "host planes with c_px = 2: the two chroma planes must interleave (NV12: v = u + 1; NV21: u = v + 1)");
+    sub = std::min(sub, n);
+    std::vector<int> devs;
+    if ((rc = host_devices(c.o, &devs))) return rc;
+    LockedCtx lc;
+    if ((rc = lc.open(c.mn, c.msc, devs[0]))) return rc;
+    c.ctx = lc;
+    c.st = nullptr;
+    DevCtx *own = c.ctx.owner();
+    size_t in_bytes = 0, out_bytes = 0;
+    yuv_mirror(*in, nullptr, sub, c.w, c.h, g.cw, g.ch, &in_bytes);
+    yuv_mirror(*out, nullptr, sub, g.W, g.H, g.ocw, g.och, &out_bytes);
+    if ((rc = own->img_io.reserve(in_bytes + out_bytes, "the frames"))) return rc;
+    unsigned char *dev = own->img_io.as<unsigned char>();
+    const YuvMirror mi = yuv_mirror(*in, dev, sub, c.w, c.h, g.cw, g.ch, &in_bytes), mo = yuv_mirror(*out, dev + in_bytes, sub, g.W, g.H, g.ocw, g.och, &out_bytes);
+    for (int b0 = 0; b0 < n; b0 += sub) {
+        const int S = std::min(sub, n - b0);
+        if ((rc = yuv_copy(mi, *in, b0, S, c.w, c.h, g.ch, true))) return rc;
+        if ((rc = process_yuv_device(c, g, S, sub, mi.d, mo.d))) { hipDeviceSynchronize(); return rc; }
+        HIP_TRY(hipDeviceSynchronize());
+        if ((rc = yuv_copy(mo, *out, b0, S, g.W, g.H, g.och, false))) return rc;
+    }
+    return W2XC_OK;
+}
+
 }  // namespace
 
 }  // namespace w2xc_eng
@@ -1009,6 +1208,63 @@ int w2xc_process_image_rgba_u8_up2x_batch(w2xc_model *noise_model, w2xc_model *s
 {
     return w2xc_process_image_rgba_u8_up2x_batch_tta(noise_model, scale_model, n, in, in_stride_bytes, w, h, out, out_stride_bytes, iterations, shrink_ratio,
                                                      bleed_passes, opts, 0);
+}
+
+// ---- YUV frames: luma through the models, chroma 2x on bytes ----
+int w2xc_process_frames_yuv_u8_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, const w2xc_yuv_planes *d_in,
+                                      const w2xc_yuv_planes *d_out, int iterations, void *hip_stream, const w2xc_opts *opts)
+try {
+    return frames_yuv_device(ImageCall(noise_model, scale_model, w, h, iterations, 0.0, hip_stream, opts), n, chroma, range, d_in, d_out);
+} W2XC_CATCH_ALL
+
+int w2xc_process_frames_yuv_u8(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, const w2xc_yuv_planes *in,
+                               const w2xc_yuv_planes *out, int iterations, const w2xc_opts *opts)
+try {
+    return frames_yuv_host(ImageCall(noise_model, scale_model, w, h, iterations, 0.0, nullptr, opts), n, chroma, range, in, out);
+} W2XC_CATCH_ALL
+
+// what the three building blocks refuse: n byte planes of bw-byte rows x h at p and n planes of `other` bytes (rows / planes as given) on the other side
+static int check_yuv_block_args(const void *p, size_t frame, size_t row, size_t row_bytes, int rows, int n, int w, int h, const void *q, size_t q_plane, size_t q_ext)
+{
+    if (!p || !q) return fail(W2XC_ERR_ARG, "null argument");
+    if (n < 1 || n > (1 << 20) || w <= 0 || h <= 0 || w > (1 << 22) || h > (1 << 22)) return fail(W2XC_ERR_ARG, "bad plane count / plane size");
+    const size_t ext = (size_t)(rows - 1) * row + row_bytes;
+    if (row < row_bytes || (n > 1 && (frame < ext || q_plane < q_ext))) return fail(W2XC_ERR_ARG, "row / plane strides below a row / a plane");
+    if (ranges_overlap(p, (size_t)(n - 1) * frame + ext, q, (size_t)(n - 1) * q_plane + q_ext)) return fail(W2XC_ERR_ARG, "source and destination overlap");
+    return W2XC_OK;
+}
+
+int w2xc_y8_to_plane_device(const unsigned char *d_src, int n, size_t frame_stride_bytes, size_t stride_bytes, int w, int h, int range, float *d_dst,
+                            size_t plane_stride_bytes, void *hip_stream)
+{
+    if (int rc = check_yuv_block_args(d_src, frame_stride_bytes, stride_bytes, (size_t)(w > 0 ? w : 1), h, n, w, h, d_dst, plane_stride_bytes, (size_t)4 * (w > 0 ? w : 1) * (h > 0 ? h : 1))) return rc;
+    if ((plane_stride_bytes & 3) || (range != W2XC_RANGE_FULL && range != W2XC_RANGE_LIMITED)) return fail(W2XC_ERR_ARG, "plane stride no multiple of 4 / unknown range");
+    HIP_TRY(w2xc_launch_y8_to_plane({const_cast<unsigned char *>(d_src), (long long)frame_stride_bytes, (long long)stride_bytes, 1}, w, h, range, d_dst,
+                                    (long long)(plane_stride_bytes / 4), n, (hipStream_t)hip_stream));
+    return W2XC_OK;
+}
+
+int w2xc_plane_to_y8_device(const float *d_src, int n, size_t plane_stride_bytes, int w, int h, int range, unsigned char *d_dst, size_t frame_stride_bytes,
+                            size_t stride_bytes, void *hip_stream)
+{
+    if (int rc = check_yuv_block_args(d_dst, frame_stride_bytes, stride_bytes, (size_t)(w > 0 ? w : 1), h, n, w, h, d_src, plane_stride_bytes, (size_t)4 * (w > 0 ? w : 1) * (h > 0 ? h : 1))) return rc;
+    if ((plane_stride_bytes & 3) || (range != W2XC_RANGE_FULL && range != W2XC_RANGE_LIMITED)) return fail(W2XC_ERR_ARG, "plane stride no multiple of 4 / unknown range");
+    HIP_TRY(w2xc_launch_plane_to_y8(d_src, (long long)(plane_stride_bytes / 4), w, h, range, {d_dst, (long long)frame_stride_bytes, (long long)stride_bytes, 1}, n,
+                                    (hipStream_t)hip_stream));
+    return W2XC_OK;
+}
+
+int w2xc_chroma2x_u8_device(const unsigned char *d_src, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int cw, int ch,
+                            unsigned char *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int ow, int oh, void *hip_stream)
+{
+    if ((src_px != 1 && src_px != 2) || (dst_px != 1 && dst_px != 2)) return fail(W2XC_ERR_ARG, "src_px / dst_px must be 1 or 2");
+    if (ow < 1 || oh < 1 || ow > 2 * (long long)cw || oh > 2 * (long long)ch) return fail(W2XC_ERR_ARG, "the output size lies outside the 2x enlargement");
+    const size_t drow = (size_t)dst_px * (ow - 1) + 1, dext = (size_t)(oh - 1) * dst_stride_bytes + drow;
+    if (dst_stride_bytes < drow) return fail(W2XC_ERR_ARG, "row / plane strides below a row / a plane");
+    if (int rc = check_yuv_block_args(d_src, src_frame_stride_bytes, src_stride_bytes, (size_t)src_px * ((cw > 0 ? cw : 1) - 1) + 1, ch, n, cw, ch, d_dst, dst_frame_stride_bytes, dext)) return rc;
+    HIP_TRY(w2xc_launch_chroma2x_u8({const_cast<unsigned char *>(d_src), (long long)src_frame_stride_bytes, (long long)src_stride_bytes, src_px}, nullptr, cw, ch,
+                                    {d_dst, (long long)dst_frame_stride_bytes, (long long)dst_stride_bytes, dst_px}, nullptr, ow, oh, n, (hipStream_t)hip_stream));
+    return W2XC_OK;
 }
 
 int w2xc_bleed_rgba_u8_device(const unsigned char *d_in, size_t in_stride_bytes, int w, int h, int passes, unsigned char *d_out_rgb, size_t out_stride_bytes,

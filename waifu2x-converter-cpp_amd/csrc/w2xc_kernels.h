@@ -184,3 +184,24 @@ hipError_t w2xc_launch_tta_spread_u8(const unsigned char *src, size_t img_stride
                                      float *tr, long long ps, int n, hipStream_t st);
 hipError_t w2xc_launch_tta_gather_u8(const float *up, const float *tr, long long ps, int w, int h, unsigned char *dst, size_t img_stride, size_t stride, int px,
                                      int byte0, int n_ch, int planes_per_image, int first_plane, int n, hipStream_t st);
+
+// ---- YUV frames (w2xc_yuv.hip; the arithmetic: include/w2xc_hip.h, "YUV frames") ----
+// One plane of each of n frames, in bytes: frame i's at p + i * frame bytes, rows `row` bytes apart, samples px bytes apart (1 = planar, 2 = one of two interleaved
+// planes: NV12's U at p, V at p + 1).
+struct W2xcU8Planes {
+    unsigned char *p;
+    long long frame, row;
+    int px;
+};
+// luma bytes -> float planes with contiguous rows, plane i at dst + i * ps floats, and back; range = W2XC_RANGE_*
+hipError_t w2xc_launch_y8_to_plane(W2xcU8Planes src, int w, int h, int range, float *dst, long long ps, int n, hipStream_t st);
+hipError_t w2xc_launch_plane_to_y8(const float *src, long long ps, int w, int h, int range, W2xcU8Planes dst, int n, hipStream_t st);
+// the bicubic 2x of chroma on bytes: the planes su (and sv: nullptr = one plane per frame) of cw x ch samples of n frames -> the leading ow x oh samples
+// (ow <= 2 cw, oh <= 2 ch) of their enlargements at du (and dv); bytes of Resize2xCubic + to_u8 on (float)byte * (float)(1.0 / 255.0).  One launch.
+hipError_t w2xc_launch_chroma2x_u8(W2xcU8Planes su, const unsigned char *sv, int cw, int ch, W2xcU8Planes du, unsigned char *dv, int ow, int oh, int n, hipStream_t st);
+// ... and chroma bytes as they are (no 2x step): cw x ch samples per plane
+hipError_t w2xc_launch_chroma_copy_u8(W2xcU8Planes su, const unsigned char *sv, int cw, int ch, W2xcU8Planes du, unsigned char *dv, int n, hipStream_t st);
+// the grid rule of w2xc_launch_chroma2x_u8 (host arithmetic): tiles of W2XC_CHROMA_TQX x W2XC_CHROMA_TQY output quads, at most W2XC_CHROMA_GRID_MAX workgroups
+#define W2XC_CHROMA_TQX 32
+#define W2XC_CHROMA_TQY 16
+#define W2XC_CHROMA_GRID_MAX 2048

@@ -1,5 +1,5 @@
 // w2xc_tta_px.h -- the per-element arithmetic the TTA kernels (w2xc_tta.hip: float planes; w2xc_tta_u8.hip: uint8 images at either end) and the colour
-// stages (w2xc_color.hip) share: ONE definition each of where an element lies in a variant, of the gather's sum and of the float -> uint8 rounding.
+// stages (w2xc_color.hip, w2xc_yuv.hip) share: ONE definition each of where an element lies in a variant, of the gather's sum and of the float -> uint8 rounding.
 // Device code only; every file that includes it is built with -ffp-contract=off.
 #pragma once
 

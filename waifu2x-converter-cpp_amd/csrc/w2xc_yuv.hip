@@ -1,0 +1,189 @@
+// w2xc_yuv.hip -- YUV frames (include/w2xc_hip.h, "YUV frames": w2xc_process_frames_yuv_u8[_device] and their building blocks): luma bytes to the float
+// plane the models take and back, and the 2x enlargement of chroma on bytes.  No colour matrix anywhere.  Built with -ffp-contract=off like w2xc_color.hip:
+// every product and sum below is its own fp32 operation.
+//   Y8ToPlane / PlaneToY8   two stages on the per-pixel skeleton (w2xc_px.h), batch forms, the range a stage member
+//   ChromaCopy              chroma bytes as they are (a call without a 2x step), from either sample stride to either
+//   k_chroma2x_u8           bytes in, bytes out: Resize2xCubic (w2xc_color.hip) on (float)byte * (float)(1.0 / 255.0), then to_u8, without a float plane of
+//                           chroma in memory
+#include "w2xc_kernels.h"
+#include "w2xc_tta_px.h"   // clampi, to_u8
+#include "w2xc_px.h"       // k_px, launch_px, row_col, cubic_coeffs
+
+// luma byte -> y: full range (float)Y * (float)(1.0 / 255.0), limited range ((float)Y - 16) * (float)(1.0 / 219.0).  Frame i's plane at dst + i * ps floats
+struct Y8ToPlane {
+    const unsigned char *src;
+    long long frame, row;
+    int w, limited;
+    float *dst;
+    long long ps;
+    __device__ __forceinline__ void operator()(int img, long long q) const
+    {
+        const RowCol at = row_col(q, w);
+        const float Y = (float)src[img * frame + at.r * row + at.c];
+        dst[img * ps + q] = limited ? (Y - 16.0f) * (float)(1.0 / 219.0) : Y * (float)(1.0 / 255.0);
+    }
+};
+hipError_t w2xc_launch_y8_to_plane(W2xcU8Planes src, int w, int h, int range, float *dst, long long ps, int n, hipStream_t st)
+{
+    return launch_px(Y8ToPlane{src.p, src.frame, src.row, w, range != 0, dst, ps}, (long long)w * h, n, st);
+}
+
+// y -> luma byte: full range to_u8, limited range saturate(rint(y * 219 + 16)), half to even, the product and the sum unfused
+struct PlaneToY8 {
+    const float *src;
+    long long ps;
+    int w, limited;
+    unsigned char *dst;
+    long long frame, row;
+    __device__ __forceinline__ void operator()(int img, long long q) const
+    {
+        const RowCol at = row_col(q, w);
+        const float y = src[img * ps + q];
+        dst[img * frame + at.r * row + at.c] = limited ? (unsigned char)clampi(__float2int_rn(y * 219.0f + 16.0f), 0, 255) : to_u8(y);
+    }
+};
+hipError_t w2xc_launch_plane_to_y8(const float *src, long long ps, int w, int h, int range, W2xcU8Planes dst, int n, hipStream_t st)
+{
+    return launch_px(PlaneToY8{src, ps, w, range != 0, dst.p, dst.frame, dst.row}, (long long)w * h, n, st);
+}
+
+// plane p of the launch: npl planes per frame (U, or U and V), frame p / npl
+struct ChromaCopy {
+    const unsigned char *su, *sv;
+    long long sframe, srow;
+    int spx, cw, npl;
+    unsigned char *du, *dv;
+    long long dframe, drow;
+    int dpx;
+    __device__ __forceinline__ void operator()(int p, long long q) const
+    {
+        const RowCol at = row_col(q, cw);
+        const int f = p / npl, v = p - f * npl;
+        (v ? dv : du)[f * dframe + at.r * drow + (long long)at.c * dpx] = (v ? sv : su)[f * sframe + at.r * srow + (long long)at.c * spx];
+    }
+};
+hipError_t w2xc_launch_chroma_copy_u8(W2xcU8Planes su, const unsigned char *sv, int cw, int ch, W2xcU8Planes du, unsigned char *dv, int n, hipStream_t st)
+{
+    const int npl = sv ? 2 : 1;
+    return launch_px(ChromaCopy{su.p, sv, su.frame, su.row, su.px, cw, npl, du.p, dv, du.frame, du.row, du.px}, (long long)cw * ch, n * npl, st);
+}
+
+// ---- the bicubic 2x of chroma, bytes to bytes ----
+// Resize2xCubic reads, for output column X, fx = (X + 0.5) * 0.5 - 0.5, sx = floor(fx), t = fx - sx and the taps sx - 1 .. sx + 2 clamped into the plane.  The
+// two columns 2 sx + 1 (t = 0.25) and 2 sx + 2 (t = 0.75) share sx and so their taps; the same holds for rows.  A QUAD (qx, qy) is those 2 x 2 outputs of the
+// source pixel (sx, sy) = (qx - 1, qy - 1): columns 2 qx - 1 and 2 qx, rows 2 qy - 1 and 2 qy, all from ONE 4 x 4 neighbourhood.  Quad 0 has only its second
+// column / row inside the plane (sx = -1: output 0, every tap clamped to 0 or 1), the last quad of an uncropped plane only its first.
+// A tile is TQX x TQY quads of one plane of one frame; a workgroup of 256 threads = 32 x 8 takes two quads per thread, TQY / 2 quad rows apart.  The source
+// pixels the tile reads -- its TQX x TQY source pixels, one more to the left and above, two more to the right and below, coordinates clamped as the taps are --
+// are fetched once, converted to c = (float)byte * (float)(1.0 / 255.0) and kept in LDS as floats, rows of CH_LD words: a wave's 32-lane halves read 32
+// consecutive words of a row (conflict-free for any row length; the odd length keeps the dword loader's column-strided writes off each other's banks).
+// DW: the source planes are planar (px = 1) and every row starts on a 4-byte boundary: an aligned group of four source pixels that lies inside the row is one
+// dword load by one thread; everything else (the clamped rim, px = 2) one byte load per LDS word.
+// Stores: the thread's own bytes, one byte store each -- a quad's two columns start on an odd column, and with px = 2 the other plane's bytes lie between
+// them --, never a read-modify-write of a byte that is another thread's.
+#define CH_TQX W2XC_CHROMA_TQX
+#define CH_TQY W2XC_CHROMA_TQY
+#define CH_SW (CH_TQX + 3)
+#define CH_SH (CH_TQY + 3)
+#define CH_LD (CH_SW + 2)
+static_assert(CH_TQX == 32 && CH_TQY == 16 && (CH_LD & 1) == 1 && CH_SW <= CH_LD, "256 threads = 32 x 8 quads, two quad rows per thread");
+
+// the four taps of one row of the neighbourhood, summed in Resize2xCubic's order
+static __device__ __forceinline__ float chroma_row_sum(const float *S, const float *c)
+{
+    float a = S[0] * c[0];
+    a = a + S[1] * c[1];
+    a = a + S[2] * c[2];
+    a = a + S[3] * c[3];
+    return a;
+}
+
+template <bool DW>
+__global__ void __launch_bounds__(256) k_chroma2x_u8(const unsigned char *su, const unsigned char *sv, long long sframe, long long srow, int spx, int cw, int ch,
+                                                     unsigned char *du, unsigned char *dv, long long dframe, long long drow, int dpx, int ow, int oh, int npl,
+                                                     int tiles_x, long long tiles, long long turns)
+{
+    __shared__ float tile[CH_SH * CH_LD];
+    const float s255 = (float)(1.0 / 255.0);
+    const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
+    float c25[4], c75[4];
+    cubic_coeffs(0.25f, c25);
+    cubic_coeffs(0.75f, c75);
+    for (long long turn = blockIdx.x; turn < turns; turn += gridDim.x) {   // a turn: one tile of one plane of one frame
+        const long long p = turn / tiles, t = turn - p * tiles;
+        const long long f = p / npl;
+        const int v = (int)(p - f * npl);
+        const unsigned char *s = (v ? sv : su) + f * sframe;
+        unsigned char *d = (v ? dv : du) + f * dframe;
+        const int qy0 = (int)(t / tiles_x) * CH_TQY, qx0 = (int)(t % tiles_x) * CH_TQX;
+        const int gx0 = qx0 - 2, gy0 = qy0 - 2;   // the source pixel of LDS word (0, 0)
+        __syncthreads();   // (the tile of the loop's previous turn has been read)
+        if (DW) {
+            // column groups of four source pixels from gx0 - 2 (a multiple of 4) on: ten cover the CH_SW columns
+            for (int i = threadIdx.x; i < CH_SH * 10; i += 256) {
+                const int r = i / 10, g = i - r * 10;
+                const int gx4 = gx0 - 2 + 4 * g;
+                const unsigned char *row = s + clampi(gy0 + r, 0, ch - 1) * srow;
+                unsigned b[4];
+                if (gx4 >= 0 && gx4 + 3 < cw) {
+                    const unsigned w4 = *reinterpret_cast<const unsigned *>(row + gx4);
+                    b[0] = w4 & 255u; b[1] = (w4 >> 8) & 255u; b[2] = (w4 >> 16) & 255u; b[3] = w4 >> 24;
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; k++) b[k] = row[clampi(gx4 + k, 0, cw - 1)];
+                }
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const int c = 4 * g - 2 + k;
+                    if (c >= 0 && c < CH_SW) tile[r * CH_LD + c] = (float)b[k] * s255;
+                }
+            }
+        } else {
+            for (int i = threadIdx.x; i < CH_SH * CH_SW; i += 256) {
+                const int r = i / CH_SW, c = i - r * CH_SW;
+                tile[r * CH_LD + c] = (float)s[clampi(gy0 + r, 0, ch - 1) * srow + (long long)clampi(gx0 + c, 0, cw - 1) * spx] * s255;
+            }
+        }
+        __syncthreads();
+        const int qx = qx0 + lx, X0 = 2 * qx - 1;   // the quad's columns X0 (t = 0.25) and X0 + 1 (t = 0.75)
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const int qr = ly + j * (CH_TQY / 2), Y0 = 2 * (qy0 + qr) - 1;   // rows Y0 (t = 0.25) and Y0 + 1 (t = 0.75)
+            if (X0 >= ow || Y0 >= oh) continue;
+            float r25[4], r75[4];   // the horizontal pass of the four rows, for either column
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const float *S = tile + (qr + k) * CH_LD + lx;
+                r25[k] = chroma_row_sum(S, c25);
+                r75[k] = chroma_row_sum(S, c75);
+            }
+            unsigned char *o = d + Y0 * drow + (long long)X0 * dpx;
+            const bool left = X0 >= 0, right = X0 + 1 < ow;
+            if (Y0 >= 0) {
+                if (left) o[0] = to_u8(chroma_row_sum(r25, c25));
+                if (right) o[dpx] = to_u8(chroma_row_sum(r75, c25));
+            }
+            if (Y0 + 1 < oh) {
+                if (left) o[drow] = to_u8(chroma_row_sum(r25, c75));
+                if (right) o[drow + dpx] = to_u8(chroma_row_sum(r75, c75));
+            }
+        }
+    }
+}
+
+hipError_t w2xc_launch_chroma2x_u8(W2xcU8Planes su, const unsigned char *sv, int cw, int ch, W2xcU8Planes du, unsigned char *dv, int ow, int oh, int n, hipStream_t st)
+{
+    if (cw < 1 || ch < 1 || ow < 1 || oh < 1 || ow > 2 * (long long)cw || oh > 2 * (long long)ch || n < 1 || (su.px != 1 && su.px != 2) || (du.px != 1 && du.px != 2) ||
+        !su.p || !du.p || (sv != nullptr) != (dv != nullptr))
+        return hipErrorInvalidValue;
+    const int npl = sv ? 2 : 1;
+    // quads 0 .. ow / 2 and 0 .. oh / 2 hold the ow x oh outputs
+    const int tiles_x = (ow / 2 + CH_TQX) / CH_TQX, tiles_y = (oh / 2 + CH_TQY) / CH_TQY;
+    const long long tiles = (long long)tiles_x * tiles_y, turns = tiles * n * npl;
+    const unsigned grid = (unsigned)(turns > W2XC_CHROMA_GRID_MAX ? W2XC_CHROMA_GRID_MAX : turns);
+    const size_t align = reinterpret_cast<size_t>(su.p) | (sv ? reinterpret_cast<size_t>(sv) : 0) | (size_t)su.row | (n > 1 ? (size_t)su.frame : 0);
+    const bool dw = su.px == 1 && (align & 3) == 0;
+    hipLaunchKernelGGL(dw ? k_chroma2x_u8<true> : k_chroma2x_u8<false>, dim3(grid), dim3(256), 0, st, su.p, sv, su.frame, su.row, su.px, cw, ch, du.p, dv, du.frame,
+                       du.row, du.px, ow, oh, npl, tiles_x, tiles, turns);
+    return hipGetLastError();
+}
