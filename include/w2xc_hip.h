@@ -732,6 +732,65 @@ int w2xc_plane_to_y8_device(const float *d_src, int n, size_t plane_stride_bytes
 int w2xc_chroma2x_u8_device(const unsigned char *d_src, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int cw, int ch,
                             unsigned char *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int ow, int oh, void *hip_stream);
 
+/* ---- YUV frames through RGB models (revision 0.4.1.8) ---------------------------------------------
+ * The frames of the section above through the models that take R, G and B: three-plane models (3 -> ... -> 3, the form most published weights have) and upconv
+ * head models.  The caller names the colour matrix; the call converts the frames' bytes to three float planes per frame, runs the passes of
+ * w2xc_process_image_rgb_u8* on them and converts back -- one colour matrix each way and one rounding to bytes, where the route over an RGB byte image has two
+ * of each.  w2xc_process_frames_yuv_u8* itself goes on refusing these models.  v1 of the reference has no such entry point; the arithmetic is defined here.
+ * Every kernel file involved is built with -ffp-contract=off: every expression below is a sequence of single fp32 operations in the order written.
+ *   constants: computed in double from the two luma weights of `matrix`, then rounded ONCE to float:
+ *              W2XC_MATRIX_BT601: Kr = 0.299, Kb = 0.114    W2XC_MATRIX_BT709: Kr = 0.2126, Kb = 0.0722    W2XC_MATRIX_BT2020 (non-constant luminance): Kr = 0.2627,
+ *              Kb = 0.0593;   Kg = 1.0 - Kr - Kb;   cRV = 2.0 * (1.0 - Kr);   cBU = 2.0 * (1.0 - Kb);   cGV = Kr * cRV / Kg;   cGU = Kb * cBU / Kg;
+ *              iRV = 1.0 / cRV;   iBU = 1.0 / cBU.
+ *   frame:     w2xc_yuv_planes, c_px 1 or 2, NV12 and NV21, the chroma sizes (w + 1) / 2 and so on and W2XC_YUV_420 / _422 / _444 as above.  W2XC_YUV_400 is
+ *              W2XC_ERR_ARG here: a grey frame belongs to the Y call.
+ *   samples in: luma as above: y = (float)Y * (float)(1.0 / 255.0), or ((float)Y - 16.0f) * (float)(1.0 / 219.0) for W2XC_RANGE_LIMITED.  Chroma: cb = (u - 128.0f) * k
+ *              and cr = (v - 128.0f) * k with k = (float)(1.0 / 255.0) for full and (float)(1.0 / 224.0) for limited range, u and v the chroma AT THE LUMA SAMPLE:
+ *   chroma at luma resolution: a chroma sample is CENTRED on its block of luma samples, the siting the chroma kernel above assumes (left-sited chroma stays
+ *              uncorrected).  Along a subsampled axis luma index x reads the chroma samples j = x >> 1 and j' = (x odd ? j + 1 : j - 1), clamped into the plane,
+ *              and the value is 0.75f * C[j] + 0.25f * C[j'] on the bytes as floats -- horizontally first, then vertically on the two row results; along an axis
+ *              that is not subsampled the sample is read as it is.  The - 128 and the scale come after this.  On bytes every one of these operations is exact in
+ *              fp32 (multiples of 1 / 4, then of 1 / 16, below 256): the order is a convention, not a rounding choice.
+ *   to RGB:    R = y + cRV * cr;   B = y + cBU * cb;   G = (y - cGU * cb) - cGV * cr;   each clamped to [0, 1], the models' domain (and what the byte image of
+ *              the old route did).  Three float planes R, G, B per frame.
+ *   passes:    those of w2xc_process_image_rgb_u8* between its two ends: with a noise model x <- CNN_noise(x); then `iterations` (0 or 1) times x <-
+ *              CNN_scale(nearest2x(x)) with the 2x folded into layer 1 -- or, for an upconv head model, the model's own 2x.  The planes between and after the
+ *              passes are unclipped.
+ *   from RGB:  (W x H planes, unclipped)  y' = (Kr * R + Kg * G) + Kb * B;   cb = (B - y') * iBU;   cr = (R - y') * iRV.
+ *              Luma byte: saturate(rint(255 y')), or saturate(rint(y' * 219.0f + 16.0f)) for limited range; half to even.
+ *              Chroma of a subsampled layout is the box mean over the luma block before the rounding: ((a + b) + (c + d)) * 0.25f for 4:2:0 (a, b the upper row
+ *              from left to right, c, d the lower), (a + b) * 0.5f for 4:2:2; a block cut by an odd edge replicates its last column / row.
+ *              Chroma byte: saturate(rint(c * 255.0f + 128.0f)), or saturate(rint(c * 224.0f + 128.0f)) for limited range.
+ *   refused, before a device is touched: a model that is not three planes to three planes W2XC_ERR_PLANES; a head model as noise model, and the options
+ *              w2xc_convert_planes[_up2x]_batch_device refuse (an unknown precision; any 16-bit precision with a head model): W2XC_ERR_UNSUPPORTED; everything the
+ *              Y call refuses as W2XC_ERR_ARG, an unknown `matrix` and W2XC_YUV_400: W2XC_ERR_ARG.
+ * The frame call is DEFINED as this route, by bytes, for every option set the route accepts: w2xc_yuv8_to_rgb_device -> w2xc_convert_planes_batch_device with
+ * nn2x = 0 (the noise pass) -> w2xc_convert_planes_batch_device with nn2x = 1, or w2xc_convert_planes_up2x_batch_device for a head model (the scale pass) ->
+ * w2xc_rgb_to_yuv8_device.  Device form, host form and the sub-batch rule as above; the pipeline's own memory per frame is three float planes per level (the
+ * noise pass's output included) and the frame's bytes in and out.  A sub-batch is ONE launch of each end and the passes between: S >= 2 frames one launch per
+ * layer where the chain has batch kernels, one frame the single-image sequence, bands included.
+ * Left out: left-sited chroma, 10 / 16-bit samples, TTA, the shrink, more than one 2x step, uint8-fused first and last layers (the float RGB planes exist in
+ * memory), multi-device striping, overlapped host sub-batches, a submit / wait pair. */
+#define W2XC_MATRIX_BT601  0
+#define W2XC_MATRIX_BT709  1
+#define W2XC_MATRIX_BT2020 2
+int w2xc_process_frames_yuv_u8_rgb_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int matrix,
+                                          const w2xc_yuv_planes *d_in, const w2xc_yuv_planes *d_out, int iterations, void *hip_stream, const w2xc_opts *opts);
+int w2xc_process_frames_yuv_u8_rgb(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int matrix,
+                                   const w2xc_yuv_planes *in, const w2xc_yuv_planes *out, int iterations, const w2xc_opts *opts);
+/* Its two ends, without a model, on the current device, asynchronous on hip_stream.  Frame i's planes R, G, B have contiguous rows of w floats and lie at d_rgb +
+ * i * image_stride_bytes + {0, 1, 2} * plane_stride_bytes.
+ * yuv8_to_rgb: "samples in", "chroma at luma resolution" and "to RGB" on n frames -> their 3 n float planes.
+ * rgb_to_yuv8: "from RGB" on 3 n float planes of w x h -> n frames.  Only the frames' own samples are written: with c_px = 2 and u, v that do not interleave,
+ *   the bytes between a plane's samples are left as they are.
+ * W2XC_ERR_ARG: null pointers, n < 1, sizes below 1 or above 2^22, what the frame call refuses of a w2xc_yuv_planes, strides that are no multiples of 4 / a plane
+ * stride below a plane / an image stride below three planes where n > 1, an unknown chroma / range / matrix, W2XC_YUV_400, written planes that overlap each other
+ * or a plane that is read. */
+int w2xc_yuv8_to_rgb_device(const w2xc_yuv_planes *d_src, int n, int w, int h, int chroma, int range, int matrix, float *d_rgb, size_t image_stride_bytes,
+                            size_t plane_stride_bytes, void *hip_stream);
+int w2xc_rgb_to_yuv8_device(const float *d_rgb, size_t image_stride_bytes, size_t plane_stride_bytes, int n, int w, int h, int chroma, int range, int matrix,
+                            const w2xc_yuv_planes *d_dst, void *hip_stream);
+
 /* the building blocks on contiguous float planes (device pointers): main.cpp:144 on one plane, :75-76, :171-172 */
 int w2xc_resize2x_cubic_device(const float *d_src, int w, int h, float *d_dst, void *hip_stream);
 /* main.cpp:158-167 on one plane (revision 0.4.1.4): cv::resize(Size(dw, dh), INTER_LINEAR) of the contiguous sw x sh plane d_src into the contiguous

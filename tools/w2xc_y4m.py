@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
-"""tools/w2xc_y4m.py in.y4m out.y4m -m noise|scale|noise_scale --model_dir DIR [--noise_level N] [--range full|limited] [--frames_per_call N]
+"""tools/w2xc_y4m.py in.y4m out.y4m -m noise|scale|noise_scale --model_dir DIR [--noise_level N] [--range full|limited] [--matrix bt601|bt709|bt2020]
+                     [--frames_per_call N]
 
-An 8-bit YUV4MPEG2 stream through the YUV frame call (w2xc_process_frames_yuv_u8): luma through the Y models, chroma enlarged on bytes -- no RGB image, no
-colour matrix.  The reader and the writer are pure Python (numpy for the planes): colour spaces C420* (C420, C420jpeg, C420mpeg2, C420paldv: all of them
+An 8-bit YUV4MPEG2 stream through the YUV frame calls.  The route follows the loaded models, as in tools/w2xc_cli.py.  Y models (one plane in, one out) go
+through w2xc_process_frames_yuv_u8: luma through the models, chroma enlarged on bytes -- no RGB image, no colour matrix; --matrix is ignored.  Models whose
+first layer takes three planes -- three-plane models and the upconv_7 schema, whose scale model enlarges by itself -- go through
+w2xc_process_frames_yuv_u8_rgb, by the colour matrix --matrix (default: bt709 for streams of 720 rows and more, bt601 below); a Cmono stream has no colour
+to convert and is refused with such models.
+The reader and the writer are pure Python (numpy for the planes): colour spaces C420* (C420, C420jpeg, C420mpeg2, C420paldv: all of them
 (w + 1) / 2 x (h + 1) / 2 chroma; the siting is not corrected, include/w2xc_hip.h), C422, C444 and Cmono; no C tag means C420jpeg, as the format says.
 The range is the stream's XCOLORRANGE=FULL|LIMITED where present, otherwise --range (default limited).  Frames go through the host call in groups of
 --frames_per_call.  With a scale step the W and H fields are doubled; F (the frame rate) and A (the pixel aspect) are those of the input -- twice the samples
@@ -22,6 +27,10 @@ if ROOT not in sys.path:
 MAGIC = b"YUV4MPEG2"
 # colour-space tag -> the chroma layout's name (the values of w2xc_amd.YUV_*: 420 = 0, 422 = 1, 444 = 2, 400 = 3)
 LAYOUTS = {"420": 0, "422": 1, "444": 2, "mono": 3}
+
+
+MATRICES = {"bt601": 0, "bt709": 1, "bt2020": 2}   # (the values of w2xc_amd.MATRIX_*)
+MONO_RGB = "Cmono stream with models that take R, G and B: a grey frame has no colour to convert -- use Y models (one plane in, one plane out)"
 
 
 INTERLACED = "interlaced stream (I%s): not supported -- its fields would have to be enlarged separately; deinterlace first"
@@ -154,14 +163,40 @@ def write_frames(f, y, u, v):
             f.write(np.ascontiguousarray(v[i]).tobytes())
 
 
+def default_matrix(h):
+    """the matrix of a stream that does not say: BT.709 for 720 rows and more, BT.601 below"""
+    return "bt709" if h >= 720 else "bt601"
+
+
+def model_route(noise_planes, scale_planes):
+    """'rgb' when the loaded models' first layers take three planes (w2xc_process_frames_yuv_u8_rgb: three-plane models, the upconv_7 schema), 'y' when they
+    take one (w2xc_process_frames_yuv_u8); None = no such model.  Models of different kinds or of neither kind are a Y4mError."""
+    loaded = [p for p in (noise_planes, scale_planes) if p is not None]
+    for p in loaded:
+        if p not in (1, 3):
+            raise Y4mError("a model whose first layer takes %d planes: only Y models (1 plane) and RGB / upconv models (3 planes) are supported" % p)
+    if len(set(loaded)) > 1:
+        raise Y4mError("mixed model kinds: use a noise model and a scale model of the same kind")
+    return "rgb" if loaded and loaded[0] == 3 else "y"
+
+
+def check_route(route, layout):
+    """what a route cannot take of a stream"""
+    if route == "rgb" and layout == LAYOUTS["mono"]:
+        raise Y4mError(MONO_RGB)
+
+
 def build_parser():
-    ap = argparse.ArgumentParser(description="8-bit YUV4MPEG2 streams through waifu2x Y models on an MI355X: luma through the CNN, chroma 2x on bytes")
+    ap = argparse.ArgumentParser(description="8-bit YUV4MPEG2 streams through waifu2x models on an MI355X: Y models (luma through the CNN, chroma 2x on bytes), or RGB and "
+                                             "upconv models by a colour matrix")
     ap.add_argument("input")
     ap.add_argument("output")
     ap.add_argument("-m", "--mode", default="noise_scale", choices=["noise", "scale", "noise_scale"])
     ap.add_argument("--noise_level", type=int, default=1, choices=[1, 2])
     ap.add_argument("--model_dir", default="models")
     ap.add_argument("--range", default="limited", choices=["full", "limited"], help="luma range where the stream has no XCOLORRANGE field")
+    ap.add_argument("--matrix", default=None, choices=sorted(MATRICES),
+                    help="colour matrix for RGB and upconv models (default: bt709 when H >= 720, else bt601); Y models use no matrix and ignore it")
     ap.add_argument("--frames_per_call", type=int, default=8)
     return ap
 
@@ -201,10 +236,15 @@ def main(argv=None):
             if args.mode in ("scale", "noise_scale"):
                 scale = w2xc._ModelSet.from_json(os.path.join(args.model_dir, "scale2.0x_model.json"))
             iterations = 1 if scale is not None else 0
+            route = model_route(noise.planes(0)[0] if noise else None, scale.planes(0)[0] if scale else None)
+            check_route(route, hdr.layout)
+            matrix = MATRICES[args.matrix or default_matrix(hdr.h)]
 
             def process(y, u, v, layout, full):
-                out = w2xc.process_frames_yuv_u8(y, u, v, chroma=layout, noise=noise, scale=scale, iterations=iterations,
-                                                 range=w2xc.RANGE_FULL if full else w2xc.RANGE_LIMITED)
+                rng = w2xc.RANGE_FULL if full else w2xc.RANGE_LIMITED
+                if route == "rgb":
+                    return w2xc.process_frames_yuv_u8_rgb(y, u, v, chroma=layout, noise=noise, scale=scale, iterations=iterations, range=rng, matrix=matrix)
+                out = w2xc.process_frames_yuv_u8(y, u, v, chroma=layout, noise=noise, scale=scale, iterations=iterations, range=rng)
                 return out if len(out) == 3 else (out[0], None, None)
 
             with open(args.output, "wb") as fout:

@@ -33,6 +33,7 @@ KERNEL_AUTO, KERNEL_DIRECT, KERNEL_MFMA, KERNEL_WINOGRAD, KERNEL_WINOGRAD32, KER
 FUSION_AUTO, FUSION_OFF, FUSION_ON, FUSION_FIRST, FUSION_LAST, FUSION_GATHER_LAUNCH, FUSION_PROG = 0, 1, 2, 3, 4, 5, 6
 YUV_420, YUV_422, YUV_444, YUV_400 = 0, 1, 2, 3
 RANGE_FULL, RANGE_LIMITED = 0, 1
+MATRIX_BT601, MATRIX_BT709, MATRIX_BT2020 = 0, 1, 2
 
 
 class W2xcError(RuntimeError):
@@ -141,6 +142,10 @@ def _load():
         "w2xc_tta_gather_u8_device": (ci, [fp, fp, cs, ci, ci, ci, ci, ci, ci, fp, cs, cs, ci, ci, vp]),
         "w2xc_process_frames_yuv_u8_device": (ci, [vp, vp, ci, ci, ci, ci, ci, C.POINTER(YuvPlanes), C.POINTER(YuvPlanes), ci, vp, C.POINTER(Opts)]),
         "w2xc_process_frames_yuv_u8": (ci, [vp, vp, ci, ci, ci, ci, ci, C.POINTER(YuvPlanes), C.POINTER(YuvPlanes), ci, C.POINTER(Opts)]),
+        "w2xc_process_frames_yuv_u8_rgb_device": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(YuvPlanes), C.POINTER(YuvPlanes), ci, vp, C.POINTER(Opts)]),
+        "w2xc_process_frames_yuv_u8_rgb": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(YuvPlanes), C.POINTER(YuvPlanes), ci, C.POINTER(Opts)]),
+        "w2xc_yuv8_to_rgb_device": (ci, [C.POINTER(YuvPlanes), ci, ci, ci, ci, ci, ci, fp, cs, cs, vp]),
+        "w2xc_rgb_to_yuv8_device": (ci, [fp, cs, cs, ci, ci, ci, ci, ci, ci, C.POINTER(YuvPlanes), vp]),
         "w2xc_y8_to_plane_device": (ci, [fp, ci, cs, cs, ci, ci, ci, fp, cs, vp]),
         "w2xc_plane_to_y8_device": (ci, [fp, ci, cs, ci, ci, ci, fp, cs, cs, vp]),
         "w2xc_chroma2x_u8_device": (ci, [fp, ci, cs, cs, ci, ci, ci, fp, cs, cs, ci, ci, ci, vp]),
@@ -1028,6 +1033,18 @@ def process_frames_yuv_u8(y, u=None, v=None, uv=None, chroma=YUV_420, noise=None
     """n YUV frames in one call (w2xc_process_frames_yuv_u8): y is an (n, h, w) uint8 array; chroma either planar -- u and v, (n, ch, cw) uint8 -- or
     interleaved -- uv, (n, ch, cw, 2) uint8, NV12 --, none with YUV_400.  Luma goes through `noise` and, `iterations` (0 or 1) times, through `scale`;
     chroma is enlarged on bytes.  Returns (Y, U, V), or (Y, UV) where the output is interleaved (out_nv12; default: as the input), or (Y,) for YUV_400."""
+    return _frames_yuv_host(None, y, u, v, uv, chroma, noise, scale, iterations, range, opts, out_nv12)
+
+
+def process_frames_yuv_u8_rgb(y, u=None, v=None, uv=None, chroma=YUV_420, noise=None, scale=None, iterations=0, range=RANGE_LIMITED, matrix=MATRIX_BT709,
+                              opts=None, out_nv12=None):
+    """n YUV frames through RGB models -- three planes to three planes -- or an upconv head model as `scale`, by the colour matrix `matrix` (MATRIX_BT601 /
+    _BT709 / _BT2020; w2xc_process_frames_yuv_u8_rgb).  Arrays and result as process_frames_yuv_u8; YUV_400 is refused: a grey frame belongs to that call."""
+    return _frames_yuv_host(matrix, y, u, v, uv, chroma, noise, scale, iterations, range, opts, out_nv12)
+
+
+def _frames_yuv_host(matrix, y, u, v, uv, chroma, noise, scale, iterations, range, opts, out_nv12):
+    """the host frame calls: matrix = None: w2xc_process_frames_yuv_u8, else w2xc_process_frames_yuv_u8_rgb with that matrix"""
     def u8(a, nd, what):
         a = np.asarray(a)
         if a.dtype != np.uint8 or a.ndim != nd:
@@ -1059,9 +1076,31 @@ def process_frames_yuv_u8(y, u=None, v=None, uv=None, chroma=YUV_420, noise=None
         else:
             ou, ov = np.empty((n, och, ocw), np.uint8), np.empty((n, och, ocw), np.uint8)
     si, so = _yuv_side(y, u, v, uv), _yuv_side(oy, ou, ov, ouv)
-    _check(_lib.w2xc_process_frames_yuv_u8(*_handles(noise, scale), n, w, h, chroma, range, C.byref(si), C.byref(so), iterations,
-                                           C.byref(opts) if opts is not None else None))
+    po = C.byref(opts) if opts is not None else None
+    if matrix is None:
+        _check(_lib.w2xc_process_frames_yuv_u8(*_handles(noise, scale), n, w, h, chroma, range, C.byref(si), C.byref(so), iterations, po))
+    else:
+        _check(_lib.w2xc_process_frames_yuv_u8_rgb(*_handles(noise, scale), n, w, h, chroma, range, matrix, C.byref(si), C.byref(so), iterations, po))
     return (oy,) if chroma == YUV_400 else (oy, ouv) if nv12 else (oy, ou, ov)
+
+
+def process_frames_yuv_u8_rgb_device(n, w, h, chroma, d_in, d_out, noise=None, scale=None, iterations=0, range=RANGE_LIMITED, matrix=MATRIX_BT709, stream=0,
+                                     opts=None):
+    """Device-pointer form (w2xc_process_frames_yuv_u8_rgb_device): n frames of w x h described by the YuvPlanes d_in through RGB models or an upconv head
+    model, the (w << iterations) x (h << iterations) frames by d_out.  Asynchronous on `stream`."""
+    _check(_lib.w2xc_process_frames_yuv_u8_rgb_device(*_handles(noise, scale), n, w, h, chroma, range, matrix, C.byref(d_in), C.byref(d_out), iterations,
+                                                      C.c_void_p(stream), C.byref(opts) if opts is not None else None))
+
+
+def yuv8_to_rgb_device(d_src, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes, stream=0):
+    """n frames (the YuvPlanes d_src) -> their 3 n float planes R, G, B in [0, 1] with contiguous rows, frame i's at d_rgb + i * image_stride_bytes +
+    {0, 1, 2} * plane_stride_bytes (w2xc_yuv8_to_rgb_device)."""
+    _check(_lib.w2xc_yuv8_to_rgb_device(C.byref(d_src), n, w, h, chroma, range, matrix, C.c_void_p(d_rgb), image_stride_bytes, plane_stride_bytes, C.c_void_p(stream)))
+
+
+def rgb_to_yuv8_device(d_rgb, image_stride_bytes, plane_stride_bytes, n, w, h, chroma, range, matrix, d_dst, stream=0):
+    """3 n float planes of w x h -> the bytes of n frames (the YuvPlanes d_dst), chroma the box mean over its luma block (w2xc_rgb_to_yuv8_device)."""
+    _check(_lib.w2xc_rgb_to_yuv8_device(C.c_void_p(d_rgb), image_stride_bytes, plane_stride_bytes, n, w, h, chroma, range, matrix, C.byref(d_dst), C.c_void_p(stream)))
 
 
 def y8_to_plane_device(d_src, n, frame_stride_bytes, stride_bytes, w, h, range, d_dst, plane_stride_bytes, stream=0):

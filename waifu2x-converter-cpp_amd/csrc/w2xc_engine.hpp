@@ -29,6 +29,8 @@
 //                           plane calls share
 //                           and YUV frames (w2xc_process_frames_yuv_u8*): process_yuv_device -- luma bytes through run_batch, chroma bytes to bytes
 //                           (kernels in w2xc_yuv.hip, on the per-pixel skeleton of w2xc_px.h)
+//                           and YUV frames through RGB and head models (w2xc_process_frames_yuv_u8_rgb*): process_yuv_rgb_device -- bytes to R, G, B planes by a
+//                           colour matrix, the passes of process_rgb_device (rgb_passes, shared), planes to bytes (kernels in w2xc_yuv_rgb.hip)
 #pragma once
 #include "../../include/w2xc_hip.h"
 

@@ -4,7 +4,8 @@
 // the first and the last layer of the call reading / writing the uint8 image themselves where their kernels can (no counterpart in v1).
 // One pipeline per route -- process_y_device, process_rgb_device -- for S images of one size: the single-image calls, the batches and the RGBA call
 // (process_rgba_device, around either) all run these two.  What is fixed for a call travels as an ImageCall, the uint8 images as U8Images views.
-// And frames that are Y, U and V already (w2xc_process_frames_yuv_u8*): process_yuv_device, the Y pipeline without its colour stages.
+// And frames that are Y, U and V already (w2xc_process_frames_yuv_u8*): process_yuv_device, the Y pipeline without its colour stages -- and, through RGB and
+// head models by a colour matrix the caller names (w2xc_process_frames_yuv_u8_rgb*), process_yuv_rgb_device: the passes of the RGB pipeline between two kernels.
 #include "w2xc_engine.hpp"
 #include "w2xc_host_geom.hpp"
 
@@ -210,33 +211,22 @@ RgbPlan rgb_plan(const ImageCall &c)
     return R;
 }
 
-// A sub-batch of S images (S <= cap; the planes are sized by cap): per level the three planes of image i lie at level + i * 3 ps, ps floats apart.  The
-// colour stages and the shrink are one launch for the sub-batch, and so is every layer of a pass of S >= 2 images where the model's chain has batch kernels
-// (run_batch_planes; elsewhere it is the single-image launch sequence per image, enqueued back to back).  A single image is a sub-batch of one: run_rows.
-// (skip: the float planes start that many bytes into the aux buffer -- reserve_aux)
-// ends (the RGBA call for head models; ROWS_U8_SRC_A / ROWS_U8_DST_PX4 / ROWS_U8_DST_A of w2xc_engine.hpp): `in` is the alpha byte of RGBA pixels, `out` byte 0
-// -- the alpha head: byte 3 -- of RGBA pixels.  Only where the call's first / last layer takes the uint8 image itself (rgb_plan: the caller asks it first).
-int process_rgb_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, size_t skip = 0, int ends = 0)
+// The planes of a level of the sub-batch: image i's three at p + i * 3 ps, w x h each, ps floats apart
+struct RgbLevel {
+    float *p;
+    int w, h;
+    long long ps;
+};
+// The CNN passes of the call -- the noise pass, then `iterations` scale passes -- on a sub-batch, what process_rgb_device and process_yuv_rgb_device (YUV frames
+// through RGB models) share.  *L: in, the planes the first pass reads (p = nullptr: the image is still the caller's uint8 source `in`); out, the planes behind
+// the last pass -- p = nullptr again where that pass wrote the uint8 image `out` itself (R.dst_u8): nothing is left to do.  *base = the next free float of the
+// call's planes, var = the variant planes of a TTA pass.
+int rgb_passes(const ImageCall &c, const RgbPlan &R, int S, int cap, U8In in, U8Out out, int ends, float **base_io, float *var, RgbLevel *L)
 {
-    DevCtx *own = c.ctx.owner();
-    const RgbPlan R = rgb_plan(c);
-    if (((ends & ROWS_U8_SRC_A) && !R.src_u8) || ((ends & (ROWS_U8_DST_PX4 | ROWS_U8_DST_A)) && !R.dst_u8))
-        return fail(W2XC_ERR_ARG, "internal error: RGBA pixels for a pass that runs around float planes");
     const long long in_cs = (ends & ROWS_U8_SRC_A) ? 0 : 1;   // (bytes between the channels of a source pixel)
-    float *base = nullptr;
-    if (R.floats) {
-        if (int rc = reserve_aux(own, skip, R.floats * (size_t)cap)) return rc;
-        base = aux_planes(own, skip);
-    }
-    float *var = base + R.var * (size_t)cap;
-    int cw = c.w, ch = c.h;
-    long long ps = (long long)plane_floats(cw, ch);
-    float *cur = nullptr;   // the current level's planes; nullptr = the image is still the caller's uint8 source
-    if (!R.src_u8) {
-        cur = base;
-        base += 3 * (size_t)cap * ps;
-        HIP_TRY(w2xc_launch_u8_to_rgb_batch(in.p, in.img, in.row, cw, ch, cur, ps, 3 * ps, S, c.st));
-    }
+    float *base = *base_io, *cur = L->p;
+    int cw = L->w, ch = L->h;
+    long long ps = L->ps;
     const int passes = (c.mn ? 1 : 0) + c.iterations;
     for (int p = 1; p <= passes; p++) {
         const bool noise = c.mn && p == 1;
@@ -272,9 +262,43 @@ int process_rgb_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, s
             int rc = run_rows(m, cm, RowsCall::whole(src, 3, head ? cw : nw, head ? ch : nh, dst, up, u8), c.st, c.o);
             if (rc) return rc;
         }
-        if (to_u8) return W2XC_OK;
+        if (to_u8) { L->p = nullptr; return W2XC_OK; }
         cur = nxt; cw = nw; ch = nh; ps = ps2;
     }
+    *base_io = base;
+    *L = {cur, cw, ch, ps};
+    return W2XC_OK;
+}
+
+// A sub-batch of S images (S <= cap; the planes are sized by cap): per level the three planes of image i lie at level + i * 3 ps, ps floats apart.  The
+// colour stages and the shrink are one launch for the sub-batch, and so is every layer of a pass of S >= 2 images where the model's chain has batch kernels
+// (run_batch_planes; elsewhere it is the single-image launch sequence per image, enqueued back to back).  A single image is a sub-batch of one: run_rows.
+// (skip: the float planes start that many bytes into the aux buffer -- reserve_aux)
+// ends (the RGBA call for head models; ROWS_U8_SRC_A / ROWS_U8_DST_PX4 / ROWS_U8_DST_A of w2xc_engine.hpp): `in` is the alpha byte of RGBA pixels, `out` byte 0
+// -- the alpha head: byte 3 -- of RGBA pixels.  Only where the call's first / last layer takes the uint8 image itself (rgb_plan: the caller asks it first).
+int process_rgb_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, size_t skip = 0, int ends = 0)
+{
+    DevCtx *own = c.ctx.owner();
+    const RgbPlan R = rgb_plan(c);
+    if (((ends & ROWS_U8_SRC_A) && !R.src_u8) || ((ends & (ROWS_U8_DST_PX4 | ROWS_U8_DST_A)) && !R.dst_u8))
+        return fail(W2XC_ERR_ARG, "internal error: RGBA pixels for a pass that runs around float planes");
+    float *base = nullptr;
+    if (R.floats) {
+        if (int rc = reserve_aux(own, skip, R.floats * (size_t)cap)) return rc;
+        base = aux_planes(own, skip);
+    }
+    float *var = base + R.var * (size_t)cap;
+    RgbLevel L = {nullptr, c.w, c.h, (long long)plane_floats(c.w, c.h)};   // (p = nullptr: the image is still the caller's uint8 source)
+    if (!R.src_u8) {
+        L.p = base;
+        base += 3 * (size_t)cap * L.ps;
+        HIP_TRY(w2xc_launch_u8_to_rgb_batch(in.p, in.img, in.row, L.w, L.h, L.p, L.ps, 3 * L.ps, S, c.st));
+    }
+    if (int rc = rgb_passes(c, R, S, cap, in, out, ends, &base, var, &L)) return rc;
+    if (!L.p) return W2XC_OK;   // (the last pass wrote the caller's image)
+    float *cur = L.p;
+    int cw = L.w, ch = L.h;
+    long long ps = L.ps;
     if (c.shrink > 0.0) {
         const long long pss = (long long)plane_floats(c.fw, c.fh);
         HIP_TRY(w2xc_launch_resize_linear_batch(cur, cur, 3 * S, ps, cw, ch, base, pss, c.fw, c.fh, 3 * S, c.st));   // (the 3 S planes of a level are ps apart)
@@ -298,7 +322,7 @@ int process_sub_batch(bool rgb, const ImageCall &c, int S, int cap, U8In in, U8O
 // The RGBA call gives its own bytes per image (per_image; 0 = the 3-channel call's, above) and ya = 2 on the Y route: a Y brings its alpha plane, so a
 // sub-batch run_batch takes whole holds half as many images.
 enum PlanKind { PLAN_Y, PLAN_RGB };
-int plan_image_call(PlanKind kind, const ImageCall &c, int *sub, size_t per_image = 0, int ya = 1)
+int plan_image_call(PlanKind kind, const ImageCall &c, int *sub, size_t per_image = 0, int ya = 1, const char *call = "w2xc_process_image_rgb_u8*")
 {
     const bool rgb = kind == PLAN_RGB;
     const w2xc_model *pass[2] = {c.mn, c.msc};
@@ -306,8 +330,8 @@ int plan_image_call(PlanKind kind, const ImageCall &c, int *sub, size_t per_imag
         if (!m) continue;
         if (m->layers.empty()) return fail(W2XC_ERR_ARG, "model has no layers");
         if (m->layers[0].nin != 3 || m->layers.back().nout != 3)
-            return fail(W2XC_ERR_PLANES, "w2xc_process_image_rgb_u8*: three planes in and three planes out (the model takes %d and gives %d)",
-                        m->layers[0].nin, m->layers.back().nout);
+            return fail(W2XC_ERR_PLANES, "%s: three planes in and three planes out (the model takes %d and gives %d)", call, m->layers[0].nin,
+                        m->layers.back().nout);
     }
     size_t k = 65535;
     pass[1] = c.iterations > 0 ? c.msc : nullptr;
@@ -771,6 +795,8 @@ int image_batch_host(bool rgb, ImageCall c, int n, const unsigned char *const *i
 // Luma through the models as the planes of run_batch, chroma from bytes to bytes in one launch: no colour matrix, no float plane of chroma.
 struct YuvGeom {
     int chroma, range;
+    bool rgb = false;       // the frames go through RGB / head models (w2xc_process_frames_yuv_u8_rgb*): process_yuv_rgb_device
+    int matrix = 0;         // ... by this colour matrix (W2XC_MATRIX_*)
     int cw = 0, ch = 0;     // the chroma planes of a w x h frame (0 x 0: W2XC_YUV_400)
     int ocw = 0, och = 0;   // ... of the call's output frame
     int W = 0, H = 0;       // the output frame
@@ -813,17 +839,36 @@ int check_yuv_side(const w2xc_yuv_planes *s, int n, int w, int h, int cw, int ch
     return W2XC_OK;
 }
 
-// everything both forms refuse, before a device is touched; *g = the geometry, *sub = frames per sub-batch
-int check_yuv_call(ImageCall &c, int n, int chroma, int range, const w2xc_yuv_planes *in, const w2xc_yuv_planes *out, YuvGeom *g, int *sub)
+// the float planes of one frame on the RGB route: three per level, the noise pass's output included
+size_t yuv_rgb_aux_floats(const ImageCall &c)
 {
-    int rc = check_process_args(c);
-    if (rc || (rc = check_y_models(c))) return rc;
+    return 3 * ((c.mn ? 2 : 1) * plane_floats(c.w, c.h) + (c.iterations ? plane_floats(2 * c.w, 2 * c.h) : 0));
+}
+
+// the precisions of the RGB route: those w2xc_convert_planes[_up2x]_batch_device take (the models' plane form is plan_image_call's check)
+int check_yuv_rgb_precision(const ImageCall &c)
+{
+    if (c.o.precision != W2XC_PRECISION_FP32 && split_terms(c.o) == 0)
+        return fail(W2XC_ERR_UNSUPPORTED, "w2xc_process_frames_yuv_u8_rgb* supports W2XC_PRECISION_FP32 / BF16X2 / BF16X3 / FP16X2");
+    if (c.iterations > 0 && c.msc && c.msc->has_head() && c.o.precision != W2XC_PRECISION_FP32)
+        return fail(W2XC_ERR_UNSUPPORTED, "16-bit precision modes: not available for a model with an upconv head (W2XC_PRECISION_FP32 only)");
+    return W2XC_OK;
+}
+
+// everything both forms refuse, before a device is touched; *g = the geometry, *sub = frames per sub-batch.  rgb: the call is w2xc_process_frames_yuv_u8_rgb*
+// -- RGB models, or an upconv head model as scale model, and a colour matrix; a grey frame (W2XC_YUV_400) belongs to the Y call
+int check_yuv_call(ImageCall &c, bool rgb, int n, int chroma, int range, int matrix, const w2xc_yuv_planes *in, const w2xc_yuv_planes *out, YuvGeom *g, int *sub)
+{
+    int rc = check_process_args(c, rgb);
+    if (rc || (rc = rgb ? check_yuv_rgb_precision(c) : check_y_models(c))) return rc;
     if (c.iterations < 0 || c.iterations > 1) return fail(W2XC_ERR_ARG, "iterations must be 0 or 1 (got %d)", c.iterations);
     if (n < 1 || n > (1 << 20)) return fail(W2XC_ERR_ARG, "batch of %d frames", n);
     if (c.w <= 0 || c.h <= 0 || c.w > (1 << 22) || c.h > (1 << 22)) return fail(W2XC_ERR_ARG, "bad frame size");
     if (chroma < W2XC_YUV_420 || chroma > W2XC_YUV_400) return fail(W2XC_ERR_ARG, "unknown chroma layout %d", chroma);
     if (range != W2XC_RANGE_FULL && range != W2XC_RANGE_LIMITED) return fail(W2XC_ERR_ARG, "unknown range %d", range);
-    g->chroma = chroma; g->range = range;
+    if (rgb && chroma == W2XC_YUV_400) return fail(W2XC_ERR_ARG, "a frame without chroma (W2XC_YUV_400) belongs to w2xc_process_frames_yuv_u8*");
+    if (rgb && (matrix < W2XC_MATRIX_BT601 || matrix > W2XC_MATRIX_BT2020)) return fail(W2XC_ERR_ARG, "unknown colour matrix %d", matrix);
+    g->chroma = chroma; g->range = range; g->rgb = rgb; g->matrix = matrix;
     g->W = c.w << c.iterations; g->H = c.h << c.iterations;
     if (chroma != W2XC_YUV_400) {
         const bool half_x = chroma != W2XC_YUV_444, half_y = chroma == W2XC_YUV_420;
@@ -834,8 +879,9 @@ int check_yuv_call(ImageCall &c, int n, int chroma, int range, const w2xc_yuv_pl
     if ((rc = check_yuv_side(in, n, c.w, c.h, g->cw, g->ch, 0, iv)) || (rc = check_yuv_side(out, n, g->W, g->H, g->ocw, g->och, 1, iv))) return rc;
     if ((rc = check_batch_overlap(iv))) return rc;
     c.fw = g->W; c.fh = g->H;
-    const size_t per = yuv_aux_floats(c.w, c.h, c.iterations) * sizeof(float) + yuv_frame_bytes(c.w, c.h, g->cw, g->ch) + yuv_frame_bytes(g->W, g->H, g->ocw, g->och);
-    return plan_image_call(PLAN_Y, c, sub, per);
+    const size_t per = (rgb ? yuv_rgb_aux_floats(c) : yuv_aux_floats(c.w, c.h, c.iterations)) * sizeof(float) + yuv_frame_bytes(c.w, c.h, g->cw, g->ch) +
+                       yuv_frame_bytes(g->W, g->H, g->ocw, g->och);
+    return plan_image_call(rgb ? PLAN_RGB : PLAN_Y, c, sub, per, 1, "w2xc_process_frames_yuv_u8_rgb*");
 }
 
 W2xcU8Planes chroma_planes(const w2xc_yuv_planes &s) { return {s.u, (long long)s.c_frame_stride, (long long)s.c_stride, s.c_px}; }
@@ -868,18 +914,44 @@ int process_yuv_device(const ImageCall &c, const YuvGeom &g, int S, int cap, con
     return W2XC_OK;
 }
 
-int frames_yuv_device(ImageCall c, int n, int chroma, int range, const w2xc_yuv_planes *in, const w2xc_yuv_planes *out)
+// YUV frames through RGB models, a sub-batch of S frames: ONE launch from the frames' bytes to three float planes per frame (k_yuv8_to_rgb), the passes of
+// process_rgb_device with float planes at both ends (rgb_passes: S >= 2 one run_batch_planes per pass, S = 1 run_rows, so bands work; a head model's pass
+// enlarges by itself), ONE launch from the planes to the bytes of the output frames (k_rgb_to_yuv8).
+int process_yuv_rgb_device(const ImageCall &c, const YuvGeom &g, int S, int cap, const w2xc_yuv_planes &in, const w2xc_yuv_planes &out)
+{
+    DevCtx *own = c.ctx.owner();
+    RgbPlan R;   // (float planes at both ends: no layer takes a uint8 image)
+    R.floats = yuv_rgb_aux_floats(c);
+    if (int rc = reserve_aux(own, 0, R.floats * (size_t)cap)) return rc;
+    float *base = aux_planes(own, 0);
+    RgbLevel L = {base, c.w, c.h, (long long)plane_floats(c.w, c.h)};
+    base += 3 * (size_t)cap * L.ps;
+    HIP_TRY(w2xc_launch_yuv8_to_rgb({in.y, (long long)in.y_frame_stride, (long long)in.y_stride, 1}, chroma_planes(in), in.v, c.w, c.h, g.chroma, g.range, g.matrix,
+                                    L.p, 3 * L.ps, L.ps, S, c.st));
+    if (int rc = rgb_passes(c, R, S, cap, U8In{nullptr, 0, 0}, U8Out{nullptr, 0, 0}, 0, &base, nullptr, &L)) return rc;
+    HIP_TRY(w2xc_launch_rgb_to_yuv8(L.p, 3 * L.ps, L.ps, L.w, L.h, g.chroma, g.range, g.matrix, {out.y, (long long)out.y_frame_stride, (long long)out.y_stride, 1},
+                                    chroma_planes(out), out.v, S, c.st));
+    return W2XC_OK;
+}
+
+int process_yuv_sub_batch(const ImageCall &c, const YuvGeom &g, int S, int cap, const w2xc_yuv_planes &in, const w2xc_yuv_planes &out)
+{
+    return g.rgb ? process_yuv_rgb_device(c, g, S, cap, in, out) : process_yuv_device(c, g, S, cap, in, out);
+}
+
+// rgb: w2xc_process_frames_yuv_u8_rgb* (RGB and head models by the colour matrix `matrix`); otherwise the Y call, which has no matrix
+int frames_yuv_device(ImageCall c, bool rgb, int n, int chroma, int range, int matrix, const w2xc_yuv_planes *in, const w2xc_yuv_planes *out)
 {
     YuvGeom g;
     int sub = 1;
-    int rc = check_yuv_call(c, n, chroma, range, in, out, &g, &sub);
+    int rc = check_yuv_call(c, rgb, n, chroma, range, matrix, in, out, &g, &sub);
     if (rc) return rc;
     sub = std::min(sub, n);
     LockedCtx lc;
     if ((rc = lc.open(c.mn, c.msc, c.o.device))) return rc;
     c.ctx = lc;
     for (int b0 = 0; b0 < n; b0 += sub)
-        if ((rc = process_yuv_device(c, g, std::min(sub, n - b0), sub, yuv_from(*in, b0, g.cw != 0), yuv_from(*out, b0, g.cw != 0)))) return rc;
+        if ((rc = process_yuv_sub_batch(c, g, std::min(sub, n - b0), sub, yuv_from(*in, b0, g.cw != 0), yuv_from(*out, b0, g.cw != 0)))) return rc;
     return W2XC_OK;
 }
 
@@ -932,11 +1004,11 @@ int yuv_copy(const YuvMirror &m, const w2xc_yuv_planes &host, size_t b0, int S, 
     return W2XC_OK;
 }
 
-int frames_yuv_host(ImageCall c, int n, int chroma, int range, const w2xc_yuv_planes *in, const w2xc_yuv_planes *out)
+int frames_yuv_host(ImageCall c, bool rgb, int n, int chroma, int range, int matrix, const w2xc_yuv_planes *in, const w2xc_yuv_planes *out)
 {
     YuvGeom g;
     int sub = 1;
-    int rc = check_yuv_call(c, n, chroma, range, in, out, &g, &sub);
+    int rc = check_yuv_call(c, rgb, n, chroma, range, matrix, in, out, &g, &sub);
     if (rc) return rc;
     if (g.cw) for (const w2xc_yuv_planes *s : {in, out})
         if (s->c_px == 2 && s->v != s->u + 1 && s->u != s->v + 1)
@@ -958,7 +1030,7 @@ int frames_yuv_host(ImageCall c, int n, int chroma, int range, const w2xc_yuv_pl
     for (int b0 = 0; b0 < n; b0 += sub) {
         const int S = std::min(sub, n - b0);
         if ((rc = yuv_copy(mi, *in, b0, S, c.w, c.h, g.ch, true))) return rc;
-        if ((rc = process_yuv_device(c, g, S, sub, mi.d, mo.d))) { hipDeviceSynchronize(); return rc; }
+        if ((rc = process_yuv_sub_batch(c, g, S, sub, mi.d, mo.d))) { hipDeviceSynchronize(); return rc; }
         HIP_TRY(hipDeviceSynchronize());
         if ((rc = yuv_copy(mo, *out, b0, S, g.W, g.H, g.och, false))) return rc;
     }
@@ -1214,13 +1286,68 @@ int w2xc_process_image_rgba_u8_up2x_batch(w2xc_model *noise_model, w2xc_model *s
 int w2xc_process_frames_yuv_u8_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, const w2xc_yuv_planes *d_in,
                                       const w2xc_yuv_planes *d_out, int iterations, void *hip_stream, const w2xc_opts *opts)
 try {
-    return frames_yuv_device(ImageCall(noise_model, scale_model, w, h, iterations, 0.0, hip_stream, opts), n, chroma, range, d_in, d_out);
+    return frames_yuv_device(ImageCall(noise_model, scale_model, w, h, iterations, 0.0, hip_stream, opts), false, n, chroma, range, 0, d_in, d_out);
 } W2XC_CATCH_ALL
 
 int w2xc_process_frames_yuv_u8(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, const w2xc_yuv_planes *in,
                                const w2xc_yuv_planes *out, int iterations, const w2xc_opts *opts)
 try {
-    return frames_yuv_host(ImageCall(noise_model, scale_model, w, h, iterations, 0.0, nullptr, opts), n, chroma, range, in, out);
+    return frames_yuv_host(ImageCall(noise_model, scale_model, w, h, iterations, 0.0, nullptr, opts), false, n, chroma, range, 0, in, out);
+} W2XC_CATCH_ALL
+
+// ---- YUV frames through RGB and head models, by a colour matrix ----
+int w2xc_process_frames_yuv_u8_rgb_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int matrix,
+                                          const w2xc_yuv_planes *d_in, const w2xc_yuv_planes *d_out, int iterations, void *hip_stream, const w2xc_opts *opts)
+try {
+    return frames_yuv_device(ImageCall(noise_model, scale_model, w, h, iterations, 0.0, hip_stream, opts), true, n, chroma, range, matrix, d_in, d_out);
+} W2XC_CATCH_ALL
+
+int w2xc_process_frames_yuv_u8_rgb(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int matrix, const w2xc_yuv_planes *in,
+                                   const w2xc_yuv_planes *out, int iterations, const w2xc_opts *opts)
+try {
+    return frames_yuv_host(ImageCall(noise_model, scale_model, w, h, iterations, 0.0, nullptr, opts), true, n, chroma, range, matrix, in, out);
+} W2XC_CATCH_ALL
+
+// what the two blocks refuse: the frames' side as check_yuv_side refuses it, the 3 n float planes, and the two sides overlapping
+static int check_yuv_rgb_block_args(const w2xc_yuv_planes *f, bool f_is_out, int n, int w, int h, int chroma, int range, int matrix, const float *rgb,
+                                    size_t image_stride_bytes, size_t plane_stride_bytes)
+{
+    if (!f || !rgb) return fail(W2XC_ERR_ARG, "null argument");
+    if (n < 1 || n > (1 << 20) || w <= 0 || h <= 0 || w > (1 << 22) || h > (1 << 22)) return fail(W2XC_ERR_ARG, "bad frame count / frame size");
+    if (chroma == W2XC_YUV_400) return fail(W2XC_ERR_ARG, "a frame without chroma (W2XC_YUV_400) has no colour to convert");
+    if (chroma < W2XC_YUV_420 || chroma > W2XC_YUV_444) return fail(W2XC_ERR_ARG, "unknown chroma layout %d", chroma);
+    if (range != W2XC_RANGE_FULL && range != W2XC_RANGE_LIMITED) return fail(W2XC_ERR_ARG, "unknown range %d", range);
+    if (matrix < W2XC_MATRIX_BT601 || matrix > W2XC_MATRIX_BT2020) return fail(W2XC_ERR_ARG, "unknown colour matrix %d", matrix);
+    const size_t plane = (size_t)4 * w * h;
+    if ((image_stride_bytes & 3) || (plane_stride_bytes & 3) || plane_stride_bytes < plane || (n > 1 && image_stride_bytes < 2 * plane_stride_bytes + plane))
+        return fail(W2XC_ERR_ARG, "plane / image strides: multiples of 4, a plane stride of at least a plane, an image stride of at least three planes");
+    const int cw = chroma != W2XC_YUV_444 ? (w + 1) / 2 : w, ch = chroma == W2XC_YUV_420 ? (h + 1) / 2 : h;
+    std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> iv;
+    if (int rc = check_yuv_side(f, n, w, h, cw, ch, f_is_out ? 1 : 0, iv)) return rc;
+    for (int i = 0; i < n; i++) for (int p = 0; p < 3; p++) {
+        const uintptr_t at = (uintptr_t)rgb + i * image_stride_bytes + p * plane_stride_bytes;
+        iv.push_back({{at, at + plane}, f_is_out ? 0 : 1});
+    }
+    return check_batch_overlap(iv);
+}
+
+int w2xc_yuv8_to_rgb_device(const w2xc_yuv_planes *d_src, int n, int w, int h, int chroma, int range, int matrix, float *d_rgb, size_t image_stride_bytes,
+                            size_t plane_stride_bytes, void *hip_stream)
+try {
+    if (int rc = check_yuv_rgb_block_args(d_src, false, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes)) return rc;
+    HIP_TRY(w2xc_launch_yuv8_to_rgb({d_src->y, (long long)d_src->y_frame_stride, (long long)d_src->y_stride, 1}, chroma_planes(*d_src), d_src->v, w, h, chroma, range,
+                                    matrix, d_rgb, (long long)(image_stride_bytes / 4), (long long)(plane_stride_bytes / 4), n, (hipStream_t)hip_stream));
+    return W2XC_OK;
+} W2XC_CATCH_ALL
+
+int w2xc_rgb_to_yuv8_device(const float *d_rgb, size_t image_stride_bytes, size_t plane_stride_bytes, int n, int w, int h, int chroma, int range, int matrix,
+                            const w2xc_yuv_planes *d_dst, void *hip_stream)
+try {
+    if (int rc = check_yuv_rgb_block_args(d_dst, true, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes)) return rc;
+    HIP_TRY(w2xc_launch_rgb_to_yuv8(d_rgb, (long long)(image_stride_bytes / 4), (long long)(plane_stride_bytes / 4), w, h, chroma, range, matrix,
+                                    {d_dst->y, (long long)d_dst->y_frame_stride, (long long)d_dst->y_stride, 1}, chroma_planes(*d_dst), d_dst->v, n,
+                                    (hipStream_t)hip_stream));
+    return W2XC_OK;
 } W2XC_CATCH_ALL
 
 // what the three building blocks refuse: n byte planes of bw-byte rows x h at p and n planes of `other` bytes (rows / planes as given) on the other side

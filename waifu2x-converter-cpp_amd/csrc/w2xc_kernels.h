@@ -205,3 +205,19 @@ hipError_t w2xc_launch_chroma_copy_u8(W2xcU8Planes su, const unsigned char *sv, 
 #define W2XC_CHROMA_TQX 32
 #define W2XC_CHROMA_TQY 16
 #define W2XC_CHROMA_GRID_MAX 2048
+
+// ---- YUV frames through RGB models (w2xc_yuv_rgb.hip; the arithmetic: include/w2xc_hip.h, "YUV frames through RGB models") ----
+// The constants of a colour matrix as the kernels take them: doubles from the two luma weights, each rounded once to float (by the launchers).
+struct W2xcYuvToRgb { float cRV, cBU, cGV, cGU; };
+struct W2xcRgbToYuv { float Kr, Kg, Kb, iBU, iRV; };
+// n frames (luma y: px = 1; chroma u and v: one W2xcU8Planes geometry for both, px = 1 or 2) -> their 3 n float planes with contiguous rows of w: frame i's R, G
+// and B at rgb + i * is + {0, 1, 2} * ps FLOATS; chroma = W2XC_YUV_420 / _422 / _444, range = W2XC_RANGE_*, matrix = W2XC_MATRIX_*.  One launch.
+hipError_t w2xc_launch_yuv8_to_rgb(W2xcU8Planes y, W2xcU8Planes u, const unsigned char *v, int w, int h, int chroma, int range, int matrix, float *rgb, long long is,
+                                   long long ps, int n, hipStream_t st);
+// ... and back: 3 n float planes of w x h -> the bytes of n frames.  One launch; only the frames' own samples are written.
+hipError_t w2xc_launch_rgb_to_yuv8(const float *rgb, long long is, long long ps, int w, int h, int chroma, int range, int matrix, W2xcU8Planes y, W2xcU8Planes u,
+                                   unsigned char *v, int n, hipStream_t st);
+// the grid rule of both launchers (host arithmetic): tiles of W2XC_YUVRGB_TCX x W2XC_YUVRGB_TCY chroma samples of one frame, at most W2XC_YUVRGB_GRID_MAX workgroups
+#define W2XC_YUVRGB_TCX 32
+#define W2XC_YUVRGB_TCY 16
+#define W2XC_YUVRGB_GRID_MAX 2048

@@ -224,6 +224,8 @@ const char *w2xc_last_error(void) { return g_last_error.c_str(); }
 // stays at 0.4.1.6.1 (callers compare it for equality): the new revision is found by the presence of the symbols.
 // 0.4.1.7: YUV frames -- w2xc_process_frames_yuv_u8[_device], w2xc_y8_to_plane_device, w2xc_plane_to_y8_device, w2xc_chroma2x_u8_device and the struct
 // w2xc_yuv_planes (additive; w2xc_opts stays 56 bytes; the string stays, the revision is found by the presence of the symbols).
+// 0.4.1.8: YUV frames through RGB and head models -- w2xc_process_frames_yuv_u8_rgb[_device], w2xc_yuv8_to_rgb_device, w2xc_rgb_to_yuv8_device and the constants
+// W2XC_MATRIX_* (additive; w2xc_opts stays 56 bytes; the string stays, the revision is found by the presence of the symbols).
 const char *w2xc_version(void) { return "w2xc_hip 0.4.1.6.1 (gfx950)"; }
 
 int w2xc_plan_rows(const w2xc_model *m, int w, int view_y0, int view_h, int plane_h, int row_begin, int row_end, const w2xc_opts *opts, w2xc_row_plan *plan)
