@@ -5,7 +5,10 @@
 //   * the runs of finished tile rows the drainer stitches tile a band's rows once;
 //   * a job flag of an earlier band never reads as finished, up to and across the restart of the epochs;
 //   * the sub-batches of a host batch cover its images once;
-//   * the image pipeline's plane buffer holds every plane the batched pipeline lays out in it.
+//   * the image pipeline's plane buffer holds every plane the batched pipeline lays out in it;
+//   * the uint8 images of the RGBA call and its float planes lie in the declared order, each on a 256-byte boundary, none over another;
+//   * the chroma planes of a YUV frame have the sizes the public header states, the device mirror of a host frame call keeps every plane of every frame
+//     apart, and the float planes the frame pipelines carve are the ones the call reserved.
 // Prints the first failing input of each property; exit status = number of failed properties.
 #include "../../waifu2x-converter-cpp_amd/csrc/w2xc_host_geom.hpp"
 
@@ -235,6 +238,128 @@ static void test_image_aux()
                       }
 }
 
+// the sweep of the RGBA and YUV layouts: odd and even sides, below, at and above a 64-float plane boundary, mixed across w and h
+static const int kSides[] = {1, 2, 3, 17, 64, 65};
+static const int kNSides = sizeof kSides / sizeof *kSides;
+
+// The RGBA call keeps five kinds of uint8 images and its float planes in one buffer, cap images of each kind side by side (plan_rgba gives the bytes per image:
+// multiples of 256, 0 where the call has none).  Each region starts on a 256-byte boundary, directly behind the one before it in the declared order -- so none
+// lies over another and an absent one takes no room -- and the buffer ends where the float planes do.
+static void test_rgba_layout()
+{
+    for (int a = 0; a < kNSides; a++)
+        for (int b = 0; b < kNSides; b++)
+            for (int cap = 1; cap <= 3; cap += 2)
+                for (int it = 0; it <= 1; it++)
+                    for (int mask = 0; mask < 32; mask++) {
+                        const int w = kSides[a], h = kSides[b], fw = w << it, fh = h << it;
+                        RgbaImageBytes R;
+                        const size_t src3 = align256((size_t)w * 3 * h), dst3 = align256((size_t)fw * 3 * fh);
+                        R.bled = mask & 1 ? src3 : 0; R.stamp = mask & 2 ? align256((size_t)w * 2 * h) : 0; R.res = mask & 4 ? dst3 : 0;
+                        R.grey = mask & 8 ? src3 : 0; R.ares = mask & 16 ? dst3 : 0;
+                        R.floats = image_aux_floats(w, h, it, 0.0, it != 0);
+                        const RgbaLayout L(R, (size_t)cap);
+                        const size_t off[] = {L.bled, L.stamp, L.res, L.grey, L.ares, L.head}, img[] = {R.bled, R.stamp, R.res, R.grey, R.ares};
+                        CHECK(off[0] == 0, "%dx%d cap=%d mask=%d: the first region starts at %zu", w, h, cap, mask, off[0]);
+                        for (int k = 0; k < 5; k++) {
+                            CHECK(off[k] % 256 == 0 && off[k + 1] % 256 == 0, "%dx%d cap=%d mask=%d: region %d starts at %zu, the next at %zu", w, h, cap, mask, k, off[k], off[k + 1]);
+                            CHECK(off[k + 1] == off[k] + (size_t)cap * img[k], "%dx%d cap=%d mask=%d: region %d [%zu, +%d x %zu) and the next at %zu", w, h, cap, mask, k, off[k],
+                                  cap, img[k], off[k + 1]);
+                        }
+                        CHECK(L.bytes == L.head + (size_t)cap * R.floats * sizeof(float), "%dx%d cap=%d mask=%d: %zu bytes, the float planes end at %zu", w, h, cap, mask, L.bytes,
+                              L.head + (size_t)cap * R.floats * sizeof(float));
+                    }
+}
+
+// The chroma planes of a w x h frame are ceil(w / 2) x ceil(h / 2) (4:2:0), ceil(w / 2) x h (4:2:2), w x h (4:4:4), none (4:0:0) -- include/w2xc_hip.h.
+// The device mirror of one side of a host frame call holds cap frames: all luma planes, then all chroma -- planar U and V, or the two interleaved planes as ONE
+// plane of 2 cw-byte rows in which U and V are neighbouring bytes.  No plane of any frame touches another, every frame of luma and of chroma starts on a
+// 256-byte boundary, a frame stride covers the frame, the planes hold yuv_frame_bytes samples per frame, and the total -- what img_io.reserve is given -- is
+// where the last plane's 256-byte share ends.
+static void test_yuv_mirror()
+{
+    const int layouts[] = {W2XC_YUV_420, W2XC_YUV_422, W2XC_YUV_444, W2XC_YUV_400};
+    for (int a = 0; a < kNSides; a++)
+        for (int b = 0; b < kNSides; b++)
+            for (int li = 0; li < 4; li++)
+                for (int c_px = 1; c_px <= 2; c_px++)
+                    for (int u_first = 0; u_first <= 1; u_first++)
+                        for (int cap = 1; cap <= 3; cap += 2) {
+                            const int w = kSides[a], h = kSides[b], chroma = layouts[li];
+                            const ChromaSize cs = yuv_chroma_size(w, h, chroma);
+                            const int want_cw = chroma == W2XC_YUV_400 ? 0 : chroma == W2XC_YUV_444 ? w : w / 2 + w % 2;
+                            const int want_ch = chroma == W2XC_YUV_400 ? 0 : chroma == W2XC_YUV_420 ? h / 2 + h % 2 : h;
+                            CHECK(cs.cw == want_cw && cs.ch == want_ch, "%dx%d layout %d: chroma planes of %dx%d, the header says %dx%d", w, h, chroma, cs.cw, cs.ch, want_cw, want_ch);
+                            const YuvMirrorLayout m = yuv_mirror_layout(c_px, u_first != 0, cap, w, h, cs.cw, cs.ch);
+                            // [start, end) of every plane of every frame, and the samples they hold
+                            std::vector<std::pair<size_t, size_t> > planes;
+                            size_t samples = 0;
+                            CHECK(m.y_stride >= (size_t)w, "%dx%d: luma rows %zu bytes apart", w, h, m.y_stride);
+                            const size_t y_ext = (size_t)(h - 1) * m.y_stride + w;
+                            CHECK(m.y_frame_stride >= y_ext && m.y_frame_stride % 256 == 0, "%dx%d: luma frames %zu bytes apart, a plane takes %zu", w, h, m.y_frame_stride, y_ext);
+                            for (int i = 0; i < cap; i++) planes.push_back(std::make_pair(i * m.y_frame_stride, i * m.y_frame_stride + y_ext));
+                            samples += (size_t)w * h;
+                            if (cs.cw) {
+                                const size_t first = std::min(m.u, m.v), row = m.pair ? 2 * (size_t)cs.cw : (size_t)cs.cw, c_ext = (size_t)(cs.ch - 1) * m.c_stride + row;
+                                CHECK(m.pair == (c_px == 2) && m.c_copy_row == row && m.c_stride >= row, "%dx%d layout %d c_px=%d: chroma rows of %zu bytes, %zu apart, copied %zu at a time",
+                                      w, h, chroma, c_px, row, m.c_stride, m.c_copy_row);
+                                CHECK(first % 256 == 0 && m.c_frame_stride % 256 == 0, "%dx%d layout %d c_px=%d: chroma frames start at %zu + i * %zu", w, h, chroma, c_px, first, m.c_frame_stride);
+                                // a plane as the kernels address it -- samples c_px bytes apart -- lies inside the rows the copies move
+                                CHECK(chroma_row_bytes(cs.cw, c_px) <= row, "%dx%d layout %d c_px=%d: a row of %zu bytes in rows of %zu", w, h, chroma, c_px, chroma_row_bytes(cs.cw, c_px), row);
+                                if (m.pair) {
+                                    CHECK(m.c_stride == 2 * (size_t)cs.cw, "%dx%d layout %d: interleaved rows %zu bytes apart, 2 cw = %d", w, h, chroma, m.c_stride, 2 * cs.cw);
+                                    CHECK(u_first ? m.v == m.u + 1 : m.u == m.v + 1, "%dx%d layout %d u_first=%d: U at %zu, V at %zu", w, h, chroma, u_first, m.u, m.v);
+                                    CHECK(m.c_frame_stride >= c_ext, "%dx%d layout %d: interleaved frames %zu apart, a plane takes %zu", w, h, chroma, m.c_frame_stride, c_ext);
+                                    for (int i = 0; i < cap; i++) planes.push_back(std::make_pair(first + i * m.c_frame_stride, first + i * m.c_frame_stride + c_ext));
+                                } else {
+                                    CHECK(m.c_frame_stride >= std::max(m.u, m.v) - first + c_ext, "%dx%d layout %d: planar frames %zu apart, U and V take %zu", w, h, chroma,
+                                          m.c_frame_stride, std::max(m.u, m.v) - first + c_ext);
+                                    for (int i = 0; i < cap; i++) {
+                                        planes.push_back(std::make_pair(m.u + i * m.c_frame_stride, m.u + i * m.c_frame_stride + c_ext));
+                                        planes.push_back(std::make_pair(m.v + i * m.c_frame_stride, m.v + i * m.c_frame_stride + c_ext));
+                                    }
+                                }
+                                samples += 2 * (size_t)cs.cw * cs.ch;
+                            } else CHECK(m.c_copy_row == 0, "%dx%d layout %d: no chroma, but rows of %zu bytes to copy", w, h, chroma, m.c_copy_row);
+                            CHECK(samples == yuv_frame_bytes(w, h, cs.cw, cs.ch), "%dx%d layout %d: the planes hold %zu samples, yuv_frame_bytes says %zu", w, h, chroma, samples,
+                                  yuv_frame_bytes(w, h, cs.cw, cs.ch));
+                            std::sort(planes.begin(), planes.end());
+                            for (size_t k = 1; k < planes.size(); k++)
+                                CHECK(planes[k - 1].second <= planes[k].first, "%dx%d layout %d c_px=%d cap=%d: the plane at %zu runs to %zu, into the one at %zu", w, h, chroma, c_px, cap,
+                                      planes[k - 1].first, planes[k - 1].second, planes[k].first);
+                            const size_t end = planes.back().second;
+                            CHECK(m.bytes >= end && m.bytes == align256(end), "%dx%d layout %d c_px=%d cap=%d: %zu bytes, the last plane ends at %zu", w, h, chroma, c_px, cap, m.bytes, end);
+                        }
+}
+
+// The float planes the frame pipelines carve per frame, walked level by level, against what the calls reserve per frame.
+//   process_yuv_device      level 0: the luma plane and the noise pass's output; with a scale pass ONE plane of the doubled size.  yuv_aux_floats reserves two
+//                           planes on every level, so with a scale pass exactly one plane of the doubled size stays unused.
+//   process_yuv_rgb_device  level 0: R, G, B; the noise pass's three output planes on the same level; a scale pass's three of the doubled size.  yuv_rgb_aux_floats
+//                           is their sum.
+static void test_yuv_aux()
+{
+    for (int a = 0; a < kNSides; a++)
+        for (int b = 0; b < kNSides; b++)
+            for (int it = 0; it <= 1; it++)
+                for (int noise = 0; noise <= 1; noise++) {
+                    const int w = kSides[a], h = kSides[b];
+                    size_t y_carved = 2 * plane_floats(w, h), rgb_carved = 3 * plane_floats(w, h);
+                    if (noise) rgb_carved += 3 * plane_floats(w, h);
+                    int lw = w, lh = h;
+                    for (int l = 0; l < it; l++) {
+                        lw *= 2; lh *= 2;
+                        y_carved += plane_floats(lw, lh);
+                        rgb_carved += 3 * plane_floats(lw, lh);
+                    }
+                    const size_t spare = it ? plane_floats(2 * w, 2 * h) : 0;
+                    CHECK(yuv_aux_floats(w, h, it) == y_carved + spare, "%dx%d it=%d: the Y call reserves %zu floats per frame, carves %zu and leaves %zu", w, h, it,
+                          yuv_aux_floats(w, h, it), y_carved, spare);
+                    CHECK(yuv_rgb_aux_floats(noise != 0, w, h, it) == rgb_carved, "%dx%d it=%d noise=%d: the RGB call reserves %zu floats per frame, carves %zu", w, h, it, noise,
+                          yuv_rgb_aux_floats(noise != 0, w, h, it), rgb_carved);
+                }
+}
+
 int main()
 {
     test_unit_rows();
@@ -244,6 +369,9 @@ int main()
     test_flag_epochs();
     test_batch_stripes();
     test_image_aux();
+    test_rgba_layout();
+    test_yuv_mirror();
+    test_yuv_aux();
     std::printf(g_failed ? "%d properties FAILED\n" : "all host geometry properties hold\n", g_failed);
     return g_failed;
 }

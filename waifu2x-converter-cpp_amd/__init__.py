@@ -763,6 +763,14 @@ def _image_host(entry, who, img, channels, noise, scale, iterations, opts, shrin
     return out
 
 
+def _image_device(entry, noise, scale, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, iterations, shrink_ratio, stream, opts, batch=None, extra=(), tail=()):
+    """the device-pointer image calls: one image, or -- batch = (n, in_image_stride_bytes, out_image_stride_bytes) -- n of them; `extra` = the entry's
+    arguments between shrink_ratio and the stream (bleed_passes), `tail` those behind opts (tta)"""
+    n, in_img, out_img = ((), (), ()) if batch is None else ((batch[0],), (batch[1],), (batch[2],))
+    _check(entry(*_handles(noise, scale), *n, C.c_void_p(d_in), *in_img, in_stride_bytes, w, h, C.c_void_p(d_out), *out_img, out_stride_bytes, iterations,
+                 float(shrink_ratio), *extra, C.c_void_p(stream), C.byref(opts) if opts is not None else None, *tail))
+
+
 def process_image_u8(img, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, tta=False):
     """The CLI's processing modes on an h x w x 3 uint8 image (main.cpp -m noise | scale | noise_scale):
     `noise` / `scale` are _ModelSet objects (either may be None); shrink_ratio = the final INTER_LINEAR shrink
@@ -776,8 +784,7 @@ def process_image_u8_device(d_in, in_stride_bytes, w, h, d_out, out_stride_bytes
                             stream=0, opts=None, tta=False):
     """Device-pointer form (w2xc_process_image_u8_ex_device / _tta_device): w x h x 3 uint8 at d_in, the result at d_out.  Asynchronous on `stream`."""
     entry, tail = _tta_entry("w2xc_process_image_u8_ex_device", tta)
-    _check(entry(*_handles(noise, scale), C.c_void_p(d_in), in_stride_bytes, w, h, C.c_void_p(d_out), out_stride_bytes, iterations, float(shrink_ratio),
-                 C.c_void_p(stream), C.byref(opts) if opts is not None else None, *tail))
+    _image_device(entry, noise, scale, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, iterations, shrink_ratio, stream, opts, tail=tail)
 
 
 def process_image_u8_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, out=None, tta=False):
@@ -827,8 +834,8 @@ def process_image_u8_batch_device(n, d_in, in_image_stride_bytes, in_stride_byte
     """Device-pointer image batch (w2xc_process_image_u8_batch_device): n images of w x h x 3 uint8 at d_in + i * in_image_stride_bytes, the
     outputs at d_out + i * out_image_stride_bytes.  Asynchronous on `stream`."""
     entry, tail = _tta_entry("w2xc_process_image_u8_batch_device", tta)
-    _check(entry(*_handles(noise, scale), n, C.c_void_p(d_in), in_image_stride_bytes, in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes,
-                 out_stride_bytes, iterations, float(shrink_ratio), C.c_void_p(stream), C.byref(opts) if opts is not None else None, *tail))
+    _image_device(entry, noise, scale, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, iterations, shrink_ratio, stream, opts,
+                  batch=(n, in_image_stride_bytes, out_image_stride_bytes), tail=tail)
 
 
 # ---- RGB models (3 planes in, 3 out): the image calls above for the form most published waifu2x weights have ----
@@ -845,8 +852,7 @@ def process_image_rgb_u8_device(d_in, in_stride_bytes, w, h, d_out, out_stride_b
                                 stream=0, opts=None, tta=False):
     """Device-pointer form (w2xc_process_image_rgb_u8_ex_device): w x h x 3 uint8 at d_in, the result at d_out.  Asynchronous on `stream`."""
     entry, tail = _tta_entry("w2xc_process_image_rgb_u8_ex_device", tta)
-    _check(entry(*_handles(noise, scale), C.c_void_p(d_in), in_stride_bytes, w, h, C.c_void_p(d_out), out_stride_bytes, iterations, float(shrink_ratio),
-                 C.c_void_p(stream), C.byref(opts) if opts is not None else None, *tail))
+    _image_device(entry, noise, scale, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, iterations, shrink_ratio, stream, opts, tail=tail)
 
 
 def process_image_rgb_u8_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, out=None, tta=False):
@@ -860,8 +866,8 @@ def process_image_rgb_u8_batch_device(n, d_in, in_image_stride_bytes, in_stride_
                                       noise=None, scale=None, iterations=0, shrink_ratio=0.0, stream=0, opts=None, tta=False):
     """Device-pointer image batch for RGB models (w2xc_process_image_rgb_u8_batch_device); arguments as process_image_u8_batch_device."""
     entry, tail = _tta_entry("w2xc_process_image_rgb_u8_batch_device", tta)
-    _check(entry(*_handles(noise, scale), n, C.c_void_p(d_in), in_image_stride_bytes, in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes,
-                 out_stride_bytes, iterations, float(shrink_ratio), C.c_void_p(stream), C.byref(opts) if opts is not None else None, *tail))
+    _image_device(entry, noise, scale, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, iterations, shrink_ratio, stream, opts,
+                  batch=(n, in_image_stride_bytes, out_image_stride_bytes), tail=tail)
 
 
 def process_image_rgb_u8_up2x_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, out=None, tta=False):
@@ -875,9 +881,8 @@ def process_image_rgb_u8_up2x_batch(imgs, noise=None, scale=None, iterations=0, 
 def process_image_rgb_u8_up2x_batch_device(n, d_in, in_image_stride_bytes, in_stride_bytes, w, h, d_out, out_image_stride_bytes, out_stride_bytes,
                                            noise=None, scale=None, iterations=0, shrink_ratio=0.0, stream=0, opts=None, tta=False):
     """Device-pointer form (w2xc_process_image_rgb_u8_up2x_batch_device); arguments as process_image_rgb_u8_batch_device."""
-    _check(_lib.w2xc_process_image_rgb_u8_up2x_batch_device(*_handles(noise, scale), n, C.c_void_p(d_in), in_image_stride_bytes, in_stride_bytes, w, h,
-                                                            C.c_void_p(d_out), out_image_stride_bytes, out_stride_bytes, iterations, float(shrink_ratio),
-                                                            C.c_void_p(stream), C.byref(opts) if opts is not None else None, 1 if tta else 0))
+    _image_device(_lib.w2xc_process_image_rgb_u8_up2x_batch_device, noise, scale, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, iterations, shrink_ratio,
+                  stream, opts, batch=(n, in_image_stride_bytes, out_image_stride_bytes), tail=(1 if tta else 0,))
 
 
 def u8_to_rgb_device(d_in, in_stride_bytes, w, h, d_planes, stream=0):
@@ -949,9 +954,8 @@ def process_image_rgba_u8_device(d_in, in_stride_bytes, w, h, d_out, out_stride_
     if tta:
         return process_image_rgba_u8_batch_device(1, d_in, 0, in_stride_bytes, w, h, d_out, 0, out_stride_bytes, noise, scale, iterations, shrink_ratio,
                                                   bleed_passes, stream, opts, tta=tta)
-    _check(_lib.w2xc_process_image_rgba_u8_ex_device(*_handles(noise, scale), C.c_void_p(d_in), in_stride_bytes, w, h,
-                                                     C.c_void_p(d_out), out_stride_bytes, iterations, float(shrink_ratio), int(bleed_passes),
-                                                     C.c_void_p(stream), C.byref(opts) if opts is not None else None))
+    _image_device(_lib.w2xc_process_image_rgba_u8_ex_device, noise, scale, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, iterations, shrink_ratio, stream,
+                  opts, extra=(int(bleed_passes),))
 
 
 def process_image_rgba_u8_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, bleed_passes=-1, out=None, tta=False):
@@ -969,8 +973,8 @@ def process_image_rgba_u8_batch_device(n, d_in, in_image_stride_bytes, in_stride
     """Device-pointer batch of RGBA images (w2xc_process_image_rgba_u8_batch_device / _batch_tta_device): n images of w x h x 4 uint8 at
     d_in + i * in_image_stride_bytes, the outputs at d_out + i * out_image_stride_bytes.  Asynchronous on `stream`."""
     entry, tail = _tta_entry("w2xc_process_image_rgba_u8_batch_device", tta)
-    _check(entry(*_handles(noise, scale), n, C.c_void_p(d_in), in_image_stride_bytes, in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes,
-                 out_stride_bytes, iterations, float(shrink_ratio), int(bleed_passes), C.c_void_p(stream), C.byref(opts) if opts is not None else None, *tail))
+    _image_device(entry, noise, scale, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, iterations, shrink_ratio, stream, opts,
+                  batch=(n, in_image_stride_bytes, out_image_stride_bytes), extra=(int(bleed_passes),), tail=tail)
 
 
 def process_image_rgba_u8_up2x_batch(imgs, noise=None, scale=None, iterations=0, opts=None, shrink_ratio=0.0, bleed_passes=-1, out=None, tta=False):
@@ -986,8 +990,8 @@ def process_image_rgba_u8_up2x_batch_device(n, d_in, in_image_stride_bytes, in_s
                                             noise=None, scale=None, iterations=0, shrink_ratio=0.0, bleed_passes=-1, stream=0, opts=None, tta=False):
     """Device-pointer form (w2xc_process_image_rgba_u8_up2x_batch_device / _batch_tta_device); arguments as process_image_rgba_u8_batch_device."""
     entry, tail = _tta_entry("w2xc_process_image_rgba_u8_up2x_batch_device", tta)
-    _check(entry(*_handles(noise, scale), n, C.c_void_p(d_in), in_image_stride_bytes, in_stride_bytes, w, h, C.c_void_p(d_out), out_image_stride_bytes,
-                 out_stride_bytes, iterations, float(shrink_ratio), int(bleed_passes), C.c_void_p(stream), C.byref(opts) if opts is not None else None, *tail))
+    _image_device(entry, noise, scale, d_in, in_stride_bytes, w, h, d_out, out_stride_bytes, iterations, shrink_ratio, stream, opts,
+                  batch=(n, in_image_stride_bytes, out_image_stride_bytes), extra=(int(bleed_passes),), tail=tail)
 
 
 def bleed_rgba_u8_device(d_in, in_stride_bytes, w, h, passes, d_out_rgb, out_stride_bytes, stream=0):

@@ -18,19 +18,21 @@
 //   w2xc_scratch.hpp        Scratch: the one owner of every grow-only device / page-locked buffer (reserve, release, the drain rule); a context lists its
 //                           buffers once, DevCtx::for_each_scratch below -- destruction, w2xc_model_trim and w2xc_debug_fill_scratch go by that list
 //   w2xc_host_geom.hpp      the integers of the host side: a unit's rows and source view, staging chunks and their taper, the rows finished job rows
-//                           cover, the job flags' epoch test, sub-batch striping, the image pipeline's planes (no HIP header; tests/cpp/host_geom_test.cpp)
+//                           cover, the job flags' epoch test, sub-batch striping, the image pipelines' planes, the RGBA call's and the YUV mirror's layout (no HIP header;
+//                           tests/cpp/host_geom_test.cpp)
 //   w2xc_host_pipeline.cpp  host plane in -> host plane out: staging rings, three streams, the feeder with its Uploader, the drainer (Stitcher), the unit
 //                           fan-out (run_units), the host batch pipeline
 //   w2xc_filter.cpp         Model::filter at the host / device boundary (src/modelHandler.cpp:26-72)
+//   w2xc_image.hpp          what the image units share: ImageCall, the U8Images views, the two pipelines' entry, tta_pass, the plan and the argument checks, and the call
+//                           forms -- host single, host batch, device batch -- every family runs its sub-batch callable through
 //   w2xc_image.cpp          N2: the CLI's image pipeline around the plane conversion (main.cpp:74-172): one pipeline for Y models and one for RGB models, each
-//                           for S images of one size; the single-image, batch and RGBA entry points around them
-//                           and test-time augmentation: tta_pass (spread -> the CNN on the 8 variants -> gather; kernels in w2xc_tta.hip, and -- the uint8
-//                           image at the outer side: the RGB and head routes of the RGBA TTA calls -- w2xc_tta_u8.hip), which both pipelines and the TTA
-//                           plane calls share
-//                           and YUV frames (w2xc_process_frames_yuv_u8*): process_yuv_device -- luma bytes through run_batch, chroma bytes to bytes
-//                           (kernels in w2xc_yuv.hip, on the per-pixel skeleton of w2xc_px.h)
-//                           and YUV frames through RGB and head models (w2xc_process_frames_yuv_u8_rgb*): process_yuv_rgb_device -- bytes to R, G, B planes by a
-//                           colour matrix, the passes of process_rgb_device (rgb_passes, shared), planes to bytes (kernels in w2xc_yuv_rgb.hip)
+//                           for S images of one size (process_y_device, process_rgb_device; rgb_passes); the plan, the checks, the call forms' bodies; the
+//                           single-image and batch entry points of both, the colour and resize blocks
+//   w2xc_image_tta.cpp      test-time augmentation: tta_pass (spread -> the CNN on the 8 variants -> gather; kernels in w2xc_tta.hip, and -- the uint8 image at the
+//                           outer side -- w2xc_tta_u8.hip), the TTA plane calls, the spread / gather blocks
+//   w2xc_image_rgba.cpp     RGBA images (w2xc_process_image_rgba_u8*): process_rgba_device around either pipeline; the bleed call and its scratch
+//   w2xc_image_yuv.cpp      YUV frames (w2xc_process_frames_yuv_u8*): process_yuv_device -- luma bytes through run_batch, chroma bytes to bytes (w2xc_yuv.hip) -- and,
+//                           through RGB and head models by a colour matrix (..._rgb*), process_yuv_rgb_device -- rgb_passes between two kernels (w2xc_yuv_rgb.hip)
 #pragma once
 #include "../../include/w2xc_hip.h"
 

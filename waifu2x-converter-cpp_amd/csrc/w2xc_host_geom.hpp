@@ -1,7 +1,10 @@
-// w2xc_host_geom.hpp -- the integers of the host side of the engine (w2xc_host_pipeline.cpp, w2xc_image.cpp): which rows a unit converts and reads, the
-// staging chunk sizes, which output rows finished tile rows cover, the job flags' epoch test, how a batch is cut into sub-batches, the float planes of the
-// image pipeline.  No HIP header: tests/cpp/host_geom_test.cpp builds it with g++ and checks what the consumers of these numbers need.
+// w2xc_host_geom.hpp -- the integers of the host side of the engine (w2xc_host_pipeline.cpp, the image units w2xc_image*.cpp): which rows a unit converts and
+// reads, the staging chunk sizes, which output rows finished tile rows cover, the job flags' epoch test, how a batch is cut into sub-batches, the float planes
+// of the image pipelines, where the RGBA call's uint8 images lie (w2xc_image_rgba.cpp), the planes of a YUV frame and their device mirror (w2xc_image_yuv.cpp).
+// No HIP header: tests/cpp/host_geom_test.cpp builds it with g++ and checks what the consumers of these numbers need.
 #pragma once
+#include "../../include/w2xc_hip.h"
+
 #include <algorithm>
 #include <cstddef>
 #include <utility>
@@ -103,6 +106,77 @@ inline size_t image_aux_floats(int w, int h, int iterations, double shrink, bool
     final_size(w, h, iterations, shrink, &fw, &fh);
     if (shrink > 0.0) need += (ya + 2) * plane_floats(fw, fh);
     return need;
+}
+
+
+inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// ---- RGBA images (w2xc_image_rgba.cpp) ----
+// what ONE image of the call takes: bytes of each of its uint8 images (a multiple of 256; 0 = the call has none), and its float planes
+struct RgbaImageBytes {
+    size_t bled = 0, stamp = 0, res = 0, grey = 0, ares = 0;
+    size_t floats = 0;
+};
+// where those lie for sub-batches of at most cap images: byte offsets, in this order; head = where the float planes start, bytes = where they end
+struct RgbaLayout {
+    size_t bled, stamp, res, grey, ares, head, bytes;
+    RgbaLayout(const RgbaImageBytes &R, size_t cap)
+    {
+        size_t at = 0;
+        const auto take = [&](size_t img) { const size_t a = at; at += cap * img; return a; };
+        bled = take(R.bled); stamp = take(R.stamp); res = take(R.res); grey = take(R.grey); ares = take(R.ares);
+        head = at;
+        bytes = at + cap * R.floats * sizeof(float);
+    }
+};
+
+// ---- YUV frames (w2xc_image_yuv.cpp) ----
+// the chroma planes of a w x h frame (include/w2xc_hip.h; yuv_chroma_size of __init__.py is its mirror): 0 x 0 for W2XC_YUV_400
+struct ChromaSize { int cw, ch; };
+inline ChromaSize yuv_chroma_size(int w, int h, int chroma)
+{
+    if (chroma == W2XC_YUV_400) return {0, 0};
+    return {chroma != W2XC_YUV_444 ? (w + 1) / 2 : w, chroma == W2XC_YUV_420 ? (h + 1) / 2 : h};
+}
+// bytes from the first to behind the last sample of a chroma row of cw samples px bytes apart
+inline size_t chroma_row_bytes(int cw, int px) { return (size_t)px * (cw - 1) + 1; }
+// the float planes of one frame of the Y call: two luma planes per level
+inline size_t yuv_aux_floats(int w, int h, int iterations) { return 2 * plane_floats(w, h) + (iterations ? 2 * plane_floats(2 * w, 2 * h) : 0); }
+// ... of the call through RGB models: three per level, the noise pass's output included
+inline size_t yuv_rgb_aux_floats(bool noise, int w, int h, int iterations)
+{
+    return 3 * ((noise ? 2 : 1) * plane_floats(w, h) + (iterations ? plane_floats(2 * w, 2 * h) : 0));
+}
+// the bytes of one frame's planes: w x h luma, two planes of cw x ch chroma
+inline size_t yuv_frame_bytes(int w, int h, int cw, int ch) { return (size_t)w * h + 2 * (size_t)cw * ch; }
+
+// The device copy of one side of a host frame call for sub-batches of at most cap frames, as byte offsets from its start: luma rows w bytes apart; chroma as
+// the caller has it -- planar planes (c_px = 1), or the two interleaved planes (c_px = 2; u_first: U is the lower byte, NV12) as ONE plane of 2 cw-byte rows --,
+// every frame of luma and of chroma on a 256-byte boundary.  bytes = what it takes: the end of the last plane's share.
+struct YuvMirrorLayout {
+    size_t y_stride = 0, y_frame_stride = 0;
+    bool pair = false;
+    size_t c_copy_row = 0;   // bytes of a chroma row the copies move (both interleaved planes at once; 0: no chroma)
+    size_t c_stride = 0, c_frame_stride = 0, u = 0, v = 0;
+    size_t bytes = 0;
+};
+inline YuvMirrorLayout yuv_mirror_layout(int c_px, bool u_first, int cap, int w, int h, int cw, int ch)
+{
+    YuvMirrorLayout m;
+    m.y_stride = (size_t)w;
+    m.y_frame_stride = align256((size_t)w * h);
+    m.bytes = m.y_frame_stride * cap;
+    if (cw) {
+        m.pair = c_px == 2;
+        m.c_copy_row = m.pair ? 2 * (size_t)cw : (size_t)cw;
+        m.c_stride = m.c_copy_row;
+        const size_t plane = align256(m.c_copy_row * ch), c0 = m.bytes;
+        m.c_frame_stride = m.pair ? plane : 2 * plane;
+        if (m.pair) { m.u = c0 + (u_first ? 0 : 1); m.v = c0 + (u_first ? 1 : 0); }
+        else { m.u = c0; m.v = c0 + plane; }
+        m.bytes += m.c_frame_stride * cap;
+    }
+    return m;
 }
 
 }  // namespace w2xc_eng

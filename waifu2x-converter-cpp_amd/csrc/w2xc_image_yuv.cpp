@@ -1,0 +1,353 @@
+// w2xc_image_yuv.cpp -- frames that are Y, U and V already (w2xc_process_frames_yuv_u8*): process_yuv_device, the Y pipeline without its colour stages (kernels in
+// w2xc_yuv.hip) -- and, through RGB and head models by a colour matrix the caller names (w2xc_process_frames_yuv_u8_rgb*), process_yuv_rgb_device: the passes of the
+// RGB pipeline (rgb_passes, w2xc_image.cpp) between two kernels (w2xc_yuv_rgb.hip).  The host forms' device mirror, and the five building blocks.
+#include "w2xc_image.hpp"
+
+namespace w2xc_eng {
+
+namespace {
+
+// ---- YUV frames (w2xc_process_frames_yuv_u8*; the arithmetic: include/w2xc_hip.h) ----
+// Luma through the models as the planes of run_batch, chroma from bytes to bytes in one launch: no colour matrix, no float plane of chroma.
+struct YuvGeom {
+    int chroma, range;
+    bool rgb = false;       // the frames go through RGB / head models (w2xc_process_frames_yuv_u8_rgb*): process_yuv_rgb_device
+    int matrix = 0;         // ... by this colour matrix (W2XC_MATRIX_*)
+    int cw = 0, ch = 0;     // the chroma planes of a w x h frame (0 x 0: W2XC_YUV_400)
+    int ocw = 0, och = 0;   // ... of the call's output frame
+    int W = 0, H = 0;       // the output frame
+};
+// (the sizes of the chroma planes, the float planes and the bytes of a frame: yuv_chroma_size, yuv_aux_floats, yuv_rgb_aux_floats, yuv_frame_bytes -- w2xc_host_geom.hpp)
+
+// one side's planes from frame b0 on
+w2xc_yuv_planes yuv_from(const w2xc_yuv_planes &s, size_t b0, bool chroma)
+{
+    w2xc_yuv_planes t = s;
+    t.y += b0 * s.y_frame_stride;
+    if (chroma) { t.u += b0 * s.c_frame_stride; t.v += b0 * s.c_frame_stride; }
+    return t;
+}
+
+// n frames of w x h luma and cw x ch chroma on one side: pointers, strides, c_px; its byte ranges go to iv tagged `tag` (check_batch_overlap)
+int check_yuv_side(const w2xc_yuv_planes *s, int n, int w, int h, int cw, int ch, int tag, std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> &iv)
+{
+    if (!s || !s->y) return fail(W2XC_ERR_ARG, "null argument");
+    const size_t y_ext = image_extent(h, s->y_stride, w, 1);
+    if (s->y_stride < (size_t)w || (n > 1 && s->y_frame_stride < y_ext)) return fail(W2XC_ERR_ARG, "luma: row stride below the row's bytes / frame stride below a plane");
+    for (int i = 0; i < n; i++) iv.push_back({{(uintptr_t)s->y + i * s->y_frame_stride, (uintptr_t)s->y + i * s->y_frame_stride + y_ext}, tag});
+    if (!cw) return W2XC_OK;
+    if (!s->u || !s->v) return fail(W2XC_ERR_ARG, "null argument");
+    if (s->c_px != 1 && s->c_px != 2) return fail(W2XC_ERR_ARG, "c_px must be 1 (planar) or 2 (interleaved), got %d", s->c_px);
+    const size_t row = chroma_row_bytes(cw, s->c_px), c_ext = (size_t)(ch - 1) * s->c_stride + row;
+    if (s->c_stride < row || (n > 1 && s->c_frame_stride < c_ext)) return fail(W2XC_ERR_ARG, "chroma: row stride below the row's bytes / frame stride below a plane");
+    // two interleaved planes (NV12: v = u + 1) are one range of bytes, two planes otherwise
+    const uintptr_t u = (uintptr_t)s->u, v = (uintptr_t)s->v;
+    const bool pair = s->c_px == 2 && (v == u + 1 || u == v + 1);
+    for (int i = 0; i < n; i++) {
+        const uintptr_t off = i * s->c_frame_stride;
+        if (pair) iv.push_back({{std::min(u, v) + off, std::min(u, v) + off + c_ext + 1}, tag});
+        else { iv.push_back({{u + off, u + off + c_ext}, tag}); iv.push_back({{v + off, v + off + c_ext}, tag}); }
+    }
+    return W2XC_OK;
+}
+
+// the layout and range enums of a frame, and the colour matrix of the calls that have one: what the frame calls and the blocks refuse alike
+int check_chroma_range(int chroma, int range)
+{
+    if (chroma < W2XC_YUV_420 || chroma > W2XC_YUV_400) return fail(W2XC_ERR_ARG, "unknown chroma layout %d", chroma);
+    if (range != W2XC_RANGE_FULL && range != W2XC_RANGE_LIMITED) return fail(W2XC_ERR_ARG, "unknown range %d", range);
+    return W2XC_OK;
+}
+int check_matrix(int matrix)
+{
+    if (matrix < W2XC_MATRIX_BT601 || matrix > W2XC_MATRIX_BT2020) return fail(W2XC_ERR_ARG, "unknown colour matrix %d", matrix);
+    return W2XC_OK;
+}
+
+// the precisions of the RGB route: those w2xc_convert_planes[_up2x]_batch_device take (the models' plane form is plan_image_call's check)
+int check_yuv_rgb_precision(const ImageCall &c)
+{
+    if (c.o.precision != W2XC_PRECISION_FP32 && split_terms(c.o) == 0)
+        return fail(W2XC_ERR_UNSUPPORTED, "w2xc_process_frames_yuv_u8_rgb* supports W2XC_PRECISION_FP32 / BF16X2 / BF16X3 / FP16X2");
+    if (c.iterations > 0 && c.msc && c.msc->has_head() && c.o.precision != W2XC_PRECISION_FP32)
+        return fail(W2XC_ERR_UNSUPPORTED, "16-bit precision modes: not available for a model with an upconv head (W2XC_PRECISION_FP32 only)");
+    return W2XC_OK;
+}
+
+// everything both forms refuse, before a device is touched; *g = the geometry, *sub = frames per sub-batch.  rgb: the call is w2xc_process_frames_yuv_u8_rgb*
+// -- RGB models, or an upconv head model as scale model, and a colour matrix; a grey frame (W2XC_YUV_400) belongs to the Y call
+int check_yuv_call(ImageCall &c, bool rgb, int n, int chroma, int range, int matrix, const w2xc_yuv_planes *in, const w2xc_yuv_planes *out, YuvGeom *g, int *sub)
+{
+    int rc = check_process_args(c, rgb);
+    if (rc || (rc = rgb ? check_yuv_rgb_precision(c) : check_y_models(c))) return rc;
+    if (c.iterations < 0 || c.iterations > 1) return fail(W2XC_ERR_ARG, "iterations must be 0 or 1 (got %d)", c.iterations);
+    if (n < 1 || n > (1 << 20)) return fail(W2XC_ERR_ARG, "batch of %d frames", n);
+    if (c.w <= 0 || c.h <= 0 || c.w > (1 << 22) || c.h > (1 << 22)) return fail(W2XC_ERR_ARG, "bad frame size");
+    if ((rc = check_chroma_range(chroma, range))) return rc;
+    if (rgb && chroma == W2XC_YUV_400) return fail(W2XC_ERR_ARG, "a frame without chroma (W2XC_YUV_400) belongs to w2xc_process_frames_yuv_u8*");
+    if (rgb && (rc = check_matrix(matrix))) return rc;
+    g->chroma = chroma; g->range = range; g->rgb = rgb; g->matrix = matrix;
+    g->W = c.w << c.iterations; g->H = c.h << c.iterations;
+    const ChromaSize ci = yuv_chroma_size(c.w, c.h, chroma), co = yuv_chroma_size(g->W, g->H, chroma);
+    g->cw = ci.cw; g->ch = ci.ch; g->ocw = co.cw; g->och = co.ch;
+    std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> iv;
+    if ((rc = check_yuv_side(in, n, c.w, c.h, g->cw, g->ch, 0, iv)) || (rc = check_yuv_side(out, n, g->W, g->H, g->ocw, g->och, 1, iv))) return rc;
+    if ((rc = check_batch_overlap(iv))) return rc;
+    c.fw = g->W; c.fh = g->H;
+    const size_t per = (rgb ? yuv_rgb_aux_floats(c.mn != nullptr, c.w, c.h, c.iterations) : yuv_aux_floats(c.w, c.h, c.iterations)) * sizeof(float) + yuv_frame_bytes(c.w, c.h, g->cw, g->ch) +
+                       yuv_frame_bytes(g->W, g->H, g->ocw, g->och);
+    return plan_image_call(rgb ? PLAN_RGB : PLAN_Y, c, sub, per, 1, "w2xc_process_frames_yuv_u8_rgb*");
+}
+
+// one side's luma planes, and the geometry of its chroma planes at U (V: the same strides from s.v), as the launchers take them
+W2xcU8Planes luma_planes(const w2xc_yuv_planes &s) { return {s.y, (long long)s.y_frame_stride, (long long)s.y_stride, 1}; }
+W2xcU8Planes chroma_planes(const w2xc_yuv_planes &s) { return {s.u, (long long)s.c_frame_stride, (long long)s.c_stride, s.c_px}; }
+
+// A sub-batch of S frames (S <= cap, the call's sub-batch size: the planes are sized by cap): luma bytes -> planes, the noise pass, the scale pass with the
+// nearest-2x folded into layer 1 -- run_batch, so bands, precisions, named kernels and fusion settings are those of w2xc_convert_batch_device --, planes ->
+// luma bytes; chroma in ONE launch, bytes to bytes.
+int process_yuv_device(const ImageCall &c, const YuvGeom &g, int S, int cap, const w2xc_yuv_planes &in, const w2xc_yuv_planes &out)
+{
+    DevCtx *own = c.ctx.owner();
+    if (int rc = reserve_aux(own, 0, yuv_aux_floats(c.w, c.h, c.iterations) * (size_t)cap)) return rc;
+    float *base = aux_planes(own, 0);
+    long long ps = (long long)plane_floats(c.w, c.h);
+    float *y = base, *yn = y + (size_t)cap * ps;
+    base += 2 * (size_t)cap * ps;
+    HIP_TRY(w2xc_launch_y8_to_plane(luma_planes(in), c.w, c.h, g.range, y, ps, S, c.st));
+    if (c.mn) {
+        if (int rc = run_batch(c.mn, c.ctx.cn, S, 0, {y, (size_t)c.w, ps}, c.w, c.h, {yn, (size_t)c.w, ps}, c.st, c.o)) return rc;
+        y = yn;
+    }
+    if (c.iterations) {
+        const long long ps2 = (long long)plane_floats(g.W, g.H);
+        if (int rc = run_batch(c.msc, c.ctx.cs, S, 1, {y, (size_t)c.w, ps}, c.w, c.h, {base, (size_t)g.W, ps2}, c.st, c.o)) return rc;
+        y = base; ps = ps2;
+    }
+    HIP_TRY(w2xc_launch_plane_to_y8(y, ps, g.W, g.H, g.range, luma_planes(out), S, c.st));
+    if (!g.cw) return W2XC_OK;
+    if (c.iterations) HIP_TRY(w2xc_launch_chroma2x_u8(chroma_planes(in), in.v, g.cw, g.ch, chroma_planes(out), out.v, g.ocw, g.och, S, c.st));
+    else HIP_TRY(w2xc_launch_chroma_copy_u8(chroma_planes(in), in.v, g.cw, g.ch, chroma_planes(out), out.v, S, c.st));
+    return W2XC_OK;
+}
+
+// YUV frames through RGB models, a sub-batch of S frames: ONE launch from the frames' bytes to three float planes per frame (k_yuv8_to_rgb), the passes of
+// process_rgb_device with float planes at both ends (rgb_passes: S >= 2 one run_batch_planes per pass, S = 1 run_rows, so bands work; a head model's pass
+// enlarges by itself), ONE launch from the planes to the bytes of the output frames (k_rgb_to_yuv8).
+int process_yuv_rgb_device(const ImageCall &c, const YuvGeom &g, int S, int cap, const w2xc_yuv_planes &in, const w2xc_yuv_planes &out)
+{
+    DevCtx *own = c.ctx.owner();
+    RgbPlan R;   // (float planes at both ends: no layer takes a uint8 image)
+    R.floats = yuv_rgb_aux_floats(c.mn != nullptr, c.w, c.h, c.iterations);
+    if (int rc = reserve_aux(own, 0, R.floats * (size_t)cap)) return rc;
+    float *base = aux_planes(own, 0);
+    RgbLevel L = {base, c.w, c.h, (long long)plane_floats(c.w, c.h)};
+    base += 3 * (size_t)cap * L.ps;
+    HIP_TRY(w2xc_launch_yuv8_to_rgb(luma_planes(in), chroma_planes(in), in.v, c.w, c.h, g.chroma, g.range, g.matrix, L.p, 3 * L.ps, L.ps, S, c.st));
+    if (int rc = rgb_passes(c, R, S, cap, U8In{nullptr, 0, 0}, U8Out{nullptr, 0, 0}, 0, &base, nullptr, &L)) return rc;
+    HIP_TRY(w2xc_launch_rgb_to_yuv8(L.p, 3 * L.ps, L.ps, L.w, L.h, g.chroma, g.range, g.matrix, luma_planes(out), chroma_planes(out), out.v, S, c.st));
+    return W2XC_OK;
+}
+
+int process_yuv_sub_batch(const ImageCall &c, const YuvGeom &g, int S, int cap, const w2xc_yuv_planes &in, const w2xc_yuv_planes &out)
+{
+    return g.rgb ? process_yuv_rgb_device(c, g, S, cap, in, out) : process_yuv_device(c, g, S, cap, in, out);
+}
+
+// rgb: w2xc_process_frames_yuv_u8_rgb* (RGB and head models by the colour matrix `matrix`); otherwise the Y call, which has no matrix
+int frames_yuv_device(ImageCall c, bool rgb, int n, int chroma, int range, int matrix, const w2xc_yuv_planes *in, const w2xc_yuv_planes *out)
+{
+    YuvGeom g;
+    int sub = 1;
+    int rc = check_yuv_call(c, rgb, n, chroma, range, matrix, in, out, &g, &sub);
+    if (rc) return rc;
+    sub = std::min(sub, n);
+    LockedCtx lc;
+    if ((rc = lc.open(c.mn, c.msc, c.o.device))) return rc;
+    c.ctx = lc;
+    return for_sub_batches(n, sub, [&](int b0, int S) { return process_yuv_sub_batch(c, g, S, sub, yuv_from(*in, b0, g.cw != 0), yuv_from(*out, b0, g.cw != 0)); });
+}
+
+// The device copy of one side of a host call, at `at` in the image buffer, laid out as L (yuv_mirror_layout, w2xc_host_geom.hpp): the side's planes as pointers
+struct YuvMirror {
+    w2xc_yuv_planes d;
+    size_t c_copy_row;   // bytes of a chroma row the copies move (both interleaved planes at once; 0: no chroma)
+    bool pair;
+};
+YuvMirror yuv_mirror(const w2xc_yuv_planes &host, unsigned char *at, const YuvMirrorLayout &L)
+{
+    YuvMirror m{host, L.c_copy_row, L.pair};
+    m.d.y = at;
+    m.d.y_stride = L.y_stride;
+    m.d.y_frame_stride = L.y_frame_stride;
+    if (L.c_copy_row) { m.d.u = at + L.u; m.d.v = at + L.v; m.d.c_stride = L.c_stride; m.d.c_frame_stride = L.c_frame_stride; }
+    return m;
+}
+// frames [b0, b0 + S) of the host side <-> the mirror's first S frames, blocking
+int yuv_copy(const YuvMirror &m, const w2xc_yuv_planes &host, size_t b0, int S, int w, int h, int ch, bool upload)
+{
+    const hipMemcpyKind kind = upload ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    const auto copy = [&](unsigned char *dev, size_t dev_row, unsigned char *hst, size_t hst_row, size_t row, int rows) {
+        return upload ? hipMemcpy2D(dev, dev_row, hst, hst_row, row, rows, kind) : hipMemcpy2D(hst, hst_row, dev, dev_row, row, rows, kind);
+    };
+    for (int i = 0; i < S; i++) {
+        HIP_TRY(copy(m.d.y + i * m.d.y_frame_stride, m.d.y_stride, host.y + (b0 + i) * host.y_frame_stride, host.y_stride, (size_t)w, h));
+        if (!m.c_copy_row) continue;
+        const size_t hoff = (b0 + i) * host.c_frame_stride, doff = i * m.d.c_frame_stride;
+        if (m.pair) HIP_TRY(copy(std::min(m.d.u, m.d.v) + doff, m.d.c_stride, std::min(host.u, host.v) + hoff, host.c_stride, m.c_copy_row, ch));
+        else {
+            HIP_TRY(copy(m.d.u + doff, m.d.c_stride, host.u + hoff, host.c_stride, m.c_copy_row, ch));
+            HIP_TRY(copy(m.d.v + doff, m.d.c_stride, host.v + hoff, host.c_stride, m.c_copy_row, ch));
+        }
+    }
+    return W2XC_OK;
+}
+
+int frames_yuv_host(ImageCall c, bool rgb, int n, int chroma, int range, int matrix, const w2xc_yuv_planes *in, const w2xc_yuv_planes *out)
+{
+    YuvGeom g;
+    int sub = 1;
+    int rc = check_yuv_call(c, rgb, n, chroma, range, matrix, in, out, &g, &sub);
+    if (rc) return rc;
+    if (g.cw) for (const w2xc_yuv_planes *s : {in, out})
+        if (s->c_px == 2 && s->v != s->u + 1 && s->u != s->v + 1)
+            return fail(W2XC_ERR_ARG, "host planes with c_px = 2: the two chroma planes must interleave (NV12: v = u + 1; NV21: u = v + 1)");
+    sub = std::min(sub, n);
+    std::vector<int> devs;
+    if ((rc = host_devices(c.o, &devs))) return rc;
+    LockedCtx lc;
+    if ((rc = lc.open(c.mn, c.msc, devs[0]))) return rc;
+    c.ctx = lc;
+    c.st = nullptr;
+    DevCtx *own = c.ctx.owner();
+    const YuvMirrorLayout li = yuv_mirror_layout(in->c_px, in->u < in->v, sub, c.w, c.h, g.cw, g.ch), lo = yuv_mirror_layout(out->c_px, out->u < out->v, sub, g.W, g.H, g.ocw, g.och);
+    if ((rc = own->img_io.reserve(li.bytes + lo.bytes, "the frames"))) return rc;
+    unsigned char *dev = own->img_io.as<unsigned char>();
+    const YuvMirror mi = yuv_mirror(*in, dev, li), mo = yuv_mirror(*out, dev + li.bytes, lo);
+    return for_sub_batches(n, sub, [&](int b0, int S) {
+        if (int r = yuv_copy(mi, *in, b0, S, c.w, c.h, g.ch, true)) return r;
+        if (int r = process_yuv_sub_batch(c, g, S, sub, mi.d, mo.d)) { hipDeviceSynchronize(); return r; }
+        HIP_TRY(hipDeviceSynchronize());
+        return yuv_copy(mo, *out, b0, S, g.W, g.H, g.och, false);
+    });
+}
+
+}  // namespace
+
+}  // namespace w2xc_eng
+
+using namespace w2xc_eng;
+
+extern "C" {
+
+// ---- YUV frames: luma through the models, chroma 2x on bytes ----
+int w2xc_process_frames_yuv_u8_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, const w2xc_yuv_planes *d_in,
+                                      const w2xc_yuv_planes *d_out, int iterations, void *hip_stream, const w2xc_opts *opts)
+try {
+    return frames_yuv_device(ImageCall(noise_model, scale_model, w, h, iterations, 0.0, hip_stream, opts), false, n, chroma, range, 0, d_in, d_out);
+} W2XC_CATCH_ALL
+
+int w2xc_process_frames_yuv_u8(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, const w2xc_yuv_planes *in,
+                               const w2xc_yuv_planes *out, int iterations, const w2xc_opts *opts)
+try {
+    return frames_yuv_host(ImageCall(noise_model, scale_model, w, h, iterations, 0.0, nullptr, opts), false, n, chroma, range, 0, in, out);
+} W2XC_CATCH_ALL
+
+// ---- YUV frames through RGB and head models, by a colour matrix ----
+int w2xc_process_frames_yuv_u8_rgb_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int matrix,
+                                          const w2xc_yuv_planes *d_in, const w2xc_yuv_planes *d_out, int iterations, void *hip_stream, const w2xc_opts *opts)
+try {
+    return frames_yuv_device(ImageCall(noise_model, scale_model, w, h, iterations, 0.0, hip_stream, opts), true, n, chroma, range, matrix, d_in, d_out);
+} W2XC_CATCH_ALL
+
+int w2xc_process_frames_yuv_u8_rgb(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int matrix, const w2xc_yuv_planes *in,
+                                   const w2xc_yuv_planes *out, int iterations, const w2xc_opts *opts)
+try {
+    return frames_yuv_host(ImageCall(noise_model, scale_model, w, h, iterations, 0.0, nullptr, opts), true, n, chroma, range, matrix, in, out);
+} W2XC_CATCH_ALL
+
+// what the two blocks refuse: the frames' side as check_yuv_side refuses it, the 3 n float planes, and the two sides overlapping
+static int check_yuv_rgb_block_args(const w2xc_yuv_planes *f, bool f_is_out, int n, int w, int h, int chroma, int range, int matrix, const float *rgb,
+                                    size_t image_stride_bytes, size_t plane_stride_bytes)
+{
+    if (!f || !rgb) return fail(W2XC_ERR_ARG, "null argument");
+    if (n < 1 || n > (1 << 20) || w <= 0 || h <= 0 || w > (1 << 22) || h > (1 << 22)) return fail(W2XC_ERR_ARG, "bad frame count / frame size");
+    if (chroma == W2XC_YUV_400) return fail(W2XC_ERR_ARG, "a frame without chroma (W2XC_YUV_400) has no colour to convert");
+    if (int rc = check_chroma_range(chroma, range)) return rc;
+    if (int rc = check_matrix(matrix)) return rc;
+    const size_t plane = (size_t)4 * w * h;
+    if ((image_stride_bytes & 3) || (plane_stride_bytes & 3) || plane_stride_bytes < plane || (n > 1 && image_stride_bytes < 2 * plane_stride_bytes + plane))
+        return fail(W2XC_ERR_ARG, "plane / image strides: multiples of 4, a plane stride of at least a plane, an image stride of at least three planes");
+    const ChromaSize cs = yuv_chroma_size(w, h, chroma);
+    std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> iv;
+    if (int rc = check_yuv_side(f, n, w, h, cs.cw, cs.ch, f_is_out ? 1 : 0, iv)) return rc;
+    for (int i = 0; i < n; i++) for (int p = 0; p < 3; p++) {
+        const uintptr_t at = (uintptr_t)rgb + i * image_stride_bytes + p * plane_stride_bytes;
+        iv.push_back({{at, at + plane}, f_is_out ? 0 : 1});
+    }
+    return check_batch_overlap(iv);
+}
+
+int w2xc_yuv8_to_rgb_device(const w2xc_yuv_planes *d_src, int n, int w, int h, int chroma, int range, int matrix, float *d_rgb, size_t image_stride_bytes,
+                            size_t plane_stride_bytes, void *hip_stream)
+try {
+    if (int rc = check_yuv_rgb_block_args(d_src, false, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes)) return rc;
+    HIP_TRY(w2xc_launch_yuv8_to_rgb(luma_planes(*d_src), chroma_planes(*d_src), d_src->v, w, h, chroma, range, matrix, d_rgb,
+                                    (long long)(image_stride_bytes / 4), (long long)(plane_stride_bytes / 4), n, (hipStream_t)hip_stream));
+    return W2XC_OK;
+} W2XC_CATCH_ALL
+
+int w2xc_rgb_to_yuv8_device(const float *d_rgb, size_t image_stride_bytes, size_t plane_stride_bytes, int n, int w, int h, int chroma, int range, int matrix,
+                            const w2xc_yuv_planes *d_dst, void *hip_stream)
+try {
+    if (int rc = check_yuv_rgb_block_args(d_dst, true, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes)) return rc;
+    HIP_TRY(w2xc_launch_rgb_to_yuv8(d_rgb, (long long)(image_stride_bytes / 4), (long long)(plane_stride_bytes / 4), w, h, chroma, range, matrix,
+                                    luma_planes(*d_dst), chroma_planes(*d_dst), d_dst->v, n, (hipStream_t)hip_stream));
+    return W2XC_OK;
+} W2XC_CATCH_ALL
+
+// what the three building blocks refuse: n byte planes of bw-byte rows x h at p and n planes of `other` bytes (rows / planes as given) on the other side
+static int check_yuv_block_args(const void *p, size_t frame, size_t row, size_t row_bytes, int rows, int n, int w, int h, const void *q, size_t q_plane, size_t q_ext)
+{
+    if (!p || !q) return fail(W2XC_ERR_ARG, "null argument");
+    if (n < 1 || n > (1 << 20) || w <= 0 || h <= 0 || w > (1 << 22) || h > (1 << 22)) return fail(W2XC_ERR_ARG, "bad plane count / plane size");
+    const size_t ext = (size_t)(rows - 1) * row + row_bytes;
+    if (row < row_bytes || (n > 1 && (frame < ext || q_plane < q_ext))) return fail(W2XC_ERR_ARG, "row / plane strides below a row / a plane");
+    if (ranges_overlap(p, (size_t)(n - 1) * frame + ext, q, (size_t)(n - 1) * q_plane + q_ext)) return fail(W2XC_ERR_ARG, "source and destination overlap");
+    return W2XC_OK;
+}
+
+int w2xc_y8_to_plane_device(const unsigned char *d_src, int n, size_t frame_stride_bytes, size_t stride_bytes, int w, int h, int range, float *d_dst,
+                            size_t plane_stride_bytes, void *hip_stream)
+{
+    if (int rc = check_yuv_block_args(d_src, frame_stride_bytes, stride_bytes, (size_t)(w > 0 ? w : 1), h, n, w, h, d_dst, plane_stride_bytes, (size_t)4 * (w > 0 ? w : 1) * (h > 0 ? h : 1))) return rc;
+    if ((plane_stride_bytes & 3) || (range != W2XC_RANGE_FULL && range != W2XC_RANGE_LIMITED)) return fail(W2XC_ERR_ARG, "plane stride no multiple of 4 / unknown range");
+    HIP_TRY(w2xc_launch_y8_to_plane({const_cast<unsigned char *>(d_src), (long long)frame_stride_bytes, (long long)stride_bytes, 1}, w, h, range, d_dst,
+                                    (long long)(plane_stride_bytes / 4), n, (hipStream_t)hip_stream));
+    return W2XC_OK;
+}
+
+int w2xc_plane_to_y8_device(const float *d_src, int n, size_t plane_stride_bytes, int w, int h, int range, unsigned char *d_dst, size_t frame_stride_bytes,
+                            size_t stride_bytes, void *hip_stream)
+{
+    if (int rc = check_yuv_block_args(d_dst, frame_stride_bytes, stride_bytes, (size_t)(w > 0 ? w : 1), h, n, w, h, d_src, plane_stride_bytes, (size_t)4 * (w > 0 ? w : 1) * (h > 0 ? h : 1))) return rc;
+    if ((plane_stride_bytes & 3) || (range != W2XC_RANGE_FULL && range != W2XC_RANGE_LIMITED)) return fail(W2XC_ERR_ARG, "plane stride no multiple of 4 / unknown range");
+    HIP_TRY(w2xc_launch_plane_to_y8(d_src, (long long)(plane_stride_bytes / 4), w, h, range, {d_dst, (long long)frame_stride_bytes, (long long)stride_bytes, 1}, n,
+                                    (hipStream_t)hip_stream));
+    return W2XC_OK;
+}
+
+int w2xc_chroma2x_u8_device(const unsigned char *d_src, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int cw, int ch,
+                            unsigned char *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int ow, int oh, void *hip_stream)
+{
+    if ((src_px != 1 && src_px != 2) || (dst_px != 1 && dst_px != 2)) return fail(W2XC_ERR_ARG, "src_px / dst_px must be 1 or 2");
+    if (ow < 1 || oh < 1 || ow > 2 * (long long)cw || oh > 2 * (long long)ch) return fail(W2XC_ERR_ARG, "the output size lies outside the 2x enlargement");
+    const size_t drow = (size_t)dst_px * (ow - 1) + 1, dext = (size_t)(oh - 1) * dst_stride_bytes + drow;
+    if (dst_stride_bytes < drow) return fail(W2XC_ERR_ARG, "row / plane strides below a row / a plane");
+    if (int rc = check_yuv_block_args(d_src, src_frame_stride_bytes, src_stride_bytes, (size_t)src_px * ((cw > 0 ? cw : 1) - 1) + 1, ch, n, cw, ch, d_dst, dst_frame_stride_bytes, dext)) return rc;
+    HIP_TRY(w2xc_launch_chroma2x_u8({const_cast<unsigned char *>(d_src), (long long)src_frame_stride_bytes, (long long)src_stride_bytes, src_px}, nullptr, cw, ch,
+                                    {d_dst, (long long)dst_frame_stride_bytes, (long long)dst_stride_bytes, dst_px}, nullptr, ow, oh, n, (hipStream_t)hip_stream));
+    return W2XC_OK;
+}
+
+}  // extern "C"
