@@ -701,7 +701,8 @@ int w2xc_tta_gather_u8_device(const float *d_up, const float *d_tr, size_t varia
  * opts->device_mask, with blocking copies around it; returns when every output plane is complete.  Host planes with c_px = 2 must be the two interleaved
  * planes of one buffer, v = u + 1 (NV12) or u = v + 1 (NV21): anything else is W2XC_ERR_ARG here.  Without a device W2XC_ERR_HIP.
  * Left out: RGB and head models on YUV frames (they need a colour matrix chosen by the caller), 10 / 16-bit samples, TTA, more than one 2x step, the shrink,
- * chroma siting correction, a submit / wait pair that overlaps frames across calls, overlapped host sub-batches, multi-device striping. */
+ * chroma siting correction, a submit / wait pair that overlaps frames across calls, overlapped host sub-batches, multi-device striping.
+ * (Samples of 9 to 16 bits in 16-bit words now live in w2xc_process_frames_yuv_u16*: "16-bit YUV frames" below.) */
 #define W2XC_YUV_420 0
 #define W2XC_YUV_422 1
 #define W2XC_YUV_444 2
@@ -770,7 +771,8 @@ int w2xc_chroma2x_u8_device(const unsigned char *d_src, int n, size_t src_frame_
  * noise pass's output included) and the frame's bytes in and out.  A sub-batch is ONE launch of each end and the passes between: S >= 2 frames one launch per
  * layer where the chain has batch kernels, one frame the single-image sequence, bands included.
  * Left out: left-sited chroma, 10 / 16-bit samples, TTA, the shrink, more than one 2x step, uint8-fused first and last layers (the float RGB planes exist in
- * memory), multi-device striping, overlapped host sub-batches, a submit / wait pair. */
+ * memory), multi-device striping, overlapped host sub-batches, a submit / wait pair.
+ * (Samples of 9 to 16 bits in 16-bit words now live in w2xc_process_frames_yuv_u16_rgb*: "16-bit YUV frames" below.) */
 #define W2XC_MATRIX_BT601  0
 #define W2XC_MATRIX_BT709  1
 #define W2XC_MATRIX_BT2020 2
@@ -790,6 +792,76 @@ int w2xc_yuv8_to_rgb_device(const w2xc_yuv_planes *d_src, int n, int w, int h, i
                             size_t plane_stride_bytes, void *hip_stream);
 int w2xc_rgb_to_yuv8_device(const float *d_rgb, size_t image_stride_bytes, size_t plane_stride_bytes, int n, int w, int h, int chroma, int range, int matrix,
                             const w2xc_yuv_planes *d_dst, void *hip_stream);
+
+/* ---- 16-bit YUV frames (revision 0.4.1.9) -----------------------------------------------------------
+ * The frames of the two sections above with samples of 8 to 16 bits in 16-bit little-endian words: what yuv420p10le / y4m C420p10 files and the P010 / P012 /
+ * P016 surfaces of hardware decoders hold.  Only the two ends differ: the float pipeline between them is the one of the 8-bit calls.  v1 of the reference has
+ * no such entry point; the arithmetic is defined here.  Every kernel file involved is built with -ffp-contract=off: every expression below is a sequence of
+ * single fp32 operations in the order written; every constant is computed in double and rounded ONCE to float.
+ *   sample:   a word holding a value of `depth` bits, 8 <= depth <= 16.  D = depth, s = 2^(D - 8), M = 2^D - 1.
+ *              W2XC_PACK_LOW  (0): the value in the low bits (yuv420p10le, y4m C420p10).  Read: word & M.  Write: the value, the high bits zero.
+ *              W2XC_PACK_HIGH (1): the value in the high bits (P010, P012, P016).  Read: word >> (16 - D), the low bits are ignored.  Write: value << (16 - D),
+ *              the low bits zero.  At D = 16 the two are the same.
+ *   frame:    w2xc_yuv16_planes is w2xc_yuv_planes with unsigned short pointers -- 2-byte aligned; strides in BYTES and even; c_px counts SAMPLES: 1 planar, 2
+ *              interleaved, P010 is v = u + 1 (one sample on) -- and one more field, `pack`: the two sides of a call may differ in packing as they may in c_px.
+ *              `depth` is an argument of the call, the same on both sides.  Chroma sizes and W2XC_YUV_420 / _422 / _444 / _400 as for the 8-bit calls.
+ *   Everything is the 8-bit definition with 255 -> M, 16 -> 16 s, 219 -> 219 s, 224 -> 224 s, 128 -> 128 s:
+ *   luma in:  W2XC_RANGE_FULL: y = (float)Y * (float)(1.0 / M);  W2XC_RANGE_LIMITED: y = ((float)Y - 16 s) * (float)(1.0 / (219 s)).
+ *   luma out: full range clamp(rint(y * M), 0, M), half to even; limited range clamp(rint(y * (219 s) + 16 s), 0, M), the product and the sum two operations.  The
+ *              clamp holds past the int32 range.
+ *   chroma, Y route (iterations = 1): c = (float)C * (float)(1.0 / M), the 2x enlargement of w2xc_resize2x_cubic_device -- its taps, clamping, coefficient
+ *              expressions and summation order --, clamp(rint(c * M), 0, M), cropped to the chroma size of a 2 w x 2 h frame.  iterations = 0: the values are
+ *              copied, repacked where the two sides differ in `pack`.
+ *   RGB route, in: chroma at luma resolution is 0.75f * C[j] + 0.25f * C[j'] with j, j', the clamping and the horizontal-then-vertical order of "YUV frames
+ *              through RGB models"; the values are multiples of 1 / 16 below 2^16 (20 bits), so the arithmetic is still exact in fp32 and the order a convention.
+ *              cb = (u - 128 s) * k and cr = (v - 128 s) * k with k = (float)(1.0 / M) for full and (float)(1.0 / (224 s)) for limited range.  The matrix
+ *              constants, R, G, B and the clamp to [0, 1] as there.
+ *   RGB route, out: y', cb, cr and the box mean over the luma block as there.  Luma word: "luma out" above.  Chroma word: clamp(rint(c * M + 128 s), 0, M) for
+ *              full range, clamp(rint(c * (224 s) + 128 s), 0, M) for limited range.
+ *   With D = 8 every constant is the 8-bit call's constant ((float)(1.0 / (219 * 1)) is (float)(1.0 / 219.0)): a frame of bytes widened to low-packed words
+ *   gives, word for byte, the 8-bit call's output.  For every D every value 0 .. M returns unchanged through luma in -> luma out, and through the chroma scale and
+ *   offset of the RGB route, in both ranges (tests/test_yuv16_api.py).
+ * w2xc_process_frames_yuv_u16[_device]: Y models, W2XC_YUV_400 included, iterations 0 or 1 -- DEFINED, by words, as w2xc_y16_to_plane_device ->
+ *   w2xc_convert_batch_device (nn2x = 0, then 1) -> w2xc_plane_to_y16_device, and w2xc_chroma2x_u16_device per chroma plane.
+ * w2xc_process_frames_yuv_u16_rgb[_device]: three-plane models, or an upconv head model as scale model, by `matrix` -- DEFINED as w2xc_yuv16_to_rgb_device ->
+ *   w2xc_convert_planes_batch_device / w2xc_convert_planes_up2x_batch_device -> w2xc_rgb_to_yuv16_device.
+ * Sub-batches, bands at S = 1, precisions, named kernels, fusion settings, the device and the host form are those of the 8-bit calls, with two bytes per sample
+ * in the per-frame memory; a sub-batch of S frames is one launch of each end and the passes between.  Host planes with c_px = 2 must be the two planes of one
+ * buffer, v = u +- 1 sample.
+ * Refused, before a device is touched: everything the corresponding 8-bit call refuses, with its code; and W2XC_ERR_ARG for a depth outside 8 .. 16, a pack that
+ * is not 0 or 1, an odd pointer, an odd row or frame stride, a stride below the row's bytes counted at 2 bytes per sample.
+ * Left out: different depths on the two sides (8-bit in with 16-bit out included), left-sited chroma, TTA, the shrink, more than one 2x step, big-endian words,
+ * packed 10-bit formats such as v210, uint16-fused first and last layers, multi-device striping, overlapped host sub-batches, a submit / wait pair. */
+#define W2XC_PACK_LOW  0
+#define W2XC_PACK_HIGH 1
+typedef struct w2xc_yuv16_planes {   /* one side of a call: n frames */
+    unsigned short *y;  size_t y_stride,  y_frame_stride;     /* bytes, even */
+    unsigned short *u, *v; size_t c_stride, c_frame_stride;    /* bytes, even; P010: v = u + 1, c_px = 2 */
+    int c_px;                                                  /* samples */
+    int pack;                                                  /* W2XC_PACK_* */
+} w2xc_yuv16_planes;
+int w2xc_process_frames_yuv_u16_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int depth,
+                                       const w2xc_yuv16_planes *d_in, const w2xc_yuv16_planes *d_out, int iterations, void *hip_stream, const w2xc_opts *opts);
+int w2xc_process_frames_yuv_u16(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int depth,
+                                const w2xc_yuv16_planes *in, const w2xc_yuv16_planes *out, int iterations, const w2xc_opts *opts);
+int w2xc_process_frames_yuv_u16_rgb_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int depth, int matrix,
+                                           const w2xc_yuv16_planes *d_in, const w2xc_yuv16_planes *d_out, int iterations, void *hip_stream, const w2xc_opts *opts);
+int w2xc_process_frames_yuv_u16_rgb(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int depth, int matrix,
+                                    const w2xc_yuv16_planes *in, const w2xc_yuv16_planes *out, int iterations, const w2xc_opts *opts);
+/* The building blocks, as those of the 8-bit sections with `depth` behind `range` and `pack` behind `depth`: strides in bytes (even), src_px / dst_px in samples.
+ * chroma2x_u16 writes only the words of its own samples: with dst_px = 2 two calls may fill the two planes in either order.
+ * W2XC_ERR_ARG: what the 8-bit blocks refuse, a depth outside 8 .. 16, a pack that is not 0 or 1, odd pointers or strides. */
+int w2xc_y16_to_plane_device(const unsigned short *d_src, int n, size_t frame_stride_bytes, size_t stride_bytes, int w, int h, int range, int depth, int pack,
+                             float *d_dst, size_t plane_stride_bytes, void *hip_stream);
+int w2xc_plane_to_y16_device(const float *d_src, int n, size_t plane_stride_bytes, int w, int h, int range, int depth, int pack, unsigned short *d_dst,
+                             size_t frame_stride_bytes, size_t stride_bytes, void *hip_stream);
+int w2xc_chroma2x_u16_device(const unsigned short *d_src, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int src_pack, int cw, int ch,
+                             int depth, unsigned short *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int dst_pack, int ow, int oh,
+                             void *hip_stream);
+int w2xc_yuv16_to_rgb_device(const w2xc_yuv16_planes *d_src, int n, int w, int h, int chroma, int range, int depth, int matrix, float *d_rgb,
+                             size_t image_stride_bytes, size_t plane_stride_bytes, void *hip_stream);
+int w2xc_rgb_to_yuv16_device(const float *d_rgb, size_t image_stride_bytes, size_t plane_stride_bytes, int n, int w, int h, int chroma, int range, int depth,
+                             int matrix, const w2xc_yuv16_planes *d_dst, void *hip_stream);
 
 /* the building blocks on contiguous float planes (device pointers): main.cpp:144 on one plane, :75-76, :171-172 */
 int w2xc_resize2x_cubic_device(const float *d_src, int w, int h, float *d_dst, void *hip_stream);

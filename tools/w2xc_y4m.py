@@ -47,7 +47,7 @@ def layout_of(tag):
         return LAYOUTS["420"]
     if tag in ("422", "444", "mono"):
         return LAYOUTS[tag]
-    raise Y4mError("unsupported colour space C%s (8-bit C420*, C422, C444 and Cmono only)" % tag)
+    raise Y4mError("unsupported colour space C%s (8-bit C420*, C422, C444 and Cmono only; 9- to 16-bit streams: tools/w2xc_y4m16.py)" % tag)
 
 
 def chroma_size(w, h, layout):
@@ -126,10 +126,12 @@ def read_header(f):
     return Header(w, h, fields)
 
 
-def read_frames(f, hdr, count):
-    """up to `count` frames: (y, u, v) as (n, h, w) and (n, ch, cw) uint8 arrays (u = v = None for Cmono), n = 0 at the end of the stream"""
-    cw, ch = chroma_size(hdr.w, hdr.h, hdr.layout)
+def read_frames(f, hdr, count, layout=None, dtype=np.uint8):
+    """up to `count` frames: (y, u, v) as (n, h, w) and (n, ch, cw) uint8 arrays (u = v = None for Cmono), n = 0 at the end of the stream.  layout / dtype: the
+    chroma layout and the sample type where the caller reads the C tag itself (tools/w2xc_y4m16.py: little-endian 16-bit words)"""
+    cw, ch = chroma_size(hdr.w, hdr.h, hdr.layout if layout is None else layout)
     ysz, csz = hdr.w * hdr.h, cw * ch
+    unit = np.dtype(dtype).itemsize
     ys, us, vs = [], [], []
     while len(ys) < count:
         line = read_line(f)
@@ -137,16 +139,16 @@ def read_frames(f, hdr, count):
             break
         if not line.startswith(b"FRAME"):
             raise Y4mError("expected a FRAME header, got %r" % line[:16])
-        data = f.read(ysz + 2 * csz)
-        if len(data) != ysz + 2 * csz:
+        data = f.read((ysz + 2 * csz) * unit)
+        if len(data) != (ysz + 2 * csz) * unit:
             raise Y4mError("the stream ends inside a frame")
-        a = np.frombuffer(data, np.uint8)
+        a = np.frombuffer(data, dtype)
         ys.append(a[:ysz].reshape(hdr.h, hdr.w))
         if csz:
             us.append(a[ysz:ysz + csz].reshape(ch, cw))
             vs.append(a[ysz + csz:].reshape(ch, cw))
     if not ys:
-        return np.empty((0, hdr.h, hdr.w), np.uint8), None, None
+        return np.empty((0, hdr.h, hdr.w), dtype), None, None
     return np.stack(ys), (np.stack(us) if csz else None), (np.stack(vs) if csz else None)
 
 
@@ -186,9 +188,9 @@ def check_route(route, layout):
         raise Y4mError(MONO_RGB)
 
 
-def build_parser():
-    ap = argparse.ArgumentParser(description="8-bit YUV4MPEG2 streams through waifu2x models on an MI355X: Y models (luma through the CNN, chroma 2x on bytes), or RGB and "
-                                             "upconv models by a colour matrix")
+def build_parser(description="8-bit YUV4MPEG2 streams through waifu2x models on an MI355X: Y models (luma through the CNN, chroma 2x on bytes), or RGB and "
+                             "upconv models by a colour matrix"):
+    ap = argparse.ArgumentParser(description=description)
     ap.add_argument("input")
     ap.add_argument("output")
     ap.add_argument("-m", "--mode", default="noise_scale", choices=["noise", "scale", "noise_scale"])
@@ -201,32 +203,34 @@ def build_parser():
     return ap
 
 
-def convert_stream(fin, fout, process, iterations, default_range="limited", frames_per_call=8):
-    """read fin, write fout; process(y, u, v, layout, full_range) -> (Y, U, V) is the frame call.  Returns the number of frames."""
+def convert_stream(fin, fout, process, iterations, default_range="limited", frames_per_call=8, layout_of_header=None, dtype=np.uint8):
+    """read fin, write fout; process(y, u, v, layout, full_range) -> (Y, U, V) is the frame call.  Returns the number of frames.  layout_of_header / dtype: how
+    another tool reads the C tag, and its sample type"""
     hdr = read_header(fin)
     if hdr.interlaced:
         raise Y4mError(INTERLACED % hdr.get("I"))
-    layout = hdr.layout
+    layout = hdr.layout if layout_of_header is None else layout_of_header(hdr)
     full = (hdr.colour_range() or default_range) == "full"
     write_header(fout, hdr.scaled(iterations))
     total = 0
     while True:
-        y, u, v = read_frames(fin, hdr, max(1, frames_per_call))
+        y, u, v = read_frames(fin, hdr, max(1, frames_per_call), layout, dtype)
         if y.shape[0] == 0:
             return total
         write_frames(fout, *process(y, u, v, layout, full))
         total += y.shape[0]
 
 
-def main(argv=None):
-    args = build_parser().parse_args(argv)
+def run_tool(name, args, layout_of_header, make_process, dtype=np.uint8):
+    """what both tools do with their parsed arguments: check the stream, load the models, route by their kind, convert.  make_process(w2xc, hdr, noise, scale,
+    iterations, route, matrix) -> the process callback of convert_stream"""
     try:
         with open(args.input, "rb") as fin:
             # what the stream itself rules out, before a model is loaded or the output file is created
             hdr = read_header(fin)
             if hdr.interlaced:
                 raise Y4mError(INTERLACED % hdr.get("I"))
-            hdr.layout, hdr.colour_range()
+            layout, _ = layout_of_header(hdr), hdr.colour_range()
             fin.seek(0)
             import __graft_entry__ as graft
             w2xc = graft.load_package()
@@ -237,23 +241,28 @@ def main(argv=None):
                 scale = w2xc._ModelSet.from_json(os.path.join(args.model_dir, "scale2.0x_model.json"))
             iterations = 1 if scale is not None else 0
             route = model_route(noise.planes(0)[0] if noise else None, scale.planes(0)[0] if scale else None)
-            check_route(route, hdr.layout)
+            check_route(route, layout)
             matrix = MATRICES[args.matrix or default_matrix(hdr.h)]
-
-            def process(y, u, v, layout, full):
-                rng = w2xc.RANGE_FULL if full else w2xc.RANGE_LIMITED
-                if route == "rgb":
-                    return w2xc.process_frames_yuv_u8_rgb(y, u, v, chroma=layout, noise=noise, scale=scale, iterations=iterations, range=rng, matrix=matrix)
-                out = w2xc.process_frames_yuv_u8(y, u, v, chroma=layout, noise=noise, scale=scale, iterations=iterations, range=rng)
-                return out if len(out) == 3 else (out[0], None, None)
-
+            process = make_process(w2xc, hdr, noise, scale, iterations, route, matrix)
             with open(args.output, "wb") as fout:
-                n = convert_stream(fin, fout, process, iterations, args.range, args.frames_per_call)
+                n = convert_stream(fin, fout, process, iterations, args.range, args.frames_per_call, layout_of_header, dtype)
     except Y4mError as e:
-        sys.stderr.write("w2xc_y4m: %s\n" % e)
+        sys.stderr.write("%s: %s\n" % (name, e))
         return 2
-    sys.stderr.write("w2xc_y4m: %d frames\n" % n)
+    sys.stderr.write("%s: %d frames\n" % (name, n))
     return 0
+
+
+def main(argv=None):
+    def make_process(w2xc, hdr, noise, scale, iterations, route, matrix):
+        def process(y, u, v, layout, full):
+            rng = w2xc.RANGE_FULL if full else w2xc.RANGE_LIMITED
+            if route == "rgb":
+                return w2xc.process_frames_yuv_u8_rgb(y, u, v, chroma=layout, noise=noise, scale=scale, iterations=iterations, range=rng, matrix=matrix)
+            out = w2xc.process_frames_yuv_u8(y, u, v, chroma=layout, noise=noise, scale=scale, iterations=iterations, range=rng)
+            return out if len(out) == 3 else (out[0], None, None)
+        return process
+    return run_tool("w2xc_y4m", build_parser().parse_args(argv), lambda hdr: hdr.layout, make_process)
 
 
 if __name__ == "__main__":

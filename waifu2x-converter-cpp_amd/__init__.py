@@ -34,6 +34,7 @@ FUSION_AUTO, FUSION_OFF, FUSION_ON, FUSION_FIRST, FUSION_LAST, FUSION_GATHER_LAU
 YUV_420, YUV_422, YUV_444, YUV_400 = 0, 1, 2, 3
 RANGE_FULL, RANGE_LIMITED = 0, 1
 MATRIX_BT601, MATRIX_BT709, MATRIX_BT2020 = 0, 1, 2
+PACK_LOW, PACK_HIGH = 0, 1
 
 
 class W2xcError(RuntimeError):
@@ -61,6 +62,12 @@ class YuvPlanes(C.Structure):
     chroma, 2: two interleaved planes (NV12: v = u + 1)."""
     _fields_ = [("y", C.c_void_p), ("y_stride", C.c_size_t), ("y_frame_stride", C.c_size_t), ("u", C.c_void_p), ("v", C.c_void_p),
                 ("c_stride", C.c_size_t), ("c_frame_stride", C.c_size_t), ("c_px", C.c_int)]
+
+
+class Yuv16Planes(C.Structure):
+    """struct w2xc_yuv16_planes (include/w2xc_hip.h): one side of a 16-bit YUV frame call -- YuvPlanes with pointers to 16-bit words (even), strides in bytes
+    (even), c_px in samples (2: P010, v = u + 2 bytes) and the packing of a value in its word (PACK_LOW / PACK_HIGH)."""
+    _fields_ = YuvPlanes._fields_ + [("pack", C.c_int)]
 
 
 def _load():
@@ -146,6 +153,15 @@ def _load():
         "w2xc_process_frames_yuv_u8_rgb": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(YuvPlanes), C.POINTER(YuvPlanes), ci, C.POINTER(Opts)]),
         "w2xc_yuv8_to_rgb_device": (ci, [C.POINTER(YuvPlanes), ci, ci, ci, ci, ci, ci, fp, cs, cs, vp]),
         "w2xc_rgb_to_yuv8_device": (ci, [fp, cs, cs, ci, ci, ci, ci, ci, ci, C.POINTER(YuvPlanes), vp]),
+        "w2xc_process_frames_yuv_u16_device": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(Yuv16Planes), C.POINTER(Yuv16Planes), ci, vp, C.POINTER(Opts)]),
+        "w2xc_process_frames_yuv_u16": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(Yuv16Planes), C.POINTER(Yuv16Planes), ci, C.POINTER(Opts)]),
+        "w2xc_process_frames_yuv_u16_rgb_device": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Yuv16Planes), C.POINTER(Yuv16Planes), ci, vp, C.POINTER(Opts)]),
+        "w2xc_process_frames_yuv_u16_rgb": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Yuv16Planes), C.POINTER(Yuv16Planes), ci, C.POINTER(Opts)]),
+        "w2xc_yuv16_to_rgb_device": (ci, [C.POINTER(Yuv16Planes), ci, ci, ci, ci, ci, ci, ci, fp, cs, cs, vp]),
+        "w2xc_rgb_to_yuv16_device": (ci, [fp, cs, cs, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Yuv16Planes), vp]),
+        "w2xc_y16_to_plane_device": (ci, [fp, ci, cs, cs, ci, ci, ci, ci, ci, fp, cs, vp]),
+        "w2xc_plane_to_y16_device": (ci, [fp, ci, cs, ci, ci, ci, ci, ci, fp, cs, cs, vp]),
+        "w2xc_chroma2x_u16_device": (ci, [fp, ci, cs, cs, ci, ci, ci, ci, ci, fp, cs, cs, ci, ci, ci, ci, vp]),
         "w2xc_y8_to_plane_device": (ci, [fp, ci, cs, cs, ci, ci, ci, fp, cs, vp]),
         "w2xc_plane_to_y8_device": (ci, [fp, ci, cs, ci, ci, ci, fp, cs, cs, vp]),
         "w2xc_chroma2x_u8_device": (ci, [fp, ci, cs, cs, ci, ci, ci, fp, cs, cs, ci, ci, ci, vp]),
@@ -1021,13 +1037,16 @@ def process_frames_yuv_u8_device(n, w, h, chroma, d_in, d_out, noise=None, scale
                                                   C.c_void_p(stream), C.byref(opts) if opts is not None else None))
 
 
-def _yuv_side(y, u, v, uv):
-    """the YuvPlanes of host arrays: y (n, h, w); u and v (n, ch, cw) planar, or uv (n, ch, cw, 2) interleaved (NV12); neither: no chroma"""
-    s = YuvPlanes()
+def _yuv_side(y, u, v, uv, pack=None):
+    """the YuvPlanes of host arrays: y (n, h, w); u and v (n, ch, cw) planar, or uv (n, ch, cw, 2) interleaved (NV12); neither: no chroma.  pack: the
+    Yuv16Planes of uint16 arrays with that packing"""
+    s = YuvPlanes() if pack is None else Yuv16Planes()
+    if pack is not None:
+        s.pack = pack
     s.y, s.y_stride, s.y_frame_stride = y.ctypes.data, y.strides[1], y.strides[0]
     s.c_px = 1
     if uv is not None:
-        s.u, s.v, s.c_stride, s.c_frame_stride, s.c_px = uv.ctypes.data, uv.ctypes.data + 1, uv.strides[1], uv.strides[0], 2
+        s.u, s.v, s.c_stride, s.c_frame_stride, s.c_px = uv.ctypes.data, uv.ctypes.data + uv.itemsize, uv.strides[1], uv.strides[0], 2
     elif u is not None:
         s.u, s.v, s.c_stride, s.c_frame_stride = u.ctypes.data, v.ctypes.data, u.strides[1], u.strides[0]
     return s
@@ -1047,12 +1066,15 @@ def process_frames_yuv_u8_rgb(y, u=None, v=None, uv=None, chroma=YUV_420, noise=
     return _frames_yuv_host(matrix, y, u, v, uv, chroma, noise, scale, iterations, range, opts, out_nv12)
 
 
-def _frames_yuv_host(matrix, y, u, v, uv, chroma, noise, scale, iterations, range, opts, out_nv12):
-    """the host frame calls: matrix = None: w2xc_process_frames_yuv_u8, else w2xc_process_frames_yuv_u8_rgb with that matrix"""
+def _frames_yuv_host(matrix, y, u, v, uv, chroma, noise, scale, iterations, range, opts, out_nv12, wide=None):
+    """the host frame calls: matrix = None: w2xc_process_frames_yuv_u8, else w2xc_process_frames_yuv_u8_rgb with that matrix; wide = (depth, pack, out_pack):
+    their forms on uint16 arrays, w2xc_process_frames_yuv_u16[_rgb]"""
+    dt, name = (np.uint8, "process_frames_yuv_u8") if wide is None else (np.uint16, "process_frames_yuv_u16")
+
     def u8(a, nd, what):
         a = np.asarray(a)
-        if a.dtype != np.uint8 or a.ndim != nd:
-            raise ValueError("process_frames_yuv_u8 wants %s as a %d-D uint8 array (got %s, shape %r)" % (what, nd, a.dtype, a.shape))
+        if a.dtype != dt or a.ndim != nd:
+            raise ValueError("%s wants %s as a %d-D %s array (got %s, shape %r)" % (name, what, nd, np.dtype(dt).name, a.dtype, a.shape))
         return np.ascontiguousarray(a)
     y = u8(y, 3, "y")
     n, h, w = y.shape
@@ -1062,25 +1084,33 @@ def _frames_yuv_host(matrix, y, u, v, uv, chroma, noise, scale, iterations, rang
     elif uv is not None:
         uv = u8(uv, 4, "uv")
         if uv.shape != (n, ch, cw, 2):
-            raise ValueError("process_frames_yuv_u8: uv must be (n, %d, %d, 2), got %r" % (ch, cw, uv.shape))
+            raise ValueError("%s: uv must be (n, %d, %d, 2), got %r" % (name, ch, cw, uv.shape))
     else:
         if u is None or v is None:
-            raise ValueError("process_frames_yuv_u8 wants u and v, or uv, unless chroma is YUV_400")
+            raise ValueError("%s wants u and v, or uv, unless chroma is YUV_400" % name)
         u, v = u8(u, 3, "u"), u8(v, 3, "v")
         if u.shape != (n, ch, cw) or v.shape != (n, ch, cw):
-            raise ValueError("process_frames_yuv_u8: u and v must be (n, %d, %d), got %r and %r" % (ch, cw, u.shape, v.shape))
+            raise ValueError("%s: u and v must be (n, %d, %d), got %r and %r" % (name, ch, cw, u.shape, v.shape))
     W, H = w << iterations, h << iterations
     ocw, och = yuv_chroma_size(W, H, chroma)
     nv12 = (uv is not None) if out_nv12 is None else bool(out_nv12)
-    oy = np.empty((n, max(H, 0), max(W, 0)), np.uint8)
+    oy = np.empty((n, max(H, 0), max(W, 0)), dt)
     ou = ov = ouv = None
     if chroma != YUV_400:
         if nv12:
-            ouv = np.empty((n, och, ocw, 2), np.uint8)
+            ouv = np.empty((n, och, ocw, 2), dt)
         else:
-            ou, ov = np.empty((n, och, ocw), np.uint8), np.empty((n, och, ocw), np.uint8)
-    si, so = _yuv_side(y, u, v, uv), _yuv_side(oy, ou, ov, ouv)
+            ou, ov = np.empty((n, och, ocw), dt), np.empty((n, och, ocw), dt)
     po = C.byref(opts) if opts is not None else None
+    if wide is not None:
+        depth, pack, out_pack = wide
+        si, so = _yuv_side(y, u, v, uv, pack), _yuv_side(oy, ou, ov, ouv, pack if out_pack is None else out_pack)
+        if matrix is None:
+            _check(_lib.w2xc_process_frames_yuv_u16(*_handles(noise, scale), n, w, h, chroma, range, depth, C.byref(si), C.byref(so), iterations, po))
+        else:
+            _check(_lib.w2xc_process_frames_yuv_u16_rgb(*_handles(noise, scale), n, w, h, chroma, range, depth, matrix, C.byref(si), C.byref(so), iterations, po))
+        return (oy,) if chroma == YUV_400 else (oy, ouv) if nv12 else (oy, ou, ov)
+    si, so = _yuv_side(y, u, v, uv), _yuv_side(oy, ou, ov, ouv)
     if matrix is None:
         _check(_lib.w2xc_process_frames_yuv_u8(*_handles(noise, scale), n, w, h, chroma, range, C.byref(si), C.byref(so), iterations, po))
     else:
@@ -1123,3 +1153,64 @@ def chroma2x_u8_device(d_src, n, src_frame_stride_bytes, src_stride_bytes, src_p
     bytes apart (w2xc_chroma2x_u8_device)."""
     _check(_lib.w2xc_chroma2x_u8_device(C.c_void_p(d_src), n, src_frame_stride_bytes, src_stride_bytes, src_px, cw, ch, C.c_void_p(d_dst), dst_frame_stride_bytes,
                                         dst_stride_bytes, dst_px, ow, oh, C.c_void_p(stream)))
+
+
+# ---- 16-bit YUV frames: values of 8 .. 16 bits in uint16 words (include/w2xc_hip.h, "16-bit YUV frames") ----
+def process_frames_yuv_u16(y, u=None, v=None, uv=None, chroma=YUV_420, noise=None, scale=None, iterations=0, range=RANGE_LIMITED, opts=None, out_nv12=None,
+                           depth=10, pack=PACK_LOW, out_pack=None):
+    """process_frames_yuv_u8 on uint16 arrays (w2xc_process_frames_yuv_u16): every word holds a value of `depth` bits (8 .. 16) in its low bits (PACK_LOW:
+    yuv420p10le, y4m C420p10) or its high bits (PACK_HIGH: P010 with uv); out_pack: the packing of the result (default: that of the input).  uv / out_nv12:
+    interleaved chroma, (n, ch, cw, 2), as P010 has it."""
+    return _frames_yuv_host(None, y, u, v, uv, chroma, noise, scale, iterations, range, opts, out_nv12, wide=(depth, pack, out_pack))
+
+
+def process_frames_yuv_u16_rgb(y, u=None, v=None, uv=None, chroma=YUV_420, noise=None, scale=None, iterations=0, range=RANGE_LIMITED, matrix=MATRIX_BT709,
+                               opts=None, out_nv12=None, depth=10, pack=PACK_LOW, out_pack=None):
+    """process_frames_yuv_u8_rgb on uint16 arrays (w2xc_process_frames_yuv_u16_rgb); depth, pack and out_pack as process_frames_yuv_u16."""
+    return _frames_yuv_host(matrix, y, u, v, uv, chroma, noise, scale, iterations, range, opts, out_nv12, wide=(depth, pack, out_pack))
+
+
+def process_frames_yuv_u16_device(n, w, h, chroma, d_in, d_out, noise=None, scale=None, iterations=0, range=RANGE_LIMITED, stream=0, opts=None, depth=10):
+    """Device-pointer form (w2xc_process_frames_yuv_u16_device): n frames of w x h described by the Yuv16Planes d_in -- its `pack` included --, the
+    (w << iterations) x (h << iterations) frames by d_out.  Asynchronous on `stream`."""
+    _check(_lib.w2xc_process_frames_yuv_u16_device(*_handles(noise, scale), n, w, h, chroma, range, depth, C.byref(d_in), C.byref(d_out), iterations,
+                                                   C.c_void_p(stream), C.byref(opts) if opts is not None else None))
+
+
+def process_frames_yuv_u16_rgb_device(n, w, h, chroma, d_in, d_out, noise=None, scale=None, iterations=0, range=RANGE_LIMITED, matrix=MATRIX_BT709, stream=0,
+                                      opts=None, depth=10):
+    """Device-pointer form (w2xc_process_frames_yuv_u16_rgb_device); arguments as process_frames_yuv_u16_device, and the colour matrix."""
+    _check(_lib.w2xc_process_frames_yuv_u16_rgb_device(*_handles(noise, scale), n, w, h, chroma, range, depth, matrix, C.byref(d_in), C.byref(d_out), iterations,
+                                                       C.c_void_p(stream), C.byref(opts) if opts is not None else None))
+
+
+def yuv16_to_rgb_device(d_src, n, w, h, chroma, range, depth, matrix, d_rgb, image_stride_bytes, plane_stride_bytes, stream=0):
+    """n frames (the Yuv16Planes d_src) -> their 3 n float planes R, G, B in [0, 1] (w2xc_yuv16_to_rgb_device); planes as yuv8_to_rgb_device."""
+    _check(_lib.w2xc_yuv16_to_rgb_device(C.byref(d_src), n, w, h, chroma, range, depth, matrix, C.c_void_p(d_rgb), image_stride_bytes, plane_stride_bytes,
+                                         C.c_void_p(stream)))
+
+
+def rgb_to_yuv16_device(d_rgb, image_stride_bytes, plane_stride_bytes, n, w, h, chroma, range, depth, matrix, d_dst, stream=0):
+    """3 n float planes of w x h -> the words of n frames (the Yuv16Planes d_dst) (w2xc_rgb_to_yuv16_device)."""
+    _check(_lib.w2xc_rgb_to_yuv16_device(C.c_void_p(d_rgb), image_stride_bytes, plane_stride_bytes, n, w, h, chroma, range, depth, matrix, C.byref(d_dst),
+                                         C.c_void_p(stream)))
+
+
+def y16_to_plane_device(d_src, n, frame_stride_bytes, stride_bytes, w, h, range, depth, pack, d_dst, plane_stride_bytes, stream=0):
+    """n luma planes of 16-bit words -> n float planes with contiguous rows (w2xc_y16_to_plane_device); strides in bytes"""
+    _check(_lib.w2xc_y16_to_plane_device(C.c_void_p(d_src), n, frame_stride_bytes, stride_bytes, w, h, range, depth, pack, C.c_void_p(d_dst), plane_stride_bytes,
+                                         C.c_void_p(stream)))
+
+
+def plane_to_y16_device(d_src, n, plane_stride_bytes, w, h, range, depth, pack, d_dst, frame_stride_bytes, stride_bytes, stream=0):
+    """n float planes with contiguous rows -> n luma planes of 16-bit words (w2xc_plane_to_y16_device); strides in bytes"""
+    _check(_lib.w2xc_plane_to_y16_device(C.c_void_p(d_src), n, plane_stride_bytes, w, h, range, depth, pack, C.c_void_p(d_dst), frame_stride_bytes, stride_bytes,
+                                         C.c_void_p(stream)))
+
+
+def chroma2x_u16_device(d_src, n, src_frame_stride_bytes, src_stride_bytes, src_px, src_pack, cw, ch, depth, d_dst, dst_frame_stride_bytes, dst_stride_bytes, dst_px,
+                        dst_pack, ow, oh, stream=0):
+    """the bicubic 2x of n chroma planes of cw x ch 16-bit samples (src_px samples apart), words to words: the leading ow x oh samples of each enlargement,
+    dst_px samples apart (w2xc_chroma2x_u16_device); strides in bytes"""
+    _check(_lib.w2xc_chroma2x_u16_device(C.c_void_p(d_src), n, src_frame_stride_bytes, src_stride_bytes, src_px, src_pack, cw, ch, depth, C.c_void_p(d_dst),
+                                         dst_frame_stride_bytes, dst_stride_bytes, dst_px, dst_pack, ow, oh, C.c_void_p(stream)))

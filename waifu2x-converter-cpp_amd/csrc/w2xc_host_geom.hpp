@@ -138,8 +138,8 @@ inline ChromaSize yuv_chroma_size(int w, int h, int chroma)
     if (chroma == W2XC_YUV_400) return {0, 0};
     return {chroma != W2XC_YUV_444 ? (w + 1) / 2 : w, chroma == W2XC_YUV_420 ? (h + 1) / 2 : h};
 }
-// bytes from the first to behind the last sample of a chroma row of cw samples px bytes apart
-inline size_t chroma_row_bytes(int cw, int px) { return (size_t)px * (cw - 1) + 1; }
+// bytes from the first to behind the last sample of a chroma row of cw samples, px samples apart, of bps bytes each (1: bytes; 2: 16-bit words)
+inline size_t chroma_row_bytes(int cw, int px, int bps = 1) { return ((size_t)px * (cw - 1) + 1) * bps; }
 // the float planes of one frame of the Y call: two luma planes per level
 inline size_t yuv_aux_floats(int w, int h, int iterations) { return 2 * plane_floats(w, h) + (iterations ? 2 * plane_floats(2 * w, 2 * h) : 0); }
 // ... of the call through RGB models: three per level, the noise pass's output included
@@ -147,12 +147,12 @@ inline size_t yuv_rgb_aux_floats(bool noise, int w, int h, int iterations)
 {
     return 3 * ((noise ? 2 : 1) * plane_floats(w, h) + (iterations ? plane_floats(2 * w, 2 * h) : 0));
 }
-// the bytes of one frame's planes: w x h luma, two planes of cw x ch chroma
-inline size_t yuv_frame_bytes(int w, int h, int cw, int ch) { return (size_t)w * h + 2 * (size_t)cw * ch; }
+// the bytes of one frame's planes: w x h luma, two planes of cw x ch chroma, bps bytes per sample
+inline size_t yuv_frame_bytes(int w, int h, int cw, int ch, int bps = 1) { return ((size_t)w * h + 2 * (size_t)cw * ch) * bps; }
 
-// The device copy of one side of a host frame call for sub-batches of at most cap frames, as byte offsets from its start: luma rows w bytes apart; chroma as
-// the caller has it -- planar planes (c_px = 1), or the two interleaved planes (c_px = 2; u_first: U is the lower byte, NV12) as ONE plane of 2 cw-byte rows --,
-// every frame of luma and of chroma on a 256-byte boundary.  bytes = what it takes: the end of the last plane's share.
+// The device copy of one side of a host frame call for sub-batches of at most cap frames, as byte offsets from its start: luma rows w samples apart; chroma as
+// the caller has it -- planar planes (c_px = 1), or the two interleaved planes (c_px = 2; u_first: U is the lower sample, NV12 / P010) as ONE plane of rows of
+// 2 cw samples --, every frame of luma and of chroma on a 256-byte boundary.  bps = bytes per sample.  bytes = what it takes: the end of the last plane's share.
 struct YuvMirrorLayout {
     size_t y_stride = 0, y_frame_stride = 0;
     bool pair = false;
@@ -160,19 +160,19 @@ struct YuvMirrorLayout {
     size_t c_stride = 0, c_frame_stride = 0, u = 0, v = 0;
     size_t bytes = 0;
 };
-inline YuvMirrorLayout yuv_mirror_layout(int c_px, bool u_first, int cap, int w, int h, int cw, int ch)
+inline YuvMirrorLayout yuv_mirror_layout(int c_px, bool u_first, int cap, int w, int h, int cw, int ch, int bps = 1)
 {
     YuvMirrorLayout m;
-    m.y_stride = (size_t)w;
-    m.y_frame_stride = align256((size_t)w * h);
+    m.y_stride = (size_t)w * bps;
+    m.y_frame_stride = align256((size_t)w * h * bps);
     m.bytes = m.y_frame_stride * cap;
     if (cw) {
         m.pair = c_px == 2;
-        m.c_copy_row = m.pair ? 2 * (size_t)cw : (size_t)cw;
+        m.c_copy_row = (m.pair ? 2 * (size_t)cw : (size_t)cw) * bps;
         m.c_stride = m.c_copy_row;
         const size_t plane = align256(m.c_copy_row * ch), c0 = m.bytes;
         m.c_frame_stride = m.pair ? plane : 2 * plane;
-        if (m.pair) { m.u = c0 + (u_first ? 0 : 1); m.v = c0 + (u_first ? 1 : 0); }
+        if (m.pair) { m.u = c0 + (u_first ? 0 : bps); m.v = c0 + (u_first ? bps : 0); }
         else { m.u = c0; m.v = c0 + plane; }
         m.bytes += m.c_frame_stride * cap;
     }

@@ -1,16 +1,19 @@
 // w2xc_image_yuv.cpp -- frames that are Y, U and V already (w2xc_process_frames_yuv_u8*): process_yuv_device, the Y pipeline without its colour stages (kernels in
 // w2xc_yuv.hip) -- and, through RGB and head models by a colour matrix the caller names (w2xc_process_frames_yuv_u8_rgb*), process_yuv_rgb_device: the passes of the
 // RGB pipeline (rgb_passes, w2xc_image.cpp) between two kernels (w2xc_yuv_rgb.hip).  The host forms' device mirror, and the five building blocks.
+// The same calls on 16-bit words (w2xc_process_frames_yuv_u16*, "16-bit YUV frames"): the checks, the geometry, the mirror and the sub-batches take the sample
+// size, and the two routes pick their ends (w2xc_yuv16.hip, w2xc_yuv16_rgb.hip) by it; the passes between the ends are the same calls.
 #include "w2xc_image.hpp"
 
 namespace w2xc_eng {
 
 namespace {
 
-// ---- YUV frames (w2xc_process_frames_yuv_u8*; the arithmetic: include/w2xc_hip.h) ----
-// Luma through the models as the planes of run_batch, chroma from bytes to bytes in one launch: no colour matrix, no float plane of chroma.
+// ---- YUV frames (w2xc_process_frames_yuv_u8* / _u16*; the arithmetic: include/w2xc_hip.h) ----
+// Luma through the models as the planes of run_batch, chroma from samples to samples in one launch: no colour matrix, no float plane of chroma.
 struct YuvGeom {
     int chroma, range;
+    int bps = 1, depth = 8;   // bytes per sample (1: w2xc_yuv_planes, 2: w2xc_yuv16_planes) and the bits of a value
     bool rgb = false;       // the frames go through RGB / head models (w2xc_process_frames_yuv_u8_rgb*): process_yuv_rgb_device
     int matrix = 0;         // ... by this colour matrix (W2XC_MATRIX_*)
     int cw = 0, ch = 0;     // the chroma planes of a w x h frame (0 x 0: W2XC_YUV_400)
@@ -19,33 +22,59 @@ struct YuvGeom {
 };
 // (the sizes of the chroma planes, the float planes and the bytes of a frame: yuv_chroma_size, yuv_aux_floats, yuv_rgb_aux_floats, yuv_frame_bytes -- w2xc_host_geom.hpp)
 
-// one side's planes from frame b0 on
-w2xc_yuv_planes yuv_from(const w2xc_yuv_planes &s, size_t b0, bool chroma)
+// One side of a call as the engine takes it, from either struct of the interface: byte pointers, strides in bytes, c_px in samples, pack (0 for bytes)
+struct YuvSide {
+    unsigned char *y = nullptr;
+    size_t y_stride = 0, y_frame_stride = 0;
+    unsigned char *u = nullptr, *v = nullptr;
+    size_t c_stride = 0, c_frame_stride = 0;
+    int c_px = 0, pack = 0;
+};
+// (a null struct stays a null side: check_yuv_side refuses it where it refuses null planes)
+template <class Planes> const YuvSide *side_of(const Planes *s, int pack, YuvSide *store)
 {
-    w2xc_yuv_planes t = s;
+    if (!s) return nullptr;
+    *store = {reinterpret_cast<unsigned char *>(s->y), s->y_stride, s->y_frame_stride, reinterpret_cast<unsigned char *>(s->u), reinterpret_cast<unsigned char *>(s->v),
+              s->c_stride, s->c_frame_stride, s->c_px, pack};
+    return store;
+}
+const YuvSide *side_of(const w2xc_yuv_planes *s, YuvSide *store) { return side_of(s, 0, store); }
+const YuvSide *side_of(const w2xc_yuv16_planes *s, YuvSide *store) { return side_of(s, s ? s->pack : 0, store); }
+
+// one side's planes from frame b0 on
+YuvSide yuv_from(const YuvSide &s, size_t b0, bool chroma)
+{
+    YuvSide t = s;
     t.y += b0 * s.y_frame_stride;
     if (chroma) { t.u += b0 * s.c_frame_stride; t.v += b0 * s.c_frame_stride; }
     return t;
 }
 
-// n frames of w x h luma and cw x ch chroma on one side: pointers, strides, c_px; its byte ranges go to iv tagged `tag` (check_batch_overlap)
-int check_yuv_side(const w2xc_yuv_planes *s, int n, int w, int h, int cw, int ch, int tag, std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> &iv)
+// n frames of w x h luma and cw x ch chroma on one side, samples of bps bytes: pointers, strides, c_px, and for words their alignment and the packing; its byte
+// ranges go to iv tagged `tag` (check_batch_overlap)
+int check_yuv_side(const YuvSide *s, int bps, int n, int w, int h, int cw, int ch, int tag, std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> &iv)
 {
     if (!s || !s->y) return fail(W2XC_ERR_ARG, "null argument");
-    const size_t y_ext = image_extent(h, s->y_stride, w, 1);
-    if (s->y_stride < (size_t)w || (n > 1 && s->y_frame_stride < y_ext)) return fail(W2XC_ERR_ARG, "luma: row stride below the row's bytes / frame stride below a plane");
+    const size_t y_ext = image_extent(h, s->y_stride, w, bps);
+    if (s->y_stride < (size_t)w * bps || (n > 1 && s->y_frame_stride < y_ext)) return fail(W2XC_ERR_ARG, "luma: row stride below the row's bytes / frame stride below a plane");
+    if (bps == 2) {
+        if (s->pack != W2XC_PACK_LOW && s->pack != W2XC_PACK_HIGH) return fail(W2XC_ERR_ARG, "pack must be W2XC_PACK_LOW or W2XC_PACK_HIGH, got %d", s->pack);
+        if (((uintptr_t)s->y | s->y_stride | s->y_frame_stride) & 1) return fail(W2XC_ERR_ARG, "luma: 16-bit samples need an even pointer and even strides");
+    }
     for (int i = 0; i < n; i++) iv.push_back({{(uintptr_t)s->y + i * s->y_frame_stride, (uintptr_t)s->y + i * s->y_frame_stride + y_ext}, tag});
     if (!cw) return W2XC_OK;
     if (!s->u || !s->v) return fail(W2XC_ERR_ARG, "null argument");
     if (s->c_px != 1 && s->c_px != 2) return fail(W2XC_ERR_ARG, "c_px must be 1 (planar) or 2 (interleaved), got %d", s->c_px);
-    const size_t row = chroma_row_bytes(cw, s->c_px), c_ext = (size_t)(ch - 1) * s->c_stride + row;
+    const size_t row = chroma_row_bytes(cw, s->c_px, bps), c_ext = (size_t)(ch - 1) * s->c_stride + row;
     if (s->c_stride < row || (n > 1 && s->c_frame_stride < c_ext)) return fail(W2XC_ERR_ARG, "chroma: row stride below the row's bytes / frame stride below a plane");
-    // two interleaved planes (NV12: v = u + 1) are one range of bytes, two planes otherwise
+    if (bps == 2 && (((uintptr_t)s->u | (uintptr_t)s->v | s->c_stride | s->c_frame_stride) & 1))
+        return fail(W2XC_ERR_ARG, "chroma: 16-bit samples need even pointers and even strides");
+    // two interleaved planes (NV12: v = u + 1 sample) are one range of bytes, two planes otherwise
     const uintptr_t u = (uintptr_t)s->u, v = (uintptr_t)s->v;
-    const bool pair = s->c_px == 2 && (v == u + 1 || u == v + 1);
+    const bool pair = s->c_px == 2 && (v == u + bps || u == v + bps);
     for (int i = 0; i < n; i++) {
         const uintptr_t off = i * s->c_frame_stride;
-        if (pair) iv.push_back({{std::min(u, v) + off, std::min(u, v) + off + c_ext + 1}, tag});
+        if (pair) iv.push_back({{std::min(u, v) + off, std::min(u, v) + off + c_ext + bps}, tag});
         else { iv.push_back({{u + off, u + off + c_ext}, tag}); iv.push_back({{v + off, v + off + c_ext}, tag}); }
     }
     return W2XC_OK;
@@ -63,6 +92,12 @@ int check_matrix(int matrix)
     if (matrix < W2XC_MATRIX_BT601 || matrix > W2XC_MATRIX_BT2020) return fail(W2XC_ERR_ARG, "unknown colour matrix %d", matrix);
     return W2XC_OK;
 }
+// the bits of a value in a 16-bit word (the calls on bytes have none to name: 8)
+int check_depth(int bps, int depth)
+{
+    if (bps == 2 && (depth < 8 || depth > 16)) return fail(W2XC_ERR_ARG, "depth must be 8 .. 16, got %d", depth);
+    return W2XC_OK;
+}
 
 // the precisions of the RGB route: those w2xc_convert_planes[_up2x]_batch_device take (the models' plane form is plan_image_call's check)
 int check_yuv_rgb_precision(const ImageCall &c)
@@ -74,39 +109,44 @@ int check_yuv_rgb_precision(const ImageCall &c)
     return W2XC_OK;
 }
 
-// everything both forms refuse, before a device is touched; *g = the geometry, *sub = frames per sub-batch.  rgb: the call is w2xc_process_frames_yuv_u8_rgb*
-// -- RGB models, or an upconv head model as scale model, and a colour matrix; a grey frame (W2XC_YUV_400) belongs to the Y call
-int check_yuv_call(ImageCall &c, bool rgb, int n, int chroma, int range, int matrix, const w2xc_yuv_planes *in, const w2xc_yuv_planes *out, YuvGeom *g, int *sub)
+// everything both forms refuse, before a device is touched; *g = the geometry (g->bps and g->depth are the caller's), *sub = frames per sub-batch.  rgb: the call
+// is w2xc_process_frames_yuv_u8_rgb* / _u16_rgb* -- RGB models, or an upconv head model as scale model, and a colour matrix; a grey frame (W2XC_YUV_400) belongs
+// to the Y call
+int check_yuv_call(ImageCall &c, bool rgb, int n, int chroma, int range, int matrix, const YuvSide *in, const YuvSide *out, YuvGeom *g, int *sub)
 {
     int rc = check_process_args(c, rgb);
     if (rc || (rc = rgb ? check_yuv_rgb_precision(c) : check_y_models(c))) return rc;
     if (c.iterations < 0 || c.iterations > 1) return fail(W2XC_ERR_ARG, "iterations must be 0 or 1 (got %d)", c.iterations);
     if (n < 1 || n > (1 << 20)) return fail(W2XC_ERR_ARG, "batch of %d frames", n);
     if (c.w <= 0 || c.h <= 0 || c.w > (1 << 22) || c.h > (1 << 22)) return fail(W2XC_ERR_ARG, "bad frame size");
-    if ((rc = check_chroma_range(chroma, range))) return rc;
-    if (rgb && chroma == W2XC_YUV_400) return fail(W2XC_ERR_ARG, "a frame without chroma (W2XC_YUV_400) belongs to w2xc_process_frames_yuv_u8*");
+    if ((rc = check_chroma_range(chroma, range)) || (rc = check_depth(g->bps, g->depth))) return rc;
+    if (rgb && chroma == W2XC_YUV_400)
+        return fail(W2XC_ERR_ARG, "a frame without chroma (W2XC_YUV_400) belongs to %s", g->bps == 2 ? "w2xc_process_frames_yuv_u16*" : "w2xc_process_frames_yuv_u8*");
     if (rgb && (rc = check_matrix(matrix))) return rc;
     g->chroma = chroma; g->range = range; g->rgb = rgb; g->matrix = matrix;
     g->W = c.w << c.iterations; g->H = c.h << c.iterations;
     const ChromaSize ci = yuv_chroma_size(c.w, c.h, chroma), co = yuv_chroma_size(g->W, g->H, chroma);
     g->cw = ci.cw; g->ch = ci.ch; g->ocw = co.cw; g->och = co.ch;
     std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> iv;
-    if ((rc = check_yuv_side(in, n, c.w, c.h, g->cw, g->ch, 0, iv)) || (rc = check_yuv_side(out, n, g->W, g->H, g->ocw, g->och, 1, iv))) return rc;
+    if ((rc = check_yuv_side(in, g->bps, n, c.w, c.h, g->cw, g->ch, 0, iv)) || (rc = check_yuv_side(out, g->bps, n, g->W, g->H, g->ocw, g->och, 1, iv))) return rc;
     if ((rc = check_batch_overlap(iv))) return rc;
     c.fw = g->W; c.fh = g->H;
-    const size_t per = (rgb ? yuv_rgb_aux_floats(c.mn != nullptr, c.w, c.h, c.iterations) : yuv_aux_floats(c.w, c.h, c.iterations)) * sizeof(float) + yuv_frame_bytes(c.w, c.h, g->cw, g->ch) +
-                       yuv_frame_bytes(g->W, g->H, g->ocw, g->och);
-    return plan_image_call(rgb ? PLAN_RGB : PLAN_Y, c, sub, per, 1, "w2xc_process_frames_yuv_u8_rgb*");
+    const size_t per = (rgb ? yuv_rgb_aux_floats(c.mn != nullptr, c.w, c.h, c.iterations) : yuv_aux_floats(c.w, c.h, c.iterations)) * sizeof(float) +
+                       yuv_frame_bytes(c.w, c.h, g->cw, g->ch, g->bps) + yuv_frame_bytes(g->W, g->H, g->ocw, g->och, g->bps);
+    return plan_image_call(rgb ? PLAN_RGB : PLAN_Y, c, sub, per, 1, g->bps == 2 ? "w2xc_process_frames_yuv_u16_rgb*" : "w2xc_process_frames_yuv_u8_rgb*");
 }
 
-// one side's luma planes, and the geometry of its chroma planes at U (V: the same strides from s.v), as the launchers take them
-W2xcU8Planes luma_planes(const w2xc_yuv_planes &s) { return {s.y, (long long)s.y_frame_stride, (long long)s.y_stride, 1}; }
-W2xcU8Planes chroma_planes(const w2xc_yuv_planes &s) { return {s.u, (long long)s.c_frame_stride, (long long)s.c_stride, s.c_px}; }
+// one side's luma planes, and the geometry of its chroma planes at U (V: the same strides from s.v), as the launchers take them: bytes, or words (strides in words)
+W2xcU8Planes luma_planes(const YuvSide &s) { return {s.y, (long long)s.y_frame_stride, (long long)s.y_stride, 1}; }
+W2xcU8Planes chroma_planes(const YuvSide &s) { return {s.u, (long long)s.c_frame_stride, (long long)s.c_stride, s.c_px}; }
+unsigned short *words(unsigned char *p) { return reinterpret_cast<unsigned short *>(p); }
+W2xcU16Planes luma_words(const YuvSide &s) { return {words(s.y), (long long)(s.y_frame_stride / 2), (long long)(s.y_stride / 2), 1, s.pack}; }
+W2xcU16Planes chroma_words(const YuvSide &s) { return {words(s.u), (long long)(s.c_frame_stride / 2), (long long)(s.c_stride / 2), s.c_px, s.pack}; }
 
-// A sub-batch of S frames (S <= cap, the call's sub-batch size: the planes are sized by cap): luma bytes -> planes, the noise pass, the scale pass with the
+// A sub-batch of S frames (S <= cap, the call's sub-batch size: the planes are sized by cap): luma samples -> planes, the noise pass, the scale pass with the
 // nearest-2x folded into layer 1 -- run_batch, so bands, precisions, named kernels and fusion settings are those of w2xc_convert_batch_device --, planes ->
-// luma bytes; chroma in ONE launch, bytes to bytes.
-int process_yuv_device(const ImageCall &c, const YuvGeom &g, int S, int cap, const w2xc_yuv_planes &in, const w2xc_yuv_planes &out)
+// luma samples; chroma in ONE launch, samples to samples.  The ends are those of the sample width; everything between them is the same.
+int process_yuv_device(const ImageCall &c, const YuvGeom &g, int S, int cap, const YuvSide &in, const YuvSide &out)
 {
     DevCtx *own = c.ctx.owner();
     if (int rc = reserve_aux(own, 0, yuv_aux_floats(c.w, c.h, c.iterations) * (size_t)cap)) return rc;
@@ -114,7 +154,9 @@ int process_yuv_device(const ImageCall &c, const YuvGeom &g, int S, int cap, con
     long long ps = (long long)plane_floats(c.w, c.h);
     float *y = base, *yn = y + (size_t)cap * ps;
     base += 2 * (size_t)cap * ps;
-    HIP_TRY(w2xc_launch_y8_to_plane(luma_planes(in), c.w, c.h, g.range, y, ps, S, c.st));
+    const bool wide = g.bps == 2;
+    if (wide) HIP_TRY(w2xc_launch_y16_to_plane(luma_words(in), c.w, c.h, g.range, g.depth, y, ps, S, c.st));
+    else HIP_TRY(w2xc_launch_y8_to_plane(luma_planes(in), c.w, c.h, g.range, y, ps, S, c.st));
     if (c.mn) {
         if (int rc = run_batch(c.mn, c.ctx.cn, S, 0, {y, (size_t)c.w, ps}, c.w, c.h, {yn, (size_t)c.w, ps}, c.st, c.o)) return rc;
         y = yn;
@@ -124,17 +166,21 @@ int process_yuv_device(const ImageCall &c, const YuvGeom &g, int S, int cap, con
         if (int rc = run_batch(c.msc, c.ctx.cs, S, 1, {y, (size_t)c.w, ps}, c.w, c.h, {base, (size_t)g.W, ps2}, c.st, c.o)) return rc;
         y = base; ps = ps2;
     }
-    HIP_TRY(w2xc_launch_plane_to_y8(y, ps, g.W, g.H, g.range, luma_planes(out), S, c.st));
+    if (wide) HIP_TRY(w2xc_launch_plane_to_y16(y, ps, g.W, g.H, g.range, g.depth, luma_words(out), S, c.st));
+    else HIP_TRY(w2xc_launch_plane_to_y8(y, ps, g.W, g.H, g.range, luma_planes(out), S, c.st));
     if (!g.cw) return W2XC_OK;
-    if (c.iterations) HIP_TRY(w2xc_launch_chroma2x_u8(chroma_planes(in), in.v, g.cw, g.ch, chroma_planes(out), out.v, g.ocw, g.och, S, c.st));
+    if (wide) {
+        if (c.iterations) HIP_TRY(w2xc_launch_chroma2x_u16(chroma_words(in), words(in.v), g.cw, g.ch, chroma_words(out), words(out.v), g.ocw, g.och, g.depth, S, c.st));
+        else HIP_TRY(w2xc_launch_chroma_copy_u16(chroma_words(in), words(in.v), g.cw, g.ch, chroma_words(out), words(out.v), g.depth, S, c.st));
+    } else if (c.iterations) HIP_TRY(w2xc_launch_chroma2x_u8(chroma_planes(in), in.v, g.cw, g.ch, chroma_planes(out), out.v, g.ocw, g.och, S, c.st));
     else HIP_TRY(w2xc_launch_chroma_copy_u8(chroma_planes(in), in.v, g.cw, g.ch, chroma_planes(out), out.v, S, c.st));
     return W2XC_OK;
 }
 
-// YUV frames through RGB models, a sub-batch of S frames: ONE launch from the frames' bytes to three float planes per frame (k_yuv8_to_rgb), the passes of
-// process_rgb_device with float planes at both ends (rgb_passes: S >= 2 one run_batch_planes per pass, S = 1 run_rows, so bands work; a head model's pass
-// enlarges by itself), ONE launch from the planes to the bytes of the output frames (k_rgb_to_yuv8).
-int process_yuv_rgb_device(const ImageCall &c, const YuvGeom &g, int S, int cap, const w2xc_yuv_planes &in, const w2xc_yuv_planes &out)
+// YUV frames through RGB models, a sub-batch of S frames: ONE launch from the frames' samples to three float planes per frame (k_yuv8_to_rgb / k_yuv16_to_rgb),
+// the passes of process_rgb_device with float planes at both ends (rgb_passes: S >= 2 one run_batch_planes per pass, S = 1 run_rows, so bands work; a head model's
+// pass enlarges by itself), ONE launch from the planes to the samples of the output frames (k_rgb_to_yuv8 / k_rgb_to_yuv16).
+int process_yuv_rgb_device(const ImageCall &c, const YuvGeom &g, int S, int cap, const YuvSide &in, const YuvSide &out)
 {
     DevCtx *own = c.ctx.owner();
     RgbPlan R;   // (float planes at both ends: no layer takes a uint8 image)
@@ -143,38 +189,49 @@ int process_yuv_rgb_device(const ImageCall &c, const YuvGeom &g, int S, int cap,
     float *base = aux_planes(own, 0);
     RgbLevel L = {base, c.w, c.h, (long long)plane_floats(c.w, c.h)};
     base += 3 * (size_t)cap * L.ps;
-    HIP_TRY(w2xc_launch_yuv8_to_rgb(luma_planes(in), chroma_planes(in), in.v, c.w, c.h, g.chroma, g.range, g.matrix, L.p, 3 * L.ps, L.ps, S, c.st));
+    const bool wide = g.bps == 2;
+    if (wide) HIP_TRY(w2xc_launch_yuv16_to_rgb(luma_words(in), chroma_words(in), words(in.v), c.w, c.h, g.chroma, g.range, g.matrix, g.depth, L.p, 3 * L.ps, L.ps, S, c.st));
+    else HIP_TRY(w2xc_launch_yuv8_to_rgb(luma_planes(in), chroma_planes(in), in.v, c.w, c.h, g.chroma, g.range, g.matrix, L.p, 3 * L.ps, L.ps, S, c.st));
     if (int rc = rgb_passes(c, R, S, cap, U8In{nullptr, 0, 0}, U8Out{nullptr, 0, 0}, 0, &base, nullptr, &L)) return rc;
-    HIP_TRY(w2xc_launch_rgb_to_yuv8(L.p, 3 * L.ps, L.ps, L.w, L.h, g.chroma, g.range, g.matrix, luma_planes(out), chroma_planes(out), out.v, S, c.st));
+    if (wide) HIP_TRY(w2xc_launch_rgb_to_yuv16(L.p, 3 * L.ps, L.ps, L.w, L.h, g.chroma, g.range, g.matrix, g.depth, luma_words(out), chroma_words(out), words(out.v), S, c.st));
+    else HIP_TRY(w2xc_launch_rgb_to_yuv8(L.p, 3 * L.ps, L.ps, L.w, L.h, g.chroma, g.range, g.matrix, luma_planes(out), chroma_planes(out), out.v, S, c.st));
     return W2XC_OK;
 }
 
-int process_yuv_sub_batch(const ImageCall &c, const YuvGeom &g, int S, int cap, const w2xc_yuv_planes &in, const w2xc_yuv_planes &out)
+int process_yuv_sub_batch(const ImageCall &c, const YuvGeom &g, int S, int cap, const YuvSide &in, const YuvSide &out)
 {
     return g.rgb ? process_yuv_rgb_device(c, g, S, cap, in, out) : process_yuv_device(c, g, S, cap, in, out);
 }
 
-// rgb: w2xc_process_frames_yuv_u8_rgb* (RGB and head models by the colour matrix `matrix`); otherwise the Y call, which has no matrix
-int frames_yuv_device(ImageCall c, bool rgb, int n, int chroma, int range, int matrix, const w2xc_yuv_planes *in, const w2xc_yuv_planes *out)
+// what a call names besides its models, its size and its planes.  rgb: w2xc_process_frames_yuv_*_rgb* (RGB and head models by the colour matrix `matrix`);
+// otherwise the Y call, which has no matrix.  bps / depth: 1 / 8 for the calls on bytes, 2 / the call's depth for those on words
+struct YuvCall {
+    bool rgb;
+    int n, chroma, range, matrix;
+    int bps = 1, depth = 8;
+};
+
+int frames_yuv_device(ImageCall c, const YuvCall &k, const YuvSide *in, const YuvSide *out)
 {
     YuvGeom g;
+    g.bps = k.bps; g.depth = k.depth;
     int sub = 1;
-    int rc = check_yuv_call(c, rgb, n, chroma, range, matrix, in, out, &g, &sub);
+    int rc = check_yuv_call(c, k.rgb, k.n, k.chroma, k.range, k.matrix, in, out, &g, &sub);
     if (rc) return rc;
-    sub = std::min(sub, n);
+    sub = std::min(sub, k.n);
     LockedCtx lc;
     if ((rc = lc.open(c.mn, c.msc, c.o.device))) return rc;
     c.ctx = lc;
-    return for_sub_batches(n, sub, [&](int b0, int S) { return process_yuv_sub_batch(c, g, S, sub, yuv_from(*in, b0, g.cw != 0), yuv_from(*out, b0, g.cw != 0)); });
+    return for_sub_batches(k.n, sub, [&](int b0, int S) { return process_yuv_sub_batch(c, g, S, sub, yuv_from(*in, b0, g.cw != 0), yuv_from(*out, b0, g.cw != 0)); });
 }
 
 // The device copy of one side of a host call, at `at` in the image buffer, laid out as L (yuv_mirror_layout, w2xc_host_geom.hpp): the side's planes as pointers
 struct YuvMirror {
-    w2xc_yuv_planes d;
+    YuvSide d;
     size_t c_copy_row;   // bytes of a chroma row the copies move (both interleaved planes at once; 0: no chroma)
     bool pair;
 };
-YuvMirror yuv_mirror(const w2xc_yuv_planes &host, unsigned char *at, const YuvMirrorLayout &L)
+YuvMirror yuv_mirror(const YuvSide &host, unsigned char *at, const YuvMirrorLayout &L)
 {
     YuvMirror m{host, L.c_copy_row, L.pair};
     m.d.y = at;
@@ -183,15 +240,15 @@ YuvMirror yuv_mirror(const w2xc_yuv_planes &host, unsigned char *at, const YuvMi
     if (L.c_copy_row) { m.d.u = at + L.u; m.d.v = at + L.v; m.d.c_stride = L.c_stride; m.d.c_frame_stride = L.c_frame_stride; }
     return m;
 }
-// frames [b0, b0 + S) of the host side <-> the mirror's first S frames, blocking
-int yuv_copy(const YuvMirror &m, const w2xc_yuv_planes &host, size_t b0, int S, int w, int h, int ch, bool upload)
+// frames [b0, b0 + S) of the host side <-> the mirror's first S frames, blocking; row = the bytes of a luma row
+int yuv_copy(const YuvMirror &m, const YuvSide &host, size_t b0, int S, size_t row, int h, int ch, bool upload)
 {
     const hipMemcpyKind kind = upload ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
-    const auto copy = [&](unsigned char *dev, size_t dev_row, unsigned char *hst, size_t hst_row, size_t row, int rows) {
-        return upload ? hipMemcpy2D(dev, dev_row, hst, hst_row, row, rows, kind) : hipMemcpy2D(hst, hst_row, dev, dev_row, row, rows, kind);
+    const auto copy = [&](unsigned char *dev, size_t dev_row, unsigned char *hst, size_t hst_row, size_t row_bytes, int rows) {
+        return upload ? hipMemcpy2D(dev, dev_row, hst, hst_row, row_bytes, rows, kind) : hipMemcpy2D(hst, hst_row, dev, dev_row, row_bytes, rows, kind);
     };
     for (int i = 0; i < S; i++) {
-        HIP_TRY(copy(m.d.y + i * m.d.y_frame_stride, m.d.y_stride, host.y + (b0 + i) * host.y_frame_stride, host.y_stride, (size_t)w, h));
+        HIP_TRY(copy(m.d.y + i * m.d.y_frame_stride, m.d.y_stride, host.y + (b0 + i) * host.y_frame_stride, host.y_stride, row, h));
         if (!m.c_copy_row) continue;
         const size_t hoff = (b0 + i) * host.c_frame_stride, doff = i * m.d.c_frame_stride;
         if (m.pair) HIP_TRY(copy(std::min(m.d.u, m.d.v) + doff, m.d.c_stride, std::min(host.u, host.v) + hoff, host.c_stride, m.c_copy_row, ch));
@@ -203,14 +260,16 @@ int yuv_copy(const YuvMirror &m, const w2xc_yuv_planes &host, size_t b0, int S, 
     return W2XC_OK;
 }
 
-int frames_yuv_host(ImageCall c, bool rgb, int n, int chroma, int range, int matrix, const w2xc_yuv_planes *in, const w2xc_yuv_planes *out)
+int frames_yuv_host(ImageCall c, const YuvCall &k, const YuvSide *in, const YuvSide *out)
 {
     YuvGeom g;
+    g.bps = k.bps; g.depth = k.depth;
     int sub = 1;
-    int rc = check_yuv_call(c, rgb, n, chroma, range, matrix, in, out, &g, &sub);
+    const int n = k.n;
+    int rc = check_yuv_call(c, k.rgb, n, k.chroma, k.range, k.matrix, in, out, &g, &sub);
     if (rc) return rc;
-    if (g.cw) for (const w2xc_yuv_planes *s : {in, out})
-        if (s->c_px == 2 && s->v != s->u + 1 && s->u != s->v + 1)
+    if (g.cw) for (const YuvSide *s : {in, out})
+        if (s->c_px == 2 && s->v != s->u + g.bps && s->u != s->v + g.bps)
             return fail(W2XC_ERR_ARG, "host planes with c_px = 2: the two chroma planes must interleave (NV12: v = u + 1; NV21: u = v + 1)");
     sub = std::min(sub, n);
     std::vector<int> devs;
@@ -220,16 +279,68 @@ int frames_yuv_host(ImageCall c, bool rgb, int n, int chroma, int range, int mat
     c.ctx = lc;
     c.st = nullptr;
     DevCtx *own = c.ctx.owner();
-    const YuvMirrorLayout li = yuv_mirror_layout(in->c_px, in->u < in->v, sub, c.w, c.h, g.cw, g.ch), lo = yuv_mirror_layout(out->c_px, out->u < out->v, sub, g.W, g.H, g.ocw, g.och);
+    const YuvMirrorLayout li = yuv_mirror_layout(in->c_px, in->u < in->v, sub, c.w, c.h, g.cw, g.ch, g.bps),
+                          lo = yuv_mirror_layout(out->c_px, out->u < out->v, sub, g.W, g.H, g.ocw, g.och, g.bps);
     if ((rc = own->img_io.reserve(li.bytes + lo.bytes, "the frames"))) return rc;
     unsigned char *dev = own->img_io.as<unsigned char>();
-    const YuvMirror mi = yuv_mirror(*in, dev, li), mo = yuv_mirror(*out, dev + li.bytes, lo);
+    YuvMirror mi = yuv_mirror(*in, dev, li), mo = yuv_mirror(*out, dev + li.bytes, lo);
     return for_sub_batches(n, sub, [&](int b0, int S) {
-        if (int r = yuv_copy(mi, *in, b0, S, c.w, c.h, g.ch, true)) return r;
+        if (int r = yuv_copy(mi, *in, b0, S, (size_t)c.w * g.bps, c.h, g.ch, true)) return r;
         if (int r = process_yuv_sub_batch(c, g, S, sub, mi.d, mo.d)) { hipDeviceSynchronize(); return r; }
         HIP_TRY(hipDeviceSynchronize());
-        return yuv_copy(mo, *out, b0, S, g.W, g.H, g.och, false);
+        return yuv_copy(mo, *out, b0, S, (size_t)g.W * g.bps, g.H, g.och, false);
     });
+}
+
+// the call forms on either struct of the interface
+template <class Planes> int frames_yuv(bool host, const ImageCall &c, const YuvCall &k, const Planes *in, const Planes *out)
+{
+    YuvSide si, so;
+    const YuvSide *pi = side_of(in, &si), *po = side_of(out, &so);
+    return host ? frames_yuv_host(c, k, pi, po) : frames_yuv_device(c, k, pi, po);
+}
+
+// what the two blocks of the RGB route refuse: the frames' side as check_yuv_side refuses it, the 3 n float planes, and the two sides overlapping
+int check_yuv_rgb_block_args(const YuvSide *f, int bps, int depth, bool f_is_out, int n, int w, int h, int chroma, int range, int matrix, const float *rgb,
+                             size_t image_stride_bytes, size_t plane_stride_bytes)
+{
+    if (!f || !rgb) return fail(W2XC_ERR_ARG, "null argument");
+    if (n < 1 || n > (1 << 20) || w <= 0 || h <= 0 || w > (1 << 22) || h > (1 << 22)) return fail(W2XC_ERR_ARG, "bad frame count / frame size");
+    if (chroma == W2XC_YUV_400) return fail(W2XC_ERR_ARG, "a frame without chroma (W2XC_YUV_400) has no colour to convert");
+    if (int rc = check_chroma_range(chroma, range)) return rc;
+    if (int rc = check_depth(bps, depth)) return rc;
+    if (int rc = check_matrix(matrix)) return rc;
+    const size_t plane = (size_t)4 * w * h;
+    if ((image_stride_bytes & 3) || (plane_stride_bytes & 3) || plane_stride_bytes < plane || (n > 1 && image_stride_bytes < 2 * plane_stride_bytes + plane))
+        return fail(W2XC_ERR_ARG, "plane / image strides: multiples of 4, a plane stride of at least a plane, an image stride of at least three planes");
+    const ChromaSize cs = yuv_chroma_size(w, h, chroma);
+    std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> iv;
+    if (int rc = check_yuv_side(f, bps, n, w, h, cs.cw, cs.ch, f_is_out ? 1 : 0, iv)) return rc;
+    for (int i = 0; i < n; i++) for (int p = 0; p < 3; p++) {
+        const uintptr_t at = (uintptr_t)rgb + i * image_stride_bytes + p * plane_stride_bytes;
+        iv.push_back({{at, at + plane}, f_is_out ? 0 : 1});
+    }
+    return check_batch_overlap(iv);
+}
+
+// what the three building blocks of the Y route refuse: n planes of samples (bps bytes each) of row_bytes-byte rows x `rows` at p and n planes of `other` bytes (rows /
+// planes as given) on the other side
+int check_yuv_block_args(const void *p, size_t frame, size_t row, size_t row_bytes, int rows, int n, int w, int h, const void *q, size_t q_plane, size_t q_ext, int bps = 1)
+{
+    if (!p || !q) return fail(W2XC_ERR_ARG, "null argument");
+    if (n < 1 || n > (1 << 20) || w <= 0 || h <= 0 || w > (1 << 22) || h > (1 << 22)) return fail(W2XC_ERR_ARG, "bad plane count / plane size");
+    const size_t ext = (size_t)(rows - 1) * row + row_bytes;
+    if (row < row_bytes || (n > 1 && (frame < ext || q_plane < q_ext))) return fail(W2XC_ERR_ARG, "row / plane strides below a row / a plane");
+    if (bps == 2 && (((uintptr_t)p | row | frame) & 1)) return fail(W2XC_ERR_ARG, "16-bit samples need an even pointer and even strides");
+    if (ranges_overlap(p, (size_t)(n - 1) * frame + ext, q, (size_t)(n - 1) * q_plane + q_ext)) return fail(W2XC_ERR_ARG, "source and destination overlap");
+    return W2XC_OK;
+}
+// ... and of their other arguments: the float planes' stride, the range, and for words the depth and the packing
+int check_luma_block_format(size_t plane_stride_bytes, int range, int bps = 1, int depth = 8, int pack = 0)
+{
+    if ((plane_stride_bytes & 3) || (range != W2XC_RANGE_FULL && range != W2XC_RANGE_LIMITED)) return fail(W2XC_ERR_ARG, "plane stride no multiple of 4 / unknown range");
+    if (pack != W2XC_PACK_LOW && pack != W2XC_PACK_HIGH) return fail(W2XC_ERR_ARG, "pack must be W2XC_PACK_LOW or W2XC_PACK_HIGH, got %d", pack);
+    return check_depth(bps, depth);
 }
 
 }  // namespace
@@ -244,84 +355,104 @@ extern "C" {
 int w2xc_process_frames_yuv_u8_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, const w2xc_yuv_planes *d_in,
                                       const w2xc_yuv_planes *d_out, int iterations, void *hip_stream, const w2xc_opts *opts)
 try {
-    return frames_yuv_device(ImageCall(noise_model, scale_model, w, h, iterations, 0.0, hip_stream, opts), false, n, chroma, range, 0, d_in, d_out);
+    return frames_yuv(false, ImageCall(noise_model, scale_model, w, h, iterations, 0.0, hip_stream, opts), {false, n, chroma, range, 0}, d_in, d_out);
 } W2XC_CATCH_ALL
 
 int w2xc_process_frames_yuv_u8(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, const w2xc_yuv_planes *in,
                                const w2xc_yuv_planes *out, int iterations, const w2xc_opts *opts)
 try {
-    return frames_yuv_host(ImageCall(noise_model, scale_model, w, h, iterations, 0.0, nullptr, opts), false, n, chroma, range, 0, in, out);
+    return frames_yuv(true, ImageCall(noise_model, scale_model, w, h, iterations, 0.0, nullptr, opts), {false, n, chroma, range, 0}, in, out);
 } W2XC_CATCH_ALL
 
 // ---- YUV frames through RGB and head models, by a colour matrix ----
 int w2xc_process_frames_yuv_u8_rgb_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int matrix,
                                           const w2xc_yuv_planes *d_in, const w2xc_yuv_planes *d_out, int iterations, void *hip_stream, const w2xc_opts *opts)
 try {
-    return frames_yuv_device(ImageCall(noise_model, scale_model, w, h, iterations, 0.0, hip_stream, opts), true, n, chroma, range, matrix, d_in, d_out);
+    return frames_yuv(false, ImageCall(noise_model, scale_model, w, h, iterations, 0.0, hip_stream, opts), {true, n, chroma, range, matrix}, d_in, d_out);
 } W2XC_CATCH_ALL
 
 int w2xc_process_frames_yuv_u8_rgb(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int matrix, const w2xc_yuv_planes *in,
                                    const w2xc_yuv_planes *out, int iterations, const w2xc_opts *opts)
 try {
-    return frames_yuv_host(ImageCall(noise_model, scale_model, w, h, iterations, 0.0, nullptr, opts), true, n, chroma, range, matrix, in, out);
+    return frames_yuv(true, ImageCall(noise_model, scale_model, w, h, iterations, 0.0, nullptr, opts), {true, n, chroma, range, matrix}, in, out);
 } W2XC_CATCH_ALL
 
-// what the two blocks refuse: the frames' side as check_yuv_side refuses it, the 3 n float planes, and the two sides overlapping
-static int check_yuv_rgb_block_args(const w2xc_yuv_planes *f, bool f_is_out, int n, int w, int h, int chroma, int range, int matrix, const float *rgb,
-                                    size_t image_stride_bytes, size_t plane_stride_bytes)
-{
-    if (!f || !rgb) return fail(W2XC_ERR_ARG, "null argument");
-    if (n < 1 || n > (1 << 20) || w <= 0 || h <= 0 || w > (1 << 22) || h > (1 << 22)) return fail(W2XC_ERR_ARG, "bad frame count / frame size");
-    if (chroma == W2XC_YUV_400) return fail(W2XC_ERR_ARG, "a frame without chroma (W2XC_YUV_400) has no colour to convert");
-    if (int rc = check_chroma_range(chroma, range)) return rc;
-    if (int rc = check_matrix(matrix)) return rc;
-    const size_t plane = (size_t)4 * w * h;
-    if ((image_stride_bytes & 3) || (plane_stride_bytes & 3) || plane_stride_bytes < plane || (n > 1 && image_stride_bytes < 2 * plane_stride_bytes + plane))
-        return fail(W2XC_ERR_ARG, "plane / image strides: multiples of 4, a plane stride of at least a plane, an image stride of at least three planes");
-    const ChromaSize cs = yuv_chroma_size(w, h, chroma);
-    std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> iv;
-    if (int rc = check_yuv_side(f, n, w, h, cs.cw, cs.ch, f_is_out ? 1 : 0, iv)) return rc;
-    for (int i = 0; i < n; i++) for (int p = 0; p < 3; p++) {
-        const uintptr_t at = (uintptr_t)rgb + i * image_stride_bytes + p * plane_stride_bytes;
-        iv.push_back({{at, at + plane}, f_is_out ? 0 : 1});
-    }
-    return check_batch_overlap(iv);
-}
+// ---- 16-bit YUV frames: the same four calls on words ----
+int w2xc_process_frames_yuv_u16_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int depth,
+                                       const w2xc_yuv16_planes *d_in, const w2xc_yuv16_planes *d_out, int iterations, void *hip_stream, const w2xc_opts *opts)
+try {
+    return frames_yuv(false, ImageCall(noise_model, scale_model, w, h, iterations, 0.0, hip_stream, opts), {false, n, chroma, range, 0, 2, depth}, d_in, d_out);
+} W2XC_CATCH_ALL
 
+int w2xc_process_frames_yuv_u16(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int depth, const w2xc_yuv16_planes *in,
+                                const w2xc_yuv16_planes *out, int iterations, const w2xc_opts *opts)
+try {
+    return frames_yuv(true, ImageCall(noise_model, scale_model, w, h, iterations, 0.0, nullptr, opts), {false, n, chroma, range, 0, 2, depth}, in, out);
+} W2XC_CATCH_ALL
+
+int w2xc_process_frames_yuv_u16_rgb_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int depth, int matrix,
+                                           const w2xc_yuv16_planes *d_in, const w2xc_yuv16_planes *d_out, int iterations, void *hip_stream, const w2xc_opts *opts)
+try {
+    return frames_yuv(false, ImageCall(noise_model, scale_model, w, h, iterations, 0.0, hip_stream, opts), {true, n, chroma, range, matrix, 2, depth}, d_in, d_out);
+} W2XC_CATCH_ALL
+
+int w2xc_process_frames_yuv_u16_rgb(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int depth, int matrix,
+                                    const w2xc_yuv16_planes *in, const w2xc_yuv16_planes *out, int iterations, const w2xc_opts *opts)
+try {
+    return frames_yuv(true, ImageCall(noise_model, scale_model, w, h, iterations, 0.0, nullptr, opts), {true, n, chroma, range, matrix, 2, depth}, in, out);
+} W2XC_CATCH_ALL
+
+// ---- the two ends of the RGB route ----
 int w2xc_yuv8_to_rgb_device(const w2xc_yuv_planes *d_src, int n, int w, int h, int chroma, int range, int matrix, float *d_rgb, size_t image_stride_bytes,
                             size_t plane_stride_bytes, void *hip_stream)
 try {
-    if (int rc = check_yuv_rgb_block_args(d_src, false, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes)) return rc;
-    HIP_TRY(w2xc_launch_yuv8_to_rgb(luma_planes(*d_src), chroma_planes(*d_src), d_src->v, w, h, chroma, range, matrix, d_rgb,
-                                    (long long)(image_stride_bytes / 4), (long long)(plane_stride_bytes / 4), n, (hipStream_t)hip_stream));
+    YuvSide store;
+    const YuvSide *s = side_of(d_src, &store);
+    if (int rc = check_yuv_rgb_block_args(s, 1, 8, false, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes)) return rc;
+    HIP_TRY(w2xc_launch_yuv8_to_rgb(luma_planes(*s), chroma_planes(*s), s->v, w, h, chroma, range, matrix, d_rgb, (long long)(image_stride_bytes / 4),
+                                    (long long)(plane_stride_bytes / 4), n, (hipStream_t)hip_stream));
     return W2XC_OK;
 } W2XC_CATCH_ALL
 
 int w2xc_rgb_to_yuv8_device(const float *d_rgb, size_t image_stride_bytes, size_t plane_stride_bytes, int n, int w, int h, int chroma, int range, int matrix,
                             const w2xc_yuv_planes *d_dst, void *hip_stream)
 try {
-    if (int rc = check_yuv_rgb_block_args(d_dst, true, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes)) return rc;
-    HIP_TRY(w2xc_launch_rgb_to_yuv8(d_rgb, (long long)(image_stride_bytes / 4), (long long)(plane_stride_bytes / 4), w, h, chroma, range, matrix,
-                                    luma_planes(*d_dst), chroma_planes(*d_dst), d_dst->v, n, (hipStream_t)hip_stream));
+    YuvSide store;
+    const YuvSide *s = side_of(d_dst, &store);
+    if (int rc = check_yuv_rgb_block_args(s, 1, 8, true, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes)) return rc;
+    HIP_TRY(w2xc_launch_rgb_to_yuv8(d_rgb, (long long)(image_stride_bytes / 4), (long long)(plane_stride_bytes / 4), w, h, chroma, range, matrix, luma_planes(*s),
+                                    chroma_planes(*s), s->v, n, (hipStream_t)hip_stream));
     return W2XC_OK;
 } W2XC_CATCH_ALL
 
-// what the three building blocks refuse: n byte planes of bw-byte rows x h at p and n planes of `other` bytes (rows / planes as given) on the other side
-static int check_yuv_block_args(const void *p, size_t frame, size_t row, size_t row_bytes, int rows, int n, int w, int h, const void *q, size_t q_plane, size_t q_ext)
-{
-    if (!p || !q) return fail(W2XC_ERR_ARG, "null argument");
-    if (n < 1 || n > (1 << 20) || w <= 0 || h <= 0 || w > (1 << 22) || h > (1 << 22)) return fail(W2XC_ERR_ARG, "bad plane count / plane size");
-    const size_t ext = (size_t)(rows - 1) * row + row_bytes;
-    if (row < row_bytes || (n > 1 && (frame < ext || q_plane < q_ext))) return fail(W2XC_ERR_ARG, "row / plane strides below a row / a plane");
-    if (ranges_overlap(p, (size_t)(n - 1) * frame + ext, q, (size_t)(n - 1) * q_plane + q_ext)) return fail(W2XC_ERR_ARG, "source and destination overlap");
+int w2xc_yuv16_to_rgb_device(const w2xc_yuv16_planes *d_src, int n, int w, int h, int chroma, int range, int depth, int matrix, float *d_rgb, size_t image_stride_bytes,
+                             size_t plane_stride_bytes, void *hip_stream)
+try {
+    YuvSide store;
+    const YuvSide *s = side_of(d_src, &store);
+    if (int rc = check_yuv_rgb_block_args(s, 2, depth, false, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes)) return rc;
+    HIP_TRY(w2xc_launch_yuv16_to_rgb(luma_words(*s), chroma_words(*s), words(s->v), w, h, chroma, range, matrix, depth, d_rgb, (long long)(image_stride_bytes / 4),
+                                     (long long)(plane_stride_bytes / 4), n, (hipStream_t)hip_stream));
     return W2XC_OK;
-}
+} W2XC_CATCH_ALL
 
+int w2xc_rgb_to_yuv16_device(const float *d_rgb, size_t image_stride_bytes, size_t plane_stride_bytes, int n, int w, int h, int chroma, int range, int depth, int matrix,
+                             const w2xc_yuv16_planes *d_dst, void *hip_stream)
+try {
+    YuvSide store;
+    const YuvSide *s = side_of(d_dst, &store);
+    if (int rc = check_yuv_rgb_block_args(s, 2, depth, true, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes)) return rc;
+    HIP_TRY(w2xc_launch_rgb_to_yuv16(d_rgb, (long long)(image_stride_bytes / 4), (long long)(plane_stride_bytes / 4), w, h, chroma, range, matrix, depth, luma_words(*s),
+                                     chroma_words(*s), words(s->v), n, (hipStream_t)hip_stream));
+    return W2XC_OK;
+} W2XC_CATCH_ALL
+
+// ---- the building blocks of the Y route ----
 int w2xc_y8_to_plane_device(const unsigned char *d_src, int n, size_t frame_stride_bytes, size_t stride_bytes, int w, int h, int range, float *d_dst,
                             size_t plane_stride_bytes, void *hip_stream)
 {
     if (int rc = check_yuv_block_args(d_src, frame_stride_bytes, stride_bytes, (size_t)(w > 0 ? w : 1), h, n, w, h, d_dst, plane_stride_bytes, (size_t)4 * (w > 0 ? w : 1) * (h > 0 ? h : 1))) return rc;
-    if ((plane_stride_bytes & 3) || (range != W2XC_RANGE_FULL && range != W2XC_RANGE_LIMITED)) return fail(W2XC_ERR_ARG, "plane stride no multiple of 4 / unknown range");
+    if (int rc = check_luma_block_format(plane_stride_bytes, range)) return rc;
     HIP_TRY(w2xc_launch_y8_to_plane({const_cast<unsigned char *>(d_src), (long long)frame_stride_bytes, (long long)stride_bytes, 1}, w, h, range, d_dst,
                                     (long long)(plane_stride_bytes / 4), n, (hipStream_t)hip_stream));
     return W2XC_OK;
@@ -331,7 +462,7 @@ int w2xc_plane_to_y8_device(const float *d_src, int n, size_t plane_stride_bytes
                             size_t stride_bytes, void *hip_stream)
 {
     if (int rc = check_yuv_block_args(d_dst, frame_stride_bytes, stride_bytes, (size_t)(w > 0 ? w : 1), h, n, w, h, d_src, plane_stride_bytes, (size_t)4 * (w > 0 ? w : 1) * (h > 0 ? h : 1))) return rc;
-    if ((plane_stride_bytes & 3) || (range != W2XC_RANGE_FULL && range != W2XC_RANGE_LIMITED)) return fail(W2XC_ERR_ARG, "plane stride no multiple of 4 / unknown range");
+    if (int rc = check_luma_block_format(plane_stride_bytes, range)) return rc;
     HIP_TRY(w2xc_launch_plane_to_y8(d_src, (long long)(plane_stride_bytes / 4), w, h, range, {d_dst, (long long)frame_stride_bytes, (long long)stride_bytes, 1}, n,
                                     (hipStream_t)hip_stream));
     return W2XC_OK;
@@ -347,6 +478,45 @@ int w2xc_chroma2x_u8_device(const unsigned char *d_src, int n, size_t src_frame_
     if (int rc = check_yuv_block_args(d_src, src_frame_stride_bytes, src_stride_bytes, (size_t)src_px * ((cw > 0 ? cw : 1) - 1) + 1, ch, n, cw, ch, d_dst, dst_frame_stride_bytes, dext)) return rc;
     HIP_TRY(w2xc_launch_chroma2x_u8({const_cast<unsigned char *>(d_src), (long long)src_frame_stride_bytes, (long long)src_stride_bytes, src_px}, nullptr, cw, ch,
                                     {d_dst, (long long)dst_frame_stride_bytes, (long long)dst_stride_bytes, dst_px}, nullptr, ow, oh, n, (hipStream_t)hip_stream));
+    return W2XC_OK;
+}
+
+int w2xc_y16_to_plane_device(const unsigned short *d_src, int n, size_t frame_stride_bytes, size_t stride_bytes, int w, int h, int range, int depth, int pack,
+                             float *d_dst, size_t plane_stride_bytes, void *hip_stream)
+{
+    if (int rc = check_yuv_block_args(d_src, frame_stride_bytes, stride_bytes, (size_t)2 * (w > 0 ? w : 1), h, n, w, h, d_dst, plane_stride_bytes, (size_t)4 * (w > 0 ? w : 1) * (h > 0 ? h : 1), 2)) return rc;
+    if (int rc = check_luma_block_format(plane_stride_bytes, range, 2, depth, pack)) return rc;
+    HIP_TRY(w2xc_launch_y16_to_plane({const_cast<unsigned short *>(d_src), (long long)(frame_stride_bytes / 2), (long long)(stride_bytes / 2), 1, pack}, w, h, range,
+                                     depth, d_dst, (long long)(plane_stride_bytes / 4), n, (hipStream_t)hip_stream));
+    return W2XC_OK;
+}
+
+int w2xc_plane_to_y16_device(const float *d_src, int n, size_t plane_stride_bytes, int w, int h, int range, int depth, int pack, unsigned short *d_dst,
+                             size_t frame_stride_bytes, size_t stride_bytes, void *hip_stream)
+{
+    if (int rc = check_yuv_block_args(d_dst, frame_stride_bytes, stride_bytes, (size_t)2 * (w > 0 ? w : 1), h, n, w, h, d_src, plane_stride_bytes, (size_t)4 * (w > 0 ? w : 1) * (h > 0 ? h : 1), 2)) return rc;
+    if (int rc = check_luma_block_format(plane_stride_bytes, range, 2, depth, pack)) return rc;
+    HIP_TRY(w2xc_launch_plane_to_y16(d_src, (long long)(plane_stride_bytes / 4), w, h, range, depth,
+                                     {d_dst, (long long)(frame_stride_bytes / 2), (long long)(stride_bytes / 2), 1, pack}, n, (hipStream_t)hip_stream));
+    return W2XC_OK;
+}
+
+int w2xc_chroma2x_u16_device(const unsigned short *d_src, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int src_pack, int cw, int ch,
+                             int depth, unsigned short *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int dst_pack, int ow, int oh,
+                             void *hip_stream)
+{
+    if ((src_px != 1 && src_px != 2) || (dst_px != 1 && dst_px != 2)) return fail(W2XC_ERR_ARG, "src_px / dst_px must be 1 or 2");
+    if (ow < 1 || oh < 1 || ow > 2 * (long long)cw || oh > 2 * (long long)ch) return fail(W2XC_ERR_ARG, "the output size lies outside the 2x enlargement");
+    const size_t drow = chroma_row_bytes(ow, dst_px, 2), dext = (size_t)(oh - 1) * dst_stride_bytes + drow;
+    if (dst_stride_bytes < drow) return fail(W2XC_ERR_ARG, "row / plane strides below a row / a plane");
+    if (int rc = check_yuv_block_args(d_src, src_frame_stride_bytes, src_stride_bytes, chroma_row_bytes(cw > 0 ? cw : 1, src_px, 2), ch, n, cw, ch, d_dst, dst_frame_stride_bytes, dext, 2)) return rc;
+    if (((uintptr_t)d_dst | dst_stride_bytes | dst_frame_stride_bytes) & 1) return fail(W2XC_ERR_ARG, "16-bit samples need an even pointer and even strides");
+    if ((src_pack != W2XC_PACK_LOW && src_pack != W2XC_PACK_HIGH) || (dst_pack != W2XC_PACK_LOW && dst_pack != W2XC_PACK_HIGH))
+        return fail(W2XC_ERR_ARG, "src_pack / dst_pack must be W2XC_PACK_LOW or W2XC_PACK_HIGH");
+    if (int rc = check_depth(2, depth)) return rc;
+    HIP_TRY(w2xc_launch_chroma2x_u16({const_cast<unsigned short *>(d_src), (long long)(src_frame_stride_bytes / 2), (long long)(src_stride_bytes / 2), src_px, src_pack},
+                                     nullptr, cw, ch, {d_dst, (long long)(dst_frame_stride_bytes / 2), (long long)(dst_stride_bytes / 2), dst_px, dst_pack}, nullptr, ow,
+                                     oh, depth, n, (hipStream_t)hip_stream));
     return W2XC_OK;
 }
 

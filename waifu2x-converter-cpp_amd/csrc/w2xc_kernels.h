@@ -221,3 +221,23 @@ hipError_t w2xc_launch_rgb_to_yuv8(const float *rgb, long long is, long long ps,
 #define W2XC_YUVRGB_TCX 32
 #define W2XC_YUVRGB_TCY 16
 #define W2XC_YUVRGB_GRID_MAX 2048
+
+// ---- 16-bit YUV frames (w2xc_yuv16.hip, w2xc_yuv16_rgb.hip; the arithmetic: include/w2xc_hip.h, "16-bit YUV frames") ----
+// One plane of each of n frames, in 16-bit words that hold a value of `depth` bits: frame i's at p + i * frame WORDS, rows `row` words apart, samples px words
+// apart (1 = planar, 2 = one of two interleaved planes: P010's U at p, V at p + 1); pack = W2XC_PACK_LOW (0: the value in the low bits) / W2XC_PACK_HIGH (1).
+struct W2xcU16Planes {
+    unsigned short *p;
+    long long frame, row;
+    int px, pack;
+};
+// the launchers of the sections above on words: the same arguments and `depth` (8 .. 16); the chroma launchers take the two sides' packings from su / du
+hipError_t w2xc_launch_y16_to_plane(W2xcU16Planes src, int w, int h, int range, int depth, float *dst, long long ps, int n, hipStream_t st);
+hipError_t w2xc_launch_plane_to_y16(const float *src, long long ps, int w, int h, int range, int depth, W2xcU16Planes dst, int n, hipStream_t st);
+// (a turn of k_chroma2x_u16 is one tile of ALL planes of one frame -- U, or U and V: tiles x n turns, at most W2XC_CHROMA_GRID_MAX workgroups)
+hipError_t w2xc_launch_chroma2x_u16(W2xcU16Planes su, const unsigned short *sv, int cw, int ch, W2xcU16Planes du, unsigned short *dv, int ow, int oh, int depth, int n,
+                                    hipStream_t st);
+hipError_t w2xc_launch_chroma_copy_u16(W2xcU16Planes su, const unsigned short *sv, int cw, int ch, W2xcU16Planes du, unsigned short *dv, int depth, int n, hipStream_t st);
+hipError_t w2xc_launch_yuv16_to_rgb(W2xcU16Planes y, W2xcU16Planes u, const unsigned short *v, int w, int h, int chroma, int range, int matrix, int depth, float *rgb,
+                                    long long is, long long ps, int n, hipStream_t st);
+hipError_t w2xc_launch_rgb_to_yuv16(const float *rgb, long long is, long long ps, int w, int h, int chroma, int range, int matrix, int depth, W2xcU16Planes y,
+                                    W2xcU16Planes u, unsigned short *v, int n, hipStream_t st);

@@ -226,6 +226,8 @@ const char *w2xc_last_error(void) { return g_last_error.c_str(); }
 // w2xc_yuv_planes (additive; w2xc_opts stays 56 bytes; the string stays, the revision is found by the presence of the symbols).
 // 0.4.1.8: YUV frames through RGB and head models -- w2xc_process_frames_yuv_u8_rgb[_device], w2xc_yuv8_to_rgb_device, w2xc_rgb_to_yuv8_device and the constants
 // W2XC_MATRIX_* (additive; w2xc_opts stays 56 bytes; the string stays, the revision is found by the presence of the symbols).
+// 0.4.1.9: 16-bit YUV frames -- w2xc_process_frames_yuv_u16[_rgb][_device], w2xc_y16_to_plane_device, w2xc_plane_to_y16_device, w2xc_chroma2x_u16_device,
+// w2xc_yuv16_to_rgb_device, w2xc_rgb_to_yuv16_device, the struct w2xc_yuv16_planes and W2XC_PACK_* (additive; w2xc_opts stays 56 bytes; the string stays).
 const char *w2xc_version(void) { return "w2xc_hip 0.4.1.6.1 (gfx950)"; }
 
 int w2xc_plan_rows(const w2xc_model *m, int w, int view_y0, int view_h, int plane_h, int row_begin, int row_end, const w2xc_opts *opts, w2xc_row_plan *plan)

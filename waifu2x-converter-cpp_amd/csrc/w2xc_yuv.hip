@@ -8,6 +8,7 @@
 #include "w2xc_kernels.h"
 #include "w2xc_tta_px.h"   // clampi, to_u8
 #include "w2xc_px.h"       // k_px, launch_px, row_col, cubic_coeffs
+#include "w2xc_yuv_px.h"   // chroma_row_sum
 
 // luma byte -> y: full range (float)Y * (float)(1.0 / 255.0), limited range ((float)Y - 16) * (float)(1.0 / 219.0).  Frame i's plane at dst + i * ps floats
 struct Y8ToPlane {
@@ -87,16 +88,6 @@ hipError_t w2xc_launch_chroma_copy_u8(W2xcU8Planes su, const unsigned char *sv, 
 #define CH_SH (CH_TQY + 3)
 #define CH_LD (CH_SW + 2)
 static_assert(CH_TQX == 32 && CH_TQY == 16 && (CH_LD & 1) == 1 && CH_SW <= CH_LD, "256 threads = 32 x 8 quads, two quad rows per thread");
-
-// the four taps of one row of the neighbourhood, summed in Resize2xCubic's order
-static __device__ __forceinline__ float chroma_row_sum(const float *S, const float *c)
-{
-    float a = S[0] * c[0];
-    a = a + S[1] * c[1];
-    a = a + S[2] * c[2];
-    a = a + S[3] * c[3];
-    return a;
-}
 
 template <bool DW>
 __global__ void __launch_bounds__(256) k_chroma2x_u8(const unsigned char *su, const unsigned char *sv, long long sframe, long long srow, int spx, int cw, int ch,

@@ -10,22 +10,13 @@
 // all frames are the turns of one grid-stride loop over at most W2XC_YUVRGB_GRID_MAX workgroups; the frame index moves only the 64-bit bases.
 #include "w2xc_kernels.h"
 #include "w2xc_tta_px.h"   // clampi, to_u8
+#include "w2xc_yuv_px.h"   // lerp31, clamp01, to_ycc, the constants of a matrix
 
 #define YR_TCX W2XC_YUVRGB_TCX
 #define YR_TCY W2XC_YUVRGB_TCY
 #define YR_LD (YR_TCX + 3)          // words per LDS row of chroma: the tile, a halo sample at either side, one word of padding -- an odd count
 #define YR_YLD (2 * YR_TCX + 4)     // bytes per LDS row of luma: the widest tile and one dword of padding
 static_assert(YR_TCX == 32 && YR_TCY == 16 && (YR_LD & 1) == 1 && (YR_YLD & 3) == 0, "256 threads = 32 x 8 chroma samples, two rows per thread");
-
-// 0.75 C[j] + 0.25 C[j']: on bytes as floats every operation is exact (multiples of 1/4 and then of 1/16 below 256)
-static __device__ __forceinline__ float lerp31(float near, float far)
-{
-    const float a = 0.75f * near;
-    const float b = 0.25f * far;
-    return a + b;
-}
-
-static __device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
 
 // ---- bytes -> R, G, B ----
 // The chroma tile with a one-sample halo along each subsampled axis (coordinates clamped into the plane, as the taps are) is fetched once for U and once for V
@@ -176,40 +167,13 @@ static hipError_t launch_to_rgb(bool dw, unsigned grid, hipStream_t st, const un
     return hipGetLastError();
 }
 
-// the constants of a matrix: doubles from the two luma weights, each rounded once to float (the header lists the expressions)
-static bool matrix_weights(int matrix, double *Kr, double *Kb)
-{
-    switch (matrix) {
-    case 0: *Kr = 0.299; *Kb = 0.114; return true;      // W2XC_MATRIX_BT601
-    case 1: *Kr = 0.2126; *Kb = 0.0722; return true;    // W2XC_MATRIX_BT709
-    case 2: *Kr = 0.2627; *Kb = 0.0593; return true;    // W2XC_MATRIX_BT2020
-    }
-    return false;
-}
-
-// every row of every float plane starts on an 8-byte boundary: a thread's two adjacent pixels are one 8-byte access
-static int rows_8_aligned(const float *rgb, long long is, long long ps, int w, int n)
-{
-    return ((reinterpret_cast<size_t>(rgb) & 7) == 0 && (w & 1) == 0 && (ps & 1) == 0 && (n == 1 || (is & 1) == 0)) ? 1 : 0;
-}
-
-static bool frame_geometry(int w, int h, int chroma, int *cw, int *ch)
-{
-    if (w < 1 || h < 1 || chroma < 0 || chroma > 2) return false;
-    *cw = chroma != 2 ? (w + 1) / 2 : w;
-    *ch = chroma == 0 ? (h + 1) / 2 : h;
-    return true;
-}
-
 hipError_t w2xc_launch_yuv8_to_rgb(W2xcU8Planes y, W2xcU8Planes u, const unsigned char *v, int w, int h, int chroma, int range, int matrix, float *rgb, long long is,
                                    long long ps, int n, hipStream_t st)
 {
-    double Kr, Kb;
+    W2xcYuvToRgb m;
     int cw, ch;
-    if (!matrix_weights(matrix, &Kr, &Kb) || !frame_geometry(w, h, chroma, &cw, &ch) || n < 1 || !y.p || !u.p || !v || !rgb || y.px != 1 || (u.px != 1 && u.px != 2))
+    if (!matrix_to_rgb(matrix, &m) || !frame_geometry(w, h, chroma, &cw, &ch) || n < 1 || !y.p || !u.p || !v || !rgb || y.px != 1 || (u.px != 1 && u.px != 2))
         return hipErrorInvalidValue;
-    const double Kg = 1.0 - Kr - Kb, cRV = 2.0 * (1.0 - Kr), cBU = 2.0 * (1.0 - Kb);
-    const W2xcYuvToRgb m = {(float)cRV, (float)cBU, (float)(Kr * cRV / Kg), (float)(Kb * cBU / Kg)};
     const int tiles_x = (cw + YR_TCX - 1) / YR_TCX, tiles_y = (ch + YR_TCY - 1) / YR_TCY;
     const long long tiles = (long long)tiles_x * tiles_y, turns = tiles * n;
     const unsigned grid = (unsigned)(turns > W2XC_YUVRGB_GRID_MAX ? W2XC_YUVRGB_GRID_MAX : turns);
@@ -228,18 +192,6 @@ hipError_t w2xc_launch_yuv8_to_rgb(W2xcU8Planes y, W2xcU8Planes u, const unsigne
 // and one V byte, and stores only to its own samples: byte stores, or -- Y16: every luma row starts on an even address -- one 16-bit store for the two luma
 // bytes of a row where both lie in the plane.  Never a read-modify-write: with dpx = 2 the bytes between a plane's samples are the other plane's.
 // Loads: v2 (every row of every float plane starts on an 8-byte boundary) fetches a thread's two adjacent pixels of a row as ONE 8-byte load per plane.
-struct YCC { float y, cb, cr; };
-static __device__ __forceinline__ YCC to_ycc(const W2xcRgbToYuv &m, float R, float G, float B)
-{
-    const float a = m.Kr * R;
-    const float b = m.Kg * G;
-    const float c = m.Kb * B;
-    YCC o;
-    o.y = (a + b) + c;
-    o.cb = (B - o.y) * m.iBU;
-    o.cr = (R - o.y) * m.iRV;
-    return o;
-}
 static __device__ __forceinline__ unsigned char luma_u8(float y, int limited)
 {
     return limited ? (unsigned char)clampi(__float2int_rn(y * 219.0f + 16.0f), 0, 255) : to_u8(y);
@@ -312,12 +264,10 @@ __global__ void __launch_bounds__(256) k_rgb_to_yuv8(const float *__restrict__ r
 hipError_t w2xc_launch_rgb_to_yuv8(const float *rgb, long long is, long long ps, int w, int h, int chroma, int range, int matrix, W2xcU8Planes y, W2xcU8Planes u,
                                    unsigned char *v, int n, hipStream_t st)
 {
-    double Kr, Kb;
+    W2xcRgbToYuv m;
     int cw, ch;
-    if (!matrix_weights(matrix, &Kr, &Kb) || !frame_geometry(w, h, chroma, &cw, &ch) || n < 1 || !y.p || !u.p || !v || !rgb || y.px != 1 || (u.px != 1 && u.px != 2))
+    if (!matrix_from_rgb(matrix, &m) || !frame_geometry(w, h, chroma, &cw, &ch) || n < 1 || !y.p || !u.p || !v || !rgb || y.px != 1 || (u.px != 1 && u.px != 2))
         return hipErrorInvalidValue;
-    const double Kg = 1.0 - Kr - Kb, cRV = 2.0 * (1.0 - Kr), cBU = 2.0 * (1.0 - Kb);
-    const W2xcRgbToYuv m = {(float)Kr, (float)Kg, (float)Kb, (float)(1.0 / cBU), (float)(1.0 / cRV)};
     const int tiles_x = (cw + YR_TCX - 1) / YR_TCX, tiles_y = (ch + YR_TCY - 1) / YR_TCY;
     const long long tiles = (long long)tiles_x * tiles_y, turns = tiles * n;
     const unsigned grid = (unsigned)(turns > W2XC_YUVRGB_GRID_MAX ? W2XC_YUVRGB_GRID_MAX : turns);
