@@ -360,8 +360,49 @@ static void test_yuv_aux()
                 }
 }
 
+// The launch grid of the YUV tile kernels: chroma2x_tile_grid / yuv_rgb_tile_grid against the expressions the six launchers each wrote out before the rule had one
+// home -- tile counts, tiles, turns (n * npl per tile for the 8-bit chroma kernel, n for the 16-bit one and the four of the RGB route) and the capped grid.
+static void test_yuv_tile_grid()
+{
+    const int TX = 32, TY = 16;   // W2XC_CHROMA_TQX / _TQY and W2XC_YUVRGB_TCX / _TCY
+    const long long CAP = 2048;   // W2XC_CHROMA_GRID_MAX and W2XC_YUVRGB_GRID_MAX
+    const int sizes[] = {1, 31, 32, 33, 63, 64, 65};
+    const int ns[] = {1, 3};
+    for (int w : sizes)
+        for (int h : sizes)
+            for (int n : ns)
+                for (int npl = 1; npl <= 2; npl++) {
+                    {   // w2xc_launch_chroma2x_u8 (per_tile = n * npl) and w2xc_launch_chroma2x_u16 (per_tile = n), w x h the OUTPUT
+                        const int tiles_x = (w / 2 + TX) / TX, tiles_y = (h / 2 + TY) / TY;
+                        const long long tiles = (long long)tiles_x * tiles_y;
+                        for (long long per : {(long long)n * npl, (long long)n}) {
+                            const long long turns = tiles * per;
+                            const unsigned grid = (unsigned)(turns > CAP ? CAP : turns);
+                            const YuvTileGrid g = chroma2x_tile_grid(w, h, per, TX, TY, CAP);
+                            CHECK(g.tiles_x == tiles_x && g.tiles == tiles && g.turns == turns && g.grid == grid, "chroma 2x %dx%d per_tile=%lld: %d %lld %lld %u", w, h, per,
+                                  g.tiles_x, g.tiles, g.turns, g.grid);
+                        }
+                    }
+                    {   // the four launchers of the RGB route, w x h the CHROMA plane
+                        const int tiles_x = (w + TX - 1) / TX, tiles_y = (h + TY - 1) / TY;
+                        const long long tiles = (long long)tiles_x * tiles_y, turns = tiles * n;
+                        const unsigned grid = (unsigned)(turns > CAP ? CAP : turns);
+                        const YuvTileGrid g = yuv_rgb_tile_grid(w, h, n, TX, TY, CAP);
+                        CHECK(g.tiles_x == tiles_x && g.tiles == tiles && g.turns == turns && g.grid == grid, "rgb route %dx%d n=%d: %d %lld %lld %u", w, h, n, g.tiles_x,
+                              g.tiles, g.turns, g.grid);
+                    }
+                }
+    // more turns than workgroups: the cap holds, the turns do not shrink
+    const YuvTileGrid c = chroma2x_tile_grid(1920, 1080, 16, TX, TY, CAP), r = yuv_rgb_tile_grid(960, 540, 8, TX, TY, CAP);
+    CHECK(c.tiles_x == 31 && c.tiles == 31 * 34 && c.turns == 31 * 34 * 16 && c.grid == 2048, "chroma 2x above the cap: %d %lld %lld %u", c.tiles_x, c.tiles, c.turns, c.grid);
+    CHECK(r.tiles_x == 30 && r.tiles == 30 * 34 && r.turns == 30 * 34 * 8 && r.grid == 2048, "rgb route above the cap: %d %lld %lld %u", r.tiles_x, r.tiles, r.turns, r.grid);
+    const YuvTileGrid edge = yuv_tile_grid(1, 2049, 1, CAP), at = yuv_tile_grid(1, 2048, 1, CAP);
+    CHECK(edge.turns == 2049 && edge.grid == 2048 && at.turns == 2048 && at.grid == 2048, "the cap at 2048 / 2049 turns: %u %u", at.grid, edge.grid);
+}
+
 int main()
 {
+    test_yuv_tile_grid();
     test_unit_rows();
     test_src_rows();
     test_chunks();

@@ -466,13 +466,18 @@ def test_launch_rules_match_the_launchers():
     for name, val in (("W2XC_CHROMA_TQX", y16.TQX), ("W2XC_CHROMA_TQY", y16.TQY), ("W2XC_CHROMA_GRID_MAX", y16.GRID_MAX), ("W2XC_YUVRGB_TCX", rr.TCX),
                       ("W2XC_YUVRGB_TCY", rr.TCY), ("W2XC_YUVRGB_GRID_MAX", rr.GRID_MAX)):
         assert "#define %s %d" % (name, val) in src
-    hip = open(os.path.join(CSRC, "w2xc_yuv16.hip")).read()
-    assert "(ow / 2 + CH_TQX) / CH_TQX" in hip and "(oh / 2 + CH_TQY) / CH_TQY" in hip and "turns = tiles * n;" in hip
-    assert "turns > W2XC_CHROMA_GRID_MAX ? W2XC_CHROMA_GRID_MAX : turns" in hip
+    # the two rules are written once, in w2xc_host_geom.hpp, for the launchers of both widths (tests/cpp/host_geom_test.cpp runs them against the expressions
+    # the launchers had); here a turn of the chroma kernel is a tile of a FRAME (n, not n * npl)
+    squeeze = lambda name: " ".join(open(os.path.join(CSRC, name)).read().split())
+    geom, hip = squeeze("w2xc_host_geom.hpp"), squeeze("w2xc_yuv16.hip")
+    assert geom.count("yuv_tile_grid((ow / 2 + tqx) / tqx, (oh / 2 + tqy) / tqy, per_tile, cap)") == 1
+    assert geom.count("yuv_tile_grid((cw + tcx - 1) / tcx, (ch + tcy - 1) / tcy, n, cap)") == 1
+    assert geom.count("turns = tiles * per_tile") == 1 and geom.count("(unsigned)(turns > cap ? cap : turns)") == 1
+    assert "chroma2x_tile_grid(ow, oh, n, CH_TQX, CH_TQY, W2XC_CHROMA_GRID_MAX)" in hip and "/ CH_TQX" not in hip
+    assert "sizeof(*p.p)" in squeeze("w2xc_yuv_tile.h"), "rows_align: the alignment of a plane's rows in BYTES"
     assert "su.px == 1 && ((salign | (sv ? reinterpret_cast<size_t>(sv) : 0)) & 7) == 0" in hip and "su.px == 2 && sv == su.p + 1 && (salign & 3) == 0" in hip
-    hip = open(os.path.join(CSRC, "w2xc_yuv16_rgb.hip")).read()
-    assert hip.count("(cw + YR_TCX - 1) / YR_TCX") == 2 and hip.count("(ch + YR_TCY - 1) / YR_TCY") == 2 and hip.count("turns = tiles * n;") == 2
-    assert hip.count("turns > W2XC_YUVRGB_GRID_MAX ? W2XC_YUVRGB_GRID_MAX : turns") == 2
+    hip = squeeze("w2xc_yuv16_rgb.hip")
+    assert hip.count("yuv_rgb_tile_grid(cw, ch, n, YR_TCX, YR_TCY, W2XC_YUVRGB_GRID_MAX)") == 2 and "/ YR_TCX" not in hip
     assert y16.chroma_launch(1, 1, 1) == (1, 1) and y16.chroma_launch(63, 31, 2) == (2, 2) and y16.chroma_launch(64, 32, 1) == (4, 4)
     assert y16.chroma_launch(960, 540, 8) == (16 * 17 * 8, 2048), "U and V of a frame are ONE turn"
     assert y16.chroma_load_path(True, 8, False) == 1 and y16.chroma_load_path(True, 4, False) == 0 and y16.chroma_load_path(False, 4, True) == 2

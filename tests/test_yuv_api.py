@@ -253,8 +253,13 @@ def test_chroma_launch_rule_matches_the_launcher():
     src = open(os.path.join(ROOT, "waifu2x-converter-cpp_amd", "csrc", "w2xc_kernels.h")).read()
     for name, val in (("W2XC_CHROMA_TQX", yr.TQX), ("W2XC_CHROMA_TQY", yr.TQY), ("W2XC_CHROMA_GRID_MAX", yr.GRID_MAX)):
         assert "#define %s %d" % (name, val) in src
-    hip = open(os.path.join(ROOT, "waifu2x-converter-cpp_amd", "csrc", "w2xc_yuv.hip")).read()
-    assert "(ow / 2 + CH_TQX) / CH_TQX" in hip and "(oh / 2 + CH_TQY) / CH_TQY" in hip and "turns > W2XC_CHROMA_GRID_MAX ? W2XC_CHROMA_GRID_MAX : turns" in hip
+    # the rule is written once, in w2xc_host_geom.hpp (chroma2x_tile_grid on yuv_tile_grid; tests/cpp/host_geom_test.cpp runs it against the expressions the
+    # launchers had), and the launcher calls it with the tile, the cap and a turn per tile and PLANE
+    squeeze = lambda name: " ".join(open(os.path.join(ROOT, "waifu2x-converter-cpp_amd", "csrc", name)).read().split())
+    geom, hip = squeeze("w2xc_host_geom.hpp"), squeeze("w2xc_yuv.hip")
+    assert geom.count("yuv_tile_grid((ow / 2 + tqx) / tqx, (oh / 2 + tqy) / tqy, per_tile, cap)") == 1
+    assert geom.count("turns = tiles * per_tile") == 1 and geom.count("(unsigned)(turns > cap ? cap : turns)") == 1
+    assert "chroma2x_tile_grid(ow, oh, (long long)n * npl, CH_TQX, CH_TQY, W2XC_CHROMA_GRID_MAX)" in hip and "/ CH_TQX" not in hip
     assert yr.chroma_launch(1, 1, 1) == (1, 1) and yr.chroma_launch(63, 31, 2) == (2, 2) and yr.chroma_launch(64, 32, 1) == (4, 4)
     assert yr.chroma_launch(1920, 1080, 16) == (31 * 34 * 16, 2048)   # quads 0 .. 960: 961 of them, 31 tiles across
 

@@ -324,9 +324,13 @@ def test_launch_rule_matches_the_launchers():
     src = open(os.path.join(ROOT, "waifu2x-converter-cpp_amd", "csrc", "w2xc_kernels.h")).read()
     for name, val in (("W2XC_YUVRGB_TCX", rr.TCX), ("W2XC_YUVRGB_TCY", rr.TCY), ("W2XC_YUVRGB_GRID_MAX", rr.GRID_MAX)):
         assert "#define %s %d" % (name, val) in src
-    hip = open(os.path.join(ROOT, "waifu2x-converter-cpp_amd", "csrc", "w2xc_yuv_rgb.hip")).read()
-    assert hip.count("(cw + YR_TCX - 1) / YR_TCX") == 2 and hip.count("(ch + YR_TCY - 1) / YR_TCY") == 2
-    assert hip.count("turns > W2XC_YUVRGB_GRID_MAX ? W2XC_YUVRGB_GRID_MAX : turns") == 2
+    # the rule is written once, in w2xc_host_geom.hpp (yuv_rgb_tile_grid on yuv_tile_grid; tests/cpp/host_geom_test.cpp runs it against the expressions the
+    # launchers had), and both launchers call it with the tile, the cap and a turn per tile and frame
+    squeeze = lambda name: " ".join(open(os.path.join(ROOT, "waifu2x-converter-cpp_amd", "csrc", name)).read().split())
+    geom, hip = squeeze("w2xc_host_geom.hpp"), squeeze("w2xc_yuv_rgb.hip")
+    assert geom.count("yuv_tile_grid((cw + tcx - 1) / tcx, (ch + tcy - 1) / tcy, n, cap)") == 1
+    assert geom.count("turns = tiles * per_tile") == 1 and geom.count("(unsigned)(turns > cap ? cap : turns)") == 1
+    assert hip.count("yuv_rgb_tile_grid(cw, ch, n, YR_TCX, YR_TCY, W2XC_YUVRGB_GRID_MAX)") == 2 and "/ YR_TCX" not in hip
     assert rr.launch(1, 1, yr.YUV_420, 1) == (1, 1) and rr.launch(64, 32, yr.YUV_420, 1) == (1, 1) and rr.launch(65, 33, yr.YUV_420, 1) == (4, 4)
     assert rr.launch(64, 32, yr.YUV_444, 3) == (12, 12) and rr.launch(64, 32, yr.YUV_422, 1) == (2, 2)
     assert rr.launch(1920, 1080, yr.YUV_420, 8) == (30 * 34 * 8, 2048)

@@ -179,4 +179,27 @@ inline YuvMirrorLayout yuv_mirror_layout(int c_px, bool u_first, int cap, int w,
     return m;
 }
 
+// ---- the launch grid of the six YUV tile kernels (w2xc_yuv_tile.h gives the tile sizes and the caps of w2xc_kernels.h) ----
+// Tiles of all frames -- or planes: per_tile turns per tile -- are the turns of one grid-stride loop over at most `cap` workgroups
+struct YuvTileGrid {
+    int tiles_x;
+    long long tiles, turns;
+    unsigned grid;
+};
+inline YuvTileGrid yuv_tile_grid(int tiles_x, int tiles_y, long long per_tile, long long cap)
+{
+    const long long tiles = (long long)tiles_x * tiles_y, turns = tiles * per_tile;
+    return {tiles_x, tiles, turns, (unsigned)(turns > cap ? cap : turns)};
+}
+// the bicubic 2x of chroma: quads 0 .. ow / 2 and 0 .. oh / 2 hold the ow x oh outputs, tqx x tqy quads a tile
+inline YuvTileGrid chroma2x_tile_grid(int ow, int oh, long long per_tile, int tqx, int tqy, long long cap)
+{
+    return yuv_tile_grid((ow / 2 + tqx) / tqx, (oh / 2 + tqy) / tqy, per_tile, cap);
+}
+// the two ends of the RGB route: cw x ch chroma samples, tcx x tcy of them a tile, a turn per tile and frame
+inline YuvTileGrid yuv_rgb_tile_grid(int cw, int ch, int n, int tcx, int tcy, long long cap)
+{
+    return yuv_tile_grid((cw + tcx - 1) / tcx, (ch + tcy - 1) / tcy, n, cap);
+}
+
 }  // namespace w2xc_eng

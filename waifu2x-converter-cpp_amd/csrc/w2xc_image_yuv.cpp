@@ -2,7 +2,8 @@
 // w2xc_yuv.hip) -- and, through RGB and head models by a colour matrix the caller names (w2xc_process_frames_yuv_u8_rgb*), process_yuv_rgb_device: the passes of the
 // RGB pipeline (rgb_passes, w2xc_image.cpp) between two kernels (w2xc_yuv_rgb.hip).  The host forms' device mirror, and the five building blocks.
 // The same calls on 16-bit words (w2xc_process_frames_yuv_u16*, "16-bit YUV frames"): the checks, the geometry, the mirror and the sub-batches take the sample
-// size, and the two routes pick their ends (w2xc_yuv16.hip, w2xc_yuv16_rgb.hip) by it; the passes between the ends are the same calls.
+// size; the ends of a route (luma_in, luma_out, chroma_out, to_rgb, from_rgb) pick their launcher (w2xc_yuv16.hip, w2xc_yuv16_rgb.hip) by it, and nothing else
+// does: the routes and the bodies of the building blocks read the same for both widths.
 #include "w2xc_image.hpp"
 
 namespace w2xc_eng {
@@ -12,7 +13,7 @@ namespace {
 // ---- YUV frames (w2xc_process_frames_yuv_u8* / _u16*; the arithmetic: include/w2xc_hip.h) ----
 // Luma through the models as the planes of run_batch, chroma from samples to samples in one launch: no colour matrix, no float plane of chroma.
 struct YuvGeom {
-    int chroma, range;
+    int chroma = W2XC_YUV_400, range = W2XC_RANGE_FULL;   // (defaults: a building block fills in only the format fields its end of a route reads)
     int bps = 1, depth = 8;   // bytes per sample (1: w2xc_yuv_planes, 2: w2xc_yuv16_planes) and the bits of a value
     bool rgb = false;       // the frames go through RGB / head models (w2xc_process_frames_yuv_u8_rgb*): process_yuv_rgb_device
     int matrix = 0;         // ... by this colour matrix (W2XC_MATRIX_*)
@@ -143,6 +144,37 @@ unsigned short *words(unsigned char *p) { return reinterpret_cast<unsigned short
 W2xcU16Planes luma_words(const YuvSide &s) { return {words(s.y), (long long)(s.y_frame_stride / 2), (long long)(s.y_stride / 2), 1, s.pack}; }
 W2xcU16Planes chroma_words(const YuvSide &s) { return {words(s.u), (long long)(s.c_frame_stride / 2), (long long)(s.c_stride / 2), s.c_px, s.pack}; }
 
+// ---- the ends of the two routes on n frames of one side: the ONE place where the sample width (g.bps) picks a launcher.  Routes and building blocks call these ----
+// luma samples of w x h -> float planes ps floats apart, and back
+hipError_t luma_in(const YuvGeom &g, const YuvSide &s, int w, int h, float *y, long long ps, int n, hipStream_t st)
+{
+    return g.bps == 2 ? w2xc_launch_y16_to_plane(luma_words(s), w, h, g.range, g.depth, y, ps, n, st) : w2xc_launch_y8_to_plane(luma_planes(s), w, h, g.range, y, ps, n, st);
+}
+hipError_t luma_out(const YuvGeom &g, const float *y, long long ps, int w, int h, const YuvSide &s, int n, hipStream_t st)
+{
+    return g.bps == 2 ? w2xc_launch_plane_to_y16(y, ps, w, h, g.range, g.depth, luma_words(s), n, st) : w2xc_launch_plane_to_y8(y, ps, w, h, g.range, luma_planes(s), n, st);
+}
+// chroma samples to chroma samples: g.cw x g.ch -> the leading g.ocw x g.och of the bicubic 2x, or (no 2x step) as they are.  A null v: one plane per frame
+hipError_t chroma_out(const YuvGeom &g, bool up2x, const YuvSide &in, const YuvSide &out, int n, hipStream_t st)
+{
+    if (g.bps == 2)
+        return up2x ? w2xc_launch_chroma2x_u16(chroma_words(in), words(in.v), g.cw, g.ch, chroma_words(out), words(out.v), g.ocw, g.och, g.depth, n, st)
+                    : w2xc_launch_chroma_copy_u16(chroma_words(in), words(in.v), g.cw, g.ch, chroma_words(out), words(out.v), g.depth, n, st);
+    return up2x ? w2xc_launch_chroma2x_u8(chroma_planes(in), in.v, g.cw, g.ch, chroma_planes(out), out.v, g.ocw, g.och, n, st)
+                : w2xc_launch_chroma_copy_u8(chroma_planes(in), in.v, g.cw, g.ch, chroma_planes(out), out.v, n, st);
+}
+// frames of w x h <-> their R, G, B planes (frame i's at rgb + i * is + {0, 1, 2} * ps floats) by g.matrix
+hipError_t to_rgb(const YuvGeom &g, const YuvSide &s, int w, int h, float *rgb, long long is, long long ps, int n, hipStream_t st)
+{
+    return g.bps == 2 ? w2xc_launch_yuv16_to_rgb(luma_words(s), chroma_words(s), words(s.v), w, h, g.chroma, g.range, g.matrix, g.depth, rgb, is, ps, n, st)
+                      : w2xc_launch_yuv8_to_rgb(luma_planes(s), chroma_planes(s), s.v, w, h, g.chroma, g.range, g.matrix, rgb, is, ps, n, st);
+}
+hipError_t from_rgb(const YuvGeom &g, const float *rgb, long long is, long long ps, int w, int h, const YuvSide &s, int n, hipStream_t st)
+{
+    return g.bps == 2 ? w2xc_launch_rgb_to_yuv16(rgb, is, ps, w, h, g.chroma, g.range, g.matrix, g.depth, luma_words(s), chroma_words(s), words(s.v), n, st)
+                      : w2xc_launch_rgb_to_yuv8(rgb, is, ps, w, h, g.chroma, g.range, g.matrix, luma_planes(s), chroma_planes(s), s.v, n, st);
+}
+
 // A sub-batch of S frames (S <= cap, the call's sub-batch size: the planes are sized by cap): luma samples -> planes, the noise pass, the scale pass with the
 // nearest-2x folded into layer 1 -- run_batch, so bands, precisions, named kernels and fusion settings are those of w2xc_convert_batch_device --, planes ->
 // luma samples; chroma in ONE launch, samples to samples.  The ends are those of the sample width; everything between them is the same.
@@ -154,9 +186,7 @@ int process_yuv_device(const ImageCall &c, const YuvGeom &g, int S, int cap, con
     long long ps = (long long)plane_floats(c.w, c.h);
     float *y = base, *yn = y + (size_t)cap * ps;
     base += 2 * (size_t)cap * ps;
-    const bool wide = g.bps == 2;
-    if (wide) HIP_TRY(w2xc_launch_y16_to_plane(luma_words(in), c.w, c.h, g.range, g.depth, y, ps, S, c.st));
-    else HIP_TRY(w2xc_launch_y8_to_plane(luma_planes(in), c.w, c.h, g.range, y, ps, S, c.st));
+    HIP_TRY(luma_in(g, in, c.w, c.h, y, ps, S, c.st));
     if (c.mn) {
         if (int rc = run_batch(c.mn, c.ctx.cn, S, 0, {y, (size_t)c.w, ps}, c.w, c.h, {yn, (size_t)c.w, ps}, c.st, c.o)) return rc;
         y = yn;
@@ -166,14 +196,8 @@ int process_yuv_device(const ImageCall &c, const YuvGeom &g, int S, int cap, con
         if (int rc = run_batch(c.msc, c.ctx.cs, S, 1, {y, (size_t)c.w, ps}, c.w, c.h, {base, (size_t)g.W, ps2}, c.st, c.o)) return rc;
         y = base; ps = ps2;
     }
-    if (wide) HIP_TRY(w2xc_launch_plane_to_y16(y, ps, g.W, g.H, g.range, g.depth, luma_words(out), S, c.st));
-    else HIP_TRY(w2xc_launch_plane_to_y8(y, ps, g.W, g.H, g.range, luma_planes(out), S, c.st));
-    if (!g.cw) return W2XC_OK;
-    if (wide) {
-        if (c.iterations) HIP_TRY(w2xc_launch_chroma2x_u16(chroma_words(in), words(in.v), g.cw, g.ch, chroma_words(out), words(out.v), g.ocw, g.och, g.depth, S, c.st));
-        else HIP_TRY(w2xc_launch_chroma_copy_u16(chroma_words(in), words(in.v), g.cw, g.ch, chroma_words(out), words(out.v), g.depth, S, c.st));
-    } else if (c.iterations) HIP_TRY(w2xc_launch_chroma2x_u8(chroma_planes(in), in.v, g.cw, g.ch, chroma_planes(out), out.v, g.ocw, g.och, S, c.st));
-    else HIP_TRY(w2xc_launch_chroma_copy_u8(chroma_planes(in), in.v, g.cw, g.ch, chroma_planes(out), out.v, S, c.st));
+    HIP_TRY(luma_out(g, y, ps, g.W, g.H, out, S, c.st));
+    if (g.cw) HIP_TRY(chroma_out(g, c.iterations != 0, in, out, S, c.st));
     return W2XC_OK;
 }
 
@@ -189,12 +213,9 @@ int process_yuv_rgb_device(const ImageCall &c, const YuvGeom &g, int S, int cap,
     float *base = aux_planes(own, 0);
     RgbLevel L = {base, c.w, c.h, (long long)plane_floats(c.w, c.h)};
     base += 3 * (size_t)cap * L.ps;
-    const bool wide = g.bps == 2;
-    if (wide) HIP_TRY(w2xc_launch_yuv16_to_rgb(luma_words(in), chroma_words(in), words(in.v), c.w, c.h, g.chroma, g.range, g.matrix, g.depth, L.p, 3 * L.ps, L.ps, S, c.st));
-    else HIP_TRY(w2xc_launch_yuv8_to_rgb(luma_planes(in), chroma_planes(in), in.v, c.w, c.h, g.chroma, g.range, g.matrix, L.p, 3 * L.ps, L.ps, S, c.st));
+    HIP_TRY(to_rgb(g, in, c.w, c.h, L.p, 3 * L.ps, L.ps, S, c.st));
     if (int rc = rgb_passes(c, R, S, cap, U8In{nullptr, 0, 0}, U8Out{nullptr, 0, 0}, 0, &base, nullptr, &L)) return rc;
-    if (wide) HIP_TRY(w2xc_launch_rgb_to_yuv16(L.p, 3 * L.ps, L.ps, L.w, L.h, g.chroma, g.range, g.matrix, g.depth, luma_words(out), chroma_words(out), words(out.v), S, c.st));
-    else HIP_TRY(w2xc_launch_rgb_to_yuv8(L.p, 3 * L.ps, L.ps, L.w, L.h, g.chroma, g.range, g.matrix, luma_planes(out), chroma_planes(out), out.v, S, c.st));
+    HIP_TRY(from_rgb(g, L.p, 3 * L.ps, L.ps, L.w, L.h, out, S, c.st));
     return W2XC_OK;
 }
 
@@ -325,7 +346,7 @@ int check_yuv_rgb_block_args(const YuvSide *f, int bps, int depth, bool f_is_out
 
 // what the three building blocks of the Y route refuse: n planes of samples (bps bytes each) of row_bytes-byte rows x `rows` at p and n planes of `other` bytes (rows /
 // planes as given) on the other side
-int check_yuv_block_args(const void *p, size_t frame, size_t row, size_t row_bytes, int rows, int n, int w, int h, const void *q, size_t q_plane, size_t q_ext, int bps = 1)
+int check_yuv_block_args(const void *p, size_t frame, size_t row, size_t row_bytes, int rows, int n, int w, int h, const void *q, size_t q_plane, size_t q_ext, int bps)
 {
     if (!p || !q) return fail(W2XC_ERR_ARG, "null argument");
     if (n < 1 || n > (1 << 20) || w <= 0 || h <= 0 || w > (1 << 22) || h > (1 << 22)) return fail(W2XC_ERR_ARG, "bad plane count / plane size");
@@ -336,11 +357,63 @@ int check_yuv_block_args(const void *p, size_t frame, size_t row, size_t row_byt
     return W2XC_OK;
 }
 // ... and of their other arguments: the float planes' stride, the range, and for words the depth and the packing
-int check_luma_block_format(size_t plane_stride_bytes, int range, int bps = 1, int depth = 8, int pack = 0)
+int check_luma_block_format(size_t plane_stride_bytes, int range, int bps, int depth, int pack)
 {
     if ((plane_stride_bytes & 3) || (range != W2XC_RANGE_FULL && range != W2XC_RANGE_LIMITED)) return fail(W2XC_ERR_ARG, "plane stride no multiple of 4 / unknown range");
     if (pack != W2XC_PACK_LOW && pack != W2XC_PACK_HIGH) return fail(W2XC_ERR_ARG, "pack must be W2XC_PACK_LOW or W2XC_PACK_HIGH, got %d", pack);
     return check_depth(bps, depth);
+}
+
+// ---- the bodies of the building blocks: a block on bytes and its twin on words are ONE of these, told apart by bps, depth and the packs (bytes: 1, 8,
+// W2XC_PACK_LOW).  out: float planes -> samples ----
+template <class Planes>
+int yuv_rgb_block(bool out, const Planes *frames, int bps, int depth, int n, int w, int h, int chroma, int range, int matrix, float *d_rgb, size_t image_stride_bytes,
+                  size_t plane_stride_bytes, void *hip_stream)
+{
+    YuvSide store;
+    const YuvSide *s = side_of(frames, &store);
+    if (int rc = check_yuv_rgb_block_args(s, bps, depth, out, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes)) return rc;
+    YuvGeom g;   // (the format alone: what the ends take)
+    g.bps = bps; g.depth = depth; g.range = range; g.chroma = chroma; g.matrix = matrix;
+    const long long is = (long long)(image_stride_bytes / 4), ps = (long long)(plane_stride_bytes / 4);
+    HIP_TRY(out ? from_rgb(g, d_rgb, is, ps, w, h, *s, n, (hipStream_t)hip_stream) : to_rgb(g, *s, w, h, d_rgb, is, ps, n, (hipStream_t)hip_stream));
+    return W2XC_OK;
+}
+
+int luma_block(bool out, const void *samples, int bps, int depth, int pack, int n, size_t frame_stride_bytes, size_t stride_bytes, int w, int h, int range,
+               const float *planes, size_t plane_stride_bytes, void *hip_stream)
+{
+    const size_t W = w > 0 ? w : 1, H = h > 0 ? h : 1;
+    if (int rc = check_yuv_block_args(samples, frame_stride_bytes, stride_bytes, bps * W, h, n, w, h, planes, plane_stride_bytes, 4 * W * H, bps)) return rc;
+    if (int rc = check_luma_block_format(plane_stride_bytes, range, bps, depth, pack)) return rc;
+    YuvSide s;
+    s.y = static_cast<unsigned char *>(const_cast<void *>(samples)); s.y_frame_stride = frame_stride_bytes; s.y_stride = stride_bytes; s.pack = pack;
+    YuvGeom g;
+    g.bps = bps; g.depth = depth; g.range = range;
+    const long long ps = (long long)(plane_stride_bytes / 4);
+    HIP_TRY(out ? luma_out(g, planes, ps, w, h, s, n, (hipStream_t)hip_stream) : luma_in(g, s, w, h, const_cast<float *>(planes), ps, n, (hipStream_t)hip_stream));
+    return W2XC_OK;
+}
+
+int chroma2x_block(const void *d_src, int bps, int depth, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int src_pack, int cw, int ch,
+                   void *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int dst_pack, int ow, int oh, void *hip_stream)
+{
+    if ((src_px != 1 && src_px != 2) || (dst_px != 1 && dst_px != 2)) return fail(W2XC_ERR_ARG, "src_px / dst_px must be 1 or 2");
+    if (ow < 1 || oh < 1 || ow > 2 * (long long)cw || oh > 2 * (long long)ch) return fail(W2XC_ERR_ARG, "the output size lies outside the 2x enlargement");
+    const size_t drow = chroma_row_bytes(ow, dst_px, bps), dext = (size_t)(oh - 1) * dst_stride_bytes + drow;
+    if (dst_stride_bytes < drow) return fail(W2XC_ERR_ARG, "row / plane strides below a row / a plane");
+    if (int rc = check_yuv_block_args(d_src, src_frame_stride_bytes, src_stride_bytes, chroma_row_bytes(cw > 0 ? cw : 1, src_px, bps), ch, n, cw, ch, d_dst, dst_frame_stride_bytes, dext, bps)) return rc;
+    if (bps == 2 && (((uintptr_t)d_dst | dst_stride_bytes | dst_frame_stride_bytes) & 1)) return fail(W2XC_ERR_ARG, "16-bit samples need an even pointer and even strides");
+    if ((src_pack != W2XC_PACK_LOW && src_pack != W2XC_PACK_HIGH) || (dst_pack != W2XC_PACK_LOW && dst_pack != W2XC_PACK_HIGH))
+        return fail(W2XC_ERR_ARG, "src_pack / dst_pack must be W2XC_PACK_LOW or W2XC_PACK_HIGH");
+    if (int rc = check_depth(bps, depth)) return rc;
+    YuvSide in, to;   // one plane per frame: no v
+    in.u = static_cast<unsigned char *>(const_cast<void *>(d_src)); in.c_frame_stride = src_frame_stride_bytes; in.c_stride = src_stride_bytes; in.c_px = src_px; in.pack = src_pack;
+    to.u = static_cast<unsigned char *>(d_dst); to.c_frame_stride = dst_frame_stride_bytes; to.c_stride = dst_stride_bytes; to.c_px = dst_px; to.pack = dst_pack;
+    YuvGeom g;
+    g.bps = bps; g.depth = depth; g.cw = cw; g.ch = ch; g.ocw = ow; g.och = oh;
+    HIP_TRY(chroma_out(g, true, in, to, n, (hipStream_t)hip_stream));
+    return W2XC_OK;
 }
 
 }  // namespace
@@ -402,122 +475,69 @@ try {
     return frames_yuv(true, ImageCall(noise_model, scale_model, w, h, iterations, 0.0, nullptr, opts), {true, n, chroma, range, matrix, 2, depth}, in, out);
 } W2XC_CATCH_ALL
 
-// ---- the two ends of the RGB route ----
+// ---- the two ends of the RGB route (yuv_rgb_block) ----
 int w2xc_yuv8_to_rgb_device(const w2xc_yuv_planes *d_src, int n, int w, int h, int chroma, int range, int matrix, float *d_rgb, size_t image_stride_bytes,
                             size_t plane_stride_bytes, void *hip_stream)
 try {
-    YuvSide store;
-    const YuvSide *s = side_of(d_src, &store);
-    if (int rc = check_yuv_rgb_block_args(s, 1, 8, false, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes)) return rc;
-    HIP_TRY(w2xc_launch_yuv8_to_rgb(luma_planes(*s), chroma_planes(*s), s->v, w, h, chroma, range, matrix, d_rgb, (long long)(image_stride_bytes / 4),
-                                    (long long)(plane_stride_bytes / 4), n, (hipStream_t)hip_stream));
-    return W2XC_OK;
+    return yuv_rgb_block(false, d_src, 1, 8, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes, hip_stream);
 } W2XC_CATCH_ALL
 
 int w2xc_rgb_to_yuv8_device(const float *d_rgb, size_t image_stride_bytes, size_t plane_stride_bytes, int n, int w, int h, int chroma, int range, int matrix,
                             const w2xc_yuv_planes *d_dst, void *hip_stream)
 try {
-    YuvSide store;
-    const YuvSide *s = side_of(d_dst, &store);
-    if (int rc = check_yuv_rgb_block_args(s, 1, 8, true, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes)) return rc;
-    HIP_TRY(w2xc_launch_rgb_to_yuv8(d_rgb, (long long)(image_stride_bytes / 4), (long long)(plane_stride_bytes / 4), w, h, chroma, range, matrix, luma_planes(*s),
-                                    chroma_planes(*s), s->v, n, (hipStream_t)hip_stream));
-    return W2XC_OK;
+    return yuv_rgb_block(true, d_dst, 1, 8, n, w, h, chroma, range, matrix, const_cast<float *>(d_rgb), image_stride_bytes, plane_stride_bytes, hip_stream);
 } W2XC_CATCH_ALL
 
 int w2xc_yuv16_to_rgb_device(const w2xc_yuv16_planes *d_src, int n, int w, int h, int chroma, int range, int depth, int matrix, float *d_rgb, size_t image_stride_bytes,
                              size_t plane_stride_bytes, void *hip_stream)
 try {
-    YuvSide store;
-    const YuvSide *s = side_of(d_src, &store);
-    if (int rc = check_yuv_rgb_block_args(s, 2, depth, false, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes)) return rc;
-    HIP_TRY(w2xc_launch_yuv16_to_rgb(luma_words(*s), chroma_words(*s), words(s->v), w, h, chroma, range, matrix, depth, d_rgb, (long long)(image_stride_bytes / 4),
-                                     (long long)(plane_stride_bytes / 4), n, (hipStream_t)hip_stream));
-    return W2XC_OK;
+    return yuv_rgb_block(false, d_src, 2, depth, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes, hip_stream);
 } W2XC_CATCH_ALL
 
 int w2xc_rgb_to_yuv16_device(const float *d_rgb, size_t image_stride_bytes, size_t plane_stride_bytes, int n, int w, int h, int chroma, int range, int depth, int matrix,
                              const w2xc_yuv16_planes *d_dst, void *hip_stream)
 try {
-    YuvSide store;
-    const YuvSide *s = side_of(d_dst, &store);
-    if (int rc = check_yuv_rgb_block_args(s, 2, depth, true, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes)) return rc;
-    HIP_TRY(w2xc_launch_rgb_to_yuv16(d_rgb, (long long)(image_stride_bytes / 4), (long long)(plane_stride_bytes / 4), w, h, chroma, range, matrix, depth, luma_words(*s),
-                                     chroma_words(*s), words(s->v), n, (hipStream_t)hip_stream));
-    return W2XC_OK;
+    return yuv_rgb_block(true, d_dst, 2, depth, n, w, h, chroma, range, matrix, const_cast<float *>(d_rgb), image_stride_bytes, plane_stride_bytes, hip_stream);
 } W2XC_CATCH_ALL
 
-// ---- the building blocks of the Y route ----
+// ---- the building blocks of the Y route (luma_block, chroma2x_block) ----
 int w2xc_y8_to_plane_device(const unsigned char *d_src, int n, size_t frame_stride_bytes, size_t stride_bytes, int w, int h, int range, float *d_dst,
                             size_t plane_stride_bytes, void *hip_stream)
 {
-    if (int rc = check_yuv_block_args(d_src, frame_stride_bytes, stride_bytes, (size_t)(w > 0 ? w : 1), h, n, w, h, d_dst, plane_stride_bytes, (size_t)4 * (w > 0 ? w : 1) * (h > 0 ? h : 1))) return rc;
-    if (int rc = check_luma_block_format(plane_stride_bytes, range)) return rc;
-    HIP_TRY(w2xc_launch_y8_to_plane({const_cast<unsigned char *>(d_src), (long long)frame_stride_bytes, (long long)stride_bytes, 1}, w, h, range, d_dst,
-                                    (long long)(plane_stride_bytes / 4), n, (hipStream_t)hip_stream));
-    return W2XC_OK;
+    return luma_block(false, d_src, 1, 8, W2XC_PACK_LOW, n, frame_stride_bytes, stride_bytes, w, h, range, d_dst, plane_stride_bytes, hip_stream);
 }
 
 int w2xc_plane_to_y8_device(const float *d_src, int n, size_t plane_stride_bytes, int w, int h, int range, unsigned char *d_dst, size_t frame_stride_bytes,
                             size_t stride_bytes, void *hip_stream)
 {
-    if (int rc = check_yuv_block_args(d_dst, frame_stride_bytes, stride_bytes, (size_t)(w > 0 ? w : 1), h, n, w, h, d_src, plane_stride_bytes, (size_t)4 * (w > 0 ? w : 1) * (h > 0 ? h : 1))) return rc;
-    if (int rc = check_luma_block_format(plane_stride_bytes, range)) return rc;
-    HIP_TRY(w2xc_launch_plane_to_y8(d_src, (long long)(plane_stride_bytes / 4), w, h, range, {d_dst, (long long)frame_stride_bytes, (long long)stride_bytes, 1}, n,
-                                    (hipStream_t)hip_stream));
-    return W2XC_OK;
+    return luma_block(true, d_dst, 1, 8, W2XC_PACK_LOW, n, frame_stride_bytes, stride_bytes, w, h, range, d_src, plane_stride_bytes, hip_stream);
 }
 
 int w2xc_chroma2x_u8_device(const unsigned char *d_src, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int cw, int ch,
                             unsigned char *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int ow, int oh, void *hip_stream)
 {
-    if ((src_px != 1 && src_px != 2) || (dst_px != 1 && dst_px != 2)) return fail(W2XC_ERR_ARG, "src_px / dst_px must be 1 or 2");
-    if (ow < 1 || oh < 1 || ow > 2 * (long long)cw || oh > 2 * (long long)ch) return fail(W2XC_ERR_ARG, "the output size lies outside the 2x enlargement");
-    const size_t drow = (size_t)dst_px * (ow - 1) + 1, dext = (size_t)(oh - 1) * dst_stride_bytes + drow;
-    if (dst_stride_bytes < drow) return fail(W2XC_ERR_ARG, "row / plane strides below a row / a plane");
-    if (int rc = check_yuv_block_args(d_src, src_frame_stride_bytes, src_stride_bytes, (size_t)src_px * ((cw > 0 ? cw : 1) - 1) + 1, ch, n, cw, ch, d_dst, dst_frame_stride_bytes, dext)) return rc;
-    HIP_TRY(w2xc_launch_chroma2x_u8({const_cast<unsigned char *>(d_src), (long long)src_frame_stride_bytes, (long long)src_stride_bytes, src_px}, nullptr, cw, ch,
-                                    {d_dst, (long long)dst_frame_stride_bytes, (long long)dst_stride_bytes, dst_px}, nullptr, ow, oh, n, (hipStream_t)hip_stream));
-    return W2XC_OK;
+    return chroma2x_block(d_src, 1, 8, n, src_frame_stride_bytes, src_stride_bytes, src_px, W2XC_PACK_LOW, cw, ch, d_dst, dst_frame_stride_bytes, dst_stride_bytes, dst_px,
+                          W2XC_PACK_LOW, ow, oh, hip_stream);
 }
 
 int w2xc_y16_to_plane_device(const unsigned short *d_src, int n, size_t frame_stride_bytes, size_t stride_bytes, int w, int h, int range, int depth, int pack,
                              float *d_dst, size_t plane_stride_bytes, void *hip_stream)
 {
-    if (int rc = check_yuv_block_args(d_src, frame_stride_bytes, stride_bytes, (size_t)2 * (w > 0 ? w : 1), h, n, w, h, d_dst, plane_stride_bytes, (size_t)4 * (w > 0 ? w : 1) * (h > 0 ? h : 1), 2)) return rc;
-    if (int rc = check_luma_block_format(plane_stride_bytes, range, 2, depth, pack)) return rc;
-    HIP_TRY(w2xc_launch_y16_to_plane({const_cast<unsigned short *>(d_src), (long long)(frame_stride_bytes / 2), (long long)(stride_bytes / 2), 1, pack}, w, h, range,
-                                     depth, d_dst, (long long)(plane_stride_bytes / 4), n, (hipStream_t)hip_stream));
-    return W2XC_OK;
+    return luma_block(false, d_src, 2, depth, pack, n, frame_stride_bytes, stride_bytes, w, h, range, d_dst, plane_stride_bytes, hip_stream);
 }
 
 int w2xc_plane_to_y16_device(const float *d_src, int n, size_t plane_stride_bytes, int w, int h, int range, int depth, int pack, unsigned short *d_dst,
                              size_t frame_stride_bytes, size_t stride_bytes, void *hip_stream)
 {
-    if (int rc = check_yuv_block_args(d_dst, frame_stride_bytes, stride_bytes, (size_t)2 * (w > 0 ? w : 1), h, n, w, h, d_src, plane_stride_bytes, (size_t)4 * (w > 0 ? w : 1) * (h > 0 ? h : 1), 2)) return rc;
-    if (int rc = check_luma_block_format(plane_stride_bytes, range, 2, depth, pack)) return rc;
-    HIP_TRY(w2xc_launch_plane_to_y16(d_src, (long long)(plane_stride_bytes / 4), w, h, range, depth,
-                                     {d_dst, (long long)(frame_stride_bytes / 2), (long long)(stride_bytes / 2), 1, pack}, n, (hipStream_t)hip_stream));
-    return W2XC_OK;
+    return luma_block(true, d_dst, 2, depth, pack, n, frame_stride_bytes, stride_bytes, w, h, range, d_src, plane_stride_bytes, hip_stream);
 }
 
 int w2xc_chroma2x_u16_device(const unsigned short *d_src, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int src_pack, int cw, int ch,
                              int depth, unsigned short *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int dst_pack, int ow, int oh,
                              void *hip_stream)
 {
-    if ((src_px != 1 && src_px != 2) || (dst_px != 1 && dst_px != 2)) return fail(W2XC_ERR_ARG, "src_px / dst_px must be 1 or 2");
-    if (ow < 1 || oh < 1 || ow > 2 * (long long)cw || oh > 2 * (long long)ch) return fail(W2XC_ERR_ARG, "the output size lies outside the 2x enlargement");
-    const size_t drow = chroma_row_bytes(ow, dst_px, 2), dext = (size_t)(oh - 1) * dst_stride_bytes + drow;
-    if (dst_stride_bytes < drow) return fail(W2XC_ERR_ARG, "row / plane strides below a row / a plane");
-    if (int rc = check_yuv_block_args(d_src, src_frame_stride_bytes, src_stride_bytes, chroma_row_bytes(cw > 0 ? cw : 1, src_px, 2), ch, n, cw, ch, d_dst, dst_frame_stride_bytes, dext, 2)) return rc;
-    if (((uintptr_t)d_dst | dst_stride_bytes | dst_frame_stride_bytes) & 1) return fail(W2XC_ERR_ARG, "16-bit samples need an even pointer and even strides");
-    if ((src_pack != W2XC_PACK_LOW && src_pack != W2XC_PACK_HIGH) || (dst_pack != W2XC_PACK_LOW && dst_pack != W2XC_PACK_HIGH))
-        return fail(W2XC_ERR_ARG, "src_pack / dst_pack must be W2XC_PACK_LOW or W2XC_PACK_HIGH");
-    if (int rc = check_depth(2, depth)) return rc;
-    HIP_TRY(w2xc_launch_chroma2x_u16({const_cast<unsigned short *>(d_src), (long long)(src_frame_stride_bytes / 2), (long long)(src_stride_bytes / 2), src_px, src_pack},
-                                     nullptr, cw, ch, {d_dst, (long long)(dst_frame_stride_bytes / 2), (long long)(dst_stride_bytes / 2), dst_px, dst_pack}, nullptr, ow,
-                                     oh, depth, n, (hipStream_t)hip_stream));
-    return W2XC_OK;
+    return chroma2x_block(d_src, 2, depth, n, src_frame_stride_bytes, src_stride_bytes, src_px, src_pack, cw, ch, d_dst, dst_frame_stride_bytes, dst_stride_bytes, dst_px,
+                          dst_pack, ow, oh, hip_stream);
 }
 
 }  // extern "C"

@@ -201,7 +201,8 @@ hipError_t w2xc_launch_plane_to_y8(const float *src, long long ps, int w, int h,
 hipError_t w2xc_launch_chroma2x_u8(W2xcU8Planes su, const unsigned char *sv, int cw, int ch, W2xcU8Planes du, unsigned char *dv, int ow, int oh, int n, hipStream_t st);
 // ... and chroma bytes as they are (no 2x step): cw x ch samples per plane
 hipError_t w2xc_launch_chroma_copy_u8(W2xcU8Planes su, const unsigned char *sv, int cw, int ch, W2xcU8Planes du, unsigned char *dv, int n, hipStream_t st);
-// the grid rule of w2xc_launch_chroma2x_u8 (host arithmetic): tiles of W2XC_CHROMA_TQX x W2XC_CHROMA_TQY output quads, at most W2XC_CHROMA_GRID_MAX workgroups
+// the grid rule of w2xc_launch_chroma2x_u8 / _u16 (chroma2x_tile_grid, w2xc_host_geom.hpp): tiles of W2XC_CHROMA_TQX x
+// W2XC_CHROMA_TQY output quads, at most W2XC_CHROMA_GRID_MAX workgroups
 #define W2XC_CHROMA_TQX 32
 #define W2XC_CHROMA_TQY 16
 #define W2XC_CHROMA_GRID_MAX 2048
@@ -217,7 +218,8 @@ hipError_t w2xc_launch_yuv8_to_rgb(W2xcU8Planes y, W2xcU8Planes u, const unsigne
 // ... and back: 3 n float planes of w x h -> the bytes of n frames.  One launch; only the frames' own samples are written.
 hipError_t w2xc_launch_rgb_to_yuv8(const float *rgb, long long is, long long ps, int w, int h, int chroma, int range, int matrix, W2xcU8Planes y, W2xcU8Planes u,
                                    unsigned char *v, int n, hipStream_t st);
-// the grid rule of both launchers (host arithmetic): tiles of W2XC_YUVRGB_TCX x W2XC_YUVRGB_TCY chroma samples of one frame, at most W2XC_YUVRGB_GRID_MAX workgroups
+// the grid rule of these launchers and their 16-bit twins (yuv_rgb_tile_grid, w2xc_host_geom.hpp): tiles of W2XC_YUVRGB_TCX x
+// W2XC_YUVRGB_TCY chroma samples of one frame, at most W2XC_YUVRGB_GRID_MAX workgroups
 #define W2XC_YUVRGB_TCX 32
 #define W2XC_YUVRGB_TCY 16
 #define W2XC_YUVRGB_GRID_MAX 2048

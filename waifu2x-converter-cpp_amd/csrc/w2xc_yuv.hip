@@ -8,7 +8,8 @@
 #include "w2xc_kernels.h"
 #include "w2xc_tta_px.h"   // clampi, to_u8
 #include "w2xc_px.h"       // k_px, launch_px, row_col, cubic_coeffs
-#include "w2xc_yuv_px.h"   // chroma_row_sum
+#include "w2xc_yuv_px.h"   // chroma_row_sum, luma_u8
+#include "w2xc_yuv_tile.h" // the tile of the bicubic 2x, the launch grid, rows_align
 
 // luma byte -> y: full range (float)Y * (float)(1.0 / 255.0), limited range ((float)Y - 16) * (float)(1.0 / 219.0).  Frame i's plane at dst + i * ps floats
 struct Y8ToPlane {
@@ -29,7 +30,7 @@ hipError_t w2xc_launch_y8_to_plane(W2xcU8Planes src, int w, int h, int range, fl
     return launch_px(Y8ToPlane{src.p, src.frame, src.row, w, range != 0, dst, ps}, (long long)w * h, n, st);
 }
 
-// y -> luma byte: full range to_u8, limited range saturate(rint(y * 219 + 16)), half to even, the product and the sum unfused
+// y -> luma byte (luma_u8)
 struct PlaneToY8 {
     const float *src;
     long long ps;
@@ -40,7 +41,7 @@ struct PlaneToY8 {
     {
         const RowCol at = row_col(q, w);
         const float y = src[img * ps + q];
-        dst[img * frame + at.r * row + at.c] = limited ? (unsigned char)clampi(__float2int_rn(y * 219.0f + 16.0f), 0, 255) : to_u8(y);
+        dst[img * frame + at.r * row + at.c] = luma_u8(y, limited);
     }
 };
 hipError_t w2xc_launch_plane_to_y8(const float *src, long long ps, int w, int h, int range, W2xcU8Planes dst, int n, hipStream_t st)
@@ -82,13 +83,6 @@ hipError_t w2xc_launch_chroma_copy_u8(W2xcU8Planes su, const unsigned char *sv, 
 // dword load by one thread; everything else (the clamped rim, px = 2) one byte load per LDS word.
 // Stores: the thread's own bytes, one byte store each -- a quad's two columns start on an odd column, and with px = 2 the other plane's bytes lie between
 // them --, never a read-modify-write of a byte that is another thread's.
-#define CH_TQX W2XC_CHROMA_TQX
-#define CH_TQY W2XC_CHROMA_TQY
-#define CH_SW (CH_TQX + 3)
-#define CH_SH (CH_TQY + 3)
-#define CH_LD (CH_SW + 2)
-static_assert(CH_TQX == 32 && CH_TQY == 16 && (CH_LD & 1) == 1 && CH_SW <= CH_LD, "256 threads = 32 x 8 quads, two quad rows per thread");
-
 template <bool DW>
 __global__ void __launch_bounds__(256) k_chroma2x_u8(const unsigned char *su, const unsigned char *sv, long long sframe, long long srow, int spx, int cw, int ch,
                                                      unsigned char *du, unsigned char *dv, long long dframe, long long drow, int dpx, int ow, int oh, int npl,
@@ -168,13 +162,9 @@ hipError_t w2xc_launch_chroma2x_u8(W2xcU8Planes su, const unsigned char *sv, int
         !su.p || !du.p || (sv != nullptr) != (dv != nullptr))
         return hipErrorInvalidValue;
     const int npl = sv ? 2 : 1;
-    // quads 0 .. ow / 2 and 0 .. oh / 2 hold the ow x oh outputs
-    const int tiles_x = (ow / 2 + CH_TQX) / CH_TQX, tiles_y = (oh / 2 + CH_TQY) / CH_TQY;
-    const long long tiles = (long long)tiles_x * tiles_y, turns = tiles * n * npl;
-    const unsigned grid = (unsigned)(turns > W2XC_CHROMA_GRID_MAX ? W2XC_CHROMA_GRID_MAX : turns);
-    const size_t align = reinterpret_cast<size_t>(su.p) | (sv ? reinterpret_cast<size_t>(sv) : 0) | (size_t)su.row | (n > 1 ? (size_t)su.frame : 0);
-    const bool dw = su.px == 1 && (align & 3) == 0;
-    hipLaunchKernelGGL(dw ? k_chroma2x_u8<true> : k_chroma2x_u8<false>, dim3(grid), dim3(256), 0, st, su.p, sv, su.frame, su.row, su.px, cw, ch, du.p, dv, du.frame,
-                       du.row, du.px, ow, oh, npl, tiles_x, tiles, turns);
+    const YuvTileGrid g = w2xc_eng::chroma2x_tile_grid(ow, oh, (long long)n * npl, CH_TQX, CH_TQY, W2XC_CHROMA_GRID_MAX);   // a turn: one tile of ONE plane
+    const bool dw = su.px == 1 && ((rows_align(su, n) | (sv ? reinterpret_cast<size_t>(sv) : 0)) & 3) == 0;
+    hipLaunchKernelGGL(dw ? k_chroma2x_u8<true> : k_chroma2x_u8<false>, dim3(g.grid), dim3(256), 0, st, su.p, sv, su.frame, su.row, su.px, cw, ch, du.p, dv, du.frame,
+                       du.row, du.px, ow, oh, npl, g.tiles_x, g.tiles, g.turns);
     return hipGetLastError();
 }

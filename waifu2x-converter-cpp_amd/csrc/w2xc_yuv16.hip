@@ -8,7 +8,8 @@
 #include "w2xc_kernels.h"
 #include "w2xc_tta_px.h"   // clampi
 #include "w2xc_px.h"       // k_px, launch_px, row_col, cubic_coeffs
-#include "w2xc_yuv_px.h"   // chroma_row_sum, u16_value, to_u16, u16_scale
+#include "w2xc_yuv_px.h"   // chroma_row_sum, u16_value, to_u16, luma_u16, u16_scale
+#include "w2xc_yuv_tile.h" // the tile of the bicubic 2x, the launch grid, rows_align
 
 // luma word -> y: full range (float)Y * (float)(1.0 / M), limited range ((float)Y - 16 s) * (float)(1.0 / (219 s)).  Frame i's plane at dst + i * ps floats
 struct Y16ToPlane {
@@ -45,8 +46,7 @@ struct PlaneToY16 {
     {
         const RowCol at = row_col(q, w);
         const float y = src[img * ps + q];
-        const unsigned v = limited ? to_u16(y, scale, off, max) : to_u16(y, scale, max);
-        dst[img * frame + at.r * row + at.c] = (unsigned short)(v << lshift);
+        dst[img * frame + at.r * row + at.c] = (unsigned short)(luma_u16(y, limited, scale, off, max) << lshift);
     }
 };
 hipError_t w2xc_launch_plane_to_y16(const float *src, long long ps, int w, int h, int range, int depth, W2xcU16Planes dst, int n, hipStream_t st)
@@ -91,13 +91,6 @@ hipError_t w2xc_launch_chroma_copy_u16(W2xcU16Planes su, const unsigned short *s
 // LOAD 0: sample by sample (the clamped rim of LOAD 1 too).
 // Stores: a thread writes only its own samples, as 16-bit stores, or -- pair: du and dv interleave as dv = du + 1 and the rows start on 4-byte boundaries -- its
 // (U, V) pair as ONE 32-bit store.  Never a read-modify-write of a word that is another thread's or another plane's.
-#define CH_TQX W2XC_CHROMA_TQX
-#define CH_TQY W2XC_CHROMA_TQY
-#define CH_SW (CH_TQX + 3)
-#define CH_SH (CH_TQY + 3)
-#define CH_LD (CH_SW + 2)
-static_assert(CH_TQX == 32 && CH_TQY == 16 && (CH_LD & 1) == 1 && CH_SW <= CH_LD, "256 threads = 32 x 8 quads, two quad rows per thread");
-
 template <int LOAD>
 __global__ void __launch_bounds__(256) k_chroma2x_u16(const unsigned short *su, const unsigned short *sv, long long sframe, long long srow, int spx, int cw, int ch,
                                                       int rshift, int max, unsigned short *du, unsigned short *dv, long long dframe, long long drow, int dpx,
@@ -199,25 +192,16 @@ hipError_t w2xc_launch_chroma2x_u16(W2xcU16Planes su, const unsigned short *sv, 
         !su.p || !du.p || (sv != nullptr) != (dv != nullptr) || depth < 8 || depth > 16)
         return hipErrorInvalidValue;
     const int npl = sv ? 2 : 1;
-    // quads 0 .. ow / 2 and 0 .. oh / 2 hold the ow x oh outputs
-    const int tiles_x = (ow / 2 + CH_TQX) / CH_TQX, tiles_y = (oh / 2 + CH_TQY) / CH_TQY;
-    const long long tiles = (long long)tiles_x * tiles_y, turns = tiles * n;
-    const unsigned grid = (unsigned)(turns > W2XC_CHROMA_GRID_MAX ? W2XC_CHROMA_GRID_MAX : turns);
-    // byte alignment of the source rows (strides are in words)
-    const size_t salign = reinterpret_cast<size_t>(su.p) | (size_t)(2 * su.row) | (n > 1 ? (size_t)(2 * su.frame) : 0);
+    const YuvTileGrid g = w2xc_eng::chroma2x_tile_grid(ow, oh, n, CH_TQX, CH_TQY, W2XC_CHROMA_GRID_MAX);   // a turn: one tile of ALL planes of a frame
+    const size_t salign = rows_align(su, n), dalign = rows_align(du, n);
     int load = 0;
     if (su.px == 1 && ((salign | (sv ? reinterpret_cast<size_t>(sv) : 0)) & 7) == 0) load = 1;
     else if (su.px == 2 && sv == su.p + 1 && (salign & 3) == 0) load = 2;
-    const size_t dalign = reinterpret_cast<size_t>(du.p) | (size_t)(2 * du.row) | (n > 1 ? (size_t)(2 * du.frame) : 0);
     const int pair = du.px == 2 && dv == du.p + 1 && (dalign & 3) == 0;
     const W2xcU16Scale k = u16_scale(depth, 0);
     const int rshift = su.pack ? 16 - depth : 0, lshift = du.pack ? 16 - depth : 0;
-#define W2XC_CHROMA16(L)                                                                                                                                             \
-    hipLaunchKernelGGL(k_chroma2x_u16<L>, dim3(grid), dim3(256), 0, st, su.p, sv, su.frame, su.row, su.px, cw, ch, rshift, k.max, du.p, dv, du.frame, du.row, du.px,     \
-                       lshift, pair, ow, oh, npl, k.inv_max, k.fmax, tiles_x, tiles, turns)
-    if (load == 2) W2XC_CHROMA16(2);
-    else if (load == 1) W2XC_CHROMA16(1);
-    else W2XC_CHROMA16(0);
-#undef W2XC_CHROMA16
+    const auto kernel = load == 2 ? k_chroma2x_u16<2> : load == 1 ? k_chroma2x_u16<1> : k_chroma2x_u16<0>;
+    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, st, su.p, sv, su.frame, su.row, su.px, cw, ch, rshift, k.max, du.p, dv, du.frame, du.row, du.px, lshift, pair,
+                       ow, oh, npl, k.inv_max, k.fmax, g.tiles_x, g.tiles, g.turns);
     return hipGetLastError();
 }

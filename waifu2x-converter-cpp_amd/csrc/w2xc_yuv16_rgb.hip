@@ -9,13 +9,11 @@
 // tiles of all frames are the turns of one grid-stride loop over at most W2XC_YUVRGB_GRID_MAX workgroups; the frame index moves only the 64-bit bases.
 #include "w2xc_kernels.h"
 #include "w2xc_tta_px.h"   // clampi
-#include "w2xc_yuv_px.h"   // lerp31, clamp01, to_ycc, u16_value, to_u16, the constants of a matrix and of a depth
+#include "w2xc_yuv_px.h"   // u16_value, to_u16, luma_u16, the constants of a matrix and of a depth
+#include "w2xc_yuv_tile.h" // the tile (YR_*), rows_align, yuv_tile_at, chroma_at_luma, rgb_px, chroma_mean
 
-#define YR_TCX W2XC_YUVRGB_TCX
-#define YR_TCY W2XC_YUVRGB_TCY
-#define YR_LD (YR_TCX + 3)          // words per LDS row of chroma: the tile, a halo sample at either side, one word of padding -- an odd count
 #define YR_YLD (2 * YR_TCX + 2)     // 16-bit words per LDS row of luma: the widest tile and one dword of padding -- 33 dwords, an odd count
-static_assert(YR_TCX == 32 && YR_TCY == 16 && (YR_LD & 1) == 1 && (YR_YLD & 1) == 0 && ((YR_YLD / 2) & 1) == 1, "256 threads = 32 x 8 chroma samples, two rows per thread");
+static_assert((YR_YLD & 1) == 0 && ((YR_YLD / 2) & 1) == 1, "a luma row in LDS is whole dwords, an odd count of them");
 
 // ---- words -> R, G, B ----
 // The chroma tiles with a one-sample halo along each subsampled axis (coordinates clamped into the plane, as the taps are) are kept in LDS as the samples' values
@@ -41,8 +39,8 @@ __global__ void __launch_bounds__(256) k_yuv16_to_rgb(const unsigned short *__re
     __shared__ __attribute__((aligned(4))) unsigned short ytile[2 * YR_TCY * YR_YLD];
     const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
     for (long long turn = blockIdx.x; turn < turns; turn += gridDim.x) {   // a turn: one tile of one frame
-        const long long f = turn / tiles, t = turn - f * tiles;
-        const int cy0 = (int)(t / tiles_x) * YR_TCY, cx0 = (int)(t % tiles_x) * YR_TCX;
+        int cx0, cy0;
+        const long long f = yuv_tile_at(turn, tiles, tiles_x, YR_TCX, YR_TCY, &cx0, &cy0);
         const int X0 = cx0 << HX, Y0 = cy0 << HY;   // the tile's first luma sample
         const unsigned short *fy = sy + f * yframe;
         // yv: the thread's groups of four luma samples go into registers first, so that their loads are in flight with those of the chroma tiles
@@ -133,24 +131,9 @@ __global__ void __launch_bounds__(256) k_yuv16_to_rgb(const unsigned short *__re
         for (int j = 0; j < 2; j++) {
             const int tr = ly + j * (YR_TCY / 2), cx = cx0 + lx, cy = cy0 + tr;
             if (cx >= cw || cy >= ch) continue;
-            // U and V at the block's luma samples: horizontally first, on the rows the vertical step needs, then vertically on the two row results
-            float cu[2][1 + HY][1 + HX];
+            float cu[2][1 + HY][1 + HX];   // U and V at the block's luma samples, from the thread's own sample
 #pragma unroll
-            for (int v = 0; v < 2; v++) {
-                const float *S = ctile[v] + (tr + HY) * YR_LD + lx + HX;   // the thread's own sample
-                float hz[1 + 2 * HY][1 + HX];                              // rows cy - 1, cy, cy + 1 (SY) or cy alone
-#pragma unroll
-                for (int r = 0; r < 1 + 2 * HY; r++) {
-                    const float *R = S + (r - HY) * YR_LD;
-                    if (SX) { hz[r][0] = lerp31(R[0], R[-1]); hz[r][HX] = lerp31(R[0], R[1]); }
-                    else hz[r][0] = R[0];
-                }
-#pragma unroll
-                for (int q = 0; q < 1 + HX; q++) {
-                    if (SY) { cu[v][0][q] = lerp31(hz[HY][q], hz[0][q]); cu[v][HY][q] = lerp31(hz[HY][q], hz[2 * HY][q]); }
-                    else cu[v][0][q] = hz[0][q];
-                }
-            }
+            for (int v = 0; v < 2; v++) chroma_at_luma<SX, SY>(ctile[v] + (tr + HY) * YR_LD + lx + HX, YR_LD, cu[v]);
 #pragma unroll
             for (int r = 0; r < 1 + HY; r++) {
                 const int Y = (cy << HY) + r;
@@ -159,14 +142,7 @@ __global__ void __launch_bounds__(256) k_yuv16_to_rgb(const unsigned short *__re
 #pragma unroll
                 for (int q = 0; q < 1 + HX; q++) {
                     const float y = ((float)u16_value(ytile[((tr << HY) + r) * YR_YLD + (lx << HX) + q], yshift, max) - y0) * ky;
-                    const float cb = (cu[0][r][q] - c0) * kc;
-                    const float cr = (cu[1][r][q] - c0) * kc;
-                    const float R = y + m.cRV * cr;
-                    const float B = y + m.cBU * cb;
-                    const float G = (y - m.cGU * cb) - m.cGV * cr;
-                    px[0][q] = clamp01(R);
-                    px[1][q] = clamp01(G);
-                    px[2][q] = clamp01(B);
+                    rgb_px(m, y, (cu[0][r][q] - c0) * kc, (cu[1][r][q] - c0) * kc, px, q);
                 }
                 const int X = cx << HX;
                 float *d = o + (long long)Y * w + X;
@@ -185,20 +161,6 @@ __global__ void __launch_bounds__(256) k_yuv16_to_rgb(const unsigned short *__re
     }
 }
 
-template <bool SX, bool SY>
-static hipError_t launch_to_rgb16(int cm, unsigned grid, hipStream_t st, const unsigned short *sy, long long yframe, long long yrow, int yv, int yshift,
-                                  const unsigned short *su, const unsigned short *sv, long long cframe, long long crow, int spx, int cshift, int max, int w, int h, int cw,
-                                  int ch, float y0, float ky, float c0, float kc, W2xcYuvToRgb m, float *rgb, long long is, long long ps, int v2, int tiles_x,
-                                  long long tiles, long long turns)
-{
-    hipLaunchKernelGGL((cm == 2 ? k_yuv16_to_rgb<2, SX, SY> : cm == 1 ? k_yuv16_to_rgb<1, SX, SY> : k_yuv16_to_rgb<0, SX, SY>), dim3(grid), dim3(256), 0, st, sy, yframe,
-                       yrow, yv, yshift, su, sv, cframe, crow, spx, cshift, max, w, h, cw, ch, y0, ky, c0, kc, m, rgb, is, ps, v2, tiles_x, tiles, turns);
-    return hipGetLastError();
-}
-
-// the byte alignment every row of a plane of words shares (strides are in words)
-static size_t rows_align(const W2xcU16Planes &p, int n) { return reinterpret_cast<size_t>(p.p) | (size_t)(2 * p.row) | (n > 1 ? (size_t)(2 * p.frame) : 0); }
-
 hipError_t w2xc_launch_yuv16_to_rgb(W2xcU16Planes y, W2xcU16Planes u, const unsigned short *v, int w, int h, int chroma, int range, int matrix, int depth, float *rgb,
                                     long long is, long long ps, int n, hipStream_t st)
 {
@@ -207,20 +169,19 @@ hipError_t w2xc_launch_yuv16_to_rgb(W2xcU16Planes y, W2xcU16Planes u, const unsi
     if (!matrix_to_rgb(matrix, &m) || !frame_geometry(w, h, chroma, &cw, &ch) || n < 1 || !y.p || !u.p || !v || !rgb || y.px != 1 || (u.px != 1 && u.px != 2) ||
         depth < 8 || depth > 16)
         return hipErrorInvalidValue;
-    const int tiles_x = (cw + YR_TCX - 1) / YR_TCX, tiles_y = (ch + YR_TCY - 1) / YR_TCY;
-    const long long tiles = (long long)tiles_x * tiles_y, turns = tiles * n;
-    const unsigned grid = (unsigned)(turns > W2XC_YUVRGB_GRID_MAX ? W2XC_YUVRGB_GRID_MAX : turns);
+    const YuvTileGrid g = w2xc_eng::yuv_rgb_tile_grid(cw, ch, n, YR_TCX, YR_TCY, W2XC_YUVRGB_GRID_MAX);
     const int yv = (rows_align(y, n) & 7) == 0;
     int cm = 0;
     if (u.px == 1 && ((rows_align(u, n) | reinterpret_cast<size_t>(v)) & 7) == 0) cm = 1;
     else if (u.px == 2 && v == u.p + 1 && (rows_align(u, n) & 3) == 0) cm = 2;
     const W2xcU16Scale k = u16_scale(depth, range != 0);
     const int v2 = rows_8_aligned(rgb, is, ps, w, n), yshift = y.pack ? 16 - depth : 0, cshift = u.pack ? 16 - depth : 0;
-#define W2XC_TO_RGB16(SX, SY)                                                                                                                                        \
-    launch_to_rgb16<SX, SY>(cm, grid, st, y.p, y.frame, y.row, yv, yshift, u.p, v, u.frame, u.row, u.px, cshift, k.max, w, h, cw, ch, k.y_off, k.y_in, k.c_mid, k.c_in, \
-                            m, rgb, is, ps, v2, tiles_x, tiles, turns)
-    return chroma == 0 ? W2XC_TO_RGB16(true, true) : chroma == 1 ? W2XC_TO_RGB16(true, false) : W2XC_TO_RGB16(false, false);
+#define W2XC_TO_RGB16(SX, SY) (cm == 2 ? k_yuv16_to_rgb<2, SX, SY> : cm == 1 ? k_yuv16_to_rgb<1, SX, SY> : k_yuv16_to_rgb<0, SX, SY>)
+    const auto kernel = chroma == 0 ? W2XC_TO_RGB16(true, true) : chroma == 1 ? W2XC_TO_RGB16(true, false) : W2XC_TO_RGB16(false, false);
 #undef W2XC_TO_RGB16
+    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, st, y.p, y.frame, y.row, yv, yshift, u.p, v, u.frame, u.row, u.px, cshift, k.max, w, h, cw, ch, k.y_off, k.y_in,
+                       k.c_mid, k.c_in, m, rgb, is, ps, v2, g.tiles_x, g.tiles, g.turns);
+    return hipGetLastError();
 }
 
 // ---- R, G, B -> words ----
@@ -239,8 +200,8 @@ __global__ void __launch_bounds__(256) k_rgb_to_yuv16(const float *__restrict__ 
     constexpr int HX = SX ? 1 : 0, HY = SY ? 1 : 0;
     const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
     for (long long turn = blockIdx.x; turn < turns; turn += gridDim.x) {
-        const long long f = turn / tiles, t = turn - f * tiles;
-        const int cy0 = (int)(t / tiles_x) * YR_TCY, cx0 = (int)(t % tiles_x) * YR_TCX;
+        int cx0, cy0;
+        const long long f = yuv_tile_at(turn, tiles, tiles_x, YR_TCX, YR_TCY, &cx0, &cy0);
         const float *s = rgb + f * is;
         unsigned short *oy = dy + f * yframe;
 #pragma unroll
@@ -270,21 +231,15 @@ __global__ void __launch_bounds__(256) k_rgb_to_yuv16(const float *__restrict__ 
                 const int Y = (cy << HY) + r, X = cx << HX;
                 if (Y >= h) continue;
                 unsigned short *d = oy + Y * yrow + X;
-                const unsigned b0 = (limited ? to_u16(p[r][0].y, ys, y0, max) : to_u16(p[r][0].y, ys, max)) << yshift;
+                const unsigned b0 = luma_u16(p[r][0].y, limited, ys, y0, max) << yshift;
                 if (SX && X + 1 < w) {
-                    const unsigned b1 = (limited ? to_u16(p[r][HX].y, ys, y0, max) : to_u16(p[r][HX].y, ys, max)) << yshift;
+                    const unsigned b1 = luma_u16(p[r][HX].y, limited, ys, y0, max) << yshift;
                     if (y32) *reinterpret_cast<unsigned *>(d) = b0 | (b1 << 16);
                     else { d[0] = (unsigned short)b0; d[1] = (unsigned short)b1; }
                 } else d[0] = (unsigned short)b0;
             }
             float cb, cr;
-            if (SX && SY) {
-                cb = ((p[0][0].cb + p[0][HX].cb) + (p[HY][0].cb + p[HY][HX].cb)) * 0.25f;
-                cr = ((p[0][0].cr + p[0][HX].cr) + (p[HY][0].cr + p[HY][HX].cr)) * 0.25f;
-            } else if (SX) {
-                cb = (p[0][0].cb + p[0][HX].cb) * 0.5f;
-                cr = (p[0][0].cr + p[0][HX].cr) * 0.5f;
-            } else { cb = p[0][0].cb; cr = p[0][0].cr; }
+            chroma_mean<SX, SY>(p, &cb, &cr);
             const long long at = f * cframe + cy * crow + (long long)cx * dpx;
             const unsigned U = to_u16(cb, cs, c0, max) << cshift, V = to_u16(cr, cs, c0, max) << cshift;
             if (uv32) *reinterpret_cast<unsigned *>(du + at) = U | (V << 16);
@@ -304,19 +259,13 @@ hipError_t w2xc_launch_rgb_to_yuv16(const float *rgb, long long is, long long ps
     if (!matrix_from_rgb(matrix, &m) || !frame_geometry(w, h, chroma, &cw, &ch) || n < 1 || !y.p || !u.p || !v || !rgb || y.px != 1 || (u.px != 1 && u.px != 2) ||
         depth < 8 || depth > 16)
         return hipErrorInvalidValue;
-    const int tiles_x = (cw + YR_TCX - 1) / YR_TCX, tiles_y = (ch + YR_TCY - 1) / YR_TCY;
-    const long long tiles = (long long)tiles_x * tiles_y, turns = tiles * n;
-    const unsigned grid = (unsigned)(turns > W2XC_YUVRGB_GRID_MAX ? W2XC_YUVRGB_GRID_MAX : turns);
+    const YuvTileGrid g = w2xc_eng::yuv_rgb_tile_grid(cw, ch, n, YR_TCX, YR_TCY, W2XC_YUVRGB_GRID_MAX);
     const int y32 = (rows_align(y, n) & 3) == 0;
     const int uv32 = u.px == 2 && v == u.p + 1 && (rows_align(u, n) & 3) == 0;
     const W2xcU16Scale k = u16_scale(depth, range != 0);
     const int limited = range != 0, v2 = rows_8_aligned(rgb, is, ps, w, n), yshift = y.pack ? 16 - depth : 0, cshift = u.pack ? 16 - depth : 0;
-#define W2XC_FROM_RGB16(SX, SY)                                                                                                                                      \
-    hipLaunchKernelGGL((k_rgb_to_yuv16<SX, SY>), dim3(grid), dim3(256), 0, st, rgb, is, ps, v2, w, h, cw, ch, limited, k.max, k.y_out, k.y_off, k.c_out, k.c_mid, m, y.p, \
-                       y.frame, y.row, y32, yshift, u.p, v, u.frame, u.row, u.px, uv32, cshift, tiles_x, tiles, turns)
-    if (chroma == 0) W2XC_FROM_RGB16(true, true);
-    else if (chroma == 1) W2XC_FROM_RGB16(true, false);
-    else W2XC_FROM_RGB16(false, false);
-#undef W2XC_FROM_RGB16
+    const auto kernel = chroma == 0 ? k_rgb_to_yuv16<true, true> : chroma == 1 ? k_rgb_to_yuv16<true, false> : k_rgb_to_yuv16<false, false>;
+    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, st, rgb, is, ps, v2, w, h, cw, ch, limited, k.max, k.y_out, k.y_off, k.c_out, k.c_mid, m, y.p, y.frame, y.row,
+                       y32, yshift, u.p, v, u.frame, u.row, u.px, uv32, cshift, g.tiles_x, g.tiles, g.turns);
     return hipGetLastError();
 }

@@ -1,10 +1,11 @@
 // w2xc_yuv_px.h -- the per-sample arithmetic of the YUV frame kernels that does not depend on the sample width: ONE definition each for the kernels on bytes
 // (w2xc_yuv.hip, w2xc_yuv_rgb.hip) and those on 16-bit words (w2xc_yuv16.hip, w2xc_yuv16_rgb.hip) -- the tap sum of the bicubic 2x, chroma at luma resolution,
-// the clamp to the models' domain, R, G, B -> y', cb, cr, the constants of a colour matrix, and the 16-bit sample format (depth, packing) as a kernel takes it.
+// the clamp to the models' domain, R, G, B -> y', cb, cr, y' -> a luma sample, the constants of a colour matrix, and the 16-bit sample format (depth, packing) as a
+// kernel takes it.  (What the tile kernels share beyond one sample -- geometry, grid, a thread's block -- is w2xc_yuv_tile.h.)
 // Every file that includes it is built with -ffp-contract=off.
 #pragma once
 #include "w2xc_kernels.h"
-#include "w2xc_tta_px.h"   // clampi
+#include "w2xc_tta_px.h"   // clampi, to_u8
 
 // the four taps of one row of the neighbourhood, summed in Resize2xCubic's order
 static __device__ __forceinline__ float chroma_row_sum(const float *S, const float *c)
@@ -46,6 +47,18 @@ static __device__ __forceinline__ unsigned u16_value(unsigned word, int rshift, 
 static __device__ __forceinline__ unsigned to_u16(float x, float scale, float offset, int max) { return (unsigned)clampi(__float2int_rn(x * scale + offset), 0, max); }
 // ... without an offset: saturate(rint(x * scale))
 static __device__ __forceinline__ unsigned to_u16(float x, float scale, int max) { return (unsigned)clampi(__float2int_rn(x * scale), 0, max); }
+
+// ---- y -> a luma sample, in the stages of the Y route and in the kernels of the RGB route alike ----
+// byte: full range to_u8, limited range saturate(rint(y * 219 + 16)), half to even, the product and the sum unfused
+static __device__ __forceinline__ unsigned char luma_u8(float y, int limited)
+{
+    return limited ? (unsigned char)clampi(__float2int_rn(y * 219.0f + 16.0f), 0, 255) : to_u8(y);
+}
+// value of a word: saturate(rint(y * M)), or saturate(rint(y * (219 s) + 16 s)) for limited range
+static __device__ __forceinline__ unsigned luma_u16(float y, int limited, float scale, float off, int max)
+{
+    return limited ? to_u16(y, scale, off, max) : to_u16(y, scale, max);
+}
 
 // ---- host: the constants of a matrix, doubles from the two luma weights, each rounded once to float (the header lists the expressions) ----
 static inline bool matrix_weights(int matrix, double *Kr, double *Kb)

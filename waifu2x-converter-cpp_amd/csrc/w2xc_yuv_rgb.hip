@@ -10,13 +10,11 @@
 // all frames are the turns of one grid-stride loop over at most W2XC_YUVRGB_GRID_MAX workgroups; the frame index moves only the 64-bit bases.
 #include "w2xc_kernels.h"
 #include "w2xc_tta_px.h"   // clampi, to_u8
-#include "w2xc_yuv_px.h"   // lerp31, clamp01, to_ycc, the constants of a matrix
+#include "w2xc_yuv_px.h"   // luma_u8, the constants of a matrix
+#include "w2xc_yuv_tile.h" // the tile (YR_*), rows_align, yuv_tile_at, chroma_at_luma, rgb_px, chroma_mean
 
-#define YR_TCX W2XC_YUVRGB_TCX
-#define YR_TCY W2XC_YUVRGB_TCY
-#define YR_LD (YR_TCX + 3)          // words per LDS row of chroma: the tile, a halo sample at either side, one word of padding -- an odd count
 #define YR_YLD (2 * YR_TCX + 4)     // bytes per LDS row of luma: the widest tile and one dword of padding
-static_assert(YR_TCX == 32 && YR_TCY == 16 && (YR_LD & 1) == 1 && (YR_YLD & 3) == 0, "256 threads = 32 x 8 chroma samples, two rows per thread");
+static_assert((YR_YLD & 3) == 0, "a luma row in LDS is whole dwords");
 
 // ---- bytes -> R, G, B ----
 // The chroma tile with a one-sample halo along each subsampled axis (coordinates clamped into the plane, as the taps are) is fetched once for U and once for V
@@ -39,8 +37,8 @@ __global__ void __launch_bounds__(256) k_yuv8_to_rgb(const unsigned char *__rest
     const float ky = limited ? (float)(1.0 / 219.0) : (float)(1.0 / 255.0), kc = limited ? (float)(1.0 / 224.0) : (float)(1.0 / 255.0);
     const float y0 = limited ? 16.0f : 0.0f;
     for (long long turn = blockIdx.x; turn < turns; turn += gridDim.x) {   // a turn: one tile of one frame
-        const long long f = turn / tiles, t = turn - f * tiles;
-        const int cy0 = (int)(t / tiles_x) * YR_TCY, cx0 = (int)(t % tiles_x) * YR_TCX;
+        int cx0, cy0;
+        const long long f = yuv_tile_at(turn, tiles, tiles_x, YR_TCX, YR_TCY, &cx0, &cy0);
         const int X0 = cx0 << HX, Y0 = cy0 << HY;   // the tile's first luma sample
         const unsigned char *fy = sy + f * yframe;
         __syncthreads();   // (the tiles of the loop's previous turn have been read)
@@ -105,24 +103,9 @@ __global__ void __launch_bounds__(256) k_yuv8_to_rgb(const unsigned char *__rest
         for (int j = 0; j < 2; j++) {
             const int tr = ly + j * (YR_TCY / 2), cx = cx0 + lx, cy = cy0 + tr;
             if (cx >= cw || cy >= ch) continue;
-            // U and V at the block's luma samples: horizontally first, on the rows the vertical step needs, then vertically on the two row results
-            float cu[2][1 + HY][1 + HX];
+            float cu[2][1 + HY][1 + HX];   // U and V at the block's luma samples, from the thread's own sample
 #pragma unroll
-            for (int v = 0; v < 2; v++) {
-                const float *S = ctile[v] + (tr + HY) * YR_LD + lx + HX;   // the thread's own sample
-                float hz[1 + 2 * HY][1 + HX];                              // rows cy - 1, cy, cy + 1 (SY) or cy alone
-#pragma unroll
-                for (int r = 0; r < 1 + 2 * HY; r++) {
-                    const float *R = S + (r - HY) * YR_LD;
-                    if (SX) { hz[r][0] = lerp31(R[0], R[-1]); hz[r][HX] = lerp31(R[0], R[1]); }
-                    else hz[r][0] = R[0];
-                }
-#pragma unroll
-                for (int q = 0; q < 1 + HX; q++) {
-                    if (SY) { cu[v][0][q] = lerp31(hz[HY][q], hz[0][q]); cu[v][HY][q] = lerp31(hz[HY][q], hz[2 * HY][q]); }
-                    else cu[v][0][q] = hz[0][q];
-                }
-            }
+            for (int v = 0; v < 2; v++) chroma_at_luma<SX, SY>(ctile[v] + (tr + HY) * YR_LD + lx + HX, YR_LD, cu[v]);
 #pragma unroll
             for (int r = 0; r < 1 + HY; r++) {
                 const int Y = (cy << HY) + r;
@@ -131,14 +114,7 @@ __global__ void __launch_bounds__(256) k_yuv8_to_rgb(const unsigned char *__rest
 #pragma unroll
                 for (int q = 0; q < 1 + HX; q++) {
                     const float y = ((float)ytile[((tr << HY) + r) * YR_YLD + (lx << HX) + q] - y0) * ky;
-                    const float cb = (cu[0][r][q] - 128.0f) * kc;
-                    const float cr = (cu[1][r][q] - 128.0f) * kc;
-                    const float R = y + m.cRV * cr;
-                    const float B = y + m.cBU * cb;
-                    const float G = (y - m.cGU * cb) - m.cGV * cr;
-                    px[0][q] = clamp01(R);
-                    px[1][q] = clamp01(G);
-                    px[2][q] = clamp01(B);
+                    rgb_px(m, y, (cu[0][r][q] - 128.0f) * kc, (cu[1][r][q] - 128.0f) * kc, px, q);
                 }
                 const int X = cx << HX;
                 float *d = o + (long long)Y * w + X;
@@ -157,16 +133,6 @@ __global__ void __launch_bounds__(256) k_yuv8_to_rgb(const unsigned char *__rest
     }
 }
 
-template <bool SX, bool SY>
-static hipError_t launch_to_rgb(bool dw, unsigned grid, hipStream_t st, const unsigned char *sy, long long yframe, long long yrow, const unsigned char *su,
-                                const unsigned char *sv, long long cframe, long long crow, int spx, int w, int h, int cw, int ch, int limited, W2xcYuvToRgb m,
-                                float *rgb, long long is, long long ps, int v2, int tiles_x, long long tiles, long long turns)
-{
-    hipLaunchKernelGGL((dw ? k_yuv8_to_rgb<true, SX, SY> : k_yuv8_to_rgb<false, SX, SY>), dim3(grid), dim3(256), 0, st, sy, yframe, yrow, su, sv, cframe, crow, spx, w,
-                       h, cw, ch, limited, m, rgb, is, ps, v2, tiles_x, tiles, turns);
-    return hipGetLastError();
-}
-
 hipError_t w2xc_launch_yuv8_to_rgb(W2xcU8Planes y, W2xcU8Planes u, const unsigned char *v, int w, int h, int chroma, int range, int matrix, float *rgb, long long is,
                                    long long ps, int n, hipStream_t st)
 {
@@ -174,17 +140,17 @@ hipError_t w2xc_launch_yuv8_to_rgb(W2xcU8Planes y, W2xcU8Planes u, const unsigne
     int cw, ch;
     if (!matrix_to_rgb(matrix, &m) || !frame_geometry(w, h, chroma, &cw, &ch) || n < 1 || !y.p || !u.p || !v || !rgb || y.px != 1 || (u.px != 1 && u.px != 2))
         return hipErrorInvalidValue;
-    const int tiles_x = (cw + YR_TCX - 1) / YR_TCX, tiles_y = (ch + YR_TCY - 1) / YR_TCY;
-    const long long tiles = (long long)tiles_x * tiles_y, turns = tiles * n;
-    const unsigned grid = (unsigned)(turns > W2XC_YUVRGB_GRID_MAX ? W2XC_YUVRGB_GRID_MAX : turns);
-    size_t align = reinterpret_cast<size_t>(y.p) | (size_t)y.row | (n > 1 ? (size_t)y.frame : 0);
-    if (u.px == 1) align |= reinterpret_cast<size_t>(u.p) | reinterpret_cast<size_t>(v) | (size_t)u.row | (n > 1 ? (size_t)u.frame : 0);
+    const YuvTileGrid g = w2xc_eng::yuv_rgb_tile_grid(cw, ch, n, YR_TCX, YR_TCY, W2XC_YUVRGB_GRID_MAX);
+    size_t align = rows_align(y, n);
+    if (u.px == 1) align |= rows_align(u, n) | reinterpret_cast<size_t>(v);
     const bool dw = (align & 3) == 0;
     const int limited = range != 0, v2 = rows_8_aligned(rgb, is, ps, w, n);
-#define W2XC_TO_RGB(SX, SY)                                                                                                                                          \
-    launch_to_rgb<SX, SY>(dw, grid, st, y.p, y.frame, y.row, u.p, v, u.frame, u.row, u.px, w, h, cw, ch, limited, m, rgb, is, ps, v2, tiles_x, tiles, turns)
-    return chroma == 0 ? W2XC_TO_RGB(true, true) : chroma == 1 ? W2XC_TO_RGB(true, false) : W2XC_TO_RGB(false, false);
+#define W2XC_TO_RGB(SX, SY) (dw ? k_yuv8_to_rgb<true, SX, SY> : k_yuv8_to_rgb<false, SX, SY>)
+    const auto kernel = chroma == 0 ? W2XC_TO_RGB(true, true) : chroma == 1 ? W2XC_TO_RGB(true, false) : W2XC_TO_RGB(false, false);
 #undef W2XC_TO_RGB
+    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, st, y.p, y.frame, y.row, u.p, v, u.frame, u.row, u.px, w, h, cw, ch, limited, m, rgb, is, ps, v2,
+                       g.tiles_x, g.tiles, g.turns);
+    return hipGetLastError();
 }
 
 // ---- R, G, B -> bytes ----
@@ -192,10 +158,6 @@ hipError_t w2xc_launch_yuv8_to_rgb(W2xcU8Planes y, W2xcU8Planes u, const unsigne
 // and one V byte, and stores only to its own samples: byte stores, or -- Y16: every luma row starts on an even address -- one 16-bit store for the two luma
 // bytes of a row where both lie in the plane.  Never a read-modify-write: with dpx = 2 the bytes between a plane's samples are the other plane's.
 // Loads: v2 (every row of every float plane starts on an 8-byte boundary) fetches a thread's two adjacent pixels of a row as ONE 8-byte load per plane.
-static __device__ __forceinline__ unsigned char luma_u8(float y, int limited)
-{
-    return limited ? (unsigned char)clampi(__float2int_rn(y * 219.0f + 16.0f), 0, 255) : to_u8(y);
-}
 static __device__ __forceinline__ unsigned char chroma_u8(float c, float scale) { return (unsigned char)clampi(__float2int_rn(c * scale + 128.0f), 0, 255); }
 
 template <bool SX, bool SY>
@@ -208,8 +170,8 @@ __global__ void __launch_bounds__(256) k_rgb_to_yuv8(const float *__restrict__ r
     const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
     const float cs = limited ? 224.0f : 255.0f;
     for (long long turn = blockIdx.x; turn < turns; turn += gridDim.x) {
-        const long long f = turn / tiles, t = turn - f * tiles;
-        const int cy0 = (int)(t / tiles_x) * YR_TCY, cx0 = (int)(t % tiles_x) * YR_TCX;
+        int cx0, cy0;
+        const long long f = yuv_tile_at(turn, tiles, tiles_x, YR_TCX, YR_TCY, &cx0, &cy0);
         const float *s = rgb + f * is;
         unsigned char *oy = dy + f * yframe;
 #pragma unroll
@@ -247,13 +209,7 @@ __global__ void __launch_bounds__(256) k_rgb_to_yuv8(const float *__restrict__ r
                 } else d[0] = (unsigned char)b0;
             }
             float cb, cr;
-            if (SX && SY) {
-                cb = ((p[0][0].cb + p[0][HX].cb) + (p[HY][0].cb + p[HY][HX].cb)) * 0.25f;
-                cr = ((p[0][0].cr + p[0][HX].cr) + (p[HY][0].cr + p[HY][HX].cr)) * 0.25f;
-            } else if (SX) {
-                cb = (p[0][0].cb + p[0][HX].cb) * 0.5f;
-                cr = (p[0][0].cr + p[0][HX].cr) * 0.5f;
-            } else { cb = p[0][0].cb; cr = p[0][0].cr; }
+            chroma_mean<SX, SY>(p, &cb, &cr);
             const long long at = f * cframe + cy * crow + (long long)cx * dpx;
             du[at] = chroma_u8(cb, cs);
             dv[at] = chroma_u8(cr, cs);
@@ -268,17 +224,11 @@ hipError_t w2xc_launch_rgb_to_yuv8(const float *rgb, long long is, long long ps,
     int cw, ch;
     if (!matrix_from_rgb(matrix, &m) || !frame_geometry(w, h, chroma, &cw, &ch) || n < 1 || !y.p || !u.p || !v || !rgb || y.px != 1 || (u.px != 1 && u.px != 2))
         return hipErrorInvalidValue;
-    const int tiles_x = (cw + YR_TCX - 1) / YR_TCX, tiles_y = (ch + YR_TCY - 1) / YR_TCY;
-    const long long tiles = (long long)tiles_x * tiles_y, turns = tiles * n;
-    const unsigned grid = (unsigned)(turns > W2XC_YUVRGB_GRID_MAX ? W2XC_YUVRGB_GRID_MAX : turns);
-    const int y16 = ((reinterpret_cast<size_t>(y.p) | (size_t)y.row | (n > 1 ? (size_t)y.frame : 0)) & 1) == 0;
+    const YuvTileGrid g = w2xc_eng::yuv_rgb_tile_grid(cw, ch, n, YR_TCX, YR_TCY, W2XC_YUVRGB_GRID_MAX);
+    const int y16 = (rows_align(y, n) & 1) == 0;
     const int limited = range != 0, v2 = rows_8_aligned(rgb, is, ps, w, n);
-#define W2XC_FROM_RGB(SX, SY)                                                                                                                                        \
-    hipLaunchKernelGGL((k_rgb_to_yuv8<SX, SY>), dim3(grid), dim3(256), 0, st, rgb, is, ps, v2, w, h, cw, ch, limited, m, y.p, y.frame, y.row, y16, u.p, v, u.frame,    \
-                       u.row, u.px, tiles_x, tiles, turns)
-    if (chroma == 0) W2XC_FROM_RGB(true, true);
-    else if (chroma == 1) W2XC_FROM_RGB(true, false);
-    else W2XC_FROM_RGB(false, false);
-#undef W2XC_FROM_RGB
+    const auto kernel = chroma == 0 ? k_rgb_to_yuv8<true, true> : chroma == 1 ? k_rgb_to_yuv8<true, false> : k_rgb_to_yuv8<false, false>;
+    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, st, rgb, is, ps, v2, w, h, cw, ch, limited, m, y.p, y.frame, y.row, y16, u.p, v, u.frame, u.row, u.px,
+                       g.tiles_x, g.tiles, g.turns);
     return hipGetLastError();
 }
