@@ -160,7 +160,7 @@ def family_of(kernel):
 
 
 # Instantiations no public call launches, each with the condition that keeps it out (file:line of this commit's sources).
-_PLANAR32 = ("w2xc_select.cpp:167 planar_between(): `if (is_wino4_layer(m, l + 1, o)) return m->layers[l + 1].nin != 32;` -- a first layer writes planar "
+_PLANAR32 = ("w2xc_select.cpp:163 resolve_chain(), the layouts: `else if (c.layer[l + 1].wino4) planar = hl[l + 1].nin != 32;` -- a first layer writes planar "
              "planes only for a conv3x3_wino4 consumer with 64 / 128 input planes, so a 32-plane first layer always writes NHWC (and Model::filter goes "
              "through NHWC: w2xc_filter.cpp:35 `writes_nhwc = (kind == W2XC_K_MFMA || kind == W2XC_K_FIRST)`)")
 _W8 = ("w2xc_kernels.hip:512 w2xc_launch_conv(): `const bool w8 = d.cout >= 64;` and the cases of cout 64 / 128 choose `w8 ? <8-wave shape> : <this one>`: "
@@ -173,8 +173,8 @@ UNREACHABLE.update({
     first(3, 32, planar=True, batch=True): _PLANAR32,
     first(3, 32, planar=True, u8=True, batch=True): _PLANAR32,
     GATHER: ("w2xc_split.hip:1034 w2xc_launch_last_gather(): `if (d.in_ps <= 1 && d.out_ps == 1)` launches conv3x3_last_gather_x4 -- layer_desc "
-             "(w2xc_select.cpp:419) gives every fused-last producer `d.out_ps = 1`, and the gather's layer is always last_direct "
-             "(w2xc_select.cpp:310-311: its one plane goes to the caller's plane, `d.out_ps = 1`, w2xc_select.cpp:403)"),
+             "(w2xc_select.cpp:381) gives every fused-last producer `d.out_ps = 1`, and the gather's layer is always last_direct "
+             "(w2xc_select.cpp:279-280: its one plane goes to the caller's plane, `d.out_ps = 1`, w2xc_select.cpp:372)"),
 })
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------

@@ -309,34 +309,39 @@ inline int refuse_head(const w2xc_model *m, const char *call)
 
 // ---- w2xc_select.cpp ----
 // the fast path's kernel kind for layer l by its shape: w2xc_pick_kernel, but the head of an upconv model is W2XC_K_UPCONV and the 128 -> 256 layer in
-// front of one is a W2XC_K_MFMA layer (conv3x3_wino4 alone has a kernel for it: layer_kind)
+// front of one is a W2XC_K_MFMA layer (conv3x3_wino4 alone has a kernel for it: resolve_chain turns it into W2XC_K_DIRECT for every other choice)
 W2xcKernelKind pick_kind(const w2xc_model *m, int l);
 int split_terms(const w2xc_opts &o);
 int split_fmt(const w2xc_opts &o);
-W2xcKernelKind layer_kind(const w2xc_model *m, int l, const w2xc_opts &o);
-bool fuse_last(const w2xc_model *m, const w2xc_opts &o);
-bool fuse_first(const w2xc_model *m, const w2xc_opts &o);
-bool fuse_first_fp32(const w2xc_model *m, const w2xc_opts &o);
-bool fuse_last_fp32(const w2xc_model *m, const w2xc_opts &o);
-bool is_wino4_layer(const w2xc_model *m, int l, const w2xc_opts &o);
-int layer_mid_variant(const w2xc_model *m, int l, const w2xc_opts &o);
-bool uses_wino4(const w2xc_model *m, const w2xc_opts &o);
-bool planar_between(const w2xc_model *m, int l, const w2xc_opts &o);
-int out_terms_of(const w2xc_model *m, int l, const w2xc_opts &o);
-bool gather_in_producer(const w2xc_model *m, const w2xc_opts &o);
-int fused_halves(int T, int cin, int cout);
-// the RGB image pipeline: may layer 1 read / the last layer write the caller's interleaved uint8 image itself (conv3x3_first / conv3x3_last, U8)?  fp32 with
-// the fast kernels and w2xc_opts.fusion other than W2XC_FUSION_OFF, a three-plane W2XC_K_FIRST / W2XC_K_LAST layer.
-bool u8_source_layer(const w2xc_model *m, const w2xc_opts &o);
-bool u8_sink_layer(const w2xc_model *m, const w2xc_opts &o);
 enum MidVariant { MID_MFMA = 0, MID_WINO32 = 1, MID_WINO4 = 3 };
+
+// What a model runs with given options, decided ONCE (resolve_chain) and handed around as data: every consumer -- the plan, the descriptors, the launch
+// strategies, the batch rule, the image routes, w2xc_layer_kernel_name -- reads this table and takes no selection decision of its own.
+struct LayerPick {            // what runs layer l (0-based) and what it leaves behind
+    W2xcKernelKind kind = W2XC_K_DIRECT;   // the kernel kind that runs it (W2XC_K_FUSED_AWAY: the next layer's launch does)
+    int midv = MID_MFMA;      // which kernel runs a W2XC_K_MFMA layer (MID_MFMA for every other kind)
+    bool wino4 = false;       // fp32 and conv3x3_wino4 (F(4x4,3x3)) runs it
+    int out_terms = 0;        // of its output: 0 = fp32 activations, T = 16-bit term planes, 9 = the partial tap planes of the last layer it computes in its epilogue
+    bool planar_out = false;  // its output (= layer l + 1's input) is planar planes, not NHWC pixels
+    int halves = 0;           // out_terms == 9: partial planes per tap (wave columns of the split tile shapes, 64-plane blocks of conv3x3_wino4)
+};
+struct Chain {
+    int T = 0, fmt = 0;       // 16-bit terms per activation value (0 = fp32) and their format: split_terms / split_fmt of the options
+    bool fused_first = false, fused_last = false;   // layers 1 + 2 in one launch / the last layer inside the epilogue of the one before it (either precision)
+    bool prog_gather = false; // fp32, fused_last: the producing launch may finish the last layer itself (conv3x3_wino4 PROG)
+    bool any_wino4 = false;   // some layer is a wino4 layer: the band geometry needs four halo rows per layer
+    bool u8_source = false, u8_sink = false;   // the RGB image pipeline: layer 1 may read / the last layer may write the caller's interleaved uint8 image itself
+    std::vector<LayerPick> layer;
+};
+// resolved per call (no cache on the model or the context: nothing to invalidate, nothing shared between threads)
+Chain resolve_chain(const w2xc_model *m, const w2xc_opts &o);
 
 // the band geometry of one run_rows call (plan_rows, w2xc_select.cpp): pure host arithmetic
 struct RowPlan {
     w2xc_opts o;              // the options the call runs with (W2XC_FUSION_AUTO gives up a fusion whose kernel cannot address the plane)
+    Chain chain;              // resolve_chain(m, o), for exactly that o
     int n = 0, w = 0, plane_h = 0;
     int HL = 1;               // halo rows per layer: 1, or 4 = the banding-invariant geometry of conv3x3_wino4
-    int T = 0;                // 16-bit terms per activation (0 = fp32)
     int band = 0;             // output rows per band
     bool last_direct = false, all_out = false;
     W2xcKernelKind last_kind = W2XC_K_DIRECT;
@@ -365,8 +370,8 @@ W2xcKernelKind layer_desc(const w2xc_model *m, const RowPlan &P, int k, int y0, 
                           W2xcConvDesc &first_d, W2xcConvDesc *d, LayerSrc *next);
 
 // ---- w2xc_rows.cpp ----
-// bd != nullptr: the batch form of the launch (conv3x3_first2_wino4 / conv3x3_wino4 / the gather; conv3x3_first / conv3x3_wino / conv3x3_last) on bd->batch images
-int launch_layer(DevCtx *c, const w2xc_model *m, int l, W2xcKernelKind kind, W2xcConvDesc d, hipStream_t st, const w2xc_opts &o,
+// midv = LayerPick::midv of layer l (which kernel runs a W2XC_K_MFMA layer); bd != nullptr: the batch form of the launch (conv3x3_first2_wino4 / conv3x3_wino4 / the gather; conv3x3_first / conv3x3_wino / conv3x3_last) on bd->batch images
+int launch_layer(DevCtx *c, const w2xc_model *m, int l, W2xcKernelKind kind, int midv, W2xcConvDesc d, hipStream_t st, const w2xc_opts &o,
                  const W2xcBatchDesc *bd = nullptr);
 
 // Hooks of the host->host tile farm into the band loop (all optional; enqueue-only, never synchronise the device):
@@ -404,7 +409,7 @@ typedef Planes<const float> PlanesIn;   // (a PlanesOut converts to it)
 typedef Planes<float> PlanesOut;
 
 // u8 (the RGB image pipeline; no hooks): ROWS_U8_SRC = `in` is an interleaved uint8 image of three channels (layer 1 runs as W2XC_K_FIRST_U8); ROWS_U8_DST =
-// the same for `out` and the last layer (W2XC_K_LAST_U8).  The caller asks only where u8_source_layer / u8_sink_layer say yes.
+// the same for `out` and the last layer (W2XC_K_LAST_U8).  The caller asks only where the chain's u8_source / u8_sink say yes.
 // The RGBA call for upconv head models (w2xc_process_image_rgba_u8_up2x_batch*) reads and writes the caller's 4-byte pixels with three more, each beside the
 // flag of its side:
 //   ROWS_U8_SRC_A    `in` points at the ALPHA byte of an RGBA image and in.ps = 0: pixels 4 bytes apart, all three input planes that byte -- the grey image

@@ -29,8 +29,8 @@ int filter_on_device(w2xc_model *m, DevCtx *c, int layer, const float *in, long 
     w2xc_opts of = o_;          // Model::filter runs ONE layer: nothing to fuse it with (and no profiling events)
     of.fusion = W2XC_FUSION_OFF;
     of.profile = 0;
-    const w2xc_opts &o = of;
-    const W2xcKernelKind kind = layer_kind(m, layer, o);
+    const LayerPick L = resolve_chain(m, of).layer[layer];   // (the chain of these options: with fusion off every layer runs alone)
+    const W2xcKernelKind kind = L.kind;
     const bool want_nhwc_in = (kind == W2XC_K_MFMA || kind == W2XC_K_LAST);
     const bool writes_nhwc = (kind == W2XC_K_MFMA || kind == W2XC_K_FIRST);
     W2xcConvDesc d;
@@ -38,7 +38,7 @@ int filter_on_device(w2xc_model *m, DevCtx *c, int layer, const float *in, long 
     d.in_h = d.out_h = h;
     d.in_w = d.out_w = w;
     d.off_y = d.off_x = -1;   // same-size conv, BORDER_REPLICATE via clamped loads (:141-142)
-    if (is_wino4_layer(m, layer, o)) {
+    if (L.wino4) {
         // conv3x3_wino4 runs a valid conv on planar planes with 16-byte aligned pixel quads: the replicate border (:141-142) is made explicit in a
         // padded planar copy of the input (one pass over Cin planes; the kernel then reads it with offset 0)
         const long long prs = ((long long)w + 2 + 31) & ~31ll, pcs = prs * (h + 2);
@@ -60,7 +60,7 @@ int filter_on_device(w2xc_model *m, DevCtx *c, int layer, const float *in, long 
             if (rc) return rc;
             d.out = fc.pout.as<float>(); d.out_rs = ors; d.out_ps = 1; d.out_cs = ors * h;
         }
-        int r = launch_layer(c, m, layer, kind, d, st, of);
+        int r = launch_layer(c, m, layer, kind, L.midv, d, st, of);
         if (r) return r;
         if (!(planar_direct || nhwc_direct)) HIP_TRY(w2xc_launch_repack(d.out, d.out_rs, 1, d.out_cs, out, out_rs, out_ps, out_cs, h, w, hl.nout, st));
         if (res_nhwc) *res_nhwc = false;
@@ -82,7 +82,7 @@ int filter_on_device(w2xc_model *m, DevCtx *c, int layer, const float *in, long 
         if (rc) return rc;
         d.out = fc.nhwc[ob].as<float>(); d.out_rs = (long long)w * hl.nout; d.out_ps = hl.nout; d.out_cs = 1;
     }
-    int r = launch_layer(c, m, layer, kind, d, st, of);
+    int r = launch_layer(c, m, layer, kind, L.midv, d, st, of);
     if (r) return r;
     if (!direct_out) HIP_TRY(w2xc_launch_repack(d.out, d.out_rs, d.out_ps, 1, out, out_rs, out_ps, out_cs, h, w, hl.nout, st));
     if (res_nhwc) *res_nhwc = !direct_out;

@@ -556,7 +556,7 @@ int convert_plane_host(w2xc_model *m, const float *in, size_t in_stride_bytes, i
     // halo rows of the units' source views: n, or 4 n when conv3x3_wino4 runs (its banding-invariant geometry, run_rows) -- if the rows handed
     // over hold that much around [row_begin, row_end); otherwise W2XC_KERNEL_AUTO means the F(2x2) kernels for this call
     int hs = (int)m->layers.size();
-    if (uses_wino4(m, o)) {
+    if (resolve_chain(m, o).any_wino4) {
         const int h4 = 4 * hs;
         const auto [need0, need1] = src_rows(row_begin, row_end, h4, up, H);
         if (in_row0 <= need0 && in_row0 + in_rows >= need1) hs = h4;

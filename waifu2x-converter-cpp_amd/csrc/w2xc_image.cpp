@@ -75,8 +75,8 @@ RgbPlan rgb_plan(const ImageCall &c)
     const int passes = (c.mn ? 1 : 0) + c.iterations;
     // (TTA: the mean is taken before the rounding, so no LAYER takes the uint8 image; the RGBA TTA calls have the spread and the gather take it -- whatever
     // the precision and the kernels -- the gather where the last pass is a scale pass with nothing behind it)
-    R.src_u8 = c.tta ? c.tta_u8 : u8_source_layer(c.mn ? c.mn : c.msc, c.o);
-    R.dst_u8 = c.tta ? c.tta_u8 && c.shrink == 0.0 && c.iterations > 0 : c.shrink == 0.0 && u8_sink_layer(c.iterations > 0 ? c.msc : c.mn, c.o);
+    R.src_u8 = c.tta ? c.tta_u8 : resolve_chain(c.mn ? c.mn : c.msc, c.o).u8_source;
+    R.dst_u8 = c.tta ? c.tta_u8 && c.shrink == 0.0 && c.iterations > 0 : c.shrink == 0.0 && resolve_chain(c.iterations > 0 ? c.msc : c.mn, c.o).u8_sink;
     if (!R.src_u8) R.floats += 3 * plane_floats(c.w, c.h);
     for (int p = 1; p <= passes; p++) {
         const int lvl = p - (c.mn ? 1 : 0);   // the pass's output level: the noise pass stays on level 0

@@ -89,7 +89,7 @@ struct AlphaRide {
 int process_y_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, size_t skip = 0, AlphaRide *al = nullptr);
 int process_rgb_device(const ImageCall &c, int S, int cap, U8In in, U8Out out, size_t skip = 0, int ends = 0);
 
-// What one image needs of float planes, and whether the call's first / last layer takes the uint8 image itself (u8_source_layer / u8_sink_layer: then the
+// What one image needs of float planes, and whether the call's first / last layer takes the uint8 image itself (the chain's u8_source / u8_sink: then the
 // float copy of the source / of the result -- 4^iterations as many pixels -- does not exist):
 struct RgbPlan {
     bool src_u8 = false, dst_u8 = false;

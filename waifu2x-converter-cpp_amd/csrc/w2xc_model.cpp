@@ -248,8 +248,8 @@ try {
     r.halo_rows_per_layer = P.HL;
     r.band_rows = P.band;
     r.n_bands = (row_end - row_begin + P.band - 1) / P.band;
-    r.fused_first = (split_terms(P.o) ? fuse_first(m, P.o) : fuse_first_fp32(m, P.o)) ? 1 : 0;
-    r.fused_last = (split_terms(P.o) ? fuse_last(m, P.o) : fuse_last_fp32(m, P.o)) ? 1 : 0;
+    r.fused_first = P.chain.fused_first ? 1 : 0;
+    r.fused_last = P.chain.fused_last ? 1 : 0;
     r.workspace_bytes[0] = P.need[0];
     r.workspace_bytes[1] = P.need[1];
     const size_t nb = plan->struct_size > 0 && (size_t)plan->struct_size < sizeof r ? (size_t)plan->struct_size : sizeof r;
@@ -608,14 +608,12 @@ const char *w2xc_layer_kernel_name(const w2xc_model *m, int layer, const w2xc_op
 {
     if (!m || layer < 0 || layer >= (int)m->layers.size()) return "";
     const w2xc_opts o = resolve_opts(opts);
-    const W2xcKernelKind k = layer_kind(m, layer, o);
+    const Chain chain = resolve_chain(m, o);
+    const LayerPick &L = chain.layer[layer];
     // (what the DEVICE entry points launch: conv3x3_wino4 PROG finishes the last layer itself there only on request; the host entry points always use it)
-    if (k == W2XC_K_LAST_GATHER && gather_in_producer(m, o) && o.fusion == W2XC_FUSION_PROG) return "(in_previous_layer)";
-    if (k == W2XC_K_MFMA) {
-        const int midv = layer_mid_variant(m, layer, o);
-        if (midv != MID_MFMA) return midv == MID_WINO4 ? "conv3x3_wino4" : "conv3x3_wino";
-    }
-    return w2xc_kernel_name(k, m->layers[layer].nin, m->layers[layer].nout);
+    if (L.kind == W2XC_K_LAST_GATHER && chain.prog_gather && o.fusion == W2XC_FUSION_PROG) return "(in_previous_layer)";
+    if (L.midv != MID_MFMA) return L.midv == MID_WINO4 ? "conv3x3_wino4" : "conv3x3_wino";
+    return w2xc_kernel_name(L.kind, m->layers[layer].nin, m->layers[layer].nout);
 }
 
 }  // extern "C"

@@ -16,12 +16,12 @@ enum W2xcKernelKind {
     W2XC_K_FIRST2_SPLIT = 10,  // layers 1 (1 -> 32) and 2 (32 -> {32,64,128}) in one kernel; launched in layer 2's slot
     W2XC_K_FUSED_AWAY = 11,    // layer 1 when W2XC_K_FIRST2_SPLIT / W2XC_K_FIRST2_WINO4 computes it: no launch
     W2XC_K_FIRST2_WINO4 = 12,  // fp32: layers 1 (1 -> 32) and 2 (32 -> 32, Winograd F(4x4,3x3)) in one kernel (w2xc_first2_wino4.hip); launched in layer 2's slot
-    // the RGB image pipeline (w2xc_process_image_rgb_u8*): never what w2xc_pick_kernel / layer_kind answer -- run_rows puts them in place of W2XC_K_FIRST /
+    // the RGB image pipeline (w2xc_process_image_rgb_u8*): never what w2xc_pick_kernel / resolve_chain answer -- run_rows puts them in place of W2XC_K_FIRST /
     // W2XC_K_LAST for the layer that touches the caller's uint8 image; both read the weight image of the kind they stand in for
     W2XC_K_FIRST_U8 = 13,      // W2XC_K_FIRST (3 -> {32,64,128}) reading an interleaved uint8 image: d.in = bytes, in_rs / in_ps / in_cs = row stride in bytes / 3 / 1
     W2XC_K_LAST_U8 = 14,       // W2XC_K_LAST ({32,64,128} -> 3) writing one: d.out = bytes, out_rs / out_ps / out_cs likewise
     // the head of an upconv model (w2xc_upconv.hip): {32,64,128,256} NHWC planes in -> {1,3} planes out at twice the size, 4x4 stride-2 transposed convolution;
-    // never what w2xc_pick_kernel answers (a head is a property of the model, not of a plane count) -- layer_kind puts it in place for the head layer
+    // never what w2xc_pick_kernel answers (a head is a property of the model, not of a plane count) -- pick_kind puts it in place for the head layer
     W2XC_K_UPCONV = 15,        // planar float planes out
     W2XC_K_UPCONV_U8 = 16,     // three interleaved uint8 channels out (as W2XC_K_LAST_U8), pixels 3 or 4 bytes apart
     W2XC_K_UPCONV_A_U8 = 17,   // the alpha head: channel 1 of a three-plane head alone, one uint8 per pixel (the w2xc_upconv_pack_alpha image, bias[1])

@@ -2,7 +2,7 @@
 // (src/convertRoutine.cpp:21-169) on MI355X, and the device-pointer entry points of include/w2xc_hip.h.
 //
 // Data layout in HBM: two ping-pong workspaces per (model, device) sized for one band; each boundary between layers picks
-// NHWC or planar fp32 (planar_between, w2xc_select.cpp); layer 1 reads the caller's planar plane with clamp-to-edge
+// NHWC or planar fp32 (resolve_chain, w2xc_select.cpp); layer 1 reads the caller's planar plane with clamp-to-edge
 // addressing (= copyMakeBorder, convertRoutine.cpp:35,96) and the last layer writes the planar output rows in place
 // (= crop + stitch, :40-46,143-161).  A band is `band_rows` output rows x full width; layer k of n computes a valid conv
 // on the haloed band (SURVEY invariants I1/I2).
@@ -77,12 +77,11 @@ hipError_t launch_kind(W2xcKernelKind kind, int midv, const W2xcConvDesc &d, con
 
 }  // namespace
 
-int launch_layer(DevCtx *c, const w2xc_model *m, int l, W2xcKernelKind kind, W2xcConvDesc d, hipStream_t st, const w2xc_opts &o, const W2xcBatchDesc *bd)
+int launch_layer(DevCtx *c, const w2xc_model *m, int l, W2xcKernelKind kind, int midv, W2xcConvDesc d, hipStream_t st, const w2xc_opts &o, const W2xcBatchDesc *bd)
 {
     DevLayer &dl = c->layers[l];
     d.cin = m->layers[l].nin;
     d.cout = m->layers[l].nout;
-    const int midv = kind == W2XC_K_MFMA ? layer_mid_variant(m, l, o) : MID_MFMA;
     int rc = W2XC_OK;
     switch (kind) {
     case W2XC_K_FUSED_AWAY: return W2XC_OK;   // computed by the next layer's W2XC_K_FIRST2_SPLIT / W2XC_K_FIRST2_WINO4 launch
@@ -108,7 +107,7 @@ int launch_layer(DevCtx *c, const w2xc_model *m, int l, W2xcKernelKind kind, W2x
         rc = midv == MID_WINO4 ? packed(&dl.w_wino4, (size_t)36 * d.cin * d.cout, [&](float *pk) { w2xc_wino4_pack(d.cin, d.cout, w, pk); })
                                : packed(&dl.w_wino, w2xc_wino_packed_floats(d.cin, d.cout), [&](float *pk) { w2xc_wino_pack(d.cin, d.cout, w, pk); });
         d.wpk = midv == MID_WINO4 ? dl.w_wino4 : dl.w_wino;
-        if (!rc && d.out_terms == 9) {   // the next (last) layer's weights ride along (fuse_last_fp32)
+        if (!rc && d.out_terms == 9) {   // the next (last) layer's weights ride along (the fp32 last-layer fusion)
             const HostLayer &hn = m->layers[l + 1];
             rc = packed(&c->layers[l + 1].w_last_wino4, w2xc_wino4_pack_last_floats(hn.nin), [&](float *pk) { w2xc_wino4_pack_last(hn.nin, hn.w.data(), pk); });
             d.w7pk = c->layers[l + 1].w_last_wino4;
@@ -146,15 +145,16 @@ struct Band {
 
     int launch(int k, W2xcKernelKind kind, const W2xcConvDesc &d) const
     {
-        if (!batch) return launch_layer(c, m, k - 1, kind, d, st, P.o);
+        const int midv = P.chain.layer[k - 1].midv;
+        if (!batch) return launch_layer(c, m, k - 1, kind, midv, d, st, P.o);
         // the image strides of layer k: the first launched layer reads the caller's planes, layer n writes them; layer j < n writes workspace (j - 1) & 1
         W2xcBatchDesc bd;
         memset(&bd, 0, sizeof bd);
         bd.batch = batch;
-        const bool first = k == 1 || (k == 2 && layer_kind(m, 0, P.o) == W2XC_K_FUSED_AWAY);
+        const bool first = k == 1 || (k == 2 && P.chain.layer[0].kind == W2XC_K_FUSED_AWAY);
         bd.in_bs = first ? in_bs : (long long)img_f[(k - 2) & 1];
         bd.out_bs = k == P.n ? out_bs : (long long)img_f[(k - 1) & 1];
-        return launch_layer(c, m, k - 1, kind, d, st, P.o, &bd);
+        return launch_layer(c, m, k - 1, kind, midv, d, st, P.o, &bd);
     }
     // stage the next band's input while this one computes
     int prefetch() const { return (hk && hk->prefetch && y1 < rb) ? hk->prefetch(y1, std::min(rb, y1 + P.band)) : W2XC_OK; }
@@ -200,8 +200,8 @@ W2xcConvDesc last_rows_of(const Band &B, const W2xcConvDesc &d, int off, int a, 
 bool prog_eligible(const Band &B, int k, W2xcKernelKind kind, const W2xcConvDesc &d)
 {
     const RowPlan &P = B.P;
-    return P.T == 0 && k == P.n - 1 && kind == W2XC_K_MFMA && d.out_terms == 9 && P.last_kind == W2XC_K_LAST_GATHER && P.last_direct && !P.all_out && d.in_ps == 1 &&
-           gather_in_producer(B.m, P.o) && P.w >= 4 && (long long)d.out_h * d.out_rs * 4 < (1ll << 32) &&
+    return P.chain.T == 0 && k == P.n - 1 && kind == W2XC_K_MFMA && d.out_terms == 9 && P.last_kind == W2XC_K_LAST_GATHER && P.last_direct && !P.all_out && d.in_ps == 1 &&
+           P.chain.prog_gather && P.w >= 4 && (long long)d.out_h * d.out_rs * 4 < (1ll << 32) &&
            ((B.hk && B.hk->prog_begin) || (!B.hk && P.o.fusion == W2XC_FUSION_PROG));
 }
 // *launched = false: the hook has no page-locked band buffer to hand out, another strategy runs the layer
@@ -272,8 +272,8 @@ bool tail32_eligible(const Band &B, int k, W2xcKernelKind kind, const W2xcConvDe
     const RowPlan &P = B.P;
     const BandHooks *hk = B.hk;
     const bool tail_unfused = d.out_terms == 0 && P.last_kind == W2XC_K_LAST;
-    const bool tail_fused4 = d.out_terms == 9 && P.last_kind == W2XC_K_LAST_GATHER && is_wino4_layer(B.m, k - 1, P.o);
-    return hk && P.T == 0 && k == P.n - 1 && P.n >= 2 && kind == W2XC_K_MFMA && (tail_unfused || tail_fused4) && P.last_direct && hk->out_chunk_rows > 0 &&
+    const bool tail_fused4 = d.out_terms == 9 && P.last_kind == W2XC_K_LAST_GATHER && P.chain.layer[k - 1].wino4;
+    return hk && P.chain.T == 0 && k == P.n - 1 && P.n >= 2 && kind == W2XC_K_MFMA && (tail_unfused || tail_fused4) && P.last_direct && hk->out_chunk_rows > 0 &&
            hk->output_ready && (B.y1 - B.y0) >= 256;
 }
 int run_tail32(const Band &B, int k, W2xcKernelKind kind, const W2xcConvDesc &d, int Tk)
@@ -352,8 +352,8 @@ int run_band(Band &B, const LayerSrc &view, int up)
     if (B.batch && (hk || o.fusion == W2XC_FUSION_PROG || !P.last_direct))
         return fail(W2XC_ERR_ARG, "internal error: a batched band that is not one plain launch per layer");
     // layer 1 of this band in row chunks (each waits only for the rows it reads) or in one launch behind the whole upload
-    const W2xcKernelKind kind1 = layer_kind(m, 0, o);
-    const bool first2_fp32 = kind1 == W2XC_K_FUSED_AWAY && n > 1 && layer_kind(m, 1, o) == W2XC_K_FIRST2_WINO4;   // (layers 1 + 2 in one launch: chunked like layer 1)
+    const W2xcKernelKind kind1 = P.chain.layer[0].kind;
+    const bool first2_fp32 = kind1 == W2XC_K_FUSED_AWAY && n > 1 && P.chain.layer[1].kind == W2XC_K_FIRST2_WINO4;   // (layers 1 + 2 in one launch: chunked like layer 1)
     B.in_chunk = (hk && hk->in_chunk && hk->input_upto && n > 1 && (kind1 == W2XC_K_FIRST || kind1 == W2XC_K_DIRECT || first2_fp32)) ? hk->in_chunk(B.y0, B.y1) : 0;
     if (hk && hk->input_needed && B.in_chunk <= 0) { int rc = hk->input_needed(B.y0, B.y1); if (rc) return rc; }
     const LayerDst dst = {B.out, B.out_rs, B.out_cs, {B.c->ws[0].as<float>(), B.c->ws[1].as<float>()}};
@@ -396,8 +396,8 @@ int run_band(Band &B, const LayerSrc &view, int up)
 // the uint8 views of a call planned as P: no hooks, channels one byte apart, and the layers they touch have the uint8 kernels
 static int check_u8_views(const w2xc_model *m, const RowPlan &P, int u8, bool hooks, long long in_ps, long long out_ps)
 {
-    if (u8 && (hooks || ((u8 & ROWS_U8_SRC) && (in_ps != ((u8 & ROWS_U8_SRC_A) ? 0 : 1) || !u8_source_layer(m, P.o))) ||
-               ((u8 & ROWS_U8_DST) && (out_ps != 1 || !P.last_direct || !u8_sink_layer(m, P.o)))))
+    if (u8 && (hooks || ((u8 & ROWS_U8_SRC) && (in_ps != ((u8 & ROWS_U8_SRC_A) ? 0 : 1) || !P.chain.u8_source)) ||
+               ((u8 & ROWS_U8_DST) && (out_ps != 1 || !P.last_direct || !P.chain.u8_sink))))
         return fail(W2XC_ERR_ARG, "internal error: a uint8 view for a layer without the uint8 kernel");
     // the forms of the RGBA head call: each beside the flag of its side, the sink's only where the last layer is a head (the alpha head: a three-plane one)
     const bool src_a = (u8 & ROWS_U8_SRC_A) != 0, dst_x = (u8 & (ROWS_U8_DST_PX4 | ROWS_U8_DST_A)) != 0, dst_fa = (u8 & ROWS_F32_DST_A) != 0;

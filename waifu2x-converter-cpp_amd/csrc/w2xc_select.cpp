@@ -1,4 +1,4 @@
-// w2xc_select.cpp -- which kernel runs which layer, which layers fuse, and the layouts between layers.
+// w2xc_select.cpp -- which kernel runs which layer, which layers fuse, and the layouts between layers: resolved once per call into a table (resolve_chain).
 #include "w2xc_engine.hpp"
 
 #include <cmath>
@@ -29,80 +29,6 @@ W2xcKernelKind pick_kind(const w2xc_model *m, int l)
     return w2xc_pick_kernel(m->layers[l].nin, m->layers[l].nout);
 }
 
-W2xcKernelKind layer_kind(const w2xc_model *m, int l, const w2xc_opts &o)
-{
-    if (m->layers[l].head) return W2XC_K_UPCONV;   // (the head has one kernel, whatever runs the 3x3 layers)
-    if (o.kernel == W2XC_KERNEL_DIRECT) return W2XC_K_DIRECT;
-    const W2xcKernelKind k = pick_kind(m, l);
-    if (wide_layer(m, l) && layer_mid_variant(m, l, o) != MID_WINO4) return W2XC_K_DIRECT;
-    const int n = (int)m->layers.size();
-    if (split_terms(o) > 0) {
-        // term planes live only BETWEEN a first/mid layer and a mid layer; everything that touches the
-        // caller's planes or the last layer is fp32.  Shapes without an MFMA kernel are unsupported.
-        if (l <= 1 && fuse_first(m, o)) return l == 0 ? W2XC_K_FUSED_AWAY : W2XC_K_FIRST2_SPLIT;
-        if (k == W2XC_K_MFMA) return l > 0 ? W2XC_K_MID_SPLIT : W2XC_K_DIRECT;
-        if (k == W2XC_K_FIRST && l == 0)
-            return (n > 1 && pick_kind(m, 1) == W2XC_K_MFMA) ? W2XC_K_FIRST_SPLIT : W2XC_K_FIRST;
-        if (k == W2XC_K_LAST && l == n - 1 && l > 0) return fuse_last(m, o) ? W2XC_K_LAST_GATHER : W2XC_K_LAST;
-        return W2XC_K_DIRECT;   // run_rows rejects this
-    }
-    if (k == W2XC_K_LAST && l == n - 1 && fuse_last_fp32(m, o)) return W2XC_K_LAST_GATHER;
-    if (l <= 1 && fuse_first_fp32(m, o)) return l == 0 ? W2XC_K_FUSED_AWAY : W2XC_K_FIRST2_WINO4;
-    return k;
-}
-
-// w2xc_opts.fusion: which of the two cross-layer fusions a call may use (both precisions; no environment switch takes part)
-static bool fusion_first_on(const w2xc_opts &o) { return o.fusion != W2XC_FUSION_OFF && o.fusion != W2XC_FUSION_LAST; }
-static bool fusion_last_on(const w2xc_opts &o) { return o.fusion != W2XC_FUSION_OFF && o.fusion != W2XC_FUSION_FIRST; }
-
-// fp32, last layer fused (fuse_last_fp32): does the producing launch also FINISH it (conv3x3_wino4 PROG: the partial tap planes are summed by the workgroup
-// whose arrival completes a 16-row x 256-column job, rows complete top to bottom while the launch runs), or does a conv3x3_last_gather launch follow
-// (rounds 4 / 5; w2xc_opts.fusion = W2XC_FUSION_GATHER_LAUNCH, and the shapes PROG has no instantiation for)?  The two are bit-identical.
-bool gather_in_producer(const w2xc_model *m, const w2xc_opts &o)
-{
-    const int n = (int)m->layers.size();
-    if (!fuse_last_fp32(m, o) || o.fusion == W2XC_FUSION_GATHER_LAUNCH) return false;
-    if (!w2xc_wino4_prog_supported(m->layers[n - 2].nin, m->layers[n - 2].nout)) return false;
-    return planar_between(m, n - 3, o);   // (the PROG instantiations read planar planes)
-}
-
-// 16-bit modes: layers 1 (ONE plane -> 32) and 2 (32 -> {32,64,128}) run as one kernel (conv3x3_first2_split) when
-// layer 2 is an ordinary split mid layer.  w2xc_opts.fusion = W2XC_FUSION_OFF / _LAST disables.
-bool fuse_first(const w2xc_model *m, const w2xc_opts &o)
-{
-    const int n = (int)m->layers.size();
-    if (!fusion_first_on(o) || o.kernel == W2XC_KERNEL_DIRECT || n < 3 || split_terms(o) == 0 || m->has_head()) return false;
-    if (m->layers[0].nin != 1 || m->layers[0].nout != 32) return false;
-    if (pick_kind(m, 1) != W2XC_K_MFMA) return false;
-    return !(n == 3 && fuse_last(m, o));   // (layer 2 would be the fused-last producer: keep that fusion instead)
-}
-
-// 16-bit modes: the last layer (cin in {32,64,128} -> ONE plane) is computed inside the epilogue of the mid layer
-// before it (conv3x3_split, out_terms = 9) and finished by conv3x3_last_gather.  w2xc_opts.fusion = W2XC_FUSION_OFF / _FIRST disables.
-bool fuse_last(const w2xc_model *m, const w2xc_opts &o)
-{
-    const int n = (int)m->layers.size();
-    if (!fusion_last_on(o) || o.kernel == W2XC_KERNEL_DIRECT || n < 3) return false;
-    const int T = split_terms(o);
-    if (T < 1 || T > 3) return false;
-    return m->layers[n - 1].nout == 1 && pick_kind(m, n - 1) == W2XC_K_LAST &&
-           pick_kind(m, n - 2) == W2XC_K_MFMA && n - 2 > 0;
-}
-
-// terms of layer l's OUTPUT in the split pipeline: T when layer l+1 is a split mid layer, else 0 (fp32); 9 = this layer writes
-// the partial tap planes of the last layer it computes in its epilogue (16-bit modes: conv3x3_split; fp32: conv3x3_wino4)
-int out_terms_of(const w2xc_model *m, int l, const w2xc_opts &o)
-{
-    const int T = split_terms(o), n = (int)m->layers.size();
-    if (T == 0) return (l == n - 2 && fuse_last_fp32(m, o)) ? 9 : 0;
-    if (l + 1 >= n) return 0;
-    if (l == n - 2 && fuse_last(m, o)) return 9;
-    return layer_kind(m, l + 1, o) == W2XC_K_MID_SPLIT ? T : 0;
-}
-
-// partial-G planes a fused-last producer writes per tap: wave columns of the split tile shapes, 64-plane blocks of conv3x3_wino4
-int fused_halves(int T, int cin, int cout) { return T > 0 ? w2xc_split_halves(T, cin, cout) : cout / 64; }
-
 // fp32 path, layers with 32 / 64 / 128 planes in and out (W2XC_K_MFMA): which kernel runs them.
 //   MID_MFMA    conv3x3_mfma2: direct implicit GEMM, a k-ordered fp32 fma chain (the closest MFMA analogue of modelHandler.cpp:134-145)
 //   MID_WINO32  conv3x3_wino:   Winograd F(2x2,3x3) on v_mfma_f32_32x32x2_f32, one wave per SIMD (round 2)
@@ -131,90 +57,131 @@ int mid_variant_for(int midv, int cin, int cout)
 }
 }  // namespace
 
-// the variant mid layer l really runs with these options
-int layer_mid_variant(const w2xc_model *m, int l, const w2xc_opts &o)
+// What the model runs with these options.  Nine passes in dependency order; each reads the model, the options and what EARLIER passes filled in, and none
+// calls a function of (m, o) -- so the order below is the whole dependency graph, and it has no cycle:
+//   1 shape      the kind of every layer by its plane counts (pick_kind, with the wide-layer rule)            <- the model
+//   2 mid        the kernel variant of the W2XC_K_MFMA shapes, and which of them are wino4 layers             <- 1, the options
+//   3 last       the last-layer fusion                                                                        <- 1, 2
+//   4 first      the first-layer fusion; it stands back where the last-layer fusion claims the same layer     <- 1, 2, 3
+//   5 kinds      the kind that runs every layer                                                               <- 1 .. 4
+//   6 terms      out_terms of every layer's output, and the halves of a tap-plane producer                    <- 3, 5
+//   7 layouts    planar or NHWC between two layers                                                            <- 2, 4, 5
+//   8 gather     may the producer of the tap planes finish the last layer itself (conv3x3_wino4 PROG)         <- 3, 7
+//   9 uint8      may layer 1 read / the last layer write the caller's uint8 image                             <- 5
+Chain resolve_chain(const w2xc_model *m, const w2xc_opts &o)
 {
-    const HostLayer &p = m->layers[l];
-    int midv = mid_variant(o);
-    if (wide_layer(m, l)) return midv == MID_WINO4 ? MID_WINO4 : MID_MFMA;   // (conv3x3_wino4 or nothing: layer_kind)
-    return mid_variant_for(midv, p.nin, p.nout);
-}
-// does any layer of the fp32 path run conv3x3_wino4 (F(4x4,3x3))?  Its 4x4 blocks make results depend on where a band's per-layer regions end,
-// unless they end on block boundaries: run_rows then computes FOUR rows of halo per layer instead of one (and needs 4 n halo rows in its view).
-bool uses_wino4(const w2xc_model *m, const w2xc_opts &o)
-{
-    if (split_terms(o) != 0 || o.precision != W2XC_PRECISION_FP32 || o.kernel == W2XC_KERNEL_DIRECT) return false;
-    for (int l = 0; l < (int)m->layers.size(); l++)
-        if (pick_kind(m, l) == W2XC_K_MFMA && layer_mid_variant(m, l, o) == MID_WINO4) return true;
-    return false;
-}
-// conv3x3_wino4 reads PLANAR activations (one plane per channel, rows of roundup32(w) floats: 16-byte aligned pixel quads, tiles on 128-byte lines)
-// -- with 32 input planes also the NHWC pixels (one 128-byte line each) that the 32-plane producers conv3x3_first / conv3x3_wino write.
-// Layer l's output (l = 0 .. n-2) is planar when its consumer is a conv3x3_wino4 layer with 64 / 128 input planes, when layer l is the fused
-// conv3x3_first2_wino4 launch (layers 1 + 2; its consumer conv3x3_wino4<32, .> then reads planar), or when layer l is a conv3x3_wino4 layer and its
-// consumer is conv3x3_direct (any strides); everything else stays NHWC (conv3x3_wino4 writes either).  Producers that write planar:
-// conv3x3_wino4, conv3x3_first2_wino4, conv3x3_first (3 -> 64 / 128), conv3x3_direct.
-bool is_wino4_layer(const w2xc_model *m, int l, const w2xc_opts &o)
-{
-    if (split_terms(o) != 0 || o.precision != W2XC_PRECISION_FP32 || o.kernel == W2XC_KERNEL_DIRECT) return false;
-    return l >= 0 && l < (int)m->layers.size() && pick_kind(m, l) == W2XC_K_MFMA && layer_mid_variant(m, l, o) == MID_WINO4;
-}
-bool planar_between(const w2xc_model *m, int l, const w2xc_opts &o)   // layout of layer l's output = layer l + 1's input
-{
+    Chain c;
     const int n = (int)m->layers.size();
-    if (l < 0 || l + 1 >= n) return false;
-    if (l == 1 && fuse_first_fp32(m, o)) return true;   // (conv3x3_first2_wino4 writes planar planes; conv3x3_wino4<32, .> reads either)
-    if (is_wino4_layer(m, l + 1, o)) return m->layers[l + 1].nin != 32;   // (32 input planes: conv3x3_wino4 reads the producer's NHWC pixels, one 128-byte line each)
-    if (!is_wino4_layer(m, l, o)) return false;
-    return layer_kind(m, l + 1, o) == W2XC_K_DIRECT;   // (conv3x3_last reads NHWC at 5.4 TB/s; its planar variant measured half of that: NHWC out there)
-}
+    const int T = c.T = split_terms(o);
+    c.fmt = split_fmt(o);
+    c.layer.resize(n);
+    if (n == 0) return c;
+    const std::vector<HostLayer> &hl = m->layers;
+    const bool fp32 = T == 0 && o.precision == W2XC_PRECISION_FP32;
+    const bool fast = o.kernel != W2XC_KERNEL_DIRECT;   // W2XC_KERNEL_DIRECT runs every layer alone on conv3x3_direct, whatever `fusion` says
+    // w2xc_opts.fusion: which of the two cross-layer fusions a call may use (both precisions; no environment switch takes part)
+    const bool first_on = o.fusion != W2XC_FUSION_OFF && o.fusion != W2XC_FUSION_LAST, last_on = o.fusion != W2XC_FUSION_OFF && o.fusion != W2XC_FUSION_FIRST;
 
-// fp32 path: the one-plane last layer inside the epilogue of the layer before it when that layer runs conv3x3_wino4 (Cout 64 / 128):
-// the producer writes Cout / 64 x 9 partial tap planes instead of Cout activation planes, conv3x3_last_gather finishes.
-// w2xc_opts.fusion = W2XC_FUSION_OFF / _ON decides per call; W2XC_FUSION_AUTO = on.
-bool fuse_last_fp32(const w2xc_model *m, const w2xc_opts &o)
-{
-    const int n = (int)m->layers.size();
-    if (split_terms(o) != 0 || o.precision != W2XC_PRECISION_FP32 || o.kernel == W2XC_KERNEL_DIRECT || n < 3) return false;
-    if (!fusion_last_on(o)) return false;   // (W2XC_FUSION_AUTO = on)
-    const HostLayer &p = m->layers[n - 2], &q = m->layers[n - 1];
-    if (q.nout != 1 || q.nin != p.nout || pick_kind(m, n - 1) != W2XC_K_LAST || pick_kind(m, n - 2) != W2XC_K_MFMA) return false;
-    const int v = layer_mid_variant(m, n - 2, o);
-    return v == MID_WINO4;
-}
+    // 1 shape
+    std::vector<W2xcKernelKind> shape(n);
+    for (int l = 0; l < n; l++) shape[l] = pick_kind(m, l);
 
-// fp32 path: layers 1 (ONE plane -> 32) and 2 (32 -> 32) in one launch (conv3x3_first2_wino4: layer 1 on the fly per Winograd patch, layer 2 as F(4x4,3x3)
-// with its weights stationary in registers) when the default kernels run the model and layer 3 reads planar planes (a conv3x3_wino4 layer).  Layer 1's 32
-// activation planes never reach HBM (convertRoutine.cpp:66-76's loop collapsed by one more launch).  w2xc_opts.fusion = W2XC_FUSION_OFF disables.
-bool fuse_first_fp32(const w2xc_model *m, const w2xc_opts &o)
-{
-    const int n = (int)m->layers.size();
-    if (split_terms(o) != 0 || o.precision != W2XC_PRECISION_FP32 || n < 3 || !fusion_first_on(o) || m->has_head()) return false;   // (head models: no cross-layer fusion)
-    if (o.kernel != W2XC_KERNEL_AUTO && o.kernel != W2XC_KERNEL_WINOGRAD4) return false;
-    const HostLayer &a = m->layers[0], &b = m->layers[1];
-    if (!w2xc_first2_wino4_supported(a.nin, a.nout, b.nout) || b.nin != a.nout) return false;
-    if (n == 4 && fuse_last_fp32(m, o)) return false;   // (layer 3 would carry the fused last layer: that instantiation reads 32 NHWC planes only)
-    return is_wino4_layer(m, 2, o);   // (layer 3 = conv3x3_wino4: it reads layer 2's planar planes)
-}
+    // 2 mid: the variant a W2XC_K_MFMA shape really runs with these options (the wide layer: conv3x3_wino4 or nothing -- pass 5 makes it conv3x3_direct).
+    // A wino4 layer is one of the fp32 path: conv3x3_wino4's 4x4 blocks make results depend on where a band's per-layer regions end, unless they end on
+    // block boundaries -- run_rows then computes FOUR rows of halo per layer instead of one (and needs 4 n halo rows in its view): any_wino4.
+    std::vector<int> midv(n, MID_MFMA);
+    for (int l = 0; l < n; l++) {
+        if (shape[l] != W2XC_K_MFMA) continue;
+        const int want = mid_variant(o);
+        midv[l] = wide_layer(m, l) ? (want == MID_WINO4 ? MID_WINO4 : MID_MFMA) : mid_variant_for(want, hl[l].nin, hl[l].nout);
+        c.layer[l].wino4 = fp32 && fast && midv[l] == MID_WINO4;
+        c.any_wino4 |= c.layer[l].wino4;
+    }
 
-// The RGB image pipeline (w2xc_image.cpp): the layer that touches the caller's interleaved uint8 image converts in its own load / store where a kernel for
-// that exists -- the W2XC_K_FIRST layer of the call's first pass (3 -> 32 / 64 / 128), the W2XC_K_LAST layer of its last pass (32 / 64 / 128 -> 3) -- and
-// the float copy of that image never reaches HBM.  fp32 and the fast kernels only; w2xc_opts.fusion = W2XC_FUSION_OFF keeps the colour kernels around
-// float planes (the same float operations in the same order: the same bytes).
-static bool u8_forms_on(const w2xc_opts &o)
-{
-    return split_terms(o) == 0 && o.precision == W2XC_PRECISION_FP32 && o.kernel != W2XC_KERNEL_DIRECT && o.fusion != W2XC_FUSION_OFF;
-}
-bool u8_source_layer(const w2xc_model *m, const w2xc_opts &o)
-{
-    return u8_forms_on(o) && !m->layers.empty() && m->layers[0].nin == 3 && layer_kind(m, 0, o) == W2XC_K_FIRST;
-}
-bool u8_sink_layer(const w2xc_model *m, const w2xc_opts &o)
-{
-    const int n = (int)m->layers.size();
-    if (!u8_forms_on(o) || n == 0 || m->layers[n - 1].nout != 3) return false;
-    const W2xcKernelKind k = layer_kind(m, n - 1, o);
-    return k == W2XC_K_LAST || k == W2XC_K_UPCONV;   // (the head of an upconv model: upconv4x4_head, U8)
+    // 3 last: the one-plane last layer is computed inside the epilogue of the mid layer before it, which writes partial tap planes instead of activations
+    // (out_terms = 9), and finished by conv3x3_last_gather.  16-bit modes: the producer is conv3x3_split (cin in {32,64,128}).  fp32: the producer runs
+    // conv3x3_wino4 (Cout 64 / 128) and writes Cout / 64 x 9 tap planes instead of Cout activation planes.  w2xc_opts.fusion = W2XC_FUSION_OFF / _FIRST
+    // disables; W2XC_FUSION_AUTO = on.  (A head model has no W2XC_K_LAST layer: no cross-layer fusion.)
+    if (last_on && fast && n >= 3 && hl[n - 1].nout == 1 && shape[n - 1] == W2XC_K_LAST && shape[n - 2] == W2XC_K_MFMA)
+        c.fused_last = T > 0 || (fp32 && hl[n - 1].nin == hl[n - 2].nout && midv[n - 2] == MID_WINO4);
+
+    // 4 first: layers 1 (ONE plane -> 32) and 2 in one launch; layer 1's 32 activation planes never reach HBM (convertRoutine.cpp:66-76's loop collapsed by
+    // one more launch).  w2xc_opts.fusion = W2XC_FUSION_OFF / _LAST disables; head models: no cross-layer fusion.
+    //   16-bit modes  conv3x3_first2_split: layer 2 (32 -> {32,64,128}) is an ordinary split mid layer.
+    //   fp32          conv3x3_first2_wino4 (layer 1 on the fly per Winograd patch, layer 2 (32 -> 32) as F(4x4,3x3) with its weights stationary in registers)
+    //                 when the default kernels run the model and layer 3 is a wino4 layer: it reads layer 2's planar planes.
+    if (first_on && fast && n >= 3 && !m->has_head()) {
+        if (T > 0) c.fused_first = hl[0].nin == 1 && hl[0].nout == 32 && shape[1] == W2XC_K_MFMA;
+        else if (fp32)
+            c.fused_first = (o.kernel == W2XC_KERNEL_AUTO || o.kernel == W2XC_KERNEL_WINOGRAD4) && w2xc_first2_wino4_supported(hl[0].nin, hl[0].nout, hl[1].nout) &&
+                            hl[1].nin == hl[0].nout && c.layer[2].wino4;
+        if (T > 0 && n == 3 && c.fused_last) c.fused_first = false;    // (layer 2 would be the fused-last producer: keep that fusion instead)
+        if (T == 0 && n == 4 && c.fused_last) c.fused_first = false;   // (layer 3 would carry the fused last layer: that instantiation reads 32 NHWC planes only)
+    }
+
+    // 5 kinds
+    for (int l = 0; l < n; l++) {
+        W2xcKernelKind &k = c.layer[l].kind;
+        k = shape[l];
+        if (k == W2XC_K_UPCONV) continue;   // (the head has one kernel, whatever runs the 3x3 layers)
+        if (!fast || (wide_layer(m, l) && midv[l] != MID_WINO4)) k = W2XC_K_DIRECT;
+        else if (l <= 1 && c.fused_first) k = l == 0 ? W2XC_K_FUSED_AWAY : T > 0 ? W2XC_K_FIRST2_SPLIT : W2XC_K_FIRST2_WINO4;
+        else if (T > 0) {
+            // term planes live only BETWEEN a first/mid layer and a mid layer; everything that touches the
+            // caller's planes or the last layer is fp32.  Shapes without an MFMA kernel are unsupported.
+            if (k == W2XC_K_MFMA) k = l > 0 ? W2XC_K_MID_SPLIT : W2XC_K_DIRECT;
+            else if (k == W2XC_K_FIRST && l == 0) k = (n > 1 && shape[1] == W2XC_K_MFMA) ? W2XC_K_FIRST_SPLIT : W2XC_K_FIRST;
+            else if (k == W2XC_K_LAST && l == n - 1 && l > 0) k = c.fused_last ? W2XC_K_LAST_GATHER : W2XC_K_LAST;
+            else k = W2XC_K_DIRECT;   // plan_rows rejects this
+        } else if (k == W2XC_K_LAST && l == n - 1 && c.fused_last) k = W2XC_K_LAST_GATHER;
+        if (k == W2XC_K_MFMA) c.layer[l].midv = midv[l];
+    }
+
+    // 6 terms: of layer l's OUTPUT in the split pipeline: T when layer l + 1 is a split mid layer, else 0 (fp32); 9 = this layer writes the partial tap
+    // planes of the last layer it computes in its epilogue (16-bit modes: conv3x3_split; fp32: conv3x3_wino4) -- `halves` of them per tap: wave columns
+    // of the split tile shapes, 64-plane blocks of conv3x3_wino4 (its epilogue sums the four plane tiles of a block on chip)
+    for (int l = 0; l + 1 < n; l++) {
+        LayerPick &L = c.layer[l];
+        if (l == n - 2 && c.fused_last) {
+            L.out_terms = 9;
+            L.halves = T > 0 ? w2xc_split_halves(T, hl[l].nin, hl[l].nout) : hl[l].nout / 64;
+        } else if (c.layer[l + 1].kind == W2XC_K_MID_SPLIT) L.out_terms = T;
+    }
+
+    // 7 layouts: conv3x3_wino4 reads PLANAR activations (one plane per channel, rows of roundup32(w) floats: 16-byte aligned pixel quads, tiles on 128-byte
+    // lines) -- with 32 input planes also the NHWC pixels (one 128-byte line each) that the 32-plane producers conv3x3_first / conv3x3_wino write.
+    // Layer l's output (l = 0 .. n-2) is planar when its consumer is a wino4 layer with 64 / 128 input planes, when layer l is the fused
+    // conv3x3_first2_wino4 launch (layers 1 + 2; its consumer conv3x3_wino4<32, .> then reads planar), or when layer l is a wino4 layer and its
+    // consumer is conv3x3_direct (any strides); everything else stays NHWC (conv3x3_wino4 writes either).  Producers that write planar:
+    // conv3x3_wino4, conv3x3_first2_wino4, conv3x3_first (3 -> 64 / 128), conv3x3_direct.
+    // (Why planar rows are roundup32(w) floats: a tile's 32-pixel row segment -- tiles start at multiples of 32 pixels -- is then ONE 128-byte line; with
+    // rows of roundup4(w) floats every segment straddled two lines, each written in two pieces by different workgroups: the 32 -> 32 layer in front took
+    // 2.0 ms instead of 0.8, measured.  layer_desc applies it.)
+    for (int l = 0; l + 1 < n; l++) {
+        bool &planar = c.layer[l].planar_out;
+        if (c.layer[l].kind == W2XC_K_FIRST2_WINO4) planar = true;   // (conv3x3_first2_wino4 writes planar planes; conv3x3_wino4<32, .> reads either)
+        else if (c.layer[l + 1].wino4) planar = hl[l + 1].nin != 32;   // (32 input planes: conv3x3_wino4 reads the producer's NHWC pixels, one 128-byte line each)
+        else if (c.layer[l].wino4) planar = c.layer[l + 1].kind == W2XC_K_DIRECT;   // (conv3x3_last reads NHWC at 5.4 TB/s; its planar variant measured half of that: NHWC out there)
+    }
+
+    // 8 gather: fp32, last layer fused: does the producing launch also FINISH it (conv3x3_wino4 PROG: the partial tap planes are summed by the workgroup
+    // whose arrival completes a 16-row x 256-column job, rows complete top to bottom while the launch runs), or does a conv3x3_last_gather launch follow
+    // (rounds 4 / 5; w2xc_opts.fusion = W2XC_FUSION_GATHER_LAUNCH, and the shapes PROG has no instantiation for)?  The two are bit-identical.
+    // (Where it may, the tap planes' rows start on 128-byte lines -- layer_desc, ws_need: a tile's 32-pixel row segment of a tap plane is then exactly ONE
+    // line, written whole, and a gather job never pulls a line into its XCD's L2 that holds columns of a tile it does not depend on -- with rows of out_w
+    // floats such a line, cached before its last columns were written, was served stale to the neighbouring job later: intermittent mismatches on small planes.)
+    c.prog_gather = T == 0 && c.fused_last && o.fusion != W2XC_FUSION_GATHER_LAUNCH && w2xc_wino4_prog_supported(hl[n - 2].nin, hl[n - 2].nout) &&
+                           c.layer[n - 3].planar_out;   // (the PROG instantiations read planar planes)
+
+    // 9 uint8: the RGB image pipeline (w2xc_image.cpp): the layer that touches the caller's interleaved uint8 image converts in its own load / store where a
+    // kernel for that exists -- the W2XC_K_FIRST layer of the call's first pass (3 -> 32 / 64 / 128), the W2XC_K_LAST layer of its last pass (32 / 64 / 128
+    // -> 3) or the head of an upconv model (upconv4x4_head, U8) -- and the float copy of that image never reaches HBM.  fp32 and the fast kernels only;
+    // w2xc_opts.fusion = W2XC_FUSION_OFF keeps the colour kernels around float planes (the same float operations in the same order: the same bytes).
+    if (fp32 && fast && o.fusion != W2XC_FUSION_OFF) {
+        c.u8_source = hl[0].nin == 3 && c.layer[0].kind == W2XC_K_FIRST;
+        c.u8_sink = hl[n - 1].nout == 3 && (c.layer[n - 1].kind == W2XC_K_LAST || c.layer[n - 1].kind == W2XC_K_UPCONV);
+    }
+    return c;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -239,13 +206,14 @@ void RowPlan::ws_need(const w2xc_model *m, int rows, size_t need[2]) const
     need[0] = need[1] = 0;
     for (int k = 1; k <= n; k++) {
         if (k == n && last_direct) break;   // written straight to d_out
-        if (k == 1 && layer_kind(m, 0, o) == W2XC_K_FUSED_AWAY) continue;   // layer 1's activations stay on chip
+        const LayerPick &L = chain.layer[k - 1];
+        if (L.kind == W2XC_K_FUSED_AWAY) continue;   // layer 1's activations stay on chip
         const size_t hk = (size_t)rows + ((HL == 1 || k == n) ? 2 * (n - k) : 6 + 8 * (n - k)), wk = (size_t)w + 2 * (n - k);
-        const int ot = out_terms_of(m, k - 1, o);
+        const int ot = L.out_terms;
         const bool fused = ot == 9;   // partial G planes of the fused last layer
         const size_t bpe = (ot >= 1 && ot <= 3) ? 2 * (size_t)ot : 4;   // bytes per activation element of layer k's output
-        const size_t px_bytes = fused ? (size_t)fused_halves(T, m->layers[k - 1].nin, m->layers[k - 1].nout) * 9 * 4 : m->layers[k - 1].nout * bpe;
-        const size_t wk_mem = (planar_between(m, k - 1, o) || (fused && T == 0 && gather_in_producer(m, o))) ? ((wk + 31) & ~(size_t)31) : wk;   // planar rows (and the tap planes a PROG launch gathers itself) start on 128-byte lines
+        const size_t px_bytes = fused ? (size_t)L.halves * 9 * 4 : m->layers[k - 1].nout * bpe;
+        const size_t wk_mem = (L.planar_out || (fused && chain.prog_gather)) ? ((wk + 31) & ~(size_t)31) : wk;   // planar rows (and the tap planes a PROG launch gathers itself) start on 128-byte lines
         need[(k - 1) & 1] = std::max(need[(k - 1) & 1], hk * wk_mem * px_bytes);
     }
 }
@@ -258,9 +226,10 @@ int plan_rows(const w2xc_model *m, const w2xc_opts &o_in, int w, int vh, int vy0
     const int n = (int)m->layers.size();
     if (n == 0) return fail(W2XC_ERR_ARG, "model has no layers");
     P.o = o_in;
+    P.chain = resolve_chain(m, P.o);
     P.n = n; P.w = w; P.plane_h = plane_h; P.all_out = all_out;
     P.HL = 1;
-    if (uses_wino4(m, P.o)) {
+    if (P.chain.any_wino4) {
         const int hs = 4 * n;
         if (plane_h > 0 && vy0 <= std::max(0, ra - hs) && vy0 + vh >= std::min(plane_h, rb + hs)) P.HL = 4;
         else if (P.o.kernel == W2XC_KERNEL_AUTO)   // a view with n halo rows only: no silent change of kernel (and rounding) -- the caller decides
@@ -272,7 +241,7 @@ int plan_rows(const w2xc_model *m, const w2xc_opts &o_in, int w, int vh, int vy0
     const bool head = m->has_head();
     if (head) {   // (the entry points that run a head model: every other one has refused it -- refuse_head)
         const HostLayer &hd = m->layers[n - 1];
-        if (split_terms(P.o) != 0) return fail(W2XC_ERR_UNSUPPORTED, "16-bit precision modes: not available for a model with an upconv head (W2XC_PRECISION_FP32 only)");
+        if (P.chain.T != 0) return fail(W2XC_ERR_UNSUPPORTED, "16-bit precision modes: not available for a model with an upconv head (W2XC_PRECISION_FP32 only)");
         if (n < 2) return fail(W2XC_ERR_UNSUPPORTED, "an upconv head needs at least one 3x3 layer in front of it");
         if (!w2xc_upconv_supported(hd.nin, hd.nout))
             return fail(W2XC_ERR_UNSUPPORTED, "upconv head %d->%d: the head kernel takes 32, 64, 128 or 256 planes (fewer than 32 are zero-padded) and gives 1 or 3", hd.decl_nin(), hd.decl_nout());
@@ -282,18 +251,17 @@ int plan_rows(const w2xc_model *m, const w2xc_opts &o_in, int w, int vh, int vy0
     for (int l = 1; l < n; l++)
         if (m->layers[l].decl_nin() != m->layers[l - 1].decl_nout())   // (what the model declares: a head model's zero padding would hide 16 against 20)
             return fail(W2XC_ERR_PLANES, "Error : Model-filter : \nnumber of input planes mismatch.\n%d,%d", m->layers[l - 1].decl_nout(), m->layers[l].decl_nin());
-    P.T = split_terms(P.o);
-    if (P.o.precision != W2XC_PRECISION_FP32 && P.T == 0) return fail(W2XC_ERR_ARG, "unknown precision %d", P.o.precision);
+    if (P.o.precision != W2XC_PRECISION_FP32 && P.chain.T == 0) return fail(W2XC_ERR_ARG, "unknown precision %d", P.o.precision);
     if (P.o.fusion < W2XC_FUSION_AUTO || P.o.fusion > W2XC_FUSION_PROG) return fail(W2XC_ERR_ARG, "unknown w2xc_opts.fusion %d", P.o.fusion);
-    if (P.T > 0)
+    if (P.chain.T > 0)
         for (int l = 0; l < n; l++)
-            if (layer_kind(m, l, P.o) == W2XC_K_DIRECT)
+            if (P.chain.layer[l].kind == W2XC_K_DIRECT)
                 return fail(W2XC_ERR_UNSUPPORTED, "16-bit precision modes: layer %d (%d->%d) has no kernel ({1,3}->{32,64,128} first, {32,64,128}->{32,64,128}, ->{1,3} last only)",
                             l + 1, m->layers[l].nin, m->layers[l].nout);
     // conv3x3_first2_wino4 addresses its 32 output planes with 32-bit lane offsets (12 plane strides + a row): planes of at most 64 Mi floats.
     // A plane too wide for that even in the shortest band: W2XC_FUSION_AUTO runs the first two layers unfused, an explicit request is refused.
     size_t first2_max_rows = 0, first2_halo = 0;
-    if (fuse_first_fp32(m, P.o)) {
+    if (P.chain.fused_first && P.chain.T == 0) {
         const size_t wk = ((size_t)w + 2 * (n - 2) + 31) & ~(size_t)31;
         first2_max_rows = ((size_t)64 << 20) / wk;
         first2_halo = P.HL == 1 ? 2 * (size_t)(n - 2) : 6 + 8 * (size_t)(n - 2);
@@ -301,12 +269,13 @@ int plan_rows(const w2xc_model *m, const w2xc_opts &o_in, int w, int vh, int vy0
             if (P.o.fusion != W2XC_FUSION_AUTO)
                 return fail(W2XC_ERR_UNSUPPORTED, "plane too wide (%d pixels) for the fused first layers; use w2xc_opts.fusion = W2XC_FUSION_AUTO, _LAST or _OFF", w);
             P.o.fusion = W2XC_FUSION_LAST;
+            P.chain = resolve_chain(m, P.o);   // (the options changed: the one place in a call where the chain is resolved a second time)
             first2_max_rows = 0;
         }
     }
     // the last layer stores straight into the caller's planar plane(s) when its kernel can address planar
     // output (conv3x3_last / conv3x3_direct); otherwise it goes through the NHWC workspace + a repack
-    P.last_kind = layer_kind(m, n - 1, P.o);
+    P.last_kind = P.chain.layer[n - 1].kind;
     P.last_direct = head || ((m->layers[n - 1].nout == 1 || all_out) &&
                     (P.last_kind == W2XC_K_LAST || P.last_kind == W2XC_K_LAST_GATHER || P.last_kind == W2XC_K_DIRECT ||
                      (m->layers[n - 1].nout == 1 && P.last_kind != W2XC_K_MFMA && P.last_kind != W2XC_K_FIRST)));
@@ -352,9 +321,9 @@ int plan_rows(const w2xc_model *m, const w2xc_opts &o_in, int w, int vh, int vy0
 W2xcKernelKind layer_desc(const w2xc_model *m, const RowPlan &P, int k, int y0, int y1, int up, const LayerSrc &src, const LayerDst &dst,
                           W2xcConvDesc &first_d, W2xcConvDesc *dp, LayerSrc *next)
 {
-    const w2xc_opts &o = P.o;
-    const int n = P.n, T = P.T;
+    const int n = P.n, T = P.chain.T;
     const HostLayer &hl = m->layers[k - 1];
+    const LayerPick &L = P.chain.layer[k - 1];
     W2xcConvDesc &d = *dp;
     memset(&d, 0, sizeof d);
     d.in = src.p; d.in_rs = src.rs; d.in_ps = src.ps; d.in_cs = src.cs;
@@ -365,9 +334,9 @@ W2xcKernelKind layer_desc(const w2xc_model *m, const RowPlan &P, int k, int y0, 
     d.out_w = P.w + 2 * (n - k);
     d.off_y = Tk - 1 - src.top;   // (k = 1: y0 - n - vy0; k > 1: 0 on the one-row-per-layer geometry)
     d.off_x = k == 1 ? -n : 0;
-    // this launch's first output row in the coordinates of the whole plane, modulo the Winograd block height (2; conv3x3_wino4: 4)
-    const W2xcKernelKind kind = layer_kind(m, k - 1, o);
-    d.wino_py = Tk & (((pick_kind(m, k - 1) == W2XC_K_MFMA && layer_mid_variant(m, k - 1, o) == MID_WINO4) || kind == W2XC_K_FIRST2_WINO4) ? 3 : 1);
+    // this launch's first output row in the coordinates of the whole plane, modulo the Winograd block height (2; conv3x3_wino4: 4) -- read by the Winograd kernels only
+    const W2xcKernelKind kind = L.kind;
+    d.wino_py = Tk & ((L.midv == MID_WINO4 || kind == W2XC_K_FIRST2_WINO4) ? 3 : 1);
     d.in_shift = k == 1 ? up : 0;
     *next = src;
     next->top = Tk;
@@ -383,7 +352,7 @@ W2xcKernelKind layer_desc(const w2xc_model *m, const RowPlan &P, int k, int y0, 
         if (kind == W2XC_K_FIRST2_WINO4) { d.off_y += first_d.off_y; d.off_x += first_d.off_x; }
         else { d.off_y = first_d.off_y; d.off_x = first_d.off_x; }
     }
-    d.out_terms = out_terms_of(m, k - 1, o);
+    d.out_terms = L.out_terms;
     d.in_ts = src.ts; d.in_gs = src.gs;   // (0 unless src holds term planes or the partial planes of a fused last layer; fp32: only that one uses the term fields)
     if (kind == W2XC_K_LAST_GATHER) d.halves = src.halves;
     if (T == 0 && kind == W2XC_K_LAST_GATHER) {
@@ -394,7 +363,7 @@ W2xcKernelKind layer_desc(const w2xc_model *m, const RowPlan &P, int k, int y0, 
     const int split_grp = T > 0 ? 16 : 0;   // channel-group size of the blocked term planes
     if (T > 0) {
         d.terms = (kind == W2XC_K_MID_SPLIT || kind == W2XC_K_FIRST2_SPLIT) ? T : 0;
-        d.fmt = split_fmt(o);
+        d.fmt = P.chain.fmt;
         d.out_ts = (long long)d.out_h * d.out_w * hl.nout;
         d.out_gs = (long long)d.out_h * d.out_w * split_grp;
     }
@@ -404,22 +373,15 @@ W2xcKernelKind layer_desc(const w2xc_model *m, const RowPlan &P, int k, int y0, 
     } else {
         d.out = dst.ws[(k - 1) & 1];
         d.out_rs = (long long)d.out_w * hl.nout; d.out_ps = hl.nout; d.out_cs = 1;
-        if (planar_between(m, k - 1, o)) {
-            // planes of out_h rows of roundup32(out_w) floats: conv3x3_wino4 reads 16-byte pixel quads, and a tile's 32-pixel row segment
-            // (tiles start at multiples of 32 pixels) is then ONE 128-byte line -- with rows of roundup4(w) floats every segment straddled two
-            // lines, each written in two pieces by different workgroups (the 32 -> 32 layer in front: 2.0 ms instead of 0.8, measured)
+        if (L.planar_out) {   // planes of out_h rows of roundup32(out_w) floats (resolve_chain, pass 7: why 32)
             d.out_rs = (d.out_w + 31) & ~31; d.out_ps = 1; d.out_cs = d.out_rs * (long long)d.out_h;
         }
         if (T > 0 && d.out_terms >= 1 && d.out_terms <= 3) { d.out_rs = (long long)d.out_w * split_grp; d.out_ps = split_grp; }
-        if (d.out_terms == 9) {   // G[half][tap][y][x]
-            // (where the producing launch finishes the last layer itself -- conv3x3_wino4 PROG --, rows start on 128-byte lines: a tile's 32-pixel row
-            //  segment of a tap plane is then exactly ONE line, written whole, and a gather job never pulls a line into its XCD's L2 that holds
-            //  columns of a tile it does not depend on -- with rows of out_w floats such a line, cached before its last columns were written, was
-            //  served stale to the neighbouring job later: intermittent mismatches on small planes)
-            d.out_rs = (T == 0 && gather_in_producer(m, o)) ? ((d.out_w + 31) & ~31) : d.out_w; d.out_ps = 1;
+        if (d.out_terms == 9) {   // G[half][tap][y][x]; rows on 128-byte lines where the producing launch finishes the last layer itself (resolve_chain, pass 8: why)
+            d.out_rs = P.chain.prog_gather ? ((d.out_w + 31) & ~31) : d.out_w; d.out_ps = 1;
             d.out_gs = (long long)d.out_h * d.out_rs;
             d.out_ts = 9 * d.out_gs;
-            d.halves = fused_halves(T, hl.nin, hl.nout);   // (fp32: conv3x3_wino4 writes planar partial planes G[64-plane block][tap][y][x]: its epilogue sums the four plane tiles of a block on chip)
+            d.halves = L.halves;
         }
     }
     next->p = d.out; next->rs = d.out_rs; next->ps = d.out_ps; next->cs = d.out_cs; next->ts = d.out_ts; next->gs = d.out_gs;
@@ -443,19 +405,19 @@ W2xcKernelKind layer_desc(const w2xc_model *m, const RowPlan &P, int k, int y0, 
 namespace {
 bool batch_chain_planes(const w2xc_model *m, const RowPlan &P)
 {
-    const w2xc_opts &o = P.o;
+    const std::vector<LayerPick> &L = P.chain.layer;
     const int n = P.n;
     if (n < 2 || !P.all_out || !P.last_direct) return false;
     if (m->layers[0].nin != 3 || m->layers[n - 1].nout != 3) return false;
     const bool head = m->has_head();
-    if (layer_kind(m, 0, o) != W2XC_K_FIRST || layer_kind(m, n - 1, o) != (head ? W2XC_K_UPCONV : W2XC_K_LAST) || out_terms_of(m, 0, o) != 0) return false;
+    if (L[0].kind != W2XC_K_FIRST || L[n - 1].kind != (head ? W2XC_K_UPCONV : W2XC_K_LAST) || L[0].out_terms != 0) return false;
     if (head && !w2xc_upconv_supported(m->layers[n - 1].nin, m->layers[n - 1].nout)) return false;
-    if (planar_between(m, n - 2, o)) return false;   // (conv3x3_last and upconv4x4_head read NHWC pixels)
+    if (L[n - 2].planar_out) return false;   // (conv3x3_last and upconv4x4_head read NHWC pixels)
     for (int l = 1; l <= n - 2; l++) {
         const HostLayer &hl = m->layers[l];
-        if (layer_kind(m, l, o) != W2XC_K_MFMA || out_terms_of(m, l, o) != 0) return false;
-        const bool in_planar = planar_between(m, l - 1, o), out_planar = planar_between(m, l, o);
-        switch (layer_mid_variant(m, l, o)) {
+        if (L[l].kind != W2XC_K_MFMA || L[l].out_terms != 0) return false;
+        const bool in_planar = L[l - 1].planar_out, out_planar = L[l].planar_out;
+        switch (L[l].midv) {
         case MID_WINO4:
             if (in_planar && out_planar ? !w2xc_wino4_batch_supported(hl.nin, hl.nout, false) : !w2xc_wino4_batch_layout_supported(hl.nin, hl.nout, !in_planar, out_planar))
                 return false;
@@ -473,18 +435,19 @@ bool batch_chain_planes(const w2xc_model *m, const RowPlan &P)
 bool batch_eligible(const w2xc_model *m, const RowPlan &P)
 {
     const w2xc_opts &o = P.o;
+    const std::vector<LayerPick> &L = P.chain.layer;
     const int n = P.n;
-    if (P.T != 0 || o.precision != W2XC_PRECISION_FP32 || o.kernel != W2XC_KERNEL_AUTO || o.fusion == W2XC_FUSION_PROG) return false;
+    if (P.chain.T != 0 || o.precision != W2XC_PRECISION_FP32 || o.kernel != W2XC_KERNEL_AUTO || o.fusion == W2XC_FUSION_PROG) return false;
     if (P.band < P.plane_h || P.plane_h <= 0) return false;
     if (batch_chain_planes(m, P)) return true;
     if (n < 5 || P.HL != 4 || P.all_out || !P.last_direct) return false;
     if (m->layers[0].nin != 1 || m->layers[n - 1].nout != 1) return false;
-    if (layer_kind(m, 0, o) != W2XC_K_FUSED_AWAY || layer_kind(m, 1, o) != W2XC_K_FIRST2_WINO4) return false;
-    if (layer_kind(m, n - 1, o) != W2XC_K_LAST_GATHER || out_terms_of(m, n - 2, o) != 9) return false;
+    if (L[0].kind != W2XC_K_FUSED_AWAY || L[1].kind != W2XC_K_FIRST2_WINO4) return false;
+    if (L[n - 1].kind != W2XC_K_LAST_GATHER || L[n - 2].out_terms != 9) return false;
     for (int l = 2; l <= n - 2; l++) {
         const HostLayer &hl = m->layers[l];
-        if (layer_kind(m, l, o) != W2XC_K_MFMA || !is_wino4_layer(m, l, o) || !planar_between(m, l - 1, o)) return false;
-        if (l < n - 2 && (!planar_between(m, l, o) || out_terms_of(m, l, o) != 0)) return false;
+        if (L[l].kind != W2XC_K_MFMA || !L[l].wino4 || !L[l - 1].planar_out) return false;
+        if (l < n - 2 && (!L[l].planar_out || L[l].out_terms != 0)) return false;
         if (!w2xc_wino4_batch_supported(hl.nin, hl.nout, l == n - 2)) return false;
     }
     return true;
