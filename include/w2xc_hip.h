@@ -863,6 +863,51 @@ int w2xc_yuv16_to_rgb_device(const w2xc_yuv16_planes *d_src, int n, int w, int h
 int w2xc_rgb_to_yuv16_device(const float *d_rgb, size_t image_stride_bytes, size_t plane_stride_bytes, int n, int w, int h, int chroma, int range, int depth,
                              int matrix, const w2xc_yuv16_planes *d_dst, void *hip_stream);
 
+/* ---- Chroma siting (revision 0.4.1.10) ----------------------------------------------------------------
+ * The three sections above treat a chroma sample as CENTRED on its block of luma samples (JPEG / MPEG-1).  Most decoded video is not: 4:2:0 from MPEG-2, H.264
+ * and HEVC is co-sited with the LEFT luma column, BT.2020 / UHD material with the TOP-LEFT luma sample, 4:2:2 with the left column almost everywhere (y4m:
+ * C420mpeg2 against C420jpeg).  Two flag bits or-ed onto the layout value say so, per axis; no frame call gains an argument:
+ *   W2XC_CHROMA_COSITED_X  along x chroma sample k sits ON luma column 2k         W2XC_CHROMA_COSITED_Y  along y chroma sample k sits ON luma row 2k
+ *   W2XC_YUV_420_LEFT, W2XC_YUV_420_TOPLEFT, W2XC_YUV_422_LEFT: the three combinations in use.
+ * The layout is chroma & 0xF, the flags chroma & 0x30; chroma sizes do not depend on the flags.  One siting applies to both sides of a call.
+ * Accepted by all eight frame calls (w2xc_process_frames_yuv_u8[_rgb][_device], w2xc_process_frames_yuv_u16[_rgb][_device]) and by the four ends of the RGB
+ * route (w2xc_yuv8_to_rgb_device, w2xc_rgb_to_yuv8_device, w2xc_yuv16_to_rgb_device, w2xc_rgb_to_yuv16_device).  Refused as W2XC_ERR_ARG, before a device is
+ * touched: a negative value, any other bit, a layout outside 0 .. 3, and a flag on an axis the layout does not subsample -- any flag with W2XC_YUV_444 or
+ * W2XC_YUV_400, W2XC_CHROMA_COSITED_Y with W2XC_YUV_422.  With no flag every call gives, byte for byte, what it gave before this revision.
+ * The arithmetic, per axis; an axis that is centred or not subsampled is exactly what the sections above define.  Single fp32 operations in the order written
+ * (-ffp-contract=off), for bytes and for words of any depth alike:
+ *   Y route, the bicubic 2x of chroma on a co-sited axis: the luma 2x is pixel-centred, output luma X sits at source luma (X + 0.5) / 2 - 0.5; source chroma k sits on
+ *              source luma 2k, output chroma m on output luma 2m, which is source chroma coordinate m / 2 - 0.125.  So sx = floor(m / 2 - 0.125) and t = 0.375 for odd
+ *              m, 0.875 for even m; the taps are sx - 1 .. sx + 2, clamped, the coefficients cubic_coeffs(t), the tap sum that of the centred enlargement --
+ *              horizontally, then vertically --, then its rounding.  Outputs 2q - 1 and 2q share sx = q - 1: the centred enlargement with (0.25, 0.75) replaced
+ *              by (0.375, 0.875) on that axis and nothing else -- not the clamping, the crop to the leading (2 w + 1) / 2 samples, nor column 0.  iterations = 0:
+ *              the samples are copied, as before.
+ *   RGB route, chroma at luma resolution on a co-sited axis: luma index x reads j = x >> 1; even x: C[j]; odd x: 0.5f * C[j] + 0.5f * C[min(j + 1, last)] -- both
+ *              exact in fp32 at every depth.  Horizontally first, then vertically on the row results.
+ *   RGB route, from R, G, B, on a co-sited axis: chroma sample k is the 1-2-1 mean around luma 2k: with l = P[max(2k - 1, 0)], m = P[2k], r = P[min(2k + 1, last)] of
+ *              cb (and of cr), (l + r) * 0.25f + m * 0.5f -- the sum, two exact scalings, one sum.  Horizontally first, on every luma row the vertical step needs
+ *              (a centred subsampled x axis: (a + b) * 0.5f of the block's two columns, the last replicated at an odd edge); then a co-sited y axis applies the
+ *              same expression to rows 2k - 1, 2k, 2k + 1 (clamped), a centred subsampled y axis (top + bottom) * 0.5f to the block's two rows, an odd edge
+ *              replicating the last row, and an axis not subsampled passes through.  Both axes centred: the box mean ((a + b) + (c + d)) * 0.25f, unchanged.
+ *              The roundings to bytes and words are unchanged.
+ * The frame calls stay DEFINED as their composed routes of public calls, the same `chroma` value handed to both ends; the Y route uses
+ * w2xc_chroma2x_u8_sited_device / w2xc_chroma2x_u16_sited_device per chroma plane, with the flags.  Those two are this revision's only new entry points (their
+ * presence marks it; w2xc_opts and w2xc_version() are unchanged): w2xc_chroma2x_u8_device / _u16_device with `cosited` behind `oh` -- any combination of the two
+ * flag bits, anything else W2XC_ERR_ARG; cosited = 0 is the centred block, byte for byte.
+ * Left out: per-plane sitings (PAL-DV 4:2:0, whose Cb and Cr sit on different lines), different sitings on the two sides of a call, TTA, the shrink, more than one
+ * 2x step. */
+#define W2XC_CHROMA_COSITED_X 0x10   /* along x a chroma sample sits ON luma column 2k (left-sited)   */
+#define W2XC_CHROMA_COSITED_Y 0x20   /* along y a chroma sample sits ON luma row 2k (top-sited)        */
+#define W2XC_YUV_420_LEFT    (W2XC_YUV_420 | W2XC_CHROMA_COSITED_X)                         /* MPEG-2, H.264, HEVC default */
+#define W2XC_YUV_420_TOPLEFT (W2XC_YUV_420 | W2XC_CHROMA_COSITED_X | W2XC_CHROMA_COSITED_Y) /* BT.2020 / UHD               */
+#define W2XC_YUV_422_LEFT    (W2XC_YUV_422 | W2XC_CHROMA_COSITED_X)
+int w2xc_chroma2x_u8_sited_device(const unsigned char *d_src, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int cw, int ch,
+                                  unsigned char *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int ow, int oh, int cosited,
+                                  void *hip_stream);
+int w2xc_chroma2x_u16_sited_device(const unsigned short *d_src, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int src_pack, int cw,
+                                   int ch, int depth, unsigned short *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int dst_pack,
+                                   int ow, int oh, int cosited, void *hip_stream);
+
 /* the building blocks on contiguous float planes (device pointers): main.cpp:144 on one plane, :75-76, :171-172 */
 int w2xc_resize2x_cubic_device(const float *d_src, int w, int h, float *d_dst, void *hip_stream);
 /* main.cpp:158-167 on one plane (revision 0.4.1.4): cv::resize(Size(dw, dh), INTER_LINEAR) of the contiguous sw x sh plane d_src into the contiguous

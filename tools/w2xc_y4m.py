@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/w2xc_y4m.py in.y4m out.y4m -m noise|scale|noise_scale --model_dir DIR [--noise_level N] [--range full|limited] [--matrix bt601|bt709|bt2020]
-                     [--frames_per_call N]
+                     [--frames_per_call N] [--siting center|left|topleft|auto]
 
 An 8-bit YUV4MPEG2 stream through the YUV frame calls.  The route follows the loaded models, as in tools/w2xc_cli.py.  Y models (one plane in, one out) go
 through w2xc_process_frames_yuv_u8: luma through the models, chroma enlarged on bytes -- no RGB image, no colour matrix; --matrix is ignored.  Models whose
@@ -8,7 +8,11 @@ first layer takes three planes -- three-plane models and the upconv_7 schema, wh
 w2xc_process_frames_yuv_u8_rgb, by the colour matrix --matrix (default: bt709 for streams of 720 rows and more, bt601 below); a Cmono stream has no colour
 to convert and is refused with such models.
 The reader and the writer are pure Python (numpy for the planes): colour spaces C420* (C420, C420jpeg, C420mpeg2, C420paldv: all of them
-(w + 1) / 2 x (h + 1) / 2 chroma; the siting is not corrected, include/w2xc_hip.h), C422, C444 and Cmono; no C tag means C420jpeg, as the format says.
+(w + 1) / 2 x (h + 1) / 2 chroma), C422, C444 and Cmono; no C tag means C420jpeg, as the format says.
+--siting says where a chroma sample sits (include/w2xc_hip.h, "Chroma siting"): center (the default: JPEG / MPEG-1, whatever the C tag says), left (on the left
+luma column: MPEG-2, H.264, HEVC), topleft (on the top-left luma sample: BT.2020 / UHD) -- on the axes the stream's layout subsamples --, or auto, by the C
+tag: C420mpeg2 and C422 are left, C420jpeg, C420, no tag and the deeper CxxxpD forms center, and C420paldv is refused: its Cb and Cr sit on different lines,
+which no call here corrects.  The C tag is passed on unchanged.
 The range is the stream's XCOLORRANGE=FULL|LIMITED where present, otherwise --range (default limited).  Frames go through the host call in groups of
 --frames_per_call.  With a scale step the W and H fields are doubled; F (the frame rate) and A (the pixel aspect) are those of the input -- twice the samples
 in both directions change neither --, every other header field is passed on as it is.  Interlaced streams (I other than p / ?) are refused: fields would have
@@ -33,6 +37,12 @@ MATRICES = {"bt601": 0, "bt709": 1, "bt2020": 2}   # (the values of w2xc_amd.MAT
 MONO_RGB = "Cmono stream with models that take R, G and B: a grey frame has no colour to convert -- use Y models (one plane in, one plane out)"
 
 
+# --siting: the flags or-ed onto the layout (the values of w2xc_amd.CHROMA_COSITED_X / _Y)
+COSITED_X, COSITED_Y = 0x10, 0x20
+SITINGS = ("center", "left", "topleft", "auto")
+PALDV = "C420paldv with --siting auto: its Cb and Cr samples sit on different lines, which no call corrects -- name a siting (center, left or topleft)"
+
+
 INTERLACED = "interlaced stream (I%s): not supported -- its fields would have to be enlarged separately; deinterlace first"
 
 
@@ -48,6 +58,22 @@ def layout_of(tag):
     if tag in ("422", "444", "mono"):
         return LAYOUTS[tag]
     raise Y4mError("unsupported colour space C%s (8-bit C420*, C422, C444 and Cmono only; 9- to 16-bit streams: tools/w2xc_y4m16.py)" % tag)
+
+
+def siting_flags(siting, tag, layout):
+    """the siting flags of a stream: --siting, the C tag's value (None: no tag) and its layout -> COSITED_X | COSITED_Y, only on the axes the layout subsamples"""
+    if siting == "auto":
+        if tag == "420paldv":
+            raise Y4mError(PALDV)
+        siting = "left" if tag in ("420mpeg2", "422") else "center"
+    if siting not in SITINGS:
+        raise Y4mError("unknown siting %r" % (siting,))
+    flags = 0
+    if siting in ("left", "topleft") and layout in (LAYOUTS["420"], LAYOUTS["422"]):
+        flags |= COSITED_X
+    if siting == "topleft" and layout == LAYOUTS["420"]:
+        flags |= COSITED_Y
+    return flags
 
 
 def chroma_size(w, h, layout):
@@ -200,6 +226,8 @@ def build_parser(description="8-bit YUV4MPEG2 streams through waifu2x models on 
     ap.add_argument("--matrix", default=None, choices=sorted(MATRICES),
                     help="colour matrix for RGB and upconv models (default: bt709 when H >= 720, else bt601); Y models use no matrix and ignore it")
     ap.add_argument("--frames_per_call", type=int, default=8)
+    ap.add_argument("--siting", default="center", choices=list(SITINGS),
+                    help="where a chroma sample sits: center (JPEG / MPEG-1), left (MPEG-2, H.264, HEVC), topleft (BT.2020 / UHD), or auto: by the C tag")
     return ap
 
 
@@ -223,7 +251,7 @@ def convert_stream(fin, fout, process, iterations, default_range="limited", fram
 
 def run_tool(name, args, layout_of_header, make_process, dtype=np.uint8):
     """what both tools do with their parsed arguments: check the stream, load the models, route by their kind, convert.  make_process(w2xc, hdr, noise, scale,
-    iterations, route, matrix) -> the process callback of convert_stream"""
+    iterations, route, matrix, flags) -> the process callback of convert_stream; flags = the siting flags the frame call gets or-ed onto the layout"""
     try:
         with open(args.input, "rb") as fin:
             # what the stream itself rules out, before a model is loaded or the output file is created
@@ -231,6 +259,7 @@ def run_tool(name, args, layout_of_header, make_process, dtype=np.uint8):
             if hdr.interlaced:
                 raise Y4mError(INTERLACED % hdr.get("I"))
             layout, _ = layout_of_header(hdr), hdr.colour_range()
+            flags = siting_flags(args.siting, hdr.get("C"), layout)
             fin.seek(0)
             import __graft_entry__ as graft
             w2xc = graft.load_package()
@@ -243,7 +272,7 @@ def run_tool(name, args, layout_of_header, make_process, dtype=np.uint8):
             route = model_route(noise.planes(0)[0] if noise else None, scale.planes(0)[0] if scale else None)
             check_route(route, layout)
             matrix = MATRICES[args.matrix or default_matrix(hdr.h)]
-            process = make_process(w2xc, hdr, noise, scale, iterations, route, matrix)
+            process = make_process(w2xc, hdr, noise, scale, iterations, route, matrix, flags)
             with open(args.output, "wb") as fout:
                 n = convert_stream(fin, fout, process, iterations, args.range, args.frames_per_call, layout_of_header, dtype)
     except Y4mError as e:
@@ -254,12 +283,12 @@ def run_tool(name, args, layout_of_header, make_process, dtype=np.uint8):
 
 
 def main(argv=None):
-    def make_process(w2xc, hdr, noise, scale, iterations, route, matrix):
+    def make_process(w2xc, hdr, noise, scale, iterations, route, matrix, flags):
         def process(y, u, v, layout, full):
             rng = w2xc.RANGE_FULL if full else w2xc.RANGE_LIMITED
             if route == "rgb":
-                return w2xc.process_frames_yuv_u8_rgb(y, u, v, chroma=layout, noise=noise, scale=scale, iterations=iterations, range=rng, matrix=matrix)
-            out = w2xc.process_frames_yuv_u8(y, u, v, chroma=layout, noise=noise, scale=scale, iterations=iterations, range=rng)
+                return w2xc.process_frames_yuv_u8_rgb(y, u, v, chroma=layout | flags, noise=noise, scale=scale, iterations=iterations, range=rng, matrix=matrix)
+            out = w2xc.process_frames_yuv_u8(y, u, v, chroma=layout | flags, noise=noise, scale=scale, iterations=iterations, range=rng)
             return out if len(out) == 3 else (out[0], None, None)
         return process
     return run_tool("w2xc_y4m", build_parser().parse_args(argv), lambda hdr: hdr.layout, make_process)

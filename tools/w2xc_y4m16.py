@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """tools/w2xc_y4m16.py in.y4m out.y4m -m noise|scale|noise_scale --model_dir DIR [--noise_level N] [--range full|limited] [--matrix bt601|bt709|bt2020]
-                       [--frames_per_call N]
+                       [--frames_per_call N] [--siting center|left|topleft|auto]
 
 A YUV4MPEG2 stream of 9- to 16-bit samples through the 16-bit YUV frame calls (include/w2xc_hip.h, "16-bit YUV frames"): colour spaces C420pD, C422pD and
 C444pD with D in 9, 10, 12, 14, 16, and CmonoD.  Samples are little-endian 16-bit words with the value in the low bits (W2XC_PACK_LOW), as the format has them.
 The header, line and stream code, the options and the routing by the loaded models are those of tools/w2xc_y4m.py: Y models go through
 w2xc_process_frames_yuv_u16, models whose first layer takes three planes through w2xc_process_frames_yuv_u16_rgb by --matrix.  8-bit streams belong to
-tools/w2xc_y4m.py and are refused here.
+tools/w2xc_y4m.py and are refused here.  --siting is that tool's: center (the default), left, topleft, or auto -- the CxxxpD tags name no siting, so auto is
+center here.
 """
 import os
 import re
@@ -64,12 +65,12 @@ def convert_stream(fin, fout, process, iterations, default_range="limited", fram
 
 
 def main(argv=None):
-    def make_process(w2xc, hdr, noise, scale, iterations, route, matrix):
+    def make_process(w2xc, hdr, noise, scale, iterations, route, matrix, flags):
         depth = header_format(hdr)[1]
 
         def process(y, u, v, layout, full):
             rng = w2xc.RANGE_FULL if full else w2xc.RANGE_LIMITED
-            kw = dict(chroma=layout, noise=noise, scale=scale, iterations=iterations, range=rng, depth=depth, pack=w2xc.PACK_LOW)
+            kw = dict(chroma=layout | flags, noise=noise, scale=scale, iterations=iterations, range=rng, depth=depth, pack=w2xc.PACK_LOW)
             y, u, v = (None if a is None else a.astype(np.uint16, copy=False) for a in (y, u, v))
             if route == "rgb":
                 return w2xc.process_frames_yuv_u16_rgb(y, u, v, matrix=matrix, **kw)

@@ -32,6 +32,9 @@ PRECISION_FP32, PRECISION_BF16, PRECISION_BF16X2, PRECISION_BF16X3, PRECISION_FP
 KERNEL_AUTO, KERNEL_DIRECT, KERNEL_MFMA, KERNEL_WINOGRAD, KERNEL_WINOGRAD32, KERNEL_WINOGRAD4 = 0, 1, 2, 3, 4, 5
 FUSION_AUTO, FUSION_OFF, FUSION_ON, FUSION_FIRST, FUSION_LAST, FUSION_GATHER_LAUNCH, FUSION_PROG = 0, 1, 2, 3, 4, 5, 6
 YUV_420, YUV_422, YUV_444, YUV_400 = 0, 1, 2, 3
+# chroma siting ("Chroma siting", include/w2xc_hip.h): flags or-ed onto a layout -- along x / y a chroma sample sits ON luma column / row 2k
+CHROMA_COSITED_X, CHROMA_COSITED_Y = 0x10, 0x20
+YUV_420_LEFT, YUV_420_TOPLEFT, YUV_422_LEFT = YUV_420 | CHROMA_COSITED_X, YUV_420 | CHROMA_COSITED_X | CHROMA_COSITED_Y, YUV_422 | CHROMA_COSITED_X
 RANGE_FULL, RANGE_LIMITED = 0, 1
 MATRIX_BT601, MATRIX_BT709, MATRIX_BT2020 = 0, 1, 2
 PACK_LOW, PACK_HIGH = 0, 1
@@ -162,9 +165,11 @@ def _load():
         "w2xc_y16_to_plane_device": (ci, [fp, ci, cs, cs, ci, ci, ci, ci, ci, fp, cs, vp]),
         "w2xc_plane_to_y16_device": (ci, [fp, ci, cs, ci, ci, ci, ci, ci, fp, cs, cs, vp]),
         "w2xc_chroma2x_u16_device": (ci, [fp, ci, cs, cs, ci, ci, ci, ci, ci, fp, cs, cs, ci, ci, ci, ci, vp]),
+        "w2xc_chroma2x_u16_sited_device": (ci, [fp, ci, cs, cs, ci, ci, ci, ci, ci, fp, cs, cs, ci, ci, ci, ci, ci, vp]),
         "w2xc_y8_to_plane_device": (ci, [fp, ci, cs, cs, ci, ci, ci, fp, cs, vp]),
         "w2xc_plane_to_y8_device": (ci, [fp, ci, cs, ci, ci, ci, fp, cs, cs, vp]),
         "w2xc_chroma2x_u8_device": (ci, [fp, ci, cs, cs, ci, ci, ci, fp, cs, cs, ci, ci, ci, vp]),
+        "w2xc_chroma2x_u8_sited_device": (ci, [fp, ci, cs, cs, ci, ci, ci, fp, cs, cs, ci, ci, ci, ci, vp]),
         "w2xc_u8_to_rgb_device": (ci, [fp, cs, ci, ci, fp, fp, fp, vp]),
         "w2xc_rgb_to_u8_device": (ci, [fp, fp, fp, ci, ci, fp, cs, vp]),
         "w2xc_process_image_u8_device": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, vp, C.POINTER(Opts)]),
@@ -1022,7 +1027,9 @@ def bleed_rgba_u8_trim():
 
 # ---- YUV frames: luma through Y models, chroma 2x on bytes (include/w2xc_hip.h, "YUV frames") ----
 def yuv_chroma_size(w, h, chroma):
-    """(cw, ch) of the chroma planes of a w x h frame; (0, 0) for YUV_400"""
+    """(cw, ch) of the chroma planes of a w x h frame; (0, 0) for YUV_400.  The siting flags (CHROMA_COSITED_*) do not change a size: they are masked off"""
+    if isinstance(chroma, int) and chroma >= 0:
+        chroma &= 0xF
     if chroma == YUV_400:
         return 0, 0
     if chroma not in (YUV_420, YUV_422, YUV_444):
@@ -1155,6 +1162,14 @@ def chroma2x_u8_device(d_src, n, src_frame_stride_bytes, src_stride_bytes, src_p
                                         dst_stride_bytes, dst_px, ow, oh, C.c_void_p(stream)))
 
 
+def chroma2x_u8_sited_device(d_src, n, src_frame_stride_bytes, src_stride_bytes, src_px, cw, ch, d_dst, dst_frame_stride_bytes, dst_stride_bytes, dst_px, ow, oh,
+                             cosited, stream=0):
+    """chroma2x_u8_device for chroma co-sited with luma: cosited = CHROMA_COSITED_X | CHROMA_COSITED_Y, any combination; 0 is chroma2x_u8_device, byte for byte
+    (w2xc_chroma2x_u8_sited_device)."""
+    _check(_lib.w2xc_chroma2x_u8_sited_device(C.c_void_p(d_src), n, src_frame_stride_bytes, src_stride_bytes, src_px, cw, ch, C.c_void_p(d_dst),
+                                              dst_frame_stride_bytes, dst_stride_bytes, dst_px, ow, oh, cosited, C.c_void_p(stream)))
+
+
 # ---- 16-bit YUV frames: values of 8 .. 16 bits in uint16 words (include/w2xc_hip.h, "16-bit YUV frames") ----
 def process_frames_yuv_u16(y, u=None, v=None, uv=None, chroma=YUV_420, noise=None, scale=None, iterations=0, range=RANGE_LIMITED, opts=None, out_nv12=None,
                            depth=10, pack=PACK_LOW, out_pack=None):
@@ -1214,3 +1229,11 @@ def chroma2x_u16_device(d_src, n, src_frame_stride_bytes, src_stride_bytes, src_
     dst_px samples apart (w2xc_chroma2x_u16_device); strides in bytes"""
     _check(_lib.w2xc_chroma2x_u16_device(C.c_void_p(d_src), n, src_frame_stride_bytes, src_stride_bytes, src_px, src_pack, cw, ch, depth, C.c_void_p(d_dst),
                                          dst_frame_stride_bytes, dst_stride_bytes, dst_px, dst_pack, ow, oh, C.c_void_p(stream)))
+
+
+def chroma2x_u16_sited_device(d_src, n, src_frame_stride_bytes, src_stride_bytes, src_px, src_pack, cw, ch, depth, d_dst, dst_frame_stride_bytes, dst_stride_bytes,
+                              dst_px, dst_pack, ow, oh, cosited, stream=0):
+    """chroma2x_u16_device for chroma co-sited with luma: cosited = CHROMA_COSITED_X | CHROMA_COSITED_Y, any combination; 0 is chroma2x_u16_device, word for word
+    (w2xc_chroma2x_u16_sited_device)."""
+    _check(_lib.w2xc_chroma2x_u16_sited_device(C.c_void_p(d_src), n, src_frame_stride_bytes, src_stride_bytes, src_px, src_pack, cw, ch, depth, C.c_void_p(d_dst),
+                                               dst_frame_stride_bytes, dst_stride_bytes, dst_px, dst_pack, ow, oh, cosited, C.c_void_p(stream)))

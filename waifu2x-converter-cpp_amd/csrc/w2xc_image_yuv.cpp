@@ -14,6 +14,7 @@ namespace {
 // Luma through the models as the planes of run_batch, chroma from samples to samples in one launch: no colour matrix, no float plane of chroma.
 struct YuvGeom {
     int chroma = W2XC_YUV_400, range = W2XC_RANGE_FULL;   // (defaults: a building block fills in only the format fields its end of a route reads)
+    int cosited = 0;        // W2XC_CHROMA_COSITED_X | _Y: the siting flags of the call's `chroma` ("Chroma siting"); chroma above is the layout alone
     int bps = 1, depth = 8;   // bytes per sample (1: w2xc_yuv_planes, 2: w2xc_yuv16_planes) and the bits of a value
     bool rgb = false;       // the frames go through RGB / head models (w2xc_process_frames_yuv_u8_rgb*): process_yuv_rgb_device
     int matrix = 0;         // ... by this colour matrix (W2XC_MATRIX_*)
@@ -81,10 +82,24 @@ int check_yuv_side(const YuvSide *s, int bps, int n, int w, int h, int cw, int c
     return W2XC_OK;
 }
 
-// the layout and range enums of a frame, and the colour matrix of the calls that have one: what the frame calls and the blocks refuse alike
-int check_chroma_range(int chroma, int range)
+// the siting flags alone (the chroma blocks of the Y route take them as `cosited`): only the two bits, and only on an axis that is subsampled
+int check_cosited(int cosited, bool sub_x, bool sub_y)
 {
-    if (chroma < W2XC_YUV_420 || chroma > W2XC_YUV_400) return fail(W2XC_ERR_ARG, "unknown chroma layout %d", chroma);
+    if (cosited < 0 || (cosited & ~(W2XC_CHROMA_COSITED_X | W2XC_CHROMA_COSITED_Y)))
+        return fail(W2XC_ERR_ARG, "cosited must be a combination of W2XC_CHROMA_COSITED_X and W2XC_CHROMA_COSITED_Y, got %d", cosited);
+    if (((cosited & W2XC_CHROMA_COSITED_X) && !sub_x) || ((cosited & W2XC_CHROMA_COSITED_Y) && !sub_y))
+        return fail(W2XC_ERR_ARG, "chroma siting flags 0x%x name an axis the layout does not subsample", cosited);
+    return W2XC_OK;
+}
+// the layout and range enums of a frame, and the colour matrix of the calls that have one: what the frame calls and the blocks refuse alike
+// `chroma` is a layout with the siting flags or-ed on: *layout = chroma & 0xF, *cosited = chroma & 0x30 -- the ONE place that decodes and refuses them
+int check_chroma_range(int chroma, int range, int *layout, int *cosited)
+{
+    const int flags = W2XC_CHROMA_COSITED_X | W2XC_CHROMA_COSITED_Y;
+    if (chroma < 0 || (chroma & ~(0xF | flags)) || (chroma & 0xF) > W2XC_YUV_400) return fail(W2XC_ERR_ARG, "unknown chroma layout %d", chroma);
+    *layout = chroma & 0xF;
+    *cosited = chroma & flags;
+    if (int rc = check_cosited(*cosited, *layout != W2XC_YUV_444 && *layout != W2XC_YUV_400, *layout == W2XC_YUV_420)) return rc;
     if (range != W2XC_RANGE_FULL && range != W2XC_RANGE_LIMITED) return fail(W2XC_ERR_ARG, "unknown range %d", range);
     return W2XC_OK;
 }
@@ -120,7 +135,7 @@ int check_yuv_call(ImageCall &c, bool rgb, int n, int chroma, int range, int mat
     if (c.iterations < 0 || c.iterations > 1) return fail(W2XC_ERR_ARG, "iterations must be 0 or 1 (got %d)", c.iterations);
     if (n < 1 || n > (1 << 20)) return fail(W2XC_ERR_ARG, "batch of %d frames", n);
     if (c.w <= 0 || c.h <= 0 || c.w > (1 << 22) || c.h > (1 << 22)) return fail(W2XC_ERR_ARG, "bad frame size");
-    if ((rc = check_chroma_range(chroma, range)) || (rc = check_depth(g->bps, g->depth))) return rc;
+    if ((rc = check_chroma_range(chroma, range, &chroma, &g->cosited)) || (rc = check_depth(g->bps, g->depth))) return rc;
     if (rgb && chroma == W2XC_YUV_400)
         return fail(W2XC_ERR_ARG, "a frame without chroma (W2XC_YUV_400) belongs to %s", g->bps == 2 ? "w2xc_process_frames_yuv_u16*" : "w2xc_process_frames_yuv_u8*");
     if (rgb && (rc = check_matrix(matrix))) return rc;
@@ -157,6 +172,9 @@ hipError_t luma_out(const YuvGeom &g, const float *y, long long ps, int w, int h
 // chroma samples to chroma samples: g.cw x g.ch -> the leading g.ocw x g.och of the bicubic 2x, or (no 2x step) as they are.  A null v: one plane per frame
 hipError_t chroma_out(const YuvGeom &g, bool up2x, const YuvSide &in, const YuvSide &out, int n, hipStream_t st)
 {
+    if (up2x && g.cosited)
+        return g.bps == 2 ? w2xc_launch_chroma2x_u16_sited(chroma_words(in), words(in.v), g.cw, g.ch, chroma_words(out), words(out.v), g.ocw, g.och, g.depth, g.cosited, n, st)
+                          : w2xc_launch_chroma2x_u8_sited(chroma_planes(in), in.v, g.cw, g.ch, chroma_planes(out), out.v, g.ocw, g.och, g.cosited, n, st);
     if (g.bps == 2)
         return up2x ? w2xc_launch_chroma2x_u16(chroma_words(in), words(in.v), g.cw, g.ch, chroma_words(out), words(out.v), g.ocw, g.och, g.depth, n, st)
                     : w2xc_launch_chroma_copy_u16(chroma_words(in), words(in.v), g.cw, g.ch, chroma_words(out), words(out.v), g.depth, n, st);
@@ -166,11 +184,17 @@ hipError_t chroma_out(const YuvGeom &g, bool up2x, const YuvSide &in, const YuvS
 // frames of w x h <-> their R, G, B planes (frame i's at rgb + i * is + {0, 1, 2} * ps floats) by g.matrix
 hipError_t to_rgb(const YuvGeom &g, const YuvSide &s, int w, int h, float *rgb, long long is, long long ps, int n, hipStream_t st)
 {
+    if (g.cosited)
+        return g.bps == 2 ? w2xc_launch_yuv16_to_rgb_sited(luma_words(s), chroma_words(s), words(s.v), w, h, g.chroma | g.cosited, g.range, g.matrix, g.depth, rgb, is, ps, n, st)
+                          : w2xc_launch_yuv8_to_rgb_sited(luma_planes(s), chroma_planes(s), s.v, w, h, g.chroma | g.cosited, g.range, g.matrix, rgb, is, ps, n, st);
     return g.bps == 2 ? w2xc_launch_yuv16_to_rgb(luma_words(s), chroma_words(s), words(s.v), w, h, g.chroma, g.range, g.matrix, g.depth, rgb, is, ps, n, st)
                       : w2xc_launch_yuv8_to_rgb(luma_planes(s), chroma_planes(s), s.v, w, h, g.chroma, g.range, g.matrix, rgb, is, ps, n, st);
 }
 hipError_t from_rgb(const YuvGeom &g, const float *rgb, long long is, long long ps, int w, int h, const YuvSide &s, int n, hipStream_t st)
 {
+    if (g.cosited)
+        return g.bps == 2 ? w2xc_launch_rgb_to_yuv16_sited(rgb, is, ps, w, h, g.chroma | g.cosited, g.range, g.matrix, g.depth, luma_words(s), chroma_words(s), words(s.v), n, st)
+                          : w2xc_launch_rgb_to_yuv8_sited(rgb, is, ps, w, h, g.chroma | g.cosited, g.range, g.matrix, luma_planes(s), chroma_planes(s), s.v, n, st);
     return g.bps == 2 ? w2xc_launch_rgb_to_yuv16(rgb, is, ps, w, h, g.chroma, g.range, g.matrix, g.depth, luma_words(s), chroma_words(s), words(s.v), n, st)
                       : w2xc_launch_rgb_to_yuv8(rgb, is, ps, w, h, g.chroma, g.range, g.matrix, luma_planes(s), chroma_planes(s), s.v, n, st);
 }
@@ -323,12 +347,12 @@ template <class Planes> int frames_yuv(bool host, const ImageCall &c, const YuvC
 
 // what the two blocks of the RGB route refuse: the frames' side as check_yuv_side refuses it, the 3 n float planes, and the two sides overlapping
 int check_yuv_rgb_block_args(const YuvSide *f, int bps, int depth, bool f_is_out, int n, int w, int h, int chroma, int range, int matrix, const float *rgb,
-                             size_t image_stride_bytes, size_t plane_stride_bytes)
+                             size_t image_stride_bytes, size_t plane_stride_bytes, int *cosited)
 {
     if (!f || !rgb) return fail(W2XC_ERR_ARG, "null argument");
     if (n < 1 || n > (1 << 20) || w <= 0 || h <= 0 || w > (1 << 22) || h > (1 << 22)) return fail(W2XC_ERR_ARG, "bad frame count / frame size");
     if (chroma == W2XC_YUV_400) return fail(W2XC_ERR_ARG, "a frame without chroma (W2XC_YUV_400) has no colour to convert");
-    if (int rc = check_chroma_range(chroma, range)) return rc;
+    if (int rc = check_chroma_range(chroma, range, &chroma, cosited)) return rc;
     if (int rc = check_depth(bps, depth)) return rc;
     if (int rc = check_matrix(matrix)) return rc;
     const size_t plane = (size_t)4 * w * h;
@@ -372,9 +396,9 @@ int yuv_rgb_block(bool out, const Planes *frames, int bps, int depth, int n, int
 {
     YuvSide store;
     const YuvSide *s = side_of(frames, &store);
-    if (int rc = check_yuv_rgb_block_args(s, bps, depth, out, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes)) return rc;
     YuvGeom g;   // (the format alone: what the ends take)
-    g.bps = bps; g.depth = depth; g.range = range; g.chroma = chroma; g.matrix = matrix;
+    if (int rc = check_yuv_rgb_block_args(s, bps, depth, out, n, w, h, chroma, range, matrix, d_rgb, image_stride_bytes, plane_stride_bytes, &g.cosited)) return rc;
+    g.bps = bps; g.depth = depth; g.range = range; g.chroma = chroma & 0xF; g.matrix = matrix;
     const long long is = (long long)(image_stride_bytes / 4), ps = (long long)(plane_stride_bytes / 4);
     HIP_TRY(out ? from_rgb(g, d_rgb, is, ps, w, h, *s, n, (hipStream_t)hip_stream) : to_rgb(g, *s, w, h, d_rgb, is, ps, n, (hipStream_t)hip_stream));
     return W2XC_OK;
@@ -396,8 +420,9 @@ int luma_block(bool out, const void *samples, int bps, int depth, int pack, int 
 }
 
 int chroma2x_block(const void *d_src, int bps, int depth, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int src_pack, int cw, int ch,
-                   void *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int dst_pack, int ow, int oh, void *hip_stream)
+                   void *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int dst_pack, int ow, int oh, int cosited, void *hip_stream)
 {
+    if (int rc = check_cosited(cosited, true, true)) return rc;
     if ((src_px != 1 && src_px != 2) || (dst_px != 1 && dst_px != 2)) return fail(W2XC_ERR_ARG, "src_px / dst_px must be 1 or 2");
     if (ow < 1 || oh < 1 || ow > 2 * (long long)cw || oh > 2 * (long long)ch) return fail(W2XC_ERR_ARG, "the output size lies outside the 2x enlargement");
     const size_t drow = chroma_row_bytes(ow, dst_px, bps), dext = (size_t)(oh - 1) * dst_stride_bytes + drow;
@@ -411,7 +436,7 @@ int chroma2x_block(const void *d_src, int bps, int depth, int n, size_t src_fram
     in.u = static_cast<unsigned char *>(const_cast<void *>(d_src)); in.c_frame_stride = src_frame_stride_bytes; in.c_stride = src_stride_bytes; in.c_px = src_px; in.pack = src_pack;
     to.u = static_cast<unsigned char *>(d_dst); to.c_frame_stride = dst_frame_stride_bytes; to.c_stride = dst_stride_bytes; to.c_px = dst_px; to.pack = dst_pack;
     YuvGeom g;
-    g.bps = bps; g.depth = depth; g.cw = cw; g.ch = ch; g.ocw = ow; g.och = oh;
+    g.bps = bps; g.depth = depth; g.cw = cw; g.ch = ch; g.ocw = ow; g.och = oh; g.cosited = cosited;
     HIP_TRY(chroma_out(g, true, in, to, n, (hipStream_t)hip_stream));
     return W2XC_OK;
 }
@@ -517,7 +542,15 @@ int w2xc_chroma2x_u8_device(const unsigned char *d_src, int n, size_t src_frame_
                             unsigned char *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int ow, int oh, void *hip_stream)
 {
     return chroma2x_block(d_src, 1, 8, n, src_frame_stride_bytes, src_stride_bytes, src_px, W2XC_PACK_LOW, cw, ch, d_dst, dst_frame_stride_bytes, dst_stride_bytes, dst_px,
-                          W2XC_PACK_LOW, ow, oh, hip_stream);
+                          W2XC_PACK_LOW, ow, oh, 0, hip_stream);
+}
+
+int w2xc_chroma2x_u8_sited_device(const unsigned char *d_src, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int cw, int ch,
+                                  unsigned char *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int ow, int oh, int cosited,
+                                  void *hip_stream)
+{
+    return chroma2x_block(d_src, 1, 8, n, src_frame_stride_bytes, src_stride_bytes, src_px, W2XC_PACK_LOW, cw, ch, d_dst, dst_frame_stride_bytes, dst_stride_bytes, dst_px,
+                          W2XC_PACK_LOW, ow, oh, cosited, hip_stream);
 }
 
 int w2xc_y16_to_plane_device(const unsigned short *d_src, int n, size_t frame_stride_bytes, size_t stride_bytes, int w, int h, int range, int depth, int pack,
@@ -537,7 +570,15 @@ int w2xc_chroma2x_u16_device(const unsigned short *d_src, int n, size_t src_fram
                              void *hip_stream)
 {
     return chroma2x_block(d_src, 2, depth, n, src_frame_stride_bytes, src_stride_bytes, src_px, src_pack, cw, ch, d_dst, dst_frame_stride_bytes, dst_stride_bytes, dst_px,
-                          dst_pack, ow, oh, hip_stream);
+                          dst_pack, ow, oh, 0, hip_stream);
+}
+
+int w2xc_chroma2x_u16_sited_device(const unsigned short *d_src, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int src_pack, int cw,
+                                   int ch, int depth, unsigned short *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int dst_pack,
+                                   int ow, int oh, int cosited, void *hip_stream)
+{
+    return chroma2x_block(d_src, 2, depth, n, src_frame_stride_bytes, src_stride_bytes, src_px, src_pack, cw, ch, d_dst, dst_frame_stride_bytes, dst_stride_bytes, dst_px,
+                          dst_pack, ow, oh, cosited, hip_stream);
 }
 
 }  // extern "C"

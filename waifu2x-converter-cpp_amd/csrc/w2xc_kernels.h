@@ -243,3 +243,20 @@ hipError_t w2xc_launch_yuv16_to_rgb(W2xcU16Planes y, W2xcU16Planes u, const unsi
                                     long long is, long long ps, int n, hipStream_t st);
 hipError_t w2xc_launch_rgb_to_yuv16(const float *rgb, long long is, long long ps, int w, int h, int chroma, int range, int matrix, int depth, W2xcU16Planes y,
                                     W2xcU16Planes u, unsigned short *v, int n, hipStream_t st);
+
+// ---- chroma co-sited with luma (w2xc_yuv_sited.hip, w2xc_yuv16_sited.hip, w2xc_yuv_rgb_sited.hip, w2xc_yuv16_rgb_sited.hip; include/w2xc_hip.h, "Chroma siting") ----
+// The six tile launchers above for chroma that sits ON luma column / row 2k: cosited = W2XC_CHROMA_COSITED_X | W2XC_CHROMA_COSITED_Y, at least one of them (0 is
+// the launchers above; a flag on an axis the layout does not subsample is hipErrorInvalidValue).  The launchers of the RGB route take the flags in `chroma`,
+// or-ed onto the layout, as the interface does.  Grids, load paths and stores are those of the centred launchers.
+hipError_t w2xc_launch_chroma2x_u8_sited(W2xcU8Planes su, const unsigned char *sv, int cw, int ch, W2xcU8Planes du, unsigned char *dv, int ow, int oh, int cosited, int n,
+                                         hipStream_t st);
+hipError_t w2xc_launch_chroma2x_u16_sited(W2xcU16Planes su, const unsigned short *sv, int cw, int ch, W2xcU16Planes du, unsigned short *dv, int ow, int oh, int depth,
+                                          int cosited, int n, hipStream_t st);
+hipError_t w2xc_launch_yuv8_to_rgb_sited(W2xcU8Planes y, W2xcU8Planes u, const unsigned char *v, int w, int h, int chroma, int range, int matrix, float *rgb,
+                                         long long is, long long ps, int n, hipStream_t st);
+hipError_t w2xc_launch_rgb_to_yuv8_sited(const float *rgb, long long is, long long ps, int w, int h, int chroma, int range, int matrix, W2xcU8Planes y, W2xcU8Planes u,
+                                         unsigned char *v, int n, hipStream_t st);
+hipError_t w2xc_launch_yuv16_to_rgb_sited(W2xcU16Planes y, W2xcU16Planes u, const unsigned short *v, int w, int h, int chroma, int range, int matrix, int depth,
+                                          float *rgb, long long is, long long ps, int n, hipStream_t st);
+hipError_t w2xc_launch_rgb_to_yuv16_sited(const float *rgb, long long is, long long ps, int w, int h, int chroma, int range, int matrix, int depth, W2xcU16Planes y,
+                                          W2xcU16Planes u, unsigned short *v, int n, hipStream_t st);

@@ -88,72 +88,8 @@ __global__ void __launch_bounds__(256) k_chroma2x_u8(const unsigned char *su, co
                                                      unsigned char *du, unsigned char *dv, long long dframe, long long drow, int dpx, int ow, int oh, int npl,
                                                      int tiles_x, long long tiles, long long turns)
 {
-    __shared__ float tile[CH_SH * CH_LD];
-    const float s255 = (float)(1.0 / 255.0);
-    const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
-    float c25[4], c75[4];
-    cubic_coeffs(0.25f, c25);
-    cubic_coeffs(0.75f, c75);
-    for (long long turn = blockIdx.x; turn < turns; turn += gridDim.x) {   // a turn: one tile of one plane of one frame
-        const long long p = turn / tiles, t = turn - p * tiles;
-        const long long f = p / npl;
-        const int v = (int)(p - f * npl);
-        const unsigned char *s = (v ? sv : su) + f * sframe;
-        unsigned char *d = (v ? dv : du) + f * dframe;
-        const int qy0 = (int)(t / tiles_x) * CH_TQY, qx0 = (int)(t % tiles_x) * CH_TQX;
-        const int gx0 = qx0 - 2, gy0 = qy0 - 2;   // the source pixel of LDS word (0, 0)
-        __syncthreads();   // (the tile of the loop's previous turn has been read)
-        if (DW) {
-            // column groups of four source pixels from gx0 - 2 (a multiple of 4) on: ten cover the CH_SW columns
-            for (int i = threadIdx.x; i < CH_SH * 10; i += 256) {
-                const int r = i / 10, g = i - r * 10;
-                const int gx4 = gx0 - 2 + 4 * g;
-                const unsigned char *row = s + clampi(gy0 + r, 0, ch - 1) * srow;
-                unsigned b[4];
-                if (gx4 >= 0 && gx4 + 3 < cw) {
-                    const unsigned w4 = *reinterpret_cast<const unsigned *>(row + gx4);
-                    b[0] = w4 & 255u; b[1] = (w4 >> 8) & 255u; b[2] = (w4 >> 16) & 255u; b[3] = w4 >> 24;
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 4; k++) b[k] = row[clampi(gx4 + k, 0, cw - 1)];
-                }
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const int c = 4 * g - 2 + k;
-                    if (c >= 0 && c < CH_SW) tile[r * CH_LD + c] = (float)b[k] * s255;
-                }
-            }
-        } else {
-            for (int i = threadIdx.x; i < CH_SH * CH_SW; i += 256) {
-                const int r = i / CH_SW, c = i - r * CH_SW;
-                tile[r * CH_LD + c] = (float)s[clampi(gy0 + r, 0, ch - 1) * srow + (long long)clampi(gx0 + c, 0, cw - 1) * spx] * s255;
-            }
-        }
-        __syncthreads();
-        const int qx = qx0 + lx, X0 = 2 * qx - 1;   // the quad's columns X0 (t = 0.25) and X0 + 1 (t = 0.75)
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            const int qr = ly + j * (CH_TQY / 2), Y0 = 2 * (qy0 + qr) - 1;   // rows Y0 (t = 0.25) and Y0 + 1 (t = 0.75)
-            if (X0 >= ow || Y0 >= oh) continue;
-            float r25[4], r75[4];   // the horizontal pass of the four rows, for either column
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const float *S = tile + (qr + k) * CH_LD + lx;
-                r25[k] = chroma_row_sum(S, c25);
-                r75[k] = chroma_row_sum(S, c75);
-            }
-            unsigned char *o = d + Y0 * drow + (long long)X0 * dpx;
-            const bool left = X0 >= 0, right = X0 + 1 < ow;
-            if (Y0 >= 0) {
-                if (left) o[0] = to_u8(chroma_row_sum(r25, c25));
-                if (right) o[dpx] = to_u8(chroma_row_sum(r75, c25));
-            }
-            if (Y0 + 1 < oh) {
-                if (left) o[drow] = to_u8(chroma_row_sum(r25, c75));
-                if (right) o[drow + dpx] = to_u8(chroma_row_sum(r75, c75));
-            }
-        }
-    }
+    constexpr bool CX = false, CY = false;   // centred along both axes (the co-sited forms: w2xc_yuv_sited.hip)
+#include "w2xc_chroma2x_u8_body.inc"
 }
 
 hipError_t w2xc_launch_chroma2x_u8(W2xcU8Planes su, const unsigned char *sv, int cw, int ch, W2xcU8Planes du, unsigned char *dv, int ow, int oh, int n, hipStream_t st)

@@ -97,92 +97,8 @@ __global__ void __launch_bounds__(256) k_chroma2x_u16(const unsigned short *su, 
                                                       int lshift, int pair, int ow, int oh, int npl, float inv_max, float fmax, int tiles_x, long long tiles,
                                                       long long turns)
 {
-    __shared__ float tile[2][CH_SH * CH_LD];
-    const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
-    float c25[4], c75[4];
-    cubic_coeffs(0.25f, c25);
-    cubic_coeffs(0.75f, c75);
-    for (long long turn = blockIdx.x; turn < turns; turn += gridDim.x) {   // a turn: one tile of the planes of one frame
-        const long long f = turn / tiles, t = turn - f * tiles;
-        const int qy0 = (int)(t / tiles_x) * CH_TQY, qx0 = (int)(t % tiles_x) * CH_TQX;
-        const int gx0 = qx0 - 2, gy0 = qy0 - 2;   // the source pixel of LDS word (0, 0)
-        __syncthreads();   // (the tiles of the loop's previous turn have been read)
-        if (LOAD == 2) {
-            const unsigned short *s = su + f * sframe;
-            for (int i = threadIdx.x; i < CH_SH * CH_SW; i += 256) {
-                const int r = i / CH_SW, c = i - r * CH_SW;
-                const unsigned w2 = *reinterpret_cast<const unsigned *>(s + clampi(gy0 + r, 0, ch - 1) * srow + (long long)clampi(gx0 + c, 0, cw - 1) * 2);
-                tile[0][r * CH_LD + c] = (float)u16_value(w2 & 0xFFFFu, rshift, max) * inv_max;
-                tile[1][r * CH_LD + c] = (float)u16_value(w2 >> 16, rshift, max) * inv_max;
-            }
-        } else {
-            for (int v = 0; v < npl; v++) {
-                const unsigned short *s = (v ? sv : su) + f * sframe;
-                float *T = tile[v];
-                if (LOAD == 1) {
-                    // column groups of four source pixels from gx0 - 2 (a multiple of 4) on: ten cover the CH_SW columns
-                    for (int i = threadIdx.x; i < CH_SH * 10; i += 256) {
-                        const int r = i / 10, g = i - r * 10;
-                        const int gx4 = gx0 - 2 + 4 * g;
-                        const unsigned short *row = s + clampi(gy0 + r, 0, ch - 1) * srow;
-                        unsigned b[4];
-                        if (gx4 >= 0 && gx4 + 3 < cw) {
-                            const uint2 w4 = *reinterpret_cast<const uint2 *>(row + gx4);
-                            b[0] = w4.x & 0xFFFFu; b[1] = w4.x >> 16; b[2] = w4.y & 0xFFFFu; b[3] = w4.y >> 16;
-                        } else {
-#pragma unroll
-                            for (int k = 0; k < 4; k++) b[k] = row[clampi(gx4 + k, 0, cw - 1)];
-                        }
-#pragma unroll
-                        for (int k = 0; k < 4; k++) {
-                            const int c = 4 * g - 2 + k;
-                            if (c >= 0 && c < CH_SW) T[r * CH_LD + c] = (float)u16_value(b[k], rshift, max) * inv_max;
-                        }
-                    }
-                } else {
-                    for (int i = threadIdx.x; i < CH_SH * CH_SW; i += 256) {
-                        const int r = i / CH_SW, c = i - r * CH_SW;
-                        T[r * CH_LD + c] = (float)u16_value(s[clampi(gy0 + r, 0, ch - 1) * srow + (long long)clampi(gx0 + c, 0, cw - 1) * spx], rshift, max) * inv_max;
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        const int qx = qx0 + lx, X0 = 2 * qx - 1;   // the quad's columns X0 (t = 0.25) and X0 + 1 (t = 0.75)
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            const int qr = ly + j * (CH_TQY / 2), Y0 = 2 * (qy0 + qr) - 1;   // rows Y0 (t = 0.25) and Y0 + 1 (t = 0.75)
-            if (X0 >= ow || Y0 >= oh) continue;
-            unsigned o[2][4] = {};   // per plane: (Y0, X0), (Y0, X0 + 1), (Y0 + 1, X0), (Y0 + 1, X0 + 1), packed words
-#pragma unroll
-            for (int v = 0; v < 2; v++) {
-                if (v >= npl) continue;
-                float r25[4], r75[4];   // the horizontal pass of the four rows, for either column
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const float *S = tile[v] + (qr + k) * CH_LD + lx;
-                    r25[k] = chroma_row_sum(S, c25);
-                    r75[k] = chroma_row_sum(S, c75);
-                }
-                o[v][0] = to_u16(chroma_row_sum(r25, c25), fmax, max) << lshift;
-                o[v][1] = to_u16(chroma_row_sum(r75, c25), fmax, max) << lshift;
-                o[v][2] = to_u16(chroma_row_sum(r25, c75), fmax, max) << lshift;
-                o[v][3] = to_u16(chroma_row_sum(r75, c75), fmax, max) << lshift;
-            }
-            const long long at = f * dframe + Y0 * drow + (long long)X0 * dpx;
-            const bool ok[4] = {Y0 >= 0 && X0 >= 0, Y0 >= 0 && X0 + 1 < ow, Y0 + 1 < oh && X0 >= 0, Y0 + 1 < oh && X0 + 1 < ow};
-            const long long off[4] = {0, dpx, drow, drow + dpx};
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                if (!ok[k]) continue;
-                if (pair) *reinterpret_cast<unsigned *>(du + at + off[k]) = o[0][k] | (o[1][k] << 16);
-                else {
-                    du[at + off[k]] = (unsigned short)o[0][k];
-                    if (npl == 2) dv[at + off[k]] = (unsigned short)o[1][k];
-                }
-            }
-        }
-    }
+    constexpr bool CX = false, CY = false;   // centred along both axes (the co-sited forms: w2xc_yuv16_sited.hip)
+#include "w2xc_chroma2x_u16_body.inc"
 }
 
 hipError_t w2xc_launch_chroma2x_u16(W2xcU16Planes su, const unsigned short *sv, int cw, int ch, W2xcU16Planes du, unsigned short *dv, int ow, int oh, int depth, int n,

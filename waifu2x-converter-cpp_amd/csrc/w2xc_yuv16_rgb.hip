@@ -32,133 +32,8 @@ __global__ void __launch_bounds__(256) k_yuv16_to_rgb(const unsigned short *__re
                                                       W2xcYuvToRgb m, float *__restrict__ rgb, long long is, long long ps, int v2, int tiles_x, long long tiles,
                                                       long long turns)
 {
-    constexpr int HX = SX ? 1 : 0, HY = SY ? 1 : 0;          // the halo
-    constexpr int SW = YR_TCX + 2 * HX, SH = YR_TCY + 2 * HY;   // the chroma tile in LDS
-    constexpr int LW = YR_TCX << HX, LH = YR_TCY << HY;       // the luma tile
-    __shared__ float ctile[2][(YR_TCY + 2) * YR_LD];
-    __shared__ __attribute__((aligned(4))) unsigned short ytile[2 * YR_TCY * YR_YLD];
-    const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
-    for (long long turn = blockIdx.x; turn < turns; turn += gridDim.x) {   // a turn: one tile of one frame
-        int cx0, cy0;
-        const long long f = yuv_tile_at(turn, tiles, tiles_x, YR_TCX, YR_TCY, &cx0, &cy0);
-        const int X0 = cx0 << HX, Y0 = cy0 << HY;   // the tile's first luma sample
-        const unsigned short *fy = sy + f * yframe;
-        // yv: the thread's groups of four luma samples go into registers first, so that their loads are in flight with those of the chroma tiles
-        constexpr int NGY = LW / 4, NJ = (LH * NGY + 255) / 256;
-        uint2 yw[NJ];
-        if (yv) {
-#pragma unroll
-            for (int j = 0; j < NJ; j++) {
-                const int i = threadIdx.x + 256 * j, r = i / NGY, g = i - r * NGY;
-                const int x4 = X0 + 4 * g;
-                yw[j] = make_uint2(0u, 0u);
-                if (i >= LH * NGY || Y0 + r >= h || x4 >= w) continue;
-                const unsigned short *row = fy + (Y0 + r) * yrow;
-                if (x4 + 3 < w) yw[j] = *reinterpret_cast<const uint2 *>(row + x4);
-                else {
-                    yw[j].x = row[x4];
-                    if (x4 + 1 < w) yw[j].x |= (unsigned)row[x4 + 1] << 16;
-                    if (x4 + 2 < w) yw[j].y = row[x4 + 2];
-                }
-            }
-        }
-        __syncthreads();   // (the tiles of the loop's previous turn have been read)
-        if (CM == 2) {
-            const unsigned short *s = su + f * cframe;
-            for (int i = threadIdx.x; i < SH * SW; i += 256) {
-                const int r = i / SW, c = i - r * SW;
-                const unsigned w2 = *reinterpret_cast<const unsigned *>(s + clampi(cy0 - HY + r, 0, ch - 1) * crow + (long long)clampi(cx0 - HX + c, 0, cw - 1) * 2);
-                ctile[0][r * YR_LD + c] = (float)u16_value(w2 & 0xFFFFu, cshift, max);
-                ctile[1][r * YR_LD + c] = (float)u16_value(w2 >> 16, cshift, max);
-            }
-        } else if (CM == 1) {
-            // column groups of four samples from cx0 - 4 HX (a multiple of 4) on; a thread fetches a group of U and the same group of V: two loads in flight
-            constexpr int NG = YR_TCX / 4 + 2 * HX;
-            const unsigned short *s0 = su + f * cframe, *s1 = sv + f * cframe;
-            for (int i = threadIdx.x; i < SH * NG; i += 256) {
-                const int r = i / NG, g = i - r * NG;
-                const int gx4 = cx0 - 4 * HX + 4 * g;
-                const long long at = clampi(cy0 - HY + r, 0, ch - 1) * crow;
-                unsigned b[2][4];
-                if (gx4 >= 0 && gx4 + 3 < cw) {
-                    const uint2 u4 = *reinterpret_cast<const uint2 *>(s0 + at + gx4), v4 = *reinterpret_cast<const uint2 *>(s1 + at + gx4);
-                    b[0][0] = u4.x & 0xFFFFu; b[0][1] = u4.x >> 16; b[0][2] = u4.y & 0xFFFFu; b[0][3] = u4.y >> 16;
-                    b[1][0] = v4.x & 0xFFFFu; b[1][1] = v4.x >> 16; b[1][2] = v4.y & 0xFFFFu; b[1][3] = v4.y >> 16;
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        const long long e = at + clampi(gx4 + k, 0, cw - 1);
-                        b[0][k] = s0[e];
-                        b[1][k] = s1[e];
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const int c = 4 * g - 3 * HX + k;
-                    if (c >= 0 && c < SW) {
-                        ctile[0][r * YR_LD + c] = (float)u16_value(b[0][k], cshift, max);
-                        ctile[1][r * YR_LD + c] = (float)u16_value(b[1][k], cshift, max);
-                    }
-                }
-            }
-        } else {
-            for (int i = threadIdx.x; i < SH * SW; i += 256) {
-                const int r = i / SW, c = i - r * SW;
-                const long long at = clampi(cy0 - HY + r, 0, ch - 1) * crow + (long long)clampi(cx0 - HX + c, 0, cw - 1) * spx;
-                ctile[0][r * YR_LD + c] = (float)u16_value((su + f * cframe)[at], cshift, max);
-                ctile[1][r * YR_LD + c] = (float)u16_value((sv + f * cframe)[at], cshift, max);
-            }
-        }
-        // luma: rows Y0 .. Y0 + LH - 1, columns X0 .. X0 + LW - 1 where they lie in the plane (nothing else of the tile is read below)
-        if (yv) {   // (the groups were fetched ahead of the chroma tiles; a group outside the plane is zeros that nothing reads)
-#pragma unroll
-            for (int j = 0; j < NJ; j++) {
-                const int i = threadIdx.x + 256 * j, r = i / NGY, g = i - r * NGY;
-                if (i >= LH * NGY) continue;
-                unsigned *d = reinterpret_cast<unsigned *>(ytile + r * YR_YLD + 4 * g);
-                d[0] = yw[j].x;
-                d[1] = yw[j].y;
-            }
-        } else {
-            for (int i = threadIdx.x; i < LH * LW; i += 256) {
-                const int r = i / LW, c = i - r * LW;
-                if (Y0 + r < h && X0 + c < w) ytile[r * YR_YLD + c] = fy[(Y0 + r) * yrow + X0 + c];
-            }
-        }
-        __syncthreads();
-        float *o = rgb + f * is;
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            const int tr = ly + j * (YR_TCY / 2), cx = cx0 + lx, cy = cy0 + tr;
-            if (cx >= cw || cy >= ch) continue;
-            float cu[2][1 + HY][1 + HX];   // U and V at the block's luma samples, from the thread's own sample
-#pragma unroll
-            for (int v = 0; v < 2; v++) chroma_at_luma<SX, SY>(ctile[v] + (tr + HY) * YR_LD + lx + HX, YR_LD, cu[v]);
-#pragma unroll
-            for (int r = 0; r < 1 + HY; r++) {
-                const int Y = (cy << HY) + r;
-                if (Y >= h) continue;
-                float px[3][1 + HX];   // R, G, B of the row's pixels
-#pragma unroll
-                for (int q = 0; q < 1 + HX; q++) {
-                    const float y = ((float)u16_value(ytile[((tr << HY) + r) * YR_YLD + (lx << HX) + q], yshift, max) - y0) * ky;
-                    rgb_px(m, y, (cu[0][r][q] - c0) * kc, (cu[1][r][q] - c0) * kc, px, q);
-                }
-                const int X = cx << HX;
-                float *d = o + (long long)Y * w + X;
-                if (SX && v2) {   // (w is even: the second pixel lies in the row)
-#pragma unroll
-                    for (int p = 0; p < 3; p++) *reinterpret_cast<float2 *>(d + p * ps) = make_float2(px[p][0], px[p][HX]);
-                } else {
-#pragma unroll
-                    for (int p = 0; p < 3; p++) {
-                        d[p * ps] = px[p][0];
-                        if (SX && X + 1 < w) d[p * ps + 1] = px[p][HX];
-                    }
-                }
-            }
-        }
-    }
+    constexpr bool CX = false, CY = false;   // centred siting (the co-sited forms: w2xc_yuv16_rgb_sited.hip)
+#include "w2xc_yuv16_to_rgb_body.inc"
 }
 
 hipError_t w2xc_launch_yuv16_to_rgb(W2xcU16Planes y, W2xcU16Planes u, const unsigned short *v, int w, int h, int chroma, int range, int matrix, int depth, float *rgb,
@@ -197,58 +72,8 @@ __global__ void __launch_bounds__(256) k_rgb_to_yuv16(const float *__restrict__ 
                                                       unsigned short *__restrict__ dv, long long cframe, long long crow, int dpx, int uv32, int cshift, int tiles_x,
                                                       long long tiles, long long turns)
 {
-    constexpr int HX = SX ? 1 : 0, HY = SY ? 1 : 0;
-    const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
-    for (long long turn = blockIdx.x; turn < turns; turn += gridDim.x) {
-        int cx0, cy0;
-        const long long f = yuv_tile_at(turn, tiles, tiles_x, YR_TCX, YR_TCY, &cx0, &cy0);
-        const float *s = rgb + f * is;
-        unsigned short *oy = dy + f * yframe;
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            const int cx = cx0 + lx, cy = cy0 + ly + j * (YR_TCY / 2);
-            if (cx >= cw || cy >= ch) continue;
-            YCC p[1 + HY][1 + HX];
-#pragma unroll
-            for (int r = 0; r < 1 + HY; r++) {
-                const int Y = min((cy << HY) + r, h - 1);
-                if (SX && v2) {   // (w is even: no block is cut at the right edge)
-                    const float *e = s + (long long)Y * w + (cx << HX);
-                    const float2 R = *reinterpret_cast<const float2 *>(e), G = *reinterpret_cast<const float2 *>(e + ps), B = *reinterpret_cast<const float2 *>(e + 2 * ps);
-                    p[r][0] = to_ycc(m, R.x, G.x, B.x);
-                    p[r][HX] = to_ycc(m, R.y, G.y, B.y);
-                    continue;
-                }
-#pragma unroll
-                for (int q = 0; q < 1 + HX; q++) {
-                    const int X = min((cx << HX) + q, w - 1);
-                    const float *e = s + (long long)Y * w + X;
-                    p[r][q] = to_ycc(m, e[0], e[ps], e[2 * ps]);
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 1 + HY; r++) {
-                const int Y = (cy << HY) + r, X = cx << HX;
-                if (Y >= h) continue;
-                unsigned short *d = oy + Y * yrow + X;
-                const unsigned b0 = luma_u16(p[r][0].y, limited, ys, y0, max) << yshift;
-                if (SX && X + 1 < w) {
-                    const unsigned b1 = luma_u16(p[r][HX].y, limited, ys, y0, max) << yshift;
-                    if (y32) *reinterpret_cast<unsigned *>(d) = b0 | (b1 << 16);
-                    else { d[0] = (unsigned short)b0; d[1] = (unsigned short)b1; }
-                } else d[0] = (unsigned short)b0;
-            }
-            float cb, cr;
-            chroma_mean<SX, SY>(p, &cb, &cr);
-            const long long at = f * cframe + cy * crow + (long long)cx * dpx;
-            const unsigned U = to_u16(cb, cs, c0, max) << cshift, V = to_u16(cr, cs, c0, max) << cshift;
-            if (uv32) *reinterpret_cast<unsigned *>(du + at) = U | (V << 16);
-            else {
-                du[at] = (unsigned short)U;
-                dv[at] = (unsigned short)V;
-            }
-        }
-    }
+    constexpr bool CX = false, CY = false;   // centred siting (the co-sited forms: w2xc_yuv16_rgb_sited.hip)
+#include "w2xc_rgb_to_yuv16_body.inc"
 }
 
 hipError_t w2xc_launch_rgb_to_yuv16(const float *rgb, long long is, long long ps, int w, int h, int chroma, int range, int matrix, int depth, W2xcU16Planes y,

@@ -25,6 +25,21 @@ static __device__ __forceinline__ float lerp31(float near, float far)
     return a + b;
 }
 
+// co-sited chroma (include/w2xc_hip.h, "Chroma siting"): the value halfway between two samples, 0.5 C[j] + 0.5 C[j + 1] -- exact on samples as floats
+static __device__ __forceinline__ float lerp11(float a, float b)
+{
+    const float x = 0.5f * a;
+    const float y = 0.5f * b;
+    return x + y;
+}
+// ... and the 1-2-1 mean around a luma sample m with its neighbours l and r: the sum, two exact scalings, one sum
+static __device__ __forceinline__ float mean121(float l, float m, float r)
+{
+    const float a = (l + r) * 0.25f;
+    const float b = m * 0.5f;
+    return a + b;
+}
+
 static __device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
 
 struct YCC { float y, cb, cr; };
@@ -54,6 +69,8 @@ static __device__ __forceinline__ unsigned char luma_u8(float y, int limited)
 {
     return limited ? (unsigned char)clampi(__float2int_rn(y * 219.0f + 16.0f), 0, 255) : to_u8(y);
 }
+// cb or cr -> a chroma byte of the RGB route: saturate(rint(c * scale + 128))
+static __device__ __forceinline__ unsigned char chroma_u8(float c, float scale) { return (unsigned char)clampi(__float2int_rn(c * scale + 128.0f), 0, 255); }
 // value of a word: saturate(rint(y * M)), or saturate(rint(y * (219 s) + 16 s)) for limited range
 static __device__ __forceinline__ unsigned luma_u16(float y, int limited, float scale, float off, int max)
 {
@@ -96,10 +113,23 @@ static inline int rows_8_aligned(const float *rgb, long long is, long long ps, i
 // the chroma planes of a w x h frame of the RGB route (4:2:0, 4:2:2, 4:4:4)
 static inline bool frame_geometry(int w, int h, int chroma, int *cw, int *ch)
 {
-    if (w < 1 || h < 1 || chroma < 0 || chroma > 2) return false;
+    if (w < 1 || h < 1 || chroma < 0) return false;
+    chroma &= 0xF;   // (the siting flags, W2XC_CHROMA_COSITED_*, do not change a size)
+    if (chroma > 2) return false;
     *cw = chroma != 2 ? (w + 1) / 2 : w;
     *ch = chroma == 0 ? (h + 1) / 2 : h;
     return true;
+}
+
+// a `chroma` value of the RGB route WITH siting flags (W2XC_CHROMA_COSITED_X 0x10, _Y 0x20): its layout and the two flags; false where it has no flag, another
+// bit, or a flag on an axis its layout does not subsample (the interface's rule, check_chroma_range in w2xc_image_yuv.cpp, refuses the same with a message)
+static inline bool sited_layout(int chroma, int *layout, bool *cx, bool *cy)
+{
+    if (chroma < 0 || (chroma & ~0x3F) || !(chroma & 0x30)) return false;
+    *layout = chroma & 0xF;
+    *cx = (chroma & 0x10) != 0;
+    *cy = (chroma & 0x20) != 0;
+    return *layout == 0 || (*layout == 1 && !*cy);
 }
 
 // the scales and offsets of a depth (D bits, s = 2^(D - 8), M = 2^D - 1) and a range, computed in double and rounded once to float

@@ -63,6 +63,29 @@ template <bool SX, bool SY> static __device__ __forceinline__ void chroma_at_lum
         else cu[0][q] = hz[0][q];
     }
 }
+// ... with chroma co-sited along x (CX) and / or y (CY): at luma 2k the sample C[k] itself, at 2k + 1 lerp11(C[k], C[k + 1]) -- the halo's sample below / to the right,
+// clamped into the plane as the tile's loader clamps it; an axis that is centred or not subsampled is chroma_at_luma's.  Horizontally first, then vertically
+template <bool SX, bool SY, bool CX, bool CY> static __device__ __forceinline__ void chroma_at_luma_sited(const float *S, int ld, float (&cu)[1 + SY][1 + SX])
+{
+    static_assert((SX || !CX) && (SY || !CY), "a co-sited axis is a subsampled one");
+    if (!CX && !CY) { chroma_at_luma<SX, SY>(S, ld, cu); return; }
+    constexpr int HX = SX ? 1 : 0, HY = SY ? 1 : 0;
+    constexpr int R0 = (SY && !CY) ? -1 : 0, NR = SY ? (CY ? 2 : 3) : 1;   // the rows the vertical step needs: cy - 1 .. cy + 1, cy and cy + 1, or cy alone
+    float hz[NR][1 + HX];
+#pragma unroll
+    for (int r = 0; r < NR; r++) {
+        const float *R = S + (R0 + r) * ld;
+        if (CX) { hz[r][0] = R[0]; hz[r][HX] = lerp11(R[0], R[1]); }
+        else if (SX) { hz[r][0] = lerp31(R[0], R[-1]); hz[r][HX] = lerp31(R[0], R[1]); }
+        else hz[r][0] = R[0];
+    }
+#pragma unroll
+    for (int q = 0; q < 1 + HX; q++) {
+        if (CY) { cu[0][q] = hz[0][q]; cu[HY][q] = lerp11(hz[0][q], hz[NR - 1][q]); }
+        else if (SY) { cu[0][q] = lerp31(hz[NR / 2][q], hz[0][q]); cu[HY][q] = lerp31(hz[NR / 2][q], hz[NR - 1][q]); }
+        else cu[0][q] = hz[0][q];
+    }
+}
 // pixel q of a row from y', cb, cr: the matrix, the clamp to the models' domain
 template <int N> static __device__ __forceinline__ void rgb_px(const W2xcYuvToRgb &m, float y, float cb, float cr, float (&px)[3][N], int q)
 {
@@ -86,4 +109,47 @@ template <bool SX, bool SY> static __device__ __forceinline__ void chroma_mean(c
         *cb = (p[0][0].cb + p[0][HX].cb) * 0.5f;
         *cr = (p[0][0].cr + p[0][HX].cr) * 0.5f;
     } else { *cb = p[0][0].cb; *cr = p[0][0].cr; }
+}
+
+// ---- device: R, G, B -> chroma co-sited with luma (w2xc_rgb_to_yuv8_body.inc, w2xc_rgb_to_yuv16_body.inc) ----
+// y', cb, cr of the pixel (X, Y) of a frame's float planes
+static __device__ __forceinline__ YCC ycc_at(const W2xcRgbToYuv &m, const float *s, long long ps, int w, int Y, int X)
+{
+    const float *e = s + (long long)Y * w + X;
+    return to_ycc(m, e[0], e[ps], e[2 * ps]);
+}
+// The horizontal pass of luma row Y for the chroma sample of lane lx of a tile that starts at chroma column cx0: p0 and p1 are the thread's pixels of that row,
+// luma columns 2 cx and 2 cx + 1 (clamped).  CX: mean121 around column 2 cx; its left neighbour, column 2 cx - 1, is p1 of the lane below in the wave's 32-lane
+// half -- every lane of the half calls this together --, for lane 0 a pixel converted from memory, at the plane's left edge the thread's own p0.  Centred: the mean
+// of the two
+template <bool CX>
+static __device__ __forceinline__ void row_chroma(const W2xcRgbToYuv &m, const float *s, long long ps, int w, int Y, int cx0, int lx, const YCC &p0, const YCC &p1,
+                                                  float *cb, float *cr)
+{
+    if (!CX) {
+        *cb = (p0.cb + p1.cb) * 0.5f;
+        *cr = (p0.cr + p1.cr) * 0.5f;
+        return;
+    }
+    float lb = __shfl_up(p1.cb, 1, 32), lr = __shfl_up(p1.cr, 1, 32);
+    const bool edge = lx == 0 && cx0 == 0;
+    lb = edge ? p0.cb : lb;
+    lr = edge ? p0.cr : lr;
+    if (lx == 0 && cx0 > 0) {
+        const YCC e = ycc_at(m, s, ps, w, Y, 2 * cx0 - 1);
+        lb = e.cb; lr = e.cr;
+    }
+    *cb = mean121(lb, p0.cb, p1.cb);
+    *cr = mean121(lr, p0.cr, p1.cr);
+}
+// ... of the luma row above a tile that starts at chroma row cy0, for the threads of tile row 0 (one 32-lane half of a wave, together): the pixels of row 2 cy0 - 1
+// at the columns of chroma sample bx are converted from memory; at the plane's top edge the row clamps to the block's own first row, whose result the caller hands in
+template <bool CX>
+static __device__ __forceinline__ void top_row_chroma(const W2xcRgbToYuv &m, const float *s, long long ps, int w, int cx0, int cy0, int bx, int lx, float own_cb,
+                                                      float own_cr, float *cb, float *cr)
+{
+    if (cy0 == 0) { *cb = own_cb; *cr = own_cr; return; }
+    const int Y = 2 * cy0 - 1;
+    const YCC p0 = ycc_at(m, s, ps, w, Y, min(2 * bx, w - 1)), p1 = ycc_at(m, s, ps, w, Y, min(2 * bx + 1, w - 1));
+    row_chroma<CX>(m, s, ps, w, Y, cx0, lx, p0, p1, cb, cr);
 }
