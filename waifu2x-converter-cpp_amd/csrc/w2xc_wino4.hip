@@ -20,12 +20,14 @@
 //              its block tile in FOUR QUARTERS over four consecutive stages, the 36 values in REGISTERS in between (Q0 raw patch + row pass of rows
 //              0..2 | Q1 rows 3..5 | Q2 column pass of columns 0..2 | Q3 columns 3..5 + nine ds_write_b128 of V): every wave carries the same 42 VALU
 //              instructions in every stage, the four waves of a block tile are one quarter apart, the two waves of a SIMD two.  The pipeline runs
-//              across items; the waves in mid-transform at an item's end park their 36 values in LDS across the epilogue.  V is two slots.
+//              across items; the waves in mid-transform at an item's end keep their 36 values in registers across the epilogue (the PROG forms, whose
+//              epilogue calls a function, park them in LDS).  V is two slots.
 //              The MFMAs are asm with the accumulator TIED: as builtins the allocator gave three of four a destination other than their
 //              accumulator input, the accumulators migrated through the file and some were spilled inside the stages.
 //   LDS        raw[3] x 11 KiB: the 18 x 36 pixel halo tile of a 4-channel slice as 16-byte chunks (channel kk, row R, pixel quad q) at
 //              chunk index kk * 168 + R * 9 + q (the stride 168 = 8 mod 16 makes the b128 patch reads conflict-free);
-//              U[2] x 36 KiB + V[2] x 18 KiB + 18 KiB (with U slot 1 the parking area of an epilogue) + bias = 159.5 KiB.
+//              U[2] x 36 KiB + V[2] x 18 KiB + 18 KiB + bias = 159.5 KiB.  U slot 1, V slot 1 and the last 18 KiB are idle across an epilogue: 72 KiB =
+//              the fused last layer's tap exchange of a whole item (PROG: U slot 1 + the 18 KiB park the transforms, V slot 1 is the exchange of one row step).
 //   Transfers  LDS-DMA (global_load_lds_dwordx4), SGPR base + 32-bit lane offset: per stage 36 U pieces (one stage ahead) and 11 raw
 //              pieces (the slice Q0 reads two stages later; the closing wait of a stage leaves its own raw pieces in flight), all issued by the
 //              four OLDER waves: they win the matrix pipe's arbitration and have the time (W4_DMA4).  A lane's 16 bytes are four
@@ -34,7 +36,7 @@
 //              channels of ONE pixel, the pixels of a row grouped by column mod 4 (conflict-free ds_read_b32 of a lane's channel).
 //   Epilogue   Y = A^T M A per output-row pair, bias, LeakyReLU; planar out: one 16-byte store = four pixels of a plane row, 8 lanes = one
 //              128-byte line (NHWC out for a consumer that wants it).  FUSE7: the model's one-plane LAST layer on the activations just
-//              computed ("taps as rows" on the MFMA), the four plane tiles of a block summed through the idle V slot: 9 partial tap planes
+//              computed ("taps as rows" on the MFMA), the four plane tiles of a block summed through idle LDS, the item in one piece: 9 partial tap planes
 //              per 64-plane block leave the chip (72 B per pixel instead of 512), conv3x3_last_gather finishes.
 //   Edges      rows are clamped (replicate) in the transfer addresses; patch columns >= in_w are ZEROED in the row pass (they only reach
 //              outputs >= out_w, and what is in memory there is not defined): results do not depend on memory contents outside the plane.

@@ -14,7 +14,7 @@
     constexpr unsigned RAW_BYTES = RAW_PIECES * 1024;
     constexpr unsigned U_BASE = 3 * RAW_BYTES, U_BYTES = 36 * 1024;
     constexpr unsigned V_BASE = U_BASE + 2 * U_BYTES, V_BYTES = 18 * 1024;
-    constexpr unsigned SPARE_BASE = V_BASE + 2 * V_BYTES;   // 18 KiB: with U slot 1 the parking area across an epilogue
+    constexpr unsigned SPARE_BASE = V_BASE + 2 * V_BYTES;   // 18 KiB: with U slot 1 and V slot 1 the fused last layer's exchange across an epilogue (PARK: with U slot 1 the parking area)
     constexpr unsigned BIAS_BASE = SPARE_BASE + V_BYTES;
     static_assert(CIN % 16 == 0 && COUT % 64 == 0 && NST % 4 == 0 && NST >= 8, "planes");
     constexpr int STRIP = 16;
@@ -185,8 +185,9 @@
     // The operand bases of a stage: with W4_KEEP_BASES they are three more lane-linear registers that live through the kernel (a ds_read's 16-bit immediate
     // reaches both V slots from one base, U's two slots need one each); rebuilt per use they were 7 VALU instructions per wave and stage -- and a VALU
     // instruction is 4 cycles of a SIMD that issues nothing else meanwhile (DESIGN.md 3)
-    unsigned ua0_v = b_voff + ua_u, ua1_v = b_voff + ua_u + U_BYTES, va_v = b_voff + va_u;
-    asm volatile("" : "+v"(ua0_v), "+v"(ua1_v), "+v"(va_v));
+    // (formed at the head of a phase's copy of the item loop and again behind every epilogue -- lane_regs() below --, so that they do not live through the
+    // epilogue: with b_voff, which they are formed from, that is room for five of the transform values in flight there)
+    unsigned ua0_v = 0, ua1_v = 0, va_v = 0;
     auto ua_of = [&](unsigned slot) { return W4_KEEP_BASES ? ldsb + (slot ? ua1_v : ua0_v) : ldsb + (lin() + (ua_u + slot * U_BYTES)); };
     auto va_of = [&](unsigned slot) { return W4_KEEP_BASES ? ldsb + va_v + slot * V_BYTES : ldsb + (lin() + (va_u + slot * V_BYTES)); };
     // transformer lane (r, kk, c) = block (block row 2 bt + r, column c), channel kk: patch row i, columns 0..3 = chunk (kk, 4 (2 bt + r) + i, c),
@@ -204,8 +205,17 @@
         const int l = lane_o(), tr_r = l >> 5, tr_k = (l >> 3) & 3, tr_c = l & 7;
         return V_BASE + (unsigned)bt * 1024u + (unsigned)((tr_k * 16 + tr_r * 8 + tr_c) * 16);
     };
-    unsigned tr_rd_v = tr_rd_calc(), tr_wr_v = tr_wr_calc();
-    asm volatile("" : "+v"(tr_rd_v), "+v"(tr_wr_v));
+    unsigned tr_rd_v = 0, tr_wr_v = 0;
+    auto lane_regs = [&]() {   // a dozen VALU instructions
+        if constexpr (W4_KEEP_BASES) {
+            ua0_v = lin() + ua_u; ua1_v = lin() + (ua_u + U_BYTES); va_v = lin() + va_u;
+            asm volatile("" : "+v"(ua0_v), "+v"(ua1_v), "+v"(va_v));
+        }
+        if constexpr (W4_KEEP_TR) {
+            tr_rd_v = tr_rd_calc(); tr_wr_v = tr_wr_calc();
+            asm volatile("" : "+v"(tr_rd_v), "+v"(tr_wr_v));
+        }
+    };
     auto tr_rd = [&]() { return W4_KEEP_TR ? tr_rd_v : tr_rd_calc(); };
     auto tr_wr = [&]() { return W4_KEEP_TR ? tr_wr_v : tr_wr_calc(); };
 
@@ -218,8 +228,8 @@
     // With PH = (pt - 2 bt) mod 4 a wave runs quarter (stage - PH) mod 4: it transforms the slices n = PH (mod 4) of its block tile, every wave carries
     // the same 42 VALU instructions in every stage, and the two waves of a SIMD (same pt) are two quarters apart (raw reads beside pure arithmetic).
     // The pipeline runs ACROSS items (the last four stages of an item work on the first slices of the next): the three waves of a block tile that
-    // are in mid-transform at an item's end park their 36 values in LDS across the epilogue (whose registers are full) -- in the U slot and the 18 KiB
-    // that are idle then -- and take them back behind it.  Nothing else of a transform touches LDS between its raw reads and its V writes: round 4's
+    // are in mid-transform at an item's end keep their 36 values in registers across the epilogue (pin_dd below; PARK: in the U slot and the 18 KiB that
+    // are idle then).  Nothing else of a transform touches LDS between its raw reads and its V writes: round 4's
     // earlier forms parked the intermediates of EVERY transform in the V ring (row-pass waves -> column-pass waves), and that traffic alone cost 0.7
     // of layer 6's 6.7 ms (timing-only ablation, profiles/r4_sweeps.log 8).
     // ---- PROG: arrivals and gather jobs (see the comment above the kernel) ----
@@ -344,6 +354,22 @@
         }
     };
 
+    // The 36 values of a transform in flight at an item's end (PH != 0) stay in REGISTERS across the epilogue: its row transform works in place on the
+    // accumulators and the operand ring is idle, so the file holds them.  The pins keep them where they are: nothing of a transform is sunk into or
+    // hoisted across the epilogue, nothing is rematerialised.  PARK (the PROG forms, whose epilogue calls w4_prog_job -- values alive across a call
+    // go through scratch: 7 spills measured for 64 planes out): the values are parked in LDS instead, in U slot 1 and the spare 18 KiB that are idle then --
+    // nine ds_write_b128, nine ds_read_b128 and a workgroup barrier of their own per item, as in every form before.
+    constexpr bool PARK = PROG;
+    auto pin_dd = [&]() {
+        float(&v)[36] = dd;   // (an asm operand alone does not capture dd into a nested generic lambda: six rows written out)
+        asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]));
+        asm volatile("" : "+v"(v[6]), "+v"(v[7]), "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]));
+        asm volatile("" : "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15]), "+v"(v[16]), "+v"(v[17]));
+        asm volatile("" : "+v"(v[18]), "+v"(v[19]), "+v"(v[20]), "+v"(v[21]), "+v"(v[22]), "+v"(v[23]));
+        asm volatile("" : "+v"(v[24]), "+v"(v[25]), "+v"(v[26]), "+v"(v[27]), "+v"(v[28]), "+v"(v[29]));
+        asm volatile("" : "+v"(v[30]), "+v"(v[31]), "+v"(v[32]), "+v"(v[33]), "+v"(v[34]), "+v"(v[35]));
+    };
+
     // A run-time "which quarter now" around the stage bodies joins 144 accumulators in phi nodes and the register allocator gives up: the item loop exists
     // four times (one copy per PH, unrolled by four stages with the quarters fixed at compile time) and a wave picks its copy once.
     auto run = [&](auto PH_) {
@@ -351,7 +377,8 @@
     using C0 = std::integral_constant<int, 0>;
     using C1 = std::integral_constant<int, 1>;
     using U0 = std::integral_constant<unsigned, 0u>;
-    // where this wave parks across an epilogue: six parkers (three per block tile) x 9 KiB = U slot 1 (idle behind the last stage's closing barrier) + the spare 18 KiB
+    lane_regs();
+    // PARK: where this wave parks across an epilogue: six parkers (three per block tile) x 9 KiB = U slot 1 (idle behind the last stage's closing barrier) + the spare 18 KiB
     const unsigned park_u = (bt * 3 + PH - 1) < 4 ? U_BASE + U_BYTES + (unsigned)(bt * 3 + PH - 1) * 9216u : SPARE_BASE + (unsigned)(bt * 3 + PH - 1 - 4) * 9216u;
     auto park = [&]() {
         char *pa = ldsb + (lin() + park_u);
@@ -559,7 +586,10 @@
         }
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // (the last MFMAs' results: the hazard the compiler does not see through the asm)
         xlim_cur = xlim_r;   // (the raw cursor entered the next item's tile five stages ago)
-        if constexpr (PH != 0) park();   // (PH = 0 has just written the V of the next item's first stage)
+        if constexpr (PH != 0) {   // (PH = 0 has just written the V of the next item's first stage)
+            if constexpr (PARK) park();
+            else pin_dd();
+        }
         {
             // ---- epilogue: Y = A^T M A, bias, LeakyReLU, stores.  C/D of the 16x16 MFMA: lane & 15 = block, register e = plane
             //      4 (lane >> 4) + e of the plane tile ----
@@ -578,7 +608,7 @@
             // FUSE7: the one-plane LAST layer (convertRoutine.cpp:66-76's next iteration) inside this epilogue, "taps as rows": per pixel the nine partial
             // sums T_tap = sum over this wave's 16 planes of w7[plane][tap] * a6[plane] on the MFMA (A = w7 of the planes 4 k + e as 16 x 4, tap = row;
             // B = the activations just computed, lane (k, block) = plane 4 k + e of a pixel of that block), summed over the four plane-tile waves
-            // through the V slot that is idle between two items, and written as 9 tap planes per 64-plane block: 72 bytes per pixel leave the chip
+            // through LDS that is idle between two items, and written as 9 tap planes per 64-plane block: 72 bytes per pixel leave the chip
             // instead of 512, and conv3x3_last_gather adds taps and blocks (0.1 ms instead of the 0.8 ms of conv3x3_last).
             float a7[4];
             if constexpr (FUSE7) {
@@ -586,10 +616,43 @@
 #pragma unroll
                 for (int e = 0; e < 4; e++) a7[e] = w7[e * 64];
             }
+            // The tap exchange.  PARK (U slot 1 and the spare hold the parked transforms): one ROW STEP at a time through V slot 1 -- [pt][tap][128 pixels]
+            // floats, 18 KiB, two workgroup barriers per row step.  Otherwise the whole ITEM at once: behind the last stage's closing barrier U slot 1, V slot 1
+            // and the spare 18 KiB are all idle until the next item's first stage fills them, 72 KiB = [pt][tap][512 pixels] floats -- plane tiles 0 and 1 in U
+            // slot 1, 2 and 3 in V slot 1 and the spare behind it (V slot 0 and U slot 0, between them, hold the next item's first stage) --, pixel index =
+            // row step * 128 + the row step's: two barriers per item.
+            constexpr bool SLAB_ITEM = FUSE7 && !PARK;
+            constexpr int SLAB_PX = SLAB_ITEM ? 512 : 128;
             char *red = ldsb + V_BASE + V_BYTES;   // (V slot 1: idle until the next item's first stage writes V of its second)
+            auto slab_of = [&](int q) {            // plane tile q's [tap][SLAB_PX] floats
+                if constexpr (SLAB_ITEM) return ldsb + (q < 2 ? U_BASE + U_BYTES + (unsigned)q * V_BYTES : V_BASE + V_BYTES + (unsigned)(q - 2) * V_BYTES);
+                else return red + q * (9 * 128 * 4);
+            };
+            static_assert(SPARE_BASE == V_BASE + 2 * V_BYTES && U_BYTES == 2 * V_BYTES && V_BYTES == 9 * 512 * 4, "the item's slab");
+            // quad `job` of a slab's [tap][pixel quad]s (tap = job / (SLAB_PX / 4)): the four plane tiles summed in the order 0..3, stored into its tap plane
+            auto tap_reduce = [&](int job, int tap, int gy, int gx) {
+                f32x4 sum = *reinterpret_cast<const f32x4 *>(slab_of(0) + job * 16);
+#pragma unroll
+                for (int q = 1; q < 4; q++) sum += *reinterpret_cast<const f32x4 *>(slab_of(q) + job * 16);   // (fixed order: reproducible)
+                if (gy >= 0 && gy < d.out_h && gx < d.out_w) {
+                    float *g = W4B_OUT + (long long)ob * d.out_ts + (long long)tap * d.out_gs + (long long)gy * d.out_rs + gx;
+                    if constexpr (PROG) {   // written through: read by the gather job of whichever workgroup arrives last
+                        if (gx + 3 < d.out_w) store16_sc1(g, sum);
+                        else {
+#pragma unroll
+                            for (int e = 0; e < 3; e++)
+                                if (gx + e < d.out_w) store4_sc1(g + e, sum[e]);
+                        }
+                    } else if (gx + 3 < d.out_w) *reinterpret_cast<f32x4u *>(g) = sum;   // (dword-aligned: rows of out_w floats)
+                    else {
+#pragma unroll
+                        for (int e = 0; e < 3; e++)
+                            if (gx + e < d.out_w) g[e] = sum[e];
+                    }
+                }
+            };
             unsigned tick = 0xFFFFFFFFu, pq0 = 0, pq1 = 0;   // PROG, control wave: what the job counters of the PREVIOUS item's arrivals held; the queue
             (void)tick; (void)pq0; (void)pq1;
-            // [pt][tap][128 pixels] floats (18 KiB)
             // The row transform A^T M of every column, all four rows at once (10 operations per column and plane; two passes over row PAIRS recompute
             // the four sums and differences: 14): the six accumulators of a (column, plane) are dead behind it, their registers hold its four results.
             float tm[4][6][4];   // [row][column j][plane e]
@@ -633,54 +696,38 @@
                         for (int e = 0; e < 4; e++)
 #pragma unroll
                             for (int j = 0; j < 4; j++) D[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a7[e], y[e][j], D[j], 0, 0, 0);
-                        // lane (k, t) holds taps 4 k .. 4 k + 3 of pixel j of block t.  The slab is [pt][tap][128 pixels] (pixel index p = (block row) * 32 +
-                        // (block column) * 4 + j): ONE 16-byte write per tap = the four pixels of this lane's block, eight lanes = 128 contiguous bytes (as
+                        // lane (k, t) holds taps 4 k .. 4 k + 3 of pixel j of block t.  A row step's pixels in the slab [pt][tap][pixel]: p = (block row) * 32 +
+                        // (block column) * 4 + j: ONE 16-byte write per tap = the four pixels of this lane's block, eight lanes = 128 contiguous bytes (as
                         // [pt][tap quad][pixel][4] the eight lanes of a write group sat 64 bytes apart: four-way bank conflicts, 9 % of layer 6's LDS cycles)
-                        const int p0 = (2 * bt + (t >> 3)) * 32 + (t & 7) * 4;
+                        const int p0 = (SLAB_ITEM ? i * 128 : 0) + (2 * bt + (t >> 3)) * 32 + (t & 7) * 4;
+                        char *slab = slab_of(pt);
                         if (k < 2) {
 #pragma unroll
-                            for (int r = 0; r < 4; r++) *reinterpret_cast<f32x4 *>(red + ((pt * 9 + 4 * k + r) * 128 + p0) * 4) = f32x4{D[0][r], D[1][r], D[2][r], D[3][r]};
+                            for (int r = 0; r < 4; r++) *reinterpret_cast<f32x4 *>(slab + ((4 * k + r) * SLAB_PX + p0) * 4) = f32x4{D[0][r], D[1][r], D[2][r], D[3][r]};
                         } else if (k == 2) {
-                            *reinterpret_cast<f32x4 *>(red + ((pt * 9 + 8) * 128 + p0) * 4) = f32x4{D[0][0], D[1][0], D[2][0], D[3][0]};
+                            *reinterpret_cast<f32x4 *>(slab + (8 * SLAB_PX + p0) * 4) = f32x4{D[0][0], D[1][0], D[2][0], D[3][0]};
                         }
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                        __builtin_amdgcn_s_barrier();
-                        asm volatile("" ::: "memory");
-                        if constexpr (PROG) {
-                            // (every wave has drained the previous item's stores in front of this barrier) its arrival, counted by wave 0; the counters'
-                            // answers are looked at three row steps further down
-                            if (i == 0 && wave == CW) prog_early(n > 0 ? item_of(n - 1) : -1, tick, pq0, pq1);
-                            if (i == 3 && wave == CW) prog_late(n > 0 ? item_of(n - 1) : -1, tick, pq0, pq1);
-                        }
-                        {
-                            const int tid = wave * 64 + lane_e;
-                            if (tid < 288) {
-                                const int tap = tid >> 5, p = (tid & 31) * 4;     // nine taps x 32 pixel quads
-                                const int gy = ty0 + 4 * (p >> 5) + i, gx = tile_x * 32 + (p & 31);
-                                f32x4 sum = *reinterpret_cast<const f32x4 *>(red + ((0 * 9 + tap) * 128 + p) * 4);
-#pragma unroll
-                                for (int q = 1; q < 4; q++) sum += *reinterpret_cast<const f32x4 *>(red + ((q * 9 + tap) * 128 + p) * 4);   // (fixed order: reproducible)
-                                if (gy >= 0 && gy < d.out_h && gx < d.out_w) {
-                                    float *g = W4B_OUT + (long long)ob * d.out_ts + (long long)tap * d.out_gs + (long long)gy * d.out_rs + gx;
-                                    if constexpr (PROG) {   // written through: read by the gather job of whichever workgroup arrives last
-                                        if (gx + 3 < d.out_w) store16_sc1(g, sum);
-                                        else {
-#pragma unroll
-                                            for (int e = 0; e < 3; e++)
-                                                if (gx + e < d.out_w) store4_sc1(g + e, sum[e]);
-                                        }
-                                    } else if (gx + 3 < d.out_w) *reinterpret_cast<f32x4u *>(g) = sum;   // (dword-aligned: rows of out_w floats)
-                                    else {
-#pragma unroll
-                                        for (int e = 0; e < 3; e++)
-                                            if (gx + e < d.out_w) g[e] = sum[e];
-                                    }
+                        if constexpr (!SLAB_ITEM) {
+                            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                            __builtin_amdgcn_s_barrier();
+                            asm volatile("" ::: "memory");
+                            if constexpr (PROG) {
+                                // (every wave has drained the previous item's stores in front of this barrier) its arrival, counted by wave 0; the counters'
+                                // answers are looked at three row steps further down
+                                if (i == 0 && wave == CW) prog_early(n > 0 ? item_of(n - 1) : -1, tick, pq0, pq1);
+                                if (i == 3 && wave == CW) prog_late(n > 0 ? item_of(n - 1) : -1, tick, pq0, pq1);
+                            }
+                            {
+                                const int tid = wave * 64 + lane_e;
+                                if (tid < 288) {
+                                    const int tap = tid >> 5, p = (tid & 31) * 4;     // nine taps x 32 pixel quads
+                                    tap_reduce(tid, tap, ty0 + 4 * (p >> 5) + i, tile_x * 32 + (p & 31));
                                 }
                             }
+                            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                            __builtin_amdgcn_s_barrier();   // (the slab is rewritten by the next row)
+                            asm volatile("" ::: "memory");
                         }
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                        __builtin_amdgcn_s_barrier();   // (the slab is rewritten by the next row)
-                        asm volatile("" ::: "memory");
                     } else if constexpr ((W4_ABL & 64) != 0) {
                         if (y[0][0] == 12345.678f) *reinterpret_cast<f32x4 *>(obase) = y[0] + y[1] + y[2] + y[3];
                     } else if constexpr (OUT_PLANAR) {
@@ -699,16 +746,43 @@
                     }
                 }
             }
+            if constexpr (SLAB_ITEM) {
+                // the item's taps are in the slab: ONE barrier, then the 9 x 128 pixel quads over all 512 threads (three or fewer each; quad `job` sits at
+                // job * 16 of every plane tile's part: lane-linear reads), one barrier before the next item's first stage writes U and V there
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+                const int tid = wave * 64 + lane_e;
+#pragma unroll
+                for (int jb = 0; jb < 3; jb++) {
+                    const int job = tid + jb * 512;
+                    if (jb < 2 || job < 9 * 128) {
+                        const int tap = job >> 7, i = (job >> 5) & 3, p = (job & 31) * 4;     // nine taps x four row steps x 32 pixel quads
+                        tap_reduce(job, tap, ty0 + 4 * (p >> 5) + i, tile_x * 32 + (p & 31));
+                    }
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+            }
             __builtin_amdgcn_s_setprio(0);
             W4_STAMP(stamp++);
             // PROG: the gather jobs the previous item's arrivals completed (the LDS word was written in front of the epilogue's last barrier)
             if constexpr (PROG) prog_run();
         }
-        // the transforms in flight back into registers; the barrier: the next stage's U transfers land on the parking area
-        if constexpr (PH != 0) unpark();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        if constexpr (PARK) {
+            // the transforms in flight back into registers; the barrier: the next stage's U transfers land on the parking area
+            if constexpr (PH != 0) unpark();
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+        } else {
+            // No barrier: the epilogue reads nothing of LDS but the bias (FUSE7: its own last barrier stands between the slab's readers and the next
+            // stage's writes), and what the next item's first stage reads and overwrites was settled by the last stage's closing barrier, as between any
+            // two stages of an item.
+            if constexpr (PH != 0) pin_dd();
+            lane_regs();   // (not kept through the epilogue)
+        }
     }
     W2XC_WAIT_VMCNT(0);   // drain the speculative transfers before the LDS is released
     if constexpr (PROG) {
