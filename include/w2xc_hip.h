@@ -702,7 +702,8 @@ int w2xc_tta_gather_u8_device(const float *d_up, const float *d_tr, size_t varia
  * planes of one buffer, v = u + 1 (NV12) or u = v + 1 (NV21): anything else is W2XC_ERR_ARG here.  Without a device W2XC_ERR_HIP.
  * Left out: RGB and head models on YUV frames (they need a colour matrix chosen by the caller), 10 / 16-bit samples, TTA, more than one 2x step, the shrink,
  * chroma siting correction, a submit / wait pair that overlaps frames across calls, overlapped host sub-batches, multi-device striping.
- * (Samples of 9 to 16 bits in 16-bit words now live in w2xc_process_frames_yuv_u16*: "16-bit YUV frames" below.) */
+ * (Samples of 9 to 16 bits in 16-bit words now live in w2xc_process_frames_yuv_u16*: "16-bit YUV frames" below.)
+ * (An output size, several 2x steps and the shrink now live in the _sized forms of these calls: "Sized YUV frames" below.) */
 #define W2XC_YUV_420 0
 #define W2XC_YUV_422 1
 #define W2XC_YUV_444 2
@@ -772,7 +773,8 @@ int w2xc_chroma2x_u8_device(const unsigned char *d_src, int n, size_t src_frame_
  * layer where the chain has batch kernels, one frame the single-image sequence, bands included.
  * Left out: left-sited chroma, 10 / 16-bit samples, TTA, the shrink, more than one 2x step, uint8-fused first and last layers (the float RGB planes exist in
  * memory), multi-device striping, overlapped host sub-batches, a submit / wait pair.
- * (Samples of 9 to 16 bits in 16-bit words now live in w2xc_process_frames_yuv_u16_rgb*: "16-bit YUV frames" below.) */
+ * (Samples of 9 to 16 bits in 16-bit words now live in w2xc_process_frames_yuv_u16_rgb*: "16-bit YUV frames" below.)
+ * (An output size, several 2x steps and the shrink now live in the _sized forms of these calls: "Sized YUV frames" below.) */
 #define W2XC_MATRIX_BT601  0
 #define W2XC_MATRIX_BT709  1
 #define W2XC_MATRIX_BT2020 2
@@ -831,7 +833,8 @@ int w2xc_rgb_to_yuv8_device(const float *d_rgb, size_t image_stride_bytes, size_
  * Refused, before a device is touched: everything the corresponding 8-bit call refuses, with its code; and W2XC_ERR_ARG for a depth outside 8 .. 16, a pack that
  * is not 0 or 1, an odd pointer, an odd row or frame stride, a stride below the row's bytes counted at 2 bytes per sample.
  * Left out: different depths on the two sides (8-bit in with 16-bit out included), left-sited chroma, TTA, the shrink, more than one 2x step, big-endian words,
- * packed 10-bit formats such as v210, uint16-fused first and last layers, multi-device striping, overlapped host sub-batches, a submit / wait pair. */
+ * packed 10-bit formats such as v210, uint16-fused first and last layers, multi-device striping, overlapped host sub-batches, a submit / wait pair.
+ * (An output size, several 2x steps and the shrink now live in the _sized forms of these calls: "Sized YUV frames" below.) */
 #define W2XC_PACK_LOW  0
 #define W2XC_PACK_HIGH 1
 typedef struct w2xc_yuv16_planes {   /* one side of a call: n frames */
@@ -895,7 +898,8 @@ int w2xc_rgb_to_yuv16_device(const float *d_rgb, size_t image_stride_bytes, size
  * presence marks it; w2xc_opts and w2xc_version() are unchanged): w2xc_chroma2x_u8_device / _u16_device with `cosited` behind `oh` -- any combination of the two
  * flag bits, anything else W2XC_ERR_ARG; cosited = 0 is the centred block, byte for byte.
  * Left out: per-plane sitings (PAL-DV 4:2:0, whose Cb and Cr sit on different lines), different sitings on the two sides of a call, TTA, the shrink, more than one
- * 2x step. */
+ * 2x step.
+ * (An output size, several 2x steps and the shrink now live in the _sized forms of these calls: "Sized YUV frames" below.) */
 #define W2XC_CHROMA_COSITED_X 0x10   /* along x a chroma sample sits ON luma column 2k (left-sited)   */
 #define W2XC_CHROMA_COSITED_Y 0x20   /* along y a chroma sample sits ON luma row 2k (top-sited)        */
 #define W2XC_YUV_420_LEFT    (W2XC_YUV_420 | W2XC_CHROMA_COSITED_X)                         /* MPEG-2, H.264, HEVC default */
@@ -907,6 +911,75 @@ int w2xc_chroma2x_u8_sited_device(const unsigned char *d_src, int n, size_t src_
 int w2xc_chroma2x_u16_sited_device(const unsigned short *d_src, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int src_pack, int cw,
                                    int ch, int depth, unsigned short *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int dst_pack,
                                    int ow, int oh, int cosited, void *hip_stream);
+
+/* ---- Sized YUV frames (revision 0.4.1.11) --------------------------------------------------------------
+ * The eight frame calls above leave a frame at its own size or at exactly twice it.  Their _sized forms take an output size and up to four 2x steps: 720p ->
+ * 1080p (1.5x), 540p -> 2160p (4x), DVD 720 x 480 -> 1920 x 1080 (2.67x by 2.25x).  Each is its base call with `out_w, out_h` in front of the output planes;
+ * w2xc_opts and w2xc_version() are unchanged, the new symbols mark the revision, and every older entry point keeps its arguments, its refusals and its bytes.
+ *   iterations: 0 .. 4, as in the image calls, or W2XC_ITERATIONS_AUTO (-1): the smallest k with (w << k) >= out_w and (h << k) >= out_h.
+ *   output size: with W = w << iterations and H = h << iterations, w <= out_w <= W and h <= out_h <= H, the two axes independent: the output is never smaller than
+ *              the input, and with iterations = 0 it has the input's size.  The output chroma planes have the chroma size of an out_w x out_h frame, by the rule
+ *              of "YUV frames".
+ *   refused, before a device is touched: everything the base call refuses, with its code, except that iterations 2 .. 4 and AUTO are legal; an output size
+ *              outside those ranges (AUTO that four steps do not reach included) W2XC_ERR_ARG; iterations >= 1 without a scale model, a head model as noise
+ *              model, as before.
+ * The arithmetic.  Every expression is a sequence of single fp32 operations in the order given, in files built with -ffp-contract=off; coordinates are computed
+ * in double, as w2xc_resize_linear_device computes its own.
+ *   luma, Y route: "luma in" of the base call; the noise pass; `iterations` times y <- CNN_scale(nearest2x(y)), which is w2xc_convert_batch_device with nn2x = 1,
+ *              unclipped between the passes; where (out_w, out_h) != (W, H), exactly w2xc_resize_linear_device from W x H to out_w x out_h; "luma out" of the
+ *              base call.
+ *   RGB route: w2xc_yuv8_to_rgb_device / w2xc_yuv16_to_rgb_device at w x h; the passes of w2xc_process_image_rgb_u8* for that many iterations (a head model
+ *              enlarges by itself, as there); w2xc_resize_linear_device on each of the three planes; w2xc_rgb_to_yuv8_device / w2xc_rgb_to_yuv16_device at
+ *              out_w x out_h.  The same `chroma` value, siting flags included, goes to both ends.
+ *   chroma, Y route: ONE step from the input plane to the output plane -- chroma does not pass the CNN, so it gains nothing from being resampled once per 2x step
+ *              and rounded to samples in between.  Per axis r = (double)w / out_w ((double)h / out_h in y), the LUMA ratio, not a quotient of chroma sizes: odd
+ *              sizes stay aligned with luma.  o = 0.5 on a centred or unsubsampled axis, 0.25 on a co-sited one.  For output chroma sample m, in double:
+ *              pos = (m + o) * r - o -- the sum, the product, the difference --, s = floor(pos), t = (float)(pos - s); the taps s - 1 .. s + 2 clamped into the
+ *              plane; the coefficients cubic_coeffs(t) of w2xc_resize2x_cubic_device; the values (float)C * (float)(1.0 / 255.0) ((float)(1.0 / M) for words); the
+ *              tap sum of the 2x enlargement, horizontally then vertically; saturate(rint(255 c)), or clamp(rint(c * M), 0, M) for words.
+ *              At r = 0.5 this IS the existing enlargement, for every m, column 0 and the crop included: centred t = 0.25 for odd m and 0.75 for even m,
+ *              co-sited 0.375 / 0.875, in both s = q - 1 for m = 2q - 1 and m = 2q (every double operation above is exact there).  At r = 1, pos = m, t = 0
+ *              and cubic_coeffs(0) is exactly (0, 1, 0, 0): the plane is copied.
+ * The frame calls are DEFINED, by bytes and words, as these composed routes of public calls, for every option set the routes accept (fusion settings, precisions,
+ * named kernels, a cutting band_rows at S = 1); the Y route uses w2xc_chroma_resize_u8_device / _u16_device per chroma plane.  With iterations <= 1 and (out_w,
+ * out_h) = (W, H) a sized call gives, byte for byte, what the base call gives: the engine runs the chroma copy where the output has the input's size and the
+ * bicubic 2x kernels at exactly twice it, the resize kernels everywhere else.  Sub-batches (the per-frame memory has the float planes of every level and of the
+ * shrunk one), bands at S = 1, the lock, the stream rules, the host form and device_mask are those of the base calls; a sub-batch is ONE chroma launch and, where
+ * the output is not the last level, ONE launch of the linear stage for its luma (or 3 S RGB) planes.
+ * The two blocks: w2xc_chroma2x_u8_sited_device / _u16_sited_device with the luma sizes of both sides (w, h, out_w, out_h: they give the ratios; out_w >= w and
+ * out_h >= h) and the layout's two subsampling flags (sub_x, sub_y, 0 or 1: with `cosited` they give o; a siting flag on an axis that is not subsampled is
+ * W2XC_ERR_ARG) behind `oh`.  Any cw x ch -> ow x oh with ow, oh >= 1: the 2x blocks' bound on ow and oh is gone, their other refusals stay.  They always run
+ * the resize kernels (tiles of 32 x 16 output samples, the source window of at most 35 x 19 samples in LDS as floats), at r = 1 and r = 0.5 too.
+ * Left out: output smaller than the input, antialiasing in the linear shrink (OpenCV has none either), a fused luma shrink-and-quantise kernel (the shrunk float
+ * plane exists in memory), a shrink fused into the from-RGB kernels, TTA, different depths or sitings on the two sides, multi-device striping, a submit / wait
+ * pair. */
+#define W2XC_ITERATIONS_AUTO (-1)
+int w2xc_process_frames_yuv_u8_sized_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range,
+                                            const w2xc_yuv_planes *d_in, int out_w, int out_h, const w2xc_yuv_planes *d_out, int iterations, void *hip_stream,
+                                            const w2xc_opts *opts);
+int w2xc_process_frames_yuv_u8_sized(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, const w2xc_yuv_planes *in,
+                                     int out_w, int out_h, const w2xc_yuv_planes *out, int iterations, const w2xc_opts *opts);
+int w2xc_process_frames_yuv_u8_rgb_sized_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int matrix,
+                                                const w2xc_yuv_planes *d_in, int out_w, int out_h, const w2xc_yuv_planes *d_out, int iterations, void *hip_stream,
+                                                const w2xc_opts *opts);
+int w2xc_process_frames_yuv_u8_rgb_sized(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int matrix,
+                                         const w2xc_yuv_planes *in, int out_w, int out_h, const w2xc_yuv_planes *out, int iterations, const w2xc_opts *opts);
+int w2xc_process_frames_yuv_u16_sized_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int depth,
+                                             const w2xc_yuv16_planes *d_in, int out_w, int out_h, const w2xc_yuv16_planes *d_out, int iterations, void *hip_stream,
+                                             const w2xc_opts *opts);
+int w2xc_process_frames_yuv_u16_sized(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int depth,
+                                      const w2xc_yuv16_planes *in, int out_w, int out_h, const w2xc_yuv16_planes *out, int iterations, const w2xc_opts *opts);
+int w2xc_process_frames_yuv_u16_rgb_sized_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int depth, int matrix,
+                                                 const w2xc_yuv16_planes *d_in, int out_w, int out_h, const w2xc_yuv16_planes *d_out, int iterations,
+                                                 void *hip_stream, const w2xc_opts *opts);
+int w2xc_process_frames_yuv_u16_rgb_sized(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int depth, int matrix,
+                                          const w2xc_yuv16_planes *in, int out_w, int out_h, const w2xc_yuv16_planes *out, int iterations, const w2xc_opts *opts);
+int w2xc_chroma_resize_u8_device(const unsigned char *d_src, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int cw, int ch,
+                                 unsigned char *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int ow, int oh, int w, int h, int out_w,
+                                 int out_h, int sub_x, int sub_y, int cosited, void *hip_stream);
+int w2xc_chroma_resize_u16_device(const unsigned short *d_src, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int src_pack, int cw,
+                                  int ch, int depth, unsigned short *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int dst_pack,
+                                  int ow, int oh, int w, int h, int out_w, int out_h, int sub_x, int sub_y, int cosited, void *hip_stream);
 
 /* the building blocks on contiguous float planes (device pointers): main.cpp:144 on one plane, :75-76, :171-172 */
 int w2xc_resize2x_cubic_device(const float *d_src, int w, int h, float *d_dst, void *hip_stream);

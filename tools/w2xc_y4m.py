@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/w2xc_y4m.py in.y4m out.y4m -m noise|scale|noise_scale --model_dir DIR [--noise_level N] [--range full|limited] [--matrix bt601|bt709|bt2020]
-                     [--frames_per_call N] [--siting center|left|topleft|auto]
+                     [--frames_per_call N] [--siting center|left|topleft|auto] [--size WxH | --scale_ratio R]
 
 An 8-bit YUV4MPEG2 stream through the YUV frame calls.  The route follows the loaded models, as in tools/w2xc_cli.py.  Y models (one plane in, one out) go
 through w2xc_process_frames_yuv_u8: luma through the models, chroma enlarged on bytes -- no RGB image, no colour matrix; --matrix is ignored.  Models whose
@@ -17,8 +17,14 @@ The range is the stream's XCOLORRANGE=FULL|LIMITED where present, otherwise --ra
 --frames_per_call.  With a scale step the W and H fields are doubled; F (the frame rate) and A (the pixel aspect) are those of the input -- twice the samples
 in both directions change neither --, every other header field is passed on as it is.  Interlaced streams (I other than p / ?) are refused: fields would have
 to be enlarged separately.
+--size WxH and --scale_ratio R name the output size (include/w2xc_hip.h, "Sized YUV frames": the _sized frame calls).  --size: as many 2x steps as reach it
+(W2XC_ITERATIONS_AUTO's rule), the last level shrunk linearly, chroma resized in one step; the output is never smaller than the input and at most 16 times it a
+side.  --scale_ratio, by the reference's rule: iterations = ceil(log2 R), the output int(W * R) x int(H * R); R = 1 needs a noise model, R < 1 is
+refused.  Either needs a scale model where a 2x step is taken (-m scale or noise_scale).  The W and H of the written header follow; without either option the
+tool behaves as before.
 """
 import argparse
+import math
 import os
 import sys
 
@@ -76,6 +82,49 @@ def siting_flags(siting, tag, layout):
     return flags
 
 
+def parse_size(text):
+    """'WxH' -> (W, H)"""
+    parts = text.lower().split("x")
+    if len(parts) != 2 or not all(p.isdigit() for p in parts) or int(parts[0]) < 1 or int(parts[1]) < 1:
+        raise Y4mError("--size wants WxH, two positive integers (got %r)" % (text,))
+    return int(parts[0]), int(parts[1])
+
+
+def auto_iterations(w, h, out_w, out_h):
+    """the smallest k with (w << k) >= out_w and (h << k) >= out_h (W2XC_ITERATIONS_AUTO's rule); 5 where four steps do not reach"""
+    k = 0
+    while k < 5 and ((w << k) < out_w or (h << k) < out_h):
+        k += 1
+    return k
+
+
+def output_plan(w, h, size, scale_ratio, has_noise, has_scale):
+    """(iterations, (out_w, out_h) or None) of a stream of w x h frames: --size (a string) or --scale_ratio (a float), neither: the tool's old rule -- one 2x
+    step with a scale model, none without -- and None, the base frame calls.  What the options cannot mean is a Y4mError"""
+    if size is not None and scale_ratio is not None:
+        raise Y4mError("--size and --scale_ratio exclude each other")
+    if size is None and scale_ratio is None:
+        return (1 if has_scale else 0), None
+    if size is not None:
+        out_w, out_h = parse_size(size)
+        if out_w < w or out_h < h:
+            raise Y4mError("--size %dx%d is smaller than the stream's %dx%d: the output is never smaller than the input" % (out_w, out_h, w, h))
+        iterations = auto_iterations(w, h, out_w, out_h)
+        if iterations > 4:
+            raise Y4mError("--size %dx%d is more than 16 times the stream's %dx%d a side (four 2x steps at the most)" % (out_w, out_h, w, h))
+    else:
+        if not (scale_ratio >= 1.0) or scale_ratio > 16.0:
+            raise Y4mError("--scale_ratio %g: 1 to 16 (the output is never smaller than the input, four 2x steps at the most)" % scale_ratio)
+        iterations = int(math.ceil(math.log2(scale_ratio)))          # main.cpp:107-108
+        out_w, out_h = int(w * scale_ratio), int(h * scale_ratio)    # :160-165
+    if iterations and not has_scale:
+        raise Y4mError("an output of %dx%d from %dx%d takes %d 2x step%s: that needs a scale model (-m scale or noise_scale)"
+                       % (out_w, out_h, w, h, iterations, "" if iterations == 1 else "s"))
+    if not iterations and not has_noise:
+        raise Y4mError("an output of the input's size takes no 2x step: that needs a noise model (-m noise or noise_scale)")
+    return iterations, (out_w, out_h)
+
+
 def chroma_size(w, h, layout):
     if layout == LAYOUTS["mono"]:
         return 0, 0
@@ -115,6 +164,10 @@ class Header:
     def scaled(self, iterations):
         """the header of the output: W and H doubled `iterations` times, every other field -- F and A among them -- kept"""
         return Header(self.w << iterations, self.h << iterations, self.fields)
+
+    def sized(self, out_w, out_h):
+        """the header of a sized output: W and H as named, every other field kept"""
+        return Header(out_w, out_h, self.fields)
 
     def line(self):
         return b" ".join([MAGIC, b"W%d" % self.w, b"H%d" % self.h] + [("%s%s" % kv).encode("ascii") for kv in self.fields]) + b"\n"
@@ -228,18 +281,21 @@ def build_parser(description="8-bit YUV4MPEG2 streams through waifu2x models on 
     ap.add_argument("--frames_per_call", type=int, default=8)
     ap.add_argument("--siting", default="center", choices=list(SITINGS),
                     help="where a chroma sample sits: center (JPEG / MPEG-1), left (MPEG-2, H.264, HEVC), topleft (BT.2020 / UHD), or auto: by the C tag")
+    ap.add_argument("--size", default=None, metavar="WxH", help="the output frame size: as many 2x steps as reach it, then a linear shrink (never below the input's size)")
+    ap.add_argument("--scale_ratio", type=float, default=None, metavar="R",
+                    help="the reference's rule: ceil(log2 R) 2x steps, output int(W * R) x int(H * R); R = 1 needs a noise model")
     return ap
 
 
-def convert_stream(fin, fout, process, iterations, default_range="limited", frames_per_call=8, layout_of_header=None, dtype=np.uint8):
+def convert_stream(fin, fout, process, iterations, default_range="limited", frames_per_call=8, layout_of_header=None, dtype=np.uint8, size=None):
     """read fin, write fout; process(y, u, v, layout, full_range) -> (Y, U, V) is the frame call.  Returns the number of frames.  layout_of_header / dtype: how
-    another tool reads the C tag, and its sample type"""
+    another tool reads the C tag, and its sample type.  size = (out_w, out_h): the W and H of the written header (default: doubled `iterations` times)"""
     hdr = read_header(fin)
     if hdr.interlaced:
         raise Y4mError(INTERLACED % hdr.get("I"))
     layout = hdr.layout if layout_of_header is None else layout_of_header(hdr)
     full = (hdr.colour_range() or default_range) == "full"
-    write_header(fout, hdr.scaled(iterations))
+    write_header(fout, hdr.scaled(iterations) if size is None else hdr.sized(*size))
     total = 0
     while True:
         y, u, v = read_frames(fin, hdr, max(1, frames_per_call), layout, dtype)
@@ -251,7 +307,8 @@ def convert_stream(fin, fout, process, iterations, default_range="limited", fram
 
 def run_tool(name, args, layout_of_header, make_process, dtype=np.uint8):
     """what both tools do with their parsed arguments: check the stream, load the models, route by their kind, convert.  make_process(w2xc, hdr, noise, scale,
-    iterations, route, matrix, flags) -> the process callback of convert_stream; flags = the siting flags the frame call gets or-ed onto the layout"""
+    iterations, route, matrix, flags, size) -> the process callback of convert_stream; flags = the siting flags the frame call gets or-ed onto the layout,
+    size = None (the base frame calls, as before) or (out_w, out_h) (--size / --scale_ratio: the _sized calls)"""
     try:
         with open(args.input, "rb") as fin:
             # what the stream itself rules out, before a model is loaded or the output file is created
@@ -260,6 +317,7 @@ def run_tool(name, args, layout_of_header, make_process, dtype=np.uint8):
                 raise Y4mError(INTERLACED % hdr.get("I"))
             layout, _ = layout_of_header(hdr), hdr.colour_range()
             flags = siting_flags(args.siting, hdr.get("C"), layout)
+            iterations, size = output_plan(hdr.w, hdr.h, args.size, args.scale_ratio, args.mode in ("noise", "noise_scale"), args.mode in ("scale", "noise_scale"))
             fin.seek(0)
             import __graft_entry__ as graft
             w2xc = graft.load_package()
@@ -268,13 +326,12 @@ def run_tool(name, args, layout_of_header, make_process, dtype=np.uint8):
                 noise = w2xc._ModelSet.from_json(os.path.join(args.model_dir, "noise%d_model.json" % args.noise_level))
             if args.mode in ("scale", "noise_scale"):
                 scale = w2xc._ModelSet.from_json(os.path.join(args.model_dir, "scale2.0x_model.json"))
-            iterations = 1 if scale is not None else 0
             route = model_route(noise.planes(0)[0] if noise else None, scale.planes(0)[0] if scale else None)
             check_route(route, layout)
             matrix = MATRICES[args.matrix or default_matrix(hdr.h)]
-            process = make_process(w2xc, hdr, noise, scale, iterations, route, matrix, flags)
+            process = make_process(w2xc, hdr, noise, scale if iterations else None, iterations, route, matrix, flags, size)
             with open(args.output, "wb") as fout:
-                n = convert_stream(fin, fout, process, iterations, args.range, args.frames_per_call, layout_of_header, dtype)
+                n = convert_stream(fin, fout, process, iterations, args.range, args.frames_per_call, layout_of_header, dtype, size)
     except Y4mError as e:
         sys.stderr.write("%s: %s\n" % (name, e))
         return 2
@@ -283,12 +340,17 @@ def run_tool(name, args, layout_of_header, make_process, dtype=np.uint8):
 
 
 def main(argv=None):
-    def make_process(w2xc, hdr, noise, scale, iterations, route, matrix, flags):
+    def make_process(w2xc, hdr, noise, scale, iterations, route, matrix, flags, size):
         def process(y, u, v, layout, full):
             rng = w2xc.RANGE_FULL if full else w2xc.RANGE_LIMITED
-            if route == "rgb":
+            if size is not None:
+                kw = dict(chroma=layout | flags, noise=noise, scale=scale, iterations=iterations, range=rng)
+                out = (w2xc.process_frames_yuv_u8_rgb_sized(y, size[0], size[1], u, v, matrix=matrix, **kw) if route == "rgb" else
+                       w2xc.process_frames_yuv_u8_sized(y, size[0], size[1], u, v, **kw))
+            elif route == "rgb":
                 return w2xc.process_frames_yuv_u8_rgb(y, u, v, chroma=layout | flags, noise=noise, scale=scale, iterations=iterations, range=rng, matrix=matrix)
-            out = w2xc.process_frames_yuv_u8(y, u, v, chroma=layout | flags, noise=noise, scale=scale, iterations=iterations, range=rng)
+            else:
+                out = w2xc.process_frames_yuv_u8(y, u, v, chroma=layout | flags, noise=noise, scale=scale, iterations=iterations, range=rng)
             return out if len(out) == 3 else (out[0], None, None)
         return process
     return run_tool("w2xc_y4m", build_parser().parse_args(argv), lambda hdr: hdr.layout, make_process)

@@ -38,6 +38,8 @@ YUV_420_LEFT, YUV_420_TOPLEFT, YUV_422_LEFT = YUV_420 | CHROMA_COSITED_X, YUV_42
 RANGE_FULL, RANGE_LIMITED = 0, 1
 MATRIX_BT601, MATRIX_BT709, MATRIX_BT2020 = 0, 1, 2
 PACK_LOW, PACK_HIGH = 0, 1
+# "Sized YUV frames": iterations = the smallest k with (w << k) >= out_w and (h << k) >= out_h (W2XC_ITERATIONS_AUTO)
+ITERATIONS_AUTO = -1
 
 
 class W2xcError(RuntimeError):
@@ -170,6 +172,17 @@ def _load():
         "w2xc_plane_to_y8_device": (ci, [fp, ci, cs, ci, ci, ci, fp, cs, cs, vp]),
         "w2xc_chroma2x_u8_device": (ci, [fp, ci, cs, cs, ci, ci, ci, fp, cs, cs, ci, ci, ci, vp]),
         "w2xc_chroma2x_u8_sited_device": (ci, [fp, ci, cs, cs, ci, ci, ci, fp, cs, cs, ci, ci, ci, ci, vp]),
+        "w2xc_process_frames_yuv_u8_sized_device": (ci, [vp, vp, ci, ci, ci, ci, ci, C.POINTER(YuvPlanes), ci, ci, C.POINTER(YuvPlanes), ci, vp, C.POINTER(Opts)]),
+        "w2xc_process_frames_yuv_u8_sized": (ci, [vp, vp, ci, ci, ci, ci, ci, C.POINTER(YuvPlanes), ci, ci, C.POINTER(YuvPlanes), ci, C.POINTER(Opts)]),
+        "w2xc_process_frames_yuv_u8_rgb_sized_device": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(YuvPlanes), ci, ci, C.POINTER(YuvPlanes), ci, vp, C.POINTER(Opts)]),
+        "w2xc_process_frames_yuv_u8_rgb_sized": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(YuvPlanes), ci, ci, C.POINTER(YuvPlanes), ci, C.POINTER(Opts)]),
+        "w2xc_process_frames_yuv_u16_sized_device": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(Yuv16Planes), ci, ci, C.POINTER(Yuv16Planes), ci, vp, C.POINTER(Opts)]),
+        "w2xc_process_frames_yuv_u16_sized": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(Yuv16Planes), ci, ci, C.POINTER(Yuv16Planes), ci, C.POINTER(Opts)]),
+        "w2xc_process_frames_yuv_u16_rgb_sized_device": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Yuv16Planes), ci, ci, C.POINTER(Yuv16Planes), ci, vp,
+                                                              C.POINTER(Opts)]),
+        "w2xc_process_frames_yuv_u16_rgb_sized": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Yuv16Planes), ci, ci, C.POINTER(Yuv16Planes), ci, C.POINTER(Opts)]),
+        "w2xc_chroma_resize_u8_device": (ci, [fp, ci, cs, cs, ci, ci, ci, fp, cs, cs, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]),
+        "w2xc_chroma_resize_u16_device": (ci, [fp, ci, cs, cs, ci, ci, ci, ci, ci, fp, cs, cs, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]),
         "w2xc_u8_to_rgb_device": (ci, [fp, cs, ci, ci, fp, fp, fp, vp]),
         "w2xc_rgb_to_u8_device": (ci, [fp, fp, fp, ci, ci, fp, cs, vp]),
         "w2xc_process_image_u8_device": (ci, [vp, vp, fp, cs, ci, ci, fp, cs, ci, vp, C.POINTER(Opts)]),
@@ -1073,9 +1086,17 @@ def process_frames_yuv_u8_rgb(y, u=None, v=None, uv=None, chroma=YUV_420, noise=
     return _frames_yuv_host(matrix, y, u, v, uv, chroma, noise, scale, iterations, range, opts, out_nv12)
 
 
-def _frames_yuv_host(matrix, y, u, v, uv, chroma, noise, scale, iterations, range, opts, out_nv12, wide=None):
+def sized_iterations(w, h, out_w, out_h):
+    """what ITERATIONS_AUTO resolves to: the smallest k with (w << k) >= out_w and (h << k) >= out_h (5 where four steps do not reach: the call refuses it)"""
+    k = 0
+    while k < 5 and ((w << k) < out_w or (h << k) < out_h):
+        k += 1
+    return k
+
+
+def _frames_yuv_host(matrix, y, u, v, uv, chroma, noise, scale, iterations, range, opts, out_nv12, wide=None, size=None):
     """the host frame calls: matrix = None: w2xc_process_frames_yuv_u8, else w2xc_process_frames_yuv_u8_rgb with that matrix; wide = (depth, pack, out_pack):
-    their forms on uint16 arrays, w2xc_process_frames_yuv_u16[_rgb]"""
+    their forms on uint16 arrays, w2xc_process_frames_yuv_u16[_rgb]; size = (out_w, out_h): their _sized forms"""
     dt, name = (np.uint8, "process_frames_yuv_u8") if wide is None else (np.uint16, "process_frames_yuv_u16")
 
     def u8(a, nd, what):
@@ -1098,8 +1119,8 @@ def _frames_yuv_host(matrix, y, u, v, uv, chroma, noise, scale, iterations, rang
         u, v = u8(u, 3, "u"), u8(v, 3, "v")
         if u.shape != (n, ch, cw) or v.shape != (n, ch, cw):
             raise ValueError("%s: u and v must be (n, %d, %d), got %r and %r" % (name, ch, cw, u.shape, v.shape))
-    W, H = w << iterations, h << iterations
-    ocw, och = yuv_chroma_size(W, H, chroma)
+    W, H = (w << iterations, h << iterations) if size is None else size
+    ocw, och = yuv_chroma_size(max(W, 0), max(H, 0), chroma)
     nv12 = (uv is not None) if out_nv12 is None else bool(out_nv12)
     oy = np.empty((n, max(H, 0), max(W, 0)), dt)
     ou = ov = ouv = None
@@ -1112,13 +1133,22 @@ def _frames_yuv_host(matrix, y, u, v, uv, chroma, noise, scale, iterations, rang
     if wide is not None:
         depth, pack, out_pack = wide
         si, so = _yuv_side(y, u, v, uv, pack), _yuv_side(oy, ou, ov, ouv, pack if out_pack is None else out_pack)
-        if matrix is None:
+        if size is not None and matrix is None:
+            _check(_lib.w2xc_process_frames_yuv_u16_sized(*_handles(noise, scale), n, w, h, chroma, range, depth, C.byref(si), W, H, C.byref(so), iterations, po))
+        elif size is not None:
+            _check(_lib.w2xc_process_frames_yuv_u16_rgb_sized(*_handles(noise, scale), n, w, h, chroma, range, depth, matrix, C.byref(si), W, H, C.byref(so),
+                                                              iterations, po))
+        elif matrix is None:
             _check(_lib.w2xc_process_frames_yuv_u16(*_handles(noise, scale), n, w, h, chroma, range, depth, C.byref(si), C.byref(so), iterations, po))
         else:
             _check(_lib.w2xc_process_frames_yuv_u16_rgb(*_handles(noise, scale), n, w, h, chroma, range, depth, matrix, C.byref(si), C.byref(so), iterations, po))
         return (oy,) if chroma == YUV_400 else (oy, ouv) if nv12 else (oy, ou, ov)
     si, so = _yuv_side(y, u, v, uv), _yuv_side(oy, ou, ov, ouv)
-    if matrix is None:
+    if size is not None and matrix is None:
+        _check(_lib.w2xc_process_frames_yuv_u8_sized(*_handles(noise, scale), n, w, h, chroma, range, C.byref(si), W, H, C.byref(so), iterations, po))
+    elif size is not None:
+        _check(_lib.w2xc_process_frames_yuv_u8_rgb_sized(*_handles(noise, scale), n, w, h, chroma, range, matrix, C.byref(si), W, H, C.byref(so), iterations, po))
+    elif matrix is None:
         _check(_lib.w2xc_process_frames_yuv_u8(*_handles(noise, scale), n, w, h, chroma, range, C.byref(si), C.byref(so), iterations, po))
     else:
         _check(_lib.w2xc_process_frames_yuv_u8_rgb(*_handles(noise, scale), n, w, h, chroma, range, matrix, C.byref(si), C.byref(so), iterations, po))
@@ -1237,3 +1267,74 @@ def chroma2x_u16_sited_device(d_src, n, src_frame_stride_bytes, src_stride_bytes
     (w2xc_chroma2x_u16_sited_device)."""
     _check(_lib.w2xc_chroma2x_u16_sited_device(C.c_void_p(d_src), n, src_frame_stride_bytes, src_stride_bytes, src_px, src_pack, cw, ch, depth, C.c_void_p(d_dst),
                                                dst_frame_stride_bytes, dst_stride_bytes, dst_px, dst_pack, ow, oh, cosited, C.c_void_p(stream)))
+
+
+# ---- Sized YUV frames: an output size, up to four 2x steps, ITERATIONS_AUTO (include/w2xc_hip.h, "Sized YUV frames") ----
+def process_frames_yuv_u8_sized(y, out_w, out_h, u=None, v=None, uv=None, chroma=YUV_420, noise=None, scale=None, iterations=ITERATIONS_AUTO, range=RANGE_LIMITED,
+                                opts=None, out_nv12=None):
+    """process_frames_yuv_u8 with the output frame out_w x out_h: iterations 0 .. 4 or ITERATIONS_AUTO, w <= out_w <= w << iterations and the same in y; the last
+    level is shrunk linearly, chroma resized in one step (w2xc_process_frames_yuv_u8_sized)."""
+    return _frames_yuv_host(None, y, u, v, uv, chroma, noise, scale, iterations, range, opts, out_nv12, size=(out_w, out_h))
+
+
+def process_frames_yuv_u8_rgb_sized(y, out_w, out_h, u=None, v=None, uv=None, chroma=YUV_420, noise=None, scale=None, iterations=ITERATIONS_AUTO, range=RANGE_LIMITED,
+                                    matrix=MATRIX_BT709, opts=None, out_nv12=None):
+    """process_frames_yuv_u8_rgb with the output frame out_w x out_h (w2xc_process_frames_yuv_u8_rgb_sized)."""
+    return _frames_yuv_host(matrix, y, u, v, uv, chroma, noise, scale, iterations, range, opts, out_nv12, size=(out_w, out_h))
+
+
+def process_frames_yuv_u16_sized(y, out_w, out_h, u=None, v=None, uv=None, chroma=YUV_420, noise=None, scale=None, iterations=ITERATIONS_AUTO, range=RANGE_LIMITED,
+                                 opts=None, out_nv12=None, depth=10, pack=PACK_LOW, out_pack=None):
+    """process_frames_yuv_u16 with the output frame out_w x out_h (w2xc_process_frames_yuv_u16_sized)."""
+    return _frames_yuv_host(None, y, u, v, uv, chroma, noise, scale, iterations, range, opts, out_nv12, wide=(depth, pack, out_pack), size=(out_w, out_h))
+
+
+def process_frames_yuv_u16_rgb_sized(y, out_w, out_h, u=None, v=None, uv=None, chroma=YUV_420, noise=None, scale=None, iterations=ITERATIONS_AUTO,
+                                     range=RANGE_LIMITED, matrix=MATRIX_BT709, opts=None, out_nv12=None, depth=10, pack=PACK_LOW, out_pack=None):
+    """process_frames_yuv_u16_rgb with the output frame out_w x out_h (w2xc_process_frames_yuv_u16_rgb_sized)."""
+    return _frames_yuv_host(matrix, y, u, v, uv, chroma, noise, scale, iterations, range, opts, out_nv12, wide=(depth, pack, out_pack), size=(out_w, out_h))
+
+
+def process_frames_yuv_u8_sized_device(n, w, h, chroma, d_in, out_w, out_h, d_out, noise=None, scale=None, iterations=ITERATIONS_AUTO, range=RANGE_LIMITED, stream=0,
+                                       opts=None):
+    """Device-pointer form (w2xc_process_frames_yuv_u8_sized_device): n frames of w x h described by the YuvPlanes d_in, the out_w x out_h frames by d_out.
+    Asynchronous on `stream`."""
+    _check(_lib.w2xc_process_frames_yuv_u8_sized_device(*_handles(noise, scale), n, w, h, chroma, range, C.byref(d_in), out_w, out_h, C.byref(d_out), iterations,
+                                                        C.c_void_p(stream), C.byref(opts) if opts is not None else None))
+
+
+def process_frames_yuv_u8_rgb_sized_device(n, w, h, chroma, d_in, out_w, out_h, d_out, noise=None, scale=None, iterations=ITERATIONS_AUTO, range=RANGE_LIMITED,
+                                           matrix=MATRIX_BT709, stream=0, opts=None):
+    """Device-pointer form (w2xc_process_frames_yuv_u8_rgb_sized_device); arguments as process_frames_yuv_u8_sized_device, and the colour matrix."""
+    _check(_lib.w2xc_process_frames_yuv_u8_rgb_sized_device(*_handles(noise, scale), n, w, h, chroma, range, matrix, C.byref(d_in), out_w, out_h, C.byref(d_out),
+                                                            iterations, C.c_void_p(stream), C.byref(opts) if opts is not None else None))
+
+
+def process_frames_yuv_u16_sized_device(n, w, h, chroma, d_in, out_w, out_h, d_out, noise=None, scale=None, iterations=ITERATIONS_AUTO, range=RANGE_LIMITED, stream=0,
+                                        opts=None, depth=10):
+    """Device-pointer form (w2xc_process_frames_yuv_u16_sized_device): Yuv16Planes on both sides, their `pack` included."""
+    _check(_lib.w2xc_process_frames_yuv_u16_sized_device(*_handles(noise, scale), n, w, h, chroma, range, depth, C.byref(d_in), out_w, out_h, C.byref(d_out),
+                                                         iterations, C.c_void_p(stream), C.byref(opts) if opts is not None else None))
+
+
+def process_frames_yuv_u16_rgb_sized_device(n, w, h, chroma, d_in, out_w, out_h, d_out, noise=None, scale=None, iterations=ITERATIONS_AUTO, range=RANGE_LIMITED,
+                                            matrix=MATRIX_BT709, stream=0, opts=None, depth=10):
+    """Device-pointer form (w2xc_process_frames_yuv_u16_rgb_sized_device); arguments as process_frames_yuv_u16_sized_device, and the colour matrix."""
+    _check(_lib.w2xc_process_frames_yuv_u16_rgb_sized_device(*_handles(noise, scale), n, w, h, chroma, range, depth, matrix, C.byref(d_in), out_w, out_h,
+                                                             C.byref(d_out), iterations, C.c_void_p(stream), C.byref(opts) if opts is not None else None))
+
+
+def chroma_resize_u8_device(d_src, n, src_frame_stride_bytes, src_stride_bytes, src_px, cw, ch, d_dst, dst_frame_stride_bytes, dst_stride_bytes, dst_px, ow, oh,
+                            w, h, out_w, out_h, sub_x, sub_y, cosited=0, stream=0):
+    """the bicubic of chroma2x_u8_sited_device at any ratio: n chroma byte planes of cw x ch -> ow x oh, positions by the LUMA sizes w x h -> out_w x out_h
+    (out_w >= w, out_h >= h), the layout's subsampling flags sub_x / sub_y (0 or 1) and `cosited` (w2xc_chroma_resize_u8_device)."""
+    _check(_lib.w2xc_chroma_resize_u8_device(C.c_void_p(d_src), n, src_frame_stride_bytes, src_stride_bytes, src_px, cw, ch, C.c_void_p(d_dst), dst_frame_stride_bytes,
+                                             dst_stride_bytes, dst_px, ow, oh, w, h, out_w, out_h, sub_x, sub_y, cosited, C.c_void_p(stream)))
+
+
+def chroma_resize_u16_device(d_src, n, src_frame_stride_bytes, src_stride_bytes, src_px, src_pack, cw, ch, depth, d_dst, dst_frame_stride_bytes, dst_stride_bytes,
+                             dst_px, dst_pack, ow, oh, w, h, out_w, out_h, sub_x, sub_y, cosited=0, stream=0):
+    """chroma_resize_u8_device on 16-bit words of `depth` bits, either packing on either side (w2xc_chroma_resize_u16_device); strides in bytes"""
+    _check(_lib.w2xc_chroma_resize_u16_device(C.c_void_p(d_src), n, src_frame_stride_bytes, src_stride_bytes, src_px, src_pack, cw, ch, depth, C.c_void_p(d_dst),
+                                              dst_frame_stride_bytes, dst_stride_bytes, dst_px, dst_pack, ow, oh, w, h, out_w, out_h, sub_x, sub_y, cosited,
+                                              C.c_void_p(stream)))

@@ -6,6 +6,7 @@
 #include "../../include/w2xc_hip.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <utility>
 #include <vector>
@@ -140,12 +141,22 @@ inline ChromaSize yuv_chroma_size(int w, int h, int chroma)
 }
 // bytes from the first to behind the last sample of a chroma row of cw samples, px samples apart, of bps bytes each (1: bytes; 2: 16-bit words)
 inline size_t chroma_row_bytes(int cw, int px, int bps = 1) { return ((size_t)px * (cw - 1) + 1) * bps; }
-// the float planes of one frame of the Y call: two luma planes per level
-inline size_t yuv_aux_floats(int w, int h, int iterations) { return 2 * plane_floats(w, h) + (iterations ? 2 * plane_floats(2 * w, 2 * h) : 0); }
-// ... of the call through RGB models: three per level, the noise pass's output included
-inline size_t yuv_rgb_aux_floats(bool noise, int w, int h, int iterations)
+// the float planes of one frame of the Y call: two luma planes per level; a sized call ("Sized YUV frames") whose output out_w x out_h is not the last level
+// has one more, the shrunk plane (out_w = 0: the output is the last level)
+inline size_t yuv_aux_floats(int w, int h, int iterations, int out_w = 0, int out_h = 0)
 {
-    return 3 * ((noise ? 2 : 1) * plane_floats(w, h) + (iterations ? plane_floats(2 * w, 2 * h) : 0));
+    size_t need = 2 * plane_floats(w, h);
+    for (int i = 1; i <= iterations; i++) need += 2 * plane_floats(w << i, h << i);
+    if (out_w && (out_w != w << iterations || out_h != h << iterations)) need += plane_floats(out_w, out_h);
+    return need;
+}
+// ... of the call through RGB models: three per level, the noise pass's output included, and the three shrunk planes of a sized call
+inline size_t yuv_rgb_aux_floats(bool noise, int w, int h, int iterations, int out_w = 0, int out_h = 0)
+{
+    size_t need = (noise ? 2 : 1) * plane_floats(w, h);
+    for (int i = 1; i <= iterations; i++) need += plane_floats(w << i, h << i);
+    if (out_w && (out_w != w << iterations || out_h != h << iterations)) need += plane_floats(out_w, out_h);
+    return 3 * need;
 }
 // the bytes of one frame's planes: w x h luma, two planes of cw x ch chroma, bps bytes per sample
 inline size_t yuv_frame_bytes(int w, int h, int cw, int ch, int bps = 1) { return ((size_t)w * h + 2 * (size_t)cw * ch) * bps; }
@@ -200,6 +211,43 @@ inline YuvTileGrid chroma2x_tile_grid(int ow, int oh, long long per_tile, int tq
 inline YuvTileGrid yuv_rgb_tile_grid(int cw, int ch, int n, int tcx, int tcy, long long cap)
 {
     return yuv_tile_grid((cw + tcx - 1) / tcx, (ch + tcy - 1) / tcy, n, cap);
+}
+
+
+// ---- the chroma of a sized frame call ("Sized YUV frames": k_chroma_resize_u8 / _u16, w2xc_yuv_sized.hip / w2xc_yuv16_sized.hip) ----
+// (these few are the kernels' own arithmetic too: host and device where a HIP compiler reads them, plain C++ elsewhere)
+#if defined(__HIP__)
+#define W2XC_GEOM_HD __host__ __device__
+#else
+#define W2XC_GEOM_HD
+#endif
+// W2XC_ITERATIONS_AUTO: the smallest k with (w << k) >= out_w and (h << k) >= out_h; 5 where 4 steps do not reach (the range check refuses it)
+inline int sized_auto_iterations(int w, int h, int out_w, int out_h)
+{
+    int k = 0;
+    while (k < 5 && (((long long)w << k) < out_w || ((long long)h << k) < out_h)) k++;
+    return k;
+}
+// One axis of the resize: r = (double)luma_in / luma_out, the LUMA ratio (<= 1: the output is never smaller than the input), and o, the offset of a chroma
+// sample against its coordinate: 0.5 on a centred or unsubsampled axis, 0.25 on a co-sited one.  Output sample m reads source coordinate
+// pos = (m + o) * r - o: three double operations in this order; s = floor(pos), t = (float)(pos - s), taps s - 1 .. s + 2 clamped into the plane.
+struct ChromaAxis { double r, o; };
+inline ChromaAxis chroma_axis(int luma_in, int luma_out, bool subsampled, bool cosited) { return {(double)luma_in / (double)luma_out, subsampled && cosited ? 0.25 : 0.5}; }
+W2XC_GEOM_HD inline double chroma_resize_pos(int m, double r, double o)
+{
+    const double a = (double)m + o;
+    const double b = a * r;
+    return b - o;
+}
+W2XC_GEOM_HD inline int chroma_resize_floor(double pos) { return (int)floor(pos); }
+// A tile of outputs that starts at m0 keeps its source window in LDS from source sample chroma_resize_origin(m0) on: the first tap of its first output.
+// With r <= 1 the floors of `len` consecutive outputs span at most `len` source samples, so the window with its taps is at most len + 3 wide (32 -> 35, 16 -> 19:
+// the window of the 2x kernels); tests/cpp/yuv_sized_geom_test.cpp holds that bound over a sweep of ratios and sizes.
+W2XC_GEOM_HD inline int chroma_resize_origin(int m0, double r, double o) { return chroma_resize_floor(chroma_resize_pos(m0, r, o)) - 1; }
+// the launch grid: tiles of tx x ty OUTPUT samples, per_tile turns per tile (frames, or frames x planes)
+inline YuvTileGrid chroma_resize_tile_grid(int ow, int oh, long long per_tile, int tx, int ty, long long cap)
+{
+    return yuv_tile_grid((ow + tx - 1) / tx, (oh + ty - 1) / ty, per_tile, cap);
 }
 
 }  // namespace w2xc_eng

@@ -4,6 +4,9 @@
 // The same calls on 16-bit words (w2xc_process_frames_yuv_u16*, "16-bit YUV frames"): the checks, the geometry, the mirror and the sub-batches take the sample
 // size; the ends of a route (luma_in, luma_out, chroma_out, to_rgb, from_rgb) pick their launcher (w2xc_yuv16.hip, w2xc_yuv16_rgb.hip) by it, and nothing else
 // does: the routes and the bodies of the building blocks read the same for both widths.
+// The sized forms (w2xc_process_frames_yuv_*_sized*, "Sized YUV frames") are the same two routes with `iterations` scale passes, a linear shrink of the last
+// level where the output is smaller than it, and chroma resized in one step (w2xc_yuv_sized.hip, w2xc_yuv16_sized.hip); the base calls are sized calls whose
+// output is the last level.
 #include "w2xc_image.hpp"
 
 namespace w2xc_eng {
@@ -20,8 +23,12 @@ struct YuvGeom {
     int matrix = 0;         // ... by this colour matrix (W2XC_MATRIX_*)
     int cw = 0, ch = 0;     // the chroma planes of a w x h frame (0 x 0: W2XC_YUV_400)
     int ocw = 0, och = 0;   // ... of the call's output frame
-    int W = 0, H = 0;       // the output frame
+    int W = 0, H = 0;       // the last level of the passes: (w << iterations) x (h << iterations)
+    int ow = 0, oh = 0;     // the output frame: W x H, or what a sized call names (w <= ow <= W, h <= oh <= H: the linear shrink of the last level)
+    ChromaAxis ax = {1.0, 0.5}, ay = {1.0, 0.5};   // chroma from the input plane to the output plane, per axis (chroma_axis: the LUMA ratio, the siting's offset)
 };
+// what chroma_out runs: the samples as they are, the bicubic 2x kernels, or the resize kernels at g.ax / g.ay
+enum ChromaMode { CHROMA_COPY, CHROMA_2X, CHROMA_RESIZE };
 // (the sizes of the chroma planes, the float planes and the bytes of a frame: yuv_chroma_size, yuv_aux_floats, yuv_rgb_aux_floats, yuv_frame_bytes -- w2xc_host_geom.hpp)
 
 // One side of a call as the engine takes it, from either struct of the interface: byte pointers, strides in bytes, c_px in samples, pack (0 for bytes)
@@ -127,12 +134,24 @@ int check_yuv_rgb_precision(const ImageCall &c)
 
 // everything both forms refuse, before a device is touched; *g = the geometry (g->bps and g->depth are the caller's), *sub = frames per sub-batch.  rgb: the call
 // is w2xc_process_frames_yuv_u8_rgb* / _u16_rgb* -- RGB models, or an upconv head model as scale model, and a colour matrix; a grey frame (W2XC_YUV_400) belongs
-// to the Y call
-int check_yuv_call(ImageCall &c, bool rgb, int n, int chroma, int range, int matrix, const YuvSide *in, const YuvSide *out, YuvGeom *g, int *sub)
+// to the Y call.  sz: the sized form ("Sized YUV frames") -- iterations 0 .. 4 or W2XC_ITERATIONS_AUTO (resolved here, into c.iterations) and an output size
+// inside [w, w << iterations] x [h, h << iterations]; null: a base call, iterations 0 .. 1 and the last level as output, refused in the words it always had
+struct YuvOutSize { int w, h; };
+int check_yuv_call(ImageCall &c, bool rgb, int n, int chroma, int range, int matrix, const YuvSide *in, const YuvSide *out, YuvGeom *g, int *sub,
+                   const YuvOutSize *sz = nullptr)
 {
+    if (sz) {   // (AUTO is resolved before the models are looked at: "iterations >= 1 without a scale model" is about the resolved count)
+        if (c.w <= 0 || c.h <= 0 || c.w > (1 << 22) || c.h > (1 << 22)) return fail(W2XC_ERR_ARG, "bad frame size");
+        if (c.iterations == W2XC_ITERATIONS_AUTO) c.iterations = sized_auto_iterations(c.w, c.h, sz->w, sz->h);
+        if (c.iterations < 0 || c.iterations > 4)
+            return fail(W2XC_ERR_ARG, "iterations must be 0 .. 4 or W2XC_ITERATIONS_AUTO (got %d; an output of %d x %d from %d x %d)", c.iterations, sz->w, sz->h, c.w, c.h);
+        if (sz->w < c.w || sz->h < c.h || sz->w > c.w << c.iterations || sz->h > c.h << c.iterations)
+            return fail(W2XC_ERR_ARG, "the output size %d x %d lies outside %d .. %d x %d .. %d (iterations = %d)", sz->w, sz->h, c.w, c.w << c.iterations, c.h,
+                        c.h << c.iterations, c.iterations);
+    }
     int rc = check_process_args(c, rgb);
     if (rc || (rc = rgb ? check_yuv_rgb_precision(c) : check_y_models(c))) return rc;
-    if (c.iterations < 0 || c.iterations > 1) return fail(W2XC_ERR_ARG, "iterations must be 0 or 1 (got %d)", c.iterations);
+    if (!sz && (c.iterations < 0 || c.iterations > 1)) return fail(W2XC_ERR_ARG, "iterations must be 0 or 1 (got %d)", c.iterations);
     if (n < 1 || n > (1 << 20)) return fail(W2XC_ERR_ARG, "batch of %d frames", n);
     if (c.w <= 0 || c.h <= 0 || c.w > (1 << 22) || c.h > (1 << 22)) return fail(W2XC_ERR_ARG, "bad frame size");
     if ((rc = check_chroma_range(chroma, range, &chroma, &g->cosited)) || (rc = check_depth(g->bps, g->depth))) return rc;
@@ -141,14 +160,18 @@ int check_yuv_call(ImageCall &c, bool rgb, int n, int chroma, int range, int mat
     if (rgb && (rc = check_matrix(matrix))) return rc;
     g->chroma = chroma; g->range = range; g->rgb = rgb; g->matrix = matrix;
     g->W = c.w << c.iterations; g->H = c.h << c.iterations;
-    const ChromaSize ci = yuv_chroma_size(c.w, c.h, chroma), co = yuv_chroma_size(g->W, g->H, chroma);
+    g->ow = sz ? sz->w : g->W; g->oh = sz ? sz->h : g->H;
+    const ChromaSize ci = yuv_chroma_size(c.w, c.h, chroma), co = yuv_chroma_size(g->ow, g->oh, chroma);
     g->cw = ci.cw; g->ch = ci.ch; g->ocw = co.cw; g->och = co.ch;
+    g->ax = chroma_axis(c.w, g->ow, chroma != W2XC_YUV_444, g->cosited & W2XC_CHROMA_COSITED_X);
+    g->ay = chroma_axis(c.h, g->oh, chroma == W2XC_YUV_420, g->cosited & W2XC_CHROMA_COSITED_Y);
     std::vector<std::pair<std::pair<uintptr_t, uintptr_t>, int>> iv;
-    if ((rc = check_yuv_side(in, g->bps, n, c.w, c.h, g->cw, g->ch, 0, iv)) || (rc = check_yuv_side(out, g->bps, n, g->W, g->H, g->ocw, g->och, 1, iv))) return rc;
+    if ((rc = check_yuv_side(in, g->bps, n, c.w, c.h, g->cw, g->ch, 0, iv)) || (rc = check_yuv_side(out, g->bps, n, g->ow, g->oh, g->ocw, g->och, 1, iv))) return rc;
     if ((rc = check_batch_overlap(iv))) return rc;
-    c.fw = g->W; c.fh = g->H;
-    const size_t per = (rgb ? yuv_rgb_aux_floats(c.mn != nullptr, c.w, c.h, c.iterations) : yuv_aux_floats(c.w, c.h, c.iterations)) * sizeof(float) +
-                       yuv_frame_bytes(c.w, c.h, g->cw, g->ch, g->bps) + yuv_frame_bytes(g->W, g->H, g->ocw, g->och, g->bps);
+    c.fw = g->ow; c.fh = g->oh;
+    const size_t per = (rgb ? yuv_rgb_aux_floats(c.mn != nullptr, c.w, c.h, c.iterations, g->ow, g->oh) : yuv_aux_floats(c.w, c.h, c.iterations, g->ow, g->oh)) *
+                           sizeof(float) +
+                       yuv_frame_bytes(c.w, c.h, g->cw, g->ch, g->bps) + yuv_frame_bytes(g->ow, g->oh, g->ocw, g->och, g->bps);
     return plan_image_call(rgb ? PLAN_RGB : PLAN_Y, c, sub, per, 1, g->bps == 2 ? "w2xc_process_frames_yuv_u16_rgb*" : "w2xc_process_frames_yuv_u8_rgb*");
 }
 
@@ -169,9 +192,15 @@ hipError_t luma_out(const YuvGeom &g, const float *y, long long ps, int w, int h
 {
     return g.bps == 2 ? w2xc_launch_plane_to_y16(y, ps, w, h, g.range, g.depth, luma_words(s), n, st) : w2xc_launch_plane_to_y8(y, ps, w, h, g.range, luma_planes(s), n, st);
 }
-// chroma samples to chroma samples: g.cw x g.ch -> the leading g.ocw x g.och of the bicubic 2x, or (no 2x step) as they are.  A null v: one plane per frame
-hipError_t chroma_out(const YuvGeom &g, bool up2x, const YuvSide &in, const YuvSide &out, int n, hipStream_t st)
+// chroma samples to chroma samples: g.cw x g.ch -> the leading g.ocw x g.och of the bicubic 2x, or (CHROMA_COPY) as they are, or (CHROMA_RESIZE) the
+// g.ocw x g.och samples of the bicubic at g.ax / g.ay.  A null v: one plane per frame
+hipError_t chroma_out(const YuvGeom &g, ChromaMode mode, const YuvSide &in, const YuvSide &out, int n, hipStream_t st)
 {
+    if (mode == CHROMA_RESIZE)
+        return g.bps == 2 ? w2xc_launch_chroma_resize_u16(chroma_words(in), words(in.v), g.cw, g.ch, chroma_words(out), words(out.v), g.ocw, g.och, g.depth, g.ax.r, g.ax.o,
+                                                           g.ay.r, g.ay.o, n, st)
+                          : w2xc_launch_chroma_resize_u8(chroma_planes(in), in.v, g.cw, g.ch, chroma_planes(out), out.v, g.ocw, g.och, g.ax.r, g.ax.o, g.ay.r, g.ay.o, n, st);
+    const bool up2x = mode == CHROMA_2X;
     if (up2x && g.cosited)
         return g.bps == 2 ? w2xc_launch_chroma2x_u16_sited(chroma_words(in), words(in.v), g.cw, g.ch, chroma_words(out), words(out.v), g.ocw, g.och, g.depth, g.cosited, n, st)
                           : w2xc_launch_chroma2x_u8_sited(chroma_planes(in), in.v, g.cw, g.ch, chroma_planes(out), out.v, g.ocw, g.och, g.cosited, n, st);
@@ -199,15 +228,24 @@ hipError_t from_rgb(const YuvGeom &g, const float *rgb, long long is, long long 
                       : w2xc_launch_rgb_to_yuv8(rgb, is, ps, w, h, g.chroma, g.range, g.matrix, luma_planes(s), chroma_planes(s), s.v, n, st);
 }
 
+// What a frame call runs for its chroma: the samples as they are where the output has the input's size, the bicubic 2x kernels at exactly twice it (the resize
+// kernels' arithmetic at r = 0.5 is theirs, byte for byte: the header says why), the resize kernels everywhere else
+ChromaMode frame_chroma_mode(const ImageCall &c, const YuvGeom &g)
+{
+    if (g.ow == c.w && g.oh == c.h) return CHROMA_COPY;
+    return g.ow == 2 * c.w && g.oh == 2 * c.h ? CHROMA_2X : CHROMA_RESIZE;
+}
+
 // A sub-batch of S frames (S <= cap, the call's sub-batch size: the planes are sized by cap): luma samples -> planes, the noise pass, the scale pass with the
 // nearest-2x folded into layer 1 -- run_batch, so bands, precisions, named kernels and fusion settings are those of w2xc_convert_batch_device --, planes ->
 // luma samples; chroma in ONE launch, samples to samples.  The ends are those of the sample width; everything between them is the same.
 int process_yuv_device(const ImageCall &c, const YuvGeom &g, int S, int cap, const YuvSide &in, const YuvSide &out)
 {
     DevCtx *own = c.ctx.owner();
-    if (int rc = reserve_aux(own, 0, yuv_aux_floats(c.w, c.h, c.iterations) * (size_t)cap)) return rc;
+    if (int rc = reserve_aux(own, 0, yuv_aux_floats(c.w, c.h, c.iterations, g.ow, g.oh) * (size_t)cap)) return rc;
     float *base = aux_planes(own, 0);
-    long long ps = (long long)plane_floats(c.w, c.h);
+    int lw = c.w, lh = c.h;   // the level the luma planes are on
+    long long ps = (long long)plane_floats(lw, lh);
     float *y = base, *yn = y + (size_t)cap * ps;
     base += 2 * (size_t)cap * ps;
     HIP_TRY(luma_in(g, in, c.w, c.h, y, ps, S, c.st));
@@ -215,13 +253,20 @@ int process_yuv_device(const ImageCall &c, const YuvGeom &g, int S, int cap, con
         if (int rc = run_batch(c.mn, c.ctx.cn, S, 0, {y, (size_t)c.w, ps}, c.w, c.h, {yn, (size_t)c.w, ps}, c.st, c.o)) return rc;
         y = yn;
     }
-    if (c.iterations) {
-        const long long ps2 = (long long)plane_floats(g.W, g.H);
-        if (int rc = run_batch(c.msc, c.ctx.cs, S, 1, {y, (size_t)c.w, ps}, c.w, c.h, {base, (size_t)g.W, ps2}, c.st, c.o)) return rc;
-        y = base; ps = ps2;
+    for (int it = 0; it < c.iterations; it++) {   // (unclipped between the passes; a level's share of the planes is two per frame, yuv_aux_floats)
+        const int nw = 2 * lw, nh = 2 * lh;
+        const long long ps2 = (long long)plane_floats(nw, nh);
+        if (int rc = run_batch(c.msc, c.ctx.cs, S, 1, {y, (size_t)lw, ps}, lw, lh, {base, (size_t)nw, ps2}, c.st, c.o)) return rc;
+        y = base; ps = ps2; lw = nw; lh = nh;
+        base += 2 * (size_t)cap * ps2;
     }
-    HIP_TRY(luma_out(g, y, ps, g.W, g.H, out, S, c.st));
-    if (g.cw) HIP_TRY(chroma_out(g, c.iterations != 0, in, out, S, c.st));
+    if (g.ow != lw || g.oh != lh) {   // a sized call below its last level: w2xc_resize_linear_device on every luma plane, ONE launch
+        const long long pss = (long long)plane_floats(g.ow, g.oh);
+        HIP_TRY(w2xc_launch_resize_linear_batch(y, y, S, ps, lw, lh, base, pss, g.ow, g.oh, S, c.st));
+        y = base; ps = pss;
+    }
+    HIP_TRY(luma_out(g, y, ps, g.ow, g.oh, out, S, c.st));
+    if (g.cw) HIP_TRY(chroma_out(g, frame_chroma_mode(c, g), in, out, S, c.st));
     return W2XC_OK;
 }
 
@@ -232,13 +277,18 @@ int process_yuv_rgb_device(const ImageCall &c, const YuvGeom &g, int S, int cap,
 {
     DevCtx *own = c.ctx.owner();
     RgbPlan R;   // (float planes at both ends: no layer takes a uint8 image)
-    R.floats = yuv_rgb_aux_floats(c.mn != nullptr, c.w, c.h, c.iterations);
+    R.floats = yuv_rgb_aux_floats(c.mn != nullptr, c.w, c.h, c.iterations, g.ow, g.oh);
     if (int rc = reserve_aux(own, 0, R.floats * (size_t)cap)) return rc;
     float *base = aux_planes(own, 0);
     RgbLevel L = {base, c.w, c.h, (long long)plane_floats(c.w, c.h)};
     base += 3 * (size_t)cap * L.ps;
     HIP_TRY(to_rgb(g, in, c.w, c.h, L.p, 3 * L.ps, L.ps, S, c.st));
     if (int rc = rgb_passes(c, R, S, cap, U8In{nullptr, 0, 0}, U8Out{nullptr, 0, 0}, 0, &base, nullptr, &L)) return rc;
+    if (g.ow != L.w || g.oh != L.h) {   // a sized call below its last level: w2xc_resize_linear_device on the 3 S planes of the level (ps apart), ONE launch
+        const long long pss = (long long)plane_floats(g.ow, g.oh);
+        HIP_TRY(w2xc_launch_resize_linear_batch(L.p, L.p, 3 * S, L.ps, L.w, L.h, base, pss, g.ow, g.oh, 3 * S, c.st));
+        L = {base, g.ow, g.oh, pss};
+    }
     HIP_TRY(from_rgb(g, L.p, 3 * L.ps, L.ps, L.w, L.h, out, S, c.st));
     return W2XC_OK;
 }
@@ -254,14 +304,25 @@ struct YuvCall {
     bool rgb;
     int n, chroma, range, matrix;
     int bps = 1, depth = 8;
+    bool sized = false;   // w2xc_process_frames_yuv_*_sized*: the output frame is out_w x out_h, iterations 0 .. 4 or W2XC_ITERATIONS_AUTO
+    int out_w = 0, out_h = 0;
 };
+
+// ... of a sized call
+YuvCall sized_call(bool rgb, int n, int chroma, int range, int matrix, int bps, int depth, int out_w, int out_h)
+{
+    YuvCall k{rgb, n, chroma, range, matrix, bps, depth};
+    k.sized = true; k.out_w = out_w; k.out_h = out_h;
+    return k;
+}
 
 int frames_yuv_device(ImageCall c, const YuvCall &k, const YuvSide *in, const YuvSide *out)
 {
     YuvGeom g;
     g.bps = k.bps; g.depth = k.depth;
     int sub = 1;
-    int rc = check_yuv_call(c, k.rgb, k.n, k.chroma, k.range, k.matrix, in, out, &g, &sub);
+    const YuvOutSize sz = {k.out_w, k.out_h};
+    int rc = check_yuv_call(c, k.rgb, k.n, k.chroma, k.range, k.matrix, in, out, &g, &sub, k.sized ? &sz : nullptr);
     if (rc) return rc;
     sub = std::min(sub, k.n);
     LockedCtx lc;
@@ -311,7 +372,8 @@ int frames_yuv_host(ImageCall c, const YuvCall &k, const YuvSide *in, const YuvS
     g.bps = k.bps; g.depth = k.depth;
     int sub = 1;
     const int n = k.n;
-    int rc = check_yuv_call(c, k.rgb, n, k.chroma, k.range, k.matrix, in, out, &g, &sub);
+    const YuvOutSize sz = {k.out_w, k.out_h};
+    int rc = check_yuv_call(c, k.rgb, n, k.chroma, k.range, k.matrix, in, out, &g, &sub, k.sized ? &sz : nullptr);
     if (rc) return rc;
     if (g.cw) for (const YuvSide *s : {in, out})
         if (s->c_px == 2 && s->v != s->u + g.bps && s->u != s->v + g.bps)
@@ -325,7 +387,7 @@ int frames_yuv_host(ImageCall c, const YuvCall &k, const YuvSide *in, const YuvS
     c.st = nullptr;
     DevCtx *own = c.ctx.owner();
     const YuvMirrorLayout li = yuv_mirror_layout(in->c_px, in->u < in->v, sub, c.w, c.h, g.cw, g.ch, g.bps),
-                          lo = yuv_mirror_layout(out->c_px, out->u < out->v, sub, g.W, g.H, g.ocw, g.och, g.bps);
+                          lo = yuv_mirror_layout(out->c_px, out->u < out->v, sub, g.ow, g.oh, g.ocw, g.och, g.bps);
     if ((rc = own->img_io.reserve(li.bytes + lo.bytes, "the frames"))) return rc;
     unsigned char *dev = own->img_io.as<unsigned char>();
     YuvMirror mi = yuv_mirror(*in, dev, li), mo = yuv_mirror(*out, dev + li.bytes, lo);
@@ -333,7 +395,7 @@ int frames_yuv_host(ImageCall c, const YuvCall &k, const YuvSide *in, const YuvS
         if (int r = yuv_copy(mi, *in, b0, S, (size_t)c.w * g.bps, c.h, g.ch, true)) return r;
         if (int r = process_yuv_sub_batch(c, g, S, sub, mi.d, mo.d)) { hipDeviceSynchronize(); return r; }
         HIP_TRY(hipDeviceSynchronize());
-        return yuv_copy(mo, *out, b0, S, (size_t)g.W * g.bps, g.H, g.och, false);
+        return yuv_copy(mo, *out, b0, S, (size_t)g.ow * g.bps, g.oh, g.och, false);
     });
 }
 
@@ -437,7 +499,37 @@ int chroma2x_block(const void *d_src, int bps, int depth, int n, size_t src_fram
     to.u = static_cast<unsigned char *>(d_dst); to.c_frame_stride = dst_frame_stride_bytes; to.c_stride = dst_stride_bytes; to.c_px = dst_px; to.pack = dst_pack;
     YuvGeom g;
     g.bps = bps; g.depth = depth; g.cw = cw; g.ch = ch; g.ocw = ow; g.och = oh; g.cosited = cosited;
-    HIP_TRY(chroma_out(g, true, in, to, n, (hipStream_t)hip_stream));
+    HIP_TRY(chroma_out(g, CHROMA_2X, in, to, n, (hipStream_t)hip_stream));
+    return W2XC_OK;
+}
+
+// w2xc_chroma_resize_u8_device / _u16_device: chroma2x_block at any ratio -- the luma sizes of both sides give the ratios, the layout's two subsampling flags
+// with `cosited` the offsets.  Always the resize kernels, at r = 1 and r = 0.5 too
+int chroma_resize_block(const void *d_src, int bps, int depth, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int src_pack, int cw, int ch,
+                        void *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int dst_pack, int ow, int oh, int w, int h, int out_w, int out_h,
+                        int sub_x, int sub_y, int cosited, void *hip_stream)
+{
+    if ((sub_x != 0 && sub_x != 1) || (sub_y != 0 && sub_y != 1)) return fail(W2XC_ERR_ARG, "sub_x / sub_y must be 0 or 1");
+    if (int rc = check_cosited(cosited, sub_x != 0, sub_y != 0)) return rc;
+    if ((src_px != 1 && src_px != 2) || (dst_px != 1 && dst_px != 2)) return fail(W2XC_ERR_ARG, "src_px / dst_px must be 1 or 2");
+    if (w < 1 || h < 1 || out_w < w || out_h < h || out_w > (1 << 22) || out_h > (1 << 22))
+        return fail(W2XC_ERR_ARG, "the luma sizes: %d x %d -> %d x %d (at least 1, at most 2^22, the output never smaller than the input)", w, h, out_w, out_h);
+    if (ow < 1 || oh < 1 || ow > (1 << 22) || oh > (1 << 22)) return fail(W2XC_ERR_ARG, "bad output plane size");
+    const size_t drow = chroma_row_bytes(ow, dst_px, bps), dext = (size_t)(oh - 1) * dst_stride_bytes + drow;
+    if (dst_stride_bytes < drow) return fail(W2XC_ERR_ARG, "row / plane strides below a row / a plane");
+    if (int rc = check_yuv_block_args(d_src, src_frame_stride_bytes, src_stride_bytes, chroma_row_bytes(cw > 0 ? cw : 1, src_px, bps), ch, n, cw, ch, d_dst, dst_frame_stride_bytes, dext, bps)) return rc;
+    if (bps == 2 && (((uintptr_t)d_dst | dst_stride_bytes | dst_frame_stride_bytes) & 1)) return fail(W2XC_ERR_ARG, "16-bit samples need an even pointer and even strides");
+    if ((src_pack != W2XC_PACK_LOW && src_pack != W2XC_PACK_HIGH) || (dst_pack != W2XC_PACK_LOW && dst_pack != W2XC_PACK_HIGH))
+        return fail(W2XC_ERR_ARG, "src_pack / dst_pack must be W2XC_PACK_LOW or W2XC_PACK_HIGH");
+    if (int rc = check_depth(bps, depth)) return rc;
+    YuvSide in, to;   // one plane per frame: no v
+    in.u = static_cast<unsigned char *>(const_cast<void *>(d_src)); in.c_frame_stride = src_frame_stride_bytes; in.c_stride = src_stride_bytes; in.c_px = src_px; in.pack = src_pack;
+    to.u = static_cast<unsigned char *>(d_dst); to.c_frame_stride = dst_frame_stride_bytes; to.c_stride = dst_stride_bytes; to.c_px = dst_px; to.pack = dst_pack;
+    YuvGeom g;
+    g.bps = bps; g.depth = depth; g.cw = cw; g.ch = ch; g.ocw = ow; g.och = oh; g.cosited = cosited;
+    g.ax = chroma_axis(w, out_w, sub_x != 0, cosited & W2XC_CHROMA_COSITED_X);
+    g.ay = chroma_axis(h, out_h, sub_y != 0, cosited & W2XC_CHROMA_COSITED_Y);
+    HIP_TRY(chroma_out(g, CHROMA_RESIZE, in, to, n, (hipStream_t)hip_stream));
     return W2XC_OK;
 }
 
@@ -579,6 +671,78 @@ int w2xc_chroma2x_u16_sited_device(const unsigned short *d_src, int n, size_t sr
 {
     return chroma2x_block(d_src, 2, depth, n, src_frame_stride_bytes, src_stride_bytes, src_px, src_pack, cw, ch, d_dst, dst_frame_stride_bytes, dst_stride_bytes, dst_px,
                           dst_pack, ow, oh, cosited, hip_stream);
+}
+
+// ---- Sized YUV frames: the eight frame calls with an output size, several 2x steps and W2XC_ITERATIONS_AUTO; the resize of chroma as a block ----
+int w2xc_process_frames_yuv_u8_sized_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, const w2xc_yuv_planes *d_in,
+                                            int out_w, int out_h, const w2xc_yuv_planes *d_out, int iterations, void *hip_stream, const w2xc_opts *opts)
+try {
+    return frames_yuv(false, ImageCall(noise_model, scale_model, w, h, iterations, 0.0, hip_stream, opts), sized_call(false, n, chroma, range, 0, 1, 8, out_w, out_h), d_in, d_out);
+} W2XC_CATCH_ALL
+
+int w2xc_process_frames_yuv_u8_sized(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, const w2xc_yuv_planes *in, int out_w,
+                                     int out_h, const w2xc_yuv_planes *out, int iterations, const w2xc_opts *opts)
+try {
+    return frames_yuv(true, ImageCall(noise_model, scale_model, w, h, iterations, 0.0, nullptr, opts), sized_call(false, n, chroma, range, 0, 1, 8, out_w, out_h), in, out);
+} W2XC_CATCH_ALL
+
+int w2xc_process_frames_yuv_u8_rgb_sized_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int matrix,
+                                                const w2xc_yuv_planes *d_in, int out_w, int out_h, const w2xc_yuv_planes *d_out, int iterations, void *hip_stream,
+                                                const w2xc_opts *opts)
+try {
+    return frames_yuv(false, ImageCall(noise_model, scale_model, w, h, iterations, 0.0, hip_stream, opts), sized_call(true, n, chroma, range, matrix, 1, 8, out_w, out_h), d_in,
+                      d_out);
+} W2XC_CATCH_ALL
+
+int w2xc_process_frames_yuv_u8_rgb_sized(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int matrix,
+                                         const w2xc_yuv_planes *in, int out_w, int out_h, const w2xc_yuv_planes *out, int iterations, const w2xc_opts *opts)
+try {
+    return frames_yuv(true, ImageCall(noise_model, scale_model, w, h, iterations, 0.0, nullptr, opts), sized_call(true, n, chroma, range, matrix, 1, 8, out_w, out_h), in, out);
+} W2XC_CATCH_ALL
+
+int w2xc_process_frames_yuv_u16_sized_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int depth,
+                                             const w2xc_yuv16_planes *d_in, int out_w, int out_h, const w2xc_yuv16_planes *d_out, int iterations, void *hip_stream,
+                                             const w2xc_opts *opts)
+try {
+    return frames_yuv(false, ImageCall(noise_model, scale_model, w, h, iterations, 0.0, hip_stream, opts), sized_call(false, n, chroma, range, 0, 2, depth, out_w, out_h), d_in,
+                      d_out);
+} W2XC_CATCH_ALL
+
+int w2xc_process_frames_yuv_u16_sized(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int depth,
+                                      const w2xc_yuv16_planes *in, int out_w, int out_h, const w2xc_yuv16_planes *out, int iterations, const w2xc_opts *opts)
+try {
+    return frames_yuv(true, ImageCall(noise_model, scale_model, w, h, iterations, 0.0, nullptr, opts), sized_call(false, n, chroma, range, 0, 2, depth, out_w, out_h), in, out);
+} W2XC_CATCH_ALL
+
+int w2xc_process_frames_yuv_u16_rgb_sized_device(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int depth, int matrix,
+                                                 const w2xc_yuv16_planes *d_in, int out_w, int out_h, const w2xc_yuv16_planes *d_out, int iterations, void *hip_stream,
+                                                 const w2xc_opts *opts)
+try {
+    return frames_yuv(false, ImageCall(noise_model, scale_model, w, h, iterations, 0.0, hip_stream, opts), sized_call(true, n, chroma, range, matrix, 2, depth, out_w, out_h),
+                      d_in, d_out);
+} W2XC_CATCH_ALL
+
+int w2xc_process_frames_yuv_u16_rgb_sized(w2xc_model *noise_model, w2xc_model *scale_model, int n, int w, int h, int chroma, int range, int depth, int matrix,
+                                          const w2xc_yuv16_planes *in, int out_w, int out_h, const w2xc_yuv16_planes *out, int iterations, const w2xc_opts *opts)
+try {
+    return frames_yuv(true, ImageCall(noise_model, scale_model, w, h, iterations, 0.0, nullptr, opts), sized_call(true, n, chroma, range, matrix, 2, depth, out_w, out_h), in,
+                      out);
+} W2XC_CATCH_ALL
+
+int w2xc_chroma_resize_u8_device(const unsigned char *d_src, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int cw, int ch,
+                                 unsigned char *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int ow, int oh, int w, int h, int out_w,
+                                 int out_h, int sub_x, int sub_y, int cosited, void *hip_stream)
+{
+    return chroma_resize_block(d_src, 1, 8, n, src_frame_stride_bytes, src_stride_bytes, src_px, W2XC_PACK_LOW, cw, ch, d_dst, dst_frame_stride_bytes, dst_stride_bytes,
+                               dst_px, W2XC_PACK_LOW, ow, oh, w, h, out_w, out_h, sub_x, sub_y, cosited, hip_stream);
+}
+
+int w2xc_chroma_resize_u16_device(const unsigned short *d_src, int n, size_t src_frame_stride_bytes, size_t src_stride_bytes, int src_px, int src_pack, int cw, int ch,
+                                  int depth, unsigned short *d_dst, size_t dst_frame_stride_bytes, size_t dst_stride_bytes, int dst_px, int dst_pack, int ow, int oh,
+                                  int w, int h, int out_w, int out_h, int sub_x, int sub_y, int cosited, void *hip_stream)
+{
+    return chroma_resize_block(d_src, 2, depth, n, src_frame_stride_bytes, src_stride_bytes, src_px, src_pack, cw, ch, d_dst, dst_frame_stride_bytes, dst_stride_bytes,
+                               dst_px, dst_pack, ow, oh, w, h, out_w, out_h, sub_x, sub_y, cosited, hip_stream);
 }
 
 }  // extern "C"

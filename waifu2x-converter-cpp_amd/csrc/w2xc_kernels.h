@@ -260,3 +260,15 @@ hipError_t w2xc_launch_yuv16_to_rgb_sited(W2xcU16Planes y, W2xcU16Planes u, cons
                                           float *rgb, long long is, long long ps, int n, hipStream_t st);
 hipError_t w2xc_launch_rgb_to_yuv16_sited(const float *rgb, long long is, long long ps, int w, int h, int chroma, int range, int matrix, int depth, W2xcU16Planes y,
                                           W2xcU16Planes u, unsigned short *v, int n, hipStream_t st);
+
+// ---- chroma of the sized frame calls (w2xc_yuv_sized.hip, w2xc_yuv16_sized.hip; include/w2xc_hip.h, "Sized YUV frames") ----
+// The bicubic of the 2x launchers at any ratio r <= 1 per axis, in one launch from the input planes to the output planes: output sample m of an axis reads
+// pos = (m + o) * r - o, with r the LUMA ratio of the axis and o = 0.5 (centred or not subsampled) or 0.25 (co-sited) -- chroma_axis, w2xc_host_geom.hpp.
+// cw x ch -> ow x oh, any sizes >= 1 (reads are clamped into the plane); tiles of W2XC_CHROMA_RESIZE_TX x W2XC_CHROMA_RESIZE_TY OUTPUT samples
+// (chroma_resize_tile_grid), at most W2XC_CHROMA_GRID_MAX workgroups; a turn is one plane's tile on bytes, all planes' tile of a frame on words.
+#define W2XC_CHROMA_RESIZE_TX 32
+#define W2XC_CHROMA_RESIZE_TY 16
+hipError_t w2xc_launch_chroma_resize_u8(W2xcU8Planes su, const unsigned char *sv, int cw, int ch, W2xcU8Planes du, unsigned char *dv, int ow, int oh, double rx, double ox,
+                                        double ry, double oy, int n, hipStream_t st);
+hipError_t w2xc_launch_chroma_resize_u16(W2xcU16Planes su, const unsigned short *sv, int cw, int ch, W2xcU16Planes du, unsigned short *dv, int ow, int oh, int depth,
+                                         double rx, double ox, double ry, double oy, int n, hipStream_t st);
