@@ -173,8 +173,8 @@ UNREACHABLE.update({
     first(3, 32, planar=True, batch=True): _PLANAR32,
     first(3, 32, planar=True, u8=True, batch=True): _PLANAR32,
     GATHER: ("w2xc_split.hip:1034 w2xc_launch_last_gather(): `if (d.in_ps <= 1 && d.out_ps == 1)` launches conv3x3_last_gather_x4 -- layer_desc "
-             "(w2xc_select.cpp:381) gives every fused-last producer `d.out_ps = 1`, and the gather's layer is always last_direct "
-             "(w2xc_select.cpp:279-280: its one plane goes to the caller's plane, `d.out_ps = 1`, w2xc_select.cpp:372)"),
+             "(w2xc_select.cpp:417) gives every fused-last producer `d.out_ps = 1`, and the gather's layer is always last_direct "
+             "(w2xc_select.cpp:315-316: its one plane goes to the caller's plane, `d.out_ps = 1`, w2xc_select.cpp:408)"),
 })
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------

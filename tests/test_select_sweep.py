@@ -23,18 +23,23 @@ def test_every_decision_is_the_recorded_one(lines):
 
 def test_the_recording_covers_what_it_is_for(w2xc):
     """the cases the recording exists for are in it: the too-wide plane with both outcomes of the fused first layers (W2XC_FUSION_AUTO gives the fusion
-    up, W2XC_FUSION_ON is refused), the banded plan, the minimum-halo refusal, both head models, and every option set of every topology"""
+    up, W2XC_FUSION_ON is refused), the plane too wide for conv3x3_wino4 on 32 NHWC planes (refused whatever the fusion), the banded plan, the minimum-halo refusal, both head models, and every option set of every topology"""
     want = select_sweep.read_fixture()
     by_key = {l.split(" | ")[0]: l.split(" | ")[1:] for l in want}
     assert len(by_key) == len(want)                                   # one line per (topology, options, plane)
     n_opts = len(list(select_sweep.option_sets(w2xc)))
     assert n_opts == 6 * 7 + 4 * 2 * 7
-    assert len(want) == n_opts * (3 * len(select_sweep.TOPOLOGIES) + 1)
+    assert len(want) == n_opts * (4 * len(select_sweep.TOPOLOGIES) + 1)
     scale = "-".join(map(str, select_sweep.SCALE))
-    auto = by_key["%s p0k0f%d 2000000x64" % (scale, w2xc.FUSION_AUTO)]
-    on = by_key["%s p0k0f%d 2000000x64" % (scale, w2xc.FUSION_ON)]
+    auto = by_key["%s p0k0f%d 1300000x64" % (scale, w2xc.FUSION_AUTO)]
+    on = by_key["%s p0k0f%d 1300000x64" % (scale, w2xc.FUSION_ON)]
     assert auto[1].split(",")[4:6] == ["0", "1"]                      # planned, without the fused first layers
     assert on[1].startswith("!%d:plane too wide" % w2xc.ERR_UNSUPPORTED)
+    # 2 000 000 pixels: the unfused chain's conv3x3_wino4<32, 64> would read 32 NHWC planes with 24 in_rs 4 >= 2^32 -- refused in the plan, with the width
+    for fusion in (w2xc.FUSION_AUTO, w2xc.FUSION_ON, w2xc.FUSION_OFF):
+        wide = by_key["%s p0k0f%d 2000000x64" % (scale, fusion)]
+        assert wide[1].startswith("!%d:plane too wide (2000000 pixels)" % w2xc.ERR_UNSUPPORTED), wide
+    assert by_key["%s p0k%df0 2000000x64" % (scale, w2xc.KERNEL_WINOGRAD32)][1][0] != "!"   # (the F(2x2) kernels have no such rule: planned)
     assert by_key["%s p0k0f0 64x64" % scale][1].split(",")[4:6] == ["1", "1"]
     assert int(by_key["%s p0k0f0 3000x4000/64M" % scale][1].split(",")[3]) > 1   # banded
     minv = [v for k, v in by_key.items() if k.endswith("min")]

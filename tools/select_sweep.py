@@ -8,6 +8,8 @@ layouts and the tap-plane halves; a refused call is its error code and message.
 
 The fixture was recorded from the library BEFORE the selection predicates became the resolved chain (resolve_chain) and is not to be regenerated for a
 change that is meant to keep the decisions; one that moves a decision regenerates it and shows the diff of the lines.
+Regenerated once since: plan_rows refuses a plane that conv3x3_wino4 cannot address in any band -- the 108 lines of 2000000x64 whose chain runs conv3x3_wino4 on
+32 NHWC planes went from a plan (whose launch failed) to that refusal, and the plane 1300000x64 joined so that the fused-first give-up stays on record.
 
 A line:   <topology> p<precision>k<kernel>f<fusion> <plane> | <kernel codes, one letter per layer> | <plan> | <batch plan>
     plan = n_layers,halo,band_rows,n_bands,fused_first,fused_last,ws0,ws1    batch plan = batched,sub_batch    refusal = !<code>:<message>"""
@@ -83,7 +85,7 @@ def _line(w2xc, ms, tag, head, n_in, name, plan_args, batch_wh, **okw):
 
 
 def sweep_lines(w2xc):
-    lines = []
+    lines, later = [], []
     for planes, head in TOPOLOGIES:
         layers = gen_model.synth_layers(planes, 7)
         ms = w2xc._ModelSet.from_layers(layers, head=gen_model.synth_head(planes[-1], head, 7) if head else None)
@@ -94,13 +96,17 @@ def sweep_lines(w2xc):
             lines.append(_line(w2xc, ms, tag, head, planes[0], "64x64", (64, 64), (64, 64), **okw))
             # banded: the solver's repeated workspace evaluation is on record
             lines.append(_line(w2xc, ms, tag, head, planes[0], "3000x4000/64M", (3000, 4000), (3000, 4000), workspace_mb=64, **okw))
-            # too wide for the fused first layers: FUSION_AUTO gives that fusion up, an explicit request is refused
+            # too wide for the fused first layers -- and for conv3x3_wino4 on 32 NHWC planes (24 in_rs 4 >= 2^32, which no band changes): every chain that
+            # has such a layer is refused, whatever the fusion
             lines.append(_line(w2xc, ms, tag, head, planes[0], "2000000x64", (2000000, 64), (2000000, 64), **okw))
+            # too wide for the fused first layers only: FUSION_AUTO gives that fusion up, an explicit request is refused (behind the lines of the first
+            # recording, which keep their places)
+            later.append(_line(w2xc, ms, tag, head, planes[0], "1300000x64", (1300000, 64), (1300000, 64), **okw))
             if planes == SCALE and not head:   # a row view with the minimum halo: refused under KERNEL_AUTO in fp32
                 ra, rb = w2xc.shard_rows(600, 3, 1)
                 y0, y1 = w2xc.shard_view(600, ra, rb, n)
                 lines.append(_line(w2xc, ms, tag, head, planes[0], "128x600[%d,%d)min" % (ra, rb), (128, 600, ra, rb, y0, y1 - y0), None, **okw))
-    return lines
+    return lines + later
 
 
 def read_fixture(path=FIXTURE):

@@ -218,6 +218,43 @@ void RowPlan::ws_need(const w2xc_model *m, int rows, size_t need[2]) const
     }
 }
 
+// The tallest band every launch of the chain can address (NO_CAP: no rule binds): the launchers' 32-bit rules restated over the region heights of a band of
+// `rows` output rows -- layer k computes at most min(rows + halo(k), plane_h + 2 (n - k)) rows (RowPlan::region; halo as in ws_need), and a plane whose
+// whole extent satisfies a rule is not capped by it.
+//   conv3x3_first2_wino4   32-bit lane offsets over its 32 output planes (12 plane strides + a row): planes of at most 64 Mi floats (w2xc_launch_first2_wino4)
+//   conv3x3_wino4          planar in: 3 in_cs 4 + 24 in_rs 4 < 2^32, in_cs = in_rs x the rows of the layer in front; 32 NHWC planes in: 24 in_rs 4 < 2^32, which
+//                          no band changes; tiles_x tiles_y (COUT / 64) < 2^31 items (w2xc_launch_wino4, launch_wino4)
+// (PROG's rule, out_h out_rs 4 < 2^32, caps nothing: prog_eligible (w2xc_rows.cpp) leaves such a band to the gather launch.)
+namespace {
+const long long NO_CAP = 1ll << 62;
+long long halo_of(const RowPlan &P, int k) { return (P.HL == 1 || k == P.n) ? 2 * (long long)(P.n - k) : 6 + 8 * (long long)(P.n - k); }
+// rows of a band when layer k may compute at most `max_h` rows
+long long band_for(const RowPlan &P, int k, long long max_h) { return P.plane_h > 0 && (long long)P.plane_h + 2 * (P.n - k) <= max_h ? NO_CAP : std::max(0ll, max_h - halo_of(P, k)); }
+long long first2_max_band(const RowPlan &P)
+{
+    const long long wk = ((long long)P.w + 2 * (P.n - 2) + 31) & ~31ll;
+    return std::max(0ll, (64ll << 20) / wk - halo_of(P, 2));   // (every band, whatever the plane's height: the cap as it has always been)
+}
+long long addr_max_band(const w2xc_model *m, const RowPlan &P, const char **rule)
+{
+    const int n = P.n;
+    long long best = NO_CAP;
+    auto cap = [&](long long b, const char *what) { if (b < best) { best = b; *rule = what; } };
+    if (P.chain.fused_first && P.chain.T == 0) cap(first2_max_band(P), "conv3x3_first2_wino4: planes of at most 64 Mi floats");
+    for (int k = 2; k <= n; k++) {
+        if (!P.chain.layer[k - 1].wino4) continue;
+        const long long in_w = (long long)P.w + 2 * (n - k + 1), out_w = (long long)P.w + 2 * (n - k);
+        if (P.chain.layer[k - 2].planar_out) {
+            const long long in_rs = (in_w + 31) & ~31ll;
+            cap(band_for(P, k - 1, (((1ll << 30) - 1) / in_rs - 24) / 3), "3 in_cs 4 + 24 in_rs 4 < 2^32");
+        } else if (24 * in_w * m->layers[k - 1].nin * 4 >= (1ll << 32)) cap(0, "24 in_rs 4 < 2^32 with 32 NHWC planes in");
+        const long long per_row = ((out_w + 31) / 32) * (m->layers[k - 1].nout / 64);
+        cap(band_for(P, k, 16 * (((1ll << 31) - 1) / per_row) - 18), "tiles_x tiles_y (COUT / 64) < 2^31");   // (tiles_y <= (out_h + 3 + 15) / 16)
+    }
+    return best;
+}
+}  // namespace
+
 // Output rows [ra, rb) of an h-row plane of which the view holds rows [vy0, vy0 + vh): halo geometry, band height, workspace bytes, and the
 // options the call really runs with (W2XC_FUSION_AUTO gives up a fusion whose kernel cannot address the plane; an explicit request fails instead).
 int plan_rows(const w2xc_model *m, const w2xc_opts &o_in, int w, int vh, int vy0, int ra, int rb, int plane_h, int n_in, bool all_out, RowPlan *p)
@@ -258,21 +295,20 @@ int plan_rows(const w2xc_model *m, const w2xc_opts &o_in, int w, int vh, int vy0
             if (P.chain.layer[l].kind == W2XC_K_DIRECT)
                 return fail(W2XC_ERR_UNSUPPORTED, "16-bit precision modes: layer %d (%d->%d) has no kernel ({1,3}->{32,64,128} first, {32,64,128}->{32,64,128}, ->{1,3} last only)",
                             l + 1, m->layers[l].nin, m->layers[l].nout);
-    // conv3x3_first2_wino4 addresses its 32 output planes with 32-bit lane offsets (12 plane strides + a row): planes of at most 64 Mi floats.
-    // A plane too wide for that even in the shortest band: W2XC_FUSION_AUTO runs the first two layers unfused, an explicit request is refused.
-    size_t first2_max_rows = 0, first2_halo = 0;
-    if (P.chain.fused_first && P.chain.T == 0) {
-        const size_t wk = ((size_t)w + 2 * (n - 2) + 31) & ~(size_t)31;
-        first2_max_rows = ((size_t)64 << 20) / wk;
-        first2_halo = P.HL == 1 ? 2 * (size_t)(n - 2) : 6 + 8 * (size_t)(n - 2);
-        if (first2_max_rows < first2_halo + 8) {
-            if (P.o.fusion != W2XC_FUSION_AUTO)
-                return fail(W2XC_ERR_UNSUPPORTED, "plane too wide (%d pixels) for the fused first layers; use w2xc_opts.fusion = W2XC_FUSION_AUTO, _LAST or _OFF", w);
-            P.o.fusion = W2XC_FUSION_LAST;
-            P.chain = resolve_chain(m, P.o);   // (the options changed: the one place in a call where the chain is resolved a second time)
-            first2_max_rows = 0;
-        }
+    // The launchers' 32-bit limits as a cap on the band (addr_max_band above).  A plane too wide for conv3x3_first2_wino4 even in the shortest band:
+    // W2XC_FUSION_AUTO runs the first two layers unfused, an explicit request is refused.  A plane no band makes addressable for conv3x3_wino4: refused
+    // here, before a device is touched -- not as a launch error in the middle of a call.
+    const char *cap_rule = "";
+    long long max_band = addr_max_band(m, P, &cap_rule);
+    if (max_band < 8 && P.chain.fused_first && P.chain.T == 0 && first2_max_band(P) < 8) {
+        if (P.o.fusion != W2XC_FUSION_AUTO)
+            return fail(W2XC_ERR_UNSUPPORTED, "plane too wide (%d pixels) for the fused first layers; use w2xc_opts.fusion = W2XC_FUSION_AUTO, _LAST or _OFF", w);
+        P.o.fusion = W2XC_FUSION_LAST;
+        P.chain = resolve_chain(m, P.o);   // (the options changed: the one place in a call where the chain is resolved a second time)
+        max_band = addr_max_band(m, P, &cap_rule);
     }
+    if (max_band < 8)
+        return fail(W2XC_ERR_UNSUPPORTED, "plane too wide (%d pixels) for conv3x3_wino4's 32-bit offsets in any band (%s); use w2xc_opts.kernel = W2XC_KERNEL_WINOGRAD32 or _MFMA", w, cap_rule);
     // the last layer stores straight into the caller's planar plane(s) when its kernel can address planar
     // output (conv3x3_last / conv3x3_direct); otherwise it goes through the NHWC workspace + a repack
     P.last_kind = P.chain.layer[n - 1].kind;
@@ -308,8 +344,8 @@ int plan_rows(const w2xc_model *m, const w2xc_opts &o_in, int w, int vh, int vy0
             band = (total + nb - 1) / nb;   // equalise (never larger than the band that was just checked)
         }
     }
-    // (the addressing limit of the fused first layers also bounds a band the caller asked for: w2xc_plan_rows reports the height that runs)
-    if (first2_max_rows && (size_t)band + first2_halo > first2_max_rows) band = (int)(first2_max_rows - first2_halo);
+    // (the addressing limits also bound a band the caller asked for: w2xc_plan_rows reports the height that runs)
+    if ((long long)band > max_band) band = (int)max_band;
     if (P.HL > 1 && band < total) band = std::max(4, band & ~3);   // (band edges on block rows: no rounding-out rows)
     P.band = std::min(band, total);
     P.ws_need(m, P.band, P.need);

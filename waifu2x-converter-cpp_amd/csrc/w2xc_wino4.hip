@@ -280,7 +280,9 @@ template <int CIN, int COUT, bool OUT_PLANAR, bool IN_NHWC = false, bool FUSE7 =
 static hipError_t launch_wino4(const W2xcConvDesc &d, hipStream_t stream)
 {
     const int tiles_x = (d.out_w + 31) / 32, tiles_y = (d.out_h + (d.wino_py & 3) + 15) / 16;
-    const int nitems = tiles_x * tiles_y * (COUT / 64);
+    const long long items = (long long)tiles_x * tiles_y * (COUT / 64);
+    if (items >= (1ll << 31)) return hipErrorInvalidValue;   // (the kernel walks items in int; plan_rows caps a band below this)
+    const int nitems = (int)items;
     constexpr size_t lds_bytes = 3 * (size_t)(11 * 1024) + 2 * (size_t)(36 * 1024) + 3 * (size_t)(18 * 1024) + COUT * 4 + (PROG ? 16 : 0);   // raw + U + V + bias (+ the job word)
     static_assert(lds_bytes <= 160 * 1024, "LDS budget");
     if constexpr (PROG) {
