@@ -6,6 +6,7 @@ samples between the samples -- are those of the centred kernels' tests, whose he
 import numpy as np
 import pytest
 
+from conftest import small_layers
 import yuv_ref as yr
 import yuv_rgb_ref as rr
 import yuv16_ref as y16
@@ -168,6 +169,38 @@ def test_chroma2x_more_turns_than_workgroups(gpu):
     assert np.array_equal(chroma2x8(gpu, planes, X), want2x(planes, X, 8))
 
 
+@pytest.fixture(scope="module")
+def y_scale(gpu):
+    """a short one-plane scale model: the Y route of a frame call needs one for its luma; its chroma never meets it"""
+    return gpu._ModelSet.from_layers(small_layers([1, 32, 32, 1], 32))
+
+
+@pytest.mark.parametrize("cosited", FLAGS, ids=FLAG_IDS)
+def test_chroma2x_every_load_path(gpu, y_scale, cosited):
+    """every instantiation of the two 2x kernels that the launchers can ask the selectors for with this flag, picked by how the buffers lie -- k_chroma2x_u8_sited
+    <DW 1> planar rows on 4-byte boundaries, <DW 0> odd addresses; k_chroma2x_u16_sited <LOAD 1> planar rows on 8-byte boundaries, <LOAD 0> odd addresses,
+    <LOAD 2> interleaved with v = u + 1 and rows on 4-byte boundaries.  The blocks take one plane a call, so LOAD 2 is reached through the 16-bit Y frame call on
+    P010 input, whose chroma is the 2x of its input whatever the model.  n = 2 frames of 33 x 17 samples: 2 x 2 tiles of 32 x 16 quads with a one-sample rim"""
+    n, cw, ch, depth = 2, 33, 17, 10
+    r = np.random.default_rng(1000 + cosited)
+    planes = r.integers(0, 256, (n, ch, cw), dtype=np.uint8)
+    want = want2x(planes, cosited, 8)
+    for aligned in (False, True):
+        assert np.array_equal(chroma2x8(gpu, planes, cosited, src_aligned=aligned, dst_aligned=aligned), want), aligned
+    U, V = (r.integers(0, 1 << depth, (n, ch, cw)).astype(np.uint16) for _ in range(2))
+    want_u, want_v = want2x(U, cosited, depth), want2x(V, cosited, depth)
+    for align in (1, 4):
+        assert np.array_equal(chroma2x16(gpu, U, depth, cosited, salign=align, dalign=align), want_u), align
+    w, h = 2 * cw, 2 * ch
+    Y = r.integers(0, 1 << depth, (n, h, w)).astype(np.uint16)
+    i = Side16(gpu, n, w, h, yr.YUV_420, "p010", 1, 2).upload(Y, U, V, depth)
+    o = Side16(gpu, n, 2 * w, 2 * h, yr.YUV_420, "planar", 0, 1)
+    gpu.process_frames_yuv_u16_device(n, w, h, yr.YUV_420 | cosited, i.s, o.s, None, y_scale, 1, yr.FULL, stream=stream().cuda_stream, depth=depth)
+    stream().synchronize()
+    _, got_u, got_v = o.download(depth)
+    assert np.array_equal(got_u, want_u) and np.array_equal(got_v, want_v)
+
+
 # ---- the two ends of the RGB route ----
 def to_rgb8(gpu, Y, U, V, chroma, rng, matrix, kind=PLANAR, aligned=False):
     n, h, w = Y.shape
@@ -275,6 +308,20 @@ def test_rgb_ends_u16_sizes(gpu, chroma):
     for k, (w, h) in enumerate(RGB_SIZES):
         check16(gpu, 1, w, h, chroma, yr.LIMITED, rr.BT2020, 10, STYLES[k % 3], k & 1, (1, 2, 4)[k % 3], bool(k % 2), 400 + k)
     check16(gpu, 1, 130, 68, chroma, yr.FULL, rr.BT709, 12, "p010", 1, 4, True, 440)
+
+
+@pytest.mark.parametrize("chroma", sr.ALL_SITED, ids=SITED_IDS)
+def test_rgb_ends_every_load_path(gpu, chroma):
+    """every instantiation of the four RGB-route kernels that the launchers can ask the selectors for with this layout and these flags, picked by how the planes
+    lie -- k_yuv8_to_rgb_sited <DW 1> rows on 4-byte boundaries, <DW 0> odd addresses; k_yuv16_to_rgb_sited <CM 1> planar chroma rows on 8-byte boundaries, <CM 2>
+    P010 rows on 4-byte boundaries, <CM 0> odd addresses; k_rgb_to_yuv8_sited / k_rgb_to_yuv16_sited have one instantiation per pair and run in every check.
+    n = 2 frames of 67 x 35 luma samples in 4:2:0, 67 x 17 in 4:2:2: chroma planes 34 wide, one tile of 32 x 16 chroma samples and a rim in both directions"""
+    w, h = (67, 35) if chroma & 0xF == yr.YUV_420 else (67, 17)
+    check8(gpu, 2, w, h, chroma, yr.LIMITED, rr.BT709, PLANAR, True, 700)
+    check8(gpu, 2, w, h, chroma, yr.FULL, rr.BT601, PLANAR, False, 702)
+    check16(gpu, 2, w, h, chroma, yr.LIMITED, rr.BT2020, 10, "planar", 0, 4, True, 704)
+    check16(gpu, 2, w, h, chroma, yr.FULL, rr.BT709, 10, "p010", 1, 2, False, 706)
+    check16(gpu, 2, w, h, chroma, yr.LIMITED, rr.BT601, 12, "planar", 1, 1, False, 708)
 
 
 @pytest.mark.parametrize("chroma", sr.SITED_LAYOUTS, ids=[sr.SITED_IDS[c] for c in sr.SITED_LAYOUTS])

@@ -475,7 +475,9 @@ def test_launch_rules_match_the_launchers():
     assert geom.count("turns = tiles * per_tile") == 1 and geom.count("(unsigned)(turns > cap ? cap : turns)") == 1
     assert "chroma2x_tile_grid(ow, oh, n, CH_TQX, CH_TQY, W2XC_CHROMA_GRID_MAX)" in hip and "/ CH_TQX" not in hip
     assert "sizeof(*p.p)" in squeeze("w2xc_yuv_tile.h"), "rows_align: the alignment of a plane's rows in BYTES"
-    assert "su.px == 1 && ((salign | (sv ? reinterpret_cast<size_t>(sv) : 0)) & 7) == 0" in hip and "su.px == 2 && sv == su.p + 1 && (salign & 3) == 0" in hip
+    prologue = squeeze("w2xc_yuv_launch.h")      # (the load paths of the words: one copy for the 2x launcher, every siting, and the resize launcher)
+    assert prologue.count("su.px == 1 && ((salign | (sv ? reinterpret_cast<size_t>(sv) : 0)) & 7) == 0") == 1
+    assert prologue.count("su.px == 2 && sv == su.p + 1 && (salign & 3) == 0") == 1 and "chroma_prologue_u16(" in hip and "salign" not in hip
     hip = squeeze("w2xc_yuv16_rgb.hip")
     assert hip.count("yuv_rgb_tile_grid(cw, ch, n, YR_TCX, YR_TCY, W2XC_YUVRGB_GRID_MAX)") == 2 and "/ YR_TCX" not in hip
     assert y16.chroma_launch(1, 1, 1) == (1, 1) and y16.chroma_launch(63, 31, 2) == (2, 2) and y16.chroma_launch(64, 32, 1) == (4, 4)

@@ -81,7 +81,10 @@ def test_symbols_constants_header_and_the_abi(w2xc):
             assert w2xc.yuv_chroma_size(w, h, chroma) == yr.chroma_size(w, h, chroma & 0xF) == sr.chroma_size(w, h, chroma)
     with pytest.raises(ValueError):
         w2xc.yuv_chroma_size(8, 8, 7)
-    assert "chroma &= 0xF" in open(os.path.join(CSRC, "w2xc_yuv_px.h")).read(), "frame_geometry masks the flags off"
+    # ... in the launchers either: ONE decoder gives the layout and the flags, frame_geometry takes the layout, and no launcher masks a flag off
+    px = open(os.path.join(CSRC, "w2xc_yuv_px.h")).read()
+    assert px.count("bool chroma_layout(int chroma, ChromaLayout *c)") == 1 and "bool frame_geometry(int w, int h, int layout," in px
+    assert "chroma &= 0xF" not in px and "sited_layout" not in px
 
 
 def test_the_rule_of_acceptance():
@@ -329,13 +332,18 @@ def test_siting_option_of_the_tools(y4m, y4m16, tmp_path, capsys):
 def test_launch_rules_and_shared_bodies():
     squeeze = lambda name: " ".join(open(os.path.join(CSRC, name)).read().split())
     sited = {n: squeeze(n) for n in ("w2xc_yuv_sited.hip", "w2xc_yuv16_sited.hip", "w2xc_yuv_rgb_sited.hip", "w2xc_yuv16_rgb_sited.hip")}
-    # the grids are the centred launchers' rules
-    assert "chroma2x_tile_grid(ow, oh, (long long)n * npl, CH_TQX, CH_TQY, W2XC_CHROMA_GRID_MAX)" in sited["w2xc_yuv_sited.hip"]
-    assert "chroma2x_tile_grid(ow, oh, n, CH_TQX, CH_TQY, W2XC_CHROMA_GRID_MAX)" in sited["w2xc_yuv16_sited.hip"]
+    # the grids are the centred launchers' rules: a kernel family has ONE launcher, in its centred file, that computes the grid once for every siting; the
+    # sited files launch nothing and hand out their instantiations
+    centred = {n: squeeze(n.replace("_sited", "")) for n in sited}
+    assert centred["w2xc_yuv_sited.hip"].count("chroma2x_tile_grid(ow, oh, (long long)n * npl, CH_TQX, CH_TQY, W2XC_CHROMA_GRID_MAX)") == 1
+    assert centred["w2xc_yuv16_sited.hip"].count("chroma2x_tile_grid(ow, oh, n, CH_TQX, CH_TQY, W2XC_CHROMA_GRID_MAX)") == 1
     for name in ("w2xc_yuv_rgb_sited.hip", "w2xc_yuv16_rgb_sited.hip"):
-        assert sited[name].count("yuv_rgb_tile_grid(cw, ch, n, YR_TCX, YR_TCY, W2XC_YUVRGB_GRID_MAX)") == 2
-    for text in sited.values():
-        assert "dim3(256)" in text and "__launch_bounds__(256)" in text
+        assert centred[name].count("yuv_rgb_tile_grid(cw, ch, n, YR_TCX, YR_TCY, W2XC_YUVRGB_GRID_MAX)") == 2
+    for name, text in sited.items():
+        assert "__launch_bounds__(256)" in text and "hipLaunchKernelGGL" not in text and "_tile_grid(" not in text and "hipError_t" not in text, name
+        assert "dim3(256)" in centred[name] and centred[name].count("_sited_kernel(") == text.count("_sited_kernel(") >= 1, name
+    kernels_h = squeeze("w2xc_kernels.h")
+    assert "_sited(" not in kernels_h and kernels_h.count("hipError_t w2xc_launch_chroma2x_u") == 2
     # one body per kernel, included by the centred kernel's file and by the sited one; the bodies hold the loops, the .hip files none
     pairs = {"w2xc_chroma2x_u8_body.inc": ("w2xc_yuv.hip", "w2xc_yuv_sited.hip"), "w2xc_chroma2x_u16_body.inc": ("w2xc_yuv16.hip", "w2xc_yuv16_sited.hip"),
              "w2xc_yuv8_to_rgb_body.inc": ("w2xc_yuv_rgb.hip", "w2xc_yuv_rgb_sited.hip"), "w2xc_rgb_to_yuv8_body.inc": ("w2xc_yuv_rgb.hip", "w2xc_yuv_rgb_sited.hip"),

@@ -182,7 +182,8 @@ unsigned short *words(unsigned char *p) { return reinterpret_cast<unsigned short
 W2xcU16Planes luma_words(const YuvSide &s) { return {words(s.y), (long long)(s.y_frame_stride / 2), (long long)(s.y_stride / 2), 1, s.pack}; }
 W2xcU16Planes chroma_words(const YuvSide &s) { return {words(s.u), (long long)(s.c_frame_stride / 2), (long long)(s.c_stride / 2), s.c_px, s.pack}; }
 
-// ---- the ends of the two routes on n frames of one side: the ONE place where the sample width (g.bps) picks a launcher.  Routes and building blocks call these ----
+// ---- the ends of the two routes on n frames of one side: the ONE place where the sample width (g.bps) picks a launcher, and it picks by nothing else -- the siting
+// (g.cosited) goes to the launcher every time, which decides it.  Routes and building blocks call these ----
 // luma samples of w x h -> float planes ps floats apart, and back
 hipError_t luma_in(const YuvGeom &g, const YuvSide &s, int w, int h, float *y, long long ps, int n, hipStream_t st)
 {
@@ -201,31 +202,22 @@ hipError_t chroma_out(const YuvGeom &g, ChromaMode mode, const YuvSide &in, cons
                                                            g.ay.r, g.ay.o, n, st)
                           : w2xc_launch_chroma_resize_u8(chroma_planes(in), in.v, g.cw, g.ch, chroma_planes(out), out.v, g.ocw, g.och, g.ax.r, g.ax.o, g.ay.r, g.ay.o, n, st);
     const bool up2x = mode == CHROMA_2X;
-    if (up2x && g.cosited)
-        return g.bps == 2 ? w2xc_launch_chroma2x_u16_sited(chroma_words(in), words(in.v), g.cw, g.ch, chroma_words(out), words(out.v), g.ocw, g.och, g.depth, g.cosited, n, st)
-                          : w2xc_launch_chroma2x_u8_sited(chroma_planes(in), in.v, g.cw, g.ch, chroma_planes(out), out.v, g.ocw, g.och, g.cosited, n, st);
     if (g.bps == 2)
-        return up2x ? w2xc_launch_chroma2x_u16(chroma_words(in), words(in.v), g.cw, g.ch, chroma_words(out), words(out.v), g.ocw, g.och, g.depth, n, st)
+        return up2x ? w2xc_launch_chroma2x_u16(chroma_words(in), words(in.v), g.cw, g.ch, chroma_words(out), words(out.v), g.ocw, g.och, g.depth, g.cosited, n, st)
                     : w2xc_launch_chroma_copy_u16(chroma_words(in), words(in.v), g.cw, g.ch, chroma_words(out), words(out.v), g.depth, n, st);
-    return up2x ? w2xc_launch_chroma2x_u8(chroma_planes(in), in.v, g.cw, g.ch, chroma_planes(out), out.v, g.ocw, g.och, n, st)
+    return up2x ? w2xc_launch_chroma2x_u8(chroma_planes(in), in.v, g.cw, g.ch, chroma_planes(out), out.v, g.ocw, g.och, g.cosited, n, st)
                 : w2xc_launch_chroma_copy_u8(chroma_planes(in), in.v, g.cw, g.ch, chroma_planes(out), out.v, n, st);
 }
 // frames of w x h <-> their R, G, B planes (frame i's at rgb + i * is + {0, 1, 2} * ps floats) by g.matrix
 hipError_t to_rgb(const YuvGeom &g, const YuvSide &s, int w, int h, float *rgb, long long is, long long ps, int n, hipStream_t st)
 {
-    if (g.cosited)
-        return g.bps == 2 ? w2xc_launch_yuv16_to_rgb_sited(luma_words(s), chroma_words(s), words(s.v), w, h, g.chroma | g.cosited, g.range, g.matrix, g.depth, rgb, is, ps, n, st)
-                          : w2xc_launch_yuv8_to_rgb_sited(luma_planes(s), chroma_planes(s), s.v, w, h, g.chroma | g.cosited, g.range, g.matrix, rgb, is, ps, n, st);
-    return g.bps == 2 ? w2xc_launch_yuv16_to_rgb(luma_words(s), chroma_words(s), words(s.v), w, h, g.chroma, g.range, g.matrix, g.depth, rgb, is, ps, n, st)
-                      : w2xc_launch_yuv8_to_rgb(luma_planes(s), chroma_planes(s), s.v, w, h, g.chroma, g.range, g.matrix, rgb, is, ps, n, st);
+    return g.bps == 2 ? w2xc_launch_yuv16_to_rgb(luma_words(s), chroma_words(s), words(s.v), w, h, g.chroma | g.cosited, g.range, g.matrix, g.depth, rgb, is, ps, n, st)
+                      : w2xc_launch_yuv8_to_rgb(luma_planes(s), chroma_planes(s), s.v, w, h, g.chroma | g.cosited, g.range, g.matrix, rgb, is, ps, n, st);
 }
 hipError_t from_rgb(const YuvGeom &g, const float *rgb, long long is, long long ps, int w, int h, const YuvSide &s, int n, hipStream_t st)
 {
-    if (g.cosited)
-        return g.bps == 2 ? w2xc_launch_rgb_to_yuv16_sited(rgb, is, ps, w, h, g.chroma | g.cosited, g.range, g.matrix, g.depth, luma_words(s), chroma_words(s), words(s.v), n, st)
-                          : w2xc_launch_rgb_to_yuv8_sited(rgb, is, ps, w, h, g.chroma | g.cosited, g.range, g.matrix, luma_planes(s), chroma_planes(s), s.v, n, st);
-    return g.bps == 2 ? w2xc_launch_rgb_to_yuv16(rgb, is, ps, w, h, g.chroma, g.range, g.matrix, g.depth, luma_words(s), chroma_words(s), words(s.v), n, st)
-                      : w2xc_launch_rgb_to_yuv8(rgb, is, ps, w, h, g.chroma, g.range, g.matrix, luma_planes(s), chroma_planes(s), s.v, n, st);
+    return g.bps == 2 ? w2xc_launch_rgb_to_yuv16(rgb, is, ps, w, h, g.chroma | g.cosited, g.range, g.matrix, g.depth, luma_words(s), chroma_words(s), words(s.v), n, st)
+                      : w2xc_launch_rgb_to_yuv8(rgb, is, ps, w, h, g.chroma | g.cosited, g.range, g.matrix, luma_planes(s), chroma_planes(s), s.v, n, st);
 }
 
 // What a frame call runs for its chroma: the samples as they are where the output has the input's size, the bicubic 2x kernels at exactly twice it (the resize

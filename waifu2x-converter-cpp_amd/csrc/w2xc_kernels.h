@@ -198,7 +198,10 @@ hipError_t w2xc_launch_y8_to_plane(W2xcU8Planes src, int w, int h, int range, fl
 hipError_t w2xc_launch_plane_to_y8(const float *src, long long ps, int w, int h, int range, W2xcU8Planes dst, int n, hipStream_t st);
 // the bicubic 2x of chroma on bytes: the planes su (and sv: nullptr = one plane per frame) of cw x ch samples of n frames -> the leading ow x oh samples
 // (ow <= 2 cw, oh <= 2 ch) of their enlargements at du (and dv); bytes of Resize2xCubic + to_u8 on (float)byte * (float)(1.0 / 255.0).  One launch.
-hipError_t w2xc_launch_chroma2x_u8(W2xcU8Planes su, const unsigned char *sv, int cw, int ch, W2xcU8Planes du, unsigned char *dv, int ow, int oh, int n, hipStream_t st);
+// cosited: 0 = chroma centred between luma samples, or W2XC_CHROMA_COSITED_X | W2XC_CHROMA_COSITED_Y for chroma that sits ON luma column / row 2k
+// (include/w2xc_hip.h, "Chroma siting": the instantiations of w2xc_yuv_sited.hip, the same grid and load path); any other bit is hipErrorInvalidValue
+hipError_t w2xc_launch_chroma2x_u8(W2xcU8Planes su, const unsigned char *sv, int cw, int ch, W2xcU8Planes du, unsigned char *dv, int ow, int oh, int cosited, int n,
+                                   hipStream_t st);
 // ... and chroma bytes as they are (no 2x step): cw x ch samples per plane
 hipError_t w2xc_launch_chroma_copy_u8(W2xcU8Planes su, const unsigned char *sv, int cw, int ch, W2xcU8Planes du, unsigned char *dv, int n, hipStream_t st);
 // the grid rule of w2xc_launch_chroma2x_u8 / _u16 (chroma2x_tile_grid, w2xc_host_geom.hpp): tiles of W2XC_CHROMA_TQX x
@@ -212,7 +215,9 @@ hipError_t w2xc_launch_chroma_copy_u8(W2xcU8Planes su, const unsigned char *sv, 
 struct W2xcYuvToRgb { float cRV, cBU, cGV, cGU; };
 struct W2xcRgbToYuv { float Kr, Kg, Kb, iBU, iRV; };
 // n frames (luma y: px = 1; chroma u and v: one W2xcU8Planes geometry for both, px = 1 or 2) -> their 3 n float planes with contiguous rows of w: frame i's R, G
-// and B at rgb + i * is + {0, 1, 2} * ps FLOATS; chroma = W2XC_YUV_420 / _422 / _444, range = W2XC_RANGE_*, matrix = W2XC_MATRIX_*.  One launch.
+// and B at rgb + i * is + {0, 1, 2} * ps FLOATS; chroma = W2XC_YUV_420 / _422 / _444 with W2XC_CHROMA_COSITED_* or-ed on as the interface takes it (a flag picks
+// the instantiations of w2xc_yuv_rgb_sited.hip, the same grid, load paths and stores; a flag on an axis the layout does not subsample is hipErrorInvalidValue:
+// chroma_layout, w2xc_yuv_px.h), range = W2XC_RANGE_*, matrix = W2XC_MATRIX_*.  One launch.
 hipError_t w2xc_launch_yuv8_to_rgb(W2xcU8Planes y, W2xcU8Planes u, const unsigned char *v, int w, int h, int chroma, int range, int matrix, float *rgb, long long is,
                                    long long ps, int n, hipStream_t st);
 // ... and back: 3 n float planes of w x h -> the bytes of n frames.  One launch; only the frames' own samples are written.
@@ -232,34 +237,18 @@ struct W2xcU16Planes {
     long long frame, row;
     int px, pack;
 };
-// the launchers of the sections above on words: the same arguments and `depth` (8 .. 16); the chroma launchers take the two sides' packings from su / du
+// the launchers of the sections above on words: the same arguments -- `cosited` and the flags in `chroma` too: the instantiations of w2xc_yuv16_sited.hip and
+// w2xc_yuv16_rgb_sited.hip -- and `depth` (8 .. 16); the chroma launchers take the two sides' packings from su / du
 hipError_t w2xc_launch_y16_to_plane(W2xcU16Planes src, int w, int h, int range, int depth, float *dst, long long ps, int n, hipStream_t st);
 hipError_t w2xc_launch_plane_to_y16(const float *src, long long ps, int w, int h, int range, int depth, W2xcU16Planes dst, int n, hipStream_t st);
 // (a turn of k_chroma2x_u16 is one tile of ALL planes of one frame -- U, or U and V: tiles x n turns, at most W2XC_CHROMA_GRID_MAX workgroups)
-hipError_t w2xc_launch_chroma2x_u16(W2xcU16Planes su, const unsigned short *sv, int cw, int ch, W2xcU16Planes du, unsigned short *dv, int ow, int oh, int depth, int n,
-                                    hipStream_t st);
+hipError_t w2xc_launch_chroma2x_u16(W2xcU16Planes su, const unsigned short *sv, int cw, int ch, W2xcU16Planes du, unsigned short *dv, int ow, int oh, int depth,
+                                    int cosited, int n, hipStream_t st);
 hipError_t w2xc_launch_chroma_copy_u16(W2xcU16Planes su, const unsigned short *sv, int cw, int ch, W2xcU16Planes du, unsigned short *dv, int depth, int n, hipStream_t st);
 hipError_t w2xc_launch_yuv16_to_rgb(W2xcU16Planes y, W2xcU16Planes u, const unsigned short *v, int w, int h, int chroma, int range, int matrix, int depth, float *rgb,
                                     long long is, long long ps, int n, hipStream_t st);
 hipError_t w2xc_launch_rgb_to_yuv16(const float *rgb, long long is, long long ps, int w, int h, int chroma, int range, int matrix, int depth, W2xcU16Planes y,
                                     W2xcU16Planes u, unsigned short *v, int n, hipStream_t st);
-
-// ---- chroma co-sited with luma (w2xc_yuv_sited.hip, w2xc_yuv16_sited.hip, w2xc_yuv_rgb_sited.hip, w2xc_yuv16_rgb_sited.hip; include/w2xc_hip.h, "Chroma siting") ----
-// The six tile launchers above for chroma that sits ON luma column / row 2k: cosited = W2XC_CHROMA_COSITED_X | W2XC_CHROMA_COSITED_Y, at least one of them (0 is
-// the launchers above; a flag on an axis the layout does not subsample is hipErrorInvalidValue).  The launchers of the RGB route take the flags in `chroma`,
-// or-ed onto the layout, as the interface does.  Grids, load paths and stores are those of the centred launchers.
-hipError_t w2xc_launch_chroma2x_u8_sited(W2xcU8Planes su, const unsigned char *sv, int cw, int ch, W2xcU8Planes du, unsigned char *dv, int ow, int oh, int cosited, int n,
-                                         hipStream_t st);
-hipError_t w2xc_launch_chroma2x_u16_sited(W2xcU16Planes su, const unsigned short *sv, int cw, int ch, W2xcU16Planes du, unsigned short *dv, int ow, int oh, int depth,
-                                          int cosited, int n, hipStream_t st);
-hipError_t w2xc_launch_yuv8_to_rgb_sited(W2xcU8Planes y, W2xcU8Planes u, const unsigned char *v, int w, int h, int chroma, int range, int matrix, float *rgb,
-                                         long long is, long long ps, int n, hipStream_t st);
-hipError_t w2xc_launch_rgb_to_yuv8_sited(const float *rgb, long long is, long long ps, int w, int h, int chroma, int range, int matrix, W2xcU8Planes y, W2xcU8Planes u,
-                                         unsigned char *v, int n, hipStream_t st);
-hipError_t w2xc_launch_yuv16_to_rgb_sited(W2xcU16Planes y, W2xcU16Planes u, const unsigned short *v, int w, int h, int chroma, int range, int matrix, int depth,
-                                          float *rgb, long long is, long long ps, int n, hipStream_t st);
-hipError_t w2xc_launch_rgb_to_yuv16_sited(const float *rgb, long long is, long long ps, int w, int h, int chroma, int range, int matrix, int depth, W2xcU16Planes y,
-                                          W2xcU16Planes u, unsigned short *v, int n, hipStream_t st);
 
 // ---- chroma of the sized frame calls (w2xc_yuv_sized.hip, w2xc_yuv16_sized.hip; include/w2xc_hip.h, "Sized YUV frames") ----
 // The bicubic of the 2x launchers at any ratio r <= 1 per axis, in one launch from the input planes to the output planes: output sample m of an axis reads

@@ -9,7 +9,8 @@
 #include "w2xc_tta_px.h"   // clampi, to_u8
 #include "w2xc_px.h"       // k_px, launch_px, row_col, cubic_coeffs
 #include "w2xc_yuv_px.h"   // chroma_row_sum, luma_u8
-#include "w2xc_yuv_tile.h" // the tile of the bicubic 2x, the launch grid, rows_align
+#include "w2xc_yuv_tile.h" // the tile of the bicubic 2x, the launch grid
+#include "w2xc_yuv_launch.h" // the kernel's parameter list, the co-sited instantiations, chroma_prologue_u8
 
 // luma byte -> y: full range (float)Y * (float)(1.0 / 255.0), limited range ((float)Y - 16) * (float)(1.0 / 219.0).  Frame i's plane at dst + i * ps floats
 struct Y8ToPlane {
@@ -84,23 +85,25 @@ hipError_t w2xc_launch_chroma_copy_u8(W2xcU8Planes su, const unsigned char *sv, 
 // Stores: the thread's own bytes, one byte store each -- a quad's two columns start on an odd column, and with px = 2 the other plane's bytes lie between
 // them --, never a read-modify-write of a byte that is another thread's.
 template <bool DW>
-__global__ void __launch_bounds__(256) k_chroma2x_u8(const unsigned char *su, const unsigned char *sv, long long sframe, long long srow, int spx, int cw, int ch,
-                                                     unsigned char *du, unsigned char *dv, long long dframe, long long drow, int dpx, int ow, int oh, int npl,
-                                                     int tiles_x, long long tiles, long long turns)
+__global__ void __launch_bounds__(256) k_chroma2x_u8(W2XC_CHROMA2X_U8_PARAMS)
 {
     constexpr bool CX = false, CY = false;   // centred along both axes (the co-sited forms: w2xc_yuv_sited.hip)
 #include "w2xc_chroma2x_u8_body.inc"
 }
 
-hipError_t w2xc_launch_chroma2x_u8(W2xcU8Planes su, const unsigned char *sv, int cw, int ch, W2xcU8Planes du, unsigned char *dv, int ow, int oh, int n, hipStream_t st)
+// cosited: 0 = centred chroma, or W2XC_CHROMA_COSITED_X | _Y -- the same grid and load path, the kernel from w2xc_yuv_sited.hip
+hipError_t w2xc_launch_chroma2x_u8(W2xcU8Planes su, const unsigned char *sv, int cw, int ch, W2xcU8Planes du, unsigned char *dv, int ow, int oh, int cosited, int n,
+                                   hipStream_t st)
 {
-    if (cw < 1 || ch < 1 || ow < 1 || oh < 1 || ow > 2 * (long long)cw || oh > 2 * (long long)ch || n < 1 || (su.px != 1 && su.px != 2) || (du.px != 1 && du.px != 2) ||
-        !su.p || !du.p || (sv != nullptr) != (dv != nullptr))
+    int npl;
+    bool dw;
+    if (!chroma_prologue_u8(su, sv, cw, ch, du, dv, ow, oh, n, &npl, &dw) || ow > 2 * (long long)cw || oh > 2 * (long long)ch || !cosited_ok(cosited))
         return hipErrorInvalidValue;
-    const int npl = sv ? 2 : 1;
     const YuvTileGrid g = w2xc_eng::chroma2x_tile_grid(ow, oh, (long long)n * npl, CH_TQX, CH_TQY, W2XC_CHROMA_GRID_MAX);   // a turn: one tile of ONE plane
-    const bool dw = su.px == 1 && ((rows_align(su, n) | (sv ? reinterpret_cast<size_t>(sv) : 0)) & 3) == 0;
-    hipLaunchKernelGGL(dw ? k_chroma2x_u8<true> : k_chroma2x_u8<false>, dim3(g.grid), dim3(256), 0, st, su.p, sv, su.frame, su.row, su.px, cw, ch, du.p, dv, du.frame,
-                       du.row, du.px, ow, oh, npl, g.tiles_x, g.tiles, g.turns);
+    const Chroma2xU8Kernel kernel = cosited ? chroma2x_u8_sited_kernel(dw, cosited & W2XC_CHROMA_COSITED_X, cosited & W2XC_CHROMA_COSITED_Y)
+                                    : dw    ? k_chroma2x_u8<true>
+                                            : k_chroma2x_u8<false>;
+    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, st, su.p, sv, su.frame, su.row, su.px, cw, ch, du.p, dv, du.frame, du.row, du.px, ow, oh, npl, g.tiles_x,
+                       g.tiles, g.turns);
     return hipGetLastError();
 }

@@ -9,7 +9,8 @@
 #include "w2xc_tta_px.h"   // clampi
 #include "w2xc_px.h"       // k_px, launch_px, row_col, cubic_coeffs
 #include "w2xc_yuv_px.h"   // chroma_row_sum, u16_value, to_u16, luma_u16, u16_scale
-#include "w2xc_yuv_tile.h" // the tile of the bicubic 2x, the launch grid, rows_align
+#include "w2xc_yuv_tile.h" // the tile of the bicubic 2x, the launch grid
+#include "w2xc_yuv_launch.h" // the kernel's parameter list, the co-sited instantiations, chroma_prologue_u16
 
 // luma word -> y: full range (float)Y * (float)(1.0 / M), limited range ((float)Y - 16 s) * (float)(1.0 / (219 s)).  Frame i's plane at dst + i * ps floats
 struct Y16ToPlane {
@@ -92,32 +93,25 @@ hipError_t w2xc_launch_chroma_copy_u16(W2xcU16Planes su, const unsigned short *s
 // Stores: a thread writes only its own samples, as 16-bit stores, or -- pair: du and dv interleave as dv = du + 1 and the rows start on 4-byte boundaries -- its
 // (U, V) pair as ONE 32-bit store.  Never a read-modify-write of a word that is another thread's or another plane's.
 template <int LOAD>
-__global__ void __launch_bounds__(256) k_chroma2x_u16(const unsigned short *su, const unsigned short *sv, long long sframe, long long srow, int spx, int cw, int ch,
-                                                      int rshift, int max, unsigned short *du, unsigned short *dv, long long dframe, long long drow, int dpx,
-                                                      int lshift, int pair, int ow, int oh, int npl, float inv_max, float fmax, int tiles_x, long long tiles,
-                                                      long long turns)
+__global__ void __launch_bounds__(256) k_chroma2x_u16(W2XC_CHROMA2X_U16_PARAMS)
 {
     constexpr bool CX = false, CY = false;   // centred along both axes (the co-sited forms: w2xc_yuv16_sited.hip)
 #include "w2xc_chroma2x_u16_body.inc"
 }
 
-hipError_t w2xc_launch_chroma2x_u16(W2xcU16Planes su, const unsigned short *sv, int cw, int ch, W2xcU16Planes du, unsigned short *dv, int ow, int oh, int depth, int n,
-                                    hipStream_t st)
+// cosited: 0 = centred chroma, or W2XC_CHROMA_COSITED_X | _Y -- the same grid, load paths and pair store, the kernel from w2xc_yuv16_sited.hip
+hipError_t w2xc_launch_chroma2x_u16(W2xcU16Planes su, const unsigned short *sv, int cw, int ch, W2xcU16Planes du, unsigned short *dv, int ow, int oh, int depth,
+                                    int cosited, int n, hipStream_t st)
 {
-    if (cw < 1 || ch < 1 || ow < 1 || oh < 1 || ow > 2 * (long long)cw || oh > 2 * (long long)ch || n < 1 || (su.px != 1 && su.px != 2) || (du.px != 1 && du.px != 2) ||
-        !su.p || !du.p || (sv != nullptr) != (dv != nullptr) || depth < 8 || depth > 16)
+    ChromaU16 c;
+    if (!chroma_prologue_u16(su, sv, cw, ch, du, dv, ow, oh, depth, n, &c) || ow > 2 * (long long)cw || oh > 2 * (long long)ch || !cosited_ok(cosited))
         return hipErrorInvalidValue;
-    const int npl = sv ? 2 : 1;
     const YuvTileGrid g = w2xc_eng::chroma2x_tile_grid(ow, oh, n, CH_TQX, CH_TQY, W2XC_CHROMA_GRID_MAX);   // a turn: one tile of ALL planes of a frame
-    const size_t salign = rows_align(su, n), dalign = rows_align(du, n);
-    int load = 0;
-    if (su.px == 1 && ((salign | (sv ? reinterpret_cast<size_t>(sv) : 0)) & 7) == 0) load = 1;
-    else if (su.px == 2 && sv == su.p + 1 && (salign & 3) == 0) load = 2;
-    const int pair = du.px == 2 && dv == du.p + 1 && (dalign & 3) == 0;
-    const W2xcU16Scale k = u16_scale(depth, 0);
-    const int rshift = su.pack ? 16 - depth : 0, lshift = du.pack ? 16 - depth : 0;
-    const auto kernel = load == 2 ? k_chroma2x_u16<2> : load == 1 ? k_chroma2x_u16<1> : k_chroma2x_u16<0>;
-    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, st, su.p, sv, su.frame, su.row, su.px, cw, ch, rshift, k.max, du.p, dv, du.frame, du.row, du.px, lshift, pair,
-                       ow, oh, npl, k.inv_max, k.fmax, g.tiles_x, g.tiles, g.turns);
+    const Chroma2xU16Kernel kernel = cosited       ? chroma2x_u16_sited_kernel(c.load, cosited & W2XC_CHROMA_COSITED_X, cosited & W2XC_CHROMA_COSITED_Y)
+                                     : c.load == 2 ? k_chroma2x_u16<2>
+                                     : c.load == 1 ? k_chroma2x_u16<1>
+                                                   : k_chroma2x_u16<0>;
+    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, st, su.p, sv, su.frame, su.row, su.px, cw, ch, c.rshift, c.k.max, du.p, dv, du.frame, du.row, du.px, c.lshift,
+                       c.pair, ow, oh, c.npl, c.k.inv_max, c.k.fmax, g.tiles_x, g.tiles, g.turns);
     return hipGetLastError();
 }

@@ -11,6 +11,7 @@
 #include "w2xc_tta_px.h"   // clampi
 #include "w2xc_yuv_px.h"   // u16_value, to_u16, luma_u16, the constants of a matrix and of a depth
 #include "w2xc_yuv_tile.h" // the tile (YR_*), rows_align, yuv_tile_at, chroma_at_luma, rgb_px, chroma_mean
+#include "w2xc_yuv_launch.h" // the kernels' parameter lists, the co-sited instantiations
 
 #define YR_YLD (2 * YR_TCX + 2)     // 16-bit words per LDS row of luma: the widest tile and one dword of padding -- 33 dwords, an odd count
 static_assert((YR_YLD & 1) == 0 && ((YR_YLD / 2) & 1) == 1, "a luma row in LDS is whole dwords, an odd count of them");
@@ -26,23 +27,21 @@ static_assert((YR_YLD & 1) == 0 && ((YR_YLD / 2) & 1) == 1, "a luma row in LDS i
 // Stores: a thread's two pixels of a row are adjacent; v2 (every row of every plane starts on an 8-byte boundary: w, ps, is even) makes them ONE 8-byte store per
 // plane; otherwise two float stores.
 template <int CM, bool SX, bool SY>
-__global__ void __launch_bounds__(256) k_yuv16_to_rgb(const unsigned short *__restrict__ sy, long long yframe, long long yrow, int yv, int yshift,
-                                                      const unsigned short *__restrict__ su, const unsigned short *__restrict__ sv, long long cframe, long long crow,
-                                                      int spx, int cshift, int max, int w, int h, int cw, int ch, float y0, float ky, float c0, float kc,
-                                                      W2xcYuvToRgb m, float *__restrict__ rgb, long long is, long long ps, int v2, int tiles_x, long long tiles,
-                                                      long long turns)
+__global__ void __launch_bounds__(256) k_yuv16_to_rgb(W2XC_YUV16_TO_RGB_PARAMS)
 {
     constexpr bool CX = false, CY = false;   // centred siting (the co-sited forms: w2xc_yuv16_rgb_sited.hip)
 #include "w2xc_yuv16_to_rgb_body.inc"
 }
 
+// chroma: the layout with W2XC_CHROMA_COSITED_* or-ed on, or with none -- the same grid, load paths and stores, with a flag the kernel from w2xc_yuv16_rgb_sited.hip
 hipError_t w2xc_launch_yuv16_to_rgb(W2xcU16Planes y, W2xcU16Planes u, const unsigned short *v, int w, int h, int chroma, int range, int matrix, int depth, float *rgb,
                                     long long is, long long ps, int n, hipStream_t st)
 {
     W2xcYuvToRgb m;
+    ChromaLayout c;
     int cw, ch;
-    if (!matrix_to_rgb(matrix, &m) || !frame_geometry(w, h, chroma, &cw, &ch) || n < 1 || !y.p || !u.p || !v || !rgb || y.px != 1 || (u.px != 1 && u.px != 2) ||
-        depth < 8 || depth > 16)
+    if (!matrix_to_rgb(matrix, &m) || !chroma_layout(chroma, &c) || !frame_geometry(w, h, c.layout, &cw, &ch) || n < 1 || !y.p || !u.p || !v || !rgb || y.px != 1 ||
+        (u.px != 1 && u.px != 2) || depth < 8 || depth > 16)
         return hipErrorInvalidValue;
     const YuvTileGrid g = w2xc_eng::yuv_rgb_tile_grid(cw, ch, n, YR_TCX, YR_TCY, W2XC_YUVRGB_GRID_MAX);
     const int yv = (rows_align(y, n) & 7) == 0;
@@ -52,7 +51,10 @@ hipError_t w2xc_launch_yuv16_to_rgb(W2xcU16Planes y, W2xcU16Planes u, const unsi
     const W2xcU16Scale k = u16_scale(depth, range != 0);
     const int v2 = rows_8_aligned(rgb, is, ps, w, n), yshift = y.pack ? 16 - depth : 0, cshift = u.pack ? 16 - depth : 0;
 #define W2XC_TO_RGB16(SX, SY) (cm == 2 ? k_yuv16_to_rgb<2, SX, SY> : cm == 1 ? k_yuv16_to_rgb<1, SX, SY> : k_yuv16_to_rgb<0, SX, SY>)
-    const auto kernel = chroma == 0 ? W2XC_TO_RGB16(true, true) : chroma == 1 ? W2XC_TO_RGB16(true, false) : W2XC_TO_RGB16(false, false);
+    const Yuv16ToRgbKernel kernel = c.cx || c.cy    ? yuv16_to_rgb_sited_kernel(cm, c.layout, c.cx, c.cy)
+                                    : c.layout == 0 ? W2XC_TO_RGB16(true, true)
+                                    : c.layout == 1 ? W2XC_TO_RGB16(true, false)
+                                                    : W2XC_TO_RGB16(false, false);
 #undef W2XC_TO_RGB16
     hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, st, y.p, y.frame, y.row, yv, yshift, u.p, v, u.frame, u.row, u.px, cshift, k.max, w, h, cw, ch, k.y_off, k.y_in,
                        k.c_mid, k.c_in, m, rgb, is, ps, v2, g.tiles_x, g.tiles, g.turns);
@@ -66,11 +68,7 @@ hipError_t w2xc_launch_yuv16_to_rgb(W2xcU16Planes y, W2xcU16Planes u, const unsi
 // Never a read-modify-write: with dpx = 2 and planes that do not interleave, the words between a plane's samples are another plane's.  No LDS.
 // Loads: v2 (every row of every float plane starts on an 8-byte boundary) fetches a thread's two adjacent pixels of a row as ONE 8-byte load per plane.
 template <bool SX, bool SY>
-__global__ void __launch_bounds__(256) k_rgb_to_yuv16(const float *__restrict__ rgb, long long is, long long ps, int v2, int w, int h, int cw, int ch, int limited,
-                                                      int max, float ys, float y0, float cs, float c0, W2xcRgbToYuv m, unsigned short *__restrict__ dy,
-                                                      long long yframe, long long yrow, int y32, int yshift, unsigned short *__restrict__ du,
-                                                      unsigned short *__restrict__ dv, long long cframe, long long crow, int dpx, int uv32, int cshift, int tiles_x,
-                                                      long long tiles, long long turns)
+__global__ void __launch_bounds__(256) k_rgb_to_yuv16(W2XC_RGB_TO_YUV16_PARAMS)
 {
     constexpr bool CX = false, CY = false;   // centred siting (the co-sited forms: w2xc_yuv16_rgb_sited.hip)
 #include "w2xc_rgb_to_yuv16_body.inc"
@@ -80,16 +78,20 @@ hipError_t w2xc_launch_rgb_to_yuv16(const float *rgb, long long is, long long ps
                                     W2xcU16Planes u, unsigned short *v, int n, hipStream_t st)
 {
     W2xcRgbToYuv m;
+    ChromaLayout c;
     int cw, ch;
-    if (!matrix_from_rgb(matrix, &m) || !frame_geometry(w, h, chroma, &cw, &ch) || n < 1 || !y.p || !u.p || !v || !rgb || y.px != 1 || (u.px != 1 && u.px != 2) ||
-        depth < 8 || depth > 16)
+    if (!matrix_from_rgb(matrix, &m) || !chroma_layout(chroma, &c) || !frame_geometry(w, h, c.layout, &cw, &ch) || n < 1 || !y.p || !u.p || !v || !rgb || y.px != 1 ||
+        (u.px != 1 && u.px != 2) || depth < 8 || depth > 16)
         return hipErrorInvalidValue;
     const YuvTileGrid g = w2xc_eng::yuv_rgb_tile_grid(cw, ch, n, YR_TCX, YR_TCY, W2XC_YUVRGB_GRID_MAX);
     const int y32 = (rows_align(y, n) & 3) == 0;
     const int uv32 = u.px == 2 && v == u.p + 1 && (rows_align(u, n) & 3) == 0;
     const W2xcU16Scale k = u16_scale(depth, range != 0);
     const int limited = range != 0, v2 = rows_8_aligned(rgb, is, ps, w, n), yshift = y.pack ? 16 - depth : 0, cshift = u.pack ? 16 - depth : 0;
-    const auto kernel = chroma == 0 ? k_rgb_to_yuv16<true, true> : chroma == 1 ? k_rgb_to_yuv16<true, false> : k_rgb_to_yuv16<false, false>;
+    const RgbToYuv16Kernel kernel = c.cx || c.cy    ? rgb_to_yuv16_sited_kernel(c.layout, c.cx, c.cy)
+                                    : c.layout == 0 ? k_rgb_to_yuv16<true, true>
+                                    : c.layout == 1 ? k_rgb_to_yuv16<true, false>
+                                                    : k_rgb_to_yuv16<false, false>;
     hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, st, rgb, is, ps, v2, w, h, cw, ch, limited, k.max, k.y_out, k.y_off, k.c_out, k.c_mid, m, y.p, y.frame, y.row,
                        y32, yshift, u.p, v, u.frame, u.row, u.px, uv32, cshift, g.tiles_x, g.tiles, g.turns);
     return hipGetLastError();

@@ -11,7 +11,8 @@
 #include "w2xc_tta_px.h"   // clampi
 #include "w2xc_px.h"       // cubic_coeffs
 #include "w2xc_yuv_px.h"   // chroma_row_sum, u16_value, to_u16, u16_scale
-#include "w2xc_yuv_tile.h" // CH_SW, CH_SH, CH_LD, rows_align; w2xc_host_geom.hpp: chroma_resize_pos / _floor / _origin, chroma_resize_tile_grid
+#include "w2xc_yuv_tile.h" // CH_SW, CH_SH, CH_LD; w2xc_host_geom.hpp: chroma_resize_pos / _floor / _origin, chroma_resize_tile_grid
+#include "w2xc_yuv_launch.h" // chroma_prologue_u16: the checks, load paths, pair store, shifts and scales of the 2x launcher
 
 #define CR_TX W2XC_CHROMA_RESIZE_TX
 #define CR_TY W2XC_CHROMA_RESIZE_TY
@@ -116,20 +117,13 @@ __global__ void __launch_bounds__(256) k_chroma_resize_u16(const unsigned short 
 hipError_t w2xc_launch_chroma_resize_u16(W2xcU16Planes su, const unsigned short *sv, int cw, int ch, W2xcU16Planes du, unsigned short *dv, int ow, int oh, int depth,
                                          double rx, double ox, double ry, double oy, int n, hipStream_t st)
 {
-    if (cw < 1 || ch < 1 || ow < 1 || oh < 1 || n < 1 || (su.px != 1 && su.px != 2) || (du.px != 1 && du.px != 2) || !su.p || !du.p || (sv != nullptr) != (dv != nullptr) ||
-        depth < 8 || depth > 16 || !(rx > 0.0 && rx <= 1.0) || !(ry > 0.0 && ry <= 1.0) || (ox != 0.5 && ox != 0.25) || (oy != 0.5 && oy != 0.25))
+    ChromaU16 c;
+    if (!chroma_prologue_u16(su, sv, cw, ch, du, dv, ow, oh, depth, n, &c) || !(rx > 0.0 && rx <= 1.0) || !(ry > 0.0 && ry <= 1.0) || (ox != 0.5 && ox != 0.25) ||
+        (oy != 0.5 && oy != 0.25))
         return hipErrorInvalidValue;
-    const int npl = sv ? 2 : 1;
     const YuvTileGrid g = w2xc_eng::chroma_resize_tile_grid(ow, oh, n, CR_TX, CR_TY, W2XC_CHROMA_GRID_MAX);   // a turn: one tile of ALL planes of a frame
-    const size_t salign = rows_align(su, n), dalign = rows_align(du, n);
-    int load = 0;
-    if (su.px == 1 && ((salign | (sv ? reinterpret_cast<size_t>(sv) : 0)) & 7) == 0) load = 1;
-    else if (su.px == 2 && sv == su.p + 1 && (salign & 3) == 0) load = 2;
-    const int pair = du.px == 2 && dv == du.p + 1 && (dalign & 3) == 0;
-    const W2xcU16Scale k = u16_scale(depth, 0);
-    const int rshift = su.pack ? 16 - depth : 0, lshift = du.pack ? 16 - depth : 0;
-    const auto kernel = load == 2 ? k_chroma_resize_u16<2> : load == 1 ? k_chroma_resize_u16<1> : k_chroma_resize_u16<0>;
-    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, st, su.p, sv, su.frame, su.row, su.px, cw, ch, rshift, k.max, du.p, dv, du.frame, du.row, du.px, lshift, pair,
-                       ow, oh, npl, k.inv_max, k.fmax, rx, ox, ry, oy, g.tiles_x, g.tiles, g.turns);
+    const auto kernel = c.load == 2 ? k_chroma_resize_u16<2> : c.load == 1 ? k_chroma_resize_u16<1> : k_chroma_resize_u16<0>;
+    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, st, su.p, sv, su.frame, su.row, su.px, cw, ch, c.rshift, c.k.max, du.p, dv, du.frame, du.row, du.px, c.lshift,
+                       c.pair, ow, oh, c.npl, c.k.inv_max, c.k.fmax, rx, ox, ry, oy, g.tiles_x, g.tiles, g.turns);
     return hipGetLastError();
 }

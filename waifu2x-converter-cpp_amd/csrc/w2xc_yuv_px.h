@@ -110,26 +110,26 @@ static inline int rows_8_aligned(const float *rgb, long long is, long long ps, i
     return ((reinterpret_cast<size_t>(rgb) & 7) == 0 && (w & 1) == 0 && (ps & 1) == 0 && (n == 1 || (is & 1) == 0)) ? 1 : 0;
 }
 
-// the chroma planes of a w x h frame of the RGB route (4:2:0, 4:2:2, 4:4:4)
-static inline bool frame_geometry(int w, int h, int chroma, int *cw, int *ch)
+// a `chroma` value of the RGB route as the interface takes it: the layout (4:2:0, 4:2:2, 4:4:4) with the siting flags W2XC_CHROMA_COSITED_X 0x10 / _Y 0x20 or-ed
+// on, or with none.  False for another bit, another layout, or a flag on an axis the layout does not subsample (the interface's rule, check_chroma_range in
+// w2xc_image_yuv.cpp, refuses the same with a message): a launcher that decodes its `chroma` here honours every flag it accepts
+struct ChromaLayout {
+    int layout;
+    bool cx, cy;
+};
+static inline bool chroma_layout(int chroma, ChromaLayout *c)
 {
-    if (w < 1 || h < 1 || chroma < 0) return false;
-    chroma &= 0xF;   // (the siting flags, W2XC_CHROMA_COSITED_*, do not change a size)
-    if (chroma > 2) return false;
-    *cw = chroma != 2 ? (w + 1) / 2 : w;
-    *ch = chroma == 0 ? (h + 1) / 2 : h;
-    return true;
+    if (chroma < 0 || (chroma & ~0x3F)) return false;
+    *c = {chroma & 0xF, (chroma & 0x10) != 0, (chroma & 0x20) != 0};
+    return c->layout == 0 || (c->layout == 1 && !c->cy) || (c->layout == 2 && !c->cx && !c->cy);
 }
-
-// a `chroma` value of the RGB route WITH siting flags (W2XC_CHROMA_COSITED_X 0x10, _Y 0x20): its layout and the two flags; false where it has no flag, another
-// bit, or a flag on an axis its layout does not subsample (the interface's rule, check_chroma_range in w2xc_image_yuv.cpp, refuses the same with a message)
-static inline bool sited_layout(int chroma, int *layout, bool *cx, bool *cy)
+// the chroma planes of a w x h frame of that layout (the siting does not change a size)
+static inline bool frame_geometry(int w, int h, int layout, int *cw, int *ch)
 {
-    if (chroma < 0 || (chroma & ~0x3F) || !(chroma & 0x30)) return false;
-    *layout = chroma & 0xF;
-    *cx = (chroma & 0x10) != 0;
-    *cy = (chroma & 0x20) != 0;
-    return *layout == 0 || (*layout == 1 && !*cy);
+    if (w < 1 || h < 1 || layout < 0 || layout > 2) return false;
+    *cw = layout != 2 ? (w + 1) / 2 : w;
+    *ch = layout == 0 ? (h + 1) / 2 : h;
+    return true;
 }
 
 // the scales and offsets of a depth (D bits, s = 2^(D - 8), M = 2^D - 1) and a range, computed in double and rounded once to float

@@ -12,6 +12,7 @@
 #include "w2xc_tta_px.h"   // clampi, to_u8
 #include "w2xc_yuv_px.h"   // luma_u8, the constants of a matrix
 #include "w2xc_yuv_tile.h" // the tile (YR_*), rows_align, yuv_tile_at, chroma_at_luma, rgb_px, chroma_mean
+#include "w2xc_yuv_launch.h" // the kernels' parameter lists, the co-sited instantiations
 
 #define YR_YLD (2 * YR_TCX + 4)     // bytes per LDS row of luma: the widest tile and one dword of padding
 static_assert((YR_YLD & 3) == 0, "a luma row in LDS is whole dwords");
@@ -23,21 +24,21 @@ static_assert((YR_YLD & 3) == 0, "a luma row in LDS is whole dwords");
 // Stores: a thread's two pixels of a row are adjacent; v2 (every row of every plane starts on an 8-byte boundary: w, ps, is even) makes them ONE 8-byte store per
 // plane, a wave's stores a contiguous run of the row; otherwise two float stores.
 template <bool DW, bool SX, bool SY>
-__global__ void __launch_bounds__(256) k_yuv8_to_rgb(const unsigned char *__restrict__ sy, long long yframe, long long yrow, const unsigned char *__restrict__ su,
-                                                     const unsigned char *__restrict__ sv, long long cframe, long long crow, int spx, int w, int h, int cw, int ch,
-                                                     int limited, W2xcYuvToRgb m, float *__restrict__ rgb, long long is, long long ps, int v2, int tiles_x,
-                                                     long long tiles, long long turns)
+__global__ void __launch_bounds__(256) k_yuv8_to_rgb(W2XC_YUV8_TO_RGB_PARAMS)
 {
     constexpr bool CX = false, CY = false;   // centred siting (the co-sited forms: w2xc_yuv_rgb_sited.hip)
 #include "w2xc_yuv8_to_rgb_body.inc"
 }
 
+// chroma: the layout with W2XC_CHROMA_COSITED_* or-ed on, or with none -- the same grid, load paths and stores, with a flag the kernel from w2xc_yuv_rgb_sited.hip
 hipError_t w2xc_launch_yuv8_to_rgb(W2xcU8Planes y, W2xcU8Planes u, const unsigned char *v, int w, int h, int chroma, int range, int matrix, float *rgb, long long is,
                                    long long ps, int n, hipStream_t st)
 {
     W2xcYuvToRgb m;
+    ChromaLayout c;
     int cw, ch;
-    if (!matrix_to_rgb(matrix, &m) || !frame_geometry(w, h, chroma, &cw, &ch) || n < 1 || !y.p || !u.p || !v || !rgb || y.px != 1 || (u.px != 1 && u.px != 2))
+    if (!matrix_to_rgb(matrix, &m) || !chroma_layout(chroma, &c) || !frame_geometry(w, h, c.layout, &cw, &ch) || n < 1 || !y.p || !u.p || !v || !rgb || y.px != 1 ||
+        (u.px != 1 && u.px != 2))
         return hipErrorInvalidValue;
     const YuvTileGrid g = w2xc_eng::yuv_rgb_tile_grid(cw, ch, n, YR_TCX, YR_TCY, W2XC_YUVRGB_GRID_MAX);
     size_t align = rows_align(y, n);
@@ -45,7 +46,10 @@ hipError_t w2xc_launch_yuv8_to_rgb(W2xcU8Planes y, W2xcU8Planes u, const unsigne
     const bool dw = (align & 3) == 0;
     const int limited = range != 0, v2 = rows_8_aligned(rgb, is, ps, w, n);
 #define W2XC_TO_RGB(SX, SY) (dw ? k_yuv8_to_rgb<true, SX, SY> : k_yuv8_to_rgb<false, SX, SY>)
-    const auto kernel = chroma == 0 ? W2XC_TO_RGB(true, true) : chroma == 1 ? W2XC_TO_RGB(true, false) : W2XC_TO_RGB(false, false);
+    const Yuv8ToRgbKernel kernel = c.cx || c.cy    ? yuv8_to_rgb_sited_kernel(dw, c.layout, c.cx, c.cy)
+                                   : c.layout == 0 ? W2XC_TO_RGB(true, true)
+                                   : c.layout == 1 ? W2XC_TO_RGB(true, false)
+                                                   : W2XC_TO_RGB(false, false);
 #undef W2XC_TO_RGB
     hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, st, y.p, y.frame, y.row, u.p, v, u.frame, u.row, u.px, w, h, cw, ch, limited, m, rgb, is, ps, v2,
                        g.tiles_x, g.tiles, g.turns);
@@ -60,10 +64,7 @@ hipError_t w2xc_launch_yuv8_to_rgb(W2xcU8Planes y, W2xcU8Planes u, const unsigne
 // (chroma_u8, the rounding of cb and cr to a byte: w2xc_yuv_px.h)
 
 template <bool SX, bool SY>
-__global__ void __launch_bounds__(256) k_rgb_to_yuv8(const float *__restrict__ rgb, long long is, long long ps, int v2, int w, int h, int cw, int ch, int limited,
-                                                     W2xcRgbToYuv m, unsigned char *__restrict__ dy, long long yframe, long long yrow, int y16,
-                                                     unsigned char *__restrict__ du, unsigned char *__restrict__ dv, long long cframe, long long crow, int dpx,
-                                                     int tiles_x, long long tiles, long long turns)
+__global__ void __launch_bounds__(256) k_rgb_to_yuv8(W2XC_RGB_TO_YUV8_PARAMS)
 {
     constexpr bool CX = false, CY = false;   // centred siting (the co-sited forms: w2xc_yuv_rgb_sited.hip)
 #include "w2xc_rgb_to_yuv8_body.inc"
@@ -73,13 +74,18 @@ hipError_t w2xc_launch_rgb_to_yuv8(const float *rgb, long long is, long long ps,
                                    unsigned char *v, int n, hipStream_t st)
 {
     W2xcRgbToYuv m;
+    ChromaLayout c;
     int cw, ch;
-    if (!matrix_from_rgb(matrix, &m) || !frame_geometry(w, h, chroma, &cw, &ch) || n < 1 || !y.p || !u.p || !v || !rgb || y.px != 1 || (u.px != 1 && u.px != 2))
+    if (!matrix_from_rgb(matrix, &m) || !chroma_layout(chroma, &c) || !frame_geometry(w, h, c.layout, &cw, &ch) || n < 1 || !y.p || !u.p || !v || !rgb || y.px != 1 ||
+        (u.px != 1 && u.px != 2))
         return hipErrorInvalidValue;
     const YuvTileGrid g = w2xc_eng::yuv_rgb_tile_grid(cw, ch, n, YR_TCX, YR_TCY, W2XC_YUVRGB_GRID_MAX);
     const int y16 = (rows_align(y, n) & 1) == 0;
     const int limited = range != 0, v2 = rows_8_aligned(rgb, is, ps, w, n);
-    const auto kernel = chroma == 0 ? k_rgb_to_yuv8<true, true> : chroma == 1 ? k_rgb_to_yuv8<true, false> : k_rgb_to_yuv8<false, false>;
+    const RgbToYuv8Kernel kernel = c.cx || c.cy    ? rgb_to_yuv8_sited_kernel(c.layout, c.cx, c.cy)
+                                   : c.layout == 0 ? k_rgb_to_yuv8<true, true>
+                                   : c.layout == 1 ? k_rgb_to_yuv8<true, false>
+                                                   : k_rgb_to_yuv8<false, false>;
     hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(256), 0, st, rgb, is, ps, v2, w, h, cw, ch, limited, m, y.p, y.frame, y.row, y16, u.p, v, u.frame, u.row, u.px,
                        g.tiles_x, g.tiles, g.turns);
     return hipGetLastError();

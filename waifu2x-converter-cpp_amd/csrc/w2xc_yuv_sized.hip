@@ -15,7 +15,8 @@
 #include "w2xc_tta_px.h"   // clampi, to_u8
 #include "w2xc_px.h"       // cubic_coeffs
 #include "w2xc_yuv_px.h"   // chroma_row_sum
-#include "w2xc_yuv_tile.h" // CH_SW, CH_SH, CH_LD, rows_align; w2xc_host_geom.hpp: chroma_resize_pos / _floor / _origin, chroma_resize_tile_grid
+#include "w2xc_yuv_tile.h" // CH_SW, CH_SH, CH_LD; w2xc_host_geom.hpp: chroma_resize_pos / _floor / _origin, chroma_resize_tile_grid
+#include "w2xc_yuv_launch.h" // chroma_prologue_u8: the checks and the load path of the 2x launcher
 
 #define CR_TX W2XC_CHROMA_RESIZE_TX
 #define CR_TY W2XC_CHROMA_RESIZE_TY
@@ -99,12 +100,12 @@ __global__ void __launch_bounds__(256) k_chroma_resize_u8(const unsigned char *s
 hipError_t w2xc_launch_chroma_resize_u8(W2xcU8Planes su, const unsigned char *sv, int cw, int ch, W2xcU8Planes du, unsigned char *dv, int ow, int oh,
                                         double rx, double ox, double ry, double oy, int n, hipStream_t st)
 {
-    if (cw < 1 || ch < 1 || ow < 1 || oh < 1 || n < 1 || (su.px != 1 && su.px != 2) || (du.px != 1 && du.px != 2) || !su.p || !du.p || (sv != nullptr) != (dv != nullptr) ||
-        !(rx > 0.0 && rx <= 1.0) || !(ry > 0.0 && ry <= 1.0) || (ox != 0.5 && ox != 0.25) || (oy != 0.5 && oy != 0.25))
+    int npl;
+    bool dw;
+    if (!chroma_prologue_u8(su, sv, cw, ch, du, dv, ow, oh, n, &npl, &dw) || !(rx > 0.0 && rx <= 1.0) || !(ry > 0.0 && ry <= 1.0) || (ox != 0.5 && ox != 0.25) ||
+        (oy != 0.5 && oy != 0.25))
         return hipErrorInvalidValue;
-    const int npl = sv ? 2 : 1;
     const YuvTileGrid g = w2xc_eng::chroma_resize_tile_grid(ow, oh, (long long)n * npl, CR_TX, CR_TY, W2XC_CHROMA_GRID_MAX);   // a turn: one tile of ONE plane
-    const bool dw = su.px == 1 && ((rows_align(su, n) | (sv ? reinterpret_cast<size_t>(sv) : 0)) & 3) == 0;
     hipLaunchKernelGGL(dw ? k_chroma_resize_u8<true> : k_chroma_resize_u8<false>, dim3(g.grid), dim3(256), 0, st, su.p, sv, su.frame, su.row, su.px, cw, ch, du.p, dv,
                        du.frame, du.row, du.px, ow, oh, npl, rx, ox, ry, oy, g.tiles_x, g.tiles, g.turns);
     return hipGetLastError();
