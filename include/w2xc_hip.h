@@ -30,7 +30,7 @@ extern "C" {
 #define W2XC_ERR_PLANES      -4   /* number of input planes mismatch (modelHandler.cpp:29-35)        */
 #define W2XC_ERR_HIP         -5   /* HIP runtime error / no device                                   */
 #define W2XC_ERR_UNSUPPORTED -6   /* kernel size != 3 (hpp:52-58 only demands square; see Q8)        */
-#define W2XC_ERR_NOMEM       -7
+#define W2XC_ERR_NOMEM       -7   /* an allocation failed: host, page-locked or device memory, weights included */
 
 /* One loaded model file == the reference's std::vector<std::unique_ptr<w2xc::Model>>
  * (one w2xc::Model per conv layer, modelHandler.hpp:24-90). */
@@ -1067,6 +1067,22 @@ int w2xc_plan_region(const w2xc_row_plan *plan, int plane_h, int layer, int y0, 
  * gives on fresh memory for every `word`: tests/test_gpu_scratch_poison.py.  device = -1: the current device.  Not to be called concurrently with
  * asynchronous work of the caller on this (model, device) that has not been synchronised. */
 int w2xc_debug_fill_scratch(w2xc_model *m, int device, unsigned word, unsigned long long *bytes);
+
+/* Test aid (0.4.1.12).  Makes ONE later event of `kind` fail on the host, in place of the runtime call it stands for -- nothing faulty reaches the device:
+ *   W2XC_DEBUG_FAIL_ALLOC   a grow-only buffer that has to grow (the allocation behind the drain and the release of the old buffer; a buffer that is
+ *                           large enough is no event) and the allocation of a weight image            -> the call returns W2XC_ERR_NOMEM
+ *   W2XC_DEBUG_FAIL_COPY    the upload of a weight image (with the model's first use on a device, and of the lazily packed images with the first
+ *                           call that runs their kernel)                                                  -> W2XC_ERR_HIP
+ *   W2XC_DEBUG_FAIL_LAUNCH  the launch of a model layer (every conv / upconv launch of every entry point; not the colour, YUV, TTA and resize
+ *                           stages, not copies, streams or events): nothing is launched               -> W2XC_ERR_HIP
+ * nth >= 1: the nth event of that kind from now on, in the whole process, fails once; the seam is then disarmed.  nth = 0 disarms.  Returns the number
+ * of events of that kind since the previous call with that kind (0 for the first): a caller counts a call's events between two calls with nth = 0.
+ * An unknown kind or a negative nth returns -1 and arms nothing.  Costs one relaxed load per event in a process that never calls it; reads no
+ * environment variable.  What a caller may assume after the non-zero return: INTEGRATION.md "After an error"; tests/test_gpu_fail_paths.py. */
+#define W2XC_DEBUG_FAIL_ALLOC  1
+#define W2XC_DEBUG_FAIL_COPY   2
+#define W2XC_DEBUG_FAIL_LAUNCH 3
+long long w2xc_debug_fail_nth(int kind, long long nth);
 
 int w2xc_device_count(void);          /* hipGetDeviceCount, 0 when no device / no driver           */
 const char *w2xc_last_error(void);    /* thread-local message of the last failing call             */

@@ -301,7 +301,8 @@ def image_row(id, symbol, py, models, n=None, ch=3, tta=False, call=None, **kw):
 def _image_rows():
     def plain(ctx, noise, scale, pi, li, po, lo, w, h, st, o):
         rc = ctx.w.lib().w2xc_process_image_u8_device(noise.handle, scale.handle, pi, li.row, w, h, po, lo.row, 1, st or None, o)
-        assert rc == 0, ctx.w.last_error()
+        if rc != 0:     # (as the package's wrappers: tests/test_gpu_fail_paths.py reads the code)
+            raise ctx.w.W2xcError(rc, ctx.w.last_error())
 
     def scale2x(ctx, noise, scale, pi, li, po, lo, w, h, st, o):
         scale.scale2x_image_u8_device(pi, li.row, w, h, po, lo.row, iterations=1, stream=st, opts=o)
@@ -445,7 +446,8 @@ def _colour_rows():
 
     def lib_call(ctx, name, *args):
         rc = getattr(ctx.w.lib(), name)(*args)      # (the argument types are declared: integers pass as pointers)
-        assert rc == 0, ctx.w.last_error()
+        if rc != 0:
+            raise ctx.w.W2xcError(rc, ctx.w.last_error())
 
     def u8_to(name, py):
         def build(ctx, v=0):

@@ -207,6 +207,7 @@ def _load():
         "w2xc_profile_read": (ci, [vp, ci, C.POINTER(C.c_float), C.POINTER(ci), ci]),
         "w2xc_profile_reset": (None, [vp, ci]),
         "w2xc_debug_fill_scratch": (ci, [vp, ci, C.c_uint, C.POINTER(C.c_ulonglong)]),
+        "w2xc_debug_fail_nth": (C.c_longlong, [ci, C.c_longlong]),
         "w2xc_layer_kernel_name": (C.c_char_p, [vp, ci, C.POINTER(Opts)]),
         "w2xc_device_count": (ci, []),
         "w2xc_last_error": (C.c_char_p, []),
@@ -232,6 +233,15 @@ def last_error():
 
 def device_count():
     return _lib.w2xc_device_count()
+
+
+DEBUG_FAIL_ALLOC, DEBUG_FAIL_COPY, DEBUG_FAIL_LAUNCH = 1, 2, 3
+
+
+def debug_fail_nth(kind, nth):
+    """Test aid (w2xc_debug_fail_nth): the nth event of `kind` (DEBUG_FAIL_*) from now on fails once, on the host, in place of the runtime call; nth = 0
+    disarms.  -> the events of that kind since the previous call with that kind; -1 for an unknown kind or a negative nth (nothing is armed)."""
+    return int(_lib.w2xc_debug_fail_nth(int(kind), int(nth)))
 
 
 def make_opts(**kw):

@@ -655,49 +655,61 @@ int batch_host_on_device(const HostBatch &b, int dev, const w2xc_opts &o, int co
         }
         return W2XC_OK;
     };
-    for (int j = 0; j < (int)subs.size(); j++) {
-        const int first = subs[j].first, cnt = subs[j].second, slot = j & 1;
-        char *din = p.d_in.as<char>() + (size_t)slot * sub * in_img, *dout = p.d_out.as<char>() + (size_t)slot * sub * out_img;
-        // ---- upload into device slot `slot` once the launches of sub-batch j - 2 have read it ----
-        if (j >= 2) HIP_TRY(hipStreamWaitEvent(p.s_h2d, p.ev_batch[slot], 0));
-        const int is = j % HostPipe::IN_SLOTS;
-        char *stage = any_in_pageable ? p.pin_in.as<char>() + (size_t)is * p.in_slot_bytes() : nullptr;
-        if (any_in_pageable && j >= HostPipe::IN_SLOTS) HIP_TRY(hipEventSynchronize(p.ev_in_slot[is]));   // its last DMA has read it
-        for (int k = 0; k < cnt; k++) {
-            const int i = first + k;
-            if (in_pin[i]) {
-                HIP_TRY(hipMemcpy2DAsync(din + (size_t)k * in_img, in_row, b.in[i], b.in_stride, in_row, b.in_rows, hipMemcpyHostToDevice, p.s_h2d));
-            } else {
-                char *st = stage + (size_t)k * in_img;
-                w2xc_host::CopyPool::get().copy_rows(st, in_row, (const char *)b.in[i], b.in_stride, in_row, b.in_rows, copy_threads);
-                HIP_TRY(hipMemcpyAsync(din + (size_t)k * in_img, st, in_row * b.in_rows, hipMemcpyHostToDevice, p.s_h2d));
+    // the sub-batches; whatever fails inside, nothing stays in flight (below)
+    rc = [&]() -> int {
+        for (int j = 0; j < (int)subs.size(); j++) {
+            const int first = subs[j].first, cnt = subs[j].second, slot = j & 1;
+            char *din = p.d_in.as<char>() + (size_t)slot * sub * in_img, *dout = p.d_out.as<char>() + (size_t)slot * sub * out_img;
+            // ---- upload into device slot `slot` once the launches of sub-batch j - 2 have read it ----
+            if (j >= 2) HIP_TRY(hipStreamWaitEvent(p.s_h2d, p.ev_batch[slot], 0));
+            const int is = j % HostPipe::IN_SLOTS;
+            char *stage = any_in_pageable ? p.pin_in.as<char>() + (size_t)is * p.in_slot_bytes() : nullptr;
+            if (any_in_pageable && j >= HostPipe::IN_SLOTS) HIP_TRY(hipEventSynchronize(p.ev_in_slot[is]));   // its last DMA has read it
+            for (int k = 0; k < cnt; k++) {
+                const int i = first + k;
+                if (in_pin[i]) {
+                    HIP_TRY(hipMemcpy2DAsync(din + (size_t)k * in_img, in_row, b.in[i], b.in_stride, in_row, b.in_rows, hipMemcpyHostToDevice, p.s_h2d));
+                } else {
+                    char *st = stage + (size_t)k * in_img;
+                    w2xc_host::CopyPool::get().copy_rows(st, in_row, (const char *)b.in[i], b.in_stride, in_row, b.in_rows, copy_threads);
+                    HIP_TRY(hipMemcpyAsync(din + (size_t)k * in_img, st, in_row * b.in_rows, hipMemcpyHostToDevice, p.s_h2d));
+                }
             }
+            HIP_TRY(hipEventRecord(p.ev_in_slot[is], p.s_h2d));
+            HIP_TRY(hipEventRecord(p.ev_input, p.s_h2d));
+            // ---- the launches, behind the upload and behind the download of sub-batch j - 2 out of the same output slot ----
+            HIP_TRY(hipStreamWaitEvent(p.s_compute, p.ev_input, 0));
+            if (j >= 2) HIP_TRY(hipStreamWaitEvent(p.s_compute, p.ev_batch[2 + slot], 0));
+            rc = b.run(dev, cnt, din, dout, p.s_compute, sub);
+            if (rc) return rc;
+            HIP_TRY(hipEventRecord(p.ev_batch[slot], p.s_compute));
+            // ---- download: page-locked images in place, the others into pinned slot j % OUT_SLOTS (stitched below, one sub-batch later) ----
+            HIP_TRY(hipStreamWaitEvent(p.s_d2h, p.ev_batch[slot], 0));
+            const int os = j % HostPipe::OUT_SLOTS;
+            for (int k = 0; k < cnt; k++) {
+                const int i = first + k;
+                if (out_pin[i]) HIP_TRY(hipMemcpy2DAsync(b.out[i], b.out_stride, dout + (size_t)k * out_img, out_row, out_row, b.out_rows, hipMemcpyDeviceToHost, p.s_d2h));
+                else HIP_TRY(hipMemcpyAsync(p.pin_out.as<char>() + (size_t)os * p.out_slot_bytes() + (size_t)k * out_img, dout + (size_t)k * out_img, out_row * b.out_rows,
+                                            hipMemcpyDeviceToHost, p.s_d2h));
+            }
+            HIP_TRY(hipEventRecord(p.ev_out_slot[os], p.s_d2h));
+            HIP_TRY(hipEventRecord(p.ev_batch[2 + slot], p.s_d2h));
+            if (j >= 1 && any_out_pageable) { rc = stitch(j - 1); if (rc) return rc; }   // (the previous sub-batch, while this one computes)
         }
-        HIP_TRY(hipEventRecord(p.ev_in_slot[is], p.s_h2d));
-        HIP_TRY(hipEventRecord(p.ev_input, p.s_h2d));
-        // ---- the launches, behind the upload and behind the download of sub-batch j - 2 out of the same output slot ----
-        HIP_TRY(hipStreamWaitEvent(p.s_compute, p.ev_input, 0));
-        if (j >= 2) HIP_TRY(hipStreamWaitEvent(p.s_compute, p.ev_batch[2 + slot], 0));
-        rc = b.run(dev, cnt, din, dout, p.s_compute, sub);
-        if (rc) return rc;
-        HIP_TRY(hipEventRecord(p.ev_batch[slot], p.s_compute));
-        // ---- download: page-locked images in place, the others into pinned slot j % OUT_SLOTS (stitched below, one sub-batch later) ----
-        HIP_TRY(hipStreamWaitEvent(p.s_d2h, p.ev_batch[slot], 0));
-        const int os = j % HostPipe::OUT_SLOTS;
-        for (int k = 0; k < cnt; k++) {
-            const int i = first + k;
-            if (out_pin[i]) HIP_TRY(hipMemcpy2DAsync(b.out[i], b.out_stride, dout + (size_t)k * out_img, out_row, out_row, b.out_rows, hipMemcpyDeviceToHost, p.s_d2h));
-            else HIP_TRY(hipMemcpyAsync(p.pin_out.as<char>() + (size_t)os * p.out_slot_bytes() + (size_t)k * out_img, dout + (size_t)k * out_img, out_row * b.out_rows,
-                                        hipMemcpyDeviceToHost, p.s_d2h));
-        }
-        HIP_TRY(hipEventRecord(p.ev_out_slot[os], p.s_d2h));
-        HIP_TRY(hipEventRecord(p.ev_batch[2 + slot], p.s_d2h));
-        if (j >= 1 && any_out_pageable) { rc = stitch(j - 1); if (rc) return rc; }   // (the previous sub-batch, while this one computes)
+        if (any_out_pageable) { rc = stitch((int)subs.size() - 1); if (rc) return rc; }
+        HIP_TRY(hipStreamSynchronize(p.s_compute));
+        HIP_TRY(hipStreamSynchronize(p.s_d2h));
+        return W2XC_OK;
+    }();
+    if (rc) {
+        // A sub-batch failed with earlier ones still on the streams: uploads out of the caller's page-locked images and the pinned ring, launches on
+        // the device slots, downloads into page-locked outputs.  The caller may free its images and the next call reuses slots and rings on return:
+        // wait for all three streams, as host_rows_on_device does (the message is the failure's, not the wait's).
+        const std::string err = g_last_error;
+        for (hipStream_t s : {p.s_h2d, p.s_compute, p.s_d2h}) (void)hipStreamSynchronize(s);
+        g_last_error = err;
     }
-    if (any_out_pageable) { rc = stitch((int)subs.size() - 1); if (rc) return rc; }
-    HIP_TRY(hipStreamSynchronize(p.s_compute));
-    HIP_TRY(hipStreamSynchronize(p.s_d2h));
-    return W2XC_OK;
+    return rc;
 }
 
 // the devices a host-pointer call runs on: those of w2xc_opts.device_mask that exist

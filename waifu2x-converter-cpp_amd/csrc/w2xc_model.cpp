@@ -68,10 +68,39 @@ w2xc_opts resolve_opts(const w2xc_opts *o)
     return r;
 }
 
+// ---- the failure seam (w2xc_debug_fail_nth): process-wide, three kinds of event ----
+std::atomic<unsigned> g_fail_watch{0};
+static std::atomic<long long> g_fail_seen[4], g_fail_armed[4];   // events since the last call of the entry point / events left until one fails (0: none)
+
+bool fail_event_watched(int kind)
+{
+    if (!((g_fail_watch.load(std::memory_order_relaxed) >> kind) & 1u)) return false;
+    g_fail_seen[kind].fetch_add(1, std::memory_order_relaxed);
+    long long left = g_fail_armed[kind].load(std::memory_order_relaxed);
+    while (left > 0)   // (events of several threads: exactly one of them takes the count from 1 to 0)
+        if (g_fail_armed[kind].compare_exchange_weak(left, left - 1, std::memory_order_relaxed)) return left == 1;
+    return false;
+}
+
+// A weight image: *d = a device copy of h, or -- on any failure -- null with nothing allocated (a lazily packed image is tested by its pointer: `packed`,
+// w2xc_rows.cpp).  A failed allocation is W2XC_ERR_NOMEM like every other one, a failed copy W2XC_ERR_HIP.
 int upload(const std::vector<float> &h, float **d)
 {
-    HIP_TRY(hipMalloc((void **)d, std::max<size_t>(h.size(), 1) * sizeof(float)));
-    HIP_TRY(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    *d = nullptr;
+    const size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(float);
+    hipError_t e = fail_event(W2XC_DEBUG_FAIL_ALLOC) ? hipErrorOutOfMemory : hipMalloc((void **)d, bytes);
+    if (e != hipSuccess) {
+        *d = nullptr;
+        (void)hipGetLastError();
+        return fail(W2XC_ERR_NOMEM, "allocating %zu bytes of device memory for a weight image failed: %s", bytes, hipGetErrorString(e));
+    }
+    e = fail_event(W2XC_DEBUG_FAIL_COPY) ? hipErrorUnknown : hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(*d);
+        *d = nullptr;
+        (void)hipGetLastError();
+        return fail(W2XC_ERR_HIP, "hipMemcpy of a weight image (%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+    }
     return W2XC_OK;
 }
 
@@ -157,7 +186,11 @@ int prof_begin(DevCtx *c, int layer, hipStream_t st, ProfEvent *ev)
         }
     }
     ev->layer = layer;
-    HIP_TRY(hipEventRecord(ev->a, st));
+    const hipError_t e = hipEventRecord(ev->a, st);
+    if (e != hipSuccess) {
+        c->pool.push_back(*ev);   // (the pair stays the context's)
+        return fail(W2XC_ERR_HIP, "hipEventRecord failed: %s", hipGetErrorString(e));
+    }
     return W2XC_OK;
 }
 
@@ -228,6 +261,7 @@ const char *w2xc_last_error(void) { return g_last_error.c_str(); }
 // W2XC_MATRIX_* (additive; w2xc_opts stays 56 bytes; the string stays, the revision is found by the presence of the symbols).
 // 0.4.1.9: 16-bit YUV frames -- w2xc_process_frames_yuv_u16[_rgb][_device], w2xc_y16_to_plane_device, w2xc_plane_to_y16_device, w2xc_chroma2x_u16_device,
 // w2xc_yuv16_to_rgb_device, w2xc_rgb_to_yuv16_device, the struct w2xc_yuv16_planes and W2XC_PACK_* (additive; w2xc_opts stays 56 bytes; the string stays).
+// 0.4.1.12: w2xc_debug_fail_nth and W2XC_DEBUG_FAIL_* (test aid, additive; w2xc_opts stays 56 bytes; the string stays, the revision is found by the symbol).
 const char *w2xc_version(void) { return "w2xc_hip 0.4.1.6.1 (gfx950)"; }
 
 int w2xc_plan_rows(const w2xc_model *m, int w, int view_y0, int view_h, int plane_h, int row_begin, int row_end, const w2xc_opts *opts, w2xc_row_plan *plan)
@@ -602,6 +636,15 @@ int w2xc_debug_fill_scratch(w2xc_model *m, int device, unsigned word, unsigned l
     c->fc.res_valid = false;   // the resident copy w2xc_opts.filter_resident promises is gone
     *bytes = total;
     return W2XC_OK;
+}
+
+// Test aid (tests/test_gpu_fail_paths.py): see include/w2xc_hip.h.  The sites: Scratch::reserve and upload (ALLOC), upload (COPY), launch_layer (LAUNCH).
+long long w2xc_debug_fail_nth(int kind, long long nth)
+{
+    if (kind < W2XC_DEBUG_FAIL_ALLOC || kind > W2XC_DEBUG_FAIL_LAUNCH || nth < 0) return -1;
+    g_fail_watch.fetch_or(1u << kind, std::memory_order_relaxed);
+    g_fail_armed[kind].store(nth, std::memory_order_relaxed);
+    return g_fail_seen[kind].exchange(0, std::memory_order_relaxed);
 }
 
 const char *w2xc_layer_kernel_name(const w2xc_model *m, int layer, const w2xc_opts *opts)

@@ -118,12 +118,12 @@ int launch_layer(DevCtx *c, const w2xc_model *m, int l, W2xcKernelKind kind, int
     ProfEvent ev;
     const bool profile = o.profile != 0;
     if (profile) { rc = prof_begin(c, l, st, &ev); if (rc) return rc; }
-    hipError_t e = launch_kind(kind, midv, d, bd, st);
+    // (the seam of w2xc_debug_fail_nth: nothing is launched, an error code stands where the launcher's would)
+    hipError_t e = fail_event(W2XC_DEBUG_FAIL_LAUNCH) ? hipErrorLaunchFailure : launch_kind(kind, midv, d, bd, st);
+    if (e == hipSuccess && profile) e = hipEventRecord(ev.b, st);
+    if (e != hipSuccess && profile) c->pool.push_back(ev);   // the pair of a launch that did not happen measures nothing: back to the pool, not to `pending`
     if (e != hipSuccess) return fail(W2XC_ERR_HIP, "launch of %s (layer %d, %d->%d) failed: %s", w2xc_kernel_name(kind, d.cin, d.cout), l, d.cin, d.cout, hipGetErrorString(e));
-    if (profile) {
-        HIP_TRY(hipEventRecord(ev.b, st));
-        c->pending.push_back(ev);
-    }
+    if (profile) c->pending.push_back(ev);
     return W2XC_OK;
 }
 

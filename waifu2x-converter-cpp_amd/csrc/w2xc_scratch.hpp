@@ -6,12 +6,20 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstddef>
 #include <cstring>
 
 namespace w2xc_eng {
 
 int fail(int code, const char *fmt, ...);
+
+// The failure seam of w2xc_debug_fail_nth (test aid; state and slow path in w2xc_model.cpp): true = this event of `kind` (W2XC_DEBUG_FAIL_*) is the one
+// armed to fail -- the caller then puts an error code where the runtime call would have been.  Until the entry point has been called once in the
+// process this is one relaxed load of a word that is zero.
+extern std::atomic<unsigned> g_fail_watch;   // bit k: events of kind k are counted
+bool fail_event_watched(int kind);
+inline bool fail_event(int kind) { return g_fail_watch.load(std::memory_order_relaxed) != 0 && fail_event_watched(kind); }
 
 // what a buffer holds: DATA is filled by w2xc_debug_fill_scratch; SYNC words (job flags, job counters) never are -- a wrong value there could only make a
 // launch wait for ever
@@ -41,7 +49,10 @@ public:
         if (bytes_ >= bytes) return W2XC_OK;
         if (p_ && hipDeviceSynchronize() != hipSuccess) return fail(W2XC_ERR_HIP, "hipDeviceSynchronize failed before %s could grow", what);
         release();
-        const hipError_t e = kind_ == DEVICE ? hipMalloc(&p_, bytes) : hipHostMalloc(&p_, bytes, kind_ == PINNED ? hipHostMallocDefault : hipHostMallocCoherent);
+        // (the seam stands where a real failure lands: behind the drain and the release, in place of the runtime call)
+        const hipError_t e = fail_event(W2XC_DEBUG_FAIL_ALLOC) ? hipErrorOutOfMemory
+                             : kind_ == DEVICE             ? hipMalloc(&p_, bytes)
+                                                           : hipHostMalloc(&p_, bytes, kind_ == PINNED ? hipHostMallocDefault : hipHostMallocCoherent);
         if (e != hipSuccess) {
             p_ = nullptr;
             (void)hipGetLastError();
